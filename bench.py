@@ -1,15 +1,21 @@
 #!/usr/bin/env python3
 """bench.py -- GSM updates/sec + achieved HBM GB/s at D=1024, B=32 (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A "step" is one GSM update -- gsm_update(samples, vs, mu0, S0) -> (mu, S), reference
 gsmvi/gsm_numpy.py:27-55 -- at configs[2] of BASELINE.json (D=1024, B=32, dense covariance,
 synthetic Gaussian target, fp64), inputs resident in HBM before the timed region.  To keep the
 Infinity Cache (256 MiB) from serving the covariance, the steps cycle over a ring of independent
-problem instances whose footprint exceeds it; the cache-resident rate (one instance, what a real
-fit loop sees) is reported beside it as "value_cache_resident".
+problem instances whose footprint exceeds it; with --full the cache-resident rate (one instance,
+what a real fit loop sees) is reported beside it as "value_cache_resident".
+
+A plain run sets up, warms up, times K steps and prints the headline.  --full adds the secondary
+figures (per-step device-time statistics, roofline and calibration, the D=4096 point, fit-iteration
+and call-path rates, CPU baseline); the --no-* switches below trim that set.  --dump-outputs DIR
+writes the last timed step's (mu, S) as DIR/mu.npy, DIR/S.npy (float64); the inputs are seeded, so
+two builds can be compared output for output.
 
 N > 1: the batch is sharded across ranks (B/N samples each), records are all-gathered over RCCL
 and every replica applies the combined update (gsm-vi_amd/dist.py); total work is fixed ->
@@ -29,9 +35,10 @@ import torch  # noqa: E402
 import torch.distributed as dist  # noqa: E402
 
 HBM_PEAK_GBS = 8000.0      # MI355X HBM3E spec peak (guide: MI355X_MICROARCH.md, chip-level parameters)
+DUMP_LIMIT_BYTES = 64 * 2 ** 20     # --dump-outputs: all files together
 
 
-def parse():
+def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=4000)
@@ -52,7 +59,14 @@ def parse():
     ap.add_argument("--shard", choices=("batch", "rows"), default="batch",
                     help="N>1 decomposition: batch (north_star; records all-gathered) or covariance row blocks "
                          "(SURVEY 8(f)3; SG column slices all-gathered, D^2 passes divided by N)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also measure every secondary figure: per-step device-time statistics, cache-resident rate, "
+                         "roofline and HBM calibration, the D=4096 point, fit-iteration and call-path rates, CPU baseline. "
+                         "Without it a run times the headline steps only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the outputs of the last timed step (mu, S; float64) as DIR/<name>.npy, "
+                         f"at most {DUMP_LIMIT_BYTES >> 20} MB in all (a seeded sample of rows beyond that)")
+    return ap.parse_args(argv)
 
 
 def make_instances(eng, D, B, n_inst, seed0=0, ldpad=0):
@@ -86,6 +100,26 @@ def make_instances(eng, D, B, n_inst, seed0=0, ldpad=0):
         inst.append(dict(X=X.contiguous(), G=G, mu0=mu0, S0=S0p, mu=eng.empty(D), S=Sout))
     torch.cuda.synchronize()
     return inst, m, P
+
+
+def dump_outputs(dirname, arrays, limit=DUMP_LIMIT_BYTES):
+    """--dump-outputs: every (name, tensor) as float64 DIR/<name>.npy.  A matrix that would take the total past `limit` is
+    written as a fixed, seeded sample of its rows instead (<name>_sample.npy, the row indices in <name>_sample_rows.npy), so
+    that two runs with the same arguments write the same files."""
+    os.makedirs(dirname, exist_ok=True)
+    used = 0
+    for name, t in arrays:
+        a = np.ascontiguousarray(t.detach().cpu().numpy(), dtype=np.float64)
+        if used + a.nbytes > limit and a.ndim == 2:
+            n = min(a.shape[0], (limit - used) // (a[0].nbytes + 8))          # each row and its index
+            rows = np.sort(np.random.default_rng(0).choice(a.shape[0], size=max(n, 0), replace=False))
+            np.save(os.path.join(dirname, f"{name}_sample_rows.npy"), rows.astype(np.float64))
+            used += rows.nbytes
+            a, name = a[rows], f"{name}_sample"
+        if used + a.nbytes > limit or a.size == 0:
+            raise ValueError(f"--dump-outputs: {name} does not fit in {limit} bytes")
+        np.save(os.path.join(dirname, f"{name}.npy"), a)
+        used += a.nbytes
 
 
 def cpu_baseline(D, B, seconds):
@@ -479,9 +513,14 @@ def main():
         el = float(t.item())
     ms_per_step = el / args.steps * 1e3
     value = args.steps / el
+    # what the last timed step computed, before anything else writes to the instances (every step writes its own ring
+    # position's outputs from fixed inputs, so the last step's position holds exactly that step's result)
+    if args.dump_outputs and rank == 0:
+        last = inst[(args.steps - 1) % n_inst]
+        dump_outputs(args.dump_outputs, [("mu", last["mu"]), ("S_row_block", last["Sr"]) if rows else ("S", last["S"])])
     # statistics of the per-step device time need more than the one or two replays a small --steps gives: top the sample up
     # to >= 30 full replays OUTSIDE the timed region (`value`, `ms_per_step` and `steps` keep their contract meaning)
-    if graph is not None and len(replay_ev) < 30:
+    if args.full and graph is not None and len(replay_ev) < 30:
         for _ in range(30 - len(replay_ev)):
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record()
@@ -489,7 +528,7 @@ def main():
             e1.record()
             replay_ev.append((e0, e1))
         torch.cuda.synchronize()
-    per_replay_us = sorted(e0.elapsed_time(e1) * 1e3 / gsize for e0, e1 in replay_ev) if replay_ev else []
+    per_replay_us = sorted(e0.elapsed_time(e1) * 1e3 / gsize for e0, e1 in replay_ev) if args.full and replay_ev else []
     step_us_stats = ({"median": per_replay_us[len(per_replay_us) // 2], "min": per_replay_us[0], "max": per_replay_us[-1],
                       "replays": len(per_replay_us), "replays_inside_timed_region": n_full if graph is not None else 0,
                       "note": "device time of each full graph replay / updates per replay (torch events on the replay "
@@ -560,7 +599,7 @@ def main():
 
     # ---- cache-resident rate: one instance, what a fit loop with a single covariance sees ------
     value_hot = None
-    if not use_dist:
+    if args.full and not use_dist:
         it = inst[0]
         g1 = None
         try:
@@ -585,170 +624,172 @@ def main():
         torch.cuda.synchronize()
         value_hot = reps * n_inst / (time.perf_counter() - th)
 
-    # ---- roofline of the dominant kernel (covariance update), dispatch-timestamp events --------
-    # Each sample is the LAST of four back-to-back updates on consecutive (HBM-cold) instances: the durations are the kernels'
-    # durations with the device busy, as in the timed region.  (Round 5: a sample per update timed from an idle device --
-    # launch, read the events, launch -- read 10.8 us for the 6.3 us covariance kernel on one box of the pool, whose clocks
-    # drop between the synchronisations, while the replayed region and rocprofv3 of the same run were unchanged.)
-    eng.set_profiling(True)
-    kt = {"panel": [], "scalars": [], "cov_update": []}
-    for k in range(2 * n_inst):
-        for q in range(4):
-            it = inst[(4 * k + q) % n_inst]
-            eng.gsm_update(it["X"], it["G"], it["mu0"], it["S0"], out=(it["mu"], it["S"]))
-        pr = eng.get_profile()
-        if k >= n_inst // 2:
-            for key in kt:
-                kt[key].append(pr[key])
-    eng.set_profiling(False)
-    avg_ms = {k: float(np.mean(v)) for k, v in kt.items()}
-    alg_bytes_update = 16.0 * D * D + 16.0 * B * D                     # pass B
-    alg_bytes_total = 24.0 * D * D + 72.0 * B * D                      # whole update
-    achieved = alg_bytes_update / (avg_ms["cov_update"] * 1e-3) / 1e9
-    traffic, mfma_util = None, None
-    tpath = os.path.join(ROOT, "profiles", "traffic.json")
-    if os.path.exists(tpath):
-        try:
-            tj = json.load(open(tpath))
-            traffic = tj.get("k_gsm_cov_update_bytes_per_launch")
-            mfma_util = next((v.get("util") for k, v in (tj.get("mfma_util") or {}).items() if "k_gsm_cov_sym" in k), None)
-        except Exception:
-            traffic = None
-    # (round-5 verdict, item 8) the same kernel's average under `rocprofv3 --kernel-trace --stats` of this command, read from the
-    # TRACKED summary of the latest published pass (profiles/rNN/kernel_stats.csv, scripts/collect_profiles.sh at the headline
-    # shape): `frac` is computed from it so that the line's figure follows from what profiles/ holds; the live dispatch events
-    # stay beside it.  Another shape than the profiled one: events only.
-    rocprof_us, rocprof_src = None, None
-    if (D, B) == (1024, 32):
-        import csv as _csv
-        import glob as _glob
-        for ks in sorted(_glob.glob(os.path.join(ROOT, "profiles", "r[0-9][0-9]", "kernel_stats.csv")), reverse=True):
+    roofline = None
+    if args.full:
+        # ---- roofline of the dominant kernel (covariance update), dispatch-timestamp events --------
+        # Each sample is the LAST of four back-to-back updates on consecutive (HBM-cold) instances: the durations are the kernels'
+        # durations with the device busy, as in the timed region.  (Round 5: a sample per update timed from an idle device --
+        # launch, read the events, launch -- read 10.8 us for the 6.3 us covariance kernel on one MI355X, whose clocks
+        # drop between the synchronisations, while the replayed region and rocprofv3 of the same run were unchanged.)
+        eng.set_profiling(True)
+        kt = {"panel": [], "scalars": [], "cov_update": []}
+        for k in range(2 * n_inst):
+            for q in range(4):
+                it = inst[(4 * k + q) % n_inst]
+                eng.gsm_update(it["X"], it["G"], it["mu0"], it["S0"], out=(it["mu"], it["S"]))
+            pr = eng.get_profile()
+            if k >= n_inst // 2:
+                for key in kt:
+                    kt[key].append(pr[key])
+        eng.set_profiling(False)
+        avg_ms = {k: float(np.mean(v)) for k, v in kt.items()}
+        alg_bytes_update = 16.0 * D * D + 16.0 * B * D                     # pass B
+        alg_bytes_total = 24.0 * D * D + 72.0 * B * D                      # whole update
+        achieved = alg_bytes_update / (avg_ms["cov_update"] * 1e-3) / 1e9
+        traffic, mfma_util = None, None
+        tpath = os.path.join(ROOT, "profiles", "traffic.json")
+        if os.path.exists(tpath):
             try:
-                rows = [r for r in _csv.DictReader(open(ks)) if "k_gsm_cov_sym<" in r["Name"]]
-                if rows:
-                    r = max(rows, key=lambda r_: int(r_["Calls"]))
-                    rocprof_us, rocprof_src = float(r["AverageNs"]) / 1e3, os.path.relpath(ks, ROOT)
-                    rocprof_calls, rocprof_min = int(r["Calls"]), float(r["MinNs"]) / 1e3
-                    break
+                tj = json.load(open(tpath))
+                traffic = tj.get("k_gsm_cov_update_bytes_per_launch")
+                mfma_util = next((v.get("util") for k, v in (tj.get("mfma_util") or {}).items() if "k_gsm_cov_sym" in k), None)
             except Exception:
-                continue
-    sym = D % 2 == 0
-    # bytes the selected kernel really moves: the symmetric kernel reads only the upper triangle of S0
-    # (4 D^2 + the diagonal tiles) and writes all of S (8 D^2); the generic one reads and writes 8 D^2 each
-    nt32 = (D + 31) // 32
-    moved = ((nt32 * (nt32 + 1) // 2) * 32 * 32 * 8.0 + 8.0 * D * D + 16.0 * B * D) if sym else alg_bytes_update
-    roofline = {"bound": "hbm", "kernel": "k_gsm_cov_sym" if sym else "k_gsm_cov_update",
-                "achieved": achieved if rocprof_us is None else alg_bytes_update / (rocprof_us * 1e-6) / 1e9, "peak": HBM_PEAK_GBS,
-                "unit": "GB/s",
-                "frac": (achieved if rocprof_us is None else alg_bytes_update / (rocprof_us * 1e-6) / 1e9) / HBM_PEAK_GBS,
-                "frac_basis": "events (live dispatch events; no published rocprofv3 summary for this shape)" if rocprof_us is None
-                else f"rocprofv3 average of {rocprof_src} ({rocprof_calls} launches, min {rocprof_min:.2f} us)",
-                "avg_kernel_us_events": avg_ms["cov_update"] * 1e3, "avg_kernel_us_rocprof": rocprof_us,
-                "achieved_events": achieved, "frac_events": achieved / HBM_PEAK_GBS, "traffic": traffic,
-                "traffic_source": "profiles/traffic.json (rocprofv3 PMC pass of an earlier run of this command; "
-                                  "not a live counter)",
-                "algorithmic_bytes_per_launch": alg_bytes_update,
-                "moved_bytes_per_launch": moved, "achieved_moved": moved / (avg_ms["cov_update"] * 1e-3) / 1e9,
-                "frac_moved": moved / (avg_ms["cov_update"] * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                "avg_kernel_us": {k: v * 1e3 for k, v in avg_ms.items()},
-                "whole_update_algorithmic_GBs": alg_bytes_total * value / 1e9,
-                "whole_update_frac": alg_bytes_total * value / 1e9 / HBM_PEAK_GBS,   # all launches of one update
-                "whole_update_frac_cache_resident": (alg_bytes_total * value_hot / 1e9 / HBM_PEAK_GBS)
-                if value_hot else None,
-                "mfma_pipe_util_profiled": mfma_util}     # SQ_VALU_MFMA_BUSY_CYCLES pass, profiles/traffic.json
-    # ---- calibration: the attainable HBM rate on this box (device copy of 1 GiB, read + write
-    # bytes) and what a plain copy of one covariance costs in the same cold ring (it moves 16 D^2 bytes, the
-    # covariance kernel's algorithmic count) -- torch's copy kernel, plumbing, not the product path.
-    if rank == 0:
-        try:
-            # the yardstick is this library's OWN streaming copy (16 B per lane, non-temporal: gsmvi_debug_stream_copy_f64 of the
-            # debug build -- calibration, not the product path; until round 3 torch's copy_ kernel stood here and read 5.0 TB/s
-            # where MI355X_MICROARCH.md's float4 copy reaches 6.29); torch's figure is kept beside it
-            import ctypes as _C
-            from gsmvi_amd import _lib as _gl
-            dbg = _C.CDLL(_gl.library_path(debug=True))
-            dbg.gsmvi_debug_stream_copy_f64.restype = _C.c_int
-            dbg.gsmvi_debug_stream_copy_f64.argtypes = [_C.c_void_p, _C.c_void_p, _C.c_void_p, _C.c_size_t]
-            big = torch.empty(2, 2 ** 27, dtype=torch.float64, device=eng.device)
-            big[0].fill_(1.0)
-            st_ = _C.c_void_p(torch.cuda.current_stream().cuda_stream)
+                traffic = None
+        # (round-5 verdict, item 8) the same kernel's average under `rocprofv3 --kernel-trace --stats` of this command, read from the
+        # TRACKED summary of the latest published pass (profiles/rNN/kernel_stats.csv, scripts/collect_profiles.sh at the headline
+        # shape): `frac` is computed from it so that the line's figure follows from what profiles/ holds; the live dispatch events
+        # stay beside it.  Another shape than the profiled one: events only.
+        rocprof_us, rocprof_src = None, None
+        if (D, B) == (1024, 32):
+            import csv as _csv
+            import glob as _glob
+            for ks in sorted(_glob.glob(os.path.join(ROOT, "profiles", "r[0-9][0-9]", "kernel_stats.csv")), reverse=True):
+                try:
+                    rows = [r for r in _csv.DictReader(open(ks)) if "k_gsm_cov_sym<" in r["Name"]]
+                    if rows:
+                        r = max(rows, key=lambda r_: int(r_["Calls"]))
+                        rocprof_us, rocprof_src = float(r["AverageNs"]) / 1e3, os.path.relpath(ks, ROOT)
+                        rocprof_calls, rocprof_min = int(r["Calls"]), float(r["MinNs"]) / 1e3
+                        break
+                except Exception:
+                    continue
+        sym = D % 2 == 0
+        # bytes the selected kernel really moves: the symmetric kernel reads only the upper triangle of S0
+        # (4 D^2 + the diagonal tiles) and writes all of S (8 D^2); the generic one reads and writes 8 D^2 each
+        nt32 = (D + 31) // 32
+        moved = ((nt32 * (nt32 + 1) // 2) * 32 * 32 * 8.0 + 8.0 * D * D + 16.0 * B * D) if sym else alg_bytes_update
+        roofline = {"bound": "hbm", "kernel": "k_gsm_cov_sym" if sym else "k_gsm_cov_update",
+                    "achieved": achieved if rocprof_us is None else alg_bytes_update / (rocprof_us * 1e-6) / 1e9, "peak": HBM_PEAK_GBS,
+                    "unit": "GB/s",
+                    "frac": (achieved if rocprof_us is None else alg_bytes_update / (rocprof_us * 1e-6) / 1e9) / HBM_PEAK_GBS,
+                    "frac_basis": "events (live dispatch events; no published rocprofv3 summary for this shape)" if rocprof_us is None
+                    else f"rocprofv3 average of {rocprof_src} ({rocprof_calls} launches, min {rocprof_min:.2f} us)",
+                    "avg_kernel_us_events": avg_ms["cov_update"] * 1e3, "avg_kernel_us_rocprof": rocprof_us,
+                    "achieved_events": achieved, "frac_events": achieved / HBM_PEAK_GBS, "traffic": traffic,
+                    "traffic_source": "profiles/traffic.json (rocprofv3 PMC pass of an earlier run of this command; "
+                                      "not a live counter)",
+                    "algorithmic_bytes_per_launch": alg_bytes_update,
+                    "moved_bytes_per_launch": moved, "achieved_moved": moved / (avg_ms["cov_update"] * 1e-3) / 1e9,
+                    "frac_moved": moved / (avg_ms["cov_update"] * 1e-3) / 1e9 / HBM_PEAK_GBS,
+                    "avg_kernel_us": {k: v * 1e3 for k, v in avg_ms.items()},
+                    "whole_update_algorithmic_GBs": alg_bytes_total * value / 1e9,
+                    "whole_update_frac": alg_bytes_total * value / 1e9 / HBM_PEAK_GBS,   # all launches of one update
+                    "whole_update_frac_cache_resident": (alg_bytes_total * value_hot / 1e9 / HBM_PEAK_GBS)
+                    if value_hot else None,
+                    "mfma_pipe_util_profiled": mfma_util}     # SQ_VALU_MFMA_BUSY_CYCLES pass, profiles/traffic.json
+        # ---- calibration: the attainable HBM rate on this device (device copy of 1 GiB, read + write
+        # bytes) and what a plain copy of one covariance costs in the same cold ring (it moves 16 D^2 bytes, the
+        # covariance kernel's algorithmic count) -- torch's copy kernel, plumbing, not the product path.
+        if rank == 0:
+            try:
+                # the yardstick is this library's OWN streaming copy (16 B per lane, non-temporal: gsmvi_debug_stream_copy_f64 of the
+                # debug build -- calibration, not the product path; until round 3 torch's copy_ kernel stood here and read 5.0 TB/s
+                # where MI355X_MICROARCH.md's float4 copy reaches 6.29); torch's figure is kept beside it
+                import ctypes as _C
+                from gsmvi_amd import _lib as _gl
+                dbg = _C.CDLL(_gl.library_path(debug=True))
+                dbg.gsmvi_debug_stream_copy_f64.restype = _C.c_int
+                dbg.gsmvi_debug_stream_copy_f64.argtypes = [_C.c_void_p, _C.c_void_p, _C.c_void_p, _C.c_size_t]
+                big = torch.empty(2, 2 ** 27, dtype=torch.float64, device=eng.device)
+                big[0].fill_(1.0)
+                st_ = _C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
-            def own_copy():
-                rc_ = dbg.gsmvi_debug_stream_copy_f64(st_, _C.c_void_p(big[1].data_ptr()), _C.c_void_p(big[0].data_ptr()),
-                                                      big[0].numel())
-                assert rc_ == 0
+                def own_copy():
+                    rc_ = dbg.gsmvi_debug_stream_copy_f64(st_, _C.c_void_p(big[1].data_ptr()), _C.c_void_p(big[0].data_ptr()),
+                                                          big[0].numel())
+                    assert rc_ == 0
 
-            rates = {}
-            for name, fn in (("own", own_copy), ("torch", lambda: big[1].copy_(big[0]))):
-                for _ in range(2):
-                    fn()
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
-                for _ in range(5):
-                    fn()
-                e1.record()
-                e1.synchronize()
-                rates[name] = 5 * 2.0 * big[0].numel() * 8 / (e0.elapsed_time(e1) * 1e-3) / 1e9
-            assert torch.equal(big[1], big[0])
-            attain = max(rates.values())
-            roofline["attainable_peak_by_kernel"] = rates
-            del big
-            gcp = torch.cuda.CUDAGraph()
-            for it in inst:
-                it["S"].copy_(it["S0"])
-            torch.cuda.synchronize()
-            with torch.cuda.graph(gcp):
+                rates = {}
+                for name, fn in (("own", own_copy), ("torch", lambda: big[1].copy_(big[0]))):
+                    for _ in range(2):
+                        fn()
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record()
+                    for _ in range(5):
+                        fn()
+                    e1.record()
+                    e1.synchronize()
+                    rates[name] = 5 * 2.0 * big[0].numel() * 8 / (e0.elapsed_time(e1) * 1e-3) / 1e9
+                assert torch.equal(big[1], big[0])
+                attain = max(rates.values())
+                roofline["attainable_peak_by_kernel"] = rates
+                del big
+                gcp = torch.cuda.CUDAGraph()
                 for it in inst:
                     it["S"].copy_(it["S0"])
-            gcp.replay()
-            torch.cuda.synchronize()
-            tc0 = time.perf_counter()
-            for _ in range(20):
+                torch.cuda.synchronize()
+                with torch.cuda.graph(gcp):
+                    for it in inst:
+                        it["S"].copy_(it["S0"])
                 gcp.replay()
-            torch.cuda.synchronize()
-            copy_us = (time.perf_counter() - tc0) / (20 * n_inst) * 1e6
-            roofline["attainable_peak"] = attain
-            # moved bytes against a moved-bytes copy rate (round-4 verdict: the former algorithmic / moved ratio could exceed 1)
-            roofline["frac_of_attainable_moved"] = roofline["achieved_moved"] / attain
-            roofline["plain_copy_same_size_us"] = copy_us
-        except Exception as e:                  # calibration only
-            roofline["attainable_peak"] = f"failed: {type(e).__name__}"
+                torch.cuda.synchronize()
+                tc0 = time.perf_counter()
+                for _ in range(20):
+                    gcp.replay()
+                torch.cuda.synchronize()
+                copy_us = (time.perf_counter() - tc0) / (20 * n_inst) * 1e6
+                roofline["attainable_peak"] = attain
+                # moved bytes against a moved-bytes copy rate (round-4 verdict: the former algorithmic / moved ratio could exceed 1)
+                roofline["frac_of_attainable_moved"] = roofline["achieved_moved"] / attain
+                roofline["plain_copy_same_size_us"] = copy_us
+            except Exception as e:                  # calibration only
+                roofline["attainable_peak"] = f"failed: {type(e).__name__}"
 
-    # ---- the same kernel where it is bandwidth- rather than latency-bound: D=4096, B=32, measured live (two cold
-    # instances, hipExt dispatch events; rocprofv3 evidence: profiles/r02/d4096_b32_kernel_stats.csv) ----
-    if rank == 0 and not use_dist and D == 1024 and not args.no_large_point:
-        try:
-            DL, BL = 4096, 32
-            li, _, _ = make_instances(eng, DL, BL, 3, seed0=7)
-            eng.set_profiling(True)
-            tl = []
-            for kk in range(12):
-                for q in range(3):                   # (the last of three back-to-back updates: device busy, see above)
-                    it = li[(3 * kk + q) % 3]
-                    eng.gsm_update(it["X"], it["G"], it["mu0"], it["S0"], out=(it["mu"], it["S"]))
-                if kk >= 3:
-                    tl.append(eng.get_profile()["cov_update"])
-            eng.set_profiling(False)
-            tms = float(np.mean(tl))
-            bl = 16.0 * DL * DL + 16.0 * BL * DL
-            roofline["large_D_point"] = {"D": DL, "B": BL, "kernel": "k_gsm_cov_sym_p (persistent form of k_gsm_cov_sym)",
-                                         "avg_kernel_us": tms * 1e3,
-                                         "algorithmic_bytes_per_launch": bl, "achieved": bl / (tms * 1e-3) / 1e9,
-                                         "frac": bl / (tms * 1e-3) / 1e9 / HBM_PEAK_GBS}
-            ntl = DL // 32
-            mvl = (ntl * (ntl + 1) // 2) * 32 * 32 * 8.0 + 8.0 * DL * DL + 16.0 * BL * DL      # upper triangle read, all of S written
-            roofline["large_D_point"]["moved_bytes_per_launch"] = mvl
-            roofline["large_D_point"]["achieved_moved"] = mvl / (tms * 1e-3) / 1e9
-            if isinstance(roofline.get("attainable_peak"), float):
-                roofline["large_D_point"]["frac_of_attainable_moved"] = mvl / (tms * 1e-3) / 1e9 / roofline["attainable_peak"]
-            del li
-            torch.cuda.empty_cache()
-        except Exception as e:                  # secondary figure only
-            roofline["large_D_point"] = f"failed: {type(e).__name__}: {e}"
+        # ---- the same kernel where it is bandwidth- rather than latency-bound: D=4096, B=32, measured live (two cold
+        # instances, hipExt dispatch events; rocprofv3 evidence: profiles/r02/d4096_b32_kernel_stats.csv) ----
+        if rank == 0 and not use_dist and D == 1024 and not args.no_large_point:
+            try:
+                DL, BL = 4096, 32
+                li, _, _ = make_instances(eng, DL, BL, 3, seed0=7)
+                eng.set_profiling(True)
+                tl = []
+                for kk in range(12):
+                    for q in range(3):                   # (the last of three back-to-back updates: device busy, see above)
+                        it = li[(3 * kk + q) % 3]
+                        eng.gsm_update(it["X"], it["G"], it["mu0"], it["S0"], out=(it["mu"], it["S"]))
+                    if kk >= 3:
+                        tl.append(eng.get_profile()["cov_update"])
+                eng.set_profiling(False)
+                tms = float(np.mean(tl))
+                bl = 16.0 * DL * DL + 16.0 * BL * DL
+                roofline["large_D_point"] = {"D": DL, "B": BL, "kernel": "k_gsm_cov_sym_p (persistent form of k_gsm_cov_sym)",
+                                             "avg_kernel_us": tms * 1e3,
+                                             "algorithmic_bytes_per_launch": bl, "achieved": bl / (tms * 1e-3) / 1e9,
+                                             "frac": bl / (tms * 1e-3) / 1e9 / HBM_PEAK_GBS}
+                ntl = DL // 32
+                mvl = (ntl * (ntl + 1) // 2) * 32 * 32 * 8.0 + 8.0 * DL * DL + 16.0 * BL * DL      # upper triangle read, all of S written
+                roofline["large_D_point"]["moved_bytes_per_launch"] = mvl
+                roofline["large_D_point"]["achieved_moved"] = mvl / (tms * 1e-3) / 1e9
+                if isinstance(roofline.get("attainable_peak"), float):
+                    roofline["large_D_point"]["frac_of_attainable_moved"] = mvl / (tms * 1e-3) / 1e9 / roofline["attainable_peak"]
+                del li
+                torch.cuda.empty_cache()
+            except Exception as e:                  # secondary figure only
+                roofline["large_D_point"] = f"failed: {type(e).__name__}: {e}"
 
     # ---- fit-iteration rate F: sample -> score -> update -> Cholesky PD check -> commit ----
     fit_rate = None
-    if not use_dist:
+    if args.full and not use_dist:
         fit_rate = {}
         tgt = gsmvi_amd.GaussianTarget(m.cpu().numpy(), precision=P.cpu().numpy())
         for method in ("dense", "factor", "auto"):
@@ -825,12 +866,13 @@ def main():
                       "ring_bytes": n_inst * per_inst, "launch": launch, "warmup_steps_run": warm_done,
                       "parallelism": "single GPU" if not use_dist else
                       (f"covariance row blocks x{world} + RCCL all-gather of SG column slices" if rows else
-                       f"batch-sharded x{world} + RCCL all-gather")},
-           "step_us": step_us_stats, "value_cache_resident": value_hot, "fit_iterations_per_s": fit_rate,
-           "fit_roofline": fit_roofline, "roofline": roofline}
+                       f"batch-sharded x{world} + RCCL all-gather")}}
+    if args.full:
+        out.update({"step_us": step_us_stats, "value_cache_resident": value_hot, "fit_iterations_per_s": fit_rate,
+                    "fit_roofline": fit_roofline, "roofline": roofline})
     if value_in_flight is not None:
         out["value_in_flight"] = value_in_flight
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(D, B, args.cpu_seconds)
     if use_dist:
         dist.destroy_process_group()

@@ -50,7 +50,7 @@ print(json.dumps(box))
 PYBOX
 [ $? -eq 0 ] || { echo "collect_profiles: box identification failed"; exit 3; }
 cd /tmp && export TMPDIR=/tmp
-ARGS="$ROOT/bench.py --steps 420 --warmup 42 --no-cpu-baseline --no-large-point --no-callpath"
+ARGS="$ROOT/bench.py --steps 420 --warmup 42 --full --no-cpu-baseline --no-large-point --no-callpath"
 timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 $ARGS > $OUT/trace.log 2>&1
 # (each counter pass up to three times: the profiler's counter tool segfaulted inside a kernel launch once in ~15 passes of
 # this round -- a pass that leaves no counter file is repeated, its first log kept beside the final one)
@@ -69,7 +69,7 @@ pmc_pass pmc_write WRITE_SIZE
 # fp64 MFMA op count, against the time the GPU was active during the dispatch
 pmc_pass pmc_mfma SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CU_CYCLES SQ_INSTS_VALU_MFMA_MOPS_F64 GRBM_GUI_ACTIVE
 # the >= 0.50 HBM-roofline point of the covariance kernel (D=4096, B=32) and the fit-iteration kernel tables
-timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_d4096 -- python3 $ROOT/bench.py --D 4096 --B 32 --steps 60 --warmup 12 --no-cpu-baseline --no-callpath > $OUT/trace_d4096.log 2>&1
+timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_d4096 -- python3 $ROOT/bench.py --D 4096 --B 32 --steps 60 --warmup 12 --full --no-cpu-baseline --no-callpath > $OUT/trace_d4096.log 2>&1
 for cfg in "1024 32 factor" "1024 32 dense" "4096 64 factor" "256 8 factor" "1024 32 bam" "1024 32 bamf" "1024 128 bam" "1024 128 bamf"; do
   tag=$(echo $cfg | tr ' ' '_')
   timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/fit_$tag -- python3 $ROOT/scripts/factor_prof.py $cfg > $OUT/fit_$tag.log 2>&1
@@ -111,8 +111,8 @@ for d in 1024 4096; do python3 scripts/potrf_dag_timeline.py $d 2>&1 | grep -v a
 python3 scripts/panel_w4_ab.py 2>&1 | grep -v amdgpu.ids > $OUT/panel_w4_ab.txt
 timeout 600 python3 scripts/scaling_model.py $OUT/scaling_model.json > $OUT/scaling_model.log 2>&1
 python3 scripts/soak_round3.py 120 > $OUT/soak.txt 2>&1
-python3 bench.py > $OUT/bench.json 2> $OUT/bench.err
-python3 bench.py --steps 20 --warmup 3 > $OUT/bench_driver_flags.json 2>> $OUT/bench.err
+python3 bench.py --full > $OUT/bench.json 2> $OUT/bench.err
+python3 bench.py --steps 20 --warmup 3 --full > $OUT/bench_driver_flags.json 2>> $OUT/bench.err
 python3 - "$OUT" <<'PY'
 import csv, glob, json, sys, collections
 out = sys.argv[1]
@@ -153,7 +153,7 @@ res["mfma_util"] = {k: v for k, v in mf.items() if v["mfma_busy_cycles_all_simds
 cov, pan, sca = per_launch("k_gsm_cov_sym"), per_launch("k_panel_fast"), per_launch("k_gsm_scalars_fast")
 if cov:
     json.dump({"source": "rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE in separate passes over `bench.py --steps 420 "
-                         "--warmup 42 --no-cpu-baseline --no-graph` (scripts/collect_profiles.sh), D=1024 B=32",
+                         "--warmup 42 --full --no-cpu-baseline --no-graph` (scripts/collect_profiles.sh), D=1024 B=32",
                "units": "counters in KiB; FETCH_SIZE doubled per MI355X_MICROARCH.md (gfx950 reports half of a coalesced "
                         "streaming read); WRITE_SIZE taken as is.  The x2 was calibrated on this box for the 8-B/lane "
                         "128-byte-segment loads of these kernels too (scripts/fetchcal.hip, profiles/r02/fetchcal.txt: "

@@ -60,8 +60,8 @@ def first(pattern):
 
 
 plain = {
-    "bench.json": "python bench.py (default flags), the JSON line",
-    "bench_driver_flags.json": "python bench.py --steps 20 --warmup 3 (the driver's flags)",
+    "bench.json": "python bench.py --full (default flags otherwise), the JSON line",
+    "bench_driver_flags.json": "python bench.py --steps 20 --warmup 3 --full (the driver's flags)",
     "configs.json": "scripts/configs_bench.py: U and F for every BASELINE config that fits one GPU",
     "offgrid_after.json": "scripts/offgrid_bench.py after (this tree)",
     "callpath.json": "scripts/callpath_bench.py: host / autograd score call path at c2 and c3, both fit methods",
@@ -97,11 +97,11 @@ for name, note in plain.items():
     publish("summary.json" if name == "rocprof_summary.json" else name, name, note)
 ks = first("trace/**/*kernel_stats.csv")
 if ks:
-    publish(ks, "kernel_stats.csv", "rocprofv3 --kernel-trace --stats of `bench.py --steps 420 --warmup 42 --no-cpu-baseline "
+    publish(ks, "kernel_stats.csv", "rocprofv3 --kernel-trace --stats of `bench.py --steps 420 --warmup 42 --full --no-cpu-baseline "
                                     "--no-large-point --no-callpath` (the headline kernel's average duration comes from here)")
 ks = first("trace_d4096/**/*kernel_stats.csv")
 if ks:
-    publish(ks, "d4096_b32_kernel_stats.csv", "rocprofv3 --kernel-trace --stats of `bench.py --D 4096 --B 32 --steps 60 --warmup 12`")
+    publish(ks, "d4096_b32_kernel_stats.csv", "rocprofv3 --kernel-trace --stats of `bench.py --D 4096 --B 32 --steps 60 --warmup 12 --full`")
 ks = first("c4_update/**/*kernel_stats.csv")
 if ks:
     publish(ks, "c4_update_kernel_stats.csv", "rocprofv3 --kernel-trace --stats of scripts/c4_update_bench.py prof")

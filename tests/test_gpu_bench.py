@@ -1,5 +1,6 @@
 """bench.py contract on the GPU box: one JSON line (last on stdout) with the required keys, the roofline and
-cpu_baseline objects; and the RCCL (nccl) batch-sharded path exercised at world_size 1."""
+cpu_baseline objects (--full); the RCCL (nccl) batch-sharded path exercised at world_size 1; a plain run prints the headline
+only, and --dump-outputs writes what its last timed step computed."""
 import json
 import os
 import subprocess
@@ -22,7 +23,7 @@ def _run(extra_env, *args):
 
 
 def test_bench_json_contract():
-    d = _run({}, "--steps", "210", "--warmup", "21", "--cpu-seconds", "2")
+    d = _run({}, "--steps", "210", "--warmup", "21", "--cpu-seconds", "2", "--full")
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
               "vs_baseline", "dtype", "data", "config", "roofline", "cpu_baseline"):
         assert k in d, k
@@ -44,12 +45,13 @@ def test_bench_json_contract():
 
 
 def test_bench_rccl_path_world1():
-    d = _run({"GSMVI_BENCH_FORCE_DIST": "1"}, "--steps", "42", "--warmup", "21", "--no-cpu-baseline", "--no-callpath")
+    d = _run({"GSMVI_BENCH_FORCE_DIST": "1"}, "--steps", "42", "--warmup", "21", "--full", "--no-cpu-baseline", "--no-callpath")
     assert d["n_gpus"] == 1 and "RCCL" in d["config"]["parallelism"] and d["value"] > 0
 
 
 def test_bench_row_block_path_world1():
-    d = _run({"GSMVI_BENCH_FORCE_DIST": "1"}, "--steps", "42", "--warmup", "21", "--no-cpu-baseline", "--no-callpath", "--shard", "rows")
+    d = _run({"GSMVI_BENCH_FORCE_DIST": "1"}, "--steps", "42", "--warmup", "21", "--full", "--no-cpu-baseline", "--no-callpath",
+             "--shard", "rows")
     assert d["n_gpus"] == 1 and "row blocks" in d["config"]["parallelism"] and d["value"] > 0
 
 
@@ -76,10 +78,41 @@ def test_bench_driver_flags_time_the_graph_path_they_name():
     de = _run({}, "--steps", "210", "--warmup", "21", "--no-cpu-baseline", "--no-callpath", "--no-graph", "--no-large-point")
     assert "hipGraph" in dg["config"]["launch"] and "hipGraph" not in de["config"]["launch"], (dg["config"]["launch"], de["config"]["launch"])
     assert dg["value"] > 0.8 * de["value"], (dg["value"], de["value"])
-    d = _run({}, "--steps", "50", "--warmup", "5", "--no-cpu-baseline", "--no-callpath")
+    d = _run({}, "--steps", "50", "--warmup", "5", "--full", "--no-cpu-baseline", "--no-callpath")
     assert d["config"]["launch"] == "hipGraph(2 x 21 updates/replay + 1 x 8)", d["config"]["launch"]
     assert "traffic_source" in d["roofline"] and d["roofline"]["moved_bytes_per_launch"] < \
         d["roofline"]["algorithmic_bytes_per_launch"]
+
+
+def test_plain_run_times_the_headline_and_dumps_the_last_step(tmp_path):
+    """No --full: the line carries the headline and nothing measured beside it.  --dump-outputs: (mu, S) of the last timed
+    step, float64, equal to the oracle's update of that step's ring instance, and the same bits in a second run (the inputs
+    are seeded, so two builds can be compared output for output)."""
+    import numpy as np
+    import gsmvi_amd
+    from bench import make_instances
+    from conftest import rel_err
+    from oracle import gsm_oracle as orc
+    runs = [_run({}, "--steps", "30", "--warmup", "5", "--dump-outputs", str(tmp_path / k)) for k in ("a", "b")]
+    for d in runs:
+        for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+            assert k in d, k
+        assert d["steps"] == 30 and d["warmup"] == 5 and d["dtype"] == "f64" and d["unit"] == "updates/s"
+        assert abs(d["value"] - 1e3 / d["ms_per_step"]) / d["value"] < 1e-6
+        for k in ("roofline", "cpu_baseline", "fit_iterations_per_s", "fit_roofline", "value_cache_resident", "step_us"):
+            assert k not in d, k
+    out = {}
+    for name, shape in (("mu", (1024,)), ("S", (1024, 1024))):
+        a, b = (np.load(tmp_path / k / f"{name}.npy") for k in ("a", "b"))
+        assert a.dtype == np.float64 and a.shape == shape and np.isfinite(a).all()
+        assert np.array_equal(a, b), name
+        out[name] = a
+    assert sorted(os.listdir(tmp_path / "a")) == ["S.npy", "mu.npy"]
+    n_inst = runs[0]["config"]["instances"]
+    inst, _, _ = make_instances(gsmvi_amd.get_engine(), 1024, 32, n_inst)
+    it = {k: v.cpu().numpy() for k, v in inst[(30 - 1) % n_inst].items() if k in ("X", "G", "mu0", "S0")}
+    mu_o, S_o = orc.gsm_update_faithful(it["X"], it["G"], it["mu0"], it["S0"])
+    assert rel_err(out["mu"], mu_o) < 1e-10 and rel_err(out["S"], S_o) < 1e-10
 
 
 def test_bench_refuses_more_gpus_than_visible():
