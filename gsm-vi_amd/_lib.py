@@ -88,6 +88,11 @@ _SIGS = {
     "gsmvi_gsm_factor_apply_cols_f64": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, _c_dp, C.c_int,
                                                   _c_dp, _c_dp, C.c_int, _c_dp, _c_dp, C.c_int, _c_dp, _c_dp, C.c_int, _c_dp,
                                                   _c_dp]),
+    "gsmvi_bam_factor_wq_partial_f64": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, _c_dp, C.c_int,
+                                                  _c_dp, C.c_int, C.c_double, _c_dp]),
+    "gsmvi_bam_factor_apply_cols_f64": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, _c_dp, C.c_int,
+                                                  _c_dp, C.c_int, _c_dp, C.c_int, _c_dp, _c_dp, _c_dp, C.c_int, C.c_double,
+                                                  _c_dp, _c_dp, C.c_int, _c_dp, _c_dp]),
     "gsmvi_commit_f64": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, _c_dp, _c_dp, _c_dp, C.c_int, _c_dp, _c_dp,
                                    C.c_int, _c_dp]),
     "gsmvi_bam_update_f64": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, _c_dp, C.c_int, _c_dp, C.c_int,

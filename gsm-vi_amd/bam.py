@@ -108,6 +108,16 @@ class BaM:
         more than one GPU (see GSM.fit).
         ``method="factor"`` with ``shard=True``: the (x_b, g_b) rows are all-gathered as in the dense form and every replica
         runs the identical factor-form update (dist.sharded_bam_factor_update); retries are collective in the same way.
+        ``shard="batch"`` is a synonym of ``shard=True``.  ``shard="cols"``: the COLUMN-sharded factor form -- every rank keeps
+        the D / P columns ``dist.col_bounds(D, P, rank)`` of the square factor F and the same entries of the mean; per
+        iteration it samples its column slice (all-gathered: B D / P doubles), scores all B samples, and the partial products
+        Qt[:, C] F[:, C]^T are all-reduced (B D doubles) before the replicated B x B and 2B x 2B chains and the update of the
+        owned block (dist.col_sharded_bam_factor_update).  It is the factor form (``method`` "auto" or "factor"), needs
+        sampler="cholesky", no forced samples, D % (64 P) == 0 and 2*batch_size <= min(D, 256).  A jitter cannot be absorbed
+        without a D x D factorisation, so it takes ``jitter=0``, or ``jitter_every=0`` (the jitter is dropped); anything else
+        raises ValueError before the first collective.  Retries and ``check_update_flag`` are collective as above; the
+        covariance is assembled (one all-gather of the blocks) only for the monitor and the return value.  ``shard_stats``
+        reports the bytes of one iteration's exchanges and of the owned block.
         ``graph=True``: factor-form fits replay blocks of 16 iterations as one hipGraph (the regulariser table on the device:
         engine.bam_reg_source); bit-identical to the eager loop and, measured, not faster on an idle host -- off by default.
         ``method="auto"`` (round 6): "dense" -- the reference's own loop: update, + jitter * I, symmetrise, Cholesky accept test
@@ -131,6 +141,15 @@ class BaM:
         eng = self._engine if self._engine is not None else get_engine()
         D, B = self.D, int(batch_size)
         assert method in ("auto", "dense", "factor"), "method must be 'auto', 'dense' or 'factor'"
+        if isinstance(shard, str):
+            if shard not in ("batch", "cols"):
+                raise ValueError(f"BaM.fit: shard must be False, True, 'batch' or 'cols', not {shard!r}")
+            shard = True if shard == "batch" else "cols"
+        if shard == "cols":
+            self._check_cols_args(D, B, method, sampler, forced_samples, jitter, jitter_every, group)
+            self.method_used = "factor"
+            return self._fit_factor_cols(eng, key, regf, mean, cov, B, niter, nprint, verbose, monitor, retries, rng, as_torch,
+                                         check_update_flag, group)
         from . import _oddpad
         if _zero_cols_from is None and _oddpad.applies(eng, D, sampler, forced_samples):
             # odd D: the (D + 1)-dimensional problem with an inert last coordinate runs on the tuned kernels (_oddpad.py).
@@ -305,6 +324,24 @@ class BaM:
         return "factor" if (jitter_every is not None and int(jitter_every) > 0) else "dense"
 
     @staticmethod
+    def _check_cols_args(D, B, method, sampler, forced_samples, jitter, jitter_every, group):
+        """shard="cols": everything that would make the column-sharded factor form wrong is refused here, before the first
+        collective (every rank sees the same arguments, so every rank raises)."""
+        if method not in ("auto", "factor"):
+            raise ValueError("BaM.fit: shard='cols' is the column-sharded FACTOR form (method 'auto' or 'factor')")
+        if sampler != "cholesky" or forced_samples is not None:
+            raise ValueError("BaM.fit: shard='cols' samples with its own factor (sampler='cholesky', no forced samples)")
+        import torch.distributed as _dist
+        world = _dist.get_world_size(group) if _dist.is_initialized() else 1
+        if D % (64 * world) != 0:
+            raise ValueError(f"BaM.fit: shard='cols' needs D ({D}) to be a multiple of 64 x the number of ranks ({world})")
+        if 2 * B > min(D, 256):
+            raise ValueError("BaM.fit: shard='cols' (factor form) needs 2*batch_size <= min(D, 256)")
+        if float(jitter) != 0.0 and (jitter_every is None or int(jitter_every) != 0):
+            raise ValueError("BaM.fit: shard='cols' cannot absorb a jitter (that takes a factorisation of the whole D x D "
+                             "covariance): pass jitter=0, or jitter_every=0 to drop the jitter")
+
+    @staticmethod
     def _flag_raised(eng, flag, collective, group):
         """check_update_flag: is the update's device flag set -- on ANY rank when sharded.  The replicas run the identical
         update on identical inputs, so their flags agree; the all-reduce (MAX) makes the retry decision collective anyway
@@ -316,6 +353,134 @@ class BaM:
             _dist.all_reduce(fb, op=_dist.ReduceOp.MAX, group=group)
             bad = int(fb.item()) != 0
         return bad
+
+    # ------------------------------------------------------------------------------
+    def _fit_factor_cols(self, eng, key, regf, mean, cov, B, niter, nprint, verbose, monitor, retries, rng, as_torch,
+                         check_update_flag, group=None):
+        """Column-sharded factor-form BaM fit (see ``fit(shard="cols")``): the loop of gsmvi/bam.py:140-216 on the state
+        (mean[C], F[:, C]) per rank -- niter+1 iterations, reg = regf(i) per attempt, collective retries, the update's own
+        2B x 2B test deciding accept / revert (counted in ``n_reverts``).  The draw stream is the one of the replicated factor
+        fit (``method="factor"``), so both follow the same path.  The initial factorisation is replicated (once per fit)."""
+        import torch.distributed as _dist
+        from .dist import col_bounds, col_gather_samples, col_sharded_bam_factor_update, _all_gather, _as_torch
+        D = self.D
+        world = _dist.get_world_size(group) if _dist.is_initialized() else 1
+        rank = _dist.get_rank(group) if _dist.is_initialized() else 0
+        lo, hi = col_bounds(D, world, rank)
+        nc = hi - lo
+        self._zc = None
+        self.jitter_every_used = 0                 # (the jitter is dropped: _check_cols_args)
+        self.n_absorbed = 0
+        mean_a = eng.zeros(D) if mean is None else eng.clone(mean).reshape(D)
+        cov0 = eng.eye(D) if cov is None else eng.clone(cov).reshape(D, D)
+        flag, n_rev = eng.new_flag(), eng.new_flag()
+        F0, _ = eng.potrf(cov0, flag=flag)
+        if eng.read_flag(flag) != 0:
+            raise ValueError("initial covariance is not positive definite")
+        Fc_a = eng.clone(F0[:, lo:hi])             # the owned block, D x D / P, its own leading dimension
+        del F0, cov0
+        bufs = [(mean_a, Fc_a), (eng.clone(mean_a), eng.empty(D, nc))]
+        a = 0
+        seed = int(np.asarray(key.cpu() if _is_torch(key) else key).flatten()[-1])
+        rs = np.random.RandomState(seed)
+        assert rng in ("auto", "numpy", "device"), "rng must be 'auto', 'numpy' or 'device'"
+        dev_rng = rng != "numpy"
+        KB = 16
+        Zblk = eng.empty(KB, B, D) if dev_rng else None
+        ndraw = 0                                  # counter-based stream: one `call` per draw, retries included
+        native = bool(getattr(self.lp_g, "device_native", False))
+        mon_native = bool(getattr(monitor, "device_native", False)) if monitor is not None else False
+        self.shard_stats = {}
+
+        def assemble():
+            """(mean, F) in full on every rank: all-gather of the owned mean entries and column blocks"""
+            m_c, F_c = bufs[a]
+            if world == 1:
+                return m_c, F_c
+            recv = eng.empty(world * D, nc)
+            _all_gather(_as_torch(recv), _as_torch(F_c), group)
+            r = recv if _is_torch(recv) else _as_torch(recv).numpy()
+            F = eng.empty(D, D)
+            for p in range(world):
+                F[:, p * nc:(p + 1) * nc] = r[p * D:(p + 1) * D]
+            mrecv = eng.empty(world * nc)
+            _all_gather(_as_torch(mrecv), _as_torch(eng.clone(m_c[lo:hi])), group)
+            m = eng.clone(mrecv) if _is_torch(mrecv) else np.array(_as_torch(mrecv).numpy(), copy=True)
+            return m, F
+
+        def state():
+            m, F = assemble()
+            c = eng.gram(F)
+            return [m, c] if mon_native else [eng.to_numpy(m).copy(), eng.to_numpy(c).copy()]
+
+        nevals = 1
+        if nprint > niter:
+            nprint = niter
+        every = max(1, niter // nprint) if nprint > 0 else 1
+        reverts_seen = 0
+        for i in range(niter + 1):
+            if verbose and i % every == 0:
+                print(f"Iteration {i} of {niter}")
+                r = eng.read_flag(n_rev)
+                if r > reverts_seen:
+                    print(f"Bad update for covariance matrix. Revert ({r - reverts_seen} since last print)")
+                    reverts_seen = r
+            if monitor is not None and i % monitor.checkpoint == 0:
+                monitor(i, state(), self.lp, key, nevals=nevals)
+                nevals = 0
+            m_c, F_c = bufs[a]
+            m_n, F_n = bufs[1 - a]
+            j = 0
+            while True:
+                st = {} if i == 0 else None        # the exchanges of one (successful) iteration
+                try:
+                    if dev_rng:
+                        if ndraw % KB == 0:
+                            eng.normal_batch(KB, B, D, seed, ndraw, out=Zblk)
+                        Z = Zblk[ndraw % KB]
+                        ndraw += 1
+                    else:
+                        Z = eng.normal_from_host(_host_draw(rs, B, D, None))
+                    X = col_gather_samples(eng, eng.sample_cols(Z, m_c[lo:hi], F_c), group, stats=st)
+                    err = None
+                    try:
+                        vs = self.lp_g(X) if native else eng.host_score(self.lp_g, X)
+                    except Exception as e_score:            # noqa: BLE001
+                        if world == 1:
+                            raise
+                        err, vs = e_score, None
+                    if world > 1:                           # agree on failure BEFORE anybody enters the all-reduce
+                        fb = torch.tensor([0 if err is None else 1], dtype=torch.int32,
+                                          device=X.device if _is_torch(X) else "cpu")
+                        _dist.all_reduce(fb, op=_dist.ReduceOp.MAX, group=group)
+                        if int(fb.item()) != 0:             # nobody has called regf yet (bam.py:194-196 order)
+                            raise err if err is not None else RuntimeError("score evaluation failed on another rank")
+                    nevals += B
+                    reg = regf(i)
+                    col_sharded_bam_factor_update(eng, Z, X, vs, m_c, F_c, reg, group=group, out=(m_n, F_n), flag=flag,
+                                                  n_reverts=n_rev, stats=st)
+                    if check_update_flag and self._flag_raised(eng, flag, world > 1, group):
+                        raise FloatingPointError("BaM update flagged a numerical failure (device flag != 0)")
+                    if st is not None:
+                        self.shard_stats.update(st)
+                    break
+                except Exception as e:                      # noqa: BLE001 -- reference behaviour
+                    if j < retries:
+                        j += 1
+                        print(f"Failed with exception {e}")
+                        print(f"Trying again {j} of {retries}")
+                    else:
+                        raise e
+            a = 1 - a                   # the kernel already returned the reverted state when its test failed: accept = swap
+        if monitor is not None:
+            monitor(niter, state(), self.lp, key, nevals=nevals)
+        self.n_reverts = eng.read_flag(n_rev)
+        self.shard_stats["block_bytes"] = D * nc * 8
+        m, F = assemble()
+        cov_t = eng.gram(F)
+        if as_torch:
+            return m, cov_t
+        return eng.to_numpy(m), eng.to_numpy(cov_t)
 
     # ------------------------------------------------------------------------------
     def _fit_factor(self, eng, key, regf, mean, cov, B, niter, nprint, verbose, monitor, retries, rng, as_torch,

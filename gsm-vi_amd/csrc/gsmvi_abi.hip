@@ -66,6 +66,12 @@ int gsmvi_bam_impl(struct gsmvi_ctx* ctx, hipStream_t st, int D, int B, const do
 int gsmvi_bam_factor_impl(gsmvi_ctx* ctx, hipStream_t st, int D, int B, const double* Z, int ldz, const double* X, int ldx,
                           const double* G, int ldg, const double* mu0, const double* F0, int ldf0, double reg, double* mu,
                           double* F, int ldf, int* info_dev, int* n_reverts_dev);
+int gsmvi_bam_factor_wq_partial_impl(gsmvi_ctx* ctx, hipStream_t st, int D, int B, int col0, int ncols, const double* G, int ldg,
+                                     const double* F0c, int ldf0, double reg, double* Wq_part);
+int gsmvi_bam_factor_apply_cols_impl(gsmvi_ctx* ctx, hipStream_t st, int D, int B, int col0, int ncols, const double* Z, int ldz,
+                                     const double* X, int ldx, const double* G, int ldg, const double* Wq, const double* mu0,
+                                     const double* F0c, int ldf0, double reg, double* mu, double* Fc, int ldf, int* info_dev,
+                                     int* n_reverts_dev);
 
 #include "gsmvi_ctx.h"
 
@@ -859,6 +865,59 @@ int gsmvi_bam_factor_update_f64(gsmvi_ctx* ctx, void* stream, int D, int B, cons
     }
     return gsmvi_bam_factor_impl(ctx, reinterpret_cast<hipStream_t>(stream), D, B, Z, ldz, X, ldx, G, ldg, mu0, F0, ldf0, reg,
                                  mu, F, ldf, info_dev, n_reverts_dev);
+}
+
+// Geometry of the column-sharded factor-form BaM entry points, checked before the context is looked at (so a machine without
+// a GPU can check it): the block, the batch bound of the factor form, reg, even D and leading dimensions, aligned blocks.
+static int bam_cols_geometry(const char* fn, int D, int B, int col0, int ncols, int ldf0, const double* F0cols, double reg) {
+    if (D <= 0 || B <= 0 || col0 < 0 || ncols <= 0 || col0 + ncols > D) {
+        gsmvi_set_error("%s: %s", fn, "column block out of range");
+        return GSMVI_ERR_BAD_ARG;
+    }
+    if (col0 % 64 != 0 || (ncols % 64 != 0 && col0 + ncols != D)) {
+        gsmvi_set_error("%s: %s", fn, "column blocks are tile aligned (multiples of 64; the last one may be ragged)");
+        return GSMVI_ERR_BAD_ARG;
+    }
+    if (!(reg > 0.0)) {
+        gsmvi_set_error("%s: %s", fn, "reg must be positive");
+        return GSMVI_ERR_BAD_ARG;
+    }
+    if (ldf0 < ncols || D % 2 != 0 || ldf0 % 2 != 0 || !aligned16(F0cols)) {
+        gsmvi_set_error("%s: %s", fn, "the column-sharded form takes even D, even leading dimensions and 16-byte aligned blocks");
+        return GSMVI_ERR_BAD_ARG;
+    }
+    if (2 * B > D || 2 * B > GSMVI_FACTOR_NMAX || D > 16384) {
+        gsmvi_set_error("%s: %s", fn, "the factor form needs 2B <= D and 2B <= 256");
+        return GSMVI_ERR_UNSUPPORTED;
+    }
+    return GSMVI_OK;
+}
+
+int gsmvi_bam_factor_wq_partial_f64(gsmvi_ctx* ctx, void* stream, int D, int B, int col0, int ncols, const double* G, int ldg,
+                                    const double* F0cols, int ldf0, double reg, double* Wq_part) {
+    BAD_ARG(!G || !F0cols || !Wq_part, "NULL argument");
+    BAD_ARG(Wq_part == G || Wq_part == F0cols, "the output must not alias an input");
+    int st = bam_cols_geometry(__func__, D, B, col0, ncols, ldf0, F0cols, reg);
+    if (st != GSMVI_OK) return st;
+    BAD_ARG(ldg < D, "leading dimension too small");
+    if ((st = check_common(ctx, D, B, __func__)) != GSMVI_OK) return st;
+    return gsmvi_bam_factor_wq_partial_impl(ctx, reinterpret_cast<hipStream_t>(stream), D, B, col0, ncols, G, ldg, F0cols, ldf0,
+                                            reg, Wq_part);
+}
+
+int gsmvi_bam_factor_apply_cols_f64(gsmvi_ctx* ctx, void* stream, int D, int B, int col0, int ncols, const double* Z, int ldz,
+                                    const double* X, int ldx, const double* G, int ldg, const double* Wq, const double* mu0,
+                                    const double* F0cols, int ldf0, double reg, double* mu, double* Fcols, int ldf, int* info_dev,
+                                    int* n_reverts_dev) {
+    BAD_ARG(!Z || !X || !G || !Wq || !mu0 || !F0cols || !mu || !Fcols || !info_dev, "NULL argument");
+    BAD_ARG(Fcols == F0cols || mu == mu0 || Fcols == Wq, "outputs must not alias inputs");
+    int st = bam_cols_geometry(__func__, D, B, col0, ncols, ldf0, F0cols, reg);
+    if (st != GSMVI_OK) return st;
+    BAD_ARG(ldz < D || ldx < D || ldg < D || ldf < ncols, "leading dimension too small");
+    BAD_ARG(ldf % 2 != 0 || !aligned16(Fcols), "the column-sharded form takes even leading dimensions and 16-byte aligned blocks");
+    if ((st = check_common(ctx, D, B, __func__)) != GSMVI_OK) return st;
+    return gsmvi_bam_factor_apply_cols_impl(ctx, reinterpret_cast<hipStream_t>(stream), D, B, col0, ncols, Z, ldz, X, ldx, G, ldg,
+                                            Wq, mu0, F0cols, ldf0, reg, mu, Fcols, ldf, info_dev, n_reverts_dev);
 }
 
 }  // extern "C"

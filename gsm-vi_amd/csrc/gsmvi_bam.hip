@@ -1071,12 +1071,13 @@ int gsmvi_bam_impl(gsmvi_ctx* ctx, hipStream_t st, int D, int B, const double* X
 //   "mean" output with mu0 = xbar = 0), which rides through the Rt F0 product.  Four passes over F0 (Wq, Rt F0, and the
 //   read + write of the update), no pass over a covariance.
 // mu = mu0/(1+reg) + r1 (S gbar) + r1 xbar, or mu0 on a reverted update (bam.py:112)
-__global__ __launch_bounds__(256) void k_bamf_commit(int D, const double* __restrict__ sg_r1, const double* __restrict__ mu0,
+// (entries [j0, j1) only: all of them, or the owned block of the column-sharded form)
+__global__ __launch_bounds__(256) void k_bamf_commit(int j0, int j1, const double* __restrict__ sg_r1, const double* __restrict__ mu0,
                                                      const double* __restrict__ xbar, bam_reg regs,
                                                      const int* __restrict__ bad, double* __restrict__ mu) {
     const double reg = regs.get();
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= D) return;
+    const int i = j0 + blockIdx.x * 256 + threadIdx.x;
+    if (i >= j1) return;
     const double r1 = reg / (1.0 + reg);
     mu[i] = *bad ? mu0[i] : mu0[i] / (1.0 + reg) + sg_r1[i] + r1 * xbar[i];
 }
@@ -1197,9 +1198,15 @@ __global__ __launch_bounds__(256) void k_bamf_pi_vg(OpBasisPi op, int nblk, cons
 // positive-definite rule (dependent draws are a failure, not a drop)
 int gsmvi_cholw_small(hipStream_t st, int n, const double* A, double* R, double* W, int* info, int info_off);
 
-int gsmvi_bam_factor_impl(gsmvi_ctx* ctx, hipStream_t st, int D, int B, const double* Z, int ldz, const double* X, int ldx,
-                          const double* G, int ldg, const double* mu0, const double* F0, int ldf0, double reg_value, double* mu,
-                          double* F, int ldf, int* info_dev, int* n_reverts_dev) {
+// The body of the factor-form update and of its column-sharded apply (gsmvi_bam_factor_apply_cols_f64).  Wq_in == NULL: Wq =
+// Qt F0^T is formed here from the whole F0 (col0 = 0, ncols = D).  Otherwise Wq_in is the all-reduced product of the ranks'
+// partials (gsmvi_bam_factor_wq_partial_impl) and F0 / F are the D x ncols blocks of the columns [col0, col0 + ncols): everything
+// of size B x D and the B x B / 2B x 2B chains are replicated, Rt F0 is taken on the block and the update kernels and the mean
+// write the block's window of 64-column tiles alone (ctx->colwin_*, as gsmvi_factor_apply_cols_impl).  mu0 entries outside the
+// block reach only Tm's columns outside it, which nothing reads back.
+static int bam_factor_body(gsmvi_ctx* ctx, hipStream_t st, int D, int B, const double* Z, int ldz, const double* X, int ldx,
+                           const double* G, int ldg, const double* Wq_in, int col0, int ncols, const double* mu0, const double* F0,
+                           int ldf0, double reg_value, double* mu, double* F, int ldf, int* info_dev, int* n_reverts_dev) {
     const bam_reg reg{reg_value, ctx->reg_dev};
     const int n = B, n2 = 2 * n;
     // workspace (ctx->sg holds 8 rmax max_D doubles, rmax = 2B + 8): 10 n + 5 rows of D
@@ -1233,8 +1240,13 @@ int gsmvi_bam_factor_impl(gsmvi_ctx* ctx, hipStream_t st, int D, int B, const do
 
     // (Tm rows 0 .. n-1 = Vw F0 = the Helmert rows of the samples themselves: the stats kernel's third track)
     bam_stats_launch(st, D, B, Z, ldz, (const double*)nullptr, X, ldx, G, ldg, reg, xbar, gbar, zerov, Qt, Ft, (double*)nullptr, mu0, Tm);
+    if (!Wq_in) {
     if ((rc = gsmvi_panel_t_product(ctx, st, D, n, Qt, D, F0, ldf0, D, ctx->pp, &kc))) return rc;
     if ((rc = gsmvi_panel_finish(st, D, n, kc, ctx->pp, nullptr, Wq, D))) return rc;
+    } else if (hipMemcpyAsync(Wq, Wq_in, sizeof(double) * n * D, hipMemcpyDeviceToDevice, st) != hipSuccess) {
+        gsmvi_set_error("%s: %s", "gsmvi_bam_factor_apply_cols_f64", "copy of Wq failed");   // ([Wq; Vw] is one operand below)
+        return GSMVI_ERR_HIP;
+    }
     // Two-level 2B x 2B chain ahead (64 < B <= 128): its first diagonal block Gamma11 = Vw Vw^T does not depend on the B x B
     // chain, so the Gram product below is taken against [Wq; Vw] (2n columns instead of n: the slabs then hold Vw Vw^T as well)
     // and [Gamma11 | I] -> [R11 | W11] runs as the second workgroup of k_bam_cholw's launch (ctx->early; factor_chain_big).
@@ -1330,6 +1342,10 @@ int gsmvi_bam_factor_impl(gsmvi_ctx* ctx, hipStream_t st, int D, int B, const do
     ctx->bam_mean = gsmf_bam_mean{xbar, Tm + (size_t)n2 * D, reg};   // 2B <= 64: the update kernel writes BaM's mean itself
     ctx->bam_mean_done = 0;
     int kcg = 1, rides = 0;
+    // the window of 64-column tiles the update launches write (the whole of F when col0 = 0, ncols = D); F0 / F are handed on
+    // as base pointers shifted so that GLOBAL column indices address the block
+    ctx->colwin_0 = col0 / 64;
+    ctx->colwin_n = (ncols + 63) / 64;
     // Large D, 64 < 2B <= 128 (the 2B x 2B chain is six small launches, ~115 us on a few CUs): the product Rt F0 (MFMA-bound,
     // 92 us at D = 4096) depends on Ft only, so it runs on the context's second stream beside the Gram product and the chain and is
     // joined in front of K'' Tm -- what the GSM factor update does with V Fm (gsmvi_factor.hip; same threshold: the two event
@@ -1341,7 +1357,7 @@ int gsmvi_bam_factor_impl(gsmvi_ctx* ctx, hipStream_t st, int D, int B, const do
         hipError_t fe = hipEventRecord(ctx->ev_fork, st);
         if (fe == hipSuccess) fe = hipStreamWaitEvent(ctx->side, ctx->ev_fork, 0);
         if (fe != hipSuccess) { gsmvi_set_error("%s: %s", "gsmvi_bam_factor_impl", "fork failed"); rc = GSMVI_ERR_HIP; }
-        if (!rc) rc = gsmvi_panel_product_out(ctx, ctx->side, D, D, n + 1, Ft + (size_t)n * D, D, nullptr, 1.0, F0, ldf0, nullptr, Tm + (size_t)n * D, D);
+        if (!rc) rc = gsmvi_panel_product_out(ctx, ctx->side, D, ncols, n + 1, Ft + (size_t)n * D, D, nullptr, 1.0, F0, ldf0, nullptr, Tm + (size_t)n * D + col0, D);
         if (!rc && hipEventRecord(ctx->ev_join, ctx->side) != hipSuccess) {
             gsmvi_set_error("%s: %s", "gsmvi_bam_factor_impl", "join failed");
             rc = GSMVI_ERR_HIP;
@@ -1349,20 +1365,21 @@ int gsmvi_bam_factor_impl(gsmvi_ctx* ctx, hipStream_t st, int D, int B, const do
         if (!rc) rc = gsmvi_factor_signed_gram(ctx, st, D, n, &kcg, info_dev, &rides);
         ctx->px = gsmvi_panel_extras();            // nothing rides in a panel launch here: the chain sums the Gram slabs itself
         if (!rc)
-            rc = gsmvi_factor_signed_back(ctx, st, D, n, mu0, F0, ldf0, mu, F, ldf, info_dev, n_reverts_dev, kcg, 0, 0, 1);
+            rc = gsmvi_factor_signed_back(ctx, st, D, n, mu0, F0 - col0, ldf0, mu, F - col0, ldf, info_dev, n_reverts_dev, kcg, 0, 0, 1);
     } else {
         rc = gsmvi_factor_signed_gram(ctx, st, D, n, &kcg, info_dev, &rides);   // Gram slabs of [Vw; Zw]; the 2B x 2B chain rides in ...
         // ... this product; with the chain riding (~35 us on one CU) it is off the critical path: unsplit, finished output, no
         // finish launch (gsmvi_factor_impl does the same with V Fm)
         const int kc_user = ctx->tune_panel_kc;
         if (rides && D >= 1024 && D <= ctx->tune_rider_direct_max_D) ctx->tune_panel_kc = 1;
-        if (!rc) rc = gsmvi_panel_product_out(ctx, st, D, D, n + 1, Ft + (size_t)n * D, D, nullptr, 1.0, F0, ldf0, nullptr, Tm + (size_t)n * D, D);
+        if (!rc) rc = gsmvi_panel_product_out(ctx, st, D, ncols, n + 1, Ft + (size_t)n * D, D, nullptr, 1.0, F0, ldf0, nullptr, Tm + (size_t)n * D + col0, D);
         ctx->tune_panel_kc = kc_user;
         const int taken = ctx->px_used;
         ctx->px = gsmvi_panel_extras();
         if (!rc)
-            rc = gsmvi_factor_signed_back(ctx, st, D, n, mu0, F0, ldf0, mu, F, ldf, info_dev, n_reverts_dev, kcg, rides, taken, 0);
+            rc = gsmvi_factor_signed_back(ctx, st, D, n, mu0, F0 - col0, ldf0, mu, F - col0, ldf, info_dev, n_reverts_dev, kcg, rides, taken, 0);
     }
+    ctx->colwin_0 = ctx->colwin_n = 0;
     ctx->fo_Rt = ctx->fo_Tm = ctx->fo_Fs = nullptr;
     ctx->chain_pi = nullptr;
     ctx->chain_x = nullptr;
@@ -1372,14 +1389,56 @@ int gsmvi_bam_factor_impl(gsmvi_ctx* ctx, hipStream_t st, int D, int B, const do
     ctx->bam_mean_done = 0;
     if (rc) return rc;
     if (!mean_done)
-    hipLaunchKernelGGL(k_bamf_commit, dim3((D + 255) / 256), dim3(256), 0, st, D, Tm + (size_t)n2 * D, mu0, xbar, reg, info_dev,
-                       mu);
+    hipLaunchKernelGGL(k_bamf_commit, dim3((ncols + 255) / 256), dim3(256), 0, st, col0, col0 + ncols, Tm + (size_t)n2 * D, mu0,
+                       xbar, reg, info_dev, mu);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) {
         gsmvi_set_error("BaM (factor form) launch failed: %s%s", hipGetErrorString(e), "");
         return GSMVI_ERR_HIP;
     }
     return GSMVI_OK;
+}
+
+int gsmvi_bam_factor_impl(gsmvi_ctx* ctx, hipStream_t st, int D, int B, const double* Z, int ldz, const double* X, int ldx,
+                          const double* G, int ldg, const double* mu0, const double* F0, int ldf0, double reg_value, double* mu,
+                          double* F, int ldf, int* info_dev, int* n_reverts_dev) {
+    return bam_factor_body(ctx, st, D, B, Z, ldz, X, ldx, G, ldg, nullptr, 0, D, mu0, F0, ldf0, reg_value, mu, F, ldf, info_dev,
+                           n_reverts_dev);
+}
+
+// ---- column-sharded factor-form BaM (bam.py:72-114 on the owned columns C = [col0, col0 + ncols) of F0) -----------------------
+// Wq = Qt F0^T is a sum over the columns of F0: this rank's term Qt[:, C] F0[:, C]^T (B x D, contiguous), for the caller to
+// all-reduce.  Qt depends on G and reg alone: the stats kernel runs with G in the draws' slot and without the samples (the rows
+// it then writes besides Qt are scratch), so Qt is the same, bit for bit, as in the apply call and in the unsharded update.
+// wg = F0 gbar, which BaM's mean needs, is Wq's last row up to the factor sqrt(reg / (1 + reg)): it travels in the same sum.
+int gsmvi_bam_factor_wq_partial_impl(gsmvi_ctx* ctx, hipStream_t st, int D, int B, int col0, int ncols, const double* G, int ldg,
+                                     const double* F0c, int ldf0, double reg_value, double* Wq_part) {
+    const bam_reg reg{reg_value, ctx->reg_dev};
+    const int n = B;
+    double* Qt = ctx->sg;                          // Qt's slot of bam_factor_body; the Ft / T1 slots behind it as scratch
+    double* scr = Qt + (size_t)2 * n * D;
+    double* xbar = scr + (size_t)(2 * n + 1) * D;
+    double* gbar = xbar + D;
+    bam_stats_launch(st, D, B, G, ldg, (const double*)nullptr, (const double*)nullptr, 0, G, ldg, reg, xbar, gbar, (double*)nullptr,
+                     Qt, scr, (double*)nullptr);
+    int kc = 1, rc;
+    if ((rc = gsmvi_panel_t_product(ctx, st, ncols, n, Qt + col0, D, F0c, ldf0, D, ctx->pp, &kc))) return rc;
+    if ((rc = gsmvi_panel_finish(st, D, n, kc, ctx->pp, nullptr, Wq_part, D))) return rc;
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) {
+        gsmvi_set_error("BaM (column-sharded) launch failed: %s%s", hipGetErrorString(e), "");
+        return GSMVI_ERR_HIP;
+    }
+    return GSMVI_OK;
+}
+
+// From the replicated Z, the gathered X, G and the all-reduced Wq: the update of the owned block Fc (D x ncols) and mu[C]
+int gsmvi_bam_factor_apply_cols_impl(gsmvi_ctx* ctx, hipStream_t st, int D, int B, int col0, int ncols, const double* Z, int ldz,
+                                     const double* X, int ldx, const double* G, int ldg, const double* Wq, const double* mu0,
+                                     const double* F0c, int ldf0, double reg_value, double* mu, double* Fc, int ldf, int* info_dev,
+                                     int* n_reverts_dev) {
+    return bam_factor_body(ctx, st, D, B, Z, ldz, X, ldx, G, ldg, Wq, col0, ncols, mu0, F0c, ldf0, reg_value, mu, Fc, ldf, info_dev,
+                           n_reverts_dev);
 }
 
 hipError_t gsmvi_bam_prepare() {

@@ -205,6 +205,33 @@ def col_sharded_gsm_factor_update(eng, Z, X, G, mu0, F0_cols, group=None, out=No
     return eng.gsm_factor_apply_cols(Z, W, X, mu0, F0_cols, lo, out=out, flag=flag, n_reverts=n_reverts)
 
 
+def col_sharded_bam_factor_update(eng, Z, X, G, mu0, F0_cols, reg, group=None, out=None, flag=None, n_reverts=None, stats=None):
+    """Factor-form BaM update with the square factor sharded by COLUMN BLOCKS (gsmvi/bam.py:72-114; the layout of
+    ``col_sharded_gsm_factor_update``): (mu, F_cols, flag).  Every rank holds the columns ``col_bounds(D, P, r)`` of F0
+    (Sigma = F0^T F0) and gets back the same columns of the new factor and ITS entries of the new mean (``mu`` is full length;
+    only the owned entries are written, the others of ``mu0`` may be stale).  Z, X (e.g. from ``col_gather_samples``) and G
+    are replicated.  One exchange: the all-reduce of the partial products Qt[:, C] F0[:, C]^T to Wq = Qt F0^T (B D doubles;
+    Qt the Helmert / gbar rows of G).  BaM's B x B chain and the 2B x 2B chain are replicated (identical inputs and
+    arithmetic: every rank takes the same accept / revert decision); the update reads and writes the owned block only."""
+    world = dist.get_world_size(group) if dist.is_initialized() else 1
+    rank = dist.get_rank(group) if dist.is_initialized() else 0
+    B, D = Z.shape
+    lo, hi = col_bounds(D, world, rank)
+    assert tuple(F0_cols.shape) == (D, hi - lo), f"rank {rank} must hold columns [{lo}, {hi}) of F0"
+    Wq = eng.bam_factor_wq_partial(G, lo, F0_cols, reg)
+    if world > 1:
+        if stats is not None:
+            stats["all_reduce_bytes"] = B * D * 8
+            stats["collectives"] = stats.get("collectives", 0) + 1
+        if isinstance(Wq, torch.Tensor):
+            _all_reduce_sum(Wq, group)
+        else:
+            t = _as_torch(Wq)
+            dist.all_reduce(t, op=dist.ReduceOp.SUM, group=group)
+            Wq = t.numpy()
+    return eng.bam_factor_apply_cols(Z, X, G, Wq, mu0, F0_cols, lo, reg, out=out, flag=flag, n_reverts=n_reverts)
+
+
 def sharded_bam_update(eng, X_local, G_local, mu0, S0, reg, jitter=0.0, group=None, out=None, flag=None, stats=None):
     """(mu, S, flag) of the BaM update for the union of all ranks' samples (gsmvi/bam.py:72-114;
     BASELINE config 4: B=128 sharded 16 per GPU).  BaM's statistics couple all samples (batch means

@@ -500,6 +500,41 @@ class HipEngine:
             C.c_void_p(n_reverts.data_ptr()) if n_reverts is not None else None))
         return mu, F, flag
 
+    def bam_factor_wq_partial(self, G, col0, F0cols, reg, out=None):
+        """The rank's PARTIAL sum of Wq = Qt F0^T over its owned columns: Qt[:, C] F0[:, C]^T (B x D), Qt the Helmert / gbar rows
+        of G (gsmvi_bam_factor_wq_partial_f64; the caller all-reduces the partials, dist.col_sharded_bam_factor_update)."""
+        B, D = G.shape
+        nc = F0cols.shape[1]
+        assert F0cols.shape == (D, nc)
+        self._ensure(D, B)                         # (the product's output is D wide: sized for (D, B), not for the block)
+        Wq = self.empty(B, D) if out is None else out
+        assert Wq.shape == (B, D) and Wq.is_contiguous()
+        pg, ldg = self._mat(G, "G")
+        pf0, ldf0 = self._mat(F0cols, "F0cols")
+        _lib.check("gsmvi_bam_factor_wq_partial_f64", self.lib.gsmvi_bam_factor_wq_partial_f64(
+            self._ctx, self._stream(), D, B, int(col0), nc, pg, ldg, pf0, ldf0, float(reg), C.c_void_p(Wq.data_ptr())))
+        return Wq
+
+    def bam_factor_apply_cols(self, Z, X, G, Wq, mu0, F0cols, col0, reg, out=None, flag=None, n_reverts=None):
+        """(mu, Fcols, flag): the factor-form BaM update of the OWNED column block from the replicated draws Z, the gathered
+        samples X, the scores G and the all-reduced Wq; mu is full length, entries C written (gsmvi_bam_factor_apply_cols_f64)."""
+        B, D = Z.shape
+        nc = F0cols.shape[1]
+        assert Wq.shape == (B, D) and Wq.is_contiguous() and X.shape == (B, D) and G.shape == (B, D) and F0cols.shape == (D, nc)
+        self._ensure(D, B)
+        mu, F = (self.empty(D), self.empty(D, nc)) if out is None else out
+        flag = self.new_flag() if flag is None else flag
+        pz, ldz = self._mat(Z, "Z")
+        px, ldx = self._mat(X, "X")
+        pg, ldg = self._mat(G, "G")
+        pf0, ldf0 = self._mat(F0cols, "F0cols")
+        pf, ldf = self._mat(F, "Fcols")
+        _lib.check("gsmvi_bam_factor_apply_cols_f64", self.lib.gsmvi_bam_factor_apply_cols_f64(
+            self._ctx, self._stream(), D, B, int(col0), nc, pz, ldz, px, ldx, pg, ldg, C.c_void_p(Wq.data_ptr()),
+            self._vec(mu0, "mu0"), pf0, ldf0, float(reg), self._vec(mu, "mu"), pf, ldf, C.c_void_p(flag.data_ptr()),
+            C.c_void_p(n_reverts.data_ptr()) if n_reverts is not None else None))
+        return mu, F, flag
+
     def gram(self, F, out=None, shift=0.0, shift_dev=None):
         """cov = F^T F (gsmvi_gram_f64): the covariance a square factor represents -- return value of the
         factor-form fit and what its monitor sees (gsm_numpy.py:129).  Not on the per-iteration path.

@@ -343,6 +343,34 @@ int gsmvi_gsm_factor_apply_cols_f64(gsmvi_ctx* ctx, void* stream, int D, int B, 
                                     int ldf0, double* mu, double* Fcols, int ldf, int* info_dev, int* n_reverts_dev);
 
 /*
+ * COLUMN-SHARDED factor-form BaM update (bam.py:72-114 on a rank's columns C = [col0, col0 + ncols) of the square factor F0,
+ * Sigma0 = F0^T F0; the same block layout and sampler as the GSM form above).  Per update:
+ *   gsmvi_sample_cols_f64              the owned slice of x = mu0 + z F0, all-gathered by the caller (B ncols doubles per rank).
+ *   gsmvi_bam_factor_wq_partial_f64    Wq_part (B x D, contiguous) = Qt[:, C] F0cols^T, Qt the B x D Helmert / gbar rows of G
+ *                                      (sqrt(reg/B), sqrt(reg/(1+reg))); the caller all-reduces the partials to Wq = Qt F0^T
+ *                                      (B D doubles).  wg = F0 gbar, which BaM's mean needs, is Wq's last row up to its scale.
+ *   gsmvi_bam_factor_apply_cols_f64    from the replicated draws Z, the gathered samples X, the scores G and the all-reduced
+ *                                      Wq: BaM's B x B chain and the 2B x 2B chain of gsmvi_bam_factor_update_f64 (replicated:
+ *                                      identical inputs and arithmetic on every rank, so the accept / revert decision agrees),
+ *                                      then Rt F0 on the block and the update of the OWNED block alone: Fcols = F0cols +
+ *                                      Rt^T K'' (Rt F0cols), mu[C] = mu0[C]/(1+reg) + r1 (Sigma gbar)[C] + r1 xbar[C].
+ *                                      mu0 / mu are full-length vectors of which entries C alone are read / written (mu0's
+ *                                      other entries may be stale); on a revert *info_dev != 0, (mu[C], Fcols) = (mu0[C], F0cols)
+ *                                      and *n_reverts_dev (may be NULL) is incremented.
+ * With col0 = 0, ncols = D the two calls give gsmvi_bam_factor_update_f64's result.  col0 % 64 == 0, ncols % 64 == 0 (the
+ * last block may be ragged), even D and leading dimensions, 16-byte aligned blocks, 2B <= min(D, 256); these are checked
+ * (GSMVI_ERR_BAD_ARG / GSMVI_ERR_UNSUPPORTED) before the context is used.  No host synchronisation, graph-capturable, workspace
+ * from the context (sized for (D, B)).  Per update a rank reads its block three times and writes it once and exchanges
+ * B (ncols + D) doubles; the B x B and 2B x 2B chains and the B x D work are not divided.
+ */
+int gsmvi_bam_factor_wq_partial_f64(gsmvi_ctx* ctx, void* stream, int D, int B, int col0, int ncols, const double* G, int ldg,
+                                    const double* F0cols, int ldf0, double reg, double* Wq_part);
+int gsmvi_bam_factor_apply_cols_f64(gsmvi_ctx* ctx, void* stream, int D, int B, int col0, int ncols, const double* Z, int ldz,
+                                    const double* X, int ldx, const double* G, int ldg, const double* Wq, const double* mu0,
+                                    const double* F0cols, int ldf0, double reg, double* mu, double* Fcols, int ldf, int* info_dev,
+                                    int* n_reverts_dev);
+
+/*
  * Whitened draws: out[0..n) ~ N(0, 1), a pure function of (seed, call, element index) -- counter-based
  * Philox4x32-10 (key = seed, counter = (pair index, call)) + Box-Muller in fp64; see csrc/gsmvi_rng.hip.
  * Replaces the standard-normal stream behind np.random.multivariate_normal (gsm_numpy.py:105,116) in
