@@ -84,3 +84,18 @@ def wrap_monitor(monitor, lp, D):
 def applies(eng, D, sampler, forced_samples):
     """odd D, the device sampler (the legacy SVD sampler and teacher-forced samples keep the literal D), a HIP engine"""
     return D % 2 == 1 and sampler == "cholesky" and forced_samples is None and getattr(eng, "name", "") == "hip"
+
+
+def fit_padded(outer, inner, args, kw, mean, cov, monitor, as_torch, defaults=None):
+    """``outer.fit`` of an odd-D problem run as ``inner.fit(*args, **kw)``, the (D + 1)-dimensional problem built by the
+    caller: returns the fit without the inert coordinate and copies the attributes the inner fit set (``defaults`` for those
+    it did not) back to ``outer``, with ``padded_dim``."""
+    eng, D = inner._engine, outer.D
+    mp, cp = inner.fit(*args, mean=pad_vec(eng, mean, D), cov=pad_mat(eng, cov, D), monitor=wrap_monitor(monitor, outer.lp, D),
+                       as_torch=True, _zero_cols_from=D, **kw)
+    for a in ("method_used", "n_reverts", "graph_replays", "graph_fallback"):
+        if hasattr(inner, a) or a in (defaults or {}):
+            setattr(outer, a, getattr(inner, a, (defaults or {}).get(a)))
+    outer.padded_dim = D + 1
+    mean_o, cov_o = mp[:D].contiguous(), cp[:D, :D].contiguous()
+    return (mean_o, cov_o) if as_torch else (eng.to_numpy(mean_o), eng.to_numpy(cov_o))

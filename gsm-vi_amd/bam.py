@@ -3,8 +3,16 @@
 import numpy as np
 import torch
 
+from . import _oddpad
+from ._fitloop import (KB, Checkpoints, DrawStream, GraphBlock, Progress, _is_torch, _legacy_mvn, eventful, initial_factor,
+                       initial_state, result, retry, scorer, seed_of, takes_out)
 from .engine import get_engine
-from .gsm import _legacy_mvn, _is_torch, _host_draw
+
+
+def _every(nprint, niter):
+    """print cadence of bam.py:177-179: ``nprint`` clamped to niter; every iteration when it is not positive"""
+    nprint = min(nprint, niter)
+    return max(1, niter // nprint) if nprint > 0 else 1
 
 
 def bam_lowrank_update(samples, vs, mu0, S0, reg, engine=None, jitter=0.0):
@@ -150,7 +158,6 @@ class BaM:
             self.method_used = "factor"
             return self._fit_factor_cols(eng, key, regf, mean, cov, B, niter, nprint, verbose, monitor, retries, rng, as_torch,
                                          check_update_flag, group)
-        from . import _oddpad
         if _zero_cols_from is None and _oddpad.applies(eng, D, sampler, forced_samples):
             # odd D: the (D + 1)-dimensional problem with an inert last coordinate runs on the tuned kernels (_oddpad.py).
             # (the corner of cov' picks up the jitter like every diagonal entry; it touches nothing else)
@@ -158,16 +165,11 @@ class BaM:
                 method = self._auto_method(D, B, sampler, forced_samples, jitter, jitter_every)
             inner = BaM(D + 1, self.lp, _oddpad.wrap_score(eng, self.lp_g, D), use_lowrank=self.use_lowrank,
                         jit_compile=self.jit_compile, engine=eng)
-            mp, cp = inner.fit(key, regf, mean=_oddpad.pad_vec(eng, mean, D), cov=_oddpad.pad_mat(eng, cov, D),
-                               batch_size=batch_size, niter=niter, nprint=nprint, verbose=verbose,
-                               check_goodness=check_goodness, monitor=_oddpad.wrap_monitor(monitor, self.lp, D),
-                               retries=retries, jitter=jitter, sampler=sampler, rng=rng, as_torch=True, shard=shard,
-                               group=group, check_update_flag=check_update_flag, method=method, root_potrf=root_potrf,
-                               graph=graph, jitter_every=jitter_every, _zero_cols_from=D)
-            self.method_used, self.n_reverts, self.padded_dim = inner.method_used, inner.n_reverts, D + 1
-            self.graph_replays, self.graph_fallback = getattr(inner, "graph_replays", 0), getattr(inner, "graph_fallback", None)
-            mean_o, cov_o = mp[:D].contiguous(), cp[:D, :D].contiguous()
-            return (mean_o, cov_o) if as_torch else (eng.to_numpy(mean_o), eng.to_numpy(cov_o))
+            return _oddpad.fit_padded(self, inner, (key, regf), dict(
+                batch_size=batch_size, niter=niter, nprint=nprint, verbose=verbose, check_goodness=check_goodness,
+                retries=retries, jitter=jitter, sampler=sampler, rng=rng, shard=shard, group=group,
+                check_update_flag=check_update_flag, method=method, root_potrf=root_potrf, graph=graph,
+                jitter_every=jitter_every), mean, cov, monitor, as_torch, defaults={"graph_replays": 0, "graph_fallback": None})
         self._zc = _zero_cols_from
         if method == "auto":
             method = self._auto_method(D, B, sampler, forced_samples, jitter, jitter_every)
@@ -181,121 +183,62 @@ class BaM:
         bmax = getattr(eng, "bam_max_batch", None)
         if bmax is not None and B > bmax:               # deterministic: raised here, not inside the retry loop
             raise ValueError(f"BaM.fit: batch_size {B} exceeds the device update's limit of {bmax}")
-        mean_t = eng.zeros(D) if mean is None else eng.clone(mean).reshape(D)
-        cov_t = eng.eye(D) if cov is None else eng.clone(cov).reshape(D, D)
-        seed = int(np.asarray(key.cpu() if _is_torch(key) else key).flatten()[-1])
+        mean_t, cov_t = initial_state(eng, D, mean, cov)
+        seed = seed_of(key, last=True)
         rs = np.random.RandomState(seed)
         assert rng in ("auto", "numpy", "device"), "rng must be 'auto', 'numpy' or 'device'"
-        dev_rng = rng == "device" or (rng == "auto" and sampler == "cholesky")   # as GSM.fit: see its docstring
-        KB = 16                         # the device draws come a block of KB per launch (the stream does not depend on the state)
-        Zblk = eng.empty(KB, B, D) if dev_rng else None
-        ndraw = 0                       # counter-based stream: one `call` per draw, retries included
-        native = bool(getattr(self.lp_g, "device_native", False))
-        mon_native = bool(getattr(monitor, "device_native", False)) if monitor is not None else False
-
-        lo, hi = 0, B
-        world = 1
+        # counter-based device stream (as GSM.fit: see its docstring): one `call` per draw, retries included
+        draws = DrawStream(eng, B, D, seed, rs, rng == "device" or (rng == "auto" and sampler == "cholesky"), self._zc)
+        score = scorer(eng, self.lp_g)
+        lo, hi, world = 0, B, 1
         if shard:
             assert sampler == "cholesky" and forced_samples is None, "shard=True needs the replicated z-stream"
-            from .dist import sharded_bam_update, shard_bounds
-            import torch.distributed as _dist
-            world = _dist.get_world_size(group) if _dist.is_initialized() else 1
-            rank = _dist.get_rank(group) if _dist.is_initialized() else 0
+            from .dist import sharded_bam_update, shard_bounds, voted_score, _world_rank, root_potrf as _root_potrf
+            world, rank = _world_rank(group)
             lo, hi = shard_bounds(B, world, rank)
+        collective = bool(shard) and world > 1
         mean_new, cov_new = eng.empty(D), eng.empty(D, D)
         R, R_new = eng.empty(D, D), eng.empty(D, D)
         Xbuf = eng.empty(hi - lo, D)
         flag, uflag, n_rev = eng.new_flag(), eng.new_flag(), eng.new_flag()
         use_factor = sampler == "cholesky" and forced_samples is None
         if use_factor:                      # the sampling factor of the initial covariance
-            eng.potrf(cov_t, out=R, flag=flag)
-            if eng.read_flag(flag) != 0:
-                raise ValueError("initial covariance is not positive definite")
+            initial_factor(eng, cov_t, flag, out=R)
+        progress = Progress(eng, n_rev, niter, _every(nprint, niter), verbose)
+        mon = Checkpoints(eng, monitor, self.lp, key, lambda: (mean_t, cov_t))
 
-        nevals = 1
-        if nprint > niter:
-            nprint = niter
-        every = max(1, niter // nprint) if nprint > 0 else 1
-        reverts_seen = 0
+        def attempt(i):
+            if forced_samples is not None:
+                X = eng.asarray(forced_samples[i])
+            elif sampler == "svd":
+                X = eng.asarray(_legacy_mvn(rs, eng.to_numpy(mean_t), eng.to_numpy(cov_t), B))
+            else:
+                X = eng.sample(draws.next()[lo:hi], mean_t, R, out=Xbuf)     # only this rank's rows when sharded
+            vs = voted_score(score, X, group) if collective else score(X)
+            mon.nevals += B
+            reg = regf(i)
+            if shard:
+                sharded_bam_update(eng, X, vs, mean_t, cov_t, reg, jitter, group=group, out=(mean_new, cov_new), flag=uflag)
+            else:
+                eng.bam_update(X, vs, mean_t, cov_t, reg, jitter, out=(mean_new, cov_new), flag=uflag)
+            if check_update_flag:
+                self._check_flag(eng, uflag, collective, group)
+
         i = 0
         for i in range(niter + 1):
-            if verbose and i % every == 0:
-                print(f"Iteration {i} of {niter}")
-                r = eng.read_flag(n_rev)
-                if r > reverts_seen:
-                    print(f"Bad update for covariance matrix. Revert ({r - reverts_seen} since last print)")
-                    reverts_seen = r
-            if monitor is not None and i % monitor.checkpoint == 0:
-                mc = [mean_t, cov_t] if mon_native else [eng.to_numpy(mean_t).copy(), eng.to_numpy(cov_t).copy()]
-                monitor(i, mc, self.lp, key, nevals=nevals)
-                nevals = 0
-            j = 0
-            while True:
-                try:
-                    if forced_samples is not None:
-                        X = eng.asarray(forced_samples[i])
-                    elif sampler == "svd":
-                        X = eng.asarray(_legacy_mvn(rs, eng.to_numpy(mean_t), eng.to_numpy(cov_t), B))
-                    else:
-                        if dev_rng:
-                            if ndraw % KB == 0:
-                                eng.normal_batch(KB, B, D, seed, ndraw, out=Zblk)
-                                if self._zc is not None:
-                                    Zblk[:, :, self._zc:] = 0.0          # inert coordinates of an odd-D fit (_oddpad.py)
-                            Z = Zblk[ndraw % KB]
-                            ndraw += 1
-                        else:
-                            Z = eng.normal_from_host(_host_draw(rs, B, D, self._zc))
-                            if self._zc is not None:
-                                Z[:, self._zc:] = 0.0
-                        X = eng.sample(Z[lo:hi], mean_t, R, out=Xbuf)     # only this rank's rows when sharded
-                    err = None
-                    try:
-                        vs = self.lp_g(X) if native else eng.host_score(self.lp_g, X)
-                    except Exception as e_score:            # noqa: BLE001
-                        if not (shard and world > 1):
-                            raise
-                        err, vs = e_score, None
-                    if shard and world > 1:                 # agree on failure BEFORE anybody enters the gather
-                        import torch
-                        fb = torch.tensor([0 if err is None else 1], dtype=torch.int32,
-                                          device=X.device if _is_torch(X) else "cpu")
-                        _dist.all_reduce(fb, op=_dist.ReduceOp.MAX, group=group)
-                        if int(fb.item()) != 0:             # nobody has called regf yet (bam.py:194-196 order)
-                            raise err if err is not None else RuntimeError("score evaluation failed on another rank")
-                    nevals += B
-                    reg = regf(i)
-                    if shard:
-                        sharded_bam_update(eng, X, vs, mean_t, cov_t, reg, jitter, group=group,
-                                           out=(mean_new, cov_new), flag=uflag)
-                    else:
-                        eng.bam_update(X, vs, mean_t, cov_t, reg, jitter, out=(mean_new, cov_new), flag=uflag)
-                    if check_update_flag and self._flag_raised(eng, uflag, shard and world > 1, group):
-                        raise FloatingPointError("BaM update flagged a numerical failure (device flag != 0)")
-                    break
-                except Exception as e:                      # noqa: BLE001 -- reference behaviour
-                    if j < retries:
-                        j += 1
-                        print(f"Failed with exception {e}")
-                        print(f"Trying again {j} of {retries}")
-                    else:
-                        raise e
+            progress.tick(i)
+            mon.tick(i)
+            retry(retries, attempt, i)
             if shard and root_potrf and world > 1:          # opt-in: one rank factors, the others receive
-                from .dist import root_potrf as _root_potrf
                 _root_potrf(eng, cov_new, R_new, flag, group=group)
             else:
                 eng.potrf(cov_new, out=R_new, flag=flag)
             eng.commit(flag, mean_new, cov_new, mean_t, cov_t, n_rev)
             if use_factor:
                 eng.commit(flag, mean_new, R_new, mean_t, R, None)
-
-        if monitor is not None:
-            mc = [mean_t, cov_t] if mon_native else [eng.to_numpy(mean_t).copy(), eng.to_numpy(cov_t).copy()]
-            monitor(i, mc, self.lp, key, nevals=nevals)
+        mon.final(i)
         self.n_reverts = eng.read_flag(n_rev)
-        if as_torch:
-            return mean_t, cov_t
-        return eng.to_numpy(mean_t), eng.to_numpy(cov_t)
+        return result(eng, mean_t, cov_t, as_torch)
 
     # How often the factor form absorbs the jitter it owes (bam.py:198: cov_new += jitter * I after EVERY update).  A diagonal
     # shift is not a low-rank change of a square factor: the fit carries the owed shift and every JITTER_EVERY accepted updates
@@ -342,17 +285,17 @@ class BaM:
                              "covariance): pass jitter=0, or jitter_every=0 to drop the jitter")
 
     @staticmethod
-    def _flag_raised(eng, flag, collective, group):
-        """check_update_flag: is the update's device flag set -- on ANY rank when sharded.  The replicas run the identical
-        update on identical inputs, so their flags agree; the all-reduce (MAX) makes the retry decision collective anyway
-        (advisor, round 4): a rank that retried alone would pair its next all-gather with its peers' NEXT iteration."""
+    def _check_flag(eng, flag, collective, group):
+        """check_update_flag: raises FloatingPointError (into the retry loop) when the update's device flag is set -- on ANY rank
+        when sharded.  The replicas run the identical update on identical inputs, so their flags agree; the failure vote makes
+        the retry decision collective anyway (advisor, round 4): a rank that retried alone would pair its next all-gather with
+        its peers' NEXT iteration."""
         bad = eng.read_flag(flag) != 0
         if collective:
-            import torch.distributed as _dist
-            fb = torch.tensor([1 if bad else 0], dtype=torch.int32, device=flag.device if _is_torch(flag) else "cpu")
-            _dist.all_reduce(fb, op=_dist.ReduceOp.MAX, group=group)
-            bad = int(fb.item()) != 0
-        return bad
+            from .dist import failure_vote
+            bad = failure_vote(bad, group, flag.device if _is_torch(flag) else "cpu")
+        if bad:
+            raise FloatingPointError("BaM update flagged a numerical failure (device flag != 0)")
 
     # ------------------------------------------------------------------------------
     def _fit_factor_cols(self, eng, key, regf, mean, cov, B, niter, nprint, verbose, monitor, retries, rng, as_torch,
@@ -361,126 +304,56 @@ class BaM:
         (mean[C], F[:, C]) per rank -- niter+1 iterations, reg = regf(i) per attempt, collective retries, the update's own
         2B x 2B test deciding accept / revert (counted in ``n_reverts``).  The draw stream is the one of the replicated factor
         fit (``method="factor"``), so both follow the same path.  The initial factorisation is replicated (once per fit)."""
-        import torch.distributed as _dist
-        from .dist import col_bounds, col_gather_samples, col_sharded_bam_factor_update, _all_gather, _as_torch
+        from .dist import col_assemble, col_bounds, col_gather_samples, col_sharded_bam_factor_update, voted_score, _world_rank
         D = self.D
-        world = _dist.get_world_size(group) if _dist.is_initialized() else 1
-        rank = _dist.get_rank(group) if _dist.is_initialized() else 0
+        world, rank = _world_rank(group)
         lo, hi = col_bounds(D, world, rank)
-        nc = hi - lo
         self._zc = None
         self.jitter_every_used = 0                 # (the jitter is dropped: _check_cols_args)
         self.n_absorbed = 0
-        mean_a = eng.zeros(D) if mean is None else eng.clone(mean).reshape(D)
-        cov0 = eng.eye(D) if cov is None else eng.clone(cov).reshape(D, D)
+        mean_a, cov0 = initial_state(eng, D, mean, cov)
         flag, n_rev = eng.new_flag(), eng.new_flag()
-        F0, _ = eng.potrf(cov0, flag=flag)
-        if eng.read_flag(flag) != 0:
-            raise ValueError("initial covariance is not positive definite")
-        Fc_a = eng.clone(F0[:, lo:hi])             # the owned block, D x D / P, its own leading dimension
-        del F0, cov0
-        bufs = [(mean_a, Fc_a), (eng.clone(mean_a), eng.empty(D, nc))]
+        Fc_a = eng.clone(initial_factor(eng, cov0, flag)[:, lo:hi])    # the owned block, D x D / P, its own leading dimension
+        del cov0
+        bufs = [(mean_a, Fc_a), (eng.clone(mean_a), eng.empty(D, hi - lo))]
         a = 0
-        seed = int(np.asarray(key.cpu() if _is_torch(key) else key).flatten()[-1])
-        rs = np.random.RandomState(seed)
+        seed = seed_of(key, last=True)
         assert rng in ("auto", "numpy", "device"), "rng must be 'auto', 'numpy' or 'device'"
-        dev_rng = rng != "numpy"
-        KB = 16
-        Zblk = eng.empty(KB, B, D) if dev_rng else None
-        ndraw = 0                                  # counter-based stream: one `call` per draw, retries included
-        native = bool(getattr(self.lp_g, "device_native", False))
-        mon_native = bool(getattr(monitor, "device_native", False)) if monitor is not None else False
+        draws = DrawStream(eng, B, D, seed, np.random.RandomState(seed), rng != "numpy")
+        score = scorer(eng, self.lp_g)
         self.shard_stats = {}
 
-        def assemble():
-            """(mean, F) in full on every rank: all-gather of the owned mean entries and column blocks"""
-            m_c, F_c = bufs[a]
-            if world == 1:
-                return m_c, F_c
-            recv = eng.empty(world * D, nc)
-            _all_gather(_as_torch(recv), _as_torch(F_c), group)
-            r = recv if _is_torch(recv) else _as_torch(recv).numpy()
-            F = eng.empty(D, D)
-            for p in range(world):
-                F[:, p * nc:(p + 1) * nc] = r[p * D:(p + 1) * D]
-            mrecv = eng.empty(world * nc)
-            _all_gather(_as_torch(mrecv), _as_torch(eng.clone(m_c[lo:hi])), group)
-            m = eng.clone(mrecv) if _is_torch(mrecv) else np.array(_as_torch(mrecv).numpy(), copy=True)
-            return m, F
-
         def state():
-            m, F = assemble()
-            c = eng.gram(F)
-            return [m, c] if mon_native else [eng.to_numpy(m).copy(), eng.to_numpy(c).copy()]
+            m, F = col_assemble(eng, *bufs[a], group)
+            return m, eng.gram(F)
 
-        nevals = 1
-        if nprint > niter:
-            nprint = niter
-        every = max(1, niter // nprint) if nprint > 0 else 1
-        reverts_seen = 0
+        progress = Progress(eng, n_rev, niter, _every(nprint, niter), verbose)
+        mon = Checkpoints(eng, monitor, self.lp, key, state)
+
+        def attempt(i):
+            st = {} if i == 0 else None            # the exchanges of one (successful) iteration
+            (m_c, F_c), (m_n, F_n) = bufs[a], bufs[1 - a]
+            Z = draws.next()
+            X = col_gather_samples(eng, eng.sample_cols(Z, m_c[lo:hi], F_c), group, stats=st)
+            vs = voted_score(score, X, group) if world > 1 else score(X)
+            mon.nevals += B
+            reg = regf(i)
+            col_sharded_bam_factor_update(eng, Z, X, vs, m_c, F_c, reg, group=group, out=(m_n, F_n), flag=flag, n_reverts=n_rev,
+                                          stats=st)
+            if check_update_flag:
+                self._check_flag(eng, flag, world > 1, group)
+            if st is not None:
+                self.shard_stats.update(st)
+
         for i in range(niter + 1):
-            if verbose and i % every == 0:
-                print(f"Iteration {i} of {niter}")
-                r = eng.read_flag(n_rev)
-                if r > reverts_seen:
-                    print(f"Bad update for covariance matrix. Revert ({r - reverts_seen} since last print)")
-                    reverts_seen = r
-            if monitor is not None and i % monitor.checkpoint == 0:
-                monitor(i, state(), self.lp, key, nevals=nevals)
-                nevals = 0
-            m_c, F_c = bufs[a]
-            m_n, F_n = bufs[1 - a]
-            j = 0
-            while True:
-                st = {} if i == 0 else None        # the exchanges of one (successful) iteration
-                try:
-                    if dev_rng:
-                        if ndraw % KB == 0:
-                            eng.normal_batch(KB, B, D, seed, ndraw, out=Zblk)
-                        Z = Zblk[ndraw % KB]
-                        ndraw += 1
-                    else:
-                        Z = eng.normal_from_host(_host_draw(rs, B, D, None))
-                    X = col_gather_samples(eng, eng.sample_cols(Z, m_c[lo:hi], F_c), group, stats=st)
-                    err = None
-                    try:
-                        vs = self.lp_g(X) if native else eng.host_score(self.lp_g, X)
-                    except Exception as e_score:            # noqa: BLE001
-                        if world == 1:
-                            raise
-                        err, vs = e_score, None
-                    if world > 1:                           # agree on failure BEFORE anybody enters the all-reduce
-                        fb = torch.tensor([0 if err is None else 1], dtype=torch.int32,
-                                          device=X.device if _is_torch(X) else "cpu")
-                        _dist.all_reduce(fb, op=_dist.ReduceOp.MAX, group=group)
-                        if int(fb.item()) != 0:             # nobody has called regf yet (bam.py:194-196 order)
-                            raise err if err is not None else RuntimeError("score evaluation failed on another rank")
-                    nevals += B
-                    reg = regf(i)
-                    col_sharded_bam_factor_update(eng, Z, X, vs, m_c, F_c, reg, group=group, out=(m_n, F_n), flag=flag,
-                                                  n_reverts=n_rev, stats=st)
-                    if check_update_flag and self._flag_raised(eng, flag, world > 1, group):
-                        raise FloatingPointError("BaM update flagged a numerical failure (device flag != 0)")
-                    if st is not None:
-                        self.shard_stats.update(st)
-                    break
-                except Exception as e:                      # noqa: BLE001 -- reference behaviour
-                    if j < retries:
-                        j += 1
-                        print(f"Failed with exception {e}")
-                        print(f"Trying again {j} of {retries}")
-                    else:
-                        raise e
+            progress.tick(i)
+            mon.tick(i)
+            retry(retries, attempt, i)
             a = 1 - a                   # the kernel already returned the reverted state when its test failed: accept = swap
-        if monitor is not None:
-            monitor(niter, state(), self.lp, key, nevals=nevals)
+        mon.final(niter)
         self.n_reverts = eng.read_flag(n_rev)
-        self.shard_stats["block_bytes"] = D * nc * 8
-        m, F = assemble()
-        cov_t = eng.gram(F)
-        if as_torch:
-            return m, cov_t
-        return eng.to_numpy(m), eng.to_numpy(cov_t)
+        self.shard_stats["block_bytes"] = D * (hi - lo) * 8
+        return result(eng, *state(), as_torch)
 
     # ------------------------------------------------------------------------------
     def _fit_factor(self, eng, key, regf, mean, cov, B, niter, nprint, verbose, monitor, retries, rng, as_torch,
@@ -490,30 +363,23 @@ class BaM:
         are all-gathered and every replica applies the identical factor update (dist.sharded_bam_factor_update)."""
         D = self.D
         assert 2 * B <= min(D, 256), "method='factor' needs 2*batch_size <= min(D, 256)"
-        mean_t = eng.zeros(D) if mean is None else eng.clone(mean).reshape(D)
-        cov0 = eng.eye(D) if cov is None else eng.clone(cov).reshape(D, D)
+        mean_t, cov0 = initial_state(eng, D, mean, cov)
         flag, n_rev = eng.new_flag(), eng.new_flag()
-        F, _ = eng.potrf(cov0, flag=flag)                   # one factorisation for the whole fit
-        if eng.read_flag(flag) != 0:
-            raise ValueError("initial covariance is not positive definite")
-        seed = int(np.asarray(key.cpu() if _is_torch(key) else key).flatten()[-1])
-        rs = np.random.RandomState(seed)
+        F = initial_factor(eng, cov0, flag)                 # one factorisation for the whole fit
+        seed = seed_of(key, last=True)
         assert rng in ("auto", "numpy", "device"), "rng must be 'auto', 'numpy' or 'device'"
         dev_rng = rng != "numpy"
-        KB = 16
-        Zblk = eng.empty(KB, B, D) if dev_rng else None
-        ndraw = 0
+        draws = DrawStream(eng, B, D, seed, np.random.RandomState(seed), dev_rng, self._zc)
         native = bool(getattr(self.lp_g, "device_native", False))
-        mon_native = bool(getattr(monitor, "device_native", False)) if monitor is not None else False
+        score = scorer(eng, self.lp_g)
         lo, hi, world = 0, B, 1
         if shard:
-            from .dist import sharded_bam_factor_update, shard_bounds
-            import torch.distributed as _dist
-            world = _dist.get_world_size(group) if _dist.is_initialized() else 1
-            rank = _dist.get_rank(group) if _dist.is_initialized() else 0
+            from .dist import sharded_bam_factor_update, shard_bounds, voted_score, _world_rank
+            world, rank = _world_rank(group)
             lo, hi = shard_bounds(B, world, rank)
-        mean_new, F_new, Xbuf = eng.empty(D), eng.empty(D, D), eng.empty(hi - lo, D)
-        state_bufs = [(mean_t, F), (mean_new, F_new)]
+        collective = bool(shard) and world > 1
+        bufs = [(mean_t, F), (eng.empty(D), eng.empty(D, D))]
+        Xbuf = eng.empty(hi - lo, D)
         a = 0
         # the jitter of bam.py:198 in factor form: owed = jitter * (accepted updates since the last absorption), absorbed every
         # jitter_every updates by F <- chol(F^T F + owed I) (JITTER_EVERY above); the covariance the monitor and the caller see
@@ -531,23 +397,30 @@ class BaM:
             return eng.gram(Fm)
 
         def absorb_now():
-            mu_c, F_c = state_bufs[a]
-            mu_o, F_o = state_bufs[1 - a]
+            (mu_c, F_c), (mu_o, F_o) = bufs[a], bufs[1 - a]
             eng.gram(F_c, out=Cbuf, shift_dev=eng.owed_shift(jitter, pend, n_rev, mark))
             eng.potrf(Cbuf, out=F_o, flag=pflag)            # the other buffer pair is scratch between two updates
             eng.commit(pflag, mu_c, F_o, mu_o, F_c, None)   # F <- R iff the factorisation succeeded (F^T F + owed I is positive
             self.n_absorbed += 1                            # definite unless the state itself is not finite: then F stays)
 
-        def state():
-            c = cov_of(state_bufs[a][1])
-            m = state_bufs[a][0]
-            return [m, c] if mon_native else [eng.to_numpy(m).copy(), eng.to_numpy(c).copy()]
+        progress = Progress(eng, n_rev, niter, _every(nprint, niter), verbose)
+        mon = Checkpoints(eng, monitor, self.lp, key, lambda: (bufs[a][0], cov_of(bufs[a][1])))
 
-        nevals = 1
-        if nprint > niter:
-            nprint = niter
-        every = max(1, niter // nprint) if nprint > 0 else 1
-        reverts_seen = 0
+        def attempt(i):
+            (mu_a, F_a), (mu_b, F_b) = bufs[a], bufs[1 - a]
+            Z = draws.next()
+            X = eng.sample(Z[lo:hi], mu_a, F_a, out=Xbuf)          # only this rank's rows when sharded
+            vs = voted_score(score, X, group) if collective else score(X)
+            mon.nevals += B
+            reg = regf(i)
+            if shard:
+                sharded_bam_factor_update(eng, Z, X, vs, mu_a, F_a, reg, group=group, out=(mu_b, F_b), flag=flag,
+                                          n_reverts=n_rev)
+            else:
+                eng.bam_factor_update(Z, X, vs, mu_a, F_a, reg, out=(mu_b, F_b), flag=flag, n_reverts=n_rev)
+            if check_update_flag:
+                self._check_flag(eng, flag, collective, group)
+
         # Blocks of KB iterations replayed as ONE hipGraph (as GSM.fit): the launches must all be capturable (a `graph_safe`
         # device score, the counter-based draw stream, no collective, no per-iteration flag read) and the one number that changes
         # between iterations -- reg = regf(i), evaluated on the host by the reference (bam.py:196) -- is read by the kernels from
@@ -562,149 +435,67 @@ class BaM:
         # from an idle device.  It is kept for callers whose host is slower or shared.
         use_graph = (graph is True and dev_rng and native and not shard and not absorb
                      and not check_update_flag and niter + 1 >= 3 * KB and bool(getattr(self.lp_g, "graph_safe", False)))
-        takes_out = False
-        if native:
-            import inspect
-            try:
-                takes_out = "out" in inspect.signature(self.lp_g).parameters
-            except (TypeError, ValueError):
-                takes_out = False
         self.graph_replays = 0
         self.graph_fallback = None
-        gstate = {"graph": None}
         if use_graph:
-            import torch
-            ctr = [torch.zeros(1, dtype=torch.int64, device=Zblk.device) for _ in range(2)]
-            reg_blk = torch.zeros(KB, dtype=torch.float64, device=Zblk.device)
+            out_ok = takes_out(self.lp_g)
+            ctr = [torch.zeros(1, dtype=torch.int64, device=draws.block.device) for _ in range(2)]
+            reg_blk = torch.zeros(KB, dtype=torch.float64, device=draws.block.device)
             reg_host = [torch.zeros(KB, dtype=torch.float64).pin_memory() for _ in range(4)]
             reg_done = [None] * 4
             Gbuf = eng.empty(hi - lo, D)
 
-        def graph_block(i_first):
-            """KB iterations (KB even: the ping-pong state ends where it started) as one replayed graph; the draw counter and
-            the regulariser table live on the device."""
-            if gstate["graph"] is None:
-                side = torch.cuda.Stream()
-                side.wait_stream(torch.cuda.current_stream())
-                g = torch.cuda.CUDAGraph()
+            def capture():
+                """KB iterations (KB even: the ping-pong state ends where it started); the draw counter and the regulariser
+                table live on the device."""
                 try:
-                    with torch.cuda.stream(side):
-                        torch.cuda.synchronize()
-                        with torch.cuda.graph(g, stream=side):
-                            for half in range(2):
-                                h0 = half * (KB // 2)
-                                eng.normal_batch(KB // 2, B, D, seed, 0, out=Zblk[h0:h0 + KB // 2], call_in=ctr[half],
-                                                 call_out=ctr[1 - half])
-                                if self._zc is not None:
-                                    Zblk[h0:h0 + KB // 2, :, self._zc:] = 0.0
-                                for k in range(KB // 2):
-                                    eng.bam_reg_source(reg_blk[h0 + k:h0 + k + 1])
-                                    mu_a, F_a = state_bufs[k & 1]
-                                    mu_b, F_b = state_bufs[1 - (k & 1)]
-                                    Zk = Zblk[h0 + k]
-                                    Xk = eng.sample(Zk, mu_a, F_a, out=Xbuf)
-                                    vk = self.lp_g(Xk, out=Gbuf) if takes_out else self.lp_g(Xk)
-                                    eng.bam_factor_update(Zk, Xk, vk, mu_a, F_a, 1.0, out=(mu_b, F_b), flag=flag, n_reverts=n_rev)   # (reg: ignored, word k is read)
+                    for half in range(2):
+                        h0 = half * (KB // 2)
+                        Zh = draws.block[h0:h0 + KB // 2]
+                        eng.normal_batch(KB // 2, B, D, seed, 0, out=Zh, call_in=ctr[half], call_out=ctr[1 - half])
+                        draws.zero(Zh)
+                        for k in range(KB // 2):
+                            eng.bam_reg_source(reg_blk[h0 + k:h0 + k + 1])
+                            (mu_a, F_a), (mu_b, F_b) = bufs[k & 1], bufs[1 - (k & 1)]
+                            Xk = eng.sample(Zh[k], mu_a, F_a, out=Xbuf)
+                            vk = self.lp_g(Xk, out=Gbuf) if out_ok else self.lp_g(Xk)
+                            eng.bam_factor_update(Zh[k], Xk, vk, mu_a, F_a, 1.0, out=(mu_b, F_b), flag=flag, n_reverts=n_rev)   # (reg: ignored, word k is read)
                 finally:
                     eng.bam_reg_source(None)
-                torch.cuda.current_stream().wait_stream(side)
-                gstate["graph"] = g
-            slot = self.graph_replays % 4
-            if reg_done[slot] is not None:
-                reg_done[slot].synchronize()                    # the copy that last read this pinned slot has run
-            for k in range(KB):
-                rk = float(regf(i_first + k))
-                if not rk > 0.0:                                 # (what the by-value entry point checks on the host)
-                    raise ValueError(f"BaM.fit: regf({i_first + k}) = {rk}: reg must be positive")
-                reg_host[slot][k] = rk
-            reg_blk.copy_(reg_host[slot], non_blocking=True)
-            reg_done[slot] = torch.cuda.Event()
-            reg_done[slot].record()
-            ctr[0].fill_(ndraw)
-            gstate["graph"].replay()
+
+            def prepare(i_first):
+                slot = self.graph_replays % 4
+                if reg_done[slot] is not None:
+                    reg_done[slot].synchronize()                # the copy that last read this pinned slot has run
+                for k in range(KB):
+                    rk = float(regf(i_first + k))
+                    if not rk > 0.0:                             # (what the by-value entry point checks on the host)
+                        raise ValueError(f"BaM.fit: regf({i_first + k}) = {rk}: reg must be positive")
+                    reg_host[slot][k] = rk
+                reg_blk.copy_(reg_host[slot], non_blocking=True)
+                reg_done[slot] = torch.cuda.Event()
+                reg_done[slot].record()
+                ctr[0].fill_(draws.call)
+
+            graph = GraphBlock(self, "BaM.fit", capture)
 
         i = 0
         while i <= niter:
             blk_end = min(i + KB, niter + 1)
-            eventful = any((verbose and j % every == 0) or (monitor is not None and j % monitor.checkpoint == 0)
-                           for j in range(i, blk_end))
             # (the first block always runs eagerly: every kernel has been launched, and the context sized, before a capture)
-            if use_graph and i > 0 and a == 0 and not eventful and blk_end - i == KB and ndraw % KB == 0:
-                try:
-                    graph_block(i)
-                except Exception as exc:                        # noqa: BLE001 -- capture unsupported here: stay eager
-                    if gstate["graph"] is not None:
-                        raise
-                    import warnings
-                    warnings.warn(f"BaM.fit: hipGraph capture of an iteration block failed ({type(exc).__name__}: {exc}); "
-                                  "the fit continues with eager launches (same numbers, more launch overhead)", RuntimeWarning)
-                    self.graph_fallback = exc
+            if (use_graph and i > 0 and a == 0 and blk_end - i == KB and draws.call % KB == 0
+                    and not eventful(progress, mon, i, blk_end)):
+                if graph.run(lambda: prepare(i)):
+                    draws.call += KB
+                    mon.nevals += B * KB
+                    i = blk_end
+                else:                                           # capture unsupported here: stay eager for the rest of the fit
                     use_graph = False
-                    torch.cuda.synchronize()
-                    continue
-                self.graph_replays += 1
-                ndraw += KB
-                nevals += B * KB
-                i = blk_end
                 continue
             for i in range(i, blk_end):
-                if verbose and i % every == 0:
-                    print(f"Iteration {i} of {niter}")
-                    r = eng.read_flag(n_rev)
-                    if r > reverts_seen:
-                        print(f"Bad update for covariance matrix. Revert ({r - reverts_seen} since last print)")
-                        reverts_seen = r
-                if monitor is not None and i % monitor.checkpoint == 0:
-                    monitor(i, state(), self.lp, key, nevals=nevals)
-                    nevals = 0
-                mu_a, F_a = state_bufs[a]
-                mu_b, F_b = state_bufs[1 - a]
-                j = 0
-                while True:
-                    try:
-                        if dev_rng:
-                            if ndraw % KB == 0:
-                                eng.normal_batch(KB, B, D, seed, ndraw, out=Zblk)
-                                if self._zc is not None:
-                                    Zblk[:, :, self._zc:] = 0.0              # inert coordinates of an odd-D fit (_oddpad.py)
-                            Z = Zblk[ndraw % KB]
-                            ndraw += 1
-                        else:
-                            Z = eng.normal_from_host(_host_draw(rs, B, D, self._zc))
-                            if self._zc is not None:
-                                Z[:, self._zc:] = 0.0
-                        X = eng.sample(Z[lo:hi], mu_a, F_a, out=Xbuf)          # only this rank's rows when sharded
-                        err = None
-                        try:
-                            vs = self.lp_g(X) if native else eng.host_score(self.lp_g, X)
-                        except Exception as e_score:            # noqa: BLE001
-                            if not (shard and world > 1):
-                                raise
-                            err, vs = e_score, None
-                        if shard and world > 1:                 # agree on failure BEFORE anybody enters the gather (as the dense fit)
-                            import torch
-                            fb = torch.tensor([0 if err is None else 1], dtype=torch.int32,
-                                              device=X.device if _is_torch(X) else "cpu")
-                            _dist.all_reduce(fb, op=_dist.ReduceOp.MAX, group=group)
-                            if int(fb.item()) != 0:
-                                raise err if err is not None else RuntimeError("score evaluation failed on another rank")
-                        nevals += B
-                        reg = regf(i)
-                        if shard:
-                            sharded_bam_factor_update(eng, Z, X, vs, mu_a, F_a, reg, group=group, out=(mu_b, F_b), flag=flag,
-                                                      n_reverts=n_rev)
-                        else:
-                            eng.bam_factor_update(Z, X, vs, mu_a, F_a, reg, out=(mu_b, F_b), flag=flag, n_reverts=n_rev)
-                        if check_update_flag and self._flag_raised(eng, flag, shard and world > 1, group):
-                            raise FloatingPointError("BaM update flagged a numerical failure (device flag != 0)")
-                        break
-                    except Exception as e:                      # noqa: BLE001 -- reference behaviour
-                        if j < retries:
-                            j += 1
-                            print(f"Failed with exception {e}")
-                            print(f"Trying again {j} of {retries}")
-                        else:
-                            raise e
+                progress.tick(i)
+                mon.tick(i)
+                retry(retries, attempt, i)
                 a = 1 - a               # the kernel already returned the reverted state when its test failed: accept = swap
                 if absorb:
                     pend += 1
@@ -712,12 +503,6 @@ class BaM:
                         absorb_now()
                         pend = 0
             i = blk_end
-        i = niter
-        if monitor is not None:
-            monitor(i, state(), self.lp, key, nevals=nevals)
+        mon.final(niter)
         self.n_reverts = eng.read_flag(n_rev)
-        mean_t, F = state_bufs[a]
-        cov_t = cov_of(F)
-        if as_torch:
-            return mean_t, cov_t
-        return eng.to_numpy(mean_t), eng.to_numpy(cov_t)
+        return result(eng, bufs[a][0], cov_of(bufs[a][1]), as_torch)

@@ -7,11 +7,10 @@ HIP kernel call through the engine (``engine.py`` -> C ABI -> ``csrc/``).
 import numpy as np
 import torch
 
+from . import _oddpad
+from ._fitloop import (KB, Checkpoints, DrawStream, GraphBlock, Progress, _is_torch, _legacy_mvn, eventful, initial_factor,
+                       initial_state, result, scorer, seed_of, takes_out)
 from .engine import get_engine
-
-
-def _is_torch(x):
-    return isinstance(x, torch.Tensor)
 
 
 def gsm_update(samples, vs, mu0, S0, engine=None, assume_symmetric=None):
@@ -57,24 +56,9 @@ def gsm_update(samples, vs, mu0, S0, engine=None, assume_symmetric=None):
     return (mu, S) if want_torch else (eng.to_numpy(mu), eng.to_numpy(S))
 
 
-def _legacy_mvn(rs, mean, cov, size):
-    """Compat sampler: the exact stream of ``np.random.multivariate_normal`` after
-    ``np.random.seed(key)`` (gsmvi/gsm_numpy.py:105,116): z from MT19937, SVD factor of cov."""
-    D = mean.shape[0]
-    z = rs.standard_normal((size, D))
-    _, s, vt = np.linalg.svd(cov)
-    return mean + z @ (np.sqrt(s)[:, None] * vt)
-
-
-def _host_draw(rs, B, D, zc):
-    """(B, D) standard normals from the host stream (rng="numpy": the reference's z-stream, gsm_numpy.py:105,116).  In the padded
-    fit of an odd-D problem (zc = the literal D, _oddpad.py) the stream is drawn at the LITERAL width and the inert columns are
-    zeros, so a seed gives the same draws as the literal-D problem (round-5 advice: it drew (B, D + 1) and shifted the stream)."""
-    if zc is None:
-        return rs.standard_normal((B, D))
-    z = np.zeros((B, D))
-    z[:, :zc] = rs.standard_normal((B, zc))
-    return z
+def _every(nprint, niter):
+    """print cadence: ``nprint`` clamped to [1, niter] (bam.py:177 guard; the reference raises ZeroDivisionError at 0)"""
+    return max(1, niter // max(1, min(int(nprint), int(niter)))) if niter > 0 else 1
 
 
 class GSM:
@@ -170,26 +154,18 @@ class GSM:
                     1e10) is ALSO reverted in factor form (tests/test_gpu_factor.py::test_g4_...), state kept bit
                     for bit.
         """
-        D_, B_ = self.D, int(batch_size)
-        from . import _oddpad
-        eng0 = self._engine if self._engine is not None else get_engine()
-        if _zero_cols_from is None and _oddpad.applies(eng0, D_, sampler, forced_samples):
+        D, B = self.D, int(batch_size)
+        eng = self._engine if self._engine is not None else get_engine()
+        if _zero_cols_from is None and _oddpad.applies(eng, D, sampler, forced_samples):
             # odd D: the (D + 1)-dimensional problem with an inert last coordinate runs on the tuned kernels (_oddpad.py)
             if method == "auto":
-                nmax = 256 if D_ >= 1024 else 128
-                method = "factor" if 2 * B_ <= min(D_, nmax) else "dense"
-            inner = GSM(D_ + 1, self.lp, _oddpad.wrap_score(eng0, self.lp_g, D_), engine=eng0)
-            mp, cp = inner.fit(key, mean=_oddpad.pad_vec(eng0, mean, D_), cov=_oddpad.pad_mat(eng0, cov, D_),
-                               batch_size=batch_size, niter=niter, nprint=nprint, verbose=verbose,
-                               check_goodness=check_goodness, monitor=_oddpad.wrap_monitor(monitor, self.lp, D_),
-                               sampler=sampler, rng=rng, as_torch=True, method=method, shard=shard, group=group, graph=graph,
-                               root_potrf=root_potrf, _zero_cols_from=D_)
-            for a in ("method_used", "n_reverts", "graph_replays", "graph_fallback"):
-                if hasattr(inner, a):
-                    setattr(self, a, getattr(inner, a))
-            self.padded_dim = D_ + 1
-            mean_o, cov_o = mp[:D_].contiguous(), cp[:D_, :D_].contiguous()
-            return (mean_o, cov_o) if as_torch else (eng0.to_numpy(mean_o), eng0.to_numpy(cov_o))
+                nmax = 256 if D >= 1024 else 128
+                method = "factor" if 2 * B <= min(D, nmax) else "dense"
+            inner = GSM(D + 1, self.lp, _oddpad.wrap_score(eng, self.lp_g, D), engine=eng)
+            return _oddpad.fit_padded(self, inner, (key,), dict(
+                batch_size=batch_size, niter=niter, nprint=nprint, verbose=verbose, check_goodness=check_goodness,
+                sampler=sampler, rng=rng, method=method, shard=shard, group=group, graph=graph, root_potrf=root_potrf),
+                mean, cov, monitor, as_torch)
         self._zc = _zero_cols_from
         if shard == "cols" and method == "auto":
             method = "factor"
@@ -197,32 +173,29 @@ class GSM:
             # 2B <= 128: always (the measured range of rounds 2-4).  128 < 2B <= 256 (two-level chain): where the dense loop's
             # O(D^3) Cholesky costs more than the whole factor update -- measured at (1024, 128): factor update 271 us against
             # 330 us for the Cholesky alone; at D = 512 the dense iteration (165 + ~40 us) still wins -- so from D = 1024 on.
-            nmax = 256 if D_ >= 1024 else 128
+            nmax = 256 if D >= 1024 else 128
             method = "factor" if (sampler == "cholesky" and forced_samples is None
-                                  and 2 * B_ <= min(D_, nmax)) else "dense"
+                                  and 2 * B <= min(D, nmax)) else "dense"
         if shard == "cols":
             assert method in ("auto", "factor") and sampler == "cholesky" and forced_samples is None, \
                 "shard='cols' is the column-sharded FACTOR form (device sampler, no forced samples)"
             self.method_used = "factor"
-            return self._fit_factor_cols(key, mean, cov, batch_size, niter, nprint, verbose, monitor, rng, as_torch, group)
+            return self._fit_factor_cols(eng, key, mean, cov, B, niter, nprint, verbose, monitor, rng, as_torch, group)
         self.method_used = method
         if method == "factor":
-            return self._fit_factor(key, mean, cov, batch_size, niter, nprint, verbose, monitor, rng, as_torch,
-                                    shard, group, graph)
+            return self._fit_factor(eng, key, mean, cov, B, niter, nprint, verbose, monitor, rng, as_torch, shard, group, graph)
         assert method == "dense", "method must be 'auto', 'dense' or 'factor'"
-        eng = self._engine if self._engine is not None else get_engine()
-        D, B = self.D, int(batch_size)
-        mean_t = eng.zeros(D) if mean is None else eng.clone(mean).reshape(D)
-        cov_t = eng.eye(D) if cov is None else eng.clone(cov).reshape(D, D)
-        nevals = 1
-        seed = int(key) if not _is_torch(key) else int(key.flatten()[0])
+        mean_t, cov_t = initial_state(eng, D, mean, cov)
+        seed = seed_of(key, last=False)
         rs = np.random.RandomState(seed)
         assert rng in ("auto", "numpy", "device"), "rng must be 'auto', 'numpy' or 'device'"
-        dev_rng = rng == "device" or (rng == "auto" and sampler == "cholesky")
-        KB = 16
-        Zblk = eng.empty(KB, B, D) if dev_rng else None
-        native = bool(getattr(self.lp_g, "device_native", False))
-        mon_native = bool(getattr(monitor, "device_native", False)) if monitor is not None else False
+        draws = DrawStream(eng, B, D, seed, rs, rng == "device" or (rng == "auto" and sampler == "cholesky"), self._zc,
+                           limit=niter + 1)
+        score = scorer(eng, self.lp_g)
+        lo, hi = 0, B
+        if shard:
+            from .dist import sharded_gsm_update, shard_bounds, _world_rank, root_potrf as _root_potrf
+            lo, hi = shard_bounds(B, *_world_rank(group))
 
         # working buffers (the user's arrays are never aliased or mutated)
         mean_new, cov_new = eng.empty(D), eng.empty(D, D)
@@ -231,221 +204,111 @@ class GSM:
         flag, n_rev = eng.new_flag(), eng.new_flag()
         use_factor = sampler == "cholesky" and forced_samples is None
         if use_factor:                      # the sampling factor of the initial covariance
-            eng.potrf(cov_t, out=R, flag=flag)
-            if eng.read_flag(flag) != 0:
-                raise ValueError("initial covariance is not positive definite")
-
-        nprint = max(1, min(int(nprint), int(niter))) if niter > 0 else 1   # bam.py:177 guard
-        every = max(1, niter // nprint) if niter > 0 else 1
-        reverts_seen = 0
+            initial_factor(eng, cov_t, flag, out=R)
+        progress = Progress(eng, n_rev, niter, _every(nprint, niter), verbose)
+        mon = Checkpoints(eng, monitor, self.lp, key, lambda: (mean_t, cov_t))
         i = 0
         for i in range(niter + 1):
-            if verbose and i % every == 0:
-                print(f"Iteration {i} of {niter}")
-                r = eng.read_flag(n_rev)
-                if r > reverts_seen:
-                    print(f"Bad update for covariance matrix. Revert ({r - reverts_seen} since last print)")
-                    reverts_seen = r
-            if monitor is not None and i % monitor.checkpoint == 0:
-                mc = [mean_t, cov_t] if mon_native else [eng.to_numpy(mean_t).copy(), eng.to_numpy(cov_t).copy()]
-                monitor(i, mc, self.lp, key, nevals=nevals)
-                nevals = 0
-
+            progress.tick(i)
+            mon.tick(i)
             if forced_samples is not None:
                 X = eng.asarray(forced_samples[i])
             elif sampler == "svd":
                 X = eng.asarray(_legacy_mvn(rs, eng.to_numpy(mean_t), eng.to_numpy(cov_t), B))
             else:
-                if dev_rng:                                     # a block of KB iterations' draws per launch (same stream)
-                    if i % KB == 0:
-                        eng.normal_batch(min(KB, niter + 1 - i), B, D, seed, i, out=Zblk[:min(KB, niter + 1 - i)])
-                        if self._zc is not None:
-                            Zblk[:, :, self._zc:] = 0.0                  # inert coordinates of an odd-D fit (_oddpad.py)
-                    Z = Zblk[i % KB]
-                else:
-                    Z = eng.normal_from_host(_host_draw(rs, B, D, self._zc))
-                    if self._zc is not None:
-                        Z[:, self._zc:] = 0.0
-                X = eng.sample(Z, mean_t, R, out=Xbuf)
+                X = eng.sample(draws.next(), mean_t, R, out=Xbuf)
             if shard:
-                from .dist import sharded_gsm_update, shard_bounds
-                import torch.distributed as _dist
-                world = _dist.get_world_size(group) if _dist.is_initialized() else 1
-                rank = _dist.get_rank(group) if _dist.is_initialized() else 0
-                lo, hi = shard_bounds(B, world, rank)
                 Xl = X[lo:hi]
-                vl = self.lp_g(Xl) if native else eng.host_score(self.lp_g, Xl)
-                sharded_gsm_update(eng, Xl, vl, mean_t, cov_t, group=group, out=(mean_new, cov_new))
+                sharded_gsm_update(eng, Xl, score(Xl), mean_t, cov_t, group=group, out=(mean_new, cov_new))
             else:
-                vs = self.lp_g(X) if native else eng.host_score(self.lp_g, X)
-                eng.gsm_update(X, vs, mean_t, cov_t, out=(mean_new, cov_new))
-            nevals += B
+                eng.gsm_update(X, score(X), mean_t, cov_t, out=(mean_new, cov_new))
+            mon.nevals += B
             if shard and root_potrf:                              # opt-in: one rank factors, the others receive
-                from .dist import root_potrf as _root_potrf
                 _root_potrf(eng, cov_new, R_new, flag, group=group)
             else:
                 eng.potrf(cov_new, out=R_new, flag=flag)          # _check_goodness, :121,:132-146
             eng.commit(flag, mean_new, cov_new, mean_t, cov_t, n_rev)
             if use_factor:
                 eng.commit(flag, mean_new, R_new, mean_t, R, None)
-
-        if verbose:
-            r = eng.read_flag(n_rev)
-            if r > reverts_seen:
-                print(f"Bad update for covariance matrix. Revert ({r - reverts_seen} since last print)")
-        if monitor is not None:
-            mc = [mean_t, cov_t] if mon_native else [eng.to_numpy(mean_t).copy(), eng.to_numpy(cov_t).copy()]
-            monitor(i, mc, self.lp, key, nevals=nevals)
+        progress.flush()
+        mon.final(i)
         self.n_reverts = eng.read_flag(n_rev)
-        if as_torch:
-            return mean_t, cov_t
-        return eng.to_numpy(mean_t), eng.to_numpy(cov_t)
+        return result(eng, mean_t, cov_t, as_torch)
 
     # ------------------------------------------------------------------------------
-    def _fit_factor_cols(self, key, mean, cov, batch_size, niter, nprint, verbose, monitor, rng, as_torch, group=None):
+    def _fit_factor_cols(self, eng, key, mean, cov, B, niter, nprint, verbose, monitor, rng, as_torch, group=None):
         """Column-sharded factor-form fit (see ``fit(shard="cols")``): the loop of gsm_numpy.py:77-129 on the state
         (mean[C], F[:, C]) per rank.  Per iteration and rank: one pass over the block for the sample slice, one for the partial
         W, two for the update (read + write) and the V F product -- 32 D (D / P) bytes --, one all-gather of B D / P doubles and
         one all-reduce of B D doubles; the 2B x 2B chain and the score evaluation are replicated.  The initial factorisation is
         replicated too (once per fit); the covariance is assembled only for the monitor and the return value."""
-        import torch.distributed as _dist
-        from .dist import col_bounds, col_gather_samples, col_sharded_gsm_factor_update, _all_gather, _as_torch
-        eng = self._engine if self._engine is not None else get_engine()
-        D, B = self.D, int(batch_size)
+        from .dist import col_assemble, col_bounds, col_gather_samples, col_sharded_gsm_factor_update, _world_rank
+        D = self.D
         assert 2 * B <= min(D, 256), "the factor form needs 2*batch_size <= min(D, 256)"
-        world = _dist.get_world_size(group) if _dist.is_initialized() else 1
-        rank = _dist.get_rank(group) if _dist.is_initialized() else 0
-        lo, hi = col_bounds(D, world, rank)
-        nc = hi - lo
-        mean_a = eng.zeros(D) if mean is None else eng.clone(mean).reshape(D)
-        cov0 = eng.eye(D) if cov is None else eng.clone(cov).reshape(D, D)
+        lo, hi = col_bounds(D, *_world_rank(group))
+        mean_a, cov0 = initial_state(eng, D, mean, cov)
         flag, n_rev = eng.new_flag(), eng.new_flag()
-        F0, _ = eng.potrf(cov0, flag=flag)
-        if eng.read_flag(flag) != 0:
-            raise ValueError("initial covariance is not positive definite")
-        Fc_a = eng.clone(F0[:, lo:hi])                      # the owned block, D x D / P, its own leading dimension
-        del F0, cov0
-        mean_b, Fc_b = eng.clone(mean_a), eng.empty(D, nc)
-        bufs = [(mean_a, Fc_a), (mean_b, Fc_b)]
+        Fc_a = eng.clone(initial_factor(eng, cov0, flag)[:, lo:hi])    # the owned block, D x D / P, its own leading dimension
+        del cov0
+        bufs = [(mean_a, Fc_a), (eng.clone(mean_a), eng.empty(D, hi - lo))]
         a = 0
-        seed = int(key) if not _is_torch(key) else int(key.flatten()[0])
-        rs = np.random.RandomState(seed)
+        seed = seed_of(key, last=False)
         assert rng in ("auto", "numpy", "device"), "rng must be 'auto', 'numpy' or 'device'"
-        dev_rng = rng != "numpy"
-        native = bool(getattr(self.lp_g, "device_native", False))
-        mon_native = bool(getattr(monitor, "device_native", False)) if monitor is not None else False
-        KB = 16
-        Zblk = eng.empty(KB, B, D) if dev_rng else None
+        draws = DrawStream(eng, B, D, seed, np.random.RandomState(seed), rng != "numpy", limit=niter + 1)
+        score = scorer(eng, self.lp_g)
         self.shard_stats = {}
 
-        def assemble():
-            """(mean, F) in full on every rank: all-gather of the owned mean entries and column blocks"""
-            m_c, F_c = bufs[a]
-            if world == 1:
-                return m_c, F_c
-            recv = eng.empty(world * D, nc)
-            _all_gather(_as_torch(recv), _as_torch(F_c), group)
-            r = recv if _is_torch(recv) else _as_torch(recv).numpy()
-            F = eng.empty(D, D)
-            for p in range(world):
-                F[:, p * nc:(p + 1) * nc] = r[p * D:(p + 1) * D]
-            mrecv = eng.empty(world * nc)
-            _all_gather(_as_torch(mrecv), _as_torch(eng.clone(m_c[lo:hi])), group)
-            m = eng.clone(mrecv) if _is_torch(mrecv) else np.array(_as_torch(mrecv).numpy(), copy=True)
-            return m, F
-
         def state():
-            m, F = assemble()
-            c = eng.gram(F)
-            return [m, c] if mon_native else [eng.to_numpy(m).copy(), eng.to_numpy(c).copy()]
+            m, F = col_assemble(eng, *bufs[a], group)
+            return m, eng.gram(F)
 
-        nevals = 1
-        nprint = max(1, min(int(nprint), int(niter))) if niter > 0 else 1
-        every = max(1, niter // nprint) if niter > 0 else 1
-        reverts_seen = 0
+        progress = Progress(eng, n_rev, niter, _every(nprint, niter), verbose)
+        mon = Checkpoints(eng, monitor, self.lp, key, state)
         for i in range(niter + 1):
-            if verbose and i % every == 0:
-                print(f"Iteration {i} of {niter}")
-                r = eng.read_flag(n_rev)
-                if r > reverts_seen:
-                    print(f"Bad update for covariance matrix. Revert ({r - reverts_seen} since last print)")
-                    reverts_seen = r
-            if monitor is not None and i % monitor.checkpoint == 0:
-                monitor(i, state(), self.lp, key, nevals=nevals)
-                nevals = 0
-            if dev_rng:
-                if i % KB == 0:
-                    eng.normal_batch(min(KB, niter + 1 - i), B, D, seed, i, out=Zblk[:min(KB, niter + 1 - i)])
-                Z = Zblk[i % KB]
-            else:
-                Z = eng.normal_from_host(rs.standard_normal((B, D)))
-            m_c, F_c = bufs[a]
-            m_n, F_n = bufs[1 - a]
-            Xc = eng.sample_cols(Z, m_c[lo:hi], F_c)
-            X = col_gather_samples(eng, Xc, group, stats=self.shard_stats if i == 0 else None)
-            vs = self.lp_g(X) if native else eng.host_score(self.lp_g, X)
-            col_sharded_gsm_factor_update(eng, Z, X, vs, m_c, F_c, group=group, out=(m_n, F_n), flag=flag, n_reverts=n_rev,
-                                          stats=self.shard_stats if i == 0 else None)
-            nevals += B
+            progress.tick(i)
+            mon.tick(i)
+            Z = draws.next()
+            (m_c, F_c), (m_n, F_n) = bufs[a], bufs[1 - a]
+            st = self.shard_stats if i == 0 else None
+            X = col_gather_samples(eng, eng.sample_cols(Z, m_c[lo:hi], F_c), group, stats=st)
+            col_sharded_gsm_factor_update(eng, Z, X, score(X), m_c, F_c, group=group, out=(m_n, F_n), flag=flag,
+                                          n_reverts=n_rev, stats=st)
+            mon.nevals += B
             a = 1 - a
-        if verbose:
-            r = eng.read_flag(n_rev)
-            if r > reverts_seen:
-                print(f"Bad update for covariance matrix. Revert ({r - reverts_seen} since last print)")
-        if monitor is not None:
-            monitor(niter, state(), self.lp, key, nevals=nevals)
+        progress.flush()
+        mon.final(niter)
         self.n_reverts = eng.read_flag(n_rev)
-        self.shard_stats["block_bytes"] = D * nc * 8
-        m, F = assemble()
-        cov_t = eng.gram(F)
-        if as_torch:
-            return m, cov_t
-        return eng.to_numpy(m), eng.to_numpy(cov_t)
+        self.shard_stats["block_bytes"] = D * (hi - lo) * 8
+        return result(eng, *state(), as_torch)
 
     # ------------------------------------------------------------------------------
-    def _fit_factor(self, key, mean, cov, batch_size, niter, nprint, verbose, monitor, rng, as_torch, shard=False,
-                    group=None, graph=None):
+    def _fit_factor(self, eng, key, mean, cov, B, niter, nprint, verbose, monitor, rng, as_torch, shard=False, group=None,
+                    graph=None):
         """Factor-form fit loop (see ``fit(method="factor")``): same driver logic as gsm_numpy.py:77-129,
         state (mean, F) with cov = F^T F materialised only for the monitor and the return value.
         ``shard=True``: every rank draws the same Z, samples and scores only its batch_size/world rows, and the
         per-sample records are all-gathered (dist.sharded_gsm_factor_update); replicas stay identical."""
-        eng = self._engine if self._engine is not None else get_engine()
-        D, B = self.D, int(batch_size)
+        D = self.D
         assert 2 * B <= min(D, 256), "method='factor' needs 2*batch_size <= min(D, 256)"
-        mean_t = eng.zeros(D) if mean is None else eng.clone(mean).reshape(D)
-        cov0 = eng.eye(D) if cov is None else eng.clone(cov).reshape(D, D)
+        mean_t, cov0 = initial_state(eng, D, mean, cov)
         flag, n_rev = eng.new_flag(), eng.new_flag()
-        F, _ = eng.potrf(cov0, flag=flag)                   # one factorisation for the whole fit
-        if eng.read_flag(flag) != 0:
-            raise ValueError("initial covariance is not positive definite")
-        seed = int(key) if not _is_torch(key) else int(key.flatten()[0])
+        F = initial_factor(eng, cov0, flag)                 # one factorisation for the whole fit
+        seed = seed_of(key, last=False)
         rs = np.random.RandomState(seed)
         assert rng in ("auto", "numpy", "device"), "rng must be 'auto', 'numpy' or 'device'"
         dev_rng = rng != "numpy"                            # the factor form always samples with its own factor
-        Zbuf = eng.empty(B, D) if dev_rng else None
         native = bool(getattr(self.lp_g, "device_native", False))
-        mon_native = bool(getattr(monitor, "device_native", False)) if monitor is not None else False
         lo, hi = 0, B
         if shard:
-            from .dist import sharded_gsm_factor_update, shard_bounds
-            import torch.distributed as _dist
-            world = _dist.get_world_size(group) if _dist.is_initialized() else 1
-            rank = _dist.get_rank(group) if _dist.is_initialized() else 0
-            lo, hi = shard_bounds(B, world, rank)
-        mean_new, F_new, Xbuf = eng.empty(D), eng.empty(D, D), eng.empty(hi - lo, D)
-
-        def state():
-            c = eng.gram(F)
-            return [mean_t, c] if mon_native else [eng.to_numpy(mean_t).copy(), eng.to_numpy(c).copy()]
-
-        nevals = 1
-        nprint = max(1, min(int(nprint), int(niter))) if niter > 0 else 1
-        every = max(1, niter // nprint) if niter > 0 else 1
-        reverts_seen = 0
-        # The draw stream does not depend on the state: the device draws come a BLOCK of KB iterations per launch.
-        KB = 16
-        Zblk = eng.empty(KB, B, D) if dev_rng else None
+            from .dist import sharded_gsm_factor_update, shard_bounds, _world_rank
+            lo, hi = shard_bounds(B, *_world_rank(group))
+        bufs = [(mean_t, F), (eng.empty(D), eng.empty(D, D))]
+        Xbuf = eng.empty(hi - lo, D)
+        draws = DrawStream(eng, B, D, seed, rs, dev_rng, self._zc, limit=niter + 1)
         Gbuf = eng.empty(hi - lo, D)
+        a = 0                                                   # which buffer pair holds the current state
+        progress = Progress(eng, n_rev, niter, _every(nprint, niter), verbose)
+        mon = Checkpoints(eng, monitor, self.lp, key, lambda: (bufs[a][0], eng.gram(bufs[a][1])))
         # A block of KB iterations whose launches are all capturable (a `graph_safe` device score, the counter-based draw
         # stream, no sharding collective) is captured ONCE into a hipGraph and replayed: at small D the Python / launch
         # overhead of ~10 calls per iteration is the bound (D = 256, B = 8: 58 us eager against 50 us replayed).  Blocks
@@ -454,26 +317,15 @@ class GSM:
         # and capturing ~200 kernel nodes costs a few ms, so graph=None takes the graph for D <= 512; graph=True forces it.
         use_graph = ((graph is True or (graph is None and D <= 512)) and dev_rng and native and not shard
                      and niter + 1 >= 3 * KB and bool(getattr(self.lp_g, "graph_safe", False)))
-        takes_out = False
-        if use_graph:
-            import inspect
-            try:
-                takes_out = "out" in inspect.signature(self.lp_g).parameters
-            except (TypeError, ValueError):
-                takes_out = False
-        gstate = {"graph": None}
+        out_ok = use_graph and takes_out(self.lp_g)
         self.graph_replays = 0                                  # blocks replayed from the captured graph (tests / diagnostics)
         self.graph_fallback = None                              # the exception that sent a graph fit back to eager launches
-        if use_graph:
-            ctr = [torch.zeros(1, dtype=torch.int64, device=Zblk.device) for _ in range(2)]
-        state_bufs = [(mean_t, F), (mean_new, F_new)]
 
         def iteration(Zi, a):
-            mu_a, F_a = state_bufs[a]
-            mu_b, F_b = state_bufs[1 - a]
+            (mu_a, F_a), (mu_b, F_b) = bufs[a], bufs[1 - a]
             X = eng.sample(Zi[lo:hi], mu_a, F_a, out=Xbuf)       # only this rank's rows when sharded
             if native:
-                vs = self.lp_g(X, out=Gbuf) if takes_out else self.lp_g(X)
+                vs = self.lp_g(X, out=Gbuf) if out_ok else self.lp_g(X)
             else:
                 vs = eng.host_score(self.lp_g, X, out=Gbuf)
             if shard:
@@ -482,84 +334,42 @@ class GSM:
             else:
                 eng.gsm_factor_update(Zi, X, vs, mu_a, F_a, out=(mu_b, F_b), flag=flag, n_reverts=n_rev)
 
-        def graph_block():
-            """KB iterations (KB even: the ping-pong state ends where it started) as one replayed graph; the draw counter
-            lives on the device and advances by KB per replay (two half-block draws on a ping-pong word pair)."""
-            if gstate["graph"] is None:
-                side = torch.cuda.Stream()
-                side.wait_stream(torch.cuda.current_stream())
-                g = torch.cuda.CUDAGraph()
-                with torch.cuda.stream(side):
-                    torch.cuda.synchronize()
-                    with torch.cuda.graph(g, stream=side):
-                        for half in range(2):
-                            eng.normal_batch(KB // 2, B, D, seed, 0, out=Zblk[half * (KB // 2):(half + 1) * (KB // 2)],
-                                             call_in=ctr[half], call_out=ctr[1 - half])
-                            if self._zc is not None:
-                                Zblk[half * (KB // 2):(half + 1) * (KB // 2), :, self._zc:] = 0.0
-                            for k in range(KB // 2):
-                                iteration(Zblk[half * (KB // 2) + k], k & 1)
-                torch.cuda.current_stream().wait_stream(side)
-                gstate["graph"] = g
-            gstate["graph"].replay()
+        if use_graph:
+            ctr = [torch.zeros(1, dtype=torch.int64, device=draws.block.device) for _ in range(2)]
 
-        a = 0                                                   # which buffer pair holds the current state
+            def capture():
+                """KB iterations (KB even: the ping-pong state ends where it started); the draw counter lives on the device and
+                advances by KB per replay (two half-block draws on a ping-pong word pair)."""
+                for half in range(2):
+                    Zh = draws.block[half * (KB // 2):(half + 1) * (KB // 2)]
+                    eng.normal_batch(KB // 2, B, D, seed, 0, out=Zh, call_in=ctr[half], call_out=ctr[1 - half])
+                    draws.zero(Zh)
+                    for k in range(KB // 2):
+                        iteration(Zh[k], k & 1)
+
+            graph = GraphBlock(self, "GSM.fit", capture)
+
         i = 0
         while i <= niter:
             blk_end = min(i + KB, niter + 1)
-            eventful = any((verbose and j % every == 0) or (monitor is not None and j % monitor.checkpoint == 0)
-                           for j in range(i, blk_end))
             # (the first block always runs eagerly: every kernel has been launched, and the context sized, before a capture)
-            if use_graph and i > 0 and a == 0 and not eventful and blk_end - i == KB:
-                ctr[0].fill_(i)                                 # (stream-ordered; the graph reads it on the device)
-                try:
-                    graph_block()
-                except Exception as exc:                        # capture unsupported here: stay eager for the rest of the fit
-                    if gstate["graph"] is not None:
-                        raise
-                    import warnings
-                    warnings.warn(f"GSM.fit: hipGraph capture of an iteration block failed ({type(exc).__name__}: {exc}); "
-                                  "the fit continues with eager launches (same numbers, more launch overhead)", RuntimeWarning)
-                    self.graph_fallback = exc
+            if use_graph and i > 0 and a == 0 and blk_end - i == KB and not eventful(progress, mon, i, blk_end):
+                if graph.run(lambda: ctr[0].fill_(i)):          # (stream-ordered; the graph reads it on the device)
+                    draws.call += KB
+                    mon.nevals += B * KB
+                    i = blk_end
+                else:                                           # capture unsupported here: stay eager for the rest of the fit
                     use_graph = False
-                    torch.cuda.synchronize()
-                    continue
-                self.graph_replays += 1
-                nevals += B * KB
-                i = blk_end
                 continue
-            if dev_rng:
-                eng.normal_batch(blk_end - i, B, D, seed, i, out=Zblk[:blk_end - i])
-                if self._zc is not None:
-                    Zblk[:, :, self._zc:] = 0.0                          # inert coordinates of an odd-D fit (_oddpad.py)
             for j in range(i, blk_end):
-                mean_t, F = state_bufs[a]
-                if verbose and j % every == 0:
-                    print(f"Iteration {j} of {niter}")
-                    r = eng.read_flag(n_rev)
-                    if r > reverts_seen:
-                        print(f"Bad update for covariance matrix. Revert ({r - reverts_seen} since last print)")
-                        reverts_seen = r
-                if monitor is not None and j % monitor.checkpoint == 0:
-                    monitor(j, state(), self.lp, key, nevals=nevals)
-                    nevals = 0
-                Zi = Zblk[j - i] if dev_rng else eng.normal_from_host(_host_draw(rs, B, D, self._zc))
-                if not dev_rng and self._zc is not None:
-                    Zi[:, self._zc:] = 0.0
-                iteration(Zi, a)
-                nevals += B
+                Zj = draws.next() if dev_rng else None          # (a block's device draws are launched ahead of its prints)
+                progress.tick(j)
+                mon.tick(j)
+                iteration(Zj if dev_rng else draws.next(), a)
+                mon.nevals += B
                 a = 1 - a                                       # the kernel already returned the reverted state when its PD
             i = blk_end                                         # test failed: accept = swapping the buffer pair
-        mean_t, F = state_bufs[a]
-        i = niter
-        if verbose:
-            r = eng.read_flag(n_rev)
-            if r > reverts_seen:
-                print(f"Bad update for covariance matrix. Revert ({r - reverts_seen} since last print)")
-        if monitor is not None:
-            monitor(i, state(), self.lp, key, nevals=nevals)
+        progress.flush()
+        mon.final(niter)
         self.n_reverts = eng.read_flag(n_rev)
-        cov_t = eng.gram(F)
-        if as_torch:
-            return mean_t, cov_t
-        return eng.to_numpy(mean_t), eng.to_numpy(cov_t)
+        return result(eng, bufs[a][0], eng.gram(bufs[a][1]), as_torch)

@@ -301,3 +301,69 @@ def test_host_score_pool_never_hands_out_an_array_somebody_kept():
     assert _unheld_entry(pool) is pool[0]
     del view, also
     assert _unheld_entry(pool) is pool[0]
+
+
+def test_progress_cadence_at_nprint_zero(capsys):
+    """The two drivers' print rules differ at nprint <= 0 (gsm.py clamps nprint to 1, bam.py:177-179 prints every iteration)
+    GSM also prints the reverts left after its last progress line."""
+    D, niter = 4, 5
+    m, cov_t, P = orc.make_gaussian_target(D, 2)
+    score = lambda x: orc.gaussian_score(x, m, P)
+    GSM(D, None, score, engine=OracleEngine()).fit(3, niter=niter, batch_size=2, nprint=0, method="dense")
+    assert capsys.readouterr().out == "Iteration 0 of 5\nIteration 5 of 5\n"
+    BaM(D, None, score, engine=OracleEngine()).fit(3, Regularizers().constant(1.0), niter=niter, batch_size=2, nprint=0)
+    assert capsys.readouterr().out == "".join(f"Iteration {i} of 5\n" for i in range(niter + 1))
+    calls = [0]
+
+    def bad_twice(x):                                   # NaN scores: the dense Cholesky test reverts those updates
+        calls[0] += 1
+        return score(x) * (np.nan if calls[0] in (5, 6) else 1.0)
+
+    GSM(D, None, bad_twice, engine=OracleEngine()).fit(3, niter=niter, batch_size=2, nprint=0, method="dense")
+    assert capsys.readouterr().out == ("Iteration 0 of 5\nIteration 5 of 5\n"                 # iteration 4, then iteration 5
+                                       "Bad update for covariance matrix. Revert (1 since last print)\n"
+                                       "Bad update for covariance matrix. Revert (1 since last print)\n")
+
+
+def test_draw_stream_blocks_and_retries_take_draws():
+    """The device draw stream of the factor fits: GSM takes draw i at iteration i and clips its last block to niter + 1
+    draws; BaM takes one draw per ATTEMPT (a retry redraws) and always launches whole blocks of 16."""
+
+    class Rec(OracleEngine):
+        def __init__(self):
+            self.launches, self.used = [], []
+
+        def normal_batch(self, ncalls, B, D, seed, call0=0, out=None, call_in=None, call_out=None):
+            self.launches.append((ncalls, call0))
+            return super().normal_batch(ncalls, B, D, seed, call0, out=out)
+
+        def gsm_factor_update(self, Z, *a, **k):
+            self.used.append(np.array(Z))
+            return super().gsm_factor_update(Z, *a, **k)
+
+        def bam_factor_update(self, Z, *a, **k):
+            self.used.append(np.array(Z))
+            return super().bam_factor_update(Z, *a, **k)
+
+    D, B, niter = 10, 2, 20
+    m, cov_t, P = orc.make_gaussian_target(D, 2)
+    eng = Rec()
+    GSM(D, None, lambda x: orc.gaussian_score(x, m, P), engine=eng).fit(7, niter=niter, batch_size=B, verbose=False,
+                                                                         method="factor", rng="device")
+    assert eng.launches == [(16, 0), (5, 16)]
+    assert all(np.array_equal(z, orc.philox_randn(7, i, B * D).reshape(B, D)) for i, z in enumerate(eng.used))
+    calls = [0]
+
+    def flaky(x):
+        calls[0] += 1
+        if calls[0] in (3, 4, 9):
+            raise FloatingPointError("synthetic score failure")
+        return orc.gaussian_score(x, m, P)
+
+    eng = Rec()
+    BaM(D, None, flaky, engine=eng).fit(5, Regularizers().constant(2.0), niter=niter, batch_size=B, verbose=False,
+                                        retries=3, jitter=0.0)
+    assert eng.launches == [(16, 0), (16, 16)]
+    taken = [c for c in range(niter + 4) if c + 1 not in (3, 4, 9)]     # the draws of the attempts that succeeded
+    assert len(eng.used) == niter + 1
+    assert all(np.array_equal(z, orc.philox_randn(5, c, B * D).reshape(B, D)) for c, z in zip(taken, eng.used))
