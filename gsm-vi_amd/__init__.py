@@ -2,6 +2,9 @@
 
 Mirrors the reference's public surface for the hot path (reference file:line):
     GSM, gsm_update                              gsmvi/gsm.py:31-133, gsmvi/gsm_numpy.py:27-129
+    gsm_update_batched, GSMBatch,
+    BatchedGaussianTarget (K problems at once,
+    D <= 64: jax.vmap(gsm_update) and its fit)   gsmvi/gsm.py:31-58, gsmvi/gsm_numpy.py:77-129
     BaM, bam_update, bam_lowrank_update,
     Regularizers                                 gsmvi/bam.py:31-274
     KLMonitor (diagnostics callback, host side),
@@ -18,6 +21,8 @@ from .engine import HipEngine, get_engine                            # noqa: F40
 from .gsm import GSM, gsm_update                                     # noqa: F401
 from .bam import BaM, bam_update, bam_lowrank_update, Regularizers   # noqa: F401
 from .targets import GaussianTarget, device_score, score_from_logp   # noqa: F401
+from .targets import BatchedGaussianTarget                           # noqa: F401
+from .batched import GSMBatch, gsm_update_batched                    # noqa: F401
 from .monitors import KLMonitor, DeviceKLMonitor                     # noqa: F401
 from .initializers import lbfgs_init                                 # noqa: F401
 from .advi import ADVI                                               # noqa: F401

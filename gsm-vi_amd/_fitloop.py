@@ -106,10 +106,12 @@ class DrawStream:
 
 class Progress:
     """"Iteration i of niter" every ``every`` iterations with the reverts counted on the device since the last print (read
-    only here, so the loop never synchronises per iteration); ``flush()`` prints the reverts after the last print."""
+    only here, so the loop never synchronises per iteration); ``flush()`` prints the reverts after the last print.  ``read``
+    (default ``eng.read_flag``) turns the counter into a number (a batched fit sums its per-problem counters)."""
 
-    def __init__(self, eng, n_rev, niter, every, verbose):
+    def __init__(self, eng, n_rev, niter, every, verbose, read=None):
         self.eng, self.n_rev, self.niter, self.every, self.verbose = eng, n_rev, niter, every, verbose
+        self.read = read
         self.seen = 0
 
     def due(self, i):
@@ -125,7 +127,7 @@ class Progress:
             self._reverts()
 
     def _reverts(self):
-        r = self.eng.read_flag(self.n_rev)
+        r = self.eng.read_flag(self.n_rev) if self.read is None else self.read(self.n_rev)
         if r > self.seen:
             print(f"Bad update for covariance matrix. Revert ({r - self.seen} since last print)")
             self.seen = r

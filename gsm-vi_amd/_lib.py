@@ -93,6 +93,14 @@ _SIGS = {
     "gsmvi_bam_factor_apply_cols_f64": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, _c_dp, C.c_int,
                                                   _c_dp, C.c_int, _c_dp, C.c_int, _c_dp, _c_dp, _c_dp, C.c_int, C.c_double,
                                                   _c_dp, _c_dp, C.c_int, _c_dp, _c_dp]),
+    "gsmvi_gsm_update_batched_f64": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, _c_dp, _c_dp, _c_dp, _c_dp,
+                                               _c_dp, _c_dp]),
+    "gsmvi_gsm_fit_init_batched_f64": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, _c_dp, _c_dp, _c_dp, _c_dp,
+                                                 _c_dp, _c_dp]),
+    "gsmvi_gsm_fit_step_batched_f64": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, _c_dp, _c_dp, _c_dp, _c_dp,
+                                                 _c_dp, _c_dp, _c_dp, _c_dp, C.c_uint64]),
+    "gsmvi_gaussian_score_batched_f64": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, _c_dp, _c_dp, _c_dp,
+                                                   _c_dp]),
     "gsmvi_commit_f64": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, _c_dp, _c_dp, _c_dp, C.c_int, _c_dp, _c_dp,
                                    C.c_int, _c_dp]),
     "gsmvi_bam_update_f64": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, _c_dp, C.c_int, _c_dp, C.c_int,

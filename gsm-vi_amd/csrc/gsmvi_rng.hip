@@ -11,30 +11,8 @@
 // bit-exact, pinned to the Random123 known-answer vectors).
 #include "gsmvi_common.h"
 #include "gsmvi_ctx.h"
+#include "gsmvi_philox.h"
 #include "../../include/gsmvi_hip.h"
-
-__device__ __forceinline__ void philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0,
-                                              unsigned k1, unsigned (&out)[4]) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const unsigned long long p0 = (unsigned long long)0xD2511F53u * c0;
-        const unsigned long long p1 = (unsigned long long)0xCD9E8D57u * c2;
-        const unsigned n0 = (unsigned)(p1 >> 32) ^ c1 ^ k0;
-        const unsigned n1 = (unsigned)p1;
-        const unsigned n2 = (unsigned)(p0 >> 32) ^ c3 ^ k1;
-        const unsigned n3 = (unsigned)p0;
-        c0 = n0; c1 = n1; c2 = n2; c3 = n3;
-        k0 += 0x9E3779B9u;
-        k1 += 0xBB67AE85u;
-    }
-    out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
-}
-
-// 53-bit uniform in (0, 1): ((a >> 5) 2^26 + (b >> 6) + 1/2) 2^-53 -- never 0, never 1
-__device__ __forceinline__ double u53(unsigned a, unsigned b) {
-    const unsigned long long m = ((unsigned long long)(a >> 5) << 26) | (unsigned long long)(b >> 6);
-    return ((double)m + 0.5) * (1.0 / 9007199254740992.0);
-}
 
 // One thread per element pair; `raw` (may be NULL) receives the four Philox words of every pair (tests).
 // blockIdx.y = c: draw number call + c goes to out + c n (several iterations' draws from one launch).  call_in (may be
@@ -57,12 +35,10 @@ __global__ __launch_bounds__(256) void k_randn(unsigned long long seed, unsigned
 #pragma unroll
         for (int k = 0; k < 4; ++k) raw[4 * p + k] = w[k];
     }
-    const double u1 = u53(w[0], w[1]), u2 = u53(w[2], w[3]);
-    const double r = sqrt(-2.0 * log(u1));
-    double s, c;
-    sincospi(2.0 * u2, &s, &c);
-    out[2 * p] = r * c;
-    if (2 * p + 1 < n) out[2 * p + 1] = r * s;
+    double z0, z1;
+    philox_normal_pair(w, z0, z1);
+    out[2 * p] = z0;
+    if (2 * p + 1 < n) out[2 * p + 1] = z1;
 }
 
 static int randn_launch(const char* fn, gsmvi_ctx* ctx, void* stream, uint64_t seed, uint64_t call, int ncalls, int64_t n,

@@ -583,7 +583,7 @@ class HipEngine:
     # kernel-family bits of include/gsmvi_hip.h (GSMVI_PATH_*)
     PATH_BITS = {"panel_fast": 0x1, "panel_wide": 0x2, "panel_generic": 0x4, "panel_t_fast": 0x8, "panel_t_generic": 0x10,
                  "scalars_fast": 0x20, "scalars_generic": 0x40, "cov_sym": 0x80, "cov_generic": 0x100, "fupd_fast": 0x200,
-                 "fupd_generic": 0x400, "lowrank_fast": 0x800, "lowrank_generic": 0x1000}
+                 "fupd_generic": 0x400, "lowrank_fast": 0x800, "lowrank_generic": 0x1000, "batched": 0x2000}
     PATH_GENERIC_MASK = 0x4 | 0x10 | 0x40 | 0x100 | 0x400 | 0x1000
 
     def last_path(self, reset=True):
@@ -658,6 +658,85 @@ class HipEngine:
         _lib.check("gsmvi_commit_f64", self.lib.gsmvi_commit_f64(
             self._ctx, self._stream(), D, C.c_void_p(flag.data_ptr()), self._vec(mu_new, "mu_new"), psn, ldsn,
             self._vec(mu, "mu"), ps, lds, C.c_void_p(n_reverts.data_ptr()) if n_reverts is not None else None))
+
+    # ---- batched GSM: K independent problems of one (D, B) (csrc/gsmvi_batched.hip) -------------------------------------
+    batched_max_D = 64         # one problem per workgroup slot, held in LDS from its first read to its last write
+    batched_max_B = 32
+
+    @staticmethod
+    def _packed(t, shape, name):
+        assert isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float64 and t.is_contiguous(), \
+            f"{name}: expected a contiguous float64 CUDA tensor"
+        assert tuple(t.shape) == tuple(shape), f"{name}: expected shape {tuple(shape)}, got {tuple(t.shape)}"
+        return C.c_void_p(t.data_ptr())
+
+    @staticmethod
+    def _ints(t, K, name):
+        if t is None:
+            return None
+        assert isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.int32 and t.is_contiguous() and t.numel() == K, \
+            f"{name}: expected a contiguous int32 CUDA tensor of {K} entries"
+        return C.c_void_p(t.data_ptr())
+
+    def eye_batch(self, K, D):
+        return torch.eye(D, dtype=torch.float64, device=self.device).expand(K, D, D).contiguous()
+
+    def batched_ints(self, K):
+        """K device int32 zeros: per-problem flags and revert counters"""
+        return torch.zeros(K, dtype=torch.int32, device=self.device)
+
+    def read_ints(self, t):
+        return t.cpu().numpy().astype(np.int64)          # synchronises
+
+    def batched_seeds(self, seeds):
+        """the problems' draw keys as a device uint64 array (stored as int64: the same bits)"""
+        return torch.tensor(np.array([int(s) & (2 ** 64 - 1) for s in seeds], dtype=np.uint64).view(np.int64),
+                            device=self.device)
+
+    def gsm_update_batched(self, X, G, mu0, S0, out=None):
+        """(mu_k, S_k) = gsm_update(X_k, G_k, mu0_k, S0_k) for every k  [gsmvi/gsm_numpy.py:27-55 under jax.vmap]; reads all
+        of each S0_k."""
+        K, B, D = X.shape
+        self._ensure(max(self._max_D, 1), max(self._max_B, 1))
+        mu, S = (self.empty(K, D), self.empty(K, D, D)) if out is None else out
+        _lib.check("gsmvi_gsm_update_batched_f64", self.lib.gsmvi_gsm_update_batched_f64(
+            self._ctx, self._stream(), K, D, B, self._packed(X, (K, B, D), "samples"), self._packed(G, (K, B, D), "vs"),
+            self._packed(mu0, (K, D), "mu0"), self._packed(S0, (K, D, D), "S0"), self._packed(mu, (K, D), "mu"),
+            self._packed(S, (K, D, D), "S")))
+        return mu, S
+
+    def gsm_fit_init_batched(self, mean, cov, R, info, seeds=None, X=None):
+        """R_k = chol(cov_k) (upper), info[k] = 0 or 1 + the first bad pivot; with ``seeds``: X_k = mean_k + Z_k R_k, Z_k = draw 0
+        of the problem's stream"""
+        K, D = mean.shape
+        B = X.shape[1] if X is not None else 1
+        self._ensure(max(self._max_D, 1), max(self._max_B, 1))
+        _lib.check("gsmvi_gsm_fit_init_batched_f64", self.lib.gsmvi_gsm_fit_init_batched_f64(
+            self._ctx, self._stream(), K, D, B, self._packed(mean, (K, D), "mean"), self._packed(cov, (K, D, D), "cov"),
+            self._packed(R, (K, D, D), "R"), self._ints(info, K, "info"),
+            C.c_void_p(seeds.data_ptr()) if seeds is not None else None,
+            self._packed(X, (K, B, D), "X") if X is not None else None))
+
+    def gsm_fit_step_batched(self, X, G, mean, cov, R=None, info=None, n_reverts=None, seeds=None, call=0):
+        """One batched fit iteration after the score (csrc/gsmvi_batched.hip): update, Cholesky test and accept / revert of
+        (mean, cov, R) per problem; with ``seeds`` X is overwritten with the samples of draw ``call``."""
+        K, B, D = X.shape
+        self._ensure(max(self._max_D, 1), max(self._max_B, 1))
+        _lib.check("gsmvi_gsm_fit_step_batched_f64", self.lib.gsmvi_gsm_fit_step_batched_f64(
+            self._ctx, self._stream(), K, D, B, self._packed(X, (K, B, D), "X"), self._packed(G, (K, B, D), "G"),
+            self._packed(mean, (K, D), "mean"), self._packed(cov, (K, D, D), "cov"),
+            self._packed(R, (K, D, D), "R") if R is not None else None, self._ints(info, K, "info"),
+            self._ints(n_reverts, K, "n_reverts"), C.c_void_p(seeds.data_ptr()) if seeds is not None else None, int(call)))
+
+    def gaussian_score_batched(self, X, m, P, out=None):
+        """G_k = -(X_k - m_k) P_k for K Gaussian targets  [examples/example_gsm_numpy.py:24-29]."""
+        K, B, D = X.shape
+        self._ensure(max(self._max_D, 1), max(self._max_B, 1))
+        G = self.empty(K, B, D) if out is None else out
+        _lib.check("gsmvi_gaussian_score_batched_f64", self.lib.gsmvi_gaussian_score_batched_f64(
+            self._ctx, self._stream(), K, D, B, self._packed(X, (K, B, D), "X"), self._packed(m, (K, D), "m"),
+            self._packed(P, (K, D, D), "P"), self._packed(G, (K, B, D), "G")))
+        return G
 
     def bam_update(self, X, G, mu0, S0, reg, jitter=0.0, out=None, flag=None):
         """(mu, S) of BaM [gsmvi/bam.py:72-114]; S symmetrised, jitter on the diagonal."""

@@ -82,3 +82,36 @@ class GaussianTarget:
         x = self.engine.asarray(x)
         r = self.mean[None, :] - x
         return -0.5 * torch.einsum("bi,ij,bj->", r, self.P, r)
+
+
+class BatchedGaussianTarget:
+    """K Gaussian targets N(means[k], cov[k]) of one dimension D for ``GSMBatch``: ``lp_g`` maps (K,B,D) samples to (K,B,D)
+    scores g_kb = -P_k (x_kb - m_k) with the batched score kernel (gsmvi_gaussian_score_batched_f64; one capturable launch,
+    marked ``graph_safe``); ``lp`` is the plain batched log-density, one sum over the batch per problem (example_gsm_numpy.py:17-29
+    per target).  Give ``cov`` (K,D,D) or ``precision`` (K,D,D)."""
+
+    def __init__(self, means, cov=None, precision=None, engine=None):
+        self.engine = engine if engine is not None else get_engine()
+        eng = self.engine
+        m = np.asarray(means, dtype=np.float64)
+        assert m.ndim == 2, "means: expected shape (K, D)"
+        if precision is None:
+            assert cov is not None, "give cov or precision"
+            precision = np.linalg.inv(np.asarray(cov, dtype=np.float64))
+        P = np.asarray(precision, dtype=np.float64)
+        assert P.shape == (m.shape[0], m.shape[1], m.shape[1]), "precision / cov: expected shape (K, D, D)"
+        self.K, self.D = int(m.shape[0]), int(m.shape[1])
+        self.mean = eng.asarray(m)
+        self.P = eng.asarray(0.5 * (P + np.swapaxes(P, 1, 2)))
+
+        def lp_g(x, out=None):
+            return eng.gaussian_score_batched(x, self.mean, self.P, out=out)
+        lp_g.device_native = True
+        lp_g.graph_safe = True          # one capturable kernel launch, no allocation when `out` is given, no host work
+        self.lp_g = lp_g
+
+    def lp(self, x):
+        """(K,) sums over the batch of -1/2 (m_k - x_kb)^T P_k (m_k - x_kb); plain torch (off the hot path)."""
+        x = self.engine.asarray(x)
+        r = self.mean[:, None, :] - x
+        return -0.5 * torch.einsum("kbi,kij,kbj->k", r, self.P, r)

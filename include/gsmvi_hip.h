@@ -12,6 +12,8 @@
  *   gsmvi/gsm_numpy.py:116    np.random.multivariate_normal(mean,cov,B) ->  gsmvi_sample_f64 (+ gsmvi_potrf_f64)
  *   gsmvi/gsm_numpy.py:105,116 np.random.seed + standard-normal stream  ->  gsmvi_randn_f64 (counter-based)
  *   gsmvi/gsm_numpy.py:132-146 _check_goodness(cov)                     ->  gsmvi_potrf_f64 (info flag)
+ *   jax.vmap(gsm_update) over K problems, D <= 64 (gsm.py:31-58)       ->  gsmvi_gsm_update_batched_f64
+ *   gsm_numpy.py:77-129 fit of K problems (dense form), D <= 64         ->  gsmvi_gsm_fit_{init,step}_batched_f64
  *   (no reference twin; gsm_numpy.py:4-55 in factor form)   ->  gsmvi_gsm_factor_update_f64
  *   gsmvi/bam.py:72-114       bam_lowrank_update(samples,vs,mu0,S0,reg) ->  gsmvi_bam_update_f64
  *   gsmvi/bam.py:31-69        bam_update(samples,vs,mu0,S0,reg)         ->  gsmvi_bam_update_f64 (same result, K6)
@@ -251,6 +253,7 @@ int gsmvi_get_profile(gsmvi_ctx* ctx, float* ms, int n);
 #define GSMVI_PATH_FUPD_GENERIC 0x0400u    /* k_gsmf_update + k_gsmf_mean                                           */
 #define GSMVI_PATH_LOWRANK_FAST 0x0800u    /* k_lowrank_update_fast: BaM's S = S0 + Vf^T Vf - Z^T Z                 */
 #define GSMVI_PATH_LOWRANK_GENERIC 0x1000u /* k_lowrank_update                                                      */
+#define GSMVI_PATH_BATCHED 0x2000u         /* k_gsm_batched / k_gauss_score_batched: the batched entry points      */
 #define GSMVI_PATH_GENERIC_MASK (0x0004u | 0x0010u | 0x0040u | 0x0100u | 0x0400u | 0x1000u)
 int gsmvi_last_path(gsmvi_ctx* ctx, unsigned* bits, int reset);
 
@@ -271,6 +274,48 @@ int gsmvi_bam_set_reg_source(gsmvi_ctx* ctx, const double* reg_dev);
 int gsmvi_gaussian_score_f64(gsmvi_ctx* ctx, void* stream, int D, int B,
                              const double* X, int ldx, const double* m,
                              const double* P, int ldp, double* G, int ldg);
+
+/*
+ * Batched GSM (K independent problems of the same (D, B)): 1 <= D <= 64, 1 <= B <= 32, K >= 1 (one launch each: K < 2^24 for
+ * D > 16, K < 2^26 for D <= 16).  Every array is packed and contiguous with a leading problem axis -- X, G (K x B x D),
+ * mu (K x D), S, R (K x D x D) -- in device memory; problem k reads and writes only slice k of each, so a NaN or a revert in
+ * one problem cannot reach another.  Out-of-range shapes and NULL or overlapping arrays return GSMVI_ERR_BAD_ARG before
+ * anything is enqueued.  No context workspace is used (the kernels keep a problem in LDS).  Sets GSMVI_PATH_BATCHED.
+ *
+ * gsmvi/gsm_numpy.py:27-55 gsm_update under jax.vmap (gsmvi/gsm.py:31-58) -> gsmvi_gsm_update_batched_f64:
+ *   (mu_k, S_k) = gsm_update(X_k, G_k, mu0_k, S0_k) for every k.  Reads ALL of S0_k (both triangles: the reference's literal
+ *   S0 + mean semantics for any square S0); S_k is exactly symmetric when S0_k is.  Outputs must not overlap inputs.
+ */
+int gsmvi_gsm_update_batched_f64(gsmvi_ctx* ctx, void* stream, int64_t K, int D, int B, const double* X, const double* G,
+                                 const double* mu0, const double* S0, double* mu, double* S);
+
+/*
+ * The start of a batched dense fit (gsmvi/gsm_numpy.py:103-116 per problem): R_k = upper Cholesky factor of cov_k (reads all of
+ * cov_k; the factorisation uses its upper triangle) and info_dev[k] = 0, or 1 + the first bad pivot (not > 0, NaN, inf).
+ * seeds_dev (K uint64 keys, may be NULL): X_k = mean_k + Z_k R_k with Z_k = draw 0 of key seeds_dev[k] of the stream of
+ * gsmvi_randn_f64, laid out as B x (D + 1) normals with the last column dropped for odd D (the layout of the single fit).
+ */
+int gsmvi_gsm_fit_init_batched_f64(gsmvi_ctx* ctx, void* stream, int64_t K, int D, int B, const double* mean, const double* cov,
+                                   double* R, int* info_dev, const uint64_t* seeds_dev, double* X);
+
+/*
+ * One iteration of the batched dense fit after the score G = lp_g(X) (gsmvi/gsm_numpy.py:116-125 per problem), one launch:
+ * the update of every problem, the Cholesky test of its new covariance (_check_goodness, gsm_numpy.py:132-146), and per
+ * problem: accept -> (mean_k, cov_k, R_k) <- (mu', S', chol(S')); revert -> all three kept bit for bit, n_reverts_dev[k] += 1
+ * (may be NULL).  info_dev (may be NULL) receives each problem's test result as gsmvi_gsm_fit_init_batched_f64 defines it.
+ * seeds_dev != NULL: X is overwritten with the next samples, X_k = mean_k + Z_k R_k of the (kept or accepted) state with Z_k =
+ * draw `call` of key seeds_dev[k] (needs R).  seeds_dev == NULL: X is left alone (teacher-forced samples; R may be NULL).
+ */
+int gsmvi_gsm_fit_step_batched_f64(gsmvi_ctx* ctx, void* stream, int64_t K, int D, int B, double* X, const double* G, double* mean,
+                                   double* cov, double* R, int* info_dev, int* n_reverts_dev, const uint64_t* seeds_dev,
+                                   uint64_t call);
+
+/*
+ * examples/example_gsm_numpy.py:24-29 for K Gaussian targets -> gsmvi_gaussian_score_batched_f64: G_k = -(X_k - 1 m_k^T) P_k
+ * (m: K x D, P: K x D x D symmetric precision matrices).  G must not overlap an input; K B D < 2^32 - 256.
+ */
+int gsmvi_gaussian_score_batched_f64(gsmvi_ctx* ctx, void* stream, int64_t K, int D, int B, const double* X, const double* m,
+                                     const double* P, double* G);
 
 /*
  * Upper Cholesky factor R (R^T R = S, R upper triangular, strictly-lower part zeroed) of a

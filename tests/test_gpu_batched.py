@@ -1,0 +1,241 @@
+"""Batched GSM on the GPU (csrc/gsmvi_batched.hip): one-shot parity with the per-problem oracle, the reference's G2
+trajectories in a batch, equality with the single dense fit, independence of the problems, per-problem reverts, bounds."""
+import numpy as np
+import pytest
+import torch
+
+from conftest import rel_err
+
+pytestmark = pytest.mark.gpu
+
+
+def _orc():
+    from oracle import gsm_oracle as orc
+    return orc
+
+
+def _states(K, B, D, seed):
+    """random one-shot inputs: S0 = A A^T / D + 0.1 I, samples around mu0, arbitrary scores"""
+    rs = np.random.RandomState(seed)
+    A = rs.standard_normal((K, D, D))
+    S0 = A @ np.swapaxes(A, 1, 2) / D + 0.1 * np.eye(D)
+    S0 = 0.5 * (S0 + np.swapaxes(S0, 1, 2))
+    mu0 = rs.standard_normal((K, D))
+    X = mu0[:, None, :] + rs.standard_normal((K, B, D))
+    V = -0.5 * (X - rs.standard_normal((K, 1, D)))
+    return X, V, mu0, S0
+
+
+@pytest.mark.parametrize("D", [1, 2, 5, 7, 10, 16, 17, 31, 32, 33, 63, 64])
+def test_one_shot_matches_the_per_problem_oracle(D):
+    import gsmvi_amd
+    orc = _orc()
+    eng = gsmvi_amd.get_engine()
+    for B in (1, 2, 5, 8, 32):
+        for K in (1, 3, 257):
+            X, V, mu0, S0 = _states(K, B, D, 1000 * D + 10 * B + K)
+            as_torch = K == 3
+            args = [torch.tensor(a, device="cuda") for a in (X, V, mu0, S0)] if as_torch else [a.copy() for a in (X, V, mu0, S0)]
+            eng.last_path(reset=True)
+            mu, S = gsmvi_amd.gsm_update_batched(*args)
+            assert eng.last_path(reset=True) == {"batched"}          # the batched kernel alone: no loop over single problems
+            if as_torch:
+                assert isinstance(mu, torch.Tensor) and mu.is_cuda
+                mu, S = mu.cpu().numpy(), S.cpu().numpy()
+                args = [a.cpu().numpy() for a in args]
+            else:
+                assert isinstance(mu, np.ndarray) and mu.dtype == np.float64
+            for a, b in zip(args, (X, V, mu0, S0)):
+                assert np.array_equal(a, b)                          # inputs untouched
+            assert mu.shape == (K, D) and S.shape == (K, D, D)
+            for k in range(K):
+                mo, So = orc.gsm_update_faithful(X[k], V[k], mu0[k], S0[k])
+                assert rel_err(mu[k], mo) <= 1e-12 and rel_err(S[k], So) <= 1e-12, (D, B, K, k)
+
+
+def _g2_batch(golden, D, slots=(2, 5), K=8):
+    """K problems at dimension D: the G2 samples and target in `slots`, random samples and other targets elsewhere"""
+    orc = _orc()
+    g = golden(f"g2_traj_D{D}.npz")
+    n = g["samples"].shape[0]
+    rs = np.random.RandomState(D)
+    ms, Ps = np.zeros((K, D)), np.zeros((K, D, D))
+    forced = 0.3 * rs.standard_normal((n, K, 2, D))
+    for k in range(K):
+        if k in slots:
+            ms[k], Ps[k] = g["target_m"], g["target_P"]
+            forced[:, k] = g["samples"]
+        else:
+            ms[k], _, Ps[k] = orc.make_gaussian_target(D, 50 + k, cond=10.0)
+    return g, ms, Ps, forced
+
+
+@pytest.mark.parametrize("D", [5, 10])
+def test_g2_trajectories_in_a_batch(golden, D):
+    import gsmvi_amd
+    orc = _orc()
+    g, ms, Ps, forced = _g2_batch(golden, D)
+    K, slots = 8, (2, 5)
+
+    def lp_g(X):
+        return np.stack([orc.gaussian_score(X[k], ms[k], Ps[k]) for k in range(K)])
+
+    # every state of the trajectory, through the engine's step (the fit's own kernel)
+    eng = gsmvi_amd.get_engine()
+    mean, cov = eng.zeros(K, D), eng.eye_batch(K, D)
+    R, info, n_rev = eng.empty(K, D, D), eng.batched_ints(K), eng.batched_ints(K)
+    eng.gsm_fit_init_batched(mean, cov, R, info)
+    states = [(mean.cpu().numpy(), cov.cpu().numpy())]
+    for i in range(forced.shape[0]):
+        X = eng.asarray(forced[i])
+        eng.gsm_fit_step_batched(X, eng.asarray(lp_g(forced[i])), mean, cov, None, info, n_rev)
+        states.append((mean.cpu().numpy(), cov.cpu().numpy()))
+    assert len(states) == 502 and eng.read_ints(n_rev)[list(slots)].tolist() == [0, 0]
+    for k in slots:
+        worst = max(max(rel_err(m[k], g["means"][j]), rel_err(c[k], g["covs"][j])) for j, (m, c) in enumerate(states))
+        assert worst < 1e-8, (k, worst)
+    # and the public fit with the same teacher-forced samples
+    fit = gsmvi_amd.GSMBatch(K, D, None, lp_g)
+    mean_f, cov_f = fit.fit(np.arange(K), niter=500, batch_size=2, verbose=False, forced_samples=forced)
+    for k in slots:
+        assert rel_err(mean_f[k], g["mean_fit"]) < 1e-8 and rel_err(cov_f[k], g["cov_fit"]) < 1e-8
+        assert np.array_equal(mean_f[k], states[-1][0][k]) and np.array_equal(cov_f[k], states[-1][1][k])
+
+
+def _targets(K, D, seed, cond=3.0):
+    """well-conditioned Gaussian targets: means U(0, 1)^D, covariance spectra log-spaced in [1, cond], random eigenvectors"""
+    ms, covs, Ps = np.zeros((K, D)), np.zeros((K, D, D)), np.zeros((K, D, D))
+    for k in range(K):
+        rs = np.random.RandomState(seed + k)
+        Q, _ = np.linalg.qr(rs.standard_normal((D, D)))
+        c = (Q * np.logspace(0.0, np.log10(cond), D)) @ Q.T
+        covs[k] = 0.5 * (c + c.T)
+        ms[k], Ps[k] = rs.random_sample(D), np.linalg.inv(covs[k])
+    return ms, covs, Ps
+
+
+@pytest.mark.parametrize("D,B", [(5, 2), (10, 2), (32, 8), (64, 8)])
+def test_each_problem_equals_the_single_dense_fit(D, B):
+    """Problem k after 200 iterations equals GSM.fit(keys[k], method="dense", rng="device") of its own target; at D <= 10
+    both have converged to the target by then.  The dense fit needs far more iterations at (32, 8) and (64, 8) -- the single
+    fit as much as the batched one (about 600 and 1500 on these targets) --, so convergence is checked there after 1500."""
+    import gsmvi_amd
+    K, niter = 16, 200
+    ms, covs, Ps = _targets(K, D, 7 * D)
+    keys = [31 * k + 5 for k in range(K)]
+    tgt = gsmvi_amd.BatchedGaussianTarget(ms, precision=Ps)
+    fit = gsmvi_amd.GSMBatch(K, D, tgt.lp, tgt.lp_g)
+    mean, cov = fit.fit(keys, batch_size=B, niter=niter, verbose=False)
+    assert fit.n_reverts.tolist() == [0] * K
+    for k in range(K):
+        t1 = gsmvi_amd.GaussianTarget(ms[k], precision=Ps[k])
+        m1, c1 = gsmvi_amd.GSM(D, t1.lp, t1.lp_g).fit(keys[k], batch_size=B, niter=niter, verbose=False, method="dense",
+                                                      rng="device")
+        assert rel_err(mean[k], m1) < 1e-8 and rel_err(cov[k], c1) < 1e-8, k
+    if D > 10:
+        mean, cov = fit.fit(keys, batch_size=B, niter=1500, verbose=False)
+    for k in range(K):
+        assert rel_err(mean[k], ms[k]) < 1e-8 and rel_err(cov[k], covs[k]) < 1e-8, k
+
+
+@pytest.mark.parametrize("D,B", [(10, 2), (33, 4)])
+def test_problem_is_independent_of_its_batch(D, B):
+    import gsmvi_amd
+    niter, key = 60, 424242
+    ms, covs, Ps = _targets(1024, D, 3)
+    mine = (ms[0].copy(), Ps[0].copy())
+    results = []
+    for K, slot, run in ((1, 0, 0), (16, 5, 0), (1024, 778, 0), (1024, 778, 1)):
+        m, P = ms[:K].copy(), Ps[:K].copy()
+        m[[0, slot]], P[[0, slot]] = m[[slot, 0]], P[[slot, 0]]       # the problem in `slot`, a different neighbour in slot 0
+        assert np.array_equal(m[slot], mine[0])
+        keys = np.arange(K) + 17
+        keys[slot] = key
+        tgt = gsmvi_amd.BatchedGaussianTarget(m, precision=P)
+        mean, cov = gsmvi_amd.GSMBatch(K, D, tgt.lp, tgt.lp_g).fit(keys, batch_size=B, niter=niter, verbose=False)
+        results.append((mean[slot], cov[slot], mean, cov))
+    for mean_k, cov_k, _, _ in results[1:]:
+        assert np.array_equal(mean_k, results[0][0]) and np.array_equal(cov_k, results[0][1])
+    assert np.array_equal(results[2][2], results[3][2]) and np.array_equal(results[2][3], results[3][3])   # run to run, K = 1024
+
+
+def test_g4_state_reverts_its_slot_only(golden):
+    import gsmvi_amd
+    g = golden("g4_revert.npz")
+    assert not bool(g["is_good"])
+    K, j = 4, 2
+    X, V, mu0, S0 = _states(K, 2, 12, 5)
+    X[j], V[j], mu0[j], S0[j] = g["samples"], g["vs"], g["mu0"], g["S0"]
+    eng = gsmvi_amd.get_engine()
+    mean, cov, Xd, Vd = (eng.asarray(a) for a in (mu0, S0, X, V))
+    info, n_rev = eng.batched_ints(K), eng.batched_ints(K)
+    eng.gsm_fit_step_batched(Xd, Vd, mean, cov, None, info, n_rev)
+    flags = eng.read_ints(info)
+    assert flags[j] != 0 and [int(f) for k, f in enumerate(flags) if k != j] == [0] * (K - 1)
+    assert eng.read_ints(n_rev).tolist() == [int(k == j) for k in range(K)]
+    assert np.array_equal(mean.cpu().numpy()[j], mu0[j]) and np.array_equal(cov.cpu().numpy()[j], S0[j])
+    mu_o, S_o = gsmvi_amd.gsm_update_batched(X, V, mu0, S0)
+    for k in range(K):
+        if k != j:
+            assert np.array_equal(mean.cpu().numpy()[k], mu_o[k]) and np.array_equal(cov.cpu().numpy()[k], S_o[k])
+
+
+def test_nan_score_reverts_one_problem_bit_for_bit():
+    import gsmvi_amd
+    orc = _orc()
+    K, D, B, niter, bad = 8, 6, 2, 30, 3
+    ms, covs, Ps = _targets(K, D, 11)
+    rs = np.random.RandomState(2)
+    mean0 = rs.standard_normal((K, D))
+    cov0 = np.stack([np.eye(D) * (0.5 + k / K) for k in range(K)])
+
+    def clean(X):
+        return np.stack([orc.gaussian_score(X[k], ms[k], Ps[k]) for k in range(K)])
+
+    def poisoned(X):
+        G = clean(X)
+        G[bad] = np.nan
+        return G
+
+    f0, f1 = gsmvi_amd.GSMBatch(K, D, None, clean), gsmvi_amd.GSMBatch(K, D, None, poisoned)
+    m0, c0 = f0.fit(range(K), mean=mean0, cov=cov0, batch_size=B, niter=niter, verbose=False)
+    m1, c1 = f1.fit(range(K), mean=mean0, cov=cov0, batch_size=B, niter=niter, verbose=False)
+    assert f1.n_reverts.tolist() == [niter + 1 if k == bad else 0 for k in range(K)]
+    assert np.array_equal(m1[bad], mean0[bad]) and np.array_equal(c1[bad], cov0[bad])
+    keep = [k for k in range(K) if k != bad]
+    assert np.array_equal(m1[keep], m0[keep]) and np.array_equal(c1[keep], c0[keep])
+
+
+def test_bounds_and_non_pd_initial_covariance():
+    import gsmvi_amd
+    with pytest.raises(ValueError, match="D = 65"):
+        gsmvi_amd.gsm_update_batched(*_states(2, 2, 65, 0))
+    with pytest.raises(ValueError, match="B = 33"):
+        gsmvi_amd.gsm_update_batched(*_states(2, 33, 8, 0))
+    with pytest.raises(ValueError, match="D = 65"):
+        gsmvi_amd.GSMBatch(2, 65, None, lambda X: -X)
+    with pytest.raises(ValueError, match="B = 33"):
+        gsmvi_amd.GSMBatch(2, 8, None, lambda X: -X).fit([1, 2], batch_size=33, niter=2, verbose=False)
+    cov = np.broadcast_to(np.eye(4), (6, 4, 4)).copy()
+    cov[4] = -np.eye(4)
+    with pytest.raises(ValueError, match=r"\[4\]"):
+        gsmvi_amd.GSMBatch(6, 4, None, lambda X: -X).fit(range(6), cov=cov, niter=2, verbose=False)
+
+
+def test_device_score_and_torch_results():
+    import gsmvi_amd
+    K, D, B = 5, 8, 4
+    ms, covs, Ps = _targets(K, D, 90)
+    tgt = gsmvi_amd.BatchedGaussianTarget(ms, cov=covs)
+    X = torch.randn(K, B, D, dtype=torch.float64, device="cuda")
+    G = tgt.lp_g(X).cpu().numpy()
+    Xn = X.cpu().numpy()
+    orc = _orc()
+    for k in range(K):
+        assert rel_err(G[k], orc.gaussian_score(Xn[k], ms[k], np.linalg.inv(covs[k]))) < 1e-12
+    lp = tgt.lp(X).cpu().numpy()
+    assert lp.shape == (K,) and all(abs(lp[k] - orc.gaussian_logp(Xn[k], ms[k], tgt.P[k].cpu().numpy())) < 1e-9 * (1 + abs(lp[k]))
+                                    for k in range(K))
+    mean, cov = gsmvi_amd.GSMBatch(K, D, tgt.lp, tgt.lp_g).fit(torch.arange(K), batch_size=B, niter=80, verbose=False,
+                                                               as_torch=True)
+    assert isinstance(mean, torch.Tensor) and mean.is_cuda and cov.shape == (K, D, D)
