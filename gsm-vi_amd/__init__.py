@@ -5,6 +5,9 @@ Mirrors the reference's public surface for the hot path (reference file:line):
     gsm_update_batched, GSMBatch,
     BatchedGaussianTarget (K problems at once,
     D <= 64: jax.vmap(gsm_update) and its fit)   gsmvi/gsm.py:31-58, gsmvi/gsm_numpy.py:77-129
+    bam_update_batched, BaMBatch (K problems at
+    once, D <= 64: jax.vmap(bam_update) and the
+    dense BaM loop, no retries)                  gsmvi/bam.py:31-114, gsmvi/bam.py:140-216
     BaM, bam_update, bam_lowrank_update,
     Regularizers                                 gsmvi/bam.py:31-274
     KLMonitor (diagnostics callback, host side),
@@ -23,6 +26,7 @@ from .bam import BaM, bam_update, bam_lowrank_update, Regularizers   # noqa: F40
 from .targets import GaussianTarget, device_score, score_from_logp   # noqa: F401
 from .targets import BatchedGaussianTarget                           # noqa: F401
 from .batched import GSMBatch, gsm_update_batched                    # noqa: F401
+from .batched import BaMBatch, bam_update_batched, bam_lowrank_update_batched   # noqa: F401
 from .monitors import KLMonitor, DeviceKLMonitor                     # noqa: F401
 from .initializers import lbfgs_init                                 # noqa: F401
 from .advi import ADVI                                               # noqa: F401

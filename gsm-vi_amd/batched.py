@@ -1,24 +1,27 @@
-"""Batched GSM: K independent problems of the same (D, B) in one launch per step (csrc/gsmvi_batched.hip).
+"""Batched GSM and BaM: K independent problems of the same (D, B) in one launch per step (csrc/gsmvi_batched.hip,
+csrc/gsmvi_bam_batched.hip).
 
-The reference's update is a pure function of (samples, vs, mu0, S0) (gsmvi/gsm.py:31-58), so ``jax.vmap(gsm_update)`` batches
-it over a leading problem axis; ``gsm_update_batched`` is that call.  ``GSMBatch.fit`` runs the dense fit of gsm_numpy.py:77-129
-for K problems at once: one launch plus the score call per iteration, whatever K is.  Bounds: 1 <= D <= 64, 1 <= B <= 32.
+The reference's updates are pure functions of (samples, vs, mu0, S0[, reg]) (gsmvi/gsm.py:31-58, gsmvi/bam.py:31-114), so
+``jax.vmap`` batches them over a leading problem axis; ``gsm_update_batched`` and ``bam_update_batched`` are those calls.
+``GSMBatch.fit`` runs the dense fit of gsm_numpy.py:77-129 and ``BaMBatch.fit`` the dense loop of bam.py:140-216 for K
+problems at once: one launch plus the score call per iteration, whatever K is.  Bounds: 1 <= D <= 64, 1 <= B <= 32.
 """
 import numpy as np
 
 from ._fitloop import Progress, _is_torch, result, scorer, seed_of, takes_out
 from .engine import get_engine
+from .bam import _every as _bam_every
 from .gsm import _every
 
 MAX_D = 64
 MAX_B = 32
 
 
-def _check_bounds(D, B):
+def _check_bounds(D, B, what="batched GSM"):
     if not 1 <= D <= MAX_D:
-        raise ValueError(f"batched GSM: D = {D} is outside 1 <= D <= {MAX_D} (one problem per workgroup, held in LDS)")
+        raise ValueError(f"{what}: D = {D} is outside 1 <= D <= {MAX_D} (one problem per workgroup, held in LDS)")
     if not 1 <= B <= MAX_B:
-        raise ValueError(f"batched GSM: batch size B = {B} is outside 1 <= B <= {MAX_B}")
+        raise ValueError(f"{what}: batch size B = {B} is outside 1 <= B <= {MAX_B}")
 
 
 def _shape(x):
@@ -47,14 +50,14 @@ def gsm_update_batched(samples, vs, mu0, S0, engine=None):
     return (mu, S) if want_torch else (eng.to_numpy(mu), eng.to_numpy(S))
 
 
-def _seeds(keys, K):
-    """problem k's stream seed: ``seed_of(keys[k])``, as GSM.fit takes it from its key"""
+def _seeds(keys, K, who="GSMBatch.fit", last=False):
+    """problem k's stream seed: ``seed_of(keys[k], last)``, as GSM.fit (last=False) or BaM.fit (last=True) takes it from its key"""
     if _is_torch(keys):
         keys = keys.detach().cpu().numpy()
     keys = list(np.asarray(keys).reshape(-1)) if not isinstance(keys, (list, tuple)) else list(keys)
     if len(keys) != K:
-        raise ValueError(f"GSMBatch.fit: {len(keys)} keys for K = {K} problems")
-    return [seed_of(int(k), last=False) for k in keys]
+        raise ValueError(f"{who}: {len(keys)} keys for K = {K} problems")
+    return [seed_of(int(k), last=last) for k in keys]
 
 
 class GSMBatch:
@@ -125,6 +128,125 @@ class GSMBatch:
             G = score(X, out=Gbuf) if out_ok else score(X)
             nxt = draw and i < niter
             eng.gsm_fit_step_batched(X, G, mean_t, cov_t, R if draw else None, None, n_rev, seeds_t if nxt else None, i + 1)
+        progress.flush()
+        self.n_reverts = eng.read_ints(n_rev)
+        return result(eng, mean_t, cov_t, as_torch)
+
+
+def _reg_values(reg, K, who):
+    """a regulariser as the engine takes it: a float, or K per-problem values (ValueError for any other length)"""
+    if _is_torch(reg):
+        reg = reg.detach().cpu().numpy()
+    r = np.asarray(reg, dtype=np.float64)
+    if r.ndim == 0:
+        return float(r)
+    r = r.reshape(-1)
+    if r.size != K:
+        raise ValueError(f"{who}: reg has {r.size} values for K = {K} problems (give one float or K values)")
+    return r
+
+
+def bam_update_batched(samples, vs, mu0, S0, reg, jitter=0.0, engine=None):
+    """``jax.vmap(bam_update)`` over K problems (gsmvi/bam.py:31-114): slice k of the result is
+    ``bam_update(samples[k], vs[k], mu0[k], S0[k], reg[k])``, symmetrised, with ``jitter`` on its diagonal (bam.py:198-199).
+
+    Inputs (K,B,D), (K,B,D), (K,D), (K,D,D); ``reg`` one float or K values.  Returns new ``(mu, S)`` of shapes (K,D), (K,D,D)
+    and never modifies its inputs.  numpy in -> float64 numpy out; CUDA torch tensors in -> torch out.  Shape errors raise
+    AssertionError like the reference (bam.py:47-48); D or B outside 1 <= D <= 64, 1 <= B <= 32, or a reg of another length
+    than K, raise ValueError before any device work.  The exact rank-B factor of U replaces ARPACK's (as ``bam_update``), so
+    B > D is legal.  A problem whose B x B chain fails (non-finite input) comes back as NaN; the others are unaffected.
+    """
+    assert len(samples.shape) == 3
+    assert len(vs.shape) == 3
+    K, B, D = _shape(samples)
+    assert _shape(vs) == (K, B, D) and _shape(mu0) == (K, D) and _shape(S0) == (K, D, D)
+    _check_bounds(D, B, "batched BaM")
+    r = _reg_values(reg, K, "bam_update_batched")
+    eng = engine if engine is not None else get_engine()
+    want_torch = _is_torch(samples)
+    Xd, Gd, m0, S0d = (eng.asarray(a).contiguous() for a in (samples, vs, mu0, S0))
+    mu, S = eng.bam_update_batched(Xd, Gd, m0, S0d, r if isinstance(r, float) else eng.batched_regs(r), float(jitter))
+    return (mu, S) if want_torch else (eng.to_numpy(mu), eng.to_numpy(S))
+
+
+def bam_lowrank_update_batched(samples, vs, mu0, S0, reg, jitter=0.0, engine=None):
+    """``jax.vmap(bam_lowrank_update)`` (gsmvi/bam.py:72-114): the same call as ``bam_update_batched``."""
+    return bam_update_batched(samples, vs, mu0, S0, reg, jitter=jitter, engine=engine)
+
+
+class BaMBatch:
+    """K independent BaM fits of the same dimension D (gsmvi/bam.py:117-216, the dense loop), one launch per iteration.
+
+    K    : number of problems.
+    D    : dimensionality, 1 <= D <= 64.
+    lp   : batched log-density (kept for symmetry with BaM; the fit does not call it).
+    lp_g : score (K,B,D) -> (K,B,D), as for GSMBatch (a plain callable gets numpy arrays; a ``device_native`` one float64
+           CUDA tensors).
+    """
+
+    def __init__(self, K, D, lp, lp_g, engine=None):
+        self.K, self.D = int(K), int(D)
+        if self.K < 1:
+            raise ValueError(f"BaMBatch: K = {K} must be at least 1")
+        _check_bounds(self.D, 1, "batched BaM")
+        self.lp = lp
+        self.lp_g = lp_g
+        self._engine = engine
+
+    def fit(self, keys, regf, mean=None, cov=None, batch_size=2, niter=5000, nprint=10, verbose=True, jitter=1e-6, *,
+            forced_samples=None, as_torch=False, monitor=None):
+        """Fit N(mean_k, cov_k) to target k for every k; returns (mean (K,D), cov (K,D,D)) and sets ``n_reverts`` (K ints).
+
+        Problem k is the computation of ``BaM(D, lp_k, lp_g_k).fit(keys[k], regf, method="dense", rng="device", ...)`` with the
+        same draws: the z of iteration i is call i of the Philox stream seeded by ``seed_of(keys[k], last=True)`` (odd D: B x
+        (D + 1) normals per call, column D dropped); only the round-off differs.  Per problem and iteration (bam.py:189-212):
+        the update with reg = regf(i), + jitter I, symmetrised, the Cholesky test, accept or revert of mean, cov and sampling
+        factor (kept bit for bit on a revert), the next samples -- one launch after the score.  ``regf(i)`` is called exactly
+        once per iteration and returns one float or K values (one per problem); ``Regularizers()`` schedules work as in
+        BaM.fit.  ``mean`` / ``cov``: (K,D) / (K,D,D), zeros and identities by default; a cov[k] that is not positive definite
+        raises ValueError naming k.  ``forced_samples``: (niter+1, K, B, D) teacher-forced samples.
+        Deviation from bam.py:189-206: there is no retry loop.  The device update never raises; a failed chain or a
+        non-finite score reverts its own problem alone (counted in ``n_reverts``).  An exception from the score or from
+        ``regf`` propagates.  ``monitor`` is not supported (TypeError).
+        """
+        if monitor is not None:
+            raise TypeError("BaMBatch.fit does not support a monitor; fit without one (or use BaM.fit per problem)")
+        K, D, B = self.K, self.D, int(batch_size)
+        niter = int(niter)
+        _check_bounds(D, B, "batched BaM")
+        seeds = _seeds(keys, K, "BaMBatch.fit", last=True)
+        if mean is not None:
+            assert _shape(mean) == (K, D), f"mean: expected shape {(K, D)}"
+        if cov is not None:
+            assert _shape(cov) == (K, D, D), f"cov: expected shape {(K, D, D)}"
+        if forced_samples is not None:
+            assert _shape(forced_samples) == (niter + 1, K, B, D), f"forced_samples: expected shape {(niter + 1, K, B, D)}"
+        eng = self._engine if self._engine is not None else get_engine()
+        mean_t = eng.zeros(K, D) if mean is None else eng.clone(mean).reshape(K, D)
+        cov_t = eng.eye_batch(K, D) if cov is None else eng.clone(cov).reshape(K, D, D)
+        draw = forced_samples is None
+        R = eng.empty(K, D, D)
+        X = eng.empty(K, B, D)
+        info, n_rev = eng.batched_ints(K), eng.batched_ints(K)
+        seeds_t = eng.batched_seeds(seeds) if draw else None
+        eng.gsm_fit_init_batched(mean_t, cov_t, R, info, seeds_t, X if draw else None)     # a BaM fit starts as a GSM fit
+        bad = np.flatnonzero(eng.read_ints(info))
+        if bad.size:
+            raise ValueError(f"BaMBatch.fit: initial covariance is not positive definite for problem(s) {bad.tolist()}")
+        score = scorer(eng, self.lp_g)
+        out_ok = not getattr(self.lp_g, "device_native", False) or takes_out(self.lp_g)
+        Gbuf = eng.empty(K, B, D)
+        progress = Progress(eng, n_rev, niter, _bam_every(nprint, niter), verbose, read=lambda t: int(eng.read_ints(t).sum()))
+        for i in range(niter + 1):
+            progress.tick(i)
+            if not draw:
+                X = eng.asarray(forced_samples[i])
+            G = score(X, out=Gbuf) if out_ok else score(X)
+            reg = _reg_values(regf(i), K, "BaMBatch.fit")
+            nxt = draw and i < niter
+            eng.bam_fit_step_batched(X, G, mean_t, cov_t, R if draw else None,
+                                     reg if isinstance(reg, float) else eng.batched_regs(reg), float(jitter), None, n_rev,
+                                     seeds_t if nxt else None, i + 1)
         progress.flush()
         self.n_reverts = eng.read_ints(n_rev)
         return result(eng, mean_t, cov_t, as_torch)

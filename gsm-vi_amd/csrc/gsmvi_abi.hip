@@ -24,6 +24,7 @@ size_t gsmvi_cov_update_lds_bytes(int SB);
 hipError_t gsmvi_cov_update_prepare();
 hipError_t gsmvi_bam_prepare();
 hipError_t gsmvi_batched_prepare();
+hipError_t gsmvi_bam_batched_prepare();
 void gsmvi_launch_gsm_cov_update(hipStream_t st, hipEvent_t* ev, int D, int B, const double* rec, int ldrec,
                                  const double* mu0, const double* S0, int lds0, double* S, int lds, double* mu_out,
                                  int SB, int s_vec_ok, int row0, int nrows);
@@ -243,6 +244,7 @@ int gsmvi_create(gsmvi_ctx** out, int device, int max_D, int max_B) {
     if (e == hipSuccess) e = gsmvi_cov_update_prepare();
     if (e == hipSuccess) e = gsmvi_bam_prepare();
     if (e == hipSuccess) e = gsmvi_batched_prepare();
+    if (e == hipSuccess) e = gsmvi_bam_batched_prepare();
     for (int k = 0; k < 8 && e == hipSuccess; ++k) e = hipEventCreate(&c->ev[k]);
     if (e == hipSuccess) e = hipStreamCreateWithFlags(&c->side, hipStreamNonBlocking);
     if (e == hipSuccess) e = hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming);
@@ -303,6 +305,7 @@ int gsmvi_set_tuning(gsmvi_ctx* ctx, const char* name, int value) {
     else if (!strcmp(name, "bam_hint_slack")) ctx->tune_bam_hint_slack = value;
     else if (!strcmp(name, "rider_direct_max_D")) ctx->tune_rider_direct_max_D = value;
     else if (!strcmp(name, "chain_pair")) ctx->tune_chain_pair = value;
+    else if (!strcmp(name, "bam_batched_pad")) ctx->tune_bam_batched_pad = value;
     else if (!strcmp(name, "lowrank_kp")) ctx->tune_lowrank_kp = value;
     else if (!strcmp(name, "bam_basis")) ctx->tune_bam_basis = value;
     else if (!strcmp(name, "scalars_nt")) ctx->tune_scalars_nt = value;

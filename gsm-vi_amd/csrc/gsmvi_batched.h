@@ -1,0 +1,152 @@
+// Shared pieces of the batched kernels (gsmvi_batched.hip: GSM, gsmvi_bam_batched.hip: BaM): the bounds,
+// the argument block, and the tail of a fit step that both methods run on their new covariance S' -- the in-LDS Cholesky
+// test, per-problem accept or revert of (mean, cov, sampling factor), and the next samples from the problem's Philox stream.
+#pragma once
+#include <hip/hip_runtime.h>
+#include "gsmvi_philox.h"
+#include <cstdint>
+
+#define GB_MAX_D 64
+#define GB_MAX_B 32
+
+struct gb_args {
+    long long K;
+    int D, B;
+    const double* X;     // UPDATE, STEP: (K, B, D) samples
+    const double* V;     // UPDATE, STEP: (K, B, D) scores
+    const double* mu0;   // UPDATE: (K, D)
+    const double* S0;    // UPDATE: (K, D, D)
+    double* mu;          // UPDATE: output; STEP: the state's mean (in / out); INIT: the mean (in)
+    double* S;           // UPDATE: output; STEP: the state's covariance (in / out); INIT: the covariance (in)
+    double* R;           // STEP, INIT: the sampling factor, (K, D, D) upper triangular (in / out); may be null in STEP
+    int* info;           // STEP, INIT: (K) 0 = positive definite, else 1 + the first bad pivot; may be null
+    int* n_rev;          // STEP: (K) incremented on a revert; may be null
+    const unsigned long long* seeds;   // STEP, INIT: (K) the problems' draw keys; null = no draw
+    unsigned long long call;           // draw number of the samples written
+    double* Xout;        // STEP, INIT: (K, B, D) next samples (may alias X: each slot reads its X before it writes)
+    // BaM only (gsmvi_bam_batched.hip)
+    double reg;          // the regulariser of every problem ...
+    const double* reg_dev;   // ... or (K) per-problem values on the device (null: `reg`)
+    double jitter;       // added to the diagonal of S' (bam.py:198)
+    int ld, ldn;         // LDS row strides of the D x D and n x n arrays
+};
+
+// padded draw row: an odd-D problem takes B x (D + 1) normals per draw, column D dropped (the layout of the single fit, _oddpad.py)
+__host__ __device__ inline int gb_dz(int D) { return D + (D & 1); }
+
+// The tail of a fit step (MODE_INIT = false) or of the fit's start (MODE_INIT = true), for the problem of one workgroup slot:
+//   S    (LDS, D x D, row stride ld)  S' on entry (only the upper triangle is used), its upper Cholesky factor on exit
+//   sreg (registers) the entries e = l + q NT of S' (row-major, stride D): what an accept writes to the state's covariance
+//   pv   (LDS, D) pivots;  Zb (LDS, B x Dz) the draws;  m0 the kept mean, m1 the new mean (LDS, D each)
+// Right-looking Cholesky, one pivot per barrier (unscaled rows: row c is final after step c and is scaled by 1 / sqrt(a_cc)
+// at the end).  Every thread of a slot reads the same pivot, so `info` is uniform in it.  A pivot that is not > 0 and finite
+// (NaN included: any NaN of S reaches a later pivot) fails, as np.linalg.cholesky does or the reference's NaN test catches
+// (gsm_numpy.py:139-146).  The loop always runs D steps (uniform barriers).  Then per problem: accept -> mean, cov, factor
+// written; revert -> nothing of the state is written, n_rev[k] += 1.  With a.seeds: X = m + z R, z = draw a.call of the
+// problem's stream (element n = b Dz + j, pair n / 2, gsmvi_rng.hip), from the kept or accepted state.
+template <int NT, int MAXE, bool MODE_INIT>
+__device__ __forceinline__ void gb_fit_tail(const gb_args& a, bool valid, long long k, int l, int ld, double* S,
+                                            const double (&sreg)[MAXE], double* pv, double* Zb, const double* m0, double* m1) {
+    const int D = a.D, B = a.B, Dz = gb_dz(D), DD = D * D, BD = B * D;
+    const size_t kd = (size_t)(valid ? k : 0) * D, kdd = (size_t)(valid ? k : 0) * DD, kbd = (size_t)(valid ? k : 0) * BD;
+    int info = 0;
+    for (int c = 0; c < D; ++c) {
+        const double acc_ = S[c * ld + c];
+        if (info == 0 && !(acc_ > 0.0 && acc_ < __builtin_huge_val())) info = c + 1;
+        const double piv = sqrt(acc_), inv = 1.0 / piv;
+        if (l == 0) pv[c] = piv;
+        if (valid) {
+#pragma unroll
+            for (int q = 0; q < MAXE; ++q) {
+                const int e = l + q * NT;
+                if (e < DD) {
+                    const int i = e / D, j = e - i * D;
+                    if (i > c && j >= i) S[i * ld + j] -= (S[c * ld + i] * inv) * (S[c * ld + j] * inv);
+                }
+            }
+        }
+        __syncthreads();
+    }
+    if (valid) {
+#pragma unroll
+        for (int q = 0; q < MAXE; ++q) {
+            const int e = l + q * NT;
+            if (e < DD) {
+                const int i = e / D, j = e - i * D;
+                S[i * ld + j] = j > i ? S[i * ld + j] / pv[i] : (j == i ? pv[i] : 0.0);
+            }
+        }
+    }
+
+    if (valid) {
+        if (MODE_INIT) {
+            if (a.R)
+#pragma unroll
+                for (int q = 0; q < MAXE; ++q) {
+                    const int e = l + q * NT;
+                    if (e < DD) {
+                        const int i = e / D, j = e - i * D;
+                        a.R[kdd + e] = S[i * ld + j];
+                    }
+                }
+        } else if (info == 0) {                                         // accept: mean, cov, factor   (gsm_numpy.py:121-123)
+            for (int i = l; i < D; i += NT) a.mu[kd + i] = m1[i];
+#pragma unroll
+            for (int q = 0; q < MAXE; ++q) {
+                const int e = l + q * NT;
+                if (e < DD) {
+                    const int i = e / D, j = e - i * D;
+                    a.S[kdd + e] = sreg[q];
+                    if (a.R) a.R[kdd + e] = S[i * ld + j];
+                }
+            }
+        } else {                                                        // revert: nothing of the state is written (:124-125)
+            if (l == 0 && a.n_rev) a.n_rev[k] += 1;
+            for (int i = l; i < D; i += NT) m1[i] = m0[i];              // the next samples come from the kept state
+            if (a.R && a.seeds)
+#pragma unroll
+                for (int q = 0; q < MAXE; ++q) {
+                    const int e = l + q * NT;
+                    if (e < DD) {
+                        const int i = e / D, j = e - i * D;
+                        S[i * ld + j] = a.R[kdd + e];
+                    }
+                }
+        }
+        if (l == 0 && a.info) a.info[k] = info;
+    }
+    if (!a.seeds) return;                                               // (uniform: no barrier follows)
+
+    __syncthreads();
+    if (valid) {
+        const unsigned long long seed = a.seeds[k], call = a.call;
+        for (int p = l; p < (B * Dz) / 2; p += NT) {
+            unsigned w[4];
+            philox4x32_10((unsigned)p, 0u, (unsigned)call, (unsigned)(call >> 32), (unsigned)seed, (unsigned)(seed >> 32), w);
+            philox_normal_pair(w, Zb[2 * p], Zb[2 * p + 1]);
+        }
+    }
+    __syncthreads();
+    if (valid) {
+        for (int e = l; e < BD; e += NT) {
+            const int b = e / D, j = e - b * D;
+            double s = 0.0;
+            for (int i = 0; i <= j; ++i) s += Zb[b * Dz + i] * S[i * ld + j];
+            a.Xout[kbd + e] = s + m1[j];
+        }
+    }
+}
+
+// ---- host side: argument checks shared by the batched entry points ----------------------------------------------------
+static inline bool gb_overlap(const void* a, size_t na, const void* b, size_t nb) {
+    const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
+    return x < y + nb && y < x + na;
+}
+
+#define GB_BAD(cond, msg)                             \
+    do {                                              \
+        if (cond) {                                   \
+            gsmvi_set_error("%s: %s", __func__, msg); \
+            return GSMVI_ERR_BAD_ARG;                 \
+        }                                             \
+    } while (0)

@@ -17,34 +17,12 @@
 // A workgroup reads and writes only its own problems' slices, so nothing -- a revert, a NaN -- crosses between problems.
 #include "gsmvi_common.h"
 #include "gsmvi_ctx.h"
-#include "gsmvi_philox.h"
+#include "gsmvi_batched.h"
 #include "../../include/gsmvi_hip.h"
 #include <cstdint>
 
-#define GB_MAX_D 64
-#define GB_MAX_B 32
-
 enum { GB_UPDATE = 0, GB_STEP = 1, GB_INIT = 2 };
 
-struct gb_args {
-    long long K;
-    int D, B;
-    const double* X;     // UPDATE, STEP: (K, B, D) samples
-    const double* V;     // UPDATE, STEP: (K, B, D) scores
-    const double* mu0;   // UPDATE: (K, D)
-    const double* S0;    // UPDATE: (K, D, D)
-    double* mu;          // UPDATE: output; STEP: the state's mean (in / out); INIT: the mean (in)
-    double* S;           // UPDATE: output; STEP: the state's covariance (in / out); INIT: the covariance (in)
-    double* R;           // STEP, INIT: the sampling factor, (K, D, D) upper triangular (in / out); may be null in STEP
-    int* info;           // STEP, INIT: (K) 0 = positive definite, else 1 + the first bad pivot; may be null
-    int* n_rev;          // STEP: (K) incremented on a revert; may be null
-    const unsigned long long* seeds;   // STEP, INIT: (K) the problems' draw keys; null = no draw
-    unsigned long long call;           // draw number of the samples written
-    double* Xout;        // STEP, INIT: (K, B, D) next samples (may alias X: each slot reads its X before it writes)
-};
-
-// padded draw row: an odd-D problem takes B x (D + 1) normals per draw, column D dropped (the layout of the single fit, _oddpad.py)
-__host__ __device__ inline int gb_dz(int D) { return D + (D & 1); }
 // LDS doubles per problem: S (D x D) + d (B x D) + g / z (B x Dz) + S0 g / e (B x D) + mu0, mu, pivots (D each) + 2 B scalars
 __host__ __device__ inline int gb_lds_doubles(int D, int B) { return D * D + 2 * B * D + B * gb_dz(D) + 3 * D + 2 * B; }
 static inline int gb_nt(int D) { return D <= 16 ? 64 : 256; }
@@ -148,90 +126,7 @@ __global__ __launch_bounds__(256) void k_gsm_batched(gb_args a) {
     }
     __syncthreads();
 
-    // Upper Cholesky R^T R = S in place, one pivot per barrier (right-looking, unscaled rows: row c is final after step c and
-    // is scaled by 1 / sqrt(a_cc) at the end).  Every thread of a problem reads the same pivot, so `info` is uniform in it.
-    // A pivot that is not > 0 and finite (NaN included: any NaN of S reaches a later pivot) fails, as np.linalg.cholesky
-    // does or the reference's NaN test catches (gsm_numpy.py:139-146).  The loop always runs D steps (uniform barriers).
-    int info = 0;
-    for (int c = 0; c < D; ++c) {
-        const double acc_ = S[c * D + c];
-        if (info == 0 && !(acc_ > 0.0 && acc_ < __builtin_huge_val())) info = c + 1;
-        const double piv = sqrt(acc_), inv = 1.0 / piv;
-        if (l == 0) pv[c] = piv;
-        if (valid) {
-#pragma unroll
-            for (int q = 0; q < MAXE; ++q) {
-                const int e = l + q * NT;
-                if (e < DD) {
-                    const int i = e / D, j = e - i * D;
-                    if (i > c && j >= i) S[e] -= (S[c * D + i] * inv) * (S[c * D + j] * inv);
-                }
-            }
-        }
-        __syncthreads();
-    }
-    if (valid) {
-#pragma unroll
-        for (int q = 0; q < MAXE; ++q) {
-            const int e = l + q * NT;
-            if (e < DD) {
-                const int i = e / D, j = e - i * D;
-                S[e] = j > i ? S[e] / pv[i] : (j == i ? pv[i] : 0.0);
-            }
-        }
-    }
-
-    if (valid) {
-        if (MODE == GB_INIT) {
-            if (a.R)
-#pragma unroll
-                for (int q = 0; q < MAXE; ++q) {
-                    const int e = l + q * NT;
-                    if (e < DD) a.R[kdd + e] = S[e];
-                }
-        } else if (info == 0) {                                         // accept: mean, cov, factor   (gsm_numpy.py:121-123)
-            for (int i = l; i < D; i += NT) a.mu[kd + i] = m1[i];
-#pragma unroll
-            for (int q = 0; q < MAXE; ++q) {
-                const int e = l + q * NT;
-                if (e < DD) {
-                    a.S[kdd + e] = sreg[q];
-                    if (a.R) a.R[kdd + e] = S[e];
-                }
-            }
-        } else {                                                        // revert: nothing of the state is written (:124-125)
-            if (l == 0 && a.n_rev) a.n_rev[k] += 1;
-            for (int i = l; i < D; i += NT) m1[i] = m0[i];              // the next samples come from the kept state
-            if (a.R && a.seeds)
-#pragma unroll
-                for (int q = 0; q < MAXE; ++q) {
-                    const int e = l + q * NT;
-                    if (e < DD) S[e] = a.R[kdd + e];
-                }
-        }
-        if (l == 0 && a.info) a.info[k] = info;
-    }
-    if (!a.seeds) return;                                               // (uniform: no barrier follows)
-
-    // the next samples: z = draw `call` of the problem's stream (element n = b Dz + j, pair n / 2, gsmvi_rng.hip), X = m + z R
-    __syncthreads();
-    if (valid) {
-        const unsigned long long seed = a.seeds[k], call = a.call;
-        for (int p = l; p < (B * Dz) / 2; p += NT) {
-            unsigned w[4];
-            philox4x32_10((unsigned)p, 0u, (unsigned)call, (unsigned)(call >> 32), (unsigned)seed, (unsigned)(seed >> 32), w);
-            philox_normal_pair(w, Gm[2 * p], Gm[2 * p + 1]);
-        }
-    }
-    __syncthreads();
-    if (valid) {
-        for (int e = l; e < BD; e += NT) {
-            const int b = e / D, j = e - b * D;
-            double s = 0.0;
-            for (int i = 0; i <= j; ++i) s += Gm[b * Dz + i] * S[i * D + j];
-            a.Xout[kbd + e] = s + m1[j];
-        }
-    }
+    gb_fit_tail<NT, MAXE, MODE == GB_INIT>(a, valid, k, l, D, S, sreg, pv, Gm, m0, m1);
 }
 
 // G_k = -(X_k - 1 m_k^T) P_k: one thread per output entry (consecutive threads = consecutive columns of P_k: coalesced)
@@ -262,19 +157,6 @@ hipError_t gsmvi_batched_prepare() {
     }
     return hipSuccess;
 }
-
-static bool gb_overlap(const void* a, size_t na, const void* b, size_t nb) {
-    const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
-    return x < y + nb && y < x + na;
-}
-
-#define GB_BAD(cond, msg)                             \
-    do {                                              \
-        if (cond) {                                   \
-            gsmvi_set_error("%s: %s", __func__, msg); \
-            return GSMVI_ERR_BAD_ARG;                 \
-        }                                             \
-    } while (0)
 
 static int gb_check(gsmvi_ctx* ctx, int64_t K, int D, int B, const char* fn) {
     if (!ctx) { gsmvi_set_error("%s: %s", fn, "ctx is NULL"); return GSMVI_ERR_BAD_ARG; }

@@ -104,6 +104,7 @@ struct gsmvi_ctx {
                                           // finished output): it is hidden behind the ~35 us chain either way (0: never)
     int tune_bam_full = 0;     // 1 = always enqueue every Newton-Schulz step (ignore the hint; tests)
     int tune_lowrank_kp = 0;   // 64: BaM's low-rank update stages 64 rows per pass for KF > 96 (A/B runs: measured equal to 32)
+    int tune_bam_batched_pad = 1;   // batched BaM: odd LDS row strides D | 1, B | 1 (0: the unpadded strides D, B; A/B runs)
     int tune_chain_pair = 1;   // two-level chain (128 < 2B <= 256): independent one-workgroup factorisations share a launch (0: A/B runs)
     gsmf_bam_mean bam_mean = {nullptr, nullptr, {0.0, nullptr}};
     int bam_mean_done = 0;

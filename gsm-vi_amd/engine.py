@@ -583,7 +583,8 @@ class HipEngine:
     # kernel-family bits of include/gsmvi_hip.h (GSMVI_PATH_*)
     PATH_BITS = {"panel_fast": 0x1, "panel_wide": 0x2, "panel_generic": 0x4, "panel_t_fast": 0x8, "panel_t_generic": 0x10,
                  "scalars_fast": 0x20, "scalars_generic": 0x40, "cov_sym": 0x80, "cov_generic": 0x100, "fupd_fast": 0x200,
-                 "fupd_generic": 0x400, "lowrank_fast": 0x800, "lowrank_generic": 0x1000, "batched": 0x2000}
+                 "fupd_generic": 0x400, "lowrank_fast": 0x800, "lowrank_generic": 0x1000, "batched": 0x2000,
+                 "batched_bam": 0x4000}
     PATH_GENERIC_MASK = 0x4 | 0x10 | 0x40 | 0x100 | 0x400 | 0x1000
 
     def last_path(self, reset=True):
@@ -737,6 +738,47 @@ class HipEngine:
             self._ctx, self._stream(), K, D, B, self._packed(X, (K, B, D), "X"), self._packed(m, (K, D), "m"),
             self._packed(P, (K, D, D), "P"), self._packed(G, (K, B, D), "G")))
         return G
+
+    # ---- batched BaM: K independent problems of one (D, B) (csrc/gsmvi_bam_batched.hip) -----------------------------------
+    def _reg_arg(self, reg, K):
+        """(scalar, device pointer) of a regulariser: a number -> (reg, NULL); a (K,) float64 CUDA tensor -> (0, its data)"""
+        if isinstance(reg, torch.Tensor):
+            assert reg.is_cuda and reg.dtype == torch.float64 and reg.is_contiguous() and reg.numel() == K, \
+                f"reg: expected a contiguous float64 CUDA tensor of {K} entries"
+            return 0.0, C.c_void_p(reg.data_ptr())
+        return float(reg), None
+
+    def batched_regs(self, values):
+        """K per-problem regularisers as a device float64 tensor"""
+        return torch.as_tensor(np.asarray(values, dtype=np.float64).reshape(-1), device=self.device)
+
+    def bam_update_batched(self, X, G, mu0, S0, reg, jitter=0.0, out=None, info=None):
+        """(mu_k, S_k) = bam_update(X_k, G_k, mu0_k, S0_k, reg_k) for every k  [gsmvi/bam.py:72-114 under jax.vmap]; S_k
+        symmetrised, jitter on its diagonal; ``reg`` a number or a (K,) device tensor; info[k] != 0: problem k's chain failed
+        (its outputs are NaN)."""
+        K, B, D = X.shape
+        self._ensure(max(self._max_D, 1), max(self._max_B, 1))
+        mu, S = (self.empty(K, D), self.empty(K, D, D)) if out is None else out
+        r, rp = self._reg_arg(reg, K)
+        _lib.check("gsmvi_bam_update_batched_f64", self.lib.gsmvi_bam_update_batched_f64(
+            self._ctx, self._stream(), K, D, B, self._packed(X, (K, B, D), "samples"), self._packed(G, (K, B, D), "vs"),
+            self._packed(mu0, (K, D), "mu0"), self._packed(S0, (K, D, D), "S0"), r, rp, float(jitter),
+            self._packed(mu, (K, D), "mu"), self._packed(S, (K, D, D), "S"), self._ints(info, K, "info")))
+        return mu, S
+
+    def bam_fit_step_batched(self, X, G, mean, cov, R=None, reg=1.0, jitter=0.0, info=None, n_reverts=None, seeds=None,
+                             call=0):
+        """One batched BaM fit iteration after the score (csrc/gsmvi_bam_batched.hip): update + jitter I, Cholesky test and
+        accept / revert of (mean, cov, R) per problem; with ``seeds`` X is overwritten with the samples of draw ``call``."""
+        K, B, D = X.shape
+        self._ensure(max(self._max_D, 1), max(self._max_B, 1))
+        r, rp = self._reg_arg(reg, K)
+        px = self._packed(X, (K, B, D), "X")
+        _lib.check("gsmvi_bam_fit_step_batched_f64", self.lib.gsmvi_bam_fit_step_batched_f64(
+            self._ctx, self._stream(), K, D, B, px, self._packed(G, (K, B, D), "G"), self._packed(mean, (K, D), "mean"),
+            self._packed(cov, (K, D, D), "cov"), self._packed(R, (K, D, D), "R") if R is not None else None, r, rp,
+            float(jitter), self._ints(info, K, "info"), self._ints(n_reverts, K, "n_reverts"),
+            C.c_void_p(seeds.data_ptr()) if seeds is not None else None, int(call), px if seeds is not None else None))
 
     def bam_update(self, X, G, mu0, S0, reg, jitter=0.0, out=None, flag=None):
         """(mu, S) of BaM [gsmvi/bam.py:72-114]; S symmetrised, jitter on the diagonal."""

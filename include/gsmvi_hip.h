@@ -15,6 +15,8 @@
  *   jax.vmap(gsm_update) over K problems, D <= 64 (gsm.py:31-58)       ->  gsmvi_gsm_update_batched_f64
  *   gsm_numpy.py:77-129 fit of K problems (dense form), D <= 64         ->  gsmvi_gsm_fit_{init,step}_batched_f64
  *   (no reference twin; gsm_numpy.py:4-55 in factor form)   ->  gsmvi_gsm_factor_update_f64
+ *   jax.vmap(bam_update) over K problems, D <= 64 (bam.py:31-114)      ->  gsmvi_bam_update_batched_f64
+ *   bam.py:189-212 fit iteration of K problems (dense), D <= 64         ->  gsmvi_bam_fit_step_batched_f64
  *   gsmvi/bam.py:72-114       bam_lowrank_update(samples,vs,mu0,S0,reg) ->  gsmvi_bam_update_f64
  *   gsmvi/bam.py:31-69        bam_update(samples,vs,mu0,S0,reg)         ->  gsmvi_bam_update_f64 (same result, K6)
  *
@@ -79,7 +81,8 @@ int gsmvi_destroy(gsmvi_ctx* ctx);
  * "rider_direct_max_D" (largest D at which the panel product carrying the chain as its rider runs unsplit, default 2048),
  * "lowrank_kp" (64 = 64-row staging passes of BaM's low-rank update); round 6: "potrf_dag" (0 = one launch per block step),
  * "potrf_spin" (poll budget of a wait inside k_potrf_dag), "potrf_workers" (cap on its worker workgroups: tests of the ticket
- * order), "panel_w4_min_D"; diagnostics "timeline", "cov_dbg"
+ * order), "panel_w4_min_D"; "bam_batched_pad" (0 = the batched BaM kernel's LDS arrays at the unpadded row strides D, B; A/B
+ * runs); diagnostics "timeline", "cov_dbg"
  * (see gsmvi_hip_debug.h). */
 int gsmvi_set_tuning(gsmvi_ctx* ctx, const char* name, int value);
 
@@ -254,6 +257,7 @@ int gsmvi_get_profile(gsmvi_ctx* ctx, float* ms, int n);
 #define GSMVI_PATH_LOWRANK_FAST 0x0800u    /* k_lowrank_update_fast: BaM's S = S0 + Vf^T Vf - Z^T Z                 */
 #define GSMVI_PATH_LOWRANK_GENERIC 0x1000u /* k_lowrank_update                                                      */
 #define GSMVI_PATH_BATCHED 0x2000u         /* k_gsm_batched / k_gauss_score_batched: the batched entry points      */
+#define GSMVI_PATH_BATCHED_BAM 0x4000u     /* k_bam_batched: the batched BaM entry points                           */
 #define GSMVI_PATH_GENERIC_MASK (0x0004u | 0x0010u | 0x0040u | 0x0100u | 0x0400u | 0x1000u)
 int gsmvi_last_path(gsmvi_ctx* ctx, unsigned* bits, int reset);
 
@@ -316,6 +320,39 @@ int gsmvi_gsm_fit_step_batched_f64(gsmvi_ctx* ctx, void* stream, int64_t K, int 
  */
 int gsmvi_gaussian_score_batched_f64(gsmvi_ctx* ctx, void* stream, int64_t K, int D, int B, const double* X, const double* m,
                                      const double* P, double* G);
+
+/*
+ * Batched BaM (K independent problems of the same (D, B)), with the bounds, the layout and the per-problem isolation of the
+ * batched GSM above: 1 <= D <= 64, 1 <= B <= 32 (B > D is legal), K >= 1 (K < 2^24 when a problem takes a whole workgroup,
+ * K < 2^26 when four share one: D <= 16 and four problems' LDS within 160 KiB).  X, G (K x B x D), mu (K x D), S, R (K x D x D),
+ * packed, in device memory.  reg_dev: NULL = the scalar `reg` for every problem, else K per-problem values on the device.
+ * Shapes, NULL arrays and overlaps are checked before the context is looked at (then a NULL ctx); every failure returns
+ * GSMVI_ERR_BAD_ARG before anything is enqueued.  No context workspace is used.  Sets GSMVI_PATH_BATCHED_BAM.
+ *
+ * gsmvi/bam.py:72-114 bam_lowrank_update (= bam.py:31-69, K6) under jax.vmap -> gsmvi_bam_update_batched_f64:
+ *   (mu_k, S_k) = bam_update(X_k, G_k, mu0_k, S0_k, reg_k) with the exact rank-B factor of U (as gsmvi_bam_update_f64), S_k
+ *   symmetrised and jitter added to its diagonal (bam.py:198-199; jitter = 0 for the update alone).  info_dev (may be NULL):
+ *   0, or 1 when problem k's B x B chain failed (non-finite input, or BB not positive definite); its mu_k and S_k are NaN.
+ *   Outputs must not overlap inputs.
+ */
+int gsmvi_bam_update_batched_f64(gsmvi_ctx* ctx, void* stream, int64_t K, int D, int B, const double* X, const double* G,
+                                 const double* mu0, const double* S0, double reg, const double* reg_dev, double jitter,
+                                 double* mu, double* S, int* info_dev);
+
+/*
+ * One iteration of the batched BaM fit after the score G = lp_g(X) (gsmvi/bam.py:189-212 per problem), one launch: the update
+ * of every problem (as gsmvi_bam_update_batched_f64), + jitter I, symmetrised (:198-199), the Cholesky test of the new
+ * covariance (:208), and per problem: accept -> (mean_k, cov_k, R_k) <- (mu', S', chol(S')); revert -> all three kept bit for
+ * bit, n_reverts_dev[k] += 1 (may be NULL).  A failed chain or a non-finite score reverts its problem.  info_dev (may be NULL):
+ * 0, or 1 + the first bad pivot of the test.  The fit starts with gsmvi_gsm_fit_init_batched_f64 (chol of the initial cov, draw 0).
+ * seeds_dev != NULL: Xout (may equal X, must not overlap anything else) receives the next samples, Xout_k = mean_k + Z_k R_k of
+ * the kept or accepted state, Z_k = draw `call` of key seeds_dev[k] (B x (D + 1) normals, column D dropped, for odd D; needs
+ * R).  seeds_dev == NULL: nothing is drawn (teacher-forced samples; R and Xout may be NULL).  info_dev and n_reverts_dev
+ * must not overlap each other or any double array; no output may overlap G, seeds_dev or reg_dev.
+ */
+int gsmvi_bam_fit_step_batched_f64(gsmvi_ctx* ctx, void* stream, int64_t K, int D, int B, const double* X, const double* G,
+                                   double* mean, double* cov, double* R, double reg, const double* reg_dev, double jitter,
+                                   int* info_dev, int* n_reverts_dev, const uint64_t* seeds_dev, uint64_t call, double* Xout);
 
 /*
  * Upper Cholesky factor R (R^T R = S, R upper triangular, strictly-lower part zeroed) of a

@@ -31,6 +31,10 @@ int gsmvi_debug_chol128(void* stream, int n, int with_inverse, const double* A, 
  * kernel that only moves bytes reaches on this box, the yardstick beside the 8 TB/s specification. */
 int gsmvi_debug_stream_copy_f64(void* stream, double* dst, const double* src, size_t n);
 
+/* The dynamic LDS bytes per workgroup, and the problems one workgroup holds, of a batched BaM launch at (D, B) (pad != 0: the
+ * odd row strides of the default, pad = 0: the knob "bam_batched_pad" = 0).  Host arithmetic only, no device needed. */
+int gsmvi_debug_bam_batched_lds(int D, int B, int pad, size_t* bytes, int* problems_per_workgroup);
+
 #pragma GCC visibility pop
 #ifdef __cplusplus
 }
