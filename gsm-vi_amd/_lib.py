@@ -105,6 +105,10 @@ _SIGS = {
                                                C.c_double, _c_dp, C.c_double, _c_dp, _c_dp, _c_dp]),
     "gsmvi_bam_fit_step_batched_f64": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, _c_dp, _c_dp, _c_dp, _c_dp,
                                                  _c_dp, C.c_double, _c_dp, C.c_double, _c_dp, _c_dp, _c_dp, C.c_uint64, _c_dp]),
+    "gsmvi_kl_draw_batched_f64": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int64, C.c_int64, _c_dp, _c_dp, _c_dp,
+                                            C.c_uint64, _c_dp, _c_dp, _c_dp]),
+    "gsmvi_logq_batched_f64": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int64, _c_dp, _c_dp, _c_dp, _c_dp,
+                                         _c_dp]),
     "gsmvi_commit_f64": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, _c_dp, _c_dp, _c_dp, C.c_int, _c_dp, _c_dp,
                                    C.c_int, _c_dp]),
     "gsmvi_bam_update_f64": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, _c_dp, C.c_int, _c_dp, C.c_int,

@@ -8,7 +8,7 @@ problems at once: one launch plus the score call per iteration, whatever K is.  
 """
 import numpy as np
 
-from ._fitloop import Progress, _is_torch, result, scorer, seed_of, takes_out
+from ._fitloop import Checkpoints, Progress, _is_torch, result, scorer, seed_of, takes_out
 from .engine import get_engine
 from .bam import _every as _bam_every
 from .gsm import _every
@@ -50,6 +50,13 @@ def gsm_update_batched(samples, vs, mu0, S0, engine=None):
     return (mu, S) if want_torch else (eng.to_numpy(mu), eng.to_numpy(S))
 
 
+def _check_monitor(monitor, who):
+    """a batched fit takes a monitor that follows K problems (``batched = True``: BatchedKLMonitor) or none"""
+    if monitor is not None and not getattr(monitor, "batched", False):
+        raise TypeError(f"{who}: the monitor must follow K problems (BatchedKLMonitor, or any monitor with batched = True); "
+                        "KLMonitor and DeviceKLMonitor follow one problem")
+
+
 def _seeds(keys, K, who="GSMBatch.fit", last=False):
     """problem k's stream seed: ``seed_of(keys[k], last)``, as GSM.fit (last=False) or BaM.fit (last=True) takes it from its key"""
     if _is_torch(keys):
@@ -65,7 +72,7 @@ class GSMBatch:
 
     K    : number of problems.
     D    : dimensionality, 1 <= D <= 64.
-    lp   : batched log-density (kept for symmetry with GSM; the fit does not call it).
+    lp   : batched log-density, (K,rows,D) -> (K,) sums or (K,rows) values: handed to a batched ``monitor`` only.
     lp_g : score (K,B,D) -> (K,B,D).  A plain callable receives and returns numpy arrays (through ``host_score``); a callable
            marked ``device_native`` (``gsmvi_amd.device_score``, ``BatchedGaussianTarget.lp_g``) receives and returns float64
            CUDA tensors and keeps the whole iteration on the GPU.
@@ -91,10 +98,12 @@ class GSMBatch:
         for bit on a revert), next samples -- one launch after the score.  ``mean`` / ``cov``: (K,D) / (K,D,D), zeros and
         identities by default; a cov[k] that is not positive definite raises ValueError naming k.  ``forced_samples``:
         (niter+1, K, B, D) teacher-forced samples.  Progress prints follow GSM.fit (reverts summed over the problems since
-        the last print; no per-iteration synchronisation).  ``monitor`` is not supported.
+        the last print; no per-iteration synchronisation).  ``monitor``: a batched monitor (``BatchedKLMonitor``), called as
+        ``monitor(i, [mean, cov], lp, keys, nevals=n)`` with the device state every ``monitor.checkpoint`` iterations before the
+        score and once after the loop (the reference's cadence, gsm_numpy.py:110-113,127-128); any other monitor raises
+        TypeError.  It only reads the state: the fit returns the same bits with or without it.
         """
-        if monitor is not None:
-            raise TypeError("GSMBatch.fit does not support a monitor; fit without one (or use GSM.fit per problem)")
+        _check_monitor(monitor, "GSMBatch.fit")
         K, D, B = self.K, self.D, int(batch_size)
         niter = int(niter)
         _check_bounds(D, B)
@@ -121,14 +130,18 @@ class GSMBatch:
         out_ok = not getattr(self.lp_g, "device_native", False) or takes_out(self.lp_g)     # (host_score takes out=)
         Gbuf = eng.empty(K, B, D)
         progress = Progress(eng, n_rev, niter, _every(nprint, niter), verbose, read=lambda t: int(eng.read_ints(t).sum()))
+        mon = Checkpoints(eng, monitor, self.lp, keys, lambda: (mean_t, cov_t))
         for i in range(niter + 1):
             progress.tick(i)
+            mon.tick(i)
             if not draw:
                 X = eng.asarray(forced_samples[i])
             G = score(X, out=Gbuf) if out_ok else score(X)
+            mon.nevals += B
             nxt = draw and i < niter
             eng.gsm_fit_step_batched(X, G, mean_t, cov_t, R if draw else None, None, n_rev, seeds_t if nxt else None, i + 1)
         progress.flush()
+        mon.final(niter)
         self.n_reverts = eng.read_ints(n_rev)
         return result(eng, mean_t, cov_t, as_torch)
 
@@ -179,7 +192,7 @@ class BaMBatch:
 
     K    : number of problems.
     D    : dimensionality, 1 <= D <= 64.
-    lp   : batched log-density (kept for symmetry with BaM; the fit does not call it).
+    lp   : batched log-density, as for GSMBatch (handed to a batched ``monitor`` only).
     lp_g : score (K,B,D) -> (K,B,D), as for GSMBatch (a plain callable gets numpy arrays; a ``device_native`` one float64
            CUDA tensors).
     """
@@ -207,10 +220,10 @@ class BaMBatch:
         raises ValueError naming k.  ``forced_samples``: (niter+1, K, B, D) teacher-forced samples.
         Deviation from bam.py:189-206: there is no retry loop.  The device update never raises; a failed chain or a
         non-finite score reverts its own problem alone (counted in ``n_reverts``).  An exception from the score or from
-        ``regf`` propagates.  ``monitor`` is not supported (TypeError).
+        ``regf`` propagates.  ``monitor``: a batched monitor (``BatchedKLMonitor``) with the cadence of GSMBatch.fit
+        (bam.py:182-185,214-215); any other monitor raises TypeError.
         """
-        if monitor is not None:
-            raise TypeError("BaMBatch.fit does not support a monitor; fit without one (or use BaM.fit per problem)")
+        _check_monitor(monitor, "BaMBatch.fit")
         K, D, B = self.K, self.D, int(batch_size)
         niter = int(niter)
         _check_bounds(D, B, "batched BaM")
@@ -237,16 +250,20 @@ class BaMBatch:
         out_ok = not getattr(self.lp_g, "device_native", False) or takes_out(self.lp_g)
         Gbuf = eng.empty(K, B, D)
         progress = Progress(eng, n_rev, niter, _bam_every(nprint, niter), verbose, read=lambda t: int(eng.read_ints(t).sum()))
+        mon = Checkpoints(eng, monitor, self.lp, keys, lambda: (mean_t, cov_t))
         for i in range(niter + 1):
             progress.tick(i)
+            mon.tick(i)
             if not draw:
                 X = eng.asarray(forced_samples[i])
             G = score(X, out=Gbuf) if out_ok else score(X)
+            mon.nevals += B
             reg = _reg_values(regf(i), K, "BaMBatch.fit")
             nxt = draw and i < niter
             eng.bam_fit_step_batched(X, G, mean_t, cov_t, R if draw else None,
                                      reg if isinstance(reg, float) else eng.batched_regs(reg), float(jitter), None, n_rev,
                                      seeds_t if nxt else None, i + 1)
         progress.flush()
+        mon.final(niter)
         self.n_reverts = eng.read_ints(n_rev)
         return result(eng, mean_t, cov_t, as_torch)

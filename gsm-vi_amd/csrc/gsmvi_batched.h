@@ -1,6 +1,7 @@
-// Shared pieces of the batched kernels (gsmvi_batched.hip: GSM, gsmvi_bam_batched.hip: BaM): the bounds,
-// the argument block, and the tail of a fit step that both methods run on their new covariance S' -- the in-LDS Cholesky
-// test, per-problem accept or revert of (mean, cov, sampling factor), and the next samples from the problem's Philox stream.
+// Shared pieces of the batched kernels (gsmvi_batched.hip: GSM, gsmvi_bam_batched.hip: BaM, gsmvi_kl_batched.hip: the KL
+// monitor): the bounds, the argument block, the in-LDS Cholesky, and the tail of a fit step that both
+// methods run on their new covariance S' -- the Cholesky test, per-problem accept or revert of (mean, cov, sampling factor),
+// and the next samples from the problem's Philox stream.
 #pragma once
 #include <hip/hip_runtime.h>
 #include "gsmvi_philox.h"
@@ -33,22 +34,18 @@ struct gb_args {
 
 // padded draw row: an odd-D problem takes B x (D + 1) normals per draw, column D dropped (the layout of the single fit, _oddpad.py)
 __host__ __device__ inline int gb_dz(int D) { return D + (D & 1); }
+// threads per problem: four problems (one wave each) per 256-thread workgroup for D <= 16, one problem above
+static inline int gb_nt(int D) { return D <= 16 ? 64 : 256; }
 
-// The tail of a fit step (MODE_INIT = false) or of the fit's start (MODE_INIT = true), for the problem of one workgroup slot:
-//   S    (LDS, D x D, row stride ld)  S' on entry (only the upper triangle is used), its upper Cholesky factor on exit
-//   sreg (registers) the entries e = l + q NT of S' (row-major, stride D): what an accept writes to the state's covariance
-//   pv   (LDS, D) pivots;  Zb (LDS, B x Dz) the draws;  m0 the kept mean, m1 the new mean (LDS, D each)
-// Right-looking Cholesky, one pivot per barrier (unscaled rows: row c is final after step c and is scaled by 1 / sqrt(a_cc)
-// at the end).  Every thread of a slot reads the same pivot, so `info` is uniform in it.  A pivot that is not > 0 and finite
-// (NaN included: any NaN of S reaches a later pivot) fails, as np.linalg.cholesky does or the reference's NaN test catches
-// (gsm_numpy.py:139-146).  The loop always runs D steps (uniform barriers).  Then per problem: accept -> mean, cov, factor
-// written; revert -> nothing of the state is written, n_rev[k] += 1.  With a.seeds: X = m + z R, z = draw a.call of the
-// problem's stream (element n = b Dz + j, pair n / 2, gsmvi_rng.hip), from the kept or accepted state.
-template <int NT, int MAXE, bool MODE_INIT>
-__device__ __forceinline__ void gb_fit_tail(const gb_args& a, bool valid, long long k, int l, int ld, double* S,
-                                            const double (&sreg)[MAXE], double* pv, double* Zb, const double* m0, double* m1) {
-    const int D = a.D, B = a.B, Dz = gb_dz(D), DD = D * D, BD = B * D;
-    const size_t kd = (size_t)(valid ? k : 0) * D, kdd = (size_t)(valid ? k : 0) * DD, kbd = (size_t)(valid ? k : 0) * BD;
+// Upper Cholesky factor of the problem of one workgroup slot, in place in LDS (S: D x D, row stride ld; only its upper
+// triangle is read).  Right-looking, one pivot per barrier (unscaled rows: row c is final after step c and is scaled by
+// 1 / sqrt(a_cc) at the end); pv (LDS, D) receives the pivots sqrt(a_cc) = R_cc.  Every thread of a slot reads the same
+// pivot, so the result -- 0, or 1 + the first pivot that is not > 0 and finite (NaN included: any NaN of S reaches a later
+// pivot), as np.linalg.cholesky fails or the reference's NaN test catches (gsm_numpy.py:139-146) -- is uniform in it.  The
+// loop always runs D steps (uniform barriers); no barrier follows the scaling (a thread rewrites only its own entries).
+template <int NT, int MAXE>
+__device__ __forceinline__ int gb_chol_lds(bool valid, int D, int l, int ld, double* S, double* pv) {
+    const int DD = D * D;
     int info = 0;
     for (int c = 0; c < D; ++c) {
         const double acc_ = S[c * ld + c];
@@ -77,6 +74,22 @@ __device__ __forceinline__ void gb_fit_tail(const gb_args& a, bool valid, long l
             }
         }
     }
+    return info;
+}
+
+// The tail of a fit step (MODE_INIT = false) or of the fit's start (MODE_INIT = true), for the problem of one workgroup slot:
+//   S    (LDS, D x D, row stride ld)  S' on entry (only the upper triangle is used), its upper Cholesky factor on exit
+//   sreg (registers) the entries e = l + q NT of S' (row-major, stride D): what an accept writes to the state's covariance
+//   pv   (LDS, D) pivots;  Zb (LDS, B x Dz) the draws;  m0 the kept mean, m1 the new mean (LDS, D each)
+// The Cholesky test is gb_chol_lds.  Then per problem: accept -> mean, cov, factor written; revert -> nothing of the state
+// is written, n_rev[k] += 1.  With a.seeds: X = m + z R, z = draw a.call of the problem's stream (element n = b Dz + j,
+// pair n / 2, gsmvi_rng.hip), from the kept or accepted state.
+template <int NT, int MAXE, bool MODE_INIT>
+__device__ __forceinline__ void gb_fit_tail(const gb_args& a, bool valid, long long k, int l, int ld, double* S,
+                                            const double (&sreg)[MAXE], double* pv, double* Zb, const double* m0, double* m1) {
+    const int D = a.D, B = a.B, Dz = gb_dz(D), DD = D * D, BD = B * D;
+    const size_t kd = (size_t)(valid ? k : 0) * D, kdd = (size_t)(valid ? k : 0) * DD, kbd = (size_t)(valid ? k : 0) * BD;
+    const int info = gb_chol_lds<NT, MAXE>(valid, D, l, ld, S, pv);
 
     if (valid) {
         if (MODE_INIT) {

@@ -25,7 +25,6 @@ enum { GB_UPDATE = 0, GB_STEP = 1, GB_INIT = 2 };
 
 // LDS doubles per problem: S (D x D) + d (B x D) + g / z (B x Dz) + S0 g / e (B x D) + mu0, mu, pivots (D each) + 2 B scalars
 __host__ __device__ inline int gb_lds_doubles(int D, int B) { return D * D + 2 * B * D + B * gb_dz(D) + 3 * D + 2 * B; }
-static inline int gb_nt(int D) { return D <= 16 ? 64 : 256; }
 
 template <int NT, int MODE>
 __global__ __launch_bounds__(256) void k_gsm_batched(gb_args a) {

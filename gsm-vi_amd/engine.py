@@ -584,7 +584,7 @@ class HipEngine:
     PATH_BITS = {"panel_fast": 0x1, "panel_wide": 0x2, "panel_generic": 0x4, "panel_t_fast": 0x8, "panel_t_generic": 0x10,
                  "scalars_fast": 0x20, "scalars_generic": 0x40, "cov_sym": 0x80, "cov_generic": 0x100, "fupd_fast": 0x200,
                  "fupd_generic": 0x400, "lowrank_fast": 0x800, "lowrank_generic": 0x1000, "batched": 0x2000,
-                 "batched_bam": 0x4000}
+                 "batched_bam": 0x4000, "batched_kl": 0x8000}
     PATH_GENERIC_MASK = 0x4 | 0x10 | 0x40 | 0x100 | 0x400 | 0x1000
 
     def last_path(self, reset=True):
@@ -779,6 +779,43 @@ class HipEngine:
             self._packed(cov, (K, D, D), "cov"), self._packed(R, (K, D, D), "R") if R is not None else None, r, rp,
             float(jitter), self._ints(info, K, "info"), self._ints(n_reverts, K, "n_reverts"),
             C.c_void_p(seeds.data_ptr()) if seeds is not None else None, int(call), px if seeds is not None else None))
+
+    # ---- batched KL monitor: K Gaussians of one D (csrc/gsmvi_kl_batched.hip) ----------------------------------------------
+    def kl_draw_batched(self, mean, cov, seeds, call, s0, nc, out=None, info=None):
+        """Rows s0 .. s0 + nc - 1 of draw ``call`` of every problem's q_k = N(mean_k, cov_k)  [gsmvi/monitors.py:101-103]:
+        X_k = mean_k + Z_k R_k with Z_k those rows of ``normal(n, D, seeds[k], call)``; returns (X (K, nc, D), logq (K,) = the
+        sum of log q_k over the rows [monitors.py:104-113], info (K,) int32: 0, or 1 + the first bad pivot of cov_k, whose X
+        rows and logq are NaN)."""
+        K, D = mean.shape
+        self._ensure(max(self._max_D, 1), max(self._max_B, 1))
+        mean, cov = mean.contiguous(), cov.contiguous()
+        X, logq = (self.empty(K, nc, D), self.empty(K)) if out is None else out
+        info = self.batched_ints(K) if info is None else info
+        assert isinstance(seeds, torch.Tensor) and seeds.is_cuda and seeds.dtype == torch.int64 and seeds.is_contiguous() \
+            and seeds.numel() == K, f"seeds: expected {K} keys from batched_seeds()"
+        _lib.check("gsmvi_kl_draw_batched_f64", self.lib.gsmvi_kl_draw_batched_f64(
+            self._ctx, self._stream(), K, D, int(nc), int(s0), self._packed(mean, (K, D), "mean"),
+            self._packed(cov, (K, D, D), "cov"), C.c_void_p(seeds.data_ptr()), int(call), self._packed(X, (K, nc, D), "X"),
+            self._packed(logq, (K,), "logq"), self._ints(info, K, "info")))
+        return X, logq, info
+
+    def take_rows(self, A, idx):
+        """(K, len(idx), D): the rows ``idx`` of every problem's block of A (K, N, D), packed (the forward-KL batch)"""
+        return torch.index_select(A, 1, torch.as_tensor(np.asarray(idx, dtype=np.int64), device=A.device)).contiguous()
+
+    def logq_batched(self, mean, cov, Y, out=None, info=None):
+        """(logq (K,), info (K,)): logq_k = sum over the rows of Y_k (K, nc, D) of log N(y; mean_k, cov_k)
+        [gsmvi/monitors.py:104-113], by forward substitution with the upper factor of cov_k; NaN where cov_k is not positive
+        definite (info[k] = 1 + the first bad pivot)."""
+        K, nc, D = Y.shape
+        self._ensure(max(self._max_D, 1), max(self._max_B, 1))
+        mean, cov, Y = mean.contiguous(), cov.contiguous(), Y.contiguous()
+        logq = self.empty(K) if out is None else out
+        info = self.batched_ints(K) if info is None else info
+        _lib.check("gsmvi_logq_batched_f64", self.lib.gsmvi_logq_batched_f64(
+            self._ctx, self._stream(), K, D, nc, self._packed(mean, (K, D), "mean"), self._packed(cov, (K, D, D), "cov"),
+            self._packed(Y, (K, nc, D), "Y"), self._packed(logq, (K,), "logq"), self._ints(info, K, "info")))
+        return logq, info
 
     def bam_update(self, X, G, mu0, S0, reg, jitter=0.0, out=None, flag=None):
         """(mu, S) of BaM [gsmvi/bam.py:72-114]; S symmetrised, jitter on the diagonal."""

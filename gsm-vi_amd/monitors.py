@@ -167,3 +167,100 @@ class DeviceKLMonitor(KLMonitor):
         self.nevals.append(self.offset_evals + nevals)
         self.offset_evals = self.nevals[-1]
         return key
+
+
+@dataclass
+class BatchedKLMonitor(KLMonitor):
+    """KLMonitor (gsmvi/monitors.py:43-125) for the K problems of a batched fit (``GSMBatch.fit``, ``BaMBatch.fit``).
+
+    Call ``mon(i, [mean, cov], lp, keys, nevals=n)`` with mean (K, D), cov (K, D, D) (device tensors or numpy) and K per-problem
+    keys; it returns ``keys``.  ``rkl`` / ``fkl`` get one float64 array of shape (K,) per call; ``nevals`` is the shared count.
+    Per call, for every problem at once (csrc/gsmvi_kl_batched.hip): ``gsmvi_kl_draw_batched_f64`` factors cov_k, draws the
+    q-samples of problem k -- the rows DeviceKLMonitor(key=keys[k]) draws, seed (keys[k] % 2^32) ^ 0x5DEECE66D, call number =
+    this monitor's call count -- and sums log q_k over them; with ``ref_samples`` (K, N, D) the rows ``permutation(N)[:n]`` of
+    one host RandomState (seeded from keys[0] on the first call, as DeviceKLMonitor seeds its own; the same rows for every
+    problem) go through ``gsmvi_logq_batched_f64``.  Rows go in chunks of at most ``_CHUNK`` (bounded workspace whatever
+    batch_size_kl is); ``lp`` is called once per chunk, with the (K, rows, D) device tensor first and numpy if it refuses it,
+    and returns (K,) sums or (K, rows) values; the sums stay on the device and one read of 2K numbers ends the call.
+    D outside 1..64, keys of another length than K or ref_samples not (K, N, D) raise ValueError before any device work.  A
+    cov_k that is not positive definite gives NaN for problem k alone; an exception from ``lp`` appends NaN arrays
+    (monitors.py:115-119).  mean and cov are only read: the monitor has its own draw stream and leaves a fit bit for bit alone.
+    """
+    engine: object = None
+    device_native = True       # the fit drivers hand over their device state
+    batched = True             # what GSMBatch.fit / BaMBatch.fit accept
+    _CHUNK = 128
+
+    def _lp_sums(self, lp, X, eng, K):
+        try:
+            v = lp(X)
+        except (TypeError, AttributeError, RuntimeError, ValueError):
+            v = lp(eng.to_numpy(X))
+        v = eng.asarray(v)
+        if len(v.shape) == 2:
+            v = v.sum(1)
+        if tuple(v.shape) != (K,):
+            raise ValueError(f"lp returned shape {tuple(v.shape)}: expected ({K},) sums or ({K}, rows) values")
+        return v
+
+    def __call__(self, i, params, lp, keys, nevals=1):
+        from .batched import MAX_D
+        shape = lambda a: tuple(int(n) for n in a.shape)                      # noqa: E731
+        if len(shape(params[0])) != 2:
+            raise ValueError(f"BatchedKLMonitor: mean must be (K, D), got {shape(params[0])}")
+        K, D = shape(params[0])
+        if not 1 <= D <= MAX_D:
+            raise ValueError(f"BatchedKLMonitor: D = {D} is outside 1 <= D <= {MAX_D}")
+        if shape(params[1]) != (K, D, D):
+            raise ValueError(f"BatchedKLMonitor: cov must be {(K, D, D)}, got {shape(params[1])}")
+        keys_l = [int(k) for k in np.asarray(list(keys) if isinstance(keys, (list, tuple, range)) else _to_numpy(keys)).reshape(-1)]
+        if len(keys_l) != K:
+            raise ValueError(f"BatchedKLMonitor: {len(keys_l)} keys for K = {K} problems")
+        if self.ref_samples is not None:
+            rs = shape(self.ref_samples)
+            if len(rs) != 3 or rs[0] != K or rs[2] != D or rs[1] < 1:
+                raise ValueError(f"BatchedKLMonitor: ref_samples must be (K, N, D) = ({K}, N, {D}), got {rs}")
+        if self.engine is None:
+            from .engine import get_engine
+            self.engine = get_engine()
+        eng = self.engine
+        if self._rs is None:
+            self._rs = np.random.RandomState(keys_l[0] % (2 ** 32))
+            self._calls = 0
+            self._seeds = (None, None)
+        c = self._calls
+        self._calls += 1
+        try:
+            seeds = tuple((k % (2 ** 32)) ^ 0x5DEECE66D for k in keys_l)
+            if self._seeds[0] != seeds:
+                self._seeds = (seeds, eng.batched_seeds(seeds))
+            mu, cov = eng.asarray(params[0]), eng.asarray(params[1])
+            n = int(self.batch_size_kl)
+            rsum = eng.zeros(K)
+            for s0 in range(0, n, self._CHUNK):              # bounded engine workspace whatever batch_size_kl is
+                X, logq, _ = eng.kl_draw_batched(mu, cov, self._seeds[1], c, s0, min(self._CHUNK, n - s0))
+                rsum = rsum + (logq - self._lp_sums(lp, X, eng, K))
+            out = eng.empty(2, K)
+            out[0] = rsum / n
+            if self.ref_samples is not None:
+                if getattr(self, "_ref", (None,))[0] is not self.ref_samples:      # uploaded once
+                    self._ref = (self.ref_samples, eng.asarray(self.ref_samples))
+                idx = self._rs.permutation(int(self._ref[1].shape[1]))[:n]
+                fsum = eng.zeros(K)
+                for s0 in range(0, len(idx), self._CHUNK):
+                    Y = eng.take_rows(self._ref[1], idx[s0:s0 + self._CHUNK])
+                    logq, _ = eng.logq_batched(mu, cov, Y)
+                    fsum = fsum + (self._lp_sums(lp, Y, eng, K) - logq)
+                out[1] = fsum / len(idx)
+            else:
+                out[1] = float("nan")
+            res = np.array(eng.to_numpy(out), dtype=np.float64)
+            self.rkl.append(res[0])
+            self.fkl.append(res[1])
+        except Exception as e:                                         # noqa: BLE001 (reference behaviour)
+            print(f"Exception occured in monitor : {e}.\nAppending NaN")
+            self.rkl.append(np.full(K, np.nan))
+            self.fkl.append(np.full(K, np.nan))
+        self.nevals.append(self.offset_evals + nevals)
+        self.offset_evals = self.nevals[-1]
+        return keys

@@ -17,6 +17,7 @@
  *   (no reference twin; gsm_numpy.py:4-55 in factor form)   ->  gsmvi_gsm_factor_update_f64
  *   jax.vmap(bam_update) over K problems, D <= 64 (bam.py:31-114)      ->  gsmvi_bam_update_batched_f64
  *   bam.py:189-212 fit iteration of K problems (dense), D <= 64         ->  gsmvi_bam_fit_step_batched_f64
+ *   monitors.py:83-125 KL monitor of K problems, D <= 64               ->  gsmvi_kl_draw_batched_f64, gsmvi_logq_batched_f64
  *   gsmvi/bam.py:72-114       bam_lowrank_update(samples,vs,mu0,S0,reg) ->  gsmvi_bam_update_f64
  *   gsmvi/bam.py:31-69        bam_update(samples,vs,mu0,S0,reg)         ->  gsmvi_bam_update_f64 (same result, K6)
  *
@@ -258,6 +259,7 @@ int gsmvi_get_profile(gsmvi_ctx* ctx, float* ms, int n);
 #define GSMVI_PATH_LOWRANK_GENERIC 0x1000u /* k_lowrank_update                                                      */
 #define GSMVI_PATH_BATCHED 0x2000u         /* k_gsm_batched / k_gauss_score_batched: the batched entry points      */
 #define GSMVI_PATH_BATCHED_BAM 0x4000u     /* k_bam_batched: the batched BaM entry points                           */
+#define GSMVI_PATH_BATCHED_KL 0x8000u      /* k_kl_batched: the batched KL monitor's entry points                  */
 #define GSMVI_PATH_GENERIC_MASK (0x0004u | 0x0010u | 0x0040u | 0x0100u | 0x0400u | 0x1000u)
 int gsmvi_last_path(gsmvi_ctx* ctx, unsigned* bits, int reset);
 
@@ -353,6 +355,32 @@ int gsmvi_bam_update_batched_f64(gsmvi_ctx* ctx, void* stream, int64_t K, int D,
 int gsmvi_bam_fit_step_batched_f64(gsmvi_ctx* ctx, void* stream, int64_t K, int D, int B, const double* X, const double* G,
                                    double* mean, double* cov, double* R, double reg, const double* reg_dev, double jitter,
                                    int* info_dev, int* n_reverts_dev, const uint64_t* seeds_dev, uint64_t call, double* Xout);
+
+/*
+ * Batched KL monitor (K Gaussians q_k = N(mean_k, cov_k) of one D): 1 <= D <= 64, K >= 1 with the grid limits of the batched GSM
+ * above, nc >= 1 rows per call.  mean (K x D), cov (K x D x D), X, Y (K x nc x D), logq_sum (K), info (K), packed, in device
+ * memory.  Both factor cov_k = R_k^T R_k (upper, in LDS: only the upper triangle of cov_k is used) and write info[k] = 0, or
+ * 1 + the first pivot that is not > 0 and finite; such a problem gets logq_sum[k] = NaN (and NaN rows of X) and no other
+ * problem is touched.  mean and cov are only read and no context workspace is used, so a call may sit between two steps of a
+ * running batched fit.  Shapes, NULL arrays and overlaps are checked before the context is looked at (then a NULL ctx); every
+ * failure returns GSMVI_ERR_BAD_ARG before anything is enqueued.  Sets GSMVI_PATH_BATCHED_KL.
+ *
+ * gsmvi/monitors.py:83-125, the reverse-KL samples of KLMonitor.__call__ (:101-103) and MultivariateNormal.log_prob on them
+ * (:104-113), for every k -> gsmvi_kl_draw_batched_f64: the rows s = s0 .. s0 + nc - 1 of draw `call` of key seeds[k],
+ *   z_s = elements s D .. s D + D - 1 of gsmvi_randn_f64(seeds[k], call, n D) (the plain layout: pair (s D + j) / 2, no odd-D
+ *   padding), X_k row s - s0 = mean_k + z_s R_k, and logq_sum[k] = sum_s (-|z_s|^2 / 2 - sum_i log R_ii - D / 2 log 2 pi).
+ *   A call split into chunks (s0 > 0) writes the same X rows, bit for bit, as the unsplit call.
+ */
+int gsmvi_kl_draw_batched_f64(gsmvi_ctx* ctx, void* stream, int64_t K, int D, int64_t nc, int64_t s0, const double* mean,
+                              const double* cov, const uint64_t* seeds, uint64_t call, double* X, double* logq_sum, int* info);
+
+/*
+ * gsmvi/monitors.py:104-113 MultivariateNormal(mean_k, cov_k).log_prob on the rows of Y_k (the forward-KL reference samples,
+ * :110-113), for every k -> gsmvi_logq_batched_f64: w = the solution of R_k^T w = y - mean_k (forward substitution) and
+ * logq_sum[k] = sum over the nc rows of (-|w|^2 / 2 - sum_i log R_ii - D / 2 log 2 pi).
+ */
+int gsmvi_logq_batched_f64(gsmvi_ctx* ctx, void* stream, int64_t K, int D, int64_t nc, const double* mean, const double* cov,
+                           const double* Y, double* logq_sum, int* info);
 
 /*
  * Upper Cholesky factor R (R^T R = S, R upper triangular, strictly-lower part zeroed) of a
