@@ -57,7 +57,7 @@ def _check_monitor(monitor, who):
                         "KLMonitor and DeviceKLMonitor follow one problem")
 
 
-def _seeds(keys, K, who="GSMBatch.fit", last=False):
+def _seeds(keys, K, who, last):
     """problem k's stream seed: ``seed_of(keys[k], last)``, as GSM.fit (last=False) or BaM.fit (last=True) takes it from its key"""
     if _is_torch(keys):
         keys = keys.detach().cpu().numpy()
@@ -67,7 +67,68 @@ def _seeds(keys, K, who="GSMBatch.fit", last=False):
     return [seed_of(int(k), last=last) for k in keys]
 
 
-class GSMBatch:
+class _BatchFit:
+    """The constructor and the fit loop of GSMBatch and BaMBatch.  A subclass gives its name (``_name``; ``_what`` in bound
+    errors), the print cadence of its single-problem fit (``_cadence``), the seed of a key (``_last``, as ``seed_of``
+    takes it) and, per fit, the launch of an iteration after the score."""
+
+    def __init__(self, K, D, lp, lp_g, engine=None):
+        self.K, self.D = int(K), int(D)
+        if self.K < 1:
+            raise ValueError(f"{self._name}: K = {K} must be at least 1")
+        _check_bounds(self.D, 1, self._what)
+        self.lp = lp
+        self.lp_g = lp_g
+        self._engine = engine
+
+    def _fit(self, step, keys, mean, cov, batch_size, niter, nprint, verbose, forced_samples, as_torch, monitor):
+        """the loop of ``fit``: ``step(eng, i, X, G, mean, cov, R, n_rev, seeds)`` launches iteration i after the score (R is
+        None for teacher-forced samples, seeds None when no next samples are drawn)"""
+        who = f"{self._name}.fit"
+        _check_monitor(monitor, who)
+        K, D, B = self.K, self.D, int(batch_size)
+        niter = int(niter)
+        _check_bounds(D, B, self._what)
+        seeds = _seeds(keys, K, who, last=self._last)
+        if mean is not None:
+            assert _shape(mean) == (K, D), f"mean: expected shape {(K, D)}"
+        if cov is not None:
+            assert _shape(cov) == (K, D, D), f"cov: expected shape {(K, D, D)}"
+        if forced_samples is not None:
+            assert _shape(forced_samples) == (niter + 1, K, B, D), f"forced_samples: expected shape {(niter + 1, K, B, D)}"
+        eng = self._engine if self._engine is not None else get_engine()
+        mean_t = eng.zeros(K, D) if mean is None else eng.clone(mean).reshape(K, D)
+        cov_t = eng.eye_batch(K, D) if cov is None else eng.clone(cov).reshape(K, D, D)
+        draw = forced_samples is None
+        R = eng.empty(K, D, D)
+        X = eng.empty(K, B, D)
+        info, n_rev = eng.batched_ints(K), eng.batched_ints(K)
+        seeds_t = eng.batched_seeds(seeds) if draw else None
+        eng.gsm_fit_init_batched(mean_t, cov_t, R, info, seeds_t, X if draw else None)     # a BaM fit starts as a GSM fit
+        bad = np.flatnonzero(eng.read_ints(info))
+        if bad.size:
+            raise ValueError(f"{who}: initial covariance is not positive definite for problem(s) {bad.tolist()}")
+        score = scorer(eng, self.lp_g)
+        out_ok = not getattr(self.lp_g, "device_native", False) or takes_out(self.lp_g)     # (host_score takes out=)
+        Gbuf = eng.empty(K, B, D)
+        progress = Progress(eng, n_rev, niter, self._cadence(nprint, niter), verbose, read=lambda t: int(eng.read_ints(t).sum()))
+        mon = Checkpoints(eng, monitor, self.lp, keys, lambda: (mean_t, cov_t))
+        for i in range(niter + 1):
+            progress.tick(i)
+            mon.tick(i)
+            if not draw:
+                X = eng.asarray(forced_samples[i])
+            G = score(X, out=Gbuf) if out_ok else score(X)
+            mon.nevals += B
+            nxt = draw and i < niter
+            step(eng, i, X, G, mean_t, cov_t, R if draw else None, n_rev, seeds_t if nxt else None)
+        progress.flush()
+        mon.final(niter)
+        self.n_reverts = eng.read_ints(n_rev)
+        return result(eng, mean_t, cov_t, as_torch)
+
+
+class GSMBatch(_BatchFit):
     """K independent GSM fits of the same dimension D (gsmvi/gsm_numpy.py:60-129, dense form), one launch per iteration.
 
     K    : number of problems.
@@ -78,14 +139,7 @@ class GSMBatch:
            CUDA tensors and keeps the whole iteration on the GPU.
     """
 
-    def __init__(self, K, D, lp, lp_g, engine=None):
-        self.K, self.D = int(K), int(D)
-        if self.K < 1:
-            raise ValueError(f"GSMBatch: K = {K} must be at least 1")
-        _check_bounds(self.D, 1)
-        self.lp = lp
-        self.lp_g = lp_g
-        self._engine = engine
+    _name, _what, _cadence, _last = "GSMBatch", "batched GSM", staticmethod(_every), False
 
     def fit(self, keys, mean=None, cov=None, batch_size=2, niter=5000, nprint=10, verbose=True, *, forced_samples=None,
             as_torch=False, monitor=None):
@@ -103,47 +157,10 @@ class GSMBatch:
         score and once after the loop (the reference's cadence, gsm_numpy.py:110-113,127-128); any other monitor raises
         TypeError.  It only reads the state: the fit returns the same bits with or without it.
         """
-        _check_monitor(monitor, "GSMBatch.fit")
-        K, D, B = self.K, self.D, int(batch_size)
-        niter = int(niter)
-        _check_bounds(D, B)
-        seeds = _seeds(keys, K)
-        if mean is not None:
-            assert _shape(mean) == (K, D), f"mean: expected shape {(K, D)}"
-        if cov is not None:
-            assert _shape(cov) == (K, D, D), f"cov: expected shape {(K, D, D)}"
-        if forced_samples is not None:
-            assert _shape(forced_samples) == (niter + 1, K, B, D), f"forced_samples: expected shape {(niter + 1, K, B, D)}"
-        eng = self._engine if self._engine is not None else get_engine()
-        mean_t = eng.zeros(K, D) if mean is None else eng.clone(mean).reshape(K, D)
-        cov_t = eng.eye_batch(K, D) if cov is None else eng.clone(cov).reshape(K, D, D)
-        draw = forced_samples is None
-        R = eng.empty(K, D, D)
-        X = eng.empty(K, B, D)
-        info, n_rev = eng.batched_ints(K), eng.batched_ints(K)
-        seeds_t = eng.batched_seeds(seeds) if draw else None
-        eng.gsm_fit_init_batched(mean_t, cov_t, R, info, seeds_t, X if draw else None)
-        bad = np.flatnonzero(eng.read_ints(info))
-        if bad.size:
-            raise ValueError(f"GSMBatch.fit: initial covariance is not positive definite for problem(s) {bad.tolist()}")
-        score = scorer(eng, self.lp_g)
-        out_ok = not getattr(self.lp_g, "device_native", False) or takes_out(self.lp_g)     # (host_score takes out=)
-        Gbuf = eng.empty(K, B, D)
-        progress = Progress(eng, n_rev, niter, _every(nprint, niter), verbose, read=lambda t: int(eng.read_ints(t).sum()))
-        mon = Checkpoints(eng, monitor, self.lp, keys, lambda: (mean_t, cov_t))
-        for i in range(niter + 1):
-            progress.tick(i)
-            mon.tick(i)
-            if not draw:
-                X = eng.asarray(forced_samples[i])
-            G = score(X, out=Gbuf) if out_ok else score(X)
-            mon.nevals += B
-            nxt = draw and i < niter
-            eng.gsm_fit_step_batched(X, G, mean_t, cov_t, R if draw else None, None, n_rev, seeds_t if nxt else None, i + 1)
-        progress.flush()
-        mon.final(niter)
-        self.n_reverts = eng.read_ints(n_rev)
-        return result(eng, mean_t, cov_t, as_torch)
+        def step(eng, i, X, G, m, c, R, n_rev, seeds):
+            eng.gsm_fit_step_batched(X, G, m, c, R, None, n_rev, seeds, i + 1)
+
+        return self._fit(step, keys, mean, cov, batch_size, niter, nprint, verbose, forced_samples, as_torch, monitor)
 
 
 def _reg_values(reg, K, who):
@@ -187,7 +204,7 @@ def bam_lowrank_update_batched(samples, vs, mu0, S0, reg, jitter=0.0, engine=Non
     return bam_update_batched(samples, vs, mu0, S0, reg, jitter=jitter, engine=engine)
 
 
-class BaMBatch:
+class BaMBatch(_BatchFit):
     """K independent BaM fits of the same dimension D (gsmvi/bam.py:117-216, the dense loop), one launch per iteration.
 
     K    : number of problems.
@@ -197,14 +214,7 @@ class BaMBatch:
            CUDA tensors).
     """
 
-    def __init__(self, K, D, lp, lp_g, engine=None):
-        self.K, self.D = int(K), int(D)
-        if self.K < 1:
-            raise ValueError(f"BaMBatch: K = {K} must be at least 1")
-        _check_bounds(self.D, 1, "batched BaM")
-        self.lp = lp
-        self.lp_g = lp_g
-        self._engine = engine
+    _name, _what, _cadence, _last = "BaMBatch", "batched BaM", staticmethod(_bam_every), True
 
     def fit(self, keys, regf, mean=None, cov=None, batch_size=2, niter=5000, nprint=10, verbose=True, jitter=1e-6, *,
             forced_samples=None, as_torch=False, monitor=None):
@@ -223,47 +233,9 @@ class BaMBatch:
         ``regf`` propagates.  ``monitor``: a batched monitor (``BatchedKLMonitor``) with the cadence of GSMBatch.fit
         (bam.py:182-185,214-215); any other monitor raises TypeError.
         """
-        _check_monitor(monitor, "BaMBatch.fit")
-        K, D, B = self.K, self.D, int(batch_size)
-        niter = int(niter)
-        _check_bounds(D, B, "batched BaM")
-        seeds = _seeds(keys, K, "BaMBatch.fit", last=True)
-        if mean is not None:
-            assert _shape(mean) == (K, D), f"mean: expected shape {(K, D)}"
-        if cov is not None:
-            assert _shape(cov) == (K, D, D), f"cov: expected shape {(K, D, D)}"
-        if forced_samples is not None:
-            assert _shape(forced_samples) == (niter + 1, K, B, D), f"forced_samples: expected shape {(niter + 1, K, B, D)}"
-        eng = self._engine if self._engine is not None else get_engine()
-        mean_t = eng.zeros(K, D) if mean is None else eng.clone(mean).reshape(K, D)
-        cov_t = eng.eye_batch(K, D) if cov is None else eng.clone(cov).reshape(K, D, D)
-        draw = forced_samples is None
-        R = eng.empty(K, D, D)
-        X = eng.empty(K, B, D)
-        info, n_rev = eng.batched_ints(K), eng.batched_ints(K)
-        seeds_t = eng.batched_seeds(seeds) if draw else None
-        eng.gsm_fit_init_batched(mean_t, cov_t, R, info, seeds_t, X if draw else None)     # a BaM fit starts as a GSM fit
-        bad = np.flatnonzero(eng.read_ints(info))
-        if bad.size:
-            raise ValueError(f"BaMBatch.fit: initial covariance is not positive definite for problem(s) {bad.tolist()}")
-        score = scorer(eng, self.lp_g)
-        out_ok = not getattr(self.lp_g, "device_native", False) or takes_out(self.lp_g)
-        Gbuf = eng.empty(K, B, D)
-        progress = Progress(eng, n_rev, niter, _bam_every(nprint, niter), verbose, read=lambda t: int(eng.read_ints(t).sum()))
-        mon = Checkpoints(eng, monitor, self.lp, keys, lambda: (mean_t, cov_t))
-        for i in range(niter + 1):
-            progress.tick(i)
-            mon.tick(i)
-            if not draw:
-                X = eng.asarray(forced_samples[i])
-            G = score(X, out=Gbuf) if out_ok else score(X)
-            mon.nevals += B
-            reg = _reg_values(regf(i), K, "BaMBatch.fit")
-            nxt = draw and i < niter
-            eng.bam_fit_step_batched(X, G, mean_t, cov_t, R if draw else None,
-                                     reg if isinstance(reg, float) else eng.batched_regs(reg), float(jitter), None, n_rev,
-                                     seeds_t if nxt else None, i + 1)
-        progress.flush()
-        mon.final(niter)
-        self.n_reverts = eng.read_ints(n_rev)
-        return result(eng, mean_t, cov_t, as_torch)
+        def step(eng, i, X, G, m, c, R, n_rev, seeds):
+            reg = _reg_values(regf(i), self.K, "BaMBatch.fit")
+            eng.bam_fit_step_batched(X, G, m, c, R, reg if isinstance(reg, float) else eng.batched_regs(reg), float(jitter), None,
+                                     n_rev, seeds, i + 1)
+
+        return self._fit(step, keys, mean, cov, batch_size, niter, nprint, verbose, forced_samples, as_torch, monitor)

@@ -42,7 +42,8 @@ __host__ __device__ inline int bb_lds_doubles(int D, int B, int ld, int ldn) {
 }
 __host__ __device__ inline int bb_lds_doubles(int D, int B) { return bb_lds_doubles(D, B, bb_ld(D), bb_ldn(B)); }
 // four problems (one wave each) per workgroup for D <= 16 when they fit in 160 KiB together, else one problem on 256 threads
-static inline int bb_nt(int D, int B) { return (D <= 16 && 4 * 8 * bb_lds_doubles(D, B) <= 160 * 1024) ? 64 : 256; }
+static inline int bb_nt(int D, int B) { return (D <= 16 && 4 * 8 * bb_lds_doubles(D, B) <= GB_LDS_MAX) ? 64 : 256; }
+static inline int bb_ppw(int D, int B) { return 256 / bb_nt(D, B); }
 
 template <int NT, int MODE>
 __global__ __launch_bounds__(256) void k_bam_batched(gb_args a) {
@@ -333,32 +334,13 @@ __global__ __launch_bounds__(256) void k_bam_batched(gb_args a) {
 }
 
 hipError_t gsmvi_bam_batched_prepare() {
-    const void* fns[] = {
-        reinterpret_cast<const void*>(k_bam_batched<64, BB_UPDATE>), reinterpret_cast<const void*>(k_bam_batched<256, BB_UPDATE>),
-        reinterpret_cast<const void*>(k_bam_batched<64, BB_STEP>), reinterpret_cast<const void*>(k_bam_batched<256, BB_STEP>)};
-    for (const void* f : fns) {
-        hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return e;
-    }
-    return hipSuccess;
-}
-
-// Shapes and arrays are checked before the context is looked at (a NULL context is the last thing reported).
-static int bb_check(gsmvi_ctx* ctx, int64_t K, int D, int B, const char* fn) {
-    if (D < 1 || D > GB_MAX_D) { gsmvi_set_error("%s: %s", fn, "D must be in [1, 64]"); return GSMVI_ERR_BAD_ARG; }
-    if (B < 1 || B > GB_MAX_B) { gsmvi_set_error("%s: %s", fn, "B must be in [1, 32]"); return GSMVI_ERR_BAD_ARG; }
-    // one launch: fewer than 2^32 threads -- K < 2^24 problems at one per workgroup, 2^26 at four
-    if (K < 1 || K > (int64_t)(256 / bb_nt(D, B)) * 16777215) {
-        gsmvi_set_error("%s: %s", fn, "K must be in [1, 2^24 - 1] (one problem per workgroup) or [1, 2^26 - 4] (four)");
-        return GSMVI_ERR_BAD_ARG;
-    }
-    (void)ctx;
-    return GSMVI_OK;
+    return gb_allow_lds(k_bam_batched<64, BB_UPDATE>, k_bam_batched<256, BB_UPDATE>, k_bam_batched<64, BB_STEP>,
+                        k_bam_batched<256, BB_STEP>);
 }
 
 // the dynamic LDS a launch requests per workgroup (and the problems it holds) at the given row strides
 static size_t bb_launch_lds(int D, int B, int ld, int ldn, int* ppw) {
-    *ppw = 256 / bb_nt(D, B);
+    *ppw = bb_ppw(D, B);
     return (size_t)*ppw * bb_lds_doubles(D, B, ld, ldn) * sizeof(double);
 }
 
@@ -378,13 +360,7 @@ static int bb_launch(gsmvi_ctx* ctx, void* stream, int mode, gb_args& a, const c
         if (mode == BB_UPDATE) BB_GO(256, BB_UPDATE); else BB_GO(256, BB_STEP);
     }
 #undef BB_GO
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        gsmvi_set_error("launch of %s failed: %s", fn, hipGetErrorString(e));
-        return GSMVI_ERR_HIP;
-    }
-    ctx->path |= GSMVI_PATH_BATCHED_BAM;
-    return GSMVI_OK;
+    return gb_launched(ctx, GSMVI_PATH_BATCHED_BAM, fn);
 }
 
 extern "C" {
@@ -392,17 +368,14 @@ extern "C" {
 int gsmvi_bam_update_batched_f64(gsmvi_ctx* ctx, void* stream, int64_t K, int D, int B, const double* X, const double* G,
                                  const double* mu0, const double* S0, double reg, const double* reg_dev, double jitter,
                                  double* mu, double* S, int* info_dev) {
-    int st = bb_check(ctx, K, D, B, __func__);
-    if (st != GSMVI_OK) return st;
+    if (int st = gb_check_shape(__func__, K, D, bb_ppw, B)) return st;
     GB_BAD(!X || !G || !mu0 || !S0 || !mu || !S, "NULL array");
-    const size_t nv = (size_t)K * D * 8, nm = (size_t)K * D * D * 8, nx = (size_t)K * B * D * 8, ni = (size_t)K * 4;
-    GB_BAD(gb_overlap(mu, nv, S, nm) || gb_overlap(mu, nv, X, nx) || gb_overlap(mu, nv, G, nx) || gb_overlap(mu, nv, mu0, nv) ||
-           gb_overlap(mu, nv, S0, nm) || gb_overlap(S, nm, X, nx) || gb_overlap(S, nm, G, nx) || gb_overlap(S, nm, mu0, nv) ||
-           gb_overlap(S, nm, S0, nm) || (reg_dev && (gb_overlap(mu, nv, reg_dev, nv / D) || gb_overlap(S, nm, reg_dev, nv / D))) ||
-           (info_dev && (gb_overlap(info_dev, ni, mu, nv) || gb_overlap(info_dev, ni, S, nm) || gb_overlap(info_dev, ni, X, nx) ||
-                         gb_overlap(info_dev, ni, G, nx) || gb_overlap(info_dev, ni, mu0, nv) || gb_overlap(info_dev, ni, S0, nm) ||
-                         (reg_dev && gb_overlap(info_dev, ni, reg_dev, nv / D)))),
-           "outputs overlap each other or an input");
+    const size_t nv = (size_t)K * D * 8, nm = (size_t)K * D * D * 8, nx = (size_t)K * B * D * 8, nk = (size_t)K * 8,
+                 ni = (size_t)K * 4;
+    if (int st = gb_check_overlaps(__func__, {{X, nx, "X", GB_RD}, {G, nx, "G", GB_RD}, {mu0, nv, "mu0", GB_RD},
+                                              {S0, nm, "S0", GB_RD}, {reg_dev, nk, "reg_dev", GB_RD}, {mu, nv, "mu", GB_WR},
+                                              {S, nm, "S", GB_WR}, {info_dev, ni, "info_dev", GB_WR}}))
+        return st;
     GB_BAD(!ctx, "ctx is NULL");
     gb_args a = {};
     a.K = K; a.D = D; a.B = B; a.X = X; a.V = G; a.mu0 = mu0; a.S0 = S0; a.mu = mu; a.S = S; a.info = info_dev;
@@ -413,30 +386,17 @@ int gsmvi_bam_update_batched_f64(gsmvi_ctx* ctx, void* stream, int64_t K, int D,
 int gsmvi_bam_fit_step_batched_f64(gsmvi_ctx* ctx, void* stream, int64_t K, int D, int B, const double* X, const double* G,
                                    double* mean, double* cov, double* R, double reg, const double* reg_dev, double jitter,
                                    int* info_dev, int* n_reverts_dev, const uint64_t* seeds_dev, uint64_t call, double* Xout) {
-    int st = bb_check(ctx, K, D, B, __func__);
-    if (st != GSMVI_OK) return st;
+    if (int st = gb_check_shape(__func__, K, D, bb_ppw, B)) return st;
     GB_BAD(!X || !G || !mean || !cov, "NULL array");
     GB_BAD(seeds_dev && (!R || !Xout), "drawing the next samples needs the sampling factor R and Xout");
-    const size_t nv = (size_t)K * D * 8, nm = (size_t)K * D * D * 8, nx = (size_t)K * B * D * 8, nr = (size_t)K * 8;
-    GB_BAD(gb_overlap(X, nx, G, nx) || gb_overlap(X, nx, mean, nv) || gb_overlap(X, nx, cov, nm) || gb_overlap(G, nx, mean, nv) ||
-           gb_overlap(G, nx, cov, nm) || gb_overlap(mean, nv, cov, nm) ||
-           (R && (gb_overlap(R, nm, X, nx) || gb_overlap(R, nm, G, nx) || gb_overlap(R, nm, mean, nv) || gb_overlap(R, nm, cov, nm))) ||
-           (reg_dev && (gb_overlap(reg_dev, nr, mean, nv) || gb_overlap(reg_dev, nr, cov, nm) || (R && gb_overlap(reg_dev, nr, R, nm)))),
-           "arrays overlap");
-    GB_BAD(Xout && Xout != X && (gb_overlap(Xout, nx, X, nx) || gb_overlap(Xout, nx, G, nx) || gb_overlap(Xout, nx, mean, nv) ||
-           gb_overlap(Xout, nx, cov, nm) || (R && gb_overlap(Xout, nx, R, nm))), "Xout overlaps an array (it may equal X)");
-    // the written int arrays (info, n_reverts) and the read-only per-problem arrays (seeds, reg) against everything else
-    const size_t ni = (size_t)K * 4;
-    const void* wr[] = {X, mean, cov, R, Xout, info_dev, n_reverts_dev};
-    const size_t wn[] = {nx, nv, nm, nm, nx, ni, ni};
-    const void* ro[] = {G, seeds_dev, reg_dev};
-    const size_t rn[] = {nx, nr, nr};
-    for (int i = 5; i < 7; ++i)
-        for (int j = 0; j < 7; ++j)
-            GB_BAD(wr[i] && wr[j] && i != j && gb_overlap(wr[i], wn[i], wr[j], wn[j]), "info_dev / n_reverts_dev overlap an array");
-    for (int i = 0; i < 3; ++i)
-        for (int j = 0; j < 7; ++j)
-            GB_BAD(ro[i] && wr[j] && gb_overlap(ro[i], rn[i], wr[j], wn[j]), "an output overlaps G, seeds_dev or reg_dev");
+    const size_t nv = (size_t)K * D * 8, nm = (size_t)K * D * D * 8, nx = (size_t)K * B * D * 8, nk = (size_t)K * 8,
+                 ni = (size_t)K * 4;
+    // X counts as written (Xout may be X).  Xout == X exactly is the one overlap allowed: X's entry then stands for both.
+    if (int st = gb_check_overlaps(__func__, {{X, nx, "X", GB_WR}, {G, nx, "G", GB_RD}, {mean, nv, "mean", GB_WR},
+                                              {cov, nm, "cov", GB_WR}, {R, nm, "R", GB_WR}, {reg_dev, nk, "reg_dev", GB_RD},
+                                              {info_dev, ni, "info_dev", GB_WR}, {n_reverts_dev, ni, "n_reverts_dev", GB_WR},
+                                              {seeds_dev, nk, "seeds_dev", GB_RD}, {Xout != X ? Xout : nullptr, nx, "Xout", GB_WR}}))
+        return st;
     GB_BAD(!ctx, "ctx is NULL");
     gb_args a = {};
     a.K = K; a.D = D; a.B = B; a.X = X; a.V = G; a.mu = mean; a.S = cov; a.R = R; a.info = info_dev; a.n_rev = n_reverts_dev;

@@ -5,7 +5,11 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include "gsmvi_philox.h"
+#include "gsmvi_ctx.h"
+#include "../../include/gsmvi_hip.h"
 #include <cstdint>
+#include <cstdio>
+#include <initializer_list>
 
 #define GB_MAX_D 64
 #define GB_MAX_B 32
@@ -150,16 +154,78 @@ __device__ __forceinline__ void gb_fit_tail(const gb_args& a, bool valid, long l
     }
 }
 
-// ---- host side: argument checks shared by the batched entry points ----------------------------------------------------
+// ---- host side: the argument checks and the launch pieces shared by the batched entry points --------------------------
+// Every entry point checks, before anything is enqueued: the shapes (gb_check_shape), its NULL arrays and own conditions
+// (GB_BAD), the overlaps (gb_check_overlaps), and the context last.  A failure returns GSMVI_ERR_BAD_ARG.
+#define GB_LDS_MAX (160 * 1024)   // dynamic LDS per workgroup that a batched kernel may request (gb_allow_lds)
+
 static inline bool gb_overlap(const void* a, size_t na, const void* b, size_t nb) {
     const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
     return x < y + nb && y < x + na;
 }
 
-#define GB_BAD(cond, msg)                             \
-    do {                                              \
-        if (cond) {                                   \
-            gsmvi_set_error("%s: %s", __func__, msg); \
-            return GSMVI_ERR_BAD_ARG;                 \
-        }                                             \
+static inline int gb_bad(const char* fn, const char* msg) {
+    gsmvi_set_error("%s: %s", fn, msg);
+    return GSMVI_ERR_BAD_ARG;
+}
+
+#define GB_BAD(cond, msg)                           \
+    do {                                            \
+        if (cond) return gb_bad(__func__, msg);     \
     } while (0)
+
+// problems per 256-thread workgroup of k_gsm_batched and k_kl_batched (B plays no part)
+static inline int gb_ppw(int D, int) { return 256 / gb_nt(D); }
+
+// 1 <= D <= 64; 1 <= B <= 32 (an entry point without B leaves the default); K >= 1 and, at ppw(D, B) problems per
+// workgroup (asked only for D and B in bounds), fewer than 2^32 threads in one launch: K <= ppw (2^24 - 1)
+static inline int gb_check_shape(const char* fn, int64_t K, int D, int (*ppw)(int D, int B), int B = 1) {
+    if (D < 1 || D > GB_MAX_D) return gb_bad(fn, "D must be in [1, 64]");
+    if (B < 1 || B > GB_MAX_B) return gb_bad(fn, "B must be in [1, 32]");
+    if (K < 1 || K > (int64_t)ppw(D, B) * 16777215)
+        return gb_bad(fn, "K must be in [1, 2^24 - 1] (one problem per workgroup) or [1, 2^26 - 4] (four)");
+    return GSMVI_OK;
+}
+
+// one array of an entry point's overlap table: written (GB_WR) if a kernel may store to it, else read-only (GB_RD)
+constexpr bool GB_RD = false, GB_WR = true;
+struct gb_arr {
+    const void* p;
+    size_t bytes;
+    const char* name;
+    bool written;
+};
+
+// The overlap rule of every batched entry point: an array that is written must not overlap any other listed array; read-only
+// arrays may overlap each other; NULL entries are skipped.  The message names both arrays.
+static inline int gb_check_overlaps(const char* fn, std::initializer_list<gb_arr> arrs) {
+    for (const gb_arr* a = arrs.begin(); a != arrs.end(); ++a)
+        for (const gb_arr* b = arrs.begin(); b != a; ++b)
+            if (a->p && b->p && (a->written || b->written) && gb_overlap(a->p, a->bytes, b->p, b->bytes)) {
+                char msg[96];
+                snprintf(msg, sizeof msg, "%s overlaps %s", (a->written ? a : b)->name, (a->written ? b : a)->name);
+                return gb_bad(fn, msg);
+            }
+    return GSMVI_OK;
+}
+
+// the end of every batched launch: a launch error -> GSMVI_ERR_HIP, else the kernel family's path bit is recorded
+static inline int gb_launched(gsmvi_ctx* ctx, unsigned path, const char* kernel) {
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) {
+        gsmvi_set_error("launch of %s failed: %s", kernel, hipGetErrorString(e));
+        return GSMVI_ERR_HIP;
+    }
+    ctx->path |= path;
+    return GSMVI_OK;
+}
+
+// lets every given kernel request up to GB_LDS_MAX of dynamic LDS (one problem of D = 64, B = 32 takes up to 145 KB)
+template <typename... F>
+static hipError_t gb_allow_lds(F*... kernels) {
+    for (const void* f : {reinterpret_cast<const void*>(kernels)...}) {
+        const hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, GB_LDS_MAX);
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}

@@ -146,27 +146,8 @@ __global__ __launch_bounds__(256) void k_gauss_score_batched(long long total, in
 }
 
 hipError_t gsmvi_batched_prepare() {
-    const void* fns[] = {
-        reinterpret_cast<const void*>(k_gsm_batched<64, GB_UPDATE>), reinterpret_cast<const void*>(k_gsm_batched<256, GB_UPDATE>),
-        reinterpret_cast<const void*>(k_gsm_batched<64, GB_STEP>), reinterpret_cast<const void*>(k_gsm_batched<256, GB_STEP>),
-        reinterpret_cast<const void*>(k_gsm_batched<64, GB_INIT>), reinterpret_cast<const void*>(k_gsm_batched<256, GB_INIT>)};
-    for (const void* f : fns) {
-        hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return e;
-    }
-    return hipSuccess;
-}
-
-static int gb_check(gsmvi_ctx* ctx, int64_t K, int D, int B, const char* fn) {
-    if (!ctx) { gsmvi_set_error("%s: %s", fn, "ctx is NULL"); return GSMVI_ERR_BAD_ARG; }
-    if (D < 1 || D > GB_MAX_D) { gsmvi_set_error("%s: %s", fn, "D must be in [1, 64]"); return GSMVI_ERR_BAD_ARG; }
-    if (B < 1 || B > GB_MAX_B) { gsmvi_set_error("%s: %s", fn, "B must be in [1, 32]"); return GSMVI_ERR_BAD_ARG; }
-    // one launch: fewer than 2^32 threads -- K < 2^24 problems for D > 16, 2^26 for D <= 16 (the D^2 arrays fill memory first)
-    if (K < 1 || K > (int64_t)(256 / gb_nt(D)) * 16777215) {
-        gsmvi_set_error("%s: %s", fn, "K must be in [1, 2^24 - 1] (D > 16) or [1, 2^26 - 4] (D <= 16)");
-        return GSMVI_ERR_BAD_ARG;
-    }
-    return GSMVI_OK;
+    return gb_allow_lds(k_gsm_batched<64, GB_UPDATE>, k_gsm_batched<256, GB_UPDATE>, k_gsm_batched<64, GB_STEP>,
+                        k_gsm_batched<256, GB_STEP>, k_gsm_batched<64, GB_INIT>, k_gsm_batched<256, GB_INIT>);
 }
 
 static int gb_launch(gsmvi_ctx* ctx, void* stream, int mode, const gb_args& a, const char* fn) {
@@ -181,26 +162,20 @@ static int gb_launch(gsmvi_ctx* ctx, void* stream, int mode, const gb_args& a, c
         if (mode == GB_UPDATE) GB_GO(256, GB_UPDATE); else if (mode == GB_STEP) GB_GO(256, GB_STEP); else GB_GO(256, GB_INIT);
     }
 #undef GB_GO
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        gsmvi_set_error("launch of %s failed: %s", fn, hipGetErrorString(e));
-        return GSMVI_ERR_HIP;
-    }
-    ctx->path |= GSMVI_PATH_BATCHED;
-    return GSMVI_OK;
+    return gb_launched(ctx, GSMVI_PATH_BATCHED, fn);
 }
 
 extern "C" {
 
 int gsmvi_gsm_update_batched_f64(gsmvi_ctx* ctx, void* stream, int64_t K, int D, int B, const double* X, const double* G,
                                  const double* mu0, const double* S0, double* mu, double* S) {
-    int st = gb_check(ctx, K, D, B, __func__);
-    if (st != GSMVI_OK) return st;
+    if (int st = gb_check_shape(__func__, K, D, gb_ppw, B)) return st;
     GB_BAD(!X || !G || !mu0 || !S0 || !mu || !S, "NULL array");
     const size_t nv = (size_t)K * D * 8, nm = (size_t)K * D * D * 8, nx = (size_t)K * B * D * 8;
-    GB_BAD(gb_overlap(mu, nv, S, nm) || gb_overlap(mu, nv, X, nx) || gb_overlap(mu, nv, G, nx) || gb_overlap(mu, nv, mu0, nv) ||
-           gb_overlap(mu, nv, S0, nm) || gb_overlap(S, nm, X, nx) || gb_overlap(S, nm, G, nx) || gb_overlap(S, nm, mu0, nv) ||
-           gb_overlap(S, nm, S0, nm), "outputs overlap each other or an input");
+    if (int st = gb_check_overlaps(__func__, {{X, nx, "X", GB_RD}, {G, nx, "G", GB_RD}, {mu0, nv, "mu0", GB_RD},
+                                              {S0, nm, "S0", GB_RD}, {mu, nv, "mu", GB_WR}, {S, nm, "S", GB_WR}}))
+        return st;
+    GB_BAD(!ctx, "ctx is NULL");
     gb_args a = {};
     a.K = K; a.D = D; a.B = B; a.X = X; a.V = G; a.mu0 = mu0; a.S0 = S0; a.mu = mu; a.S = S;
     return gb_launch(ctx, stream, GB_UPDATE, a, "k_gsm_batched (update)");
@@ -208,13 +183,16 @@ int gsmvi_gsm_update_batched_f64(gsmvi_ctx* ctx, void* stream, int64_t K, int D,
 
 int gsmvi_gsm_fit_init_batched_f64(gsmvi_ctx* ctx, void* stream, int64_t K, int D, int B, const double* mean, const double* cov,
                                    double* R, int* info_dev, const uint64_t* seeds_dev, double* X) {
-    int st = gb_check(ctx, K, D, B, __func__);
-    if (st != GSMVI_OK) return st;
+    if (int st = gb_check_shape(__func__, K, D, gb_ppw, B)) return st;
     GB_BAD(!mean || !cov || !R || !info_dev, "NULL array");
     GB_BAD(seeds_dev && !X, "seeds given without X");
-    const size_t nv = (size_t)K * D * 8, nm = (size_t)K * D * D * 8, nx = (size_t)K * B * D * 8;
-    GB_BAD(gb_overlap(R, nm, cov, nm) || gb_overlap(R, nm, mean, nv) || (X && (gb_overlap(X, nx, R, nm) ||
-           gb_overlap(X, nx, cov, nm) || gb_overlap(X, nx, mean, nv))), "outputs overlap each other or an input");
+    const size_t nv = (size_t)K * D * 8, nm = (size_t)K * D * D * 8, nx = (size_t)K * B * D * 8, nk = (size_t)K * 8,
+                 ni = (size_t)K * 4;
+    if (int st = gb_check_overlaps(__func__, {{mean, nv, "mean", GB_RD}, {cov, nm, "cov", GB_RD}, {R, nm, "R", GB_WR},
+                                              {info_dev, ni, "info_dev", GB_WR}, {seeds_dev, nk, "seeds_dev", GB_RD},
+                                              {X, nx, "X", GB_WR}}))
+        return st;
+    GB_BAD(!ctx, "ctx is NULL");
     gb_args a = {};
     a.K = K; a.D = D; a.B = B; a.mu = const_cast<double*>(mean); a.S = const_cast<double*>(cov); a.R = R; a.info = info_dev;
     a.seeds = reinterpret_cast<const unsigned long long*>(seeds_dev); a.call = 0; a.Xout = X;
@@ -224,15 +202,16 @@ int gsmvi_gsm_fit_init_batched_f64(gsmvi_ctx* ctx, void* stream, int64_t K, int 
 int gsmvi_gsm_fit_step_batched_f64(gsmvi_ctx* ctx, void* stream, int64_t K, int D, int B, double* X, const double* G, double* mean,
                                    double* cov, double* R, int* info_dev, int* n_reverts_dev, const uint64_t* seeds_dev,
                                    uint64_t call) {
-    int st = gb_check(ctx, K, D, B, __func__);
-    if (st != GSMVI_OK) return st;
+    if (int st = gb_check_shape(__func__, K, D, gb_ppw, B)) return st;
     GB_BAD(!X || !G || !mean || !cov, "NULL array");
     GB_BAD(seeds_dev && !R, "drawing the next samples needs the sampling factor R");
-    const size_t nv = (size_t)K * D * 8, nm = (size_t)K * D * D * 8, nx = (size_t)K * B * D * 8;
-    GB_BAD(gb_overlap(X, nx, G, nx) || gb_overlap(X, nx, mean, nv) || gb_overlap(X, nx, cov, nm) || gb_overlap(G, nx, mean, nv) ||
-           gb_overlap(G, nx, cov, nm) || gb_overlap(mean, nv, cov, nm) ||
-           (R && (gb_overlap(R, nm, X, nx) || gb_overlap(R, nm, G, nx) || gb_overlap(R, nm, mean, nv) || gb_overlap(R, nm, cov, nm))),
-           "arrays overlap");
+    const size_t nv = (size_t)K * D * 8, nm = (size_t)K * D * D * 8, nx = (size_t)K * B * D * 8, nk = (size_t)K * 8,
+                 ni = (size_t)K * 4;
+    if (int st = gb_check_overlaps(__func__, {{X, nx, "X", GB_WR}, {G, nx, "G", GB_RD}, {mean, nv, "mean", GB_WR},
+                                              {cov, nm, "cov", GB_WR}, {R, nm, "R", GB_WR}, {info_dev, ni, "info_dev", GB_WR},
+                                              {n_reverts_dev, ni, "n_reverts_dev", GB_WR}, {seeds_dev, nk, "seeds_dev", GB_RD}}))
+        return st;
+    GB_BAD(!ctx, "ctx is NULL");
     gb_args a = {};
     a.K = K; a.D = D; a.B = B; a.X = X; a.V = G; a.mu = mean; a.S = cov; a.R = R; a.info = info_dev; a.n_rev = n_reverts_dev;
     a.seeds = reinterpret_cast<const unsigned long long*>(seeds_dev); a.call = call; a.Xout = seeds_dev ? X : nullptr;
@@ -241,23 +220,17 @@ int gsmvi_gsm_fit_step_batched_f64(gsmvi_ctx* ctx, void* stream, int64_t K, int 
 
 int gsmvi_gaussian_score_batched_f64(gsmvi_ctx* ctx, void* stream, int64_t K, int D, int B, const double* X, const double* m,
                                      const double* P, double* G) {
-    int st = gb_check(ctx, K, D, B, __func__);
-    if (st != GSMVI_OK) return st;
+    if (int st = gb_check_shape(__func__, K, D, gb_ppw, B)) return st;
     GB_BAD(!X || !m || !P || !G, "NULL array");
-    const size_t nx = (size_t)K * B * D * 8;
-    GB_BAD(gb_overlap(G, nx, X, nx) || gb_overlap(G, nx, m, (size_t)K * D * 8) || gb_overlap(G, nx, P, (size_t)K * D * D * 8),
-           "G overlaps an input");
+    const size_t nv = (size_t)K * D * 8, nm = (size_t)K * D * D * 8, nx = (size_t)K * B * D * 8;
+    if (int st = gb_check_overlaps(__func__, {{X, nx, "X", GB_RD}, {m, nv, "m", GB_RD}, {P, nm, "P", GB_RD}, {G, nx, "G", GB_WR}}))
+        return st;
     const long long total = (long long)K * B * D;
     GB_BAD(total > 0xFFFFFF00ll, "K B D must be below 2^32 - 256 (one thread per score entry)");
+    GB_BAD(!ctx, "ctx is NULL");
     hipLaunchKernelGGL(k_gauss_score_batched, dim3((unsigned)((total + 255) / 256)), dim3(256), 0,
                        reinterpret_cast<hipStream_t>(stream), total, D, B, X, m, P, G);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        gsmvi_set_error("launch of %s failed: %s", "k_gauss_score_batched", hipGetErrorString(e));
-        return GSMVI_ERR_HIP;
-    }
-    ctx->path |= GSMVI_PATH_BATCHED;
-    return GSMVI_OK;
+    return gb_launched(ctx, GSMVI_PATH_BATCHED, "k_gauss_score_batched");
 }
 
 }  // extern "C"

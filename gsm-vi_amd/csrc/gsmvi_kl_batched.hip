@@ -158,19 +158,6 @@ __global__ __launch_bounds__(256) void k_kl_batched(kb_args a) {
     }
 }
 
-// Shapes and arrays are checked before the context is looked at (a NULL context is the last thing reported).
-static int kb_check(int64_t K, int D, int64_t nc, const char* fn) {
-    if (D < 1 || D > GB_MAX_D) { gsmvi_set_error("%s: %s", fn, "D must be in [1, 64]"); return GSMVI_ERR_BAD_ARG; }
-    // one launch: fewer than 2^32 threads -- K < 2^24 problems at one per workgroup (D > 16), 2^26 at four (D <= 16)
-    if (K < 1 || K > (int64_t)(256 / gb_nt(D)) * 16777215) {
-        gsmvi_set_error("%s: %s", fn, "K must be in [1, 2^24 - 1] (D > 16) or [1, 2^26 - 4] (D <= 16)");
-        return GSMVI_ERR_BAD_ARG;
-    }
-    if (nc < 1) { gsmvi_set_error("%s: %s", fn, "nc must be at least 1"); return GSMVI_ERR_BAD_ARG; }
-    if (nc > (INT64_MAX / 8 / D) / K) { gsmvi_set_error("%s: %s", fn, "K nc D is too large"); return GSMVI_ERR_BAD_ARG; }
-    return GSMVI_OK;
-}
-
 static int kb_launch(gsmvi_ctx* ctx, void* stream, int mode, kb_args& a, const char* fn) {
     const int nt = gb_nt(a.D), ppw = 256 / nt;
     a.ld = a.D | 1;
@@ -186,33 +173,23 @@ static int kb_launch(gsmvi_ctx* ctx, void* stream, int mode, kb_args& a, const c
         if (mode == KB_DRAW) KB_GO(256, KB_DRAW); else KB_GO(256, KB_EVAL);
     }
 #undef KB_GO
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        gsmvi_set_error("launch of %s failed: %s", fn, hipGetErrorString(e));
-        return GSMVI_ERR_HIP;
-    }
-    ctx->path |= GSMVI_PATH_BATCHED_KL;
-    return GSMVI_OK;
+    return gb_launched(ctx, GSMVI_PATH_BATCHED_KL, fn);
 }
 
 extern "C" {
 
 int gsmvi_kl_draw_batched_f64(gsmvi_ctx* ctx, void* stream, int64_t K, int D, int64_t nc, int64_t s0, const double* mean,
                               const double* cov, const uint64_t* seeds, uint64_t call, double* X, double* logq_sum, int* info) {
-    int st = kb_check(K, D, nc, __func__);
-    if (st != GSMVI_OK) return st;
+    if (int st = gb_check_shape(__func__, K, D, gb_ppw)) return st;
+    GB_BAD(nc < 1, "nc must be at least 1");
+    GB_BAD(nc > (INT64_MAX / 8 / D) / K, "K nc D is too large");
     GB_BAD(s0 < 0 || s0 > (INT64_MAX / 2 - nc) / D, "s0 must be >= 0 and (s0 + nc) D below 2^62");
     GB_BAD(!mean || !cov || !seeds || !X || !logq_sum || !info, "NULL array");
     const size_t nv = (size_t)K * D * 8, nm = (size_t)K * D * D * 8, nx = (size_t)K * nc * D * 8, nk = (size_t)K * 8,
                  ni = (size_t)K * 4;
-    const void* wr[] = {X, logq_sum, info};
-    const size_t wn[] = {nx, nk, ni};
-    const void* ro[] = {mean, cov, seeds};
-    const size_t rn[] = {nv, nm, nk};
-    for (int i = 0; i < 3; ++i)
-        for (int j = 0; j < 3; ++j)
-            GB_BAD((i != j && gb_overlap(wr[i], wn[i], wr[j], wn[j])) || gb_overlap(wr[i], wn[i], ro[j], rn[j]),
-                   "outputs overlap each other or an input");
+    if (int st = gb_check_overlaps(__func__, {{mean, nv, "mean", GB_RD}, {cov, nm, "cov", GB_RD}, {seeds, nk, "seeds", GB_RD},
+                                              {X, nx, "X", GB_WR}, {logq_sum, nk, "logq_sum", GB_WR}, {info, ni, "info", GB_WR}}))
+        return st;
     GB_BAD(!ctx, "ctx is NULL");
     kb_args a = {};
     a.K = K; a.D = D; a.nc = nc; a.s0 = s0; a.mean = mean; a.cov = cov;
@@ -222,19 +199,15 @@ int gsmvi_kl_draw_batched_f64(gsmvi_ctx* ctx, void* stream, int64_t K, int D, in
 
 int gsmvi_logq_batched_f64(gsmvi_ctx* ctx, void* stream, int64_t K, int D, int64_t nc, const double* mean, const double* cov,
                            const double* Y, double* logq_sum, int* info) {
-    int st = kb_check(K, D, nc, __func__);
-    if (st != GSMVI_OK) return st;
+    if (int st = gb_check_shape(__func__, K, D, gb_ppw)) return st;
+    GB_BAD(nc < 1, "nc must be at least 1");
+    GB_BAD(nc > (INT64_MAX / 8 / D) / K, "K nc D is too large");
     GB_BAD(!mean || !cov || !Y || !logq_sum || !info, "NULL array");
     const size_t nv = (size_t)K * D * 8, nm = (size_t)K * D * D * 8, ny = (size_t)K * nc * D * 8, nk = (size_t)K * 8,
                  ni = (size_t)K * 4;
-    const void* wr[] = {logq_sum, info};
-    const size_t wn[] = {nk, ni};
-    const void* ro[] = {mean, cov, Y};
-    const size_t rn[] = {nv, nm, ny};
-    for (int i = 0; i < 2; ++i) {
-        GB_BAD(gb_overlap(wr[i], wn[i], wr[1 - i], wn[1 - i]), "outputs overlap each other or an input");
-        for (int j = 0; j < 3; ++j) GB_BAD(gb_overlap(wr[i], wn[i], ro[j], rn[j]), "outputs overlap each other or an input");
-    }
+    if (int st = gb_check_overlaps(__func__, {{mean, nv, "mean", GB_RD}, {cov, nm, "cov", GB_RD}, {Y, ny, "Y", GB_RD},
+                                              {logq_sum, nk, "logq_sum", GB_WR}, {info, ni, "info", GB_WR}}))
+        return st;
     GB_BAD(!ctx, "ctx is NULL");
     kb_args a = {};
     a.K = K; a.D = D; a.nc = nc; a.mean = mean; a.cov = cov; a.Y = Y; a.logq = logq_sum; a.info = info;

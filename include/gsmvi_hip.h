@@ -285,8 +285,11 @@ int gsmvi_gaussian_score_f64(gsmvi_ctx* ctx, void* stream, int D, int B,
  * Batched GSM (K independent problems of the same (D, B)): 1 <= D <= 64, 1 <= B <= 32, K >= 1 (one launch each: K < 2^24 for
  * D > 16, K < 2^26 for D <= 16).  Every array is packed and contiguous with a leading problem axis -- X, G (K x B x D),
  * mu (K x D), S, R (K x D x D) -- in device memory; problem k reads and writes only slice k of each, so a NaN or a revert in
- * one problem cannot reach another.  Out-of-range shapes and NULL or overlapping arrays return GSMVI_ERR_BAD_ARG before
- * anything is enqueued.  No context workspace is used (the kernels keep a problem in LDS).  Sets GSMVI_PATH_BATCHED.
+ * one problem cannot reach another.  Shapes, NULL arrays and overlaps are checked before the context is looked at (then a
+ * NULL ctx); every failure returns GSMVI_ERR_BAD_ARG before anything is enqueued.  The overlap rule of every batched entry
+ * point: an array that a kernel may write (an output, a fit's state or counters, a fit step's X) must not overlap any other
+ * array of the call, NULL ones aside; read-only arrays may overlap each other.  No context workspace is used (the kernels
+ * keep a problem in LDS).  Sets GSMVI_PATH_BATCHED.
  *
  * gsmvi/gsm_numpy.py:27-55 gsm_update under jax.vmap (gsmvi/gsm.py:31-58) -> gsmvi_gsm_update_batched_f64:
  *   (mu_k, S_k) = gsm_update(X_k, G_k, mu0_k, S0_k) for every k.  Reads ALL of S0_k (both triangles: the reference's literal

@@ -37,8 +37,9 @@ def test_batched_bam_entry_points_are_declared_and_exported():
     assert HipEngine.PATH_BITS["batched_bam"] == 0x4000 and not HipEngine.PATH_GENERIC_MASK & 0x4000
 
 
-def test_abi_checks_arguments_before_the_context():
-    """every bad argument is reported with a NULL context (no device work can have started); valid ones end at the context"""
+def test_abi_checks_arguments_before_the_context_and_names_overlapping_arrays():
+    """every bad argument is reported with a NULL context (no device work can have started); valid ones end at the context;
+    an overlap is reported with the names of both arrays"""
     lib = _lib.load_library()
     buf = (C.c_double * 4096)()
     p = C.cast(buf, C.c_void_p).value
@@ -73,11 +74,11 @@ def test_abi_checks_arguments_before_the_context():
                                                   info, nrev, seeds, 0, Xout)
 
     assert step2(info=i1, nrev=i2) == 1 and "ctx is NULL" in err()
-    assert step2(info=q + 8 * 128) == 1 and "info_dev / n_reverts_dev overlap" in err()      # info inside mean
-    assert step2(nrev=q + 8 * 256) == 1 and "info_dev / n_reverts_dev overlap" in err()      # n_reverts inside cov
-    assert step2(info=i1, nrev=i1 + 4) == 1 and "info_dev / n_reverts_dev overlap" in err()  # the two counters overlap
+    assert step2(info=q + 8 * 128) == 1 and "info_dev overlaps mean" in err()                # info inside mean
+    assert step2(nrev=q + 8 * 256) == 1 and "n_reverts_dev overlaps cov" in err()            # n_reverts inside cov
+    assert step2(info=i1, nrev=i1 + 4) == 1 and "n_reverts_dev overlaps info_dev" in err()   # the two counters overlap
     assert step2(reg_dev=q + 8 * 128) == 1 and "overlap" in err()
-    assert step2(seeds=q + 8 * 256, R=q + 8 * 1024, Xout=p) == 1 and "overlaps G, seeds_dev or reg_dev" in err()
+    assert step2(seeds=q + 8 * 256, R=q + 8 * 1024, Xout=p) == 1 and "cov overlaps seeds_dev" in err()
     assert upd(1, 4, 2) == 1
     assert lib.gsmvi_bam_update_batched_f64(None, None, 1, 4, 2, p, p, p, p, 1.0, None, 0.0, q, q + 8 * 64, p) == 1 \
         and "overlap" in err()                                          # info over an input
