@@ -14,6 +14,9 @@ Mirrors the reference's public surface for the hot path (reference file:line):
     DeviceKLMonitor (same protocol, on the GPU)  gsmvi/monitors.py:43-125
     BatchedKLMonitor (the same for the K problems
     of GSMBatch / BaMBatch, one launch per chunk) gsmvi/monitors.py:43-125
+    ADVIBatch, Adam (the ELBO baseline for K
+    problems at once, D <= 64: closed-form
+    gradient + Adam in one launch per iteration) gsmvi/advi.py:8-112
     lbfgs_init, ADVI (initialiser and the ELBO
     baseline of the examples; off the hot path)  gsmvi/initializers.py:5-17, gsmvi/advi.py:8-112
 All GSM / BaM numerics run in hand-written HIP kernels (libgsmvi_hip.so, C ABI in include/gsmvi_hip.h)
@@ -29,6 +32,7 @@ from .targets import GaussianTarget, device_score, score_from_logp   # noqa: F40
 from .targets import BatchedGaussianTarget                           # noqa: F401
 from .batched import GSMBatch, gsm_update_batched                    # noqa: F401
 from .batched import BaMBatch, bam_update_batched, bam_lowrank_update_batched   # noqa: F401
+from .batched import ADVIBatch, Adam                                 # noqa: F401
 from .monitors import KLMonitor, DeviceKLMonitor, BatchedKLMonitor   # noqa: F401
 from .initializers import lbfgs_init                                 # noqa: F401
 from .advi import ADVI                                               # noqa: F401

@@ -1,10 +1,11 @@
-"""Batched GSM and BaM: K independent problems of the same (D, B) in one launch per step (csrc/gsmvi_batched.hip,
-csrc/gsmvi_bam_batched.hip).
+"""Batched GSM, BaM and ADVI: K independent problems of the same (D, B) in one launch per step (csrc/gsmvi_batched.hip,
+csrc/gsmvi_bam_batched.hip, csrc/gsmvi_advi_batched.hip).
 
 The reference's updates are pure functions of (samples, vs, mu0, S0[, reg]) (gsmvi/gsm.py:31-58, gsmvi/bam.py:31-114), so
 ``jax.vmap`` batches them over a leading problem axis; ``gsm_update_batched`` and ``bam_update_batched`` are those calls.
 ``GSMBatch.fit`` runs the dense fit of gsm_numpy.py:77-129 and ``BaMBatch.fit`` the dense loop of bam.py:140-216 for K
-problems at once: one launch plus the score call per iteration, whatever K is.  Bounds: 1 <= D <= 64, 1 <= B <= 32.
+problems at once: one launch plus the score call per iteration, whatever K is.  ``ADVIBatch.fit`` is the ELBO baseline they are
+compared against (gsmvi/advi.py:47-112) in the same form.  Bounds: 1 <= D <= 64, 1 <= B <= 32.
 """
 import numpy as np
 
@@ -12,6 +13,7 @@ from ._fitloop import Checkpoints, Progress, _is_torch, result, scorer, seed_of,
 from .engine import get_engine
 from .bam import _every as _bam_every
 from .gsm import _every
+from .monitors import lp_sums
 
 MAX_D = 64
 MAX_B = 32
@@ -70,7 +72,8 @@ def _seeds(keys, K, who, last):
 class _BatchFit:
     """The constructor and the fit loop of GSMBatch and BaMBatch.  A subclass gives its name (``_name``; ``_what`` in bound
     errors), the print cadence of its single-problem fit (``_cadence``), the seed of a key (``_last``, as ``seed_of``
-    takes it) and, per fit, the launch of an iteration after the score."""
+    takes it) and, per fit, the launch of an iteration after the score.  (ADVIBatch takes the constructor and runs a loop of its
+    own: its state is not (mean, cov, factor) and nothing in it reverts.)"""
 
     def __init__(self, K, D, lp, lp_g, engine=None):
         self.K, self.D = int(K), int(D)
@@ -163,8 +166,9 @@ class GSMBatch(_BatchFit):
         return self._fit(step, keys, mean, cov, batch_size, niter, nprint, verbose, forced_samples, as_torch, monitor)
 
 
-def _reg_values(reg, K, who):
-    """a regulariser as the engine takes it: a float, or K per-problem values (ValueError for any other length)"""
+def _reg_values(reg, K, who, what="reg"):
+    """a regulariser (or a step size, ``what``) as the engine takes it: a float, or K per-problem values (ValueError for any
+    other length)"""
     if _is_torch(reg):
         reg = reg.detach().cpu().numpy()
     r = np.asarray(reg, dtype=np.float64)
@@ -172,7 +176,7 @@ def _reg_values(reg, K, who):
         return float(r)
     r = r.reshape(-1)
     if r.size != K:
-        raise ValueError(f"{who}: reg has {r.size} values for K = {K} problems (give one float or K values)")
+        raise ValueError(f"{who}: {what} has {r.size} values for K = {K} problems (give one float or K values)")
     return r
 
 
@@ -239,3 +243,107 @@ class BaMBatch(_BatchFit):
                                      n_rev, seeds, i + 1)
 
         return self._fit(step, keys, mean, cov, batch_size, niter, nprint, verbose, forced_samples, as_torch, monitor)
+
+
+class Adam:
+    """Adam as ``ADVIBatch.fit`` takes it: the counterpart of ``optax.adam(lr, b1, b2, eps)`` in the reference's call
+    (examples/example_advi.py) and of ``torch.optim.Adam`` at its defaults.  ``lr``: a float, K per-problem values, or a
+    callable ``i -> float or K values`` (an optax schedule), asked once per iteration."""
+
+    def __init__(self, lr, b1=0.9, b2=0.999, eps=1e-8):
+        self.lr, self.b1, self.b2, self.eps = lr, float(b1), float(b2), float(eps)
+        if not (0.0 <= self.b1 < 1.0 and 0.0 <= self.b2 < 1.0):
+            raise ValueError(f"Adam: b1 = {b1} and b2 = {b2} must be in [0, 1)")
+        if not self.eps >= 0.0:
+            raise ValueError(f"Adam: eps = {eps} must not be negative")
+
+    def lr_at(self, i, K, who):
+        """the step size of iteration i: a float, or K values"""
+        return _reg_values(self.lr(i) if callable(self.lr) else self.lr, K, who, "lr")
+
+
+class ADVIBatch(_BatchFit):
+    """K independent full-rank ADVI fits of the same dimension D (gsmvi/advi.py:8-112), one launch per iteration after the score.
+
+    The ELBO baseline the reference compares GSM and BaM against, for K problems at once: q_k = N(loc_k, L_k L_k^T), Adam on
+    (loc_k, the D (D + 1) / 2 entries of L_k) with the closed-form gradient of the reference's loss (advi.py:31-45), so the
+    user supplies the score and no autograd runs (csrc/gsmvi_advi_batched.hip).
+
+    K    : number of problems.
+    D    : dimensionality, 1 <= D <= 64.
+    lp   : batched log-density, (K,rows,D) -> (K,) sums or (K,rows) values: the losses and a batched ``monitor`` call it; may be
+           None (then no losses are returned).
+    lp_g : score (K,B,D) -> (K,B,D), as for GSMBatch (a plain callable gets numpy arrays; a ``device_native`` one float64 CUDA
+           tensors and keeps the whole iteration on the GPU).
+    """
+
+    _name, _what, _cadence, _last = "ADVIBatch", "batched ADVI", staticmethod(_every), False
+
+    def fit(self, keys, opt, mean=None, cov=None, batch_size=8, niter=1000, nprint=10, monitor=None, *, verbose=True,
+            track_loss=True, forced_z=None, as_torch=False):
+        """Fit N(mean_k, cov_k) to target k for every k; returns (mean (K,D), cov (K,D,D), losses (niter+1,K) or None): the
+        reference's positional order and defaults (advi.py:47), ``niter + 1`` steps as the reference runs.
+
+        ``opt``: an ``Adam``.  Per problem and iteration i (advi.py:69-73,100): with the samples x_b = loc + L z_b of the current
+        state and their scores, losses[i] = -(sum_b lp(x_b) - sum_b log q(x_b)), the gradient, Adam step i + 1, and the next
+        samples from the updated state -- one launch after the score.  z of iteration i is call i of the Philox stream seeded
+        by ``seed_of(keys[k])``, in the layout of ``GSMBatch.fit``: with the same keys the two fits consume the same normals.
+        ``mean`` / ``cov``: (K,D) / (K,D,D), zeros and identities by default; a cov[k] that is not positive definite raises
+        ValueError naming k.  ``forced_z``: (niter+1, K, B, D) teacher-forced normals in place of the stream.  The losses
+        accumulate on the device and are read once after the loop; ``track_loss=False`` (or ``lp`` None) never calls ``lp`` and
+        returns None for them.  A non-finite score is not caught: that problem's state is NaN from then on, as in the
+        reference, and no other problem changes.  ``monitor``: a batched monitor (``BatchedKLMonitor``), called as
+        ``monitor(i, [mean, cov], lp, keys, nevals=n)`` with the cadence of advi.py:93-98,109-110; the covariance L L^T is formed
+        only at a checkpoint, and the fit returns the same bits with or without a monitor; any other monitor raises TypeError.
+        """
+        who = "ADVIBatch.fit"
+        _check_monitor(monitor, who)
+        if not isinstance(opt, Adam):
+            raise TypeError(f"{who}: opt must be a gsmvi_amd.Adam (the optimiser is built into the step kernel)")
+        K, D, B = self.K, self.D, int(batch_size)
+        niter = int(niter)
+        _check_bounds(D, B, self._what)
+        seeds = _seeds(keys, K, who, last=self._last)
+        if mean is not None:
+            assert _shape(mean) == (K, D), f"mean: expected shape {(K, D)}"
+        if cov is not None:
+            assert _shape(cov) == (K, D, D), f"cov: expected shape {(K, D, D)}"
+        if forced_z is not None:
+            assert _shape(forced_z) == (niter + 1, K, B, D), f"forced_z: expected shape {(niter + 1, K, B, D)}"
+        lr0 = opt.lr_at(0, K, who)
+        eng = self._engine if self._engine is not None else get_engine()
+        P = D * (D + 1) // 2
+        loc = eng.zeros(K, D) if mean is None else eng.clone(mean).reshape(K, D)
+        cov_t = eng.eye_batch(K, D) if cov is None else eng.clone(cov).reshape(K, D, D)
+        draw = forced_z is None
+        scales, X, logq, info = eng.empty(K, P), eng.empty(K, B, D), eng.empty(K), eng.batched_ints(K)
+        seeds_t = eng.batched_seeds(seeds) if draw else None
+        Zf = None if draw else eng.asarray(forced_z)
+        eng.advi_init_batched(loc, cov_t, scales, info, seeds_t, None if draw else Zf[0], X, logq)
+        bad = np.flatnonzero(eng.read_ints(info))
+        if bad.size:
+            raise ValueError(f"{who}: initial covariance is not positive definite for problem(s) {bad.tolist()}")
+        moments = tuple(eng.zeros(K, n) for n in (D, D, P, P))
+        score = scorer(eng, self.lp_g)
+        out_ok = not getattr(self.lp_g, "device_native", False) or takes_out(self.lp_g)
+        Gbuf = eng.empty(K, B, D)
+        track = bool(track_loss) and self.lp is not None
+        losses = eng.zeros(niter + 1, K) if track else None
+        progress = Progress(eng, None, niter, self._cadence(nprint, niter), verbose, read=lambda t: 0)     # (nothing reverts)
+        mon = Checkpoints(eng, monitor, self.lp, keys, lambda: (loc, eng.advi_cov_batched(scales, D)))
+        for i in range(niter + 1):
+            progress.tick(i)
+            mon.tick(i)
+            G = score(X, out=Gbuf) if out_ok else score(X)
+            mon.nevals += B
+            if track:
+                losses[i] = logq - lp_sums(self.lp, X, eng, K)
+            nxt = i < niter
+            lr = lr0 if i == 0 else opt.lr_at(i, K, who)
+            eng.advi_step_batched(G, loc, scales, moments, i + 1, lr if isinstance(lr, float) else eng.batched_regs(lr),
+                                  opt.b1, opt.b2, opt.eps, seeds=seeds_t, call=i + 1, Zcur=None if draw else Zf[i],
+                                  Znext=Zf[i + 1] if nxt and not draw else None, Xout=X if nxt else None,
+                                  logq=logq if nxt else None)
+        mon.final(niter)
+        mean_t, cov_t = result(eng, loc, eng.advi_cov_batched(scales, D), as_torch)
+        return mean_t, cov_t, (losses if as_torch or losses is None else eng.to_numpy(losses))

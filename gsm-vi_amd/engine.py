@@ -584,7 +584,7 @@ class HipEngine:
     PATH_BITS = {"panel_fast": 0x1, "panel_wide": 0x2, "panel_generic": 0x4, "panel_t_fast": 0x8, "panel_t_generic": 0x10,
                  "scalars_fast": 0x20, "scalars_generic": 0x40, "cov_sym": 0x80, "cov_generic": 0x100, "fupd_fast": 0x200,
                  "fupd_generic": 0x400, "lowrank_fast": 0x800, "lowrank_generic": 0x1000, "batched": 0x2000,
-                 "batched_bam": 0x4000, "batched_kl": 0x8000}
+                 "batched_bam": 0x4000, "batched_kl": 0x8000, "batched_advi": 0x10000}
     PATH_GENERIC_MASK = 0x4 | 0x10 | 0x40 | 0x100 | 0x400 | 0x1000
 
     def last_path(self, reset=True):
@@ -816,6 +816,53 @@ class HipEngine:
             self._ctx, self._stream(), K, D, nc, self._packed(mean, (K, D), "mean"), self._packed(cov, (K, D, D), "cov"),
             self._packed(Y, (K, nc, D), "Y"), self._packed(logq, (K,), "logq"), self._ints(info, K, "info")))
         return logq, info
+
+    # ---- batched ADVI: K full-rank ELBO fits of one (D, B) (csrc/gsmvi_advi_batched.hip) ----------------------------------
+    @staticmethod
+    def _dp(t, shape, name):
+        return HipEngine._packed(t, shape, name) if t is not None else None
+
+    def advi_init_batched(self, mean, cov, scales, info, seeds=None, Z=None, X=None, logq=None):
+        """scales_k = packed lower Cholesky factor of cov_k (np.tril_indices order), info[k] = 0 or 1 + the first bad pivot; with
+        ``seeds`` (draw 0) or ``Z`` (given normals): X_k = mean_k + Z_k L_k^T and logq[k] = sum_b log q_k(x_kb)
+        [gsmvi/advi.py:80-86]"""
+        K, D = mean.shape
+        B = X.shape[1] if X is not None else 1
+        P = D * (D + 1) // 2
+        self._ensure(max(self._max_D, 1), max(self._max_B, 1))
+        _lib.check("gsmvi_advi_init_batched_f64", self.lib.gsmvi_advi_init_batched_f64(
+            self._ctx, self._stream(), K, D, B, self._packed(mean, (K, D), "mean"), self._packed(cov, (K, D, D), "cov"),
+            self._packed(scales, (K, P), "scales"), self._ints(info, K, "info"),
+            C.c_void_p(seeds.data_ptr()) if seeds is not None else None, self._dp(Z, (K, B, D), "Z"),
+            self._dp(X, (K, B, D), "X"), self._dp(logq, (K,), "logq")))
+
+    def advi_step_batched(self, G, loc, scales, moments, t, lr, b1=0.9, b2=0.999, eps=1e-8, seeds=None, call=0, Zcur=None,
+                          Znext=None, Xout=None, logq=None):
+        """One batched ADVI iteration after the score (csrc/gsmvi_advi_batched.hip): the closed-form ELBO gradient and Adam step
+        ``t`` on (loc, scales) and ``moments`` = (m_loc, v_loc, m_s, v_s), all in place [gsmvi/advi.py:31-45,69-73]; ``lr`` a
+        number or a (K,) device tensor; with ``Xout`` the next samples and their ``logq`` from the updated state (z = draw
+        ``call`` of ``seeds``, or ``Znext``; the z behind G is draw ``call`` - 1, or ``Zcur``)."""
+        K, B, D = G.shape
+        P = D * (D + 1) // 2
+        self._ensure(max(self._max_D, 1), max(self._max_B, 1))
+        m_loc, v_loc, m_s, v_s = moments
+        r, rp = self._reg_arg(lr, K)
+        _lib.check("gsmvi_advi_step_batched_f64", self.lib.gsmvi_advi_step_batched_f64(
+            self._ctx, self._stream(), K, D, B, self._packed(G, (K, B, D), "G"), self._packed(loc, (K, D), "loc"),
+            self._packed(scales, (K, P), "scales"), self._packed(m_loc, (K, D), "m_loc"), self._packed(v_loc, (K, D), "v_loc"),
+            self._packed(m_s, (K, P), "m_s"), self._packed(v_s, (K, P), "v_s"), int(t), r, rp, float(b1), float(b2), float(eps),
+            C.c_void_p(seeds.data_ptr()) if seeds is not None else None, int(call), self._dp(Zcur, (K, B, D), "Zcur"),
+            self._dp(Znext, (K, B, D), "Znext"), self._dp(Xout, (K, B, D), "Xout"), self._dp(logq, (K,), "logq")))
+
+    def advi_cov_batched(self, scales, D, out=None):
+        """cov_k = L_k L_k^T (K, D, D), exactly symmetric, from the packed factors (K, D (D + 1) / 2)  [gsmvi/advi.py:25-29]"""
+        K = scales.shape[0]
+        self._ensure(max(self._max_D, 1), max(self._max_B, 1))
+        cov = self.empty(K, D, D) if out is None else out
+        _lib.check("gsmvi_advi_cov_batched_f64", self.lib.gsmvi_advi_cov_batched_f64(
+            self._ctx, self._stream(), K, D, self._packed(scales, (K, D * (D + 1) // 2), "scales"),
+            self._packed(cov, (K, D, D), "cov")))
+        return cov
 
     def bam_update(self, X, G, mu0, S0, reg, jitter=0.0, out=None, flag=None):
         """(mu, S) of BaM [gsmvi/bam.py:72-114]; S symmetrised, jitter on the diagonal."""

@@ -169,6 +169,21 @@ class DeviceKLMonitor(KLMonitor):
         return key
 
 
+def lp_sums(lp, X, eng, K):
+    """(K,) per-problem sums of a batched log-density over the rows of X (K, rows, D): ``lp`` gets the engine's array first and
+    numpy if it refuses it, and returns (K,) sums or (K, rows) values (BatchedKLMonitor, ADVIBatch's losses)"""
+    try:
+        v = lp(X)
+    except (TypeError, AttributeError, RuntimeError, ValueError):
+        v = lp(eng.to_numpy(X))
+    v = eng.asarray(v)
+    if len(v.shape) == 2:
+        v = v.sum(1)
+    if tuple(v.shape) != (K,):
+        raise ValueError(f"lp returned shape {tuple(v.shape)}: expected ({K},) sums or ({K}, rows) values")
+    return v
+
+
 @dataclass
 class BatchedKLMonitor(KLMonitor):
     """KLMonitor (gsmvi/monitors.py:43-125) for the K problems of a batched fit (``GSMBatch.fit``, ``BaMBatch.fit``).
@@ -192,16 +207,7 @@ class BatchedKLMonitor(KLMonitor):
     _CHUNK = 128
 
     def _lp_sums(self, lp, X, eng, K):
-        try:
-            v = lp(X)
-        except (TypeError, AttributeError, RuntimeError, ValueError):
-            v = lp(eng.to_numpy(X))
-        v = eng.asarray(v)
-        if len(v.shape) == 2:
-            v = v.sum(1)
-        if tuple(v.shape) != (K,):
-            raise ValueError(f"lp returned shape {tuple(v.shape)}: expected ({K},) sums or ({K}, rows) values")
-        return v
+        return lp_sums(lp, X, eng, K)
 
     def __call__(self, i, params, lp, keys, nevals=1):
         from .batched import MAX_D

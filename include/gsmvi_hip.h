@@ -18,6 +18,8 @@
  *   jax.vmap(bam_update) over K problems, D <= 64 (bam.py:31-114)      ->  gsmvi_bam_update_batched_f64
  *   bam.py:189-212 fit iteration of K problems (dense), D <= 64         ->  gsmvi_bam_fit_step_batched_f64
  *   monitors.py:83-125 KL monitor of K problems, D <= 64               ->  gsmvi_kl_draw_batched_f64, gsmvi_logq_batched_f64
+ *   advi.py:31-45,69-73 ELBO gradient + optimiser step, K problems      ->  gsmvi_advi_step_batched_f64
+ *   advi.py:80-86 initial (loc, scales), :23-27 scales -> covariance    ->  gsmvi_advi_init_batched_f64, gsmvi_advi_cov_batched_f64
  *   gsmvi/bam.py:72-114       bam_lowrank_update(samples,vs,mu0,S0,reg) ->  gsmvi_bam_update_f64
  *   gsmvi/bam.py:31-69        bam_update(samples,vs,mu0,S0,reg)         ->  gsmvi_bam_update_f64 (same result, K6)
  *
@@ -260,6 +262,7 @@ int gsmvi_get_profile(gsmvi_ctx* ctx, float* ms, int n);
 #define GSMVI_PATH_BATCHED 0x2000u         /* k_gsm_batched / k_gauss_score_batched: the batched entry points      */
 #define GSMVI_PATH_BATCHED_BAM 0x4000u     /* k_bam_batched: the batched BaM entry points                           */
 #define GSMVI_PATH_BATCHED_KL 0x8000u      /* k_kl_batched: the batched KL monitor's entry points                  */
+#define GSMVI_PATH_BATCHED_ADVI 0x10000u   /* k_advi_batched / k_advi_cov_batched: the batched ADVI entry points   */
 #define GSMVI_PATH_GENERIC_MASK (0x0004u | 0x0010u | 0x0040u | 0x0100u | 0x0400u | 0x1000u)
 int gsmvi_last_path(gsmvi_ctx* ctx, unsigned* bits, int reset);
 
@@ -384,6 +387,50 @@ int gsmvi_kl_draw_batched_f64(gsmvi_ctx* ctx, void* stream, int64_t K, int D, in
  */
 int gsmvi_logq_batched_f64(gsmvi_ctx* ctx, void* stream, int64_t K, int D, int64_t nc, const double* mean, const double* cov,
                            const double* Y, double* logq_sum, int* info);
+
+/*
+ * Batched ADVI (K independent full-rank fits of the same (D, B); the ELBO baseline of gsmvi/advi.py), with the bounds, the
+ * layout and the per-problem isolation of the batched GSM above: 1 <= D <= 64, 1 <= B <= 32, K >= 1.  The family is
+ * N(loc_k, L_k L_k^T), L_k lower triangular; `scales` (K x D (D + 1) / 2, packed) holds the entries of L_k in np.tril_indices
+ * order (row-major over the lower triangle: entry (i, j), j <= i, at i (i + 1) / 2 + j; advi.py:23-27,80-83).  loc, m_loc, v_loc
+ * (K x D), scales, m_s, v_s (K x D (D + 1) / 2), G, X, Z (K x B x D), logq_sum, lr_dev (K), packed, in device memory.  Draws:
+ * draw c of key seeds_dev[k] is B x (D + 1) normals for odd D, column D dropped -- the layout of the batched GSM and BaM fits,
+ * so the same keys give the same z to all three.  Shapes, NULL arrays and overlaps are checked before the context is looked at
+ * (then a NULL ctx); every failure returns GSMVI_ERR_BAD_ARG before anything is enqueued.  No context workspace is used.  Sets
+ * GSMVI_PATH_BATCHED_ADVI.
+ *
+ * gsmvi/advi.py:80-86, the start of a fit -> gsmvi_advi_init_batched_f64: scales_k = the lower Cholesky factor of cov_k (the
+ *   factorisation reads the upper triangle of cov_k), info_dev[k] as gsmvi_gsm_fit_init_batched_f64 defines it.  With seeds_dev
+ *   (z = draw 0) or Z (K x B x D given normals; not both): X_k = loc_k + Z_k L_k^T and
+ *   logq_sum[k] = sum_b (-|z_b|^2 / 2) - B sum_i log|L_ii| - B D / 2 log 2 pi; with neither, X and logq_sum must be NULL.
+ */
+int gsmvi_advi_init_batched_f64(gsmvi_ctx* ctx, void* stream, int64_t K, int D, int B, const double* mean, const double* cov,
+                                double* scales, int* info_dev, const uint64_t* seeds_dev, const double* Z, double* X,
+                                double* logq_sum);
+
+/*
+ * gsmvi/advi.py:31-45 (the loss and its gradient) and :69-73 (the optimiser step), one iteration after the score G = lp_g(X),
+ * one launch -> gsmvi_advi_step_batched_f64.  With z the normals behind X (x_b = loc + L z_b), the gradient of the loss
+ * -(sum_b lp(x_b) - sum_b log q(x_b)) is  d / d loc = -sum_b g_b,  d / d L_ij = -sum_b g_bi z_bj (j <= i), and -B / L_ii more on
+ * the diagonal.  Adam, in place on loc, scales and the moments: m <- b1 m + (1 - b1) g, v <- b2 v + (1 - b2) g^2,
+ * p <- p - (lr / (1 - b1^t)) m / (sqrt(v) / sqrt(1 - b2^t) + eps), t = iteration + 1 >= 1 (torch.optim.Adam at its defaults,
+ * optax.adam).  lr_dev: NULL = the scalar lr for every problem, else K per-problem values.  Then, unless Xout is NULL, the next
+ * samples Xout_k = loc_k + Z_k L_k^T and their logq_sum[k] (as in the init) from the UPDATED state; Xout and logq_sum go together.
+ * seeds_dev != NULL: the z behind G is draw call - 1 of key seeds_dev[k] (call >= 1), regenerated in the kernel, and the next z is
+ * draw call; Zcur and Znext must be NULL.  seeds_dev == NULL: Zcur (K x B x D) is the z behind G and, with Xout, Znext the next z.
+ * A non-finite score is not caught: it makes that problem's state NaN from then on, and touches no other problem.
+ * Written: loc, scales, the moments, Xout, logq_sum; none of them may overlap any other array of the call.
+ */
+int gsmvi_advi_step_batched_f64(gsmvi_ctx* ctx, void* stream, int64_t K, int D, int B, const double* G, double* loc,
+                                double* scales, double* m_loc, double* v_loc, double* m_s, double* v_s, int64_t t, double lr,
+                                const double* lr_dev, double b1, double b2, double eps, const uint64_t* seeds_dev, uint64_t call,
+                                const double* Zcur, const double* Znext, double* Xout, double* logq_sum);
+
+/*
+ * gsmvi/advi.py:23-27 scales_to_cov for K problems -> gsmvi_advi_cov_batched_f64: cov_k = L_k L_k^T (K x D x D), exactly
+ * symmetric (entries (i, j) and (j, i) sum the same products in the same order).
+ */
+int gsmvi_advi_cov_batched_f64(gsmvi_ctx* ctx, void* stream, int64_t K, int D, const double* scales, double* cov);
 
 /*
  * Upper Cholesky factor R (R^T R = S, R upper triangular, strictly-lower part zeroed) of a

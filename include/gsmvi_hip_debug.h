@@ -35,6 +35,10 @@ int gsmvi_debug_stream_copy_f64(void* stream, double* dst, const double* src, si
  * odd row strides of the default, pad = 0: the knob "bam_batched_pad" = 0).  Host arithmetic only, no device needed. */
 int gsmvi_debug_bam_batched_lds(int D, int B, int pad, size_t* bytes, int* problems_per_workgroup);
 
+/* The same for a batched ADVI launch at (D, B): mode 0 = gsmvi_advi_init_batched_f64, 1 = gsmvi_advi_step_batched_f64,
+ * 2 = gsmvi_advi_cov_batched_f64 (B plays no part).  Host arithmetic only, no device needed. */
+int gsmvi_debug_advi_batched_lds(int D, int B, int mode, size_t* bytes, int* problems_per_workgroup);
+
 #pragma GCC visibility pop
 #ifdef __cplusplus
 }
