@@ -17,6 +17,10 @@ Mirrors the reference's public surface for the hot path (reference file:line):
     ADVIBatch, Adam (the ELBO baseline for K
     problems at once, D <= 64: closed-form
     gradient + Adam in one launch per iteration) gsmvi/advi.py:8-112
+    BatchedLogisticTarget (K Bayesian logistic
+    regressions, D <= 64: log-density and score
+    of all of them in one launch -- the lp / lp_g
+    of the three batched fits and the monitor)   examples/example_gsm.py:34-35 (log_prob, jit(grad(.)))
     lbfgs_init, ADVI (initialiser and the ELBO
     baseline of the examples; off the hot path)  gsmvi/initializers.py:5-17, gsmvi/advi.py:8-112
 All GSM / BaM numerics run in hand-written HIP kernels (libgsmvi_hip.so, C ABI in include/gsmvi_hip.h)
@@ -29,7 +33,7 @@ from .engine import HipEngine, get_engine                            # noqa: F40
 from .gsm import GSM, gsm_update                                     # noqa: F401
 from .bam import BaM, bam_update, bam_lowrank_update, Regularizers   # noqa: F401
 from .targets import GaussianTarget, device_score, score_from_logp   # noqa: F401
-from .targets import BatchedGaussianTarget                           # noqa: F401
+from .targets import BatchedGaussianTarget, BatchedLogisticTarget    # noqa: F401
 from .batched import GSMBatch, gsm_update_batched                    # noqa: F401
 from .batched import BaMBatch, bam_update_batched, bam_lowrank_update_batched   # noqa: F401
 from .batched import ADVIBatch, Adam                                 # noqa: F401

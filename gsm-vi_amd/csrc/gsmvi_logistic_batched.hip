@@ -1,0 +1,306 @@
+// Batched logistic target: score and log-density of K Bayesian logistic regressions of one (N, D), D <= 64, at nc points each,
+// in one launch ("Batched logistic target").
+//
+// The reference's users hand the fits a model's log_prob and jit(grad(...)) of it (examples/example_gsm.py:34-35), which XLA
+// fuses into a kernel or two.  Here, for problem k with design matrix A_k (N rows a_n of length D), labels y_kn in [0, 1],
+// n_k <= N valid rows and prior precision lam_k >= 0, at the rows x of X_k:
+//   eta_n   = a_n . x
+//   lp(x)   = sum_{n < n_k} [ y_n eta_n - softplus(eta_n) ] - lam_k |x|^2 / 2
+//   g(x)    = sum_{n < n_k} ( y_n - sigma(eta_n) ) a_n - lam_k x
+// with e = exp(-|eta|), sigma = 1 / (1 + e) for eta >= 0 and e / (1 + e) otherwise, softplus = max(eta, 0) + log1p(e).
+//   k_logistic_batched<NT, WANT> : WANT = LB_G (the score alone: no logarithm), LB_LP (the density alone: no second pass over
+//                                  the tile), or both from one pass
+// Work mapping: the slots of gsmvi_batched.h (gb_nt(D) threads per problem, four problems per 256-thread workgroup for
+// D <= 16).  The launch walks the rows of X_k in tiles of TC (32; 16 in the four-problem packing) and, per such tile, the rows
+// of A_k in tiles of LB_TN = 32, so neither nc nor N is bounded by LDS.  A tile of A_k is staged in LDS once (row stride D | 1)
+// and used twice: thread (n, c-group) forms eta for its row n and up to CQ rows of X (A_n j read once per CQ products, the x
+// broadcast), applies the link and leaves r = y - sigma (and the density's term) in LDS (row stride 33); then thread (c, j)
+// owns the outputs g_cj for up to MAXQ rows c and sums r_cn A_nj over the tile's rows in order.  The next tile of A_k (and of
+// y_k) is loaded into registers right after the barrier that publishes the current one and is written to LDS only after the
+// current one is consumed: A is the only large stream and its loads are in flight during both passes.
+// Order: every output row (k, c) sums over n = 0 .. n_k - 1 in that order in one thread, so it does not depend on K, nc, the
+// tiling of nc or the slot packing.  Rows n >= n_k are never loaded.  A row of X with a non-finite entry gets NaN outputs (by
+// a flag, not by arithmetic: sigma saturates and would hide an infinity).  A slot reads and writes only its own problem's
+// slices and every slot runs the same barriers (2 + 3 ceil(N / 32) per tile of X rows), so nothing crosses between problems.
+// All inputs are only read; no context workspace.
+#include "gsmvi_common.h"
+#include "gsmvi_ctx.h"
+#include "gsmvi_batched.h"
+#include "../../include/gsmvi_hip.h"
+#include "../../include/gsmvi_hip_debug.h"   // gsmvi_debug_logistic_batched_lds
+#include <cstdint>
+#include <type_traits>
+
+enum { LB_G = 1, LB_LP = 2 };
+#define LB_TN 32   // rows of A_k per tile
+#define LB_AQ 8    // tile elements per thread: LB_TN D / NT <= 8 in both packings
+
+struct lb_args {
+    long long K, N;
+    int D, nc, tcm;             // dimension, rows of X per problem, rows of X held in LDS = min(nc, TC)
+    const double* A;            // (K, N, D)
+    const double* y;            // (K, N)
+    const int* counts;          // (K) valid rows, clamped to 0 .. N (null: N)
+    double lam;                 // the prior precision of every problem ...
+    const double* lam_dev;      // ... or (K) per-problem values on the device (null: `lam`)
+    const double* X;            // (K, nc, D)
+    double* G;                  // (K, nc, D) or null
+    double* lp;                 // (K, nc) or null
+};
+
+__host__ __device__ inline int lb_tc(int NT) { return NT == 256 ? 32 : 16; }
+// LDS doubles per problem: the A tile (32 x (D | 1)) + its y (32) + the X tile (tcm x (D | 1)) + the row flags (tcm) + r and
+// the density's terms (tcm x 33 each, as wanted).  (64, 32 rows, both): 6336 doubles, 49.5 KB; four problems of (16, 16 rows,
+// both): 4 x 1920 doubles, 60 KB
+__host__ __device__ inline int lb_lds_doubles(int D, int tcm, int want) {
+    return LB_TN * (D | 1) + LB_TN + tcm * ((D | 1) + 1 + (LB_TN | 1) * ((want & LB_G ? 1 : 0) + (want & LB_LP ? 1 : 0)));
+}
+
+// f(integral_constant<int, n>) for the runtime n in 1 .. MAX: the two inner loops below run with a compile-time number of rows of X
+// per thread, so that they are branch-free and their LDS reads are issued in batches (a uniform `if (q < n)` inside them is a
+// scalar branch per product, and every product then waits for its own LDS read)
+template <int Q, int MAX, typename F>
+__device__ __forceinline__ void lb_rows(int n, F&& f) {
+    if constexpr (Q >= MAX) {
+        f(std::integral_constant<int, MAX>{});
+    } else {
+        if (n == Q)
+            f(std::integral_constant<int, Q>{});
+        else
+            lb_rows<Q + 1, MAX>(n, f);
+    }
+}
+
+template <int NT, int WANT>
+__global__ __launch_bounds__(256) void k_logistic_batched(lb_args a) {
+    extern __shared__ double lb_sm[];
+    constexpr int PPW = 256 / NT, TC = NT == 256 ? 32 : 16;
+    constexpr int NG = NT / LB_TN, CQ = TC / NG;        // eta pass: NG groups of 32 threads, CQ rows of X per thread
+    constexpr int MAXQ = TC / 4;                        // score pass: rows of X per thread (NT / D >= 4 rows side by side)
+    constexpr bool HAS_G = (WANT & LB_G) != 0, HAS_LP = (WANT & LB_LP) != 0;
+    const int D = a.D, ld = D | 1, ldr = LB_TN | 1, tcm = a.tcm;
+    const long long N = a.N;
+    const int slot = threadIdx.x / NT, l = threadIdx.x % NT;
+    const long long k = (long long)blockIdx.x * PPW + slot;
+    const bool valid = k < a.K;               // a tail slot runs every barrier and nothing else
+    double* As = lb_sm + (size_t)slot * lb_lds_doubles(D, tcm, WANT);
+    double* Ys = As + LB_TN * ld;             // 32         y of the tile's rows
+    double* Xs = Ys + LB_TN;                  // tcm x ld   the rows of X
+    double* Rb = Xs + tcm * ld;               // tcm        0, or NaN for a row of X with a non-finite entry
+    double* Rs = Rb + tcm;                    // tcm x ldr  r = y - sigma(eta)
+    double* Ts = Rs + (HAS_G ? tcm * ldr : 0);   // tcm x ldr  y eta - softplus(eta)
+    const size_t kk = (size_t)(valid ? k : 0);
+    const double* Ak = a.A + kk * (size_t)N * D;
+    const double* yk = a.y + kk * (size_t)N;
+    const double* Xk = a.X + kk * (size_t)a.nc * D;
+    const double qnan = __longlong_as_double(0x7ff8000000000000LL);
+
+    long long nk = 0;                         // the rows that count
+    double lam = 0.0;
+    if (valid) {
+        nk = N;
+        if (a.counts) {
+            const long long c = a.counts[k];
+            nk = c < 0 ? 0 : (c > N ? N : c);
+        }
+        lam = a.lam_dev ? a.lam_dev[k] : a.lam;
+    }
+    // the tile elements e = l + q NT of this thread as (row, column), stepped without a division
+    const int row0 = l / D, col0 = l - row0 * D, dr = NT / D, dc = NT - dr * D;
+    // the eta pass: row en of the tile, rows eg + q NG of X;  the score pass: column gj, rows gc0 + q CW of X
+    const int en = l % LB_TN, eg = l / LB_TN;
+    const int CW = NT / D, gj = col0, gc0 = row0;
+    const bool gact = l < CW * D;
+
+    for (int c0 = 0; c0 < a.nc; c0 += TC) {
+        const int tc = a.nc - c0 < TC ? a.nc - c0 : TC;
+        if (valid)
+            for (int e = l; e < tc * D; e += NT) {
+                const int r = e / D, j = e - r * D;
+                Xs[r * ld + j] = Xk[(size_t)(c0 + r) * D + j];
+            }
+        // the first tile of A_k and y_k into registers
+        double pre[LB_AQ], ypre = 0.0;
+        {
+            const int tnv = (int)(nk < LB_TN ? nk : LB_TN), te = tnv * D;
+#pragma unroll
+            for (int q = 0; q < LB_AQ; ++q) {
+                const int e = l + q * NT;
+                pre[q] = e < te ? Ak[e] : 0.0;
+            }
+            if (l < tnv) ypre = yk[l];
+        }
+        __syncthreads();
+        double xx = 0.0;                      // |x|^2 of row l (threads l < tc)
+        if (valid && l < tc) {
+            double z = 0.0;
+            for (int j = 0; j < D; ++j) {
+                const double x = Xs[l * ld + j];
+                z += x * 0.0;
+                xx += x * x;
+            }
+            Rb[l] = z;
+        }
+
+        double acc[MAXQ], lpacc = 0.0;
+#pragma unroll
+        for (int q = 0; q < MAXQ; ++q) acc[q] = 0.0;
+        const int nq = (tc + CW - 1) / CW;    // rows of X per thread in the score pass and in the eta pass (uniform in the slot)
+        const int nqe = (tc + NG - 1) / NG;
+
+        for (long long n0 = 0; n0 < N; n0 += LB_TN) {
+            const long long left = nk - n0;
+            const int tnv = left < 0 ? 0 : (int)(left < LB_TN ? left : LB_TN), te = tnv * D;
+            {                                 // registers -> LDS (the previous tile was consumed before the last barrier)
+                int r = row0, c = col0;
+#pragma unroll
+                for (int q = 0; q < LB_AQ; ++q) {
+                    if (l + q * NT < te) As[r * ld + c] = pre[q];
+                    r += dr;
+                    c += dc;
+                    if (c >= D) {
+                        c -= D;
+                        ++r;
+                    }
+                }
+                if (l < tnv) Ys[l] = ypre;
+            }
+            __syncthreads();
+            {                                 // the next tile's loads: in flight while this one is consumed
+                const long long left2 = left - LB_TN;
+                const int tnv2 = left2 < 0 ? 0 : (int)(left2 < LB_TN ? left2 : LB_TN), te2 = tnv2 * D;
+                const double* An = Ak + (size_t)(n0 + LB_TN) * D;
+#pragma unroll
+                for (int q = 0; q < LB_AQ; ++q) {
+                    const int e = l + q * NT;
+                    if (e < te2) pre[q] = An[e];
+                }
+                if (l < tnv2) ypre = yk[n0 + LB_TN + l];
+            }
+            if (en < tnv && eg < tc) {        // eta, the link
+                double eta[CQ];
+                int xo[CQ];
+#pragma unroll
+                for (int q = 0; q < CQ; ++q) {
+                    eta[q] = 0.0;
+                    const int c = eg + q * NG;
+                    xo[q] = (c < tc ? c : tc - 1) * ld;
+                }
+                const double* ar = As + en * ld;
+                lb_rows<1, CQ>(nqe, [&](auto nr) {
+#pragma unroll 8
+                    for (int j = 0; j < D; ++j) {
+                        const double av = ar[j];
+#pragma unroll
+                        for (int q = 0; q < decltype(nr)::value; ++q) eta[q] = fma(av, Xs[xo[q] + j], eta[q]);
+                    }
+                });
+                // eta goes through this thread's own LDS cells, so that the link below is ONE copy of exp / log1p in a rolled
+                // loop (unrolled over q it takes 170 - 230 VGPRs)
+                double* Es = HAS_G ? Rs : Ts;
+#pragma unroll
+                for (int q = 0; q < CQ; ++q)
+                    if (eg + q * NG < tc) Es[(eg + q * NG) * ldr + en] = eta[q];
+                const double yv = Ys[en];
+#pragma unroll 1
+                for (int c = eg; c < tc; c += NG) {
+                    const double h = Es[c * ldr + en], e = exp(-fabs(h)), d = 1.0 + e;
+                    if (HAS_G) Rs[c * ldr + en] = yv - (h >= 0.0 ? 1.0 / d : e / d);
+                    if (HAS_LP) Ts[c * ldr + en] = yv * h - ((h > 0.0 ? h : 0.0) + log1p(e));
+                }
+            }
+            __syncthreads();
+            if (HAS_G && gact && gc0 < tc) {  // g_cj += sum over the tile's rows, in order
+                int ro[MAXQ];
+#pragma unroll
+                for (int q = 0; q < MAXQ; ++q) {
+                    const int c = gc0 + q * CW;
+                    ro[q] = (c < tc ? c : tc - 1) * ldr;
+                }
+                lb_rows<1, MAXQ>(nq, [&](auto nr) {
+#pragma unroll 8
+                    for (int n = 0; n < tnv; ++n) {
+                        const double av = As[n * ld + gj];
+#pragma unroll
+                        for (int q = 0; q < decltype(nr)::value; ++q) acc[q] = fma(Rs[ro[q] + n], av, acc[q]);
+                    }
+                });
+            }
+            if (HAS_LP && l < tc && valid)
+                for (int n = 0; n < tnv; ++n) lpacc += Ts[l * ldr + n];
+            __syncthreads();                  // the next tile overwrites As, Ys, Rs, Ts
+        }
+
+        if (valid) {
+            if (HAS_G && gact) {
+#pragma unroll
+                for (int q = 0; q < MAXQ; ++q) {
+                    const int c = gc0 + q * CW;
+                    if (c < tc) {
+                        const double v = acc[q] - lam * Xs[c * ld + gj];
+                        a.G[(kk * (size_t)a.nc + (size_t)(c0 + c)) * D + gj] = Rb[c] == 0.0 ? v : qnan;
+                    }
+                }
+            }
+            if (HAS_LP && l < tc) a.lp[kk * (size_t)a.nc + (size_t)(c0 + l)] = Rb[l] == 0.0 ? lpacc - 0.5 * lam * xx : qnan;
+        }
+        __syncthreads();                      // the next tile of X rows overwrites Xs and Rb
+    }
+}
+
+// dynamic LDS bytes of a launch at (D, nc, want): at most 60 KB, below the default limit, so no kernel attribute is needed
+static size_t lb_launch_lds(int D, int nc, int want, int* ppw, int* tcm) {
+    const int nt = gb_nt(D), tc = lb_tc(nt);
+    *ppw = 256 / nt;
+    *tcm = nc < tc ? nc : tc;
+    return (size_t)*ppw * lb_lds_doubles(D, *tcm, want) * sizeof(double);
+}
+
+extern "C" {
+
+int gsmvi_logistic_batched_f64(gsmvi_ctx* ctx, void* stream, int64_t K, int D, int nc, int64_t N, const double* A, const double* y,
+                               const int* counts_dev, double prior_prec, const double* prior_prec_dev, const double* X, double* G,
+                               double* lp) {
+    if (int st = gb_check_shape(__func__, K, D, gb_ppw)) return st;
+    GB_BAD(nc < 1, "nc must be at least 1");
+    GB_BAD(N < 1, "N must be at least 1");
+    GB_BAD(N > (INT64_MAX / 8 / D) / K, "K N D is too large");
+    GB_BAD(nc > (INT64_MAX / 8 / D) / K, "K nc D is too large");
+    GB_BAD(!A || !y || !X, "NULL array");
+    GB_BAD(!G && !lp, "give G or lp (or both)");
+    GB_BAD(!prior_prec_dev && !(prior_prec >= 0.0 && prior_prec < __builtin_huge_val()), "prior_prec must be finite and >= 0");
+    const size_t na = (size_t)K * N * D * 8, ny = (size_t)K * N * 8, nx = (size_t)K * nc * D * 8, nl = (size_t)K * nc * 8,
+                 nk = (size_t)K * 8, ni = (size_t)K * 4;
+    if (int st = gb_check_overlaps(__func__, {{A, na, "A", GB_RD}, {y, ny, "y", GB_RD}, {counts_dev, ni, "counts_dev", GB_RD},
+                                              {prior_prec_dev, nk, "prior_prec_dev", GB_RD}, {X, nx, "X", GB_RD},
+                                              {G, nx, "G", GB_WR}, {lp, nl, "lp", GB_WR}}))
+        return st;
+    GB_BAD(!ctx, "ctx is NULL");
+    const int want = (G ? LB_G : 0) | (lp ? LB_LP : 0);
+    lb_args a = {};
+    a.K = K; a.N = N; a.D = D; a.nc = nc; a.A = A; a.y = y; a.counts = counts_dev; a.lam = prior_prec; a.lam_dev = prior_prec_dev;
+    a.X = X; a.G = G; a.lp = lp;
+    int ppw;
+    const size_t lds = lb_launch_lds(D, nc, want, &ppw, &a.tcm);
+    const unsigned grid = (unsigned)((K + ppw - 1) / ppw);
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+#define LB_GO(NTV, W) hipLaunchKernelGGL((k_logistic_batched<NTV, W>), dim3(grid), dim3(256), lds, st, a)
+    if (ppw == 4) {
+        if (want == LB_G) LB_GO(64, LB_G); else if (want == LB_LP) LB_GO(64, LB_LP); else LB_GO(64, LB_G | LB_LP);
+    } else {
+        if (want == LB_G) LB_GO(256, LB_G); else if (want == LB_LP) LB_GO(256, LB_LP); else LB_GO(256, LB_G | LB_LP);
+    }
+#undef LB_GO
+    return gb_launched(ctx, GSMVI_PATH_BATCHED_TARGET, "k_logistic_batched");
+}
+
+// include/gsmvi_hip_debug.h: what a launch at (D, nc) requests (exported by the debug library only); want: 1 = G, 2 = lp, 3 = both
+int gsmvi_debug_logistic_batched_lds(int D, int nc, int want, size_t* bytes, int* problems_per_workgroup) {
+    GB_BAD(D < 1 || D > GB_MAX_D || nc < 1 || want < 1 || want > 3 || !bytes || !problems_per_workgroup,
+           "bad shape, want or NULL output");
+    int tcm;
+    *bytes = lb_launch_lds(D, nc, want, problems_per_workgroup, &tcm);
+    return GSMVI_OK;
+}
+
+}  // extern "C"

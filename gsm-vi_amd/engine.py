@@ -584,7 +584,7 @@ class HipEngine:
     PATH_BITS = {"panel_fast": 0x1, "panel_wide": 0x2, "panel_generic": 0x4, "panel_t_fast": 0x8, "panel_t_generic": 0x10,
                  "scalars_fast": 0x20, "scalars_generic": 0x40, "cov_sym": 0x80, "cov_generic": 0x100, "fupd_fast": 0x200,
                  "fupd_generic": 0x400, "lowrank_fast": 0x800, "lowrank_generic": 0x1000, "batched": 0x2000,
-                 "batched_bam": 0x4000, "batched_kl": 0x8000, "batched_advi": 0x10000}
+                 "batched_bam": 0x4000, "batched_kl": 0x8000, "batched_advi": 0x10000, "batched_target": 0x20000}
     PATH_GENERIC_MASK = 0x4 | 0x10 | 0x40 | 0x100 | 0x400 | 0x1000
 
     def last_path(self, reset=True):
@@ -688,6 +688,10 @@ class HipEngine:
 
     def read_ints(self, t):
         return t.cpu().numpy().astype(np.int64)          # synchronises
+
+    def batched_counts(self, values):
+        """K per-problem counts as a device int32 tensor"""
+        return torch.as_tensor(np.asarray(values, dtype=np.int32).reshape(-1), device=self.device)
 
     def batched_seeds(self, seeds):
         """the problems' draw keys as a device uint64 array (stored as int64: the same bits)"""
@@ -863,6 +867,30 @@ class HipEngine:
             self._ctx, self._stream(), K, D, self._packed(scales, (K, D * (D + 1) // 2), "scales"),
             self._packed(cov, (K, D, D), "cov")))
         return cov
+
+    # ---- batched logistic target: K regressions of one (N, D) (csrc/gsmvi_logistic_batched.hip) ---------------------------
+    def logistic_batched(self, X, A, y, counts=None, prior_prec=1.0, out=None, lp_out=None, want="g"):
+        """Score and / or log-density of K Bayesian logistic regressions at the rows of X (K, nc, D), one launch
+        [examples/example_gsm.py:34-35 for this model]: A (K, N, D), y (K, N), ``counts`` None or K device int32 valid rows,
+        ``prior_prec`` a number or a (K,) device tensor.  ``want`` = "g" -> G (K, nc, D) (no logarithm is evaluated), "lp" -> the
+        values (K, nc), "both" -> (G, lp)."""
+        if want not in ("g", "lp", "both"):
+            raise ValueError(f"want = {want!r}: expected 'g', 'lp' or 'both'")
+        X = X.contiguous()
+        K, nc, D = X.shape
+        N = A.shape[1]
+        self._ensure(max(self._max_D, 1), max(self._max_B, 1))
+        G = lp = None
+        if want != "lp":
+            G = self.empty(K, nc, D) if out is None else out
+        if want != "g":
+            lp = self.empty(K, nc) if lp_out is None else lp_out
+        r, rp = self._reg_arg(prior_prec, K)
+        _lib.check("gsmvi_logistic_batched_f64", self.lib.gsmvi_logistic_batched_f64(
+            self._ctx, self._stream(), K, D, nc, N, self._packed(A, (K, N, D), "A"), self._packed(y, (K, N), "y"),
+            self._ints(counts, K, "counts"), r, rp, self._packed(X, (K, nc, D), "X"), self._dp(G, (K, nc, D), "out"),
+            self._dp(lp, (K, nc), "lp_out")))
+        return G if want == "g" else lp if want == "lp" else (G, lp)
 
     def bam_update(self, X, G, mu0, S0, reg, jitter=0.0, out=None, flag=None):
         """(mu, S) of BaM [gsmvi/bam.py:72-114]; S symmetrised, jitter on the diagonal."""

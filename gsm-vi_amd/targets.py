@@ -5,6 +5,8 @@
 kernel.  ``device_score`` marks a user callable as taking/returning CUDA tensors;
 ``score_from_logp`` is the sum-then-autograd helper matching the JAX examples
 (examples/example_gsm.py:34-35: ``lp_g = jit(grad(lambda x: sum(lp(x))))``).
+``BatchedLogisticTarget`` is the first non-Gaussian device target of the batched fits: K Bayesian logistic
+regressions, score and log-density from one HIP launch.
 """
 import numpy as np
 import torch
@@ -115,3 +117,78 @@ class BatchedGaussianTarget:
         x = self.engine.asarray(x)
         r = self.mean[:, None, :] - x
         return -0.5 * torch.einsum("kbi,kij,kbj->k", r, self.P, r)
+
+
+def _host_array(x):
+    """numpy view or copy of a host array or of a tensor on any device (validation only)"""
+    return x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x)
+
+
+class BatchedLogisticTarget:
+    """K Bayesian logistic regressions with their own data sets, for ``GSMBatch``, ``BaMBatch``, ``ADVIBatch`` and
+    ``BatchedKLMonitor``.  Problem k has the design matrix A[k] (N, D), labels y[k] (N,) in [0, 1] (soft labels allowed),
+    ``counts[k]`` <= N valid rows (None: all N; the rows beyond are ignored whatever they hold) and the prior N(0, I / lam_k),
+    ``prior_precision`` = lam a float or K values, 0 = flat.  With eta = A[k] x:
+
+        lp_k(x)      = sum_n [ y_n eta_n - softplus(eta_n) ] - lam_k |x|^2 / 2          (unnormalised log posterior)
+        grad lp_k(x) = sum_n ( y_n - sigmoid(eta_n) ) a_n - lam_k x
+
+    in the overflow-safe forms (e = exp(-|eta|); sigmoid = 1 / (1 + e) for eta >= 0, e / (1 + e) otherwise; softplus =
+    max(eta, 0) + log1p(e)), evaluated by gsmvi_logistic_batched_f64: what examples/example_gsm.py:34-35 gets from a model's
+    log_prob and jit(grad(...)).  numpy arrays or tensors in; everything is kept on the device as float64 / int32.  Arguments
+    are validated on the host before any device work (ValueError naming the argument).
+
+    ``lp_g(x, out=None)``: (K, B, D) -> (K, B, D) scores, ``device_native`` and ``graph_safe`` (one capturable launch, no
+    allocation with ``out``).  ``lp(x)``: (K, rows, D) -> (K, rows) values (what ADVIBatch's losses and BatchedKLMonitor sum per
+    problem); a device tensor or numpy.  ``lp_and_score(x)``: (scores, values) from one launch."""
+
+    def __init__(self, A, y, prior_precision=1.0, counts=None, engine=None):
+        sa, sy = tuple(int(n) for n in A.shape), tuple(int(n) for n in y.shape)
+        if len(sa) != 3 or min(sa) < 1:
+            raise ValueError(f"A: expected shape (K, N, D) with K, N, D >= 1, got {sa}")
+        K, N, D = sa
+        if not 1 <= D <= 64:
+            raise ValueError(f"A: D = {D} is outside 1 <= D <= 64")
+        if sy != (K, N):
+            raise ValueError(f"y: expected shape (K, N) = {(K, N)}, got {sy}")
+        cnt = None
+        if counts is not None:
+            cnt = np.asarray(_host_array(counts))
+            if cnt.shape != (K,) or not np.issubdtype(cnt.dtype, np.integer):
+                raise ValueError(f"counts: expected {K} integers, got shape {cnt.shape}, dtype {cnt.dtype}")
+            if (cnt < 0).any() or (cnt > N).any():
+                raise ValueError(f"counts: values outside 0 .. N = {N} for problems {np.flatnonzero((cnt < 0) | (cnt > N)).tolist()}")
+        yh = np.asarray(_host_array(y), dtype=np.float64)
+        live = np.arange(N)[None, :] < (cnt[:, None] if cnt is not None else N)
+        bad = live & ~((yh >= 0.0) & (yh <= 1.0))                     # (a NaN fails both comparisons)
+        if bad.any():
+            raise ValueError(f"y: values outside [0, 1] or non-finite in the valid rows of problems "
+                             f"{np.flatnonzero(bad.any(1)).tolist()}")
+        lam = np.asarray(_host_array(prior_precision), dtype=np.float64)
+        if lam.shape not in ((), (K,)):
+            raise ValueError(f"prior_precision: expected a number or {K} values, got shape {lam.shape}")
+        if not (np.isfinite(lam) & (lam >= 0.0)).all():
+            raise ValueError("prior_precision: expected finite values >= 0")
+        self.engine = engine if engine is not None else get_engine()
+        eng = self.engine
+        self.K, self.N, self.D = K, N, D
+        self.A = eng.asarray(A.contiguous() if isinstance(A, torch.Tensor) else A)
+        self.y = eng.asarray(yh)
+        self.counts = eng.batched_counts(cnt) if cnt is not None else None
+        self.prior_precision = float(lam) if lam.shape == () else eng.batched_regs(lam)
+
+        def lp_g(x, out=None):
+            return eng.logistic_batched(x, self.A, self.y, self.counts, self.prior_precision, out=out, want="g")
+        lp_g.device_native = True
+        lp_g.graph_safe = True          # one capturable kernel launch, no allocation when `out` is given, no host work
+        self.lp_g = lp_g
+
+    def lp(self, x):
+        """(K, rows) values lp_k(x_kr) at the rows of x (K, rows, D), a device tensor or numpy; one launch"""
+        eng = self.engine
+        return eng.logistic_batched(eng.asarray(x), self.A, self.y, self.counts, self.prior_precision, want="lp")
+
+    def lp_and_score(self, x):
+        """(scores (K, rows, D), values (K, rows)) from one launch"""
+        eng = self.engine
+        return eng.logistic_batched(eng.asarray(x), self.A, self.y, self.counts, self.prior_precision, want="both")

@@ -20,6 +20,7 @@
  *   monitors.py:83-125 KL monitor of K problems, D <= 64               ->  gsmvi_kl_draw_batched_f64, gsmvi_logq_batched_f64
  *   advi.py:31-45,69-73 ELBO gradient + optimiser step, K problems      ->  gsmvi_advi_step_batched_f64
  *   advi.py:80-86 initial (loc, scales), :23-27 scales -> covariance    ->  gsmvi_advi_init_batched_f64, gsmvi_advi_cov_batched_f64
+ *   examples/example_gsm.py:34-35 a model's log_prob and jit(grad(.)) of it, K logistic regressions -> gsmvi_logistic_batched_f64
  *   gsmvi/bam.py:72-114       bam_lowrank_update(samples,vs,mu0,S0,reg) ->  gsmvi_bam_update_f64
  *   gsmvi/bam.py:31-69        bam_update(samples,vs,mu0,S0,reg)         ->  gsmvi_bam_update_f64 (same result, K6)
  *
@@ -263,6 +264,7 @@ int gsmvi_get_profile(gsmvi_ctx* ctx, float* ms, int n);
 #define GSMVI_PATH_BATCHED_BAM 0x4000u     /* k_bam_batched: the batched BaM entry points                           */
 #define GSMVI_PATH_BATCHED_KL 0x8000u      /* k_kl_batched: the batched KL monitor's entry points                  */
 #define GSMVI_PATH_BATCHED_ADVI 0x10000u   /* k_advi_batched / k_advi_cov_batched: the batched ADVI entry points   */
+#define GSMVI_PATH_BATCHED_TARGET 0x20000u /* k_logistic_batched: the batched non-Gaussian target's entry point     */
 #define GSMVI_PATH_GENERIC_MASK (0x0004u | 0x0010u | 0x0040u | 0x0100u | 0x0400u | 0x1000u)
 int gsmvi_last_path(gsmvi_ctx* ctx, unsigned* bits, int reset);
 
@@ -431,6 +433,30 @@ int gsmvi_advi_step_batched_f64(gsmvi_ctx* ctx, void* stream, int64_t K, int D, 
  * symmetric (entries (i, j) and (j, i) sum the same products in the same order).
  */
 int gsmvi_advi_cov_batched_f64(gsmvi_ctx* ctx, void* stream, int64_t K, int D, const double* scales, double* cov);
+
+/*
+ * Batched logistic target: the log-density and the score of K Bayesian logistic regressions of one (N, D) at nc points each,
+ * one launch.  examples/example_gsm.py:34-35, the model's log_prob and lp_g = jit(grad(...)) of it (which XLA fuses into a
+ * kernel or two), for this model -> gsmvi_logistic_batched_f64.  Problem k has the design matrix A_k (N rows a_n of length D),
+ * labels y_kn in [0, 1] (soft labels allowed), n_k valid rows and prior precision lam_k >= 0 (prior N(0, I / lam_k); 0 = flat).
+ * At the rows x of X_k, with eta_n = a_n . x:
+ *   lp[k, c] = sum_{n < n_k} [ y_n eta_n - softplus(eta_n) ] - lam_k |x|^2 / 2         (unnormalised log posterior)
+ *   G[k, c]  = sum_{n < n_k} ( y_n - sigma(eta_n) ) a_n - lam_k x
+ * in the overflow-safe forms e = exp(-|eta|), sigma = 1 / (1 + e) for eta >= 0 and e / (1 + e) otherwise, softplus =
+ * max(eta, 0) + log1p(e).  A (K x N x D), y (K x N), X, G (K x nc x D), lp (K x nc), packed, in device memory; 1 <= D <= 64 and K
+ * with the grid limits of the batched GSM above; nc >= 1 and N >= 1 are not bounded by LDS (both are walked in tiles).
+ * counts_dev: NULL = N valid rows everywhere, else K ints on the device, each clamped to 0 .. N in the kernel (the host does not
+ * read them); rows n >= n_k are never loaded, whatever they hold.  prior_prec_dev: NULL = the scalar prior_prec for every
+ * problem, else K values.  At least one of G, lp is given; G alone evaluates no logarithm.  Every output row sums over n in the
+ * order 0 .. n_k - 1 and depends on A_k, y_k, n_k, lam_k and its own row of X only: the same bits for any K, nc and neighbours.
+ * A row of X with a non-finite entry gets NaN outputs and no other row is touched; a non-finite entry in a valid row of A_k or
+ * y_k stays in problem k.  Shapes, NULL arrays and overlaps (G and lp are the written arrays) are checked before the context is
+ * looked at (then a NULL ctx); every failure returns GSMVI_ERR_BAD_ARG before anything is enqueued.  Inputs are only read; no
+ * context workspace is used.  Sets GSMVI_PATH_BATCHED_TARGET.
+ */
+int gsmvi_logistic_batched_f64(gsmvi_ctx* ctx, void* stream, int64_t K, int D, int nc, int64_t N, const double* A, const double* y,
+                               const int* counts_dev, double prior_prec, const double* prior_prec_dev, const double* X, double* G,
+                               double* lp);
 
 /*
  * Upper Cholesky factor R (R^T R = S, R upper triangular, strictly-lower part zeroed) of a

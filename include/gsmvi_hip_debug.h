@@ -39,6 +39,10 @@ int gsmvi_debug_bam_batched_lds(int D, int B, int pad, size_t* bytes, int* probl
  * 2 = gsmvi_advi_cov_batched_f64 (B plays no part).  Host arithmetic only, no device needed. */
 int gsmvi_debug_advi_batched_lds(int D, int B, int mode, size_t* bytes, int* problems_per_workgroup);
 
+/* The same for a gsmvi_logistic_batched_f64 launch at (D, nc): want 1 = G alone, 2 = lp alone, 3 = both.  Host arithmetic only,
+ * no device needed. */
+int gsmvi_debug_logistic_batched_lds(int D, int nc, int want, size_t* bytes, int* problems_per_workgroup);
+
 #pragma GCC visibility pop
 #ifdef __cplusplus
 }
