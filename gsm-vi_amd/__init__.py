@@ -21,6 +21,9 @@ Mirrors the reference's public surface for the hot path (reference file:line):
     regressions, D <= 64: log-density and score
     of all of them in one launch -- the lp / lp_g
     of the three batched fits and the monitor)   examples/example_gsm.py:34-35 (log_prob, jit(grad(.)))
+    lbfgs_init_batched (the L-BFGS initialiser
+    for K problems at once, D <= 64: one launch
+    per function evaluation after lp_g and lp)   gsmvi/initializers.py:5-17
     lbfgs_init, ADVI (initialiser and the ELBO
     baseline of the examples; off the hot path)  gsmvi/initializers.py:5-17, gsmvi/advi.py:8-112
 All GSM / BaM numerics run in hand-written HIP kernels (libgsmvi_hip.so, C ABI in include/gsmvi_hip.h)
@@ -38,7 +41,7 @@ from .batched import GSMBatch, gsm_update_batched                    # noqa: F40
 from .batched import BaMBatch, bam_update_batched, bam_lowrank_update_batched   # noqa: F401
 from .batched import ADVIBatch, Adam                                 # noqa: F401
 from .monitors import KLMonitor, DeviceKLMonitor, BatchedKLMonitor   # noqa: F401
-from .initializers import lbfgs_init                                 # noqa: F401
+from .initializers import lbfgs_init, lbfgs_init_batched, LbfgsBatchedResult   # noqa: F401
 from .advi import ADVI                                               # noqa: F401
 
 __version__ = "0.1.0"

@@ -584,7 +584,8 @@ class HipEngine:
     PATH_BITS = {"panel_fast": 0x1, "panel_wide": 0x2, "panel_generic": 0x4, "panel_t_fast": 0x8, "panel_t_generic": 0x10,
                  "scalars_fast": 0x20, "scalars_generic": 0x40, "cov_sym": 0x80, "cov_generic": 0x100, "fupd_fast": 0x200,
                  "fupd_generic": 0x400, "lowrank_fast": 0x800, "lowrank_generic": 0x1000, "batched": 0x2000,
-                 "batched_bam": 0x4000, "batched_kl": 0x8000, "batched_advi": 0x10000, "batched_target": 0x20000}
+                 "batched_bam": 0x4000, "batched_kl": 0x8000, "batched_advi": 0x10000, "batched_target": 0x20000,
+                 "batched_lbfgs": 0x40000}
     PATH_GENERIC_MASK = 0x4 | 0x10 | 0x40 | 0x100 | 0x400 | 0x1000
 
     def last_path(self, reset=True):
@@ -891,6 +892,50 @@ class HipEngine:
             self._ints(counts, K, "counts"), r, rp, self._packed(X, (K, nc, D), "X"), self._dp(G, (K, nc, D), "out"),
             self._dp(lp, (K, nc), "lp_out")))
         return G if want == "g" else lp if want == "lp" else (G, lp)
+
+    # ---- batched L-BFGS initialiser: K minimisations of one D (csrc/gsmvi_lbfgs_batched.hip) --------------------------------
+    def lbfgs_state_batched(self, x0):
+        """The state of K L-BFGS runs started at the rows of x0 (K, D), as include/gsmvi_hip.h lays it out: a dict of device
+        arrays x, g, d, Xt (K, D), S, Y (K, 10, D), sc (K, 24), ist (K, 8) int32 and the one-element counter ``stopped``"""
+        K, D = x0.shape
+        x = self.asarray(x0).clone(memory_format=torch.contiguous_format)
+        return {"x": x, "g": self.zeros(K, D), "d": self.zeros(K, D), "Xt": x.clone(), "S": self.zeros(K, 10, D),
+                "Y": self.zeros(K, 10, D), "sc": self.zeros(K, 24), "ist": torch.zeros(K, 8, dtype=torch.int32, device=self.device),
+                "stopped": self.new_flag()}
+
+    def lbfgs_step_batched(self, fv, gv, state, start=False, sign=-1.0, maxiter=1000, maxfun=1000, gtol=1e-5,
+                           ftol=2.220446049250313e-09):
+        """One launch of the batched L-BFGS initialiser (csrc/gsmvi_lbfgs_batched.hip) after the evaluation at ``state["Xt"]``:
+        phi = sign fv (K,), its gradient sign gv (K, D) (sign = -1: lp and its score).  ``start``: the first evaluation;
+        otherwise accept or reject the trial point of every running problem, update its state in place and write its next
+        trial point; ``state["stopped"]`` (optional) grows by the problems that stopped  [gsmvi/initializers.py:5-17]"""
+        K, D = state["x"].shape
+        self._ensure(max(self._max_D, 1), max(self._max_B, 1))
+        ist = state["ist"]
+        assert isinstance(ist, torch.Tensor) and ist.is_cuda and ist.dtype == torch.int32 and ist.is_contiguous() \
+            and tuple(ist.shape) == (K, 8), f"ist: expected a contiguous int32 CUDA tensor of shape {(K, 8)}"
+        stopped = state.get("stopped")
+        _lib.check("gsmvi_lbfgs_step_batched_f64", self.lib.gsmvi_lbfgs_step_batched_f64(
+            self._ctx, self._stream(), K, D, int(bool(start)), self._packed(fv, (K,), "fv"), self._packed(gv, (K, D), "gv"),
+            float(sign), self._packed(state["x"], (K, D), "x"), self._packed(state["g"], (K, D), "g"),
+            self._packed(state["d"], (K, D), "d"), self._packed(state["S"], (K, 10, D), "S"),
+            self._packed(state["Y"], (K, 10, D), "Y"), self._packed(state["sc"], (K, 24), "sc"), C.c_void_p(ist.data_ptr()),
+            self._packed(state["Xt"], (K, D), "Xt"), self._ints(stopped, 1, "stopped"), int(maxiter), int(maxfun), float(gtol),
+            float(ftol)))
+
+    def lbfgs_hess_inv_batched(self, state, out=None):
+        """cov_k (K, D, D) = the dense BFGS inverse-Hessian product of the pairs held in ``state`` (S, Y, ist) on an identity
+        base, exactly symmetric  [scipy.optimize.LbfgsInvHessProduct.todense, gsmvi/initializers.py:15]"""
+        K, _, D = state["S"].shape
+        self._ensure(max(self._max_D, 1), max(self._max_B, 1))
+        ist = state["ist"]
+        assert isinstance(ist, torch.Tensor) and ist.is_cuda and ist.dtype == torch.int32 and ist.is_contiguous() \
+            and tuple(ist.shape) == (K, 8), f"ist: expected a contiguous int32 CUDA tensor of shape {(K, 8)}"
+        cov = self.empty(K, D, D) if out is None else out
+        _lib.check("gsmvi_lbfgs_hess_inv_batched_f64", self.lib.gsmvi_lbfgs_hess_inv_batched_f64(
+            self._ctx, self._stream(), K, D, self._packed(state["S"], (K, 10, D), "S"), self._packed(state["Y"], (K, 10, D), "Y"),
+            C.c_void_p(ist.data_ptr()), self._packed(cov, (K, D, D), "cov")))
+        return cov
 
     def bam_update(self, X, G, mu0, S0, reg, jitter=0.0, out=None, flag=None):
         """(mu, S) of BaM [gsmvi/bam.py:72-114]; S symmetrised, jitter on the diagonal."""

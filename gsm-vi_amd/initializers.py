@@ -5,7 +5,13 @@ optimum together with the optimiser's dense inverse-Hessian estimate as the star
 ``GSM.fit`` / ``BaM.fit``, plus the scipy result object.  Additions: ``lp`` / ``lp_g`` may be the
 device-native callables of this package (they are fed a (1, D) CUDA tensor then), and ``lp`` may return a
 one-element array instead of a scalar.
+
+``lbfgs_init_batched`` is the same initialiser for the K problems of a batched fit (``GSMBatch``, ``BaMBatch``, ``ADVIBatch``):
+plain L-BFGS with a backtracking line search in HIP (csrc/gsmvi_lbfgs_batched.hip), one launch per function evaluation after
+the score and ``lp``, whatever K is.
 """
+from dataclasses import dataclass
+
 import numpy as np
 from scipy.optimize import minimize
 
@@ -43,3 +49,90 @@ def lbfgs_init(x0, lp, lp_g=None, maxiter=1000, maxfun=1000):
         jac = lambda x: -score(x)
     res = minimize(neg, x0, method="L-BFGS-B", jac=jac, options={"maxiter": maxiter, "maxfun": maxfun})
     return res.x, res.hess_inv.todense(), res
+
+
+@dataclass
+class LbfgsBatchedResult:
+    """What ``lbfgs_init_batched`` found, per problem (arrays of length K, or (K, D)): the minimiser ``x`` of -lp, ``fun`` = -lp
+    and ``jac`` = -score at it, iterations ``nit`` and evaluations ``nfev`` the problem used before it stopped, ``status``
+    (1 converged, 2 ``maxiter`` or ``maxfun`` reached, 3 line search failed, 4 non-finite start; 0 still running: only when the
+    loop was cut short) and ``success`` = ``status == 1``.  ``nlaunch`` is shared: the evaluation rounds that ran.  Every
+    problem is scored in every round, so it is the ``offset_evals`` of a ``BatchedKLMonitor`` that follows the fits."""
+    x: np.ndarray
+    fun: np.ndarray
+    jac: np.ndarray
+    nit: np.ndarray
+    nfev: np.ndarray
+    status: np.ndarray
+    success: np.ndarray
+    nlaunch: int
+
+
+def lbfgs_init_batched(x0, lp, lp_g, maxiter=1000, maxfun=1000, *, gtol=1e-5, ftol=2.220446049250313e-09, check_every=8,
+                       as_torch=False, engine=None):
+    """``lbfgs_init`` (gsmvi/initializers.py:5-17) for K problems of one D at once: returns ``(mean (K, D), cov (K, D, D), res)``,
+    the L-BFGS maximisers of ``lp_k``, the dense BFGS inverse-Hessian products of the stored pairs on an identity base (what
+    ``res.hess_inv.todense()`` is in scipy: ``LbfgsInvHessProduct(S, Y).todense()``) and a ``LbfgsBatchedResult``.
+
+    ``x0``: (K, D), or (D,): the same start for every problem (K is then the ``K`` of the target whose method ``lp`` is, 1 if it
+    has none).  1 <= D <= 64, K >= 1.  ``lp_g``: (K, 1, D) -> (K, 1, D), ``lp``: (K, 1, D) -> (K,) or
+    (K, 1): the batched callables of the fits and of ``BatchedKLMonitor`` (``device_native`` ones stay on the GPU; any other
+    score goes through the host round trip of the fits).  Both are required: the line search needs the value, and the
+    reference's numerical-gradient fallback (scipy's, without ``lp_g``) is not carried over.
+
+    This is plain L-BFGS (history 10, scipy's ``maxcor``) with an Armijo backtracking search (c1 = 1e-4, halving, 20 rejected
+    trials at most), not a port of L-BFGS-B: no bounds, no Cauchy point, no More-Thuente search, so the evaluation counts differ
+    from scipy's (on well-conditioned posteriors by one or two, on ill-conditioned quadratics of D <= 10 by more: L-BFGS-B's
+    subspace step is missing).  ``maxiter``, ``maxfun``, ``gtol``, ``ftol`` are scipy's L-BFGS-B options at scipy's defaults as
+    the reference passes them.  A round is: ``lp_g`` and ``lp`` at the K trial points, then one launch that accepts or rejects
+    every problem's trial, updates its state and writes the next trial points.  A problem that has stopped is frozen, bit for
+    bit, while the others go on.  The loop does not synchronise per round: it reads the device's count of stopped problems
+    every ``check_every`` rounds and leaves when it equals K, so the result does not depend on ``check_every``; only
+    ``res.nlaunch`` does.  Prints nothing."""
+    from ._fitloop import scorer, takes_out
+    from .batched import MAX_D
+    from .monitors import lp_sums
+    if lp is None or lp_g is None:
+        raise ValueError("lbfgs_init_batched: lp and lp_g are both required (no numerical gradient)")
+    if not hasattr(x0, "shape"):
+        x0 = np.asarray(x0, dtype=np.float64)
+    shape = tuple(int(n) for n in x0.shape)
+    if len(shape) == 1:                                 # one start for every problem of the target that owns lp
+        shape = (int(getattr(getattr(lp, "__self__", None), "K", 1)),) + shape
+    elif len(shape) != 2:
+        raise ValueError(f"lbfgs_init_batched: x0 must be (K, D) or (D,), got {tuple(x0.shape)}")
+    K, D = shape
+    if not 1 <= D <= MAX_D:
+        raise ValueError(f"lbfgs_init_batched: D = {D} is outside 1 <= D <= {MAX_D}")
+    if K < 1:
+        raise ValueError(f"lbfgs_init_batched: K = {K} must be at least 1")
+    maxiter, maxfun, check_every = int(maxiter), int(maxfun), int(check_every)
+    if maxiter < 1 or maxfun < 2 or check_every < 1:
+        raise ValueError("lbfgs_init_batched: maxiter and check_every must be at least 1, maxfun at least 2")
+    if not (gtol >= 0.0 and ftol >= 0.0):
+        raise ValueError("lbfgs_init_batched: gtol and ftol must be >= 0")
+    if engine is None:
+        from .engine import get_engine
+        engine = get_engine()
+    eng = engine
+    x0 = eng.asarray(x0)
+    st = eng.lbfgs_state_batched(x0.reshape(K, D) if x0.dim() == 2 else x0.expand(K, D))
+    Xt = st["Xt"].reshape(K, 1, D)                      # the trial points where the callables read them (a view)
+    score = scorer(eng, lp_g)
+    Gbuf = eng.empty(K, 1, D) if not getattr(lp_g, "device_native", False) or takes_out(lp_g) else None
+    nlaunch = 0
+    for r in range(1, maxfun + 1):
+        G = score(Xt, out=Gbuf) if Gbuf is not None else score(Xt)
+        v = lp_sums(lp, Xt, eng, K)
+        eng.lbfgs_step_batched(v.contiguous(), G.reshape(K, D), st, start=r == 1, sign=-1.0, maxiter=maxiter, maxfun=maxfun,
+                               gtol=gtol, ftol=ftol)
+        nlaunch = r
+        if r % check_every == 0 and eng.read_flag(st["stopped"]) == K:
+            break
+    cov = eng.lbfgs_hess_inv_batched(st)
+    ist = eng.read_ints(st["ist"])
+    status = ist[:, 0]
+    res = LbfgsBatchedResult(x=eng.to_numpy(st["x"]), fun=eng.to_numpy(st["sc"][:, 0]).copy(), jac=eng.to_numpy(st["g"]),
+                             nit=ist[:, 1].copy(), nfev=ist[:, 2].copy(), status=status.copy(), success=status == 1,
+                             nlaunch=nlaunch)
+    return (st["x"], cov, res) if as_torch else (res.x.copy(), eng.to_numpy(cov), res)

@@ -21,6 +21,7 @@
  *   advi.py:31-45,69-73 ELBO gradient + optimiser step, K problems      ->  gsmvi_advi_step_batched_f64
  *   advi.py:80-86 initial (loc, scales), :23-27 scales -> covariance    ->  gsmvi_advi_init_batched_f64, gsmvi_advi_cov_batched_f64
  *   examples/example_gsm.py:34-35 a model's log_prob and jit(grad(.)) of it, K logistic regressions -> gsmvi_logistic_batched_f64
+ *   initializers.py:5-17 lbfgs_init (maximiser of lp, dense inverse-Hessian estimate), K problems -> gsmvi_lbfgs_step_batched_f64, gsmvi_lbfgs_hess_inv_batched_f64
  *   gsmvi/bam.py:72-114       bam_lowrank_update(samples,vs,mu0,S0,reg) ->  gsmvi_bam_update_f64
  *   gsmvi/bam.py:31-69        bam_update(samples,vs,mu0,S0,reg)         ->  gsmvi_bam_update_f64 (same result, K6)
  *
@@ -265,6 +266,7 @@ int gsmvi_get_profile(gsmvi_ctx* ctx, float* ms, int n);
 #define GSMVI_PATH_BATCHED_KL 0x8000u      /* k_kl_batched: the batched KL monitor's entry points                  */
 #define GSMVI_PATH_BATCHED_ADVI 0x10000u   /* k_advi_batched / k_advi_cov_batched: the batched ADVI entry points   */
 #define GSMVI_PATH_BATCHED_TARGET 0x20000u /* k_logistic_batched: the batched non-Gaussian target's entry point     */
+#define GSMVI_PATH_BATCHED_LBFGS 0x40000u  /* k_lbfgs_step_batched / k_lbfgs_hess_inv_batched: the batched initialiser   */
 #define GSMVI_PATH_GENERIC_MASK (0x0004u | 0x0010u | 0x0040u | 0x0100u | 0x0400u | 0x1000u)
 int gsmvi_last_path(gsmvi_ctx* ctx, unsigned* bits, int reset);
 
@@ -457,6 +459,42 @@ int gsmvi_advi_cov_batched_f64(gsmvi_ctx* ctx, void* stream, int64_t K, int D, c
 int gsmvi_logistic_batched_f64(gsmvi_ctx* ctx, void* stream, int64_t K, int D, int nc, int64_t N, const double* A, const double* y,
                                const int* counts_dev, double prior_prec, const double* prior_prec_dev, const double* X, double* G,
                                double* lp);
+
+/*
+ * Batched L-BFGS initialiser (gsmvi/initializers.py:5-17 for K problems of one D): the minimiser of phi_k = -lp_k as the mean and
+ * the dense BFGS inverse-Hessian product of the stored pairs on an identity base (scipy.optimize.LbfgsInvHessProduct(S, Y)
+ * .todense(), what res.hess_inv.todense() is) as the covariance.  Plain L-BFGS, history 10, Armijo backtracking (c1 = 1e-4,
+ * halving, at most 20 rejected trials per search); not a port of L-BFGS-B (no bounds, no Cauchy point, no More-Thuente search).
+ * 1 <= D <= 64, K >= 1 with the grid limits of the batched GSM above.  State, caller-owned, packed, in device memory:
+ *   x, g, d (K x D)  the last accepted point, the gradient of phi there, the search direction
+ *   S, Y (K x 10 x D) ring buffers of the pairs s = x' - x, y = g' - g; the held pairs are the slots head - n .. head - 1 (mod 10)
+ *   sc (K x 24)      [0] f = phi(x), [1] the trial step t, [2] g.d, [3] spare, [4..13] s.y of the ten slots, [14..23] y.y
+ *   ist (K x 8)      [0] status (0 running, 1 converged, 2 maxiter / maxfun reached, 3 line search failed, 4 non-finite start),
+ *                    [1] nit, [2] nfev, [3] nls (rejected trials of this search), [4] n = pairs held, [5] head = next slot, [6..7] spare
+ *   Xt (K x D)       the trial point: where the caller evaluates lp and its score next (K x 1 x D for the batched callables)
+ * gsmvi_lbfgs_step_batched_f64, one launch per evaluation.  ft = sign fv[k], gt = sign gv[k] (sign = -1: fv, gv are lp and its
+ * score at Xt; sign = 1: phi and its gradient).  start != 0: x holds x0 and Xt a copy of it; every other entry of the state is
+ * written: nfev = 1; non-finite ft or gt -> status 4; max|g| <= gtol -> status 1; else d = -g, t = min(1, 1 / |g|_2), g.d, Xt = x + t d.
+ * start == 0, for every problem with status 0: nfev += 1; ok = ft, gt finite and ft <= f + (1e-4 t) (g.d).  Not ok: t <- t / 2,
+ * nls += 1; nls > 20 -> status 3; else nfev >= maxfun -> status 2; else Xt = x + t d.  Ok: s = Xt - x, y = gt - g, (x, f, g) <- (Xt,
+ * ft, gt), nit += 1, the pair goes to slot head iff s.y > 2.2e-16 y.y; then max|g| <= gtol or fprev - f <= ftol max(|fprev|, |f|, 1)
+ * -> status 1; else nit >= maxiter or nfev >= maxfun -> status 2; else d = -H g by the two-loop recursion (scale s.y / y.y of the
+ * newest pair), t = 1 (no pair held, or g.d not < 0, which also drops the history: the steepest-descent start above), nls = 0,
+ * Xt = x + t d.  A problem whose status is not 0 is frozen: nothing of it is written.  *stopped_dev (one int, may be NULL) grows by
+ * the number of problems that stopped in this launch.  Every dot product is summed in an order fixed by D alone, so a problem's
+ * bits do not depend on K or on its neighbours.  maxiter >= 1, maxfun >= 2, gtol, ftol >= 0.  Written: the state and
+ * *stopped_dev, none of which may overlap any other array of the call.
+ * gsmvi_lbfgs_hess_inv_batched_f64: cov_k (K x D x D) = H after H_0 = I and, over the held pairs from oldest to newest with
+ * rho = 1 / s.y, H <- (I - rho s y^T) H (I - rho y s^T) + rho s s^T; exactly symmetric; the identity when no pair is held.  Reads
+ * S, Y and ist[4], ist[5] only.
+ * Both: shapes, NULL arrays and overlaps are checked before the context is looked at (then a NULL ctx); every failure returns
+ * GSMVI_ERR_BAD_ARG before anything is enqueued.  No context workspace is used.  Sets GSMVI_PATH_BATCHED_LBFGS.
+ */
+int gsmvi_lbfgs_step_batched_f64(gsmvi_ctx* ctx, void* stream, int64_t K, int D, int start, const double* fv, const double* gv,
+                                 double sign, double* x, double* g, double* d, double* S, double* Y, double* sc, int* ist,
+                                 double* Xt, int* stopped_dev, int maxiter, int maxfun, double gtol, double ftol);
+int gsmvi_lbfgs_hess_inv_batched_f64(gsmvi_ctx* ctx, void* stream, int64_t K, int D, const double* S, const double* Y,
+                                     const int* ist, double* cov);
 
 /*
  * Upper Cholesky factor R (R^T R = S, R upper triangular, strictly-lower part zeroed) of a

@@ -43,6 +43,10 @@ int gsmvi_debug_advi_batched_lds(int D, int B, int mode, size_t* bytes, int* pro
  * no device needed. */
 int gsmvi_debug_logistic_batched_lds(int D, int nc, int want, size_t* bytes, int* problems_per_workgroup);
 
+/* The same for a batched L-BFGS launch at D: mode 0 = gsmvi_lbfgs_step_batched_f64, 1 = gsmvi_lbfgs_hess_inv_batched_f64.  Host
+ * arithmetic only, no device needed. */
+int gsmvi_debug_lbfgs_batched_lds(int D, int mode, size_t* bytes, int* problems_per_workgroup);
+
 #pragma GCC visibility pop
 #ifdef __cplusplus
 }
