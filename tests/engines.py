@@ -1,6 +1,7 @@
-"""Test-only engine with the HipEngine interface backed by the numpy oracle.  It lets the CPU suite
-exercise the fit drivers' HOST logic (RNG stream, monitor cadence, revert, retries, sharding).  It is
-never importable from the product package."""
+"""Test-only engines with the HipEngine interface backed by the numpy oracle.  They let the CPU suite
+exercise the fit drivers' HOST logic (RNG stream, monitor cadence, revert, retries, sharding; the batched
+fits through OracleBatchedEngine and OracleBatchedBaMEngine).  They are never importable from the product
+package."""
 import numpy as np
 
 from oracle import gsm_oracle as orc
@@ -309,3 +310,217 @@ class OracleEngine:
             out[1][...] = S
             return out[0], out[1], flag
         return mu, S, flag
+
+
+def pivot_code(S):
+    """what the batched kernels write to ``info`` for a covariance that failed its Cholesky test: 1 + the first pivot that is
+    not > 0 and finite, by the elimination of tests/batched_step_ref.py (at least 1: numpy's test has already failed)"""
+    from batched_step_ref import verdict
+    return max(verdict(S)[0], 1)
+
+
+class OracleBatchedEngine:
+    """Batched engine on the oracle: every problem k runs the operations the single dense fit runs on tests/engines.py's
+    OracleEngine (orc.gsm_update_batched, the Cholesky test, x = mean + z R), so a problem of a batched fit equals the single
+    fit of its key bit for bit; a failed test reports the device's code, 1 + the first bad pivot (pivot_code).  Draw `call` of
+    problem k is the device stream restated on the CPU: B x Dz normals of philox_randn(seed_k, call), Dz = D rounded up to
+    even, column D dropped for odd D.  ``calls`` records every engine call."""
+    name = "oracle-batched(test-only)"
+
+    def __init__(self):
+        self.calls = []
+        self.draws = []           # (seed, call, Z) of every problem's draw, in order
+
+    def _rec(self, what):
+        self.calls.append(what)
+
+    def asarray(self, x):
+        self._rec("asarray")
+        return np.array(x, dtype=np.float64, copy=True)
+
+    def clone(self, x):
+        self._rec("clone")
+        return np.array(x, dtype=np.float64, copy=True)
+
+    def to_numpy(self, t):
+        return np.asarray(t)
+
+    def empty(self, *shape):
+        self._rec("empty")
+        return np.full(shape, np.nan)
+
+    def zeros(self, *shape):
+        self._rec("zeros")
+        return np.zeros(shape)
+
+    def eye_batch(self, K, D):
+        self._rec("eye_batch")
+        return np.broadcast_to(np.eye(D), (K, D, D)).copy()
+
+    def batched_ints(self, K):
+        self._rec("batched_ints")
+        return np.zeros(K, dtype=np.int64)
+
+    def read_ints(self, t):
+        return np.array(t, dtype=np.int64)
+
+    def batched_seeds(self, seeds):
+        self._rec("batched_seeds")
+        return np.array([int(s) & (2 ** 64 - 1) for s in seeds], dtype=np.uint64)
+
+    def host_score(self, lp_g, X, out=None):
+        self._rec("host_score")
+        g = np.asarray(lp_g(np.array(X, copy=True)), dtype=np.float64)
+        out[...] = g
+        return out
+
+    def _draw(self, seed, call, B, D):
+        Dz = D + (D & 1)
+        Z = orc.philox_randn(int(seed), call, B * Dz).reshape(B, Dz)[:, :D]
+        self.draws.append((int(seed), call, Z.copy()))
+        return Z
+
+    def gsm_fit_init_batched(self, mean, cov, R, info, seeds=None, X=None):
+        self._rec("init")
+        for k in range(mean.shape[0]):
+            if orc.cov_is_good(cov[k]):
+                R[k] = np.linalg.cholesky(cov[k]).T
+                info[k] = 0
+            else:
+                info[k] = pivot_code(cov[k])
+            if seeds is not None:
+                X[k] = mean[k][None, :] + self._draw(seeds[k], 0, X.shape[1], X.shape[2]) @ R[k]
+
+    def gsm_fit_step_batched(self, X, G, mean, cov, R=None, info=None, n_reverts=None, seeds=None, call=0):
+        self._rec(("step", call, seeds is not None))
+        for k in range(mean.shape[0]):
+            mu, S = orc.gsm_update_batched(X[k], G[k], mean[k], cov[k])
+            good = orc.cov_is_good(S)
+            if good:
+                mean[k], cov[k] = mu, S
+                if R is not None:
+                    R[k] = np.linalg.cholesky(S).T
+            elif n_reverts is not None:
+                n_reverts[k] += 1
+            if info is not None:
+                info[k] = 0 if good else pivot_code(S)
+            if seeds is not None:
+                X[k] = mean[k][None, :] + self._draw(seeds[k], call, X.shape[1], X.shape[2]) @ R[k]
+
+
+class _Arr(np.ndarray):
+    """a host array with the one tensor method the one-shot path calls"""
+
+    def contiguous(self):
+        return self
+
+
+class OracleBatchedBaMEngine:
+    """Batched BaM engine on the oracle: every problem k runs the operations of bam_oracle.bam_fit's iteration
+    (bam_lowrank_update_exact, + jitter I, symmetrise, the Cholesky test) and x = mean + z R; draw `call` of problem k is the
+    device stream restated on the CPU (B x Dz normals of philox_randn(seed_k, call), column D dropped for odd D).  ``calls``
+    records every engine call, ``regs`` the regulariser of every step, ``seen`` the samples of every step."""
+    name = "oracle-batched-bam(test-only)"
+
+    def __init__(self):
+        self.calls, self.draws, self.regs, self.seen = [], [], [], []
+
+    def _rec(self, what):
+        self.calls.append(what)
+
+    def asarray(self, x):
+        self._rec("asarray")
+        return np.array(x, dtype=np.float64, copy=True).view(_Arr)
+
+    def clone(self, x):
+        self._rec("clone")
+        return np.array(x, dtype=np.float64, copy=True)
+
+    def to_numpy(self, t):
+        return np.asarray(t)
+
+    def empty(self, *shape):
+        self._rec("empty")
+        return np.full(shape, np.nan)
+
+    def zeros(self, *shape):
+        self._rec("zeros")
+        return np.zeros(shape)
+
+    def eye_batch(self, K, D):
+        self._rec("eye_batch")
+        return np.broadcast_to(np.eye(D), (K, D, D)).copy()
+
+    def batched_ints(self, K):
+        self._rec("batched_ints")
+        return np.zeros(K, dtype=np.int64)
+
+    def read_ints(self, t):
+        return np.array(t, dtype=np.int64)
+
+    def batched_seeds(self, seeds):
+        self._rec("batched_seeds")
+        return np.array([int(s) & (2 ** 64 - 1) for s in seeds], dtype=np.uint64)
+
+    def batched_regs(self, values):
+        self._rec("batched_regs")
+        return np.array(values, dtype=np.float64)
+
+    def host_score(self, lp_g, X, out=None):
+        self._rec("host_score")
+        out[...] = np.asarray(lp_g(np.array(X, copy=True)), dtype=np.float64)
+        return out
+
+    def _draw(self, seed, call, B, D):
+        Dz = D + (D & 1)
+        Z = orc.philox_randn(int(seed), call, B * Dz).reshape(B, Dz)[:, :D]
+        self.draws.append((int(seed), call, Z.copy()))
+        return Z
+
+    def gsm_fit_init_batched(self, mean, cov, R, info, seeds=None, X=None):
+        self._rec("init")
+        for k in range(mean.shape[0]):
+            if orc.cov_is_good(cov[k]):
+                R[k] = np.linalg.cholesky(cov[k]).T
+                info[k] = 0
+            else:
+                info[k] = pivot_code(cov[k])
+            if seeds is not None:
+                X[k] = mean[k][None, :] + self._draw(seeds[k], 0, X.shape[1], X.shape[2]) @ R[k]
+
+    def bam_update_batched(self, X, G, mu0, S0, reg, jitter=0.0, out=None, info=None):
+        self._rec("update")
+        K, B, D = X.shape
+        regs = np.broadcast_to(np.asarray(reg, dtype=np.float64), (K,))
+        mu, S = np.empty((K, D)), np.empty((K, D, D))
+        for k in range(K):
+            m, s = borc.bam_lowrank_update_exact(X[k], G[k], mu0[k], S0[k], regs[k])
+            mu[k], S[k] = m, 0.5 * (s + s.T) + jitter * np.eye(D)
+        return mu.view(_Arr), S.view(_Arr)
+
+    def bam_fit_step_batched(self, X, G, mean, cov, R=None, reg=1.0, jitter=0.0, info=None, n_reverts=None, seeds=None,
+                             call=0):
+        self._rec(("step", call, seeds is not None))
+        K, B, D = X.shape
+        regs = np.broadcast_to(np.asarray(reg, dtype=np.float64), (K,)).copy()
+        self.regs.append(reg)
+        self.seen.append(np.array(X, copy=True))
+        for k in range(K):
+            with np.errstate(all="ignore"):
+                try:
+                    mu, S = borc.bam_lowrank_update_exact(X[k], G[k], mean[k], cov[k], regs[k])
+                    S = S + np.eye(D) * jitter
+                    S = (S + S.T) / 2.0
+                except (ValueError, np.linalg.LinAlgError):        # the device update never raises: a failed chain reverts
+                    mu, S = mean[k], np.full((D, D), np.nan)
+            good = orc.cov_is_good(S)
+            if good:
+                mean[k], cov[k] = mu, S
+                if R is not None:
+                    R[k] = np.linalg.cholesky(S).T
+            elif n_reverts is not None:
+                n_reverts[k] += 1
+            if info is not None:
+                info[k] = 0 if good else pivot_code(S)
+            if seeds is not None:
+                X[k] = mean[k][None, :] + self._draw(seeds[k], call, B, D) @ R[k]

@@ -1,5 +1,5 @@
 """Batched BaM without a GPU: the C ABI declarations and argument checks, and the host logic of BaMBatch.fit driven by an
-oracle-backed batched engine defined here (the pattern of tests/test_batched_cpu.py): seeds and draw calls, the regulariser
+oracle-backed batched engine of tests/engines.py: seeds and draw calls, the regulariser
 calls, per-problem reverts, bounds and shape errors."""
 import ctypes as C
 import os
@@ -15,6 +15,7 @@ from gsmvi_amd._fitloop import seed_of
 from gsmvi_amd import _lib
 from oracle import gsm_oracle as orc
 from oracle import bam_oracle as borc
+from engines import OracleBatchedBaMEngine
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ["gsmvi_bam_update_batched_f64", "gsmvi_bam_fit_step_batched_f64"]
@@ -82,124 +83,6 @@ def test_abi_checks_arguments_before_the_context_and_names_overlapping_arrays():
     assert upd(1, 4, 2) == 1
     assert lib.gsmvi_bam_update_batched_f64(None, None, 1, 4, 2, p, p, p, p, 1.0, None, 0.0, q, q + 8 * 64, p) == 1 \
         and "overlap" in err()                                          # info over an input
-
-
-class _Arr(np.ndarray):
-    """a host array with the one tensor method the one-shot path calls"""
-
-    def contiguous(self):
-        return self
-
-
-class OracleBatchedBaMEngine:
-    """Batched BaM engine on the oracle: every problem k runs the operations of bam_oracle.bam_fit's iteration
-    (bam_lowrank_update_exact, + jitter I, symmetrise, the Cholesky test) and x = mean + z R; draw `call` of problem k is the
-    device stream restated on the CPU (B x Dz normals of philox_randn(seed_k, call), column D dropped for odd D).  ``calls``
-    records every engine call, ``regs`` the regulariser of every step, ``seen`` the samples of every step."""
-    name = "oracle-batched-bam(test-only)"
-
-    def __init__(self):
-        self.calls, self.draws, self.regs, self.seen = [], [], [], []
-
-    def _rec(self, what):
-        self.calls.append(what)
-
-    def asarray(self, x):
-        self._rec("asarray")
-        return np.array(x, dtype=np.float64, copy=True).view(_Arr)
-
-    def clone(self, x):
-        self._rec("clone")
-        return np.array(x, dtype=np.float64, copy=True)
-
-    def to_numpy(self, t):
-        return np.asarray(t)
-
-    def empty(self, *shape):
-        self._rec("empty")
-        return np.full(shape, np.nan)
-
-    def zeros(self, *shape):
-        self._rec("zeros")
-        return np.zeros(shape)
-
-    def eye_batch(self, K, D):
-        self._rec("eye_batch")
-        return np.broadcast_to(np.eye(D), (K, D, D)).copy()
-
-    def batched_ints(self, K):
-        self._rec("batched_ints")
-        return np.zeros(K, dtype=np.int64)
-
-    def read_ints(self, t):
-        return np.array(t, dtype=np.int64)
-
-    def batched_seeds(self, seeds):
-        self._rec("batched_seeds")
-        return np.array([int(s) & (2 ** 64 - 1) for s in seeds], dtype=np.uint64)
-
-    def batched_regs(self, values):
-        self._rec("batched_regs")
-        return np.array(values, dtype=np.float64)
-
-    def host_score(self, lp_g, X, out=None):
-        self._rec("host_score")
-        out[...] = np.asarray(lp_g(np.array(X, copy=True)), dtype=np.float64)
-        return out
-
-    def _draw(self, seed, call, B, D):
-        Dz = D + (D & 1)
-        Z = orc.philox_randn(int(seed), call, B * Dz).reshape(B, Dz)[:, :D]
-        self.draws.append((int(seed), call, Z.copy()))
-        return Z
-
-    def gsm_fit_init_batched(self, mean, cov, R, info, seeds=None, X=None):
-        self._rec("init")
-        for k in range(mean.shape[0]):
-            if orc.cov_is_good(cov[k]):
-                R[k] = np.linalg.cholesky(cov[k]).T
-                info[k] = 0
-            else:
-                info[k] = 1
-            if seeds is not None:
-                X[k] = mean[k][None, :] + self._draw(seeds[k], 0, X.shape[1], X.shape[2]) @ R[k]
-
-    def bam_update_batched(self, X, G, mu0, S0, reg, jitter=0.0, out=None, info=None):
-        self._rec("update")
-        K, B, D = X.shape
-        regs = np.broadcast_to(np.asarray(reg, dtype=np.float64), (K,))
-        mu, S = np.empty((K, D)), np.empty((K, D, D))
-        for k in range(K):
-            m, s = borc.bam_lowrank_update_exact(X[k], G[k], mu0[k], S0[k], regs[k])
-            mu[k], S[k] = m, 0.5 * (s + s.T) + jitter * np.eye(D)
-        return mu.view(_Arr), S.view(_Arr)
-
-    def bam_fit_step_batched(self, X, G, mean, cov, R=None, reg=1.0, jitter=0.0, info=None, n_reverts=None, seeds=None,
-                             call=0):
-        self._rec(("step", call, seeds is not None))
-        K, B, D = X.shape
-        regs = np.broadcast_to(np.asarray(reg, dtype=np.float64), (K,)).copy()
-        self.regs.append(reg)
-        self.seen.append(np.array(X, copy=True))
-        for k in range(K):
-            with np.errstate(all="ignore"):
-                try:
-                    mu, S = borc.bam_lowrank_update_exact(X[k], G[k], mean[k], cov[k], regs[k])
-                    S = S + np.eye(D) * jitter
-                    S = (S + S.T) / 2.0
-                except (ValueError, np.linalg.LinAlgError):        # the device update never raises: a failed chain reverts
-                    mu, S = mean[k], np.full((D, D), np.nan)
-            good = orc.cov_is_good(S)
-            if good:
-                mean[k], cov[k] = mu, S
-                if R is not None:
-                    R[k] = np.linalg.cholesky(S).T
-            elif n_reverts is not None:
-                n_reverts[k] += 1
-            if info is not None:
-                info[k] = 0 if good else 1
-            if seeds is not None:
-                X[k] = mean[k][None, :] + self._draw(seeds[k], call, B, D) @ R[k]
 
 
 def _targets(K, D, seed=0):

@@ -1,5 +1,5 @@
-"""Batched GSM without a GPU: the C ABI declarations, and the host logic of GSMBatch.fit driven by an oracle-backed batched
-engine defined here (the pattern of tests/engines.py): seeds and draw calls, per-problem reverts, bounds and shape errors."""
+"""Batched GSM without a GPU: the C ABI declarations, and the host logic of GSMBatch.fit driven by the oracle-backed batched
+engine of tests/engines.py: seeds and draw calls, per-problem reverts, bounds and shape errors."""
 import os
 import re
 
@@ -11,7 +11,7 @@ from gsmvi_amd.gsm import GSM
 from gsmvi_amd._fitloop import seed_of
 from gsmvi_amd import _lib
 from oracle import gsm_oracle as orc
-from engines import OracleEngine
+from engines import OracleBatchedEngine, OracleEngine
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ["gsmvi_gsm_update_batched_f64", "gsmvi_gsm_fit_init_batched_f64", "gsmvi_gsm_fit_step_batched_f64",
@@ -27,94 +27,6 @@ def test_batched_entry_points_are_declared_and_exported():
         assert name in _lib.exported_symbols()
     assert re.search(r"#define\s+GSMVI_PATH_BATCHED\s+0x2000u", hdr)
     assert "#define GSMVI_ABI_VERSION 1" in hdr
-
-
-class OracleBatchedEngine:
-    """Batched engine on the oracle: every problem k runs the operations the single dense fit runs on tests/engines.py's
-    OracleEngine (orc.gsm_update_batched, the Cholesky test, x = mean + z R), so a problem of a batched fit equals the single
-    fit of its key bit for bit.  Draw `call` of problem k is the device stream restated on the CPU: B x Dz normals of
-    philox_randn(seed_k, call), Dz = D rounded up to even, column D dropped for odd D.  ``calls`` records every engine call."""
-    name = "oracle-batched(test-only)"
-
-    def __init__(self):
-        self.calls = []
-        self.draws = []           # (seed, call, Z) of every problem's draw, in order
-
-    def _rec(self, what):
-        self.calls.append(what)
-
-    def asarray(self, x):
-        self._rec("asarray")
-        return np.array(x, dtype=np.float64, copy=True)
-
-    def clone(self, x):
-        self._rec("clone")
-        return np.array(x, dtype=np.float64, copy=True)
-
-    def to_numpy(self, t):
-        return np.asarray(t)
-
-    def empty(self, *shape):
-        self._rec("empty")
-        return np.full(shape, np.nan)
-
-    def zeros(self, *shape):
-        self._rec("zeros")
-        return np.zeros(shape)
-
-    def eye_batch(self, K, D):
-        self._rec("eye_batch")
-        return np.broadcast_to(np.eye(D), (K, D, D)).copy()
-
-    def batched_ints(self, K):
-        self._rec("batched_ints")
-        return np.zeros(K, dtype=np.int64)
-
-    def read_ints(self, t):
-        return np.array(t, dtype=np.int64)
-
-    def batched_seeds(self, seeds):
-        self._rec("batched_seeds")
-        return np.array([int(s) & (2 ** 64 - 1) for s in seeds], dtype=np.uint64)
-
-    def host_score(self, lp_g, X, out=None):
-        self._rec("host_score")
-        g = np.asarray(lp_g(np.array(X, copy=True)), dtype=np.float64)
-        out[...] = g
-        return out
-
-    def _draw(self, seed, call, B, D):
-        Dz = D + (D & 1)
-        Z = orc.philox_randn(int(seed), call, B * Dz).reshape(B, Dz)[:, :D]
-        self.draws.append((int(seed), call, Z.copy()))
-        return Z
-
-    def gsm_fit_init_batched(self, mean, cov, R, info, seeds=None, X=None):
-        self._rec("init")
-        for k in range(mean.shape[0]):
-            if orc.cov_is_good(cov[k]):
-                R[k] = np.linalg.cholesky(cov[k]).T
-                info[k] = 0
-            else:
-                info[k] = 1
-            if seeds is not None:
-                X[k] = mean[k][None, :] + self._draw(seeds[k], 0, X.shape[1], X.shape[2]) @ R[k]
-
-    def gsm_fit_step_batched(self, X, G, mean, cov, R=None, info=None, n_reverts=None, seeds=None, call=0):
-        self._rec(("step", call, seeds is not None))
-        for k in range(mean.shape[0]):
-            mu, S = orc.gsm_update_batched(X[k], G[k], mean[k], cov[k])
-            good = orc.cov_is_good(S)
-            if good:
-                mean[k], cov[k] = mu, S
-                if R is not None:
-                    R[k] = np.linalg.cholesky(S).T
-            elif n_reverts is not None:
-                n_reverts[k] += 1
-            if info is not None:
-                info[k] = 0 if good else 1
-            if seeds is not None:
-                X[k] = mean[k][None, :] + self._draw(seeds[k], call, X.shape[1], X.shape[2]) @ R[k]
 
 
 def _targets(K, D, seed=0):
@@ -188,6 +100,43 @@ def test_nan_score_reverts_one_problem_alone(capsys):
     out = capsys.readouterr().out
     counts = [int(n) for n in re.findall(r"Revert \((\d+) since last print\)", out)]
     assert sum(counts) == niter + 1 and out.count("Iteration ") == 4
+
+
+def _poisoned_at(score, iterations, rows=None):
+    """``score`` with NaN (in ``rows`` of its leading axis, or everywhere) on the calls numbered in ``iterations``: a fit calls
+    its score once per iteration"""
+    count = [0]
+
+    def lp_g(X):
+        G = np.array(score(X), copy=True)
+        if count[0] in iterations:
+            G[slice(None) if rows is None else rows] = np.nan
+        count[0] += 1
+        return G
+    return lp_g
+
+
+def test_problem_reverts_and_recovers_like_the_single_fit():
+    """The score of problem j is NaN at iterations 3, 4 and 10 only: each time it keeps its state and draws the next samples
+    from the kept mean and factor, so it continues as the single dense fit with the same poisoned schedule does, bit for bit;
+    the other problems never notice."""
+    K, D, B, niter, j, when = 4, 6, 3, 20, 1, {3, 4, 10}
+    keys = np.array([3, 99, 1000, 5])
+    ms, Ps = _targets(K, D, seed=1)
+    mean0 = np.random.RandomState(0).standard_normal((K, D))
+    clean = _batched_score(ms, Ps)
+    ref = GSMBatch(K, D, None, clean, engine=OracleBatchedEngine())
+    m_ref, c_ref = ref.fit(keys, mean=mean0, batch_size=B, niter=niter, verbose=False)
+    fit = GSMBatch(K, D, None, _poisoned_at(clean, when, rows=j), engine=OracleBatchedEngine())
+    m, c = fit.fit(keys, mean=mean0, batch_size=B, niter=niter, verbose=False)
+    assert ref.n_reverts.tolist() == [0] * K and fit.n_reverts.tolist() == [3 if k == j else 0 for k in range(K)]
+    g = GSM(D, None, _poisoned_at(lambda x: orc.gaussian_score(x, ms[j], Ps[j]), when), engine=OracleEngine())
+    m1, c1 = g.fit(int(keys[j]), mean=mean0[j], batch_size=B, niter=niter, verbose=False, method="dense", rng="device")
+    assert g.n_reverts == 3
+    assert np.array_equal(m[j], m1) and np.array_equal(c[j], c1)
+    assert not np.array_equal(m[j], m_ref[j])                 # the schedule changed the problem's trajectory
+    others = [k for k in range(K) if k != j]
+    assert np.array_equal(m[others], m_ref[others]) and np.array_equal(c[others], c_ref[others])
 
 
 def test_forced_samples_take_no_draws():
