@@ -21,6 +21,9 @@ Mirrors the reference's public surface for the hot path (reference file:line):
     regressions, D <= 64: log-density and score
     of all of them in one launch -- the lp / lp_g
     of the three batched fits and the monitor)   examples/example_gsm.py:34-35 (log_prob, jit(grad(.)))
+    BatchedGLMTarget (the same launch for K
+    Poisson, probit, Gaussian or logistic
+    regressions with offsets)                    examples/example_gsm.py:34-35 (log_prob, jit(grad(.)))
     lbfgs_init_batched (the L-BFGS initialiser
     for K problems at once, D <= 64: one launch
     per function evaluation after lp_g and lp)   gsmvi/initializers.py:5-17
@@ -37,6 +40,7 @@ from .gsm import GSM, gsm_update                                     # noqa: F40
 from .bam import BaM, bam_update, bam_lowrank_update, Regularizers   # noqa: F401
 from .targets import GaussianTarget, device_score, score_from_logp   # noqa: F401
 from .targets import BatchedGaussianTarget, BatchedLogisticTarget    # noqa: F401
+from .targets import BatchedGLMTarget                                # noqa: F401
 from .batched import GSMBatch, gsm_update_batched                    # noqa: F401
 from .batched import BaMBatch, bam_update_batched, bam_lowrank_update_batched   # noqa: F401
 from .batched import ADVIBatch, Adam                                 # noqa: F401

@@ -23,6 +23,18 @@
 // a flag, not by arithmetic: sigma saturates and would hide an infinity).  A slot reads and writes only its own problem's
 // slices and every slot runs the same barriers (2 + 3 ceil(N / 32) per tile of X rows), so nothing crosses between problems.
 // All inputs are only read; no context workspace.
+//
+// The same kernel scores a family of generalised linear models (gsmvi_glm_batched_f64; DESIGN.md section 9, "Batched GLM
+// targets"): eta_n = a_n . x + o_kn with an optional offset o (K, N), lp = sum_n t(eta_n, y_n) - lam_k |x|^2 / 2 and
+// g = sum_n r(eta_n, y_n) a_n - lam_k x, where the link (r, t) is lb_link<FAM>, the third template parameter:
+//   logistic  r = y - sigma(eta)                               t = y eta - softplus(eta)            (the forms above)
+//   poisson   r = y - e^eta                                    t = y eta - e^eta                    (log link; -log y! dropped)
+//   probit    r = y phi/Phi(eta) - (1 - y) phi/Phi(-eta)       t = y log Phi(eta) + (1 - y) log Phi(-eta)
+//   gaussian  r = tau_k (y - eta)                              t = -tau_k (y - eta)^2 / 2           (identity link, precision tau_k)
+// Everything else -- tiling, prefetch, packing, order of summation, counts, priors, the row flags -- is the one copy below.  The
+// offset of a tile rides beside its y (32 more doubles of LDS per problem, only in the kernels with OFF, the fourth template
+// parameter: the launches without an offset keep the code and the registers they had before there was one).  A Poisson row for
+// which some valid e^eta is not finite gets NaN outputs through the row flag of a non-finite row of X.
 #include "gsmvi_common.h"
 #include "gsmvi_ctx.h"
 #include "gsmvi_batched.h"
@@ -32,6 +44,8 @@
 #include <type_traits>
 
 enum { LB_G = 1, LB_LP = 2 };
+enum { LB_LOGISTIC = GSMVI_GLM_LOGISTIC, LB_POISSON = GSMVI_GLM_POISSON, LB_PROBIT = GSMVI_GLM_PROBIT,
+       LB_GAUSSIAN = GSMVI_GLM_GAUSSIAN };
 #define LB_TN 32   // rows of A_k per tile
 #define LB_AQ 8    // tile elements per thread: LB_TN D / NT <= 8 in both packings
 
@@ -46,14 +60,61 @@ struct lb_args {
     const double* X;            // (K, nc, D)
     double* G;                  // (K, nc, D) or null
     double* lp;                 // (K, nc) or null
+    // the GLM families (appended: the logistic launches keep the argument block they had)
+    const double* offset;       // (K, N) added to eta, or null
+    double tau;                 // gaussian family: the noise precision of every problem ...
+    const double* tau_dev;      // ... or (K) per-problem values on the device (null: `tau`)
 };
 
 __host__ __device__ inline int lb_tc(int NT) { return NT == 256 ? 32 : 16; }
-// LDS doubles per problem: the A tile (32 x (D | 1)) + its y (32) + the X tile (tcm x (D | 1)) + the row flags (tcm) + r and
-// the density's terms (tcm x 33 each, as wanted).  (64, 32 rows, both): 6336 doubles, 49.5 KB; four problems of (16, 16 rows,
-// both): 4 x 1920 doubles, 60 KB
-__host__ __device__ inline int lb_lds_doubles(int D, int tcm, int want) {
-    return LB_TN * (D | 1) + LB_TN + tcm * ((D | 1) + 1 + (LB_TN | 1) * ((want & LB_G ? 1 : 0) + (want & LB_LP ? 1 : 0)));
+// LDS doubles per problem: the A tile (32 x (D | 1)) + its y (32) + its offset (32, when one is given) + the X tile (tcm x
+// (D | 1)) + the row flags (tcm) + r and the density's terms (tcm x 33 each, as wanted).  (64, 32 rows, both): 6336 doubles,
+// 49.5 KB; four problems of (16, 16 rows, both): 4 x 1920 doubles, 60 KB; with an offset 32 doubles per problem more: 49.75 KB
+// and 61 KB
+__host__ __device__ inline int lb_lds_doubles(int D, int tcm, int want, bool off = false) {
+    return LB_TN * (D | 1) + LB_TN + (off ? LB_TN : 0) +
+           tcm * ((D | 1) + 1 + (LB_TN | 1) * ((want & LB_G ? 1 : 0) + (want & LB_LP ? 1 : 0)));
+}
+
+// The link of family FAM at eta = h, label y (tau: the gaussian noise precision): r = d t / d eta and t, each evaluated only
+// when wanted.  Returns false when the row of X must be flagged (poisson: e^eta is not finite); what r and t then hold reaches
+// no output, the flag replaces every output of the row.
+template <int FAM, bool HAS_G, bool HAS_LP>
+__device__ __forceinline__ bool lb_link(double h, double y, double tau, double& r, double& t) {
+    if constexpr (FAM == LB_LOGISTIC) {
+        const double e = exp(-fabs(h)), d = 1.0 + e;
+        if (HAS_G) r = y - (h >= 0.0 ? 1.0 / d : e / d);
+        if (HAS_LP) t = y * h - ((h > 0.0 ? h : 0.0) + log1p(e));
+        return true;
+    } else if constexpr (FAM == LB_POISSON) {
+        const double m = exp(h);
+        if (HAS_G) r = y - m;
+        if (HAS_LP) t = y * h - m;
+        return m < __builtin_huge_val();                   // (false for a NaN too)
+    } else if constexpr (FAM == LB_PROBIT) {
+        // s = |eta|, u = erfcx(s / sqrt 2), e = exp(-s^2 / 2), q = u e / 2 = Phi(-s).  Tail side: log Phi(-s) = log(u / 2) - s^2 / 2,
+        // phi / Phi(-s) = sqrt(2 / pi) / u.  Central side: log Phi(s) = log1p(-q), phi / Phi(s) = e / sqrt(2 pi) / (1 - q).
+        const double s = fabs(h), u = erfcx(s * 0.70710678118654752440), hs = 0.5 * (s * s), e = exp(-hs), q = 0.5 * (u * e);
+        const double rt = 0.79788456080286535588 / u, rc = e * 0.39894228040143267794 / (1.0 - q);
+        double lt = 0.0, lc = 0.0;
+        if (HAS_LP) {
+            lt = log(0.5 * u) - hs;
+            lc = log1p(-q);
+        }
+        if (h >= 0.0) {                                    // Phi(eta) is the central side
+            if (HAS_G) r = y * rc - (1.0 - y) * rt;
+            if (HAS_LP) t = y * lc + (1.0 - y) * lt;
+        } else {
+            if (HAS_G) r = y * rt - (1.0 - y) * rc;
+            if (HAS_LP) t = y * lt + (1.0 - y) * lc;
+        }
+        return true;
+    } else {
+        const double d = y - h;
+        if (HAS_G) r = tau * d;
+        if (HAS_LP) t = -0.5 * (tau * (d * d));
+        return true;
+    }
 }
 
 // f(integral_constant<int, n>) for the runtime n in 1 .. MAX: the two inner loops below run with a compile-time number of rows of X
@@ -71,7 +132,7 @@ __device__ __forceinline__ void lb_rows(int n, F&& f) {
     }
 }
 
-template <int NT, int WANT>
+template <int NT, int WANT, int FAM, bool OFF>
 __global__ __launch_bounds__(256) void k_logistic_batched(lb_args a) {
     extern __shared__ double lb_sm[];
     constexpr int PPW = 256 / NT, TC = NT == 256 ? 32 : 16;
@@ -83,20 +144,29 @@ __global__ __launch_bounds__(256) void k_logistic_batched(lb_args a) {
     const int slot = threadIdx.x / NT, l = threadIdx.x % NT;
     const long long k = (long long)blockIdx.x * PPW + slot;
     const bool valid = k < a.K;               // a tail slot runs every barrier and nothing else
-    double* As = lb_sm + (size_t)slot * lb_lds_doubles(D, tcm, WANT);
+    double* As = lb_sm + (size_t)slot * lb_lds_doubles(D, tcm, WANT, OFF);
     double* Ys = As + LB_TN * ld;             // 32         y of the tile's rows
-    double* Xs = Ys + LB_TN;                  // tcm x ld   the rows of X
+    double* Os = Ys + LB_TN;                  // 32         their offsets, when given
+    double* Xs = Os + (OFF ? LB_TN : 0);      // tcm x ld   the rows of X
     double* Rb = Xs + tcm * ld;               // tcm        0, or NaN for a row of X with a non-finite entry
-    double* Rs = Rb + tcm;                    // tcm x ldr  r = y - sigma(eta)
-    double* Ts = Rs + (HAS_G ? tcm * ldr : 0);   // tcm x ldr  y eta - softplus(eta)
+    double* Rs = Rb + tcm;                    // tcm x ldr  r(eta, y) of the link
+    double* Ts = Rs + (HAS_G ? tcm * ldr : 0);   // tcm x ldr  t(eta, y) of the link
     const size_t kk = (size_t)(valid ? k : 0);
     const double* Ak = a.A + kk * (size_t)N * D;
     const double* yk = a.y + kk * (size_t)N;
+    // y_k and the offset share the prefetch: lane l < 32 carries y of the tile's row l, lane 32 + l its offset, and Os follows Ys
+    // (without an offset: lane l < 32 and y alone, as before there was one)
+    const int yl = OFF ? l % LB_TN : l;
+    // (an OFF launch without an offset -- the poisson family always takes the OFF kernels, see lb_go -- loads nothing in the
+    // upper lanes: the offset's tile is zeros)
+    const bool yload = !OFF || l < LB_TN || a.offset != nullptr;
+    const double* yo = OFF && l >= LB_TN && a.offset ? a.offset + kk * (size_t)N : yk;
+#define LB_YLANE(t) (OFF ? l < 2 * LB_TN && yl < (t) : l < (t))
     const double* Xk = a.X + kk * (size_t)a.nc * D;
     const double qnan = __longlong_as_double(0x7ff8000000000000LL);
 
     long long nk = 0;                         // the rows that count
-    double lam = 0.0;
+    double lam = 0.0, tau = 1.0;
     if (valid) {
         nk = N;
         if (a.counts) {
@@ -104,6 +174,7 @@ __global__ __launch_bounds__(256) void k_logistic_batched(lb_args a) {
             nk = c < 0 ? 0 : (c > N ? N : c);
         }
         lam = a.lam_dev ? a.lam_dev[k] : a.lam;
+        if (FAM == LB_GAUSSIAN) tau = a.tau_dev ? a.tau_dev[k] : a.tau;
     }
     // the tile elements e = l + q NT of this thread as (row, column), stepped without a division
     const int row0 = l / D, col0 = l - row0 * D, dr = NT / D, dc = NT - dr * D;
@@ -128,7 +199,7 @@ __global__ __launch_bounds__(256) void k_logistic_batched(lb_args a) {
                 const int e = l + q * NT;
                 pre[q] = e < te ? Ak[e] : 0.0;
             }
-            if (l < tnv) ypre = yk[l];
+            if (LB_YLANE(tnv) && yload) ypre = yo[yl];
         }
         __syncthreads();
         double xx = 0.0;                      // |x|^2 of row l (threads l < tc)
@@ -163,7 +234,7 @@ __global__ __launch_bounds__(256) void k_logistic_batched(lb_args a) {
                         ++r;
                     }
                 }
-                if (l < tnv) Ys[l] = ypre;
+                if (LB_YLANE(tnv)) Ys[l] = ypre;
             }
             __syncthreads();
             {                                 // the next tile's loads: in flight while this one is consumed
@@ -175,7 +246,7 @@ __global__ __launch_bounds__(256) void k_logistic_batched(lb_args a) {
                     const int e = l + q * NT;
                     if (e < te2) pre[q] = An[e];
                 }
-                if (l < tnv2) ypre = yk[n0 + LB_TN + l];
+                if (LB_YLANE(tnv2) && yload) ypre = yo[n0 + LB_TN + yl];
             }
             if (en < tnv && eg < tc) {        // eta, the link
                 double eta[CQ];
@@ -195,6 +266,11 @@ __global__ __launch_bounds__(256) void k_logistic_batched(lb_args a) {
                         for (int q = 0; q < decltype(nr)::value; ++q) eta[q] = fma(av, Xs[xo[q] + j], eta[q]);
                     }
                 });
+                if (OFF) {
+                    const double ov = Os[en];
+#pragma unroll
+                    for (int q = 0; q < CQ; ++q) eta[q] += ov;
+                }
                 // eta goes through this thread's own LDS cells, so that the link below is ONE copy of exp / log1p in a rolled
                 // loop (unrolled over q it takes 170 - 230 VGPRs)
                 double* Es = HAS_G ? Rs : Ts;
@@ -204,9 +280,11 @@ __global__ __launch_bounds__(256) void k_logistic_batched(lb_args a) {
                 const double yv = Ys[en];
 #pragma unroll 1
                 for (int c = eg; c < tc; c += NG) {
-                    const double h = Es[c * ldr + en], e = exp(-fabs(h)), d = 1.0 + e;
-                    if (HAS_G) Rs[c * ldr + en] = yv - (h >= 0.0 ? 1.0 / d : e / d);
-                    if (HAS_LP) Ts[c * ldr + en] = yv * h - ((h > 0.0 ? h : 0.0) + log1p(e));
+                    double r = 0.0, t = 0.0;
+                    const bool fine = lb_link<FAM, HAS_G, HAS_LP>(Es[c * ldr + en], yv, tau, r, t);
+                    if (HAS_G) Rs[c * ldr + en] = r;
+                    if (HAS_LP) Ts[c * ldr + en] = t;
+                    if (FAM == LB_POISSON && !fine) Rb[c] = qnan;     // (any number of threads, the same value)
                 }
             }
             __syncthreads();
@@ -246,14 +324,93 @@ __global__ __launch_bounds__(256) void k_logistic_batched(lb_args a) {
         }
         __syncthreads();                      // the next tile of X rows overwrites Xs and Rb
     }
+#undef LB_YLANE
 }
 
-// dynamic LDS bytes of a launch at (D, nc, want): at most 60 KB, below the default limit, so no kernel attribute is needed
-static size_t lb_launch_lds(int D, int nc, int want, int* ppw, int* tcm) {
+// dynamic LDS bytes of a launch at (D, nc, want): at most 60 KB (61 KB with an offset), below the default limit of 64 KB, so no
+// kernel attribute is needed
+static size_t lb_launch_lds(int D, int nc, int want, bool off, int* ppw, int* tcm) {
     const int nt = gb_nt(D), tc = lb_tc(nt);
     *ppw = 256 / nt;
     *tcm = nc < tc ? nc : tc;
-    return (size_t)*ppw * lb_lds_doubles(D, *tcm, want) * sizeof(double);
+    return (size_t)*ppw * lb_lds_doubles(D, *tcm, want, off) * sizeof(double);
+}
+
+// does a launch of `family` carry the offset's tile: with an offset, and always for the poisson family (whose 256-thread score
+// kernel without the tile is the one instantiation that needs more than 256 registers and so runs at half the occupancy and
+// 1.5 times the time of the one with it; a NULL offset is then a tile of zeros, and eta + 0 changes no bit of r or t)
+// This is a choice made for one compiler's register allocation: DESIGN.md says how to re-check it after a toolchain change.
+static bool lb_off_tile(int family, bool has_offset) { return has_offset || family == GSMVI_GLM_POISSON; }
+static bool lb_off(int family, const double* offset) { return lb_off_tile(family, offset != nullptr); }
+
+template <int FAM>
+static void lb_go(int ppw, int want, unsigned grid, size_t lds, hipStream_t st, const lb_args& a) {
+    const bool off = lb_off(FAM, a.offset);
+#define LB_GO(NTV, W)                                                                                          \
+    do {                                                                                                       \
+        if (off)                                                                                               \
+            hipLaunchKernelGGL((k_logistic_batched<NTV, W, FAM, true>), dim3(grid), dim3(256), lds, st, a);    \
+        else if constexpr (FAM != LB_POISSON)                                                                  \
+            hipLaunchKernelGGL((k_logistic_batched<NTV, W, FAM, false>), dim3(grid), dim3(256), lds, st, a);   \
+    } while (0)
+    if (ppw == 4) {
+        if (want == LB_G) LB_GO(64, LB_G);
+        else if (want == LB_LP) LB_GO(64, LB_LP);
+        else LB_GO(64, LB_G | LB_LP);
+    } else {
+        if (want == LB_G) LB_GO(256, LB_G);
+        else if (want == LB_LP) LB_GO(256, LB_LP);
+        else LB_GO(256, LB_G | LB_LP);
+    }
+#undef LB_GO
+}
+
+// The body of both entry points: every check (shapes, the family and its noise precision, NULL arrays, overlaps, the context
+// last), then the one launch.  `fn` names the entry point in the messages.
+static int lb_run(const char* fn, gsmvi_ctx* ctx, void* stream, int64_t K, int D, int nc, int64_t N, int family, const double* A,
+                  const double* y, const double* offset, const int* counts_dev, double noise_prec, const double* noise_prec_dev,
+                  double prior_prec, const double* prior_prec_dev, const double* X, double* G, double* lp) {
+#define LB_BAD(cond, msg)                     \
+    do {                                      \
+        if (cond) return gb_bad(fn, msg);     \
+    } while (0)
+    if (int st = gb_check_shape(fn, K, D, gb_ppw)) return st;
+    LB_BAD(nc < 1, "nc must be at least 1");
+    LB_BAD(N < 1, "N must be at least 1");
+    LB_BAD(N > (INT64_MAX / 8 / D) / K, "K N D is too large");
+    LB_BAD(nc > (INT64_MAX / 8 / D) / K, "K nc D is too large");
+    LB_BAD(family < GSMVI_GLM_LOGISTIC || family > GSMVI_GLM_GAUSSIAN, "family must be one of GSMVI_GLM_LOGISTIC .. GSMVI_GLM_GAUSSIAN");
+    LB_BAD(!A || !y || !X, "NULL array");
+    LB_BAD(!G && !lp, "give G or lp (or both)");
+    LB_BAD(!prior_prec_dev && !(prior_prec >= 0.0 && prior_prec < __builtin_huge_val()), "prior_prec must be finite and >= 0");
+    if (family == GSMVI_GLM_GAUSSIAN)
+        LB_BAD(!noise_prec_dev && !(noise_prec > 0.0 && noise_prec < __builtin_huge_val()), "noise_prec must be finite and > 0");
+    else
+        LB_BAD(noise_prec_dev || noise_prec != 1.0, "noise_prec is the gaussian family's: give 1.0 and NULL for any other");
+    const size_t na = (size_t)K * N * D * 8, ny = (size_t)K * N * 8, nx = (size_t)K * nc * D * 8, nl = (size_t)K * nc * 8,
+                 nk = (size_t)K * 8, ni = (size_t)K * 4;
+    if (int st = gb_check_overlaps(fn, {{A, na, "A", GB_RD}, {y, ny, "y", GB_RD}, {offset, ny, "offset", GB_RD},
+                                        {counts_dev, ni, "counts_dev", GB_RD}, {noise_prec_dev, nk, "noise_prec_dev", GB_RD},
+                                        {prior_prec_dev, nk, "prior_prec_dev", GB_RD}, {X, nx, "X", GB_RD}, {G, nx, "G", GB_WR},
+                                        {lp, nl, "lp", GB_WR}}))
+        return st;
+    LB_BAD(!ctx, "ctx is NULL");
+#undef LB_BAD
+    const int want = (G ? LB_G : 0) | (lp ? LB_LP : 0);
+    lb_args a = {};
+    a.K = K; a.N = N; a.D = D; a.nc = nc; a.A = A; a.y = y; a.offset = offset; a.tau = noise_prec; a.tau_dev = noise_prec_dev;
+    a.counts = counts_dev; a.lam = prior_prec; a.lam_dev = prior_prec_dev; a.X = X; a.G = G; a.lp = lp;
+    int ppw;
+    const size_t lds = lb_launch_lds(D, nc, want, lb_off(family, offset), &ppw, &a.tcm);
+    const unsigned grid = (unsigned)((K + ppw - 1) / ppw);
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    switch (family) {
+        case GSMVI_GLM_LOGISTIC: lb_go<LB_LOGISTIC>(ppw, want, grid, lds, st, a); break;
+        case GSMVI_GLM_POISSON: lb_go<LB_POISSON>(ppw, want, grid, lds, st, a); break;
+        case GSMVI_GLM_PROBIT: lb_go<LB_PROBIT>(ppw, want, grid, lds, st, a); break;
+        default: lb_go<LB_GAUSSIAN>(ppw, want, grid, lds, st, a); break;
+    }
+    return gb_launched(ctx, GSMVI_PATH_BATCHED_TARGET, "k_logistic_batched");
 }
 
 extern "C" {
@@ -261,37 +418,16 @@ extern "C" {
 int gsmvi_logistic_batched_f64(gsmvi_ctx* ctx, void* stream, int64_t K, int D, int nc, int64_t N, const double* A, const double* y,
                                const int* counts_dev, double prior_prec, const double* prior_prec_dev, const double* X, double* G,
                                double* lp) {
-    if (int st = gb_check_shape(__func__, K, D, gb_ppw)) return st;
-    GB_BAD(nc < 1, "nc must be at least 1");
-    GB_BAD(N < 1, "N must be at least 1");
-    GB_BAD(N > (INT64_MAX / 8 / D) / K, "K N D is too large");
-    GB_BAD(nc > (INT64_MAX / 8 / D) / K, "K nc D is too large");
-    GB_BAD(!A || !y || !X, "NULL array");
-    GB_BAD(!G && !lp, "give G or lp (or both)");
-    GB_BAD(!prior_prec_dev && !(prior_prec >= 0.0 && prior_prec < __builtin_huge_val()), "prior_prec must be finite and >= 0");
-    const size_t na = (size_t)K * N * D * 8, ny = (size_t)K * N * 8, nx = (size_t)K * nc * D * 8, nl = (size_t)K * nc * 8,
-                 nk = (size_t)K * 8, ni = (size_t)K * 4;
-    if (int st = gb_check_overlaps(__func__, {{A, na, "A", GB_RD}, {y, ny, "y", GB_RD}, {counts_dev, ni, "counts_dev", GB_RD},
-                                              {prior_prec_dev, nk, "prior_prec_dev", GB_RD}, {X, nx, "X", GB_RD},
-                                              {G, nx, "G", GB_WR}, {lp, nl, "lp", GB_WR}}))
-        return st;
-    GB_BAD(!ctx, "ctx is NULL");
-    const int want = (G ? LB_G : 0) | (lp ? LB_LP : 0);
-    lb_args a = {};
-    a.K = K; a.N = N; a.D = D; a.nc = nc; a.A = A; a.y = y; a.counts = counts_dev; a.lam = prior_prec; a.lam_dev = prior_prec_dev;
-    a.X = X; a.G = G; a.lp = lp;
-    int ppw;
-    const size_t lds = lb_launch_lds(D, nc, want, &ppw, &a.tcm);
-    const unsigned grid = (unsigned)((K + ppw - 1) / ppw);
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-#define LB_GO(NTV, W) hipLaunchKernelGGL((k_logistic_batched<NTV, W>), dim3(grid), dim3(256), lds, st, a)
-    if (ppw == 4) {
-        if (want == LB_G) LB_GO(64, LB_G); else if (want == LB_LP) LB_GO(64, LB_LP); else LB_GO(64, LB_G | LB_LP);
-    } else {
-        if (want == LB_G) LB_GO(256, LB_G); else if (want == LB_LP) LB_GO(256, LB_LP); else LB_GO(256, LB_G | LB_LP);
-    }
-#undef LB_GO
-    return gb_launched(ctx, GSMVI_PATH_BATCHED_TARGET, "k_logistic_batched");
+    return lb_run(__func__, ctx, stream, K, D, nc, N, GSMVI_GLM_LOGISTIC, A, y, nullptr, counts_dev, 1.0, nullptr, prior_prec,
+                  prior_prec_dev, X, G, lp);
+}
+
+int gsmvi_glm_batched_f64(gsmvi_ctx* ctx, void* stream, int64_t K, int D, int nc, int64_t N, int family, const double* A,
+                          const double* y, const double* offset, const int* counts_dev, double noise_prec,
+                          const double* noise_prec_dev, double prior_prec, const double* prior_prec_dev, const double* X, double* G,
+                          double* lp) {
+    return lb_run(__func__, ctx, stream, K, D, nc, N, family, A, y, offset, counts_dev, noise_prec, noise_prec_dev, prior_prec,
+                  prior_prec_dev, X, G, lp);
 }
 
 // include/gsmvi_hip_debug.h: what a launch at (D, nc) requests (exported by the debug library only); want: 1 = G, 2 = lp, 3 = both
@@ -299,7 +435,18 @@ int gsmvi_debug_logistic_batched_lds(int D, int nc, int want, size_t* bytes, int
     GB_BAD(D < 1 || D > GB_MAX_D || nc < 1 || want < 1 || want > 3 || !bytes || !problems_per_workgroup,
            "bad shape, want or NULL output");
     int tcm;
-    *bytes = lb_launch_lds(D, nc, want, problems_per_workgroup, &tcm);
+    *bytes = lb_launch_lds(D, nc, want, false, problems_per_workgroup, &tcm);
+    return GSMVI_OK;
+}
+
+// the same for a gsmvi_glm_batched_f64 launch of `family`, through the launch's own rule for the offset's tile (lb_off)
+int gsmvi_debug_glm_batched_lds(int D, int nc, int want, int family, int has_offset, size_t* bytes,
+                                int* problems_per_workgroup) {
+    GB_BAD(D < 1 || D > GB_MAX_D || nc < 1 || want < 1 || want > 3 || family < GSMVI_GLM_LOGISTIC ||
+               family > GSMVI_GLM_GAUSSIAN || !bytes || !problems_per_workgroup,
+           "bad shape, want, family or NULL output");
+    int tcm;
+    *bytes = lb_launch_lds(D, nc, want, lb_off_tile(family, has_offset != 0), problems_per_workgroup, &tcm);
     return GSMVI_OK;
 }
 

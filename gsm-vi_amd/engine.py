@@ -893,6 +893,39 @@ class HipEngine:
             self._dp(lp, (K, nc), "lp_out")))
         return G if want == "g" else lp if want == "lp" else (G, lp)
 
+    # ---- batched GLM targets: the same launch for a family of links (csrc/gsmvi_logistic_batched.hip) -----------------------
+    GLM_FAMILIES = {"logistic": 0, "poisson": 1, "probit": 2, "gaussian": 3}     # GSMVI_GLM_* of include/gsmvi_hip.h
+
+    def glm_batched(self, X, A, y, family, offset=None, counts=None, prior_prec=1.0, noise_prec=1.0, out=None, lp_out=None,
+                    want="g"):
+        """Score and / or log-density of K generalised linear models at the rows of X (K, nc, D), one launch
+        [examples/example_gsm.py:34-35 for these models]: ``family`` "logistic", "poisson" (log link), "probit" or "gaussian"
+        (identity link, noise precision ``noise_prec``: a number or a (K,) device tensor, this family only); A (K, N, D), y
+        (K, N), ``offset`` None or (K, N) added to A x, ``counts`` None or K device int32 valid rows, ``prior_prec`` a number or
+        a (K,) device tensor.  ``want`` = "g" -> G (K, nc, D), "lp" -> the values (K, nc), "both" -> (G, lp)."""
+        if want not in ("g", "lp", "both"):
+            raise ValueError(f"want = {want!r}: expected 'g', 'lp' or 'both'")
+        if family not in self.GLM_FAMILIES:
+            raise ValueError(f"family = {family!r}: expected one of {sorted(self.GLM_FAMILIES)}")
+        X = X.contiguous()
+        K, nc, D = X.shape
+        N = A.shape[1]
+        self._ensure(max(self._max_D, 1), max(self._max_B, 1))
+        G = lp = None
+        if want != "lp":
+            G = self.empty(K, nc, D) if out is None else out
+        if want != "g":
+            lp = self.empty(K, nc) if lp_out is None else lp_out
+        r, rp = self._reg_arg(prior_prec, K)
+        t, tp = self._reg_arg(noise_prec, K)
+        if tp is not None:
+            t = 1.0                                                   # (the scalar is unused with K values)
+        _lib.check("gsmvi_glm_batched_f64", self.lib.gsmvi_glm_batched_f64(
+            self._ctx, self._stream(), K, D, nc, N, self.GLM_FAMILIES[family], self._packed(A, (K, N, D), "A"),
+            self._packed(y, (K, N), "y"), self._dp(offset, (K, N), "offset"), self._ints(counts, K, "counts"), t, tp, r, rp,
+            self._packed(X, (K, nc, D), "X"), self._dp(G, (K, nc, D), "out"), self._dp(lp, (K, nc), "lp_out")))
+        return G if want == "g" else lp if want == "lp" else (G, lp)
+
     # ---- batched L-BFGS initialiser: K minimisations of one D (csrc/gsmvi_lbfgs_batched.hip) --------------------------------
     def lbfgs_state_batched(self, x0):
         """The state of K L-BFGS runs started at the rows of x0 (K, D), as include/gsmvi_hip.h lays it out: a dict of device

@@ -6,7 +6,8 @@ kernel.  ``device_score`` marks a user callable as taking/returning CUDA tensors
 ``score_from_logp`` is the sum-then-autograd helper matching the JAX examples
 (examples/example_gsm.py:34-35: ``lp_g = jit(grad(lambda x: sum(lp(x))))``).
 ``BatchedLogisticTarget`` is the first non-Gaussian device target of the batched fits: K Bayesian logistic
-regressions, score and log-density from one HIP launch.
+regressions, score and log-density from one HIP launch.  ``BatchedGLMTarget`` is the same launch for a family of generalised
+linear models: Poisson, probit, Gaussian and logistic, with offsets.
 """
 import numpy as np
 import torch
@@ -192,3 +193,116 @@ class BatchedLogisticTarget:
         """(scores (K, rows, D), values (K, rows)) from one launch"""
         eng = self.engine
         return eng.logistic_batched(eng.asarray(x), self.A, self.y, self.counts, self.prior_precision, want="both")
+
+
+class BatchedGLMTarget:
+    """K Bayesian generalised linear models with their own data sets, for ``GSMBatch``, ``BaMBatch``, ``ADVIBatch``,
+    ``BatchedKLMonitor`` and ``lbfgs_init_batched``: ``BatchedLogisticTarget``'s protocol for a family of links.  Problem k has
+    the design matrix A[k] (N, D), responses y[k] (N,), an optional ``offset[k]`` (N,) added to the linear predictor (a log
+    exposure, say), ``counts[k]`` <= N valid rows (None: all N; the rows beyond are ignored whatever they hold) and the prior
+    N(0, I / lam_k), ``prior_precision`` = lam a float or K values, 0 = flat.  With eta = A[k] x + offset[k]:
+
+        lp_k(x) = sum_n t(eta_n, y_n) - lam_k |x|^2 / 2,      grad lp_k(x) = sum_n r(eta_n, y_n) a_n - lam_k x
+
+        family       y                  r                                          t
+        "logistic"   in [0, 1]          y - sigmoid(eta)                           y eta - softplus(eta)
+        "poisson"    >= 0, finite       y - exp(eta)                               y eta - exp(eta)      (log link; -log y! dropped)
+        "probit"     in [0, 1]          y phi/Phi(eta) - (1 - y) phi/Phi(-eta)     y log Phi(eta) + (1 - y) log Phi(-eta)
+        "gaussian"   finite             tau_k (y - eta)                            -tau_k (y - eta)^2 / 2   (identity link)
+
+    evaluated by gsmvi_glm_batched_f64: what examples/example_gsm.py:34-35 gets from a model's log_prob and jit(grad(...)).
+    ``noise_precision`` = tau, a float or K values > 0, is the Gaussian family's alone.  A Poisson point whose exp(eta) overflows
+    in a valid row gets NaN outputs (the fits then revert that step).  numpy arrays or tensors in; everything is kept on the
+    device as float64 / int32.  Arguments are validated on the host before any device work (ValueError naming the argument and
+    the problems).
+
+    ``lp_g(x, out=None)``: (K, B, D) -> (K, B, D) scores, ``device_native`` and ``graph_safe`` (one capturable launch, no
+    allocation with ``out``).  ``lp(x)``: (K, rows, D) -> (K, rows) values; a device tensor or numpy.  ``lp_and_score(x)``:
+    (scores, values) from one launch."""
+
+    FAMILIES = ("logistic", "poisson", "probit", "gaussian")
+
+    def __init__(self, A, y, family, prior_precision=1.0, counts=None, offset=None, noise_precision=1.0, engine=None):
+        if family not in self.FAMILIES:
+            raise ValueError(f"family: expected one of {self.FAMILIES}, got {family!r}")
+        sa, sy = tuple(int(n) for n in A.shape), tuple(int(n) for n in y.shape)
+        if len(sa) != 3 or min(sa) < 1:
+            raise ValueError(f"A: expected shape (K, N, D) with K, N, D >= 1, got {sa}")
+        K, N, D = sa
+        if not 1 <= D <= 64:
+            raise ValueError(f"A: D = {D} is outside 1 <= D <= 64")
+        if sy != (K, N):
+            raise ValueError(f"y: expected shape (K, N) = {(K, N)}, got {sy}")
+        cnt = None
+        if counts is not None:
+            cnt = np.asarray(_host_array(counts))
+            if cnt.shape != (K,) or not np.issubdtype(cnt.dtype, np.integer):
+                raise ValueError(f"counts: expected {K} integers, got shape {cnt.shape}, dtype {cnt.dtype}")
+            if (cnt < 0).any() or (cnt > N).any():
+                raise ValueError(f"counts: values outside 0 .. N = {N} for problems {np.flatnonzero((cnt < 0) | (cnt > N)).tolist()}")
+        yh = np.asarray(_host_array(y), dtype=np.float64)
+        live = np.arange(N)[None, :] < (cnt[:, None] if cnt is not None else N)
+        with np.errstate(invalid="ignore"):
+            if family in ("logistic", "probit"):
+                good, what = (yh >= 0.0) & (yh <= 1.0), "outside [0, 1] or non-finite"     # (a NaN fails both comparisons)
+            elif family == "poisson":
+                good, what = (yh >= 0.0) & np.isfinite(yh), "negative or non-finite"
+            else:
+                good, what = np.isfinite(yh), "non-finite"
+        bad = live & ~good
+        if bad.any():
+            raise ValueError(f"y: values {what} in the valid rows of problems {np.flatnonzero(bad.any(1)).tolist()} "
+                             f"(family {family!r})")
+        oh = None
+        if offset is not None:
+            so = tuple(int(n) for n in offset.shape) if hasattr(offset, "shape") else np.shape(offset)
+            if so != (K, N):
+                raise ValueError(f"offset: expected shape (K, N) = {(K, N)}, got {so}")
+            oh = np.asarray(_host_array(offset), dtype=np.float64)
+            bad = live & ~np.isfinite(oh)
+            if bad.any():
+                raise ValueError(f"offset: non-finite values in the valid rows of problems {np.flatnonzero(bad.any(1)).tolist()}")
+        lam = np.asarray(_host_array(prior_precision), dtype=np.float64)
+        if lam.shape not in ((), (K,)):
+            raise ValueError(f"prior_precision: expected a number or {K} values, got shape {lam.shape}")
+        if not (np.isfinite(lam) & (lam >= 0.0)).all():
+            raise ValueError("prior_precision: expected finite values >= 0")
+        tau = np.asarray(_host_array(noise_precision), dtype=np.float64)
+        if tau.shape not in ((), (K,)):
+            raise ValueError(f"noise_precision: expected a number or {K} values, got shape {tau.shape}")
+        if family != "gaussian" and not (tau == 1.0).all():
+            raise ValueError(f"noise_precision: only family 'gaussian' has one (family {family!r}: leave it at 1.0)")
+        if not (np.isfinite(tau) & (tau > 0.0)).all():
+            where = "" if tau.shape == () else f" (problems {np.flatnonzero(~(np.isfinite(tau) & (tau > 0.0))).tolist()})"
+            raise ValueError(f"noise_precision: expected finite values > 0{where}")
+        self.engine = engine if engine is not None else get_engine()
+        eng = self.engine
+        self.family = family
+        self.K, self.N, self.D = K, N, D
+        self.A = eng.asarray(A.contiguous() if isinstance(A, torch.Tensor) else A)
+        self.y = eng.asarray(yh)
+        self.offset = eng.asarray(oh) if oh is not None else None
+        self.counts = eng.batched_counts(cnt) if cnt is not None else None
+        self.prior_precision = float(lam) if lam.shape == () else eng.batched_regs(lam)
+        if family != "gaussian":
+            self.noise_precision = 1.0
+        else:
+            self.noise_precision = float(tau) if tau.shape == () else eng.batched_regs(tau)
+
+        def lp_g(x, out=None):
+            return self._call(x, out=out, want="g")
+        lp_g.device_native = True
+        lp_g.graph_safe = True          # one capturable kernel launch, no allocation when `out` is given, no host work
+        self.lp_g = lp_g
+
+    def _call(self, x, **kw):
+        return self.engine.glm_batched(x, self.A, self.y, self.family, offset=self.offset, counts=self.counts,
+                                       prior_prec=self.prior_precision, noise_prec=self.noise_precision, **kw)
+
+    def lp(self, x):
+        """(K, rows) values lp_k(x_kr) at the rows of x (K, rows, D), a device tensor or numpy; one launch"""
+        return self._call(self.engine.asarray(x), want="lp")
+
+    def lp_and_score(self, x):
+        """(scores (K, rows, D), values (K, rows)) from one launch"""
+        return self._call(self.engine.asarray(x), want="both")

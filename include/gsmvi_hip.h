@@ -21,6 +21,7 @@
  *   advi.py:31-45,69-73 ELBO gradient + optimiser step, K problems      ->  gsmvi_advi_step_batched_f64
  *   advi.py:80-86 initial (loc, scales), :23-27 scales -> covariance    ->  gsmvi_advi_init_batched_f64, gsmvi_advi_cov_batched_f64
  *   examples/example_gsm.py:34-35 a model's log_prob and jit(grad(.)) of it, K logistic regressions -> gsmvi_logistic_batched_f64
+ *   examples/example_gsm.py:34-35 the same for K Poisson, probit or Gaussian regressions with offsets -> gsmvi_glm_batched_f64
  *   initializers.py:5-17 lbfgs_init (maximiser of lp, dense inverse-Hessian estimate), K problems -> gsmvi_lbfgs_step_batched_f64, gsmvi_lbfgs_hess_inv_batched_f64
  *   gsmvi/bam.py:72-114       bam_lowrank_update(samples,vs,mu0,S0,reg) ->  gsmvi_bam_update_f64
  *   gsmvi/bam.py:31-69        bam_update(samples,vs,mu0,S0,reg)         ->  gsmvi_bam_update_f64 (same result, K6)
@@ -459,6 +460,37 @@ int gsmvi_advi_cov_batched_f64(gsmvi_ctx* ctx, void* stream, int64_t K, int D, c
 int gsmvi_logistic_batched_f64(gsmvi_ctx* ctx, void* stream, int64_t K, int D, int nc, int64_t N, const double* A, const double* y,
                                const int* counts_dev, double prior_prec, const double* prior_prec_dev, const double* X, double* G,
                                double* lp);
+
+/*
+ * Batched GLM targets: the same launch for a family of generalised linear models.  examples/example_gsm.py:34-35, a model's
+ * log_prob and lp_g = jit(grad(...)) of it, for K Poisson, probit, Gaussian or logistic regressions of one (N, D) ->
+ * gsmvi_glm_batched_f64.  Everything is as in gsmvi_logistic_batched_f64 above except the link and the offset: with
+ * eta_n = a_n . x + o_kn (offset (K x N) on the device, NULL = no offset),
+ *   lp[k, c] = sum_{n < n_k} t(eta_n, y_n) - lam_k |x|^2 / 2,      G[k, c] = sum_{n < n_k} r(eta_n, y_n) a_n - lam_k x,
+ *   family                 y                    r = dt / d eta                               t
+ *   GSMVI_GLM_LOGISTIC     in [0, 1]            y - sigma(eta)                               y eta - softplus(eta)
+ *   GSMVI_GLM_POISSON      >= 0, finite         y - e^eta                                    y eta - e^eta   (log link; -log y! dropped)
+ *   GSMVI_GLM_PROBIT       in [0, 1]            y phi/Phi(eta) - (1 - y) phi/Phi(-eta)       y log Phi(eta) + (1 - y) log Phi(-eta)
+ *   GSMVI_GLM_GAUSSIAN     finite               tau_k (y - eta)                              -tau_k (y - eta)^2 / 2   (identity link)
+ * The probit link is evaluated from u = erfcx(|eta| / sqrt 2) and e = exp(-eta^2 / 2): log Phi(-|eta|) = log(u / 2) - eta^2 / 2,
+ * phi / Phi(-|eta|) = sqrt(2 / pi) / u, log Phi(|eta|) = log1p(-u e / 2), phi / Phi(|eta|) = e / sqrt(2 pi) / (1 - u e / 2): finite out
+ * to |eta| = 1e4.  The ranges of y are the caller's to keep (not checked here).  noise_prec / noise_prec_dev (NULL = the scalar,
+ * else K values tau_k on the device) belong to the Gaussian family, where the scalar must be finite and > 0; for any other
+ * family anything but 1.0 and NULL is GSMVI_ERR_BAD_ARG, as is an unknown family.  GSMVI_GLM_LOGISTIC with offset = NULL gives the
+ * bits of gsmvi_logistic_batched_f64.  The rules of that entry point hold: rows n >= n_k are never loaded, every output row sums
+ * n = 0 .. n_k - 1 in order in one thread (the same bits for any K, nc and neighbours), a row of X with a non-finite entry gets NaN
+ * outputs.  Poisson adds: a row of X for which some valid e^eta is not finite (eta above 709.78) gets NaN outputs in the same way,
+ * and no other row or problem is touched.  Checks (offset and noise_prec_dev are read-only arrays of the overlap rule) come
+ * before the context is looked at; inputs are only read; no context workspace.  Sets GSMVI_PATH_BATCHED_TARGET.
+ */
+#define GSMVI_GLM_LOGISTIC 0
+#define GSMVI_GLM_POISSON 1
+#define GSMVI_GLM_PROBIT 2
+#define GSMVI_GLM_GAUSSIAN 3
+int gsmvi_glm_batched_f64(gsmvi_ctx* ctx, void* stream, int64_t K, int D, int nc, int64_t N, int family, const double* A,
+                          const double* y, const double* offset, const int* counts_dev, double noise_prec,
+                          const double* noise_prec_dev, double prior_prec, const double* prior_prec_dev, const double* X, double* G,
+                          double* lp);
 
 /*
  * Batched L-BFGS initialiser (gsmvi/initializers.py:5-17 for K problems of one D): the minimiser of phi_k = -lp_k as the mean and

@@ -43,6 +43,13 @@ int gsmvi_debug_advi_batched_lds(int D, int B, int mode, size_t* bytes, int* pro
  * no device needed. */
 int gsmvi_debug_logistic_batched_lds(int D, int nc, int want, size_t* bytes, int* problems_per_workgroup);
 
+/* The same for a gsmvi_glm_batched_f64 launch of `family` (GSMVI_GLM_*) at (D, nc), with (has_offset != 0) or without an offset,
+ * by the rule the launch itself uses: the tile of the offset (32 doubles per problem) is there with an offset and, for
+ * GSMVI_GLM_POISSON, always.  Without the tile the figures are those of gsmvi_debug_logistic_batched_lds.  Host arithmetic only,
+ * no device needed. */
+int gsmvi_debug_glm_batched_lds(int D, int nc, int want, int family, int has_offset, size_t* bytes,
+                                int* problems_per_workgroup);
+
 /* The same for a batched L-BFGS launch at D: mode 0 = gsmvi_lbfgs_step_batched_f64, 1 = gsmvi_lbfgs_hess_inv_batched_f64.  Host
  * arithmetic only, no device needed. */
 int gsmvi_debug_lbfgs_batched_lds(int D, int mode, size_t* bytes, int* problems_per_workgroup);
