@@ -27,6 +27,9 @@ Mirrors the reference's public surface for the hot path (reference file:line):
     lbfgs_init_batched (the L-BFGS initialiser
     for K problems at once, D <= 64: one launch
     per function evaluation after lp_g and lp)   gsmvi/initializers.py:5-17
+    laplace_init_batched (the Newton mode and the
+    inverse Hessian of K GLM posteriors, D <= 64:
+    one launch per round, fp64-MFMA Gram product) gsmvi/initializers.py:5-17 (the role; no reference twin)
     lbfgs_init, ADVI (initialiser and the ELBO
     baseline of the examples; off the hot path)  gsmvi/initializers.py:5-17, gsmvi/advi.py:8-112
 All GSM / BaM numerics run in hand-written HIP kernels (libgsmvi_hip.so, C ABI in include/gsmvi_hip.h)
@@ -46,6 +49,7 @@ from .batched import BaMBatch, bam_update_batched, bam_lowrank_update_batched   
 from .batched import ADVIBatch, Adam                                 # noqa: F401
 from .monitors import KLMonitor, DeviceKLMonitor, BatchedKLMonitor   # noqa: F401
 from .initializers import lbfgs_init, lbfgs_init_batched, LbfgsBatchedResult   # noqa: F401
+from .initializers import laplace_init_batched, LaplaceBatchedResult          # noqa: F401
 from .advi import ADVI                                               # noqa: F401
 
 __version__ = "0.1.0"

@@ -123,6 +123,11 @@ _SIGS = {
                                                _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, C.c_int, C.c_int, C.c_double,
                                                C.c_double]),
     "gsmvi_lbfgs_hess_inv_batched_f64": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, _c_dp, _c_dp, _c_dp, _c_dp]),
+    "gsmvi_glm_hessian_batched_f64": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int64, C.c_int, _c_dp, _c_dp, _c_dp,
+                                                _c_dp, C.c_double, _c_dp, C.c_double, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp]),
+    "gsmvi_laplace_step_batched_f64": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int64, C.c_int, _c_dp, _c_dp, _c_dp,
+                                                 _c_dp, C.c_double, _c_dp, C.c_double, _c_dp, C.c_int, _c_dp, _c_dp, _c_dp, _c_dp,
+                                                 _c_dp, _c_dp, _c_dp, C.c_int, C.c_int, C.c_double]),
     "gsmvi_commit_f64": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, _c_dp, _c_dp, _c_dp, C.c_int, _c_dp, _c_dp,
                                    C.c_int, _c_dp]),
     "gsmvi_bam_update_f64": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, _c_dp, C.c_int, _c_dp, C.c_int,

@@ -1,0 +1,598 @@
+// Batched Laplace initialiser: the negative Hessian of K GLM posteriors of one (N, D), D <= 64, its inverse, and one damped
+// Newton (IRLS) round per launch for every running problem ("Batched Laplace initialiser").
+//
+// The reference has no Laplace initialiser: it starts its fits from the L-BFGS-B maximiser of lp and the optimiser's dense
+// inverse-Hessian estimate (gsmvi/initializers.py:5-17), for a model given as log_prob and jit(grad(...)) of it
+// (examples/example_gsm.py:34-35).  For the four GLM families of gsmvi_glm_batched_f64 the second derivative is closed-form:
+// with eta_n = a_n . x + o_kn and the weight w = -dr / d eta of gsmvi_glm_link.h,
+//   H_k(x) = sum_{n < n_k} w(eta_n, y_n) a_n a_n^T + lam_k I          (the negative Hessian of lp_k: positive semi-definite)
+// and the Newton direction of phi = -lp is d = -H^{-1} g, g = -score.
+//   k_laplace_batched<NT, FAM, LP_HESS> : H_k at the rows of X, cov_k = H_k^{-1} and info_k
+//   k_laplace_batched<NT, FAM, LP_STEP> : f, g and H at the trial point Xt_k in ONE sweep over A_k, then the accept / reject
+//                                         decision of the line search, the stopping tests, the factorisation, d, and the next
+//                                         trial point
+// Work mapping: the slots of gsmvi_batched.h (gb_nt(D) threads per problem, four problems -- one wave each -- per 256-thread
+// workgroup for D <= 16).  A slot walks the rows of A_k in tiles of LB_TN = 32, staged in LDS zero-padded to Dp = 16 ceil(D / 16)
+// columns (row stride Dp + 1) and to 32 rows; the next tile's loads are in flight while the current one is consumed, as in
+// k_logistic_batched.  Per tile: NT / 32 adjacent lanes share a row's eta (a butterfly over them), one of them applies the link
+// and leaves r, t, w of the row in LDS; then the Gram product runs on the fp64 MFMA (16 x 16 x 4): for the 16 x 16 block (bi, bj),
+// bi <= bj, of H the A operand is w_n a_{n, 16 bi + c} and the B operand a_{n, 16 bj + c}, both from the tile, eight steps per
+// tile, and the accumulators (at most three blocks per wave: ten blocks of the upper triangle over four waves at Dp = 64) stay in
+// registers across all of N.  Thread j < D sums g_j = sum_n r_n a_nj over the tile's rows in order, one thread sums t.
+// After the sweep the upper triangle (i <= j; of a diagonal block too: (w a_i) a_j and (w a_j) a_i round differently) goes to LDS,
+// lam is added to the diagonal, and H is written mirrored: exactly symmetric.  The Cholesky factorisation is the right-looking
+// one of gb_chol_lds with a relative pivot rule: pivot j fails when it is not finite or not > 64 eps H_jj, so a rank-deficient
+// H fails whatever the rounding.  The Newton direction is two triangular solves in the slot's first wave (component l in lane
+// l, one broadcast per column).  The inverse is R^{-1} R^{-T}: thread j back-substitutes column j of R^{-1} into row j of the
+// (free) lower triangle, then entry (i, j), i <= j, is one dot product, written to (i, j) and (j, i).
+// Order: every sum over n runs n = 0 .. n_k - 1 in tiles of 32, eight MFMA steps of four rows per tile; it depends on (N, D)
+// alone, not on K, the slot packing or the neighbours.  Rows n >= n_k are never loaded.  A slot reads and writes only slice k of
+// every array and every slot of a workgroup runs the same barriers.  A problem whose status is not 0 is frozen: its slot loads
+// nothing of A_k, does none of the per-tile work (as every slot does for the tiles past n_k) and writes nothing; it still runs
+// the barriers of the sweep beside its running neighbours.  A workgroup all of whose problems are frozen leaves at once.
+// Ordering in the Hessian entry: H is written from LDS (the lower triangle from the mirrored cells, which other threads own),
+// then a barrier, then the factorisation overwrites those cells in place.  Inputs are only read; no context workspace.
+#include "gsmvi_common.h"
+#include "gsmvi_ctx.h"
+#include "gsmvi_batched.h"
+#include "gsmvi_glm_link.h"
+#include "../../include/gsmvi_hip.h"
+#include <cmath>
+#include <cstdint>
+
+#define LP_NSC 4       // doubles per problem in sc
+#define LP_NIS 8       // ints per problem in ist
+#define LP_AQ 8        // tile elements per thread: LB_TN D / NT <= 8 in both packings
+#define LP_PIVOT_REL 1.4210854715202004e-14   // 64 eps
+enum { LP_F = 0, LP_T = 1, LP_GD = 2 };
+enum { LP_STATUS = 0, LP_NIT = 1, LP_NFEV = 2, LP_NLS = 3 };
+enum { LP_HESS = 0, LP_STEP = 1 };
+
+struct lp_args {
+    long long K, N;
+    int D, start;
+    const double* A;            // (K, N, D)
+    const double* y;            // (K, N)
+    const double* offset;       // (K, N) or null
+    const int* counts;          // (K) valid rows, clamped to 0 .. N (null: N)
+    double lam;
+    const double* lam_dev;
+    double tau;
+    const double* tau_dev;
+    // LP_HESS
+    const double* X;            // (K, D)
+    double* H;                  // (K, D, D) or null
+    double* cov;                // (K, D, D) or null
+    int* info;                  // (K), with cov
+    // LP_STEP: the state
+    double* x;                  // (K, D)
+    double* g;                  // (K, D)
+    double* d;                  // (K, D)
+    double* sc;                 // (K, 4)
+    int* ist;                   // (K, 8)
+    double* Xt;                 // (K, D)
+    int* stopped;               // (1) or null
+    int maxiter, maxfun;
+    double gtol;
+};
+
+__host__ __device__ inline int lp_dp(int D) { return ((D + 15) >> 4) << 4; }
+// LDS doubles per problem: the A tile (32 x (Dp + 1)), y, offset, r, w, t of its rows (32 each), x, g, pivots, the diagonal of H
+// and the diagonal of R^{-1} (Dp each), four cells, H (D x (D | 1)).  D = 64: 6724 doubles, 52.5 KB; four problems of D = 16: 33 KB
+__host__ __device__ inline int lp_lds_doubles(int D) {
+    const int Dp = lp_dp(D);
+    return LB_TN * (Dp + 1) + 5 * LB_TN + 5 * Dp + 4 + D * (D | 1);
+}
+
+__device__ __forceinline__ double lp_wave_sum(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    return v;
+}
+
+__device__ __forceinline__ double lp_wave_max(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o));
+    return v;
+}
+
+__device__ __forceinline__ bool lp_finite(double v) { return fabs(v) < __builtin_huge_val(); }
+
+// gb_chol_lds with the relative pivot rule (dg: the diagonal of S before the factorisation): 0, or 1 + the first pivot that is
+// not finite or not > 64 eps dg[c].  `on` is uniform in the slot; every slot runs the D barriers.
+template <int NT, int MAXE>
+__device__ __forceinline__ int lp_chol_lds(bool on, int D, int l, int ld, double* S, double* pv, const double* dg) {
+    const int DD = D * D;
+    int info = 0;
+    for (int c = 0; c < D; ++c) {
+        if (on) {
+            const double acc_ = S[c * ld + c];
+            if (info == 0 && !(acc_ > LP_PIVOT_REL * dg[c] && acc_ < __builtin_huge_val())) info = c + 1;
+            const double piv = sqrt(acc_), inv = 1.0 / piv;
+            if (l == 0) pv[c] = piv;
+#pragma unroll
+            for (int q = 0; q < MAXE; ++q) {
+                const int e = l + q * NT;
+                if (e < DD) {
+                    const int i = e / D, j = e - i * D;
+                    if (i > c && j >= i) S[i * ld + j] -= (S[c * ld + i] * inv) * (S[c * ld + j] * inv);
+                }
+            }
+        }
+        __syncthreads();
+    }
+    if (on) {
+#pragma unroll
+        for (int q = 0; q < MAXE; ++q) {
+            const int e = l + q * NT;
+            if (e < DD) {
+                const int i = e / D, j = e - i * D;
+                if (j > i) S[i * ld + j] = S[i * ld + j] / pv[i];
+                else if (j == i) S[i * ld + j] = pv[i];
+            }
+        }
+    }
+    __syncthreads();
+    return info;
+}
+
+template <int NT, int FAM, int MODE>
+__global__ __launch_bounds__(256) void k_laplace_batched(lp_args a) {
+    extern __shared__ double lp_sm[];
+    constexpr int PPW = 256 / NT, NW = NT / 64, NG = NT / LB_TN;
+    constexpr int MAXT = NT == 256 ? 3 : 1;       // 16 x 16 blocks of H per wave
+    constexpr int MAXE = NT == 256 ? 16 : 4;      // entries of H per thread
+    constexpr bool STEP = MODE == LP_STEP;
+    const int D = a.D, nb = (D + 15) >> 4, Dp = nb * 16, lda = Dp + 1, ldh = D | 1, DD = D * D;
+    const long long N = a.N;
+    const int slot = threadIdx.x / NT, l = threadIdx.x % NT;
+    const long long k = (long long)blockIdx.x * PPW + slot;
+    const bool valid = k < a.K;
+    const size_t kk = (size_t)(valid ? k : 0), kd = kk * D;
+    double* As = lp_sm + (size_t)slot * lp_lds_doubles(D);
+    double* Ys = As + LB_TN * lda;
+    double* Os = Ys + LB_TN;
+    double* Rs = Os + LB_TN;
+    double* Ws = Rs + LB_TN;
+    double* Ts = Ws + LB_TN;
+    double* xs = Ts + LB_TN;                  // Dp  the point (zeros beyond D)
+    double* gs = xs + Dp;                     // Dp  g = -score there
+    double* pv = gs + Dp;                     // Dp  pivots R_cc
+    double* dg = pv + Dp;                     // Dp  the diagonal of H
+    double* rd = dg + Dp;                     // Dp  the diagonal of R^{-1}
+    double* cell = rd + Dp;                   // [0] NaN when a poisson row is flagged, [1] f
+    double* Hs = cell + 4;                    // D x ldh
+    const double qnan = __longlong_as_double(0x7ff8000000000000LL);
+
+    int* is = STEP ? a.ist + kk * LP_NIS : nullptr;
+    double* sc = STEP ? a.sc + kk * LP_NSC : nullptr;
+    int status = 0, nit = 0, nfev = 0, nls = 0;
+    double f = 0.0, t = 0.0, gd = 0.0;
+    bool live = valid;
+    if (STEP) {
+        if (valid && !a.start) {
+            status = is[LP_STATUS]; nit = is[LP_NIT]; nfev = is[LP_NFEV]; nls = is[LP_NLS];
+            f = sc[LP_F]; t = sc[LP_T]; gd = sc[LP_GD];
+        }
+        live = valid && status == 0;
+        if (!__syncthreads_or(live)) return;  // every problem of the workgroup is frozen (uniform)
+    }
+
+    const double* Ak = a.A + kk * (size_t)N * D;
+    const double* yk = a.y + kk * (size_t)N;
+    const double* ok_ = a.offset ? a.offset + kk * (size_t)N : nullptr;
+    long long nk = 0;                         // the rows that count (a frozen slot: none, so nothing of A_k is loaded)
+    double lam = 0.0, tau = 1.0;
+    if (live) {
+        nk = N;
+        if (a.counts) {
+            const long long c = a.counts[k];
+            nk = c < 0 ? 0 : (c > N ? N : c);
+        }
+        lam = a.lam_dev ? a.lam_dev[k] : a.lam;
+        if (FAM == LB_GAUSSIAN) tau = a.tau_dev ? a.tau_dev[k] : a.tau;
+    }
+    for (int e = l; e < LB_TN * lda; e += NT) As[e] = 0.0;          // the padding columns stay zero
+    if (l < Dp) {
+        const double* xsrc = STEP ? a.Xt : a.X;
+        xs[l] = live && l < D ? xsrc[kd + l] : 0.0;
+    }
+    if (l == 0) cell[0] = 0.0;
+    __syncthreads();                          // the zeros are in place before any thread writes the first tile
+
+    // the blocks of the upper triangle that this wave accumulates: block w + q NW in the order (0,0) (0,1) .. (0,nb-1) (1,1) ..
+    const int wv = l >> 6, ln = l & 63, cc = ln & 15, ks = ln >> 4, ntiles = nb * (nb + 1) / 2;
+    int ti[MAXT], tj[MAXT];
+    v4d acc[MAXT];
+#pragma unroll
+    for (int q = 0; q < MAXT; ++q) {
+        int tt = wv + q * NW, bi = 0;
+        if (tt >= ntiles) {
+            ti[q] = -1;
+            tj[q] = 0;
+        } else {
+            while (tt >= nb - bi) {
+                tt -= nb - bi;
+                ++bi;
+            }
+            ti[q] = 16 * bi;
+            tj[q] = 16 * (bi + tt);
+        }
+        acc[q] = v4d{0.0, 0.0, 0.0, 0.0};
+    }
+    // the tile elements e = l + q NT of this thread as (row, column), stepped without a division
+    const int row0 = l / D, col0 = l - row0 * D, dr = NT / D, dc = NT - dr * D;
+    const int en = l / NG, eg = l % NG;       // the eta pass: row en of the tile, columns eg, eg + NG, ..
+
+    double pre[LP_AQ], ypre = 0.0, opre = 0.0;
+    {
+        const int tnv = (int)(nk < LB_TN ? nk : LB_TN), te = tnv * D;
+#pragma unroll
+        for (int q = 0; q < LP_AQ; ++q) {
+            const int e = l + q * NT;
+            pre[q] = e < te ? Ak[e] : 0.0;
+        }
+        if (l < tnv) {
+            ypre = yk[l];
+            if (ok_) opre = ok_[l];
+        }
+    }
+    double gacc = 0.0, facc = 0.0;
+
+    for (long long n0 = 0; n0 < N; n0 += LB_TN) {
+        const long long left = nk - n0;
+        const int tnv = left < 0 ? 0 : (int)(left < LB_TN ? left : LB_TN);
+        // a tile without a row that counts (past n_k; every tile of a frozen slot) does none of the work below: it only runs
+        // the barriers, which must stay uniform across the slots of a workgroup (tnv is uniform in the slot)
+        if (tnv > 0) {                        // registers -> LDS: the whole tile, zeros in the rows that do not count
+            int r = row0, c = col0;
+#pragma unroll
+            for (int q = 0; q < LP_AQ; ++q) {
+                if (l + q * NT < LB_TN * D) As[r * lda + c] = pre[q];
+                r += dr;
+                c += dc;
+                if (c >= D) {
+                    c -= D;
+                    ++r;
+                }
+            }
+            if (l < LB_TN) {
+                Ys[l] = ypre;
+                Os[l] = opre;
+            }
+        }
+        __syncthreads();
+        {                                     // the next tile's loads: in flight while this one is consumed
+            const long long left2 = left - LB_TN;
+            const int tnv2 = left2 < 0 ? 0 : (int)(left2 < LB_TN ? left2 : LB_TN), te2 = tnv2 * D;
+            const double* An = Ak + (size_t)(n0 + LB_TN) * D;
+#pragma unroll
+            for (int q = 0; q < LP_AQ; ++q) {
+                const int e = l + q * NT;
+                pre[q] = e < te2 ? An[e] : 0.0;
+            }
+            ypre = 0.0;
+            opre = 0.0;
+            if (l < tnv2) {
+                ypre = yk[n0 + LB_TN + l];
+                if (ok_) opre = ok_[n0 + LB_TN + l];
+            }
+        }
+        if (tnv > 0) {                        // eta of row en: NG adjacent lanes take the columns eg + i NG, then a butterfly
+            const double* ar = As + en * lda;
+            double eta = 0.0;
+            for (int j = eg; j < D; j += NG) eta = fma(ar[j], xs[j], eta);
+#pragma unroll
+            for (int o = NG / 2; o > 0; o >>= 1) eta += __shfl_xor(eta, o);
+            eta += Os[en];
+            if (eg == 0) {
+                double r = 0.0, tt = 0.0, w = 0.0;
+                const double yv = Ys[en];
+                bool fine = lb_weight<FAM>(eta, yv, tau, w);
+                if (STEP) fine = lb_link<FAM, true, true>(eta, yv, tau, r, tt) && fine;
+                const bool on = en < tnv;
+                Ws[en] = on ? w : 0.0;
+                if (STEP) {
+                    Rs[en] = on ? r : 0.0;
+                    Ts[en] = on ? tt : 0.0;
+                }
+                if (FAM == LB_POISSON && on && !fine) cell[0] = qnan;   // (any number of threads, the same value)
+            }
+        }
+        __syncthreads();
+#pragma unroll
+        for (int q = 0; q < MAXT; ++q) {
+            if (ti[q] >= 0 && tnv > 0) {      // (wave-uniform)
+                const double* pa = As + ks * lda + ti[q] + cc;
+                const double* pb = As + ks * lda + tj[q] + cc;
+#pragma unroll
+                for (int s = 0; s < LB_TN / 4; ++s) {
+                    const double av = Ws[4 * s + ks] * pa[4 * s * lda], bv = pb[4 * s * lda];
+                    acc[q] = GSMVI_MFMA_F64(av, bv, acc[q]);
+                }
+            }
+        }
+        if (STEP) {
+            if (l < D)
+                for (int n = 0; n < tnv; ++n) gacc = fma(Rs[n], As[n * lda + l], gacc);
+            if (l == NT - 1)
+                for (int n = 0; n < tnv; ++n) facc += Ts[n];
+        }
+        __syncthreads();                      // the next tile overwrites As, Ys, Os, Rs, Ws, Ts
+    }
+
+    // the upper triangle of sum_n w a a^T -> LDS, g and f of phi = -lp
+#pragma unroll
+    for (int q = 0; q < MAXT; ++q) {
+        if (ti[q] >= 0) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int i = ti[q] + ks + 4 * r, j = tj[q] + cc;
+                if (i <= j && j < D) Hs[i * ldh + j] = acc[q][r];
+            }
+        }
+    }
+    if (STEP) {
+        if (l < Dp) gs[l] = l < D ? -(gacc - lam * xs[l]) : 0.0;
+        if (l == NT - 1) {
+            double xx = 0.0;
+            for (int j = 0; j < D; ++j) xx += xs[j] * xs[j];
+            cell[1] = -(facc - 0.5 * lam * xx);
+        }
+    }
+    __syncthreads();
+    if (l < D) {
+        const double v = Hs[l * ldh + l] + lam;
+        Hs[l * ldh + l] = v;
+        dg[l] = v;
+    }
+    __syncthreads();
+    // a non-finite x or a flagged poisson row (uniform in the slot: every wave forms it from the same numbers)
+    const bool bad = !(lp_wave_sum(ln < D ? xs[ln] * 0.0 : 0.0) == 0.0) || !(cell[0] == 0.0);
+
+    double ft = 0.0, gtl = 0.0, gmax = 0.0;
+    bool fin = false, ok = false, need = false;
+    if (STEP) {
+        ft = bad ? qnan : cell[1];
+        gtl = ln < D ? (bad ? qnan : gs[ln]) : 0.0;
+        fin = !bad && lp_finite(ft) && __all(lp_finite(gtl));
+        gmax = lp_wave_max(fabs(gtl));
+        if (live) {
+            if (a.start)
+                need = fin && !(gmax <= a.gtol);
+            else {
+                ok = fin && ft <= (f + (1e-4 * t) * gd) + 1e-10 * fmax(1.0, fabs(f));
+                need = ok && !(gmax <= a.gtol) && !(nit + 1 >= a.maxiter || nfev + 1 >= a.maxfun);
+            }
+        }
+    } else {
+        need = live && !bad && a.cov != nullptr;
+        if (live && a.H) {
+#pragma unroll
+            for (int q = 0; q < MAXE; ++q) {
+                const int e = l + q * NT;
+                if (e < DD) {
+                    const int i = e / D, j = e - i * D;
+                    a.H[kk * DD + e] = bad ? qnan : (i <= j ? Hs[i * ldh + j] : Hs[j * ldh + i]);
+                }
+            }
+        }
+        // entry (i, j), i > j, was read from another thread's cell (j, i): every read of H is done before the factorisation
+        // below starts to overwrite it in place
+        __syncthreads();
+    }
+
+    int info = lp_chol_lds<NT, MAXE>(need, D, l, ldh, Hs, pv, dg);     // (its last barrier publishes R and the pivots)
+
+    if (!STEP) {
+        if (!a.cov) return;                   // (uniform)
+        if (live && bad) info = 1;
+        const bool inv = need && info == 0;
+        if (inv && l < D) {                   // column l of R^{-1} into row l of the lower triangle, its diagonal into rd
+            const int j = l;
+            const double xj = 1.0 / pv[j];
+            rd[j] = xj;
+            for (int i = j - 1; i >= 0; --i) {
+                double s = 0.0;
+                for (int c = i + 1; c < j; ++c) s += Hs[i * ldh + c] * Hs[j * ldh + c];
+                s += Hs[i * ldh + j] * xj;
+                Hs[j * ldh + i] = -s / pv[i];
+            }
+        }
+        __syncthreads();
+        if (live) {
+#pragma unroll
+            for (int q = 0; q < MAXE; ++q) {
+                const int e = l + q * NT;
+                if (e < DD) {
+                    const int i = e / D, j = e - i * D;
+                    if (i <= j) {
+                        double s;
+                        if (inv) {
+                            s = (i == j ? rd[j] : Hs[j * ldh + i]) * rd[j];
+                            for (int c = j + 1; c < D; ++c) s += Hs[c * ldh + i] * Hs[c * ldh + j];
+                        } else
+                            s = i == j ? 1.0 : 0.0;                     // nothing is known: the identity
+                        a.cov[kk * DD + e] = s;
+                        a.cov[kk * DD + (size_t)j * D + i] = s;
+                    }
+                }
+            }
+            if (l == 0) a.info[k] = info;
+        }
+        return;
+    }
+
+    if (!live || l >= 64) return;             // the rest is the first wave's: component l of every vector in lane l
+    const bool act = l < D;
+    double xl = act ? xs[l] : 0.0, gl = gtl, dl = 0.0;
+    bool newdir = false;
+    if (a.start) {
+        nfev = 1;
+        nit = 0;
+        nls = 0;
+        f = ft;
+        t = 0.0;
+        gd = 0.0;
+        if (!fin) status = 4;
+        else if (gmax <= a.gtol) status = 1;
+        else if (info != 0) status = 5;
+        else newdir = true;
+    } else {
+        nfev += 1;
+        if (!ok) {
+            t = 0.5 * t;
+            nls += 1;
+            if (nls > 20) status = 3;
+            else if (nfev >= a.maxfun) status = 2;
+            else if (act) a.Xt[kd + l] = a.x[kd + l] + t * a.d[kd + l];
+            if (l == 0) {
+                sc[LP_T] = t;
+                is[LP_NLS] = nls; is[LP_NFEV] = nfev; is[LP_STATUS] = status;
+                if (status != 0 && a.stopped) atomicAdd(a.stopped, 1);
+            }
+            return;
+        }
+        f = ft;
+        nit += 1;
+        if (gmax <= a.gtol) status = 1;
+        else if (nit >= a.maxiter || nfev >= a.maxfun) status = 2;
+        else if (info != 0) status = 5;
+        else newdir = true;
+    }
+    if (newdir) {                             // d = -H^{-1} g: R^T z = g, R s = z (R upper, R^T R = H)
+        double b = gl;
+        for (int c = 0; c < D; ++c) {
+            const double zc = __shfl(b, c) / pv[c];
+            if (l == c) b = zc;
+            else if (l > c && act) b -= Hs[c * ldh + l] * zc;
+        }
+        for (int c = D - 1; c >= 0; --c) {
+            const double sc_ = __shfl(b, c) / pv[c];
+            if (l == c) b = sc_;
+            else if (l < c) b -= Hs[l * ldh + c] * sc_;
+        }
+        dl = act ? -b : 0.0;
+        t = 1.0;
+        gd = lp_wave_sum(gl * dl);
+        nls = 0;
+    }
+    if (act) {
+        a.x[kd + l] = xl;
+        a.g[kd + l] = gl;
+        if (newdir || a.start) a.d[kd + l] = dl;
+        if (newdir) a.Xt[kd + l] = xl + dl;
+    }
+    if (l == 0) {
+        sc[LP_F] = f;
+        if (newdir || a.start) {
+            sc[LP_T] = t;
+            sc[LP_GD] = gd;
+        }
+        if (a.start) sc[3] = 0.0;
+        is[LP_STATUS] = status; is[LP_NIT] = nit; is[LP_NFEV] = nfev; is[LP_NLS] = nls;
+        if (a.start) { is[4] = 0; is[5] = 0; is[6] = 0; is[7] = 0; }
+        if (status != 0 && a.stopped) atomicAdd(a.stopped, 1);
+    }
+}
+
+// dynamic LDS bytes of a launch at D: at most 52.5 KB, below the default limit of 64 KB, so no kernel attribute is needed
+static size_t lp_launch_lds(int D, int* ppw) {
+    *ppw = 256 / gb_nt(D);
+    return (size_t)*ppw * lp_lds_doubles(D) * sizeof(double);
+}
+
+template <int MODE>
+static void lp_go(int family, int ppw, unsigned grid, size_t lds, hipStream_t st, const lp_args& a) {
+#define LP_GO(FAM)                                                                                       \
+    do {                                                                                                 \
+        if (ppw == 4)                                                                                    \
+            hipLaunchKernelGGL((k_laplace_batched<64, FAM, MODE>), dim3(grid), dim3(256), lds, st, a);   \
+        else                                                                                             \
+            hipLaunchKernelGGL((k_laplace_batched<256, FAM, MODE>), dim3(grid), dim3(256), lds, st, a);  \
+    } while (0)
+    switch (family) {
+        case GSMVI_GLM_LOGISTIC: LP_GO(LB_LOGISTIC); break;
+        case GSMVI_GLM_POISSON: LP_GO(LB_POISSON); break;
+        case GSMVI_GLM_PROBIT: LP_GO(LB_PROBIT); break;
+        default: LP_GO(LB_GAUSSIAN); break;
+    }
+#undef LP_GO
+}
+
+// the checks that both entry points share with gsmvi_glm_batched_f64: shapes, the family and its noise precision, the prior
+static int lp_check_model(const char* fn, int64_t K, int D, int64_t N, int family, double noise_prec, const double* noise_prec_dev,
+                          double prior_prec, const double* prior_prec_dev) {
+#define LP_BAD(cond, msg)                     \
+    do {                                      \
+        if (cond) return gb_bad(fn, msg);     \
+    } while (0)
+    if (int st = gb_check_shape(fn, K, D, gb_ppw)) return st;
+    LP_BAD(N < 1, "N must be at least 1");
+    LP_BAD(N > (INT64_MAX / 8 / D) / K, "K N D is too large");
+    LP_BAD(family < GSMVI_GLM_LOGISTIC || family > GSMVI_GLM_GAUSSIAN, "family must be one of GSMVI_GLM_LOGISTIC .. GSMVI_GLM_GAUSSIAN");
+    LP_BAD(!prior_prec_dev && !(prior_prec >= 0.0 && prior_prec < __builtin_huge_val()), "prior_prec must be finite and >= 0");
+    if (family == GSMVI_GLM_GAUSSIAN)
+        LP_BAD(!noise_prec_dev && !(noise_prec > 0.0 && noise_prec < __builtin_huge_val()), "noise_prec must be finite and > 0");
+    else
+        LP_BAD(noise_prec_dev || noise_prec != 1.0, "noise_prec is the gaussian family's: give 1.0 and NULL for any other");
+#undef LP_BAD
+    return GSMVI_OK;
+}
+
+extern "C" {
+
+int gsmvi_glm_hessian_batched_f64(gsmvi_ctx* ctx, void* stream, int64_t K, int D, int64_t N, int family, const double* A,
+                                  const double* y, const double* offset, const int* counts_dev, double noise_prec,
+                                  const double* noise_prec_dev, double prior_prec, const double* prior_prec_dev, const double* X,
+                                  double* H, double* cov, int* info_dev) {
+    if (int st = lp_check_model(__func__, K, D, N, family, noise_prec, noise_prec_dev, prior_prec, prior_prec_dev)) return st;
+    GB_BAD(!A || !y || !X, "NULL array");
+    GB_BAD(!H && !cov, "give H or cov (or both)");
+    GB_BAD((cov != nullptr) != (info_dev != nullptr), "info_dev is required with cov and only with it");
+    const size_t na = (size_t)K * N * D * 8, ny = (size_t)K * N * 8, nx = (size_t)K * D * 8, nh = nx * D, nk = (size_t)K * 8,
+                 ni = (size_t)K * 4;
+    if (int st = gb_check_overlaps(__func__, {{A, na, "A", GB_RD}, {y, ny, "y", GB_RD}, {offset, ny, "offset", GB_RD},
+                                              {counts_dev, ni, "counts_dev", GB_RD}, {noise_prec_dev, nk, "noise_prec_dev", GB_RD},
+                                              {prior_prec_dev, nk, "prior_prec_dev", GB_RD}, {X, nx, "X", GB_RD}, {H, nh, "H", GB_WR},
+                                              {cov, nh, "cov", GB_WR}, {info_dev, ni, "info_dev", GB_WR}}))
+        return st;
+    GB_BAD(!ctx, "ctx is NULL");
+    lp_args a = {};
+    a.K = K; a.N = N; a.D = D; a.A = A; a.y = y; a.offset = offset; a.counts = counts_dev; a.lam = prior_prec;
+    a.lam_dev = prior_prec_dev; a.tau = noise_prec; a.tau_dev = noise_prec_dev; a.X = X; a.H = H; a.cov = cov; a.info = info_dev;
+    int ppw;
+    const size_t lds = lp_launch_lds(D, &ppw);
+    lp_go<LP_HESS>(family, ppw, (unsigned)((K + ppw - 1) / ppw), lds, reinterpret_cast<hipStream_t>(stream), a);
+    return gb_launched(ctx, GSMVI_PATH_BATCHED_LAPLACE, "k_laplace_batched");
+}
+
+int gsmvi_laplace_step_batched_f64(gsmvi_ctx* ctx, void* stream, int64_t K, int D, int64_t N, int family, const double* A,
+                                   const double* y, const double* offset, const int* counts_dev, double noise_prec,
+                                   const double* noise_prec_dev, double prior_prec, const double* prior_prec_dev, int start,
+                                   double* x, double* g, double* d, double* sc, int* ist, double* Xt, int* stopped_dev, int maxiter,
+                                   int maxfun, double gtol) {
+    if (int st = lp_check_model(__func__, K, D, N, family, noise_prec, noise_prec_dev, prior_prec, prior_prec_dev)) return st;
+    GB_BAD(!A || !y || !x || !g || !d || !sc || !ist || !Xt, "NULL array");
+    GB_BAD(maxiter < 1 || maxfun < 2, "maxiter must be at least 1 and maxfun at least 2");
+    GB_BAD(!(gtol >= 0.0), "gtol must be >= 0");
+    const size_t na = (size_t)K * N * D * 8, ny = (size_t)K * N * 8, nv = (size_t)K * D * 8, nk = (size_t)K * 8, ni = (size_t)K * 4;
+    if (int st = gb_check_overlaps(__func__, {{A, na, "A", GB_RD}, {y, ny, "y", GB_RD}, {offset, ny, "offset", GB_RD},
+                                              {counts_dev, ni, "counts_dev", GB_RD}, {noise_prec_dev, nk, "noise_prec_dev", GB_RD},
+                                              {prior_prec_dev, nk, "prior_prec_dev", GB_RD}, {x, nv, "x", GB_WR}, {g, nv, "g", GB_WR},
+                                              {d, nv, "d", GB_WR}, {sc, (size_t)K * LP_NSC * 8, "sc", GB_WR},
+                                              {ist, (size_t)K * LP_NIS * 4, "ist", GB_WR}, {Xt, nv, "Xt", GB_WR},
+                                              {stopped_dev, 4, "stopped_dev", GB_WR}}))
+        return st;
+    GB_BAD(!ctx, "ctx is NULL");
+    lp_args a = {};
+    a.K = K; a.N = N; a.D = D; a.start = start != 0; a.A = A; a.y = y; a.offset = offset; a.counts = counts_dev; a.lam = prior_prec;
+    a.lam_dev = prior_prec_dev; a.tau = noise_prec; a.tau_dev = noise_prec_dev; a.x = x; a.g = g; a.d = d; a.sc = sc; a.ist = ist;
+    a.Xt = Xt; a.stopped = stopped_dev; a.maxiter = maxiter; a.maxfun = maxfun; a.gtol = gtol;
+    int ppw;
+    const size_t lds = lp_launch_lds(D, &ppw);
+    lp_go<LP_STEP>(family, ppw, (unsigned)((K + ppw - 1) / ppw), lds, reinterpret_cast<hipStream_t>(stream), a);
+    return gb_launched(ctx, GSMVI_PATH_BATCHED_LAPLACE, "k_laplace_batched");
+}
+
+}  // extern "C"

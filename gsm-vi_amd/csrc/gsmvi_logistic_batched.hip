@@ -38,15 +38,12 @@
 #include "gsmvi_common.h"
 #include "gsmvi_ctx.h"
 #include "gsmvi_batched.h"
+#include "gsmvi_glm_link.h"                  // lb_link, the families, LB_TN
 #include "../../include/gsmvi_hip.h"
 #include "../../include/gsmvi_hip_debug.h"   // gsmvi_debug_logistic_batched_lds
 #include <cstdint>
 #include <type_traits>
 
-enum { LB_G = 1, LB_LP = 2 };
-enum { LB_LOGISTIC = GSMVI_GLM_LOGISTIC, LB_POISSON = GSMVI_GLM_POISSON, LB_PROBIT = GSMVI_GLM_PROBIT,
-       LB_GAUSSIAN = GSMVI_GLM_GAUSSIAN };
-#define LB_TN 32   // rows of A_k per tile
 #define LB_AQ 8    // tile elements per thread: LB_TN D / NT <= 8 in both packings
 
 struct lb_args {
@@ -74,47 +71,6 @@ __host__ __device__ inline int lb_tc(int NT) { return NT == 256 ? 32 : 16; }
 __host__ __device__ inline int lb_lds_doubles(int D, int tcm, int want, bool off = false) {
     return LB_TN * (D | 1) + LB_TN + (off ? LB_TN : 0) +
            tcm * ((D | 1) + 1 + (LB_TN | 1) * ((want & LB_G ? 1 : 0) + (want & LB_LP ? 1 : 0)));
-}
-
-// The link of family FAM at eta = h, label y (tau: the gaussian noise precision): r = d t / d eta and t, each evaluated only
-// when wanted.  Returns false when the row of X must be flagged (poisson: e^eta is not finite); what r and t then hold reaches
-// no output, the flag replaces every output of the row.
-template <int FAM, bool HAS_G, bool HAS_LP>
-__device__ __forceinline__ bool lb_link(double h, double y, double tau, double& r, double& t) {
-    if constexpr (FAM == LB_LOGISTIC) {
-        const double e = exp(-fabs(h)), d = 1.0 + e;
-        if (HAS_G) r = y - (h >= 0.0 ? 1.0 / d : e / d);
-        if (HAS_LP) t = y * h - ((h > 0.0 ? h : 0.0) + log1p(e));
-        return true;
-    } else if constexpr (FAM == LB_POISSON) {
-        const double m = exp(h);
-        if (HAS_G) r = y - m;
-        if (HAS_LP) t = y * h - m;
-        return m < __builtin_huge_val();                   // (false for a NaN too)
-    } else if constexpr (FAM == LB_PROBIT) {
-        // s = |eta|, u = erfcx(s / sqrt 2), e = exp(-s^2 / 2), q = u e / 2 = Phi(-s).  Tail side: log Phi(-s) = log(u / 2) - s^2 / 2,
-        // phi / Phi(-s) = sqrt(2 / pi) / u.  Central side: log Phi(s) = log1p(-q), phi / Phi(s) = e / sqrt(2 pi) / (1 - q).
-        const double s = fabs(h), u = erfcx(s * 0.70710678118654752440), hs = 0.5 * (s * s), e = exp(-hs), q = 0.5 * (u * e);
-        const double rt = 0.79788456080286535588 / u, rc = e * 0.39894228040143267794 / (1.0 - q);
-        double lt = 0.0, lc = 0.0;
-        if (HAS_LP) {
-            lt = log(0.5 * u) - hs;
-            lc = log1p(-q);
-        }
-        if (h >= 0.0) {                                    // Phi(eta) is the central side
-            if (HAS_G) r = y * rc - (1.0 - y) * rt;
-            if (HAS_LP) t = y * lc + (1.0 - y) * lt;
-        } else {
-            if (HAS_G) r = y * rt - (1.0 - y) * rc;
-            if (HAS_LP) t = y * lt + (1.0 - y) * lc;
-        }
-        return true;
-    } else {
-        const double d = y - h;
-        if (HAS_G) r = tau * d;
-        if (HAS_LP) t = -0.5 * (tau * (d * d));
-        return true;
-    }
 }
 
 // f(integral_constant<int, n>) for the runtime n in 1 .. MAX: the two inner loops below run with a compile-time number of rows of X

@@ -585,7 +585,7 @@ class HipEngine:
                  "scalars_fast": 0x20, "scalars_generic": 0x40, "cov_sym": 0x80, "cov_generic": 0x100, "fupd_fast": 0x200,
                  "fupd_generic": 0x400, "lowrank_fast": 0x800, "lowrank_generic": 0x1000, "batched": 0x2000,
                  "batched_bam": 0x4000, "batched_kl": 0x8000, "batched_advi": 0x10000, "batched_target": 0x20000,
-                 "batched_lbfgs": 0x40000}
+                 "batched_lbfgs": 0x40000, "batched_laplace": 0x80000}
     PATH_GENERIC_MASK = 0x4 | 0x10 | 0x40 | 0x100 | 0x400 | 0x1000
 
     def last_path(self, reset=True):
@@ -969,6 +969,67 @@ class HipEngine:
             self._ctx, self._stream(), K, D, self._packed(state["S"], (K, 10, D), "S"), self._packed(state["Y"], (K, 10, D), "Y"),
             C.c_void_p(ist.data_ptr()), self._packed(cov, (K, D, D), "cov")))
         return cov
+
+    # ---- batched Laplace initialiser: Hessian, inverse and Newton rounds of the GLM targets (csrc/gsmvi_laplace_batched.hip) ----
+    def _glm_model_args(self, A, y, family, offset, counts, prior_prec, noise_prec):
+        """the model's arguments of the two Laplace entry points, in the order of include/gsmvi_hip.h"""
+        if family not in self.GLM_FAMILIES:
+            raise ValueError(f"family = {family!r}: expected one of {sorted(self.GLM_FAMILIES)}")
+        K, N, D = A.shape
+        r, rp = self._reg_arg(prior_prec, K)
+        t, tp = self._reg_arg(noise_prec, K)
+        if tp is not None:
+            t = 1.0                                                   # (the scalar is unused with K values)
+        return (K, D, N, self.GLM_FAMILIES[family], self._packed(A, (K, N, D), "A"), self._packed(y, (K, N), "y"),
+                self._dp(offset, (K, N), "offset"), self._ints(counts, K, "counts"), t, tp, r, rp)
+
+    def glm_hessian_batched(self, X, A, y, family, offset=None, counts=None, prior_prec=1.0, noise_prec=1.0, want="h", out=None,
+                            cov_out=None, info_out=None):
+        """The negative Hessian H_k = A_k^T W A_k + lam_k I of lp_k at the rows of X (K, D) and / or its inverse, one launch
+        (the Gram product on the fp64 MFMA)  [no reference twin; the model of examples/example_gsm.py:34-35]: ``want`` = "h" ->
+        H (K, D, D), "cov" -> (cov, info), "both" -> (H, cov, info); ``info`` (K,) int32: 0, or 1 + the first failing pivot, and
+        then cov_k = I.  The other arguments are ``glm_batched``'s."""
+        if want not in ("h", "cov", "both"):
+            raise ValueError(f"want = {want!r}: expected 'h', 'cov' or 'both'")
+        X = X.contiguous()
+        K, D = X.shape
+        self._ensure(max(self._max_D, 1), max(self._max_B, 1))
+        H = cov = info = None
+        if want != "cov":
+            H = self.empty(K, D, D) if out is None else out
+        if want != "h":
+            cov = self.empty(K, D, D) if cov_out is None else cov_out
+            info = torch.zeros(K, dtype=torch.int32, device=self.device) if info_out is None else info_out
+        _lib.check("gsmvi_glm_hessian_batched_f64", self.lib.gsmvi_glm_hessian_batched_f64(
+            self._ctx, self._stream(), *self._glm_model_args(A, y, family, offset, counts, prior_prec, noise_prec),
+            self._packed(X, (K, D), "X"), self._dp(H, (K, D, D), "out"), self._dp(cov, (K, D, D), "cov_out"),
+            self._ints(info, K, "info_out")))
+        return H if want == "h" else (cov, info) if want == "cov" else (H, cov, info)
+
+    def laplace_state_batched(self, x0):
+        """The state of K Newton runs started at the rows of x0 (K, D), as include/gsmvi_hip.h lays it out: a dict of device
+        arrays x, g, d, Xt (K, D), sc (K, 4), ist (K, 8) int32 and the one-element counter ``stopped``"""
+        K, D = x0.shape
+        x = self.asarray(x0).clone(memory_format=torch.contiguous_format)
+        return {"x": x, "g": self.zeros(K, D), "d": self.zeros(K, D), "Xt": x.clone(), "sc": self.zeros(K, 4),
+                "ist": torch.zeros(K, 8, dtype=torch.int32, device=self.device), "stopped": self.new_flag()}
+
+    def laplace_step_batched(self, state, A, y, family, offset=None, counts=None, prior_prec=1.0, noise_prec=1.0, start=False,
+                             maxiter=100, maxfun=200, gtol=1e-8):
+        """One damped Newton round of every running problem of ``state`` (csrc/gsmvi_laplace_batched.hip): f, g and H at
+        ``state["Xt"]`` in one sweep over A, then accept or reject, the stopping tests, the next direction and trial point;
+        ``state["stopped"]`` (optional) grows by the problems that stopped  [the role of gsmvi/initializers.py:5-17]"""
+        K, D = state["x"].shape
+        self._ensure(max(self._max_D, 1), max(self._max_B, 1))
+        ist = state["ist"]
+        assert isinstance(ist, torch.Tensor) and ist.is_cuda and ist.dtype == torch.int32 and ist.is_contiguous() \
+            and tuple(ist.shape) == (K, 8), f"ist: expected a contiguous int32 CUDA tensor of shape {(K, 8)}"
+        stopped = state.get("stopped")
+        _lib.check("gsmvi_laplace_step_batched_f64", self.lib.gsmvi_laplace_step_batched_f64(
+            self._ctx, self._stream(), *self._glm_model_args(A, y, family, offset, counts, prior_prec, noise_prec),
+            int(bool(start)), self._packed(state["x"], (K, D), "x"), self._packed(state["g"], (K, D), "g"),
+            self._packed(state["d"], (K, D), "d"), self._packed(state["sc"], (K, 4), "sc"), C.c_void_p(ist.data_ptr()),
+            self._packed(state["Xt"], (K, D), "Xt"), self._ints(stopped, 1, "stopped"), int(maxiter), int(maxfun), float(gtol)))
 
     def bam_update(self, X, G, mu0, S0, reg, jitter=0.0, out=None, flag=None):
         """(mu, S) of BaM [gsmvi/bam.py:72-114]; S symmetrised, jitter on the diagonal."""

@@ -143,6 +143,10 @@ class BatchedLogisticTarget:
     allocation with ``out``).  ``lp(x)``: (K, rows, D) -> (K, rows) values (what ADVIBatch's losses and BatchedKLMonitor sum per
     problem); a device tensor or numpy.  ``lp_and_score(x)``: (scores, values) from one launch."""
 
+    family = "logistic"                 # the model as ``laplace_init_batched`` and ``neg_hessian`` hand it to the GLM kernels
+    offset = None
+    noise_precision = 1.0
+
     def __init__(self, A, y, prior_precision=1.0, counts=None, engine=None):
         sa, sy = tuple(int(n) for n in A.shape), tuple(int(n) for n in y.shape)
         if len(sa) != 3 or min(sa) < 1:
@@ -193,6 +197,13 @@ class BatchedLogisticTarget:
         """(scores (K, rows, D), values (K, rows)) from one launch"""
         eng = self.engine
         return eng.logistic_batched(eng.asarray(x), self.A, self.y, self.counts, self.prior_precision, want="both")
+
+    def neg_hessian(self, x):
+        """(K, D, D) negative Hessians A_k^T W A_k + lam_k I of lp_k at the rows of x (K, D), W = diag(sigmoid (1 - sigmoid)),
+        exactly symmetric; a device tensor or numpy; one launch"""
+        eng = self.engine
+        return eng.glm_hessian_batched(eng.asarray(x), self.A, self.y, "logistic", counts=self.counts,
+                                       prior_prec=self.prior_precision, want="h")
 
 
 class BatchedGLMTarget:
@@ -306,3 +317,11 @@ class BatchedGLMTarget:
     def lp_and_score(self, x):
         """(scores (K, rows, D), values (K, rows)) from one launch"""
         return self._call(self.engine.asarray(x), want="both")
+
+    def neg_hessian(self, x):
+        """(K, D, D) negative Hessians A_k^T W A_k + lam_k I of lp_k at the rows of x (K, D), W = diag(-dr / d eta) (logistic:
+        sigmoid (1 - sigmoid); poisson: exp(eta); probit: y hp (hp + eta) + (1 - y) hm (hm - eta) with hp = phi / Phi(eta), hm =
+        phi / Phi(-eta); gaussian: tau_k), exactly symmetric; a device tensor or numpy; one launch"""
+        eng = self.engine
+        return eng.glm_hessian_batched(eng.asarray(x), self.A, self.y, self.family, offset=self.offset, counts=self.counts,
+                                       prior_prec=self.prior_precision, noise_prec=self.noise_precision, want="h")

@@ -23,6 +23,7 @@
  *   examples/example_gsm.py:34-35 a model's log_prob and jit(grad(.)) of it, K logistic regressions -> gsmvi_logistic_batched_f64
  *   examples/example_gsm.py:34-35 the same for K Poisson, probit or Gaussian regressions with offsets -> gsmvi_glm_batched_f64
  *   initializers.py:5-17 lbfgs_init (maximiser of lp, dense inverse-Hessian estimate), K problems -> gsmvi_lbfgs_step_batched_f64, gsmvi_lbfgs_hess_inv_batched_f64
+ *   initializers.py:5-17 the same role by Newton rounds on the GLMs of examples/example_gsm.py:34-35 (no reference twin) -> gsmvi_glm_hessian_batched_f64, gsmvi_laplace_step_batched_f64
  *   gsmvi/bam.py:72-114       bam_lowrank_update(samples,vs,mu0,S0,reg) ->  gsmvi_bam_update_f64
  *   gsmvi/bam.py:31-69        bam_update(samples,vs,mu0,S0,reg)         ->  gsmvi_bam_update_f64 (same result, K6)
  *
@@ -268,6 +269,7 @@ int gsmvi_get_profile(gsmvi_ctx* ctx, float* ms, int n);
 #define GSMVI_PATH_BATCHED_ADVI 0x10000u   /* k_advi_batched / k_advi_cov_batched: the batched ADVI entry points   */
 #define GSMVI_PATH_BATCHED_TARGET 0x20000u /* k_logistic_batched: the batched non-Gaussian target's entry point     */
 #define GSMVI_PATH_BATCHED_LBFGS 0x40000u  /* k_lbfgs_step_batched / k_lbfgs_hess_inv_batched: the batched initialiser   */
+#define GSMVI_PATH_BATCHED_LAPLACE 0x80000u /* k_laplace_batched: the batched GLM Hessian and Newton step             */
 #define GSMVI_PATH_GENERIC_MASK (0x0004u | 0x0010u | 0x0040u | 0x0100u | 0x0400u | 0x1000u)
 int gsmvi_last_path(gsmvi_ctx* ctx, unsigned* bits, int reset);
 
@@ -527,6 +529,57 @@ int gsmvi_lbfgs_step_batched_f64(gsmvi_ctx* ctx, void* stream, int64_t K, int D,
                                  double* Xt, int* stopped_dev, int maxiter, int maxfun, double gtol, double ftol);
 int gsmvi_lbfgs_hess_inv_batched_f64(gsmvi_ctx* ctx, void* stream, int64_t K, int D, const double* S, const double* Y,
                                      const int* ist, double* cov);
+
+/*
+ * Batched Laplace initialiser: the Newton mode of K GLM posteriors of one (N, D) and the inverse of the negative Hessian there
+ * as the covariance.  The reference has no Laplace initialiser: this fills the role of gsmvi/initializers.py:5-17 (the maximiser
+ * of lp as the mean, an inverse-Hessian estimate as the covariance) for the models of examples/example_gsm.py:34-35 whose second
+ * derivative is closed-form, the four families of gsmvi_glm_batched_f64.  With eta_n = a_n . x + o_kn and the weight
+ *   w = -dr / d eta:   logistic  sigma (1 - sigma) = e / (1 + e)^2, e = exp(-|eta|)      poisson  e^eta      gaussian  tau_k
+ *                      probit    y hp (hp + eta) + (1 - y) hm (hm - eta), hp = phi / Phi(eta), hm = phi / Phi(-eta)
+ * (probit: the tail side cancels, hp + eta at eta < 0 and hm - eta at eta > 0, so the relative error of w grows like eps eta^2),
+ *   H_k(x) = sum_{n < n_k} w(eta_n, y_n) a_n a_n^T + lam_k I         the negative Hessian of lp_k at x, positive semi-definite.
+ * The argument meanings, bounds and grid limits of gsmvi_glm_batched_f64 hold for both entry points (1 <= D <= 64, any N >= 1,
+ * counts_dev clamped in the kernel and rows n >= n_k never loaded, noise_prec the gaussian family's alone).  The Gram product runs
+ * on the fp64 MFMA over tiles of 32 rows; every sum over n is taken in an order fixed by (N, D) alone, so a problem's bits depend
+ * on its own data only, not on K or its neighbours.
+ *
+ * gsmvi_glm_hessian_batched_f64: at the rows x_k of X (K x D), H (K x D x D, or NULL) = H_k(x_k), exactly symmetric (one triangle
+ * is computed and mirrored); cov (K x D x D, or NULL) = H_k^{-1} through a Cholesky factorisation, exactly symmetric; info_dev
+ * (K ints, required with cov and only with it): 0, or 1 + the index j of the first pivot that is not finite or not > 64 eps H_jj
+ * (a relative rule: a rank-deficient H fails whatever the rounding), and then cov_k is the identity (nothing is known: what
+ * gsmvi_lbfgs_hess_inv_batched_f64 gives without a pair).  A non-finite x_k or (poisson) a valid row whose e^eta is not finite
+ * gives H_k = NaN, info[k] = 1, cov_k = I, and no other problem is touched.  At least one of H, cov is given.
+ *
+ * gsmvi_laplace_step_batched_f64: one launch is one damped Newton round of phi_k = -lp_k for every running problem.  State,
+ * caller-owned, packed, in device memory, laid out like the L-BFGS state above:
+ *   x, g, d, Xt (K x D)  the last accepted point, the gradient of phi there, the Newton direction, the trial point
+ *   sc (K x 4)           [0] f = phi(x), [1] the trial step t, [2] g.d, [3] spare
+ *   ist (K x 8)          [0] status (0 running, 1 converged, 2 maxiter / maxfun reached, 3 line search failed, 4 non-finite start,
+ *                        5 H not positive definite), [1] nit, [2] nfev, [3] nls (rejected trials of this search), [4..7] spare
+ * Per running problem the launch evaluates ft, gt and H at Xt in one sweep over A_k.  start != 0 (Xt holds x0; every entry of the
+ * state is written): x = Xt, nfev = 1; ft or gt not finite -> status 4; max|g| <= gtol -> status 1; else H is factored (failure by
+ * the pivot rule above -> status 5) and d = -H^{-1} g, t = 1, g.d, Xt = x + d.  start == 0: nfev += 1; ok = ft, gt finite and
+ * ft <= f + (1e-4 t) (g.d) + 1e-10 max(1, |f|) (the slack keeps the test decidable where the decrease of f is below its own
+ * rounding).  Not ok: t <- t / 2, nls += 1; nls > 20 -> status 3; else nfev >= maxfun -> status 2; else Xt = x + t d.  Ok: (x, f, g)
+ * <- (Xt, ft, gt), nit += 1; max|g| <= gtol -> status 1; else nit >= maxiter or nfev >= maxfun -> status 2; else H(x) is factored
+ * (failure -> status 5) and d = -H^{-1} g, t = 1, nls = 0, g.d, Xt = x + d.  A problem whose status is not 0 is frozen: nothing of
+ * it is written and nothing of A_k is loaded for it.  *stopped_dev (one int, may be NULL) grows by the number of problems that
+ * stopped in this launch.  maxiter >= 1, maxfun >= 2, gtol >= 0.  Written: the state and *stopped_dev, none of which may overlap
+ * any other array of the call.
+ * Both: shapes, NULL arrays and overlaps are checked before the context is looked at (then a NULL ctx); every failure returns
+ * GSMVI_ERR_BAD_ARG before anything is enqueued.  Inputs are only read; no context workspace is used.  Sets
+ * GSMVI_PATH_BATCHED_LAPLACE.
+ */
+int gsmvi_glm_hessian_batched_f64(gsmvi_ctx* ctx, void* stream, int64_t K, int D, int64_t N, int family, const double* A,
+                                  const double* y, const double* offset, const int* counts_dev, double noise_prec,
+                                  const double* noise_prec_dev, double prior_prec, const double* prior_prec_dev, const double* X,
+                                  double* H, double* cov, int* info_dev);
+int gsmvi_laplace_step_batched_f64(gsmvi_ctx* ctx, void* stream, int64_t K, int D, int64_t N, int family, const double* A,
+                                   const double* y, const double* offset, const int* counts_dev, double noise_prec,
+                                   const double* noise_prec_dev, double prior_prec, const double* prior_prec_dev, int start,
+                                   double* x, double* g, double* d, double* sc, int* ist, double* Xt, int* stopped_dev, int maxiter,
+                                   int maxfun, double gtol);
 
 /*
  * Upper Cholesky factor R (R^T R = S, R upper triangular, strictly-lower part zeroed) of a
