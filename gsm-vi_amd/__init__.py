@@ -24,6 +24,10 @@ Mirrors the reference's public surface for the hot path (reference file:line):
     BatchedGLMTarget (the same launch for K
     Poisson, probit, Gaussian or logistic
     regressions with offsets)                    examples/example_gsm.py:34-35 (log_prob, jit(grad(.)))
+    BatchedGLMTarget.predict, GLMPrediction (the
+    posterior predictive of K fitted GLMs on new
+    rows: mean, variance of the linear predictor,
+    predictive mean, held-out elpd; one launch)  examples/example_gsm.py:34-35, the use of the fit; no reference twin
     lbfgs_init_batched (the L-BFGS initialiser
     for K problems at once, D <= 64: one launch
     per function evaluation after lp_g and lp)   gsmvi/initializers.py:5-17
@@ -43,7 +47,7 @@ from .gsm import GSM, gsm_update                                     # noqa: F40
 from .bam import BaM, bam_update, bam_lowrank_update, Regularizers   # noqa: F401
 from .targets import GaussianTarget, device_score, score_from_logp   # noqa: F401
 from .targets import BatchedGaussianTarget, BatchedLogisticTarget    # noqa: F401
-from .targets import BatchedGLMTarget                                # noqa: F401
+from .targets import BatchedGLMTarget, GLMPrediction                 # noqa: F401
 from .batched import GSMBatch, gsm_update_batched                    # noqa: F401
 from .batched import BaMBatch, bam_update_batched, bam_lowrank_update_batched   # noqa: F401
 from .batched import ADVIBatch, Adam                                 # noqa: F401

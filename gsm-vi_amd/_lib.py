@@ -128,6 +128,9 @@ _SIGS = {
     "gsmvi_laplace_step_batched_f64": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int64, C.c_int, _c_dp, _c_dp, _c_dp,
                                                  _c_dp, C.c_double, _c_dp, C.c_double, _c_dp, C.c_int, _c_dp, _c_dp, _c_dp, _c_dp,
                                                  _c_dp, _c_dp, _c_dp, C.c_int, C.c_int, C.c_double]),
+    "gsmvi_glm_predict_batched_f64": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int64, C.c_int, _c_dp, _c_dp, _c_dp,
+                                                _c_dp, C.c_double, _c_dp, _c_dp, _c_dp, C.c_int, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp,
+                                                _c_dp, _c_dp]),
     "gsmvi_commit_f64": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, _c_dp, _c_dp, _c_dp, C.c_int, _c_dp, _c_dp,
                                    C.c_int, _c_dp]),
     "gsmvi_bam_update_f64": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, _c_dp, C.c_int, _c_dp, C.c_int,

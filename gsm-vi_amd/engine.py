@@ -585,7 +585,7 @@ class HipEngine:
                  "scalars_fast": 0x20, "scalars_generic": 0x40, "cov_sym": 0x80, "cov_generic": 0x100, "fupd_fast": 0x200,
                  "fupd_generic": 0x400, "lowrank_fast": 0x800, "lowrank_generic": 0x1000, "batched": 0x2000,
                  "batched_bam": 0x4000, "batched_kl": 0x8000, "batched_advi": 0x10000, "batched_target": 0x20000,
-                 "batched_lbfgs": 0x40000, "batched_laplace": 0x80000}
+                 "batched_lbfgs": 0x40000, "batched_laplace": 0x80000, "batched_predict": 0x100000}
     PATH_GENERIC_MASK = 0x4 | 0x10 | 0x40 | 0x100 | 0x400 | 0x1000
 
     def last_path(self, reset=True):
@@ -1030,6 +1030,50 @@ class HipEngine:
             int(bool(start)), self._packed(state["x"], (K, D), "x"), self._packed(state["g"], (K, D), "g"),
             self._packed(state["d"], (K, D), "d"), self._packed(state["sc"], (K, 4), "sc"), C.c_void_p(ist.data_ptr()),
             self._packed(state["Xt"], (K, D), "Xt"), self._ints(stopped, 1, "stopped"), int(maxiter), int(maxfun), float(gtol)))
+
+    # ---- batched GLM posterior predictive: the use of K fitted Gaussians (csrc/gsmvi_glm_predict_batched.hip) -----------------
+    @staticmethod
+    def gauss_hermite(Q):
+        """(nodes t, log weights) of the Q-point Gauss-Hermite rule (weight exp(-t^2)) as float64 arrays: the table
+        gsmvi_glm_predict_batched_f64 is handed (numpy.polynomial.hermite.hermgauss; no table lives in the library)"""
+        t, w = np.polynomial.hermite.hermgauss(int(Q))
+        return np.asarray(t, dtype=np.float64), np.log(np.asarray(w, dtype=np.float64))
+
+    def _gh_table(self, Q):
+        """the device copy of ``gauss_hermite(Q)``, uploaded once per Q and kept on the engine"""
+        cache = self.__dict__.setdefault("_gh_tables", {})
+        if Q not in cache:
+            t, lw = self.gauss_hermite(Q)
+            cache[Q] = (self.asarray(t), self.asarray(lw))
+        return cache[Q]
+
+    def glm_predict_batched(self, mean, cov, A, family, offset=None, y=None, counts=None, noise_prec=1.0, nodes=32):
+        """The posterior predictive of K fitted GLMs at the rows of A (K, M, D) under q_k = N(mean_k, cov_k), one launch (the
+        product A cov on the fp64 MFMA)  [examples/example_gsm.py:34-35, the use of the fit; no reference twin]: returns
+        (eta_mean, eta_var, pmean (K, M), lpd (K, M), elpd (K,)), the last two None without ``y``.  ``family``, ``offset``,
+        ``counts`` and ``noise_prec`` are ``glm_batched``'s; ``nodes`` = Q Gauss-Hermite nodes, 1 .. 64."""
+        if family not in self.GLM_FAMILIES:
+            raise ValueError(f"family = {family!r}: expected one of {sorted(self.GLM_FAMILIES)}")
+        Q = int(nodes)
+        if not 1 <= Q <= 64:
+            raise ValueError(f"nodes = {nodes!r}: expected 1 .. 64")
+        K, M, D = A.shape
+        self._ensure(max(self._max_D, 1), max(self._max_B, 1))
+        gt, gl = self._gh_table(Q)
+        em, ev, pm = self.empty(K, M), self.empty(K, M), self.empty(K, M)
+        lpd = elpd = None
+        if y is not None:
+            lpd, elpd = self.empty(K, M), self.empty(K)
+        t, tp = self._reg_arg(noise_prec, K)
+        if tp is not None:
+            t = 1.0                                                   # (the scalar is unused with K values)
+        _lib.check("gsmvi_glm_predict_batched_f64", self.lib.gsmvi_glm_predict_batched_f64(
+            self._ctx, self._stream(), K, D, M, self.GLM_FAMILIES[family], self._packed(A, (K, M, D), "A"),
+            self._dp(offset, (K, M), "offset"), self._dp(y, (K, M), "y"), self._ints(counts, K, "counts"), t, tp,
+            self._packed(mean, (K, D), "mean"), self._packed(cov, (K, D, D), "cov"), Q, self._packed(gt, (Q,), "gh_t"),
+            self._packed(gl, (Q,), "gh_logw"), self._packed(em, (K, M), "eta_mean"), self._packed(ev, (K, M), "eta_var"),
+            self._packed(pm, (K, M), "pmean"), self._dp(lpd, (K, M), "lpd"), self._dp(elpd, (K,), "elpd")))
+        return em, ev, pm, lpd, elpd
 
     def bam_update(self, X, G, mu0, S0, reg, jitter=0.0, out=None, flag=None):
         """(mu, S) of BaM [gsmvi/bam.py:72-114]; S symmetrised, jitter on the diagonal."""

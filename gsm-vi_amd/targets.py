@@ -7,8 +7,12 @@ kernel.  ``device_score`` marks a user callable as taking/returning CUDA tensors
 (examples/example_gsm.py:34-35: ``lp_g = jit(grad(lambda x: sum(lp(x))))``).
 ``BatchedLogisticTarget`` is the first non-Gaussian device target of the batched fits: K Bayesian logistic
 regressions, score and log-density from one HIP launch.  ``BatchedGLMTarget`` is the same launch for a family of generalised
-linear models: Poisson, probit, Gaussian and logistic, with offsets.
+linear models: Poisson, probit, Gaussian and logistic, with offsets.  Both have ``predict``: the posterior predictive of the
+fitted Gaussians on new rows (``GLMPrediction``), one HIP launch.
 """
+from dataclasses import dataclass
+from typing import Any
+
 import numpy as np
 import torch
 
@@ -125,6 +129,116 @@ def _host_array(x):
     return x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x)
 
 
+def _check_counts(counts, K, N, rows="N"):
+    """``counts`` of K problems of N rows each as a host integer array (None stays None), else ValueError"""
+    if counts is None:
+        return None
+    cnt = np.asarray(_host_array(counts))
+    if cnt.shape != (K,) or not np.issubdtype(cnt.dtype, np.integer):
+        raise ValueError(f"counts: expected {K} integers, got shape {cnt.shape}, dtype {cnt.dtype}")
+    if (cnt < 0).any() or (cnt > N).any():
+        raise ValueError(f"counts: values outside 0 .. {rows} = {N} for problems {np.flatnonzero((cnt < 0) | (cnt > N)).tolist()}")
+    return cnt
+
+
+def _live_rows(cnt, N):
+    """(K, N) or (1, N) mask of the rows that count"""
+    return np.arange(N)[None, :] < (cnt[:, None] if cnt is not None else N)
+
+
+def _check_responses(y, family, live, name_family=True):
+    """the responses as a host float64 array, their range per family checked in the valid rows, else ValueError"""
+    yh = np.asarray(_host_array(y), dtype=np.float64)
+    with np.errstate(invalid="ignore"):
+        if family in ("logistic", "probit"):
+            good, what = (yh >= 0.0) & (yh <= 1.0), "outside [0, 1] or non-finite"     # (a NaN fails both comparisons)
+        elif family == "poisson":
+            good, what = (yh >= 0.0) & np.isfinite(yh), "negative or non-finite"
+        else:
+            good, what = np.isfinite(yh), "non-finite"
+    bad = live & ~good
+    if bad.any():
+        raise ValueError(f"y: values {what} in the valid rows of problems {np.flatnonzero(bad.any(1)).tolist()}"
+                         + (f" (family {family!r})" if name_family else ""))
+    return yh
+
+
+def _check_offset(offset, K, N, live, rows="N"):
+    """the offsets as a host float64 array (None stays None), shape and finiteness in the valid rows checked, else ValueError"""
+    if offset is None:
+        return None
+    so = tuple(int(n) for n in offset.shape) if hasattr(offset, "shape") else np.shape(offset)
+    if so != (K, N):
+        raise ValueError(f"offset: expected shape (K, {rows}) = {(K, N)}, got {so}")
+    oh = np.asarray(_host_array(offset), dtype=np.float64)
+    bad = live & ~np.isfinite(oh)
+    if bad.any():
+        raise ValueError(f"offset: non-finite values in the valid rows of problems {np.flatnonzero(bad.any(1)).tolist()}")
+    return oh
+
+
+@dataclass
+class GLMPrediction:
+    """What ``BatchedGLMTarget.predict`` and ``BatchedLogisticTarget.predict`` return for M new rows of each of K problems under
+    the fitted q_k = N(mean_k, cov_k): ``eta_mean`` = a . mean_k + o and ``eta_var`` = a^T cov_k a (the raw value: negative
+    where cov_k is not positive semi-definite), the Gaussian of the linear predictor; ``mean`` = E[E[y | eta]], the predictive
+    mean of the response; with ``y``, ``lpd`` = log E[p(y | eta)] (normalised) per row and ``elpd`` (K,), its sum over the valid
+    rows: the held-out score by which fits of one model are compared.  (K, M) each; rows beyond ``counts[k]`` are NaN; ``lpd`` and
+    ``elpd`` are None without ``y``.  numpy arrays or device tensors, as the call's ``mean`` was.
+    [examples/example_gsm.py:34-35, the use of the fit; no reference twin]"""
+    eta_mean: Any
+    eta_var: Any
+    mean: Any
+    lpd: Any
+    elpd: Any
+
+
+def _predict(target, mean, cov, A_new, offset, y, counts, nodes):
+    """``predict`` of both GLM targets: the checks on the host, then one launch (gsmvi_glm_predict_batched_f64)"""
+    K, D, family = target.K, target.D, target.family
+    if isinstance(nodes, bool) or not isinstance(nodes, (int, np.integer)) or not 1 <= nodes <= 64:
+        raise ValueError(f"nodes: expected an integer in 1 .. 64, got {nodes!r}")
+    sa = tuple(int(n) for n in A_new.shape) if hasattr(A_new, "shape") else np.shape(A_new)
+    if len(sa) != 3 or min(sa) < 1 or sa[0] != K or sa[2] != D:
+        raise ValueError(f"A_new: expected shape (K, M, D) with K = {K}, D = {D} and M >= 1, got {sa}")
+    M = sa[1]
+    sm = tuple(int(n) for n in mean.shape) if hasattr(mean, "shape") else np.shape(mean)
+    if sm != (K, D):
+        raise ValueError(f"mean: expected shape (K, D) = {(K, D)}, got {sm}")
+    sc = tuple(int(n) for n in cov.shape) if hasattr(cov, "shape") else np.shape(cov)
+    if sc != (K, D, D):
+        raise ValueError(f"cov: expected shape (K, D, D) = {(K, D, D)}, got {sc}")
+    cnt = _check_counts(counts, K, M, rows="M")
+    live = _live_rows(cnt, M)
+    yh = None
+    if y is not None:
+        sy = tuple(int(n) for n in y.shape) if hasattr(y, "shape") else np.shape(y)
+        if sy != (K, M):
+            raise ValueError(f"y: expected shape (K, M) = {(K, M)}, got {sy}")
+        yh = _check_responses(y, family, live, name_family=isinstance(target, BatchedGLMTarget))
+    oh = _check_offset(offset, K, M, live, rows="M")
+    eng = target.engine
+    as_tensor = isinstance(mean, torch.Tensor)
+    dev = lambda x: eng.asarray(x.contiguous() if isinstance(x, torch.Tensor) else x)      # noqa: E731
+    out = eng.glm_predict_batched(dev(mean), dev(cov), dev(A_new), family, offset=eng.asarray(oh) if oh is not None else None,
+                                  y=eng.asarray(yh) if yh is not None else None,
+                                  counts=eng.batched_counts(cnt) if cnt is not None else None,
+                                  noise_prec=target.noise_precision, nodes=int(nodes))
+    if not as_tensor:
+        out = tuple(eng.to_numpy(t) if t is not None else None for t in out)
+    return GLMPrediction(*out)
+
+
+_PREDICT_DOC = """The posterior predictive of the K fitted problems on new rows: ``mean`` (K, D) and ``cov`` (K, D, D) are the
+        fitted Gaussians (of GSMBatch, BaMBatch, ADVIBatch or ``laplace_init_batched``), ``A_new`` (K, M, D) the new rows,
+        ``offset`` (K, M) their offsets (None: none, whether or not the target was built with one: the new rows are new data),
+        ``y`` (K, M) their responses (None: no ``lpd`` / ``elpd``), ``counts`` (K,) the valid rows per problem (None: all M),
+        ``nodes`` = Q the Gauss-Hermite nodes, 1 .. 64.  Returns a ``GLMPrediction``; numpy in gives numpy out, CUDA tensors in
+        give tensors out.  ``y``, ``offset`` and ``counts`` are validated as the constructor validates its own (ValueError
+        naming the argument and the problems), the shapes and ``nodes`` too, before any device work.  The quadrature is
+        accurate for modest eta_var (DESIGN.md section 9); the gaussian family is closed-form.  One launch."""
+
+
 class BatchedLogisticTarget:
     """K Bayesian logistic regressions with their own data sets, for ``GSMBatch``, ``BaMBatch``, ``ADVIBatch`` and
     ``BatchedKLMonitor``.  Problem k has the design matrix A[k] (N, D), labels y[k] (N,) in [0, 1] (soft labels allowed),
@@ -156,19 +270,9 @@ class BatchedLogisticTarget:
             raise ValueError(f"A: D = {D} is outside 1 <= D <= 64")
         if sy != (K, N):
             raise ValueError(f"y: expected shape (K, N) = {(K, N)}, got {sy}")
-        cnt = None
-        if counts is not None:
-            cnt = np.asarray(_host_array(counts))
-            if cnt.shape != (K,) or not np.issubdtype(cnt.dtype, np.integer):
-                raise ValueError(f"counts: expected {K} integers, got shape {cnt.shape}, dtype {cnt.dtype}")
-            if (cnt < 0).any() or (cnt > N).any():
-                raise ValueError(f"counts: values outside 0 .. N = {N} for problems {np.flatnonzero((cnt < 0) | (cnt > N)).tolist()}")
-        yh = np.asarray(_host_array(y), dtype=np.float64)
-        live = np.arange(N)[None, :] < (cnt[:, None] if cnt is not None else N)
-        bad = live & ~((yh >= 0.0) & (yh <= 1.0))                     # (a NaN fails both comparisons)
-        if bad.any():
-            raise ValueError(f"y: values outside [0, 1] or non-finite in the valid rows of problems "
-                             f"{np.flatnonzero(bad.any(1)).tolist()}")
+        cnt = _check_counts(counts, K, N)
+        live = _live_rows(cnt, N)
+        yh = _check_responses(y, "logistic", live, name_family=False)
         lam = np.asarray(_host_array(prior_precision), dtype=np.float64)
         if lam.shape not in ((), (K,)):
             raise ValueError(f"prior_precision: expected a number or {K} values, got shape {lam.shape}")
@@ -204,6 +308,10 @@ class BatchedLogisticTarget:
         eng = self.engine
         return eng.glm_hessian_batched(eng.asarray(x), self.A, self.y, "logistic", counts=self.counts,
                                        prior_prec=self.prior_precision, want="h")
+
+    def predict(self, mean, cov, A_new, offset=None, y=None, counts=None, nodes=32):
+        return _predict(self, mean, cov, A_new, offset, y, counts, nodes)
+    predict.__doc__ = _PREDICT_DOC
 
 
 class BatchedGLMTarget:
@@ -244,35 +352,10 @@ class BatchedGLMTarget:
             raise ValueError(f"A: D = {D} is outside 1 <= D <= 64")
         if sy != (K, N):
             raise ValueError(f"y: expected shape (K, N) = {(K, N)}, got {sy}")
-        cnt = None
-        if counts is not None:
-            cnt = np.asarray(_host_array(counts))
-            if cnt.shape != (K,) or not np.issubdtype(cnt.dtype, np.integer):
-                raise ValueError(f"counts: expected {K} integers, got shape {cnt.shape}, dtype {cnt.dtype}")
-            if (cnt < 0).any() or (cnt > N).any():
-                raise ValueError(f"counts: values outside 0 .. N = {N} for problems {np.flatnonzero((cnt < 0) | (cnt > N)).tolist()}")
-        yh = np.asarray(_host_array(y), dtype=np.float64)
-        live = np.arange(N)[None, :] < (cnt[:, None] if cnt is not None else N)
-        with np.errstate(invalid="ignore"):
-            if family in ("logistic", "probit"):
-                good, what = (yh >= 0.0) & (yh <= 1.0), "outside [0, 1] or non-finite"     # (a NaN fails both comparisons)
-            elif family == "poisson":
-                good, what = (yh >= 0.0) & np.isfinite(yh), "negative or non-finite"
-            else:
-                good, what = np.isfinite(yh), "non-finite"
-        bad = live & ~good
-        if bad.any():
-            raise ValueError(f"y: values {what} in the valid rows of problems {np.flatnonzero(bad.any(1)).tolist()} "
-                             f"(family {family!r})")
-        oh = None
-        if offset is not None:
-            so = tuple(int(n) for n in offset.shape) if hasattr(offset, "shape") else np.shape(offset)
-            if so != (K, N):
-                raise ValueError(f"offset: expected shape (K, N) = {(K, N)}, got {so}")
-            oh = np.asarray(_host_array(offset), dtype=np.float64)
-            bad = live & ~np.isfinite(oh)
-            if bad.any():
-                raise ValueError(f"offset: non-finite values in the valid rows of problems {np.flatnonzero(bad.any(1)).tolist()}")
+        cnt = _check_counts(counts, K, N)
+        live = _live_rows(cnt, N)
+        yh = _check_responses(y, family, live)
+        oh = _check_offset(offset, K, N, live)
         lam = np.asarray(_host_array(prior_precision), dtype=np.float64)
         if lam.shape not in ((), (K,)):
             raise ValueError(f"prior_precision: expected a number or {K} values, got shape {lam.shape}")
@@ -325,3 +408,7 @@ class BatchedGLMTarget:
         eng = self.engine
         return eng.glm_hessian_batched(eng.asarray(x), self.A, self.y, self.family, offset=self.offset, counts=self.counts,
                                        prior_prec=self.prior_precision, noise_prec=self.noise_precision, want="h")
+
+    def predict(self, mean, cov, A_new, offset=None, y=None, counts=None, nodes=32):
+        return _predict(self, mean, cov, A_new, offset, y, counts, nodes)
+    predict.__doc__ = _PREDICT_DOC

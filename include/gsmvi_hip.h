@@ -24,6 +24,7 @@
  *   examples/example_gsm.py:34-35 the same for K Poisson, probit or Gaussian regressions with offsets -> gsmvi_glm_batched_f64
  *   initializers.py:5-17 lbfgs_init (maximiser of lp, dense inverse-Hessian estimate), K problems -> gsmvi_lbfgs_step_batched_f64, gsmvi_lbfgs_hess_inv_batched_f64
  *   initializers.py:5-17 the same role by Newton rounds on the GLMs of examples/example_gsm.py:34-35 (no reference twin) -> gsmvi_glm_hessian_batched_f64, gsmvi_laplace_step_batched_f64
+ *   examples/example_gsm.py:34-35 the use of the fit: predictions and the held-out score of K fitted GLMs (no reference twin) -> gsmvi_glm_predict_batched_f64
  *   gsmvi/bam.py:72-114       bam_lowrank_update(samples,vs,mu0,S0,reg) ->  gsmvi_bam_update_f64
  *   gsmvi/bam.py:31-69        bam_update(samples,vs,mu0,S0,reg)         ->  gsmvi_bam_update_f64 (same result, K6)
  *
@@ -270,6 +271,7 @@ int gsmvi_get_profile(gsmvi_ctx* ctx, float* ms, int n);
 #define GSMVI_PATH_BATCHED_TARGET 0x20000u /* k_logistic_batched: the batched non-Gaussian target's entry point     */
 #define GSMVI_PATH_BATCHED_LBFGS 0x40000u  /* k_lbfgs_step_batched / k_lbfgs_hess_inv_batched: the batched initialiser   */
 #define GSMVI_PATH_BATCHED_LAPLACE 0x80000u /* k_laplace_batched: the batched GLM Hessian and Newton step             */
+#define GSMVI_PATH_BATCHED_PREDICT 0x100000u /* k_glm_predict_batched: the batched GLM posterior predictive             */
 #define GSMVI_PATH_GENERIC_MASK (0x0004u | 0x0010u | 0x0040u | 0x0100u | 0x0400u | 0x1000u)
 int gsmvi_last_path(gsmvi_ctx* ctx, unsigned* bits, int reset);
 
@@ -580,6 +582,40 @@ int gsmvi_laplace_step_batched_f64(gsmvi_ctx* ctx, void* stream, int64_t K, int 
                                    const double* noise_prec_dev, double prior_prec, const double* prior_prec_dev, int start,
                                    double* x, double* g, double* d, double* sc, int* ist, double* Xt, int* stopped_dev, int maxiter,
                                    int maxfun, double gtol);
+
+/*
+ * Batched GLM posterior predictive: what a fitted q_k = N(mean_k, cov_k) over the coefficients of K GLMs of one D says about M new
+ * rows per problem, one launch.  examples/example_gsm.py:34-35 builds the model and the reference stops at the fitted (mean, cov):
+ * this is the use of the fit (predictions and the held-out score, the expected log predictive density), with no reference twin.
+ * The model's arguments are those of gsmvi_glm_hessian_batched_f64 with the number of new rows M in place of N and no prior:
+ * family, A (K x M x D), offset (K x M or NULL), y (K x M or NULL), counts_dev (K ints or NULL, clamped to 0 .. M in the kernel),
+ * noise_prec / noise_prec_dev (the gaussian family's alone: 1.0 and NULL for any other).  mean (K x D) and cov (K x D x D, read as
+ * given, both triangles) are the posterior.  Q (1 <= Q <= 64) and gh_t, gh_logw (Q doubles each, on the device) are the
+ * Gauss-Hermite nodes and the logarithms of their weights (numpy.polynomial.hermite.hermgauss; no table lives in the library).
+ * For row n < n_k of problem k:
+ *   m = a_n . mean_k + o_kn,   v = a_n^T cov_k a_n,   v+ = max(v, 0),   s = sqrt(2 v+),   eta_q = m + s t_q
+ *   eta_mean = m,  eta_var = v (the raw value: a covariance that is not positive semi-definite shows), and
+ *   family     pmean = E[E[y | eta]]                        lpd = log E[p(y | eta)]  (normalised)
+ *   gaussian   m                                            -log(2 pi (v+ + 1 / tau_k)) / 2 - (y - m)^2 / (2 (v+ + 1 / tau_k))
+ *   probit     Phi(m / sqrt(1 + v+))  (through erfc)        LSE_q(logw_q + t(eta_q, y)) - log(pi) / 2
+ *   poisson    exp(m + v+ / 2)                              LSE_q(logw_q + y eta_q - e^eta_q) - log(pi) / 2 - lgamma(y + 1)
+ *   logistic   sum_q exp(logw_q) sigma(eta_q) / sqrt(pi)    LSE_q(logw_q + t(eta_q, y)) - log(pi) / 2
+ * with t the family's t of gsmvi_glm_batched_f64 above, LSE the log-sum-exp with the maximum taken first and the sum in ascending
+ * q; the gaussian family uses no quadrature.  elpd[k] = sum_{n < n_k} lpd[k, n], summed in row order by one thread, so its bits
+ * depend on (M, D) and the problem's own data only.  Outputs: eta_mean, eta_var, pmean (K x M each, required), lpd (K x M) and
+ * elpd (K): both required with y, both NULL without it.  Rows n >= n_k are never loaded and all their outputs are NaN.  A row whose
+ * m or v is not finite has NaN outputs and makes elpd[k] NaN; nothing outside slice k is touched.  Everything else is what IEEE
+ * arithmetic gives from the formulas (a poisson node whose e^eta overflows contributes -inf to the LSE).  The product A cov runs
+ * on the fp64 MFMA over tiles of 32 rows.  1 <= D <= 64, M >= 1, K with the grid limits of the batched GSM above.  Shapes, NULL
+ * arrays and overlaps (the five outputs are the written arrays) are checked before the context is looked at (then a NULL ctx);
+ * every failure returns GSMVI_ERR_BAD_ARG before anything is enqueued.  Inputs are only read; no context workspace is used.  Sets
+ * GSMVI_PATH_BATCHED_PREDICT.
+ */
+int gsmvi_glm_predict_batched_f64(gsmvi_ctx* ctx, void* stream, int64_t K, int D, int64_t M, int family, const double* A,
+                                  const double* offset, const double* y, const int* counts_dev, double noise_prec,
+                                  const double* noise_prec_dev, const double* mean, const double* cov, int Q, const double* gh_t,
+                                  const double* gh_logw, double* eta_mean, double* eta_var, double* pmean, double* lpd,
+                                  double* elpd);
 
 /*
  * Upper Cholesky factor R (R^T R = S, R upper triangular, strictly-lower part zeroed) of a
