@@ -28,6 +28,11 @@ Mirrors the reference's public surface for the hot path (reference file:line):
     posterior predictive of K fitted GLMs on new
     rows: mean, variance of the linear predictor,
     predictive mean, held-out elpd; one launch)  examples/example_gsm.py:34-35, the use of the fit; no reference twin
+    psis_batched, psis_weights_batched,
+    PSISBatchedResult (is the fitted q_k usable?
+    Pareto-smoothed importance diagnostic of K
+    Gaussians: khat, ess, log Z, corrected
+    moments; one launch after the target's lp)   gsmvi/monitors.py:83-125 (the role; no reference twin)
     lbfgs_init_batched (the L-BFGS initialiser
     for K problems at once, D <= 64: one launch
     per function evaluation after lp_g and lp)   gsmvi/initializers.py:5-17
@@ -54,6 +59,7 @@ from .batched import ADVIBatch, Adam                                 # noqa: F40
 from .monitors import KLMonitor, DeviceKLMonitor, BatchedKLMonitor   # noqa: F401
 from .initializers import lbfgs_init, lbfgs_init_batched, LbfgsBatchedResult   # noqa: F401
 from .initializers import laplace_init_batched, LaplaceBatchedResult          # noqa: F401
+from .diagnostics import psis_batched, psis_weights_batched, PSISBatchedResult   # noqa: F401
 from .advi import ADVI                                               # noqa: F401
 
 __version__ = "0.1.0"

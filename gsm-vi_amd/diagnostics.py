@@ -1,0 +1,123 @@
+"""Diagnostics of fitted batched posteriors: the Pareto-smoothed importance sampling (PSIS) check of K Gaussians q_k = N(mean_k,
+cov_k) against their targets, one launch after the target's ``lp`` (csrc/gsmvi_psis_batched.hip; Vehtari, Simpson, Gelman, Yao,
+Gabry, "Pareto smoothed importance sampling", JMLR 2024).  ``BatchedKLMonitor`` traces a reverse KL up to each target's unknown
+constant; this says per problem, on one scale, whether q_k can be trusted: the shape khat of the importance ratios' tail, the
+effective sample size, an estimate of the log normalising constant, and importance-corrected moments."""
+from dataclasses import dataclass
+
+import numpy as np
+
+from .monitors import _to_numpy
+
+MIN_DRAWS, MAX_DRAWS = 5, 4096
+
+
+def khat_threshold(S):
+    """min(1 - 1 / log10(S), 0.7): the khat below which S draws give a usable importance estimate"""
+    return min(1.0 - 1.0 / np.log10(S), 0.7)
+
+
+@dataclass
+class PSISBatchedResult:
+    """What ``psis_batched`` / ``psis_weights_batched`` return (numpy arrays, or the engine's tensors with ``as_torch``):
+    ``khat`` (K,) the tail shape (+inf: the tail had fewer than 5 entries), ``ess`` (K,) the effective sample size of the
+    smoothed weights, ``log_z`` (K,) the estimate of log of the integral of exp(lp_k), ``log_weights`` (K, S) the normalised smoothed log
+    weights, ``log_ratios`` (K, S) lp_k - log q_k, ``samples`` (K, S, D) the draws, ``mean`` (K, D) and ``cov`` (K, D, D) the
+    importance-weighted moments (None without ``moments``), ``info`` (K,): 0, -1 = non-finite ratios, -2 = tail too short,
+    1 + the first bad pivot of cov_k (outputs NaN for -1 and the pivot codes), ``threshold`` = min(1 - 1 / log10(S), 0.7),
+    ``ok`` (K,) = (info == 0) & (khat < threshold), ``nlaunch`` the kernel launches made.  ``psis_weights_batched`` leaves the
+    fields that need q (``samples``, ``mean``, ``cov``) None; its ``log_ratios`` are the caller's."""
+    khat: object
+    ess: object
+    log_z: object
+    log_weights: object
+    log_ratios: object
+    samples: object
+    mean: object
+    cov: object
+    info: object
+    threshold: float
+    ok: object
+    nlaunch: int
+
+
+def _shape(a):
+    return tuple(int(n) for n in a.shape)
+
+
+def _result(eng, as_torch, S, nlaunch, khat, ess, log_z, lw, logr, X, mean_is, cov_is, info):
+    thr = khat_threshold(S)
+    ok = (info == 0) & (khat < thr)
+    if not as_torch:
+        conv = lambda t: None if t is None else np.asarray(eng.to_numpy(t))      # noqa: E731
+        khat, ess, log_z, lw, logr, X, mean_is, cov_is, ok = (conv(t) for t in (khat, ess, log_z, lw, logr, X, mean_is, cov_is, ok))
+        info = np.asarray(eng.read_ints(info))
+    return PSISBatchedResult(khat=khat, ess=ess, log_z=log_z, log_weights=lw, log_ratios=logr, samples=X, mean=mean_is,
+                             cov=cov_is, info=info, threshold=thr, ok=ok, nlaunch=nlaunch)
+
+
+def psis_batched(lp, mean, cov, keys, num_draws=1024, *, call=0, moments=True, as_torch=False, engine=None):
+    """The PSIS diagnostic of K fitted Gaussians q_k = N(mean_k, cov_k) against their targets: returns a ``PSISBatchedResult``.
+
+    ``lp`` maps a (K, S, D) block of points to the (K, S) values lp_k(x_ks), unnormalised or not (``BatchedGLMTarget.lp``,
+    ``BatchedLogisticTarget.lp``, ``BatchedGaussianTarget.lp_rows``); mean (K, D) and cov (K, D, D) are device tensors or numpy;
+    ``keys`` are K per-problem keys.  Two launches and one call of ``lp``: S = ``num_draws`` draws of every q_k (one call of
+    ``kl_draw_batched``, the stream of ``BatchedKLMonitor``: seed (keys[k] % 2**32) ^ 0x5DEECE66D, draw number ``call``), then
+    ``lp`` once, with the device tensor first and numpy if it refuses it, then ``gsmvi_psis_batched_f64``: log q_k per row, the
+    Pareto fit to the largest ratios, the smoothed weights and, with ``moments``, the importance-weighted mean and covariance.
+    mean and cov are only read, so a running fit is left bit for bit alone.  The sample block takes K * S * D * 8 bytes of
+    device memory (512 MB at K = 8192, S = 1024, D = 8; 4 GB at D = 64), the ratios and weights 2 * K * S * 8 more.
+    D outside 1..64, ``num_draws`` outside 5..4096, keys of another length than K or a cov that is not (K, D, D) raise ValueError
+    before any device work; so does an ``lp`` that returns (K,) sums -- give ``lp_rows``."""
+    from .batched import MAX_D
+    if len(_shape(mean)) != 2:
+        raise ValueError(f"psis_batched: mean must be (K, D), got {_shape(mean)}")
+    K, D = _shape(mean)
+    if not 1 <= D <= MAX_D:
+        raise ValueError(f"psis_batched: D = {D} is outside 1 <= D <= {MAX_D}")
+    if _shape(cov) != (K, D, D):
+        raise ValueError(f"psis_batched: cov must be {(K, D, D)}, got {_shape(cov)}")
+    S = int(num_draws)
+    if S != num_draws or not MIN_DRAWS <= S <= MAX_DRAWS:
+        raise ValueError(f"psis_batched: num_draws = {num_draws} is outside {MIN_DRAWS} <= num_draws <= {MAX_DRAWS}")
+    keys_l = [int(k) for k in np.asarray(list(keys) if isinstance(keys, (list, tuple, range)) else _to_numpy(keys)).reshape(-1)]
+    if len(keys_l) != K:
+        raise ValueError(f"psis_batched: {len(keys_l)} keys for K = {K} problems")
+    if engine is None:
+        from .engine import get_engine
+        engine = get_engine()
+    eng = engine
+    seeds = eng.batched_seeds(tuple((k % (2 ** 32)) ^ 0x5DEECE66D for k in keys_l))
+    mu, cv = eng.asarray(mean), eng.asarray(cov)
+    X, _, _ = eng.kl_draw_batched(mu, cv, seeds, int(call), 0, S)
+    try:
+        v = lp(X)
+    except (TypeError, AttributeError, RuntimeError, ValueError):
+        v = lp(eng.to_numpy(X))
+    v = eng.asarray(v)
+    if _shape(v) == (K,):
+        raise ValueError(f"psis_batched: lp returned ({K},) sums: PSIS needs the ({K}, {S}) values per row -- give lp_rows "
+                         "(BatchedGaussianTarget.lp_rows) or a log-density that returns (K, rows)")
+    if _shape(v) != (K, S):
+        raise ValueError(f"psis_batched: lp returned shape {_shape(v)}: expected ({K}, {S}) values")
+    logr, lw, khat, ess, log_z, mean_is, cov_is, info = eng.psis_batched(mu, cv, X, v, moments=bool(moments))
+    return _result(eng, as_torch, S, 2, khat, ess, log_z, lw, logr, X, mean_is, cov_is, info)
+
+
+def psis_weights_batched(log_ratios, *, as_torch=False, engine=None):
+    """The PSIS stage alone on the caller's own log ratios (K, S), 5 <= S <= 4096, one launch (gsmvi_psis_weights_batched_f64):
+    returns a ``PSISBatchedResult`` whose ``samples``, ``mean`` and ``cov`` are None.  A shape that is not (K, S) or S out of
+    bounds raises ValueError before any device work."""
+    sh = _shape(log_ratios)
+    if len(sh) != 2 or sh[0] < 1:
+        raise ValueError(f"psis_weights_batched: log_ratios must be (K, S), got {sh}")
+    K, S = sh
+    if not MIN_DRAWS <= S <= MAX_DRAWS:
+        raise ValueError(f"psis_weights_batched: S = {S} is outside {MIN_DRAWS} <= S <= {MAX_DRAWS}")
+    if engine is None:
+        from .engine import get_engine
+        engine = get_engine()
+    eng = engine
+    logr = eng.asarray(log_ratios)
+    lw, khat, ess, log_z, info = eng.psis_weights_batched(logr)
+    return _result(eng, as_torch, S, 1, khat, ess, log_z, lw, logr, None, None, None, info)

@@ -585,7 +585,8 @@ class HipEngine:
                  "scalars_fast": 0x20, "scalars_generic": 0x40, "cov_sym": 0x80, "cov_generic": 0x100, "fupd_fast": 0x200,
                  "fupd_generic": 0x400, "lowrank_fast": 0x800, "lowrank_generic": 0x1000, "batched": 0x2000,
                  "batched_bam": 0x4000, "batched_kl": 0x8000, "batched_advi": 0x10000, "batched_target": 0x20000,
-                 "batched_lbfgs": 0x40000, "batched_laplace": 0x80000, "batched_predict": 0x100000}
+                 "batched_lbfgs": 0x40000, "batched_laplace": 0x80000, "batched_predict": 0x100000,
+                 "batched_psis": 0x200000}
     PATH_GENERIC_MASK = 0x4 | 0x10 | 0x40 | 0x100 | 0x400 | 0x1000
 
     def last_path(self, reset=True):
@@ -1074,6 +1075,41 @@ class HipEngine:
             self._packed(gl, (Q,), "gh_logw"), self._packed(em, (K, M), "eta_mean"), self._packed(ev, (K, M), "eta_var"),
             self._packed(pm, (K, M), "pmean"), self._dp(lpd, (K, M), "lpd"), self._dp(elpd, (K,), "elpd")))
         return em, ev, pm, lpd, elpd
+
+    # ---- batched Pareto-smoothed importance diagnostic of K fitted Gaussians (csrc/gsmvi_psis_batched.hip) ----------------------
+    def psis_weights_batched(self, logr):
+        """The PSIS stage on the log ratios logr (K, S), 5 <= S <= 4096, one launch (gsmvi_psis_weights_batched_f64; the steps
+        are in include/gsmvi_hip.h): returns (lw (K, S) normalised smoothed log weights, khat (K,), ess (K,), log_z (K,), info
+        (K,) int32: 0, -1 = non-finite ratios (the problem's outputs are NaN), -2 = tail too short to fit (khat = +inf))."""
+        logr = logr.contiguous()
+        K, S = logr.shape
+        self._ensure(max(self._max_D, 1), max(self._max_B, 1))
+        lw, khat, ess, log_z, info = self.empty(K, S), self.empty(K), self.empty(K), self.empty(K), self.batched_ints(K)
+        _lib.check("gsmvi_psis_weights_batched_f64", self.lib.gsmvi_psis_weights_batched_f64(
+            self._ctx, self._stream(), K, S, self._packed(logr, (K, S), "logr"), self._packed(lw, (K, S), "lw"),
+            self._packed(khat, (K,), "khat"), self._packed(ess, (K,), "ess"), self._packed(log_z, (K,), "log_z"),
+            self._ints(info, K, "info")))
+        return lw, khat, ess, log_z, info
+
+    def psis_batched(self, mean, cov, X, lp, moments=True):
+        """The fused diagnostic of q_k = N(mean_k, cov_k) from its draws X (K, S, D) and the target's values lp (K, S) at them,
+        one launch (gsmvi_psis_batched_f64): log q_k per row by forward substitution with the upper factor of cov_k, the PSIS
+        stage on logr = lp - log q, and with ``moments`` the importance-weighted mean and covariance.  Returns (logr (K, S), lw
+        (K, S), khat, ess, log_z (K,), mean_is (K, D), cov_is (K, D, D) -- both None without ``moments`` --, info (K,) int32:
+        psis_weights_batched's codes, or 1 + the first bad pivot of cov_k, whose outputs are all NaN)."""
+        K, S, D = X.shape
+        self._ensure(max(self._max_D, 1), max(self._max_B, 1))
+        mean, cov, X, lp = mean.contiguous(), cov.contiguous(), X.contiguous(), lp.contiguous()
+        logr, lw, khat, ess, log_z = self.empty(K, S), self.empty(K, S), self.empty(K), self.empty(K), self.empty(K)
+        mean_is, cov_is = (self.empty(K, D), self.empty(K, D, D)) if moments else (None, None)
+        info = self.batched_ints(K)
+        _lib.check("gsmvi_psis_batched_f64", self.lib.gsmvi_psis_batched_f64(
+            self._ctx, self._stream(), K, D, S, self._packed(mean, (K, D), "mean"), self._packed(cov, (K, D, D), "cov"),
+            self._packed(X, (K, S, D), "X"), self._packed(lp, (K, S), "lp"), self._packed(logr, (K, S), "logr"),
+            self._packed(lw, (K, S), "lw"), self._packed(khat, (K,), "khat"), self._packed(ess, (K,), "ess"),
+            self._packed(log_z, (K,), "log_z"), self._dp(mean_is, (K, D), "mean_is"), self._dp(cov_is, (K, D, D), "cov_is"),
+            self._ints(info, K, "info")))
+        return logr, lw, khat, ess, log_z, mean_is, cov_is, info
 
     def bam_update(self, X, G, mu0, S0, reg, jitter=0.0, out=None, flag=None):
         """(mu, S) of BaM [gsmvi/bam.py:72-114]; S symmetrised, jitter on the diagonal."""

@@ -123,6 +123,13 @@ class BatchedGaussianTarget:
         r = self.mean[:, None, :] - x
         return -0.5 * torch.einsum("kbi,kij,kbj->k", r, self.P, r)
 
+    def lp_rows(self, x):
+        """(K, rows) values -1/2 (m_k - x_kr)^T P_k (m_k - x_kr) at the rows of x (K, rows, D): what ``psis_batched`` needs (``lp``
+        returns their sums); plain torch (off the hot path)."""
+        x = self.engine.asarray(x)
+        r = self.mean[:, None, :] - x
+        return -0.5 * torch.einsum("kbi,kij,kbj->kb", r, self.P, r)
+
 
 def _host_array(x):
     """numpy view or copy of a host array or of a tensor on any device (validation only)"""

@@ -25,6 +25,8 @@
  *   initializers.py:5-17 lbfgs_init (maximiser of lp, dense inverse-Hessian estimate), K problems -> gsmvi_lbfgs_step_batched_f64, gsmvi_lbfgs_hess_inv_batched_f64
  *   initializers.py:5-17 the same role by Newton rounds on the GLMs of examples/example_gsm.py:34-35 (no reference twin) -> gsmvi_glm_hessian_batched_f64, gsmvi_laplace_step_batched_f64
  *   examples/example_gsm.py:34-35 the use of the fit: predictions and the held-out score of K fitted GLMs (no reference twin) -> gsmvi_glm_predict_batched_f64
+ *   monitors.py:83-125 the role (is q_k close to its target?), per problem and comparable across problems: the Pareto-smoothed
+ *   importance diagnostic of K fitted Gaussians (no reference twin)    ->  gsmvi_psis_batched_f64, gsmvi_psis_weights_batched_f64
  *   gsmvi/bam.py:72-114       bam_lowrank_update(samples,vs,mu0,S0,reg) ->  gsmvi_bam_update_f64
  *   gsmvi/bam.py:31-69        bam_update(samples,vs,mu0,S0,reg)         ->  gsmvi_bam_update_f64 (same result, K6)
  *
@@ -272,6 +274,7 @@ int gsmvi_get_profile(gsmvi_ctx* ctx, float* ms, int n);
 #define GSMVI_PATH_BATCHED_LBFGS 0x40000u  /* k_lbfgs_step_batched / k_lbfgs_hess_inv_batched: the batched initialiser   */
 #define GSMVI_PATH_BATCHED_LAPLACE 0x80000u /* k_laplace_batched: the batched GLM Hessian and Newton step             */
 #define GSMVI_PATH_BATCHED_PREDICT 0x100000u /* k_glm_predict_batched: the batched GLM posterior predictive             */
+#define GSMVI_PATH_BATCHED_PSIS 0x200000u /* k_psis_batched: the batched Pareto-smoothed importance diagnostic            */
 #define GSMVI_PATH_GENERIC_MASK (0x0004u | 0x0010u | 0x0040u | 0x0100u | 0x0400u | 0x1000u)
 int gsmvi_last_path(gsmvi_ctx* ctx, unsigned* bits, int reset);
 
@@ -616,6 +619,51 @@ int gsmvi_glm_predict_batched_f64(gsmvi_ctx* ctx, void* stream, int64_t K, int D
                                   const double* noise_prec_dev, const double* mean, const double* cov, int Q, const double* gh_t,
                                   const double* gh_logw, double* eta_mean, double* eta_var, double* pmean, double* lpd,
                                   double* elpd);
+
+/*
+ * Batched Pareto-smoothed importance sampling (PSIS) diagnostic: can the fitted q_k = N(mean_k, cov_k) of K problems of one D be
+ * trusted as an importance proposal for its target?  The reference's monitor (monitors.py:83-125) answers with a reverse KL up to
+ * each target's unknown constant; this answers per problem on one scale (Vehtari, Simpson, Gelman, Yao, Gabry, "Pareto smoothed
+ * importance sampling", JMLR 2024; tail fit: Zhang & Stephens 2009 with the weakly informative prior), with no reference twin.
+ * One launch, one problem per workgroup.
+ * gsmvi_psis_weights_batched_f64 runs the PSIS stage on the caller's log ratios logr (K x S); for each problem k:
+ *   1. a NaN or +inf among the S ratios, or every ratio -inf: info[k] = -1 and every output of k is NaN (-inf alone is legal:
+ *      a point outside the support, weight 0)
+ *   2. lw = logr - max(logr);  M = ceil(min(S / 5, 3 sqrt(S)))
+ *   3. sort ascending by (value, row) -- numpy's stable argsort;  cutoff = max(sorted[S - M - 1], log(DBL_MIN));  the tail is the
+ *      n entries with lw > cutoff (ties at the cutoff stay out)
+ *   4. n <= 4: khat = +inf, info[k] = -2, no smoothing (steps 7-8 still run)
+ *   5. else x_i = exp(tail_i) - exp(cutoff) ascending, m = 30 + floor(sqrt(n)), and for j = 1 .. m
+ *        b_j = (1 - sqrt(m / (j - 1/2))) / (3 x[floor(n / 4 + 1/2) - 1]) + 1 / x[n - 1]      (0-based x)
+ *        kappa_j = mean_i log1p(-b_j x_i),   L_j = n (log(-b_j / kappa_j) - kappa_j - 1),   omega_j = 1 / sum_i exp(L_i - L_j)
+ *      every omega_j < 10 DBL_EPSILON is dropped and the rest renormalised;  b = sum_j omega_j b_j,  kappa = mean_i log1p(-b x_i),
+ *      sigma = -kappa / b,  khat = (n kappa + 5) / (n + 10)
+ *   6. khat finite: the i-th smallest tail entry becomes log(sigma expm1(-khat log1p(-p_i)) / khat + exp(cutoff)), p_i = (i + 1/2) / n
+ *      (khat == 0: -sigma log1p(-p_i) in place of the first term)
+ *   7. lw = lw > 0 ? 0 : lw
+ *   8. lse = log sum exp(lw);  lw[k] = lw - lse (K x S, in row order);  ess[k] = 1 / sum exp(2 (lw - lse));
+ *      log_z[k] = lse + max(logr) - log S (the estimate of the log normalising constant);  khat[k], info[k] as above (0 = fitted)
+ * khat below min(1 - 1 / log10(S), 0.7) says the proposal is usable.  Every sum is a fixed tree (a thread's entries in order, a
+ * butterfly within each wave, the waves in order; no atomics), so the outputs are bit-identical from run to run.
+ * gsmvi_psis_batched_f64 is the fused entry: X (K x S x D) are draws of q_k and lp (K x S) the target's values at them.  Per problem:
+ *   a. R = the upper Cholesky factor of cov_k (only its upper triangle is read); a pivot that is not > 0 and finite: info[k] = 1 + that
+ *      pivot and every output of k is NaN.  Else for each row R^T w = x_s - mean_k by forward substitution,
+ *      logq_s = -|w|^2 / 2 - sum_i log R_ii - D / 2 log 2 pi, and logr[k, s] = lp_s - logq_s (K x S, written as computed even where
+ *      step 1 then refuses them: the caller sees which row was not finite)
+ *   b. the PSIS stage above on logr[k]
+ *   c. with mean_is (K x D) and cov_is (K x D x D) -- both or neither --, w_s = exp(lw_s) and d_s = x_s - mean_k:
+ *      mean_is[k] = mean_k + sum_s w_s d_s,  cov_is[k] = sum_s w_s d_s d_s^T - (sum_s w_s d_s)(sum_s w_s d_s)^T, exactly symmetric;
+ *      each entry is summed in row order by one thread (a second read of X_k)
+ * 5 <= S <= 4096, 1 <= D <= 64, K >= 1 with the grid limit of one problem per workgroup (K <= 2^24 - 1).  Shapes, NULL arrays and
+ * overlaps (every output is a written array) are checked before the context is looked at (then a NULL ctx); every failure returns
+ * GSMVI_ERR_BAD_ARG before anything is enqueued.  Inputs are only read; no context workspace is used; one capturable launch with no
+ * host synchronisation.  Both set GSMVI_PATH_BATCHED_PSIS.
+ */
+int gsmvi_psis_weights_batched_f64(gsmvi_ctx* ctx, void* stream, int64_t K, int64_t S, const double* logr, double* lw,
+                                   double* khat, double* ess, double* log_z, int* info);
+int gsmvi_psis_batched_f64(gsmvi_ctx* ctx, void* stream, int64_t K, int D, int64_t S, const double* mean, const double* cov,
+                           const double* X, const double* lp, double* logr, double* lw, double* khat, double* ess,
+                           double* log_z, double* mean_is, double* cov_is, int* info);
 
 /*
  * Upper Cholesky factor R (R^T R = S, R upper triangular, strictly-lower part zeroed) of a
