@@ -1,5 +1,6 @@
 // Shared pieces of the batched kernels (gsmvi_batched.hip: GSM, gsmvi_bam_batched.hip: BaM, gsmvi_kl_batched.hip: the KL
-// monitor): the bounds, the argument block, the in-LDS Cholesky, and the tail of a fit step that both
+// monitor; the GLM, L-BFGS, Laplace, predictive and PSIS files): the bounds, the argument block, the wave
+// butterflies, the in-LDS Cholesky, the host-side argument checks, and the tail of a fit step that both
 // methods run on their new covariance S' -- the Cholesky test, per-problem accept or revert of (mean, cov, sampling factor),
 // and the next samples from the problem's Philox stream.
 #pragma once
@@ -40,6 +41,22 @@ struct gb_args {
 __host__ __device__ inline int gb_dz(int D) { return D + (D & 1); }
 // threads per problem: four problems (one wave each) per 256-thread workgroup for D <= 16, one problem above
 static inline int gb_nt(int D) { return D <= 16 ? 64 : 256; }
+
+// The 64-lane butterflies of the kernels that keep a vector of D <= 64 components one wave wide (L-BFGS, Laplace): a fixed
+// order that depends on nothing but the lanes' values, and no barrier
+__device__ __forceinline__ double gb_wave_sum(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    return v;
+}
+
+__device__ __forceinline__ double gb_wave_max(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o));
+    return v;
+}
+
+__device__ __forceinline__ bool gb_finite(double v) { return fabs(v) < __builtin_huge_val(); }
 
 // Upper Cholesky factor of the problem of one workgroup slot, in place in LDS (S: D x D, row stride ld; only its upper
 // triangle is read).  Right-looking, one pivot per barrier (unscaled rows: row c is final after step c and is scaled by
@@ -198,15 +215,18 @@ struct gb_arr {
 
 // The overlap rule of every batched entry point: an array that is written must not overlap any other listed array; read-only
 // arrays may overlap each other; NULL entries are skipped.  The message names both arrays.
-static inline int gb_check_overlaps(const char* fn, std::initializer_list<gb_arr> arrs) {
-    for (const gb_arr* a = arrs.begin(); a != arrs.end(); ++a)
-        for (const gb_arr* b = arrs.begin(); b != a; ++b)
+static inline int gb_check_overlaps(const char* fn, const gb_arr* first, const gb_arr* last) {
+    for (const gb_arr* a = first; a != last; ++a)
+        for (const gb_arr* b = first; b != a; ++b)
             if (a->p && b->p && (a->written || b->written) && gb_overlap(a->p, a->bytes, b->p, b->bytes)) {
                 char msg[96];
                 snprintf(msg, sizeof msg, "%s overlaps %s", (a->written ? a : b)->name, (a->written ? b : a)->name);
                 return gb_bad(fn, msg);
             }
     return GSMVI_OK;
+}
+static inline int gb_check_overlaps(const char* fn, std::initializer_list<gb_arr> arrs) {
+    return gb_check_overlaps(fn, arrs.begin(), arrs.end());
 }
 
 // the end of every batched launch: a launch error -> GSMVI_ERR_HIP, else the kernel family's path bit is recorded

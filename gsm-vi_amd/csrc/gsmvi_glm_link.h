@@ -1,5 +1,6 @@
 // The links of the batched GLM kernels (gsmvi_logistic_batched.hip: score and density; gsmvi_laplace_batched.hip: Hessian and
-// Newton step): r = dt / d eta and t of family FAM (lb_link), and the weight w = -dr / d eta (lb_weight).
+// Newton step; gsmvi_glm_predict_batched.hip: the predictive): r = dt / d eta and t of family FAM
+// (lb_link), and the weight w = -dr / d eta (lb_weight).  What surrounds the kernels is in gsmvi_glm_model.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include "../../include/gsmvi_hip.h"

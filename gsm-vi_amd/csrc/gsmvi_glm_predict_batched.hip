@@ -29,10 +29,12 @@
 // Order: every sum of a row is taken in an order fixed by D and Q alone; elpd runs n = 0 .. n_k - 1 in one thread.  A slot reads
 // and writes only slice k of every array and every slot of a workgroup runs the same barriers.  Rows n >= n_k are never loaded;
 // their outputs are NaN.  A row whose m or v is not finite has NaN outputs (and makes elpd[k] NaN).  No context workspace.
+// The new rows are a glm_model (gp_args::m: N = M, y or null, no prior): its checks, overlap entries, family dispatch and
+// per-problem prologue are gsmvi_glm_model.h's, shared with the score and Laplace entries.
 #include "gsmvi_common.h"
 #include "gsmvi_ctx.h"
 #include "gsmvi_batched.h"
-#include "gsmvi_glm_link.h"
+#include "gsmvi_glm_model.h"
 #include "../../include/gsmvi_hip.h"
 #include <cmath>
 #include <cstdint>
@@ -44,14 +46,7 @@
 #define GP_NROW 6      // per-row LDS arrays of a tile: y, o, m, s, lpd, bad
 
 struct gp_args {
-    long long K, M;
-    int D, Q;
-    const double* A;            // (K, M, D)
-    const double* offset;       // (K, M) or null
-    const double* y;            // (K, M) or null
-    const int* counts;          // (K) valid rows, clamped to 0 .. M (null: M)
-    double tau;
-    const double* tau_dev;
+    glm_model m;                // the new rows: N = M, y (K, M) or null, no prior
     const double* mean;         // (K, D)
     const double* cov;          // (K, D, D)
     const double* gh_t;         // (Q)
@@ -61,32 +56,30 @@ struct gp_args {
     double* pmean;              // (K, M)
     double* lpd;                // (K, M), with y
     double* elpd;               // (K), with y
+    int Q;
 };
 
-__host__ __device__ inline int gp_dp(int D) { return ((D + 15) >> 4) << 4; }
 // doubles of the tile region: the A tile (32 x (Dp + 1)), later the node values of NT / 8 rows (GP_LF each)
 __host__ __device__ inline int gp_tile_doubles(int D, int nt) {
-    const int t = LB_TN * (gp_dp(D) + 1), f = (nt / GP_QL) * GP_LF;
+    const int t = LB_TN * (glm_dp(D) + 1), f = (nt / GP_QL) * GP_LF;
     return t > f ? t : f;
 }
 // LDS doubles per problem: Sigma (Dp x (Dp + 1)), mu (Dp), the tile region, six per-row arrays and the Dp / 16 partial sums of v
 // (32 each).  D = 64: 6624 doubles; with the workgroup's quadrature table (3 x 64) 53.25 KB.  Four problems of D = 16: 34.5 KB
 __host__ __device__ inline int gp_lds_doubles(int D, int nt) {
-    const int Dp = gp_dp(D);
+    const int Dp = glm_dp(D);
     return Dp * (Dp + 1) + Dp + gp_tile_doubles(D, nt) + GP_NROW * LB_TN + (Dp / 16) * LB_TN;
 }
-
-__device__ __forceinline__ bool gp_finite(double v) { return fabs(v) < __builtin_huge_val(); }
 
 template <int NT, int FAM>
 __global__ __launch_bounds__(256) void k_glm_predict_batched(gp_args a) {
     extern __shared__ double gp_sm[];
     constexpr int PPW = 256 / NT, NW = NT / 64, NG = NT / LB_TN, RG = NT / GP_QL, NGRP = LB_TN / RG;
-    const int D = a.D, Q = a.Q, nb = (D + 15) >> 4, Dp = nb * 16, lda = Dp + 1, DD = D * D;
-    const long long M = a.M;
+    const int D = a.m.D, Q = a.Q, nb = (D + 15) >> 4, Dp = nb * 16, lda = Dp + 1, DD = D * D;
+    const long long M = a.m.N;
     const int slot = threadIdx.x / NT, l = threadIdx.x % NT;
     const long long k = (long long)blockIdx.x * PPW + slot;
-    const bool valid = k < a.K, hasy = a.y != nullptr;
+    const bool valid = k < a.m.K, hasy = a.m.y != nullptr;
     const bool quad = FAM == LB_LOGISTIC || (hasy && FAM != LB_GAUSSIAN);       // (uniform in the launch)
     const size_t kk = (size_t)(valid ? k : 0);
     double* gt = gp_sm;                       // the nodes, the logarithms of the weights, the weights: one copy per workgroup
@@ -104,23 +97,16 @@ __global__ __launch_bounds__(256) void k_glm_predict_batched(gp_args a) {
     double* Vp = Bd + LB_TN;                  // nb x 32 partial sums of v
     const double qnan = __longlong_as_double(0x7ff8000000000000LL);
 
-    const double* Ak = a.A + kk * (size_t)M * D;
-    const double* yk = hasy ? a.y + kk * (size_t)M : nullptr;
-    const double* ok_ = a.offset ? a.offset + kk * (size_t)M : nullptr;
+    const double* Ak = a.m.A + kk * (size_t)M * D;
+    const double* yk = hasy ? a.m.y + kk * (size_t)M : nullptr;
+    const double* ok_ = a.m.offset ? a.m.offset + kk * (size_t)M : nullptr;
     double* em = a.eta_mean + kk * (size_t)M;
     double* ev = a.eta_var + kk * (size_t)M;
     double* pm = a.pmean + kk * (size_t)M;
     double* lp = hasy ? a.lpd + kk * (size_t)M : nullptr;
-    long long nk = 0;                         // the rows that count (a slot without a problem: none, so nothing is loaded)
-    double tau = 1.0;
-    if (valid) {
-        nk = M;
-        if (a.counts) {
-            const long long c = a.counts[k];
-            nk = c < 0 ? 0 : (c > M ? M : c);
-        }
-        if (FAM == LB_GAUSSIAN) tau = a.tau_dev ? a.tau_dev[k] : a.tau;
-    }
+    const glm_problem pk = glm_problem_of<FAM>(a.m, k, valid);
+    const long long nk = pk.nk;               // the rows that count (a slot without a problem: none, so nothing is loaded)
+    const double tau = pk.tau;
     if ((int)threadIdx.x < Q) {
         const double lw = a.gh_logw[threadIdx.x];
         gt[threadIdx.x] = a.gh_t[threadIdx.x];
@@ -235,7 +221,7 @@ __global__ __launch_bounds__(256) void k_glm_predict_batched(gp_args a) {
             double v = 0.0;
             for (int jb = 0; jb < nb; ++jb) v += Vp[jb * LB_TN + n];
             const double m = Ms[n];
-            const bool bad = !(gp_finite(m) && gp_finite(v));
+            const bool bad = !(gb_finite(m) && gb_finite(v));
             const double vp = v > 0.0 ? v : 0.0;
             Hs[n] = sqrt(2.0 * vp);
             Bd[n] = bad ? 1.0 : 0.0;
@@ -332,23 +318,6 @@ static size_t gp_launch_lds(int D, int* ppw) {
     return ((size_t)3 * GP_MAXQ + (size_t)*ppw * gp_lds_doubles(D, nt)) * sizeof(double);
 }
 
-static void gp_go(int family, int ppw, unsigned grid, size_t lds, hipStream_t st, const gp_args& a) {
-#define GP_GO(FAM)                                                                                     \
-    do {                                                                                               \
-        if (ppw == 4)                                                                                  \
-            hipLaunchKernelGGL((k_glm_predict_batched<64, FAM>), dim3(grid), dim3(256), lds, st, a);   \
-        else                                                                                           \
-            hipLaunchKernelGGL((k_glm_predict_batched<256, FAM>), dim3(grid), dim3(256), lds, st, a);  \
-    } while (0)
-    switch (family) {
-        case GSMVI_GLM_LOGISTIC: GP_GO(LB_LOGISTIC); break;
-        case GSMVI_GLM_POISSON: GP_GO(LB_POISSON); break;
-        case GSMVI_GLM_PROBIT: GP_GO(LB_PROBIT); break;
-        default: GP_GO(LB_GAUSSIAN); break;
-    }
-#undef GP_GO
-}
-
 extern "C" {
 
 int gsmvi_glm_predict_batched_f64(gsmvi_ctx* ctx, void* stream, int64_t K, int D, int64_t M, int family, const double* A,
@@ -356,35 +325,30 @@ int gsmvi_glm_predict_batched_f64(gsmvi_ctx* ctx, void* stream, int64_t K, int D
                                   const double* noise_prec_dev, const double* mean, const double* cov, int Q, const double* gh_t,
                                   const double* gh_logw, double* eta_mean, double* eta_var, double* pmean, double* lpd,
                                   double* elpd) {
-    if (int st = gb_check_shape(__func__, K, D, gb_ppw)) return st;
-    GB_BAD(M < 1, "M must be at least 1");
-    GB_BAD(M > (INT64_MAX / 8 / D) / K, "K M D is too large");
-    GB_BAD(family < GSMVI_GLM_LOGISTIC || family > GSMVI_GLM_GAUSSIAN, "family must be one of GSMVI_GLM_LOGISTIC .. GSMVI_GLM_GAUSSIAN");
-    if (family == GSMVI_GLM_GAUSSIAN)
-        GB_BAD(!noise_prec_dev && !(noise_prec > 0.0 && noise_prec < __builtin_huge_val()), "noise_prec must be finite and > 0");
-    else
-        GB_BAD(noise_prec_dev || noise_prec != 1.0, "noise_prec is the gaussian family's: give 1.0 and NULL for any other");
+    const glm_model m = {K, M, D, A, y, offset, counts_dev, 0.0, nullptr, noise_prec, noise_prec_dev};
+    if (int st = glm_check_model(__func__, m, family, "M", false)) return st;
     GB_BAD(Q < 1 || Q > GP_MAXQ, "Q must be in [1, 64]");
     GB_BAD(!A || !mean || !cov || !gh_t || !gh_logw || !eta_mean || !eta_var || !pmean, "NULL array");
     GB_BAD((y != nullptr) != (lpd != nullptr) || (y != nullptr) != (elpd != nullptr),
            "lpd and elpd are required with y and only with it");
-    const size_t na = (size_t)K * M * D * 8, nm = (size_t)K * M * 8, nx = (size_t)K * D * 8, nh = nx * D, nk = (size_t)K * 8,
-                 ni = (size_t)K * 4, nq = (size_t)Q * 8;
-    if (int st = gb_check_overlaps(__func__, {{A, na, "A", GB_RD}, {offset, nm, "offset", GB_RD}, {y, nm, "y", GB_RD},
-                                              {counts_dev, ni, "counts_dev", GB_RD}, {noise_prec_dev, nk, "noise_prec_dev", GB_RD},
-                                              {mean, nx, "mean", GB_RD}, {cov, nh, "cov", GB_RD}, {gh_t, nq, "gh_t", GB_RD},
-                                              {gh_logw, nq, "gh_logw", GB_RD}, {eta_mean, nm, "eta_mean", GB_WR},
-                                              {eta_var, nm, "eta_var", GB_WR}, {pmean, nm, "pmean", GB_WR}, {lpd, nm, "lpd", GB_WR},
-                                              {elpd, nk, "elpd", GB_WR}}))
+    const size_t nm = (size_t)K * M * 8, nx = (size_t)K * D * 8, nq = (size_t)Q * 8;
+    if (int st = gb_check_overlaps(__func__, m, {{mean, nx, "mean", GB_RD}, {cov, nx * D, "cov", GB_RD}, {gh_t, nq, "gh_t", GB_RD},
+                                                 {gh_logw, nq, "gh_logw", GB_RD}, {eta_mean, nm, "eta_mean", GB_WR},
+                                                 {eta_var, nm, "eta_var", GB_WR}, {pmean, nm, "pmean", GB_WR}, {lpd, nm, "lpd", GB_WR},
+                                                 {elpd, (size_t)K * 8, "elpd", GB_WR}}))
         return st;
     GB_BAD(!ctx, "ctx is NULL");
-    gp_args a = {};
-    a.K = K; a.M = M; a.D = D; a.Q = Q; a.A = A; a.offset = offset; a.y = y; a.counts = counts_dev; a.tau = noise_prec;
-    a.tau_dev = noise_prec_dev; a.mean = mean; a.cov = cov; a.gh_t = gh_t; a.gh_logw = gh_logw; a.eta_mean = eta_mean;
-    a.eta_var = eta_var; a.pmean = pmean; a.lpd = lpd; a.elpd = elpd;
+    const gp_args a = {m, mean, cov, gh_t, gh_logw, eta_mean, eta_var, pmean, lpd, elpd, Q};
     int ppw;
     const size_t lds = gp_launch_lds(D, &ppw);
-    gp_go(family, ppw, (unsigned)((K + ppw - 1) / ppw), lds, reinterpret_cast<hipStream_t>(stream), a);
+    const unsigned grid = (unsigned)((K + ppw - 1) / ppw);
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    glm_for_family(family, [&](auto fam) {
+        if (ppw == 4)
+            hipLaunchKernelGGL((k_glm_predict_batched<64, decltype(fam)::value>), dim3(grid), dim3(256), lds, st, a);
+        else
+            hipLaunchKernelGGL((k_glm_predict_batched<256, decltype(fam)::value>), dim3(grid), dim3(256), lds, st, a);
+    });
     return gb_launched(ctx, GSMVI_PATH_BATCHED_PREDICT, "k_glm_predict_batched");
 }
 

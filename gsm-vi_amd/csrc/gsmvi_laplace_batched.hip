@@ -32,10 +32,12 @@
 // the barriers of the sweep beside its running neighbours.  A workgroup all of whose problems are frozen leaves at once.
 // Ordering in the Hessian entry: H is written from LDS (the lower triangle from the mirrored cells, which other threads own),
 // then a barrier, then the factorisation overwrites those cells in place.  Inputs are only read; no context workspace.
+// The model's fields (lp_args::m), their checks, their overlap entries, the dispatch on the family and the per-problem prologue
+// are gsmvi_glm_model.h's, shared with the score and predictive entries; the butterflies are gsmvi_batched.h's.
 #include "gsmvi_common.h"
 #include "gsmvi_ctx.h"
 #include "gsmvi_batched.h"
-#include "gsmvi_glm_link.h"
+#include "gsmvi_glm_model.h"
 #include "../../include/gsmvi_hip.h"
 #include <cmath>
 #include <cstdint>
@@ -49,16 +51,8 @@ enum { LP_STATUS = 0, LP_NIT = 1, LP_NFEV = 2, LP_NLS = 3 };
 enum { LP_HESS = 0, LP_STEP = 1 };
 
 struct lp_args {
-    long long K, N;
-    int D, start;
-    const double* A;            // (K, N, D)
-    const double* y;            // (K, N)
-    const double* offset;       // (K, N) or null
-    const int* counts;          // (K) valid rows, clamped to 0 .. N (null: N)
-    double lam;
-    const double* lam_dev;
-    double tau;
-    const double* tau_dev;
+    glm_model m;
+    int start;
     // LP_HESS
     const double* X;            // (K, D)
     double* H;                  // (K, D, D) or null
@@ -76,27 +70,12 @@ struct lp_args {
     double gtol;
 };
 
-__host__ __device__ inline int lp_dp(int D) { return ((D + 15) >> 4) << 4; }
 // LDS doubles per problem: the A tile (32 x (Dp + 1)), y, offset, r, w, t of its rows (32 each), x, g, pivots, the diagonal of H
 // and the diagonal of R^{-1} (Dp each), four cells, H (D x (D | 1)).  D = 64: 6724 doubles, 52.5 KB; four problems of D = 16: 33 KB
 __host__ __device__ inline int lp_lds_doubles(int D) {
-    const int Dp = lp_dp(D);
+    const int Dp = glm_dp(D);
     return LB_TN * (Dp + 1) + 5 * LB_TN + 5 * Dp + 4 + D * (D | 1);
 }
-
-__device__ __forceinline__ double lp_wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
-__device__ __forceinline__ double lp_wave_max(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o));
-    return v;
-}
-
-__device__ __forceinline__ bool lp_finite(double v) { return fabs(v) < __builtin_huge_val(); }
 
 // gb_chol_lds with the relative pivot rule (dg: the diagonal of S before the factorisation): 0, or 1 + the first pivot that is
 // not finite or not > 64 eps dg[c].  `on` is uniform in the slot; every slot runs the D barriers.
@@ -143,11 +122,11 @@ __global__ __launch_bounds__(256) void k_laplace_batched(lp_args a) {
     constexpr int MAXT = NT == 256 ? 3 : 1;       // 16 x 16 blocks of H per wave
     constexpr int MAXE = NT == 256 ? 16 : 4;      // entries of H per thread
     constexpr bool STEP = MODE == LP_STEP;
-    const int D = a.D, nb = (D + 15) >> 4, Dp = nb * 16, lda = Dp + 1, ldh = D | 1, DD = D * D;
-    const long long N = a.N;
+    const int D = a.m.D, nb = (D + 15) >> 4, Dp = nb * 16, lda = Dp + 1, ldh = D | 1, DD = D * D;
+    const long long N = a.m.N;
     const int slot = threadIdx.x / NT, l = threadIdx.x % NT;
     const long long k = (long long)blockIdx.x * PPW + slot;
-    const bool valid = k < a.K;
+    const bool valid = k < a.m.K;
     const size_t kk = (size_t)(valid ? k : 0), kd = kk * D;
     double* As = lp_sm + (size_t)slot * lp_lds_doubles(D);
     double* Ys = As + LB_TN * lda;
@@ -178,20 +157,12 @@ __global__ __launch_bounds__(256) void k_laplace_batched(lp_args a) {
         if (!__syncthreads_or(live)) return;  // every problem of the workgroup is frozen (uniform)
     }
 
-    const double* Ak = a.A + kk * (size_t)N * D;
-    const double* yk = a.y + kk * (size_t)N;
-    const double* ok_ = a.offset ? a.offset + kk * (size_t)N : nullptr;
-    long long nk = 0;                         // the rows that count (a frozen slot: none, so nothing of A_k is loaded)
-    double lam = 0.0, tau = 1.0;
-    if (live) {
-        nk = N;
-        if (a.counts) {
-            const long long c = a.counts[k];
-            nk = c < 0 ? 0 : (c > N ? N : c);
-        }
-        lam = a.lam_dev ? a.lam_dev[k] : a.lam;
-        if (FAM == LB_GAUSSIAN) tau = a.tau_dev ? a.tau_dev[k] : a.tau;
-    }
+    const double* Ak = a.m.A + kk * (size_t)N * D;
+    const double* yk = a.m.y + kk * (size_t)N;
+    const double* ok_ = a.m.offset ? a.m.offset + kk * (size_t)N : nullptr;
+    const glm_problem pk = glm_problem_of<FAM>(a.m, k, live);
+    const long long nk = pk.nk;               // the rows that count (a frozen slot: none, so nothing of A_k is loaded)
+    const double lam = pk.lam, tau = pk.tau;
     for (int e = l; e < LB_TN * lda; e += NT) As[e] = 0.0;          // the padding columns stay zero
     if (l < Dp) {
         const double* xsrc = STEP ? a.Xt : a.X;
@@ -348,15 +319,15 @@ __global__ __launch_bounds__(256) void k_laplace_batched(lp_args a) {
     }
     __syncthreads();
     // a non-finite x or a flagged poisson row (uniform in the slot: every wave forms it from the same numbers)
-    const bool bad = !(lp_wave_sum(ln < D ? xs[ln] * 0.0 : 0.0) == 0.0) || !(cell[0] == 0.0);
+    const bool bad = !(gb_wave_sum(ln < D ? xs[ln] * 0.0 : 0.0) == 0.0) || !(cell[0] == 0.0);
 
     double ft = 0.0, gtl = 0.0, gmax = 0.0;
     bool fin = false, ok = false, need = false;
     if (STEP) {
         ft = bad ? qnan : cell[1];
         gtl = ln < D ? (bad ? qnan : gs[ln]) : 0.0;
-        fin = !bad && lp_finite(ft) && __all(lp_finite(gtl));
-        gmax = lp_wave_max(fabs(gtl));
+        fin = !bad && gb_finite(ft) && __all(gb_finite(gtl));
+        gmax = gb_wave_max(fabs(gtl));
         if (live) {
             if (a.start)
                 need = fin && !(gmax <= a.gtol);
@@ -474,7 +445,7 @@ __global__ __launch_bounds__(256) void k_laplace_batched(lp_args a) {
         }
         dl = act ? -b : 0.0;
         t = 1.0;
-        gd = lp_wave_sum(gl * dl);
+        gd = gb_wave_sum(gl * dl);
         nls = 0;
     }
     if (act) {
@@ -503,41 +474,18 @@ static size_t lp_launch_lds(int D, int* ppw) {
 }
 
 template <int MODE>
-static void lp_go(int family, int ppw, unsigned grid, size_t lds, hipStream_t st, const lp_args& a) {
-#define LP_GO(FAM)                                                                                       \
-    do {                                                                                                 \
-        if (ppw == 4)                                                                                    \
-            hipLaunchKernelGGL((k_laplace_batched<64, FAM, MODE>), dim3(grid), dim3(256), lds, st, a);   \
-        else                                                                                             \
-            hipLaunchKernelGGL((k_laplace_batched<256, FAM, MODE>), dim3(grid), dim3(256), lds, st, a);  \
-    } while (0)
-    switch (family) {
-        case GSMVI_GLM_LOGISTIC: LP_GO(LB_LOGISTIC); break;
-        case GSMVI_GLM_POISSON: LP_GO(LB_POISSON); break;
-        case GSMVI_GLM_PROBIT: LP_GO(LB_PROBIT); break;
-        default: LP_GO(LB_GAUSSIAN); break;
-    }
-#undef LP_GO
-}
-
-// the checks that both entry points share with gsmvi_glm_batched_f64: shapes, the family and its noise precision, the prior
-static int lp_check_model(const char* fn, int64_t K, int D, int64_t N, int family, double noise_prec, const double* noise_prec_dev,
-                          double prior_prec, const double* prior_prec_dev) {
-#define LP_BAD(cond, msg)                     \
-    do {                                      \
-        if (cond) return gb_bad(fn, msg);     \
-    } while (0)
-    if (int st = gb_check_shape(fn, K, D, gb_ppw)) return st;
-    LP_BAD(N < 1, "N must be at least 1");
-    LP_BAD(N > (INT64_MAX / 8 / D) / K, "K N D is too large");
-    LP_BAD(family < GSMVI_GLM_LOGISTIC || family > GSMVI_GLM_GAUSSIAN, "family must be one of GSMVI_GLM_LOGISTIC .. GSMVI_GLM_GAUSSIAN");
-    LP_BAD(!prior_prec_dev && !(prior_prec >= 0.0 && prior_prec < __builtin_huge_val()), "prior_prec must be finite and >= 0");
-    if (family == GSMVI_GLM_GAUSSIAN)
-        LP_BAD(!noise_prec_dev && !(noise_prec > 0.0 && noise_prec < __builtin_huge_val()), "noise_prec must be finite and > 0");
-    else
-        LP_BAD(noise_prec_dev || noise_prec != 1.0, "noise_prec is the gaussian family's: give 1.0 and NULL for any other");
-#undef LP_BAD
-    return GSMVI_OK;
+static int lp_go(gsmvi_ctx* ctx, void* stream, int family, const lp_args& a) {
+    int ppw;
+    const size_t lds = lp_launch_lds(a.m.D, &ppw);
+    const unsigned grid = (unsigned)((a.m.K + ppw - 1) / ppw);
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    glm_for_family(family, [&](auto fam) {
+        if (ppw == 4)
+            hipLaunchKernelGGL((k_laplace_batched<64, decltype(fam)::value, MODE>), dim3(grid), dim3(256), lds, st, a);
+        else
+            hipLaunchKernelGGL((k_laplace_batched<256, decltype(fam)::value, MODE>), dim3(grid), dim3(256), lds, st, a);
+    });
+    return gb_launched(ctx, GSMVI_PATH_BATCHED_LAPLACE, "k_laplace_batched");
 }
 
 extern "C" {
@@ -546,25 +494,19 @@ int gsmvi_glm_hessian_batched_f64(gsmvi_ctx* ctx, void* stream, int64_t K, int D
                                   const double* y, const double* offset, const int* counts_dev, double noise_prec,
                                   const double* noise_prec_dev, double prior_prec, const double* prior_prec_dev, const double* X,
                                   double* H, double* cov, int* info_dev) {
-    if (int st = lp_check_model(__func__, K, D, N, family, noise_prec, noise_prec_dev, prior_prec, prior_prec_dev)) return st;
+    const glm_model m = {K, N, D, A, y, offset, counts_dev, prior_prec, prior_prec_dev, noise_prec, noise_prec_dev};
+    if (int st = glm_check_model(__func__, m, family, "N", true)) return st;
     GB_BAD(!A || !y || !X, "NULL array");
     GB_BAD(!H && !cov, "give H or cov (or both)");
     GB_BAD((cov != nullptr) != (info_dev != nullptr), "info_dev is required with cov and only with it");
-    const size_t na = (size_t)K * N * D * 8, ny = (size_t)K * N * 8, nx = (size_t)K * D * 8, nh = nx * D, nk = (size_t)K * 8,
-                 ni = (size_t)K * 4;
-    if (int st = gb_check_overlaps(__func__, {{A, na, "A", GB_RD}, {y, ny, "y", GB_RD}, {offset, ny, "offset", GB_RD},
-                                              {counts_dev, ni, "counts_dev", GB_RD}, {noise_prec_dev, nk, "noise_prec_dev", GB_RD},
-                                              {prior_prec_dev, nk, "prior_prec_dev", GB_RD}, {X, nx, "X", GB_RD}, {H, nh, "H", GB_WR},
-                                              {cov, nh, "cov", GB_WR}, {info_dev, ni, "info_dev", GB_WR}}))
+    const size_t nx = (size_t)K * D * 8, nh = nx * D;
+    if (int st = gb_check_overlaps(__func__, m, {{X, nx, "X", GB_RD}, {H, nh, "H", GB_WR}, {cov, nh, "cov", GB_WR},
+                                                 {info_dev, (size_t)K * 4, "info_dev", GB_WR}}))
         return st;
     GB_BAD(!ctx, "ctx is NULL");
     lp_args a = {};
-    a.K = K; a.N = N; a.D = D; a.A = A; a.y = y; a.offset = offset; a.counts = counts_dev; a.lam = prior_prec;
-    a.lam_dev = prior_prec_dev; a.tau = noise_prec; a.tau_dev = noise_prec_dev; a.X = X; a.H = H; a.cov = cov; a.info = info_dev;
-    int ppw;
-    const size_t lds = lp_launch_lds(D, &ppw);
-    lp_go<LP_HESS>(family, ppw, (unsigned)((K + ppw - 1) / ppw), lds, reinterpret_cast<hipStream_t>(stream), a);
-    return gb_launched(ctx, GSMVI_PATH_BATCHED_LAPLACE, "k_laplace_batched");
+    a.m = m; a.X = X; a.H = H; a.cov = cov; a.info = info_dev;
+    return lp_go<LP_HESS>(ctx, stream, family, a);
 }
 
 int gsmvi_laplace_step_batched_f64(gsmvi_ctx* ctx, void* stream, int64_t K, int D, int64_t N, int family, const double* A,
@@ -572,27 +514,22 @@ int gsmvi_laplace_step_batched_f64(gsmvi_ctx* ctx, void* stream, int64_t K, int 
                                    const double* noise_prec_dev, double prior_prec, const double* prior_prec_dev, int start,
                                    double* x, double* g, double* d, double* sc, int* ist, double* Xt, int* stopped_dev, int maxiter,
                                    int maxfun, double gtol) {
-    if (int st = lp_check_model(__func__, K, D, N, family, noise_prec, noise_prec_dev, prior_prec, prior_prec_dev)) return st;
+    const glm_model m = {K, N, D, A, y, offset, counts_dev, prior_prec, prior_prec_dev, noise_prec, noise_prec_dev};
+    if (int st = glm_check_model(__func__, m, family, "N", true)) return st;
     GB_BAD(!A || !y || !x || !g || !d || !sc || !ist || !Xt, "NULL array");
     GB_BAD(maxiter < 1 || maxfun < 2, "maxiter must be at least 1 and maxfun at least 2");
     GB_BAD(!(gtol >= 0.0), "gtol must be >= 0");
-    const size_t na = (size_t)K * N * D * 8, ny = (size_t)K * N * 8, nv = (size_t)K * D * 8, nk = (size_t)K * 8, ni = (size_t)K * 4;
-    if (int st = gb_check_overlaps(__func__, {{A, na, "A", GB_RD}, {y, ny, "y", GB_RD}, {offset, ny, "offset", GB_RD},
-                                              {counts_dev, ni, "counts_dev", GB_RD}, {noise_prec_dev, nk, "noise_prec_dev", GB_RD},
-                                              {prior_prec_dev, nk, "prior_prec_dev", GB_RD}, {x, nv, "x", GB_WR}, {g, nv, "g", GB_WR},
-                                              {d, nv, "d", GB_WR}, {sc, (size_t)K * LP_NSC * 8, "sc", GB_WR},
-                                              {ist, (size_t)K * LP_NIS * 4, "ist", GB_WR}, {Xt, nv, "Xt", GB_WR},
-                                              {stopped_dev, 4, "stopped_dev", GB_WR}}))
+    const size_t nv = (size_t)K * D * 8;
+    if (int st = gb_check_overlaps(__func__, m, {{x, nv, "x", GB_WR}, {g, nv, "g", GB_WR}, {d, nv, "d", GB_WR},
+                                                 {sc, (size_t)K * LP_NSC * 8, "sc", GB_WR},
+                                                 {ist, (size_t)K * LP_NIS * 4, "ist", GB_WR}, {Xt, nv, "Xt", GB_WR},
+                                                 {stopped_dev, 4, "stopped_dev", GB_WR}}))
         return st;
     GB_BAD(!ctx, "ctx is NULL");
     lp_args a = {};
-    a.K = K; a.N = N; a.D = D; a.start = start != 0; a.A = A; a.y = y; a.offset = offset; a.counts = counts_dev; a.lam = prior_prec;
-    a.lam_dev = prior_prec_dev; a.tau = noise_prec; a.tau_dev = noise_prec_dev; a.x = x; a.g = g; a.d = d; a.sc = sc; a.ist = ist;
-    a.Xt = Xt; a.stopped = stopped_dev; a.maxiter = maxiter; a.maxfun = maxfun; a.gtol = gtol;
-    int ppw;
-    const size_t lds = lp_launch_lds(D, &ppw);
-    lp_go<LP_STEP>(family, ppw, (unsigned)((K + ppw - 1) / ppw), lds, reinterpret_cast<hipStream_t>(stream), a);
-    return gb_launched(ctx, GSMVI_PATH_BATCHED_LAPLACE, "k_laplace_batched");
+    a.m = m; a.start = start != 0; a.x = x; a.g = g; a.d = d; a.sc = sc; a.ist = ist; a.Xt = Xt; a.stopped = stopped_dev;
+    a.maxiter = maxiter; a.maxfun = maxfun; a.gtol = gtol;
+    return lp_go<LP_STEP>(ctx, stream, family, a);
 }
 
 }  // extern "C"

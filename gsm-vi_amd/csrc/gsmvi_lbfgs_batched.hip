@@ -18,8 +18,9 @@
 // Work mapping: the slots of gsmvi_batched.h (gb_nt(D) threads per problem, four problems per 256-thread workgroup for
 // D <= 16).  All threads of a slot bring the held pairs into LDS; after the one barrier of the launch the slot's first wave
 // does the step with component l of every vector in lane l (D <= 64: a vector is one wave wide).  Every dot product is the
-// 64-lane butterfly of that wave (lanes >= D add zeros): a fixed order that depends on nothing but D, and no barrier.  A lane
-// reads and writes only column l of the LDS buffers after the barrier.  A problem that has stopped (status != 0) is frozen:
+// 64-lane butterfly of that wave (gb_wave_sum of gsmvi_batched.h; lanes >= D add zeros): a fixed order that depends on nothing
+// but D, and no barrier.  A lane reads and writes only column l of the LDS buffers after the barrier.  A problem that has
+// stopped (status != 0) is frozen:
 // the launch writes nothing of it.  A slot reads and writes only slice k of every array and every slot runs the same single
 // barrier, so nothing crosses between problems.  Only the newest pair's slot of the ring buffers is written.
 #include "gsmvi_common.h"
@@ -60,20 +61,6 @@ struct gl_args {
 __host__ __device__ inline int gl_lds_doubles(int D, int mode) {
     return mode == GL_STEP ? 2 * GL_M * D + 2 * GL_M : D * (D | 1) + 2 * GL_M * D + D + GL_M;
 }
-
-__device__ __forceinline__ double gl_wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
-__device__ __forceinline__ double gl_wave_max(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o));
-    return v;
-}
-
-__device__ __forceinline__ bool gl_finite(double v) { return fabs(v) < __builtin_huge_val(); }
 
 // is ring-buffer slot i one of the n pairs that end at head - 1
 __device__ __forceinline__ bool gl_held(int i, int head, int n) {
@@ -117,7 +104,7 @@ __global__ __launch_bounds__(256) void k_lbfgs_step_batched(gl_args a) {
         ft = a.sign * a.fv[kk];
         if (act) gtl = a.sign * a.gv[kd + ln];
     }
-    const bool fin = gl_finite(ft) && __all(gl_finite(gtl));
+    const bool fin = gb_finite(ft) && __all(gb_finite(gtl));
     const bool ok = live && !a.start && fin && ft <= f + (1e-4 * t) * gd;
     if (ok) {                                                           // the held pairs are needed for the next direction
         for (int e = l; e < GL_M * D; e += NT) {
@@ -140,7 +127,7 @@ __global__ __launch_bounds__(256) void k_lbfgs_step_batched(gl_args a) {
         nfev = 1;
         f = ft;
         gl = gtl;
-        const double gmax = gl_wave_max(fabs(gl));
+        const double gmax = gb_wave_max(fabs(gl));
         if (!fin) status = 4;
         else if (gmax <= a.gtol) status = 1;
         else steepest = true;
@@ -168,7 +155,7 @@ __global__ __launch_bounds__(256) void k_lbfgs_step_batched(gl_args a) {
         const double fprev = f;
         xl = xtl; f = ft; gl = gtl;
         nit += 1;
-        const double sy = gl_wave_sum(s * y), yy = gl_wave_sum(y * y);
+        const double sy = gb_wave_sum(s * y), yy = gb_wave_sum(y * y);
         if (sy > 2.2e-16 * yy) {
             if (act) {
                 Sl[head * D + ln] = s;
@@ -185,7 +172,7 @@ __global__ __launch_bounds__(256) void k_lbfgs_step_batched(gl_args a) {
             head = head + 1 == GL_M ? 0 : head + 1;
             np = np < GL_M ? np + 1 : GL_M;
         }
-        const double gmax = gl_wave_max(fabs(gl));
+        const double gmax = gb_wave_max(fabs(gl));
         if (gmax <= a.gtol || (fprev - f) <= a.ftol * fmax(fmax(fabs(fprev), fabs(f)), 1.0)) status = 1;
         else if (nit >= a.maxiter || nfev >= a.maxfun) status = 2;
         else if (np == 0) steepest = true;
@@ -197,7 +184,7 @@ __global__ __launch_bounds__(256) void k_lbfgs_step_batched(gl_args a) {
                 if (j < np) {
                     const int i = head - 1 - j < 0 ? head - 1 - j + GL_M : head - 1 - j;
                     const double si = act ? Sl[i * D + ln] : 0.0, yi = act ? Yl[i * D + ln] : 0.0;
-                    const double alpha = (1.0 / lsy[i]) * gl_wave_sum(si * q);
+                    const double alpha = (1.0 / lsy[i]) * gb_wave_sum(si * q);
                     al[j] = alpha;
                     q = q - alpha * yi;
                 }
@@ -209,13 +196,13 @@ __global__ __launch_bounds__(256) void k_lbfgs_step_batched(gl_args a) {
                 if (j < np) {
                     const int i = head - 1 - j < 0 ? head - 1 - j + GL_M : head - 1 - j;
                     const double si = act ? Sl[i * D + ln] : 0.0, yi = act ? Yl[i * D + ln] : 0.0;
-                    const double beta = (1.0 / lsy[i]) * gl_wave_sum(yi * r);
+                    const double beta = (1.0 / lsy[i]) * gb_wave_sum(yi * r);
                     r = r + si * (al[j] - beta);
                 }
             }
             dl = -r;
             t = 1.0;
-            gd = gl_wave_sum(gl * dl);
+            gd = gb_wave_sum(gl * dl);
             nls = 0;
             trial = true;
             if (!(gd < 0.0)) {                                          // not a descent direction: drop the history
@@ -227,9 +214,9 @@ __global__ __launch_bounds__(256) void k_lbfgs_step_batched(gl_args a) {
     }
     if (steepest) {
         dl = -gl;
-        const double nrm = sqrt(gl_wave_sum(gl * gl));
+        const double nrm = sqrt(gb_wave_sum(gl * gl));
         t = fmin(1.0, 1.0 / nrm);
-        gd = gl_wave_sum(gl * dl);
+        gd = gb_wave_sum(gl * dl);
         nls = 0;
         trial = true;
     }

@@ -35,10 +35,12 @@
 // offset of a tile rides beside its y (32 more doubles of LDS per problem, only in the kernels with OFF, the fourth template
 // parameter: the launches without an offset keep the code and the registers they had before there was one).  A Poisson row for
 // which some valid e^eta is not finite gets NaN outputs through the row flag of a non-finite row of X.
+// Host side: the model's checks, its overlap entries and the dispatch on the family are gsmvi_glm_model.h's, shared with the
+// Laplace and predictive entries; lb_run adds what is this launch's own (nc, X, G, lp).
 #include "gsmvi_common.h"
 #include "gsmvi_ctx.h"
 #include "gsmvi_batched.h"
-#include "gsmvi_glm_link.h"                  // lb_link, the families, LB_TN
+#include "gsmvi_glm_model.h"                 // glm_model and its checks; gsmvi_glm_link.h: lb_link, the families, LB_TN
 #include "../../include/gsmvi_hip.h"
 #include "../../include/gsmvi_hip_debug.h"   // gsmvi_debug_logistic_batched_lds
 #include <cstdint>
@@ -46,6 +48,8 @@
 
 #define LB_AQ 8    // tile elements per thread: LB_TN D / NT <= 8 in both packings
 
+// (the model's fields in this kernel's own order, not a glm_model: with the shared block in front, the register allocation of the
+// 256-thread gaussian density kernel changes, and the 256-thread kernels sit at a register cliff, see lb_off_tile)
 struct lb_args {
     long long K, N;
     int D, nc, tcm;             // dimension, rows of X per problem, rows of X held in LDS = min(nc, TC)
@@ -321,51 +325,31 @@ static void lb_go(int ppw, int want, unsigned grid, size_t lds, hipStream_t st, 
 #undef LB_GO
 }
 
-// The body of both entry points: every check (shapes, the family and its noise precision, NULL arrays, overlaps, the context
-// last), then the one launch.  `fn` names the entry point in the messages.
-static int lb_run(const char* fn, gsmvi_ctx* ctx, void* stream, int64_t K, int D, int nc, int64_t N, int family, const double* A,
-                  const double* y, const double* offset, const int* counts_dev, double noise_prec, const double* noise_prec_dev,
-                  double prior_prec, const double* prior_prec_dev, const double* X, double* G, double* lp) {
+// The body of both entry points: every check (the model, the entry's own shapes and NULL arrays, overlaps, the context last),
+// then the one launch.  `fn` names the entry point in the messages.
+static int lb_run(const char* fn, gsmvi_ctx* ctx, void* stream, int family, const glm_model& m, int nc, const double* X, double* G,
+                  double* lp) {
 #define LB_BAD(cond, msg)                     \
     do {                                      \
         if (cond) return gb_bad(fn, msg);     \
     } while (0)
-    if (int st = gb_check_shape(fn, K, D, gb_ppw)) return st;
+    if (int st = glm_check_model(fn, m, family, "N", true)) return st;
     LB_BAD(nc < 1, "nc must be at least 1");
-    LB_BAD(N < 1, "N must be at least 1");
-    LB_BAD(N > (INT64_MAX / 8 / D) / K, "K N D is too large");
-    LB_BAD(nc > (INT64_MAX / 8 / D) / K, "K nc D is too large");
-    LB_BAD(family < GSMVI_GLM_LOGISTIC || family > GSMVI_GLM_GAUSSIAN, "family must be one of GSMVI_GLM_LOGISTIC .. GSMVI_GLM_GAUSSIAN");
-    LB_BAD(!A || !y || !X, "NULL array");
+    LB_BAD(nc > (INT64_MAX / 8 / m.D) / m.K, "K nc D is too large");
+    LB_BAD(!m.A || !m.y || !X, "NULL array");
     LB_BAD(!G && !lp, "give G or lp (or both)");
-    LB_BAD(!prior_prec_dev && !(prior_prec >= 0.0 && prior_prec < __builtin_huge_val()), "prior_prec must be finite and >= 0");
-    if (family == GSMVI_GLM_GAUSSIAN)
-        LB_BAD(!noise_prec_dev && !(noise_prec > 0.0 && noise_prec < __builtin_huge_val()), "noise_prec must be finite and > 0");
-    else
-        LB_BAD(noise_prec_dev || noise_prec != 1.0, "noise_prec is the gaussian family's: give 1.0 and NULL for any other");
-    const size_t na = (size_t)K * N * D * 8, ny = (size_t)K * N * 8, nx = (size_t)K * nc * D * 8, nl = (size_t)K * nc * 8,
-                 nk = (size_t)K * 8, ni = (size_t)K * 4;
-    if (int st = gb_check_overlaps(fn, {{A, na, "A", GB_RD}, {y, ny, "y", GB_RD}, {offset, ny, "offset", GB_RD},
-                                        {counts_dev, ni, "counts_dev", GB_RD}, {noise_prec_dev, nk, "noise_prec_dev", GB_RD},
-                                        {prior_prec_dev, nk, "prior_prec_dev", GB_RD}, {X, nx, "X", GB_RD}, {G, nx, "G", GB_WR},
-                                        {lp, nl, "lp", GB_WR}}))
+    const size_t nx = (size_t)m.K * nc * m.D * 8;
+    if (int st = gb_check_overlaps(fn, m, {{X, nx, "X", GB_RD}, {G, nx, "G", GB_WR}, {lp, (size_t)m.K * nc * 8, "lp", GB_WR}}))
         return st;
     LB_BAD(!ctx, "ctx is NULL");
 #undef LB_BAD
     const int want = (G ? LB_G : 0) | (lp ? LB_LP : 0);
-    lb_args a = {};
-    a.K = K; a.N = N; a.D = D; a.nc = nc; a.A = A; a.y = y; a.offset = offset; a.tau = noise_prec; a.tau_dev = noise_prec_dev;
-    a.counts = counts_dev; a.lam = prior_prec; a.lam_dev = prior_prec_dev; a.X = X; a.G = G; a.lp = lp;
+    lb_args a = {m.K, m.N, m.D, nc, 0, m.A, m.y, m.counts, m.lam, m.lam_dev, X, G, lp, m.offset, m.tau, m.tau_dev};
     int ppw;
-    const size_t lds = lb_launch_lds(D, nc, want, lb_off(family, offset), &ppw, &a.tcm);
-    const unsigned grid = (unsigned)((K + ppw - 1) / ppw);
+    const size_t lds = lb_launch_lds(m.D, nc, want, lb_off(family, m.offset), &ppw, &a.tcm);
+    const unsigned grid = (unsigned)((m.K + ppw - 1) / ppw);
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    switch (family) {
-        case GSMVI_GLM_LOGISTIC: lb_go<LB_LOGISTIC>(ppw, want, grid, lds, st, a); break;
-        case GSMVI_GLM_POISSON: lb_go<LB_POISSON>(ppw, want, grid, lds, st, a); break;
-        case GSMVI_GLM_PROBIT: lb_go<LB_PROBIT>(ppw, want, grid, lds, st, a); break;
-        default: lb_go<LB_GAUSSIAN>(ppw, want, grid, lds, st, a); break;
-    }
+    glm_for_family(family, [&](auto fam) { lb_go<decltype(fam)::value>(ppw, want, grid, lds, st, a); });
     return gb_launched(ctx, GSMVI_PATH_BATCHED_TARGET, "k_logistic_batched");
 }
 
@@ -374,16 +358,16 @@ extern "C" {
 int gsmvi_logistic_batched_f64(gsmvi_ctx* ctx, void* stream, int64_t K, int D, int nc, int64_t N, const double* A, const double* y,
                                const int* counts_dev, double prior_prec, const double* prior_prec_dev, const double* X, double* G,
                                double* lp) {
-    return lb_run(__func__, ctx, stream, K, D, nc, N, GSMVI_GLM_LOGISTIC, A, y, nullptr, counts_dev, 1.0, nullptr, prior_prec,
-                  prior_prec_dev, X, G, lp);
+    return lb_run(__func__, ctx, stream, GSMVI_GLM_LOGISTIC, {K, N, D, A, y, nullptr, counts_dev, prior_prec, prior_prec_dev, 1.0, nullptr},
+                  nc, X, G, lp);
 }
 
 int gsmvi_glm_batched_f64(gsmvi_ctx* ctx, void* stream, int64_t K, int D, int nc, int64_t N, int family, const double* A,
                           const double* y, const double* offset, const int* counts_dev, double noise_prec,
                           const double* noise_prec_dev, double prior_prec, const double* prior_prec_dev, const double* X, double* G,
                           double* lp) {
-    return lb_run(__func__, ctx, stream, K, D, nc, N, family, A, y, offset, counts_dev, noise_prec, noise_prec_dev, prior_prec,
-                  prior_prec_dev, X, G, lp);
+    return lb_run(__func__, ctx, stream, family,
+                  {K, N, D, A, y, offset, counts_dev, prior_prec, prior_prec_dev, noise_prec, noise_prec_dev}, nc, X, G, lp);
 }
 
 // include/gsmvi_hip_debug.h: what a launch at (D, nc) requests (exported by the debug library only); want: 1 = G, 2 = lp, 3 = both

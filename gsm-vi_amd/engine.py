@@ -871,13 +871,18 @@ class HipEngine:
         return cov
 
     # ---- batched logistic target: K regressions of one (N, D) (csrc/gsmvi_logistic_batched.hip) ---------------------------
+    @staticmethod
+    def _check_want(want, a, b):
+        """``want`` of the entries with two outputs: one of them or "both", else ValueError"""
+        if want not in (a, b, "both"):
+            raise ValueError(f"want = {want!r}: expected {a!r}, {b!r} or 'both'")
+
     def logistic_batched(self, X, A, y, counts=None, prior_prec=1.0, out=None, lp_out=None, want="g"):
         """Score and / or log-density of K Bayesian logistic regressions at the rows of X (K, nc, D), one launch
         [examples/example_gsm.py:34-35 for this model]: A (K, N, D), y (K, N), ``counts`` None or K device int32 valid rows,
         ``prior_prec`` a number or a (K,) device tensor.  ``want`` = "g" -> G (K, nc, D) (no logarithm is evaluated), "lp" -> the
         values (K, nc), "both" -> (G, lp)."""
-        if want not in ("g", "lp", "both"):
-            raise ValueError(f"want = {want!r}: expected 'g', 'lp' or 'both'")
+        self._check_want(want, "g", "lp")
         X = X.contiguous()
         K, nc, D = X.shape
         N = A.shape[1]
@@ -897,6 +902,13 @@ class HipEngine:
     # ---- batched GLM targets: the same launch for a family of links (csrc/gsmvi_logistic_batched.hip) -----------------------
     GLM_FAMILIES = {"logistic": 0, "poisson": 1, "probit": 2, "gaussian": 3}     # GSMVI_GLM_* of include/gsmvi_hip.h
 
+    def _glm_family_args(self, family, noise_prec, K):
+        """(GSMVI_GLM_* code, noise_prec, noise_prec_dev) of every GLM entry point; an unknown family: ValueError"""
+        if family not in self.GLM_FAMILIES:
+            raise ValueError(f"family = {family!r}: expected one of {sorted(self.GLM_FAMILIES)}")
+        t, tp = self._reg_arg(noise_prec, K)
+        return self.GLM_FAMILIES[family], 1.0 if tp is not None else t, tp     # (the scalar is unused with K values)
+
     def glm_batched(self, X, A, y, family, offset=None, counts=None, prior_prec=1.0, noise_prec=1.0, out=None, lp_out=None,
                     want="g"):
         """Score and / or log-density of K generalised linear models at the rows of X (K, nc, D), one launch
@@ -904,10 +916,8 @@ class HipEngine:
         (identity link, noise precision ``noise_prec``: a number or a (K,) device tensor, this family only); A (K, N, D), y
         (K, N), ``offset`` None or (K, N) added to A x, ``counts`` None or K device int32 valid rows, ``prior_prec`` a number or
         a (K,) device tensor.  ``want`` = "g" -> G (K, nc, D), "lp" -> the values (K, nc), "both" -> (G, lp)."""
-        if want not in ("g", "lp", "both"):
-            raise ValueError(f"want = {want!r}: expected 'g', 'lp' or 'both'")
-        if family not in self.GLM_FAMILIES:
-            raise ValueError(f"family = {family!r}: expected one of {sorted(self.GLM_FAMILIES)}")
+        self._check_want(want, "g", "lp")
+        fam, t, tp = self._glm_family_args(family, noise_prec, X.shape[0])
         X = X.contiguous()
         K, nc, D = X.shape
         N = A.shape[1]
@@ -918,11 +928,8 @@ class HipEngine:
         if want != "g":
             lp = self.empty(K, nc) if lp_out is None else lp_out
         r, rp = self._reg_arg(prior_prec, K)
-        t, tp = self._reg_arg(noise_prec, K)
-        if tp is not None:
-            t = 1.0                                                   # (the scalar is unused with K values)
         _lib.check("gsmvi_glm_batched_f64", self.lib.gsmvi_glm_batched_f64(
-            self._ctx, self._stream(), K, D, nc, N, self.GLM_FAMILIES[family], self._packed(A, (K, N, D), "A"),
+            self._ctx, self._stream(), K, D, nc, N, fam, self._packed(A, (K, N, D), "A"),
             self._packed(y, (K, N), "y"), self._dp(offset, (K, N), "offset"), self._ints(counts, K, "counts"), t, tp, r, rp,
             self._packed(X, (K, nc, D), "X"), self._dp(G, (K, nc, D), "out"), self._dp(lp, (K, nc), "lp_out")))
         return G if want == "g" else lp if want == "lp" else (G, lp)
@@ -974,14 +981,10 @@ class HipEngine:
     # ---- batched Laplace initialiser: Hessian, inverse and Newton rounds of the GLM targets (csrc/gsmvi_laplace_batched.hip) ----
     def _glm_model_args(self, A, y, family, offset, counts, prior_prec, noise_prec):
         """the model's arguments of the two Laplace entry points, in the order of include/gsmvi_hip.h"""
-        if family not in self.GLM_FAMILIES:
-            raise ValueError(f"family = {family!r}: expected one of {sorted(self.GLM_FAMILIES)}")
         K, N, D = A.shape
+        fam, t, tp = self._glm_family_args(family, noise_prec, K)
         r, rp = self._reg_arg(prior_prec, K)
-        t, tp = self._reg_arg(noise_prec, K)
-        if tp is not None:
-            t = 1.0                                                   # (the scalar is unused with K values)
-        return (K, D, N, self.GLM_FAMILIES[family], self._packed(A, (K, N, D), "A"), self._packed(y, (K, N), "y"),
+        return (K, D, N, fam, self._packed(A, (K, N, D), "A"), self._packed(y, (K, N), "y"),
                 self._dp(offset, (K, N), "offset"), self._ints(counts, K, "counts"), t, tp, r, rp)
 
     def glm_hessian_batched(self, X, A, y, family, offset=None, counts=None, prior_prec=1.0, noise_prec=1.0, want="h", out=None,
@@ -990,8 +993,7 @@ class HipEngine:
         (the Gram product on the fp64 MFMA)  [no reference twin; the model of examples/example_gsm.py:34-35]: ``want`` = "h" ->
         H (K, D, D), "cov" -> (cov, info), "both" -> (H, cov, info); ``info`` (K,) int32: 0, or 1 + the first failing pivot, and
         then cov_k = I.  The other arguments are ``glm_batched``'s."""
-        if want not in ("h", "cov", "both"):
-            raise ValueError(f"want = {want!r}: expected 'h', 'cov' or 'both'")
+        self._check_want(want, "h", "cov")
         X = X.contiguous()
         K, D = X.shape
         self._ensure(max(self._max_D, 1), max(self._max_B, 1))
@@ -1053,8 +1055,7 @@ class HipEngine:
         product A cov on the fp64 MFMA)  [examples/example_gsm.py:34-35, the use of the fit; no reference twin]: returns
         (eta_mean, eta_var, pmean (K, M), lpd (K, M), elpd (K,)), the last two None without ``y``.  ``family``, ``offset``,
         ``counts`` and ``noise_prec`` are ``glm_batched``'s; ``nodes`` = Q Gauss-Hermite nodes, 1 .. 64."""
-        if family not in self.GLM_FAMILIES:
-            raise ValueError(f"family = {family!r}: expected one of {sorted(self.GLM_FAMILIES)}")
+        fam, t, tp = self._glm_family_args(family, noise_prec, A.shape[0])
         Q = int(nodes)
         if not 1 <= Q <= 64:
             raise ValueError(f"nodes = {nodes!r}: expected 1 .. 64")
@@ -1065,11 +1066,8 @@ class HipEngine:
         lpd = elpd = None
         if y is not None:
             lpd, elpd = self.empty(K, M), self.empty(K)
-        t, tp = self._reg_arg(noise_prec, K)
-        if tp is not None:
-            t = 1.0                                                   # (the scalar is unused with K values)
         _lib.check("gsmvi_glm_predict_batched_f64", self.lib.gsmvi_glm_predict_batched_f64(
-            self._ctx, self._stream(), K, D, M, self.GLM_FAMILIES[family], self._packed(A, (K, M, D), "A"),
+            self._ctx, self._stream(), K, D, M, fam, self._packed(A, (K, M, D), "A"),
             self._dp(offset, (K, M), "offset"), self._dp(y, (K, M), "y"), self._ints(counts, K, "counts"), t, tp,
             self._packed(mean, (K, D), "mean"), self._packed(cov, (K, D, D), "cov"), Q, self._packed(gt, (Q,), "gh_t"),
             self._packed(gl, (Q,), "gh_logw"), self._packed(em, (K, M), "eta_mean"), self._packed(ev, (K, M), "eta_var"),

@@ -178,8 +178,8 @@ def laplace_init_batched(target, x0=None, maxiter=100, maxfun=200, *, gtol=1e-8,
     it reads the device's count of stopped problems every ``check_every`` rounds and leaves when it equals K, so the result
     does not depend on ``check_every``; only ``res.nlaunch`` does.  One more launch gives the covariance at the final points.
     Prints nothing."""
-    from .targets import BatchedGLMTarget, BatchedLogisticTarget
-    if not isinstance(target, (BatchedGLMTarget, BatchedLogisticTarget)):
+    from .targets import BatchedGLMTarget
+    if not isinstance(target, BatchedGLMTarget):
         raise TypeError(f"laplace_init_batched: target must be a BatchedGLMTarget or a BatchedLogisticTarget, "
                         f"got {type(target).__name__}")
     K, D = target.K, target.D

@@ -7,7 +7,7 @@ kernel.  ``device_score`` marks a user callable as taking/returning CUDA tensors
 (examples/example_gsm.py:34-35: ``lp_g = jit(grad(lambda x: sum(lp(x))))``).
 ``BatchedLogisticTarget`` is the first non-Gaussian device target of the batched fits: K Bayesian logistic
 regressions, score and log-density from one HIP launch.  ``BatchedGLMTarget`` is the same launch for a family of generalised
-linear models: Poisson, probit, Gaussian and logistic, with offsets.  Both have ``predict``: the posterior predictive of the
+linear models: Poisson, probit, Gaussian and logistic, with offsets; the logistic class is its ``family="logistic"`` case.  They have ``predict``: the posterior predictive of the
 fitted Gaussians on new rows (``GLMPrediction``), one HIP launch.
 """
 from dataclasses import dataclass
@@ -136,6 +136,26 @@ def _host_array(x):
     return x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x)
 
 
+def _shape(x):
+    """the shape of an array, a tensor or nested lists as a tuple of ints"""
+    return tuple(int(n) for n in x.shape) if hasattr(x, "shape") else np.shape(x)
+
+
+def _check_per_problem(x, name, K, positive=False, fixed=None):
+    """``x``, a number or K values, as a host float64 array: finite and >= 0, or (``positive``) > 0 with the offending problems
+    listed; ``fixed``: the message for an ``x`` that must stay at 1.0 and does not; else ValueError"""
+    v = np.asarray(_host_array(x), dtype=np.float64)
+    if v.shape not in ((), (K,)):
+        raise ValueError(f"{name}: expected a number or {K} values, got shape {v.shape}")
+    if fixed is not None and not (v == 1.0).all():
+        raise ValueError(f"{name}: {fixed}")
+    good = np.isfinite(v) & (v > 0.0 if positive else v >= 0.0)
+    if not good.all():
+        where = f" (problems {np.flatnonzero(~good).tolist()})" if positive and v.shape != () else ""
+        raise ValueError(f"{name}: expected finite values {'> 0' if positive else '>= 0'}{where}")
+    return v
+
+
 def _check_counts(counts, K, N, rows="N"):
     """``counts`` of K problems of N rows each as a host integer array (None stays None), else ValueError"""
     if counts is None:
@@ -174,7 +194,7 @@ def _check_offset(offset, K, N, live, rows="N"):
     """the offsets as a host float64 array (None stays None), shape and finiteness in the valid rows checked, else ValueError"""
     if offset is None:
         return None
-    so = tuple(int(n) for n in offset.shape) if hasattr(offset, "shape") else np.shape(offset)
+    so = _shape(offset)
     if so != (K, N):
         raise ValueError(f"offset: expected shape (K, {rows}) = {(K, N)}, got {so}")
     oh = np.asarray(_host_array(offset), dtype=np.float64)
@@ -198,127 +218,6 @@ class GLMPrediction:
     mean: Any
     lpd: Any
     elpd: Any
-
-
-def _predict(target, mean, cov, A_new, offset, y, counts, nodes):
-    """``predict`` of both GLM targets: the checks on the host, then one launch (gsmvi_glm_predict_batched_f64)"""
-    K, D, family = target.K, target.D, target.family
-    if isinstance(nodes, bool) or not isinstance(nodes, (int, np.integer)) or not 1 <= nodes <= 64:
-        raise ValueError(f"nodes: expected an integer in 1 .. 64, got {nodes!r}")
-    sa = tuple(int(n) for n in A_new.shape) if hasattr(A_new, "shape") else np.shape(A_new)
-    if len(sa) != 3 or min(sa) < 1 or sa[0] != K or sa[2] != D:
-        raise ValueError(f"A_new: expected shape (K, M, D) with K = {K}, D = {D} and M >= 1, got {sa}")
-    M = sa[1]
-    sm = tuple(int(n) for n in mean.shape) if hasattr(mean, "shape") else np.shape(mean)
-    if sm != (K, D):
-        raise ValueError(f"mean: expected shape (K, D) = {(K, D)}, got {sm}")
-    sc = tuple(int(n) for n in cov.shape) if hasattr(cov, "shape") else np.shape(cov)
-    if sc != (K, D, D):
-        raise ValueError(f"cov: expected shape (K, D, D) = {(K, D, D)}, got {sc}")
-    cnt = _check_counts(counts, K, M, rows="M")
-    live = _live_rows(cnt, M)
-    yh = None
-    if y is not None:
-        sy = tuple(int(n) for n in y.shape) if hasattr(y, "shape") else np.shape(y)
-        if sy != (K, M):
-            raise ValueError(f"y: expected shape (K, M) = {(K, M)}, got {sy}")
-        yh = _check_responses(y, family, live, name_family=isinstance(target, BatchedGLMTarget))
-    oh = _check_offset(offset, K, M, live, rows="M")
-    eng = target.engine
-    as_tensor = isinstance(mean, torch.Tensor)
-    dev = lambda x: eng.asarray(x.contiguous() if isinstance(x, torch.Tensor) else x)      # noqa: E731
-    out = eng.glm_predict_batched(dev(mean), dev(cov), dev(A_new), family, offset=eng.asarray(oh) if oh is not None else None,
-                                  y=eng.asarray(yh) if yh is not None else None,
-                                  counts=eng.batched_counts(cnt) if cnt is not None else None,
-                                  noise_prec=target.noise_precision, nodes=int(nodes))
-    if not as_tensor:
-        out = tuple(eng.to_numpy(t) if t is not None else None for t in out)
-    return GLMPrediction(*out)
-
-
-_PREDICT_DOC = """The posterior predictive of the K fitted problems on new rows: ``mean`` (K, D) and ``cov`` (K, D, D) are the
-        fitted Gaussians (of GSMBatch, BaMBatch, ADVIBatch or ``laplace_init_batched``), ``A_new`` (K, M, D) the new rows,
-        ``offset`` (K, M) their offsets (None: none, whether or not the target was built with one: the new rows are new data),
-        ``y`` (K, M) their responses (None: no ``lpd`` / ``elpd``), ``counts`` (K,) the valid rows per problem (None: all M),
-        ``nodes`` = Q the Gauss-Hermite nodes, 1 .. 64.  Returns a ``GLMPrediction``; numpy in gives numpy out, CUDA tensors in
-        give tensors out.  ``y``, ``offset`` and ``counts`` are validated as the constructor validates its own (ValueError
-        naming the argument and the problems), the shapes and ``nodes`` too, before any device work.  The quadrature is
-        accurate for modest eta_var (DESIGN.md section 9); the gaussian family is closed-form.  One launch."""
-
-
-class BatchedLogisticTarget:
-    """K Bayesian logistic regressions with their own data sets, for ``GSMBatch``, ``BaMBatch``, ``ADVIBatch`` and
-    ``BatchedKLMonitor``.  Problem k has the design matrix A[k] (N, D), labels y[k] (N,) in [0, 1] (soft labels allowed),
-    ``counts[k]`` <= N valid rows (None: all N; the rows beyond are ignored whatever they hold) and the prior N(0, I / lam_k),
-    ``prior_precision`` = lam a float or K values, 0 = flat.  With eta = A[k] x:
-
-        lp_k(x)      = sum_n [ y_n eta_n - softplus(eta_n) ] - lam_k |x|^2 / 2          (unnormalised log posterior)
-        grad lp_k(x) = sum_n ( y_n - sigmoid(eta_n) ) a_n - lam_k x
-
-    in the overflow-safe forms (e = exp(-|eta|); sigmoid = 1 / (1 + e) for eta >= 0, e / (1 + e) otherwise; softplus =
-    max(eta, 0) + log1p(e)), evaluated by gsmvi_logistic_batched_f64: what examples/example_gsm.py:34-35 gets from a model's
-    log_prob and jit(grad(...)).  numpy arrays or tensors in; everything is kept on the device as float64 / int32.  Arguments
-    are validated on the host before any device work (ValueError naming the argument).
-
-    ``lp_g(x, out=None)``: (K, B, D) -> (K, B, D) scores, ``device_native`` and ``graph_safe`` (one capturable launch, no
-    allocation with ``out``).  ``lp(x)``: (K, rows, D) -> (K, rows) values (what ADVIBatch's losses and BatchedKLMonitor sum per
-    problem); a device tensor or numpy.  ``lp_and_score(x)``: (scores, values) from one launch."""
-
-    family = "logistic"                 # the model as ``laplace_init_batched`` and ``neg_hessian`` hand it to the GLM kernels
-    offset = None
-    noise_precision = 1.0
-
-    def __init__(self, A, y, prior_precision=1.0, counts=None, engine=None):
-        sa, sy = tuple(int(n) for n in A.shape), tuple(int(n) for n in y.shape)
-        if len(sa) != 3 or min(sa) < 1:
-            raise ValueError(f"A: expected shape (K, N, D) with K, N, D >= 1, got {sa}")
-        K, N, D = sa
-        if not 1 <= D <= 64:
-            raise ValueError(f"A: D = {D} is outside 1 <= D <= 64")
-        if sy != (K, N):
-            raise ValueError(f"y: expected shape (K, N) = {(K, N)}, got {sy}")
-        cnt = _check_counts(counts, K, N)
-        live = _live_rows(cnt, N)
-        yh = _check_responses(y, "logistic", live, name_family=False)
-        lam = np.asarray(_host_array(prior_precision), dtype=np.float64)
-        if lam.shape not in ((), (K,)):
-            raise ValueError(f"prior_precision: expected a number or {K} values, got shape {lam.shape}")
-        if not (np.isfinite(lam) & (lam >= 0.0)).all():
-            raise ValueError("prior_precision: expected finite values >= 0")
-        self.engine = engine if engine is not None else get_engine()
-        eng = self.engine
-        self.K, self.N, self.D = K, N, D
-        self.A = eng.asarray(A.contiguous() if isinstance(A, torch.Tensor) else A)
-        self.y = eng.asarray(yh)
-        self.counts = eng.batched_counts(cnt) if cnt is not None else None
-        self.prior_precision = float(lam) if lam.shape == () else eng.batched_regs(lam)
-
-        def lp_g(x, out=None):
-            return eng.logistic_batched(x, self.A, self.y, self.counts, self.prior_precision, out=out, want="g")
-        lp_g.device_native = True
-        lp_g.graph_safe = True          # one capturable kernel launch, no allocation when `out` is given, no host work
-        self.lp_g = lp_g
-
-    def lp(self, x):
-        """(K, rows) values lp_k(x_kr) at the rows of x (K, rows, D), a device tensor or numpy; one launch"""
-        eng = self.engine
-        return eng.logistic_batched(eng.asarray(x), self.A, self.y, self.counts, self.prior_precision, want="lp")
-
-    def lp_and_score(self, x):
-        """(scores (K, rows, D), values (K, rows)) from one launch"""
-        eng = self.engine
-        return eng.logistic_batched(eng.asarray(x), self.A, self.y, self.counts, self.prior_precision, want="both")
-
-    def neg_hessian(self, x):
-        """(K, D, D) negative Hessians A_k^T W A_k + lam_k I of lp_k at the rows of x (K, D), W = diag(sigmoid (1 - sigmoid)),
-        exactly symmetric; a device tensor or numpy; one launch"""
-        eng = self.engine
-        return eng.glm_hessian_batched(eng.asarray(x), self.A, self.y, "logistic", counts=self.counts,
-                                       prior_prec=self.prior_precision, want="h")
-
-    def predict(self, mean, cov, A_new, offset=None, y=None, counts=None, nodes=32):
-        return _predict(self, mean, cov, A_new, offset, y, counts, nodes)
-    predict.__doc__ = _PREDICT_DOC
 
 
 class BatchedGLMTarget:
@@ -347,35 +246,26 @@ class BatchedGLMTarget:
     (scores, values) from one launch."""
 
     FAMILIES = ("logistic", "poisson", "probit", "gaussian")
+    _y_names_family = True              # the ``y:`` messages end with the family
 
     def __init__(self, A, y, family, prior_precision=1.0, counts=None, offset=None, noise_precision=1.0, engine=None):
         if family not in self.FAMILIES:
             raise ValueError(f"family: expected one of {self.FAMILIES}, got {family!r}")
-        sa, sy = tuple(int(n) for n in A.shape), tuple(int(n) for n in y.shape)
+        sa = _shape(A)
         if len(sa) != 3 or min(sa) < 1:
             raise ValueError(f"A: expected shape (K, N, D) with K, N, D >= 1, got {sa}")
         K, N, D = sa
         if not 1 <= D <= 64:
             raise ValueError(f"A: D = {D} is outside 1 <= D <= 64")
-        if sy != (K, N):
-            raise ValueError(f"y: expected shape (K, N) = {(K, N)}, got {sy}")
+        if _shape(y) != (K, N):
+            raise ValueError(f"y: expected shape (K, N) = {(K, N)}, got {_shape(y)}")
         cnt = _check_counts(counts, K, N)
         live = _live_rows(cnt, N)
-        yh = _check_responses(y, family, live)
+        yh = _check_responses(y, family, live, name_family=self._y_names_family)
         oh = _check_offset(offset, K, N, live)
-        lam = np.asarray(_host_array(prior_precision), dtype=np.float64)
-        if lam.shape not in ((), (K,)):
-            raise ValueError(f"prior_precision: expected a number or {K} values, got shape {lam.shape}")
-        if not (np.isfinite(lam) & (lam >= 0.0)).all():
-            raise ValueError("prior_precision: expected finite values >= 0")
-        tau = np.asarray(_host_array(noise_precision), dtype=np.float64)
-        if tau.shape not in ((), (K,)):
-            raise ValueError(f"noise_precision: expected a number or {K} values, got shape {tau.shape}")
-        if family != "gaussian" and not (tau == 1.0).all():
-            raise ValueError(f"noise_precision: only family 'gaussian' has one (family {family!r}: leave it at 1.0)")
-        if not (np.isfinite(tau) & (tau > 0.0)).all():
-            where = "" if tau.shape == () else f" (problems {np.flatnonzero(~(np.isfinite(tau) & (tau > 0.0))).tolist()})"
-            raise ValueError(f"noise_precision: expected finite values > 0{where}")
+        lam = _check_per_problem(prior_precision, "prior_precision", K)
+        tau = _check_per_problem(noise_precision, "noise_precision", K, positive=True, fixed=None if family == "gaussian" else
+                                 f"only family 'gaussian' has one (family {family!r}: leave it at 1.0)")
         self.engine = engine if engine is not None else get_engine()
         eng = self.engine
         self.family = family
@@ -385,10 +275,7 @@ class BatchedGLMTarget:
         self.offset = eng.asarray(oh) if oh is not None else None
         self.counts = eng.batched_counts(cnt) if cnt is not None else None
         self.prior_precision = float(lam) if lam.shape == () else eng.batched_regs(lam)
-        if family != "gaussian":
-            self.noise_precision = 1.0
-        else:
-            self.noise_precision = float(tau) if tau.shape == () else eng.batched_regs(tau)
+        self.noise_precision = 1.0 if family != "gaussian" else float(tau) if tau.shape == () else eng.batched_regs(tau)
 
         def lp_g(x, out=None):
             return self._call(x, out=out, want="g")
@@ -417,5 +304,67 @@ class BatchedGLMTarget:
                                        prior_prec=self.prior_precision, noise_prec=self.noise_precision, want="h")
 
     def predict(self, mean, cov, A_new, offset=None, y=None, counts=None, nodes=32):
-        return _predict(self, mean, cov, A_new, offset, y, counts, nodes)
-    predict.__doc__ = _PREDICT_DOC
+        """The posterior predictive of the K fitted problems on new rows: ``mean`` (K, D) and ``cov`` (K, D, D) are the
+        fitted Gaussians (of GSMBatch, BaMBatch, ADVIBatch or ``laplace_init_batched``), ``A_new`` (K, M, D) the new rows,
+        ``offset`` (K, M) their offsets (None: none, whether or not the target was built with one: the new rows are new data),
+        ``y`` (K, M) their responses (None: no ``lpd`` / ``elpd``), ``counts`` (K,) the valid rows per problem (None: all M),
+        ``nodes`` = Q the Gauss-Hermite nodes, 1 .. 64.  Returns a ``GLMPrediction``; numpy in gives numpy out, CUDA tensors in
+        give tensors out.  ``y``, ``offset`` and ``counts`` are validated as the constructor validates its own (ValueError
+        naming the argument and the problems), the shapes and ``nodes`` too, before any device work.  The quadrature is
+        accurate for modest eta_var; the gaussian family is closed-form.  One launch."""
+        K, D, family = self.K, self.D, self.family
+        if isinstance(nodes, bool) or not isinstance(nodes, (int, np.integer)) or not 1 <= nodes <= 64:
+            raise ValueError(f"nodes: expected an integer in 1 .. 64, got {nodes!r}")
+        sa = _shape(A_new)
+        if len(sa) != 3 or min(sa) < 1 or sa[0] != K or sa[2] != D:
+            raise ValueError(f"A_new: expected shape (K, M, D) with K = {K}, D = {D} and M >= 1, got {sa}")
+        M = sa[1]
+        if _shape(mean) != (K, D):
+            raise ValueError(f"mean: expected shape (K, D) = {(K, D)}, got {_shape(mean)}")
+        if _shape(cov) != (K, D, D):
+            raise ValueError(f"cov: expected shape (K, D, D) = {(K, D, D)}, got {_shape(cov)}")
+        cnt = _check_counts(counts, K, M, rows="M")
+        live = _live_rows(cnt, M)
+        yh = None
+        if y is not None:
+            if _shape(y) != (K, M):
+                raise ValueError(f"y: expected shape (K, M) = {(K, M)}, got {_shape(y)}")
+            yh = _check_responses(y, family, live, name_family=self._y_names_family)
+        oh = _check_offset(offset, K, M, live, rows="M")
+        eng = self.engine
+        as_tensor = isinstance(mean, torch.Tensor)
+        dev = lambda x: eng.asarray(x.contiguous() if isinstance(x, torch.Tensor) else x)      # noqa: E731
+        out = eng.glm_predict_batched(dev(mean), dev(cov), dev(A_new), family, offset=eng.asarray(oh) if oh is not None else None,
+                                      y=eng.asarray(yh) if yh is not None else None,
+                                      counts=eng.batched_counts(cnt) if cnt is not None else None,
+                                      noise_prec=self.noise_precision, nodes=int(nodes))
+        if not as_tensor:
+            out = tuple(eng.to_numpy(t) if t is not None else None for t in out)
+        return GLMPrediction(*out)
+
+
+class BatchedLogisticTarget(BatchedGLMTarget):
+    """K Bayesian logistic regressions with their own data sets, for ``GSMBatch``, ``BaMBatch``, ``ADVIBatch`` and
+    ``BatchedKLMonitor``.  Problem k has the design matrix A[k] (N, D), labels y[k] (N,) in [0, 1] (soft labels allowed),
+    ``counts[k]`` <= N valid rows (None: all N; the rows beyond are ignored whatever they hold) and the prior N(0, I / lam_k),
+    ``prior_precision`` = lam a float or K values, 0 = flat.  With eta = A[k] x:
+
+        lp_k(x)      = sum_n [ y_n eta_n - softplus(eta_n) ] - lam_k |x|^2 / 2          (unnormalised log posterior)
+        grad lp_k(x) = sum_n ( y_n - sigmoid(eta_n) ) a_n - lam_k x
+
+    in the overflow-safe forms (e = exp(-|eta|); sigmoid = 1 / (1 + e) for eta >= 0, e / (1 + e) otherwise; softplus =
+    max(eta, 0) + log1p(e)), evaluated by gsmvi_logistic_batched_f64: what examples/example_gsm.py:34-35 gets from a model's
+    log_prob and jit(grad(...)).  numpy arrays or tensors in; everything is kept on the device as float64 / int32.  Arguments
+    are validated on the host before any device work (ValueError naming the argument).
+
+    ``lp_g(x, out=None)``: (K, B, D) -> (K, B, D) scores, ``device_native`` and ``graph_safe`` (one capturable launch, no
+    allocation with ``out``).  ``lp(x)``: (K, rows, D) -> (K, rows) values (what ADVIBatch's losses and BatchedKLMonitor sum per
+    problem); a device tensor or numpy.  ``lp_and_score(x)``: (scores, values) from one launch."""
+
+    _y_names_family = False
+
+    def __init__(self, A, y, prior_precision=1.0, counts=None, engine=None):
+        super().__init__(A, y, "logistic", prior_precision, counts, engine=engine)
+
+    def _call(self, x, **kw):           # the logistic entry point of its own: the model is the GLM's with no offset and tau = 1
+        return self.engine.logistic_batched(x, self.A, self.y, self.counts, self.prior_precision, **kw)

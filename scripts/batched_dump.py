@@ -1,6 +1,8 @@
 """Seeded dump of the batched GSM and BaM kernels' outputs, for before / after comparisons of a library change (DESIGN.md
 section 9): at eight (D, B) shapes, K = 13 (a tail slot in the four-problem workgroups), the one-shot update, a 20-iteration
-fit and a fit with one NaN target, for both methods -- 48 arrays of results.
+fit and a fit with one NaN target, for both methods -- 48 arrays of results; and the GLM entry points (score and density, the
+logistic entry, Hessian and inverse, six Newton rounds, the predictive, three L-BFGS rounds) at K = 13 for the four families
+with and without an offset, at (D, N, rows of X) shapes on both sides of every packing and tile boundary.
 
   python scripts/batched_dump.py OUT.npz                 dump with the library the package loads
   GSMVI_HIP_LIB_VARIANT=old python scripts/batched_dump.py OUT.npz   ... with gsm-vi_amd/libgsmvi_hip_old.so
@@ -14,11 +16,66 @@ import numpy as np
 SHAPES = ((1, 1), (4, 2), (5, 2), (10, 2), (16, 8), (17, 3), (33, 4), (64, 8))
 
 
+# D: one lane, the four-problem packing's last, the first of one problem per workgroup, the largest; N: one row, a full tile of
+# 32, one row more, three tiles; rows of X: one, an odd count above the packed tile of 16, one above the tile of 32
+GLM_SHAPES = ((1, 1, 1), (1, 70, 33), (16, 32, 17), (16, 33, 33), (17, 33, 1), (17, 70, 17), (64, 32, 33), (64, 70, 17))
+GLM_FAMILIES = ("logistic", "poisson", "probit", "gaussian")
+
+
+def dump_glm(out, K=13):
+    """the outputs of every GLM entry point: counts 0 for problem 1 and N for problem 2, lam = 0 for problem 0, K values of
+    tau for the gaussian family; every array as float64"""
+    from gsmvi_amd.engine import get_engine
+    eng = get_engine()
+    host = lambda *ts: np.concatenate([eng.to_numpy(t).astype(np.float64).reshape(K, -1) for t in ts], 1)     # noqa: E731
+    for D, N, rows in GLM_SHAPES:
+        for fi, family in enumerate(GLM_FAMILIES):
+            rs = np.random.RandomState(10000 * D + 100 * N + 10 * rows + fi)
+            Ah = rs.standard_normal((K, N, D)) / np.sqrt(D)
+            oh = 0.3 * rs.standard_normal((K, N))
+            eta = np.einsum("knd,kd->kn", Ah, rs.standard_normal((K, D))) + oh
+            tau_h = 0.5 + rs.random_sample(K)
+            if family == "poisson":
+                yh = rs.poisson(np.exp(np.minimum(eta, 3.0))).astype(np.float64)
+            elif family == "gaussian":
+                yh = eta + rs.standard_normal((K, N)) / np.sqrt(tau_h)[:, None]
+            else:
+                yh = (rs.random_sample((K, N)) < 1.0 / (1.0 + np.exp(-eta))).astype(np.float64)
+            cnt = np.array([max(1, N - k) for k in range(K)])
+            cnt[1], cnt[2] = 0, N
+            lam_h = 0.1 + rs.random_sample(K)
+            lam_h[0] = 0.0
+            R = rs.standard_normal((K, D, D))
+            A, y, X = eng.asarray(Ah), eng.asarray(yh), eng.asarray(rs.standard_normal((K, rows, D)))
+            mean, cov = eng.asarray(0.3 * rs.standard_normal((K, D))), eng.asarray(R @ np.swapaxes(R, 1, 2) / D + 0.1 * np.eye(D))
+            for off in (None, eng.asarray(oh)):
+                model = dict(offset=off, counts=eng.batched_counts(cnt), prior_prec=eng.batched_regs(lam_h),
+                             noise_prec=eng.batched_regs(tau_h) if family == "gaussian" else 1.0)
+                tag = f"{family}_{'off' if off is not None else 'nooff'}_D{D}_N{N}_r{rows}"
+                out[f"glm_{tag}"] = host(*eng.glm_batched(X, A, y, family, want="both", **model))
+                if family == "logistic" and off is None:
+                    out[f"logistic_{tag}"] = host(*eng.logistic_batched(X, A, y, model["counts"], model["prior_prec"], want="both"))
+                out[f"hessian_{tag}"] = host(*eng.glm_hessian_batched(X[:, 0].contiguous(), A, y, family, want="both", **model))
+                st = eng.laplace_state_batched(eng.zeros(K, D))
+                for r in range(6):
+                    eng.laplace_step_batched(st, A, y, family, start=r == 0, **model)
+                    out[f"laplace{r}_{tag}"] = host(*(st[n] for n in ("x", "g", "d", "Xt", "sc", "ist")))
+                out[f"predict_{tag}"] = host(*eng.glm_predict_batched(mean, cov, A, family, offset=off, y=y, counts=model["counts"],
+                                                                      noise_prec=model["noise_prec"], nodes=8))
+                st = eng.lbfgs_state_batched(eng.zeros(K, D))
+                for r in range(3):
+                    G, lp = eng.glm_batched(st["Xt"].reshape(K, 1, D), A, y, family, want="both", **model)
+                    eng.lbfgs_step_batched(lp.reshape(K), G.reshape(K, D), st, start=r == 0)
+                    out[f"lbfgs{r}_{tag}"] = host(*(st[n] for n in ("x", "g", "d", "Xt", "S", "Y", "sc", "ist")))
+                out[f"lbfgs_cov_{tag}"] = host(eng.lbfgs_hess_inv_batched(st))
+
+
 def dump(path):
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     import gsmvi_amd
     K = 13
     out = {}
+    dump_glm(out, K)
     for D, B in SHAPES:
         rs = np.random.RandomState(100 * D + B)
         A = rs.standard_normal((K, D, D))

@@ -16,24 +16,11 @@ def sigmoid_softplus(eta):
 
 
 def score_and_lp(A, y, counts, lam, X):
-    """A (K, N, D), y (K, N), counts (K,) or None, lam a number or (K,), X (K, rows, D) -> G (K, rows, D), lp (K, rows); a
-    per-problem loop.  A row of X with a non-finite entry gets NaN outputs, as the kernel gives it."""
-    A, y, X = np.asarray(A, dtype=np.float64), np.asarray(y, dtype=np.float64), np.asarray(X, dtype=np.float64)
-    K, N, D = A.shape
-    lam = np.broadcast_to(np.asarray(lam, dtype=np.float64), (K,))
-    G, lp = np.empty_like(X), np.empty(X.shape[:2])
-    for k in range(K):
-        n = N if counts is None else int(min(max(int(counts[k]), 0), N))
-        Ak, yk = A[k, :n], y[k, :n]
-        with np.errstate(all="ignore"):
-            eta = X[k] @ Ak.T                                           # (rows, n)
-            sig, sp = sigmoid_softplus(eta)
-            G[k] = (yk[None, :] - sig) @ Ak - lam[k] * X[k]
-            lp[k] = (yk[None, :] * eta - sp).sum(1) - 0.5 * lam[k] * (X[k] * X[k]).sum(1)
-        bad = ~np.isfinite(X[k]).all(1)
-        G[k, bad] = np.nan
-        lp[k, bad] = np.nan
-    return G, lp
+    """A (K, N, D), y (K, N), counts (K,) or None, lam a number or (K,), X (K, rows, D) -> G (K, rows, D), lp (K, rows): the loop
+    of glm_batched_ref.score_and_lp for the logistic family without an offset (imported here: that module imports this one).
+    A row of X with a non-finite entry gets NaN outputs, as the kernel gives it."""
+    from glm_batched_ref import score_and_lp as glm_score_and_lp
+    return glm_score_and_lp("logistic", A, y, None, counts, lam, 1.0, X)
 
 
 def make_inputs(K, N, D, rows, scale=1.0, soft=False, seed=None):
