@@ -33,6 +33,10 @@ Mirrors the reference's public surface for the hot path (reference file:line):
     Pareto-smoothed importance diagnostic of K
     Gaussians: khat, ess, log Z, corrected
     moments; one launch after the target's lp)   gsmvi/monitors.py:83-125 (the role; no reference twin)
+    psis_loo_batched, LOOBatchedResult,
+    BatchedGLMTarget.loo (PSIS leave-one-out of K
+    fitted GLM posteriors: elpd_loo, p_loo, se and
+    the pointwise khat; one launch after psis_batched) examples/example_gsm.py:34-35, comparing fitted models; no reference twin
     lbfgs_init_batched (the L-BFGS initialiser
     for K problems at once, D <= 64: one launch
     per function evaluation after lp_g and lp)   gsmvi/initializers.py:5-17
@@ -60,6 +64,7 @@ from .monitors import KLMonitor, DeviceKLMonitor, BatchedKLMonitor   # noqa: F40
 from .initializers import lbfgs_init, lbfgs_init_batched, LbfgsBatchedResult   # noqa: F401
 from .initializers import laplace_init_batched, LaplaceBatchedResult          # noqa: F401
 from .diagnostics import psis_batched, psis_weights_batched, PSISBatchedResult   # noqa: F401
+from .diagnostics import psis_loo_batched, LOOBatchedResult          # noqa: F401
 from .advi import ADVI                                               # noqa: F401
 
 __version__ = "0.1.0"

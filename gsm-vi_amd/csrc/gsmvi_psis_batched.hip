@@ -11,17 +11,14 @@
 // padded with +inf to S2 = the next power of two, their S2 indices, the S normalised weights in row order, the tail (at most
 // 192 exceedances) and the 43 candidates of its fit, and for the fused entry R (D x ld), mean, pivots and a tile of rows
 // (tr x ldy, odd strides D | 1): at most 134 KB (D = 64, S = 4096), inside GB_LDS_MAX.
-// Stage (b): two reductions (non-finite count, maximum); a bitonic network on (value, index) pairs, ascending by value then by
-// index -- numpy's stable argsort, so ties fall the same way on every run; the tail lies at the end of the sorted array, the
-// fit runs on it with four lanes per candidate (each sums every fourth exceedance in order; the four partial sums are added in
-// order), the smoothed values overwrite it in place; truncation, log-sum-exp and the effective sample size are sums over the
-// sorted array; the weights return to row order through the indices.  Every sum is a fixed tree -- a thread's own entries
-// in order, a butterfly within each wave, then the four waves in order -- and there are no atomics: the outputs are
-// bit-identical from run to run.  Every thread runs every barrier whatever its problem's verdict (the verdicts only select what
-// is written), and a workgroup reads and writes only its own problem's slices.  Inputs are only read; no context workspace.
+// Stage (b) is ps_stage of gsmvi_psis_stage.h (shared with the leave-one-out kernel, gsmvi_psis_loo_batched.hip): every sum is a
+// fixed tree and there are no atomics, so the outputs are bit-identical from run to run.  Every thread runs every barrier
+// whatever its problem's verdict (the verdicts only select what is written), and a workgroup reads and writes only its own
+// problem's slices.  Inputs are only read; no context workspace.
 #include "gsmvi_common.h"
 #include "gsmvi_ctx.h"
 #include "gsmvi_batched.h"
+#include "gsmvi_psis_stage.h"
 #include "../../include/gsmvi_hip.h"
 #include <cfloat>
 #include <cmath>
@@ -29,10 +26,6 @@
 
 enum { PS_WEIGHTS = 0, PS_FUSED = 1 };
 #define PS_Q 8          // tile elements per thread: tr = max(1, 256 PS_Q / D) rows, at most S
-#define PS_MIN_S 5
-#define PS_MAX_S 4096
-#define PS_MAX_M 192    // the longest tail: ceil(3 sqrt(4096))
-#define PS_MAX_J 44     // candidates of the tail fit: 30 + floor(sqrt(n)) <= 43
 
 struct ps_args {
     long long K;
@@ -57,29 +50,8 @@ __host__ __device__ inline int ps_tile_rows(int D, int S) {
     const int t = (256 * PS_Q) / D;
     return t < S ? t : S;
 }
-// LDS doubles of the PSIS stage: sorted values (S2), weights in row order (S), the tail, b_j, L_j, omega_j, 4 partial sums per
-// candidate, 8 for the reductions; of the fused entry also R (D x ld), mean, pivots, first moments (D each), the tile
-__host__ __device__ inline int ps_lds_doubles(int S, int S2) { return S2 + S + PS_MAX_M + 7 * PS_MAX_J + 8; }
+// LDS doubles of the fused entry beside the stage's (ps_lds_doubles): R (D x ld), mean, pivots, first moments (D each), the tile
 __host__ __device__ inline int ps_lds_fused(int D, int ld, int ldy, int tr) { return D * ld + 3 * D + tr * ldy; }
-
-// the block's sum, to every thread: a butterfly within each wave, then the four waves in order
-__device__ __forceinline__ double ps_sum(double v, double* red, int l) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    __syncthreads();                    // the readers of the previous reduction are done
-    if ((l & 63) == 0) red[l >> 6] = v;
-    __syncthreads();
-    return ((red[0] + red[1]) + red[2]) + red[3];
-}
-
-__device__ __forceinline__ double ps_max(double v, double* red, int l) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o));
-    __syncthreads();
-    if ((l & 63) == 0) red[l >> 6] = v;
-    __syncthreads();
-    return fmax(fmax(red[0], red[1]), fmax(red[2], red[3]));
-}
 
 template <int MODE>
 __global__ __launch_bounds__(256) void k_psis_batched(ps_args a) {
@@ -87,22 +59,16 @@ __global__ __launch_bounds__(256) void k_psis_batched(ps_args a) {
     const int l = threadIdx.x, S = a.S, S2 = a.S2, M = a.M;
     const int D = a.D, ld = a.ld, ldy = a.ldy, TR = a.tr, DD = D * D;
     const size_t k = blockIdx.x;              // one problem per workgroup: the grid is K
-    double* val = ps_sm;                      // S2     log ratios, shifted, sorted, smoothed, truncated
-    double* lwu = val + S2;                   // S      normalised log weights in row order, then the weights
-    double* xs = lwu + S;                     // 192    the tail's exceedances, ascending
-    double* bs = xs + PS_MAX_M;               // 44     b_j
-    double* Ls = bs + PS_MAX_J;               // 44     L_j
-    double* ws = Ls + PS_MAX_J;               // 44     omega_j
-    double* part = ws + PS_MAX_J;             // 4 x 44 partial sums of kappa_j
-    double* red = part + 4 * PS_MAX_J;        // 8      per-wave partial results
-    double* R = red + 8;                      // FUSED: D x ld
+    double* R = ps_sm + ps_lds_doubles(S, S2);   // FUSED: D x ld
     double* m = R + D * ld;                   // D      mean
     double* pv = m + D;                       // D      pivots R_cc
     double* mom = pv + D;                     // D      sum w d
     double* T = mom + D;                      // TR x ldy  x - mean, then w
-    int* idx = reinterpret_cast<int*>(MODE == PS_FUSED ? T + TR * ldy : R);   // S2 row numbers
+    const ps_lds sm = ps_carve(ps_sm, reinterpret_cast<int*>(MODE == PS_FUSED ? T + TR * ldy : R), S, S2);
+    double* val = sm.val;                     // S2     the log ratios
+    double* lwu = sm.lwu;                     // S      normalised log weights in row order, then the weights
     const size_t ks = k * (size_t)S;
-    const double qnan = __longlong_as_double(0x7ff8000000000000LL), inf = __builtin_huge_val();
+    const double qnan = __longlong_as_double(0x7ff8000000000000LL);
 
     // ---- (a) the log ratios ----------------------------------------------------------------------------------------------
     int cinfo = 0;
@@ -152,115 +118,15 @@ __global__ __launch_bounds__(256) void k_psis_batched(ps_args a) {
         __syncthreads();
     }
 
-    // ---- (b) 1-2: non-finite input, the shift ----------------------------------------------------------------------------
-    double nb = 0.0, vmax = -inf;
-    for (int s = l; s < S; s += 256) {
-        const double v = val[s];
-        if (!(v < inf)) nb += 1.0;            // NaN or +inf
-        vmax = fmax(vmax, v);
-    }
-    nb = ps_sum(nb, red, l);
-    vmax = ps_max(vmax, red, l);
-    const bool bad = cinfo != 0 || nb > 0.0 || vmax == -inf;
-    for (int p = l; p < S2; p += 256) {       // (each thread rewrites the entries it read)
-        val[p] = p < S ? val[p] - vmax : inf;
-        idx[p] = p;
-    }
-    __syncthreads();
-
-    // ---- 3: ascending by (value, index): a bitonic network on the S2 pairs, one barrier per stage ---------------------------
-    for (int kk = 2; kk <= S2; kk <<= 1)
-        for (int j = kk >> 1; j > 0; j >>= 1) {
-            for (int t = l; t < (S2 >> 1); t += 256) {
-                const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1)), p = i | j;
-                const double va = val[i], vb = val[p];
-                const int ia = idx[i], ib = idx[p];
-                const bool after = va > vb || (va == vb && ia > ib);
-                if (after == ((i & kk) == 0)) {
-                    val[i] = vb; val[p] = va;
-                    idx[i] = ib; idx[p] = ia;
-                }
-            }
-            __syncthreads();
-        }
-    const double LOG_DBL_MIN = -708.39641853226410622;
-    double cut = val[S - M - 1];
-    cut = cut > LOG_DBL_MIN ? cut : LOG_DBL_MIN;
-    const double ec = exp(cut);
-    const int n = (int)ps_sum(l < M && val[S - M + l] > cut ? 1.0 : 0.0, red, l);   // the tail: the last n sorted entries
-    if (l < n) xs[l] = exp(val[S - n + l]) - ec;
-    __syncthreads();
-
-    // ---- 4-5: the tail fit (n > 4) -----------------------------------------------------------------------------------------
-    const bool fit = n > 4;
-    const int mj = 30 + (int)sqrt((double)n);
-    const double dn = (double)n;
-    {
-        const int jj = l >> 2, q = l & 3;
-        if (fit && jj < mj) {
-            const double b = (1.0 - sqrt((double)mj / ((double)(jj + 1) - 0.5))) / (3.0 * xs[(n + 2) / 4 - 1]) + 1.0 / xs[n - 1];
-            double s = 0.0;
-            for (int i = q; i < n; i += 4) s += log1p(-b * xs[i]);
-            part[l] = s;
-            if (q == 0) bs[jj] = b;
-        }
-    }
-    __syncthreads();
-    if (fit && l < mj) {
-        const double kap = (((part[4 * l] + part[4 * l + 1]) + part[4 * l + 2]) + part[4 * l + 3]) / dn;
-        Ls[l] = dn * (log(-bs[l] / kap) - kap - 1.0);
-    }
-    __syncthreads();
-    if (fit && l < mj) {
-        double s = 0.0;
-        for (int i = 0; i < mj; ++i) s += exp(Ls[i] - Ls[l]);
-        const double om = 1.0 / s;
-        ws[l] = om < 10.0 * DBL_EPSILON ? 0.0 : om;
-    }
-    __syncthreads();
-    double bb = 0.0, kh = inf, sigma = 0.0;
-    if (fit) {                                // (every thread, the same order)
-        double sw = 0.0;
-        for (int j = 0; j < mj; ++j) sw += ws[j];
-        for (int j = 0; j < mj; ++j) bb += (ws[j] / sw) * bs[j];
-    }
-    const double kap = ps_sum(fit && l < n ? log1p(-bb * xs[l]) : 0.0, red, l) / dn;
-    if (fit) {
-        sigma = -kap / bb;
-        kh = (dn * kap + 5.0) / (dn + 10.0);
-    }
-
-    // ---- 6: the smoothed tail ------------------------------------------------------------------------------------------------
-    if (fit && kh - kh == 0.0 && l < n) {     // (khat finite)
-        const double lq = log1p(-((double)l + 0.5) / dn);
-        const double q = kh == 0.0 ? -sigma * lq : sigma * expm1(-kh * lq) / kh;
-        val[S - n + l] = log(q + ec);
-    }
-    __syncthreads();
-
-    // ---- 7-8: truncate, normalise, summarise --------------------------------------------------------------------------------
-    double s1 = 0.0;
-    for (int p = l; p < S; p += 256) {
-        double v = val[p];
-        v = v > 0.0 ? 0.0 : v;
-        val[p] = v;
-        s1 += exp(v);
-    }
-    const double lse = log(ps_sum(s1, red, l));
-    double s2 = 0.0;
-    for (int p = l; p < S; p += 256) {
-        const double v = val[p] - lse;
-        const int s = idx[p];
-        if (s < S) lwu[s] = v;                // (always, unless the ratios held a NaN: then nothing of lwu is used)
-        s2 += exp(2.0 * v);
-    }
-    const double ess = 1.0 / ps_sum(s2, red, l);   // (its barriers also publish lwu)
+    // ---- (b) the PSIS stage -------------------------------------------------------------------------------------------------
+    const ps_verdict v = ps_stage(sm, S, S2, M, l, cinfo != 0);
+    const bool bad = v.bad;
     for (int s = l; s < S; s += 256) a.lw[ks + s] = bad ? qnan : lwu[s];
     if (l == 0) {
-        a.khat[k] = bad ? qnan : kh;
-        a.ess[k] = bad ? qnan : ess;
-        a.log_z[k] = bad ? qnan : lse + vmax - log((double)S);
-        a.info[k] = cinfo != 0 ? cinfo : (bad ? -1 : (fit ? 0 : -2));
+        a.khat[k] = bad ? qnan : v.khat;
+        a.ess[k] = bad ? qnan : v.ess;
+        a.log_z[k] = bad ? qnan : v.lse + v.vmax - log((double)S);
+        a.info[k] = cinfo != 0 ? cinfo : (bad ? -1 : (v.fit ? 0 : -2));
     }
 
     // ---- (c) the importance-weighted moments: a second walk over X ------------------------------------------------------------
@@ -329,10 +195,7 @@ static int ps_ppw(int, int) { return 1; }     // one problem per workgroup at ev
 
 static int ps_launch(gsmvi_ctx* ctx, void* stream, int mode, ps_args& a, const char* fn) {
     const int S = a.S;
-    a.S2 = 8;
-    while (a.S2 < S) a.S2 <<= 1;
-    const int m5 = (S + 4) / 5, m3 = (int)ceil(3.0 * sqrt((double)S));
-    a.M = m5 < m3 ? m5 : m3;
+    ps_sizes(S, &a.S2, &a.M);
     size_t lds = (size_t)ps_lds_doubles(S, a.S2) * sizeof(double) + (size_t)a.S2 * sizeof(int);
     if (mode == PS_FUSED) {
         a.ld = a.D | 1;

@@ -586,7 +586,7 @@ class HipEngine:
                  "fupd_generic": 0x400, "lowrank_fast": 0x800, "lowrank_generic": 0x1000, "batched": 0x2000,
                  "batched_bam": 0x4000, "batched_kl": 0x8000, "batched_advi": 0x10000, "batched_target": 0x20000,
                  "batched_lbfgs": 0x40000, "batched_laplace": 0x80000, "batched_predict": 0x100000,
-                 "batched_psis": 0x200000}
+                 "batched_psis": 0x200000, "batched_loo": 0x400000}
     PATH_GENERIC_MASK = 0x4 | 0x10 | 0x40 | 0x100 | 0x400 | 0x1000
 
     def last_path(self, reset=True):
@@ -1108,6 +1108,34 @@ class HipEngine:
             self._packed(log_z, (K,), "log_z"), self._dp(mean_is, (K, D), "mean_is"), self._dp(cov_is, (K, D, D), "cov_is"),
             self._ints(info, K, "info")))
         return logr, lw, khat, ess, log_z, mean_is, cov_is, info
+
+    # ---- batched PSIS leave-one-out of K fitted GLM posteriors (csrc/gsmvi_psis_loo_batched.hip) ----------------------------------
+    def psis_loo_tile(self, D, S):
+        """gsmvi_psis_loo_tile: the observations one workgroup of ``psis_loo_batched`` takes at (D, S); a pure function, no GPU"""
+        return int(self.lib.gsmvi_psis_loo_tile(int(D), int(S)))
+
+    def psis_loo_batched(self, X, logr, lw, A, y, family, offset=None, counts=None, noise_prec=1.0, pointwise_loglik=False):
+        """PSIS leave-one-out of K fitted GLM posteriors from the draws X (K, S, D) of q_k and the problem-level ratios ``logr``
+        and smoothed weights ``lw`` (K, S) of ``psis_batched`` on the same draws, one launch (gsmvi_psis_loo_batched_f64; the
+        definition is in include/gsmvi_hip.h)  [no reference twin]: returns (elpd, lpd, khat, ess (K, N), info (K, N) int32: 0,
+        -1 = non-finite ratios (the row's outputs are NaN), -2 = tail too short (khat = +inf), -3 = not a valid row, loglik
+        (K, N, S) or None without ``pointwise_loglik``).  ``family``, ``offset``, ``counts`` and ``noise_prec`` are
+        ``glm_batched``'s."""
+        K, S, D = X.shape
+        N = A.shape[1]
+        fam, t, tp = self._glm_family_args(family, noise_prec, K)
+        self._ensure(max(self._max_D, 1), max(self._max_B, 1))
+        X, logr, lw = X.contiguous(), logr.contiguous(), lw.contiguous()
+        elpd, lpd, khat, ess = self.empty(K, N), self.empty(K, N), self.empty(K, N), self.empty(K, N)
+        info = self.batched_ints(K * N).view(K, N)
+        loglik = self.empty(K, N, S) if pointwise_loglik else None
+        _lib.check("gsmvi_psis_loo_batched_f64", self.lib.gsmvi_psis_loo_batched_f64(
+            self._ctx, self._stream(), fam, K, N, D, S, self._packed(A, (K, N, D), "A"), self._packed(y, (K, N), "y"),
+            self._dp(offset, (K, N), "offset"), self._ints(counts, K, "counts"), t, tp, self._packed(X, (K, S, D), "X"),
+            self._packed(logr, (K, S), "logr"), self._packed(lw, (K, S), "lw"), self._dp(loglik, (K, N, S), "loglik"),
+            self._packed(elpd, (K, N), "elpd"), self._packed(lpd, (K, N), "lpd"), self._packed(khat, (K, N), "khat"),
+            self._packed(ess, (K, N), "ess"), self._ints(info, K * N, "info")))
+        return elpd, lpd, khat, ess, info, loglik
 
     def bam_update(self, X, G, mu0, S0, reg, jitter=0.0, out=None, flag=None):
         """(mu, S) of BaM [gsmvi/bam.py:72-114]; S symmetrised, jitter on the diagonal."""

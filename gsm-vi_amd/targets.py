@@ -342,6 +342,13 @@ class BatchedGLMTarget:
             out = tuple(eng.to_numpy(t) if t is not None else None for t in out)
         return GLMPrediction(*out)
 
+    def loo(self, mean, cov, keys, **kw):
+        """``psis_loo_batched(self, mean, cov, keys, **kw)``: the PSIS leave-one-out density of every observation under the fitted
+        q_k = N(mean_k, cov_k) (a ``LOOBatchedResult``: ``elpd_loo``, ``p_loo``, ``se`` per problem, the pointwise values and
+        their khat)"""
+        from .diagnostics import psis_loo_batched
+        return psis_loo_batched(self, mean, cov, keys, **kw)
+
 
 class BatchedLogisticTarget(BatchedGLMTarget):
     """K Bayesian logistic regressions with their own data sets, for ``GSMBatch``, ``BaMBatch``, ``ADVIBatch`` and

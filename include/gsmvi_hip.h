@@ -27,6 +27,8 @@
  *   examples/example_gsm.py:34-35 the use of the fit: predictions and the held-out score of K fitted GLMs (no reference twin) -> gsmvi_glm_predict_batched_f64
  *   monitors.py:83-125 the role (is q_k close to its target?), per problem and comparable across problems: the Pareto-smoothed
  *   importance diagnostic of K fitted Gaussians (no reference twin)    ->  gsmvi_psis_batched_f64, gsmvi_psis_weights_batched_f64
+ *   examples/example_gsm.py:34-35 the comparison of fitted models: the PSIS leave-one-out density of every observation of K fitted
+ *   GLMs (no reference twin)                                           ->  gsmvi_psis_loo_batched_f64, gsmvi_psis_loo_tile
  *   gsmvi/bam.py:72-114       bam_lowrank_update(samples,vs,mu0,S0,reg) ->  gsmvi_bam_update_f64
  *   gsmvi/bam.py:31-69        bam_update(samples,vs,mu0,S0,reg)         ->  gsmvi_bam_update_f64 (same result, K6)
  *
@@ -275,6 +277,7 @@ int gsmvi_get_profile(gsmvi_ctx* ctx, float* ms, int n);
 #define GSMVI_PATH_BATCHED_LAPLACE 0x80000u /* k_laplace_batched: the batched GLM Hessian and Newton step             */
 #define GSMVI_PATH_BATCHED_PREDICT 0x100000u /* k_glm_predict_batched: the batched GLM posterior predictive             */
 #define GSMVI_PATH_BATCHED_PSIS 0x200000u /* k_psis_batched: the batched Pareto-smoothed importance diagnostic            */
+#define GSMVI_PATH_BATCHED_LOO 0x400000u /* k_psis_loo_batched: the batched PSIS leave-one-out                                */
 #define GSMVI_PATH_GENERIC_MASK (0x0004u | 0x0010u | 0x0040u | 0x0100u | 0x0400u | 0x1000u)
 int gsmvi_last_path(gsmvi_ctx* ctx, unsigned* bits, int reset);
 
@@ -664,6 +667,47 @@ int gsmvi_psis_weights_batched_f64(gsmvi_ctx* ctx, void* stream, int64_t K, int6
 int gsmvi_psis_batched_f64(gsmvi_ctx* ctx, void* stream, int64_t K, int D, int64_t S, const double* mean, const double* cov,
                            const double* X, const double* lp, double* logr, double* lw, double* khat, double* ess,
                            double* log_z, double* mean_is, double* cov_is, int* info);
+
+/*
+ * Batched PSIS leave-one-out (PSIS-LOO): the pointwise leave-one-out log predictive density of every observation of K fitted GLM
+ * posteriors, from S draws of the approximation q_k (Vehtari, Gelman, Gabry, "Practical Bayesian model evaluation using
+ * leave-one-out cross-validation and WAIC", 2017; the ratios carry the correction for draws taken from an approximation in place of
+ * the posterior: Magnusson, Andersen, Jonasson, Vehtari, "Bayesian leave-one-out cross-validation for large data", 2019).  The
+ * reference has no twin.  One launch, one workgroup per (problem, tile of gsmvi_psis_loo_tile(D, S) observations).
+ * The model's arguments are those of gsmvi_glm_predict_batched_f64 (family, A (K x N x D), y (K x N, required), offset (K x N or
+ * NULL), counts_dev (K ints or NULL), noise_prec / noise_prec_dev: the gaussian family's alone) with no prior.  X (K x S x D) are the
+ * draws x_s of q_k, logr (K x S) the ratios lp - log q and lw (K x S) the normalised smoothed log weights that
+ * gsmvi_psis_batched_f64 writes for the same draws.  n_k = counts_dev[k] clamped to 0 .. N (N without counts_dev).  For problem k
+ * and row i < n_k:
+ *   eta_si = a_i . x_s + offset_i
+ *   l_si   = log p(y_i | eta_si), normalised as the lpd of gsmvi_glm_predict_batched_f64 is: t of gsmvi_glm_batched_f64's link at
+ *            (eta_si, y_i, tau_k); the poisson family subtracts lgamma(y_i + 1), the gaussian family adds log(tau_k / (2 pi)) / 2;
+ *            a draw that the link flags (poisson: e^eta not finite) has l_si = NaN
+ *   rho_si = logr_s - l_si (one subtraction): the log ratio of the posterior without observation i to q_k, up to a constant
+ *   the PSIS stage, steps 1-8 of gsmvi_psis_weights_batched_f64 above exactly (the (value, row) order of the sort and the -1 / -2
+ *   verdicts included), on rho_.i gives the normalised smoothed log weights w_si, khat[k, i], ess[k, i] and info[k, i]
+ *   elpd[k, i] = log sum_s exp(w_si + l_si):  the leave-one-out log predictive density
+ *   lpd[k, i]  = log sum_s exp(lw_s + l_si):  the importance-corrected in-sample density; p_loo is lpd - elpd
+ * both as max + log sum exp(. - max), the maximum and the sum each a fixed tree over the S draws (a thread's entries in order, a
+ * butterfly within each wave, the waves in order; no atomics): the outputs are bit-identical from run to run.
+ * info[k, i] = -1 (a NaN or +inf among rho_.i -- a NaN l_si, a NaN logr of a failed problem-level run --, or every rho -inf): elpd,
+ * lpd, khat and ess of (k, i) are NaN.  info[k, i] = -2 (fewer than five tail entries): plain self-normalised weights and
+ * khat = +inf, as in the weights entry.  Rows i >= n_k are never loaded: elpd, lpd, khat and ess are NaN and info[k, i] = -3.  A verdict
+ * touches only its own (k, i).  loglik (K x N x S, or NULL) receives l_si (NaN for rows i >= n_k).  Outputs: elpd, lpd, khat, ess
+ * (K x N doubles each) and info (K x N ints), all required.
+ * gsmvi_psis_loo_tile(D, S) is a pure function (no GPU): the observations per workgroup, the largest count of at most 4 whose
+ * l_si (S doubles each) fit in the workgroup's 160 KB of LDS beside max(stage, tiles) doubles, where stage = S2 + S + 508 + S2 / 2
+ * (S2 = S rounded up to a power of two, at least 8) and tiles = 80 (16 ceil(D / 16) + 1) + 48; 0 for D or S out of bounds.
+ * 1 <= D <= 64, 5 <= S <= 4096, N >= 1, K >= 1 with K ceil(N / gsmvi_psis_loo_tile(D, S)) <= 2^24 - 1.  Shapes, NULL arrays and
+ * overlaps (every output is a written array) are checked before the context is looked at (then a NULL ctx); every failure returns
+ * GSMVI_ERR_BAD_ARG before anything is enqueued.  Inputs are only read; no context workspace is used; one capturable launch with no
+ * host synchronisation.  Sets GSMVI_PATH_BATCHED_LOO.
+ */
+int gsmvi_psis_loo_tile(int D, int64_t S);
+int gsmvi_psis_loo_batched_f64(gsmvi_ctx* ctx, void* stream, int family, int64_t K, int64_t N, int D, int64_t S, const double* A,
+                               const double* y, const double* offset, const int* counts_dev, double noise_prec,
+                               const double* noise_prec_dev, const double* X, const double* logr, const double* lw,
+                               double* loglik, double* elpd, double* lpd, double* khat, double* ess, int* info);
 
 /*
  * Upper Cholesky factor R (R^T R = S, R upper triangular, strictly-lower part zeroed) of a
