@@ -45,6 +45,11 @@ bool gsmvi_launch_gsm_scalars_fast(hipStream_t st, hipEvent_t* ev, int D, int B,
 bool gsmvi_launch_gsm_cov_sym(hipStream_t st, hipEvent_t* ev, int D, int B, const double* rec, int ldrec,
                               const double* mu0, const double* S0, int lds0, double* S, int lds, double* mu_out,
                               int dbg, unsigned long long* stamps, int num_cu);
+void gsmvi_launch_panel_fast_part(hipStream_t st, hipEvent_t* ev, dim3 grid, int D, int B, const double* G, int ldg,
+                                  const double* S0, int lds0, double* Pp, int chunks_per_wg, const double* X, int ldx,
+                                  const double* mu0, double* Qg, double* Qm);
+void gsmvi_launch_gsm_cov_sym_slabs(hipStream_t st, hipEvent_t* ev, int D, int B, const struct gsm_slab_src& fs, const double* mu0,
+                                    const double* S0, int lds0, double* S, int lds, double* mu_out);
 int gsmvi_panel_fast_chunk(int MT);
 int gsmvi_potrf_impl(struct gsmvi_ctx* ctx, hipStream_t st, int D, const double* S, int lds, double* R, int ldr,
                      int* info_dev);
@@ -313,6 +318,7 @@ int gsmvi_set_tuning(gsmvi_ctx* ctx, const char* name, int value) {
     else if (!strcmp(name, "lowrank_kp")) ctx->tune_lowrank_kp = value;
     else if (!strcmp(name, "bam_basis")) ctx->tune_bam_basis = value;
     else if (!strcmp(name, "scalars_nt")) ctx->tune_scalars_nt = value;
+    else if (!strcmp(name, "gsm_two_launch")) ctx->tune_gsm_two_launch = value;
     else if (!strcmp(name, "cov_dbg")) ctx->tune_cov_dbg = value;   // ablation bits, timing experiments only
     else if (!strcmp(name, "timeline")) {                           // whole-update timeline stamps (diagnostic)
         if (value && !ctx->stamps) {
@@ -590,6 +596,57 @@ static int gsm_records(gsmvi_ctx* ctx, hipStream_t hs, int D, int B, int kc, con
     return check_launch("k_gsm_scalars");
 }
 
+// The dense update in TWO launches (no per-sample launch, no records): the product launch leaves partial dots beside its
+// slabs, the covariance launch forms its factor tiles from samples, slabs and partials (gsmvi_fast.hip: k_panel_fast<.., PART>,
+// k_gsm_cov_sym<.., FROM_SLABS>).  One gated shape family; *cpw_out, *kc_out = the product's split (the arithmetic of
+// gsmvi_panel_product_nc).  The diagnostics that stamp or ablate the three kernels keep the three launches.
+static bool gsm_two_launch_gate(const gsmvi_ctx* ctx, int D, int B, const double* X, int ldx, const double* G, int ldg,
+                                const double* mu0, const double* S0, int lds0, const double* S, int lds, int* cpw_out,
+                                int* kc_out) {
+    if (!ctx->tune_gsm_two_launch || ctx->tune_no_fast || ctx->tune_timeline || ctx->tune_cov_dbg) return false;
+    if (B != 16 && B != 32) return false;
+    if (D % 256 != 0 || D > 1024) return false;
+    if (ldx % 2 != 0 || ldg % 2 != 0 || lds0 % 2 != 0 || lds % 2 != 0) return false;
+    if (!aligned16(X) || !aligned16(G) || !aligned16(mu0) || !aligned16(S0) || !aligned16(S)) return false;
+    const int strips = D / 16, nchunks = D / 256;              // one row block of B samples: MT = B / 16, chunks of 256 rows
+    int kc = ctx->tune_panel_kc > 0 ? ctx->tune_panel_kc : (2 * ctx->num_cu + strips - 1) / strips;
+    if (kc > nchunks) kc = nchunks;
+    if (kc < 1) kc = 1;
+    const int cpw = (nchunks + kc - 1) / kc;
+    kc = (nchunks + cpw - 1) / cpw;
+    if (kc > 4 || kc * cpw != nchunks) return false;           // <= 4 slabs of whole chunks
+    *cpw_out = cpw;
+    *kc_out = kc;
+    return true;
+}
+
+static int gsm_two_launch(gsmvi_ctx* ctx, hipStream_t hs, int D, int B, int cpw, int kc, const double* X, int ldx,
+                          const double* G, int ldg, const double* mu0, const double* S0, int lds0, double* mu, double* S,
+                          int lds) {
+    const int strips = D / 16;
+    double* Qg = ctx->sg;                                       // [B][kc * strips], then [B][strips]: the record area is unused here
+    double* Qm = Qg + (size_t)B * kc * strips;
+    ctx->px = gsmvi_panel_extras();
+    ctx->px_used = 1;
+    hipEvent_t* ev0 = ctx->stage_events(0);
+    ctx->ev_valid[1] = 0;                                       // no per-sample launch: gsmvi_get_profile reports -1 for it
+    gsmvi_launch_panel_fast_part(hs, ev0, dim3(strips, kc, 1), D, B, G, ldg, S0, lds0, ctx->pp, cpw, X, ldx, mu0, Qg, Qm);
+    ctx->path |= GSMVI_PATH_PANEL_FAST;
+    int st = check_launch("k_panel_fast(partials)");
+    if (st != GSMVI_OK) return st;
+    gsm_slab_src fs;
+    fs.X = X;
+    fs.ldx = ldx;
+    fs.Pp = ctx->pp;
+    fs.Qg = Qg;
+    fs.Qm = Qm;
+    fs.KC = kc;
+    fs.strips = strips;
+    gsmvi_launch_gsm_cov_sym_slabs(hs, ctx->stage_events(2), D, B, fs, mu0, S0, lds0, S, lds, mu);
+    ctx->path |= GSMVI_PATH_COV_SYM | GSMVI_PATH_GSM_TWO_LAUNCH;
+    return check_launch("k_gsm_cov_sym(slabs)");
+}
+
 int gsmvi_gsm_update_f64(gsmvi_ctx* ctx, void* stream, int D, int B, const double* X, int ldx, const double* G,
                          int ldg, const double* mu0, const double* S0, int lds0, double* mu, double* S, int lds) {
     int st = check_common(ctx, D, B, __func__);
@@ -599,6 +656,9 @@ int gsmvi_gsm_update_f64(gsmvi_ctx* ctx, void* stream, int D, int B, const doubl
     BAD_ARG(S == S0 || mu == mu0, "outputs must not alias inputs");
     hipStream_t hs = reinterpret_cast<hipStream_t>(stream);
     const int ldrec = 3 * D + (D & 1);            // even stride keeps every record 16-byte aligned
+    int cpw2 = 0, kc2 = 0;
+    if (gsm_two_launch_gate(ctx, D, B, X, ldx, G, ldg, mu0, S0, lds0, S, lds, &cpw2, &kc2))
+        return gsm_two_launch(ctx, hs, D, B, cpw2, kc2, X, ldx, G, ldg, mu0, S0, lds0, mu, S, lds);
     st = gsm_local_stage(ctx, hs, D, B, X, ldx, G, ldg, mu0, S0, lds0, ctx->sg, ldrec);
     if (st != GSMVI_OK) return st;
     return gsm_apply(ctx, hs, D, B, ctx->sg, ldrec, mu0, S0, lds0, mu, S, lds);

@@ -37,6 +37,22 @@ struct gsmvi_panel_extras {
     const double* rd_R11 = nullptr;         // jmode 2, B % 16 == 0: the finished first diagonal block [R11 | W11] of the chain's Gram
     const double* rd_W11 = nullptr;         // matrix (B x B each, compact; Gvv's factor from k_bam_small48's side workgroup)
     int w4 = 0;                             // this launch takes the prefetching form k_panel_fast_p (round 6; set by the product drivers: large D, on the grid)
+    // k_panel_fast<.., PART> (the two-launch dense GSM update: A = G, M = S0, nrows = 16 or 32; never with the extras above) takes
+    // its five arguments in members that are free there, so that the kernel-argument block of every other instance -- and with it
+    // the offsets of the hidden arguments behind it -- is byte for byte what it was:  sj_src = X, sj_len = ldx, msl = mu0,
+    // sj_dst = Qg, mfin = Qm.  Beside its slab every workgroup leaves Qg[b][slab * strips + strip] = the sum over the strip's 16
+    // columns of G[b][col] slab[b][col], and the workgroups of slab 0 Qm[b][strip] = the sum of (mu0[col] - X[b][col]) G[b][col]
+    // (strips = gridDim.x).  Set by gsmvi_launch_panel_fast_part only.
+};
+
+// Where k_gsm_cov_sym<.., FROM_SLABS> takes its factor tiles from (the two-launch dense GSM update): the samples, the split-K
+// slabs of G S0 and the partial dots the product launch left beside them (layout: the last comment of gsmvi_panel_extras).
+struct gsm_slab_src {
+    const double* X = nullptr;
+    const double* Pp = nullptr;
+    const double* Qg = nullptr;
+    const double* Qm = nullptr;
+    int ldx = 0, KC = 0, strips = 0;
 };
 
 // BaM's regulariser as the kernels take it: by value, or -- so that a captured hipGraph can be replayed with another value
@@ -97,6 +113,7 @@ struct gsmvi_ctx {
                                // count is 1 (no hand-off involved); 0 = always product + k_panel_finish (A/B tests)
     int tune_scalars_nt = 0;   // threads per sample in k_gsm_scalars_fast (256/512/1024; 0 = default)
     int tune_no_fast = 0;      // 1 = force the guarded generic kernels (tests)
+    int tune_gsm_two_launch = 1;   // dense GSM update at B in {16, 32}, D % 256 == 0, D <= 1024 without the per-sample launch (0: three launches; A/B runs)
     int* bam_hint_host = nullptr;       // pinned word: k* of the last device BaM chain (step-count hint, never synchronised on)
     int tune_bam_kenq = 0;     // > 0: enqueue exactly this many multi-workgroup steps (tests of the tail kernel)
     int tune_bam_hint_slack = 1;   // Newton-Schulz steps enqueued beyond the previous call's k* (round 4: 1; before: 2; 0 measured in round 5)

@@ -45,7 +45,12 @@
 // RAG (round 5) = the clamped form for D % 64 != 0 or ncols % 16 != 0; RAG = false is the round-4 code, instruction for
 // instruction (the clamps and the straddling-wave branch cost 6 - 11 % on the grid shapes when they were unconditional:
 // scripts/cov_ab_rounds.py).
-template <int MT, bool HAS_SHIFT, int CHW, bool EXTRA, bool RIDER = false, bool RAG = false>
+// PART (two-launch dense GSM update; A = G, M = S0, one row block of NR = nrows samples, on the grid) = the launch also leaves
+// PARTIAL DOTS beside its slab (arguments: the last comment of gsmvi_panel_extras): per (sample, strip of 16 columns, slab) the sum of G slab over the
+// strip, and from the workgroups of slab 0 the sum of (mu0 - x) G.  The covariance kernel behind this launch re-reduces them in
+// every workgroup (k_gsm_cov_sym<.., FROM_SLABS>), so the per-sample launch between the two and its record round trip are gone;
+// the only ordering is the kernel boundary.  PART = false is the code as it was, instruction for instruction.
+template <int MT, bool HAS_SHIFT, int CHW, bool EXTRA, bool RIDER = false, bool RAG = false, bool PART = false>
 __global__ __launch_bounds__(512) void k_panel_fast(int D, int nrows, const double* __restrict__ A, int lda,
                                                     const double* __restrict__ shift, double alpha,
                                                     const double* __restrict__ M, int ldm,
@@ -85,6 +90,8 @@ __global__ __launch_bounds__(512) void k_panel_fast(int D, int nrows, const doub
     v4d acc[MT];
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt) acc[mt] = (v4d){0.0, 0.0, 0.0, 0.0};
+    static_assert(!PART || (MT <= 2 && !RAG && !RIDER && !HAS_SHIFT), "partial dots: one pass of the store loop, on the grid");
+    double pq_g = 0.0, pq_x = 0.0, pq_m = 0.0;     // PART: G, X, mu0 at this thread's (sample, column) of the store loop
 
     for (int ch = 0; ch < chunks_per_wg; ++ch) {
         const int cbase = (blockIdx.y * chunks_per_wg + ch) * CHW;          // block-uniform
@@ -170,6 +177,12 @@ __global__ __launch_bounds__(512) void k_panel_fast(int D, int nrows, const doub
                 m[s] = M[(size_t)(r < D ? r : D - 1) * ldm + j];
             }
         }
+        if constexpr (PART) {              // BEHIND the M stream: consumed only by the epilogue, nothing waits for them before
+            const int prow = r0 + ((tid >> 4) & (NR - 1)), pcol = blockIdx.x * 16 + (tid & 15);
+            pq_g = A[(size_t)prow * lda + pcol];
+            pq_x = px.sj_src[(size_t)prow * px.sj_len + pcol];     // X, ldx
+            pq_m = px.msl[pcol];                                   // mu0
+        }
         __builtin_amdgcn_sched_barrier(0);
         if (ch > 0) __syncthreads();       // previous chunk's MFMA reads of As are done
 #pragma unroll
@@ -219,6 +232,14 @@ __global__ __launch_bounds__(512) void k_panel_fast(int D, int nrows, const doub
             for (int ww = 0; ww < 8; ww += 2) s += red[(ww * NR + rr) * 17 + cc] + red[((ww + 1) * NR + rr) * 17 + cc];
             if (Out == nullptr) Pp[((size_t)blockIdx.y * nrows + row) * ncols + blockIdx.x * 16 + cc] = s;
             else Out[(size_t)row * ldo + blockIdx.x * 16 + cc] = s + (addvec ? addvec[blockIdx.x * 16 + cc] : 0.0);
+            if constexpr (PART) {          // (nrows == NR: the 16 lanes of a DPP row are the 16 columns of sample rr; whole waves run)
+                const double pg = row16_sum(pq_g * s);
+                if (cc == 0) px.sj_dst[((size_t)row * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x] = pg;      // Qg
+                if (blockIdx.y == 0) {
+                    const double pm = row16_sum((pq_m - pq_x) * pq_g);
+                    if (cc == 0) px.mfin[(size_t)row * gridDim.x + blockIdx.x] = pm;                             // Qm
+                }
+            }
         }
     }
     if (EXTRA && px.sj_src != nullptr) {            // side job: this workgroup's slice of a slab sum
@@ -447,13 +468,28 @@ __global__ __launch_bounds__(NT) void k_gsm_scalars_fast(int D, int B, int KC, c
 // =====================================================================================
 // RAG (round 5) = edge tiles (D % 32 != 0) and / or fewer than SB samples (B < SB): clamped re-reads, zero-staged sample rows,
 // guarded stores.  RAG = false is the round-4 code plus the run-time 1/B (the clamps cost 6 % on the grid shapes when unconditional).
-template <int SB, bool RAG>
-__global__ __launch_bounds__(512) void k_gsm_cov_sym(int D, int B, double invB, const double* __restrict__ rec, int ldrec,
+// FROM_SLABS (two-launch dense GSM update; B == SB in {16, 32}, D % 256 == 0, D <= 1024) = there are no records: the factor
+// tiles are formed HERE from the samples, the split-K slabs of G S0 and the partial dots that the product launch left beside
+// them (k_panel_fast<.., PART>), by the arithmetic of k_gsm_scalars_fast element for element.  Thread -> (sample b = unit >> 4,
+// column pair) is the same for the partial dots and for every staged tile, so the 16 lanes of a DPP row reduce sample b's
+// partials (fixed order: each lane its units ln, ln + 16, .. sequentially, then row16_sum) and hold beta_b, c_b for exactly the
+// units they stage: no LDS hand-off, no barrier, and nothing that waits on another workgroup.  Every workgroup repeats the
+// reduction (B x (KC + 1) x D / 16 doubles from L2) -- that is the price of dropping a launch.  Items, tile layout, MFMA chains
+// and the store path are those of FROM_SLABS = false, which is the code as it was, instruction for instruction.
+// Registers: S0, the partials and the column blocks I, J0, J1 are 29 16-B units per thread, 116 VGPRs if all were in flight at
+// once, and two workgroups per CU need <= 128 in all.  So the loads go out in TWO batches: S0, the partials (right behind S0:
+// vmcnt counts in issue order, they come back first) and blocks I, J0; then, once the partials are summed, block J1, whose
+// latency hides behind the scalar algebra and the staging of the other two blocks.
+// (FROM_SLABS holds 29 16-B units per thread in flight; it is compiled for four waves per SIMD -- at most 128 VGPRs -- because the
+// 16 late single-tile workgroups cost nothing only while they share a CU with a resident two-tile one; 2 is what
+// __launch_bounds__(512) alone implies, so the other instances are compiled as before.)
+template <int SB, bool RAG, bool FROM_SLABS = false>
+__global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(FROM_SLABS ? 4 : 2))) void k_gsm_cov_sym(int D, int B, double invB, const double* __restrict__ rec, int ldrec,
                                                      const double* __restrict__ mu0,
                                                      const double* __restrict__ S0, int lds0,
                                                      double* __restrict__ S, int lds,
                                                      double* __restrict__ mu_out, int dbg,
-                                                     unsigned long long* __restrict__ stamps) {
+                                                     unsigned long long* __restrict__ stamps, gsm_slab_src fs) {
 #define STAMP(k)                                                                          \
     do {                                                                                  \
         if (stamps && threadIdx.x == 0) stamps[(size_t)blockIdx.x * 8 + (k)] = __builtin_amdgcn_s_memrealtime(); \
@@ -520,34 +556,107 @@ __global__ __launch_bounds__(512) void k_gsm_cov_sym(int D, int B, double invB, 
     }
     __builtin_amdgcn_sched_barrier(0);           // keep the HBM loads of S0 ahead of the L2-resident staging loads
     v2d stg[UPT];
-#pragma unroll
-    for (int q = 0; q < UPT; ++q) {
-        const int g = q * 512 + tid;             // global unit over six tiles
-        const int tile = g / NU, u = g % NU;     // NU is a power of two
-        const int b = u >> 4, c2 = 2 * (u & 15);
-        // tile 0,1: I block (d, e); 2,3: J0 block; 4,5: J1 block (= J0 again when there is no second tile)
-        const int colbase = (tile < 2) ? I0 : (J0 + ((tile >= 4 && two) ? 32 : 0));
-        const int colc = (RAG && colbase + c2 >= D) ? D - 2 : colbase + c2;   // (a column beyond D only feeds outputs that are not stored)
-        // the 16 single-tile workgroups (they share a CU with a two-tile one) neither load nor stage a second column
-        // block, and their waves 4-7 issue no MFMA: 32 instead of 64 MFMAs per SIMD on those CUs (they were the
-        // kernel's 0.9 us tail: profiles/r02/timeline_cold_three_launch.txt).  tile is wave-uniform.
-        // (any B <= SB: sample rows b >= B do not exist -- the address is clamped and the unit is zeroed at staging time,
-        // so that no use of a loaded value sits between the loads)
-        stg[q] = (two || tile < 4) ? *reinterpret_cast<const v2d*>(rec + (size_t)((RAG && b >= B) ? B - 1 : b) * ldrec + (tile & 1) * D + colc)
-                                   : (v2d){0.0, 0.0};
-    }
     double dmu_part = 0.0;
-    if (diag && tid < 256) {                     // dmu tile for the new mean: column = tid & 31, samples tid>>5 + 8k
-        double dv[SB / 8];
+    v2d dmuI = {0.0, 0.0};                       // FROM_SLABS: dmu of this thread's unit of block I (the mean, diagonal workgroups)
+    if constexpr (FROM_SLABS) {
+        static_assert(!RAG && NPASS == 1 && 512 % NU == 0, "two-launch form: B == SB in {16, 32}, on the grid");
+        // SB = 16: the two halves of the workgroup hold the same units; half 0 stages the d tiles, half 1 the e tiles
+        const int u = tid & (NU - 1), b = u >> 4, ln = u & 15, c2 = 2 * ln;
+        const bool st_d = (NU == 512) || tid < NU, st_e = (NU == 512) || tid >= NU;
+        const int nqg = (fs.KC * fs.strips) >> 1, nqm = fs.strips >> 1;       // 16-B units of partials per sample (<= 128, <= 32)
+        // (workspace addresses as a uniform base + a 32-bit byte offset per lane -- all of it is < 2 MB here: one VGPR per address)
+        auto ld16 = [](const double* base, unsigned byte_off) {
+            return *reinterpret_cast<const v2d*>(reinterpret_cast<const char*>(base) + byte_off);
+        };
+        const unsigned qg0 = (unsigned)(b * nqg) * 16u, qm0 = (unsigned)(b * nqm) * 16u;
+        v2d qg[8], qm[2];
 #pragma unroll
-        for (int k = 0; k < SB / 8; ++k) {
-            const int b = (tid >> 5) + 8 * k, ci = I0 + (tid & 31);
-            dv[k] = rec[(size_t)((RAG && b >= B) ? B - 1 : b) * ldrec + 2 * D + ((RAG && ci >= D) ? D - 1 : ci)];
+        for (int k = 0; k < 8; ++k) qg[k] = ld16(fs.Qg, qg0 + 16u * (unsigned)(ln + 16 * k < nqg ? ln + 16 * k : nqg - 1));
+#pragma unroll
+        for (int k = 0; k < 2; ++k) qm[k] = ld16(fs.Qm, qm0 + 16u * (unsigned)(ln + 16 * k < nqm ? ln + 16 * k : nqm - 1));
+        const int col[3] = {I0 + c2, J0 + c2, J0 + 32 + c2};
+        const size_t slab = (size_t)B * D;
+        v2d xv[3], m0[3], sl[3][4];
+        auto load_block = [&](int cb) {          // X, mu0 and the slabs (beyond KC: a re-read of the last one, dropped below) of one column block
+            xv[cb] = *reinterpret_cast<const v2d*>(fs.X + (size_t)b * fs.ldx + col[cb]);
+            m0[cb] = ld16(mu0, 8u * (unsigned)col[cb]);
+#pragma unroll
+            for (int kc = 0; kc < 4; ++kc)
+                sl[cb][kc] = *reinterpret_cast<const v2d*>(fs.Pp + (size_t)(kc < fs.KC ? kc : fs.KC - 1) * slab + (size_t)b * D + col[cb]);
+        };
+        load_block(0);
+        load_block(1);
+        double gs = 0.0, ms = 0.0;               // this lane's share of sample b's partial dots, in unit order
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            const bool in = ln + 16 * k < nqg;
+            gs += in ? qg[k].x : 0.0;
+            gs += in ? qg[k].y : 0.0;
         }
 #pragma unroll
-        for (int k = 0; k < SB / 8; ++k) dmu_part += (!RAG || (tid >> 5) + 8 * k < B) ? dv[k] : 0.0;
+        for (int k = 0; k < 2; ++k) {
+            const bool in = ln + 16 * k < nqm;
+            ms += in ? qm[k].x : 0.0;
+            ms += in ? qm[k].y : 0.0;
+        }
+        // SECOND batch, behind the sums (the empty asm pins them in front of it): the second column block, which is staged last,
+        // takes the registers the partials held.  (block-uniform: the single-tile workgroups have no second column block)
+        asm volatile("" : "+v"(gs), "+v"(ms) : : "memory");
+        if (two) load_block(2);
+        // the scalars of sample b, by the expressions of k_gsm_scalars_fast
+        const double gSg = row16_sum(gs), mv = row16_sum(ms);
+        const double rho = 0.5 * sqrt(1.0 + 4.0 * (gSg + mv * mv)) - 0.5;
+        const double den = 1.0 + rho + mv;
+        const double beta = 1.0 / (1.0 + rho), c = (gSg - mv) / den;
+        if (stamps) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); STAMP(1); }
+#pragma unroll
+        for (int cb = 0; cb < 3; ++cb)
+            if (cb < 2 || two) {
+                v2d sg = {0.0, 0.0}, dd, dm, ee;
+#pragma unroll
+                for (int kc = 0; kc < 4; ++kc) {
+                    sg.x += (kc < fs.KC) ? sl[cb][kc].x : 0.0;
+                    sg.y += (kc < fs.KC) ? sl[cb][kc].y : 0.0;
+                }
+                dd.x = m0[cb].x - xv[cb].x;
+                dd.y = m0[cb].y - xv[cb].y;
+                dm.x = beta * ((sg.x - dd.x) - c * dd.x);
+                dm.y = beta * ((sg.y - dd.y) - c * dd.y);
+                ee.x = dd.x + dm.x;
+                ee.y = dd.y + dm.y;
+                if (st_d) *reinterpret_cast<v2d*>(smem + (2 * cb) * TILE + b * RS + c2) = dd;
+                if (st_e) *reinterpret_cast<v2d*>(smem + (2 * cb + 1) * TILE + b * RS + c2) = ee;
+                if (cb == 0) dmuI = dm;
+            }
+    } else {
+#pragma unroll
+        for (int q = 0; q < UPT; ++q) {
+            const int g = q * 512 + tid;             // global unit over six tiles
+            const int tile = g / NU, u = g % NU;     // NU is a power of two
+            const int b = u >> 4, c2 = 2 * (u & 15);
+            // tile 0,1: I block (d, e); 2,3: J0 block; 4,5: J1 block (= J0 again when there is no second tile)
+            const int colbase = (tile < 2) ? I0 : (J0 + ((tile >= 4 && two) ? 32 : 0));
+            const int colc = (RAG && colbase + c2 >= D) ? D - 2 : colbase + c2;   // (a column beyond D only feeds outputs that are not stored)
+            // the 16 single-tile workgroups (they share a CU with a two-tile one) neither load nor stage a second column
+            // block, and their waves 4-7 issue no MFMA: 32 instead of 64 MFMAs per SIMD on those CUs (they were the
+            // kernel's 0.9 us tail: profiles/r02/timeline_cold_three_launch.txt).  tile is wave-uniform.
+            // (any B <= SB: sample rows b >= B do not exist -- the address is clamped and the unit is zeroed at staging time,
+            // so that no use of a loaded value sits between the loads)
+            stg[q] = (two || tile < 4) ? *reinterpret_cast<const v2d*>(rec + (size_t)((RAG && b >= B) ? B - 1 : b) * ldrec + (tile & 1) * D + colc)
+                                       : (v2d){0.0, 0.0};
+        }
+        if (diag && tid < 256) {                     // dmu tile for the new mean: column = tid & 31, samples tid>>5 + 8k
+            double dv[SB / 8];
+#pragma unroll
+            for (int k = 0; k < SB / 8; ++k) {
+                const int b = (tid >> 5) + 8 * k, ci = I0 + (tid & 31);
+                dv[k] = rec[(size_t)((RAG && b >= B) ? B - 1 : b) * ldrec + 2 * D + ((RAG && ci >= D) ? D - 1 : ci)];
+            }
+#pragma unroll
+            for (int k = 0; k < SB / 8; ++k) dmu_part += (!RAG || (tid >> 5) + 8 * k < B) ? dv[k] : 0.0;
+        }
     }
-    if (stamps) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); STAMP(1); }
+    if (!FROM_SLABS && stamps) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); STAMP(1); }
 
     // ---- per pass of SBP samples: factor tiles -> LDS verbatim, then MFMA.  One 16x16 block per wave;
     // chain 0 = d-part, chain 1 = e-part; operands go to registers first so the chains issue back to back.
@@ -556,13 +665,15 @@ __global__ __launch_bounds__(512) void k_gsm_cov_sym(int D, int B, double invB, 
 #pragma unroll
     for (int pass = 0; pass < NPASS; ++pass) {
         if (pass > 0) __syncthreads();           // the previous pass's operand reads are done
+        if constexpr (!FROM_SLABS) {             // (FROM_SLABS staged its tiles above)
 #pragma unroll
-        for (int q = 0; q < UPT; ++q) {
-            const int g = q * 512 + tid;
-            const int tile = g / NU, u = g % NU;
-            const int b = u >> 4;
-            if (b / SBP == pass && (two || tile < 4))
-                *reinterpret_cast<v2d*>(smem + tile * TILE + (b % SBP) * RS + 2 * (u & 15)) = (!RAG || b < B) ? stg[q] : (v2d){0.0, 0.0};
+            for (int q = 0; q < UPT; ++q) {
+                const int g = q * 512 + tid;
+                const int tile = g / NU, u = g % NU;
+                const int b = u >> 4;
+                if (b / SBP == pass && (two || tile < 4))
+                    *reinterpret_cast<v2d*>(smem + tile * TILE + (b % SBP) * RS + 2 * (u & 15)) = (!RAG || b < B) ? stg[q] : (v2d){0.0, 0.0};
+            }
         }
         __syncthreads();
         if (pass == 0) STAMP(2);
@@ -626,12 +737,22 @@ __global__ __launch_bounds__(512) void k_gsm_cov_sym(int D, int B, double invB, 
     }
     if (diag) {
         __syncthreads();
-        if (tid < 256) smem[tid] = dmu_part;     // [8][32]
+        if constexpr (FROM_SLABS) {              // the dmu tile of block I [SB][32] through LDS: the two-level order of the record form
+            if (tid < NU) *reinterpret_cast<v2d*>(smem + (tid >> 4) * 32 + 2 * (tid & 15)) = dmuI;
+            __syncthreads();
+            if (tid < 256) {
+#pragma unroll
+                for (int k = 0; k < SB / 8; ++k) dmu_part += smem[((tid >> 5) + 8 * k) * 32 + (tid & 31)];
+                smem[SB * 32 + tid] = dmu_part;  // [8][32] behind the tile
+            }
+        } else {
+            if (tid < 256) smem[tid] = dmu_part; // [8][32]
+        }
         __syncthreads();
         if (tid < 32) {
             double s = 0.0;
 #pragma unroll
-            for (int q = 0; q < 8; ++q) s += smem[q * 32 + tid];
+            for (int q = 0; q < 8; ++q) s += smem[(FROM_SLABS ? SB * 32 : 0) + q * 32 + tid];
             if (!RAG || I0 + tid < D) mu_out[I0 + tid] = mu0[I0 + tid] + s * invB;
         }
     }
@@ -1056,6 +1177,23 @@ void gsmvi_launch_panel_fast(hipStream_t st, hipEvent_t* ev, int MT, dim3 grid, 
 #undef PF
 }
 
+// The product launch of the two-launch dense GSM update: slabs Pp[kc][B][D] of G S0 (grid (D / 16, kc, 1), chunks of 256 rows)
+// plus the partial dots Qg, Qm (the caller checked the gate: B in {16, 32} = one row block, D % 256 == 0, aligned operands).
+void gsmvi_launch_panel_fast_part(hipStream_t st, hipEvent_t* ev, dim3 grid, int D, int B, const double* G, int ldg,
+                                  const double* S0, int lds0, double* Pp, int chunks_per_wg, const double* X, int ldx,
+                                  const double* mu0, double* Qg, double* Qm) {
+    gsmvi_panel_extras px;                     // (PART's arguments ride in free members: gsmvi_ctx.h)
+    px.sj_src = X;
+    px.sj_len = ldx;
+    px.msl = mu0;
+    px.sj_dst = Qg;
+    px.mfin = Qm;
+#define PFQ(MTV) GSMVI_LAUNCH((k_panel_fast<MTV, false, 256, false, false, false, true>), grid, dim3(512), 0, st, ev, D, B, G, ldg, \
+                              nullptr, 1.0, S0, lds0, Pp, chunks_per_wg, D, nullptr, nullptr, 0, nullptr, px)
+    if (B == 16) PFQ(1); else PFQ(2);
+#undef PFQ
+}
+
 // column width of one staged chunk for a given MT (the ABI's chunk arithmetic must agree)
 int gsmvi_panel_fast_chunk(int MT) { return MT == 4 ? 128 : 256; }
 
@@ -1118,7 +1256,7 @@ bool gsmvi_launch_gsm_cov_sym(hipStream_t st, hipEvent_t* ev, int D, int B, cons
     const dim3 grid(n_items);
 #define CS(SBV, RG)                                                                                         \
     GSMVI_LAUNCH((k_gsm_cov_sym<SBV, RG>), grid, dim3(512), 0, st, ev, D, B, invB, rec, ldrec, mu0, S0, lds0, S, lds, mu_out, dbg, \
-                 stamps)
+                 stamps, gsm_slab_src())
     if (rag) {
         switch (SB) {
             case 16: CS(16, true); break;
@@ -1136,4 +1274,17 @@ bool gsmvi_launch_gsm_cov_sym(hipStream_t st, hipEvent_t* ev, int D, int B, cons
     }
 #undef CS
     return true;
+}
+
+// The covariance launch of the two-launch dense GSM update (the caller checked the gate: B in {16, 32}, D % 256 == 0, D <= 1024,
+// KC <= 4, even leading dimensions, 16-byte aligned bases).  Same grid as above.
+void gsmvi_launch_gsm_cov_sym_slabs(hipStream_t st, hipEvent_t* ev, int D, int B, const gsm_slab_src& fs, const double* mu0,
+                                    const double* S0, int lds0, double* S, int lds, double* mu_out) {
+    const dim3 grid(cov_sym_grid(D / 32));
+    const double invB = 1.0 / (double)B;
+#define CSS(SBV)                                                                                                          \
+    GSMVI_LAUNCH((k_gsm_cov_sym<SBV, false, true>), grid, dim3(512), 0, st, ev, D, B, invB, nullptr, 0, mu0, S0, lds0, S, lds, mu_out, \
+                 0, nullptr, fs)
+    if (B == 16) CSS(16); else CSS(32);
+#undef CSS
 }

@@ -586,7 +586,7 @@ class HipEngine:
                  "fupd_generic": 0x400, "lowrank_fast": 0x800, "lowrank_generic": 0x1000, "batched": 0x2000,
                  "batched_bam": 0x4000, "batched_kl": 0x8000, "batched_advi": 0x10000, "batched_target": 0x20000,
                  "batched_lbfgs": 0x40000, "batched_laplace": 0x80000, "batched_predict": 0x100000,
-                 "batched_psis": 0x200000, "batched_loo": 0x400000}
+                 "batched_psis": 0x200000, "batched_loo": 0x400000, "gsm_two_launch": 0x800000}
     PATH_GENERIC_MASK = 0x4 | 0x10 | 0x40 | 0x100 | 0x400 | 0x1000
 
     def last_path(self, reset=True):
@@ -611,7 +611,8 @@ class HipEngine:
         _lib.check("gsmvi_set_profiling", self.lib.gsmvi_set_profiling(self._ctx, int(bool(on))))
 
     def get_profile(self):
-        """Kernel durations (ms) of the last profiled update: panel, scalars, cov_update."""
+        """Kernel durations (ms) of the last profiled update: panel, scalars, cov_update (-1: that launch did not run, as
+        ``scalars`` in the two-launch form of the dense update)."""
         ms = (C.c_float * 3)()
         _lib.check("gsmvi_get_profile", self.lib.gsmvi_get_profile(self._ctx, ms, 3))
         return {"panel": ms[0], "scalars": ms[1], "cov_update": ms[2]}

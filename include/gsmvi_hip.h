@@ -94,7 +94,9 @@ int gsmvi_destroy(gsmvi_ctx* ctx);
  * "lowrank_kp" (64 = 64-row staging passes of BaM's low-rank update); round 6: "potrf_dag" (0 = one launch per block step),
  * "potrf_spin" (poll budget of a wait inside k_potrf_dag), "potrf_workers" (cap on its worker workgroups: tests of the ticket
  * order), "panel_w4_min_D"; "bam_batched_pad" (0 = the batched BaM kernel's LDS arrays at the unpadded row strides D, B; A/B
- * runs); diagnostics "timeline", "cov_dbg"
+ * runs); "gsm_two_launch" (default 1: the dense GSM update at B in {16, 32}, D % 256 == 0, D <= 1024 with even leading
+ * dimensions and 16-byte aligned arrays runs as two launches without the per-sample kernel; 0 = always three launches);
+ * diagnostics "timeline", "cov_dbg"
  * (see gsmvi_hip_debug.h). */
 int gsmvi_set_tuning(gsmvi_ctx* ctx, const char* name, int value);
 
@@ -105,6 +107,8 @@ int gsmvi_set_tuning(gsmvi_ctx* ctx, const char* name, int value);
  *   mu  (D)          new mean           S  (D x D, lds)  new covariance
  * mu = mu0 + mean_b dmu_b ; S = S0 + mean_b (d_b d_b^T - e_b e_b^T), d_b = mu0 - x_b, e_b = d_b + dmu_b.
  * Three kernels: panel product SG = G S0 (fp64 MFMA), per-sample scalars, rank-2B update (fp64 MFMA).
+ * For B in {16, 32}, D % 256 == 0, D <= 1024, even leading dimensions and 16-byte aligned arrays: TWO kernels -- the product
+ * also leaves partial dots, the update forms its factor tiles itself (knob "gsm_two_launch"; GSMVI_PATH_GSM_TWO_LAUNCH).
  * PRECONDITION: S0 is symmetric (a covariance).  For D % 32 == 0 and B in {16, 32, 64} the update kernel reads only
  * the UPPER triangle of S0 and mirrors the result, so S comes out exactly symmetric; for other shapes the generic
  * kernel reads all of S0.  A non-symmetric S0 therefore gives shape-dependent results that differ from
@@ -241,7 +245,8 @@ int gsmvi_gsm_factor_update_sharded_f64(gsmvi_ctx* ctx, void* stream, void* nccl
  * Profiling mode (used by bench.py for the roofline line): when on, the three kernels of the GSM
  * update are launched with dispatch-timestamp events; gsmvi_get_profile waits for the last call
  * and returns the kernel durations in milliseconds: ms[0] panel product, ms[1] per-sample
- * scalars, ms[2] covariance update (-1 where a stage did not run).
+ * scalars, ms[2] covariance update.  A slot is -1 when that launch did not run in the last profiled call: the two-launch
+ * form of the update (GSMVI_PATH_GSM_TWO_LAUNCH) has no per-sample launch, so ms[1] = -1 there -- never a stale time.
  */
 int gsmvi_set_profiling(gsmvi_ctx* ctx, int on);
 int gsmvi_get_profile(gsmvi_ctx* ctx, float* ms, int n);
@@ -278,6 +283,7 @@ int gsmvi_get_profile(gsmvi_ctx* ctx, float* ms, int n);
 #define GSMVI_PATH_BATCHED_PREDICT 0x100000u /* k_glm_predict_batched: the batched GLM posterior predictive             */
 #define GSMVI_PATH_BATCHED_PSIS 0x200000u /* k_psis_batched: the batched Pareto-smoothed importance diagnostic            */
 #define GSMVI_PATH_BATCHED_LOO 0x400000u /* k_psis_loo_batched: the batched PSIS leave-one-out                                */
+#define GSMVI_PATH_GSM_TWO_LAUNCH 0x800000u /* the dense GSM update ran as two launches (no k_gsm_scalars_fast, no records)          */
 #define GSMVI_PATH_GENERIC_MASK (0x0004u | 0x0010u | 0x0040u | 0x0100u | 0x0400u | 0x1000u)
 int gsmvi_last_path(gsmvi_ctx* ctx, unsigned* bits, int reset);
 
