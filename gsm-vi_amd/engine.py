@@ -586,7 +586,8 @@ class HipEngine:
                  "fupd_generic": 0x400, "lowrank_fast": 0x800, "lowrank_generic": 0x1000, "batched": 0x2000,
                  "batched_bam": 0x4000, "batched_kl": 0x8000, "batched_advi": 0x10000, "batched_target": 0x20000,
                  "batched_lbfgs": 0x40000, "batched_laplace": 0x80000, "batched_predict": 0x100000,
-                 "batched_psis": 0x200000, "batched_loo": 0x400000, "gsm_two_launch": 0x800000}
+                 "batched_psis": 0x200000, "batched_loo": 0x400000, "gsm_two_launch": 0x800000,
+                 "batched_softmax": 0x1000000}
     PATH_GENERIC_MASK = 0x4 | 0x10 | 0x40 | 0x100 | 0x400 | 0x1000
 
     def last_path(self, reset=True):
@@ -899,6 +900,38 @@ class HipEngine:
             self._ints(counts, K, "counts"), r, rp, self._packed(X, (K, nc, D), "X"), self._dp(G, (K, nc, D), "out"),
             self._dp(lp, (K, nc), "lp_out")))
         return G if want == "g" else lp if want == "lp" else (G, lp)
+
+    # ---- batched softmax target: K multinomial logit regressions of one (N, C, P) (csrc/gsmvi_softmax_batched.hip) ----------
+    def softmax_batched(self, X, A, labels, num_classes, counts=None, prior_prec=1.0, out=None, lp_out=None, want="g"):
+        """Score and / or log-density of K Bayesian multinomial logit regressions at the rows of X (K, nc, D), D = (C - 1) P,
+        class-major, class C - 1 the reference class, one launch [examples/example_gsm.py:34-35 for this model]: A (K, N, P),
+        ``labels`` (K, N) device int32 in 0 .. C - 1, ``num_classes`` = C, ``counts`` None or K device int32 valid rows,
+        ``prior_prec`` a number or a (K,) device tensor.  ``want`` = "g" -> G (K, nc, D) (no logarithm is evaluated), "lp" -> the
+        values (K, nc), "both" -> (G, lp)."""
+        self._check_want(want, "g", "lp")
+        X = X.contiguous()
+        K, nc, D = X.shape
+        N, P, Cc = A.shape[1], A.shape[2], int(num_classes)
+        if Cc < 2 or (Cc - 1) * P != D:
+            raise ValueError(f"X: expected (num_classes - 1) P = {(Cc - 1) * P} columns, got {D}")
+        assert labels.is_cuda and labels.dtype == torch.int32 and labels.is_contiguous() and tuple(labels.shape) == (K, N), \
+            f"labels: expected a contiguous int32 CUDA tensor of shape {(K, N)}"
+        self._ensure(max(self._max_D, 1), max(self._max_B, 1))
+        G = lp = None
+        if want != "lp":
+            G = self.empty(K, nc, D) if out is None else out
+        if want != "g":
+            lp = self.empty(K, nc) if lp_out is None else lp_out
+        r, rp = self._reg_arg(prior_prec, K)
+        _lib.check("gsmvi_softmax_batched_f64", self.lib.gsmvi_softmax_batched_f64(
+            self._ctx, self._stream(), K, Cc, P, nc, N, self._packed(A, (K, N, P), "A"), C.c_void_p(labels.data_ptr()),
+            self._ints(counts, K, "counts"), r, rp, self._packed(X, (K, nc, D), "X"), self._dp(G, (K, nc, D), "out"),
+            self._dp(lp, (K, nc), "lp_out")))
+        return G if want == "g" else lp if want == "lp" else (G, lp)
+
+    def batched_labels(self, values):
+        """(K, N) integer labels as a device int32 tensor"""
+        return torch.as_tensor(np.ascontiguousarray(values, dtype=np.int32), device=self.device)
 
     # ---- batched GLM targets: the same launch for a family of links (csrc/gsmvi_logistic_batched.hip) -----------------------
     GLM_FAMILIES = {"logistic": 0, "poisson": 1, "probit": 2, "gaussian": 3}     # GSMVI_GLM_* of include/gsmvi_hip.h

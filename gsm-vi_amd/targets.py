@@ -8,7 +8,14 @@ kernel.  ``device_score`` marks a user callable as taking/returning CUDA tensors
 ``BatchedLogisticTarget`` is the first non-Gaussian device target of the batched fits: K Bayesian logistic
 regressions, score and log-density from one HIP launch.  ``BatchedGLMTarget`` is the same launch for a family of generalised
 linear models: Poisson, probit, Gaussian and logistic, with offsets; the logistic class is its ``family="logistic"`` case.  They have ``predict``: the posterior predictive of the
-fitted Gaussians on new rows (``GLMPrediction``), one HIP launch.
+fitted Gaussians on new rows (``GLMPrediction``), one HIP launch.  ``BatchedSoftmaxTarget`` is the multiclass response: K
+multinomial logit regressions (C classes, C - 1 linear predictors per row), a launch and a class of its own.
+
+    target                    response                        entry point                    laplace / predict / loo
+    BatchedGaussianTarget     (a Gaussian density)            gsmvi_gaussian_score_batched_f64   no
+    BatchedLogisticTarget     y in [0, 1]                     gsmvi_logistic_batched_f64         yes
+    BatchedGLMTarget          poisson, probit, gaussian, ...  gsmvi_glm_batched_f64              yes
+    BatchedSoftmaxTarget      integer labels in 0 .. C - 1    gsmvi_softmax_batched_f64          no (TypeError)
 """
 from dataclasses import dataclass
 from typing import Any
@@ -375,3 +382,92 @@ class BatchedLogisticTarget(BatchedGLMTarget):
 
     def _call(self, x, **kw):           # the logistic entry point of its own: the model is the GLM's with no offset and tau = 1
         return self.engine.logistic_batched(x, self.A, self.y, self.counts, self.prior_precision, **kw)
+
+
+def _check_labels(y, C, live):
+    """the labels as a host int32 array: an integer dtype or floats with integral values, in 0 .. C - 1 in the valid rows (the
+    rows beyond are stored as 0), else ValueError naming the problems"""
+    yh = np.asarray(_host_array(y))
+    if yh.dtype == np.bool_ or not (np.issubdtype(yh.dtype, np.integer) or np.issubdtype(yh.dtype, np.floating)):
+        raise ValueError(f"y: expected integer labels (an integer dtype, or floats with integral values), got dtype {yh.dtype}")
+    with np.errstate(invalid="ignore"):
+        good = (yh >= 0) & (yh <= C - 1)                              # (a NaN fails both comparisons)
+        if np.issubdtype(yh.dtype, np.floating):
+            good &= yh == np.floor(yh)
+    bad = live & ~good
+    if bad.any():
+        raise ValueError(f"y: labels that are not integers in 0 .. num_classes - 1 = {C - 1} in the valid rows of problems "
+                         f"{np.flatnonzero(bad.any(1)).tolist()}")
+    return np.where(live & good, yh, 0).astype(np.int32)
+
+
+class BatchedSoftmaxTarget:
+    """K Bayesian multinomial logit (softmax) regressions with their own data sets, for ``GSMBatch``, ``BaMBatch``,
+    ``ADVIBatch``, ``BatchedKLMonitor``, ``lbfgs_init_batched`` and ``psis_batched``.  Problem k has the design matrix A[k]
+    (N, P), integer labels y[k] (N,) in 0 .. C - 1 (``num_classes`` = C >= 2; no soft labels), ``counts[k]`` <= N valid rows
+    (None: all N; the rows beyond are ignored whatever they hold) and the prior N(0, I / lam_k), ``prior_precision`` = lam a float
+    or K values, 0 = flat.  Class C - 1 is the reference class with zero coefficients; the parameter is x in R^D, D = (C - 1) P
+    <= 64, class-major: x[c P + j] = W_cj.  With eta_nc = a_n . w_c for c < C - 1 and eta_n,C-1 = 0:
+
+        m_n = max_c eta_nc,   s_n = sum_c exp(eta_nc - m_n)
+        lp_k(x)      = sum_n [ eta_n,y_n - m_n - log s_n ] - lam_k |x|^2 / 2            (unnormalised log posterior)
+        grad lp_k(x) = sum_n ( [y_n = c] - exp(eta_nc - m_n) / s_n ) a_nj - lam_k x_cj   (c < C - 1)
+
+    evaluated by gsmvi_softmax_batched_f64: what examples/example_gsm.py:34-35 gets from a model's log_prob and jit(grad(...)).
+    numpy arrays or tensors in; everything is kept on the device as float64 / int32.  Arguments are validated on the host before
+    any device work (ValueError naming the argument and the problems).  It is not a ``BatchedGLMTarget``: there is no offset, and
+    ``laplace_init_batched``, ``predict`` and ``psis_loo_batched`` do not take it (TypeError).
+
+    ``lp_g(x, out=None)``: (K, B, D) -> (K, B, D) scores, ``device_native`` and ``graph_safe`` (one capturable launch, no
+    allocation with ``out``).  ``lp(x)``: (K, rows, D) -> (K, rows) values; a device tensor or numpy.  ``lp_and_score(x)``:
+    (scores, values) from one launch.  Attributes ``K, N, D, P, C``."""
+
+    def __init__(self, A, y, num_classes, prior_precision=1.0, counts=None, engine=None):
+        if isinstance(num_classes, bool) or not isinstance(num_classes, (int, np.integer)) or num_classes < 2:
+            raise ValueError(f"num_classes: expected an integer >= 2, got {num_classes!r}")
+        C = int(num_classes)
+        sa = _shape(A)
+        if len(sa) != 3 or min(sa) < 1:
+            raise ValueError(f"A: expected shape (K, N, P) with K, N, P >= 1, got {sa}")
+        K, N, P = sa
+        if (C - 1) * P > 64:
+            raise ValueError(f"num_classes: D = (num_classes - 1) P = {(C - 1) * P} is outside 1 <= D <= 64 (P = {P})")
+        if _shape(y) != (K, N):
+            raise ValueError(f"y: expected shape (K, N) = {(K, N)}, got {_shape(y)}")
+        cnt = _check_counts(counts, K, N)
+        yh = _check_labels(y, C, _live_rows(cnt, N))
+        lam = _check_per_problem(prior_precision, "prior_precision", K)
+        self.engine = engine if engine is not None else get_engine()
+        eng = self.engine
+        self.K, self.N, self.P, self.C, self.D = K, N, P, C, (C - 1) * P
+        self.A = eng.asarray(A.contiguous() if isinstance(A, torch.Tensor) else A)
+        self.y = eng.batched_labels(yh)
+        self.counts = eng.batched_counts(cnt) if cnt is not None else None
+        self.prior_precision = float(lam) if lam.shape == () else eng.batched_regs(lam)
+
+        def lp_g(x, out=None):
+            return self._call(x, out=out, want="g")
+        lp_g.device_native = True
+        lp_g.graph_safe = True          # one capturable kernel launch, no allocation when `out` is given, no host work
+        self.lp_g = lp_g
+
+    def _call(self, x, **kw):
+        return self.engine.softmax_batched(x, self.A, self.y, self.C, counts=self.counts, prior_prec=self.prior_precision, **kw)
+
+    def lp(self, x):
+        """(K, rows) values lp_k(x_kr) at the rows of x (K, rows, D), a device tensor or numpy; one launch"""
+        return self._call(self.engine.asarray(x), want="lp")
+
+    def lp_and_score(self, x):
+        """(scores (K, rows, D), values (K, rows)) from one launch"""
+        return self._call(self.engine.asarray(x), want="both")
+
+    def predict(self, *args, **kw):
+        """not built yet for this target: TypeError (the predictive is ``BatchedGLMTarget.predict``'s, one linear predictor per row)"""
+        raise TypeError("BatchedSoftmaxTarget.predict: the posterior predictive takes a BatchedGLMTarget or a BatchedLogisticTarget; "
+                        "the softmax target has none yet")
+
+    def loo(self, mean, cov, keys, **kw):
+        """``psis_loo_batched(self, ...)``, which takes the GLM targets only: TypeError"""
+        from .diagnostics import psis_loo_batched
+        return psis_loo_batched(self, mean, cov, keys, **kw)

@@ -22,6 +22,7 @@
  *   advi.py:80-86 initial (loc, scales), :23-27 scales -> covariance    ->  gsmvi_advi_init_batched_f64, gsmvi_advi_cov_batched_f64
  *   examples/example_gsm.py:34-35 a model's log_prob and jit(grad(.)) of it, K logistic regressions -> gsmvi_logistic_batched_f64
  *   examples/example_gsm.py:34-35 the same for K Poisson, probit or Gaussian regressions with offsets -> gsmvi_glm_batched_f64
+ *   examples/example_gsm.py:34-35 the same for K multinomial logit (softmax) regressions of C classes -> gsmvi_softmax_batched_f64
  *   initializers.py:5-17 lbfgs_init (maximiser of lp, dense inverse-Hessian estimate), K problems -> gsmvi_lbfgs_step_batched_f64, gsmvi_lbfgs_hess_inv_batched_f64
  *   initializers.py:5-17 the same role by Newton rounds on the GLMs of examples/example_gsm.py:34-35 (no reference twin) -> gsmvi_glm_hessian_batched_f64, gsmvi_laplace_step_batched_f64
  *   examples/example_gsm.py:34-35 the use of the fit: predictions and the held-out score of K fitted GLMs (no reference twin) -> gsmvi_glm_predict_batched_f64
@@ -284,6 +285,7 @@ int gsmvi_get_profile(gsmvi_ctx* ctx, float* ms, int n);
 #define GSMVI_PATH_BATCHED_PSIS 0x200000u /* k_psis_batched: the batched Pareto-smoothed importance diagnostic            */
 #define GSMVI_PATH_BATCHED_LOO 0x400000u /* k_psis_loo_batched: the batched PSIS leave-one-out                                */
 #define GSMVI_PATH_GSM_TWO_LAUNCH 0x800000u /* the dense GSM update ran as two launches (no k_gsm_scalars_fast, no records)          */
+#define GSMVI_PATH_BATCHED_SOFTMAX 0x1000000u /* k_softmax_batched: the batched multinomial logit target's entry point            */
 #define GSMVI_PATH_GENERIC_MASK (0x0004u | 0x0010u | 0x0040u | 0x0100u | 0x0400u | 0x1000u)
 int gsmvi_last_path(gsmvi_ctx* ctx, unsigned* bits, int reset);
 
@@ -507,6 +509,35 @@ int gsmvi_glm_batched_f64(gsmvi_ctx* ctx, void* stream, int64_t K, int D, int nc
                           const double* y, const double* offset, const int* counts_dev, double noise_prec,
                           const double* noise_prec_dev, double prior_prec, const double* prior_prec_dev, const double* X, double* G,
                           double* lp);
+
+/*
+ * Batched softmax target: the log-density and the score of K Bayesian multinomial logit regressions of one (N, C, P) at nc points
+ * each, one launch.  examples/example_gsm.py:34-35, the model's log_prob and lp_g = jit(grad(...)) of it, for a response with C
+ * classes -> gsmvi_softmax_batched_f64.  Problem k has the design matrix A_k (N rows a_n of P features), integer labels y_kn in
+ * 0 .. C - 1, n_k valid rows and prior precision lam_k >= 0 (prior N(0, I / lam_k); 0 = flat).  Class C - 1 is the reference class
+ * with zero coefficients; the parameter is x in R^D, D = (C - 1) P, laid out class-major: x[c P + j] = W_cj.  At a row x of X_k:
+ *   eta_nc = a_n . w_c  (c < C-1),   eta_n,C-1 = 0
+ *   m_n    = max_c eta_nc            (over all C values, the 0 included)
+ *   s_n    = sum_{c=0..C-1} exp(eta_nc - m_n)     (class order; the reference class last)
+ *   lp(x)  = sum_{n<n_k} [ eta_n,y_n - m_n - log s_n ] - lam_k |x|^2 / 2
+ *   g_cj   = sum_{n<n_k} ( [y_n = c] - exp(eta_nc - m_n)/s_n ) a_nj - lam_k x_cj      (c < C-1)
+ * A (K x N x P) doubles, labels (K x N) ints, X, G (K x nc x D), lp (K x nc), packed, in device memory.  C >= 2, P >= 1,
+ * 1 <= D <= 64 and K with the grid limits of the batched GSM above; nc >= 1 and N >= 1 are not bounded by LDS (both are walked in
+ * tiles; the tile of X rows shrinks as C grows).  counts_dev: NULL = N valid rows everywhere, else K ints on the device, each
+ * clamped to 0 .. N in the kernel; rows n >= n_k are never loaded, whatever they hold.  prior_prec_dev: NULL = the scalar prior_prec
+ * (finite, >= 0) for every problem, else K values.  At least one of G, lp is given; G alone evaluates no logarithm, lp alone makes
+ * no second pass over a tile.  Every output row sums over n in the order 0 .. n_k - 1 in one thread and depends on A_k, y_k, n_k,
+ * lam_k and its own row of X only: the same bits for any K, nc, tiling and neighbours.  A row of X with a non-finite entry, or for
+ * which some valid eta is not finite, gets NaN outputs and no other row is touched.  The maximum is subtracted, so nothing else can
+ * overflow.  A label is used in comparisons and selects only, never as an index: a label outside 0 .. C - 1 reads nothing out of
+ * bounds (its row counts as one whose class has eta = 0 and no residual indicator; the ranges are the caller's to keep).  Shapes,
+ * NULL arrays, the scalar prior and overlaps (G and lp are the written arrays) are checked before the context is looked at (then a
+ * NULL ctx); every failure returns GSMVI_ERR_BAD_ARG before anything is enqueued.  Inputs are only read; no context workspace is
+ * used; one capturable launch.  Sets GSMVI_PATH_BATCHED_SOFTMAX.
+ */
+int gsmvi_softmax_batched_f64(gsmvi_ctx* ctx, void* stream, int64_t K, int C, int P, int nc, int64_t N, const double* A,
+                              const int* labels, const int* counts_dev, double prior_prec, const double* prior_prec_dev,
+                              const double* X, double* G, double* lp);
 
 /*
  * Batched L-BFGS initialiser (gsmvi/initializers.py:5-17 for K problems of one D): the minimiser of phi_k = -lp_k as the mean and
