@@ -47,9 +47,9 @@ bool gsmvi_launch_gsm_cov_sym(hipStream_t st, hipEvent_t* ev, int D, int B, cons
                               int dbg, unsigned long long* stamps, int num_cu);
 void gsmvi_launch_panel_fast_part(hipStream_t st, hipEvent_t* ev, dim3 grid, int D, int B, const double* G, int ldg,
                                   const double* S0, int lds0, double* Pp, int chunks_per_wg, const double* X, int ldx,
-                                  const double* mu0, double* Qg, double* Qm);
+                                  const double* mu0, double* Qg, double* Qm, int chw);
 void gsmvi_launch_gsm_cov_sym_slabs(hipStream_t st, hipEvent_t* ev, int D, int B, const struct gsm_slab_src& fs, const double* mu0,
-                                    const double* S0, int lds0, double* S, int lds, double* mu_out);
+                                    const double* S0, int lds0, double* S, int lds, double* mu_out, int kct);
 int gsmvi_panel_fast_chunk(int MT);
 int gsmvi_potrf_impl(struct gsmvi_ctx* ctx, hipStream_t st, int D, const double* S, int lds, double* R, int ldr,
                      int* info_dev);
@@ -600,9 +600,12 @@ static int gsm_records(gsmvi_ctx* ctx, hipStream_t hs, int D, int B, int kc, con
 // slabs, the covariance launch forms its factor tiles from samples, slabs and partials (gsmvi_fast.hip: k_panel_fast<.., PART>,
 // k_gsm_cov_sym<.., FROM_SLABS>).  One gated shape family; *cpw_out, *kc_out = the product's split (the arithmetic of
 // gsmvi_panel_product_nc).  The diagnostics that stamp or ablate the three kernels keep the three launches.
+// *chw_out = rows per chunk of the product.  Round 8: D = 1024 (four 256-row chunks) with no explicit "panel_kc" runs as TWO
+// slabs of one 512-row chunk each -- half the slabs and half the Qg partials that every covariance workgroup re-reads; an
+// explicit "panel_kc" keeps 256-row chunks with that split (panel_kc=4: the round-7 route, for A/B runs in one process).
 static bool gsm_two_launch_gate(const gsmvi_ctx* ctx, int D, int B, const double* X, int ldx, const double* G, int ldg,
                                 const double* mu0, const double* S0, int lds0, const double* S, int lds, int* cpw_out,
-                                int* kc_out) {
+                                int* kc_out, int* chw_out) {
     if (!ctx->tune_gsm_two_launch || ctx->tune_no_fast || ctx->tune_timeline || ctx->tune_cov_dbg) return false;
     if (B != 16 && B != 32) return false;
     if (D % 256 != 0 || D > 1024) return false;
@@ -617,10 +620,16 @@ static bool gsm_two_launch_gate(const gsmvi_ctx* ctx, int D, int B, const double
     if (kc > 4 || kc * cpw != nchunks) return false;           // <= 4 slabs of whole chunks
     *cpw_out = cpw;
     *kc_out = kc;
+    *chw_out = 256;
+    if (nchunks == 4 && ctx->tune_panel_kc <= 0) {
+        *cpw_out = 1;
+        *kc_out = 2;
+        *chw_out = 512;
+    }
     return true;
 }
 
-static int gsm_two_launch(gsmvi_ctx* ctx, hipStream_t hs, int D, int B, int cpw, int kc, const double* X, int ldx,
+static int gsm_two_launch(gsmvi_ctx* ctx, hipStream_t hs, int D, int B, int cpw, int kc, int chw, const double* X, int ldx,
                           const double* G, int ldg, const double* mu0, const double* S0, int lds0, double* mu, double* S,
                           int lds) {
     const int strips = D / 16;
@@ -630,8 +639,9 @@ static int gsm_two_launch(gsmvi_ctx* ctx, hipStream_t hs, int D, int B, int cpw,
     ctx->px_used = 1;
     hipEvent_t* ev0 = ctx->stage_events(0);
     ctx->ev_valid[1] = 0;                                       // no per-sample launch: gsmvi_get_profile reports -1 for it
-    gsmvi_launch_panel_fast_part(hs, ev0, dim3(strips, kc, 1), D, B, G, ldg, S0, lds0, ctx->pp, cpw, X, ldx, mu0, Qg, Qm);
-    ctx->path |= GSMVI_PATH_PANEL_FAST;
+    // (512-row chunks: one workgroup per (strip, slab, 16 samples) -- the launcher's comment in gsmvi_fast.hip)
+    gsmvi_launch_panel_fast_part(hs, ev0, dim3(strips, kc, chw == 512 ? B / 16 : 1), D, B, G, ldg, S0, lds0, ctx->pp, cpw, X, ldx, mu0, Qg, Qm, chw);
+    ctx->path |= GSMVI_PATH_PANEL_FAST | (chw == 512 ? GSMVI_PATH_PANEL_CHUNK512 : 0u);
     int st = check_launch("k_panel_fast(partials)");
     if (st != GSMVI_OK) return st;
     gsm_slab_src fs;
@@ -642,7 +652,7 @@ static int gsm_two_launch(gsmvi_ctx* ctx, hipStream_t hs, int D, int B, int cpw,
     fs.Qm = Qm;
     fs.KC = kc;
     fs.strips = strips;
-    gsmvi_launch_gsm_cov_sym_slabs(hs, ctx->stage_events(2), D, B, fs, mu0, S0, lds0, S, lds, mu);
+    gsmvi_launch_gsm_cov_sym_slabs(hs, ctx->stage_events(2), D, B, fs, mu0, S0, lds0, S, lds, mu, chw == 512 ? 2 : 4);
     ctx->path |= GSMVI_PATH_COV_SYM | GSMVI_PATH_GSM_TWO_LAUNCH;
     return check_launch("k_gsm_cov_sym(slabs)");
 }
@@ -656,9 +666,9 @@ int gsmvi_gsm_update_f64(gsmvi_ctx* ctx, void* stream, int D, int B, const doubl
     BAD_ARG(S == S0 || mu == mu0, "outputs must not alias inputs");
     hipStream_t hs = reinterpret_cast<hipStream_t>(stream);
     const int ldrec = 3 * D + (D & 1);            // even stride keeps every record 16-byte aligned
-    int cpw2 = 0, kc2 = 0;
-    if (gsm_two_launch_gate(ctx, D, B, X, ldx, G, ldg, mu0, S0, lds0, S, lds, &cpw2, &kc2))
-        return gsm_two_launch(ctx, hs, D, B, cpw2, kc2, X, ldx, G, ldg, mu0, S0, lds0, mu, S, lds);
+    int cpw2 = 0, kc2 = 0, chw2 = 0;
+    if (gsm_two_launch_gate(ctx, D, B, X, ldx, G, ldg, mu0, S0, lds0, S, lds, &cpw2, &kc2, &chw2))
+        return gsm_two_launch(ctx, hs, D, B, cpw2, kc2, chw2, X, ldx, G, ldg, mu0, S0, lds0, mu, S, lds);
     st = gsm_local_stage(ctx, hs, D, B, X, ldx, G, ldg, mu0, S0, lds0, ctx->sg, ldrec);
     if (st != GSMVI_OK) return st;
     return gsm_apply(ctx, hs, D, B, ctx->sg, ldrec, mu0, S0, lds0, mu, S, lds);

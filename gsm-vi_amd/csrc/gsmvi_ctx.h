@@ -42,11 +42,14 @@ struct gsmvi_panel_extras {
     // the offsets of the hidden arguments behind it -- is byte for byte what it was:  sj_src = X, sj_len = ldx, msl = mu0,
     // sj_dst = Qg, mfin = Qm.  Beside its slab every workgroup leaves Qg[b][slab * strips + strip] = the sum over the strip's 16
     // columns of G[b][col] slab[b][col], and the workgroups of slab 0 Qm[b][strip] = the sum of (mu0[col] - X[b][col]) G[b][col]
-    // (strips = gridDim.x).  Set by gsmvi_launch_panel_fast_part only.
+    // (strips = gridDim.x; slabs = gridDim.y: 2 with 512-row chunks at D = 1024, where gridDim.z = B / 16 sample blocks of one
+    // 16-row tile each write their own rows of both).  Set by gsmvi_launch_panel_fast_part only.
 };
 
 // Where k_gsm_cov_sym<.., FROM_SLABS> takes its factor tiles from (the two-launch dense GSM update): the samples, the split-K
 // slabs of G S0 and the partial dots the product launch left beside them (layout: the last comment of gsmvi_panel_extras).
+// Qm = Qg + B * KC * strips in the record area: the offset follows the split (KC = 2 on the 512-row route of D = 1024), and
+// every call writes all of Qg and Qm that its covariance launch reads.
 struct gsm_slab_src {
     const double* X = nullptr;
     const double* Pp = nullptr;

@@ -45,7 +45,7 @@
 // RAG (round 5) = the clamped form for D % 64 != 0 or ncols % 16 != 0; RAG = false is the round-4 code, instruction for
 // instruction (the clamps and the straddling-wave branch cost 6 - 11 % on the grid shapes when they were unconditional:
 // scripts/cov_ab_rounds.py).
-// PART (two-launch dense GSM update; A = G, M = S0, one row block of NR = nrows samples, on the grid) = the launch also leaves
+// PART (two-launch dense GSM update; A = G, M = S0, row blocks of NR samples with nrows % NR == 0, on the grid) = the launch also leaves
 // PARTIAL DOTS beside its slab (arguments: the last comment of gsmvi_panel_extras): per (sample, strip of 16 columns, slab) the sum of G slab over the
 // strip, and from the workgroups of slab 0 the sum of (mu0 - x) G.  The covariance kernel behind this launch re-reduces them in
 // every workgroup (k_gsm_cov_sym<.., FROM_SLABS>), so the per-sample launch between the two and its record round trip are gone;
@@ -232,7 +232,7 @@ __global__ __launch_bounds__(512) void k_panel_fast(int D, int nrows, const doub
             for (int ww = 0; ww < 8; ww += 2) s += red[(ww * NR + rr) * 17 + cc] + red[((ww + 1) * NR + rr) * 17 + cc];
             if (Out == nullptr) Pp[((size_t)blockIdx.y * nrows + row) * ncols + blockIdx.x * 16 + cc] = s;
             else Out[(size_t)row * ldo + blockIdx.x * 16 + cc] = s + (addvec ? addvec[blockIdx.x * 16 + cc] : 0.0);
-            if constexpr (PART) {          // (nrows == NR: the 16 lanes of a DPP row are the 16 columns of sample rr; whole waves run)
+            if constexpr (PART) {          // (nrows % NR == 0: the 16 lanes of a DPP row are the 16 columns of sample row; whole waves run)
                 const double pg = row16_sum(pq_g * s);
                 if (cc == 0) px.sj_dst[((size_t)row * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x] = pg;      // Qg
                 if (blockIdx.y == 0) {
@@ -483,7 +483,11 @@ __global__ __launch_bounds__(NT) void k_gsm_scalars_fast(int D, int B, int KC, c
 // (FROM_SLABS holds 29 16-B units per thread in flight; it is compiled for four waves per SIMD -- at most 128 VGPRs -- because the
 // 16 late single-tile workgroups cost nothing only while they share a CU with a resident two-tile one; 2 is what
 // __launch_bounds__(512) alone implies, so the other instances are compiled as before.)
-template <int SB, bool RAG, bool FROM_SLABS = false>
+// KCT (round 8) = how many slabs the FROM_SLABS form is compiled for.  4 is the form above (any KC <= 4 at run time, the absent
+// slabs and partials are clamped re-reads).  2 serves the 512-row split of D = 1024 (k_panel_fast<.., 512, .., PART>: exactly two
+// slabs, 128 Qg and 64 Qm partials per sample): 4 + 2 units of partials and two slab units per column block are 20 units per
+// thread, so ALL loads go out in one batch and both slabs exist.  Same unit order in the sums, slabs added as p0 + p1.
+template <int SB, bool RAG, bool FROM_SLABS = false, int KCT = 4>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(FROM_SLABS ? 4 : 2))) void k_gsm_cov_sym(int D, int B, double invB, const double* __restrict__ rec, int ldrec,
                                                      const double* __restrict__ mu0,
                                                      const double* __restrict__ S0, int lds0,
@@ -560,6 +564,8 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(FROM_SLABS 
     v2d dmuI = {0.0, 0.0};                       // FROM_SLABS: dmu of this thread's unit of block I (the mean, diagonal workgroups)
     if constexpr (FROM_SLABS) {
         static_assert(!RAG && NPASS == 1 && 512 % NU == 0, "two-launch form: B == SB in {16, 32}, on the grid");
+        static_assert(KCT == 2 || KCT == 4, "slab count of the two-launch form");
+        constexpr int NQG = 2 * KCT;             // 16-B units of Qg per lane: KCT * strips / 2 <= 16 * NQG at strips <= 64
         // SB = 16: the two halves of the workgroup hold the same units; half 0 stages the d tiles, half 1 the e tiles
         const int u = tid & (NU - 1), b = u >> 4, ln = u & 15, c2 = 2 * ln;
         const bool st_d = (NU == 512) || tid < NU, st_e = (NU == 512) || tid >= NU;
@@ -569,26 +575,29 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(FROM_SLABS 
             return *reinterpret_cast<const v2d*>(reinterpret_cast<const char*>(base) + byte_off);
         };
         const unsigned qg0 = (unsigned)(b * nqg) * 16u, qm0 = (unsigned)(b * nqm) * 16u;
-        v2d qg[8], qm[2];
+        v2d qg[NQG], qm[2];
 #pragma unroll
-        for (int k = 0; k < 8; ++k) qg[k] = ld16(fs.Qg, qg0 + 16u * (unsigned)(ln + 16 * k < nqg ? ln + 16 * k : nqg - 1));
+        for (int k = 0; k < NQG; ++k) qg[k] = ld16(fs.Qg, qg0 + 16u * (unsigned)(ln + 16 * k < nqg ? ln + 16 * k : nqg - 1));
 #pragma unroll
         for (int k = 0; k < 2; ++k) qm[k] = ld16(fs.Qm, qm0 + 16u * (unsigned)(ln + 16 * k < nqm ? ln + 16 * k : nqm - 1));
         const int col[3] = {I0 + c2, J0 + c2, J0 + 32 + c2};
         const size_t slab = (size_t)B * D;
-        v2d xv[3], m0[3], sl[3][4];
+        v2d xv[3], m0[3], sl[3][KCT];
         auto load_block = [&](int cb) {          // X, mu0 and the slabs (beyond KC: a re-read of the last one, dropped below) of one column block
             xv[cb] = *reinterpret_cast<const v2d*>(fs.X + (size_t)b * fs.ldx + col[cb]);
             m0[cb] = ld16(mu0, 8u * (unsigned)col[cb]);
 #pragma unroll
-            for (int kc = 0; kc < 4; ++kc)
-                sl[cb][kc] = *reinterpret_cast<const v2d*>(fs.Pp + (size_t)(kc < fs.KC ? kc : fs.KC - 1) * slab + (size_t)b * D + col[cb]);
+            for (int kc = 0; kc < KCT; ++kc)
+                sl[cb][kc] = *reinterpret_cast<const v2d*>(fs.Pp + (size_t)(KCT == 2 ? kc : (kc < fs.KC ? kc : fs.KC - 1)) * slab + (size_t)b * D + col[cb]);
         };
         load_block(0);
         load_block(1);
+        if constexpr (KCT == 2) {                // one batch: the second column block goes out with everything else
+            if (two) load_block(2);
+        }
         double gs = 0.0, ms = 0.0;               // this lane's share of sample b's partial dots, in unit order
 #pragma unroll
-        for (int k = 0; k < 8; ++k) {
+        for (int k = 0; k < NQG; ++k) {
             const bool in = ln + 16 * k < nqg;
             gs += in ? qg[k].x : 0.0;
             gs += in ? qg[k].y : 0.0;
@@ -599,10 +608,12 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(FROM_SLABS 
             ms += in ? qm[k].x : 0.0;
             ms += in ? qm[k].y : 0.0;
         }
-        // SECOND batch, behind the sums (the empty asm pins them in front of it): the second column block, which is staged last,
-        // takes the registers the partials held.  (block-uniform: the single-tile workgroups have no second column block)
-        asm volatile("" : "+v"(gs), "+v"(ms) : : "memory");
-        if (two) load_block(2);
+        // SECOND batch (KCT = 4), behind the sums (the empty asm pins them in front of it): the second column block, which is staged
+        // last, takes the registers the partials held.  (block-uniform: the single-tile workgroups have no second column block)
+        if constexpr (KCT == 4) {
+            asm volatile("" : "+v"(gs), "+v"(ms) : : "memory");
+            if (two) load_block(2);
+        }
         // the scalars of sample b, by the expressions of k_gsm_scalars_fast
         const double gSg = row16_sum(gs), mv = row16_sum(ms);
         const double rho = 0.5 * sqrt(1.0 + 4.0 * (gSg + mv * mv)) - 0.5;
@@ -613,10 +624,15 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(FROM_SLABS 
         for (int cb = 0; cb < 3; ++cb)
             if (cb < 2 || two) {
                 v2d sg = {0.0, 0.0}, dd, dm, ee;
+                if constexpr (KCT == 2) {
+                    sg.x = sl[cb][0].x + sl[cb][1].x;
+                    sg.y = sl[cb][0].y + sl[cb][1].y;
+                } else {
 #pragma unroll
-                for (int kc = 0; kc < 4; ++kc) {
-                    sg.x += (kc < fs.KC) ? sl[cb][kc].x : 0.0;
-                    sg.y += (kc < fs.KC) ? sl[cb][kc].y : 0.0;
+                    for (int kc = 0; kc < 4; ++kc) {
+                        sg.x += (kc < fs.KC) ? sl[cb][kc].x : 0.0;
+                        sg.y += (kc < fs.KC) ? sl[cb][kc].y : 0.0;
+                    }
                 }
                 dd.x = m0[cb].x - xv[cb].x;
                 dd.y = m0[cb].y - xv[cb].y;
@@ -1179,18 +1195,24 @@ void gsmvi_launch_panel_fast(hipStream_t st, hipEvent_t* ev, int MT, dim3 grid, 
 
 // The product launch of the two-launch dense GSM update: slabs Pp[kc][B][D] of G S0 (grid (D / 16, kc, 1), chunks of 256 rows)
 // plus the partial dots Qg, Qm (the caller checked the gate: B in {16, 32} = one row block, D % 256 == 0, aligned operands).
+// chw = 512 (round 8; D = 1024 only): grid (D / 16, 2, B / 16), ONE 512-row chunk and 16 samples per workgroup (MT = 1 also at
+// B = 32), so the whole split of a workgroup is one load batch (64 KB of G through LDS, 64 KB of S0), there are two slabs and
+// 2 D / 16 Qg partials per sample, and B = 32 still fills 256 workgroups.  The two sample halves of a (strip, slab) read the
+// same S0 rows; their linear ids differ by 128, the same XCD, and the second read is served from its L2 (DESIGN 8.1, round 8:
+// the MT = 2 form on 128 workgroups staged 128 KB per workgroup and was 2 us slower per launch).
 void gsmvi_launch_panel_fast_part(hipStream_t st, hipEvent_t* ev, dim3 grid, int D, int B, const double* G, int ldg,
                                   const double* S0, int lds0, double* Pp, int chunks_per_wg, const double* X, int ldx,
-                                  const double* mu0, double* Qg, double* Qm) {
+                                  const double* mu0, double* Qg, double* Qm, int chw) {
     gsmvi_panel_extras px;                     // (PART's arguments ride in free members: gsmvi_ctx.h)
     px.sj_src = X;
     px.sj_len = ldx;
     px.msl = mu0;
     px.sj_dst = Qg;
     px.mfin = Qm;
-#define PFQ(MTV) GSMVI_LAUNCH((k_panel_fast<MTV, false, 256, false, false, false, true>), grid, dim3(512), 0, st, ev, D, B, G, ldg, \
-                              nullptr, 1.0, S0, lds0, Pp, chunks_per_wg, D, nullptr, nullptr, 0, nullptr, px)
-    if (B == 16) PFQ(1); else PFQ(2);
+#define PFQ(MTV, CW) GSMVI_LAUNCH((k_panel_fast<MTV, false, CW, false, false, false, true>), grid, dim3(512), 0, st, ev, D, B, G, ldg, \
+                                  nullptr, 1.0, S0, lds0, Pp, chunks_per_wg, D, nullptr, nullptr, 0, nullptr, px)
+    if (chw == 512) PFQ(1, 512);
+    else { if (B == 16) PFQ(1, 256); else PFQ(2, 256); }
 #undef PFQ
 }
 
@@ -1277,14 +1299,16 @@ bool gsmvi_launch_gsm_cov_sym(hipStream_t st, hipEvent_t* ev, int D, int B, cons
 }
 
 // The covariance launch of the two-launch dense GSM update (the caller checked the gate: B in {16, 32}, D % 256 == 0, D <= 1024,
-// KC <= 4, even leading dimensions, 16-byte aligned bases).  Same grid as above.
+// KC <= 4, even leading dimensions, 16-byte aligned bases).  Same grid as above.  kct = 2: the instance compiled for exactly two
+// slabs (the caller's product ran the 512-row split: fs.KC == 2, D == 1024); kct = 4: any KC <= 4.
 void gsmvi_launch_gsm_cov_sym_slabs(hipStream_t st, hipEvent_t* ev, int D, int B, const gsm_slab_src& fs, const double* mu0,
-                                    const double* S0, int lds0, double* S, int lds, double* mu_out) {
+                                    const double* S0, int lds0, double* S, int lds, double* mu_out, int kct) {
     const dim3 grid(cov_sym_grid(D / 32));
     const double invB = 1.0 / (double)B;
-#define CSS(SBV)                                                                                                          \
-    GSMVI_LAUNCH((k_gsm_cov_sym<SBV, false, true>), grid, dim3(512), 0, st, ev, D, B, invB, nullptr, 0, mu0, S0, lds0, S, lds, mu_out, \
+#define CSS(SBV, KV)                                                                                                      \
+    GSMVI_LAUNCH((k_gsm_cov_sym<SBV, false, true, KV>), grid, dim3(512), 0, st, ev, D, B, invB, nullptr, 0, mu0, S0, lds0, S, lds, mu_out, \
                  0, nullptr, fs)
-    if (B == 16) CSS(16); else CSS(32);
+    if (kct == 2) { if (B == 16) CSS(16, 2); else CSS(32, 2); }
+    else { if (B == 16) CSS(16, 4); else CSS(32, 4); }
 #undef CSS
 }

@@ -96,7 +96,8 @@ int gsmvi_destroy(gsmvi_ctx* ctx);
  * "potrf_spin" (poll budget of a wait inside k_potrf_dag), "potrf_workers" (cap on its worker workgroups: tests of the ticket
  * order), "panel_w4_min_D"; "bam_batched_pad" (0 = the batched BaM kernel's LDS arrays at the unpadded row strides D, B; A/B
  * runs); "gsm_two_launch" (default 1: the dense GSM update at B in {16, 32}, D % 256 == 0, D <= 1024 with even leading
- * dimensions and 16-byte aligned arrays runs as two launches without the per-sample kernel; 0 = always three launches);
+ * dimensions and 16-byte aligned arrays runs as two launches without the per-sample kernel; 0 = always three launches;
+ * an explicit "panel_kc" also selects 256-row chunks for its product at D = 1024, where the default is two 512-row slabs);
  * diagnostics "timeline", "cov_dbg"
  * (see gsmvi_hip_debug.h). */
 int gsmvi_set_tuning(gsmvi_ctx* ctx, const char* name, int value);
@@ -110,6 +111,8 @@ int gsmvi_set_tuning(gsmvi_ctx* ctx, const char* name, int value);
  * Three kernels: panel product SG = G S0 (fp64 MFMA), per-sample scalars, rank-2B update (fp64 MFMA).
  * For B in {16, 32}, D % 256 == 0, D <= 1024, even leading dimensions and 16-byte aligned arrays: TWO kernels -- the product
  * also leaves partial dots, the update forms its factor tiles itself (knob "gsm_two_launch"; GSMVI_PATH_GSM_TWO_LAUNCH).
+ * At D = 1024 that product runs as two slabs of one 512-row chunk each (GSMVI_PATH_PANEL_CHUNK512) unless "panel_kc" is set
+ * explicitly, which keeps 256-row chunks with that split ("panel_kc" = 4: four slabs).
  * PRECONDITION: S0 is symmetric (a covariance).  For D % 32 == 0 and B in {16, 32, 64} the update kernel reads only
  * the UPPER triangle of S0 and mirrors the result, so S comes out exactly symmetric; for other shapes the generic
  * kernel reads all of S0.  A non-symmetric S0 therefore gives shape-dependent results that differ from
@@ -286,6 +289,7 @@ int gsmvi_get_profile(gsmvi_ctx* ctx, float* ms, int n);
 #define GSMVI_PATH_BATCHED_LOO 0x400000u /* k_psis_loo_batched: the batched PSIS leave-one-out                                */
 #define GSMVI_PATH_GSM_TWO_LAUNCH 0x800000u /* the dense GSM update ran as two launches (no k_gsm_scalars_fast, no records)          */
 #define GSMVI_PATH_BATCHED_SOFTMAX 0x1000000u /* k_softmax_batched: the batched multinomial logit target's entry point            */
+#define GSMVI_PATH_PANEL_CHUNK512 0x2000000u /* the two-launch product ran as two slabs of one 512-row chunk each (D = 1024, no explicit "panel_kc") */
 #define GSMVI_PATH_GENERIC_MASK (0x0004u | 0x0010u | 0x0040u | 0x0100u | 0x0400u | 0x1000u)
 int gsmvi_last_path(gsmvi_ctx* ctx, unsigned* bits, int reset);
 
