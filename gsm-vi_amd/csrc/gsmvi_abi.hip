@@ -83,6 +83,7 @@ int gsmvi_bam_factor_apply_cols_impl(gsmvi_ctx* ctx, hipStream_t st, int D, int 
                                      int* n_reverts_dev);
 
 #include "gsmvi_ctx.h"
+#include "gsmvi_panel_split.h"
 
 static thread_local std::string g_last_error;
 
@@ -360,11 +361,14 @@ int gsmvi_debug_read_stamps(gsmvi_ctx* ctx, unsigned long long* out, int n) {
     return GSMVI_OK;
 }
 
+// workspace region of the two diagnostics below: 0 = panel slabs, 1 = finished panels, 2 = small matrices
+static double* ws_region(const gsmvi_ctx* ctx, int region) { return region == 0 ? ctx->pp : (region == 1 ? ctx->sg : ctx->small); }
+
 /* Diagnostic: copy n doubles from a workspace region (0 = panel slabs, 1 = finished panels, 2 = small
  * matrices) starting at element `offset` to host memory.  Tests and debugging only. */
 int gsmvi_debug_read_workspace(gsmvi_ctx* ctx, int region, size_t offset, double* out, size_t n) {
     BAD_ARG(!ctx || !out || region < 0 || region > 2, "bad argument");
-    const double* base = region == 0 ? ctx->pp : (region == 1 ? ctx->sg : ctx->small);
+    const double* base = ws_region(ctx, region);
     HIP_TRY(hipDeviceSynchronize());
     HIP_TRY(hipMemcpy(out, base + offset, sizeof(double) * n, hipMemcpyDeviceToHost));
     return GSMVI_OK;
@@ -373,7 +377,7 @@ int gsmvi_debug_read_workspace(gsmvi_ctx* ctx, int region, size_t offset, double
 // device address of a workspace region (diagnostic scripts view intermediates in place)
 int gsmvi_debug_workspace_ptr(gsmvi_ctx* ctx, int region, double** out) {
     BAD_ARG(!ctx || !out || region < 0 || region > 2, "bad argument");
-    *out = region == 0 ? ctx->pp : (region == 1 ? ctx->sg : ctx->small);
+    *out = ws_region(ctx, region);
     return GSMVI_OK;
 }
 
@@ -419,40 +423,44 @@ int gsmvi_panel_product_nc(gsmvi_ctx* ctx, hipStream_t st, hipEvent_t* ev, int D
                            const double* A, int lda, const double* shift, double alpha, const double* M, int ldm,
                            double* Pp, int* kc_out);
 
+// Launch shape of a product with nrows rows of A and ncols columns of M (one workgroup per 16-column strip, slab and block
+// of 16 * MT rows), and whether the tuned kernel can take it.
+struct panel_shape {
+    int strips, MT, zblocks, a_vec_ok;
+    bool fast;
+};
+
+static panel_shape panel_shape_of(const gsmvi_ctx* ctx, int D, int ncols, int nrows, const double* A, int lda, const double* shift) {
+    const int MT = nrows <= 16 ? 1 : (nrows <= 32 ? 2 : 4);
+    const int zblocks = (nrows + 16 * MT - 1) / (16 * MT);
+    const int a_vec_ok = (lda % 2 == 0) && aligned16(A);
+    // any even inner dimension D and any ncols since round 5 (the kernel clamps); the slab-operand extra needs D % 16 == 0
+    const bool fast = !ctx->tune_no_fast && D % 2 == 0 && a_vec_ok && (!shift || aligned16(shift)) && !(ctx->px.msl && D % 16 != 0);
+    return {(ncols + 15) / 16, MT, zblocks, a_vec_ok, fast};
+}
+
 // Product with a FINISHED output Out (nrows x ncols, ldo) = addvec + alpha (A - shift) M.  On the fast path with a split-K
 // count of 1 the product launch writes Out itself; otherwise product + k_panel_finish.  Same numbers either way.
 int gsmvi_panel_product_out(gsmvi_ctx* ctx, hipStream_t st, int D, int ncols, int nrows, const double* A, int lda,
                             const double* shift, double alpha, const double* M, int ldm, const double* addvec, double* Out,
                             int ldo) {
-    const int strips = (ncols + 15) / 16;
-    const int MT = nrows <= 16 ? 1 : (nrows <= 32 ? 2 : 4);
-    const int zblocks = (nrows + 16 * MT - 1) / (16 * MT);
-    const int a_vec_ok = (lda % 2 == 0) && aligned16(A);
-    const bool fast = !ctx->tune_no_fast && ctx->tune_direct_out && D % 2 == 0 && a_vec_ok &&
-                      (!shift || aligned16(shift)) && !(ctx->px.msl && D % 16 != 0);
-    if (fast) {
-        const int chw = gsmvi_panel_fast_chunk(MT);
-        const int nchunks = (D + chw - 1) / chw;
+    const panel_shape ps = panel_shape_of(ctx, D, ncols, nrows, A, lda, shift);
+    if (ps.fast && ctx->tune_direct_out) {
+        const int chw = gsmvi_panel_fast_chunk(ps.MT);
         // the split the plain product would take (two workgroups per CU wanted); the one-launch form is used only when
         // that split is kc == 1 -- never at the price of fewer workgroups (D = 4096: kc = 2, 512 workgroups; forcing
         // kc = 1 there cost 20 % of the product's speed)
-        int kc = ctx->tune_panel_kc > 0 ? ctx->tune_panel_kc
-                                        : (2 * ctx->num_cu + strips * zblocks - 1) / (strips * zblocks);
-        if (kc > nchunks) kc = nchunks;
-        if (kc > GSMVI_MAX_KC) kc = GSMVI_MAX_KC;
-        if (kc >= 1) {
-            const int cpw = (nchunks + kc - 1) / kc;
-            kc = (nchunks + cpw - 1) / cpw;
-            // only the hand-off-free case (kc == 1): the product writes the finished output itself
-            if (kc == 1 && strips * zblocks <= 1024) {
-                const gsmvi_panel_extras px = ctx->px;
-                ctx->px = gsmvi_panel_extras();
-                ctx->px_used = 1;
-                gsmvi_launch_panel_fast(st, nullptr, MT, dim3(strips, kc, zblocks), D, nrows, A, lda, shift, alpha, M, ldm,
-                                        ctx->pp, cpw, ncols, ctx->timeline_stamps(0), Out, ldo, addvec, &px);
-                ctx->path |= GSMVI_PATH_PANEL_FAST;
-                return check_launch("k_panel_fast(out)");
-            }
+        const gsmvi_panel_split sp = gsmvi_panel_split_k(ps.strips * ps.zblocks, (D + chw - 1) / chw, ctx->tune_panel_kc,
+                                                         ctx->num_cu, GSMVI_MAX_KC);
+        // only the hand-off-free case (kc == 1): the product writes the finished output itself
+        if (sp.kc == 1 && ps.strips * ps.zblocks <= 1024) {
+            const gsmvi_panel_extras px = ctx->px;
+            ctx->px = gsmvi_panel_extras();
+            ctx->px_used = 1;
+            gsmvi_launch_panel_fast(st, nullptr, ps.MT, dim3(ps.strips, sp.kc, ps.zblocks), D, nrows, A, lda, shift, alpha, M,
+                                    ldm, ctx->pp, sp.cpw, ncols, ctx->timeline_stamps(0), Out, ldo, addvec, &px);
+            ctx->path |= GSMVI_PATH_PANEL_FAST;
+            return check_launch("k_panel_fast(out)");
         }
     }
     int kc = 1;
@@ -465,12 +473,9 @@ int gsmvi_panel_product_out(gsmvi_ctx* ctx, hipStream_t st, int D, int ncols, in
 int gsmvi_panel_product_nc(gsmvi_ctx* ctx, hipStream_t st, hipEvent_t* ev, int D, int ncols, int nrows,
                            const double* A, int lda, const double* shift, double alpha, const double* M, int ldm,
                            double* Pp, int* kc_out) {
-    const int strips = (ncols + 15) / 16;
-    const int MT = nrows <= 16 ? 1 : (nrows <= 32 ? 2 : 4);
-    const int zblocks = (nrows + 16 * MT - 1) / (16 * MT);
-    const int a_vec_ok = (lda % 2 == 0) && aligned16(A);
-    // any even inner dimension D and any ncols since round 5 (the kernel clamps); the slab-operand extra needs D % 16 == 0
-    const bool fast = !ctx->tune_no_fast && D % 2 == 0 && a_vec_ok && (!shift || aligned16(shift)) && !(ctx->px.msl && D % 16 != 0);
+    const panel_shape ps = panel_shape_of(ctx, D, ncols, nrows, A, lda, shift);
+    const int strips = ps.strips, MT = ps.MT, zblocks = ps.zblocks;
+    const bool fast = ps.fast;
     // 64-row panels of a D-sized product are MFMA-bound: the 64 x 64-tile kernel (gsmvi_wide.hip).  Not with extras: those
     // launches (K'' Tm with slab-summed rows, side jobs, the rider) stay on the narrow kernel.
     if (fast && MT == 4 && ctx->tune_wide && ncols % 64 == 0 && ncols >= 1024 && D >= 1024 && D % 64 == 0 && ldm % 2 == 0 && aligned16(M) &&
@@ -486,13 +491,8 @@ int gsmvi_panel_product_nc(gsmvi_ctx* ctx, hipStream_t st, hipEvent_t* ev, int D
     }
     const int chw = fast ? gsmvi_panel_fast_chunk(MT) : 256;       // rows of M per chunk
     const int nchunks = (D + chw - 1) / chw;
-    int kc = ctx->tune_panel_kc > 0 ? ctx->tune_panel_kc
-                                    : (2 * ctx->num_cu + strips * zblocks - 1) / (strips * zblocks);
-    if (kc > nchunks) kc = nchunks;
-    if (kc > GSMVI_MAX_KC) kc = GSMVI_MAX_KC;
-    if (kc < 1) kc = 1;
-    const int cpw = (nchunks + kc - 1) / kc;
-    kc = (nchunks + cpw - 1) / cpw;
+    const gsmvi_panel_split sp = gsmvi_panel_split_k(strips * zblocks, nchunks, ctx->tune_panel_kc, ctx->num_cu, GSMVI_MAX_KC);
+    const int kc = sp.kc, cpw = sp.cpw;
     *kc_out = kc;
     gsmvi_panel_extras px = ctx->px;
     ctx->px = gsmvi_panel_extras();                // extras are for ONE launch; px_used reports whether the fast kernel took them
@@ -509,7 +509,7 @@ int gsmvi_panel_product_nc(gsmvi_ctx* ctx, hipStream_t st, hipEvent_t* ev, int D
     }
     ctx->path |= GSMVI_PATH_PANEL_GENERIC;
     gsmvi_launch_panel_partial(st, ev, MT, dim3(strips, kc, zblocks), D, ncols, nrows, A, lda, shift, alpha, M,
-                               ldm, Pp, cpw, a_vec_ok);
+                               ldm, Pp, cpw, ps.a_vec_ok);
     return check_launch("k_panel_partial");
 }
 
@@ -548,6 +548,35 @@ static int check_common(gsmvi_ctx* ctx, int D, int B, const char* fn) {
     return GSMVI_OK;
 }
 
+// The bound of the factor forms (the 2B x 2B chain of gsmvi_factor.hip), reported under the entry's name; `hint` ends the
+// message (where to go instead).  B == 0: the D-only form of the batch-sharded local stage, whose B is a rank's share.
+static int check_factor_form(const char* fn, int D, int B, const char* hint) {
+    if (B == 0 ? D > 16384 : (2 * B > D || 2 * B > GSMVI_FACTOR_NMAX || D > 16384)) {
+        gsmvi_set_error(B == 0 ? "%s: the factor form supports D <= 16384%s" : "%s: the factor form needs 2B <= D and 2B <= 256%s",
+                        fn, hint);
+        return GSMVI_ERR_UNSUPPORTED;
+    }
+    return GSMVI_OK;
+}
+
+// The owned column block [col0, col0 + ncols) of the column-sharded factor forms: inside a D-column factor, tile aligned.
+// Looks at no context (a machine without a GPU can check it).
+static int check_col_block(const char* fn, int D, int B, int col0, int ncols) {
+    if (D <= 0 || B <= 0 || col0 < 0 || ncols <= 0 || col0 + ncols > D) {
+        gsmvi_set_error("%s: %s", fn, "column block out of range");
+        return GSMVI_ERR_BAD_ARG;
+    }
+    if (col0 % 64 != 0 || (ncols % 64 != 0 && col0 + ncols != D)) {
+        gsmvi_set_error("%s: %s", fn, "column blocks are tile aligned (multiples of 64; the last one may be ragged)");
+        return GSMVI_ERR_BAD_ARG;
+    }
+    return GSMVI_OK;
+}
+
+// ... and what its kernels ask of a block: 16-byte loads and stores of pairs along its rows
+static bool col_block_vec_ok(int D, int ld, const double* block) { return D % 2 == 0 && ld % 2 == 0 && aligned16(block); }
+static const char* const k_col_block_vec_msg = "the column-sharded form takes even D, even leading dimensions and 16-byte aligned blocks";
+
 extern "C" {
 
 static int gsm_records(gsmvi_ctx* ctx, hipStream_t hs, int D, int B, int kc, const double* X, int ldx,
@@ -559,6 +588,14 @@ static int gsm_local_stage(gsmvi_ctx* ctx, hipStream_t hs, int D, int B, const d
     int st = gsmvi_panel_product(ctx, hs, ctx->stage_events(0), D, B, G, ldg, nullptr, 1.0, S0, lds0, ctx->pp, &kc);
     if (st != GSMVI_OK) return st;
     return gsm_records(ctx, hs, D, B, kc, X, ldx, G, ldg, mu0, ctx->pp, rec, ldrec);
+}
+
+// Staged samples per pass of the guarded covariance kernel (k_gsm_cov_update): B rounded up to even, at most 64; `tuned` > 0
+// (the "update_sb" knob, for the entry points that honour it) replaces B.
+static int cov_update_sb(int B, int tuned) {
+    int SB = tuned > 0 ? tuned : ((B + 1) & ~1);
+    if (SB > 64) SB = 64;
+    return (SB + 1) & ~1;
 }
 
 static int gsm_apply(gsmvi_ctx* ctx, hipStream_t hs, int D, int B, const double* rec, int ldrec, const double* mu0,
@@ -574,9 +611,7 @@ static int gsm_apply(gsmvi_ctx* ctx, hipStream_t hs, int D, int B, const double*
         return check_launch("k_gsm_cov_sym");
     }
     ctx->path |= GSMVI_PATH_COV_GENERIC;
-    int SB = ctx->tune_update_sb > 0 ? ctx->tune_update_sb : ((B + 1) & ~1);
-    if (SB > 64) SB = 64;
-    SB = (SB + 1) & ~1;
+    const int SB = cov_update_sb(B, ctx->tune_update_sb);
     const int s_vec_ok = (lds0 % 2 == 0) && (lds % 2 == 0) && aligned16(S0) && aligned16(S);
     gsmvi_launch_gsm_cov_update(hs, ctx->stage_events(2), D, B, rec, ldrec, mu0, S0, lds0, S, lds, mu, SB, s_vec_ok,
                                 0, D);
@@ -598,8 +633,8 @@ static int gsm_records(gsmvi_ctx* ctx, hipStream_t hs, int D, int B, int kc, con
 
 // The dense update in TWO launches (no per-sample launch, no records): the product launch leaves partial dots beside its
 // slabs, the covariance launch forms its factor tiles from samples, slabs and partials (gsmvi_fast.hip: k_panel_fast<.., PART>,
-// k_gsm_cov_sym<.., FROM_SLABS>).  One gated shape family; *cpw_out, *kc_out = the product's split (the arithmetic of
-// gsmvi_panel_product_nc).  The diagnostics that stamp or ablate the three kernels keep the three launches.
+// k_gsm_cov_sym<.., FROM_SLABS>).  One gated shape family; *cpw_out, *kc_out = the product's split (gsmvi_panel_split_k, as
+// gsmvi_panel_product_nc takes it).  The diagnostics that stamp or ablate the three kernels keep the three launches.
 // *chw_out = rows per chunk of the product.  Round 8: D = 1024 (four 256-row chunks) with no explicit "panel_kc" runs as TWO
 // slabs of one 512-row chunk each -- half the slabs and half the Qg partials that every covariance workgroup re-reads; an
 // explicit "panel_kc" keeps 256-row chunks with that split (panel_kc=4: the round-7 route, for A/B runs in one process).
@@ -612,14 +647,10 @@ static bool gsm_two_launch_gate(const gsmvi_ctx* ctx, int D, int B, const double
     if (ldx % 2 != 0 || ldg % 2 != 0 || lds0 % 2 != 0 || lds % 2 != 0) return false;
     if (!aligned16(X) || !aligned16(G) || !aligned16(mu0) || !aligned16(S0) || !aligned16(S)) return false;
     const int strips = D / 16, nchunks = D / 256;              // one row block of B samples: MT = B / 16, chunks of 256 rows
-    int kc = ctx->tune_panel_kc > 0 ? ctx->tune_panel_kc : (2 * ctx->num_cu + strips - 1) / strips;
-    if (kc > nchunks) kc = nchunks;
-    if (kc < 1) kc = 1;
-    const int cpw = (nchunks + kc - 1) / kc;
-    kc = (nchunks + cpw - 1) / cpw;
-    if (kc > 4 || kc * cpw != nchunks) return false;           // <= 4 slabs of whole chunks
-    *cpw_out = cpw;
-    *kc_out = kc;
+    const gsmvi_panel_split sp = gsmvi_panel_split_k(strips, nchunks, ctx->tune_panel_kc, ctx->num_cu, GSMVI_MAX_KC);
+    if (sp.kc > 4 || sp.kc * sp.cpw != nchunks) return false;  // <= 4 slabs of whole chunks
+    *cpw_out = sp.cpw;
+    *kc_out = sp.kc;
     *chw_out = 256;
     if (nchunks == 4 && ctx->tune_panel_kc <= 0) {
         *cpw_out = 1;
@@ -693,8 +724,7 @@ int gsmvi_gsm_update_general_f64(gsmvi_ctx* ctx, void* stream, int D, int B, con
     if (st != GSMVI_OK) return st;
     st = gsm_records(ctx, hs, D, B, kc, X, ldx, G, ldg, mu0, ctx->pp, ctx->sg, ldrec);
     if (st != GSMVI_OK) return st;
-    int SB = (B + 1) & ~1;
-    if (SB > 64) SB = 64;
+    const int SB = cov_update_sb(B, 0);             // (this entry does not honour "update_sb")
     const int s_vec_ok = (lds0 % 2 == 0) && (lds % 2 == 0) && aligned16(S0) && aligned16(S);
     ctx->path |= GSMVI_PATH_COV_GENERIC;
     gsmvi_launch_gsm_cov_update(hs, nullptr, D, B, ctx->sg, ldrec, mu0, S0, lds0, S, lds, mu, SB, s_vec_ok, 0, D);
@@ -761,9 +791,7 @@ int gsmvi_gsm_apply_rows_f64(gsmvi_ctx* ctx, void* stream, int D, int B, int row
     BAD_ARG(ldrec < gsmvi_gsm_record_len(D), "ldrec smaller than gsmvi_gsm_record_len(D)");
     BAD_ARG(Srows == S0rows || (mu && mu == mu0), "outputs must not alias inputs");
     hipStream_t hs = reinterpret_cast<hipStream_t>(stream);
-    int SB = ctx->tune_update_sb > 0 ? ctx->tune_update_sb : ((B + 1) & ~1);
-    if (SB > 64) SB = 64;
-    SB = (SB + 1) & ~1;
+    const int SB = cov_update_sb(B, ctx->tune_update_sb);
     const int s_vec_ok = (lds0 % 2 == 0) && (lds % 2 == 0) && aligned16(S0rows) && aligned16(Srows);
     ctx->path |= GSMVI_PATH_COV_GENERIC;           // (the row-block kernel is the guarded one: a shard's rows need no mirror tiles)
     gsmvi_launch_gsm_cov_update(hs, ctx->stage_events(2), D, B, rec, ldrec, mu0, S0rows, lds0, Srows, lds, mu, SB,
@@ -808,16 +836,11 @@ int gsmvi_gsm_factor_apply_cols_f64(gsmvi_ctx* ctx, void* stream, int D, int B, 
     int st = check_common(ctx, D, B, __func__);
     if (st != GSMVI_OK) return st;
     BAD_ARG(!Z || !W || !X || !mu0 || !F0cols || !mu || !Fcols || !info_dev, "NULL argument");
-    BAD_ARG(col0 < 0 || ncols <= 0 || col0 + ncols > D, "column block out of range");
-    BAD_ARG(col0 % 64 != 0 || (ncols % 64 != 0 && col0 + ncols != D), "column blocks are tile aligned (multiples of 64; the last one may be ragged)");
+    if ((st = check_col_block(__func__, D, B, col0, ncols)) != GSMVI_OK) return st;
     BAD_ARG(ldz < D || ldx < D || ldf0 < ncols || ldf < ncols, "leading dimension too small");
     BAD_ARG(Fcols == F0cols || mu == mu0, "outputs must not alias inputs");
-    BAD_ARG(D % 2 != 0 || ldf0 % 2 != 0 || ldf % 2 != 0 || !aligned16(F0cols) || !aligned16(Fcols),
-            "the column-sharded form takes even D, even leading dimensions and 16-byte aligned blocks");
-    if (2 * B > D || 2 * B > GSMVI_FACTOR_NMAX || D > 16384) {
-        gsmvi_set_error("%s: %s", __func__, "the factor form needs 2B <= D and 2B <= 256");
-        return GSMVI_ERR_UNSUPPORTED;
-    }
+    BAD_ARG(!col_block_vec_ok(D, ldf0, F0cols) || !col_block_vec_ok(D, ldf, Fcols), k_col_block_vec_msg);
+    if ((st = check_factor_form(__func__, D, B, "")) != GSMVI_OK) return st;
     return gsmvi_factor_apply_cols_impl(ctx, reinterpret_cast<hipStream_t>(stream), D, B, col0, ncols, Z, ldz, W, D, X, ldx, mu0,
                                         F0cols, ldf0, mu, Fcols, ldf, info_dev, n_reverts_dev);
 }
@@ -875,10 +898,7 @@ int gsmvi_gsm_factor_update_f64(gsmvi_ctx* ctx, void* stream, int D, int B, cons
     BAD_ARG(!Z || !X || !G || !mu0 || !F0 || !mu || !F || !info_dev, "NULL argument");
     BAD_ARG(ldz < D || ldx < D || ldg < D || ldf0 < D || ldf < D, "leading dimension smaller than D");
     BAD_ARG(F == F0 || mu == mu0, "outputs must not alias inputs");
-    if (2 * B > D || 2 * B > GSMVI_FACTOR_NMAX || D > 16384) {
-        gsmvi_set_error("%s: %s", __func__, "the factor form needs 2B <= D and 2B <= 256; use gsmvi_gsm_update_f64");
-        return GSMVI_ERR_UNSUPPORTED;
-    }
+    if ((st = check_factor_form(__func__, D, B, "; use gsmvi_gsm_update_f64")) != GSMVI_OK) return st;
     return gsmvi_factor_impl(ctx, reinterpret_cast<hipStream_t>(stream), D, B, Z, ldz, X, ldx, G, ldg, mu0, F0, ldf0,
                              mu, F, ldf, info_dev, n_reverts_dev);
 }
@@ -891,10 +911,7 @@ int gsmvi_gsm_factor_local_stage_f64(gsmvi_ctx* ctx, void* stream, int D, int B_
     BAD_ARG(!Z || !X || !G || !mu0 || !F0 || !rec, "NULL argument");
     BAD_ARG(ldz < D || ldx < D || ldg < D || ldf0 < D, "leading dimension smaller than D");
     BAD_ARG(ldrec < gsmvi_gsm_record_len(D), "ldrec smaller than gsmvi_gsm_record_len(D)");
-    if (D > 16384) {
-        gsmvi_set_error("%s: %s", __func__, "the factor form supports D <= 16384");
-        return GSMVI_ERR_UNSUPPORTED;
-    }
+    if ((st = check_factor_form(__func__, D, 0, "")) != GSMVI_OK) return st;      // (B_local is a share of the batch: D only)
     return gsmvi_factor_local_impl(ctx, reinterpret_cast<hipStream_t>(stream), D, B_local, Z, ldz, X, ldx, G, ldg, mu0,
                                    F0, ldf0, rec, ldrec);
 }
@@ -908,10 +925,7 @@ int gsmvi_gsm_factor_apply_f64(gsmvi_ctx* ctx, void* stream, int D, int B, const
     BAD_ARG(ldz < D || ldf0 < D || ldf < D, "leading dimension smaller than D");
     BAD_ARG(ldrec < gsmvi_gsm_record_len(D), "ldrec smaller than gsmvi_gsm_record_len(D)");
     BAD_ARG(F == F0 || mu == mu0, "outputs must not alias inputs");
-    if (2 * B > D || 2 * B > GSMVI_FACTOR_NMAX || D > 16384) {
-        gsmvi_set_error("%s: %s", __func__, "the factor form needs 2B <= D and 2B <= 256; use gsmvi_gsm_update_f64");
-        return GSMVI_ERR_UNSUPPORTED;
-    }
+    if ((st = check_factor_form(__func__, D, B, "; use gsmvi_gsm_update_f64")) != GSMVI_OK) return st;
     return gsmvi_factor_apply_impl(ctx, reinterpret_cast<hipStream_t>(stream), D, B, Z, ldz, rec, ldrec, mu0, F0, ldf0,
                                    mu, F, ldf, info_dev, n_reverts_dev);
 }
@@ -938,10 +952,7 @@ int gsmvi_bam_factor_update_f64(gsmvi_ctx* ctx, void* stream, int D, int B, cons
     BAD_ARG(ldz < D || ldx < D || ldg < D || ldf0 < D || ldf < D, "leading dimension smaller than D");
     BAD_ARG(F == F0 || mu == mu0, "outputs must not alias inputs");
     BAD_ARG(!(reg > 0.0), "reg must be positive");
-    if (2 * B > D || 2 * B > GSMVI_FACTOR_NMAX || D > 16384) {
-        gsmvi_set_error("%s: %s", __func__, "the factor form needs 2B <= D and 2B <= 256; use gsmvi_bam_update_f64");
-        return GSMVI_ERR_UNSUPPORTED;
-    }
+    if ((st = check_factor_form(__func__, D, B, "; use gsmvi_bam_update_f64")) != GSMVI_OK) return st;
     return gsmvi_bam_factor_impl(ctx, reinterpret_cast<hipStream_t>(stream), D, B, Z, ldz, X, ldx, G, ldg, mu0, F0, ldf0, reg,
                                  mu, F, ldf, info_dev, n_reverts_dev);
 }
@@ -949,27 +960,17 @@ int gsmvi_bam_factor_update_f64(gsmvi_ctx* ctx, void* stream, int D, int B, cons
 // Geometry of the column-sharded factor-form BaM entry points, checked before the context is looked at (so a machine without
 // a GPU can check it): the block, the batch bound of the factor form, reg, even D and leading dimensions, aligned blocks.
 static int bam_cols_geometry(const char* fn, int D, int B, int col0, int ncols, int ldf0, const double* F0cols, double reg) {
-    if (D <= 0 || B <= 0 || col0 < 0 || ncols <= 0 || col0 + ncols > D) {
-        gsmvi_set_error("%s: %s", fn, "column block out of range");
-        return GSMVI_ERR_BAD_ARG;
-    }
-    if (col0 % 64 != 0 || (ncols % 64 != 0 && col0 + ncols != D)) {
-        gsmvi_set_error("%s: %s", fn, "column blocks are tile aligned (multiples of 64; the last one may be ragged)");
-        return GSMVI_ERR_BAD_ARG;
-    }
+    int st = check_col_block(fn, D, B, col0, ncols);
+    if (st != GSMVI_OK) return st;
     if (!(reg > 0.0)) {
         gsmvi_set_error("%s: %s", fn, "reg must be positive");
         return GSMVI_ERR_BAD_ARG;
     }
-    if (ldf0 < ncols || D % 2 != 0 || ldf0 % 2 != 0 || !aligned16(F0cols)) {
-        gsmvi_set_error("%s: %s", fn, "the column-sharded form takes even D, even leading dimensions and 16-byte aligned blocks");
+    if (ldf0 < ncols || !col_block_vec_ok(D, ldf0, F0cols)) {
+        gsmvi_set_error("%s: %s", fn, k_col_block_vec_msg);
         return GSMVI_ERR_BAD_ARG;
     }
-    if (2 * B > D || 2 * B > GSMVI_FACTOR_NMAX || D > 16384) {
-        gsmvi_set_error("%s: %s", fn, "the factor form needs 2B <= D and 2B <= 256");
-        return GSMVI_ERR_UNSUPPORTED;
-    }
-    return GSMVI_OK;
+    return check_factor_form(fn, D, B, "");
 }
 
 int gsmvi_bam_factor_wq_partial_f64(gsmvi_ctx* ctx, void* stream, int D, int B, int col0, int ncols, const double* G, int ldg,

@@ -31,6 +31,18 @@ def _unheld_entry(pool):
     return None
 
 
+def _device_index(device):
+    """the index of ``device``: None = torch's current device, an int, or anything torch.device takes (no index: 0)"""
+    if device is None:
+        return torch.cuda.current_device()
+    return device if isinstance(device, int) else (torch.device(device).index or 0)
+
+
+def _ptr(t):
+    """the raw device address of a tensor; None travels as NULL"""
+    return None if t is None else C.c_void_p(t.data_ptr())
+
+
 class HipEngine:
     """One context (workspace + launch heuristics) on one device; grows on demand."""
 
@@ -44,8 +56,7 @@ class HipEngine:
     def __init__(self, device=None, max_D=0, max_B=0):
         self.lib = _lib.load_library()
         _require_gpu()
-        self.device = torch.device("cuda", torch.cuda.current_device() if device is None else
-                                   (device if isinstance(device, int) else torch.device(device).index or 0))
+        self.device = torch.device("cuda", _device_index(device))
         self._ctx = C.c_void_p()
         self._max_D = 0
         self._max_B = 0
@@ -55,6 +66,8 @@ class HipEngine:
         self._stage = {}           # shape -> [pinned staging tensor, event behind its last host -> device copy] (from_host)
         self._hs = {}              # shape -> pinned buffers of the host-callable round trip (host_score)
         self.host_score_profile = None   # a dict here makes host_score accumulate its three phases (benchmarks only)
+        self._reg_word = None      # the device word BaM's regulariser is read from (bam_reg_source), kept alive while it is the source
+        self._gh_tables = {}       # Q -> device copy of the Q-point Gauss-Hermite table (glm_predict_batched)
         if max_D and max_B:
             self._ensure(max_D, max_B)
 
@@ -86,10 +99,22 @@ class HipEngine:
         _lib.check("gsmvi_create", self.lib.gsmvi_create(C.byref(ctx), self.device.index, newD, newB))
         self._ctx, self._max_D, self._max_B = ctx, newD, newB
         for k, v in self._tuning.items():          # knobs survive a context regrow
-            _lib.check("gsmvi_set_tuning", self.lib.gsmvi_set_tuning(self._ctx, k.encode(), int(v)))
-        word = getattr(self, "_reg_word", None)    # ... and so does the regulariser's device source (bam_reg_source): a regrown
-        if word is not None:                       # context that silently fell back to the by-value argument would be WRONG
-            _lib.check("gsmvi_bam_set_reg_source", self.lib.gsmvi_bam_set_reg_source(self._ctx, C.c_void_p(word.data_ptr())))
+            self._call_ctx("gsmvi_set_tuning", k.encode(), int(v))
+        if self._reg_word is not None:             # ... and so does the regulariser's device source (bam_reg_source): a regrown
+            self._call_ctx("gsmvi_bam_set_reg_source", _ptr(self._reg_word))     # context that fell back to the by-value argument would be WRONG
+
+    def _any_ctx(self):
+        """a context of any size: the entry points that use no (D, B) workspace need one all the same"""
+        self._ensure(max(self._max_D, 1), max(self._max_B, 1))
+
+    def _call(self, name, *args):
+        """one launch: entry point ``name`` on the current context and torch stream; a non-zero status raises (_lib.check).
+        Call it after the method's ``_ensure``: the context is read here."""
+        _lib.check(name, getattr(self.lib, name)(self._ctx, self._stream(), *args))
+
+    def _call_ctx(self, name, *args):
+        """the same for the entry points that take the context and no stream (knobs, path bits, profile)"""
+        _lib.check(name, getattr(self.lib, name)(self._ctx, *args))
 
     def release_retired(self):
         """Destroy the contexts a regrow left behind.  Only when no captured graph that used them will be replayed again."""
@@ -115,8 +140,8 @@ class HipEngine:
 
     def set_tuning(self, name, value):
         self._tuning[name] = int(value)
-        self._ensure(max(self._max_D, 1), max(self._max_B, 1))
-        _lib.check("gsmvi_set_tuning", self.lib.gsmvi_set_tuning(self._ctx, name.encode(), int(value)))
+        self._any_ctx()
+        self._call_ctx("gsmvi_set_tuning", name.encode(), int(value))
 
     # ---- array helpers ------------------------------------------------------------------
     def asarray(self, x):
@@ -257,12 +282,10 @@ class HipEngine:
         """(B, D) standard normals from the counter-based device stream (csrc/gsmvi_rng.hip): a pure function of
         (seed, call, element index).  Replaces the z-stream of np.random.multivariate_normal
         (gsmvi/gsm_numpy.py:105,116); ``call`` is the fit iteration."""
-        self._ensure(max(self._max_D, 1), max(self._max_B, 1))
+        self._any_ctx()
         Z = self.empty(B, D) if out is None else out
         assert Z.is_contiguous() and Z.numel() == B * D
-        _lib.check("gsmvi_randn_f64", self.lib.gsmvi_randn_f64(
-            self._ctx, self._stream(), int(seed) & (2 ** 64 - 1), int(call), B * D, C.c_void_p(Z.data_ptr()),
-            C.c_void_p(raw.data_ptr()) if raw is not None else None))
+        self._call("gsmvi_randn_f64", int(seed) & (2 ** 64 - 1), int(call), B * D, _ptr(Z), _ptr(raw))
         return Z
 
     def normal_batch(self, ncalls, B, D, seed, call0=0, out=None, call_in=None, call_out=None):
@@ -270,13 +293,11 @@ class HipEngine:
         block of fit iterations (the draw stream does not depend on the state).  ``call_in`` / ``call_out``: device int64
         words (1-element tensors); *call_in is added to call0 on the device and *call_out receives *call_in + ncalls, so a
         graph-captured launch advances through the stream on every replay."""
-        self._ensure(max(self._max_D, 1), max(self._max_B, 1))
+        self._any_ctx()
         Z = self.empty(ncalls, B, D) if out is None else out
         assert Z.is_contiguous() and Z.numel() == ncalls * B * D
-        _lib.check("gsmvi_randn_batch_f64", self.lib.gsmvi_randn_batch_f64(
-            self._ctx, self._stream(), int(seed) & (2 ** 64 - 1), int(call0), int(ncalls), B * D, C.c_void_p(Z.data_ptr()),
-            C.c_void_p(call_in.data_ptr()) if call_in is not None else None,
-            C.c_void_p(call_out.data_ptr()) if call_out is not None else None))
+        self._call("gsmvi_randn_batch_f64", int(seed) & (2 ** 64 - 1), int(call0), int(ncalls), B * D,
+                   _ptr(Z), _ptr(call_in), _ptr(call_out))
         return Z
 
     def _stream(self):
@@ -289,13 +310,13 @@ class HipEngine:
         assert isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float64, \
             f"{name}: expected a float64 CUDA tensor"
         assert t.dim() == 2 and t.stride(1) == 1, f"{name}: expected a 2-D tensor with unit inner stride"
-        return C.c_void_p(t.data_ptr()), int(t.stride(0)) if t.shape[0] > 1 else int(max(t.stride(0), t.shape[1]))
+        return _ptr(t), int(t.stride(0)) if t.shape[0] > 1 else int(max(t.stride(0), t.shape[1]))
 
     @staticmethod
     def _vec(t, name):
         assert isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float64 and t.dim() == 1 \
             and (t.numel() <= 1 or t.stride(0) == 1), f"{name}: expected a contiguous float64 CUDA vector"
-        return C.c_void_p(t.data_ptr())
+        return _ptr(t)
 
     # ---- the hot path -------------------------------------------------------------------
     def gsm_update(self, X, G, mu0, S0, out=None, general=False):
@@ -307,14 +328,9 @@ class HipEngine:
         assert G.shape == (B, D) and mu0.shape == (D,) and S0.shape == (D, D)
         self._ensure(D, B)
         mu, S = (self.empty(D), self.empty(D, D)) if out is None else out
-        px, ldx = self._mat(X, "samples")
-        pg, ldg = self._mat(G, "vs")
-        ps0, lds0 = self._mat(S0, "S0")
-        ps, lds = self._mat(S, "S")
         name = "gsmvi_gsm_update_general_f64" if general else "gsmvi_gsm_update_f64"
-        _lib.check(name, getattr(self.lib, name)(
-            self._ctx, self._stream(), D, B, px, ldx, pg, ldg, self._vec(mu0, "mu0"), ps0, lds0,
-            self._vec(mu, "mu"), ps, lds))
+        self._call(name, D, B, *self._mat(X, "samples"), *self._mat(G, "vs"), self._vec(mu0, "mu0"), *self._mat(S0, "S0"),
+                   self._vec(mu, "mu"), *self._mat(S, "S"))
         return mu, S
 
     def record_len(self, D):
@@ -326,12 +342,8 @@ class HipEngine:
         Bl, D = X.shape
         self._ensure(D, Bl)
         rec = self.empty(Bl, self.record_len(D)) if out is None else out
-        px, ldx = self._mat(X, "samples")
-        pg, ldg = self._mat(G, "vs")
-        ps0, lds0 = self._mat(S0, "S0")
-        pr, ldr = self._mat(rec, "rec")
-        _lib.check("gsmvi_gsm_local_stage_f64", self.lib.gsmvi_gsm_local_stage_f64(
-            self._ctx, self._stream(), D, Bl, px, ldx, pg, ldg, self._vec(mu0, "mu0"), ps0, lds0, pr, ldr))
+        self._call("gsmvi_gsm_local_stage_f64", D, Bl, *self._mat(X, "samples"), *self._mat(G, "vs"), self._vec(mu0, "mu0"),
+                   *self._mat(S0, "S0"), *self._mat(rec, "rec"))
         return rec
 
     def gsm_apply(self, rec, mu0, S0, out=None):
@@ -340,12 +352,8 @@ class HipEngine:
         D = mu0.shape[0]
         self._ensure(D, B)
         mu, S = (self.empty(D), self.empty(D, D)) if out is None else out
-        pr, ldr = self._mat(rec, "rec")
-        ps0, lds0 = self._mat(S0, "S0")
-        ps, lds = self._mat(S, "S")
-        _lib.check("gsmvi_gsm_apply_f64", self.lib.gsmvi_gsm_apply_f64(
-            self._ctx, self._stream(), D, B, pr, ldr, self._vec(mu0, "mu0"), ps0, lds0, self._vec(mu, "mu"),
-            ps, lds))
+        self._call("gsmvi_gsm_apply_f64", D, B, *self._mat(rec, "rec"), self._vec(mu0, "mu0"), *self._mat(S0, "S0"),
+                   self._vec(mu, "mu"), *self._mat(S, "S"))
         return mu, S
 
     # ---- row-block sharded covariance ---------------------------------
@@ -356,11 +364,8 @@ class HipEngine:
         assert S0_rows.shape == (nr, D)
         self._ensure(D, B)
         SGc = self.empty(B, nr) if out is None else out
-        pg, ldg = self._mat(G, "vs")
-        ps0, lds0 = self._mat(S0_rows, "S0_rows")
-        po, ldo = self._mat(SGc, "SGcols")
-        _lib.check("gsmvi_gsm_rows_stage_f64", self.lib.gsmvi_gsm_rows_stage_f64(
-            self._ctx, self._stream(), D, B, nr, pg, ldg, ps0, lds0, po, ldo))
+        self._call("gsmvi_gsm_rows_stage_f64", D, B, nr, *self._mat(G, "vs"), *self._mat(S0_rows, "S0_rows"),
+                   *self._mat(SGc, "SGcols"))
         return SGc
 
     def gsm_records(self, X, G, mu0, SG, out=None):
@@ -369,12 +374,8 @@ class HipEngine:
         assert SG.shape == (B, D) and SG.is_contiguous()
         self._ensure(D, B)
         rec = self.empty(B, self.record_len(D)) if out is None else out
-        px, ldx = self._mat(X, "samples")
-        pg, ldg = self._mat(G, "vs")
-        pr, ldr = self._mat(rec, "rec")
-        _lib.check("gsmvi_gsm_records_f64", self.lib.gsmvi_gsm_records_f64(
-            self._ctx, self._stream(), D, B, px, ldx, pg, ldg, self._vec(mu0, "mu0"), C.c_void_p(SG.data_ptr()),
-            pr, ldr))
+        self._call("gsmvi_gsm_records_f64", D, B, *self._mat(X, "samples"), *self._mat(G, "vs"), self._vec(mu0, "mu0"),
+                   _ptr(SG), *self._mat(rec, "rec"))
         return rec
 
     def gsm_apply_rows(self, rec, mu0, S0_rows, row0, out=None):
@@ -384,12 +385,8 @@ class HipEngine:
         nr = S0_rows.shape[0]
         self._ensure(D, B)
         mu, S = (self.empty(D), self.empty(nr, D)) if out is None else out
-        pr, ldr = self._mat(rec, "rec")
-        ps0, lds0 = self._mat(S0_rows, "S0_rows")
-        ps, lds = self._mat(S, "S_rows")
-        _lib.check("gsmvi_gsm_apply_rows_f64", self.lib.gsmvi_gsm_apply_rows_f64(
-            self._ctx, self._stream(), D, B, int(row0), nr, pr, ldr, self._vec(mu0, "mu0"), ps0, lds0,
-            self._vec(mu, "mu"), ps, lds))
+        self._call("gsmvi_gsm_apply_rows_f64", D, B, int(row0), nr, *self._mat(rec, "rec"), self._vec(mu0, "mu0"),
+                   *self._mat(S0_rows, "S0_rows"), self._vec(mu, "mu"), *self._mat(S, "S_rows"))
         return mu, S
 
     def gsm_factor_update(self, Z, X, G, mu0, F0, out=None, flag=None, n_reverts=None):
@@ -399,15 +396,9 @@ class HipEngine:
         self._ensure(D, B)
         mu, F = (self.empty(D), self.empty(D, D)) if out is None else out
         flag = self.new_flag() if flag is None else flag
-        pz, ldz = self._mat(Z, "Z")
-        px, ldx = self._mat(X, "X")
-        pg, ldg = self._mat(G, "G")
-        pf0, ldf0 = self._mat(F0, "F0")
-        pf, ldf = self._mat(F, "F")
-        _lib.check("gsmvi_gsm_factor_update_f64", self.lib.gsmvi_gsm_factor_update_f64(
-            self._ctx, self._stream(), D, B, pz, ldz, px, ldx, pg, ldg, self._vec(mu0, "mu0"), pf0, ldf0,
-            self._vec(mu, "mu"), pf, ldf, C.c_void_p(flag.data_ptr()),
-            C.c_void_p(n_reverts.data_ptr()) if n_reverts is not None else None))
+        self._call("gsmvi_gsm_factor_update_f64", D, B, *self._mat(Z, "Z"), *self._mat(X, "X"), *self._mat(G, "G"),
+                   self._vec(mu0, "mu0"), *self._mat(F0, "F0"), self._vec(mu, "mu"), *self._mat(F, "F"),
+                   _ptr(flag), _ptr(n_reverts))
         return mu, F, flag
 
     def bam_factor_update(self, Z, X, G, mu0, F0, reg, out=None, flag=None, n_reverts=None):
@@ -417,15 +408,9 @@ class HipEngine:
         self._ensure(D, B)
         mu, F = (self.empty(D), self.empty(D, D)) if out is None else out
         flag = self.new_flag() if flag is None else flag
-        pz, ldz = self._mat(Z, "Z")
-        px, ldx = self._mat(X, "X")
-        pg, ldg = self._mat(G, "G")
-        pf0, ldf0 = self._mat(F0, "F0")
-        pf, ldf = self._mat(F, "F")
-        _lib.check("gsmvi_bam_factor_update_f64", self.lib.gsmvi_bam_factor_update_f64(
-            self._ctx, self._stream(), D, B, pz, ldz, px, ldx, pg, ldg, self._vec(mu0, "mu0"), pf0, ldf0, float(reg),
-            self._vec(mu, "mu"), pf, ldf, C.c_void_p(flag.data_ptr()),
-            C.c_void_p(n_reverts.data_ptr()) if n_reverts is not None else None))
+        self._call("gsmvi_bam_factor_update_f64", D, B, *self._mat(Z, "Z"), *self._mat(X, "X"), *self._mat(G, "G"),
+                   self._vec(mu0, "mu0"), *self._mat(F0, "F0"), float(reg), self._vec(mu, "mu"), *self._mat(F, "F"),
+                   _ptr(flag), _ptr(n_reverts))
         return mu, F, flag
 
     def gsm_factor_local_stage(self, Z_l, X_l, G_l, mu0, F0, out=None):
@@ -433,13 +418,8 @@ class HipEngine:
         Bl, D = Z_l.shape
         self._ensure(D, Bl)
         rec = self.empty(Bl, self.record_len(D)) if out is None else out
-        pz, ldz = self._mat(Z_l, "Z")
-        px, ldx = self._mat(X_l, "X")
-        pg, ldg = self._mat(G_l, "G")
-        pf0, ldf0 = self._mat(F0, "F0")
-        pr, ldr = self._mat(rec, "rec")
-        _lib.check("gsmvi_gsm_factor_local_stage_f64", self.lib.gsmvi_gsm_factor_local_stage_f64(
-            self._ctx, self._stream(), D, Bl, pz, ldz, px, ldx, pg, ldg, self._vec(mu0, "mu0"), pf0, ldf0, pr, ldr))
+        self._call("gsmvi_gsm_factor_local_stage_f64", D, Bl, *self._mat(Z_l, "Z"), *self._mat(X_l, "X"),
+                   *self._mat(G_l, "G"), self._vec(mu0, "mu0"), *self._mat(F0, "F0"), *self._mat(rec, "rec"))
         return rec
 
     def gsm_factor_apply(self, Z, rec, mu0, F0, out=None, flag=None, n_reverts=None):
@@ -449,14 +429,9 @@ class HipEngine:
         self._ensure(D, B)
         mu, F = (self.empty(D), self.empty(D, D)) if out is None else out
         flag = self.new_flag() if flag is None else flag
-        pz, ldz = self._mat(Z, "Z")
-        pr, ldr = self._mat(rec, "rec")
-        pf0, ldf0 = self._mat(F0, "F0")
-        pf, ldf = self._mat(F, "F")
-        _lib.check("gsmvi_gsm_factor_apply_f64", self.lib.gsmvi_gsm_factor_apply_f64(
-            self._ctx, self._stream(), D, B, pz, ldz, pr, ldr, self._vec(mu0, "mu0"), pf0, ldf0,
-            self._vec(mu, "mu"), pf, ldf, C.c_void_p(flag.data_ptr()),
-            C.c_void_p(n_reverts.data_ptr()) if n_reverts is not None else None))
+        self._call("gsmvi_gsm_factor_apply_f64", D, B, *self._mat(Z, "Z"), *self._mat(rec, "rec"), self._vec(mu0, "mu0"),
+                   *self._mat(F0, "F0"), self._vec(mu, "mu"), *self._mat(F, "F"), _ptr(flag),
+                   _ptr(n_reverts))
         return mu, F, flag
 
     # ---- column-sharded factor form (dist.col_sharded_gsm_factor_update) --------------------------
@@ -467,11 +442,8 @@ class HipEngine:
         assert Fcols.shape == (D, nc) and mu_cols.shape == (nc,)
         self._ensure(D, B)
         X = self.empty(B, nc) if out is None else out
-        pz, ldz = self._mat(Z, "Z")
-        pf, ldf = self._mat(Fcols, "Fcols")
-        px, ldx = self._mat(X, "Xcols")
-        _lib.check("gsmvi_sample_cols_f64", self.lib.gsmvi_sample_cols_f64(
-            self._ctx, self._stream(), D, B, nc, pz, ldz, self._vec(mu_cols, "mu_cols"), pf, ldf, px, ldx))
+        self._call("gsmvi_sample_cols_f64", D, B, nc, *self._mat(Z, "Z"), self._vec(mu_cols, "mu_cols"),
+                   *self._mat(Fcols, "Fcols"), *self._mat(X, "Xcols"))
         return X
 
     def gsm_factor_w_partial(self, G, col0, Fcols, out=None):
@@ -490,14 +462,9 @@ class HipEngine:
         self._ensure(D, B)
         mu, F = (self.empty(D), self.empty(D, nc)) if out is None else out
         flag = self.new_flag() if flag is None else flag
-        pz, ldz = self._mat(Z, "Z")
-        px, ldx = self._mat(X, "X")
-        pf0, ldf0 = self._mat(F0cols, "F0cols")
-        pf, ldf = self._mat(F, "Fcols")
-        _lib.check("gsmvi_gsm_factor_apply_cols_f64", self.lib.gsmvi_gsm_factor_apply_cols_f64(
-            self._ctx, self._stream(), D, B, int(col0), nc, pz, ldz, C.c_void_p(W.data_ptr()), px, ldx, self._vec(mu0, "mu0"),
-            pf0, ldf0, self._vec(mu, "mu"), pf, ldf, C.c_void_p(flag.data_ptr()),
-            C.c_void_p(n_reverts.data_ptr()) if n_reverts is not None else None))
+        self._call("gsmvi_gsm_factor_apply_cols_f64", D, B, int(col0), nc, *self._mat(Z, "Z"), _ptr(W),
+                   *self._mat(X, "X"), self._vec(mu0, "mu0"), *self._mat(F0cols, "F0cols"), self._vec(mu, "mu"),
+                   *self._mat(F, "Fcols"), _ptr(flag), _ptr(n_reverts))
         return mu, F, flag
 
     def bam_factor_wq_partial(self, G, col0, F0cols, reg, out=None):
@@ -509,10 +476,8 @@ class HipEngine:
         self._ensure(D, B)                         # (the product's output is D wide: sized for (D, B), not for the block)
         Wq = self.empty(B, D) if out is None else out
         assert Wq.shape == (B, D) and Wq.is_contiguous()
-        pg, ldg = self._mat(G, "G")
-        pf0, ldf0 = self._mat(F0cols, "F0cols")
-        _lib.check("gsmvi_bam_factor_wq_partial_f64", self.lib.gsmvi_bam_factor_wq_partial_f64(
-            self._ctx, self._stream(), D, B, int(col0), nc, pg, ldg, pf0, ldf0, float(reg), C.c_void_p(Wq.data_ptr())))
+        self._call("gsmvi_bam_factor_wq_partial_f64", D, B, int(col0), nc, *self._mat(G, "G"), *self._mat(F0cols, "F0cols"),
+                   float(reg), _ptr(Wq))
         return Wq
 
     def bam_factor_apply_cols(self, Z, X, G, Wq, mu0, F0cols, col0, reg, out=None, flag=None, n_reverts=None):
@@ -524,15 +489,9 @@ class HipEngine:
         self._ensure(D, B)
         mu, F = (self.empty(D), self.empty(D, nc)) if out is None else out
         flag = self.new_flag() if flag is None else flag
-        pz, ldz = self._mat(Z, "Z")
-        px, ldx = self._mat(X, "X")
-        pg, ldg = self._mat(G, "G")
-        pf0, ldf0 = self._mat(F0cols, "F0cols")
-        pf, ldf = self._mat(F, "Fcols")
-        _lib.check("gsmvi_bam_factor_apply_cols_f64", self.lib.gsmvi_bam_factor_apply_cols_f64(
-            self._ctx, self._stream(), D, B, int(col0), nc, pz, ldz, px, ldx, pg, ldg, C.c_void_p(Wq.data_ptr()),
-            self._vec(mu0, "mu0"), pf0, ldf0, float(reg), self._vec(mu, "mu"), pf, ldf, C.c_void_p(flag.data_ptr()),
-            C.c_void_p(n_reverts.data_ptr()) if n_reverts is not None else None))
+        self._call("gsmvi_bam_factor_apply_cols_f64", D, B, int(col0), nc, *self._mat(Z, "Z"), *self._mat(X, "X"),
+                   *self._mat(G, "G"), _ptr(Wq), self._vec(mu0, "mu0"), *self._mat(F0cols, "F0cols"),
+                   float(reg), self._vec(mu, "mu"), *self._mat(F, "Fcols"), _ptr(flag), _ptr(n_reverts))
         return mu, F, flag
 
     def gram(self, F, out=None, shift=0.0, shift_dev=None):
@@ -544,14 +503,10 @@ class HipEngine:
         assert F.shape == (D, D)
         self._ensure(D, max(self._max_B, 1))
         Cm = self.empty(D, D) if out is None else out
-        pf, ldf = self._mat(F, "F")
-        pc, ldc = self._mat(Cm, "C")
         if shift == 0.0 and shift_dev is None:
-            _lib.check("gsmvi_gram_f64", self.lib.gsmvi_gram_f64(self._ctx, self._stream(), D, pf, ldf, pc, ldc))
+            self._call("gsmvi_gram_f64", D, *self._mat(F, "F"), *self._mat(Cm, "C"))
         else:
-            _lib.check("gsmvi_gram_shift_f64", self.lib.gsmvi_gram_shift_f64(
-                self._ctx, self._stream(), D, pf, ldf, float(shift),
-                C.c_void_p(shift_dev.data_ptr()) if shift_dev is not None else None, pc, ldc))
+            self._call("gsmvi_gram_shift_f64", D, *self._mat(F, "F"), float(shift), _ptr(shift_dev), *self._mat(Cm, "C"))
         return Cm
 
     def owed_shift(self, jitter, pend, n_rev, mark, advance=True):
@@ -572,12 +527,8 @@ class HipEngine:
         self._ensure(D, max(self._max_B, 1))
         Z = self.empty(n, D)
         ld = self.empty(1)
-        px, ldx = self._mat(X, "X")
-        pr, ldr = self._mat(R, "R")
-        pz, ldz = self._mat(Z, "Z")
-        _lib.check("gsmvi_whiten_rows_f64", self.lib.gsmvi_whiten_rows_f64(
-            self._ctx, self._stream(), D, n, pr, ldr, px, ldx, self._vec(mu, "mu") if mu is not None else None,
-            pz, ldz, C.c_void_p(ld.data_ptr())))
+        self._call("gsmvi_whiten_rows_f64", D, n, *self._mat(R, "R"), *self._mat(X, "X"),
+                   self._vec(mu, "mu") if mu is not None else None, *self._mat(Z, "Z"), _ptr(ld))
         return Z, ld
 
     # kernel-family bits of include/gsmvi_hip.h (GSMVI_PATH_*)
@@ -593,29 +544,28 @@ class HipEngine:
     def last_path(self, reset=True):
         """Names of the kernel families launched on this context since the last reset (gsmvi_last_path): how tests and
         profiles check that an off-grid shape stayed on the tuned kernels (no name ending in ``_generic``)."""
-        self._ensure(max(self._max_D, 1), max(self._max_B, 1))
+        self._any_ctx()
         bits = C.c_uint(0)
-        _lib.check("gsmvi_last_path", self.lib.gsmvi_last_path(self._ctx, C.byref(bits), int(bool(reset))))
+        self._call_ctx("gsmvi_last_path", C.byref(bits), int(bool(reset)))
         return {k for k, v in self.PATH_BITS.items() if bits.value & v}
 
     def bam_reg_source(self, word):
         """gsmvi_bam_set_reg_source: ``word`` (a 1-element float64 device tensor) makes every BaM update launched from now on
         read its regulariser from that word when its kernels EXECUTE (a captured graph can then be replayed with another
         value; the ``reg`` argument is ignored); ``None`` restores the by-value argument."""
-        self._ensure(max(self._max_D, 1), max(self._max_B, 1))
-        self._reg_word = word                                   # (kept alive while it is the source)
-        ptr = None if word is None else C.c_void_p(word.data_ptr())
-        _lib.check("gsmvi_bam_set_reg_source", self.lib.gsmvi_bam_set_reg_source(self._ctx, ptr))
+        self._any_ctx()
+        self._reg_word = word
+        self._call_ctx("gsmvi_bam_set_reg_source", _ptr(word))
 
     def set_profiling(self, on):
-        self._ensure(max(self._max_D, 1), max(self._max_B, 1))
-        _lib.check("gsmvi_set_profiling", self.lib.gsmvi_set_profiling(self._ctx, int(bool(on))))
+        self._any_ctx()
+        self._call_ctx("gsmvi_set_profiling", int(bool(on)))
 
     def get_profile(self):
         """Kernel durations (ms) of the last profiled update: panel, scalars, cov_update (-1: that launch did not run, as
         ``scalars`` in the two-launch form of the dense update)."""
         ms = (C.c_float * 3)()
-        _lib.check("gsmvi_get_profile", self.lib.gsmvi_get_profile(self._ctx, ms, 3))
+        self._call_ctx("gsmvi_get_profile", ms, 3)
         return {"panel": ms[0], "scalars": ms[1], "cov_update": ms[2]}
 
     def gaussian_score(self, X, m, P, out=None):
@@ -623,11 +573,8 @@ class HipEngine:
         B, D = X.shape
         self._ensure(D, B)
         G = self.empty(B, D) if out is None else out
-        px, ldx = self._mat(X, "X")
-        pp, ldp = self._mat(P, "P")
-        pg, ldg = self._mat(G, "G")
-        _lib.check("gsmvi_gaussian_score_f64", self.lib.gsmvi_gaussian_score_f64(
-            self._ctx, self._stream(), D, B, px, ldx, self._vec(m, "m"), pp, ldp, pg, ldg))
+        self._call("gsmvi_gaussian_score_f64", D, B, *self._mat(X, "X"), self._vec(m, "m"), *self._mat(P, "P"),
+                   *self._mat(G, "G"))
         return G
 
     def potrf(self, S, out=None, flag=None):
@@ -636,10 +583,7 @@ class HipEngine:
         self._ensure(D, max(self._max_B, 1))
         R = self.empty(D, D) if out is None else out
         flag = self.new_flag() if flag is None else flag
-        ps, lds = self._mat(S, "S")
-        pr, ldr = self._mat(R, "R")
-        _lib.check("gsmvi_potrf_f64", self.lib.gsmvi_potrf_f64(
-            self._ctx, self._stream(), D, ps, lds, pr, ldr, C.c_void_p(flag.data_ptr())))
+        self._call("gsmvi_potrf_f64", D, *self._mat(S, "S"), *self._mat(R, "R"), _ptr(flag))
         return R, flag
 
     def sample(self, Z, mu, R, out=None):
@@ -647,22 +591,15 @@ class HipEngine:
         B, D = Z.shape
         self._ensure(D, B)
         X = self.empty(B, D) if out is None else out
-        pz, ldz = self._mat(Z, "Z")
-        pr, ldr = self._mat(R, "R")
-        px, ldx = self._mat(X, "X")
-        _lib.check("gsmvi_sample_f64", self.lib.gsmvi_sample_f64(
-            self._ctx, self._stream(), D, B, pz, ldz, self._vec(mu, "mu"), pr, ldr, px, ldx))
+        self._call("gsmvi_sample_f64", D, B, *self._mat(Z, "Z"), self._vec(mu, "mu"), *self._mat(R, "R"), *self._mat(X, "X"))
         return X
 
     def commit(self, flag, mu_new, S_new, mu, S, n_reverts=None):
         """In place: (mu, S) <- (mu_new, S_new) iff flag == 0   [gsmvi/gsm_numpy.py:121-125]."""
         D = mu.shape[0]
         self._ensure(D, max(self._max_B, 1))
-        psn, ldsn = self._mat(S_new, "S_new")
-        ps, lds = self._mat(S, "S")
-        _lib.check("gsmvi_commit_f64", self.lib.gsmvi_commit_f64(
-            self._ctx, self._stream(), D, C.c_void_p(flag.data_ptr()), self._vec(mu_new, "mu_new"), psn, ldsn,
-            self._vec(mu, "mu"), ps, lds, C.c_void_p(n_reverts.data_ptr()) if n_reverts is not None else None))
+        self._call("gsmvi_commit_f64", D, _ptr(flag), self._vec(mu_new, "mu_new"),
+                   *self._mat(S_new, "S_new"), self._vec(mu, "mu"), *self._mat(S, "S"), _ptr(n_reverts))
 
     # ---- batched GSM: K independent problems of one (D, B) (csrc/gsmvi_batched.hip) -------------------------------------
     batched_max_D = 64         # one problem per workgroup slot, held in LDS from its first read to its last write
@@ -673,7 +610,7 @@ class HipEngine:
         assert isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float64 and t.is_contiguous(), \
             f"{name}: expected a contiguous float64 CUDA tensor"
         assert tuple(t.shape) == tuple(shape), f"{name}: expected shape {tuple(shape)}, got {tuple(t.shape)}"
-        return C.c_void_p(t.data_ptr())
+        return _ptr(t)
 
     @staticmethod
     def _ints(t, K, name):
@@ -681,7 +618,7 @@ class HipEngine:
             return None
         assert isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.int32 and t.is_contiguous() and t.numel() == K, \
             f"{name}: expected a contiguous int32 CUDA tensor of {K} entries"
-        return C.c_void_p(t.data_ptr())
+        return _ptr(t)
 
     def eye_batch(self, K, D):
         return torch.eye(D, dtype=torch.float64, device=self.device).expand(K, D, D).contiguous()
@@ -706,12 +643,11 @@ class HipEngine:
         """(mu_k, S_k) = gsm_update(X_k, G_k, mu0_k, S0_k) for every k  [gsmvi/gsm_numpy.py:27-55 under jax.vmap]; reads all
         of each S0_k."""
         K, B, D = X.shape
-        self._ensure(max(self._max_D, 1), max(self._max_B, 1))
+        self._any_ctx()
         mu, S = (self.empty(K, D), self.empty(K, D, D)) if out is None else out
-        _lib.check("gsmvi_gsm_update_batched_f64", self.lib.gsmvi_gsm_update_batched_f64(
-            self._ctx, self._stream(), K, D, B, self._packed(X, (K, B, D), "samples"), self._packed(G, (K, B, D), "vs"),
-            self._packed(mu0, (K, D), "mu0"), self._packed(S0, (K, D, D), "S0"), self._packed(mu, (K, D), "mu"),
-            self._packed(S, (K, D, D), "S")))
+        self._call("gsmvi_gsm_update_batched_f64", K, D, B, self._packed(X, (K, B, D), "samples"),
+                   self._packed(G, (K, B, D), "vs"), self._packed(mu0, (K, D), "mu0"), self._packed(S0, (K, D, D), "S0"),
+                   self._packed(mu, (K, D), "mu"), self._packed(S, (K, D, D), "S"))
         return mu, S
 
     def gsm_fit_init_batched(self, mean, cov, R, info, seeds=None, X=None):
@@ -719,32 +655,28 @@ class HipEngine:
         of the problem's stream"""
         K, D = mean.shape
         B = X.shape[1] if X is not None else 1
-        self._ensure(max(self._max_D, 1), max(self._max_B, 1))
-        _lib.check("gsmvi_gsm_fit_init_batched_f64", self.lib.gsmvi_gsm_fit_init_batched_f64(
-            self._ctx, self._stream(), K, D, B, self._packed(mean, (K, D), "mean"), self._packed(cov, (K, D, D), "cov"),
-            self._packed(R, (K, D, D), "R"), self._ints(info, K, "info"),
-            C.c_void_p(seeds.data_ptr()) if seeds is not None else None,
-            self._packed(X, (K, B, D), "X") if X is not None else None))
+        self._any_ctx()
+        self._call("gsmvi_gsm_fit_init_batched_f64", K, D, B, self._packed(mean, (K, D), "mean"),
+                   self._packed(cov, (K, D, D), "cov"), self._packed(R, (K, D, D), "R"), self._ints(info, K, "info"),
+                   _ptr(seeds), self._dp(X, (K, B, D), "X"))
 
     def gsm_fit_step_batched(self, X, G, mean, cov, R=None, info=None, n_reverts=None, seeds=None, call=0):
         """One batched fit iteration after the score (csrc/gsmvi_batched.hip): update, Cholesky test and accept / revert of
         (mean, cov, R) per problem; with ``seeds`` X is overwritten with the samples of draw ``call``."""
         K, B, D = X.shape
-        self._ensure(max(self._max_D, 1), max(self._max_B, 1))
-        _lib.check("gsmvi_gsm_fit_step_batched_f64", self.lib.gsmvi_gsm_fit_step_batched_f64(
-            self._ctx, self._stream(), K, D, B, self._packed(X, (K, B, D), "X"), self._packed(G, (K, B, D), "G"),
-            self._packed(mean, (K, D), "mean"), self._packed(cov, (K, D, D), "cov"),
-            self._packed(R, (K, D, D), "R") if R is not None else None, self._ints(info, K, "info"),
-            self._ints(n_reverts, K, "n_reverts"), C.c_void_p(seeds.data_ptr()) if seeds is not None else None, int(call)))
+        self._any_ctx()
+        self._call("gsmvi_gsm_fit_step_batched_f64", K, D, B, self._packed(X, (K, B, D), "X"),
+                   self._packed(G, (K, B, D), "G"), self._packed(mean, (K, D), "mean"), self._packed(cov, (K, D, D), "cov"),
+                   self._dp(R, (K, D, D), "R"), self._ints(info, K, "info"), self._ints(n_reverts, K, "n_reverts"),
+                   _ptr(seeds), int(call))
 
     def gaussian_score_batched(self, X, m, P, out=None):
         """G_k = -(X_k - m_k) P_k for K Gaussian targets  [examples/example_gsm_numpy.py:24-29]."""
         K, B, D = X.shape
-        self._ensure(max(self._max_D, 1), max(self._max_B, 1))
+        self._any_ctx()
         G = self.empty(K, B, D) if out is None else out
-        _lib.check("gsmvi_gaussian_score_batched_f64", self.lib.gsmvi_gaussian_score_batched_f64(
-            self._ctx, self._stream(), K, D, B, self._packed(X, (K, B, D), "X"), self._packed(m, (K, D), "m"),
-            self._packed(P, (K, D, D), "P"), self._packed(G, (K, B, D), "G")))
+        self._call("gsmvi_gaussian_score_batched_f64", K, D, B, self._packed(X, (K, B, D), "X"),
+                   self._packed(m, (K, D), "m"), self._packed(P, (K, D, D), "P"), self._packed(G, (K, B, D), "G"))
         return G
 
     # ---- batched BaM: K independent problems of one (D, B) (csrc/gsmvi_bam_batched.hip) -----------------------------------
@@ -753,7 +685,7 @@ class HipEngine:
         if isinstance(reg, torch.Tensor):
             assert reg.is_cuda and reg.dtype == torch.float64 and reg.is_contiguous() and reg.numel() == K, \
                 f"reg: expected a contiguous float64 CUDA tensor of {K} entries"
-            return 0.0, C.c_void_p(reg.data_ptr())
+            return 0.0, _ptr(reg)
         return float(reg), None
 
     def batched_regs(self, values):
@@ -765,13 +697,13 @@ class HipEngine:
         symmetrised, jitter on its diagonal; ``reg`` a number or a (K,) device tensor; info[k] != 0: problem k's chain failed
         (its outputs are NaN)."""
         K, B, D = X.shape
-        self._ensure(max(self._max_D, 1), max(self._max_B, 1))
+        self._any_ctx()
         mu, S = (self.empty(K, D), self.empty(K, D, D)) if out is None else out
         r, rp = self._reg_arg(reg, K)
-        _lib.check("gsmvi_bam_update_batched_f64", self.lib.gsmvi_bam_update_batched_f64(
-            self._ctx, self._stream(), K, D, B, self._packed(X, (K, B, D), "samples"), self._packed(G, (K, B, D), "vs"),
-            self._packed(mu0, (K, D), "mu0"), self._packed(S0, (K, D, D), "S0"), r, rp, float(jitter),
-            self._packed(mu, (K, D), "mu"), self._packed(S, (K, D, D), "S"), self._ints(info, K, "info")))
+        self._call("gsmvi_bam_update_batched_f64", K, D, B, self._packed(X, (K, B, D), "samples"),
+                   self._packed(G, (K, B, D), "vs"), self._packed(mu0, (K, D), "mu0"), self._packed(S0, (K, D, D), "S0"), r,
+                   rp, float(jitter), self._packed(mu, (K, D), "mu"), self._packed(S, (K, D, D), "S"),
+                   self._ints(info, K, "info"))
         return mu, S
 
     def bam_fit_step_batched(self, X, G, mean, cov, R=None, reg=1.0, jitter=0.0, info=None, n_reverts=None, seeds=None,
@@ -779,14 +711,13 @@ class HipEngine:
         """One batched BaM fit iteration after the score (csrc/gsmvi_bam_batched.hip): update + jitter I, Cholesky test and
         accept / revert of (mean, cov, R) per problem; with ``seeds`` X is overwritten with the samples of draw ``call``."""
         K, B, D = X.shape
-        self._ensure(max(self._max_D, 1), max(self._max_B, 1))
+        self._any_ctx()
         r, rp = self._reg_arg(reg, K)
         px = self._packed(X, (K, B, D), "X")
-        _lib.check("gsmvi_bam_fit_step_batched_f64", self.lib.gsmvi_bam_fit_step_batched_f64(
-            self._ctx, self._stream(), K, D, B, px, self._packed(G, (K, B, D), "G"), self._packed(mean, (K, D), "mean"),
-            self._packed(cov, (K, D, D), "cov"), self._packed(R, (K, D, D), "R") if R is not None else None, r, rp,
-            float(jitter), self._ints(info, K, "info"), self._ints(n_reverts, K, "n_reverts"),
-            C.c_void_p(seeds.data_ptr()) if seeds is not None else None, int(call), px if seeds is not None else None))
+        self._call("gsmvi_bam_fit_step_batched_f64", K, D, B, px, self._packed(G, (K, B, D), "G"),
+                   self._packed(mean, (K, D), "mean"), self._packed(cov, (K, D, D), "cov"), self._dp(R, (K, D, D), "R"), r,
+                   rp, float(jitter), self._ints(info, K, "info"), self._ints(n_reverts, K, "n_reverts"), _ptr(seeds),
+                   int(call), px if seeds is not None else None)
 
     # ---- batched KL monitor: K Gaussians of one D (csrc/gsmvi_kl_batched.hip) ----------------------------------------------
     def kl_draw_batched(self, mean, cov, seeds, call, s0, nc, out=None, info=None):
@@ -795,16 +726,15 @@ class HipEngine:
         sum of log q_k over the rows [monitors.py:104-113], info (K,) int32: 0, or 1 + the first bad pivot of cov_k, whose X
         rows and logq are NaN)."""
         K, D = mean.shape
-        self._ensure(max(self._max_D, 1), max(self._max_B, 1))
+        self._any_ctx()
         mean, cov = mean.contiguous(), cov.contiguous()
         X, logq = (self.empty(K, nc, D), self.empty(K)) if out is None else out
         info = self.batched_ints(K) if info is None else info
         assert isinstance(seeds, torch.Tensor) and seeds.is_cuda and seeds.dtype == torch.int64 and seeds.is_contiguous() \
             and seeds.numel() == K, f"seeds: expected {K} keys from batched_seeds()"
-        _lib.check("gsmvi_kl_draw_batched_f64", self.lib.gsmvi_kl_draw_batched_f64(
-            self._ctx, self._stream(), K, D, int(nc), int(s0), self._packed(mean, (K, D), "mean"),
-            self._packed(cov, (K, D, D), "cov"), C.c_void_p(seeds.data_ptr()), int(call), self._packed(X, (K, nc, D), "X"),
-            self._packed(logq, (K,), "logq"), self._ints(info, K, "info")))
+        self._call("gsmvi_kl_draw_batched_f64", K, D, int(nc), int(s0), self._packed(mean, (K, D), "mean"),
+                   self._packed(cov, (K, D, D), "cov"), _ptr(seeds), int(call),
+                   self._packed(X, (K, nc, D), "X"), self._packed(logq, (K,), "logq"), self._ints(info, K, "info"))
         return X, logq, info
 
     def take_rows(self, A, idx):
@@ -816,13 +746,13 @@ class HipEngine:
         [gsmvi/monitors.py:104-113], by forward substitution with the upper factor of cov_k; NaN where cov_k is not positive
         definite (info[k] = 1 + the first bad pivot)."""
         K, nc, D = Y.shape
-        self._ensure(max(self._max_D, 1), max(self._max_B, 1))
+        self._any_ctx()
         mean, cov, Y = mean.contiguous(), cov.contiguous(), Y.contiguous()
         logq = self.empty(K) if out is None else out
         info = self.batched_ints(K) if info is None else info
-        _lib.check("gsmvi_logq_batched_f64", self.lib.gsmvi_logq_batched_f64(
-            self._ctx, self._stream(), K, D, nc, self._packed(mean, (K, D), "mean"), self._packed(cov, (K, D, D), "cov"),
-            self._packed(Y, (K, nc, D), "Y"), self._packed(logq, (K,), "logq"), self._ints(info, K, "info")))
+        self._call("gsmvi_logq_batched_f64", K, D, nc, self._packed(mean, (K, D), "mean"),
+                   self._packed(cov, (K, D, D), "cov"), self._packed(Y, (K, nc, D), "Y"), self._packed(logq, (K,), "logq"),
+                   self._ints(info, K, "info"))
         return logq, info
 
     # ---- batched ADVI: K full-rank ELBO fits of one (D, B) (csrc/gsmvi_advi_batched.hip) ----------------------------------
@@ -837,12 +767,10 @@ class HipEngine:
         K, D = mean.shape
         B = X.shape[1] if X is not None else 1
         P = D * (D + 1) // 2
-        self._ensure(max(self._max_D, 1), max(self._max_B, 1))
-        _lib.check("gsmvi_advi_init_batched_f64", self.lib.gsmvi_advi_init_batched_f64(
-            self._ctx, self._stream(), K, D, B, self._packed(mean, (K, D), "mean"), self._packed(cov, (K, D, D), "cov"),
-            self._packed(scales, (K, P), "scales"), self._ints(info, K, "info"),
-            C.c_void_p(seeds.data_ptr()) if seeds is not None else None, self._dp(Z, (K, B, D), "Z"),
-            self._dp(X, (K, B, D), "X"), self._dp(logq, (K,), "logq")))
+        self._any_ctx()
+        self._call("gsmvi_advi_init_batched_f64", K, D, B, self._packed(mean, (K, D), "mean"),
+                   self._packed(cov, (K, D, D), "cov"), self._packed(scales, (K, P), "scales"), self._ints(info, K, "info"),
+                   _ptr(seeds), self._dp(Z, (K, B, D), "Z"), self._dp(X, (K, B, D), "X"), self._dp(logq, (K,), "logq"))
 
     def advi_step_batched(self, G, loc, scales, moments, t, lr, b1=0.9, b2=0.999, eps=1e-8, seeds=None, call=0, Zcur=None,
                           Znext=None, Xout=None, logq=None):
@@ -852,24 +780,23 @@ class HipEngine:
         ``call`` of ``seeds``, or ``Znext``; the z behind G is draw ``call`` - 1, or ``Zcur``)."""
         K, B, D = G.shape
         P = D * (D + 1) // 2
-        self._ensure(max(self._max_D, 1), max(self._max_B, 1))
+        self._any_ctx()
         m_loc, v_loc, m_s, v_s = moments
         r, rp = self._reg_arg(lr, K)
-        _lib.check("gsmvi_advi_step_batched_f64", self.lib.gsmvi_advi_step_batched_f64(
-            self._ctx, self._stream(), K, D, B, self._packed(G, (K, B, D), "G"), self._packed(loc, (K, D), "loc"),
-            self._packed(scales, (K, P), "scales"), self._packed(m_loc, (K, D), "m_loc"), self._packed(v_loc, (K, D), "v_loc"),
-            self._packed(m_s, (K, P), "m_s"), self._packed(v_s, (K, P), "v_s"), int(t), r, rp, float(b1), float(b2), float(eps),
-            C.c_void_p(seeds.data_ptr()) if seeds is not None else None, int(call), self._dp(Zcur, (K, B, D), "Zcur"),
-            self._dp(Znext, (K, B, D), "Znext"), self._dp(Xout, (K, B, D), "Xout"), self._dp(logq, (K,), "logq")))
+        self._call("gsmvi_advi_step_batched_f64", K, D, B, self._packed(G, (K, B, D), "G"), self._packed(loc, (K, D), "loc"),
+                   self._packed(scales, (K, P), "scales"), self._packed(m_loc, (K, D), "m_loc"),
+                   self._packed(v_loc, (K, D), "v_loc"), self._packed(m_s, (K, P), "m_s"), self._packed(v_s, (K, P), "v_s"),
+                   int(t), r, rp, float(b1), float(b2), float(eps), _ptr(seeds), int(call),
+                   self._dp(Zcur, (K, B, D), "Zcur"), self._dp(Znext, (K, B, D), "Znext"), self._dp(Xout, (K, B, D), "Xout"),
+                   self._dp(logq, (K,), "logq"))
 
     def advi_cov_batched(self, scales, D, out=None):
         """cov_k = L_k L_k^T (K, D, D), exactly symmetric, from the packed factors (K, D (D + 1) / 2)  [gsmvi/advi.py:25-29]"""
         K = scales.shape[0]
-        self._ensure(max(self._max_D, 1), max(self._max_B, 1))
+        self._any_ctx()
         cov = self.empty(K, D, D) if out is None else out
-        _lib.check("gsmvi_advi_cov_batched_f64", self.lib.gsmvi_advi_cov_batched_f64(
-            self._ctx, self._stream(), K, D, self._packed(scales, (K, D * (D + 1) // 2), "scales"),
-            self._packed(cov, (K, D, D), "cov")))
+        self._call("gsmvi_advi_cov_batched_f64", K, D, self._packed(scales, (K, D * (D + 1) // 2), "scales"),
+                   self._packed(cov, (K, D, D), "cov"))
         return cov
 
     # ---- batched logistic target: K regressions of one (N, D) (csrc/gsmvi_logistic_batched.hip) ---------------------------
@@ -879,27 +806,33 @@ class HipEngine:
         if want not in (a, b, "both"):
             raise ValueError(f"want = {want!r}: expected {a!r}, {b!r} or 'both'")
 
-    def logistic_batched(self, X, A, y, counts=None, prior_prec=1.0, out=None, lp_out=None, want="g"):
-        """Score and / or log-density of K Bayesian logistic regressions at the rows of X (K, nc, D), one launch
-        [examples/example_gsm.py:34-35 for this model]: A (K, N, D), y (K, N), ``counts`` None or K device int32 valid rows,
-        ``prior_prec`` a number or a (K,) device tensor.  ``want`` = "g" -> G (K, nc, D) (no logarithm is evaluated), "lp" -> the
-        values (K, nc), "both" -> (G, lp)."""
+    def _want_g_lp(self, want, X, out, lp_out):
+        """The ``want`` protocol of the target launches at the rows of X (K, nc, D): checks ``want``; returns G (K, nc, D)
+        (``out`` when given; None for "lp"), lp (K, nc) (``lp_out`` when given; None for "g") and what the method returns"""
         self._check_want(want, "g", "lp")
-        X = X.contiguous()
         K, nc, D = X.shape
-        N = A.shape[1]
-        self._ensure(max(self._max_D, 1), max(self._max_B, 1))
         G = lp = None
         if want != "lp":
             G = self.empty(K, nc, D) if out is None else out
         if want != "g":
             lp = self.empty(K, nc) if lp_out is None else lp_out
+        return G, lp, (G if want == "g" else lp if want == "lp" else (G, lp))
+
+    def logistic_batched(self, X, A, y, counts=None, prior_prec=1.0, out=None, lp_out=None, want="g"):
+        """Score and / or log-density of K Bayesian logistic regressions at the rows of X (K, nc, D), one launch
+        [examples/example_gsm.py:34-35 for this model]: A (K, N, D), y (K, N), ``counts`` None or K device int32 valid rows,
+        ``prior_prec`` a number or a (K,) device tensor.  ``want`` = "g" -> G (K, nc, D) (no logarithm is evaluated), "lp" -> the
+        values (K, nc), "both" -> (G, lp)."""
+        G, lp, ret = self._want_g_lp(want, X, out, lp_out)
+        X = X.contiguous()
+        K, nc, D = X.shape
+        N = A.shape[1]
+        self._any_ctx()
         r, rp = self._reg_arg(prior_prec, K)
-        _lib.check("gsmvi_logistic_batched_f64", self.lib.gsmvi_logistic_batched_f64(
-            self._ctx, self._stream(), K, D, nc, N, self._packed(A, (K, N, D), "A"), self._packed(y, (K, N), "y"),
-            self._ints(counts, K, "counts"), r, rp, self._packed(X, (K, nc, D), "X"), self._dp(G, (K, nc, D), "out"),
-            self._dp(lp, (K, nc), "lp_out")))
-        return G if want == "g" else lp if want == "lp" else (G, lp)
+        self._call("gsmvi_logistic_batched_f64", K, D, nc, N, self._packed(A, (K, N, D), "A"), self._packed(y, (K, N), "y"),
+                   self._ints(counts, K, "counts"), r, rp, self._packed(X, (K, nc, D), "X"), self._dp(G, (K, nc, D), "out"),
+                   self._dp(lp, (K, nc), "lp_out"))
+        return ret
 
     # ---- batched softmax target: K multinomial logit regressions of one (N, C, P) (csrc/gsmvi_softmax_batched.hip) ----------
     def softmax_batched(self, X, A, labels, num_classes, counts=None, prior_prec=1.0, out=None, lp_out=None, want="g"):
@@ -908,7 +841,7 @@ class HipEngine:
         ``labels`` (K, N) device int32 in 0 .. C - 1, ``num_classes`` = C, ``counts`` None or K device int32 valid rows,
         ``prior_prec`` a number or a (K,) device tensor.  ``want`` = "g" -> G (K, nc, D) (no logarithm is evaluated), "lp" -> the
         values (K, nc), "both" -> (G, lp)."""
-        self._check_want(want, "g", "lp")
+        G, lp, ret = self._want_g_lp(want, X, out, lp_out)
         X = X.contiguous()
         K, nc, D = X.shape
         N, P, Cc = A.shape[1], A.shape[2], int(num_classes)
@@ -916,18 +849,12 @@ class HipEngine:
             raise ValueError(f"X: expected (num_classes - 1) P = {(Cc - 1) * P} columns, got {D}")
         assert labels.is_cuda and labels.dtype == torch.int32 and labels.is_contiguous() and tuple(labels.shape) == (K, N), \
             f"labels: expected a contiguous int32 CUDA tensor of shape {(K, N)}"
-        self._ensure(max(self._max_D, 1), max(self._max_B, 1))
-        G = lp = None
-        if want != "lp":
-            G = self.empty(K, nc, D) if out is None else out
-        if want != "g":
-            lp = self.empty(K, nc) if lp_out is None else lp_out
+        self._any_ctx()
         r, rp = self._reg_arg(prior_prec, K)
-        _lib.check("gsmvi_softmax_batched_f64", self.lib.gsmvi_softmax_batched_f64(
-            self._ctx, self._stream(), K, Cc, P, nc, N, self._packed(A, (K, N, P), "A"), C.c_void_p(labels.data_ptr()),
-            self._ints(counts, K, "counts"), r, rp, self._packed(X, (K, nc, D), "X"), self._dp(G, (K, nc, D), "out"),
-            self._dp(lp, (K, nc), "lp_out")))
-        return G if want == "g" else lp if want == "lp" else (G, lp)
+        self._call("gsmvi_softmax_batched_f64", K, Cc, P, nc, N, self._packed(A, (K, N, P), "A"),
+                   _ptr(labels), self._ints(counts, K, "counts"), r, rp, self._packed(X, (K, nc, D), "X"),
+                   self._dp(G, (K, nc, D), "out"), self._dp(lp, (K, nc), "lp_out"))
+        return ret
 
     def batched_labels(self, values):
         """(K, N) integer labels as a device int32 tensor"""
@@ -950,23 +877,17 @@ class HipEngine:
         (identity link, noise precision ``noise_prec``: a number or a (K,) device tensor, this family only); A (K, N, D), y
         (K, N), ``offset`` None or (K, N) added to A x, ``counts`` None or K device int32 valid rows, ``prior_prec`` a number or
         a (K,) device tensor.  ``want`` = "g" -> G (K, nc, D), "lp" -> the values (K, nc), "both" -> (G, lp)."""
-        self._check_want(want, "g", "lp")
+        G, lp, ret = self._want_g_lp(want, X, out, lp_out)
         fam, t, tp = self._glm_family_args(family, noise_prec, X.shape[0])
         X = X.contiguous()
         K, nc, D = X.shape
         N = A.shape[1]
-        self._ensure(max(self._max_D, 1), max(self._max_B, 1))
-        G = lp = None
-        if want != "lp":
-            G = self.empty(K, nc, D) if out is None else out
-        if want != "g":
-            lp = self.empty(K, nc) if lp_out is None else lp_out
+        self._any_ctx()
         r, rp = self._reg_arg(prior_prec, K)
-        _lib.check("gsmvi_glm_batched_f64", self.lib.gsmvi_glm_batched_f64(
-            self._ctx, self._stream(), K, D, nc, N, fam, self._packed(A, (K, N, D), "A"),
-            self._packed(y, (K, N), "y"), self._dp(offset, (K, N), "offset"), self._ints(counts, K, "counts"), t, tp, r, rp,
-            self._packed(X, (K, nc, D), "X"), self._dp(G, (K, nc, D), "out"), self._dp(lp, (K, nc), "lp_out")))
-        return G if want == "g" else lp if want == "lp" else (G, lp)
+        self._call("gsmvi_glm_batched_f64", K, D, nc, N, fam, self._packed(A, (K, N, D), "A"), self._packed(y, (K, N), "y"),
+                   self._dp(offset, (K, N), "offset"), self._ints(counts, K, "counts"), t, tp, r, rp,
+                   self._packed(X, (K, nc, D), "X"), self._dp(G, (K, nc, D), "out"), self._dp(lp, (K, nc), "lp_out"))
+        return ret
 
     # ---- batched L-BFGS initialiser: K minimisations of one D (csrc/gsmvi_lbfgs_batched.hip) --------------------------------
     def lbfgs_state_batched(self, x0):
@@ -978,6 +899,14 @@ class HipEngine:
                 "Y": self.zeros(K, 10, D), "sc": self.zeros(K, 24), "ist": torch.zeros(K, 8, dtype=torch.int32, device=self.device),
                 "stopped": self.new_flag()}
 
+    @staticmethod
+    def _ist(state, K):
+        """the int32 words ``ist`` (K, 8) of an L-BFGS or Laplace state, checked, as a raw pointer"""
+        ist = state["ist"]
+        assert isinstance(ist, torch.Tensor) and ist.is_cuda and ist.dtype == torch.int32 and ist.is_contiguous() \
+            and tuple(ist.shape) == (K, 8), f"ist: expected a contiguous int32 CUDA tensor of shape {(K, 8)}"
+        return _ptr(ist)
+
     def lbfgs_step_batched(self, fv, gv, state, start=False, sign=-1.0, maxiter=1000, maxfun=1000, gtol=1e-5,
                            ftol=2.220446049250313e-09):
         """One launch of the batched L-BFGS initialiser (csrc/gsmvi_lbfgs_batched.hip) after the evaluation at ``state["Xt"]``:
@@ -985,31 +914,25 @@ class HipEngine:
         otherwise accept or reject the trial point of every running problem, update its state in place and write its next
         trial point; ``state["stopped"]`` (optional) grows by the problems that stopped  [gsmvi/initializers.py:5-17]"""
         K, D = state["x"].shape
-        self._ensure(max(self._max_D, 1), max(self._max_B, 1))
-        ist = state["ist"]
-        assert isinstance(ist, torch.Tensor) and ist.is_cuda and ist.dtype == torch.int32 and ist.is_contiguous() \
-            and tuple(ist.shape) == (K, 8), f"ist: expected a contiguous int32 CUDA tensor of shape {(K, 8)}"
+        self._any_ctx()
         stopped = state.get("stopped")
-        _lib.check("gsmvi_lbfgs_step_batched_f64", self.lib.gsmvi_lbfgs_step_batched_f64(
-            self._ctx, self._stream(), K, D, int(bool(start)), self._packed(fv, (K,), "fv"), self._packed(gv, (K, D), "gv"),
-            float(sign), self._packed(state["x"], (K, D), "x"), self._packed(state["g"], (K, D), "g"),
-            self._packed(state["d"], (K, D), "d"), self._packed(state["S"], (K, 10, D), "S"),
-            self._packed(state["Y"], (K, 10, D), "Y"), self._packed(state["sc"], (K, 24), "sc"), C.c_void_p(ist.data_ptr()),
-            self._packed(state["Xt"], (K, D), "Xt"), self._ints(stopped, 1, "stopped"), int(maxiter), int(maxfun), float(gtol),
-            float(ftol)))
+        self._call("gsmvi_lbfgs_step_batched_f64", K, D, int(bool(start)), self._packed(fv, (K,), "fv"),
+                   self._packed(gv, (K, D), "gv"), float(sign), self._packed(state["x"], (K, D), "x"),
+                   self._packed(state["g"], (K, D), "g"), self._packed(state["d"], (K, D), "d"),
+                   self._packed(state["S"], (K, 10, D), "S"), self._packed(state["Y"], (K, 10, D), "Y"),
+                   self._packed(state["sc"], (K, 24), "sc"), self._ist(state, K),
+                   self._packed(state["Xt"], (K, D), "Xt"), self._ints(stopped, 1, "stopped"), int(maxiter), int(maxfun),
+                   float(gtol), float(ftol))
 
     def lbfgs_hess_inv_batched(self, state, out=None):
         """cov_k (K, D, D) = the dense BFGS inverse-Hessian product of the pairs held in ``state`` (S, Y, ist) on an identity
         base, exactly symmetric  [scipy.optimize.LbfgsInvHessProduct.todense, gsmvi/initializers.py:15]"""
         K, _, D = state["S"].shape
-        self._ensure(max(self._max_D, 1), max(self._max_B, 1))
-        ist = state["ist"]
-        assert isinstance(ist, torch.Tensor) and ist.is_cuda and ist.dtype == torch.int32 and ist.is_contiguous() \
-            and tuple(ist.shape) == (K, 8), f"ist: expected a contiguous int32 CUDA tensor of shape {(K, 8)}"
+        self._any_ctx()
         cov = self.empty(K, D, D) if out is None else out
-        _lib.check("gsmvi_lbfgs_hess_inv_batched_f64", self.lib.gsmvi_lbfgs_hess_inv_batched_f64(
-            self._ctx, self._stream(), K, D, self._packed(state["S"], (K, 10, D), "S"), self._packed(state["Y"], (K, 10, D), "Y"),
-            C.c_void_p(ist.data_ptr()), self._packed(cov, (K, D, D), "cov")))
+        self._call("gsmvi_lbfgs_hess_inv_batched_f64", K, D, self._packed(state["S"], (K, 10, D), "S"),
+                   self._packed(state["Y"], (K, 10, D), "Y"), self._ist(state, K),
+                   self._packed(cov, (K, D, D), "cov"))
         return cov
 
     # ---- batched Laplace initialiser: Hessian, inverse and Newton rounds of the GLM targets (csrc/gsmvi_laplace_batched.hip) ----
@@ -1030,17 +953,16 @@ class HipEngine:
         self._check_want(want, "h", "cov")
         X = X.contiguous()
         K, D = X.shape
-        self._ensure(max(self._max_D, 1), max(self._max_B, 1))
+        self._any_ctx()
         H = cov = info = None
         if want != "cov":
             H = self.empty(K, D, D) if out is None else out
         if want != "h":
             cov = self.empty(K, D, D) if cov_out is None else cov_out
             info = torch.zeros(K, dtype=torch.int32, device=self.device) if info_out is None else info_out
-        _lib.check("gsmvi_glm_hessian_batched_f64", self.lib.gsmvi_glm_hessian_batched_f64(
-            self._ctx, self._stream(), *self._glm_model_args(A, y, family, offset, counts, prior_prec, noise_prec),
-            self._packed(X, (K, D), "X"), self._dp(H, (K, D, D), "out"), self._dp(cov, (K, D, D), "cov_out"),
-            self._ints(info, K, "info_out")))
+        self._call("gsmvi_glm_hessian_batched_f64",
+                   *self._glm_model_args(A, y, family, offset, counts, prior_prec, noise_prec), self._packed(X, (K, D), "X"),
+                   self._dp(H, (K, D, D), "out"), self._dp(cov, (K, D, D), "cov_out"), self._ints(info, K, "info_out"))
         return H if want == "h" else (cov, info) if want == "cov" else (H, cov, info)
 
     def laplace_state_batched(self, x0):
@@ -1057,16 +979,14 @@ class HipEngine:
         ``state["Xt"]`` in one sweep over A, then accept or reject, the stopping tests, the next direction and trial point;
         ``state["stopped"]`` (optional) grows by the problems that stopped  [the role of gsmvi/initializers.py:5-17]"""
         K, D = state["x"].shape
-        self._ensure(max(self._max_D, 1), max(self._max_B, 1))
-        ist = state["ist"]
-        assert isinstance(ist, torch.Tensor) and ist.is_cuda and ist.dtype == torch.int32 and ist.is_contiguous() \
-            and tuple(ist.shape) == (K, 8), f"ist: expected a contiguous int32 CUDA tensor of shape {(K, 8)}"
+        self._any_ctx()
         stopped = state.get("stopped")
-        _lib.check("gsmvi_laplace_step_batched_f64", self.lib.gsmvi_laplace_step_batched_f64(
-            self._ctx, self._stream(), *self._glm_model_args(A, y, family, offset, counts, prior_prec, noise_prec),
-            int(bool(start)), self._packed(state["x"], (K, D), "x"), self._packed(state["g"], (K, D), "g"),
-            self._packed(state["d"], (K, D), "d"), self._packed(state["sc"], (K, 4), "sc"), C.c_void_p(ist.data_ptr()),
-            self._packed(state["Xt"], (K, D), "Xt"), self._ints(stopped, 1, "stopped"), int(maxiter), int(maxfun), float(gtol)))
+        self._call("gsmvi_laplace_step_batched_f64",
+                   *self._glm_model_args(A, y, family, offset, counts, prior_prec, noise_prec), int(bool(start)),
+                   self._packed(state["x"], (K, D), "x"), self._packed(state["g"], (K, D), "g"),
+                   self._packed(state["d"], (K, D), "d"), self._packed(state["sc"], (K, 4), "sc"),
+                   self._ist(state, K), self._packed(state["Xt"], (K, D), "Xt"), self._ints(stopped, 1, "stopped"),
+                   int(maxiter), int(maxfun), float(gtol))
 
     # ---- batched GLM posterior predictive: the use of K fitted Gaussians (csrc/gsmvi_glm_predict_batched.hip) -----------------
     @staticmethod
@@ -1078,11 +998,10 @@ class HipEngine:
 
     def _gh_table(self, Q):
         """the device copy of ``gauss_hermite(Q)``, uploaded once per Q and kept on the engine"""
-        cache = self.__dict__.setdefault("_gh_tables", {})
-        if Q not in cache:
+        if Q not in self._gh_tables:
             t, lw = self.gauss_hermite(Q)
-            cache[Q] = (self.asarray(t), self.asarray(lw))
-        return cache[Q]
+            self._gh_tables[Q] = (self.asarray(t), self.asarray(lw))
+        return self._gh_tables[Q]
 
     def glm_predict_batched(self, mean, cov, A, family, offset=None, y=None, counts=None, noise_prec=1.0, nodes=32):
         """The posterior predictive of K fitted GLMs at the rows of A (K, M, D) under q_k = N(mean_k, cov_k), one launch (the
@@ -1094,18 +1013,18 @@ class HipEngine:
         if not 1 <= Q <= 64:
             raise ValueError(f"nodes = {nodes!r}: expected 1 .. 64")
         K, M, D = A.shape
-        self._ensure(max(self._max_D, 1), max(self._max_B, 1))
+        self._any_ctx()
         gt, gl = self._gh_table(Q)
         em, ev, pm = self.empty(K, M), self.empty(K, M), self.empty(K, M)
         lpd = elpd = None
         if y is not None:
             lpd, elpd = self.empty(K, M), self.empty(K)
-        _lib.check("gsmvi_glm_predict_batched_f64", self.lib.gsmvi_glm_predict_batched_f64(
-            self._ctx, self._stream(), K, D, M, fam, self._packed(A, (K, M, D), "A"),
-            self._dp(offset, (K, M), "offset"), self._dp(y, (K, M), "y"), self._ints(counts, K, "counts"), t, tp,
-            self._packed(mean, (K, D), "mean"), self._packed(cov, (K, D, D), "cov"), Q, self._packed(gt, (Q,), "gh_t"),
-            self._packed(gl, (Q,), "gh_logw"), self._packed(em, (K, M), "eta_mean"), self._packed(ev, (K, M), "eta_var"),
-            self._packed(pm, (K, M), "pmean"), self._dp(lpd, (K, M), "lpd"), self._dp(elpd, (K,), "elpd")))
+        self._call("gsmvi_glm_predict_batched_f64", K, D, M, fam, self._packed(A, (K, M, D), "A"),
+                   self._dp(offset, (K, M), "offset"), self._dp(y, (K, M), "y"), self._ints(counts, K, "counts"), t, tp,
+                   self._packed(mean, (K, D), "mean"), self._packed(cov, (K, D, D), "cov"), Q,
+                   self._packed(gt, (Q,), "gh_t"), self._packed(gl, (Q,), "gh_logw"), self._packed(em, (K, M), "eta_mean"),
+                   self._packed(ev, (K, M), "eta_var"), self._packed(pm, (K, M), "pmean"), self._dp(lpd, (K, M), "lpd"),
+                   self._dp(elpd, (K,), "elpd"))
         return em, ev, pm, lpd, elpd
 
     # ---- batched Pareto-smoothed importance diagnostic of K fitted Gaussians (csrc/gsmvi_psis_batched.hip) ----------------------
@@ -1115,12 +1034,11 @@ class HipEngine:
         (K,) int32: 0, -1 = non-finite ratios (the problem's outputs are NaN), -2 = tail too short to fit (khat = +inf))."""
         logr = logr.contiguous()
         K, S = logr.shape
-        self._ensure(max(self._max_D, 1), max(self._max_B, 1))
+        self._any_ctx()
         lw, khat, ess, log_z, info = self.empty(K, S), self.empty(K), self.empty(K), self.empty(K), self.batched_ints(K)
-        _lib.check("gsmvi_psis_weights_batched_f64", self.lib.gsmvi_psis_weights_batched_f64(
-            self._ctx, self._stream(), K, S, self._packed(logr, (K, S), "logr"), self._packed(lw, (K, S), "lw"),
-            self._packed(khat, (K,), "khat"), self._packed(ess, (K,), "ess"), self._packed(log_z, (K,), "log_z"),
-            self._ints(info, K, "info")))
+        self._call("gsmvi_psis_weights_batched_f64", K, S, self._packed(logr, (K, S), "logr"),
+                   self._packed(lw, (K, S), "lw"), self._packed(khat, (K,), "khat"), self._packed(ess, (K,), "ess"),
+                   self._packed(log_z, (K,), "log_z"), self._ints(info, K, "info"))
         return lw, khat, ess, log_z, info
 
     def psis_batched(self, mean, cov, X, lp, moments=True):
@@ -1130,17 +1048,16 @@ class HipEngine:
         (K, S), khat, ess, log_z (K,), mean_is (K, D), cov_is (K, D, D) -- both None without ``moments`` --, info (K,) int32:
         psis_weights_batched's codes, or 1 + the first bad pivot of cov_k, whose outputs are all NaN)."""
         K, S, D = X.shape
-        self._ensure(max(self._max_D, 1), max(self._max_B, 1))
+        self._any_ctx()
         mean, cov, X, lp = mean.contiguous(), cov.contiguous(), X.contiguous(), lp.contiguous()
         logr, lw, khat, ess, log_z = self.empty(K, S), self.empty(K, S), self.empty(K), self.empty(K), self.empty(K)
         mean_is, cov_is = (self.empty(K, D), self.empty(K, D, D)) if moments else (None, None)
         info = self.batched_ints(K)
-        _lib.check("gsmvi_psis_batched_f64", self.lib.gsmvi_psis_batched_f64(
-            self._ctx, self._stream(), K, D, S, self._packed(mean, (K, D), "mean"), self._packed(cov, (K, D, D), "cov"),
-            self._packed(X, (K, S, D), "X"), self._packed(lp, (K, S), "lp"), self._packed(logr, (K, S), "logr"),
-            self._packed(lw, (K, S), "lw"), self._packed(khat, (K,), "khat"), self._packed(ess, (K,), "ess"),
-            self._packed(log_z, (K,), "log_z"), self._dp(mean_is, (K, D), "mean_is"), self._dp(cov_is, (K, D, D), "cov_is"),
-            self._ints(info, K, "info")))
+        self._call("gsmvi_psis_batched_f64", K, D, S, self._packed(mean, (K, D), "mean"),
+                   self._packed(cov, (K, D, D), "cov"), self._packed(X, (K, S, D), "X"), self._packed(lp, (K, S), "lp"),
+                   self._packed(logr, (K, S), "logr"), self._packed(lw, (K, S), "lw"), self._packed(khat, (K,), "khat"),
+                   self._packed(ess, (K,), "ess"), self._packed(log_z, (K,), "log_z"), self._dp(mean_is, (K, D), "mean_is"),
+                   self._dp(cov_is, (K, D, D), "cov_is"), self._ints(info, K, "info"))
         return logr, lw, khat, ess, log_z, mean_is, cov_is, info
 
     # ---- batched PSIS leave-one-out of K fitted GLM posteriors (csrc/gsmvi_psis_loo_batched.hip) ----------------------------------
@@ -1158,17 +1075,17 @@ class HipEngine:
         K, S, D = X.shape
         N = A.shape[1]
         fam, t, tp = self._glm_family_args(family, noise_prec, K)
-        self._ensure(max(self._max_D, 1), max(self._max_B, 1))
+        self._any_ctx()
         X, logr, lw = X.contiguous(), logr.contiguous(), lw.contiguous()
         elpd, lpd, khat, ess = self.empty(K, N), self.empty(K, N), self.empty(K, N), self.empty(K, N)
         info = self.batched_ints(K * N).view(K, N)
         loglik = self.empty(K, N, S) if pointwise_loglik else None
-        _lib.check("gsmvi_psis_loo_batched_f64", self.lib.gsmvi_psis_loo_batched_f64(
-            self._ctx, self._stream(), fam, K, N, D, S, self._packed(A, (K, N, D), "A"), self._packed(y, (K, N), "y"),
-            self._dp(offset, (K, N), "offset"), self._ints(counts, K, "counts"), t, tp, self._packed(X, (K, S, D), "X"),
-            self._packed(logr, (K, S), "logr"), self._packed(lw, (K, S), "lw"), self._dp(loglik, (K, N, S), "loglik"),
-            self._packed(elpd, (K, N), "elpd"), self._packed(lpd, (K, N), "lpd"), self._packed(khat, (K, N), "khat"),
-            self._packed(ess, (K, N), "ess"), self._ints(info, K * N, "info")))
+        self._call("gsmvi_psis_loo_batched_f64", fam, K, N, D, S, self._packed(A, (K, N, D), "A"),
+                   self._packed(y, (K, N), "y"), self._dp(offset, (K, N), "offset"), self._ints(counts, K, "counts"), t, tp,
+                   self._packed(X, (K, S, D), "X"), self._packed(logr, (K, S), "logr"), self._packed(lw, (K, S), "lw"),
+                   self._dp(loglik, (K, N, S), "loglik"), self._packed(elpd, (K, N), "elpd"),
+                   self._packed(lpd, (K, N), "lpd"), self._packed(khat, (K, N), "khat"), self._packed(ess, (K, N), "ess"),
+                   self._ints(info, K * N, "info"))
         return elpd, lpd, khat, ess, info, loglik
 
     def bam_update(self, X, G, mu0, S0, reg, jitter=0.0, out=None, flag=None):
@@ -1180,13 +1097,9 @@ class HipEngine:
         self._ensure(D, B)
         mu, S = (self.empty(D), self.empty(D, D)) if out is None else out
         flag = self.new_flag() if flag is None else flag
-        px, ldx = self._mat(X, "samples")
-        pg, ldg = self._mat(G, "vs")
-        ps0, lds0 = self._mat(S0, "S0")
-        ps, lds = self._mat(S, "S")
-        _lib.check("gsmvi_bam_update_f64", self.lib.gsmvi_bam_update_f64(
-            self._ctx, self._stream(), D, B, px, ldx, pg, ldg, self._vec(mu0, "mu0"), ps0, lds0,
-            float(reg), float(jitter), self._vec(mu, "mu"), ps, lds, C.c_void_p(flag.data_ptr())))
+        self._call("gsmvi_bam_update_f64", D, B, *self._mat(X, "samples"), *self._mat(G, "vs"), self._vec(mu0, "mu0"),
+                   *self._mat(S0, "S0"), float(reg), float(jitter), self._vec(mu, "mu"), *self._mat(S, "S"),
+                   _ptr(flag))
         return mu, S, flag
 
 
@@ -1199,8 +1112,7 @@ def get_engine(device=None):
     threads; give every extra stream / thread its own ``HipEngine(device)`` (as bench.py --in-flight does)."""
     _lib.load_library()
     _require_gpu()
-    idx = torch.cuda.current_device() if device is None else (device if isinstance(device, int)
-                                                              else (torch.device(device).index or 0))
+    idx = _device_index(device)
     if idx not in _ENGINES:
         _ENGINES[idx] = HipEngine(idx)
     return _ENGINES[idx]
