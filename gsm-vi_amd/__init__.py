@@ -43,6 +43,10 @@ Mirrors the reference's public surface for the hot path (reference file:line):
     lbfgs_init_batched (the L-BFGS initialiser
     for K problems at once, D <= 64: one launch
     per function evaluation after lp_g and lp)   gsmvi/initializers.py:5-17
+    pathfinder_init_batched, PathfinderBatchedResult
+    (single-path Pathfinder for K problems, D <= 64:
+    the Gaussian along the L-BFGS path with the best
+    ELBO estimate; two launches per round more)  gsmvi/initializers.py:5-17 (the role; no reference twin)
     laplace_init_batched (the Newton mode and the
     inverse Hessian of K GLM posteriors, D <= 64:
     one launch per round, fp64-MFMA Gram product) gsmvi/initializers.py:5-17 (the role; no reference twin)
@@ -67,6 +71,7 @@ from .batched import ADVIBatch, Adam                                 # noqa: F40
 from .monitors import KLMonitor, DeviceKLMonitor, BatchedKLMonitor   # noqa: F401
 from .initializers import lbfgs_init, lbfgs_init_batched, LbfgsBatchedResult   # noqa: F401
 from .initializers import laplace_init_batched, LaplaceBatchedResult          # noqa: F401
+from .initializers import pathfinder_init_batched, PathfinderBatchedResult    # noqa: F401
 from .diagnostics import psis_batched, psis_weights_batched, PSISBatchedResult   # noqa: F401
 from .diagnostics import psis_loo_batched, LOOBatchedResult          # noqa: F401
 from .advi import ADVI                                               # noqa: F401

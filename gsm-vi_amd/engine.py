@@ -538,7 +538,7 @@ class HipEngine:
                  "batched_bam": 0x4000, "batched_kl": 0x8000, "batched_advi": 0x10000, "batched_target": 0x20000,
                  "batched_lbfgs": 0x40000, "batched_laplace": 0x80000, "batched_predict": 0x100000,
                  "batched_psis": 0x200000, "batched_loo": 0x400000, "gsm_two_launch": 0x800000,
-                 "batched_softmax": 0x1000000, "panel_chunk512": 0x2000000}
+                 "batched_softmax": 0x1000000, "panel_chunk512": 0x2000000, "batched_pathfinder": 0x4000000}
     PATH_GENERIC_MASK = 0x4 | 0x10 | 0x40 | 0x100 | 0x400 | 0x1000
 
     def last_path(self, reset=True):
@@ -934,6 +934,56 @@ class HipEngine:
                    self._packed(state["Y"], (K, 10, D), "Y"), self._ist(state, K),
                    self._packed(cov, (K, D, D), "cov"))
         return cov
+
+    # ---- batched Pathfinder initialiser: ELBO-selected Gaussians along the L-BFGS path (csrc/gsmvi_pathfinder_batched.hip) ------
+    pathfinder_max_draws = 4096
+
+    def pathfinder_state_batched(self, x0, M):
+        """The state of K Pathfinder selections over L-BFGS runs started at the rows of x0 (K, D), with M draws per path point:
+        a dict of device arrays seen (K) int32 = -1, fresh, info, npts (K) int32, mu (K, D), cov (K, D, D), X (K, M, D), logq,
+        elbo_last (K), and the best point so far: best_elbo (K) = -inf, best_mean (K, D) = x0, best_cov (K, D, D) = I,
+        best_it (K) int32 = -1"""
+        K, D = x0.shape
+        M = int(M)
+        assert 1 <= M <= self.pathfinder_max_draws, f"M = {M} is outside 1 <= M <= {self.pathfinder_max_draws}"
+        ints = lambda v: torch.full((K,), v, dtype=torch.int32, device=self.device)      # noqa: E731
+        return {"seen": ints(-1), "fresh": ints(0), "mu": self.zeros(K, D), "cov": self.zeros(K, D, D), "X": self.zeros(K, M, D),
+                "logq": self.zeros(K), "info": ints(0), "elbo_last": torch.full((K,), float("nan"), dtype=torch.float64,
+                                                                                device=self.device),
+                "best_elbo": torch.full((K,), float("-inf"), dtype=torch.float64, device=self.device),
+                "best_mean": self.asarray(x0).clone(memory_format=torch.contiguous_format), "best_cov": self.eye_batch(K, D),
+                "best_it": ints(-1), "npts": ints(0)}
+
+    def pathfinder_propose_batched(self, lbfgs_state, pf_state, seeds, h0=0.0):
+        """The first Pathfinder launch of a round, after ``lbfgs_step_batched``: for every problem whose L-BFGS run accepted a
+        point since its last proposal (``pf_state["fresh"]``), the Gaussian of the held pairs on the base ``h0`` I (0: the newest
+        pair's s.y / y.y) -> mu, cov, and M draws of draw number nit of the problem's stream -> X, logq; any other problem gets
+        its point in every row of X and a NaN logq  [the role of gsmvi/initializers.py:5-17]"""
+        K, M, D = pf_state["X"].shape
+        self._any_ctx()
+        st, pf = lbfgs_state, pf_state
+        assert isinstance(seeds, torch.Tensor) and seeds.is_cuda and seeds.dtype == torch.int64 and seeds.is_contiguous() \
+            and seeds.numel() == K, f"seeds: expected {K} keys from batched_seeds()"
+        self._call("gsmvi_pathfinder_propose_batched_f64", K, D, M, self._packed(st["x"], (K, D), "x"),
+                   self._packed(st["g"], (K, D), "g"), self._packed(st["S"], (K, 10, D), "S"),
+                   self._packed(st["Y"], (K, 10, D), "Y"), self._packed(st["sc"], (K, 24), "sc"), self._ist(st, K), _ptr(seeds),
+                   self._ints(pf["seen"], K, "seen"), float(h0), self._ints(pf["fresh"], K, "fresh"),
+                   self._packed(pf["mu"], (K, D), "mu"), self._packed(pf["cov"], (K, D, D), "cov"),
+                   self._packed(pf["X"], (K, M, D), "X"), self._packed(pf["logq"], (K,), "logq"), self._ints(pf["info"], K, "info"))
+
+    def pathfinder_select_batched(self, lpsum, lbfgs_state, pf_state):
+        """The second Pathfinder launch of a round, after lp of ``pf_state["X"]`` summed over the rows (``lpsum`` (K,)): the ELBO
+        estimate (lpsum - logq) / M of every fresh problem -> elbo_last, npts += fresh, and a finite estimate above best_elbo
+        (strictly: the first maximum wins) replaces best_elbo, best_mean, best_cov, best_it"""
+        K, M, D = pf_state["X"].shape
+        self._any_ctx()
+        pf = pf_state
+        self._call("gsmvi_pathfinder_select_batched_f64", K, D, M, self._packed(lpsum, (K,), "lpsum"),
+                   self._packed(pf["logq"], (K,), "logq"), self._ints(pf["fresh"], K, "fresh"), self._ints(pf["info"], K, "info"),
+                   self._ist(lbfgs_state, K), self._packed(pf["mu"], (K, D), "mu"), self._packed(pf["cov"], (K, D, D), "cov"),
+                   self._packed(pf["elbo_last"], (K,), "elbo_last"), self._ints(pf["npts"], K, "npts"),
+                   self._packed(pf["best_elbo"], (K,), "best_elbo"), self._packed(pf["best_mean"], (K, D), "best_mean"),
+                   self._packed(pf["best_cov"], (K, D, D), "best_cov"), self._ints(pf["best_it"], K, "best_it"))
 
     # ---- batched Laplace initialiser: Hessian, inverse and Newton rounds of the GLM targets (csrc/gsmvi_laplace_batched.hip) ----
     def _glm_model_args(self, A, y, family, offset, counts, prior_prec, noise_prec):

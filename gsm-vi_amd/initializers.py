@@ -10,6 +10,10 @@ one-element array instead of a scalar.
 plain L-BFGS with a backtracking line search in HIP (csrc/gsmvi_lbfgs_batched.hip), one launch per function evaluation after
 the score and ``lp``, whatever K is.
 
+``pathfinder_init_batched`` walks the same L-BFGS path and picks the start by how well it fits: every accepted iterate
+defines a Gaussian from the pairs held at that moment, a few draws estimate its ELBO, and the best is returned (single-path
+Pathfinder; csrc/gsmvi_pathfinder_batched.hip).  Any target with ``lp`` and ``lp_g``.
+
 ``laplace_init_batched`` is the second-order start for the built-in GLM targets (``BatchedGLMTarget``,
 ``BatchedLogisticTarget``): a damped Newton (IRLS) iteration in HIP (csrc/gsmvi_laplace_batched.hip), one launch per round, and
 the Laplace covariance (A^T W A + lam I)^-1 at the mode.
@@ -140,6 +144,124 @@ def lbfgs_init_batched(x0, lp, lp_g, maxiter=1000, maxfun=1000, *, gtol=1e-5, ft
                              nit=ist[:, 1].copy(), nfev=ist[:, 2].copy(), status=status.copy(), success=status == 1,
                              nlaunch=nlaunch)
     return (st["x"], cov, res) if as_torch else (res.x.copy(), eng.to_numpy(cov), res)
+
+
+@dataclass
+class PathfinderBatchedResult:
+    """What ``pathfinder_init_batched`` found, per problem (arrays of length K, or (K, D)).  The L-BFGS fields are those of
+    ``LbfgsBatchedResult``, bit for bit what ``lbfgs_init_batched`` reports with the same options: ``x``, ``fun``, ``jac``, ``nit``,
+    ``nfev``, ``status`` and the shared ``nlaunch``.  ``elbo`` is the best ELBO estimate along the path (-inf: no path point had
+    a finite one), ``best_it`` the L-BFGS iteration whose Gaussian was returned (0: the start point; -1: none), ``n_points`` the
+    path points that were tried, ``success`` = ``best_it >= 0``.  ``nevals`` = ``nlaunch`` (1 + M) is shared: every round
+    evaluates ``lp`` at the trial point and at the M draws of every problem, so it is the ``offset_evals`` of a
+    ``BatchedKLMonitor`` that follows the fits."""
+    x: np.ndarray
+    fun: np.ndarray
+    jac: np.ndarray
+    nit: np.ndarray
+    nfev: np.ndarray
+    status: np.ndarray
+    success: np.ndarray
+    nlaunch: int
+    elbo: np.ndarray
+    best_it: np.ndarray
+    n_points: np.ndarray
+    nevals: int
+
+
+def pathfinder_init_batched(x0, lp, lp_g, maxiter=1000, maxfun=1000, *, num_elbo_draws=5, h0="pair", seed=0, gtol=1e-5,
+                            ftol=2.220446049250313e-09, check_every=8, as_torch=False, engine=None):
+    """Single-path Pathfinder (Zhang, Carpenter, Gelman, Vehtari 2022) for K problems of one D at once: returns ``(mean (K, D),
+    cov (K, D, D), res)``, the Gaussian along the L-BFGS path of ``lbfgs_init_batched`` with the best ELBO estimate and a
+    ``PathfinderBatchedResult``.  It fills the role of ``lbfgs_init`` (gsmvi/initializers.py:5-17) with a start that is chosen by
+    how well it fits, for any target with ``lp`` and ``lp_g``.
+
+    ``x0``, ``lp``, ``lp_g``, ``maxiter``, ``maxfun``, ``gtol``, ``ftol``, ``check_every``: as in ``lbfgs_init_batched``; the
+    L-BFGS trajectory is the same, bit for bit.  Every accepted iterate x (the start point included) defines N(mu, Sigma):
+    Sigma = the BFGS inverse-Hessian product of the pairs held at that moment on the base gamma I, mu = x + Sigma score(x).
+    ``h0`` = "pair": gamma = s.y / y.y of the newest pair, the scale the two-loop recursion uses (1 before the first pair); a
+    positive float fixes gamma (1.0 gives ``lbfgs_init_batched``'s covariance at every point).  The paper's diagonal base alpha
+    is replaced by gamma I: a stated simplification.  ``num_elbo_draws`` = M in 1 .. 4096 draws per path
+    point, from the counter-based stream of key ``engine.batched_seeds``(seed + k) and draw number = the iteration, estimate
+    ELBO = mean(lp(x_s) - log q(x_s)); the first maximum over the path wins.  A round is six launches against
+    ``lbfgs_init_batched``'s three: score and lp at the trial points, the L-BFGS step, the proposal, lp at the (K, M, D) draws,
+    the selection.  A problem whose path has no finite ELBO keeps its last x, the identity covariance and ``elbo`` = -inf
+    (what ``laplace_init_batched`` does for a lost problem).  The result does not depend on ``check_every``; only ``res.nlaunch``
+    and ``res.nevals`` do.  Prints nothing."""
+    from ._fitloop import scorer, takes_out
+    from .batched import MAX_D
+    from .monitors import lp_sums
+    if lp is None or lp_g is None:
+        raise ValueError("pathfinder_init_batched: lp and lp_g are both required (no numerical gradient)")
+    if not hasattr(x0, "shape"):
+        x0 = np.asarray(x0, dtype=np.float64)
+    shape = tuple(int(n) for n in x0.shape)
+    if len(shape) == 1:                                 # one start for every problem of the target that owns lp
+        shape = (int(getattr(getattr(lp, "__self__", None), "K", 1)),) + shape
+    elif len(shape) != 2:
+        raise ValueError(f"pathfinder_init_batched: x0 must be (K, D) or (D,), got {tuple(x0.shape)}")
+    K, D = shape
+    if not 1 <= D <= MAX_D:
+        raise ValueError(f"pathfinder_init_batched: D = {D} is outside 1 <= D <= {MAX_D}")
+    if K < 1:
+        raise ValueError(f"pathfinder_init_batched: K = {K} must be at least 1")
+    maxiter, maxfun, check_every = int(maxiter), int(maxfun), int(check_every)
+    if maxiter < 1 or maxfun < 2 or check_every < 1:
+        raise ValueError("pathfinder_init_batched: maxiter and check_every must be at least 1, maxfun at least 2")
+    if not (gtol >= 0.0 and ftol >= 0.0):
+        raise ValueError("pathfinder_init_batched: gtol and ftol must be >= 0")
+    M = int(num_elbo_draws)
+    if M != num_elbo_draws or not 1 <= M <= 4096:
+        raise ValueError(f"pathfinder_init_batched: num_elbo_draws = {num_elbo_draws} is outside 1 <= num_elbo_draws <= 4096")
+    if isinstance(h0, str):
+        if h0 != "pair":
+            raise ValueError(f"pathfinder_init_batched: h0 must be \"pair\" or a positive float, got {h0!r}")
+        base = 0.0
+    else:
+        base = float(h0)
+        if not (base > 0.0 and base < float("inf")):
+            raise ValueError(f"pathfinder_init_batched: h0 must be \"pair\" or a positive float, got {h0!r}")
+    if engine is None:
+        from .engine import get_engine
+        engine = get_engine()
+    eng = engine
+    x0 = eng.asarray(x0)
+    x0 = x0.reshape(K, D) if len(x0.shape) == 2 else (x0.expand(K, D) if hasattr(x0, "expand") else np.broadcast_to(x0, (K, D)))
+    st = eng.lbfgs_state_batched(x0)
+    pf = eng.pathfinder_state_batched(st["x"], M)
+    seeds = eng.batched_seeds([int(seed) + k for k in range(K)])
+    Xt = st["Xt"].reshape(K, 1, D)                      # the trial points where the callables read them (a view)
+    score = scorer(eng, lp_g)
+    Gbuf = eng.empty(K, 1, D) if not getattr(lp_g, "device_native", False) or takes_out(lp_g) else None
+    packed = lambda v: v.contiguous() if hasattr(v, "contiguous") else np.ascontiguousarray(v)      # noqa: E731
+    nlaunch = 0
+    for r in range(1, maxfun + 1):
+        G = score(Xt, out=Gbuf) if Gbuf is not None else score(Xt)
+        v = lp_sums(lp, Xt, eng, K)
+        eng.lbfgs_step_batched(packed(v), G.reshape(K, D), st, start=r == 1, sign=-1.0, maxiter=maxiter, maxfun=maxfun,
+                               gtol=gtol, ftol=ftol)
+        eng.pathfinder_propose_batched(st, pf, seeds, h0=base)
+        eng.pathfinder_select_batched(packed(lp_sums(lp, pf["X"], eng, K)), st, pf)
+        nlaunch = r
+        if r % check_every == 0 and eng.read_flag(st["stopped"]) == K:
+            break
+    ist = eng.read_ints(st["ist"])
+    status = ist[:, 0]
+    best_it = eng.read_ints(pf["best_it"])
+    mean, cov = pf["best_mean"], pf["best_cov"]
+    lost = np.flatnonzero(best_it < 0)
+    if lost.size:                                       # no finite ELBO on the path: the last x (the covariance is still I)
+        if isinstance(mean, np.ndarray):
+            mean[lost] = st["x"][lost]
+        else:
+            import torch
+            idx = torch.as_tensor(lost, device=mean.device)
+            mean[idx] = st["x"][idx]
+    res = PathfinderBatchedResult(x=eng.to_numpy(st["x"]), fun=eng.to_numpy(st["sc"][:, 0]).copy(), jac=eng.to_numpy(st["g"]),
+                                  nit=ist[:, 1].copy(), nfev=ist[:, 2].copy(), status=status.copy(), success=best_it >= 0,
+                                  nlaunch=nlaunch, elbo=eng.to_numpy(pf["best_elbo"]).copy(), best_it=best_it.copy(),
+                                  n_points=eng.read_ints(pf["npts"]).copy(), nevals=nlaunch * (1 + M))
+    return (mean, cov, res) if as_torch else (eng.to_numpy(mean).copy(), eng.to_numpy(cov).copy(), res)
 
 
 @dataclass

@@ -25,6 +25,7 @@
  *   examples/example_gsm.py:34-35 the same for K multinomial logit (softmax) regressions of C classes -> gsmvi_softmax_batched_f64
  *   initializers.py:5-17 lbfgs_init (maximiser of lp, dense inverse-Hessian estimate), K problems -> gsmvi_lbfgs_step_batched_f64, gsmvi_lbfgs_hess_inv_batched_f64
  *   initializers.py:5-17 the same role by Newton rounds on the GLMs of examples/example_gsm.py:34-35 (no reference twin) -> gsmvi_glm_hessian_batched_f64, gsmvi_laplace_step_batched_f64
+ *   initializers.py:5-17 the same role with a start picked by its ELBO along the L-BFGS path (Pathfinder; no reference twin) -> gsmvi_pathfinder_propose_batched_f64, gsmvi_pathfinder_select_batched_f64
  *   examples/example_gsm.py:34-35 the use of the fit: predictions and the held-out score of K fitted GLMs (no reference twin) -> gsmvi_glm_predict_batched_f64
  *   monitors.py:83-125 the role (is q_k close to its target?), per problem and comparable across problems: the Pareto-smoothed
  *   importance diagnostic of K fitted Gaussians (no reference twin)    ->  gsmvi_psis_batched_f64, gsmvi_psis_weights_batched_f64
@@ -290,6 +291,7 @@ int gsmvi_get_profile(gsmvi_ctx* ctx, float* ms, int n);
 #define GSMVI_PATH_GSM_TWO_LAUNCH 0x800000u /* the dense GSM update ran as two launches (no k_gsm_scalars_fast, no records)          */
 #define GSMVI_PATH_BATCHED_SOFTMAX 0x1000000u /* k_softmax_batched: the batched multinomial logit target's entry point            */
 #define GSMVI_PATH_PANEL_CHUNK512 0x2000000u /* the two-launch product ran as two slabs of one 512-row chunk each (D = 1024, no explicit "panel_kc") */
+#define GSMVI_PATH_BATCHED_PATHFINDER 0x4000000u /* k_pf_propose / k_pf_select: the batched Pathfinder initialiser                  */
 #define GSMVI_PATH_GENERIC_MASK (0x0004u | 0x0010u | 0x0040u | 0x0100u | 0x0400u | 0x1000u)
 int gsmvi_last_path(gsmvi_ctx* ctx, unsigned* bits, int reset);
 
@@ -578,6 +580,42 @@ int gsmvi_lbfgs_step_batched_f64(gsmvi_ctx* ctx, void* stream, int64_t K, int D,
                                  double* Xt, int* stopped_dev, int maxiter, int maxfun, double gtol, double ftol);
 int gsmvi_lbfgs_hess_inv_batched_f64(gsmvi_ctx* ctx, void* stream, int64_t K, int D, const double* S, const double* Y,
                                      const int* ist, double* cov);
+
+/*
+ * Batched Pathfinder initialiser, single-path form (Zhang, Carpenter, Gelman, Vehtari 2022): the role of gsmvi/initializers.py:5-17
+ * (a mean and a covariance to start a fit from) with a start that is picked by how well it fits.  Every accepted iterate of the
+ * batched L-BFGS above defines a Gaussian from the pairs held at that moment; M draws estimate its ELBO; the best is kept.  Two
+ * launches per L-BFGS round, one before and one after the caller's lp of the draws.  1 <= D <= 64, 1 <= M <= 4096, K >= 1 with the
+ * grid limits of the batched GSM above.  All arrays packed, in device memory.
+ * gsmvi_pathfinder_propose_batched_f64 reads the L-BFGS state (x, g, S, Y, sc, ist as laid out above), seeds (K stream keys) and
+ * seen (K ints; the caller starts them at -1, so the start point is path point 0).  Per problem: fresh[k] = (ist[1] = nit != seen[k]),
+ * then seen[k] <- nit.  Not fresh (a rejected trial, a frozen problem): the M rows of X_k <- x_k (so that the lp that follows reads
+ * defined memory), logq_sum[k] <- NaN, and nothing else of problem k is written.  Fresh: gamma = h0 if h0 > 0, else s.y / y.y of
+ * the newest held pair (sc[4 + i] / sc[14 + i], i = head - 1 mod 10; 1 with no pair held); Sigma = H after H_0 = gamma I and, over
+ * the held pairs from oldest to newest with rho = 1 / s.y, H <- (I - rho s y^T) H (I - rho y s^T) + rho s s^T -- the recursion of
+ * gsmvi_lbfgs_hess_inv_batched_f64 in the same operations (h0 = 1 gives its bits), exactly symmetric; mu = x - Sigma g (g is the
+ * gradient of phi = -lp, as the state holds it); R = chol(Sigma), upper; z = the rows 0 .. M - 1 of draw `call` = nit of the problem's
+ * stream in the plain layout of gsmvi_kl_draw_batched_f64 (element s D + j, pair (s D + j) / 2, no odd-D padding); X_k row s = mu +
+ * z_s R; logq_sum[k] = sum_s (-|z_s|^2 / 2 - sum_i log R_ii - D / 2 log 2 pi); mu (K x D), cov (K x D x D) = Sigma and info[k] = 0,
+ * or 1 + the first pivot that is not > 0 and finite, are written.  A bad pivot or a mean that is not finite (a non-finite gradient)
+ * gives NaN rows and a NaN logq_sum[k]; no other problem is touched.  The base gamma I in place of the paper's diagonal alpha is a
+ * stated simplification.
+ * gsmvi_pathfinder_select_batched_f64: e = (lpsum[k] - logq_sum[k]) / M for fresh[k] != 0 and info[k] = 0, NaN otherwise;
+ * elbo_last[k] = e; npts[k] += (fresh[k] != 0); e finite and e > best_elbo[k] (strict: the first maximum wins) -> best_elbo[k] = e,
+ * best_mean_k = mu_k, best_cov_k = cov_k, best_it[k] = ist[1]; otherwise nothing of the problem's best state is written.
+ * Both: every sum runs in an order fixed by (D, M) alone, so a problem's bits depend neither on K nor on its neighbours.  Shapes,
+ * NULL arrays and overlaps (a written array may overlap no other array of the call) are checked before the context is looked at
+ * (then a NULL ctx); every failure returns GSMVI_ERR_BAD_ARG before anything is enqueued.  No context workspace is used; one
+ * capturable launch each.  Sets GSMVI_PATH_BATCHED_PATHFINDER.
+ */
+int gsmvi_pathfinder_propose_batched_f64(gsmvi_ctx* ctx, void* stream, int64_t K, int D, int64_t M, const double* x,
+                                         const double* g, const double* S, const double* Y, const double* sc, const int* ist,
+                                         const uint64_t* seeds, int* seen, double h0, int* fresh, double* mu, double* cov,
+                                         double* X, double* logq_sum, int* info);
+int gsmvi_pathfinder_select_batched_f64(gsmvi_ctx* ctx, void* stream, int64_t K, int D, int64_t M, const double* lpsum,
+                                        const double* logq_sum, const int* fresh, const int* info, const int* ist, const double* mu,
+                                        const double* cov, double* elbo_last, int* npts, double* best_elbo, double* best_mean,
+                                        double* best_cov, int* best_it);
 
 /*
  * Batched Laplace initialiser: the Newton mode of K GLM posteriors of one (N, D) and the inverse of the negative Hessian there

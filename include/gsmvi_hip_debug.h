@@ -59,6 +59,10 @@ int gsmvi_debug_softmax_batched_lds(int C, int P, int nc, int want, size_t* byte
  * arithmetic only, no device needed. */
 int gsmvi_debug_lbfgs_batched_lds(int D, int mode, size_t* bytes, int* problems_per_workgroup);
 
+/* The same for a gsmvi_pathfinder_propose_batched_f64 launch at D, and the rows of draws one tile holds (whatever M is).  Host
+ * arithmetic only, no device needed. */
+int gsmvi_debug_pathfinder_batched_lds(int D, size_t* bytes, int* problems_per_workgroup, int* tile_rows);
+
 #pragma GCC visibility pop
 #ifdef __cplusplus
 }
