@@ -47,9 +47,11 @@ bool gsmvi_launch_gsm_cov_sym(hipStream_t st, hipEvent_t* ev, int D, int B, cons
                               int dbg, unsigned long long* stamps, int num_cu);
 void gsmvi_launch_panel_fast_part(hipStream_t st, hipEvent_t* ev, dim3 grid, int D, int B, const double* G, int ldg,
                                   const double* S0, int lds0, double* Pp, int chunks_per_wg, const double* X, int ldx,
-                                  const double* mu0, double* Qg, double* Qm, int chw);
+                                  const double* mu0, double* Qg, double* Qm, int chw, unsigned long long* stamps);
 void gsmvi_launch_gsm_cov_sym_slabs(hipStream_t st, hipEvent_t* ev, int D, int B, const struct gsm_slab_src& fs, const double* mu0,
-                                    const double* S0, int lds0, double* S, int lds, double* mu_out, int kct);
+                                    const double* S0, int lds0, double* S, int lds, double* mu_out, int kct, bool fold,
+                                    unsigned long long* stamps);
+int gsmvi_cov_sym_pairs(int nt);
 int gsmvi_panel_fast_chunk(int MT);
 int gsmvi_potrf_impl(struct gsmvi_ctx* ctx, hipStream_t st, int D, const double* S, int lds, double* R, int ldr,
                      int* info_dev);
@@ -320,6 +322,7 @@ int gsmvi_set_tuning(gsmvi_ctx* ctx, const char* name, int value) {
     else if (!strcmp(name, "bam_basis")) ctx->tune_bam_basis = value;
     else if (!strcmp(name, "scalars_nt")) ctx->tune_scalars_nt = value;
     else if (!strcmp(name, "gsm_two_launch")) ctx->tune_gsm_two_launch = value;
+    else if (!strcmp(name, "cov_fold_diag")) ctx->tune_cov_fold_diag = value;
     else if (!strcmp(name, "cov_dbg")) ctx->tune_cov_dbg = value;   // ablation bits, timing experiments only
     else if (!strcmp(name, "timeline")) {                           // whole-update timeline stamps (diagnostic)
         if (value && !ctx->stamps) {
@@ -634,14 +637,14 @@ static int gsm_records(gsmvi_ctx* ctx, hipStream_t hs, int D, int B, int kc, con
 // The dense update in TWO launches (no per-sample launch, no records): the product launch leaves partial dots beside its
 // slabs, the covariance launch forms its factor tiles from samples, slabs and partials (gsmvi_fast.hip: k_panel_fast<.., PART>,
 // k_gsm_cov_sym<.., FROM_SLABS>).  One gated shape family; *cpw_out, *kc_out = the product's split (gsmvi_panel_split_k, as
-// gsmvi_panel_product_nc takes it).  The diagnostics that stamp or ablate the three kernels keep the three launches.
+// gsmvi_panel_product_nc takes it).  The diagnostic that ablates the three kernels ("cov_dbg") keeps the three launches.
 // *chw_out = rows per chunk of the product.  Round 8: D = 1024 (four 256-row chunks) with no explicit "panel_kc" runs as TWO
 // slabs of one 512-row chunk each -- half the slabs and half the Qg partials that every covariance workgroup re-reads; an
 // explicit "panel_kc" keeps 256-row chunks with that split (panel_kc=4: the round-7 route, for A/B runs in one process).
 static bool gsm_two_launch_gate(const gsmvi_ctx* ctx, int D, int B, const double* X, int ldx, const double* G, int ldg,
                                 const double* mu0, const double* S0, int lds0, const double* S, int lds, int* cpw_out,
                                 int* kc_out, int* chw_out) {
-    if (!ctx->tune_gsm_two_launch || ctx->tune_no_fast || ctx->tune_timeline || ctx->tune_cov_dbg) return false;
+    if (!ctx->tune_gsm_two_launch || ctx->tune_no_fast || ctx->tune_cov_dbg) return false;   // (round 9: "timeline" stamps this route too)
     if (B != 16 && B != 32) return false;
     if (D % 256 != 0 || D > 1024) return false;
     if (ldx % 2 != 0 || ldg % 2 != 0 || lds0 % 2 != 0 || lds % 2 != 0) return false;
@@ -671,7 +674,8 @@ static int gsm_two_launch(gsmvi_ctx* ctx, hipStream_t hs, int D, int B, int cpw,
     hipEvent_t* ev0 = ctx->stage_events(0);
     ctx->ev_valid[1] = 0;                                       // no per-sample launch: gsmvi_get_profile reports -1 for it
     // (512-row chunks: one workgroup per (strip, slab, 16 samples) -- the launcher's comment in gsmvi_fast.hip)
-    gsmvi_launch_panel_fast_part(hs, ev0, dim3(strips, kc, chw == 512 ? B / 16 : 1), D, B, G, ldg, S0, lds0, ctx->pp, cpw, X, ldx, mu0, Qg, Qm, chw);
+    gsmvi_launch_panel_fast_part(hs, ev0, dim3(strips, kc, chw == 512 ? B / 16 : 1), D, B, G, ldg, S0, lds0, ctx->pp, cpw, X, ldx, mu0, Qg, Qm, chw,
+                                 ctx->timeline_stamps(0));
     ctx->path |= GSMVI_PATH_PANEL_FAST | (chw == 512 ? GSMVI_PATH_PANEL_CHUNK512 : 0u);
     int st = check_launch("k_panel_fast(partials)");
     if (st != GSMVI_OK) return st;
@@ -683,8 +687,12 @@ static int gsm_two_launch(gsmvi_ctx* ctx, hipStream_t hs, int D, int B, int cpw,
     fs.Qm = Qm;
     fs.KC = kc;
     fs.strips = strips;
-    gsmvi_launch_gsm_cov_sym_slabs(hs, ctx->stage_events(2), D, B, fs, mu0, S0, lds0, S, lds, mu, chw == 512 ? 2 : 4);
-    ctx->path |= GSMVI_PATH_COV_SYM | GSMVI_PATH_GSM_TWO_LAUNCH;
+    // round 9: the diagonal leftover tiles ride in two-tile workgroups where those alone fill the device (D = 1024 on 256 CUs);
+    // with fewer workgroups than CUs a leftover is better off as a workgroup of its own on an idle CU ("cov_fold_diag" = 2: always)
+    const bool fold = ctx->tune_cov_fold_diag >= 2 || (ctx->tune_cov_fold_diag == 1 && gsmvi_cov_sym_pairs(D / 32) >= ctx->num_cu);
+    gsmvi_launch_gsm_cov_sym_slabs(hs, ctx->stage_events(2), D, B, fs, mu0, S0, lds0, S, lds, mu, chw == 512 ? 2 : 4, fold,
+                                   ctx->timeline_stamps(2));
+    ctx->path |= GSMVI_PATH_COV_SYM | GSMVI_PATH_GSM_TWO_LAUNCH | (fold ? GSMVI_PATH_COV_FOLD_DIAG : 0u);
     return check_launch("k_gsm_cov_sym(slabs)");
 }
 

@@ -116,6 +116,8 @@ struct gsmvi_ctx {
                                // count is 1 (no hand-off involved); 0 = always product + k_panel_finish (A/B tests)
     int tune_scalars_nt = 0;   // threads per sample in k_gsm_scalars_fast (256/512/1024; 0 = default)
     int tune_no_fast = 0;      // 1 = force the guarded generic kernels (tests)
+    int tune_cov_fold_diag = 1;    // two-launch form: the diagonal leftover tiles of k_gsm_cov_sym<.., FROM_SLABS> as third tiles of two-tile workgroups
+                                   // (0: workgroups of their own, the grid as it was; 1: where the two-tile workgroups fill the device; 2: always)
     int tune_gsm_two_launch = 1;   // dense GSM update at B in {16, 32}, D % 256 == 0, D <= 1024 without the per-sample launch (0: three launches; A/B runs)
     int* bam_hint_host = nullptr;       // pinned word: k* of the last device BaM chain (step-count hint, never synchronised on)
     int tune_bam_kenq = 0;     // > 0: enqueue exactly this many multi-workgroup steps (tests of the tail kernel)

@@ -487,13 +487,23 @@ __global__ __launch_bounds__(NT) void k_gsm_scalars_fast(int D, int B, int KC, c
 // slabs and partials are clamped re-reads).  2 serves the 512-row split of D = 1024 (k_panel_fast<.., 512, .., PART>: exactly two
 // slabs, 128 Qg and 64 Qm partials per sample): 4 + 2 units of partials and two slab units per column block are 20 units per
 // thread, so ALL loads go out in one batch and both slabs exist.  Same unit order in the sums, slabs added as p0 + p1.
-template <int SB, bool RAG, bool FROM_SLABS = false, int KCT = 4>
+// FOLD (round 9; FROM_SLABS only) = the grid is the n_two two-tile workgroups alone (256 at D = 1024: one per CU, nothing shares a
+// CU).  The diagonal tile (r, r) of a row r with an odd tile count, which used to be a workgroup of its own, is a THIRD tile of a
+// workgroup that has staged block r anyway:
+//   rows with >= 3 tiles: the first pair workgroup of row r, tiles (r, r + 1), (r, r + 2) -- both operands are its staged I tiles;
+//   the last row (1 tile): the pair workgroup of row nt - 2, tiles (nt - 2, nt - 2), (nt - 2, nt - 1) -- both are its staged J1 tiles.
+// The host adds one S0 unit per thread (the 32 x 32 tile is 512 units), four 16 x 16 MFMA blocks on waves 0-3 (chains as in a
+// diagonal workgroup: the same staged values in the same order), a third LW buffer behind the two (inside the LDS it has), one
+// 8 KB store without a mirror behind the mirror stores, and mu of block r from the dmu units it staged that block from, in the
+// two-level order of the diagonal workgroups, on the barriers the store path has anyway.
+template <int SB, bool RAG, bool FROM_SLABS = false, int KCT = 4, bool FOLD = false>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(FROM_SLABS ? 4 : 2))) void k_gsm_cov_sym(int D, int B, double invB, const double* __restrict__ rec, int ldrec,
                                                      const double* __restrict__ mu0,
                                                      const double* __restrict__ S0, int lds0,
                                                      double* __restrict__ S, int lds,
                                                      double* __restrict__ mu_out, int dbg,
                                                      unsigned long long* __restrict__ stamps, gsm_slab_src fs) {
+    static_assert(!FOLD || FROM_SLABS, "folded diagonal tiles: the two-launch form only");
 #define STAMP(k)                                                                          \
     do {                                                                                  \
         if (stamps && threadIdx.x == 0) stamps[(size_t)blockIdx.x * 8 + (k)] = __builtin_amdgcn_s_memrealtime(); \
@@ -522,7 +532,8 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(FROM_SLABS 
     const int n_two = ((nt >> 1) * ((nt + 1) >> 1));             // sum_m floor(m/2), m = 1..nt   // and store only what lies inside
     int ti, tj0;
     bool two;
-    if ((int)blockIdx.x < n_two) {
+    int fold = 0;                                                // FOLD: 1 = hosts the diagonal tile of its own row, 2 = that of the last row
+    if (FOLD || (int)blockIdx.x < n_two) {
         int rem = blockIdx.x;
         ti = 0;
         for (;;) {
@@ -533,6 +544,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(FROM_SLABS 
         }
         tj0 = ti + ((nt - ti) & 1) + 2 * rem;                    // odd tile count: the pairs start right of the diagonal tile
         two = true;
+        if constexpr (FOLD) fold = (((nt - ti) & 1) && rem == 0) ? 1 : (ti == nt - 2 ? 2 : 0);   // block-uniform
     } else {
         const int k = blockIdx.x - n_two;                        // k-th row with an odd tile count: its DIAGONAL tile (no
         ti = ((nt & 1) ? 0 : 1) + 2 * k;                         // mirror store, so the late single-tile workgroups are light)
@@ -558,10 +570,16 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(FROM_SLABS 
         const int gr = (RAG && I0 + i >= D) ? D - 1 : I0 + i, gc = (RAG && Jt + 2 * j2 >= D) ? D - 2 : Jt + 2 * j2;
         s0v[q] = (dbg & 2) ? (v2d){1.0, 1.0} : *reinterpret_cast<const v2d*>(S0 + (size_t)gr * lds0 + gc);
     }
+    const int X0 = (fold == 2) ? J0 + 32 : I0;   // FOLD: the folded diagonal tile is S[X0 .. X0 + 31][X0 .. X0 + 31], unit = tid
+    v2d s0x = {0.0, 0.0};
+    if constexpr (FOLD) {
+        if (fold) s0x = *reinterpret_cast<const v2d*>(S0 + (size_t)(X0 + (tid >> 4)) * lds0 + X0 + 2 * (tid & 15));
+    }
     __builtin_amdgcn_sched_barrier(0);           // keep the HBM loads of S0 ahead of the L2-resident staging loads
     v2d stg[UPT];
     double dmu_part = 0.0;
     v2d dmuI = {0.0, 0.0};                       // FROM_SLABS: dmu of this thread's unit of block I (the mean, diagonal workgroups)
+    v2d dmuX = {0.0, 0.0};                       // FOLD: the same of the folded tile's block (I, or J1 for the last row)
     if constexpr (FROM_SLABS) {
         static_assert(!RAG && NPASS == 1 && 512 % NU == 0, "two-launch form: B == SB in {16, 32}, on the grid");
         static_assert(KCT == 2 || KCT == 4, "slab count of the two-launch form");
@@ -618,12 +636,19 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(FROM_SLABS 
         const double gSg = row16_sum(gs), mv = row16_sum(ms);
         const double rho = 0.5 * sqrt(1.0 + 4.0 * (gSg + mv * mv)) - 0.5;
         const double den = 1.0 + rho + mv;
-        const double beta = 1.0 / (1.0 + rho), c = (gSg - mv) / den;
+        double beta = 1.0 / (1.0 + rho), c = (gSg - mv) / den;
         if (stamps) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); STAMP(1); }
 #pragma unroll
         for (int cb = 0; cb < 3; ++cb)
             if (cb < 2 || two) {
                 v2d sg = {0.0, 0.0}, dd, dm, ee;
+                // (round 9) the square root and the two divisions need the partials only, which come back first: the empty asm makes
+                // every slab, X and mu0 unit pass through a statement that takes beta and c, so that no slab add -- and with it the
+                // wait for all 20 units -- can be scheduled in front of that chain (it was); block by block, in staging order
+                if constexpr (KCT == 2) {
+                    if (cb == 0) asm volatile("" : "+v"(beta), "+v"(c), "+v"(xv[0]), "+v"(m0[0]), "+v"(sl[0][0]), "+v"(sl[0][1]));
+                    else asm volatile("" : "+v"(xv[cb]), "+v"(m0[cb]), "+v"(sl[cb][0]), "+v"(sl[cb][1]));
+                }
                 if constexpr (KCT == 2) {
                     sg.x = sl[cb][0].x + sl[cb][1].x;
                     sg.y = sl[cb][0].y + sl[cb][1].y;
@@ -643,6 +668,9 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(FROM_SLABS 
                 if (st_d) *reinterpret_cast<v2d*>(smem + (2 * cb) * TILE + b * RS + c2) = dd;
                 if (st_e) *reinterpret_cast<v2d*>(smem + (2 * cb + 1) * TILE + b * RS + c2) = ee;
                 if (cb == 0) dmuI = dm;
+                if constexpr (FOLD) {
+                    if (cb == (fold == 2 ? 2 : 0)) dmuX = dm;
+                }
             }
     } else {
 #pragma unroll
@@ -678,6 +706,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(FROM_SLABS 
     // chain 0 = d-part, chain 1 = e-part; operands go to registers first so the chains issue back to back.
     constexpr int NS = SBP / 4;
     v4d accd = {0.0, 0.0, 0.0, 0.0}, acce = {0.0, 0.0, 0.0, 0.0};
+    v4d xaccd = {0.0, 0.0, 0.0, 0.0}, xacce = {0.0, 0.0, 0.0, 0.0};   // FOLD: the folded tile's chains
 #pragma unroll
     for (int pass = 0; pass < NPASS; ++pass) {
         if (pass > 0) __syncthreads();           // the previous pass's operand reads are done
@@ -714,6 +743,25 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(FROM_SLABS 
                 acce = GSMVI_MFMA_F64(ae[s], be[s], acce);
             }
         }
+        if constexpr (FOLD) {                    // the folded diagonal tile: block (wr, wc) on wave w < 4, both operands from block X,
+            if (fold && t == 0) {                // (wave-uniform) behind the wave's own block, in the registers that one has freed.
+                // (Reading these operands between the MFMA steps of tile 0 let the compiler interleave all four chains: 128 VGPRs
+                // and 68 B of scratch; one tile after the other keeps 97 VGPRs and no scratch.)
+                const double* xdp = smem + (fold == 2 ? 4 : 0) * TILE + ks * RS + c;
+#pragma unroll
+                for (int s = 0; s < NS; ++s) {
+                    ad[s] = xdp[4 * s * RS + 16 * wr];
+                    ae[s] = xdp[TILE + 4 * s * RS + 16 * wr];
+                    bd[s] = xdp[4 * s * RS + 16 * wc];
+                    be[s] = xdp[TILE + 4 * s * RS + 16 * wc];
+                }
+#pragma unroll
+                for (int s = 0; s < NS; ++s) {
+                    xaccd = GSMVI_MFMA_F64(ad[s], bd[s], xaccd);
+                    xacce = GSMVI_MFMA_F64(ae[s], be[s], xacce);
+                }
+            }
+        }
     }
     // ---- stores through LDS, 16 B per lane: the update tile U_t = (D_I^T D_J - E_I^T E_J)/B goes to LDS in accumulator
     // layout; W_t = S0[I, J_t] + U_t is formed in store layout (row segments of 256 B), stored, written back to LDS, and
@@ -724,8 +772,28 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(FROM_SLABS 
 #pragma unroll
         for (int r = 0; r < 4; ++r) LW[(16 * wr + ks + 4 * r) * 33 + 16 * wc + c] = (accd[r] - acce[r]) * invB;
     }
+    // FOLD: the folded tile's update goes behind the two, [3][32 x 33], and the dmu tile of its block behind that -- both inside
+    // the staged tiles' LDS and outside everything the two tiles use below, so the folded tile's mean rides on the barriers that
+    // are here anyway (two-level order of the record form, as for block I below) and its store goes out last, behind the mirror
+    constexpr int LXO = 2 * 32 * 33, MUO = 3 * 32 * 33;
+    if constexpr (FOLD) {
+        static_assert(!FOLD || MUO + SB * 32 + 256 <= 6 * TILE, "third LW buffer and the dmu tile inside the staged tiles");
+        if (fold && t == 0) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) smem[LXO + (16 * wr + ks + 4 * r) * 33 + 16 * wc + c] = (xaccd[r] - xacce[r]) * invB;
+        }
+        if (fold && tid < NU) *reinterpret_cast<v2d*>(smem + MUO + (tid >> 4) * 32 + 2 * (tid & 15)) = dmuX;
+    }
     if (stamps) STAMP(3);
     __syncthreads();
+    if constexpr (FOLD) {
+        if (fold && tid < 256) {
+            double part = 0.0;
+#pragma unroll
+            for (int k = 0; k < SB / 8; ++k) part += smem[MUO + ((tid >> 5) + 8 * k) * 32 + (tid & 31)];
+            smem[MUO + SB * 32 + tid] = part;    // [8][32] behind the tile
+        }
+    }
     if (mine) {
 #pragma unroll
         for (int q = 0; q < 2; ++q) {
@@ -749,6 +817,22 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(FROM_SLABS 
             m2.x = LW[(2 * i2) * 33 + j];
             m2.y = LW[(2 * i2 + 1) * 33 + j];
             if (!RAG || (Jt + j < D && I0 + 2 * i2 < D)) *reinterpret_cast<v2d*>(S + (size_t)(Jt + j) * lds + I0 + 2 * i2) = m2;
+        }
+    }
+    if constexpr (FOLD) {
+        if (fold) {
+            if (tid < 32) {
+                double s = 0.0;
+#pragma unroll
+                for (int q = 0; q < 8; ++q) s += smem[MUO + SB * 32 + q * 32 + tid];
+                mu_out[X0 + tid] = mu0[X0 + tid] + s * invB;
+            }
+            // W = S0 + U in store layout, one unit per thread; a diagonal tile has no mirror
+            const int i = tid >> 4, j2 = tid & 15;
+            v2d wv2;
+            wv2.x = s0x.x + smem[LXO + i * 33 + 2 * j2];
+            wv2.y = s0x.y + smem[LXO + i * 33 + 2 * j2 + 1];
+            *reinterpret_cast<v2d*>(S + (size_t)(X0 + i) * lds + X0 + 2 * j2) = wv2;
         }
     }
     if (diag) {
@@ -1202,7 +1286,7 @@ void gsmvi_launch_panel_fast(hipStream_t st, hipEvent_t* ev, int MT, dim3 grid, 
 // the MT = 2 form on 128 workgroups staged 128 KB per workgroup and was 2 us slower per launch).
 void gsmvi_launch_panel_fast_part(hipStream_t st, hipEvent_t* ev, dim3 grid, int D, int B, const double* G, int ldg,
                                   const double* S0, int lds0, double* Pp, int chunks_per_wg, const double* X, int ldx,
-                                  const double* mu0, double* Qg, double* Qm, int chw) {
+                                  const double* mu0, double* Qg, double* Qm, int chw, unsigned long long* stamps) {
     gsmvi_panel_extras px;                     // (PART's arguments ride in free members: gsmvi_ctx.h)
     px.sj_src = X;
     px.sj_len = ldx;
@@ -1210,7 +1294,7 @@ void gsmvi_launch_panel_fast_part(hipStream_t st, hipEvent_t* ev, dim3 grid, int
     px.sj_dst = Qg;
     px.mfin = Qm;
 #define PFQ(MTV, CW) GSMVI_LAUNCH((k_panel_fast<MTV, false, CW, false, false, false, true>), grid, dim3(512), 0, st, ev, D, B, G, ldg, \
-                                  nullptr, 1.0, S0, lds0, Pp, chunks_per_wg, D, nullptr, nullptr, 0, nullptr, px)
+                                  nullptr, 1.0, S0, lds0, Pp, chunks_per_wg, D, stamps, nullptr, 0, nullptr, px)
     if (chw == 512) PFQ(1, 512);
     else { if (B == 16) PFQ(1, 256); else PFQ(2, 256); }
 #undef PFQ
@@ -1246,6 +1330,9 @@ static int cov_sym_grid(int nt) {
     for (int ti = 0; ti < nt; ++ti) n += (nt - ti + 1) / 2;
     return n;
 }
+
+// the two-tile workgroups among them (the kernel's n_two): all of the grid when the diagonal leftovers are folded
+int gsmvi_cov_sym_pairs(int nt) { return (nt >> 1) * ((nt + 1) >> 1); }
 
 bool gsmvi_launch_gsm_cov_sym(hipStream_t st, hipEvent_t* ev, int D, int B, const double* rec, int ldrec,
                               const double* mu0, const double* S0, int lds0, double* S, int lds, double* mu_out,
@@ -1301,14 +1388,18 @@ bool gsmvi_launch_gsm_cov_sym(hipStream_t st, hipEvent_t* ev, int D, int B, cons
 // The covariance launch of the two-launch dense GSM update (the caller checked the gate: B in {16, 32}, D % 256 == 0, D <= 1024,
 // KC <= 4, even leading dimensions, 16-byte aligned bases).  Same grid as above.  kct = 2: the instance compiled for exactly two
 // slabs (the caller's product ran the 512-row split: fs.KC == 2, D == 1024); kct = 4: any KC <= 4.
+// fold (round 9): the grid is the two-tile workgroups alone, the diagonal leftovers are third tiles of their hosts (FOLD above).
 void gsmvi_launch_gsm_cov_sym_slabs(hipStream_t st, hipEvent_t* ev, int D, int B, const gsm_slab_src& fs, const double* mu0,
-                                    const double* S0, int lds0, double* S, int lds, double* mu_out, int kct) {
-    const dim3 grid(cov_sym_grid(D / 32));
+                                    const double* S0, int lds0, double* S, int lds, double* mu_out, int kct, bool fold,
+                                    unsigned long long* stamps) {
+    const dim3 grid(fold ? gsmvi_cov_sym_pairs(D / 32) : cov_sym_grid(D / 32));
     const double invB = 1.0 / (double)B;
-#define CSS(SBV, KV)                                                                                                      \
-    GSMVI_LAUNCH((k_gsm_cov_sym<SBV, false, true, KV>), grid, dim3(512), 0, st, ev, D, B, invB, nullptr, 0, mu0, S0, lds0, S, lds, mu_out, \
-                 0, nullptr, fs)
-    if (kct == 2) { if (B == 16) CSS(16, 2); else CSS(32, 2); }
-    else { if (B == 16) CSS(16, 4); else CSS(32, 4); }
+#define CSS(SBV, KV, FV)                                                                                                  \
+    GSMVI_LAUNCH((k_gsm_cov_sym<SBV, false, true, KV, FV>), grid, dim3(512), 0, st, ev, D, B, invB, nullptr, 0, mu0, S0, lds0, S, lds, mu_out, \
+                 0, stamps, fs)
+#define CSF(SBV, KV) do { if (fold) CSS(SBV, KV, true); else CSS(SBV, KV, false); } while (0)
+    if (kct == 2) { if (B == 16) CSF(16, 2); else CSF(32, 2); }
+    else { if (B == 16) CSF(16, 4); else CSF(32, 4); }
+#undef CSF
 #undef CSS
 }

@@ -538,7 +538,8 @@ class HipEngine:
                  "batched_bam": 0x4000, "batched_kl": 0x8000, "batched_advi": 0x10000, "batched_target": 0x20000,
                  "batched_lbfgs": 0x40000, "batched_laplace": 0x80000, "batched_predict": 0x100000,
                  "batched_psis": 0x200000, "batched_loo": 0x400000, "gsm_two_launch": 0x800000,
-                 "batched_softmax": 0x1000000, "panel_chunk512": 0x2000000, "batched_pathfinder": 0x4000000}
+                 "batched_softmax": 0x1000000, "panel_chunk512": 0x2000000, "batched_pathfinder": 0x4000000,
+                 "cov_fold_diag": 0x8000000}
     PATH_GENERIC_MASK = 0x4 | 0x10 | 0x40 | 0x100 | 0x400 | 0x1000
 
     def last_path(self, reset=True):

@@ -99,6 +99,9 @@ int gsmvi_destroy(gsmvi_ctx* ctx);
  * runs); "gsm_two_launch" (default 1: the dense GSM update at B in {16, 32}, D % 256 == 0, D <= 1024 with even leading
  * dimensions and 16-byte aligned arrays runs as two launches without the per-sample kernel; 0 = always three launches;
  * an explicit "panel_kc" also selects 256-row chunks for its product at D = 1024, where the default is two 512-row slabs);
+ * round 9: "cov_fold_diag" (two-launch form: the diagonal leftover tiles of the covariance launch ride as third tiles in
+ * two-tile workgroups instead of being workgroups of their own; 1 = where the two-tile workgroups alone fill the device,
+ * i.e. D = 1024 on 256 CUs, default; 0 = never; 2 = at every two-launch shape; results are bit for bit the same);
  * diagnostics "timeline", "cov_dbg"
  * (see gsmvi_hip_debug.h). */
 int gsmvi_set_tuning(gsmvi_ctx* ctx, const char* name, int value);
@@ -292,6 +295,7 @@ int gsmvi_get_profile(gsmvi_ctx* ctx, float* ms, int n);
 #define GSMVI_PATH_BATCHED_SOFTMAX 0x1000000u /* k_softmax_batched: the batched multinomial logit target's entry point            */
 #define GSMVI_PATH_PANEL_CHUNK512 0x2000000u /* the two-launch product ran as two slabs of one 512-row chunk each (D = 1024, no explicit "panel_kc") */
 #define GSMVI_PATH_BATCHED_PATHFINDER 0x4000000u /* k_pf_propose / k_pf_select: the batched Pathfinder initialiser                  */
+#define GSMVI_PATH_COV_FOLD_DIAG 0x8000000u /* the two-launch covariance launch ran without single-tile workgroups: diagonal leftovers folded ("cov_fold_diag") */
 #define GSMVI_PATH_GENERIC_MASK (0x0004u | 0x0010u | 0x0040u | 0x0100u | 0x0400u | 0x1000u)
 int gsmvi_last_path(gsmvi_ctx* ctx, unsigned* bits, int reset);
 
