@@ -50,6 +50,9 @@ Mirrors the reference's public surface for the hot path (reference file:line):
     laplace_init_batched (the Newton mode and the
     inverse Hessian of K GLM posteriors, D <= 64:
     one launch per round, fp64-MFMA Gram product) gsmvi/initializers.py:5-17 (the role; no reference twin)
+    laplace_init_softmax_batched (the same start
+    for K multinomial logit posteriors, D <= 64,
+    and BatchedSoftmaxTarget.neg_hessian)        gsmvi/initializers.py:5-17 (the role; no reference twin)
     lbfgs_init, ADVI (initialiser and the ELBO
     baseline of the examples; off the hot path)  gsmvi/initializers.py:5-17, gsmvi/advi.py:8-112
 All GSM / BaM numerics run in hand-written HIP kernels (libgsmvi_hip.so, C ABI in include/gsmvi_hip.h)
@@ -71,6 +74,7 @@ from .batched import ADVIBatch, Adam                                 # noqa: F40
 from .monitors import KLMonitor, DeviceKLMonitor, BatchedKLMonitor   # noqa: F401
 from .initializers import lbfgs_init, lbfgs_init_batched, LbfgsBatchedResult   # noqa: F401
 from .initializers import laplace_init_batched, LaplaceBatchedResult          # noqa: F401
+from .initializers import laplace_init_softmax_batched                        # noqa: F401
 from .initializers import pathfinder_init_batched, PathfinderBatchedResult    # noqa: F401
 from .diagnostics import psis_batched, psis_weights_batched, PSISBatchedResult   # noqa: F401
 from .diagnostics import psis_loo_batched, LOOBatchedResult          # noqa: F401

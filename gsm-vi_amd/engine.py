@@ -539,7 +539,7 @@ class HipEngine:
                  "batched_lbfgs": 0x40000, "batched_laplace": 0x80000, "batched_predict": 0x100000,
                  "batched_psis": 0x200000, "batched_loo": 0x400000, "gsm_two_launch": 0x800000,
                  "batched_softmax": 0x1000000, "panel_chunk512": 0x2000000, "batched_pathfinder": 0x4000000,
-                 "cov_fold_diag": 0x8000000}
+                 "cov_fold_diag": 0x8000000, "batched_softmax_laplace": 0x10000000}
     PATH_GENERIC_MASK = 0x4 | 0x10 | 0x40 | 0x100 | 0x400 | 0x1000
 
     def last_path(self, reset=True):
@@ -1034,6 +1034,55 @@ class HipEngine:
         stopped = state.get("stopped")
         self._call("gsmvi_laplace_step_batched_f64",
                    *self._glm_model_args(A, y, family, offset, counts, prior_prec, noise_prec), int(bool(start)),
+                   self._packed(state["x"], (K, D), "x"), self._packed(state["g"], (K, D), "g"),
+                   self._packed(state["d"], (K, D), "d"), self._packed(state["sc"], (K, 4), "sc"),
+                   self._ist(state, K), self._packed(state["Xt"], (K, D), "Xt"), self._ints(stopped, 1, "stopped"),
+                   int(maxiter), int(maxfun), float(gtol))
+
+    # ---- batched softmax Laplace initialiser: the same for the multinomial logit (csrc/gsmvi_softmax_laplace_batched.hip) -------
+    def _softmax_model_args(self, A, labels, num_classes, counts, prior_prec, D):
+        """the model's arguments of the two softmax Laplace entry points, in the order of include/gsmvi_hip.h"""
+        K, N, P = A.shape
+        Cc = int(num_classes)
+        if Cc < 2 or (Cc - 1) * P != D:
+            raise ValueError(f"expected (num_classes - 1) P = {(Cc - 1) * P} columns, got {D}")
+        assert labels.is_cuda and labels.dtype == torch.int32 and labels.is_contiguous() and tuple(labels.shape) == (K, N), \
+            f"labels: expected a contiguous int32 CUDA tensor of shape {(K, N)}"
+        r, rp = self._reg_arg(prior_prec, K)
+        return (K, Cc, P, N, self._packed(A, (K, N, P), "A"), _ptr(labels), self._ints(counts, K, "counts"), r, rp)
+
+    def softmax_hessian_batched(self, X, A, labels, num_classes, counts=None, prior_prec=1.0, want="h", out=None, cov_out=None,
+                                info_out=None):
+        """The negative Hessian of lp_k of K multinomial logit posteriors at the rows of X (K, D), D = (C - 1) P class-major,
+        and / or its inverse, one launch (the class-coupled Gram product on the fp64 MFMA)  [no reference twin; the model of
+        examples/example_gsm.py:34-35]: block (c, c') of H_k is sum_n w_n,cc' a_n a_n^T + lam_k [c = c'] I with w_n,cc =
+        p_nc (1 - p_nc) and w_n,cc' = -p_nc p_nc'.  ``want`` = "h" -> H (K, D, D), "cov" -> (cov, info), "both" -> (H, cov, info);
+        ``info`` (K,) int32: 0, or 1 + the first failing pivot, and then cov_k = I.  The other arguments are ``softmax_batched``'s."""
+        self._check_want(want, "h", "cov")
+        X = X.contiguous()
+        K, D = X.shape
+        self._any_ctx()
+        H = cov = info = None
+        if want != "cov":
+            H = self.empty(K, D, D) if out is None else out
+        if want != "h":
+            cov = self.empty(K, D, D) if cov_out is None else cov_out
+            info = torch.zeros(K, dtype=torch.int32, device=self.device) if info_out is None else info_out
+        self._call("gsmvi_softmax_hessian_batched_f64", *self._softmax_model_args(A, labels, num_classes, counts, prior_prec, D),
+                   self._packed(X, (K, D), "X"), self._dp(H, (K, D, D), "out"), self._dp(cov, (K, D, D), "cov_out"),
+                   self._ints(info, K, "info_out"))
+        return H if want == "h" else (cov, info) if want == "cov" else (H, cov, info)
+
+    def softmax_laplace_step_batched(self, state, A, labels, num_classes, counts=None, prior_prec=1.0, start=False, maxiter=100,
+                                     maxfun=200, gtol=1e-8):
+        """One damped Newton round of every running problem of ``state`` (``laplace_state_batched``) for the multinomial logit
+        posteriors (csrc/gsmvi_softmax_laplace_batched.hip): f, g and H at ``state["Xt"]`` in one sweep over A, then the round of
+        ``laplace_step_batched``, the same state machine  [the role of gsmvi/initializers.py:5-17]"""
+        K, D = state["x"].shape
+        self._any_ctx()
+        stopped = state.get("stopped")
+        self._call("gsmvi_softmax_laplace_step_batched_f64",
+                   *self._softmax_model_args(A, labels, num_classes, counts, prior_prec, D), int(bool(start)),
                    self._packed(state["x"], (K, D), "x"), self._packed(state["g"], (K, D), "g"),
                    self._packed(state["d"], (K, D), "d"), self._packed(state["sc"], (K, 4), "sc"),
                    self._ist(state, K), self._packed(state["Xt"], (K, D), "Xt"), self._ints(stopped, 1, "stopped"),

@@ -16,7 +16,9 @@ Pathfinder; csrc/gsmvi_pathfinder_batched.hip).  Any target with ``lp`` and ``lp
 
 ``laplace_init_batched`` is the second-order start for the built-in GLM targets (``BatchedGLMTarget``,
 ``BatchedLogisticTarget``): a damped Newton (IRLS) iteration in HIP (csrc/gsmvi_laplace_batched.hip), one launch per round, and
-the Laplace covariance (A^T W A + lam I)^-1 at the mode.
+the Laplace covariance (A^T W A + lam I)^-1 at the mode.  ``laplace_init_softmax_batched`` is the same start for
+``BatchedSoftmaxTarget``, on the class-coupled Hessian of the multinomial logit (csrc/gsmvi_softmax_laplace_batched.hip); the two
+share one host loop.
 """
 from dataclasses import dataclass
 
@@ -304,34 +306,42 @@ def laplace_init_batched(target, x0=None, maxiter=100, maxfun=200, *, gtol=1e-8,
     if not isinstance(target, BatchedGLMTarget):
         raise TypeError(f"laplace_init_batched: target must be a BatchedGLMTarget or a BatchedLogisticTarget, "
                         f"got {type(target).__name__}")
+    model = dict(offset=target.offset, counts=target.counts, prior_prec=target.prior_precision,
+                 noise_prec=target.noise_precision)
+    eng = engine if engine is not None else target.engine
+    return _laplace_run("laplace_init_batched", target, x0, maxiter, maxfun, gtol, check_every, as_torch, eng,
+                        lambda st, **kw: eng.laplace_step_batched(st, target.A, target.y, target.family, **kw, **model),
+                        lambda x: eng.glm_hessian_batched(x, target.A, target.y, target.family, want="cov", **model))
+
+
+def _laplace_run(name, target, x0, maxiter, maxfun, gtol, check_every, as_torch, eng, step, cov_at):
+    """The host loop of the Laplace initialisers, once: the argument checks (errors carry ``name``), the state, one ``step(state,
+    start=, maxiter=, maxfun=, gtol=)`` launch per round until the device's count of stopped problems equals K, then
+    ``cov_at(x)`` -> (cov, info) at the final points, the identity for every problem without success, and the result."""
     K, D = target.K, target.D
     maxiter, maxfun, check_every = int(maxiter), int(maxfun), int(check_every)
     if maxiter < 1 or maxfun < 2 or check_every < 1:
-        raise ValueError("laplace_init_batched: maxiter and check_every must be at least 1, maxfun at least 2")
+        raise ValueError(f"{name}: maxiter and check_every must be at least 1, maxfun at least 2")
     if not gtol >= 0.0:
-        raise ValueError("laplace_init_batched: gtol must be >= 0")
-    eng = engine if engine is not None else target.engine
+        raise ValueError(f"{name}: gtol must be >= 0")
     if x0 is None:
         x0 = np.zeros((K, D))
     elif not hasattr(x0, "shape"):
         x0 = np.asarray(x0, dtype=np.float64)
     shape = tuple(int(n) for n in x0.shape)
     if shape not in ((D,), (K, D)):
-        raise ValueError(f"laplace_init_batched: x0 must be None, (D,) = {(D,)} or (K, D) = {(K, D)}, got {shape}")
+        raise ValueError(f"{name}: x0 must be None, (D,) = {(D,)} or (K, D) = {(K, D)}, got {shape}")
     x0 = eng.asarray(x0)
     if len(shape) == 1:
         x0 = x0.reshape(1, D).repeat(K, 0) if isinstance(x0, np.ndarray) else x0.reshape(1, D).expand(K, D)
-    model = dict(offset=target.offset, counts=target.counts, prior_prec=target.prior_precision,
-                 noise_prec=target.noise_precision)
     st = eng.laplace_state_batched(x0)
     nlaunch = 0
     for r in range(1, maxfun + 1):
-        eng.laplace_step_batched(st, target.A, target.y, target.family, start=r == 1, maxiter=maxiter, maxfun=maxfun, gtol=gtol,
-                                 **model)
+        step(st, start=r == 1, maxiter=maxiter, maxfun=maxfun, gtol=gtol)
         nlaunch = r
         if r % check_every == 0 and eng.read_flag(st["stopped"]) == K:
             break
-    cov, info = eng.glm_hessian_batched(st["x"], target.A, target.y, target.family, want="cov", **model)
+    cov, info = cov_at(st["x"])
     ist = eng.read_ints(st["ist"])
     status, info = ist[:, 0].copy(), eng.read_ints(info)
     success = (status == 1) & (info == 0)
@@ -346,3 +356,23 @@ def laplace_init_batched(target, x0=None, maxiter=100, maxfun=200, *, gtol=1e-8,
                                nit=ist[:, 1].copy(), nfev=ist[:, 2].copy(), status=status, success=success, info=info,
                                nlaunch=nlaunch)
     return (st["x"], cov, res) if as_torch else (res.x.copy(), eng.to_numpy(cov), res)
+
+
+def laplace_init_softmax_batched(target, x0=None, maxiter=100, maxfun=200, *, gtol=1e-8, check_every=4, as_torch=False, engine=None):
+    """The Laplace start of K multinomial logit posteriors at once: returns ``(mean (K, D), cov (K, D, D), res)``, the Newton
+    modes of ``lp_k``, the inverses of the negative Hessians there (``BatchedSoftmaxTarget.neg_hessian``: block (c, c') is
+    sum_n w_n,cc' a_n a_n^T + lam_k [c = c'] I) and a ``LaplaceBatchedResult``.  It fills the role of ``lbfgs_init``
+    (gsmvi/initializers.py:5-17) for the softmax target.
+
+    ``target``: a ``BatchedSoftmaxTarget`` (anything else: TypeError).  The posterior is log-concave, and everything else --
+    ``x0``, the damped Newton iteration and its line search, the stopping rule, ``check_every``, one launch per round
+    (csrc/gsmvi_softmax_laplace_batched.hip), the frozen problems, the failure policy (a problem without success returns its
+    last ``x`` and the identity) and the defaults -- is ``laplace_init_batched``'s, word for word.  Prints nothing."""
+    from .targets import BatchedSoftmaxTarget
+    if not isinstance(target, BatchedSoftmaxTarget):
+        raise TypeError(f"laplace_init_softmax_batched: target must be a BatchedSoftmaxTarget, got {type(target).__name__}")
+    model = dict(counts=target.counts, prior_prec=target.prior_precision)
+    eng = engine if engine is not None else target.engine
+    return _laplace_run("laplace_init_softmax_batched", target, x0, maxiter, maxfun, gtol, check_every, as_torch, eng,
+                        lambda st, **kw: eng.softmax_laplace_step_batched(st, target.A, target.y, target.C, **kw, **model),
+                        lambda x: eng.softmax_hessian_batched(x, target.A, target.y, target.C, want="cov", **model))

@@ -15,7 +15,8 @@ multinomial logit regressions (C classes, C - 1 linear predictors per row), a la
     BatchedGaussianTarget     (a Gaussian density)            gsmvi_gaussian_score_batched_f64   no
     BatchedLogisticTarget     y in [0, 1]                     gsmvi_logistic_batched_f64         yes
     BatchedGLMTarget          poisson, probit, gaussian, ...  gsmvi_glm_batched_f64              yes
-    BatchedSoftmaxTarget      integer labels in 0 .. C - 1    gsmvi_softmax_batched_f64          no (TypeError)
+    BatchedSoftmaxTarget      integer labels in 0 .. C - 1    gsmvi_softmax_batched_f64          laplace_init_softmax_batched and
+                                                                                                 neg_hessian; predict, loo: no (TypeError)
 """
 from dataclasses import dataclass
 from typing import Any
@@ -416,11 +417,12 @@ class BatchedSoftmaxTarget:
     evaluated by gsmvi_softmax_batched_f64: what examples/example_gsm.py:34-35 gets from a model's log_prob and jit(grad(...)).
     numpy arrays or tensors in; everything is kept on the device as float64 / int32.  Arguments are validated on the host before
     any device work (ValueError naming the argument and the problems).  It is not a ``BatchedGLMTarget``: there is no offset, and
-    ``laplace_init_batched``, ``predict`` and ``psis_loo_batched`` do not take it (TypeError).
+    ``laplace_init_batched``, ``predict`` and ``psis_loo_batched`` do not take it (TypeError).  Its second-order start is
+    ``laplace_init_softmax_batched``, on the closed-form negative Hessian that ``neg_hessian`` returns.
 
     ``lp_g(x, out=None)``: (K, B, D) -> (K, B, D) scores, ``device_native`` and ``graph_safe`` (one capturable launch, no
     allocation with ``out``).  ``lp(x)``: (K, rows, D) -> (K, rows) values; a device tensor or numpy.  ``lp_and_score(x)``:
-    (scores, values) from one launch.  Attributes ``K, N, D, P, C``."""
+    (scores, values) from one launch.  ``neg_hessian(x)``: (K, D) -> (K, D, D).  Attributes ``K, N, D, P, C``."""
 
     def __init__(self, A, y, num_classes, prior_precision=1.0, counts=None, engine=None):
         if isinstance(num_classes, bool) or not isinstance(num_classes, (int, np.integer)) or num_classes < 2:
@@ -461,6 +463,14 @@ class BatchedSoftmaxTarget:
     def lp_and_score(self, x):
         """(scores (K, rows, D), values (K, rows)) from one launch"""
         return self._call(self.engine.asarray(x), want="both")
+
+    def neg_hessian(self, x):
+        """(K, D, D) negative Hessians of lp_k at the rows of x (K, D): block (c, c') is sum_n w_n,cc' a_n a_n^T + lam_k [c = c'] I
+        with p_nc = exp(eta_nc - m_n) / s_n, w_n,cc = p_nc (1 - p_nc) and w_n,cc' = -p_nc p_nc' (1 - p formed as a sum over the other
+        classes, so a saturated class keeps its digits), exactly symmetric; a device tensor or numpy; one launch"""
+        eng = self.engine
+        return eng.softmax_hessian_batched(eng.asarray(x), self.A, self.y, self.C, counts=self.counts,
+                                           prior_prec=self.prior_precision, want="h")
 
     def predict(self, *args, **kw):
         """not built yet for this target: TypeError (the predictive is ``BatchedGLMTarget.predict``'s, one linear predictor per row)"""

@@ -24,7 +24,8 @@
  *   examples/example_gsm.py:34-35 the same for K Poisson, probit or Gaussian regressions with offsets -> gsmvi_glm_batched_f64
  *   examples/example_gsm.py:34-35 the same for K multinomial logit (softmax) regressions of C classes -> gsmvi_softmax_batched_f64
  *   initializers.py:5-17 lbfgs_init (maximiser of lp, dense inverse-Hessian estimate), K problems -> gsmvi_lbfgs_step_batched_f64, gsmvi_lbfgs_hess_inv_batched_f64
- *   initializers.py:5-17 the same role by Newton rounds on the GLMs of examples/example_gsm.py:34-35 (no reference twin) -> gsmvi_glm_hessian_batched_f64, gsmvi_laplace_step_batched_f64
+ *   initializers.py:5-17 the same role by Newton rounds on the GLMs of examples/example_gsm.py:34-35 (no reference twin) -> gsmvi_glm_hessian_batched_f64, gsmvi_laplace_step_batched_f64,
+ *   gsmvi_softmax_hessian_batched_f64, gsmvi_softmax_laplace_step_batched_f64 (the multinomial logit)
  *   initializers.py:5-17 the same role with a start picked by its ELBO along the L-BFGS path (Pathfinder; no reference twin) -> gsmvi_pathfinder_propose_batched_f64, gsmvi_pathfinder_select_batched_f64
  *   examples/example_gsm.py:34-35 the use of the fit: predictions and the held-out score of K fitted GLMs (no reference twin) -> gsmvi_glm_predict_batched_f64
  *   monitors.py:83-125 the role (is q_k close to its target?), per problem and comparable across problems: the Pareto-smoothed
@@ -296,6 +297,7 @@ int gsmvi_get_profile(gsmvi_ctx* ctx, float* ms, int n);
 #define GSMVI_PATH_PANEL_CHUNK512 0x2000000u /* the two-launch product ran as two slabs of one 512-row chunk each (D = 1024, no explicit "panel_kc") */
 #define GSMVI_PATH_BATCHED_PATHFINDER 0x4000000u /* k_pf_propose / k_pf_select: the batched Pathfinder initialiser                  */
 #define GSMVI_PATH_COV_FOLD_DIAG 0x8000000u /* the two-launch covariance launch ran without single-tile workgroups: diagonal leftovers folded ("cov_fold_diag") */
+#define GSMVI_PATH_BATCHED_SOFTMAX_LAPLACE 0x10000000u /* k_softmax_laplace_batched: the batched multinomial logit Hessian and Newton step */
 #define GSMVI_PATH_GENERIC_MASK (0x0004u | 0x0010u | 0x0040u | 0x0100u | 0x0400u | 0x1000u)
 int gsmvi_last_path(gsmvi_ctx* ctx, unsigned* bits, int reset);
 
@@ -671,6 +673,44 @@ int gsmvi_laplace_step_batched_f64(gsmvi_ctx* ctx, void* stream, int64_t K, int 
                                    const double* noise_prec_dev, double prior_prec, const double* prior_prec_dev, int start,
                                    double* x, double* g, double* d, double* sc, int* ist, double* Xt, int* stopped_dev, int maxiter,
                                    int maxfun, double gtol);
+
+/*
+ * Batched softmax Laplace initialiser: the Newton mode of K multinomial logit posteriors of one (N, C, P) and the inverse of the
+ * negative Hessian there as the covariance.  The reference has no Laplace initialiser: this fills the role of
+ * gsmvi/initializers.py:5-17 (the maximiser of lp as the mean, an inverse-Hessian estimate as the covariance) for the multinomial
+ * logit model of gsmvi_softmax_batched_f64, given to the reference as log_prob and jit(grad(...)) of it
+ * (examples/example_gsm.py:34-35).  With that entry's parametrisation (class C - 1 the reference class, eta = 0; x[c P + j] = W_cj;
+ * D = (C - 1) P <= 64), its m_n and s_n, and p_nc = exp(eta_nc - m_n) / s_n, for d = c P + i and d' = c' P + j, c, c' < C - 1:
+ *   H_k(x)[d, d'] = sum_{n < n_k} w_n,cc' a_ni a_nj + lam_k [d = d']      the negative Hessian of lp_k at x, positive semi-definite
+ *   w_n,cc  = p_nc (1 - p_nc),   w_n,cc' = -p_nc p_nc'  (c != c'),   phi = -lp,   g = -score,   d_newton = -H^{-1} g.
+ * 1 - p_nc is a sum over the other classes: with c* the first class that attains m_n (e_c* = 1 exactly), s_rest = sum_{c != c*} e_c
+ * and s = 1 + s_rest, 1 - p_c* = s_rest / s and 1 - p_c = (s - e_c) / s for c != c* (s - e_c >= 1); the reference class takes part
+ * in m, s and s_rest like any other.  It is never 1.0 - p and never a difference of two Gram sums, which lose every digit of a
+ * diagonal class block when one class saturates.  The residual of the gradient is 1 - p_nc in that form where y_n = c and -p_nc
+ * elsewhere.  The argument meanings, bounds and grid limits of gsmvi_softmax_batched_f64 hold for both entry points (C >= 2, P >= 1,
+ * any N >= 1, counts_dev clamped in the kernel and rows n >= n_k never loaded, a label used in comparisons only).  The Gram
+ * product runs on the fp64 MFMA over tiles of 32 rows; every sum over n is taken in an order fixed by (N, C, P) alone, so a
+ * problem's bits depend on its own data only, not on K or its neighbours.
+ *
+ * gsmvi_softmax_hessian_batched_f64: H, cov and info_dev as gsmvi_glm_hessian_batched_f64 gives them, at the rows x_k of X (K x D).
+ * A non-finite x_k or a valid row with a non-finite eta gives H_k = NaN, info[k] = 1, cov_k = I (by a flag, not by arithmetic), and
+ * no other problem is touched.  At least one of H, cov is given; info_dev is required with cov and only with it.
+ *
+ * gsmvi_softmax_laplace_step_batched_f64: one launch is one damped Newton round of phi_k = -lp_k for every running problem: the
+ * state (x, g, d, Xt (K x D), sc (K x 4), ist (K x 8)), the status codes, the Armijo test with its slack, the halving, the 20
+ * rejections, *stopped_dev and the meaning of start, maxiter, maxfun and gtol are those documented for
+ * gsmvi_laplace_step_batched_f64, word for word; a non-finite x or eta is status 4 at the start and a rejected trial later.
+ * Both: shapes, NULL arrays and overlaps are checked before the context is looked at (then a NULL ctx); every failure returns
+ * GSMVI_ERR_BAD_ARG before anything is enqueued.  Inputs are only read; no context workspace is used; at most 64 KB of dynamic
+ * LDS (no kernel attribute).  Sets GSMVI_PATH_BATCHED_SOFTMAX_LAPLACE.
+ */
+int gsmvi_softmax_hessian_batched_f64(gsmvi_ctx* ctx, void* stream, int64_t K, int C, int P, int64_t N, const double* A,
+                                      const int* labels, const int* counts_dev, double prior_prec, const double* prior_prec_dev,
+                                      const double* X, double* H, double* cov, int* info_dev);
+int gsmvi_softmax_laplace_step_batched_f64(gsmvi_ctx* ctx, void* stream, int64_t K, int C, int P, int64_t N, const double* A,
+                                           const int* labels, const int* counts_dev, double prior_prec,
+                                           const double* prior_prec_dev, int start, double* x, double* g, double* d, double* sc,
+                                           int* ist, double* Xt, int* stopped_dev, int maxiter, int maxfun, double gtol);
 
 /*
  * Batched GLM posterior predictive: what a fitted q_k = N(mean_k, cov_k) over the coefficients of K GLMs of one D says about M new

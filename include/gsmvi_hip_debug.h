@@ -55,6 +55,10 @@ int gsmvi_debug_glm_batched_lds(int D, int nc, int want, int family, int has_off
 int gsmvi_debug_softmax_batched_lds(int C, int P, int nc, int want, size_t* bytes, int* problems_per_workgroup,
                                     int* x_rows_per_tile);
 
+/* The same for a gsmvi_softmax_hessian_batched_f64 or gsmvi_softmax_laplace_step_batched_f64 launch at (C, P) (both request the
+ * same: H aliases the sweep's tiles).  Host arithmetic only, no device needed. */
+int gsmvi_debug_softmax_laplace_lds(int C, int P, size_t* bytes, int* problems_per_workgroup);
+
 /* The same for a batched L-BFGS launch at D: mode 0 = gsmvi_lbfgs_step_batched_f64, 1 = gsmvi_lbfgs_hess_inv_batched_f64.  Host
  * arithmetic only, no device needed. */
 int gsmvi_debug_lbfgs_batched_lds(int D, int mode, size_t* bytes, int* problems_per_workgroup);
