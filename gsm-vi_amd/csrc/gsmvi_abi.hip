@@ -47,10 +47,10 @@ bool gsmvi_launch_gsm_cov_sym(hipStream_t st, hipEvent_t* ev, int D, int B, cons
                               int dbg, unsigned long long* stamps, int num_cu);
 void gsmvi_launch_panel_fast_part(hipStream_t st, hipEvent_t* ev, dim3 grid, int D, int B, const double* G, int ldg,
                                   const double* S0, int lds0, double* Pp, int chunks_per_wg, const double* X, int ldx,
-                                  const double* mu0, double* Qg, double* Qm, int chw, unsigned long long* stamps);
+                                  const double* mu0, double* Qg, double* Qm, int chw, bool qm_whole, unsigned long long* stamps);
 void gsmvi_launch_gsm_cov_sym_slabs(hipStream_t st, hipEvent_t* ev, int D, int B, const struct gsm_slab_src& fs, const double* mu0,
                                     const double* S0, int lds0, double* S, int lds, double* mu_out, int kct, bool fold,
-                                    unsigned long long* stamps);
+                                    bool s0_last, bool store_wt, bool qm_whole, unsigned long long* stamps);
 int gsmvi_cov_sym_pairs(int nt);
 int gsmvi_panel_fast_chunk(int MT);
 int gsmvi_potrf_impl(struct gsmvi_ctx* ctx, hipStream_t st, int D, const double* S, int lds, double* R, int ldr,
@@ -323,6 +323,9 @@ int gsmvi_set_tuning(gsmvi_ctx* ctx, const char* name, int value) {
     else if (!strcmp(name, "scalars_nt")) ctx->tune_scalars_nt = value;
     else if (!strcmp(name, "gsm_two_launch")) ctx->tune_gsm_two_launch = value;
     else if (!strcmp(name, "cov_fold_diag")) ctx->tune_cov_fold_diag = value;
+    else if (!strcmp(name, "cov_s0_last")) ctx->tune_cov_s0_last = value;
+    else if (!strcmp(name, "cov_store_wt")) ctx->tune_cov_store_wt = value;
+    else if (!strcmp(name, "panel_qm_whole")) ctx->tune_panel_qm_whole = value;
     else if (!strcmp(name, "cov_dbg")) ctx->tune_cov_dbg = value;   // ablation bits, timing experiments only
     else if (!strcmp(name, "timeline")) {                           // whole-update timeline stamps (diagnostic)
         if (value && !ctx->stamps) {
@@ -674,9 +677,11 @@ static int gsm_two_launch(gsmvi_ctx* ctx, hipStream_t hs, int D, int B, int cpw,
     hipEvent_t* ev0 = ctx->stage_events(0);
     ctx->ev_valid[1] = 0;                                       // no per-sample launch: gsmvi_get_profile reports -1 for it
     // (512-row chunks: one workgroup per (strip, slab, 16 samples) -- the launcher's comment in gsmvi_fast.hip)
+    // round 10: one Qm value per sample ("panel_qm_whole"; the 512-row-chunk route only, D = 1024: one 16-byte unit per thread)
+    const bool qm_whole = chw == 512 && D == 1024 && ctx->tune_panel_qm_whole != 0;
     gsmvi_launch_panel_fast_part(hs, ev0, dim3(strips, kc, chw == 512 ? B / 16 : 1), D, B, G, ldg, S0, lds0, ctx->pp, cpw, X, ldx, mu0, Qg, Qm, chw,
-                                 ctx->timeline_stamps(0));
-    ctx->path |= GSMVI_PATH_PANEL_FAST | (chw == 512 ? GSMVI_PATH_PANEL_CHUNK512 : 0u);
+                                 qm_whole, ctx->timeline_stamps(0));
+    ctx->path |= GSMVI_PATH_PANEL_FAST | (chw == 512 ? GSMVI_PATH_PANEL_CHUNK512 : 0u) | (qm_whole ? GSMVI_PATH_PANEL_QM_WHOLE : 0u);
     int st = check_launch("k_panel_fast(partials)");
     if (st != GSMVI_OK) return st;
     gsm_slab_src fs;
@@ -690,9 +695,15 @@ static int gsm_two_launch(gsmvi_ctx* ctx, hipStream_t hs, int D, int B, int cpw,
     // round 9: the diagonal leftover tiles ride in two-tile workgroups where those alone fill the device (D = 1024 on 256 CUs);
     // with fewer workgroups than CUs a leftover is better off as a workgroup of its own on an idle CU ("cov_fold_diag" = 2: always)
     const bool fold = ctx->tune_cov_fold_diag >= 2 || (ctx->tune_cov_fold_diag == 1 && gsmvi_cov_sym_pairs(D / 32) >= ctx->num_cu);
+    // round 10, the two-slab form only: S0 issued and waited for last ("cov_s0_last"); write-through stores of S ("cov_store_wt":
+    // 32-bit byte offsets into S, so only where its extent allows them -- D = 1024 reaches 2^31 bytes only at lds >= 262144; beyond
+    // that the plain form runs and the path bit is not set)
+    const bool s0_last = chw == 512 && ctx->tune_cov_s0_last != 0;
+    const bool store_wt = chw == 512 && ctx->tune_cov_store_wt != 0 && (size_t)D * (size_t)lds * sizeof(double) < ((size_t)1 << 31);
     gsmvi_launch_gsm_cov_sym_slabs(hs, ctx->stage_events(2), D, B, fs, mu0, S0, lds0, S, lds, mu, chw == 512 ? 2 : 4, fold,
-                                   ctx->timeline_stamps(2));
-    ctx->path |= GSMVI_PATH_COV_SYM | GSMVI_PATH_GSM_TWO_LAUNCH | (fold ? GSMVI_PATH_COV_FOLD_DIAG : 0u);
+                                   s0_last, store_wt, qm_whole, ctx->timeline_stamps(2));
+    ctx->path |= GSMVI_PATH_COV_SYM | GSMVI_PATH_GSM_TWO_LAUNCH | (fold ? GSMVI_PATH_COV_FOLD_DIAG : 0u) |
+                 (s0_last ? GSMVI_PATH_COV_S0_LAST : 0u) | (store_wt ? GSMVI_PATH_COV_STORE_WT : 0u);
     return check_launch("k_gsm_cov_sym(slabs)");
 }
 

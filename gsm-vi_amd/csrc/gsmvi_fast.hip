@@ -50,7 +50,13 @@
 // strip, and from the workgroups of slab 0 the sum of (mu0 - x) G.  The covariance kernel behind this launch re-reduces them in
 // every workgroup (k_gsm_cov_sym<.., FROM_SLABS>), so the per-sample launch between the two and its record round trip are gone;
 // the only ordering is the kernel boundary.  PART = false is the code as it was, instruction for instruction.
-template <int MT, bool HAS_SHIFT, int CHW, bool EXTRA, bool RIDER = false, bool RAG = false, bool PART = false>
+// QMW (round 10; PART on the 512-row-chunk grid (D / 16, 2, B / 16) only, knob "panel_qm_whole") = ONE Qm value per sample instead
+// of D / 16 pieces that every covariance workgroup re-sums: the slab-1 workgroups with blockIdx.x < 16 have no Qm work, so
+// workgroup (x, 1, z) takes sample b = 16 z + x, thread tid the 16-byte unit tid of G[b], X[b] and mu0 (loaded behind the M stream,
+// where the pq_* loads are), forms (mu0 - x) g over its pair behind the store loop and the workgroup sums in a fixed order:
+// row16_sum, the 32 row sums through LDS (the reduction buffer is free by then), one thread adds them in index order and writes
+// Qm[b].  The slab-0 workgroups neither load X and mu0 nor form their pieces.
+template <int MT, bool HAS_SHIFT, int CHW, bool EXTRA, bool RIDER = false, bool RAG = false, bool PART = false, bool QMW = false>
 __global__ __launch_bounds__(512) void k_panel_fast(int D, int nrows, const double* __restrict__ A, int lda,
                                                     const double* __restrict__ shift, double alpha,
                                                     const double* __restrict__ M, int ldm,
@@ -91,7 +97,9 @@ __global__ __launch_bounds__(512) void k_panel_fast(int D, int nrows, const doub
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt) acc[mt] = (v4d){0.0, 0.0, 0.0, 0.0};
     static_assert(!PART || (MT <= 2 && !RAG && !RIDER && !HAS_SHIFT), "partial dots: one pass of the store loop, on the grid");
+    static_assert(!QMW || (PART && CHW == 512 && MT == 1), "whole-sample Qm: the 512-row-chunk product of the two-launch form");
     double pq_g = 0.0, pq_x = 0.0, pq_m = 0.0;     // PART: G, X, mu0 at this thread's (sample, column) of the store loop
+    [[maybe_unused]] v2d wq_g, wq_x, wq_m;         // QMW: unit tid of G[b], X[b], mu0 in the workgroup that sums Qm[b]
 
     for (int ch = 0; ch < chunks_per_wg; ++ch) {
         const int cbase = (blockIdx.y * chunks_per_wg + ch) * CHW;          // block-uniform
@@ -180,8 +188,15 @@ __global__ __launch_bounds__(512) void k_panel_fast(int D, int nrows, const doub
         if constexpr (PART) {              // BEHIND the M stream: consumed only by the epilogue, nothing waits for them before
             const int prow = r0 + ((tid >> 4) & (NR - 1)), pcol = blockIdx.x * 16 + (tid & 15);
             pq_g = A[(size_t)prow * lda + pcol];
-            pq_x = px.sj_src[(size_t)prow * px.sj_len + pcol];     // X, ldx
-            pq_m = px.msl[pcol];                                   // mu0
+            if constexpr (!QMW) {
+                pq_x = px.sj_src[(size_t)prow * px.sj_len + pcol];     // X, ldx
+                pq_m = px.msl[pcol];                                   // mu0
+            } else if (blockIdx.y == 1 && blockIdx.x < 16) {           // block-uniform: this workgroup sums Qm of sample qm_b
+                const int qm_b = 16 * blockIdx.z + blockIdx.x, qm_c = 2 * tid < D ? 2 * tid : 0;
+                wq_g = *reinterpret_cast<const v2d*>(A + (size_t)qm_b * lda + qm_c);
+                wq_x = *reinterpret_cast<const v2d*>(px.sj_src + (size_t)qm_b * px.sj_len + qm_c);
+                wq_m = *reinterpret_cast<const v2d*>(px.msl + qm_c);
+            }
         }
         __builtin_amdgcn_sched_barrier(0);
         if (ch > 0) __syncthreads();       // previous chunk's MFMA reads of As are done
@@ -235,10 +250,26 @@ __global__ __launch_bounds__(512) void k_panel_fast(int D, int nrows, const doub
             if constexpr (PART) {          // (nrows % NR == 0: the 16 lanes of a DPP row are the 16 columns of sample row; whole waves run)
                 const double pg = row16_sum(pq_g * s);
                 if (cc == 0) px.sj_dst[((size_t)row * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x] = pg;      // Qg
-                if (blockIdx.y == 0) {
+                if (!QMW && blockIdx.y == 0) {
                     const double pm = row16_sum((pq_m - pq_x) * pq_g);
                     if (cc == 0) px.mfin[(size_t)row * gridDim.x + blockIdx.x] = pm;                             // Qm
                 }
+            }
+        }
+    }
+    if constexpr (QMW) {
+        if (blockIdx.y == 1 && blockIdx.x < 16) {  // (mu0 - x_b) . g_b of sample qm_b, fixed order
+            const int qm_b = 16 * blockIdx.z + blockIdx.x;
+            const double pr = 2 * tid < D ? (wq_m.x - wq_x.x) * wq_g.x + (wq_m.y - wq_x.y) * wq_g.y : 0.0;
+            const double rs = row16_sum(pr);
+            __syncthreads();                       // the store loop's reads of red are done
+            if ((tid & 15) == 0) red[tid >> 4] = rs;
+            __syncthreads();
+            if (tid == 0) {
+                double s = 0.0;
+#pragma unroll
+                for (int i = 0; i < 32; ++i) s += red[i];
+                px.mfin[qm_b] = s;                 // Qm[b]
             }
         }
     }
@@ -496,7 +527,24 @@ __global__ __launch_bounds__(NT) void k_gsm_scalars_fast(int D, int B, int KC, c
 // diagonal workgroup: the same staged values in the same order), a third LW buffer behind the two (inside the LDS it has), one
 // 8 KB store without a mirror behind the mirror stores, and mu of block r from the dmu units it staged that block from, in the
 // two-level order of the diagonal workgroups, on the barriers the store path has anyway.
-template <int SB, bool RAG, bool FROM_SLABS = false, int KCT = 4, bool FOLD = false>
+typedef unsigned int v4u __attribute__((ext_vector_type(4)));   // the payload type of a 16-B buffer store
+// S0L (round 10; the KCT = 2 forms only, knob "cov_s0_last") = the S0 tile is the LAST thing loaded and the last thing waited
+// for.  It is the only operand that comes from HBM or the Infinity Cache (everything else was written or read by the product
+// launch just before), it is used only in W = S0 + U behind the MFMAs, and vector loads come back in issue order: issued first,
+// it stood in front of the partial sums, the rho / beta / c chain and the staging of all three column blocks.  Here the
+// partials go out first, then blocks I, J0, J1, then s0v[0..1] and s0x between two sched_barriers; every wait in front of the
+// W step is counted so that those three stay outstanding (a non-host re-reads its own s0v[1] unit as s0x: a load under the
+// block-uniform branch would make the compiler's waits at the join cover one S0 unit in the hosts), and the barriers between
+// staging and the W step are s_waitcnt lgkmcnt(0); s_barrier, which cannot drain the vector-memory counter whatever the
+// compiler makes of __syncthreads().  That is safe: no thread reads global data that another thread of its workgroup wrote.
+// Same values, same operations, same order: results are those of S0L = false bit for bit.
+// WT (round 10; the KCT = 2 forms only, knob "cov_store_wt") = the stores of S (tiles, mirrors, the folded tile; not mu) are 16-B
+// write-through stores (buffer stores with sc1): the lines leave the L2 while other workgroups still compute instead of being
+// written back at the end of the launch, and they do not stay in the L2.  32-bit byte offsets: the launcher checks the extent.
+// QMW (round 10; the KCT = 2 forms only, knob "panel_qm_whole") = the product launch left ONE Qm value per sample
+// (k_panel_fast<.., PART, QMW>): mv is one 8-byte load issued with the Qg units; the two Qm units, their sum and the second
+// row16_sum are gone from the chain.  mv is summed in another order than the per-strip pieces: mu and S move at rounding level.
+template <int SB, bool RAG, bool FROM_SLABS = false, int KCT = 4, bool FOLD = false, bool S0L = false, bool WT = false, bool QMW = false>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(FROM_SLABS ? 4 : 2))) void k_gsm_cov_sym(int D, int B, double invB, const double* __restrict__ rec, int ldrec,
                                                      const double* __restrict__ mu0,
                                                      const double* __restrict__ S0, int lds0,
@@ -504,6 +552,13 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(FROM_SLABS 
                                                      double* __restrict__ mu_out, int dbg,
                                                      unsigned long long* __restrict__ stamps, gsm_slab_src fs) {
     static_assert(!FOLD || FROM_SLABS, "folded diagonal tiles: the two-launch form only");
+    static_assert(!(S0L || WT || QMW) || (FROM_SLABS && KCT == 2 && !RAG), "S0 last / write-through stores / whole-sample Qm: the two-slab two-launch form only, on the grid");
+    // barriers between staging and the W step: LDS-only where S0 is in flight across them
+#define PRE_W_BARRIER()                                                                   \
+    do {                                                                                  \
+        if constexpr (S0L) asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); \
+        else __syncthreads();                                                             \
+    } while (0)
 #define STAMP(k)                                                                          \
     do {                                                                                  \
         if (stamps && threadIdx.x == 0) stamps[(size_t)blockIdx.x * 8 + (k)] = __builtin_amdgcn_s_memrealtime(); \
@@ -564,18 +619,20 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(FROM_SLABS 
     const int Jt = J0 + 32 * ((t == 1 && two) ? 1 : 0);
     const int tl = tid & 255;
     v2d s0v[2];
+    if constexpr (!S0L) {
 #pragma unroll
-    for (int q = 0; q < 2; ++q) {
-        const int unit = q * 256 + tl, i = unit >> 4, j2 = unit & 15;
-        const int gr = (RAG && I0 + i >= D) ? D - 1 : I0 + i, gc = (RAG && Jt + 2 * j2 >= D) ? D - 2 : Jt + 2 * j2;
-        s0v[q] = (dbg & 2) ? (v2d){1.0, 1.0} : *reinterpret_cast<const v2d*>(S0 + (size_t)gr * lds0 + gc);
+        for (int q = 0; q < 2; ++q) {
+            const int unit = q * 256 + tl, i = unit >> 4, j2 = unit & 15;
+            const int gr = (RAG && I0 + i >= D) ? D - 1 : I0 + i, gc = (RAG && Jt + 2 * j2 >= D) ? D - 2 : Jt + 2 * j2;
+            s0v[q] = (dbg & 2) ? (v2d){1.0, 1.0} : *reinterpret_cast<const v2d*>(S0 + (size_t)gr * lds0 + gc);
+        }
     }
     const int X0 = (fold == 2) ? J0 + 32 : I0;   // FOLD: the folded diagonal tile is S[X0 .. X0 + 31][X0 .. X0 + 31], unit = tid
     v2d s0x = {0.0, 0.0};
-    if constexpr (FOLD) {
+    if constexpr (FOLD && !S0L) {
         if (fold) s0x = *reinterpret_cast<const v2d*>(S0 + (size_t)(X0 + (tid >> 4)) * lds0 + X0 + 2 * (tid & 15));
     }
-    __builtin_amdgcn_sched_barrier(0);           // keep the HBM loads of S0 ahead of the L2-resident staging loads
+    if constexpr (!S0L) __builtin_amdgcn_sched_barrier(0);   // keep the HBM loads of S0 ahead of the L2-resident staging loads
     v2d stg[UPT];
     double dmu_part = 0.0;
     v2d dmuI = {0.0, 0.0};                       // FROM_SLABS: dmu of this thread's unit of block I (the mean, diagonal workgroups)
@@ -596,8 +653,12 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(FROM_SLABS 
         v2d qg[NQG], qm[2];
 #pragma unroll
         for (int k = 0; k < NQG; ++k) qg[k] = ld16(fs.Qg, qg0 + 16u * (unsigned)(ln + 16 * k < nqg ? ln + 16 * k : nqg - 1));
+        [[maybe_unused]] double mvq = 0.0;
+        if constexpr (QMW) mvq = fs.Qm[b];
+        else {
 #pragma unroll
-        for (int k = 0; k < 2; ++k) qm[k] = ld16(fs.Qm, qm0 + 16u * (unsigned)(ln + 16 * k < nqm ? ln + 16 * k : nqm - 1));
+            for (int k = 0; k < 2; ++k) qm[k] = ld16(fs.Qm, qm0 + 16u * (unsigned)(ln + 16 * k < nqm ? ln + 16 * k : nqm - 1));
+        }
         const int col[3] = {I0 + c2, J0 + c2, J0 + 32 + c2};
         const size_t slab = (size_t)B * D;
         v2d xv[3], m0[3], sl[3][KCT];
@@ -613,6 +674,20 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(FROM_SLABS 
         if constexpr (KCT == 2) {                // one batch: the second column block goes out with everything else
             if (two) load_block(2);
         }
+        if constexpr (S0L) {                     // the S0 units: the last global loads of the kernel (2, and a third with FOLD);
+            // (the dbg & 2 ablation of the record form is not honoured here: the "cov_dbg" diagnostic never takes this route)
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int q = 0; q < 2; ++q) {
+                const int unit = q * 256 + tl;
+                s0v[q] = *reinterpret_cast<const v2d*>(S0 + (size_t)(I0 + (unit >> 4)) * lds0 + Jt + 2 * (unit & 15));
+            }
+            if constexpr (FOLD) {
+                const int xr = fold ? X0 + (tid >> 4) : I0 + ((256 + tl) >> 4), xc = fold ? X0 + 2 * (tid & 15) : Jt + 2 * (tl & 15);
+                s0x = *reinterpret_cast<const v2d*>(S0 + (size_t)xr * lds0 + xc);
+            }
+            __builtin_amdgcn_sched_barrier(0);
+        }
         double gs = 0.0, ms = 0.0;               // this lane's share of sample b's partial dots, in unit order
 #pragma unroll
         for (int k = 0; k < NQG; ++k) {
@@ -620,11 +695,13 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(FROM_SLABS 
             gs += in ? qg[k].x : 0.0;
             gs += in ? qg[k].y : 0.0;
         }
+        if constexpr (!QMW) {
 #pragma unroll
-        for (int k = 0; k < 2; ++k) {
-            const bool in = ln + 16 * k < nqm;
-            ms += in ? qm[k].x : 0.0;
-            ms += in ? qm[k].y : 0.0;
+            for (int k = 0; k < 2; ++k) {
+                const bool in = ln + 16 * k < nqm;
+                ms += in ? qm[k].x : 0.0;
+                ms += in ? qm[k].y : 0.0;
+            }
         }
         // SECOND batch (KCT = 4), behind the sums (the empty asm pins them in front of it): the second column block, which is staged
         // last, takes the registers the partials held.  (block-uniform: the single-tile workgroups have no second column block)
@@ -633,11 +710,19 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(FROM_SLABS 
             if (two) load_block(2);
         }
         // the scalars of sample b, by the expressions of k_gsm_scalars_fast
-        const double gSg = row16_sum(gs), mv = row16_sum(ms);
+        const double gSg = row16_sum(gs);
+        double mv;
+        if constexpr (QMW) mv = mvq;
+        else mv = row16_sum(ms);
         const double rho = 0.5 * sqrt(1.0 + 4.0 * (gSg + mv * mv)) - 0.5;
         const double den = 1.0 + rho + mv;
         double beta = 1.0 / (1.0 + rho), c = (gSg - mv) / den;
-        if (stamps) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); STAMP(1); }
+        if (stamps) {                            // "loads landed": with S0 last, the staged units -- the S0 units stay outstanding
+            if constexpr (!S0L) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            else if constexpr (FOLD) asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
+            else asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
+            STAMP(1);
+        }
 #pragma unroll
         for (int cb = 0; cb < 3; ++cb)
             if (cb < 2 || two) {
@@ -709,7 +794,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(FROM_SLABS 
     v4d xaccd = {0.0, 0.0, 0.0, 0.0}, xacce = {0.0, 0.0, 0.0, 0.0};   // FOLD: the folded tile's chains
 #pragma unroll
     for (int pass = 0; pass < NPASS; ++pass) {
-        if (pass > 0) __syncthreads();           // the previous pass's operand reads are done
+        if (pass > 0) PRE_W_BARRIER();           // the previous pass's operand reads are done
         if constexpr (!FROM_SLABS) {             // (FROM_SLABS staged its tiles above)
 #pragma unroll
             for (int q = 0; q < UPT; ++q) {
@@ -720,7 +805,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(FROM_SLABS 
                     *reinterpret_cast<v2d*>(smem + tile * TILE + (b % SBP) * RS + 2 * (u & 15)) = (!RAG || b < B) ? stg[q] : (v2d){0.0, 0.0};
             }
         }
-        __syncthreads();
+        PRE_W_BARRIER();
         if (pass == 0) STAMP(2);
         double ad[NS], ae[NS], bd[NS], be[NS];
         if (mine) {
@@ -766,7 +851,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(FROM_SLABS 
     // ---- stores through LDS, 16 B per lane: the update tile U_t = (D_I^T D_J - E_I^T E_J)/B goes to LDS in accumulator
     // layout; W_t = S0[I, J_t] + U_t is formed in store layout (row segments of 256 B), stored, written back to LDS, and
     // the mirror S[J_t, I] = W_t^T is read from there by columns (row stride 33: conflict-free both ways)
-    __syncthreads();                             // everyone is done reading the factor tiles
+    PRE_W_BARRIER();                             // everyone is done reading the factor tiles
     double* LW = smem + t * 32 * 33;             // [2][32 x 33]
     if (mine) {
 #pragma unroll
@@ -785,7 +870,16 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(FROM_SLABS 
         if (fold && tid < NU) *reinterpret_cast<v2d*>(smem + MUO + (tid >> 4) * 32 + 2 * (tid & 15)) = dmuX;
     }
     if (stamps) STAMP(3);
-    __syncthreads();
+    PRE_W_BARRIER();
+    if constexpr (S0L) {                         // "S0 landed": the first wait that reaches 0 stands here, in front of the W step
+        if (stamps) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); STAMP(6); }
+    }
+    // WT: the stores of S go write-through through a buffer descriptor over S (aux 16 = sc1)
+    [[maybe_unused]] __amdgpu_buffer_rsrc_t srs;
+    if constexpr (WT) srs = __builtin_amdgcn_make_buffer_rsrc(S, 0, (int)(((size_t)(D - 1) * lds + D) * sizeof(double)), 0x00020000);
+    [[maybe_unused]] auto store_wt = [&](size_t off, v2d v) {
+        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(v4u, v), srs, (int)(off * sizeof(double)), 0, 16);
+    };
     if constexpr (FOLD) {
         if (fold && tid < 256) {
             double part = 0.0;
@@ -801,7 +895,8 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(FROM_SLABS 
             v2d wv2;
             wv2.x = s0v[q].x + LW[i * 33 + 2 * j2];
             wv2.y = s0v[q].y + LW[i * 33 + 2 * j2 + 1];
-            if (!RAG || (I0 + i < D && Jt + 2 * j2 < D)) *reinterpret_cast<v2d*>(S + (size_t)(I0 + i) * lds + Jt + 2 * j2) = wv2;
+            if constexpr (WT) store_wt((size_t)(I0 + i) * lds + Jt + 2 * j2, wv2);
+            else if (!RAG || (I0 + i < D && Jt + 2 * j2 < D)) *reinterpret_cast<v2d*>(S + (size_t)(I0 + i) * lds + Jt + 2 * j2) = wv2;
             LW[i * 33 + 2 * j2] = wv2.x;
             LW[i * 33 + 2 * j2 + 1] = wv2.y;
         }
@@ -816,7 +911,8 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(FROM_SLABS 
             v2d m2;
             m2.x = LW[(2 * i2) * 33 + j];
             m2.y = LW[(2 * i2 + 1) * 33 + j];
-            if (!RAG || (Jt + j < D && I0 + 2 * i2 < D)) *reinterpret_cast<v2d*>(S + (size_t)(Jt + j) * lds + I0 + 2 * i2) = m2;
+            if constexpr (WT) store_wt((size_t)(Jt + j) * lds + I0 + 2 * i2, m2);
+            else if (!RAG || (Jt + j < D && I0 + 2 * i2 < D)) *reinterpret_cast<v2d*>(S + (size_t)(Jt + j) * lds + I0 + 2 * i2) = m2;
         }
     }
     if constexpr (FOLD) {
@@ -832,7 +928,8 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(FROM_SLABS 
             v2d wv2;
             wv2.x = s0x.x + smem[LXO + i * 33 + 2 * j2];
             wv2.y = s0x.y + smem[LXO + i * 33 + 2 * j2 + 1];
-            *reinterpret_cast<v2d*>(S + (size_t)(X0 + i) * lds + X0 + 2 * j2) = wv2;
+            if constexpr (WT) store_wt((size_t)(X0 + i) * lds + X0 + 2 * j2, wv2);
+            else *reinterpret_cast<v2d*>(S + (size_t)(X0 + i) * lds + X0 + 2 * j2) = wv2;
         }
     }
     if (diag) {
@@ -859,6 +956,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(FROM_SLABS 
     STAMP(4);
     if (stamps) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); STAMP(5); }
 #undef STAMP
+#undef PRE_W_BARRIER
 }
 
 // =====================================================================================
@@ -1286,7 +1384,7 @@ void gsmvi_launch_panel_fast(hipStream_t st, hipEvent_t* ev, int MT, dim3 grid, 
 // the MT = 2 form on 128 workgroups staged 128 KB per workgroup and was 2 us slower per launch).
 void gsmvi_launch_panel_fast_part(hipStream_t st, hipEvent_t* ev, dim3 grid, int D, int B, const double* G, int ldg,
                                   const double* S0, int lds0, double* Pp, int chunks_per_wg, const double* X, int ldx,
-                                  const double* mu0, double* Qg, double* Qm, int chw, unsigned long long* stamps) {
+                                  const double* mu0, double* Qg, double* Qm, int chw, bool qm_whole, unsigned long long* stamps) {
     gsmvi_panel_extras px;                     // (PART's arguments ride in free members: gsmvi_ctx.h)
     px.sj_src = X;
     px.sj_len = ldx;
@@ -1295,7 +1393,10 @@ void gsmvi_launch_panel_fast_part(hipStream_t st, hipEvent_t* ev, dim3 grid, int
     px.mfin = Qm;
 #define PFQ(MTV, CW) GSMVI_LAUNCH((k_panel_fast<MTV, false, CW, false, false, false, true>), grid, dim3(512), 0, st, ev, D, B, G, ldg, \
                                   nullptr, 1.0, S0, lds0, Pp, chunks_per_wg, D, stamps, nullptr, 0, nullptr, px)
-    if (chw == 512) PFQ(1, 512);
+    if (chw == 512 && qm_whole)             // one Qm value per sample from the idle slab-1 workgroups (QMW above)
+        GSMVI_LAUNCH((k_panel_fast<1, false, 512, false, false, false, true, true>), grid, dim3(512), 0, st, ev, D, B, G, ldg, nullptr, 1.0, S0,
+                     lds0, Pp, chunks_per_wg, D, stamps, nullptr, 0, nullptr, px);
+    else if (chw == 512) PFQ(1, 512);
     else { if (B == 16) PFQ(1, 256); else PFQ(2, 256); }
 #undef PFQ
 }
@@ -1391,15 +1492,27 @@ bool gsmvi_launch_gsm_cov_sym(hipStream_t st, hipEvent_t* ev, int D, int B, cons
 // fold (round 9): the grid is the two-tile workgroups alone, the diagonal leftovers are third tiles of their hosts (FOLD above).
 void gsmvi_launch_gsm_cov_sym_slabs(hipStream_t st, hipEvent_t* ev, int D, int B, const gsm_slab_src& fs, const double* mu0,
                                     const double* S0, int lds0, double* S, int lds, double* mu_out, int kct, bool fold,
-                                    unsigned long long* stamps) {
+                                    bool s0_last, bool store_wt, bool qm_whole, unsigned long long* stamps) {
     const dim3 grid(fold ? gsmvi_cov_sym_pairs(D / 32) : cov_sym_grid(D / 32));
     const double invB = 1.0 / (double)B;
-#define CSS(SBV, KV, FV)                                                                                                  \
-    GSMVI_LAUNCH((k_gsm_cov_sym<SBV, false, true, KV, FV>), grid, dim3(512), 0, st, ev, D, B, invB, nullptr, 0, mu0, S0, lds0, S, lds, mu_out, \
-                 0, stamps, fs)
-#define CSF(SBV, KV) do { if (fold) CSS(SBV, KV, true); else CSS(SBV, KV, false); } while (0)
-    if (kct == 2) { if (B == 16) CSF(16, 2); else CSF(32, 2); }
-    else { if (B == 16) CSF(16, 4); else CSF(32, 4); }
+#define CSQ(SBV, KV, FV, LV, WV, QV)                                                                                      \
+    GSMVI_LAUNCH((k_gsm_cov_sym<SBV, false, true, KV, FV, LV, WV, QV>), grid, dim3(512), 0, st, ev, D, B, invB, nullptr, 0, mu0, S0, lds0, S, \
+                 lds, mu_out, 0, stamps, fs)
+    // (whole-sample Qm, "panel_qm_whole": kct == 2 only, the caller passes false otherwise)
+#define CSS(SBV, KV, FV, LV, WV) do { if (KV == 2 && qm_whole) CSQ(SBV, 2, FV, LV, WV, true); else CSQ(SBV, KV, FV, LV, WV, false); } while (0)
+#define CSF(SBV, KV, LV, WV) do { if (fold) CSS(SBV, KV, true, LV, WV); else CSS(SBV, KV, false, LV, WV); } while (0)
+    // round 10 (kct == 2 only; the caller passes false otherwise): S0 issued and waited for last, write-through stores of S
+#define CSL(SBV)                                                                                                          \
+    do {                                                                                                                  \
+        if (s0_last && store_wt) CSF(SBV, 2, true, true);                                                                 \
+        else if (s0_last) CSF(SBV, 2, true, false);                                                                       \
+        else if (store_wt) CSF(SBV, 2, false, true);                                                                      \
+        else CSF(SBV, 2, false, false);                                                                                   \
+    } while (0)
+    if (kct == 2) { if (B == 16) CSL(16); else CSL(32); }
+    else { if (B == 16) CSF(16, 4, false, false); else CSF(32, 4, false, false); }
+#undef CSL
 #undef CSF
 #undef CSS
+#undef CSQ
 }

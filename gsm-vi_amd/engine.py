@@ -539,7 +539,8 @@ class HipEngine:
                  "batched_lbfgs": 0x40000, "batched_laplace": 0x80000, "batched_predict": 0x100000,
                  "batched_psis": 0x200000, "batched_loo": 0x400000, "gsm_two_launch": 0x800000,
                  "batched_softmax": 0x1000000, "panel_chunk512": 0x2000000, "batched_pathfinder": 0x4000000,
-                 "cov_fold_diag": 0x8000000, "batched_softmax_laplace": 0x10000000}
+                 "cov_fold_diag": 0x8000000, "batched_softmax_laplace": 0x10000000, "cov_s0_last": 0x20000000,
+                 "cov_store_wt": 0x40000000, "panel_qm_whole": 0x80000000}
     PATH_GENERIC_MASK = 0x4 | 0x10 | 0x40 | 0x100 | 0x400 | 0x1000
 
     def last_path(self, reset=True):

@@ -103,6 +103,11 @@ int gsmvi_destroy(gsmvi_ctx* ctx);
  * round 9: "cov_fold_diag" (two-launch form: the diagonal leftover tiles of the covariance launch ride as third tiles in
  * two-tile workgroups instead of being workgroups of their own; 1 = where the two-tile workgroups alone fill the device,
  * i.e. D = 1024 on 256 CUs, default; 0 = never; 2 = at every two-launch shape; results are bit for bit the same);
+ * round 10, both for the two-slab covariance launch (D = 1024, no explicit "panel_kc") and both with bit-identical results:
+ * "cov_s0_last" (1 = the Sigma0 tile is the last load issued and the last one waited for, behind the staging and the MFMAs),
+ * "cov_store_wt" (1 = Sigma' is stored write-through, where D * lds * 8 < 2^31; the lines do not stay in the L2);
+ * "panel_qm_whole" (same route; 1 = the product leaves one (mu0 - x_b).g_b per sample instead of D / 16 pieces that every
+ * covariance workgroup re-sums; another summation order, so mu and Sigma' move at rounding level; default 0);
  * diagnostics "timeline", "cov_dbg"
  * (see gsmvi_hip_debug.h). */
 int gsmvi_set_tuning(gsmvi_ctx* ctx, const char* name, int value);
@@ -298,6 +303,9 @@ int gsmvi_get_profile(gsmvi_ctx* ctx, float* ms, int n);
 #define GSMVI_PATH_BATCHED_PATHFINDER 0x4000000u /* k_pf_propose / k_pf_select: the batched Pathfinder initialiser                  */
 #define GSMVI_PATH_COV_FOLD_DIAG 0x8000000u /* the two-launch covariance launch ran without single-tile workgroups: diagonal leftovers folded ("cov_fold_diag") */
 #define GSMVI_PATH_BATCHED_SOFTMAX_LAPLACE 0x10000000u /* k_softmax_laplace_batched: the batched multinomial logit Hessian and Newton step */
+#define GSMVI_PATH_COV_S0_LAST 0x20000000u /* the two-slab covariance launch issued and waited for its S0 tile last ("cov_s0_last") */
+#define GSMVI_PATH_COV_STORE_WT 0x40000000u /* the two-slab covariance launch stored S write-through ("cov_store_wt") */
+#define GSMVI_PATH_PANEL_QM_WHOLE 0x80000000u /* the two-slab product left one Qm value per sample ("panel_qm_whole") */
 #define GSMVI_PATH_GENERIC_MASK (0x0004u | 0x0010u | 0x0040u | 0x0100u | 0x0400u | 0x1000u)
 int gsmvi_last_path(gsmvi_ctx* ctx, unsigned* bits, int reset);
 

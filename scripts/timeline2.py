@@ -67,6 +67,10 @@ for i in order[-4:]:
     print("   ", int(i), " ".join(f"{v:6.2f}" for v in us[i, :6]))
 ph = np.diff(us[:, :6], axis=1)
 print("phase medians (loads, stage, mfma, mirror, drain):", np.round(np.median(ph, axis=0), 2), " p95:", np.round(np.percentile(ph, 95, axis=0), 2))
+if (a[live][:, 6] > 0).all():    # "cov_s0_last": [1] = staged units landed (S0 still in flight), [6] = S0 landed, right before the W step
+    s0 = us[:, 6]
+    print("S0 landed: after start", np.round(np.median(s0 - us[:, 0]), 2), " after 'loads landed'", np.round(np.median(s0 - us[:, 1]), 2),
+          " after the MFMAs", np.round(np.median(s0 - us[:, 3]), 2), " p95 of the last:", np.round(np.percentile(s0 - us[:, 3], 95), 2))
 print("blocks >= 256 (single-tile): end median", np.median(end[256:]) if len(end) > 256 else None, " blocks < 256: end median", np.median(end[:256]), "p95", np.percentile(end[:256], 95))
 a = st[0]; live = a[:, 0] > 0; usp = (a[live] - t0) / 100.0
 php = np.diff(usp[:, :4], axis=1)
