@@ -40,6 +40,9 @@ Mirrors the reference's public surface for the hot path (reference file:line):
     BatchedGLMTarget.loo (PSIS leave-one-out of K
     fitted GLM posteriors: elpd_loo, p_loo, se and
     the pointwise khat; one launch after psis_batched) examples/example_gsm.py:34-35, comparing fitted models; no reference twin
+    psis_loo_softmax_batched (the same for K fitted
+    multinomial logit posteriors: the class-coupled
+    pointwise likelihood on the fp64 MFMA; one launch) examples/example_gsm.py:34-35, comparing fitted models; no reference twin
     lbfgs_init_batched (the L-BFGS initialiser
     for K problems at once, D <= 64: one launch
     per function evaluation after lp_g and lp)   gsmvi/initializers.py:5-17
@@ -78,6 +81,7 @@ from .initializers import laplace_init_softmax_batched                        # 
 from .initializers import pathfinder_init_batched, PathfinderBatchedResult    # noqa: F401
 from .diagnostics import psis_batched, psis_weights_batched, PSISBatchedResult   # noqa: F401
 from .diagnostics import psis_loo_batched, LOOBatchedResult          # noqa: F401
+from .diagnostics import psis_loo_softmax_batched                    # noqa: F401
 from .advi import ADVI                                               # noqa: F401
 
 __version__ = "0.1.0"

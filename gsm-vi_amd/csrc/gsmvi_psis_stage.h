@@ -1,7 +1,8 @@
 // The PSIS stage of the batched diagnostics: steps 1-8 of the definition in include/gsmvi_hip.h (gsmvi_psis_weights_batched_f64)
 // on the S log ratios that one 256-thread workgroup holds in LDS.  One copy, called by k_psis_batched<PS_WEIGHTS>,
-// k_psis_batched<PS_FUSED> (gsmvi_psis_batched.hip: once per problem) and k_psis_loo_batched (gsmvi_psis_loo_batched.hip: once
-// per observation); DESIGN.md section 9.
+// k_psis_batched<PS_FUSED> (gsmvi_psis_batched.hip: once per problem), k_psis_loo_batched (gsmvi_psis_loo_batched.hip: once per
+// observation) and its twin for the multinomial logit, k_psis_loo_softmax_batched (gsmvi_psis_loo_softmax_batched.hip, which carries
+// a copy of k_psis_loo_batched's per-observation statements around the call: change both together); DESIGN.md section 9.
 // In LDS: the S ratios padded with +inf to S2 = the next power of two, their S2 indices, the S normalised weights in row order,
 // the tail (at most 192 exceedances) and the 43 candidates of its fit.  Two reductions (non-finite count, maximum); a bitonic
 // network on (value, index) pairs, ascending by value then by index -- numpy's stable argsort, so ties fall the same way on

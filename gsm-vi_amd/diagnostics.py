@@ -5,7 +5,8 @@ constant; this says per problem, on one scale, whether q_k can be trusted: the s
 effective sample size, an estimate of the log normalising constant, and importance-corrected moments.  ``psis_loo_batched`` takes
 the same draws one step further for the GLM targets: the PSIS leave-one-out log predictive density of every observation
 (csrc/gsmvi_psis_loo_batched.hip; Vehtari, Gelman, Gabry 2017; Magnusson, Andersen, Jonasson, Vehtari 2019), the number by which
-fitted models are compared."""
+fitted models are compared; ``psis_loo_softmax_batched`` is the same for ``BatchedSoftmaxTarget``
+(csrc/gsmvi_psis_loo_softmax_batched.hip)."""
 from dataclasses import dataclass
 
 import numpy as np
@@ -153,71 +154,34 @@ class LOOBatchedResult:
     nlaunch: int
 
 
-def _reusable(psis, K, D, eng):
+def _reusable(psis, K, D, eng, fn="psis_loo_batched"):
     """(X, logr, lw) of a ``PSISBatchedResult`` that still holds its device tensors, else ValueError naming what is missing (a
     field that is None, or a host copy where the engine works on device tensors)"""
     import torch
     on_device = isinstance(getattr(eng, "device", None), torch.device)
     if not isinstance(psis, PSISBatchedResult):
-        raise ValueError(f"psis_loo_batched: psis must be a PSISBatchedResult of psis_batched(..., as_torch=True), got {type(psis).__name__}")
+        raise ValueError(f"{fn}: psis must be a PSISBatchedResult of psis_batched(..., as_torch=True), got {type(psis).__name__}")
     parts = (("samples", psis.samples), ("log_ratios", psis.log_ratios), ("log_weights", psis.log_weights))
     missing = [n for n, t in parts if t is None or (on_device and not isinstance(t, torch.Tensor))]
     if missing:
-        raise ValueError(f"psis_loo_batched: psis holds no device tensor for {', '.join(missing)}: give the result of "
+        raise ValueError(f"{fn}: psis holds no device tensor for {', '.join(missing)}: give the result of "
                          "psis_batched(..., as_torch=True)")
     X, logr, lw = (t for _, t in parts)
     if len(_shape(X)) != 3 or _shape(X)[0] != K or _shape(X)[2] != D:
-        raise ValueError(f"psis_loo_batched: psis.samples must be ({K}, S, {D}), got {_shape(X)}")
+        raise ValueError(f"{fn}: psis.samples must be ({K}, S, {D}), got {_shape(X)}")
     S = _shape(X)[1]
     if _shape(logr) != (K, S) or _shape(lw) != (K, S):
-        raise ValueError(f"psis_loo_batched: psis.log_ratios and psis.log_weights must be {(K, S)}, got {_shape(logr)} and {_shape(lw)}")
+        raise ValueError(f"{fn}: psis.log_ratios and psis.log_weights must be {(K, S)}, got {_shape(logr)} and {_shape(lw)}")
     return X, logr, lw
 
 
-def psis_loo_batched(target, mean, cov, keys, num_draws=1024, *, call=0, psis=None, pointwise_loglik=False, as_torch=False,
-                     engine=None):
-    """PSIS leave-one-out of K fitted GLM posteriors q_k = N(mean_k, cov_k): returns a ``LOOBatchedResult``.
-
-    ``target`` is the ``BatchedGLMTarget`` or ``BatchedLogisticTarget`` the posteriors were fitted to (its A, y, offset, counts
-    and noise precision are the model; anything else raises TypeError); mean (K, D), cov (K, D, D) and ``keys`` are
-    ``psis_batched``'s.  Without ``psis`` it first runs ``psis_batched(target.lp, mean, cov, keys, num_draws, call=call,
-    moments=False, as_torch=True)`` (two launches and one call of ``target.lp``); with ``psis``, the result of such a call, its
-    draws, ratios and weights are reused (``num_draws`` and ``call`` are then not used).  Then one launch,
-    gsmvi_psis_loo_batched_f64: the pointwise log likelihood l_si of every draw on the fp64 MFMA, and per observation the PSIS
-    stage on the ratios logr_s - l_si and the two log-sum-exps (the definition is in include/gsmvi_hip.h).  The per-problem
-    sums are torch reductions of the (K, N) outputs under the mask of ``target.counts``.  ``pointwise_loglik`` also returns the
-    (K, N, S) block l_si (K * N * S * 8 bytes).  mean and cov are only read.
-    A mean that is not (K, D) of the target, a cov that is not (K, D, D), ``num_draws`` outside 5..4096, keys of another length
-    than K, or a ``psis`` that is not a ``PSISBatchedResult`` holding device tensors of the right shapes raise ValueError before
-    any device work."""
+def _loo_result(eng, target, psis, S, nlaunch, as_torch, elpd_i, lpd_i, khat, ess, info, loglik):
+    """The ``LOOBatchedResult`` of the pointwise outputs of a leave-one-out launch (``psis_loo_batched`` and
+    ``psis_loo_softmax_batched``): the per-problem summaries are torch reductions under the mask of the valid rows of
+    ``target.counts`` (a stand-in engine's numpy arrays: on the host)"""
     import torch
-    from .targets import BatchedGLMTarget
-    if not isinstance(target, BatchedGLMTarget):
-        raise TypeError(f"psis_loo_batched: target must be a BatchedGLMTarget or BatchedLogisticTarget, got {type(target).__name__}")
-    K, N, D = target.K, target.N, target.D
-    if _shape(mean) != (K, D):
-        raise ValueError(f"psis_loo_batched: mean must be (K, D) = {(K, D)} of the target, got {_shape(mean)}")
-    if _shape(cov) != (K, D, D):
-        raise ValueError(f"psis_loo_batched: cov must be {(K, D, D)}, got {_shape(cov)}")
-    keys_l = [int(k) for k in np.asarray(list(keys) if isinstance(keys, (list, tuple, range)) else _to_numpy(keys)).reshape(-1)]
-    if len(keys_l) != K:
-        raise ValueError(f"psis_loo_batched: {len(keys_l)} keys for K = {K} problems")
-    eng = engine if engine is not None else target.engine
-    if psis is None:
-        S = int(num_draws)
-        if S != num_draws or not MIN_DRAWS <= S <= MAX_DRAWS:
-            raise ValueError(f"psis_loo_batched: num_draws = {num_draws} is outside {MIN_DRAWS} <= num_draws <= {MAX_DRAWS}")
-        psis = psis_batched(target.lp, mean, cov, keys_l, S, call=call, moments=False, as_torch=True, engine=eng)
-        nlaunch = psis.nlaunch + 1
-    else:
-        nlaunch = 1
-    X, logr, lw = _reusable(psis, K, D, eng)
-    S = _shape(X)[1]
-    elpd_i, lpd_i, khat, ess, info, loglik = eng.psis_loo_batched(
-        X, logr, lw, target.A, target.y, target.family, offset=target.offset, counts=target.counts,
-        noise_prec=target.noise_precision, pointwise_loglik=bool(pointwise_loglik))
+    K, N = target.K, target.N
     thr = khat_threshold(S)
-    # the per-problem summaries: torch reductions under the mask of the valid rows (a stand-in engine's numpy arrays: on the host)
     ten = lambda a: a if isinstance(a, torch.Tensor) else torch.as_tensor(np.asarray(a))      # noqa: E731
     e, lp_, kh, inf = ten(elpd_i), ten(lpd_i), ten(khat), ten(info)
     nk = ten(target.counts).to(e.device).clamp(0, N) if target.counts is not None else torch.full((K,), N, device=e.device)
@@ -237,3 +201,82 @@ def psis_loo_batched(target, mean, cov, keys, num_draws=1024, *, call=0, psis=No
         out = {n: None if t is None else np.asarray(eng.to_numpy(t)) for n, t in out.items()}
         out["info"] = out["info"].astype(np.int64)
     return LOOBatchedResult(psis=psis, threshold=thr, nlaunch=nlaunch, **out)
+
+
+def _loo_draws(fn, target, mean, cov, keys, num_draws, call, psis, engine):
+    """The argument checks and the problem-level run shared by the two leave-one-out functions: (eng, psis, nlaunch, X, logr, lw)"""
+    K, D = target.K, target.D
+    if _shape(mean) != (K, D):
+        raise ValueError(f"{fn}: mean must be (K, D) = {(K, D)} of the target, got {_shape(mean)}")
+    if _shape(cov) != (K, D, D):
+        raise ValueError(f"{fn}: cov must be {(K, D, D)}, got {_shape(cov)}")
+    keys_l = [int(k) for k in np.asarray(list(keys) if isinstance(keys, (list, tuple, range)) else _to_numpy(keys)).reshape(-1)]
+    if len(keys_l) != K:
+        raise ValueError(f"{fn}: {len(keys_l)} keys for K = {K} problems")
+    eng = engine if engine is not None else target.engine
+    if psis is None:
+        S = int(num_draws)
+        if S != num_draws or not MIN_DRAWS <= S <= MAX_DRAWS:
+            raise ValueError(f"{fn}: num_draws = {num_draws} is outside {MIN_DRAWS} <= num_draws <= {MAX_DRAWS}")
+        psis = psis_batched(target.lp, mean, cov, keys_l, S, call=call, moments=False, as_torch=True, engine=eng)
+        nlaunch = psis.nlaunch + 1
+    else:
+        nlaunch = 1
+    X, logr, lw = _reusable(psis, K, D, eng, fn)
+    return eng, psis, nlaunch, X, logr, lw
+
+
+def psis_loo_batched(target, mean, cov, keys, num_draws=1024, *, call=0, psis=None, pointwise_loglik=False, as_torch=False,
+                     engine=None):
+    """PSIS leave-one-out of K fitted GLM posteriors q_k = N(mean_k, cov_k): returns a ``LOOBatchedResult``.
+
+    ``target`` is the ``BatchedGLMTarget`` or ``BatchedLogisticTarget`` the posteriors were fitted to (its A, y, offset, counts
+    and noise precision are the model; anything else raises TypeError); mean (K, D), cov (K, D, D) and ``keys`` are
+    ``psis_batched``'s.  Without ``psis`` it first runs ``psis_batched(target.lp, mean, cov, keys, num_draws, call=call,
+    moments=False, as_torch=True)`` (two launches and one call of ``target.lp``); with ``psis``, the result of such a call, its
+    draws, ratios and weights are reused (``num_draws`` and ``call`` are then not used).  Then one launch,
+    gsmvi_psis_loo_batched_f64: the pointwise log likelihood l_si of every draw on the fp64 MFMA, and per observation the PSIS
+    stage on the ratios logr_s - l_si and the two log-sum-exps (the definition is in include/gsmvi_hip.h).  The per-problem
+    sums are torch reductions of the (K, N) outputs under the mask of ``target.counts``.  ``pointwise_loglik`` also returns the
+    (K, N, S) block l_si (K * N * S * 8 bytes).  mean and cov are only read.
+    A mean that is not (K, D) of the target, a cov that is not (K, D, D), ``num_draws`` outside 5..4096, keys of another length
+    than K, or a ``psis`` that is not a ``PSISBatchedResult`` holding device tensors of the right shapes raise ValueError before
+    any device work."""
+    from .targets import BatchedGLMTarget
+    if not isinstance(target, BatchedGLMTarget):
+        raise TypeError(f"psis_loo_batched: target must be a BatchedGLMTarget or BatchedLogisticTarget, got {type(target).__name__}")
+    eng, psis, nlaunch, X, logr, lw = _loo_draws("psis_loo_batched", target, mean, cov, keys, num_draws, call, psis, engine)
+    S = _shape(X)[1]
+    elpd_i, lpd_i, khat, ess, info, loglik = eng.psis_loo_batched(
+        X, logr, lw, target.A, target.y, target.family, offset=target.offset, counts=target.counts,
+        noise_prec=target.noise_precision, pointwise_loglik=bool(pointwise_loglik))
+    return _loo_result(eng, target, psis, S, nlaunch, as_torch, elpd_i, lpd_i, khat, ess, info, loglik)
+
+
+def psis_loo_softmax_batched(target, mean, cov, keys, num_draws=1024, *, call=0, psis=None, pointwise_loglik=False, as_torch=False,
+                             engine=None):
+    """PSIS leave-one-out of K fitted multinomial logit posteriors q_k = N(mean_k, cov_k): returns a ``LOOBatchedResult``, the
+    twin of ``psis_loo_batched`` for the class-coupled likelihood.
+
+    ``target`` is the ``BatchedSoftmaxTarget`` the posteriors were fitted to (its A, labels, number of classes and counts are the
+    model; anything else raises TypeError); mean (K, D), D = (C - 1) P, cov (K, D, D) and ``keys`` are ``psis_batched``'s.
+    Without ``psis`` it first runs ``psis_batched(target.lp, mean, cov, keys, num_draws, call=call, moments=False,
+    as_torch=True)`` (two launches and one call of ``target.lp``); with ``psis``, the result of such a call, its draws, ratios
+    and weights are reused (``num_draws`` and ``call`` are then not used).  Then one launch,
+    gsmvi_psis_loo_softmax_batched_f64: per class the linear predictors of every draw on the fp64 MFMA, the pointwise log
+    likelihood l_si = eta_y - m - log sum_c exp(eta_c - m), and per observation the PSIS stage on the ratios logr_s - l_si and the
+    two log-sum-exps (the definition is in include/gsmvi_hip.h).  No (K, N, S) block of log likelihoods and no (K, S, N, C) block
+    of probabilities is formed unless ``pointwise_loglik`` asks for the first (K * N * S * 8 bytes).  The per-problem sums are
+    those of ``psis_loo_batched``.  mean and cov are only read.
+    A mean that is not (K, D) of the target, a cov that is not (K, D, D), ``num_draws`` outside 5..4096, keys of another length
+    than K, or a ``psis`` that is not a ``PSISBatchedResult`` holding device tensors of the right shapes raise ValueError before
+    any device work."""
+    from .targets import BatchedSoftmaxTarget
+    fn = "psis_loo_softmax_batched"
+    if not isinstance(target, BatchedSoftmaxTarget):
+        raise TypeError(f"{fn}: target must be a BatchedSoftmaxTarget, got {type(target).__name__}")
+    eng, psis, nlaunch, X, logr, lw = _loo_draws(fn, target, mean, cov, keys, num_draws, call, psis, engine)
+    S = _shape(X)[1]
+    elpd_i, lpd_i, khat, ess, info, loglik = eng.psis_loo_softmax_batched(
+        X, logr, lw, target.A, target.y, target.C, counts=target.counts, pointwise_loglik=bool(pointwise_loglik))
+    return _loo_result(eng, target, psis, S, nlaunch, as_torch, elpd_i, lpd_i, khat, ess, info, loglik)

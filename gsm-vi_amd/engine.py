@@ -1189,6 +1189,37 @@ class HipEngine:
                    self._ints(info, K * N, "info"))
         return elpd, lpd, khat, ess, info, loglik
 
+    # ---- the same for K fitted multinomial logit posteriors (csrc/gsmvi_psis_loo_softmax_batched.hip) --------------------------
+    def psis_loo_softmax_tile(self, C, P, S):
+        """gsmvi_psis_loo_softmax_tile: the observations one workgroup of ``psis_loo_softmax_batched`` takes at (C, P, S); a pure
+        function, no GPU"""
+        return int(self.lib.gsmvi_psis_loo_softmax_tile(int(C), int(P), int(S)))
+
+    def psis_loo_softmax_batched(self, X, logr, lw, A, labels, num_classes, counts=None, pointwise_loglik=False):
+        """PSIS leave-one-out of K fitted multinomial logit posteriors from the draws X (K, S, D) of q_k, D = (C - 1) P
+        class-major, and the problem-level ratios ``logr`` and smoothed weights ``lw`` (K, S) of ``psis_batched`` on the same draws,
+        one launch (gsmvi_psis_loo_softmax_batched_f64; the definition is in include/gsmvi_hip.h)  [no reference twin]: returns
+        what ``psis_loo_batched`` returns, (elpd, lpd, khat, ess (K, N), info (K, N) int32, loglik (K, N, S) or None).  ``A``
+        (K, N, P), ``labels`` (K, N) int32, ``num_classes`` and ``counts`` are ``softmax_batched``'s."""
+        K, S, D = X.shape
+        _, N, P = A.shape
+        Cc = int(num_classes)
+        if Cc < 2 or (Cc - 1) * P != D:
+            raise ValueError(f"expected (num_classes - 1) P = {(Cc - 1) * P} columns, got {D}")
+        assert labels.is_cuda and labels.dtype == torch.int32 and labels.is_contiguous() and tuple(labels.shape) == (K, N), \
+            f"labels: expected a contiguous int32 CUDA tensor of shape {(K, N)}"
+        self._any_ctx()
+        X, logr, lw = X.contiguous(), logr.contiguous(), lw.contiguous()
+        elpd, lpd, khat, ess = self.empty(K, N), self.empty(K, N), self.empty(K, N), self.empty(K, N)
+        info = self.batched_ints(K * N).view(K, N)
+        loglik = self.empty(K, N, S) if pointwise_loglik else None
+        self._call("gsmvi_psis_loo_softmax_batched_f64", K, Cc, P, N, S, self._packed(A, (K, N, P), "A"), _ptr(labels),
+                   self._ints(counts, K, "counts"), self._packed(X, (K, S, D), "X"), self._packed(logr, (K, S), "logr"),
+                   self._packed(lw, (K, S), "lw"), self._dp(loglik, (K, N, S), "loglik"), self._packed(elpd, (K, N), "elpd"),
+                   self._packed(lpd, (K, N), "lpd"), self._packed(khat, (K, N), "khat"), self._packed(ess, (K, N), "ess"),
+                   self._ints(info, K * N, "info"))
+        return elpd, lpd, khat, ess, info, loglik
+
     def bam_update(self, X, G, mu0, S0, reg, jitter=0.0, out=None, flag=None):
         """(mu, S) of BaM [gsmvi/bam.py:72-114]; S symmetrised, jitter on the diagonal."""
         assert X.dim() == 2 and G.dim() == 2            # bam.py:47-48

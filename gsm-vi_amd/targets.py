@@ -418,7 +418,9 @@ class BatchedSoftmaxTarget:
     numpy arrays or tensors in; everything is kept on the device as float64 / int32.  Arguments are validated on the host before
     any device work (ValueError naming the argument and the problems).  It is not a ``BatchedGLMTarget``: there is no offset, and
     ``laplace_init_batched``, ``predict`` and ``psis_loo_batched`` do not take it (TypeError).  Its second-order start is
-    ``laplace_init_softmax_batched``, on the closed-form negative Hessian that ``neg_hessian`` returns.
+    ``laplace_init_softmax_batched``, on the closed-form negative Hessian that ``neg_hessian`` returns, and its PSIS leave-one-out
+    is ``psis_loo_softmax_batched(target, mean, cov, keys, ...)`` (``.loo`` stays ``psis_loo_batched``'s TypeError; there is no
+    ``predict`` yet).
 
     ``lp_g(x, out=None)``: (K, B, D) -> (K, B, D) scores, ``device_native`` and ``graph_safe`` (one capturable launch, no
     allocation with ``out``).  ``lp(x)``: (K, rows, D) -> (K, rows) values; a device tensor or numpy.  ``lp_and_score(x)``:

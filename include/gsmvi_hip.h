@@ -32,6 +32,7 @@
  *   importance diagnostic of K fitted Gaussians (no reference twin)    ->  gsmvi_psis_batched_f64, gsmvi_psis_weights_batched_f64
  *   examples/example_gsm.py:34-35 the comparison of fitted models: the PSIS leave-one-out density of every observation of K fitted
  *   GLMs (no reference twin)                                           ->  gsmvi_psis_loo_batched_f64, gsmvi_psis_loo_tile
+ *   the same for K fitted multinomial logit regressions (no reference twin) -> gsmvi_psis_loo_softmax_batched_f64, gsmvi_psis_loo_softmax_tile
  *   gsmvi/bam.py:72-114       bam_lowrank_update(samples,vs,mu0,S0,reg) ->  gsmvi_bam_update_f64
  *   gsmvi/bam.py:31-69        bam_update(samples,vs,mu0,S0,reg)         ->  gsmvi_bam_update_f64 (same result, K6)
  *
@@ -296,7 +297,7 @@ int gsmvi_get_profile(gsmvi_ctx* ctx, float* ms, int n);
 #define GSMVI_PATH_BATCHED_LAPLACE 0x80000u /* k_laplace_batched: the batched GLM Hessian and Newton step             */
 #define GSMVI_PATH_BATCHED_PREDICT 0x100000u /* k_glm_predict_batched: the batched GLM posterior predictive             */
 #define GSMVI_PATH_BATCHED_PSIS 0x200000u /* k_psis_batched: the batched Pareto-smoothed importance diagnostic            */
-#define GSMVI_PATH_BATCHED_LOO 0x400000u /* k_psis_loo_batched: the batched PSIS leave-one-out                                */
+#define GSMVI_PATH_BATCHED_LOO 0x400000u /* k_psis_loo_batched: the batched PSIS leave-one-out; with GSMVI_PATH_BATCHED_SOFTMAX: k_psis_loo_softmax_batched */
 #define GSMVI_PATH_GSM_TWO_LAUNCH 0x800000u /* the dense GSM update ran as two launches (no k_gsm_scalars_fast, no records)          */
 #define GSMVI_PATH_BATCHED_SOFTMAX 0x1000000u /* k_softmax_batched: the batched multinomial logit target's entry point            */
 #define GSMVI_PATH_PANEL_CHUNK512 0x2000000u /* the two-launch product ran as two slabs of one 512-row chunk each (D = 1024, no explicit "panel_kc") */
@@ -839,6 +840,49 @@ int gsmvi_psis_loo_batched_f64(gsmvi_ctx* ctx, void* stream, int family, int64_t
                                const double* y, const double* offset, const int* counts_dev, double noise_prec,
                                const double* noise_prec_dev, const double* X, const double* logr, const double* lw,
                                double* loglik, double* elpd, double* lpd, double* khat, double* ess, int* info);
+
+/*
+ * Batched softmax PSIS leave-one-out: the same for K fitted multinomial logit posteriors (the model of gsmvi_softmax_batched_f64).
+ * The reference has no twin.  One launch, one workgroup per (problem, tile of gsmvi_psis_loo_softmax_tile(C, P, S) observations).
+ * Problem k has A_k (N x P; A is K x N x P), integer labels y_ki (K x N ints), n_k = counts_dev[k] clamped to 0 .. N valid rows (N
+ * without counts_dev), C classes with D = (C - 1) P <= 64, class C - 1 the reference class, and the draws x_s (s < S; X is
+ * K x S x D) of q_k, class-major as in the target: x_s[c P + j] = W_cj.  logr (K x S) and lw (K x S) are what
+ * gsmvi_psis_batched_f64 writes for the same draws.  For a valid row i < n_k:
+ *   eta_sic = a_i . x_s[c P .. c P + P - 1]  (c < C - 1),   eta_si,C-1 = 0
+ *   m_si    = max_c eta_sic   (all C values, the 0 included)
+ *   z_si    = sum_{c = 0 .. C-1} exp(eta_sic - m_si)   (class order, the reference class last)
+ *   l_si    = eta_si,y_i - m_si - log z_si
+ * the target's per-row density term, with no prior.  l_si is NaN in three cases: one of the C - 1 dot products is not finite; x_s
+ * has a non-finite entry; y_i is outside 0 .. C - 1 (a label is only compared, never used as an index).  Nothing else produces a
+ * NaN: where the product runs over zero-padded positions of a_i, the matching operand is 0 as well.
+ * From there on the text is that of gsmvi_psis_loo_batched_f64 above, word for word:
+ *   rho_si = logr_s - l_si (one subtraction)
+ *   the PSIS stage, steps 1-8 of gsmvi_psis_weights_batched_f64 exactly (the (value, row) order of the sort and the -1 / -2
+ *   verdicts included), on rho_.i gives the normalised smoothed log weights w_si, khat[k, i], ess[k, i] and info[k, i]
+ *   elpd[k, i] = log sum_s exp(w_si + l_si)
+ *   lpd[k, i]  = log sum_s exp(lw_s + l_si)
+ * both as max + log sum exp(. - max), the maximum and the sum each a fixed tree over the S draws (a thread's entries in order, a
+ * butterfly within each wave, the waves in order; no atomics): the outputs are bit-identical from run to run.
+ * info[k, i] = -1 (a NaN or +inf among rho_.i, or every rho -inf): elpd, lpd, khat and ess of (k, i) are NaN.  info[k, i] = -2 (fewer
+ * than five tail entries): plain self-normalised weights and khat = +inf.  Rows i >= n_k are never loaded: elpd, lpd, khat and ess
+ * are NaN and info[k, i] = -3.  A verdict touches only its own (k, i).  loglik (K x N x S, or NULL) receives l_si (NaN for rows
+ * i >= n_k).  Outputs: elpd, lpd, khat, ess (K x N doubles each) and info (K x N ints), all required.
+ * gsmvi_psis_loo_softmax_tile(C, P, S) is a pure function (no GPU): the observations per workgroup, the largest count of at most 4
+ * whose l_si (S doubles each) fit in the workgroup's 160 KB of LDS (20480 doubles) beside max(stage, tiles) doubles, where stage =
+ * S2 + S + 508 + S2 / 2 (S2 = S rounded up to a power of two, at least 8) and tiles = 64 (D | 1) + 16 (4 ceil(P / 4) + 1) + 16;
+ * 0 for (C, P) or S out of bounds.
+ * C >= 2, P >= 1, D = (C - 1) P <= 64, 5 <= S <= 4096, N >= 1, K >= 1 with K ceil(N / gsmvi_psis_loo_softmax_tile(C, P, S)) <=
+ * 2^24 - 1, K N S doubles addressable.  Shapes, NULL arrays and overlaps (loglik, elpd, lpd, khat, ess and info are the written
+ * arrays, everything else is read) are checked before the context is looked at (then a NULL ctx); every failure returns
+ * GSMVI_ERR_BAD_ARG before anything is enqueued.  Inputs are only read; no context workspace is used; one capturable launch with no
+ * host synchronisation and no atomics.  Sets GSMVI_PATH_BATCHED_LOO | GSMVI_PATH_BATCHED_SOFTMAX: after a reset exactly that pair
+ * identifies this launch (the GLM leave-one-out sets the first bit alone, the softmax score launch the second alone).
+ */
+int gsmvi_psis_loo_softmax_tile(int C, int P, int64_t S);
+int gsmvi_psis_loo_softmax_batched_f64(gsmvi_ctx* ctx, void* stream, int64_t K, int C, int P, int64_t N, int64_t S,
+                                       const double* A, const int* labels, const int* counts_dev, const double* X,
+                                       const double* logr, const double* lw, double* loglik, double* elpd, double* lpd,
+                                       double* khat, double* ess, int* info);
 
 /*
  * Upper Cholesky factor R (R^T R = S, R upper triangular, strictly-lower part zeroed) of a
