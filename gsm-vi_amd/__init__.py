@@ -43,6 +43,11 @@ Mirrors the reference's public surface for the hot path (reference file:line):
     psis_loo_softmax_batched (the same for K fitted
     multinomial logit posteriors: the class-coupled
     pointwise likelihood on the fp64 MFMA; one launch) examples/example_gsm.py:34-35, comparing fitted models; no reference twin
+    predict_softmax_batched, SoftmaxPrediction (the
+    posterior predictive of K fitted multinomial
+    logit posteriors on new rows, from draws of q_k,
+    uniform or PSIS-weighted: class probabilities,
+    labels, held-out elpd; one launch after the draws) examples/example_gsm.py:34-35, the use of the fit; no reference twin
     lbfgs_init_batched (the L-BFGS initialiser
     for K problems at once, D <= 64: one launch
     per function evaluation after lp_g and lp)   gsmvi/initializers.py:5-17
@@ -71,6 +76,7 @@ from .targets import GaussianTarget, device_score, score_from_logp   # noqa: F40
 from .targets import BatchedGaussianTarget, BatchedLogisticTarget    # noqa: F401
 from .targets import BatchedGLMTarget, GLMPrediction                 # noqa: F401
 from .targets import BatchedSoftmaxTarget                            # noqa: F401
+from .targets import predict_softmax_batched, SoftmaxPrediction      # noqa: F401
 from .batched import GSMBatch, gsm_update_batched                    # noqa: F401
 from .batched import BaMBatch, bam_update_batched, bam_lowrank_update_batched   # noqa: F401
 from .batched import ADVIBatch, Adam                                 # noqa: F401

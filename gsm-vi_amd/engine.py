@@ -1220,6 +1220,37 @@ class HipEngine:
                    self._ints(info, K * N, "info"))
         return elpd, lpd, khat, ess, info, loglik
 
+    # ---- batched softmax posterior predictive: the use of K fitted multinomial logit posteriors (csrc/gsmvi_softmax_predict_batched.hip)
+    def softmax_predict_lds_bytes(self, C, P):
+        """gsmvi_softmax_predict_lds_bytes: the dynamic LDS in bytes of one workgroup of ``softmax_predict_batched`` at (C, P), 0
+        out of bounds; a pure function, no GPU"""
+        return int(self.lib.gsmvi_softmax_predict_lds_bytes(int(C), int(P)))
+
+    def softmax_predict_batched(self, X, lw, A, num_classes, labels=None, counts=None):
+        """The posterior predictive of K fitted multinomial logit posteriors at the rows of A (K, M, P) from the draws X (K, S, D)
+        of q_k, D = (C - 1) P class-major, weighted by the normalised log weights ``lw`` (K, S) (``psis_batched``'s; None:
+        uniform), one launch (gsmvi_softmax_predict_batched_f64; the definition is in include/gsmvi_hip.h)  [no reference twin]:
+        returns (prob (K, M, C), lpd (K, M) or None without ``labels``).  ``labels`` (K, M) int32, ``num_classes`` and ``counts``
+        are ``softmax_batched``'s, for the new rows."""
+        K, S, D = X.shape
+        _, M, P = A.shape
+        Cc = int(num_classes)
+        if Cc < 2 or (Cc - 1) * P != D:
+            raise ValueError(f"expected (num_classes - 1) P = {(Cc - 1) * P} columns, got {D}")
+        if labels is not None:
+            assert labels.is_cuda and labels.dtype == torch.int32 and labels.is_contiguous() and tuple(labels.shape) == (K, M), \
+                f"labels: expected a contiguous int32 CUDA tensor of shape {(K, M)}"
+        self._any_ctx()
+        X = X.contiguous()
+        lw = lw.contiguous() if lw is not None else None
+        prob = self.empty(K, M, Cc)
+        lpd = self.empty(K, M) if labels is not None else None
+        self._call("gsmvi_softmax_predict_batched_f64", K, Cc, P, M, S, self._packed(A, (K, M, P), "A"),
+                   _ptr(labels) if labels is not None else None, self._ints(counts, K, "counts"),
+                   self._packed(X, (K, S, D), "X"), self._dp(lw, (K, S), "lw"), self._packed(prob, (K, M, Cc), "prob"),
+                   self._dp(lpd, (K, M), "lpd"))
+        return prob, lpd
+
     def bam_update(self, X, G, mu0, S0, reg, jitter=0.0, out=None, flag=None):
         """(mu, S) of BaM [gsmvi/bam.py:72-114]; S symmetrised, jitter on the diagonal."""
         assert X.dim() == 2 and G.dim() == 2            # bam.py:47-48

@@ -16,7 +16,12 @@ multinomial logit regressions (C classes, C - 1 linear predictors per row), a la
     BatchedLogisticTarget     y in [0, 1]                     gsmvi_logistic_batched_f64         yes
     BatchedGLMTarget          poisson, probit, gaussian, ...  gsmvi_glm_batched_f64              yes
     BatchedSoftmaxTarget      integer labels in 0 .. C - 1    gsmvi_softmax_batched_f64          laplace_init_softmax_batched and
-                                                                                                 neg_hessian; predict, loo: no (TypeError)
+                                                                                                 neg_hessian; predict, loo: no (TypeError):
+                                                                                                 predict_softmax_batched,
+                                                                                                 psis_loo_softmax_batched
+
+``predict_softmax_batched`` is the softmax target's posterior predictive (``SoftmaxPrediction``): class probabilities and the
+held-out score of new rows from draws of the fitted Gaussians, one HIP launch after the draws.
 """
 from dataclasses import dataclass
 from typing import Any
@@ -419,8 +424,8 @@ class BatchedSoftmaxTarget:
     any device work (ValueError naming the argument and the problems).  It is not a ``BatchedGLMTarget``: there is no offset, and
     ``laplace_init_batched``, ``predict`` and ``psis_loo_batched`` do not take it (TypeError).  Its second-order start is
     ``laplace_init_softmax_batched``, on the closed-form negative Hessian that ``neg_hessian`` returns, and its PSIS leave-one-out
-    is ``psis_loo_softmax_batched(target, mean, cov, keys, ...)`` (``.loo`` stays ``psis_loo_batched``'s TypeError; there is no
-    ``predict`` yet).
+    is ``psis_loo_softmax_batched(target, mean, cov, keys, ...)`` (``.loo`` stays ``psis_loo_batched``'s TypeError).  Its posterior
+    predictive is ``predict_softmax_batched(target, mean, cov, A_new, keys, ...)`` (``.predict`` stays a TypeError that names it).
 
     ``lp_g(x, out=None)``: (K, B, D) -> (K, B, D) scores, ``device_native`` and ``graph_safe`` (one capturable launch, no
     allocation with ``out``).  ``lp(x)``: (K, rows, D) -> (K, rows) values; a device tensor or numpy.  ``lp_and_score(x)``:
@@ -475,11 +480,120 @@ class BatchedSoftmaxTarget:
                                            prior_prec=self.prior_precision, want="h")
 
     def predict(self, *args, **kw):
-        """not built yet for this target: TypeError (the predictive is ``BatchedGLMTarget.predict``'s, one linear predictor per row)"""
-        raise TypeError("BatchedSoftmaxTarget.predict: the posterior predictive takes a BatchedGLMTarget or a BatchedLogisticTarget; "
-                        "the softmax target has none yet")
+        """TypeError: the quadrature of ``BatchedGLMTarget.predict`` is for one linear predictor per row; the softmax target's
+        predictive is ``predict_softmax_batched(target, mean, cov, A_new, keys, ...)``, from draws of q_k"""
+        raise TypeError("BatchedSoftmaxTarget.predict: the method is the GLM targets' (one linear predictor per row); call "
+                        "predict_softmax_batched(target, mean, cov, A_new, keys, ...) for the softmax target")
 
     def loo(self, mean, cov, keys, **kw):
         """``psis_loo_batched(self, ...)``, which takes the GLM targets only: TypeError"""
         from .diagnostics import psis_loo_batched
         return psis_loo_batched(self, mean, cov, keys, **kw)
+
+
+@dataclass
+class SoftmaxPrediction:
+    """What ``predict_softmax_batched`` returns for M new rows of each of K multinomial logit problems under the fitted q_k =
+    N(mean_k, cov_k) (numpy arrays, or the engine's tensors with ``as_torch``): ``prob`` (K, M, C) the predictive class
+    probabilities, the (weighted) mean over the draws of softmax(eta); ``label`` (K, M) int64 the first maximum of ``prob``, -1
+    where the row is NaN; with ``y``, ``lpd`` (K, M) = log E[p(y | eta)] per row and ``elpd`` (K,), its sum over the valid rows:
+    the held-out score by which fits of one model are compared (both None without ``y``).  Rows beyond ``counts[k]`` are NaN.
+    ``psis`` the problem-level ``PSISBatchedResult`` whose draws (and, with ``weights="psis"``, weights) were used (device
+    tensors: hand it back as ``psis=`` to reuse them), None where none was made or given; ``num_draws`` = S; ``nlaunch`` the
+    kernel launches made.  [examples/example_gsm.py:34-35, the use of the fit; no reference twin]"""
+    prob: Any
+    label: Any
+    lpd: Any
+    elpd: Any
+    psis: Any
+    num_draws: int
+    nlaunch: int
+
+
+def predict_softmax_batched(target, mean, cov, A_new, keys, y=None, counts=None, num_draws=1024, *, call=0, psis=None,
+                            weights="uniform", as_torch=False, engine=None):
+    """The posterior predictive of K fitted multinomial logit posteriors q_k = N(mean_k, cov_k) on new rows: returns a
+    ``SoftmaxPrediction``.
+
+    ``target`` is the ``BatchedSoftmaxTarget`` the posteriors were fitted to (its number of classes and P are the model; anything
+    else raises TypeError); mean (K, D), D = (C - 1) P, cov (K, D, D) and ``keys`` are ``psis_batched``'s; ``A_new`` (K, M, P) are
+    the new rows, ``y`` (K, M) their integer labels (None: no ``lpd`` / ``elpd``), ``counts`` (K,) the valid rows per problem
+    (None: all M).  A softmax row has C - 1 coupled linear predictors, so there is no one-dimensional quadrature: the predictive
+    is a mean over S = ``num_draws`` draws of q_k.
+    ``weights="uniform"``: one call of ``kl_draw_batched`` with ``psis_batched``'s seed rule (seed (keys[k] % 2**32) ^
+    0x5DEECE66D, draw number ``call``: the bits ``psis_batched`` would draw), no call of ``target.lp``, then one launch,
+    gsmvi_softmax_predict_batched_f64 (the definition is in include/gsmvi_hip.h): per class the linear predictors of every draw
+    on the fp64 MFMA, the class probabilities summed over the draws and the log-sum-exp of the rows' log likelihoods; no
+    (K, S, M, C) block is formed.  ``weights="psis"``: first ``psis_batched(target.lp, mean, cov, keys, num_draws, call=call,
+    moments=False, as_torch=True)``, then the launch with its smoothed ``log_weights``: the importance-corrected predictive; the
+    result carries ``psis`` (khat, ``ok``), and a problem whose problem-level run failed comes out NaN.  ``psis=``, the result
+    of such a call, is reused (``num_draws`` and ``call`` are then not used): its draws alone with ``"uniform"``, its weights
+    too with ``"psis"``.  mean and cov are only read.
+    An ``A_new`` that is not (K, M, P), a mean that is not (K, D) of the target, a cov that is not (K, D, D), labels outside
+    0 .. C - 1 in the valid rows, bad ``counts``, keys of another length than K, ``num_draws`` outside 5..4096, an unknown
+    ``weights`` or a ``psis`` that is not a ``PSISBatchedResult`` holding device tensors of the right shapes raise ValueError
+    naming the argument before any device work."""
+    from .diagnostics import MAX_DRAWS, MIN_DRAWS, _reusable, psis_batched
+    from .monitors import _to_numpy
+    fn = "predict_softmax_batched"
+    if not isinstance(target, BatchedSoftmaxTarget):
+        raise TypeError(f"{fn}: target must be a BatchedSoftmaxTarget, got {type(target).__name__}")
+    if weights not in ("uniform", "psis"):
+        raise ValueError(f"{fn}: weights: expected 'uniform' or 'psis', got {weights!r}")
+    K, D, P, C = target.K, target.D, target.P, target.C
+    sa = _shape(A_new)
+    if len(sa) != 3 or min(sa) < 1 or sa[0] != K or sa[2] != P:
+        raise ValueError(f"{fn}: A_new: expected shape (K, M, P) with K = {K}, P = {P} and M >= 1, got {sa}")
+    M = sa[1]
+    if _shape(mean) != (K, D):
+        raise ValueError(f"{fn}: mean must be (K, D) = {(K, D)} of the target, got {_shape(mean)}")
+    if _shape(cov) != (K, D, D):
+        raise ValueError(f"{fn}: cov must be {(K, D, D)}, got {_shape(cov)}")
+    try:
+        cnt = _check_counts(counts, K, M, rows="M")
+        yh = None
+        if y is not None:
+            if _shape(y) != (K, M):
+                raise ValueError(f"y: expected shape (K, M) = {(K, M)}, got {_shape(y)}")
+            yh = _check_labels(y, C, _live_rows(cnt, M))
+    except ValueError as e:
+        raise ValueError(f"{fn}: {e}") from None
+    keys_l = [int(k) for k in np.asarray(list(keys) if isinstance(keys, (list, tuple, range)) else _to_numpy(keys)).reshape(-1)]
+    if len(keys_l) != K:
+        raise ValueError(f"{fn}: {len(keys_l)} keys for K = {K} problems")
+    eng = engine if engine is not None else target.engine
+    if psis is None:
+        S = int(num_draws)
+        if S != num_draws or not MIN_DRAWS <= S <= MAX_DRAWS:
+            raise ValueError(f"{fn}: num_draws = {num_draws} is outside {MIN_DRAWS} <= num_draws <= {MAX_DRAWS}")
+        if weights == "psis":
+            psis = psis_batched(target.lp, mean, cov, keys_l, S, call=call, moments=False, as_torch=True, engine=eng)
+            nlaunch = psis.nlaunch + 1
+            X, _, lw = _reusable(psis, K, D, eng, fn)
+        else:
+            seeds = eng.batched_seeds(tuple((k % (2 ** 32)) ^ 0x5DEECE66D for k in keys_l))
+            X, _, _ = eng.kl_draw_batched(eng.asarray(mean), eng.asarray(cov), seeds, int(call), 0, S)
+            nlaunch, lw = 2, None
+    else:
+        X, _, lw = _reusable(psis, K, D, eng, fn)
+        S = _shape(X)[1]
+        nlaunch = 1
+        if weights == "uniform":
+            lw = None
+    prob, lpd = eng.softmax_predict_batched(X, lw, eng.asarray(A_new.contiguous() if isinstance(A_new, torch.Tensor) else A_new), C,
+                                            labels=eng.batched_labels(yh) if yh is not None else None,
+                                            counts=eng.batched_counts(cnt) if cnt is not None else None)
+    ten = lambda a: a if isinstance(a, torch.Tensor) else torch.as_tensor(np.asarray(a))      # noqa: E731
+    pt = ten(prob)
+    label = torch.where(torch.isnan(pt).any(2), torch.full((), -1, dtype=torch.int64, device=pt.device), pt.argmax(2))
+    elpd = None
+    if lpd is not None:
+        lt = ten(lpd)
+        nk = ten(cnt).to(lt.device) if cnt is not None else torch.full((K,), M, device=lt.device)
+        mask = torch.arange(M, device=lt.device)[None, :] < nk[:, None]
+        elpd = torch.where(mask, lt, torch.zeros((), dtype=lt.dtype, device=lt.device)).sum(1)
+    out = dict(prob=prob, label=label, lpd=lpd, elpd=elpd)
+    if not as_torch:
+        out = {n: None if t is None else np.asarray(eng.to_numpy(t)) for n, t in out.items()}
+        out["label"] = out["label"].astype(np.int64)
+    return SoftmaxPrediction(psis=psis, num_draws=S, nlaunch=nlaunch, **out)

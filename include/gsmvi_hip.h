@@ -33,6 +33,8 @@
  *   examples/example_gsm.py:34-35 the comparison of fitted models: the PSIS leave-one-out density of every observation of K fitted
  *   GLMs (no reference twin)                                           ->  gsmvi_psis_loo_batched_f64, gsmvi_psis_loo_tile
  *   the same for K fitted multinomial logit regressions (no reference twin) -> gsmvi_psis_loo_softmax_batched_f64, gsmvi_psis_loo_softmax_tile
+ *   examples/example_gsm.py:34-35 the use of the fit for K fitted multinomial logit regressions: class probabilities and the held-out
+ *   score from draws of q_k (no reference twin)                        ->  gsmvi_softmax_predict_batched_f64, gsmvi_softmax_predict_lds_bytes
  *   gsmvi/bam.py:72-114       bam_lowrank_update(samples,vs,mu0,S0,reg) ->  gsmvi_bam_update_f64
  *   gsmvi/bam.py:31-69        bam_update(samples,vs,mu0,S0,reg)         ->  gsmvi_bam_update_f64 (same result, K6)
  *
@@ -295,7 +297,7 @@ int gsmvi_get_profile(gsmvi_ctx* ctx, float* ms, int n);
 #define GSMVI_PATH_BATCHED_TARGET 0x20000u /* k_logistic_batched: the batched non-Gaussian target's entry point     */
 #define GSMVI_PATH_BATCHED_LBFGS 0x40000u  /* k_lbfgs_step_batched / k_lbfgs_hess_inv_batched: the batched initialiser   */
 #define GSMVI_PATH_BATCHED_LAPLACE 0x80000u /* k_laplace_batched: the batched GLM Hessian and Newton step             */
-#define GSMVI_PATH_BATCHED_PREDICT 0x100000u /* k_glm_predict_batched: the batched GLM posterior predictive             */
+#define GSMVI_PATH_BATCHED_PREDICT 0x100000u /* k_glm_predict_batched: the batched GLM posterior predictive; with GSMVI_PATH_BATCHED_SOFTMAX: k_softmax_predict_batched */
 #define GSMVI_PATH_BATCHED_PSIS 0x200000u /* k_psis_batched: the batched Pareto-smoothed importance diagnostic            */
 #define GSMVI_PATH_BATCHED_LOO 0x400000u /* k_psis_loo_batched: the batched PSIS leave-one-out; with GSMVI_PATH_BATCHED_SOFTMAX: k_psis_loo_softmax_batched */
 #define GSMVI_PATH_GSM_TWO_LAUNCH 0x800000u /* the dense GSM update ran as two launches (no k_gsm_scalars_fast, no records)          */
@@ -883,6 +885,52 @@ int gsmvi_psis_loo_softmax_batched_f64(gsmvi_ctx* ctx, void* stream, int64_t K, 
                                        const double* A, const int* labels, const int* counts_dev, const double* X,
                                        const double* logr, const double* lw, double* loglik, double* elpd, double* lpd,
                                        double* khat, double* ess, int* info);
+
+/*
+ * Batched softmax posterior predictive: what the fitted q_k = N(mean_k, cov_k) of K multinomial logit regressions (the model of
+ * gsmvi_softmax_batched_f64) says about M new rows per problem, from S draws of q_k: the class probabilities and, with the rows'
+ * labels, the log predictive density of every row (the held-out score).  The C - 1 linear predictors of a row are coupled, so the
+ * one-dimensional quadrature of gsmvi_glm_predict_batched_f64 does not apply; the draws are those of gsmvi_kl_draw_batched_f64,
+ * optionally with the smoothed weights of gsmvi_psis_batched_f64.  The reference has no twin.  One launch, one 256-thread workgroup
+ * per (problem, tile of 16 new rows).
+ * A (K x M x P) are the new rows, labels (K x M ints, or NULL) their classes, n_k = counts_dev[k] clamped to 0 .. M valid rows (M
+ * without counts_dev), C classes with D = (C - 1) P <= 64, class C - 1 the reference class, X (K x S x D) the draws x_s of q_k,
+ * class-major as in the target: x_s[c P + j] = W_cj.  lw (K x S, or NULL) are normalised log weights, e.g. the log_weights of
+ * gsmvi_psis_batched_f64 for the same draws; NULL means uniform: lw_s = -log S and w_s = 1.0 / S.  For a valid row i < n_k and draw s:
+ *   eta_sic = a_i . x_s[c P .. c P + P - 1]  (c < C - 1),   eta_si,C-1 = 0
+ *   m_si    = max_c eta_sic   (all C values, the 0 included)
+ *   z_si    = sum_{c = 0 .. C-1} exp(eta_sic - m_si)   (class order, the reference class last)
+ *   p_sic   = exp(eta_sic - m_si) / z_si
+ *   prob[k, i, c] = sum_s w_s p_sic,   w_s = exp(lw_s)
+ *   l_si    = eta_si,y_i - m_si - log z_si
+ *   lpd[k, i]     = log sum_s exp(lw_s + l_si)
+ * lpd is a log-sum-exp that cannot underflow: a fixed tree of (max, scaled sum) pairs merged as (m1, s1) + (m2, s2) =
+ * (M, s1 e^(m1 - M) + s2 e^(m2 - M)), M = max(m1, m2); a pair whose maximum is -inf contributes 0.  A held-out row whose true
+ * class has eta near -800 at every draw keeps a finite lpd (the log of a linear-space sum would be -inf).  prob is summed in linear
+ * space.  Every sum is a fixed tree (a lane's entries in order, a fixed cross-lane order, the draw tiles in order, the waves in
+ * order; no atomics): the outputs are bit-identical from run to run.
+ * Draws s >= S of a partial tile contribute nothing (masked, not weighted).  A draw whose eta is not finite for row i (a non-finite
+ * entry of a_i or of x_s, 0 x inf included; where the product runs over zero-padded positions of a_i the matching operand is 0 as
+ * well, so nothing else does it) makes the C probabilities and the lpd of row i NaN.  A problem whose lw holds a NaN or +inf, or
+ * only -inf, has NaN in every valid row (a lone -inf is legal: weight 0).  A label outside 0 .. C - 1 gives a NaN lpd for its row
+ * only (a label is only compared, never used as an index).  Rows i >= n_k are never loaded and their outputs are NaN.  A verdict
+ * touches only its own (k, i) or k.  Outputs: prob (K x M x C, required) and lpd (K x M): required exactly when labels is given,
+ * NULL otherwise.
+ * gsmvi_softmax_predict_lds_bytes(C, P) is a pure function (no GPU): the dynamic LDS of the launch in bytes, 8 (64 (D | 1) +
+ * 16 (4 ceil(P / 4) + 1) + 64 C + 344) -- the tile of 64 draws, the 16 rows, the accumulators of (wave, class, row), the weights
+ * of the tile and the waves' partial results --, at most 69952 (C = 65, P = 1), inside the workgroup's 160 KB; 0 for (C, P) out of
+ * bounds.
+ * C >= 2, P >= 1, D = (C - 1) P <= 64, 1 <= S <= 4096, M >= 1, K >= 1 with K ceil(M / 16) <= 2^24 - 1.  Shapes, NULL arrays, the
+ * labels / lpd pairing and overlaps (prob and lpd are the written arrays, everything else is read) are checked before the context
+ * is looked at (then a NULL ctx); every failure returns GSMVI_ERR_BAD_ARG before anything is enqueued.  Inputs are only read; no
+ * context workspace is used; one capturable launch with no host synchronisation and no atomics.  Sets GSMVI_PATH_BATCHED_PREDICT |
+ * GSMVI_PATH_BATCHED_SOFTMAX: after a reset exactly that pair identifies this launch (the GLM predictive sets the first bit alone,
+ * the softmax score launch the second alone).
+ */
+int gsmvi_softmax_predict_lds_bytes(int C, int P);
+int gsmvi_softmax_predict_batched_f64(gsmvi_ctx* ctx, void* stream, int64_t K, int C, int P, int64_t M, int64_t S,
+                                      const double* A, const int* labels, const int* counts_dev, const double* X,
+                                      const double* lw, double* prob, double* lpd);
 
 /*
  * Upper Cholesky factor R (R^T R = S, R upper triangular, strictly-lower part zeroed) of a
