@@ -9,9 +9,9 @@
 //       way; wave w takes the 16 draws 16 w .. 16 w + 15 of the tile, the A operand x_{s, 4 j + ks}, the B operand
 //       a_{i, 4 j + ks}, Dp / 4 steps.  Each accumulator entry gets its offset, goes through lb_link (gsmvi_glm_link.h) and is
 //       normalised as the predictive's lpd is; the tile's l_si stay in LDS (NI x S doubles).
-//   (2) per observation of the tile: rho_s = logr_s - l_si into the stage's array, ps_stage (gsmvi_psis_stage.h: the one copy of
-//       steps 1-8), then the two log-sum-exps -- the maximum by a block reduction, then the sum of exp(. - max) --
-//       elpd from the stage's weights, lpd from the problem-level weights lw.
+//   (2) per observation of the tile: ps_loo_stage (gsmvi_psis_stage.h, shared with k_psis_loo_softmax_batched): rho_s = logr_s -
+//       l_si into the PSIS stage's array, ps_stage, then the two log-sum-exps -- elpd from the stage's weights, lpd from the
+//       problem-level weights lw.
 // The tiles of (1) lie over the stage's LDS (they are dead before the first stage starts).  NI is the largest count, at most
 // PL_NI_CAP, whose l_si fit beside that region in GB_LDS_MAX.  Every sum is a fixed tree and there are no atomics; every thread
 // of a workgroup runs the same barriers whatever the verdicts (the number of valid observations of a tile is uniform in it); a
@@ -25,40 +25,19 @@
 #include <cmath>
 #include <cstdint>
 
-#define PL_TR 64        // draws per tile of X_k: one 16-row MFMA block per wave
-#define PL_NB 16        // rows of the A operand's tile: the MFMA's 16 columns, NI of them in use
-#ifndef PL_NI_CAP
-#define PL_NI_CAP 4     // observations per workgroup at most (fewer observations, more workgroups per CU)
-#endif
-
 struct pl_args {
     glm_model m;                // the fitted model: A, y, offset, counts, noise precision; no prior
     int S, S2, M;               // draws, draws padded to a power of two, the tail size before ties
     int NI, U;                  // observations per tile; doubles of the region the stage and the MFMA tiles share
     unsigned ntile;             // tiles per problem: ceil(N / NI)
     const double* X;            // (K, S, D) the draws of q_k
-    const double* logr;         // (K, S) lp - log q of the problem-level run
-    const double* lw;           // (K, S) its normalised smoothed log weights
-    double* loglik;             // (K, N, S) or null
-    double* elpd;               // (K, N) each
-    double* lpd;
-    double* khat;
-    double* ess;
-    int* info;                  // (K, N) 0; -1 non-finite ratios; -2 tail too short; -3 not a valid row
+    ps_loo_io o;                // the ratios and weights of the problem-level run, the outputs
 };
 
-// doubles of the shared region: the stage's arrays and its S2 indices, or the two MFMA tiles and three per-observation arrays
-__host__ __device__ inline int pl_region_doubles(int D, int S, int S2) {
-    const int stage = ps_lds_doubles(S, S2) + S2 / 2, tiles = (PL_TR + PL_NB) * (glm_dp(D) + 1) + 3 * PL_NB;
-    return stage > tiles ? stage : tiles;
-}
+// doubles of the kernel's own use of the shared region: the two MFMA tiles and three per-observation arrays
+static inline int pl_tiles_doubles(int D) { return (PS_LOO_TR + PS_LOO_NB) * (glm_dp(D) + 1) + 3 * PS_LOO_NB; }
 
-static int pl_tile(int D, int S) {
-    int S2, M;
-    ps_sizes(S, &S2, &M);
-    const int fit = (GB_LDS_MAX / 8 - pl_region_doubles(D, S, S2)) / S;     // >= 2 at (64, 4096)
-    return fit < PL_NI_CAP ? fit : PL_NI_CAP;
-}
+static int pl_tile(int D, int S) { return ps_loo_tile(pl_tiles_doubles(D), S, PL_NI_CAP); }
 
 template <int FAM>
 __global__ __launch_bounds__(256) void k_psis_loo_batched(pl_args a) {
@@ -72,23 +51,23 @@ __global__ __launch_bounds__(256) void k_psis_loo_batched(pl_args a) {
     const glm_problem pk = glm_problem_of<FAM>(a.m, (long long)k, true);
     const int nv = (int)(pk.nk - i0 < 0 ? 0 : (pk.nk - i0 < ni ? pk.nk - i0 : ni));  // its valid observations: the first nv
     const ps_lds sm = ps_carve(pl_sm, reinterpret_cast<int*>(pl_sm + ps_lds_doubles(S, S2)), S, S2);
-    double* Xs = pl_sm;                       // PL_TR x lda   a tile of draws          (over the stage's arrays)
-    double* As = Xs + PL_TR * lda;            // PL_NB x lda   the tile's rows of A_k
-    double* ys = As + PL_NB * lda;            // PL_NB each: y_i, offset_i, the normalising term of l_si
-    double* os = ys + PL_NB;
-    double* cs = os + PL_NB;
+    double* Xs = pl_sm;                       // 64 x lda      a tile of draws          (over the stage's arrays)
+    double* As = Xs + PS_LOO_TR * lda;        // 16 x lda      the tile's rows of A_k
+    double* ys = As + PS_LOO_NB * lda;        // 16 each: y_i, offset_i, the normalising term of l_si
+    double* os = ys + PS_LOO_NB;
+    double* cs = os + PS_LOO_NB;
     double* ell = pl_sm + a.U;                // NI x S        l_si of the tile
     const size_t ks = k * (size_t)S, kn = k * (size_t)N + (size_t)i0;
-    const double qnan = __longlong_as_double(0x7ff8000000000000LL), inf = __builtin_huge_val();
+    const double qnan = __longlong_as_double(0x7ff8000000000000LL);
 
     // ---- (1) l_si of the tile's valid observations ------------------------------------------------------------------------
     if (nv > 0) {                             // (uniform in the workgroup)
         const double* Ak = a.m.A + kn * D;
-        for (int e = l; e < PL_NB * lda; e += 256) {
+        for (int e = l; e < PS_LOO_NB * lda; e += 256) {
             const int r = e / lda, j = e - r * lda;
             As[e] = r < nv && j < D ? Ak[(size_t)r * D + j] : 0.0;
         }
-        if (l < PL_NB) {
+        if (l < PS_LOO_NB) {
             const double yv = l < nv ? a.m.y[kn + l] : 0.0;
             ys[l] = yv;
             os[l] = a.m.offset && l < nv ? a.m.offset[kn + l] : 0.0;
@@ -96,9 +75,9 @@ __global__ __launch_bounds__(256) void k_psis_loo_batched(pl_args a) {
         }
         const double* Xk = a.X + ks * D;
         const int wv = l >> 6, ln = l & 63, cc = ln & 15, kq = ln >> 4;
-        for (int t0 = 0; t0 < S; t0 += PL_TR) {
+        for (int t0 = 0; t0 < S; t0 += PS_LOO_TR) {
             __syncthreads();                  // the previous tile's readers are done
-            for (int e = l; e < PL_TR * lda; e += 256) {
+            for (int e = l; e < PS_LOO_TR * lda; e += 256) {
                 const int r = e / lda, j = e - r * lda;
                 Xs[e] = t0 + r < S && j < D ? Xk[(size_t)(t0 + r) * D + j] : 0.0;
             }
@@ -122,55 +101,7 @@ __global__ __launch_bounds__(256) void k_psis_loo_batched(pl_args a) {
     }
     __syncthreads();                          // l_si is published; the tiles are dead, the stage may take their place
 
-    // ---- (2) per observation: the PSIS stage on rho, then the two log-sum-exps ------------------------------------------------
-    for (int i = 0; i < ni; ++i) {
-        const size_t ki = kn + i;
-        double* lk = a.loglik ? a.loglik + ki * S : nullptr;
-        if (i >= nv) {                        // not a valid row (uniform in the workgroup: no barrier is skipped by a part of it)
-            if (lk)
-                for (int s = l; s < S; s += 256) lk[s] = qnan;
-            if (l == 0) {
-                a.elpd[ki] = qnan;
-                a.lpd[ki] = qnan;
-                a.khat[ki] = qnan;
-                a.ess[ki] = qnan;
-                a.info[ki] = -3;
-            }
-            continue;
-        }
-        const double* el = ell + i * S;
-        for (int s = l; s < S; s += 256) {
-            const double e = el[s];
-            sm.val[s] = a.logr[ks + s] - e;
-            if (lk) lk[s] = e;
-        }
-        __syncthreads();
-        const ps_verdict v = ps_stage(sm, S, S2, M, l, false);
-        double m1 = -inf, m2 = -inf;
-        for (int s = l; s < S; s += 256) {
-            const double e = el[s];
-            m1 = fmax(m1, sm.lwu[s] + e);
-            m2 = fmax(m2, a.lw[ks + s] + e);
-        }
-        m1 = ps_max(m1, sm.red, l);
-        m2 = ps_max(m2, sm.red, l);
-        double s1 = 0.0, s2 = 0.0;
-        for (int s = l; s < S; s += 256) {
-            const double e = el[s];
-            s1 += exp((sm.lwu[s] + e) - m1);
-            s2 += exp((a.lw[ks + s] + e) - m2);
-        }
-        s1 = ps_sum(s1, sm.red, l);
-        s2 = ps_sum(s2, sm.red, l);
-        if (l == 0) {
-            a.elpd[ki] = v.bad ? qnan : m1 + log(s1);
-            a.lpd[ki] = v.bad ? qnan : m2 + log(s2);
-            a.khat[ki] = v.bad ? qnan : v.khat;
-            a.ess[ki] = v.bad ? qnan : v.ess;
-            a.info[ki] = v.bad ? -1 : (v.fit ? 0 : -2);
-        }
-        __syncthreads();                      // the next observation overwrites the stage's arrays
-    }
+    ps_loo_stage(a.o, sm, ell, ni, nv, ks, kn, S, S2, M, l);     // (2)
 }
 
 hipError_t gsmvi_psis_loo_batched_prepare() {
@@ -209,9 +140,10 @@ int gsmvi_psis_loo_batched_f64(gsmvi_ctx* ctx, void* stream, int family, int64_t
     a.S = (int)S;
     ps_sizes(a.S, &a.S2, &a.M);
     a.NI = NI;
-    a.U = pl_region_doubles(D, a.S, a.S2);
+    a.U = ps_loo_region_doubles(pl_tiles_doubles(D), a.S, a.S2);
     a.ntile = (unsigned)ntile;
-    a.X = X; a.logr = logr; a.lw = lw; a.loglik = loglik; a.elpd = elpd; a.lpd = lpd; a.khat = khat; a.ess = ess; a.info = info;
+    a.X = X;
+    a.o = {logr, lw, loglik, elpd, lpd, khat, ess, info};
     const size_t lds = ((size_t)a.U + (size_t)NI * a.S) * sizeof(double);      // <= GB_LDS_MAX by the choice of NI
     const unsigned grid = (unsigned)(K * ntile);
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);

@@ -41,6 +41,7 @@
 #include "gsmvi_ctx.h"
 #include "gsmvi_batched.h"
 #include "gsmvi_laplace_stage.h"
+#include "gsmvi_softmax_model.h"
 #include "../../include/gsmvi_hip.h"
 #include "../../include/gsmvi_hip_debug.h"   // gsmvi_debug_softmax_laplace_lds
 #include <cmath>
@@ -126,16 +127,9 @@ __global__ __launch_bounds__(256) void k_softmax_laplace_batched(sl_args a) {
 
     const double* Ak = a.A + kk * (size_t)N * P;
     const int* yk = a.labels + kk * (size_t)N;
-    long long nk = 0;                         // the rows that count (a frozen slot: none, so nothing of A_k is loaded)
-    double lam = 0.0;
-    if (live) {
-        nk = N;
-        if (a.counts) {
-            const long long c = a.counts[k];
-            nk = c < 0 ? 0 : (c > N ? N : c);
-        }
-        lam = a.lam_dev ? a.lam_dev[k] : a.lam;
-    }
+    const sm_problem pk = sm_problem_of(a.counts, a.lam, a.lam_dev, N, k, live);
+    const long long nk = pk.nk;               // the rows that count (a frozen slot: none, so nothing of A_k is loaded)
+    const double lam = pk.lam;
     if (l < Dp) {
         const double* xsrc = STEP ? a.Xt : a.X;
         xs[l] = live && l < D ? xsrc[kd + l] : 0.0;
@@ -383,41 +377,20 @@ static int sl_go(gsmvi_ctx* ctx, void* stream, const sl_args& a) {
     return gb_launched(ctx, GSMVI_PATH_BATCHED_SOFTMAX_LAPLACE, "k_softmax_laplace_batched");
 }
 
-// C >= 2 and 1 <= (C - 1) P <= 64, without forming a product that could overflow (the rule of gsmvi_softmax_batched_f64)
-static bool sl_shape_ok(int C, int P) { return C >= 2 && P >= 1 && C - 1 <= GB_MAX_D && P <= GB_MAX_D && (C - 1) * P <= GB_MAX_D; }
-
-// the model's checks of both entry points, in the order of gsmvi_softmax_batched_f64
-static int sl_check_model(const char* fn, int64_t K, int C, int P, int64_t N, const double* prior_prec_dev, double prior_prec) {
-    if (C < 2) return gb_bad(fn, "C must be at least 2");
-    if (!sl_shape_ok(C, P)) return gb_bad(fn, "P must be at least 1 and D = (C - 1) P in [1, 64]");
-    const int D = (C - 1) * P;
-    if (int st = gb_check_shape(fn, K, D, gb_ppw)) return st;
-    if (N < 1) return gb_bad(fn, "N must be at least 1");
-    if (N > (INT64_MAX / 8 / D) / K) return gb_bad(fn, "K N D is too large");
-    if (!prior_prec_dev && !(prior_prec >= 0.0 && prior_prec < __builtin_huge_val()))
-        return gb_bad(fn, "prior_prec must be finite and >= 0");
-    return GSMVI_OK;
-}
-
 extern "C" {
 
 int gsmvi_softmax_hessian_batched_f64(gsmvi_ctx* ctx, void* stream, int64_t K, int C, int P, int64_t N, const double* A,
                                       const int* labels, const int* counts_dev, double prior_prec, const double* prior_prec_dev,
                                       const double* X, double* H, double* cov, int* info_dev) {
-    if (int st = sl_check_model(__func__, K, C, P, N, prior_prec_dev, prior_prec)) return st;
-    const int D = (C - 1) * P;
+    const sm_model m = sm_model_of(K, N, C, P, A, labels, counts_dev, prior_prec, prior_prec_dev);
+    if (int st = sm_check_model(__func__, m, true, "N")) return st;
+    const int D = m.D;
     GB_BAD(!A || !labels || !X, "NULL array");
     GB_BAD(!H && !cov, "give H or cov (or both)");
     GB_BAD((cov != nullptr) != (info_dev != nullptr), "info_dev is required with cov and only with it");
     const size_t nx = (size_t)K * D * 8, nh = nx * D;
-    if (int st = gb_check_overlaps(__func__, {{A, (size_t)K * N * P * 8, "A", GB_RD},
-                                              {labels, (size_t)K * N * 4, "labels", GB_RD},
-                                              {counts_dev, (size_t)K * 4, "counts_dev", GB_RD},
-                                              {prior_prec_dev, (size_t)K * 8, "prior_prec_dev", GB_RD},
-                                              {X, nx, "X", GB_RD},
-                                              {H, nh, "H", GB_WR},
-                                              {cov, nh, "cov", GB_WR},
-                                              {info_dev, (size_t)K * 4, "info_dev", GB_WR}}))
+    if (int st = gb_check_overlaps(__func__, m, {{X, nx, "X", GB_RD}, {H, nh, "H", GB_WR}, {cov, nh, "cov", GB_WR},
+                                                 {info_dev, (size_t)K * 4, "info_dev", GB_WR}}))
         return st;
     GB_BAD(!ctx, "ctx is NULL");
     sl_args a = {};
@@ -430,20 +403,17 @@ int gsmvi_softmax_laplace_step_batched_f64(gsmvi_ctx* ctx, void* stream, int64_t
                                            const int* labels, const int* counts_dev, double prior_prec,
                                            const double* prior_prec_dev, int start, double* x, double* g, double* d, double* sc,
                                            int* ist, double* Xt, int* stopped_dev, int maxiter, int maxfun, double gtol) {
-    if (int st = sl_check_model(__func__, K, C, P, N, prior_prec_dev, prior_prec)) return st;
-    const int D = (C - 1) * P;
+    const sm_model m = sm_model_of(K, N, C, P, A, labels, counts_dev, prior_prec, prior_prec_dev);
+    if (int st = sm_check_model(__func__, m, true, "N")) return st;
+    const int D = m.D;
     GB_BAD(!A || !labels || !x || !g || !d || !sc || !ist || !Xt, "NULL array");
     GB_BAD(maxiter < 1 || maxfun < 2, "maxiter must be at least 1 and maxfun at least 2");
     GB_BAD(!(gtol >= 0.0), "gtol must be >= 0");
     const size_t nv = (size_t)K * D * 8;
-    if (int st = gb_check_overlaps(__func__, {{A, (size_t)K * N * P * 8, "A", GB_RD},
-                                              {labels, (size_t)K * N * 4, "labels", GB_RD},
-                                              {counts_dev, (size_t)K * 4, "counts_dev", GB_RD},
-                                              {prior_prec_dev, (size_t)K * 8, "prior_prec_dev", GB_RD},
-                                              {x, nv, "x", GB_WR}, {g, nv, "g", GB_WR}, {d, nv, "d", GB_WR},
-                                              {sc, (size_t)K * LP_NSC * 8, "sc", GB_WR},
-                                              {ist, (size_t)K * LP_NIS * 4, "ist", GB_WR}, {Xt, nv, "Xt", GB_WR},
-                                              {stopped_dev, 4, "stopped_dev", GB_WR}}))
+    if (int st = gb_check_overlaps(__func__, m, {{x, nv, "x", GB_WR}, {g, nv, "g", GB_WR}, {d, nv, "d", GB_WR},
+                                                 {sc, (size_t)K * LP_NSC * 8, "sc", GB_WR},
+                                                 {ist, (size_t)K * LP_NIS * 4, "ist", GB_WR}, {Xt, nv, "Xt", GB_WR},
+                                                 {stopped_dev, 4, "stopped_dev", GB_WR}}))
         return st;
     GB_BAD(!ctx, "ctx is NULL");
     sl_args a = {};
@@ -455,7 +425,7 @@ int gsmvi_softmax_laplace_step_batched_f64(gsmvi_ctx* ctx, void* stream, int64_t
 
 // include/gsmvi_hip_debug.h: what a launch at (C, P) requests (exported by the debug library only)
 int gsmvi_debug_softmax_laplace_lds(int C, int P, size_t* bytes, int* problems_per_workgroup) {
-    GB_BAD(!sl_shape_ok(C, P) || !bytes || !problems_per_workgroup, "bad shape or NULL output");
+    GB_BAD(!sm_shape_ok(C, P) || !bytes || !problems_per_workgroup, "bad shape or NULL output");
     *bytes = sl_launch_lds(C, P, problems_per_workgroup);
     return GSMVI_OK;
 }

@@ -22,14 +22,14 @@
 // draw s < S, and a problem whose lw holds a NaN or +inf or only -inf (two block reductions over lw_k before the first tile:
 // ps_sum and ps_max of gsmvi_psis_stage.h, the only use of that header here), write NaN.
 // The padding rule is k_psis_loo_softmax_batched's: a k position 4 j + kq >= P feeds 0.0 from the X side and loads nothing, so a
-// padded position is 0 x 0 and no LDS word outside the row's D entries is read.  sp_eta is a copy of pls_eta
-// (gsmvi_psis_loo_softmax_batched.hip), copied, not shared, so that file's object code stays as it is: change both together.
+// padded position is 0 x 0 and no LDS word outside the row's D entries is read (sm_eta of gsmvi_softmax_model.h, shared with it).
 // Every thread of a workgroup runs the same barriers whatever the verdicts; a workgroup reads only slice k of the inputs and
 // writes only its own (k, i) entries.  A label is compared, never used as an index.  Inputs are only read; no context workspace.
 #include "gsmvi_common.h"
 #include "gsmvi_ctx.h"
 #include "gsmvi_batched.h"
 #include "gsmvi_psis_stage.h"
+#include "gsmvi_softmax_model.h"
 #include "../../include/gsmvi_hip.h"
 #include <cmath>
 #include <cstdint>
@@ -52,24 +52,10 @@ struct sp_args {
     double* lpd;                // (K, M) or null
 };
 
-__host__ __device__ inline int sp_pp(int P) { return ((P + 3) >> 2) << 2; }
-
-// C >= 2 and 1 <= (C - 1) P <= 64, without forming a product that could overflow
-static bool sp_shape_ok(int C, int P) { return C >= 2 && P >= 1 && C - 1 <= GB_MAX_D && P <= GB_MAX_D && (C - 1) * P <= GB_MAX_D; }
-
 // doubles of the launch's LDS: the X tile, the A tile, the 16 labels, lw_s and w_s of the tile, the accumulator slots, the four
 // waves' lpd pairs and row flags, the 8 words of the block reductions
 __host__ __device__ inline int sp_lds_doubles(int C, int P) {
-    return SP_TR * (((C - 1) * P) | 1) + SP_NB * (sp_pp(P) + 1) + SP_NB + 2 * SP_TR + 4 * SP_NB * C + 3 * 4 * SP_NB + 8;
-}
-
-// eta_c of the lane's four (draw, row) pairs: the MFMA chain of class c (pls_eta's copy: change both together).  px points at the
-// lane's row of the X tile plus kq, pb at its row of the A tile plus kq; a k position 4 j + kq >= P feeds 0.0 and loads nothing.
-__device__ __forceinline__ v4d sp_eta(const double* px, const double* pb, int c, int P, int Pp, int kq) {
-    const double* pa = px + c * P;
-    v4d acc = v4d{0.0, 0.0, 0.0, 0.0};
-    for (int j = 0; j < Pp; j += 4) acc = GSMVI_MFMA_F64(j + kq < P ? pa[j] : 0.0, pb[j], acc);
-    return acc;
+    return SP_TR * (((C - 1) * P) | 1) + SP_NB * (sm_pp(P) + 1) + SP_NB + 2 * SP_TR + 4 * SP_NB * C + 3 * 4 * SP_NB + 8;
 }
 
 // (m1, s1) + (m2, s2) of two log-sum-exp pairs, into the first: (M, s1 e^(m1 - M) + s2 e^(m2 - M)) with M the larger maximum, whose
@@ -83,16 +69,12 @@ __device__ __forceinline__ void sp_merge(double& m1, double& s1, double m2, doub
 
 __global__ __launch_bounds__(256) void k_softmax_predict_batched(sp_args a) {
     extern __shared__ double sp_sm[];
-    const int l = threadIdx.x, S = a.S, C = a.C, P = a.P, Cm = C - 1, D = a.D, Pp = sp_pp(P), lda = Pp + 1, ldx = D | 1;
+    const int l = threadIdx.x, S = a.S, C = a.C, P = a.P, Cm = C - 1, D = a.D, Pp = sm_pp(P), lda = Pp + 1, ldx = D | 1;
     const long long M = a.M;
     const size_t k = blockIdx.x / a.ntile;
     const long long i0 = (long long)(blockIdx.x - (unsigned)k * a.ntile) * SP_NB;    // the tile's first row
     const int ni = (int)(M - i0 < SP_NB ? M - i0 : SP_NB);
-    long long nk = M;
-    if (a.counts) {
-        const long long c = a.counts[k];
-        nk = c < 0 ? 0 : (c > M ? M : c);
-    }
+    const long long nk = sm_rows_of(a.counts, (long long)k, M);
     const int nv = (int)(nk - i0 < 0 ? 0 : (nk - i0 < ni ? nk - i0 : ni));           // its valid rows: the first nv
     double* Xs = sp_sm;                       // SP_TR x ldx   a tile of draws
     double* As = Xs + SP_TR * ldx;            // SP_NB x lda   the tile's rows of A_k, zero-padded
@@ -167,7 +149,7 @@ __global__ __launch_bounds__(256) void k_softmax_predict_batched(sp_args a) {
             }
 #pragma unroll 1
             for (int c = 0; c < Cm; ++c) {                  // sweep 1: the maximum, eta_y, the finiteness
-                const v4d acc = sp_eta(px, pb, c, P, Pp, kq);
+                const v4d acc = sm_eta(px, pb, c, P, Pp, kq);
                 if (live) {
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
@@ -180,7 +162,7 @@ __global__ __launch_bounds__(256) void k_softmax_predict_batched(sp_args a) {
             double z[4] = {0.0, 0.0, 0.0, 0.0};
 #pragma unroll 1
             for (int c = 0; c < Cm; ++c) {                  // sweep 2: the same chain, the sum in class order
-                const v4d acc = sp_eta(px, pb, c, P, Pp, kq);
+                const v4d acc = sm_eta(px, pb, c, P, Pp, kq);
                 if (live) {
 #pragma unroll
                     for (int r = 0; r < 4; ++r) z[r] += exp(acc[r] - m[r]);
@@ -196,7 +178,7 @@ __global__ __launch_bounds__(256) void k_softmax_predict_batched(sp_args a) {
 #pragma unroll 1
             for (int c = 0; c < C; ++c) {                   // sweep 3: the probabilities, class by class, the reference class last
                 v4d acc = v4d{0.0, 0.0, 0.0, 0.0};
-                if (c < Cm) acc = sp_eta(px, pb, c, P, Pp, kq);     // (uniform in the wave)
+                if (c < Cm) acc = sm_eta(px, pb, c, P, Pp, kq);     // (uniform in the wave)
                 double v = 0.0;
                 if (live) {
 #pragma unroll
@@ -260,18 +242,16 @@ hipError_t gsmvi_softmax_predict_batched_prepare() { return gb_allow_lds(k_softm
 extern "C" {
 
 int gsmvi_softmax_predict_lds_bytes(int C, int P) {
-    if (!sp_shape_ok(C, P)) return 0;
+    if (!sm_shape_ok(C, P)) return 0;
     return sp_lds_doubles(C, P) * (int)sizeof(double);
 }
 
 int gsmvi_softmax_predict_batched_f64(gsmvi_ctx* ctx, void* stream, int64_t K, int C, int P, int64_t M, int64_t S,
                                       const double* A, const int* labels, const int* counts_dev, const double* X,
                                       const double* lw, double* prob, double* lpd) {
-    GB_BAD(C < 2, "C must be at least 2");
-    GB_BAD(!sp_shape_ok(C, P), "P must be at least 1 and D = (C - 1) P in [1, 64]");
-    const int D = (C - 1) * P;
-    GB_BAD(K < 1 || K > 16777215, "K must be in [1, 2^24 - 1]");
-    GB_BAD(M < 1, "M must be at least 1");
+    const sm_model m = sm_model_of(K, M, C, P, A, labels, counts_dev);
+    if (int st = sm_check_model(__func__, m, false, "M")) return st;
+    const int D = m.D;
     GB_BAD(S < 1 || S > SP_MAX_S, "S must be in [1, 4096]");
     GB_BAD(!A || !X || !prob, "NULL array");
     GB_BAD((labels != nullptr) != (lpd != nullptr), "labels and lpd are given together or not at all");
@@ -279,9 +259,8 @@ int gsmvi_softmax_predict_batched_f64(gsmvi_ctx* ctx, void* stream, int64_t K, i
     const int64_t ntile = (M + SP_NB - 1) / SP_NB;
     GB_BAD(ntile > 16777215 / K, "K ceil(M / 16) must be at most 2^24 - 1 (one tile of 16 rows per workgroup)");
     const size_t nm = (size_t)K * M * 8, ns = (size_t)K * S * 8;
-    if (int st = gb_check_overlaps(__func__, {{A, nm * P, "A", GB_RD}, {labels, (size_t)K * M * 4, "labels", GB_RD},
-                                              {counts_dev, (size_t)K * 4, "counts_dev", GB_RD}, {X, ns * D, "X", GB_RD},
-                                              {lw, ns, "lw", GB_RD}, {prob, nm * C, "prob", GB_WR}, {lpd, nm, "lpd", GB_WR}}))
+    if (int st = gb_check_overlaps(__func__, m, {{X, ns * D, "X", GB_RD}, {lw, ns, "lw", GB_RD}, {prob, nm * C, "prob", GB_WR},
+                                                 {lpd, nm, "lpd", GB_WR}}))
         return st;
     GB_BAD(!ctx, "ctx is NULL");
     sp_args a = {};

@@ -837,6 +837,20 @@ class HipEngine:
         return ret
 
     # ---- batched softmax target: K multinomial logit regressions of one (N, C, P) (csrc/gsmvi_softmax_batched.hip) ----------
+    def _softmax_model_args(self, K, D, A, labels, num_classes, counts, prior_prec=None, prefix=""):
+        """The model of the five softmax entry points, checked against the K problems and D columns of the caller's points or
+        draws: the sizes (C, P, N) and the arrays A, labels, counts_dev and -- with ``prior_prec``, which the leave-one-out and the predictive
+        do not have -- the prior's two arguments, each in the order of include/gsmvi_hip.h.  ``labels`` None (the predictive
+        without them) passes NULL; ``prefix`` names the checked array in the message."""
+        N, P, Cc = A.shape[1], A.shape[2], int(num_classes)
+        if Cc < 2 or (Cc - 1) * P != D:
+            raise ValueError(f"{prefix}expected (num_classes - 1) P = {(Cc - 1) * P} columns, got {D}")
+        if labels is not None:
+            assert labels.is_cuda and labels.dtype == torch.int32 and labels.is_contiguous() and tuple(labels.shape) == (K, N), \
+                f"labels: expected a contiguous int32 CUDA tensor of shape {(K, N)}"
+        model = (self._packed(A, (K, N, P), "A"), _ptr(labels) if labels is not None else None, self._ints(counts, K, "counts"))
+        return (Cc, P, N), model + (self._reg_arg(prior_prec, K) if prior_prec is not None else ())
+
     def softmax_batched(self, X, A, labels, num_classes, counts=None, prior_prec=1.0, out=None, lp_out=None, want="g"):
         """Score and / or log-density of K Bayesian multinomial logit regressions at the rows of X (K, nc, D), D = (C - 1) P,
         class-major, class C - 1 the reference class, one launch [examples/example_gsm.py:34-35 for this model]: A (K, N, P),
@@ -846,15 +860,9 @@ class HipEngine:
         G, lp, ret = self._want_g_lp(want, X, out, lp_out)
         X = X.contiguous()
         K, nc, D = X.shape
-        N, P, Cc = A.shape[1], A.shape[2], int(num_classes)
-        if Cc < 2 or (Cc - 1) * P != D:
-            raise ValueError(f"X: expected (num_classes - 1) P = {(Cc - 1) * P} columns, got {D}")
-        assert labels.is_cuda and labels.dtype == torch.int32 and labels.is_contiguous() and tuple(labels.shape) == (K, N), \
-            f"labels: expected a contiguous int32 CUDA tensor of shape {(K, N)}"
+        (Cc, P, N), model = self._softmax_model_args(K, D, A, labels, num_classes, counts, prior_prec, prefix="X: ")
         self._any_ctx()
-        r, rp = self._reg_arg(prior_prec, K)
-        self._call("gsmvi_softmax_batched_f64", K, Cc, P, nc, N, self._packed(A, (K, N, P), "A"),
-                   _ptr(labels), self._ints(counts, K, "counts"), r, rp, self._packed(X, (K, nc, D), "X"),
+        self._call("gsmvi_softmax_batched_f64", K, Cc, P, nc, N, *model, self._packed(X, (K, nc, D), "X"),
                    self._dp(G, (K, nc, D), "out"), self._dp(lp, (K, nc), "lp_out"))
         return ret
 
@@ -1041,17 +1049,6 @@ class HipEngine:
                    int(maxiter), int(maxfun), float(gtol))
 
     # ---- batched softmax Laplace initialiser: the same for the multinomial logit (csrc/gsmvi_softmax_laplace_batched.hip) -------
-    def _softmax_model_args(self, A, labels, num_classes, counts, prior_prec, D):
-        """the model's arguments of the two softmax Laplace entry points, in the order of include/gsmvi_hip.h"""
-        K, N, P = A.shape
-        Cc = int(num_classes)
-        if Cc < 2 or (Cc - 1) * P != D:
-            raise ValueError(f"expected (num_classes - 1) P = {(Cc - 1) * P} columns, got {D}")
-        assert labels.is_cuda and labels.dtype == torch.int32 and labels.is_contiguous() and tuple(labels.shape) == (K, N), \
-            f"labels: expected a contiguous int32 CUDA tensor of shape {(K, N)}"
-        r, rp = self._reg_arg(prior_prec, K)
-        return (K, Cc, P, N, self._packed(A, (K, N, P), "A"), _ptr(labels), self._ints(counts, K, "counts"), r, rp)
-
     def softmax_hessian_batched(self, X, A, labels, num_classes, counts=None, prior_prec=1.0, want="h", out=None, cov_out=None,
                                 info_out=None):
         """The negative Hessian of lp_k of K multinomial logit posteriors at the rows of X (K, D), D = (C - 1) P class-major,
@@ -1069,9 +1066,9 @@ class HipEngine:
         if want != "h":
             cov = self.empty(K, D, D) if cov_out is None else cov_out
             info = torch.zeros(K, dtype=torch.int32, device=self.device) if info_out is None else info_out
-        self._call("gsmvi_softmax_hessian_batched_f64", *self._softmax_model_args(A, labels, num_classes, counts, prior_prec, D),
-                   self._packed(X, (K, D), "X"), self._dp(H, (K, D, D), "out"), self._dp(cov, (K, D, D), "cov_out"),
-                   self._ints(info, K, "info_out"))
+        (Cc, P, N), model = self._softmax_model_args(K, D, A, labels, num_classes, counts, prior_prec)
+        self._call("gsmvi_softmax_hessian_batched_f64", K, Cc, P, N, *model, self._packed(X, (K, D), "X"),
+                   self._dp(H, (K, D, D), "out"), self._dp(cov, (K, D, D), "cov_out"), self._ints(info, K, "info_out"))
         return H if want == "h" else (cov, info) if want == "cov" else (H, cov, info)
 
     def softmax_laplace_step_batched(self, state, A, labels, num_classes, counts=None, prior_prec=1.0, start=False, maxiter=100,
@@ -1082,8 +1079,8 @@ class HipEngine:
         K, D = state["x"].shape
         self._any_ctx()
         stopped = state.get("stopped")
-        self._call("gsmvi_softmax_laplace_step_batched_f64",
-                   *self._softmax_model_args(A, labels, num_classes, counts, prior_prec, D), int(bool(start)),
+        (Cc, P, N), model = self._softmax_model_args(K, D, A, labels, num_classes, counts, prior_prec)
+        self._call("gsmvi_softmax_laplace_step_batched_f64", K, Cc, P, N, *model, int(bool(start)),
                    self._packed(state["x"], (K, D), "x"), self._packed(state["g"], (K, D), "g"),
                    self._packed(state["d"], (K, D), "d"), self._packed(state["sc"], (K, 4), "sc"),
                    self._ist(state, K), self._packed(state["Xt"], (K, D), "Xt"), self._ints(stopped, 1, "stopped"),
@@ -1202,22 +1199,16 @@ class HipEngine:
         what ``psis_loo_batched`` returns, (elpd, lpd, khat, ess (K, N), info (K, N) int32, loglik (K, N, S) or None).  ``A``
         (K, N, P), ``labels`` (K, N) int32, ``num_classes`` and ``counts`` are ``softmax_batched``'s."""
         K, S, D = X.shape
-        _, N, P = A.shape
-        Cc = int(num_classes)
-        if Cc < 2 or (Cc - 1) * P != D:
-            raise ValueError(f"expected (num_classes - 1) P = {(Cc - 1) * P} columns, got {D}")
-        assert labels.is_cuda and labels.dtype == torch.int32 and labels.is_contiguous() and tuple(labels.shape) == (K, N), \
-            f"labels: expected a contiguous int32 CUDA tensor of shape {(K, N)}"
+        (Cc, P, N), model = self._softmax_model_args(K, D, A, labels, num_classes, counts)
         self._any_ctx()
         X, logr, lw = X.contiguous(), logr.contiguous(), lw.contiguous()
         elpd, lpd, khat, ess = self.empty(K, N), self.empty(K, N), self.empty(K, N), self.empty(K, N)
         info = self.batched_ints(K * N).view(K, N)
         loglik = self.empty(K, N, S) if pointwise_loglik else None
-        self._call("gsmvi_psis_loo_softmax_batched_f64", K, Cc, P, N, S, self._packed(A, (K, N, P), "A"), _ptr(labels),
-                   self._ints(counts, K, "counts"), self._packed(X, (K, S, D), "X"), self._packed(logr, (K, S), "logr"),
-                   self._packed(lw, (K, S), "lw"), self._dp(loglik, (K, N, S), "loglik"), self._packed(elpd, (K, N), "elpd"),
-                   self._packed(lpd, (K, N), "lpd"), self._packed(khat, (K, N), "khat"), self._packed(ess, (K, N), "ess"),
-                   self._ints(info, K * N, "info"))
+        self._call("gsmvi_psis_loo_softmax_batched_f64", K, Cc, P, N, S, *model, self._packed(X, (K, S, D), "X"),
+                   self._packed(logr, (K, S), "logr"), self._packed(lw, (K, S), "lw"), self._dp(loglik, (K, N, S), "loglik"),
+                   self._packed(elpd, (K, N), "elpd"), self._packed(lpd, (K, N), "lpd"), self._packed(khat, (K, N), "khat"),
+                   self._packed(ess, (K, N), "ess"), self._ints(info, K * N, "info"))
         return elpd, lpd, khat, ess, info, loglik
 
     # ---- batched softmax posterior predictive: the use of K fitted multinomial logit posteriors (csrc/gsmvi_softmax_predict_batched.hip)
@@ -1233,22 +1224,14 @@ class HipEngine:
         returns (prob (K, M, C), lpd (K, M) or None without ``labels``).  ``labels`` (K, M) int32, ``num_classes`` and ``counts``
         are ``softmax_batched``'s, for the new rows."""
         K, S, D = X.shape
-        _, M, P = A.shape
-        Cc = int(num_classes)
-        if Cc < 2 or (Cc - 1) * P != D:
-            raise ValueError(f"expected (num_classes - 1) P = {(Cc - 1) * P} columns, got {D}")
-        if labels is not None:
-            assert labels.is_cuda and labels.dtype == torch.int32 and labels.is_contiguous() and tuple(labels.shape) == (K, M), \
-                f"labels: expected a contiguous int32 CUDA tensor of shape {(K, M)}"
+        (Cc, P, M), model = self._softmax_model_args(K, D, A, labels, num_classes, counts)
         self._any_ctx()
         X = X.contiguous()
         lw = lw.contiguous() if lw is not None else None
         prob = self.empty(K, M, Cc)
         lpd = self.empty(K, M) if labels is not None else None
-        self._call("gsmvi_softmax_predict_batched_f64", K, Cc, P, M, S, self._packed(A, (K, M, P), "A"),
-                   _ptr(labels) if labels is not None else None, self._ints(counts, K, "counts"),
-                   self._packed(X, (K, S, D), "X"), self._dp(lw, (K, S), "lw"), self._packed(prob, (K, M, Cc), "prob"),
-                   self._dp(lpd, (K, M), "lpd"))
+        self._call("gsmvi_softmax_predict_batched_f64", K, Cc, P, M, S, *model, self._packed(X, (K, S, D), "X"),
+                   self._dp(lw, (K, S), "lw"), self._packed(prob, (K, M, Cc), "prob"), self._dp(lpd, (K, M), "lpd"))
         return prob, lpd
 
     def bam_update(self, X, G, mu0, S0, reg, jitter=0.0, out=None, flag=None):

@@ -1,8 +1,10 @@
 """Seeded dump of the batched GSM and BaM kernels' outputs, for before / after comparisons of a library change (DESIGN.md
 section 9): at eight (D, B) shapes, K = 13 (a tail slot in the four-problem workgroups), the one-shot update, a 20-iteration
 fit and a fit with one NaN target, for both methods -- 48 arrays of results; and the GLM entry points (score and density, the
-logistic entry, Hessian and inverse, six Newton rounds, the predictive, three L-BFGS rounds) at K = 13 for the four families
-with and without an offset, at (D, N, rows of X) shapes on both sides of every packing and tile boundary.
+logistic entry, Hessian and inverse, six Newton rounds, the predictive, three L-BFGS rounds, the leave-one-out) at K = 13 for the
+four families with and without an offset, at (D, N, rows of X) shapes on both sides of every packing and tile boundary; and the
+softmax entry points (score and density in the three ``want``s, Hessian and inverse, six Newton rounds, the leave-one-out, the
+predictive) at K = 13, at (C, P, N, rows of X, S) shapes on both sides of theirs.
 
   python scripts/batched_dump.py OUT.npz                 dump with the library the package loads
   GSMVI_HIP_LIB_VARIANT=old python scripts/batched_dump.py OUT.npz   ... with gsm-vi_amd/libgsmvi_hip_old.so
@@ -20,6 +22,11 @@ SHAPES = ((1, 1), (4, 2), (5, 2), (10, 2), (16, 8), (17, 3), (33, 4), (64, 8))
 # 32, one row more, three tiles; rows of X: one, an odd count above the packed tile of 16, one above the tile of 32
 GLM_SHAPES = ((1, 1, 1), (1, 70, 33), (16, 32, 17), (16, 33, 33), (17, 33, 1), (17, 70, 17), (64, 32, 33), (64, 70, 17))
 GLM_FAMILIES = ("logistic", "poisson", "probit", "gaussian")
+
+
+# (C, P): the smallest model, the widest row, the most classes, the four-problem packing's last D, P % 4 != 0, D = 64 with
+# P % 4 = 2; N: one row, a full tile of 32, one row more; rows of X as above; S: the fewest draws, one above a tile of 64
+SOFTMAX_SHAPES = ((2, 1, 1, 1, 5), (2, 64, 33, 17, 65), (65, 1, 32, 33, 5), (17, 1, 33, 17, 65), (5, 3, 32, 33, 65), (33, 2, 33, 1, 5))
 
 
 def dump_glm(out, K=13):
@@ -68,6 +75,50 @@ def dump_glm(out, K=13):
                     eng.lbfgs_step_batched(lp.reshape(K), G.reshape(K, D), st, start=r == 0)
                     out[f"lbfgs{r}_{tag}"] = host(*(st[n] for n in ("x", "g", "d", "Xt", "S", "Y", "sc", "ist")))
                 out[f"lbfgs_cov_{tag}"] = host(eng.lbfgs_hess_inv_batched(st))
+                S = 5 if rows == 1 else 65                  # the fewest draws, one above a tile of 64
+                rl = np.random.RandomState(rs.randint(2 ** 31))
+                Xd, logr = eng.asarray(0.5 * rl.standard_normal((K, S, D))), eng.asarray(rl.standard_normal((K, S)))
+                out[f"loo_{tag}"] = host(*eng.psis_loo_batched(Xd, logr, eng.psis_weights_batched(logr)[0], A, y, family, offset=off,
+                                                               counts=model["counts"], noise_prec=model["noise_prec"],
+                                                               pointwise_loglik=True))
+
+
+def dump_softmax(out, K=13):
+    """the outputs of every softmax entry point: counts 0 for problem 1 and N for problem 2, lam = 0 for problem 0, the reference
+    class among the labels; every array as float64"""
+    from gsmvi_amd.engine import get_engine
+    eng = get_engine()
+    host = lambda *ts: np.concatenate([eng.to_numpy(t).astype(np.float64).reshape(K, -1) for t in ts], 1)     # noqa: E731
+    for C, P, N, rows, S in SOFTMAX_SHAPES:
+        D = (C - 1) * P
+        rs = np.random.RandomState(100000 * C + 1000 * P + 10 * N + rows)
+        yh = rs.randint(0, C, (K, N))
+        yh[:, 0] = C - 1
+        cnt = np.array([max(1, N - k) for k in range(K)])
+        cnt[1], cnt[2] = 0, N
+        lam_h = 0.1 + rs.random_sample(K)
+        lam_h[0] = 0.0
+        A, y = eng.asarray(rs.standard_normal((K, N, P)) / np.sqrt(P)), eng.batched_labels(yh)
+        X = eng.asarray(rs.standard_normal((K, rows, D)))
+        Xd, logr = eng.asarray(0.5 * rs.standard_normal((K, S, D))), eng.asarray(rs.standard_normal((K, S)))
+        lw = eng.psis_weights_batched(logr)[0]
+        model = dict(counts=eng.batched_counts(cnt), prior_prec=eng.batched_regs(lam_h))
+        tag = f"C{C}_P{P}_N{N}_r{rows}_S{S}"
+        out[f"softmax_g_{tag}"] = host(eng.softmax_batched(X, A, y, C, want="g", **model))
+        out[f"softmax_lp_{tag}"] = host(eng.softmax_batched(X, A, y, C, want="lp", **model))
+        out[f"softmax_both_{tag}"] = host(*eng.softmax_batched(X, A, y, C, want="both", **model))
+        out[f"softmax_hessian_{tag}"] = host(*eng.softmax_hessian_batched(X[:, 0].contiguous(), A, y, C, want="both", **model))
+        st = eng.laplace_state_batched(eng.zeros(K, D))
+        for r in range(6):
+            eng.softmax_laplace_step_batched(st, A, y, C, start=r == 0, **model)
+            out[f"softmax_laplace{r}_{tag}"] = host(*(st[n] for n in ("x", "g", "d", "Xt", "sc", "ist")))
+        out[f"softmax_loo_{tag}"] = host(*eng.psis_loo_softmax_batched(Xd, logr, lw, A, y, C, counts=model["counts"],
+                                                                       pointwise_loglik=True))
+        for wname, w in (("uniform", None), ("weighted", lw)):
+            prob, _ = eng.softmax_predict_batched(Xd, w, A, C, counts=model["counts"])
+            out[f"softmax_predict_{wname}_{tag}"] = host(prob)
+            out[f"softmax_predict_{wname}_labels_{tag}"] = host(*eng.softmax_predict_batched(Xd, w, A, C, labels=y,
+                                                                                             counts=model["counts"]))
 
 
 def dump(path):
@@ -76,6 +127,7 @@ def dump(path):
     K = 13
     out = {}
     dump_glm(out, K)
+    dump_softmax(out, K)
     for D, B in SHAPES:
         rs = np.random.RandomState(100 * D + B)
         A = rs.standard_normal((K, D, D))
