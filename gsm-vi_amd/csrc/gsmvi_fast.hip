@@ -637,6 +637,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(FROM_SLABS 
     double dmu_part = 0.0;
     v2d dmuI = {0.0, 0.0};                       // FROM_SLABS: dmu of this thread's unit of block I (the mean, diagonal workgroups)
     v2d dmuX = {0.0, 0.0};                       // FOLD: the same of the folded tile's block (I, or J1 for the last row)
+    [[maybe_unused]] double mu0I = 0.0, mu0X = 0.0;   // FROM_SLABS: mu0 of the mean epilogues (block I; FOLD: block X), entry tid & 31
     if constexpr (FROM_SLABS) {
         static_assert(!RAG && NPASS == 1 && 512 % NU == 0, "two-launch form: B == SB in {16, 32}, on the grid");
         static_assert(KCT == 2 || KCT == 4, "slab count of the two-launch form");
@@ -658,6 +659,16 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(FROM_SLABS 
         else {
 #pragma unroll
             for (int k = 0; k < 2; ++k) qm[k] = ld16(fs.Qm, qm0 + 16u * (unsigned)(ln + 16 * k < nqm ? ln + 16 * k : nqm - 1));
+        }
+        // (round 11) mu0 of the mean epilogues, 8 B per lane, with this first batch, on wave 0 (whose lanes tid < 32 use it) whatever
+        // the workgroup is: every vector load that a later wait is counted against is issued behind the join, so the branch costs
+        // no wait, and with S0L the loads stand in front of the S0 units.  (On all eight waves: the same tail, 0.04 us more in
+        // every workgroup's load and staging phases.)  Loaded where it is used -- behind the stores of S -- it put s_waitcnt
+        // vmcnt(0) between the mirror stores and the mu store, and with it a full drain of the write-through stores in front of
+        // the folded tile's store.
+        if (w == 0) {
+            mu0I = mu0[I0 + (tid & 31)];
+            if constexpr (FOLD) mu0X = mu0[X0 + (tid & 31)];
         }
         const int col[3] = {I0 + c2, J0 + c2, J0 + 32 + c2};
         const size_t slab = (size_t)B * D;
@@ -902,6 +913,10 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(FROM_SLABS 
         }
     }
     const bool need = mine && !(t == 0 && diag) && !(dbg & 1);
+    // (round 11) S0 last: the folded tile's S0 unit came in right behind the two above.  Waited for HERE the wait is counted and
+    // free; left to its use behind the mirror branch it is a vmcnt(2) at the join (the path without mirror stores has two
+    // stores behind the unit), which in a host waits for three of the four write-through stores to be acknowledged.
+    if constexpr (FOLD && S0L) asm volatile("" : "+v"(s0x));
     __syncthreads();
     if (need) {
         // unit = (row j of J_t, column pair i2 of I): S[J_t + j][I0 + 2 i2 .. + 1] = W_t[2 i2 .. + 1][j]
@@ -917,12 +932,6 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(FROM_SLABS 
     }
     if constexpr (FOLD) {
         if (fold) {
-            if (tid < 32) {
-                double s = 0.0;
-#pragma unroll
-                for (int q = 0; q < 8; ++q) s += smem[MUO + SB * 32 + q * 32 + tid];
-                mu_out[X0 + tid] = mu0[X0 + tid] + s * invB;
-            }
             // W = S0 + U in store layout, one unit per thread; a diagonal tile has no mirror
             const int i = tid >> 4, j2 = tid & 15;
             v2d wv2;
@@ -930,6 +939,14 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(FROM_SLABS 
             wv2.y = s0x.y + smem[LXO + i * 33 + 2 * j2 + 1];
             if constexpr (WT) store_wt((size_t)(X0 + i) * lds + X0 + 2 * j2, wv2);
             else *reinterpret_cast<v2d*>(S + (size_t)(X0 + i) * lds + X0 + 2 * j2) = wv2;
+            // (round 11) the mean BEHIND the folded tile's store: the 8 KB of S are what the launch ends on, the eight LDS reads
+            // and adds of these 32 lanes stood in front of wave 0's share of them
+            if (tid < 32) {
+                double s = 0.0;
+#pragma unroll
+                for (int q = 0; q < 8; ++q) s += smem[MUO + SB * 32 + q * 32 + tid];
+                mu_out[X0 + tid] = mu0X + s * invB;
+            }
         }
     }
     if (diag) {
@@ -950,7 +967,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(FROM_SLABS 
             double s = 0.0;
 #pragma unroll
             for (int q = 0; q < 8; ++q) s += smem[(FROM_SLABS ? SB * 32 : 0) + q * 32 + tid];
-            if (!RAG || I0 + tid < D) mu_out[I0 + tid] = mu0[I0 + tid] + s * invB;
+            if (!RAG || I0 + tid < D) mu_out[I0 + tid] = (FROM_SLABS ? mu0I : mu0[I0 + tid]) + s * invB;
         }
     }
     STAMP(4);

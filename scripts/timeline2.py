@@ -72,6 +72,20 @@ if (a[live][:, 6] > 0).all():    # "cov_s0_last": [1] = staged units landed (S0 
     print("S0 landed: after start", np.round(np.median(s0 - us[:, 0]), 2), " after 'loads landed'", np.round(np.median(s0 - us[:, 1]), 2),
           " after the MFMAs", np.round(np.median(s0 - us[:, 3]), 2), " p95 of the last:", np.round(np.percentile(s0 - us[:, 3], 95), 2))
 print("blocks >= 256 (single-tile): end median", np.median(end[256:]) if len(end) > 256 else None, " blocks < 256: end median", np.median(end[:256]), "p95", np.percentile(end[:256], 95))
+# ---- the hosts of the folded diagonal tiles against the other workgroups (folded grid: the two-tile workgroups alone) ----
+nt = D // 32
+if len(end) == (nt >> 1) * ((nt + 1) >> 1):
+    host = []
+    for ti in range(nt):
+        for rem in range((nt - ti) >> 1):
+            host.append((((nt - ti) & 1) == 1 and rem == 0) or ti == nt - 2)
+    host = np.array(host)
+    for nm, sel in (("hosts", host), ("others", ~host)):
+        e, p = end[sel], ph[sel]
+        print(f"{nm:6s} {sel.sum():3d} WGs: end min/median/max {e.min():.2f}/{np.median(e):.2f}/{e.max():.2f}  staged->MFMA done "
+              f"{p[:, 2].min():.2f}/{np.median(p[:, 2]):.2f}/{p[:, 2].max():.2f}  MFMA done->last store issued "
+              f"{p[:, 3].min():.2f}/{np.median(p[:, 3]):.2f}/{p[:, 3].max():.2f}  drain {np.median(p[:, 4]):.2f}")
+    print(f"hosts' last end - others' median end: {end[host].max() - np.median(end[~host]):.2f} us;  launch span {end.max() - us[:, 0].min():.2f} us")
 a = st[0]; live = a[:, 0] > 0; usp = (a[live] - t0) / 100.0
 php = np.diff(usp[:, :4], axis=1)
 print("panel phase medians (staged, mfma, end):", np.round(np.median(php, axis=0), 2), " p95:", np.round(np.percentile(php, 95, axis=0), 2))
