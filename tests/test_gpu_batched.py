@@ -28,6 +28,7 @@ def _states(K, B, D, seed):
 
 @pytest.mark.parametrize("D", [1, 2, 5, 7, 10, 16, 17, 31, 32, 33, 63, 64])
 def test_one_shot_matches_the_per_problem_oracle(D):
+    """shapes, paths and types on easy states at a fixed bar; accuracy at the float64 floor: tests/test_gpu_batched_hard.py"""
     import gsmvi_amd
     orc = _orc()
     eng = gsmvi_amd.get_engine()
