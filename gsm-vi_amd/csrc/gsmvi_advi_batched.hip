@@ -108,8 +108,7 @@ __device__ __forceinline__ double ga_fill_z(const ga_args& a, long long k, int l
 
 // The samples of the slot's problem and their log q: X = loc + Z L^T with L given by at(i, j) (j <= i), products first, then
 // the mean (gb_fit_tail's order); logq[k] = -acc / 2 - B sum_i log|L_ii| - B D / 2 log 2 pi with acc = the slot's sum of |z|^2
-// (summed over the slot by a fixed butterfly in each wave, then the waves in order).  Every thread of the slot calls it
-// (barrier inside for NT > 64).
+// (summed over the slot by gb_slot_sum of gsmvi_batched.h).  Every thread of the slot calls it (barrier inside for NT > 64).
 template <int NT, typename At>
 __device__ __forceinline__ void ga_sample(const ga_args& a, bool valid, long long k, int l, double acc, const double* Zb,
                                           const double* loc, double* red, At at) {
@@ -126,13 +125,7 @@ __device__ __forceinline__ void ga_sample(const ga_args& a, bool valid, long lon
     // thread l < D folds -B log|L_ll| into its share, so the D logarithms run side by side and one reduction serves both sums
     double v = -0.5 * acc;
     if (valid && l < D) v -= (double)B * log(fabs(at(l, l)));
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    if (NT > 64) {
-        if ((l & 63) == 0) red[l >> 6] = v;
-        __syncthreads();
-        if (l == 0) v = red[0] + red[1] + red[2] + red[3];
-    }
+    v = gb_slot_sum<NT>(v, l, red);
     if (valid && l == 0) a.logq[k] = v - 0.5 * (double)B * D * 1.8378770664093454836;   // log 2 pi
 }
 

@@ -2,7 +2,7 @@
 // monitor; the GLM, L-BFGS, Laplace, predictive and PSIS files): the bounds, the argument block, the wave
 // butterflies, the in-LDS Cholesky, the host-side argument checks, and the tail of a fit step that both
 // methods run on their new covariance S' -- the Cholesky test, per-problem accept or revert of (mean, cov, sampling factor),
-// and the next samples from the problem's Philox stream.
+// and the next samples from the problem's Philox stream -- and the slot sum and log-density sum that end a draw.
 #pragma once
 #include <hip/hip_runtime.h>
 #include "gsmvi_philox.h"
@@ -169,6 +169,30 @@ __device__ __forceinline__ void gb_fit_tail(const gb_args& a, bool valid, long l
             a.Xout[kbd + e] = s + m1[j];
         }
     }
+}
+
+// ---- the two sums at the end of a Gaussian draw or evaluation (KL monitor, Pathfinder, ADVI), for one workgroup slot ---------
+
+// The sum of v over the slot: a fixed butterfly in each wave, then the four waves in order through red (LDS, 4).  The result is
+// in thread l == 0 (in every thread of a one-wave slot).  Every thread of every slot calls it (one barrier for NT > 64).
+template <int NT>
+__device__ __forceinline__ double gb_slot_sum(double v, int l, double* red) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    if (NT > 64) {
+        if ((l & 63) == 0) red[l >> 6] = v;
+        __syncthreads();
+        if (l == 0) v = red[0] + red[1] + red[2] + red[3];
+    }
+    return v;
+}
+
+// sum over `rows` rows of log N(x; m, R^T R) from acc = sum |z|^2 of the rows and the pivots pv = diag R; NaN when not `ok`
+__device__ __forceinline__ double gb_logq_sum(bool ok, double acc, long long rows, int D, const double* pv) {
+    double lg = 0.0;
+    for (int i = 0; i < D; ++i) lg += log(pv[i]);
+    const double n = (double)rows;
+    return ok ? -0.5 * acc - n * lg - 0.5 * n * D * 1.8378770664093454836 : __longlong_as_double(0x7ff8000000000000LL);   // log 2 pi
 }
 
 // ---- host side: the argument checks and the launch pieces shared by the batched entry points --------------------------

@@ -12,7 +12,8 @@
 // Work mapping: the problem of one workgroup slot (gb_nt(D) threads: four problems per 256-thread workgroup for D <= 16) lives
 // in LDS: R (D x ld), the mean, the pivots, and a tile of rows (TR x ldy) that the launch walks through, so nc is unbounded
 // and the LDS is not.  The row strides are odd (D | 1): the substitution's lanes walk down a column of the tile, and each meets
-// a different LDS bank.  The Cholesky is gb_chol_lds (gsmvi_batched.h), the one the batched fit steps test with.  A draw
+// a different LDS bank.  The Cholesky is gb_chol_lds (gsmvi_batched.h), the one the batched fit steps test with; the slot sum
+// and the log-density sum are gb_slot_sum and gb_logq_sum of gsmvi_batched.h, shared with k_pf_propose.  A draw
 // element depends only on (seed, call, element index), and x_sj sums its products in a fixed order, so a call split into
 // chunks (s0 > 0) writes the same x bit for bit as the unsplit call.  A pivot that is not > 0 and finite: info[k] = 1 + that
 // pivot, logq_sum[k] = NaN and problem k's rows of X are NaN.  A slot reads and writes only its own problem's slices, and
@@ -141,19 +142,9 @@ __global__ __launch_bounds__(256) void k_kl_batched(kb_args a) {
         }
     }
 
-    // sum over the slot: a fixed butterfly in each wave, then the waves in order
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
-    if (NT > 64) {
-        if ((l & 63) == 0) red[l >> 6] = acc;
-        __syncthreads();
-        if (l == 0) acc = red[0] + red[1] + red[2] + red[3];
-    }
+    acc = gb_slot_sum<NT>(acc, l, red);
     if (valid && l == 0) {
-        double lg = 0.0;
-        for (int i = 0; i < D; ++i) lg += log(pv[i]);
-        const double n = (double)a.nc;
-        a.logq[k] = ok ? -0.5 * acc - n * lg - 0.5 * n * D * 1.8378770664093454836 : qnan;   // log 2 pi
+        a.logq[k] = gb_logq_sum(ok, acc, a.nc, D, pv);
         a.info[k] = info;
     }
 }

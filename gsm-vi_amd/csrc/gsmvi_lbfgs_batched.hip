@@ -23,19 +23,20 @@
 // stopped (status != 0) is frozen:
 // the launch writes nothing of it.  A slot reads and writes only slice k of every array and every slot runs the same single
 // barrier, so nothing crosses between problems.  Only the newest pair's slot of the ring buffers is written.
+// The layout of the state and the ring-buffer test are gsmvi_lbfgs_state.h's, shared with gsmvi_pathfinder_batched.hip.  That
+// header also holds the clamped read of the counters and the dense recursion as functions, for k_pf_propose; both kernels here
+// keep the same statements inline (through the functions the step kernel lost a range proof and the dense estimate missed one
+// of six cases of the speed check: DESIGN.md section 9, "One copy of each initialiser stage"), so a change to the header's copy
+// belongs here too.
 #include "gsmvi_common.h"
 #include "gsmvi_ctx.h"
 #include "gsmvi_batched.h"
+#include "gsmvi_lbfgs_state.h"
 #include "../../include/gsmvi_hip.h"
 #include "../../include/gsmvi_hip_debug.h"   // gsmvi_debug_lbfgs_batched_lds
 #include <cmath>
 #include <cstdint>
 
-#define GL_M 10        // history length (scipy's maxcor)
-#define GL_NSC 24      // doubles per problem in sc
-#define GL_NIS 8       // ints per problem in ist
-enum { GL_F = 0, GL_T = 1, GL_GD = 2, GL_SY = 4, GL_YY = 14 };
-enum { GL_STATUS = 0, GL_NIT = 1, GL_NFEV = 2, GL_NLS = 3, GL_NP = 4, GL_HEAD = 5 };
 enum { GL_STEP = 0, GL_HESS = 1 };
 
 struct gl_args {
@@ -62,14 +63,6 @@ __host__ __device__ inline int gl_lds_doubles(int D, int mode) {
     return mode == GL_STEP ? 2 * GL_M * D + 2 * GL_M : D * (D | 1) + 2 * GL_M * D + D + GL_M;
 }
 
-// is ring-buffer slot i one of the n pairs that end at head - 1
-__device__ __forceinline__ bool gl_held(int i, int head, int n) {
-    int o = i - (head - n);
-    if (o >= GL_M) o -= GL_M;
-    if (o < 0) o += GL_M;          // head - n >= -10
-    return o < n;
-}
-
 template <int NT>
 __global__ __launch_bounds__(256) void k_lbfgs_step_batched(gl_args a) {
     extern __shared__ double gl_sm[];
@@ -93,8 +86,8 @@ __global__ __launch_bounds__(256) void k_lbfgs_step_batched(gl_args a) {
     if (valid && !a.start) {
         status = is[GL_STATUS]; nit = is[GL_NIT]; nfev = is[GL_NFEV]; nls = is[GL_NLS];
         np = is[GL_NP]; head = is[GL_HEAD];
-        np = np < 0 ? 0 : (np > GL_M ? GL_M : np);                      // (an uploaded state cannot index outside the buffers)
-        head = ((head % GL_M) + GL_M) % GL_M;
+        np = np < 0 ? 0 : (np > GL_M ? GL_M : np);                      // gl_load_ring's clamp, restated: through the function
+        head = ((head % GL_M) + GL_M) % GL_M;                           // the compiler no longer knows np, head >= 0 below
         f = sc[GL_F]; t = sc[GL_T]; gd = sc[GL_GD];
     }
     const bool live = valid && status == 0;
@@ -256,6 +249,8 @@ __global__ __launch_bounds__(256) void k_lbfgs_hess_inv_batched(long long K, int
     double* Yl = Sl + GL_M * D;
     double* u = Yl + GL_M * D;
     double* lsy = u + D;
+    // from here to the write of cov: the statements of gl_load_ring, gl_dense_fill and gl_dense_rounds (gsmvi_lbfgs_state.h) with
+    // the base 1, restated; a change to either copy belongs in the other
     int np = 0, head = 0;
     if (valid) {
         np = ist[kk * GL_NIS + GL_NP];

@@ -5,8 +5,9 @@
 // Two launches per L-BFGS round, around the caller's lp of the draws:
 //   k_pf_propose<NT> : fresh[k] = (nit of the L-BFGS state != seen[k]), seen[k] <- nit.  A fresh problem: gamma = h0 if h0 > 0,
 //                      else s.y / y.y of the newest held pair (1 without a pair); Sigma = H after H_0 = gamma I and, over the held
-//                      pairs oldest to newest, H <- (I - rho s y^T) H (I - rho y s^T) + rho s s^T -- the recursion of
-//                      k_lbfgs_hess_inv_batched in the same operations and the same order, only the base differs; mu = x - Sigma g;
+//                      pairs oldest to newest, H <- (I - rho s y^T) H (I - rho y s^T) + rho s s^T -- gl_dense_fill and
+//                      gl_dense_rounds of gsmvi_lbfgs_state.h, the statements of k_lbfgs_hess_inv_batched with the base gamma
+//                      in place of 1; mu = x - Sigma g;
 //                      R = chol(Sigma) (upper, gb_chol_lds); the rows s = 0 .. M - 1 of draw `call` = nit of key seeds[k] (element
 //                      s D + j, pair (s D + j) / 2: the plain layout of k_kl_batched), X_k row s = mu + z_s R and
 //                      logq[k] = sum_s (-|z_s|^2 / 2 - sum_i log R_ii - D / 2 log 2 pi); mu, cov, info written.  A bad pivot, or
@@ -18,21 +19,22 @@
 //                      best_cov, best_it <- e, mu, Sigma, nit; otherwise nothing of the best state is written.
 // Work mapping: the slots of gsmvi_batched.h (gb_nt(D) threads per problem, four problems per 256-thread workgroup for D <= 16).
 // The matrix lives in LDS with the odd row stride D | 1 (the product u = H y and the substitution walk down a column: every lane
-// another bank); the draws are walked in row tiles of k_kl_batched's shape, so M does not bound the LDS.  Every slot runs every
-// barrier (3 + 2 x 10 + D + 1, then 2 per tile, then 1 for NT = 256), a slot reads and writes only slice k of every array, and
-// every sum runs in an order fixed by (D, M) alone: a problem's bits depend neither on K nor on its neighbours.  No scratch, no
-// context workspace.
+// another bank); the draws are walked in row tiles of k_kl_batched's shape, so M does not bound the LDS: the draw of a tile and
+// x = mu + z R are k_kl_batched's statements, restated here (on shared functions this kernel missed the speed bound at every
+// D <= 16: DESIGN.md section 9, "One copy of each initialiser stage"), so a change to one belongs in the other; the
+// slot sum and the log-density sum are gb_slot_sum and gb_logq_sum of gsmvi_batched.h.  The state's layout and the clamped read
+// of its counters are gsmvi_lbfgs_state.h's.  Every slot runs every barrier (3 + 2 x 10 + D + 1, then 2 per tile, then 1 for
+// NT = 256), a slot reads and writes only slice k of every array, and every sum runs in an order fixed by (D, M) alone: a
+// problem's bits depend neither on K nor on its neighbours.  No scratch, no context workspace.
 #include "gsmvi_common.h"
 #include "gsmvi_ctx.h"
 #include "gsmvi_batched.h"
+#include "gsmvi_lbfgs_state.h"
 #include "../../include/gsmvi_hip.h"
 #include "../../include/gsmvi_hip_debug.h"   // gsmvi_debug_pathfinder_batched_lds
 #include <cmath>
 #include <cstdint>
 
-#define PF_M 10        // history length of the L-BFGS state
-#define PF_NSC 24      // doubles per problem in sc: [4..13] s.y, [14..23] y.y of the ten slots
-#define PF_NIS 8       // ints per problem in ist: [1] nit, [4] pairs held, [5] next slot
 #define PF_Q 4         // tile elements per thread: TR = max(1, NT PF_Q / D) rows (k_kl_batched's tile)
 #define PF_MAX_DRAWS 4096
 
@@ -59,15 +61,7 @@ struct pf_args {
 __host__ __device__ inline int pf_tile_rows(int D, int NT) { return (NT * PF_Q) / D > 1 ? (NT * PF_Q) / D : 1; }
 // LDS doubles per problem: H (D x ld) + S, Y (10 x D each) + u, g, mean, pivots (D each) + s.y (10) + the row tile + 4 partial sums
 __host__ __device__ inline int pf_lds_doubles(int D, int ld, int ldy, int tr) {
-    return D * ld + 2 * PF_M * D + 4 * D + PF_M + tr * ldy + 4;
-}
-
-// is ring-buffer slot i one of the n pairs that end at head - 1
-__device__ __forceinline__ bool pf_held(int i, int head, int n) {
-    int o = i - (head - n);
-    if (o >= PF_M) o -= PF_M;
-    if (o < 0) o += PF_M;               // head - n >= -10
-    return o < n;
+    return D * ld + 2 * GL_M * D + 4 * D + GL_M + tr * ldy + 4;
 }
 
 template <int NT>
@@ -81,13 +75,13 @@ __global__ __launch_bounds__(256) void k_pf_propose(pf_args a) {
     const bool valid = k < a.K;               // a tail slot runs every barrier and nothing else
     double* H = pf_sm + (size_t)slot * pf_lds_doubles(D, ld, ldy, TR);
     double* Sl = H + D * ld;                  // 10 x D
-    double* Yl = Sl + PF_M * D;               // 10 x D
-    double* u = Yl + PF_M * D;                // D      H y
+    double* Yl = Sl + GL_M * D;               // 10 x D
+    double* u = Yl + GL_M * D;                // D      H y
     double* gl = u + D;                       // D      gradient
     double* m = gl + D;                       // D      mean
     double* pv = m + D;                       // D      pivots R_cc
     double* lsy = pv + D;                     // 10     s.y of the slots
-    double* T = lsy + PF_M;                   // TR x ldy  the draws of a tile
+    double* T = lsy + GL_M;                   // TR x ldy  the draws of a tile
     double* red = T + TR * ldy;               // 4      per-wave partial sums
     const size_t kk = (size_t)(valid ? k : 0), kd = kk * D, kdd = kk * DD;
     const size_t krow = kk * (size_t)a.M * D;
@@ -97,64 +91,23 @@ __global__ __launch_bounds__(256) void k_pf_propose(pf_args a) {
     bool on = false;                          // valid and fresh: uniform in the slot (every thread reads the same words)
     double xl = 0.0;
     if (valid) {
-        nit = a.ist[kk * PF_NIS + 1];
-        np = a.ist[kk * PF_NIS + 4];
-        head = a.ist[kk * PF_NIS + 5];
-        np = np < 0 ? 0 : (np > PF_M ? PF_M : np);                      // (an uploaded state cannot index outside the buffers)
-        head = ((head % PF_M) + PF_M) % PF_M;
+        nit = a.ist[kk * GL_NIS + GL_NIT];
+        gl_load_ring(a.ist + kk * GL_NIS, np, head);
         on = nit != a.seen[kk];               // seen[k] is written by thread 0 after the last barrier of the launch
     }
     if (on) {
         double gamma = a.h0;
         if (!(gamma > 0.0)) {
-            const int nw = head == 0 ? PF_M - 1 : head - 1;
-            gamma = np > 0 ? a.sc[kk * PF_NSC + 4 + nw] / a.sc[kk * PF_NSC + 14 + nw] : 1.0;
+            const int nw = head == 0 ? GL_M - 1 : head - 1;
+            gamma = np > 0 ? a.sc[kk * GL_NSC + GL_SY + nw] / a.sc[kk * GL_NSC + GL_YY + nw] : 1.0;
         }
-        for (int e = l; e < PF_M * D; e += NT) {
-            const bool h = pf_held(e / D, head, np);
-            Sl[e] = h ? a.S[kk * PF_M * D + e] : 0.0;
-            Yl[e] = h ? a.Y[kk * PF_M * D + e] : 0.0;
-        }
-        for (int e = l; e < DD; e += NT) {
-            const int i = e / D, j = e - i * D;
-            H[i * ld + j] = i == j ? gamma : 0.0;
-        }
+        gl_dense_fill<NT>(D, l, ld, np, head, gamma, a.S, a.Y, kk, H, Sl, Yl);
         if (l < D) {
             gl[l] = a.g[kd + l];
             xl = a.x[kd + l];
         }
     }
-    __syncthreads();
-    if (on && l < PF_M) {                                               // s.y of slot l, summed in the order 0 .. D - 1
-        double acc = 0.0;
-        for (int j = 0; j < D; ++j) acc += Sl[l * D + j] * Yl[l * D + j];
-        lsy[l] = acc;
-    }
-    __syncthreads();
-    for (int p = 0; p < PF_M; ++p) {                                    // oldest to newest; every slot runs all ten rounds
-        const bool go = on && p < np;
-        int i = head - np + p;
-        if (i < 0) i += PF_M;
-        const double* s = Sl + i * D;
-        const double* y = Yl + i * D;
-        if (go && l < D) {                                              // u = H y
-            double acc = 0.0;
-            for (int j = 0; j < D; ++j) acc += H[l * ld + j] * y[j];
-            u[l] = acc;
-        }
-        __syncthreads();
-        if (go) {
-            const double rho = 1.0 / lsy[i];
-            double yu = 0.0;                                            // every thread the same sum in the same order
-            for (int j = 0; j < D; ++j) yu += y[j] * u[j];
-            const double c = (rho * rho) * yu + rho;
-            for (int e = l; e < DD; e += NT) {
-                const int r = e / D, q = e - r * D;
-                H[r * ld + q] = (H[r * ld + q] - rho * (s[r] * u[q] + u[r] * s[q])) + c * (s[r] * s[q]);
-            }
-        }
-        __syncthreads();
-    }
+    gl_dense_rounds<NT>(on, D, l, ld, np, head, H, Sl, Yl, u, lsy);
     if (on) {
         for (int e = l; e < DD; e += NT) {
             const int i = e / D, j = e - i * D;
@@ -217,20 +170,10 @@ __global__ __launch_bounds__(256) void k_pf_propose(pf_args a) {
         __syncthreads();                      // the next tile overwrites T
     }
 
-    // sum over the slot: a fixed butterfly in each wave, then the waves in order
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
-    if (NT > 64) {
-        if ((l & 63) == 0) red[l >> 6] = acc;
-        __syncthreads();
-        if (l == 0) acc = red[0] + red[1] + red[2] + red[3];
-    }
+    acc = gb_slot_sum<NT>(acc, l, red);
     if (valid && l == 0) {
         if (on) {
-            double lg = 0.0;
-            for (int i = 0; i < D; ++i) lg += log(pv[i]);
-            const double n = (double)a.M;
-            a.logq[kk] = ok ? -0.5 * acc - n * lg - 0.5 * n * D * 1.8378770664093454836 : qnan;   // log 2 pi
+            a.logq[kk] = gb_logq_sum(ok, acc, a.M, D, pv);
             a.info[kk] = info;
             a.fresh[kk] = 1;
             a.seen[kk] = nit;
@@ -283,7 +226,7 @@ __global__ __launch_bounds__(256) void k_pf_select(ps_args a) {
     if (!take) return;
     if (l == 0) {
         a.best_elbo[kk] = e;
-        a.best_it[kk] = a.ist[kk * PF_NIS + 1];
+        a.best_it[kk] = a.ist[kk * GL_NIS + GL_NIT];
     }
     for (int i = l; i < D; i += NT) a.best_mean[kk * D + i] = a.mu[kk * D + i];
     for (int i = l; i < DD; i += NT) a.best_cov[kk * DD + i] = a.cov[kk * DD + i];
@@ -308,10 +251,10 @@ int gsmvi_pathfinder_propose_batched_f64(gsmvi_ctx* ctx, void* stream, int64_t K
     GB_BAD(M > (INT64_MAX / 8 / D) / K, "K M D is too large");
     GB_BAD(!x || !g || !S || !Y || !sc || !ist || !seeds || !seen || !fresh || !mu || !cov || !X || !logq_sum || !info, "NULL array");
     GB_BAD(!(h0 >= 0.0) || !(h0 < __builtin_huge_val()), "h0 must be 0 (the newest pair's scale) or a positive finite number");
-    const size_t nk = (size_t)K * 8, ni = (size_t)K * 4, nv = (size_t)K * D * 8, nm = nv * D, nh = nv * PF_M,
+    const size_t nk = (size_t)K * 8, ni = (size_t)K * 4, nv = (size_t)K * D * 8, nm = nv * D, nh = nv * GL_M,
                  nx = (size_t)K * M * D * 8;
     if (int st = gb_check_overlaps(__func__, {{x, nv, "x", GB_RD}, {g, nv, "g", GB_RD}, {S, nh, "S", GB_RD}, {Y, nh, "Y", GB_RD},
-                                              {sc, (size_t)K * PF_NSC * 8, "sc", GB_RD}, {ist, (size_t)K * PF_NIS * 4, "ist", GB_RD},
+                                              {sc, (size_t)K * GL_NSC * 8, "sc", GB_RD}, {ist, (size_t)K * GL_NIS * 4, "ist", GB_RD},
                                               {seeds, nk, "seeds", GB_RD}, {seen, ni, "seen", GB_WR}, {fresh, ni, "fresh", GB_WR},
                                               {mu, nv, "mu", GB_WR}, {cov, nm, "cov", GB_WR}, {X, nx, "X", GB_WR},
                                               {logq_sum, nk, "logq_sum", GB_WR}, {info, ni, "info", GB_WR}}))
@@ -342,7 +285,7 @@ int gsmvi_pathfinder_select_batched_f64(gsmvi_ctx* ctx, void* stream, int64_t K,
                !best_cov || !best_it, "NULL array");
     const size_t nk = (size_t)K * 8, ni = (size_t)K * 4, nv = (size_t)K * D * 8, nm = nv * D;
     if (int st = gb_check_overlaps(__func__, {{lpsum, nk, "lpsum", GB_RD}, {logq_sum, nk, "logq_sum", GB_RD}, {fresh, ni, "fresh", GB_RD},
-                                              {info, ni, "info", GB_RD}, {ist, (size_t)K * PF_NIS * 4, "ist", GB_RD}, {mu, nv, "mu", GB_RD},
+                                              {info, ni, "info", GB_RD}, {ist, (size_t)K * GL_NIS * 4, "ist", GB_RD}, {mu, nv, "mu", GB_RD},
                                               {cov, nm, "cov", GB_RD}, {elbo_last, nk, "elbo_last", GB_WR}, {npts, ni, "npts", GB_WR},
                                               {best_elbo, nk, "best_elbo", GB_WR}, {best_mean, nv, "best_mean", GB_WR},
                                               {best_cov, nm, "best_cov", GB_WR}, {best_it, ni, "best_it", GB_WR}}))

@@ -4,7 +4,9 @@ fit and a fit with one NaN target, for both methods -- 48 arrays of results; and
 logistic entry, Hessian and inverse, six Newton rounds, the predictive, three L-BFGS rounds, the leave-one-out) at K = 13 for the
 four families with and without an offset, at (D, N, rows of X) shapes on both sides of every packing and tile boundary; and the
 softmax entry points (score and density in the three ``want``s, Hessian and inverse, six Newton rounds, the leave-one-out, the
-predictive) at K = 13, at (C, P, N, rows of X, S) shapes on both sides of theirs.
+predictive) at K = 13, at (C, P, N, rows of X, S) shapes on both sides of theirs; and the KL monitor's draw (one call and two
+chunks) and log-density, Pathfinder's propose and select over five L-BFGS rounds, and one ADVI start and step, at K = 13 and
+six D, with the fewest rows and one more than a tile.
 
   python scripts/batched_dump.py OUT.npz                 dump with the library the package loads
   GSMVI_HIP_LIB_VARIANT=old python scripts/batched_dump.py OUT.npz   ... with gsm-vi_amd/libgsmvi_hip_old.so
@@ -27,6 +29,11 @@ GLM_FAMILIES = ("logistic", "poisson", "probit", "gaussian")
 # (C, P): the smallest model, the widest row, the most classes, the four-problem packing's last D, P % 4 != 0, D = 64 with
 # P % 4 = 2; N: one row, a full tile of 32, one row more; rows of X as above; S: the fewest draws, one above a tile of 64
 SOFTMAX_SHAPES = ((2, 1, 1, 1, 5), (2, 64, 33, 17, 65), (65, 1, 32, 33, 5), (17, 1, 33, 17, 65), (5, 3, 32, 33, 65), (33, 2, 33, 1, 5))
+
+
+# D of the KL, Pathfinder and ADVI entries: one lane, an odd D, the four-problem packing's last, the first of one problem per
+# workgroup, an odd D above it, the largest; rows: the fewest, and one more than a tile of the draw stage
+INIT_DIMS = (1, 5, 16, 17, 33, 64)
 
 
 def dump_glm(out, K=13):
@@ -121,6 +128,65 @@ def dump_softmax(out, K=13):
                                                                                              counts=model["counts"]))
 
 
+def dump_initialisers(out, K=13):
+    """the draw and log-density of the KL monitor (the draw as one call and as two chunks), Pathfinder's propose and select over
+    five L-BFGS rounds on logistic posteriors (the base from the newest pair and the base 1), and one ADVI start and step;
+    problem 3's covariance is not positive definite in the KL entries and in ADVI's start"""
+    from gsmvi_amd.engine import get_engine
+    import gsmvi_amd
+    eng = get_engine()
+    host = lambda *ts: np.concatenate([eng.to_numpy(t).astype(np.float64).reshape(K, -1) for t in ts], 1)     # noqa: E731
+    seeds = eng.batched_seeds(range(100, 100 + K))
+    for D in INIT_DIMS:
+        # rows per tile of the draw stage: kb_tile_rows / pf_tile_rows of the two kernels, KB_Q = PF_Q = 4 elements per thread of
+        # gb_nt(D) = 64 (D <= 16) or 256 threads; restated here, so it follows a change of either by hand
+        tile = max(1, 4 * (64 if D <= 16 else 256) // D)
+        rs = np.random.RandomState(7000 + D)
+        R = rs.standard_normal((K, D, D))
+        covh = R @ np.swapaxes(R, 1, 2) / D + 0.5 * np.eye(D)
+        mh = rs.standard_normal((K, D))
+        Ah = rs.standard_normal((K, 33, D)) / np.sqrt(D)
+        yh = (rs.random_sample((K, 33)) < 1.0 / (1.0 + np.exp(-np.einsum("knd,kd->kn", Ah, mh)))).astype(np.float64)
+        tgt = gsmvi_amd.BatchedLogisticTarget(eng.asarray(Ah), eng.asarray(yh), 0.5)
+        bad = covh.copy()
+        bad[3, D - 1, D - 1] = -1.0
+        mean, cov = eng.asarray(0.3 * rs.standard_normal((K, D))), eng.asarray(bad)
+        for n in (1, tile + 1):
+            tag = f"D{D}_n{n}"
+            X, lq, info = eng.kl_draw_batched(mean, cov, seeds, 3, 0, n)
+            out[f"kl_draw_{tag}"] = host(X, lq, info)
+            if n > 1:                                       # the same rows as two chunks, the second one not at a tile's start
+                h = n // 2
+                Xa, lqa, ia = eng.kl_draw_batched(mean, cov, seeds, 3, 0, h)
+                Xb, lqb, ib = eng.kl_draw_batched(mean, cov, seeds, 3, h, n - h)
+                out[f"kl_draw_chunks_{tag}"] = host(Xa, Xb, lqa, lqb, ia, ib)
+            Y = eng.asarray(rs.standard_normal((K, n, D)))
+            out[f"logq_{tag}"] = host(*eng.logq_batched(mean, cov, Y))
+            for h0 in (0.0, 1.0):
+                st = eng.lbfgs_state_batched(eng.asarray(0.1 * rs.standard_normal((K, D))))
+                pf = eng.pathfinder_state_batched(st["x"], n)
+                Xt = st["Xt"].reshape(K, 1, D)
+                for r in range(5):
+                    eng.lbfgs_step_batched(tgt.lp(Xt).reshape(K), tgt.lp_g(Xt).reshape(K, D), st, start=r == 0)
+                    eng.pathfinder_propose_batched(st, pf, seeds, h0=h0)
+                    out[f"pf_propose{r}_h{h0:g}_{tag}"] = host(*(pf[k] for k in ("seen", "fresh", "info", "mu", "cov", "X", "logq")))
+                    eng.pathfinder_select_batched(tgt.lp(pf["X"]).sum(1), st, pf)
+                    out[f"pf_select{r}_h{h0:g}_{tag}"] = host(*(pf[k] for k in ("elbo_last", "npts", "best_elbo", "best_mean",
+                                                                                "best_cov", "best_it")))
+                out[f"pf_hess_inv_h{h0:g}_{tag}"] = host(eng.lbfgs_hess_inv_batched(st))
+            if n <= 32:                                     # ADVI's batch is at most 32
+                P = D * (D + 1) // 2
+                scales, info = eng.empty(K, P), eng.batched_ints(K)
+                X, logq = eng.empty(K, n, D), eng.empty(K)
+                eng.advi_init_batched(mean, cov, scales, info, seeds=seeds, X=X, logq=logq)
+                out[f"advi_init_{tag}"] = host(scales, info, X, logq)
+                loc, sc = mean.clone(), eng.asarray(np.linalg.cholesky(covh)[:, np.tril_indices(D)[0], np.tril_indices(D)[1]])
+                mom = tuple(eng.zeros(K, m) for m in (D, D, P, P))
+                G = eng.asarray(rs.standard_normal((K, n, D)))
+                eng.advi_step_batched(G, loc, sc, mom, 1, 1e-2, seeds=seeds, call=1, Xout=X, logq=logq)
+                out[f"advi_step_{tag}"] = host(loc, sc, *mom, X, logq)
+
+
 def dump(path):
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     import gsmvi_amd
@@ -128,6 +194,7 @@ def dump(path):
     out = {}
     dump_glm(out, K)
     dump_softmax(out, K)
+    dump_initialisers(out, K)
     for D, B in SHAPES:
         rs = np.random.RandomState(100 * D + B)
         A = rs.standard_normal((K, D, D))
