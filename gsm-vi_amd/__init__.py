@@ -24,6 +24,9 @@ Mirrors the reference's public surface for the hot path (reference file:line):
     BatchedGLMTarget (the same launch for K
     Poisson, probit, Gaussian or logistic
     regressions with offsets)                    examples/example_gsm.py:34-35 (log_prob, jit(grad(.)))
+    SharedDesignGLMTarget (K such regressions on
+    ONE design matrix, with observation weights:
+    both products on the fp64 MFMA, no copy of A) examples/example_gsm.py:34-35 (log_prob, jit(grad(.)))
     BatchedSoftmaxTarget (K multinomial logit
     regressions of C classes, (C - 1) P <= 64:
     log-density and score in one launch)         examples/example_gsm.py:34-35 (log_prob, jit(grad(.)))
@@ -76,6 +79,7 @@ from .targets import GaussianTarget, device_score, score_from_logp   # noqa: F40
 from .targets import BatchedGaussianTarget, BatchedLogisticTarget    # noqa: F401
 from .targets import BatchedGLMTarget, GLMPrediction                 # noqa: F401
 from .targets import BatchedSoftmaxTarget                            # noqa: F401
+from .targets import SharedDesignGLMTarget                           # noqa: F401
 from .targets import predict_softmax_batched, SoftmaxPrediction      # noqa: F401
 from .batched import GSMBatch, gsm_update_batched                    # noqa: F401
 from .batched import BaMBatch, bam_update_batched, bam_lowrank_update_batched   # noqa: F401

@@ -899,6 +899,26 @@ class HipEngine:
                    self._packed(X, (K, nc, D), "X"), self._dp(G, (K, nc, D), "out"), self._dp(lp, (K, nc), "lp_out"))
         return ret
 
+    # ---- shared-design GLM target: K problems on one design matrix (csrc/gsmvi_glm_shared_batched.hip) -----------------------
+    def glm_shared_batched(self, X, A, y, family, offset=None, weights=None, prior_prec=1.0, noise_prec=1.0, out=None,
+                           lp_out=None, want="g"):
+        """Score and / or log-density of K generalised linear models that share ONE design matrix, at the rows of X (K, nc, D),
+        one launch on the fp64 MFMA [examples/example_gsm.py:34-35 for these models]: ``family`` and the precisions as in
+        ``glm_batched``; A (N, D) shared, y (K, N), ``offset`` None or (K, N) added to A x, ``weights`` None or (K, N)
+        observation weights >= 0 (a weight of 0 removes the observation whatever it holds).  ``want`` = "g" -> G (K, nc, D),
+        "lp" -> the values (K, nc), "both" -> (G, lp)."""
+        G, lp, ret = self._want_g_lp(want, X, out, lp_out)
+        fam, t, tp = self._glm_family_args(family, noise_prec, X.shape[0])
+        X = X.contiguous()
+        K, nc, D = X.shape
+        N = A.shape[0]
+        self._any_ctx()
+        r, rp = self._reg_arg(prior_prec, K)
+        self._call("gsmvi_glm_shared_batched_f64", K, D, nc, N, fam, self._packed(A, (N, D), "A"), self._packed(y, (K, N), "y"),
+                   self._dp(offset, (K, N), "offset"), self._dp(weights, (K, N), "weights"), t, tp, r, rp,
+                   self._packed(X, (K, nc, D), "X"), self._dp(G, (K, nc, D), "out"), self._dp(lp, (K, nc), "lp_out"))
+        return ret
+
     # ---- batched L-BFGS initialiser: K minimisations of one D (csrc/gsmvi_lbfgs_batched.hip) --------------------------------
     def lbfgs_state_batched(self, x0):
         """The state of K L-BFGS runs started at the rows of x0 (K, D), as include/gsmvi_hip.h lays it out: a dict of device

@@ -15,6 +15,8 @@ multinomial logit regressions (C classes, C - 1 linear predictors per row), a la
     BatchedGaussianTarget     (a Gaussian density)            gsmvi_gaussian_score_batched_f64   no
     BatchedLogisticTarget     y in [0, 1]                     gsmvi_logistic_batched_f64         yes
     BatchedGLMTarget          poisson, probit, gaussian, ...  gsmvi_glm_batched_f64              yes
+    SharedDesignGLMTarget     the same four, ONE A (N, D),    gsmvi_glm_shared_batched_f64       no (not a BatchedGLMTarget: the
+                              observation weights                                                isinstance checks refuse it)
     BatchedSoftmaxTarget      integer labels in 0 .. C - 1    gsmvi_softmax_batched_f64          laplace_init_softmax_batched and
                                                                                                  neg_hessian; predict, loo: no (TypeError):
                                                                                                  predict_softmax_batched,
@@ -388,6 +390,98 @@ class BatchedLogisticTarget(BatchedGLMTarget):
 
     def _call(self, x, **kw):           # the logistic entry point of its own: the model is the GLM's with no offset and tau = 1
         return self.engine.logistic_batched(x, self.A, self.y, self.counts, self.prior_precision, **kw)
+
+
+def _check_weights(weights, K, N):
+    """the observation weights as a host float64 array (None stays None): shape (K, N), finite and >= 0, else ValueError"""
+    if weights is None:
+        return None
+    sw = _shape(weights)
+    if sw != (K, N):
+        raise ValueError(f"weights: expected shape (K, N) = {(K, N)}, got {sw}")
+    wh = np.asarray(_host_array(weights), dtype=np.float64)
+    with np.errstate(invalid="ignore"):
+        bad = ~(np.isfinite(wh) & (wh >= 0.0))
+    if bad.any():
+        raise ValueError(f"weights: negative or non-finite values for problems {np.flatnonzero(bad.any(1)).tolist()}")
+    return wh
+
+
+class SharedDesignGLMTarget:
+    """K Bayesian generalised linear models on ONE design matrix, for ``GSMBatch``, ``BaMBatch``, ``ADVIBatch``,
+    ``BatchedKLMonitor``, ``lbfgs_init_batched``, ``pathfinder_init_batched`` and ``psis_batched``: ``BatchedGLMTarget``'s protocol
+    (attributes ``K``, ``N``, ``D``, ``family``; ``lp_g``, ``lp``, ``lp_and_score``) for the case where every problem has the same
+    covariates -- many responses regressed on one design, a sweep over the prior or noise precision, the Bayesian or case
+    bootstrap and tempered likelihoods.  ``A`` (N, D) is shared and held once; problem k has responses ``y[k]`` (N,), an optional
+    ``offset[k]`` (N,) added to the linear predictor, optional observation weights ``weights[k]`` (N,), finite and >= 0, and the
+    prior N(0, I / lam_k), ``prior_precision`` = lam a float or K values, 0 = flat.  With eta = A x + offset[k] and the link
+    (r, t) of ``family`` (the table of ``BatchedGLMTarget``):
+
+        lp_k(x) = sum_n w_kn t(eta_n, y_kn) - lam_k |x|^2 / 2,      grad lp_k(x) = sum_n w_kn r(eta_n, y_kn) a_n - lam_k x
+
+    evaluated by gsmvi_glm_shared_batched_f64: what examples/example_gsm.py:34-35 gets from a model's log_prob and
+    jit(grad(...)), with both sums on the fp64 MFMA and no copy of A per problem.  There is no ``counts``: a weight of 0 removes
+    an observation, and ``y`` and ``offset`` are validated only where the weight is > 0 (elsewhere anything goes, NaN included).
+    ``noise_precision`` = tau, a float or K values > 0, is the Gaussian family's alone.  A Poisson point whose exp(eta) overflows
+    at an observation with w > 0 gets NaN outputs (the fits then revert that step).  numpy arrays or tensors in; everything is
+    kept on the device as float64.  Arguments are validated on the host before any device work (ValueError naming the argument
+    and the problems).
+
+    ``lp_g(x, out=None)``: (K, B, D) -> (K, B, D) scores, ``device_native`` and ``graph_safe`` (one capturable launch, no
+    allocation with ``out``).  ``lp(x)``: (K, rows, D) -> (K, rows) values.  ``lp_and_score(x)``: (scores, values) from one launch.
+    Not a ``BatchedGLMTarget``: it has no ``neg_hessian``, ``predict`` or ``loo``, and ``laplace_init_batched``,
+    ``psis_loo_batched`` refuse it."""
+
+    FAMILIES = BatchedGLMTarget.FAMILIES
+
+    def __init__(self, A, y, family, prior_precision=1.0, offset=None, weights=None, noise_precision=1.0, engine=None):
+        if family not in self.FAMILIES:
+            raise ValueError(f"family: expected one of {self.FAMILIES}, got {family!r}")
+        sa = _shape(A)
+        if len(sa) != 2 or min(sa) < 1:
+            raise ValueError(f"A: expected shape (N, D) with N, D >= 1 (one design matrix for all problems), got {sa}")
+        N, D = sa
+        if not 1 <= D <= 64:
+            raise ValueError(f"A: D = {D} is outside 1 <= D <= 64")
+        sy = _shape(y)
+        if len(sy) != 2 or sy[0] < 1 or sy[1] != N:
+            raise ValueError(f"y: expected shape (K, N) with K >= 1 and N = {N}, got {sy}")
+        K = sy[0]
+        wh = _check_weights(weights, K, N)
+        live = wh > 0.0 if wh is not None else np.ones((1, N), dtype=bool)
+        yh = _check_responses(y, family, live)
+        oh = _check_offset(offset, K, N, live)
+        lam = _check_per_problem(prior_precision, "prior_precision", K)
+        tau = _check_per_problem(noise_precision, "noise_precision", K, positive=True, fixed=None if family == "gaussian" else
+                                 f"only family 'gaussian' has one (family {family!r}: leave it at 1.0)")
+        self.engine = engine if engine is not None else get_engine()
+        eng = self.engine
+        self.family = family
+        self.K, self.N, self.D = K, N, D
+        self.A = eng.asarray(A.contiguous() if isinstance(A, torch.Tensor) else A)
+        self.y = eng.asarray(yh)
+        self.offset = eng.asarray(oh) if oh is not None else None
+        self.weights = eng.asarray(wh) if wh is not None else None
+        self.prior_precision = float(lam) if lam.shape == () else eng.batched_regs(lam)
+        self.noise_precision = 1.0 if family != "gaussian" else float(tau) if tau.shape == () else eng.batched_regs(tau)
+
+        def lp_g(x, out=None):
+            return self._call(x, out=out, want="g")
+        lp_g.device_native = True
+        lp_g.graph_safe = True          # one capturable kernel launch, no allocation when `out` is given, no host work
+        self.lp_g = lp_g
+
+    def _call(self, x, **kw):
+        return self.engine.glm_shared_batched(x, self.A, self.y, self.family, offset=self.offset, weights=self.weights,
+                                              prior_prec=self.prior_precision, noise_prec=self.noise_precision, **kw)
+
+    def lp(self, x):
+        """(K, rows) values lp_k(x_kr) at the rows of x (K, rows, D), a device tensor or numpy; one launch"""
+        return self._call(self.engine.asarray(x), want="lp")
+
+    def lp_and_score(self, x):
+        """(scores (K, rows, D), values (K, rows)) from one launch"""
+        return self._call(self.engine.asarray(x), want="both")
 
 
 def _check_labels(y, C, live):

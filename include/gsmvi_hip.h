@@ -22,6 +22,7 @@
  *   advi.py:80-86 initial (loc, scales), :23-27 scales -> covariance    ->  gsmvi_advi_init_batched_f64, gsmvi_advi_cov_batched_f64
  *   examples/example_gsm.py:34-35 a model's log_prob and jit(grad(.)) of it, K logistic regressions -> gsmvi_logistic_batched_f64
  *   examples/example_gsm.py:34-35 the same for K Poisson, probit or Gaussian regressions with offsets -> gsmvi_glm_batched_f64
+ *   examples/example_gsm.py:34-35 the same for K such regressions on ONE design matrix, with observation weights -> gsmvi_glm_shared_batched_f64
  *   examples/example_gsm.py:34-35 the same for K multinomial logit (softmax) regressions of C classes -> gsmvi_softmax_batched_f64
  *   initializers.py:5-17 lbfgs_init (maximiser of lp, dense inverse-Hessian estimate), K problems -> gsmvi_lbfgs_step_batched_f64, gsmvi_lbfgs_hess_inv_batched_f64
  *   initializers.py:5-17 the same role by Newton rounds on the GLMs of examples/example_gsm.py:34-35 (no reference twin) -> gsmvi_glm_hessian_batched_f64, gsmvi_laplace_step_batched_f64,
@@ -532,6 +533,31 @@ int gsmvi_glm_batched_f64(gsmvi_ctx* ctx, void* stream, int64_t K, int D, int nc
                           const double* y, const double* offset, const int* counts_dev, double noise_prec,
                           const double* noise_prec_dev, double prior_prec, const double* prior_prec_dev, const double* X, double* G,
                           double* lp);
+
+/*
+ * Shared-design GLM target: the same four families for K problems that share ONE design matrix.  examples/example_gsm.py:34-35, a
+ * model's log_prob and lp_g = jit(grad(...)) of it, for K regressions on the same covariates (many responses, a sweep over the
+ * precisions, the Bayesian bootstrap) -> gsmvi_glm_shared_batched_f64.  A is (N x D), shared; y, offset (NULL = none) and weights
+ * (NULL = 1 everywhere) are (K x N) on the device; X, G (K x nc x D), lp (K x nc).  With eta_n = a_n . x + o_kn and (r, t) the
+ * family's link of gsmvi_glm_batched_f64 above,
+ *   lp[k, c] = sum_n w_kn t(eta_n, y_kn) - lam_k |x|^2 / 2,      G[k, c] = sum_n w_kn r(eta_n, y_kn) a_n - lam_k x.
+ * The K nc rows of X are stacked into one tall matrix and both sums run on the f64 MFMA against tiles of A: no copy of A per
+ * problem.  1 <= D <= 64, any N >= 1 and nc >= 1, K with the grid limits of gsmvi_glm_batched_f64 and K nc <= 64 (2^31 - 1).  There
+ * is no counts argument: a weight of 0 says the same.  An observation with w_kn = 0 (or a weight that is not > 0) contributes
+ * exactly nothing whatever y_kn, o_kn and eta hold there (removed by selection, not multiplied by 0); the weights' sign and the
+ * ranges of y are the caller's to keep.  The precisions are as in gsmvi_glm_batched_f64 (noise_prec: the Gaussian family only).
+ * Every output row sums over n in an order fixed by N alone (G: one accumulation chain over n ascending; lp: four interleaved
+ * partial sums added in a fixed order), with no atomics: the same bits from run to run, for any K and nc, alone or among other
+ * rows and problems.  A row of X with a non-finite entry gets NaN outputs, and a Poisson row for which some e^eta at an
+ * observation with w > 0 is not finite does; no other row is touched.  A non-finite entry of A reaches every problem (A is
+ * shared).  Checks (shapes, family, precisions, NULL arrays, G or lp, overlaps: G and lp are the written arrays, every other
+ * array is read-only) come before the context is looked at (then a NULL ctx) and return GSMVI_ERR_BAD_ARG before anything is
+ * enqueued.  Inputs are only read; no context workspace.  Sets GSMVI_PATH_BATCHED_TARGET.
+ */
+int gsmvi_glm_shared_batched_f64(gsmvi_ctx* ctx, void* stream, int64_t K, int D, int nc, int64_t N, int family, const double* A,
+                                 const double* y, const double* offset, const double* weights, double noise_prec,
+                                 const double* noise_prec_dev, double prior_prec, const double* prior_prec_dev, const double* X,
+                                 double* G, double* lp);
 
 /*
  * Batched softmax target: the log-density and the score of K Bayesian multinomial logit regressions of one (N, C, P) at nc points

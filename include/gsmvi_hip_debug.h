@@ -50,6 +50,10 @@ int gsmvi_debug_logistic_batched_lds(int D, int nc, int want, size_t* bytes, int
 int gsmvi_debug_glm_batched_lds(int D, int nc, int want, int family, int has_offset, size_t* bytes,
                                 int* problems_per_workgroup);
 
+/* The same for a gsmvi_glm_shared_batched_f64 launch of `family` at D (neither nc nor N plays a part: the one tile of A), and the
+ * stacked rows of X one workgroup takes.  Host arithmetic only, no device needed. */
+int gsmvi_debug_glm_shared_batched_lds(int D, int want, int family, size_t* bytes, int* rows_per_workgroup);
+
 /* The same for a gsmvi_softmax_batched_f64 launch at (C, P, nc), and the rows of X one tile holds at (C, P) (the launch holds
  * min(nc, that) rows).  Host arithmetic only, no device needed. */
 int gsmvi_debug_softmax_batched_lds(int C, int P, int nc, int want, size_t* bytes, int* problems_per_workgroup,
