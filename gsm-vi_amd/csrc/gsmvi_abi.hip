@@ -49,7 +49,8 @@ bool gsmvi_launch_gsm_cov_sym(hipStream_t st, hipEvent_t* ev, int D, int B, cons
                               int dbg, unsigned long long* stamps, int num_cu);
 void gsmvi_launch_panel_fast_part(hipStream_t st, hipEvent_t* ev, dim3 grid, int D, int B, const double* G, int ldg,
                                   const double* S0, int lds0, double* Pp, int chunks_per_wg, const double* X, int ldx,
-                                  const double* mu0, double* Qg, double* Qm, int chw, bool qm_whole, unsigned long long* stamps);
+                                  const double* mu0, double* Qg, double* Qm, int chw, bool qm_whole, int stream,
+                                  unsigned long long* stamps);
 void gsmvi_launch_gsm_cov_sym_slabs(hipStream_t st, hipEvent_t* ev, int D, int B, const struct gsm_slab_src& fs, const double* mu0,
                                     const double* S0, int lds0, double* S, int lds, double* mu_out, int kct, bool fold,
                                     bool s0_last, bool store_wt, bool qm_whole, unsigned long long* stamps);
@@ -330,6 +331,7 @@ int gsmvi_set_tuning(gsmvi_ctx* ctx, const char* name, int value) {
     else if (!strcmp(name, "cov_s0_last")) ctx->tune_cov_s0_last = value;
     else if (!strcmp(name, "cov_store_wt")) ctx->tune_cov_store_wt = value;
     else if (!strcmp(name, "panel_qm_whole")) ctx->tune_panel_qm_whole = value;
+    else if (!strcmp(name, "panel_stream")) ctx->tune_panel_stream = value;
     else if (!strcmp(name, "cov_dbg")) ctx->tune_cov_dbg = value;   // ablation bits, timing experiments only
     else if (!strcmp(name, "timeline")) {                           // whole-update timeline stamps (diagnostic)
         if (value && !ctx->stamps) {
@@ -683,8 +685,12 @@ static int gsm_two_launch(gsmvi_ctx* ctx, hipStream_t hs, int D, int B, int cpw,
     // (512-row chunks: one workgroup per (strip, slab, 16 samples) -- the launcher's comment in gsmvi_fast.hip)
     // round 10: one Qm value per sample ("panel_qm_whole"; the 512-row-chunk route only, D = 1024: one 16-byte unit per thread)
     const bool qm_whole = chw == 512 && D == 1024 && ctx->tune_panel_qm_whole != 0;
+    // round 12: the product's left operand streamed per wave ("panel_stream": 1 = in two stages, the count that measured faster at
+    // B = 32 in three jobs of three; 4 = in four, for A/B runs; the 512-row-chunk route without whole-sample
+    // Qm only; the same bytes either way, so no path bit -- the timeline's stamp words 4 - 7 tell the instances apart)
+    const int stream = (chw == 512 && D == 1024 && cpw == 1 && !qm_whole && ctx->tune_panel_stream != 0) ? (ctx->tune_panel_stream == 4 ? 4 : 2) : 0;
     gsmvi_launch_panel_fast_part(hs, ev0, dim3(strips, kc, chw == 512 ? B / 16 : 1), D, B, G, ldg, S0, lds0, ctx->pp, cpw, X, ldx, mu0, Qg, Qm, chw,
-                                 qm_whole, ctx->timeline_stamps(0));
+                                 qm_whole, stream, ctx->timeline_stamps(0));
     ctx->path |= GSMVI_PATH_PANEL_FAST | (chw == 512 ? GSMVI_PATH_PANEL_CHUNK512 : 0u) | (qm_whole ? GSMVI_PATH_PANEL_QM_WHOLE : 0u);
     int st = check_launch("k_panel_fast(partials)");
     if (st != GSMVI_OK) return st;

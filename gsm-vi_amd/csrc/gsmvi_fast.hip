@@ -56,7 +56,101 @@
 // where the pq_* loads are), forms (mu0 - x) g over its pair behind the store loop and the workgroup sums in a fixed order:
 // row16_sum, the 32 row sums through LDS (the reduction buffer is free by then), one thread adds them in index order and writes
 // Qm[b].  The slab-0 workgroups neither load X and mu0 nor form their pieces.
-template <int MT, bool HAS_SHIFT, int CHW, bool EXTRA, bool RIDER = false, bool RAG = false, bool PART = false, bool QMW = false>
+// STREAM (round 12; PART on the 512-row-chunk grid only, knob "panel_stream") = NSTAGE in {2, 4}: a wave loads the part of the left
+// operand that it multiplies, in NSTAGE pieces along K, and starts each piece's MFMAs behind that piece alone -- no workgroup
+// barrier and no wait for the other seven waves in front of the first MFMA (panel_stream_chunk below; two stages ship, DESIGN 8.1
+// round 12).  0 = the code as it was, instruction for instruction; -1 = that code with its landing profile in the timeline's stamps.
+// The chunk of a STREAM > 0 instance: wave w multiplies columns 64 w .. 64 w + 63 of the staged 16 x 512 chunk (ap = As + c * LDG +
+// 64 w + ks, MFMA step s = columns 4 s .. 4 s + 3 of them), so stage q = steps q * 16 / NS .. is the block of 16 sample rows x
+// 64 / NS columns at column 64 w + q * 64 / NS.  A wave-instruction loads RPI rows x UPR 16-byte units of it: lane l takes row
+// i * RPI + l / UPR, unit l % UPR (NS = 4: 8 rows x 128 B), and writes it to the position the operand reads use.  The eight
+// lanes of one ds_write_b128 group write eight consecutive units of one row = all 32 banks once: conflict-free.
+// Issue order: G of stage 0, S0 of stage 0, G of stage 1, ... , the three partial-dot loads last; vmcnt counts in issue order, so
+// the wait in front of stage q's staging leaves every load of the later stages outstanding.  Within a wave LDS operations
+// execute in order and no wave reads what another wrote before the barrier in front of the cross-wave reduction, so a stage
+// needs lgkmcnt(0) and a compiler barrier between its writes and its operand reads, nothing more.  The products enter the
+// accumulator in the order s = 0 .. 15 as they do without STREAM: bit-identical slabs.
+// Preconditions (the launcher checks them): D == 512 * gridDim.y (every wave's rows exist), nrows % 16 == 0.
+// Stamp words 4 - 7 (thread 0): stage 0 staged, first MFMA issued, last stage staged (also word 1), last MFMA done.
+template <int NS>
+__device__ __forceinline__ void panel_stream_chunk(double* As, int D, int nrows, const double* __restrict__ A, int lda, double alpha,
+                                                   const double* __restrict__ M, int ldm, const gsmvi_panel_extras& px,
+                                                   unsigned long long* __restrict__ stamps, v4d& acc, double& pq_g, double& pq_x,
+                                                   double& pq_m) {
+    static_assert(NS == 2 || NS == 4, "stages of the streamed left operand");
+    constexpr int LDG = 514;                       // as k_panel_fast<.., 512, ..>
+    constexpr int UPR = 32 / NS;                   // 16-B units per row and stage
+    constexpr int RPI = 64 / UPR;                  // rows per wave-instruction
+    constexpr int IPS = 16 / RPI;                  // wave-instructions (units per lane) per stage
+    constexpr int SPS = 16 / NS;                   // MFMA steps per stage
+    const int tid = threadIdx.x, w = tid >> 6, l = tid & 63, c = l & 15, ks = l >> 4;
+    const int cbase = blockIdx.y * 512, r0 = blockIdx.z * 16, j = blockIdx.x * 16 + c;
+    const int lrow = l / UPR, lcol = 64 * w + 2 * (l % UPR);       // this lane's row within an instruction, column within stage 0
+    unsigned long long t4 = 0, t5 = 0, t6 = 0;
+    v2d ga[NS][IPS];
+    double m[16];
+    unsigned okbits = 0;
+    const double* mp = M + (size_t)(cbase + 64 * w + ks) * ldm + j;
+#pragma unroll
+    for (int q = 0; q < NS; ++q) {
+#pragma unroll
+        for (int i = 0; i < IPS; ++i) {
+            const int grow = r0 + i * RPI + lrow, col = cbase + lcol + q * (64 / NS);
+            const bool ok = grow < nrows && col < D;
+            ga[q][i] = *reinterpret_cast<const v2d*>(A + (size_t)(grow < nrows ? grow : nrows - 1) * lda + (col < D ? col : 0));
+            okbits |= (ok ? 1u : 0u) << (q * IPS + i);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int s = q * SPS; s < (q + 1) * SPS; ++s) m[s] = mp[(size_t)(4 * s) * ldm];
+        __builtin_amdgcn_sched_barrier(0);
+    }
+    {                                              // the partial-dot loads, as k_panel_fast<.., PART> issues them: last
+        const int prow = r0 + ((tid >> 4) & 15), pcol = blockIdx.x * 16 + (tid & 15);
+        pq_g = A[(size_t)prow * lda + pcol];
+        pq_x = px.sj_src[(size_t)prow * px.sj_len + pcol];     // X, ldx
+        pq_m = px.msl[pcol];                                   // mu0
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    const double* ap = As + c * LDG + 64 * w + ks;
+#pragma unroll
+    for (int q = 0; q < NS; ++q) {
+#pragma unroll
+        for (int i = 0; i < IPS; ++i) {
+            v2d v = ga[q][i];
+            if (!((okbits >> (q * IPS + i)) & 1u)) v = (v2d){0.0, 0.0};
+            v.x *= alpha; v.y *= alpha;
+            *reinterpret_cast<v2d*>(&As[(i * RPI + lrow) * LDG + lcol + q * (64 / NS)]) = v;
+        }
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");     // this wave's writes are in LDS; no other wave's are read
+        __builtin_amdgcn_wave_barrier();
+        if (stamps) { if (q == 0) t4 = __builtin_amdgcn_s_memrealtime(); if (q == NS - 1) t6 = __builtin_amdgcn_s_memrealtime(); }
+        double av[SPS];
+#pragma unroll
+        for (int s = 0; s < SPS; ++s) av[s] = ap[q * (64 / NS) + 4 * s];
+#pragma unroll
+        for (int s = 0; s < SPS; ++s) {
+            acc = GSMVI_MFMA_F64(av[s], m[q * SPS + s], acc);
+            if (stamps && q == 0 && s == 0) t5 = __builtin_amdgcn_s_memrealtime();
+        }
+        __builtin_amdgcn_sched_barrier(0);         // stage q + 1's staging stays behind stage q's MFMAs
+    }
+    if (stamps) {                                  // (times are kept in registers until here: a stamp store would count in vmcnt)
+        asm volatile("" ::"s"(__builtin_amdgcn_readfirstlane(__double2loint(acc[0]))) : "memory");   // the last MFMA's result exists
+        const unsigned long long t7 = __builtin_amdgcn_s_memrealtime();
+        const unsigned wg = (blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
+        if (tid == 0 && wg < GSMVI_STAMP_WG) {
+            stamps[(size_t)wg * 8 + 1] = t6;       // "left operand staged", as without STREAM: wave 0's last stage
+            stamps[(size_t)wg * 8 + 4] = t4;
+            stamps[(size_t)wg * 8 + 5] = t5;
+            stamps[(size_t)wg * 8 + 6] = t6;
+            stamps[(size_t)wg * 8 + 7] = t7;
+        }
+    }
+}
+
+template <int MT, bool HAS_SHIFT, int CHW, bool EXTRA, bool RIDER = false, bool RAG = false, bool PART = false, bool QMW = false,
+          int STREAM = 0>
 __global__ __launch_bounds__(512) void k_panel_fast(int D, int nrows, const double* __restrict__ A, int lda,
                                                     const double* __restrict__ shift, double alpha,
                                                     const double* __restrict__ M, int ldm,
@@ -98,10 +192,20 @@ __global__ __launch_bounds__(512) void k_panel_fast(int D, int nrows, const doub
     for (int mt = 0; mt < MT; ++mt) acc[mt] = (v4d){0.0, 0.0, 0.0, 0.0};
     static_assert(!PART || (MT <= 2 && !RAG && !RIDER && !HAS_SHIFT), "partial dots: one pass of the store loop, on the grid");
     static_assert(!QMW || (PART && CHW == 512 && MT == 1), "whole-sample Qm: the 512-row-chunk product of the two-launch form");
+    static_assert(STREAM == 0 || (PART && CHW == 512 && MT == 1 && !RAG && !RIDER && !EXTRA && !HAS_SHIFT && !QMW),
+                  "streamed left operand: the 512-row-chunk product of the two-launch form");
+    // STREAM = -1: the code of STREAM = 0 with the landing profile of its one load batch in stamp words 4 - 7 (launched only with the
+    // timeline diagnostic on and "panel_stream" = 0, so that the instance without stamps stays what it was)
+    constexpr bool LANDING = STREAM == -1;
+    [[maybe_unused]] unsigned long long tl_first = 0, tl_last = 0, tl_s0 = 0;
     double pq_g = 0.0, pq_x = 0.0, pq_m = 0.0;     // PART: G, X, mu0 at this thread's (sample, column) of the store loop
     [[maybe_unused]] v2d wq_g, wq_x, wq_m;         // QMW: unit tid of G[b], X[b], mu0 in the workgroup that sums Qm[b]
 
     for (int ch = 0; ch < chunks_per_wg; ++ch) {
+        if constexpr (STREAM > 0) {        // one chunk per workgroup (the launcher checks it)
+            panel_stream_chunk<STREAM>(As, D, nrows, A, lda, alpha, M, ldm, px, stamps, acc[0], pq_g, pq_x, pq_m);
+            break;
+        }
         const int cbase = (blockIdx.y * chunks_per_wg + ch) * CHW;          // block-uniform
         if (cbase >= D) break;
         const int wbase = cbase + w * RW;                                   // wave-uniform: 8 waves x RW rows
@@ -204,6 +308,10 @@ __global__ __launch_bounds__(512) void k_panel_fast(int D, int nrows, const doub
         for (int q = 0; q < UPT; ++q) {
             const int u = q * 512 + tid;
             const int row = u / U16, c16 = u % U16;
+            if constexpr (LANDING) {       // this wave's first / last G unit landed (8 G units, 16 S0 loads and 3 partial-dot loads
+                if (stamps && q == 0) { asm volatile("s_waitcnt vmcnt(26)" ::: "memory"); tl_first = __builtin_amdgcn_s_memrealtime(); }     // in flight:
+                if (stamps && q == UPT - 1) { asm volatile("s_waitcnt vmcnt(19)" ::: "memory"); tl_last = __builtin_amdgcn_s_memrealtime(); }   // issue order)
+            }
             v2d v = ga[q];
             if (!((okbits >> q) & 1u)) v = HAS_SHIFT ? gs[q] : (v2d){0.0, 0.0};   // contributes alpha*(x-x) = 0
             if (HAS_SHIFT) { v.x -= gs[q].x; v.y -= gs[q].y; }
@@ -212,6 +320,17 @@ __global__ __launch_bounds__(512) void k_panel_fast(int D, int nrows, const doub
         }
         __syncthreads();
         PSTAMP(1);                         // left operand staged (the M stream may still be in flight)
+        if constexpr (LANDING) {           // words 4 - 6: wave 0's first G unit, last G unit and last S0 load landed (wave 0 alone waits for
+            if (stamps && w == 0) {        // its S0 in front of its MFMAs); word 7: wave 7's last G unit -- the skew the barrier above absorbs.
+                asm volatile("s_waitcnt vmcnt(3)" ::: "memory");       // Kept in registers until here: a stamp store would count in vmcnt.
+                tl_s0 = __builtin_amdgcn_s_memrealtime();
+            }
+            const unsigned wg_ = (blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
+            if (stamps && wg_ < GSMVI_STAMP_WG) {
+                if (tid == 0) { stamps[(size_t)wg_ * 8 + 4] = tl_first; stamps[(size_t)wg_ * 8 + 5] = tl_last; stamps[(size_t)wg_ * 8 + 6] = tl_s0; }
+                if (tid == 448) stamps[(size_t)wg_ * 8 + 7] = tl_last;
+            }
+        }
         if (wave_in) {
             const double* ap = As + c * LDG + RW * w + ks;
             double av[MT][NST];                     // operands to registers first: no LDS round trip per MFMA step
@@ -1401,7 +1520,8 @@ void gsmvi_launch_panel_fast(hipStream_t st, hipEvent_t* ev, int MT, dim3 grid, 
 // the MT = 2 form on 128 workgroups staged 128 KB per workgroup and was 2 us slower per launch).
 void gsmvi_launch_panel_fast_part(hipStream_t st, hipEvent_t* ev, dim3 grid, int D, int B, const double* G, int ldg,
                                   const double* S0, int lds0, double* Pp, int chunks_per_wg, const double* X, int ldx,
-                                  const double* mu0, double* Qg, double* Qm, int chw, bool qm_whole, unsigned long long* stamps) {
+                                  const double* mu0, double* Qg, double* Qm, int chw, bool qm_whole, int stream,
+                                  unsigned long long* stamps) {
     gsmvi_panel_extras px;                     // (PART's arguments ride in free members: gsmvi_ctx.h)
     px.sj_src = X;
     px.sj_len = ldx;
@@ -1413,7 +1533,15 @@ void gsmvi_launch_panel_fast_part(hipStream_t st, hipEvent_t* ev, dim3 grid, int
     if (chw == 512 && qm_whole)             // one Qm value per sample from the idle slab-1 workgroups (QMW above)
         GSMVI_LAUNCH((k_panel_fast<1, false, 512, false, false, false, true, true>), grid, dim3(512), 0, st, ev, D, B, G, ldg, nullptr, 1.0, S0,
                      lds0, Pp, chunks_per_wg, D, stamps, nullptr, 0, nullptr, px);
-    else if (chw == 512) PFQ(1, 512);
+    else if (chw == 512 && stream != 0 && chunks_per_wg == 1 && D == 512 * (int)grid.y && B % 16 == 0) {
+        // the left operand streamed per wave (STREAM above; knob "panel_stream"): the same slabs and partials, bit for bit
+#define PFS(NS) GSMVI_LAUNCH((k_panel_fast<1, false, 512, false, false, false, true, false, NS>), grid, dim3(512), 0, st, ev, D, B, G, ldg, \
+                             nullptr, 1.0, S0, lds0, Pp, chunks_per_wg, D, stamps, nullptr, 0, nullptr, px)
+        if (stream == 4) PFS(4); else PFS(2);
+    } else if (chw == 512 && stamps != nullptr && chunks_per_wg == 1) {
+        PFS(-1);                            // timeline diagnostic: the unstreamed code with its landing profile in words 4 - 7
+#undef PFS
+    } else if (chw == 512) PFQ(1, 512);
     else { if (B == 16) PFQ(1, 256); else PFQ(2, 256); }
 #undef PFQ
 }

@@ -112,6 +112,10 @@ int gsmvi_destroy(gsmvi_ctx* ctx);
  * "cov_store_wt" (1 = Sigma' is stored write-through, where D * lds * 8 < 2^31; the lines do not stay in the L2);
  * "panel_qm_whole" (same route; 1 = the product leaves one (mu0 - x_b).g_b per sample instead of D / 16 pieces that every
  * covariance workgroup re-sums; another summation order, so mu and Sigma' move at rounding level; default 0);
+ * round 12: "panel_stream" (the product launch of the same route, without "panel_qm_whole": 1 = every wave loads the part of
+ * G that it multiplies, in two stages along K, and starts a stage's MFMAs behind that stage's loads alone, with no workgroup
+ * barrier in front of the first MFMA; 4 = in four stages, 2 = as 1, for A/B runs; 0 = one load batch staged by the whole workgroup behind a
+ * barrier; bit-identical results, no path bit: the timeline diagnostic's stamp words 4 - 7 of the product tell them apart);
  * diagnostics "timeline", "cov_dbg"
  * (see gsmvi_hip_debug.h). */
 int gsmvi_set_tuning(gsmvi_ctx* ctx, const char* name, int value);

@@ -47,7 +47,8 @@ for trial in range(4):
         for c in cols:
             s += f"[{c}] {np.nanmin(us[:, c]):6.2f}/{np.nanmedian(us[:, c]):6.2f}/{np.nanmax(us[:, c]):6.2f}  "
         print(s)
-        first, last = np.nanmin(us[:, cols[0]]), np.nanmax(us[:, cols[-1]])
+        end_col = 3 if k == 0 else cols[-1]      # the product's words 4 - 7 lie inside its run: [3] is its end
+        first, last = np.nanmin(us[:, cols[0]]), np.nanmax(us[:, end_col])
         if prev_end is not None:
             print(f"         gap from previous kernel's last stamp to this kernel's first start: {first - prev_end:.2f} us")
         print(f"         span {last - first:.2f} us")
@@ -89,3 +90,19 @@ if len(end) == (nt >> 1) * ((nt + 1) >> 1):
 a = st[0]; live = a[:, 0] > 0; usp = (a[live] - t0) / 100.0
 php = np.diff(usp[:, :4], axis=1)
 print("panel phase medians (staged, mfma, end):", np.round(np.median(php, axis=0), 2), " p95:", np.round(np.percentile(php, 95, axis=0), 2))
+# ---- the product's words 4 - 7 (round 12) ----
+def _mp(x):
+    return f"{np.median(x):.2f} (p95 {np.percentile(x, 95):.2f}, max {x.max():.2f})"
+if (a[live][:, 4:8] > 0).all():
+    t = usp - usp[:, :1]
+    if (a[live][:, 1] == a[live][:, 6]).all():      # "panel_stream": [4] stage 0 staged, [5] first MFMA issued, [6] = [1] last stage staged, [7] last MFMA done
+        print("panel (streamed), us after the workgroup's start, median (p95, max): stage 0 staged", _mp(t[:, 4]), " first MFMA issued", _mp(t[:, 5]),
+              " last stage staged", _mp(t[:, 6]), " last MFMA done", _mp(t[:, 7]))
+        print("panel (streamed) per stage: start -> stage 0 staged", _mp(t[:, 4]), " stage 0 -> last stage staged", _mp(t[:, 6] - t[:, 4]),
+              " last stage staged -> last MFMA done", _mp(t[:, 7] - t[:, 6]), " -> reduction barrier", _mp(t[:, 2] - t[:, 7]), " -> end", _mp(t[:, 3] - t[:, 2]))
+    else:                                           # "panel_stream" = 0: wave 0's [4] first G unit, [5] last G unit, [6] last S0 load landed; [7] wave 7's last G unit
+        print("panel landing profile, us after the workgroup's start, median (p95, max): first G", _mp(t[:, 4]), " last G", _mp(t[:, 5]),
+              " staged", _mp(t[:, 1]), " last S0", _mp(t[:, 6]))
+        print("panel landing profile: first G -> last G", _mp(t[:, 5] - t[:, 4]), " last G -> staged", _mp(t[:, 1] - t[:, 5]),
+              " last G -> last S0", _mp(t[:, 6] - t[:, 5]), " wave skew |wave 7 - wave 0| of the last G unit", _mp(np.abs(t[:, 7] - t[:, 5])),
+              " staged - later wave's last G", _mp(t[:, 1] - np.maximum(t[:, 5], t[:, 7])))
