@@ -663,7 +663,273 @@ typedef unsigned int v4u __attribute__((ext_vector_type(4)));   // the payload t
 // QMW (round 10; the KCT = 2 forms only, knob "panel_qm_whole") = the product launch left ONE Qm value per sample
 // (k_panel_fast<.., PART, QMW>): mv is one 8-byte load issued with the Qg units; the two Qm units, their sum and the second
 // row16_sum are gone from the chain.  mv is summed in another order than the per-strip pieces: mu and S move at rounding level.
-template <int SB, bool RAG, bool FROM_SLABS = false, int KCT = 4, bool FOLD = false, bool S0L = false, bool WT = false, bool QMW = false>
+// QUAD (round 13; FROM_SLABS, even nt; knob "cov_diag_quad") = another item map with no hosts.  The first nt/2 workgroups are
+// QUADS: quad p owns the upper triangle of the diagonal 64 x 64 block, tiles (2p, 2p), (2p, 2p + 1), (2p + 1, 2p + 1), stages the
+// column blocks A = 2p and B = 2p + 1 alone (four LDS tiles) and writes mu of both.  Every other tile (i, j) has j/2 > i/2 and
+// belongs to the pair (i; 2 (j/2), 2 (j/2) + 1): nt/2 - i/2 - 1 pairs in row i, never diagonal, never a host, the two-tile code
+// below as it is.  (nt/2)^2 workgroups in all -- 256 at D = 1024, one per CU as with FOLD -- the quads first.
+// A quad is this function.  Its ten 16 x 16 blocks (block (1, 0) of a diagonal tile is the transpose of block (0, 1): the same
+// products in the same k order, so it is written, not computed) are twenty chains of SB/4 MFMAs, five per SIMD (waves s, s + 4):
+//   waves 4-7: the four blocks of tile (A, B), block (wr, wc) as in a pair: d- and e-chain each;
+//   wave 0: (A, A) block (0, 0); wave 1: (A, A) (0, 1); wave 2: (A, A) (1, 1); wave 3: (B, B) (0, 0): d- and e-chain each;
+//   (B, B) block (0, 1): d-chain on wave 0, e-chain on wave 1;  (B, B) block (1, 1): d-chain on wave 2, e-chain on wave 3.
+// A split block's d-accumulator goes through LDS outside the staged tiles, so the barrier that ends the operand reads also hands
+// it over, and the e wave forms (accd - acce) * invB from the same values.  Every chain runs s = 0 .. NS - 1 from zero as in a
+// host or a diagonal workgroup, W = S0 + U reads the whole S0 tile (its lower-left block too), and the means take the two-level
+// order of the record form: mu and S are those of FOLD and of the plain grid bit for bit.  Stores: tile (A, A) by waves 0-3,
+// tile (A, B) by waves 4-7, tile (B, B) one unit per thread, then the mirror of (A, B) by waves 4-7 -- four tile stores, as a pair.
+// LDS behind the MFMAs: three LW buffers, the two dmu tiles, their 2 x [8][32] partial sums; the 2 x 256 handed-over accumulators
+// lie behind those and behind the staged tiles (COV_QUAD_LDS doubles: 41 728 B at SB = 16, inside the six tiles at SB = 32).
+template <int SB>
+constexpr int COV_QUAD_SCR = (3 * 32 * 33 + 2 * SB * 32 + 512 > 4 * SB * 48) ? 3 * 32 * 33 + 2 * SB * 32 + 512 : 4 * SB * 48;
+template <int SB>
+constexpr int COV_QUAD_LDS = COV_QUAD_SCR<SB> + 512;
+
+template <int SB, int KCT, bool S0L, bool WT>
+__device__ __forceinline__ void gsm_cov_quad(double* __restrict__ smem, int p, int D, int B, double invB, const double* __restrict__ mu0,
+                                             const double* __restrict__ S0, int lds0, double* __restrict__ S, int lds,
+                                             double* __restrict__ mu_out, unsigned long long* __restrict__ stamps, const gsm_slab_src& fs) {
+#define QBARRIER()                                                                        \
+    do {                                                                                  \
+        if constexpr (S0L) asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); \
+        else __syncthreads();                                                             \
+    } while (0)
+#define QSTAMP(k)                                                                         \
+    do {                                                                                  \
+        if (stamps && threadIdx.x == 0) stamps[(size_t)blockIdx.x * 8 + (k)] = __builtin_amdgcn_s_memrealtime(); \
+    } while (0)
+    constexpr int RS = 48, TILE = SB * RS, NU = SB * 16, NS = SB / 4, NQG = 2 * KCT;
+    constexpr int LWS = 32 * 33, MUO = 3 * LWS, PAO = MUO + 2 * SB * 32, SCO = COV_QUAD_SCR<SB>;
+    static_assert(512 % NU == 0 && (KCT == 2 || KCT == 4), "two-launch form: B == SB in {16, 32}");
+    static_assert(SCO >= 4 * TILE && SCO >= PAO + 512, "handed-over accumulators outside the staged tiles and the store path's LDS");
+    const int A0 = 64 * p, B0 = A0 + 32;
+    const int tid = threadIdx.x, w = tid >> 6, l = tid & 63, c = l & 15, ks = l >> 4;
+    const int t = w >> 2, wr = (w >> 1) & 1, wc = w & 1, tl = tid & 255;
+    const int Jt = t ? B0 : A0;                  // S0 and store units of waves 0-3: tile (A, A); of waves 4-7: tile (A, B)
+    const int u = tid & (NU - 1), b = u >> 4, ln = u & 15, c2 = 2 * ln;
+    const bool st_d = (NU == 512) || tid < NU, st_e = (NU == 512) || tid >= NU;
+    const int nqg = (fs.KC * fs.strips) >> 1, nqm = fs.strips >> 1;
+    auto ld16 = [](const double* base, unsigned byte_off) {
+        return *reinterpret_cast<const v2d*>(reinterpret_cast<const char*>(base) + byte_off);
+    };
+    v2d s0v[2], s0x;
+    auto load_s0 = [&]() {
+#pragma unroll
+        for (int q = 0; q < 2; ++q) {
+            const int unit = q * 256 + tl;
+            s0v[q] = *reinterpret_cast<const v2d*>(S0 + (size_t)(A0 + (unit >> 4)) * lds0 + Jt + 2 * (unit & 15));
+        }
+        s0x = *reinterpret_cast<const v2d*>(S0 + (size_t)(B0 + (tid >> 4)) * lds0 + B0 + 2 * (tid & 15));
+    };
+    if constexpr (!S0L) {
+        load_s0();
+        __builtin_amdgcn_sched_barrier(0);
+    }
+    const unsigned qg0 = (unsigned)(b * nqg) * 16u, qm0 = (unsigned)(b * nqm) * 16u;
+    v2d qg[NQG], qm[2];
+#pragma unroll
+    for (int k = 0; k < NQG; ++k) qg[k] = ld16(fs.Qg, qg0 + 16u * (unsigned)(ln + 16 * k < nqg ? ln + 16 * k : nqg - 1));
+#pragma unroll
+    for (int k = 0; k < 2; ++k) qm[k] = ld16(fs.Qm, qm0 + 16u * (unsigned)(ln + 16 * k < nqm ? ln + 16 * k : nqm - 1));
+    double mu0q = 0.0;                           // mu0 of the mean epilogue: entries A0 .. A0 + 63 on wave 0
+    if (w == 0) mu0q = mu0[A0 + l];
+    const int col[2] = {A0 + c2, B0 + c2};
+    const size_t slab = (size_t)B * D;
+    v2d xv[2], m0[2], sl[2][KCT];
+    auto load_block = [&](int cb) {
+        xv[cb] = *reinterpret_cast<const v2d*>(fs.X + (size_t)b * fs.ldx + col[cb]);
+        m0[cb] = ld16(mu0, 8u * (unsigned)col[cb]);
+#pragma unroll
+        for (int kc = 0; kc < KCT; ++kc)
+            sl[cb][kc] = *reinterpret_cast<const v2d*>(fs.Pp + (size_t)(KCT == 2 ? kc : (kc < fs.KC ? kc : fs.KC - 1)) * slab + (size_t)b * D + col[cb]);
+    };
+    load_block(0);
+    if constexpr (KCT == 2) load_block(1);
+    if constexpr (S0L) {                         // the three S0 units: the last global loads
+        __builtin_amdgcn_sched_barrier(0);
+        load_s0();
+        __builtin_amdgcn_sched_barrier(0);
+    }
+    double gs = 0.0, ms = 0.0;
+#pragma unroll
+    for (int k = 0; k < NQG; ++k) {
+        const bool in = ln + 16 * k < nqg;
+        gs += in ? qg[k].x : 0.0;
+        gs += in ? qg[k].y : 0.0;
+    }
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+        const bool in = ln + 16 * k < nqm;
+        ms += in ? qm[k].x : 0.0;
+        ms += in ? qm[k].y : 0.0;
+    }
+    if constexpr (KCT == 4) {                    // second batch behind the sums, as in the pairs
+        asm volatile("" : "+v"(gs), "+v"(ms) : : "memory");
+        load_block(1);
+    }
+    const double gSg = row16_sum(gs);
+    const double mv = row16_sum(ms);
+    const double rho = 0.5 * sqrt(1.0 + 4.0 * (gSg + mv * mv)) - 0.5;
+    const double den = 1.0 + rho + mv;
+    double beta = 1.0 / (1.0 + rho), cc = (gSg - mv) / den;
+    if (stamps) {
+        if constexpr (S0L) asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
+        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        QSTAMP(1);
+    }
+    v2d dmuq[2];
+#pragma unroll
+    for (int cb = 0; cb < 2; ++cb) {
+        v2d sg = {0.0, 0.0}, dd, dm, ee;
+        if constexpr (KCT == 2) {
+            if (cb == 0) asm volatile("" : "+v"(beta), "+v"(cc), "+v"(xv[0]), "+v"(m0[0]), "+v"(sl[0][0]), "+v"(sl[0][1]));
+            else asm volatile("" : "+v"(xv[cb]), "+v"(m0[cb]), "+v"(sl[cb][0]), "+v"(sl[cb][1]));
+            sg.x = sl[cb][0].x + sl[cb][1].x;
+            sg.y = sl[cb][0].y + sl[cb][1].y;
+        } else {
+#pragma unroll
+            for (int kc = 0; kc < 4; ++kc) {
+                sg.x += (kc < fs.KC) ? sl[cb][kc].x : 0.0;
+                sg.y += (kc < fs.KC) ? sl[cb][kc].y : 0.0;
+            }
+        }
+        dd.x = m0[cb].x - xv[cb].x;
+        dd.y = m0[cb].y - xv[cb].y;
+        dm.x = beta * ((sg.x - dd.x) - cc * dd.x);
+        dm.y = beta * ((sg.y - dd.y) - cc * dd.y);
+        ee.x = dd.x + dm.x;
+        ee.y = dd.y + dm.y;
+        if (st_d) *reinterpret_cast<v2d*>(smem + (2 * cb) * TILE + b * RS + c2) = dd;
+        if (st_e) *reinterpret_cast<v2d*>(smem + (2 * cb + 1) * TILE + b * RS + c2) = ee;
+        dmuq[cb] = dm;
+    }
+    QBARRIER();
+    QSTAMP(2);
+    // ---- the chains: a whole block per wave (LDS tiles: 0 = D_A, 1 = E_A, 2 = D_B, 3 = E_B), then one chain of a split block
+    v4d accd = {0.0, 0.0, 0.0, 0.0}, acce = {0.0, 0.0, 0.0, 0.0}, xacc = {0.0, 0.0, 0.0, 0.0};
+    {
+        const int ta = (w == 3) ? 2 : 0, tb = (w >= 3) ? 2 : 0;                  // wave-uniform
+        const int br = (w >= 4) ? wr : (w == 2 ? 1 : 0), bc = (w >= 4) ? wc : ((w == 1 || w == 2) ? 1 : 0);
+        const double* adp = smem + ta * TILE + ks * RS + 16 * br + c;
+        const double* bdp = smem + tb * TILE + ks * RS + 16 * bc + c;
+        double ad[NS], ae[NS], bd[NS], be[NS];
+#pragma unroll
+        for (int s = 0; s < NS; ++s) {
+            ad[s] = adp[4 * s * RS];
+            ae[s] = adp[TILE + 4 * s * RS];
+            bd[s] = bdp[4 * s * RS];
+            be[s] = bdp[TILE + 4 * s * RS];
+        }
+#pragma unroll
+        for (int s = 0; s < NS; ++s) {
+            accd = GSMVI_MFMA_F64(ad[s], bd[s], accd);
+            acce = GSMVI_MFMA_F64(ae[s], be[s], acce);
+        }
+        if (w < 4) {                             // (B, B) block (w >> 1, 1): the d-chain on the even wave, the e-chain on the odd one
+            const double* xp = smem + (2 + (w & 1)) * TILE + ks * RS + c;
+#pragma unroll
+            for (int s = 0; s < NS; ++s) {
+                ad[s] = xp[4 * s * RS + 16 * (w >> 1)];
+                bd[s] = xp[4 * s * RS + 16];
+            }
+#pragma unroll
+            for (int s = 0; s < NS; ++s) xacc = GSMVI_MFMA_F64(ad[s], bd[s], xacc);
+            if (!(w & 1)) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r) smem[SCO + (w >> 1) * 256 + r * 64 + l] = xacc[r];
+            }
+        }
+    }
+    QBARRIER();                                  // the factor tiles are read, the d-accumulators of the split blocks are in LDS
+    {
+        const int lw = (w >= 4) ? 1 : (w == 3 ? 2 : 0);
+        const int br = (w >= 4) ? wr : (w == 2 ? 1 : 0), bc = (w >= 4) ? wc : ((w == 1 || w == 2) ? 1 : 0);
+        double* LW = smem + lw * LWS;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const double v = (accd[r] - acce[r]) * invB;
+            LW[(16 * br + ks + 4 * r) * 33 + 16 * bc + c] = v;
+            if (w == 1) LW[(16 + c) * 33 + ks + 4 * r] = v;                      // (A, A) block (1, 0) = block (0, 1)^T
+        }
+        if (w < 4 && (w & 1)) {
+            double* LX = smem + 2 * LWS;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const double v = (smem[SCO + (w >> 1) * 256 + r * 64 + l] - xacc[r]) * invB;
+                LX[(16 * (w >> 1) + ks + 4 * r) * 33 + 16 + c] = v;
+                if (w == 1) LX[(16 + c) * 33 + ks + 4 * r] = v;                  // (B, B) block (1, 0) = block (0, 1)^T
+            }
+        }
+    }
+    if (tid < NU) {                              // the dmu tiles of blocks A and B, [SB][32] each
+        *reinterpret_cast<v2d*>(smem + MUO + (tid >> 4) * 32 + 2 * (tid & 15)) = dmuq[0];
+        *reinterpret_cast<v2d*>(smem + MUO + SB * 32 + (tid >> 4) * 32 + 2 * (tid & 15)) = dmuq[1];
+    }
+    QSTAMP(3);
+    QBARRIER();
+    if constexpr (S0L) {
+        if (stamps) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); QSTAMP(6); }
+    }
+    [[maybe_unused]] __amdgpu_buffer_rsrc_t srs;
+    if constexpr (WT) srs = __builtin_amdgcn_make_buffer_rsrc(S, 0, (int)(((size_t)(D - 1) * lds + D) * sizeof(double)), 0x00020000);
+    auto store_s = [&](size_t off, v2d v) {
+        if constexpr (WT) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(v4u, v), srs, (int)(off * sizeof(double)), 0, 16);
+        else *reinterpret_cast<v2d*>(S + off) = v;
+    };
+    {                                            // first level of the means: block tid >> 8, row group (tid >> 5) & 7, column tid & 31
+        const double* mt = smem + MUO + (tid >> 8) * SB * 32;
+        double part = 0.0;
+#pragma unroll
+        for (int k = 0; k < SB / 8; ++k) part += mt[(((tid >> 5) & 7) + 8 * k) * 32 + (tid & 31)];
+        smem[PAO + tid] = part;                  // 2 x [8][32]
+    }
+    {
+        double* LW = smem + t * LWS;
+#pragma unroll
+        for (int q = 0; q < 2; ++q) {
+            const int unit = q * 256 + tl, i = unit >> 4, j2 = unit & 15;
+            v2d wv2;
+            wv2.x = s0v[q].x + LW[i * 33 + 2 * j2];
+            wv2.y = s0v[q].y + LW[i * 33 + 2 * j2 + 1];
+            store_s((size_t)(A0 + i) * lds + Jt + 2 * j2, wv2);
+            if (t) {                             // tile (A, B) goes back to LDS for its mirror
+                LW[i * 33 + 2 * j2] = wv2.x;
+                LW[i * 33 + 2 * j2 + 1] = wv2.y;
+            }
+        }
+    }
+    {                                            // tile (B, B): one unit per thread, no mirror
+        const int i = tid >> 4, j2 = tid & 15;
+        v2d wv2;
+        wv2.x = s0x.x + smem[2 * LWS + i * 33 + 2 * j2];
+        wv2.y = s0x.y + smem[2 * LWS + i * 33 + 2 * j2 + 1];
+        store_s((size_t)(B0 + i) * lds + B0 + 2 * j2, wv2);
+    }
+    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");   // LDS only: the stores above stay in flight
+    if (t) {
+        const double* LW = smem + LWS;
+#pragma unroll
+        for (int q = 0; q < 2; ++q) {
+            const int unit = q * 256 + tl, j = unit >> 4, i2 = unit & 15;
+            v2d m2;
+            m2.x = LW[(2 * i2) * 33 + j];
+            m2.y = LW[(2 * i2 + 1) * 33 + j];
+            store_s((size_t)(B0 + j) * lds + A0 + 2 * i2, m2);
+        }
+    }
+    if (w == 0) {                                // second level: mu of blocks A (lanes 0-31) and B (lanes 32-63)
+        double s = 0.0;
+#pragma unroll
+        for (int q = 0; q < 8; ++q) s += smem[PAO + (l >> 5) * 256 + q * 32 + (l & 31)];
+        mu_out[A0 + l] = mu0q + s * invB;
+    }
+    QSTAMP(4);
+    if (stamps) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); QSTAMP(5); }
+#undef QSTAMP
+#undef QBARRIER
+}
+
+template <int SB, bool RAG, bool FROM_SLABS = false, int KCT = 4, bool FOLD = false, bool S0L = false, bool WT = false, bool QMW = false, bool QUAD = false>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(FROM_SLABS ? 4 : 2))) void k_gsm_cov_sym(int D, int B, double invB, const double* __restrict__ rec, int ldrec,
                                                      const double* __restrict__ mu0,
                                                      const double* __restrict__ S0, int lds0,
@@ -672,6 +938,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(FROM_SLABS 
                                                      unsigned long long* __restrict__ stamps, gsm_slab_src fs) {
     static_assert(!FOLD || FROM_SLABS, "folded diagonal tiles: the two-launch form only");
     static_assert(!(S0L || WT || QMW) || (FROM_SLABS && KCT == 2 && !RAG), "S0 last / write-through stores / whole-sample Qm: the two-slab two-launch form only, on the grid");
+    static_assert(!QUAD || (FROM_SLABS && !FOLD && !QMW && !RAG && (SB == 16 || SB == 32)), "quads: the two-launch form, in place of the fold");
     // barriers between staging and the W step: LDS-only where S0 is in flight across them
 #define PRE_W_BARRIER()                                                                   \
     do {                                                                                  \
@@ -694,7 +961,8 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(FROM_SLABS 
     constexpr int NU = SB * 16;                  // 16-B units per tile over all samples
     constexpr int UPT = (6 * NU) / 512;          // units per thread over the six tiles
     static_assert((6 * NU) % 512 == 0, "tile units must divide over 512 threads");
-    __shared__ __attribute__((aligned(16))) double smem[6 * TILE >= 2 * 32 * 33 ? 6 * TILE : 2 * 32 * 33];
+    constexpr int QLDS = QUAD ? COV_QUAD_LDS<SB> : 0;   // (a quad's LDS: more than the six tiles at SB = 16)
+    __shared__ __attribute__((aligned(16))) double smem[6 * TILE >= 2 * 32 * 33 ? (6 * TILE >= QLDS ? 6 * TILE : QLDS) : 2 * 32 * 33];
     // staged tiles, in this order: DI, EI, DJ0, EJ0, DJ1, EJ1
 
     // ---- which tiles: row block ti, column blocks tj0, tj0+1 ------------------------------------
@@ -707,7 +975,22 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(FROM_SLABS 
     int ti, tj0;
     bool two;
     int fold = 0;                                                // FOLD: 1 = hosts the diagonal tile of its own row, 2 = that of the last row
-    if (FOLD || (int)blockIdx.x < n_two) {
+    if constexpr (QUAD) {                                        // quads first (gsm_cov_quad above), then the pairs right of them
+        if ((int)blockIdx.x < (nt >> 1)) {
+            gsm_cov_quad<SB, KCT, S0L, WT>(smem, blockIdx.x, D, B, invB, mu0, S0, lds0, S, lds, mu_out, stamps, fs);
+            return;
+        }
+        int rem = blockIdx.x - (nt >> 1);
+        ti = 0;
+        for (;;) {
+            const int inrow = (nt >> 1) - (ti >> 1) - 1;
+            if (rem < inrow) break;
+            rem -= inrow;
+            ++ti;
+        }
+        tj0 = 2 * ((ti >> 1) + 1) + 2 * rem;
+        two = true;
+    } else if (FOLD || (int)blockIdx.x < n_two) {
         int rem = blockIdx.x;
         ti = 0;
         for (;;) {
@@ -1580,6 +1863,9 @@ static int cov_sym_grid(int nt) {
 // the two-tile workgroups among them (the kernel's n_two): all of the grid when the diagonal leftovers are folded
 int gsmvi_cov_sym_pairs(int nt) { return (nt >> 1) * ((nt + 1) >> 1); }
 
+// the quad / pair map (QUAD of k_gsm_cov_sym; even nt): nt / 2 quads, then nt / 2 - i / 2 - 1 pairs in row i
+static int cov_sym_quad_grid(int nt) { return (nt >> 1) * (nt >> 1); }
+
 bool gsmvi_launch_gsm_cov_sym(hipStream_t st, hipEvent_t* ev, int D, int B, const double* rec, int ldrec,
                               const double* mu0, const double* S0, int lds0, double* S, int lds, double* mu_out,
                               int dbg, unsigned long long* stamps, int num_cu) {
@@ -1637,9 +1923,21 @@ bool gsmvi_launch_gsm_cov_sym(hipStream_t st, hipEvent_t* ev, int D, int B, cons
 // fold (round 9): the grid is the two-tile workgroups alone, the diagonal leftovers are third tiles of their hosts (FOLD above).
 void gsmvi_launch_gsm_cov_sym_slabs(hipStream_t st, hipEvent_t* ev, int D, int B, const gsm_slab_src& fs, const double* mu0,
                                     const double* S0, int lds0, double* S, int lds, double* mu_out, int kct, bool fold,
-                                    bool s0_last, bool store_wt, bool qm_whole, unsigned long long* stamps) {
-    const dim3 grid(fold ? gsmvi_cov_sym_pairs(D / 32) : cov_sym_grid(D / 32));
+                                    bool s0_last, bool store_wt, bool qm_whole, bool quad, unsigned long long* stamps) {
     const double invB = 1.0 / (double)B;
+    // quad (round 13; the caller passes it for the shipped two-slab form -- S0 last, write-through stores, per-strip Qm -- and for
+    // the plain kct = 4 form only): the quad / pair map, (nt / 2)^2 workgroups
+    if (quad) {
+        const dim3 qgrid(cov_sym_quad_grid(D / 32));
+#define CSD(SBV, KV, LV, WV)                                                                                              \
+    GSMVI_LAUNCH((k_gsm_cov_sym<SBV, false, true, KV, false, LV, WV, false, true>), qgrid, dim3(512), 0, st, ev, D, B, invB, nullptr, 0, mu0, \
+                 S0, lds0, S, lds, mu_out, 0, stamps, fs)
+        if (kct == 2) { if (B == 16) CSD(16, 2, true, true); else CSD(32, 2, true, true); }
+        else { if (B == 16) CSD(16, 4, false, false); else CSD(32, 4, false, false); }
+#undef CSD
+        return;
+    }
+    const dim3 grid(fold ? gsmvi_cov_sym_pairs(D / 32) : cov_sym_grid(D / 32));
 #define CSQ(SBV, KV, FV, LV, WV, QV)                                                                                      \
     GSMVI_LAUNCH((k_gsm_cov_sym<SBV, false, true, KV, FV, LV, WV, QV>), grid, dim3(512), 0, st, ev, D, B, invB, nullptr, 0, mu0, S0, lds0, S, \
                  lds, mu_out, 0, stamps, fs)

@@ -116,6 +116,10 @@ int gsmvi_destroy(gsmvi_ctx* ctx);
  * G that it multiplies, in two stages along K, and starts a stage's MFMAs behind that stage's loads alone, with no workgroup
  * barrier in front of the first MFMA; 4 = in four stages, 2 = as 1, for A/B runs; 0 = one load batch staged by the whole workgroup behind a
  * barrier; bit-identical results, no path bit: the timeline diagnostic's stamp words 4 - 7 of the product tell them apart);
+ * round 13: "cov_diag_quad" (the covariance launch where the fold runs: no hosts -- D / 64 workgroups own the diagonal 64 x 64
+ * blocks, three tiles on two staged column blocks, every other tile rides in a pair; 1 = where the fold runs by default on the
+ * two-slab form with "cov_s0_last" and "cov_store_wt" on and "panel_qm_whole" off, default; 0 = the fold as it was; 2 = wherever
+ * "cov_fold_diag" is not 0, for tests; bit-identical results, reported under GSMVI_PATH_COV_FOLD_DIAG);
  * diagnostics "timeline", "cov_dbg"
  * (see gsmvi_hip_debug.h). */
 int gsmvi_set_tuning(gsmvi_ctx* ctx, const char* name, int value);

@@ -75,7 +75,24 @@ if (a[live][:, 6] > 0).all():    # "cov_s0_last": [1] = staged units landed (S0 
 print("blocks >= 256 (single-tile): end median", np.median(end[256:]) if len(end) > 256 else None, " blocks < 256: end median", np.median(end[:256]), "p95", np.percentile(end[:256], 95))
 # ---- the hosts of the folded diagonal tiles against the other workgroups (folded grid: the two-tile workgroups alone) ----
 nt = D // 32
-if len(end) == (nt >> 1) * ((nt + 1) >> 1):
+# ---- the quads against the pairs (round 13, "cov_diag_quad": the same grid size as the fold at D = 1024, so the knobs decide) ----
+import re as _re
+_ctx_h = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "gsm-vi_amd", "csrc", "gsmvi_ctx.h")).read()
+_knob = {k: int(_re.search(rf"int\s+tune_{k}\s*=\s*(\d+)\s*;", _ctx_h).group(1))
+         for k in ("cov_diag_quad", "cov_fold_diag", "cov_s0_last", "cov_store_wt", "panel_qm_whole", "panel_kc")}
+_knob.update({kv.split("=")[0]: int(kv.split("=")[1]) for kv in sys.argv[2:]})
+quad_on = (_knob["cov_diag_quad"] != 0 and _knob["cov_fold_diag"] != 0 and _knob["cov_s0_last"] != 0 and _knob["cov_store_wt"] != 0
+           and _knob["panel_qm_whole"] == 0 and _knob["panel_kc"] <= 0 and len(end) == (nt >> 1) ** 2)
+if quad_on:
+    quad = np.arange(len(end)) < (nt >> 1)
+    for nm, sel in (("quads", quad), ("pairs", ~quad)):
+        e, p = end[sel], ph[sel]
+        print(f"{nm:6s} {sel.sum():3d} WGs: end min/median/max {e.min():.2f}/{np.median(e):.2f}/{e.max():.2f}  staged->MFMA done "
+              f"{p[:, 2].min():.2f}/{np.median(p[:, 2]):.2f}/{p[:, 2].max():.2f}  MFMA done->last store issued "
+              f"{p[:, 3].min():.2f}/{np.median(p[:, 3]):.2f}/{p[:, 3].max():.2f}  drain {np.median(p[:, 4]):.2f}")
+    print(f"quads' last end - pairs' median end: {end[quad].max() - np.median(end[~quad]):.2f} us;  quads' last end - pairs' last end: "
+          f"{end[quad].max() - end[~quad].max():.2f} us;  launch span {end.max() - us[:, 0].min():.2f} us")
+elif len(end) == (nt >> 1) * ((nt + 1) >> 1):
     host = []
     for ti in range(nt):
         for rem in range((nt - ti) >> 1):
@@ -86,7 +103,8 @@ if len(end) == (nt >> 1) * ((nt + 1) >> 1):
         print(f"{nm:6s} {sel.sum():3d} WGs: end min/median/max {e.min():.2f}/{np.median(e):.2f}/{e.max():.2f}  staged->MFMA done "
               f"{p[:, 2].min():.2f}/{np.median(p[:, 2]):.2f}/{p[:, 2].max():.2f}  MFMA done->last store issued "
               f"{p[:, 3].min():.2f}/{np.median(p[:, 3]):.2f}/{p[:, 3].max():.2f}  drain {np.median(p[:, 4]):.2f}")
-    print(f"hosts' last end - others' median end: {end[host].max() - np.median(end[~host]):.2f} us;  launch span {end.max() - us[:, 0].min():.2f} us")
+    print(f"hosts' last end - others' median end: {end[host].max() - np.median(end[~host]):.2f} us;  hosts' last end - others' last end: "
+          f"{end[host].max() - end[~host].max():.2f} us;  launch span {end.max() - us[:, 0].min():.2f} us")
 a = st[0]; live = a[:, 0] > 0; usp = (a[live] - t0) / 100.0
 php = np.diff(usp[:, :4], axis=1)
 print("panel phase medians (staged, mfma, end):", np.round(np.median(php, axis=0), 2), " p95:", np.round(np.percentile(php, 95, axis=0), 2))
