@@ -9,6 +9,8 @@ enum { LB_G = 1, LB_LP = 2 };
 enum { LB_LOGISTIC = GSMVI_GLM_LOGISTIC, LB_POISSON = GSMVI_GLM_POISSON, LB_PROBIT = GSMVI_GLM_PROBIT,
        LB_GAUSSIAN = GSMVI_GLM_GAUSSIAN };
 #define LB_TN 32   // rows of A_k per tile
+#define LB_PROBIT_S0 4.0   // lb_weight<LB_PROBIT>: the tail side is the continued fraction from |eta| = 4 on
+#define LB_PROBIT_CF 40    // ... at this depth
 
 // The link of family FAM at eta = h, label y (tau: the gaussian noise precision): r = d t / d eta and t, each evaluated only
 // when wanted.  Returns false when the row of X must be flagged (poisson: e^eta is not finite); what r and t then hold reaches
@@ -32,7 +34,13 @@ __device__ __forceinline__ bool lb_link(double h, double y, double tau, double& 
         const double rt = 0.79788456080286535588 / u, rc = e * 0.39894228040143267794 / (1.0 - q);
         double lt = 0.0, lc = 0.0;
         if (HAS_LP) {
-            lt = log(0.5 * u) - hs;
+            // From |eta| = 1.34e154 on s^2 overflows; held at the largest finite number, a tail label of weight exactly 0 gives
+            // the -0 it gives at every other eta, not the NaN of 0 * inf.  (A maximum and not a select on y: the 256-thread
+            // density kernel of k_logistic_batched has no register to spare.  A NaN eta still reaches t through lc.)  The
+            // consequence for a tail label of weight > 0 there: t is (1 - y) times -1.8e308, finite, where log Phi(-s) itself
+            // is below the float64 range from 1.9e154 on and the earlier form gave -inf.  Nothing may take lp = -inf as the
+            // sign of such an eta.
+            lt = fmax(log(0.5 * u) - hs, -1.7976931348623157e308);
             lc = log1p(-q);
         }
         if (h >= 0.0) {                                    // Phi(eta) is the central side
@@ -55,9 +63,17 @@ __device__ __forceinline__ bool lb_link(double h, double y, double tau, double& 
 // families are log-concave, so w >= 0 up to rounding.  Returns false when the row must be flagged (poisson: e^eta not finite).
 //   logistic  sigma (1 - sigma) = e / (1 + e)^2, e = exp(-|eta|)
 //   poisson   e^eta
-//   probit    y hp (hp + eta) + (1 - y) hm (hm - eta) with hp = phi / Phi(eta), hm = phi / Phi(-eta): the two values lb_link forms
-//             from erfcx.  On the tail side (hp at eta < 0, hm at eta > 0) h -+ eta cancels: h ~ |eta| + 1 / |eta|, so the factor
-//             is ~ 1 / |eta| from two terms of size |eta| and the relative error of w grows like eps eta^2 (1e-14 at |eta| = 8).
+//   probit    y wp + (1 - y) wm with wp = hp (hp + eta), wm = hm (hm - eta), hp = phi / Phi(eta), hm = phi / Phi(-eta): the two
+//             values lb_link forms from erfcx.  With s = |eta| one of the two is the central side, h (h + s), a sum of positive
+//             terms; the other is the tail side (wp at eta < 0, wm at eta > 0), h (h - s) with h ~ s + 1 / s: the subtraction
+//             cancels, and what is left has the relative error of erfcx times about s^2 (by 1e8 it was the whole value).  So
+//             from s = LB_PROBIT_S0 on the tail side comes without a subtraction, from Laplace's continued fraction of the
+//             Mills ratio, h = s + K, K = 1 / (s + 2 / (s + 3 / (s + ..))): with z = 1 / s^2 and g = s K = 1 / (1 + 2 z / (1 + 3 z /
+//             (1 + ..))), h (h - s) = g (1 + z g).  g is the convergent of depth LB_PROBIT_CF as ONE ratio of its forward
+//             recurrence (all terms positive, z <= 1 / 16: no overflow, one division); its truncation error at s = 4 is 0.05 eps
+//             and falls with s.  Below S0 the subtraction stays, with erfcx's error times at most 17 ("The
+//             links element by element", has the measured figures).  Both sides are finite for every finite eta and
+//             0 <= w <= 1, so a label weight of exactly 0 never meets an infinity.
 //   gaussian  tau
 template <int FAM>
 __device__ __forceinline__ bool lb_weight(double h, double y, double tau, double& w) {
@@ -71,8 +87,24 @@ __device__ __forceinline__ bool lb_weight(double h, double y, double tau, double
     } else if constexpr (FAM == LB_PROBIT) {
         const double s = fabs(h), u = erfcx(s * 0.70710678118654752440), hs = 0.5 * (s * s), e = exp(-hs), q = 0.5 * (u * e);
         const double rt = 0.79788456080286535588 / u, rc = e * 0.39894228040143267794 / (1.0 - q);
-        const double hp = h >= 0.0 ? rc : rt, hm = h >= 0.0 ? rt : rc;
-        w = y * (hp * (hp + h)) + (1.0 - y) * (hm * (hm - h));
+        const double wc = rc * (rc + s);                   // the central side
+        double wt;                                         // the tail side
+        if (s >= LB_PROBIT_S0) {
+            const double x = 1.0 / s, z = x * x;
+            double a0 = 0.0, a1 = 1.0, b0 = 1.0, b1 = 1.0;  // numerator and denominator of the convergents of g
+#pragma unroll
+            for (int k = 2; k <= LB_PROBIT_CF; ++k) {
+                const double c = k * z, a2 = fma(c, a0, a1), b2 = fma(c, b0, b1);
+                a0 = a1;
+                a1 = a2;
+                b0 = b1;
+                b1 = b2;
+            }
+            const double g = a1 / b1;
+            wt = g * fma(z, g, 1.0);
+        } else
+            wt = rt * (rt - s);
+        w = h >= 0.0 ? y * wc + (1.0 - y) * wt : y * wt + (1.0 - y) * wc;
         return true;
     } else {
         w = tau;

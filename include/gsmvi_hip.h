@@ -675,7 +675,9 @@ int gsmvi_pathfinder_select_batched_f64(gsmvi_ctx* ctx, void* stream, int64_t K,
  * derivative is closed-form, the four families of gsmvi_glm_batched_f64.  With eta_n = a_n . x + o_kn and the weight
  *   w = -dr / d eta:   logistic  sigma (1 - sigma) = e / (1 + e)^2, e = exp(-|eta|)      poisson  e^eta      gaussian  tau_k
  *                      probit    y hp (hp + eta) + (1 - y) hm (hm - eta), hp = phi / Phi(eta), hm = phi / Phi(-eta)
- * (probit: the tail side cancels, hp + eta at eta < 0 and hm - eta at eta > 0, so the relative error of w grows like eps eta^2),
+ * (probit: the tail side, hp + eta at eta < 0 and hm - eta at eta > 0, cancels: formed by subtraction its relative error grows
+ * like eps eta^2 until it is the whole value, so from |eta| = 4 on it is g (1 + g / eta^2), g = 1 / (1 + 2 / eta^2 / (1 + 3 / eta^2 / ..))
+ * from the continued fraction of the Mills ratio, without a subtraction; 0 <= w <= 1 for every finite eta),
  *   H_k(x) = sum_{n < n_k} w(eta_n, y_n) a_n a_n^T + lam_k I         the negative Hessian of lp_k at x, positive semi-definite.
  * The argument meanings, bounds and grid limits of gsmvi_glm_batched_f64 hold for both entry points (1 <= D <= 64, any N >= 1,
  * counts_dev clamped in the kernel and rows n >= n_k never loaded, noise_prec the gaussian family's alone).  The Gram product runs

@@ -34,7 +34,8 @@ def link(family, eta, y, tau=1.0):
         e = np.exp(-hs)
         q = 0.5 * (u * e)
         rt, rc = 0.79788456080286535588 / u, e * 0.39894228040143267794 / (1.0 - q)
-        lt, lc = np.log(0.5 * u) - hs, np.log1p(-q)
+        # (lt held at the largest finite number: from |eta| = 1.34e154 on s^2 overflows, and 0 * inf would be a NaN)
+        lt, lc = np.fmax(np.log(0.5 * u) - hs, -1.7976931348623157e308), np.log1p(-q)
         pos = eta >= 0.0
         r = np.where(pos, y * rc - (1.0 - y) * rt, y * rt - (1.0 - y) * rc)
         t = np.where(pos, y * lc + (1.0 - y) * lt, y * lt + (1.0 - y) * lc)

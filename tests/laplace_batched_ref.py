@@ -21,6 +21,7 @@ FAMILIES = gref.FAMILIES
 SHAPES = ((5, 40, 3), (6, 70, 10), (5, 33, 16), (5, 65, 17), (5, 70, 33), (4, 150, 64))
 STEP_GTOL = 1e-6
 PIVOT_REL = 64 * 2.220446049250313e-16
+PROBIT_S0, PROBIT_CF = 4.0, 40             # LB_PROBIT_S0, LB_PROBIT_CF of csrc/gsmvi_glm_link.h
 # make_inputs seeds of the step test's trajectories where the default one (N + D) puts a decision on its threshold
 # (tests/test_laplace_batched_cpu.py asserts the margins for every entry, default or not): (family, (K, N, D)) -> seed
 SEEDS = {("logistic", (5, 40, 3)): 1, ("logistic", (6, 70, 10)): 1, ("logistic", (5, 33, 16)): 13, ("logistic", (5, 65, 17)): 1,
@@ -46,9 +47,17 @@ def weights(family, eta, y, tau=1.0):
         e = np.exp(-hs)
         q = 0.5 * (u * e)
         rt, rc = 0.79788456080286535588 / u, e * 0.39894228040143267794 / (1.0 - q)
-        pos = eta >= 0.0
-        hp, hm = np.where(pos, rc, rt), np.where(pos, rt, rc)
-        return y * (hp * (hp + eta)) + (1.0 - y) * (hm * (hm - eta)), none
+        # the central side h (h + s), and the tail side h (h - s): from s = PROBIT_S0 on g (1 + z g) with z = 1 / s^2 and
+        # g = 1 / (1 + 2 z / (1 + 3 z / ..)) (Laplace's continued fraction of the Mills ratio) as one ratio of its forward recurrence
+        wc = rc * (rc + s)
+        z = 1.0 / np.maximum(s, PROBIT_S0)
+        z = z * z
+        a0, a1, b0, b1 = 0.0, 1.0, 1.0, 1.0
+        for k in range(2, PROBIT_CF + 1):
+            a0, a1, b0, b1 = a1, a1 + (k * z) * a0, b1, b1 + (k * z) * b0
+        g = a1 / b1
+        wt = np.where(s >= PROBIT_S0, g * (1.0 + z * g), rt * (rt - s))
+        return np.where(eta >= 0.0, y * wc + (1.0 - y) * wt, y * wt + (1.0 - y) * wc), none
     if family == "gaussian":
         return np.broadcast_to(np.asarray(tau, dtype=np.float64), np.shape(eta)).copy(), none
     raise ValueError(family)

@@ -40,8 +40,8 @@ def _lp_torch(family, A, y, o, lam, tau):
 @pytest.mark.parametrize("family", ref.FAMILIES)
 @pytest.mark.parametrize("K,N,D", [(3, 1, 1), (4, 33, 17), (3, 70, 10)])
 def test_restated_hessian_is_autograd_of_the_written_density(family, K, N, D):
-    """offsets, counts, per-problem lam and tau; X scaled so that |eta| <= 8, where the probit weight's tail cancellation
-    (relative error ~ eps eta^2) stays far below the bar of 1e-10 of max|H|"""
+    """offsets, counts, per-problem lam and tau; X scaled so that |eta| <= 8, where float64 autograd of log_ndtr is itself
+    good to the bar of 1e-10 of max|H| (the weights at any eta are held to mpmath in tests/test_glm_link_truth_cpu.py)"""
     A, y, o, counts, lam, tau, X = gref.make_inputs(family, K, N, D, 1)
     X = X[:, 0, :]
     for k in range(K):                                                  # hold |eta| to 8
