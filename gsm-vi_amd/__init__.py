@@ -30,6 +30,9 @@ Mirrors the reference's public surface for the hot path (reference file:line):
     BatchedSoftmaxTarget (K multinomial logit
     regressions of C classes, (C - 1) P <= 64:
     log-density and score in one launch)         examples/example_gsm.py:34-35 (log_prob, jit(grad(.)))
+    BatchedNegBinomialTarget (K negative binomial
+    regressions with a fitted log size, P + 1 <= 64:
+    log-density and score in one launch)         examples/example_gsm.py:34-35 (log_prob, jit(grad(.)))
     BatchedGLMTarget.predict, GLMPrediction (the
     posterior predictive of K fitted GLMs on new
     rows: mean, variance of the linear predictor,
@@ -80,6 +83,7 @@ from .targets import BatchedGaussianTarget, BatchedLogisticTarget    # noqa: F40
 from .targets import BatchedGLMTarget, GLMPrediction                 # noqa: F401
 from .targets import BatchedSoftmaxTarget                            # noqa: F401
 from .targets import SharedDesignGLMTarget                           # noqa: F401
+from .targets import BatchedNegBinomialTarget                        # noqa: F401
 from .targets import predict_softmax_batched, SoftmaxPrediction      # noqa: F401
 from .batched import GSMBatch, gsm_update_batched                    # noqa: F401
 from .batched import BaMBatch, bam_update_batched, bam_lowrank_update_batched   # noqa: F401

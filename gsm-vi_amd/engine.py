@@ -899,6 +899,29 @@ class HipEngine:
                    self._packed(X, (K, nc, D), "X"), self._dp(G, (K, nc, D), "out"), self._dp(lp, (K, nc), "lp_out"))
         return ret
 
+    # ---- batched negative binomial target: K count regressions with a fitted size (csrc/gsmvi_negbin_batched.hip) -------------
+    def negbin_batched(self, X, A, y, offset=None, counts=None, prior_prec=1.0, log_size_mean=0.0, log_size_prec=1.0, out=None,
+                       lp_out=None, want="g"):
+        """Score and / or log-density of K negative binomial regressions at the rows of X (K, nc, P + 1) = (beta, theta), theta =
+        log of the size, one launch [examples/example_gsm.py:34-35 for this model]: A (K, N, P), y (K, N) >= 0, ``offset`` None or
+        (K, N) added to A beta, ``counts`` None or K device int32 valid rows; ``prior_prec`` (of beta), ``log_size_mean`` and
+        ``log_size_prec`` (the prior N(mean, 1 / prec) of theta) each a number or a (K,) device tensor.  ``want`` = "g" -> G
+        (K, nc, P + 1), "lp" -> the values (K, nc), "both" -> (G, lp)."""
+        N, P = A.shape[1], A.shape[2]
+        if X.shape[2] != P + 1:
+            raise ValueError(f"X: expected P + 1 = {P + 1} columns (beta, then the log size), got {X.shape[2]}")
+        G, lp, ret = self._want_g_lp(want, X, out, lp_out)
+        X = X.contiguous()
+        K, nc, D = X.shape
+        self._any_ctx()
+        r, rp = self._reg_arg(prior_prec, K)
+        m, mp = self._reg_arg(log_size_mean, K)
+        s, sp = self._reg_arg(log_size_prec, K)
+        self._call("gsmvi_negbin_batched_f64", K, P, nc, N, self._packed(A, (K, N, P), "A"), self._packed(y, (K, N), "y"),
+                   self._dp(offset, (K, N), "offset"), self._ints(counts, K, "counts"), m, mp, s, sp, r, rp,
+                   self._packed(X, (K, nc, D), "X"), self._dp(G, (K, nc, D), "out"), self._dp(lp, (K, nc), "lp_out"))
+        return ret
+
     # ---- shared-design GLM target: K problems on one design matrix (csrc/gsmvi_glm_shared_batched.hip) -----------------------
     def glm_shared_batched(self, X, A, y, family, offset=None, weights=None, prior_prec=1.0, noise_prec=1.0, out=None,
                            lp_out=None, want="g"):

@@ -17,6 +17,8 @@ multinomial logit regressions (C classes, C - 1 linear predictors per row), a la
     BatchedGLMTarget          poisson, probit, gaussian, ...  gsmvi_glm_batched_f64              yes
     SharedDesignGLMTarget     the same four, ONE A (N, D),    gsmvi_glm_shared_batched_f64       no (not a BatchedGLMTarget: the
                               observation weights                                                isinstance checks refuse it)
+    BatchedNegBinomialTarget  counts y >= 0, a fitted size    gsmvi_negbin_batched_f64           no (not a BatchedGLMTarget: the Hessian
+                              (x = (beta, log r))                                                has a 2 x 2 block per row)
     BatchedSoftmaxTarget      integer labels in 0 .. C - 1    gsmvi_softmax_batched_f64          laplace_init_softmax_batched and
                                                                                                  neg_hessian; predict, loo: no (TypeError):
                                                                                                  predict_softmax_batched,
@@ -474,6 +476,92 @@ class SharedDesignGLMTarget:
     def _call(self, x, **kw):
         return self.engine.glm_shared_batched(x, self.A, self.y, self.family, offset=self.offset, weights=self.weights,
                                               prior_prec=self.prior_precision, noise_prec=self.noise_precision, **kw)
+
+    def lp(self, x):
+        """(K, rows) values lp_k(x_kr) at the rows of x (K, rows, D), a device tensor or numpy; one launch"""
+        return self._call(self.engine.asarray(x), want="lp")
+
+    def lp_and_score(self, x):
+        """(scores (K, rows, D), values (K, rows)) from one launch"""
+        return self._call(self.engine.asarray(x), want="both")
+
+
+def _check_finite_per_problem(x, name, K):
+    """``x``, a number or K values, as a host float64 array: finite (any sign), else ValueError"""
+    v = np.asarray(_host_array(x), dtype=np.float64)
+    if v.shape not in ((), (K,)):
+        raise ValueError(f"{name}: expected a number or {K} values, got shape {v.shape}")
+    if not np.isfinite(v).all():
+        raise ValueError(f"{name}: expected finite values")
+    return v
+
+
+class BatchedNegBinomialTarget:
+    """K Bayesian negative binomial regressions with their own data sets -- overdispersed counts, the dispersion fitted -- for
+    ``GSMBatch``, ``BaMBatch``, ``ADVIBatch``, ``BatchedKLMonitor``, ``lbfgs_init_batched``, ``pathfinder_init_batched`` and
+    ``psis_batched``.  Problem k has the design matrix A[k] (N, P), responses y[k] (N,) >= 0 (finite; they need not be integers),
+    an optional ``offset[k]`` (N,) added to the linear predictor (a log exposure, say) and ``counts[k]`` <= N valid rows (None: all
+    N; the rows beyond are ignored whatever they hold).  The parameter is x = (beta, theta) in R^D, D = P + 1 <= 64: theta = log r
+    is the log of the size, the variance of an observation is mu + mu^2 / r, and r -> inf is the Poisson model.  With eta = A[k]
+    beta + offset[k], d = eta - theta and r = exp(theta):
+
+        t_n          = lgamma(y_n + r) - lgamma(r) - r softplus(d_n) - y_n softplus(-d_n)
+        lp_k(x)      = sum_n t_n - lam_k |beta|^2 / 2 - kap_k (theta - m_k)^2 / 2            (unnormalised: -lgamma(y + 1) dropped)
+        grad lp_k(x) = ( sum_n [y_n sigmoid(-d_n) - r sigmoid(d_n)] a_n - lam_k beta,
+                         sum_n [r (psi(y_n + r) - psi(r) - softplus(d_n)) - (y_n sigmoid(-d_n) - r sigmoid(d_n))] - kap_k (theta - m_k) )
+
+    evaluated by gsmvi_negbin_batched_f64: what examples/example_gsm.py:34-35 gets from a model's log_prob and jit(grad(...)).
+    The priors: beta ~ N(0, I / lam_k), ``prior_precision`` = lam; theta ~ N(m_k, 1 / kap_k), ``log_size_mean`` = m and
+    ``log_size_precision`` = kap; each a float or K values, a precision of 0 = flat.  The two differences of lgamma and of psi
+    are evaluated as differences (never as two calls), and exp(eta) is never formed: the outputs are finite wherever the truth
+    is.  A point whose exp(theta) is not a positive normal number (|theta| above 708) gets NaN outputs (the fits then revert that
+    step).  numpy arrays or tensors in; everything is kept on the device as float64 / int32.  Arguments are validated on the host
+    before any device work (ValueError naming the argument and the problems).
+
+    ``lp_g(x, out=None)``: (K, B, D) -> (K, B, D) scores, ``device_native`` and ``graph_safe`` (one capturable launch, no
+    allocation with ``out``).  ``lp(x)``: (K, rows, D) -> (K, rows) values; a device tensor or numpy.  ``lp_and_score(x)``:
+    (scores, values) from one launch.  Attributes ``K, N, P, D``.  Not a ``BatchedGLMTarget``: its Hessian is not A^T W A (every
+    row contributes a 2 x 2 block in (eta, theta)), so it has no ``neg_hessian``, ``predict`` or ``loo``, and
+    ``laplace_init_batched`` and ``psis_loo_batched`` refuse it (TypeError)."""
+
+    def __init__(self, A, y, prior_precision=1.0, counts=None, offset=None, log_size_mean=0.0, log_size_precision=1.0,
+                 engine=None):
+        sa = _shape(A)
+        if len(sa) != 3 or min(sa) < 1:
+            raise ValueError(f"A: expected shape (K, N, P) with K, N, P >= 1, got {sa}")
+        K, N, P = sa
+        if P + 1 > 64:
+            raise ValueError(f"A: D = P + 1 = {P + 1} is outside 2 <= D <= 64 (beta and the log size)")
+        if _shape(y) != (K, N):
+            raise ValueError(f"y: expected shape (K, N) = {(K, N)}, got {_shape(y)}")
+        cnt = _check_counts(counts, K, N)
+        live = _live_rows(cnt, N)
+        yh = _check_responses(y, "poisson", live, name_family=False)      # the count range: finite and >= 0
+        oh = _check_offset(offset, K, N, live)
+        lam = _check_per_problem(prior_precision, "prior_precision", K)
+        tm = _check_finite_per_problem(log_size_mean, "log_size_mean", K)
+        tk = _check_per_problem(log_size_precision, "log_size_precision", K)
+        self.engine = engine if engine is not None else get_engine()
+        eng = self.engine
+        self.K, self.N, self.P, self.D = K, N, P, P + 1
+        self.A = eng.asarray(A.contiguous() if isinstance(A, torch.Tensor) else A)
+        self.y = eng.asarray(yh)
+        self.offset = eng.asarray(oh) if oh is not None else None
+        self.counts = eng.batched_counts(cnt) if cnt is not None else None
+        self.prior_precision = float(lam) if lam.shape == () else eng.batched_regs(lam)
+        self.log_size_mean = float(tm) if tm.shape == () else eng.batched_regs(tm)
+        self.log_size_precision = float(tk) if tk.shape == () else eng.batched_regs(tk)
+
+        def lp_g(x, out=None):
+            return self._call(x, out=out, want="g")
+        lp_g.device_native = True
+        lp_g.graph_safe = True          # one capturable kernel launch, no allocation when `out` is given, no host work
+        self.lp_g = lp_g
+
+    def _call(self, x, **kw):
+        return self.engine.negbin_batched(x, self.A, self.y, offset=self.offset, counts=self.counts,
+                                          prior_prec=self.prior_precision, log_size_mean=self.log_size_mean,
+                                          log_size_prec=self.log_size_precision, **kw)
 
     def lp(self, x):
         """(K, rows) values lp_k(x_kr) at the rows of x (K, rows, D), a device tensor or numpy; one launch"""

@@ -568,6 +568,37 @@ int gsmvi_glm_shared_batched_f64(gsmvi_ctx* ctx, void* stream, int64_t K, int D,
                                  double* G, double* lp);
 
 /*
+ * Batched negative binomial target: the log-density and the score of K overdispersed count regressions of one (N, P) at nc points
+ * each, one launch.  examples/example_gsm.py:34-35, a model's log_prob and lp_g = jit(grad(...)) of it, for counts whose variance
+ * exceeds their mean -> gsmvi_negbin_batched_f64.  Problem k has the design matrix A_k (N rows a_n of P columns), responses
+ * y_kn >= 0 (finite; they need not be integers), an optional offset o_kn (NULL = none), n_k valid rows, and the parameter
+ * x = (beta, theta) of length D = P + 1: theta = log r is the log of the size (variance mu + mu^2 / r; r -> inf is Poisson).  With
+ * eta_n = a_n . beta + o_n, d_n = eta_n - theta, r = e^theta, dlg(y, r) = lgamma(y + r) - lgamma(r), dps(y, r) = psi(y + r) - psi(r):
+ *   t       = dlg(y, r) - r softplus(d) - y softplus(-d)        (log NB(y | mu = e^eta, r) without -lgamma(y + 1))
+ *   r_eta   = y sigma(-d) - r sigma(d)                          (= dt / d eta)
+ *   r_theta = r (dps(y, r) - softplus(d)) - r_eta               (= dt / d theta)
+ *   lp[k, c]      = sum_{n < n_k} t_n - lam_k |beta|^2 / 2 - kap_k (theta - m_k)^2 / 2
+ *   G[k, c, :P]   = sum_{n < n_k} r_eta,n a_n - lam_k beta
+ *   G[k, c, P]    = sum_{n < n_k} r_theta,n - kap_k (theta - m_k)
+ * The two differences are evaluated as differences of Stirling's series (after ten steps of the recurrence for r < 10), never as
+ * two calls: accurate to a few eps of the terms of t, r_eta and r_theta as written.  e^eta is never formed, so there is no overflow
+ * rule as for the Poisson family: the outputs are finite wherever the truth is.  A (K x N x P), y, offset (K x N), X, G
+ * (K x nc x (P + 1)), lp (K x nc), packed, in device memory; 1 <= P <= 63; K, nc, N, counts_dev and prior_prec / prior_prec_dev
+ * (lam, the prior N(0, I / lam_k) of beta) as in gsmvi_glm_batched_f64; theta_mean / theta_mean_dev (m, finite) and theta_prec /
+ * theta_prec_dev (kap, finite and >= 0; 0 = flat) in the same scalar-or-K-values style: the prior N(m_k, 1 / kap_k) of theta.
+ * At least one of G, lp is given.  Every output row sums over n in the order 0 .. n_k - 1 in one thread (r_theta into the last
+ * component) and depends on its problem and its own row of X only: the same bits for any K, nc and neighbours; no atomics.  Rows
+ * n >= n_k are never loaded; n_k = 0 leaves the two priors.  A row of X with a non-finite entry, or whose e^theta is not a positive
+ * normal number (|theta| above 708), gets NaN outputs and no other row is touched.  Shapes, priors, NULL arrays and overlaps (G and
+ * lp are the written arrays) are checked before the context is looked at (then a NULL ctx); every failure returns
+ * GSMVI_ERR_BAD_ARG before anything is enqueued.  Inputs are only read; no context workspace.  Sets GSMVI_PATH_BATCHED_TARGET.
+ */
+int gsmvi_negbin_batched_f64(gsmvi_ctx* ctx, void* stream, int64_t K, int P, int nc, int64_t N, const double* A, const double* y,
+                             const double* offset, const int* counts_dev, double theta_mean, const double* theta_mean_dev,
+                             double theta_prec, const double* theta_prec_dev, double prior_prec, const double* prior_prec_dev,
+                             const double* X, double* G, double* lp);
+
+/*
  * Batched softmax target: the log-density and the score of K Bayesian multinomial logit regressions of one (N, C, P) at nc points
  * each, one launch.  examples/example_gsm.py:34-35, the model's log_prob and lp_g = jit(grad(...)) of it, for a response with C
  * classes -> gsmvi_softmax_batched_f64.  Problem k has the design matrix A_k (N rows a_n of P features), integer labels y_kn in
