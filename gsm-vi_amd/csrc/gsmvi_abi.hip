@@ -54,7 +54,7 @@ void gsmvi_launch_panel_fast_part(hipStream_t st, hipEvent_t* ev, dim3 grid, int
                                   unsigned long long* stamps);
 void gsmvi_launch_gsm_cov_sym_slabs(hipStream_t st, hipEvent_t* ev, int D, int B, const struct gsm_slab_src& fs, const double* mu0,
                                     const double* S0, int lds0, double* S, int lds, double* mu_out, int kct, bool fold,
-                                    bool s0_last, bool store_wt, bool qm_whole, bool quad, unsigned long long* stamps);
+                                    bool s0_last, bool store_wt, bool qm_whole, bool quad, bool wave_store, unsigned long long* stamps);
 int gsmvi_cov_sym_pairs(int nt);
 int gsmvi_panel_fast_chunk(int MT);
 int gsmvi_potrf_impl(struct gsmvi_ctx* ctx, hipStream_t st, int D, const double* S, int lds, double* R, int ldr,
@@ -331,6 +331,7 @@ int gsmvi_set_tuning(gsmvi_ctx* ctx, const char* name, int value) {
     else if (!strcmp(name, "gsm_two_launch")) ctx->tune_gsm_two_launch = value;
     else if (!strcmp(name, "cov_fold_diag")) ctx->tune_cov_fold_diag = value;
     else if (!strcmp(name, "cov_diag_quad")) ctx->tune_cov_diag_quad = value;
+    else if (!strcmp(name, "cov_wave_store")) ctx->tune_cov_wave_store = value;
     else if (!strcmp(name, "cov_s0_last")) ctx->tune_cov_s0_last = value;
     else if (!strcmp(name, "cov_store_wt")) ctx->tune_cov_store_wt = value;
     else if (!strcmp(name, "panel_qm_whole")) ctx->tune_panel_qm_whole = value;
@@ -718,11 +719,13 @@ static int gsm_two_launch(gsmvi_ctx* ctx, hipStream_t hs, int D, int B, int cpw,
     // (D = 1024: as many workgroups as CUs), 2 = wherever "cov_fold_diag" is not 0 (tests: D = 256 on the four-slab form).  Every
     // other combination keeps the fold.  No path bit of its own: the leftovers still have no workgroup of their own, which is what
     // GSMVI_PATH_COV_FOLD_DIAG says.
+    // round 14: "cov_wave_store" -- wherever the quads run, every wave of the covariance launch forms, stores and mirrors the block
+    // it computed (gsmvi_fast.hip: WST); 0 = the store path through the shared LW buffers.  Bit-identical, no path bit (none is left).
     const bool quad_form = chw == 512 ? (s0_last && store_wt && !qm_whole) : true;
     const bool quad = quad_form && ((ctx->tune_cov_diag_quad >= 2 && ctx->tune_cov_fold_diag != 0) ||
                                     (ctx->tune_cov_diag_quad == 1 && chw == 512 && ctx->tune_cov_fold_diag == 1 && fold));
     gsmvi_launch_gsm_cov_sym_slabs(hs, ctx->stage_events(2), D, B, fs, mu0, S0, lds0, S, lds, mu, chw == 512 ? 2 : 4, fold,
-                                   s0_last, store_wt, qm_whole, quad, ctx->timeline_stamps(2));
+                                   s0_last, store_wt, qm_whole, quad, quad && ctx->tune_cov_wave_store != 0, ctx->timeline_stamps(2));
     ctx->path |= GSMVI_PATH_COV_SYM | GSMVI_PATH_GSM_TWO_LAUNCH | ((fold || quad) ? GSMVI_PATH_COV_FOLD_DIAG : 0u) |
                  (s0_last ? GSMVI_PATH_COV_S0_LAST : 0u) | (store_wt ? GSMVI_PATH_COV_STORE_WT : 0u);
     return check_launch("k_gsm_cov_sym(slabs)");

@@ -121,7 +121,9 @@ struct gsmvi_ctx {
     int tune_cov_diag_quad = 1;    // two-launch form, where the fold runs: no hosts -- nt/2 workgroups own the diagonal 64 x 64 blocks (three tiles, two staged
                                    // column blocks), every other tile rides in a pair (0: the fold as it was; 1: where the fold runs by default, on the shipped
                                    // two-slab form (S0 last, write-through stores, per-strip Qm); 2: also on the plain four-slab form, for tests); bit-identical
-    int tune_cov_s0_last = 1;      // two-launch form, two slabs (D = 1024): the S0 tile of k_gsm_cov_sym<.., FROM_SLABS, 2> is loaded and waited for LAST
+    int tune_cov_wave_store = 1;   // where the quads run: every wave forms, stores and mirrors its own 16 x 16 block -- no barrier and no shared LDS behind the MFMAs
+                                   // (0: the store path through the LW buffers, three workgroup barriers; A/B runs); bit-identical results
+    int tune_cov_s0_last = 1;     // two-launch form, two slabs (D = 1024): the S0 tile of k_gsm_cov_sym<.., FROM_SLABS, 2> is loaded and waited for LAST
     int tune_cov_store_wt = 1;     // the same form: S is stored write-through (16-B sc1 stores); bit-identical results either way
     int tune_panel_qm_whole = 0;   // the same route: ONE Qm value per sample from the product's idle slab-1 workgroups (results move at rounding level)
     int tune_panel_stream = 1;     // the same route without whole-sample Qm: a wave of the product loads the part of G it multiplies, in stages along K, and starts each

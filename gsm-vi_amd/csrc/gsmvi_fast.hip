@@ -685,7 +685,94 @@ constexpr int COV_QUAD_SCR = (3 * 32 * 33 + 2 * SB * 32 + 512 > 4 * SB * 48) ? 3
 template <int SB>
 constexpr int COV_QUAD_LDS = COV_QUAD_SCR<SB> + 512;
 
-template <int SB, int KCT, bool S0L, bool WT>
+// WST (round 14; the QUAD instances only, knob "cov_wave_store") = the store path per WAVE.  A wave holds a whole 16 x 16 block of
+// U = (acc_d - acc_e) / B in accumulator layout (lane (c = l & 15, ks = l >> 4): rows ks + 4 r, r = 0 .. 3, of column c), and the
+// store path above spread the 16-B store units of a tile over the four waves that computed its blocks -- hence accumulators -> LW,
+// barrier, W = S0 + U in store layout -> LW, barrier, mirror by columns: three workgroup barriers and two LDS round trips behind
+// the last MFMA, no arithmetic in them, every wave waiting three times for the slowest of eight.  Here a wave forms, stores and
+// mirrors its block alone:
+//   S0 in the wave's own layout: lane (c, ks) loads the units (row ks + 4 (c & 1) [+ 8], columns c & ~1, + 1) of its block -- two
+//     16-B loads per thread as before, issued where s0v[] was;
+//   exchange: lanes c and c ^ 1 swap through DPP quad_perm [1, 0, 3, 2]: an even lane sends u[1], u[3] and receives u[0], u[2] of
+//     its neighbour (the same rows ks, ks + 8, column c + 1), an odd lane the reverse -- every lane then holds the two
+//     row-contiguous units it loaded S0 for, W = S0 + U by the same additions on the same values, and a wave instruction stores
+//     eight 128-B row segments;
+//   mirror: the block goes to a wave-private [16][18] LDS buffer (two ds_write_b128: the eight lanes of a write group cover the 32
+//     banks once) and comes back by columns (lane (j = (l >> 3) + 8 q, i2 = l & 7) reads rows 2 i2, 2 i2 + 1 of column j: 72 i2 + 2 j
+//     mod 64 over a half wave's 8 x 4 lanes is a permutation) as units S[J + j][I + 2 i2 ..].  Row stride 18, not 17: with 17 the
+//     four columns a half wave reads in one ds_read_b64 land on offsets j + {0, 2, .., 14} + 17 (row parity) mod 32, and no choice
+//     of four (column, parity) pairs that the second read can complement tiles the 32 double-banks -- a two-way conflict on every
+//     read; 18 is conflict free both ways and keeps the units 16-B aligned.
+// The eight buffers (8 x 288 doubles = 18 432 B) lie BEHIND the staged tiles and a quad's LDS, so a wave that is done with its MFMAs
+// writes nothing another wave may still be reading: no barrier behind the one that ends the staging, the only LDS a wave reads
+// behind its MFMAs is what it wrote itself (s_waitcnt lgkmcnt(0) + a wave barrier), and a wave leaves when its four stores are out.
+// Same chains, same (acc_d - acc_e) * invB, same S0 + U, copies for the mirror: mu and S are those of WST = false bit for bit.
+constexpr int COV_WST_RS = 18, COV_WST_PB = 16 * COV_WST_RS;
+// The two halves of that path.  gsm_cov_wave_direct: exchange, W = S0 + U, the block's two direct stores (STORE), and the block into a
+// [16][18] buffer -- PBW 1: W, for a mirror that is a copy; 2: U, for a transpose inside a diagonal tile, which is S0's own lower-left
+// block plus U^T; 0: nothing.  gsm_cov_wave_mirror: the buffer by columns, S0 units in that layout added where ADD, two stores.
+template <bool WT>
+__device__ __forceinline__ void gsm_cov_wave_st(double* __restrict__ S, [[maybe_unused]] __amdgpu_buffer_rsrc_t srs, size_t off, v2d v) {
+    if constexpr (WT) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(v4u, v), srs, (int)(off * sizeof(double)), 0, 16);
+    else *reinterpret_cast<v2d*>(S + off) = v;
+}
+template <bool WT, int PBW, bool STORE = true>
+__device__ __forceinline__ void gsm_cov_wave_direct(const v4d u, [[maybe_unused]] const v2d s0a, [[maybe_unused]] const v2d s0b,
+                                                    [[maybe_unused]] double* __restrict__ PB, double* __restrict__ S,
+                                                    __amdgpu_buffer_rsrc_t srs, [[maybe_unused]] size_t doff, int lds, int l) {
+    const int c = l & 15, ks = l >> 4;
+    const bool odd = c & 1;
+    const double x0 = dpp_f64<0xB1>(odd ? u[0] : u[1]);      // quad_perm [1, 0, 3, 2]: the neighbour's half of this lane's units
+    const double x1 = dpp_f64<0xB1>(odd ? u[2] : u[3]);
+    v2d ua, ub;
+    ua.x = odd ? x0 : u[0];
+    ua.y = odd ? u[1] : x0;
+    ub.x = odd ? x1 : u[2];
+    ub.y = odd ? u[3] : x1;
+    const int ra = ks + 4 * (c & 1), ca = c & ~1;
+    [[maybe_unused]] v2d w0, w1;
+    if constexpr (STORE) {
+        w0.x = s0a.x + ua.x;
+        w0.y = s0a.y + ua.y;
+        w1.x = s0b.x + ub.x;
+        w1.y = s0b.y + ub.y;
+        gsm_cov_wave_st<WT>(S, srs, doff + (size_t)ra * lds + ca, w0);
+        gsm_cov_wave_st<WT>(S, srs, doff + (size_t)(ra + 8) * lds + ca, w1);
+    }
+    static_assert(PBW != 1 || STORE, "a mirror that is a copy needs W");
+    if constexpr (PBW == 1) {
+        *reinterpret_cast<v2d*>(PB + ra * COV_WST_RS + ca) = w0;
+        *reinterpret_cast<v2d*>(PB + (ra + 8) * COV_WST_RS + ca) = w1;
+    } else if constexpr (PBW == 2) {
+        *reinterpret_cast<v2d*>(PB + ra * COV_WST_RS + ca) = ua;
+        *reinterpret_cast<v2d*>(PB + (ra + 8) * COV_WST_RS + ca) = ub;
+    }
+}
+template <bool WT, bool ADD>
+__device__ __forceinline__ void gsm_cov_wave_mirror(const double* PB, [[maybe_unused]] const v2d s0ma, [[maybe_unused]] const v2d s0mb,
+                                                    double* __restrict__ S, __amdgpu_buffer_rsrc_t srs, size_t moff, int lds, int l) {
+    const int i2 = l & 7, jj = l >> 3;
+#pragma unroll
+    for (int q = 0; q < 2; ++q) {
+        const int j = jj + 8 * q;
+        v2d m2;
+        m2.x = PB[(2 * i2) * COV_WST_RS + j];
+        m2.y = PB[(2 * i2 + 1) * COV_WST_RS + j];
+        if constexpr (ADD) {
+            m2.x = (q ? s0mb : s0ma).x + m2.x;
+            m2.y = (q ? s0mb : s0ma).y + m2.y;
+        }
+        gsm_cov_wave_st<WT>(S, srs, moff + (size_t)j * lds + 2 * i2, m2);
+    }
+}
+// a wave's own LDS writes are done (its stores stay in flight); nothing moves across
+#define COV_WAVE_SYNC()                                             \
+    do {                                                            \
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");          \
+        __builtin_amdgcn_wave_barrier();                            \
+    } while (0)
+
+template <int SB, int KCT, bool S0L, bool WT, bool WST = false>
 __device__ __forceinline__ void gsm_cov_quad(double* __restrict__ smem, int p, int D, int B, double invB, const double* __restrict__ mu0,
                                              const double* __restrict__ S0, int lds0, double* __restrict__ S, int lds,
                                              double* __restrict__ mu_out, unsigned long long* __restrict__ stamps, const gsm_slab_src& fs) {
@@ -702,6 +789,11 @@ __device__ __forceinline__ void gsm_cov_quad(double* __restrict__ smem, int p, i
     constexpr int LWS = 32 * 33, MUO = 3 * LWS, PAO = MUO + 2 * SB * 32, SCO = COV_QUAD_SCR<SB>;
     static_assert(512 % NU == 0 && (KCT == 2 || KCT == 4), "two-launch form: B == SB in {16, 32}");
     static_assert(SCO >= 4 * TILE && SCO >= PAO + 512, "handed-over accumulators outside the staged tiles and the store path's LDS");
+    // WST: the waves' private buffers (QPB: where the kernel puts them); the dmu tiles and their partial sums OUTSIDE the staged tiles
+    // (they are written at staging time): where they were at SB = 16, in the gap between a quad's LDS and the pairs' six tiles at SB = 32
+    constexpr int QPB = 6 * TILE >= COV_QUAD_LDS<SB> ? 6 * TILE : COV_QUAD_LDS<SB>;
+    constexpr int MUW = MUO >= 4 * TILE ? MUO : COV_QUAD_LDS<SB>, PAW = MUW + 2 * SB * 32;
+    static_assert(!WST || (MUW >= 4 * TILE && PAW + 512 <= (MUO >= 4 * TILE ? SCO : QPB)), "WST: the means' LDS outside the staged tiles, the hand-over and the private buffers");
     const int A0 = 64 * p, B0 = A0 + 32;
     const int tid = threadIdx.x, w = tid >> 6, l = tid & 63, c = l & 15, ks = l >> 4;
     const int t = w >> 2, wr = (w >> 1) & 1, wc = w & 1, tl = tid & 255;
@@ -713,7 +805,25 @@ __device__ __forceinline__ void gsm_cov_quad(double* __restrict__ smem, int p, i
         return *reinterpret_cast<const v2d*>(reinterpret_cast<const char*>(base) + byte_off);
     };
     v2d s0v[2], s0x;
+    // WST: FOUR S0 units per lane, in the layout of the blocks the wave stores (the same count on every wave, so that every wait in
+    // front of them stays counted): s0w[0..1] its whole block (waves 4-7: block (wr, wc) of tile (A, B); wave 0: (A, A) (0, 0); 1:
+    // (A, A) (0, 1); 2: (A, A) (1, 1); 3: (B, B) (0, 0)); s0w[2..3] its second block -- wave 0: (B, B) (0, 1); 1: (A, A) (1, 0) in the
+    // mirror's layout; 2: (B, B) (1, 0) in the mirror's layout; 3: (B, B) (1, 1); waves 4-7 re-read s0w[0..1]
+    [[maybe_unused]] v2d s0w[4];
     auto load_s0 = [&]() {
+        if constexpr (WST) {
+            const int r0 = (w >= 4) ? A0 + 16 * wr : (w == 3 ? B0 : (w == 2 ? A0 + 16 : A0));
+            const int c0 = (w >= 4) ? B0 + 16 * wc : (w == 3 ? B0 : (w == 0 ? A0 : A0 + 16));
+            const int r1 = (w >= 4) ? r0 : (w == 0 ? B0 : (w == 1 ? A0 + 16 : B0 + 16));
+            const int c1 = (w >= 4) ? c0 : (w == 1 ? A0 : (w == 2 ? B0 : B0 + 16));
+            const bool mir = w == 1 || w == 2;   // wave-uniform
+            const int dr = ks + 4 * (c & 1), dc = c & ~1, lr = mir ? (l >> 3) : dr, lc = mir ? 2 * (l & 7) : dc;
+#pragma unroll
+            for (int q = 0; q < 2; ++q) s0w[q] = *reinterpret_cast<const v2d*>(S0 + (size_t)(r0 + dr + 8 * q) * lds0 + c0 + dc);
+#pragma unroll
+            for (int q = 0; q < 2; ++q) s0w[2 + q] = *reinterpret_cast<const v2d*>(S0 + (size_t)(r1 + lr + 8 * q) * lds0 + c1 + lc);
+            return;
+        }
 #pragma unroll
         for (int q = 0; q < 2; ++q) {
             const int unit = q * 256 + tl;
@@ -773,7 +883,8 @@ __device__ __forceinline__ void gsm_cov_quad(double* __restrict__ smem, int p, i
     const double den = 1.0 + rho + mv;
     double beta = 1.0 / (1.0 + rho), cc = (gSg - mv) / den;
     if (stamps) {
-        if constexpr (S0L) asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
+        if constexpr (S0L && WST) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
+        else if constexpr (S0L) asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
         else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         QSTAMP(1);
     }
@@ -802,11 +913,43 @@ __device__ __forceinline__ void gsm_cov_quad(double* __restrict__ smem, int p, i
         if (st_d) *reinterpret_cast<v2d*>(smem + (2 * cb) * TILE + b * RS + c2) = dd;
         if (st_e) *reinterpret_cast<v2d*>(smem + (2 * cb + 1) * TILE + b * RS + c2) = ee;
         dmuq[cb] = dm;
+        if constexpr (WST) {                     // the dmu tile [SB][32] of this block goes out with the staging: the barrier below covers it
+            if (tid < NU) *reinterpret_cast<v2d*>(smem + MUW + cb * SB * 32 + (tid >> 4) * 32 + 2 * (tid & 15)) = dm;
+        }
     }
     QBARRIER();
     QSTAMP(2);
     // ---- the chains: a whole block per wave (LDS tiles: 0 = D_A, 1 = E_A, 2 = D_B, 3 = E_B), then one chain of a split block
     v4d accd = {0.0, 0.0, 0.0, 0.0}, acce = {0.0, 0.0, 0.0, 0.0}, xacc = {0.0, 0.0, 0.0, 0.0};
+    // ---- WST: the split chains FIRST, and the quad's one barrier between them and the whole blocks.  Waves 0-3 run their chain of a
+    // split block (the same operands in the same order, from zero) and leave its accumulator in LDS -- the d-chains where they
+    // always went, the e-chain of (B, B) (0, 1) in wave 0's private buffer, that of (B, B) (1, 1) in wave 3's --, all eight waves
+    // sum the first level of the means (the dmu tiles were staged), and the barrier hands all of it over.  Behind it nobody waits
+    // for anybody: a wave runs the chains of its whole block and then forms, stores and mirrors TWO blocks alone (below).
+    if constexpr (WST) {
+        if (w < 4) {
+            const double* xp = smem + (2 + (w & 1)) * TILE + ks * RS + c;
+            double xa[NS], xb[NS];
+#pragma unroll
+            for (int s = 0; s < NS; ++s) {
+                xa[s] = xp[4 * s * RS + 16 * (w >> 1)];
+                xb[s] = xp[4 * s * RS + 16];
+            }
+#pragma unroll
+            for (int s = 0; s < NS; ++s) xacc = GSMVI_MFMA_F64(xa[s], xb[s], xacc);
+            double* xo = (w & 1) ? smem + QPB + (w == 1 ? 0 : 3) * COV_WST_PB : smem + SCO + (w >> 1) * 256;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) xo[r * 64 + l] = xacc[r];
+        }
+        {                                        // first level of the means: block tid >> 8, row group (tid >> 5) & 7, column tid & 31
+            const double* mt = smem + MUW + (tid >> 8) * SB * 32;
+            double part = 0.0;
+#pragma unroll
+            for (int k = 0; k < SB / 8; ++k) part += mt[(((tid >> 5) & 7) + 8 * k) * 32 + (tid & 31)];
+            smem[PAW + tid] = part;              // 2 x [8][32]
+        }
+        asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");   // LDS only: the S0 loads stay in flight
+    }
     {
         const int ta = (w == 3) ? 2 : 0, tb = (w >= 3) ? 2 : 0;                  // wave-uniform
         const int br = (w >= 4) ? wr : (w == 2 ? 1 : 0), bc = (w >= 4) ? wc : ((w == 1 || w == 2) ? 1 : 0);
@@ -825,6 +968,7 @@ __device__ __forceinline__ void gsm_cov_quad(double* __restrict__ smem, int p, i
             accd = GSMVI_MFMA_F64(ad[s], bd[s], accd);
             acce = GSMVI_MFMA_F64(ae[s], be[s], acce);
         }
+        if constexpr (!WST) {
         if (w < 4) {                             // (B, B) block (w >> 1, 1): the d-chain on the even wave, the e-chain on the odd one
             const double* xp = smem + (2 + (w & 1)) * TILE + ks * RS + c;
 #pragma unroll
@@ -839,6 +983,68 @@ __device__ __forceinline__ void gsm_cov_quad(double* __restrict__ smem, int p, i
                 for (int r = 0; r < 4; ++r) smem[SCO + (w >> 1) * 256 + r * 64 + l] = xacc[r];
             }
         }
+        }
+    }
+    // ---- WST: no barrier behind the MFMAs.  Every wave forms, stores and mirrors two blocks alone, four stores of S each:
+    //   waves 4-7: block (wr, wc) of tile (A, B) and its mirror, as a pair's;
+    //   wave 0: (A, A) (0, 0); (B, B) (0, 1) from the handed-over d- and e-chain;  wave 3: (B, B) (0, 0); (B, B) (1, 1) likewise;
+    //   wave 1: (A, A) (0, 1) and its transpose (A, A) (1, 0) = S0's own lower-left block + U(0, 1)^T, through its buffer;
+    //   wave 2: (A, A) (1, 1); the transpose (B, B) (1, 0) from the same two handed-over chains as wave 0 reads -- the same
+    //           (d - e) * invB on the same values -- through its buffer;  wave 0 then adds the second level of the means.
+    if constexpr (WST) {
+        double* PBQ = smem + QPB;
+        v4d u;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) u[r] = (accd[r] - acce[r]) * invB;
+        if (stamps) {                            // [3] wave 0's MFMAs done, [6] S0 landed
+            asm volatile("" : "+v"(u));
+            QSTAMP(3);
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            QSTAMP(6);
+        }
+        __amdgpu_buffer_rsrc_t srs = __builtin_amdgcn_make_buffer_rsrc(S, 0, 0, 0);   // (plain stores: not used)
+        if constexpr (WT) srs = __builtin_amdgcn_make_buffer_rsrc(S, 0, (int)(((size_t)(D - 1) * lds + D) * sizeof(double)), 0x00020000);
+        // all four S0 units are waited for HERE, in front of the first store: s0w[2..3] came in right behind s0w[0..1], and a wait
+        // for them behind the first stores is a vmcnt(1) at the join of these branches (the waves have issued two or four stores by
+        // then), which waits for all but one of the write-through stores to be acknowledged
+        asm volatile("" : "+v"(s0w[0]), "+v"(s0w[1]), "+v"(s0w[2]), "+v"(s0w[3]));
+        if (w >= 4) {
+            double* PB = PBQ + w * COV_WST_PB;
+            gsm_cov_wave_direct<WT, 1>(u, s0w[0], s0w[1], PB, S, srs, (size_t)(A0 + 16 * wr) * lds + B0 + 16 * wc, lds, l);
+            COV_WAVE_SYNC();
+            gsm_cov_wave_mirror<WT, false>(PB, s0w[0], s0w[1], S, srs, (size_t)(B0 + 16 * wc) * lds + A0 + 16 * wr, lds, l);
+        } else if (w == 1) {
+            double* PB = PBQ + COV_WST_PB;
+            gsm_cov_wave_direct<WT, 2>(u, s0w[0], s0w[1], PB, S, srs, (size_t)A0 * lds + A0 + 16, lds, l);
+            COV_WAVE_SYNC();
+            gsm_cov_wave_mirror<WT, true>(PB, s0w[2], s0w[3], S, srs, (size_t)(A0 + 16) * lds + A0, lds, l);
+        } else {
+            const int X0 = (w == 3) ? B0 : (w == 2 ? A0 + 16 : A0), bi = (w == 3) ? 1 : 0;
+            gsm_cov_wave_direct<WT, 0>(u, s0w[0], s0w[1], nullptr, S, srs, (size_t)X0 * lds + X0, lds, l);
+            const double* xd = smem + SCO + bi * 256;              // the handed-over chains of (B, B) (bi, 1)
+            const double* xe = PBQ + (bi ? 3 : 0) * COV_WST_PB;
+            v4d xu;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) xu[r] = (xd[r * 64 + l] - xe[r * 64 + l]) * invB;
+            if (w == 2) {
+                double* PB = PBQ + 2 * COV_WST_PB;
+                gsm_cov_wave_direct<WT, 2, false>(xu, s0w[2], s0w[3], PB, S, srs, 0, lds, l);
+                COV_WAVE_SYNC();
+                gsm_cov_wave_mirror<WT, true>(PB, s0w[2], s0w[3], S, srs, (size_t)(B0 + 16) * lds + B0, lds, l);
+            } else {
+                gsm_cov_wave_direct<WT, 0>(xu, s0w[2], s0w[3], nullptr, S, srs, (size_t)(B0 + 16 * bi) * lds + B0 + 16, lds, l);
+            }
+            if (w == 0) {                        // second level: mu of blocks A (lanes 0-31) and B (lanes 32-63)
+                double s = 0.0;
+#pragma unroll
+                for (int q = 0; q < 8; ++q) s += smem[PAW + (l >> 5) * 256 + q * 32 + (l & 31)];
+                mu_out[A0 + l] = mu0q + s * invB;
+            }
+        }
+        if (stamps) __syncthreads();             // [4]: every wave has issued its last store (the timeline instance only)
+        QSTAMP(4);
+        if (stamps) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); QSTAMP(5); }
+        return;
     }
     QBARRIER();                                  // the factor tiles are read, the d-accumulators of the split blocks are in LDS
     {
@@ -929,8 +1135,9 @@ __device__ __forceinline__ void gsm_cov_quad(double* __restrict__ smem, int p, i
 #undef QBARRIER
 }
 
-template <int SB, bool RAG, bool FROM_SLABS = false, int KCT = 4, bool FOLD = false, bool S0L = false, bool WT = false, bool QMW = false, bool QUAD = false>
-__global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(FROM_SLABS ? 4 : 2))) void k_gsm_cov_sym(int D, int B, double invB, const double* __restrict__ rec, int ldrec,
+template <int SB, bool RAG, bool FROM_SLABS = false, int KCT = 4, bool FOLD = false, bool S0L = false, bool WT = false, bool QMW = false, bool QUAD = false,
+          bool WST = false>
+__global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(FROM_SLABS && !(WST && SB == 32) ? 4 : 2))) void k_gsm_cov_sym(int D, int B, double invB, const double* __restrict__ rec, int ldrec,
                                                      const double* __restrict__ mu0,
                                                      const double* __restrict__ S0, int lds0,
                                                      double* __restrict__ S, int lds,
@@ -939,6 +1146,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(FROM_SLABS 
     static_assert(!FOLD || FROM_SLABS, "folded diagonal tiles: the two-launch form only");
     static_assert(!(S0L || WT || QMW) || (FROM_SLABS && KCT == 2 && !RAG), "S0 last / write-through stores / whole-sample Qm: the two-slab two-launch form only, on the grid");
     static_assert(!QUAD || (FROM_SLABS && !FOLD && !QMW && !RAG && (SB == 16 || SB == 32)), "quads: the two-launch form, in place of the fold");
+    static_assert(!WST || QUAD, "per-wave store path: the quad / pair map only (no diagonal pair, no host, no edge tile)");
     // barriers between staging and the W step: LDS-only where S0 is in flight across them
 #define PRE_W_BARRIER()                                                                   \
     do {                                                                                  \
@@ -962,7 +1170,9 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(FROM_SLABS 
     constexpr int UPT = (6 * NU) / 512;          // units per thread over the six tiles
     static_assert((6 * NU) % 512 == 0, "tile units must divide over 512 threads");
     constexpr int QLDS = QUAD ? COV_QUAD_LDS<SB> : 0;   // (a quad's LDS: more than the six tiles at SB = 16)
-    __shared__ __attribute__((aligned(16))) double smem[6 * TILE >= 2 * 32 * 33 ? (6 * TILE >= QLDS ? 6 * TILE : QLDS) : 2 * 32 * 33];
+    constexpr int PBO = 6 * TILE >= 2 * 32 * 33 ? (6 * TILE >= QLDS ? 6 * TILE : QLDS) : 2 * 32 * 33;   // WST: the waves' private buffers behind it
+    static_assert(!WST || (PBO % 2 == 0 && PBO >= 6 * TILE && PBO >= QLDS), "private buffers: 16-B aligned, behind the staged tiles and a quad's LDS");
+    __shared__ __attribute__((aligned(16))) double smem[PBO + (WST ? 8 * COV_WST_PB : 0)];
     // staged tiles, in this order: DI, EI, DJ0, EJ0, DJ1, EJ1
 
     // ---- which tiles: row block ti, column blocks tj0, tj0+1 ------------------------------------
@@ -977,7 +1187,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(FROM_SLABS 
     int fold = 0;                                                // FOLD: 1 = hosts the diagonal tile of its own row, 2 = that of the last row
     if constexpr (QUAD) {                                        // quads first (gsm_cov_quad above), then the pairs right of them
         if ((int)blockIdx.x < (nt >> 1)) {
-            gsm_cov_quad<SB, KCT, S0L, WT>(smem, blockIdx.x, D, B, invB, mu0, S0, lds0, S, lds, mu_out, stamps, fs);
+            gsm_cov_quad<SB, KCT, S0L, WT, WST>(smem, blockIdx.x, D, B, invB, mu0, S0, lds0, S, lds, mu_out, stamps, fs);
             return;
         }
         int rem = blockIdx.x - (nt >> 1);
@@ -1021,7 +1231,11 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(FROM_SLABS 
     const int Jt = J0 + 32 * ((t == 1 && two) ? 1 : 0);
     const int tl = tid & 255;
     v2d s0v[2];
-    if constexpr (!S0L) {
+    if constexpr (!S0L && WST) {                 // WST: the lane's two units of block (wr, wc), rows ks + 4 (c & 1) [+ 8], columns c & ~1, + 1
+#pragma unroll
+        for (int q = 0; q < 2; ++q)
+            s0v[q] = *reinterpret_cast<const v2d*>(S0 + (size_t)(I0 + 16 * wr + ks + 4 * (c & 1) + 8 * q) * lds0 + Jt + 16 * wc + (c & ~1));
+    } else if constexpr (!S0L) {
 #pragma unroll
         for (int q = 0; q < 2; ++q) {
             const int unit = q * 256 + tl, i = unit >> 4, j2 = unit & 15;
@@ -1092,8 +1306,10 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(FROM_SLABS 
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int q = 0; q < 2; ++q) {
-                const int unit = q * 256 + tl;
-                s0v[q] = *reinterpret_cast<const v2d*>(S0 + (size_t)(I0 + (unit >> 4)) * lds0 + Jt + 2 * (unit & 15));
+                [[maybe_unused]] const int unit = q * 256 + tl;
+                if constexpr (WST)               // (block (wr, wc) in the wave's own layout; the lane column c is shadowed below, not here)
+                    s0v[q] = *reinterpret_cast<const v2d*>(S0 + (size_t)(I0 + 16 * wr + ks + 4 * (l & 1) + 8 * q) * lds0 + Jt + 16 * wc + (l & 14));
+                else s0v[q] = *reinterpret_cast<const v2d*>(S0 + (size_t)(I0 + (unit >> 4)) * lds0 + Jt + 2 * (unit & 15));
             }
             if constexpr (FOLD) {
                 const int xr = fold ? X0 + (tid >> 4) : I0 + ((256 + tl) >> 4), xc = fold ? X0 + 2 * (tid & 15) : Jt + 2 * (tl & 15);
@@ -1260,6 +1476,29 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(FROM_SLABS 
                 }
             }
         }
+    }
+    // ---- WST: every wave forms, stores and mirrors its own block (gsm_cov_wave_store); no barrier, no shared LDS.  A pair of the
+    // quad map is never diagonal: no mean here.
+    if constexpr (WST) {
+        v4d u;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) u[r] = (accd[r] - acce[r]) * invB;
+        if (stamps) {                            // [3] "MFMAs done" (wave 0's), [6] "S0 landed", as without the flag
+            asm volatile("" : "+v"(u));
+            STAMP(3);
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            STAMP(6);
+        }
+        __amdgpu_buffer_rsrc_t wrs = __builtin_amdgcn_make_buffer_rsrc(S, 0, 0, 0);   // (plain stores: not used)
+        if constexpr (WT) wrs = __builtin_amdgcn_make_buffer_rsrc(S, 0, (int)(((size_t)(D - 1) * lds + D) * sizeof(double)), 0x00020000);
+        double* PB = smem + PBO + w * COV_WST_PB;
+        gsm_cov_wave_direct<WT, 1>(u, s0v[0], s0v[1], PB, S, wrs, (size_t)(I0 + 16 * wr) * lds + Jt + 16 * wc, lds, l);
+        COV_WAVE_SYNC();
+        gsm_cov_wave_mirror<WT, false>(PB, s0v[0], s0v[1], S, wrs, (size_t)(Jt + 16 * wc) * lds + I0 + 16 * wr, lds, l);
+        if (stamps) __syncthreads();             // [4] still means "every wave has issued its last store" (the timeline instance only)
+        STAMP(4);
+        if (stamps) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); STAMP(5); }
+        return;
     }
     // ---- stores through LDS, 16 B per lane: the update tile U_t = (D_I^T D_J - E_I^T E_J)/B goes to LDS in accumulator
     // layout; W_t = S0[I, J_t] + U_t is formed in store layout (row segments of 256 B), stored, written back to LDS, and
@@ -1923,18 +2162,21 @@ bool gsmvi_launch_gsm_cov_sym(hipStream_t st, hipEvent_t* ev, int D, int B, cons
 // fold (round 9): the grid is the two-tile workgroups alone, the diagonal leftovers are third tiles of their hosts (FOLD above).
 void gsmvi_launch_gsm_cov_sym_slabs(hipStream_t st, hipEvent_t* ev, int D, int B, const gsm_slab_src& fs, const double* mu0,
                                     const double* S0, int lds0, double* S, int lds, double* mu_out, int kct, bool fold,
-                                    bool s0_last, bool store_wt, bool qm_whole, bool quad, unsigned long long* stamps) {
+                                    bool s0_last, bool store_wt, bool qm_whole, bool quad, bool wave_store, unsigned long long* stamps) {
     const double invB = 1.0 / (double)B;
     // quad (round 13; the caller passes it for the shipped two-slab form -- S0 last, write-through stores, per-strip Qm -- and for
     // the plain kct = 4 form only): the quad / pair map, (nt / 2)^2 workgroups
     if (quad) {
         const dim3 qgrid(cov_sym_quad_grid(D / 32));
-#define CSD(SBV, KV, LV, WV)                                                                                              \
-    GSMVI_LAUNCH((k_gsm_cov_sym<SBV, false, true, KV, false, LV, WV, false, true>), qgrid, dim3(512), 0, st, ev, D, B, invB, nullptr, 0, mu0, \
+#define CSE(SBV, KV, LV, WV, SV)                                                                                          \
+    GSMVI_LAUNCH((k_gsm_cov_sym<SBV, false, true, KV, false, LV, WV, false, true, SV>), qgrid, dim3(512), 0, st, ev, D, B, invB, nullptr, 0, mu0, \
                  S0, lds0, S, lds, mu_out, 0, stamps, fs)
+        // round 14 ("cov_wave_store"): the same four instances with the per-wave store path
+#define CSD(SBV, KV, LV, WV) do { if (wave_store) CSE(SBV, KV, LV, WV, true); else CSE(SBV, KV, LV, WV, false); } while (0)
         if (kct == 2) { if (B == 16) CSD(16, 2, true, true); else CSD(32, 2, true, true); }
         else { if (B == 16) CSD(16, 4, false, false); else CSD(32, 4, false, false); }
 #undef CSD
+#undef CSE
         return;
     }
     const dim3 grid(fold ? gsmvi_cov_sym_pairs(D / 32) : cov_sym_grid(D / 32));

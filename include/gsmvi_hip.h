@@ -120,6 +120,10 @@ int gsmvi_destroy(gsmvi_ctx* ctx);
  * blocks, three tiles on two staged column blocks, every other tile rides in a pair; 1 = where the fold runs by default on the
  * two-slab form with "cov_s0_last" and "cov_store_wt" on and "panel_qm_whole" off, default; 0 = the fold as it was; 2 = wherever
  * "cov_fold_diag" is not 0, for tests; bit-identical results, reported under GSMVI_PATH_COV_FOLD_DIAG);
+ * round 14: "cov_wave_store" (wherever "cov_diag_quad" selects the quads: 1 = every wave of the covariance launch forms W =
+ * Sigma0 + U for the 16 x 16 block it computed, stores it and mirrors it through a wave-private LDS buffer, with no workgroup
+ * barrier behind the MFMAs, default; 0 = the store path through shared LDS buffers and three barriers; bit-identical results,
+ * no path bit);
  * diagnostics "timeline", "cov_dbg"
  * (see gsmvi_hip_debug.h). */
 int gsmvi_set_tuning(gsmvi_ctx* ctx, const char* name, int value);

@@ -79,11 +79,12 @@ nt = D // 32
 import re as _re
 _ctx_h = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "gsm-vi_amd", "csrc", "gsmvi_ctx.h")).read()
 _knob = {k: int(_re.search(rf"int\s+tune_{k}\s*=\s*(\d+)\s*;", _ctx_h).group(1))
-         for k in ("cov_diag_quad", "cov_fold_diag", "cov_s0_last", "cov_store_wt", "panel_qm_whole", "panel_kc")}
+         for k in ("cov_diag_quad", "cov_wave_store", "cov_fold_diag", "cov_s0_last", "cov_store_wt", "panel_qm_whole", "panel_kc")}
 _knob.update({kv.split("=")[0]: int(kv.split("=")[1]) for kv in sys.argv[2:]})
 quad_on = (_knob["cov_diag_quad"] != 0 and _knob["cov_fold_diag"] != 0 and _knob["cov_s0_last"] != 0 and _knob["cov_store_wt"] != 0
            and _knob["panel_qm_whole"] == 0 and _knob["panel_kc"] <= 0 and len(end) == (nt >> 1) ** 2)
 if quad_on:
+    print(f"cov_wave_store = {_knob['cov_wave_store']} (round 14: 1 = per-wave store path; [4] stands behind a barrier in the stamped instance only)")
     quad = np.arange(len(end)) < (nt >> 1)
     for nm, sel in (("quads", quad), ("pairs", ~quad)):
         e, p = end[sel], ph[sel]
