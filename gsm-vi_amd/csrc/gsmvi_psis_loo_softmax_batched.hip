@@ -10,8 +10,10 @@
 //       the A operand is x_{s, c P + 4 j + kq}, the B operand a_{i, 4 j + kq}, Pp / 4 steps.  Two sweeps over the classes, the
 //       MFMA chain recomputed in the second (the same instructions on the same LDS values: the same bits): sweep 1 takes
 //       m = max(0, eta_c), selects eta_y and notes a non-finite eta; sweep 2 sums exp(eta_c - m) in class order and adds the
-//       reference class's exp(-m) last.  No eta is stored and the registers do not depend on C.  Only lanes whose column is a
-//       valid observation run the comparisons and exponentials.  The tile's l_si stay in LDS (NI x S doubles).
+//       reference class's exp(-m) last, as z = 1 + rest (sm_add_term of gsmvi_softmax_model.h: the terms below 1, then the count
+//       of the terms that are 1), and log z is log1p(rest) (sm_log_s: log(z) is 0 where rest < eps / 2).  No eta is stored and
+//       the registers do not depend on C.  Only lanes whose column is a valid observation run the comparisons and exponentials.
+//       The tile's l_si stay in LDS (NI x S doubles).
 //       The padding rule: with P % 4 != 0 the k positions 4 j + kq >= P of class c would address x entries of class c + 1 (past
 //       column D - 1 at the last class), and there the B operand holds a padded zero: 0 x non-finite = NaN would flag a draw
 //       that the definition does not.  The X tile keeps the memory layout and the A operand is MASKED instead: a lane whose k
@@ -109,13 +111,13 @@ __global__ __launch_bounds__(256) void k_psis_loo_softmax_batched(pls_args a) {
                         }
                     }
                 }
-                double z[4] = {0.0, 0.0, 0.0, 0.0};
+                double z[4] = {0.0, 0.0, 0.0, 0.0}, nt[4] = {0.0, 0.0, 0.0, 0.0};      // z = 1 + rest: sm_add_term
 #pragma unroll 1
                 for (int c = 0; c < Cm; ++c) {                  // sweep 2: the same chain, the sum in class order
                     const v4d acc = sm_eta(px, pb, c, P, Pp, kq);
                     if (live) {
 #pragma unroll
-                        for (int r = 0; r < 4; ++r) z[r] += exp(acc[r] - m[r]);
+                        for (int r = 0; r < 4; ++r) sm_add_term(z[r], nt[r], exp(acc[r] - m[r]));
                     }
                 }
                 if (live) {
@@ -123,7 +125,9 @@ __global__ __launch_bounds__(256) void k_psis_loo_softmax_batched(pls_args a) {
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
                         const int s = t0 + 16 * wv + kq + 4 * r;    // the draw; cc is the observation
-                        if (s < S) ell[cc * S + s] = yok && fine[r] ? ey[r] - m[r] - log(z[r] + exp(0.0 - m[r])) : qnan;
+                        sm_add_term(z[r], nt[r], exp(0.0 - m[r]));
+                        const double rest = sm_rest(z[r], nt[r]);
+                        if (s < S) ell[cc * S + s] = yok && fine[r] ? ey[r] - m[r] - sm_log_s(rest, 1.0 + rest) : qnan;
                     }
                 }
             }

@@ -7,7 +7,9 @@
 //   eta_nc = a_n . w_c  (c < C-1),   eta_n,C-1 = 0
 //   m_n    = max_c eta_nc            (over all C values, the 0 included)
 //   s_n    = sum_{c=0..C-1} exp(eta_nc - m_n)     (class order; the reference class last)
-//   lp(x)  = sum_{n<n_k} [ eta_n,y_n - m_n - log s_n ] - lam_k |x|^2 / 2
+//          = 1 + rest_n: the terms below 1 in that order, then the count of the terms that are 1 less one (sm_add_term)
+//   lp(x)  = sum_{n<n_k} [ eta_n,y_n - m_n - log s_n ] - lam_k |x|^2 / 2     (log s_n as log1p(rest_n): sm_log_s; log(s_n) is 0
+//                                                                            where rest_n < eps / 2)
 //   g_cj   = sum_{n<n_k} ( [y_n = c] - exp(eta_nc - m_n)/s_n ) a_nj - lam_k x_cj      (c < C-1)
 //   k_softmax_batched<NT, WANT> : WANT = SB_G (the score alone: no logarithm), SB_LP (the density alone: no second pass over
 //                                 the tile), or both from one pass
@@ -224,18 +226,20 @@ __global__ __launch_bounds__(256, 2) void k_softmax_batched(sb_args a) {
                         m = fmax(m, eta);
                         etay = c == yv ? eta : etay;
                     }
-                    double s = 0.0;
+                    double rest = 0.0, nt = 0.0;      // s = 1 + rest: the terms below 1, and the count of those that are 1 (sm_add_term)
 #pragma unroll 1
                     for (int c = 0; c < Cm; ++c) {
                         const double e = exp(er[c * ldr] - m);
-                        s += e;
+                        sm_add_term(rest, nt, e);
                         if (HAS_G) er[c * ldr] = e;
                     }
-                    s += exp(0.0 - m);
+                    sm_add_term(rest, nt, exp(0.0 - m));
+                    rest = sm_rest(rest, nt);
+                    const double s = 1.0 + rest;
                     if (HAS_G)
 #pragma unroll 2
                         for (int c = 0; c < Cm; ++c) er[c * ldr] = (c == yv ? 1.0 : 0.0) - er[c * ldr] / s;
-                    if (HAS_LP) Ts[q * ldr + en] = etay - m - log(s);
+                    if (HAS_LP) Ts[q * ldr + en] = etay - m - sm_log_s(rest, s);
                     if (!fine) Rb[q] = qnan;          // (any number of threads, the same value)
                 }
             }

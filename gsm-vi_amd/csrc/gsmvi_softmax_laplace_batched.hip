@@ -15,7 +15,8 @@
 // digit of its diagonal block): with c* the first class that attains m (e_c* = 1 exactly), s_rest = sum_{c != c*} e_c and
 // s = 1 + s_rest,   1 - p_c* = s_rest / s,   1 - p_c = (s - e_c) / s  (c != c*; s - e_c >= 1).  The reference class takes part in m, s
 // and s_rest like any other (it is the last candidate for c*).  The residual is r_nc = 1 - p_nc in that form where y_n = c and
-// -p_nc elsewhere; the density's term is eta_n,y_n - m_n - log s_n.
+// -p_nc elsewhere; the density's term is eta_n,y_n - m_n - log s_n with log s_n as log1p(s_rest) (sm_log_s of gsmvi_softmax_model.h:
+// log(s_n) is 0 where s_rest < eps / 2).
 // Work mapping: the slots of gsmvi_batched.h (gb_nt(D) threads per problem, four problems -- one wave each -- per 256-thread
 // workgroup for D <= 16).  A slot walks the rows of A_k in tiles of SL_TN = 32 (row stride P | 1, all 32 rows written, zeros in the
 // rows that do not count); the next tile's loads are in flight while the current one is consumed.  Per tile: NT / 32 adjacent lanes
@@ -272,7 +273,7 @@ __global__ __launch_bounds__(256) void k_softmax_laplace_batched(sl_args a) {
                 Qb[c * SL_LDR + en] = on ? (c == cs ? rest : sn - e) / sn : 0.0;
             }
             if (eg == 0) {
-                if (STEP) Ts[en] = on ? etay - m - log(sn) : 0.0;
+                if (STEP) Ts[en] = on ? etay - m - sm_log_s(rest, sn) : 0.0;
                 if (on && !fine) cell[0] = qnan;      // (any number of threads, the same value)
             }
         }

@@ -43,6 +43,28 @@ __device__ __forceinline__ v4d sm_eta(const double* px, const double* pb, int c,
     return acc;
 }
 
+// s = sum_c exp(eta_c - m) as 1 + rest, and log s without the rounding of s.  A term e = exp(eta_c - m) is exactly 1 for a class
+// that attains m and below 1 for every other, so floor(e) tells the two apart without a comparison: the terms below 1 are summed
+// in class order (rest), the ones counted (nt >= 1), and rest + (nt - 1) is s - 1 with the relative error of a sum of positive
+// terms.  log(s) alone returns 0 where rest < eps / 2 (the winning class ahead by more than 1 / eps), where the definition's log s
+// is rest; sm_log_s adds what the rounding of s = 1 + rest dropped, d = rest - (s - 1) (exact while rest <= 1), as the first-order
+// term d / s, with 2 - s for 1 / s below s = 2 (the error, d (s - 1)^2 / s, stays under 0.4 eps of log s) and nothing from s = 2 on
+// (d / s <= eps / 2 next to log s >= 0.69): log1p(rest) to two eps, at the cost of log and six operations.
+// k_softmax_batched, k_psis_loo_softmax_batched and k_softmax_predict_batched sum this way; k_softmax_laplace_batched has its own
+// rest (it needs c*, the first class that attains m, for 1 - p) and shares sm_log_s.
+__device__ __forceinline__ void sm_add_term(double& rest, double& nt, double e) {
+    const double f = floor(e);
+    rest += e - f;
+    nt += f;
+}
+
+__device__ __forceinline__ double sm_rest(double rest, double nt) { return rest + (nt - 1.0); }
+
+__device__ __forceinline__ double sm_log_s(double rest, double s) {
+    const double d = rest - (s - 1.0);
+    return log(s) + (s < 2.0 ? d * (2.0 - s) : 0.0);
+}
+
 // the rows of problem k that count: counts[k] clamped to 0 .. N (null: N)
 __device__ __forceinline__ long long sm_rows_of(const int* counts, long long k, long long N) {
     if (!counts) return N;

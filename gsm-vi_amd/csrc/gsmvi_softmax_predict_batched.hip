@@ -11,7 +11,8 @@
 // in each (the same instructions on the same LDS values: the same bits), so no eta is stored and the registers do not depend
 // on C:
 //   sweep 1  m = max(0, eta_c), eta_y by comparison with the label, a non-finite eta noted
-//   sweep 2  z = sum_c exp(eta_c - m) in class order, the reference class's exp(-m) last
+//   sweep 2  z = sum_c exp(eta_c - m) in class order, the reference class's exp(-m) last, as 1 + rest (sm_add_term of
+//            gsmvi_softmax_model.h); the lpd's log z is log1p(rest) (sm_log_s: log(z) is 0 where rest < eps / 2)
 //   sweep 3  per class (the reference class last) the lane's four exp(eta_c - m) (w_s / z) in order, draws s >= S left out, then
 //            the four lanes of the row by a butterfly (xor 16, xor 32); lane kq = 0 adds the sum to the LDS slot of (wave, class, row)
 // The slots (4 x C x 16 doubles) are the per-class accumulators: each is updated by one thread alone, tile after tile.  lpd is a
@@ -159,20 +160,22 @@ __global__ __launch_bounds__(256) void k_softmax_predict_batched(sp_args a) {
                     }
                 }
             }
-            double z[4] = {0.0, 0.0, 0.0, 0.0};
+            double rest[4] = {0.0, 0.0, 0.0, 0.0}, nt[4] = {0.0, 0.0, 0.0, 0.0};      // z = 1 + rest: sm_add_term
 #pragma unroll 1
             for (int c = 0; c < Cm; ++c) {                  // sweep 2: the same chain, the sum in class order
                 const v4d acc = sm_eta(px, pb, c, P, Pp, kq);
                 if (live) {
 #pragma unroll
-                    for (int r = 0; r < 4; ++r) z[r] += exp(acc[r] - m[r]);
+                    for (int r = 0; r < 4; ++r) sm_add_term(rest[r], nt[r], exp(acc[r] - m[r]));
                 }
             }
-            double e0[4], g[4];                             // the reference class's term; the draw's weight over z, 0 for s >= S
+            double e0[4], z[4], g[4];                       // the reference class's term; z; the draw's weight over z, 0 for s >= S
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 e0[r] = exp(0.0 - m[r]);
-                z[r] += e0[r];
+                sm_add_term(rest[r], nt[r], e0[r]);
+                rest[r] = sm_rest(rest[r], nt[r]);
+                z[r] = 1.0 + rest[r];
                 g[r] = in[r] ? w[r] / z[r] : 0.0;           // w_s / z_si once: p_sic w_s = exp(eta_sic - m_si) (w_s / z_si)
             }
 #pragma unroll 1
@@ -194,7 +197,7 @@ __global__ __launch_bounds__(256) void k_softmax_predict_batched(sp_args a) {
                     double t[4];
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
-                        t[r] = in[r] ? lws[16 * wv + kq + 4 * r] + (ey[r] - m[r] - log(z[r])) : -inf;
+                        t[r] = in[r] ? lws[16 * wv + kq + 4 * r] + (ey[r] - m[r] - sm_log_s(rest[r], z[r])) : -inf;
                         tm = fmax(tm, t[r]);
                     }
 #pragma unroll

@@ -613,6 +613,9 @@ int gsmvi_negbin_batched_f64(gsmvi_ctx* ctx, void* stream, int64_t K, int P, int
  *   s_n    = sum_{c=0..C-1} exp(eta_nc - m_n)     (class order; the reference class last)
  *   lp(x)  = sum_{n<n_k} [ eta_n,y_n - m_n - log s_n ] - lam_k |x|^2 / 2
  *   g_cj   = sum_{n<n_k} ( [y_n = c] - exp(eta_nc - m_n)/s_n ) a_nj - lam_k x_cj      (c < C-1)
+ * The term of the first class that attains m_n is exactly 1, so every softmax entry point sums the other terms alone (rest_n),
+ * takes s_n = 1 + rest_n and evaluates log s_n as log1p(rest_n): where the reference class (or any other) wins by more than
+ * 1 / eps, s_n rounds to 1 and log(s_n) would return 0 for a term that is -rest_n.
  * A (K x N x P) doubles, labels (K x N) ints, X, G (K x nc x D), lp (K x nc), packed, in device memory.  C >= 2, P >= 1,
  * 1 <= D <= 64 and K with the grid limits of the batched GSM above; nc >= 1 and N >= 1 are not bounded by LDS (both are walked in
  * tiles; the tile of X rows shrinks as C grows).  counts_dev: NULL = N valid rows everywhere, else K ints on the device, each

@@ -8,6 +8,8 @@ k, draws x_s of q_k (class-major: x_s[c P + j] = W_cj) and a valid row i < n_k
     m_si    = max_c eta_sic,   z_si = sum_{c = 0 .. C-1} exp(eta_sic - m_si)   (class order, the reference class last)
     l_si    = eta_si,y_i - m_si - log z_si
 
+with z = 1 + rest and log z = log1p(rest) in the kernels' forms (softmax_batched_ref's ``s_minus_one`` and ``log_s``).
+
 NaN where a dot product is not finite, where x_s has a non-finite entry, and where y_i is outside 0 .. C - 1 (compared, never an
 index).  From there the text is the GLM leave-one-out's, so the stage and the log-sum-exps are psis_loo_ref's ``loo_batched`` and
 ``summaries`` on the l_si block: there is no second copy."""
@@ -75,13 +77,11 @@ def loglik_softmax(A, labels, C, counts, X, dtype=LD):
             dots = np.einsum("np,scp->nsc", A[k, :n].astype(dtype), W)                  # (n, S, C - 1)
             eta = np.concatenate([dots, np.zeros((n, S, 1), dtype=dtype)], axis=2)
             m = eta.max(axis=2)
-            z = np.zeros((n, S), dtype=dtype)
-            for c in range(C):                                                          # class order; the reference class last
-                z = z + np.exp(eta[:, :, c] - m)
+            rest = sref.s_minus_one(np.exp(eta - m[:, :, None]))                         # class order; the reference class last
             etay = np.zeros((n, S), dtype=dtype)
             for c in range(C):                                                          # a label is compared, never an index
                 etay = np.where((y[k, :n] == c)[:, None], eta[:, :, c], etay)
-            ell = etay - m - np.log(z)
+            ell = etay - m - sref.log_s(rest, 1 + rest)                                 # log z, z = 1 + rest
         bad = ~np.isfinite(dots).all(axis=2) | ~np.isfinite(X[k]).all(axis=1)[None, :]
         bad |= ((y[k, :n] < 0) | (y[k, :n] > C - 1))[:, None]
         out[k, :n] = np.where(bad, dtype(np.nan), ell)

@@ -5,8 +5,8 @@ lam_k, class C - 1 the reference class and x[c P + j] = W_cj:
 
     eta_nc = a_n . w_c  (c < C-1),   eta_n,C-1 = 0
     m_n    = max_c eta_nc            (over all C values, the 0 included)
-    s_n    = sum_{c=0..C-1} exp(eta_nc - m_n)     (class order; the reference class last)
-    lp(x)  = sum_{n<n_k} [ eta_n,y_n - m_n - log s_n ] - lam_k |x|^2 / 2
+    s_n    = sum_{c=0..C-1} exp(eta_nc - m_n) = 1 + rest_n     (class order, the reference class last: ``s_minus_one``)
+    lp(x)  = sum_{n<n_k} [ eta_n,y_n - m_n - log s_n ] - lam_k |x|^2 / 2     (log s_n as log1p(rest_n): ``log_s``)
     g_cj   = sum_{n<n_k} ( [y_n = c] - exp(eta_nc - m_n)/s_n ) a_nj - lam_k x_cj      (c < C-1)
 
 with the kernel's NaN rule: a row of X with a non-finite entry, or for which some valid eta is not finite, gets NaN outputs.  It
@@ -44,6 +44,24 @@ def nc_grid(C, P):
     return sorted(set(NCS) | {t, t + 1})
 
 
+def s_minus_one(e):
+    """rest = s - 1 of the terms e (..., C) = exp(eta - m) <= 1 as the kernels sum it (sm_add_term of csrc/gsmvi_softmax_model.h):
+    a term is exactly 1 for a class that attains m and below 1 otherwise, so floor(e) tells them apart; the terms below 1 in
+    class order (the reference class last), then the count of the terms that are 1, less one"""
+    rest, nt = np.zeros(e.shape[:-1], dtype=e.dtype), np.zeros(e.shape[:-1], dtype=e.dtype)
+    for c in range(e.shape[-1]):
+        f = np.floor(e[..., c])
+        rest, nt = rest + (e[..., c] - f), nt + f
+    return rest + (nt - 1)
+
+
+def log_s(rest, s):
+    """log s = log1p(rest) for s = 1 + rest as the kernels form it (sm_log_s): log(s) plus what the rounding of s dropped,
+    d = rest - (s - 1), times 2 - s for 1 / s below s = 2 and nothing from there on; log(s) alone is 0 where rest < eps / 2"""
+    d = rest - (s - 1)
+    return np.log(s) + np.where(s < 2, d * (2 - s), 0 * d)
+
+
 def score_and_lp(A, y, C, counts, lam, X, dtype=np.float64):
     """A (K, N, P), y (K, N) integers, C classes, counts (K,) or None, lam a number or (K,), X (K, rows, (C - 1) P) ->
     G (K, rows, D), lp (K, rows) in ``dtype`` (float64 or np.longdouble); a per-problem loop with the kernel's NaN rule."""
@@ -62,14 +80,13 @@ def score_and_lp(A, y, C, counts, lam, X, dtype=np.float64):
             eta = np.concatenate([np.einsum("np,rcp->rnc", Ak, W), np.zeros((rows, n, 1), dtype=dtype)], axis=2)    # (rows, n, C)
             m = eta.max(axis=2, keepdims=True) if n else eta[:, :, :1]
             e = np.exp(eta - m)
-            s = np.zeros((rows, n), dtype=dtype)
-            for c in range(C):                                          # class order; the reference class last
-                s = s + e[:, :, c]
+            rest = s_minus_one(e)
+            s = 1 + rest
             hot = (yk[:, None] == np.arange(C)[None, :]).astype(dtype)  # (n, C)
             etay = (eta * hot[None]).sum(axis=2)
             r = hot[None, :, :C - 1] - e[:, :, :C - 1] / s[:, :, None]
             G[k] = np.einsum("rnc,np->rcp", r, Ak).reshape(rows, D) - lam[k] * X[k]
-            lp[k] = (etay - m[:, :, 0] - np.log(s)).sum(axis=1) - 0.5 * lam[k] * (X[k] * X[k]).sum(axis=1)
+            lp[k] = (etay - m[:, :, 0] - log_s(rest, s)).sum(axis=1) - 0.5 * lam[k] * (X[k] * X[k]).sum(axis=1)
         bad = ~np.isfinite(X[k]).all(axis=1) | ~np.isfinite(eta).all(axis=(1, 2))
         G[k, bad] = np.nan
         lp[k, bad] = np.nan

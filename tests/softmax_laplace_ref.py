@@ -40,7 +40,7 @@ def problem(A, y, C, counts, lam, k):
 
 
 def probabilities(A, x, C):
-    """eta (n, C), m, s, p and the accurate 1 - p (n, C) in the kernel's forms, in the dtype of A and x"""
+    """eta (n, C), m, s_rest, p and the accurate 1 - p (n, C) in the kernel's forms, in the dtype of A and x"""
     n, P = A.shape
     dt = np.result_type(A.dtype, x.dtype)
     eta = np.concatenate([A @ x.reshape(C - 1, P).T, np.zeros((n, 1), dtype=dt)], axis=1)
@@ -56,7 +56,7 @@ def probabilities(A, x, C):
     p = e / s[:, None]
     q = (s[:, None] - e) / s[:, None]
     q[rows, cs] = rest / s
-    return eta, m, s, p, q
+    return eta, m, rest, p, q
 
 
 def evaluate(p, x):
@@ -69,9 +69,9 @@ def evaluate(p, x):
     Cm = C - 1
     D = Cm * P
     with np.errstate(all="ignore"):
-        eta, m, s, pr, q = probabilities(A, x, C)
+        eta, m, rest, pr, q = probabilities(A, x, C)
         hot = y[:, None] == np.arange(C)[None, :]
-        t = (eta * hot).sum(axis=1) - m - np.log(s)
+        t = (eta * hot).sum(axis=1) - m - sref.log_s(rest, 1 + rest)    # (log(s) is 0 where s_rest < eps / 2)
         r = np.where(hot, q, -pr)[:, :Cm]
         f = -(t.sum() - 0.5 * lam * (x * x).sum())
         g = -((r.T @ A).reshape(D) - lam * x)

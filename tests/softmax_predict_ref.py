@@ -21,6 +21,7 @@ import numpy as np
 
 import psis_loo_ref as lref
 import psis_loo_softmax_ref as sref
+import softmax_batched_ref as bref
 from psis_loo_ref import LD, valid_rows      # noqa: F401
 from psis_loo_softmax_ref import draw_labels, loglik_softmax      # noqa: F401
 
@@ -83,10 +84,9 @@ def predict(A, labels, C, counts, X, lw, dtype=LD):
             dots = np.einsum("np,scp->nsc", A[k, :n].astype(dtype), W)                    # (n, S, C - 1)
             eta = np.concatenate([dots, np.zeros((n, S, 1), dtype=dtype)], axis=2)
             m = eta.max(axis=2)
-            z = np.zeros((n, S), dtype=dtype)
-            for c in range(C):                                                            # class order; the reference class last
-                z = z + np.exp(eta[:, :, c] - m)
-            p = np.exp(eta - m[:, :, None]) / z[:, :, None]
+            e = np.exp(eta - m[:, :, None])
+            z = 1 + bref.s_minus_one(e)                                                   # class order; the reference class last
+            p = e / z[:, :, None]
             pr = np.einsum("s,nsc->nc", w, p)
             bad = (~np.isfinite(dots).all(axis=2) | ~np.isfinite(X[k]).all(axis=1)[None, :]).any(axis=1)      # (n,) rows
             prob[k, :n] = np.where(bad[:, None], nan, pr)
