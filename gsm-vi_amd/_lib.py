@@ -139,6 +139,12 @@ _SIGS = {
     "gsmvi_laplace_step_batched_f64": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int64, C.c_int, _c_dp, _c_dp, _c_dp,
                                                  _c_dp, C.c_double, _c_dp, C.c_double, _c_dp, C.c_int, _c_dp, _c_dp, _c_dp, _c_dp,
                                                  _c_dp, _c_dp, _c_dp, C.c_int, C.c_int, C.c_double]),
+    "gsmvi_glm_shared_hessian_batched_f64": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int64, C.c_int, _c_dp, _c_dp,
+                                                       _c_dp, _c_dp, C.c_double, _c_dp, C.c_double, _c_dp, _c_dp, _c_dp, _c_dp,
+                                                       _c_dp]),
+    "gsmvi_laplace_shared_step_batched_f64": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int64, C.c_int, _c_dp, _c_dp,
+                                                        _c_dp, _c_dp, C.c_double, _c_dp, C.c_double, _c_dp, C.c_int, _c_dp, _c_dp,
+                                                        _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, C.c_int, C.c_int, C.c_double]),
     "gsmvi_softmax_hessian_batched_f64": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int64, _c_dp, _c_dp, _c_dp,
                                                     C.c_double, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp]),
     "gsmvi_softmax_laplace_step_batched_f64": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int64, _c_dp, _c_dp,

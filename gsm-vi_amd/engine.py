@@ -1129,6 +1129,53 @@ class HipEngine:
                    self._ist(state, K), self._packed(state["Xt"], (K, D), "Xt"), self._ints(stopped, 1, "stopped"),
                    int(maxiter), int(maxfun), float(gtol))
 
+    # ---- shared-design Laplace initialiser: the same for K GLMs on one design matrix (csrc/gsmvi_laplace_shared_batched.hip) -----
+    def _glm_shared_model_args(self, K, A, y, family, offset, weights, prior_prec, noise_prec):
+        """the model's arguments of the two shared-design Laplace entry points, in the order of include/gsmvi_hip.h"""
+        N, D = A.shape
+        fam, t, tp = self._glm_family_args(family, noise_prec, K)
+        r, rp = self._reg_arg(prior_prec, K)
+        return (K, D, N, fam, self._packed(A, (N, D), "A"), self._packed(y, (K, N), "y"), self._dp(offset, (K, N), "offset"),
+                self._dp(weights, (K, N), "weights"), t, tp, r, rp)
+
+    def glm_shared_hessian_batched(self, X, A, y, family, offset=None, weights=None, prior_prec=1.0, noise_prec=1.0, want="h",
+                                   out=None, cov_out=None, info_out=None):
+        """The negative Hessian H_k = A^T diag(v_k w_k) A + lam_k I of lp_k of K GLMs that share ONE design matrix, at the rows
+        of X (K, D), and / or its inverse, one launch (the Gram product on the fp64 MFMA, one staged tile of A per workgroup)
+        [no reference twin; the model of examples/example_gsm.py:34-35]: ``want`` = "h" -> H (K, D, D), "cov" -> (cov, info),
+        "both" -> (H, cov, info); ``info`` (K,) int32: 0, or 1 + the first failing pivot, and then cov_k = I.  The other
+        arguments are ``glm_shared_batched``'s."""
+        self._check_want(want, "h", "cov")
+        X = X.contiguous()
+        K, D = X.shape
+        self._any_ctx()
+        H = cov = info = None
+        if want != "cov":
+            H = self.empty(K, D, D) if out is None else out
+        if want != "h":
+            cov = self.empty(K, D, D) if cov_out is None else cov_out
+            info = torch.zeros(K, dtype=torch.int32, device=self.device) if info_out is None else info_out
+        self._call("gsmvi_glm_shared_hessian_batched_f64",
+                   *self._glm_shared_model_args(K, A, y, family, offset, weights, prior_prec, noise_prec),
+                   self._packed(X, (K, D), "X"), self._dp(H, (K, D, D), "out"), self._dp(cov, (K, D, D), "cov_out"),
+                   self._ints(info, K, "info_out"))
+        return H if want == "h" else (cov, info) if want == "cov" else (H, cov, info)
+
+    def laplace_shared_step_batched(self, state, A, y, family, offset=None, weights=None, prior_prec=1.0, noise_prec=1.0,
+                                    start=False, maxiter=100, maxfun=200, gtol=1e-8):
+        """One damped Newton round of every running problem of ``state`` (``laplace_state_batched``) for K GLMs that share ONE
+        design matrix (csrc/gsmvi_laplace_shared_batched.hip): f, g and H at ``state["Xt"]`` in one sweep over A, then the round
+        of ``laplace_step_batched``, the same state machine  [the role of gsmvi/initializers.py:5-17]"""
+        K, D = state["x"].shape
+        self._any_ctx()
+        stopped = state.get("stopped")
+        self._call("gsmvi_laplace_shared_step_batched_f64",
+                   *self._glm_shared_model_args(K, A, y, family, offset, weights, prior_prec, noise_prec), int(bool(start)),
+                   self._packed(state["x"], (K, D), "x"), self._packed(state["g"], (K, D), "g"),
+                   self._packed(state["d"], (K, D), "d"), self._packed(state["sc"], (K, 4), "sc"),
+                   self._ist(state, K), self._packed(state["Xt"], (K, D), "Xt"), self._ints(stopped, 1, "stopped"),
+                   int(maxiter), int(maxfun), float(gtol))
+
     # ---- batched GLM posterior predictive: the use of K fitted Gaussians (csrc/gsmvi_glm_predict_batched.hip) -----------------
     @staticmethod
     def gauss_hermite(Q):

@@ -17,8 +17,9 @@ Pathfinder; csrc/gsmvi_pathfinder_batched.hip).  Any target with ``lp`` and ``lp
 ``laplace_init_batched`` is the second-order start for the built-in GLM targets (``BatchedGLMTarget``,
 ``BatchedLogisticTarget``): a damped Newton (IRLS) iteration in HIP (csrc/gsmvi_laplace_batched.hip), one launch per round, and
 the Laplace covariance (A^T W A + lam I)^-1 at the mode.  ``laplace_init_softmax_batched`` is the same start for
-``BatchedSoftmaxTarget``, on the class-coupled Hessian of the multinomial logit (csrc/gsmvi_softmax_laplace_batched.hip); the two
-share one host loop.
+``BatchedSoftmaxTarget``, on the class-coupled Hessian of the multinomial logit (csrc/gsmvi_softmax_laplace_batched.hip), and
+``laplace_init_shared_batched`` for ``SharedDesignGLMTarget``, K problems with observation weights on one design matrix that is
+never replicated (csrc/gsmvi_laplace_shared_batched.hip); the three share one host loop.
 """
 from dataclasses import dataclass
 
@@ -302,10 +303,11 @@ def laplace_init_batched(target, x0=None, maxiter=100, maxfun=200, *, gtol=1e-8,
     it reads the device's count of stopped problems every ``check_every`` rounds and leaves when it equals K, so the result
     does not depend on ``check_every``; only ``res.nlaunch`` does.  One more launch gives the covariance at the final points.
     Prints nothing."""
-    from .targets import BatchedGLMTarget
+    from .targets import BatchedGLMTarget, SharedDesignGLMTarget
     if not isinstance(target, BatchedGLMTarget):
+        hint = "; call laplace_init_shared_batched(target, ...) for it" if isinstance(target, SharedDesignGLMTarget) else ""
         raise TypeError(f"laplace_init_batched: target must be a BatchedGLMTarget or a BatchedLogisticTarget, "
-                        f"got {type(target).__name__}")
+                        f"got {type(target).__name__}{hint}")
     model = dict(offset=target.offset, counts=target.counts, prior_prec=target.prior_precision,
                  noise_prec=target.noise_precision)
     eng = engine if engine is not None else target.engine
@@ -376,3 +378,34 @@ def laplace_init_softmax_batched(target, x0=None, maxiter=100, maxfun=200, *, gt
     return _laplace_run("laplace_init_softmax_batched", target, x0, maxiter, maxfun, gtol, check_every, as_torch, eng,
                         lambda st, **kw: eng.softmax_laplace_step_batched(st, target.A, target.y, target.C, **kw, **model),
                         lambda x: eng.softmax_hessian_batched(x, target.A, target.y, target.C, want="cov", **model))
+
+
+def laplace_init_shared_batched(target, x0=None, maxiter=100, maxfun=200, *, gtol=1e-8, check_every=4, as_torch=False, engine=None):
+    """The Laplace start of K GLM posteriors on ONE design matrix at once: returns ``(mean (K, D), cov (K, D, D), res)``, the
+    Newton modes of ``lp_k``, the inverses of the negative Hessians A^T diag(v_k w_k) A + lam_k I there
+    (``neg_hessian_shared_batched``) and a ``LaplaceBatchedResult``.  It fills the role of ``lbfgs_init``
+    (gsmvi/initializers.py:5-17) for the shared-design target: responses, offsets, observation weights and precisions per
+    problem, the design held once and never replicated.
+
+    ``target``: a ``SharedDesignGLMTarget`` (anything else: TypeError).  Weights >= 0 keep all four families log-concave, and
+    everything else -- ``x0``, the damped Newton iteration and its line search, the stopping rule, ``check_every``, one launch
+    per round (csrc/gsmvi_laplace_shared_batched.hip), the frozen problems, the failure policy (a problem without success
+    returns its last ``x`` and the identity) and the defaults -- is ``laplace_init_batched``'s, word for word.  A problem whose
+    weights are all zero is its prior: with lam_k > 0 it converges at once at x = 0 with cov = I / lam_k; with lam_k = 0 both its
+    gradient and its Hessian are zero.  One thing is this function's own: a problem that the launches stopped by the gradient
+    test (the device's status word 1: that test comes before the factorisation) but whose Hessian at that point fails the
+    final factorisation (``info`` != 0) is reported with ``res.status`` 5, Hessian not positive definite, not 1: a stationary
+    point without a positive definite Hessian is no mode to expand around.  It has no ``success`` and gets the identity, as
+    before; the all-zero-weights problem with lam_k = 0 is the plain case (``status`` 5, ``info`` 1).  Prints nothing."""
+    from .targets import SharedDesignGLMTarget
+    if not isinstance(target, SharedDesignGLMTarget):
+        raise TypeError(f"laplace_init_shared_batched: target must be a SharedDesignGLMTarget, got {type(target).__name__}")
+    model = dict(offset=target.offset, weights=target.weights, prior_prec=target.prior_precision,
+                 noise_prec=target.noise_precision)
+    eng = engine if engine is not None else target.engine
+    mean, cov, res = _laplace_run(
+        "laplace_init_shared_batched", target, x0, maxiter, maxfun, gtol, check_every, as_torch, eng,
+        lambda st, **kw: eng.laplace_shared_step_batched(st, target.A, target.y, target.family, **kw, **model),
+        lambda x: eng.glm_shared_hessian_batched(x, target.A, target.y, target.family, want="cov", **model))
+    res.status = np.where((res.status == 1) & (res.info != 0), 5, res.status)     # stationary, but H is not positive definite
+    return mean, cov, res

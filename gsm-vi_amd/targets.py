@@ -15,8 +15,11 @@ multinomial logit regressions (C classes, C - 1 linear predictors per row), a la
     BatchedGaussianTarget     (a Gaussian density)            gsmvi_gaussian_score_batched_f64   no
     BatchedLogisticTarget     y in [0, 1]                     gsmvi_logistic_batched_f64         yes
     BatchedGLMTarget          poisson, probit, gaussian, ...  gsmvi_glm_batched_f64              yes
-    SharedDesignGLMTarget     the same four, ONE A (N, D),    gsmvi_glm_shared_batched_f64       no (not a BatchedGLMTarget: the
-                              observation weights                                                isinstance checks refuse it)
+    SharedDesignGLMTarget     the same four, ONE A (N, D),    gsmvi_glm_shared_batched_f64       laplace_init_shared_batched and
+                              observation weights                                                neg_hessian_shared_batched (free
+                                                                                                 functions); predict, loo: no (not a
+                                                                                                 BatchedGLMTarget: the isinstance
+                                                                                                 checks refuse it)
     BatchedNegBinomialTarget  counts y >= 0, a fitted size    gsmvi_negbin_batched_f64           no (not a BatchedGLMTarget: the Hessian
                               (x = (beta, log r))                                                has a 2 x 2 block per row)
     BatchedSoftmaxTarget      integer labels in 0 .. C - 1    gsmvi_softmax_batched_f64          laplace_init_softmax_batched and
@@ -432,7 +435,8 @@ class SharedDesignGLMTarget:
     ``lp_g(x, out=None)``: (K, B, D) -> (K, B, D) scores, ``device_native`` and ``graph_safe`` (one capturable launch, no
     allocation with ``out``).  ``lp(x)``: (K, rows, D) -> (K, rows) values.  ``lp_and_score(x)``: (scores, values) from one launch.
     Not a ``BatchedGLMTarget``: it has no ``neg_hessian``, ``predict`` or ``loo``, and ``laplace_init_batched``,
-    ``psis_loo_batched`` refuse it."""
+    ``psis_loo_batched`` refuse it.  Its negative Hessian is ``neg_hessian_shared_batched(target, x)`` and its second-order start
+    ``laplace_init_shared_batched(target, ...)``, both on the shared design without a copy per problem."""
 
     FAMILIES = BatchedGLMTarget.FAMILIES
 
@@ -484,6 +488,23 @@ class SharedDesignGLMTarget:
     def lp_and_score(self, x):
         """(scores (K, rows, D), values (K, rows)) from one launch"""
         return self._call(self.engine.asarray(x), want="both")
+
+
+def neg_hessian_shared_batched(target, x, *, engine=None):
+    """(K, D, D) negative Hessians A^T diag(v_k w_k) A + lam_k I of lp_k of a ``SharedDesignGLMTarget`` at the rows of x (K, D):
+    w = -dr / d eta of the family (the table of ``BatchedGLMTarget.neg_hessian``), v_k the observation weights; an observation
+    whose weight is 0 contributes exactly nothing, whatever its y and offset hold.  Exactly symmetric; a device tensor or numpy
+    in; one launch (gsmvi_glm_shared_hessian_batched_f64), no copy of the design per problem.  Anything that is not a
+    ``SharedDesignGLMTarget`` raises TypeError."""
+    if not isinstance(target, SharedDesignGLMTarget):
+        raise TypeError(f"neg_hessian_shared_batched: target must be a SharedDesignGLMTarget, got {type(target).__name__}")
+    K, D = target.K, target.D
+    if _shape(x) != (K, D):
+        raise ValueError(f"neg_hessian_shared_batched: x must be (K, D) = {(K, D)} of the target, got {_shape(x)}")
+    eng = engine if engine is not None else target.engine
+    return eng.glm_shared_hessian_batched(eng.asarray(x), target.A, target.y, target.family, offset=target.offset,
+                                          weights=target.weights, prior_prec=target.prior_precision,
+                                          noise_prec=target.noise_precision, want="h")
 
 
 def _check_finite_per_problem(x, name, K):

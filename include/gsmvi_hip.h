@@ -26,7 +26,8 @@
  *   examples/example_gsm.py:34-35 the same for K multinomial logit (softmax) regressions of C classes -> gsmvi_softmax_batched_f64
  *   initializers.py:5-17 lbfgs_init (maximiser of lp, dense inverse-Hessian estimate), K problems -> gsmvi_lbfgs_step_batched_f64, gsmvi_lbfgs_hess_inv_batched_f64
  *   initializers.py:5-17 the same role by Newton rounds on the GLMs of examples/example_gsm.py:34-35 (no reference twin) -> gsmvi_glm_hessian_batched_f64, gsmvi_laplace_step_batched_f64,
- *   gsmvi_softmax_hessian_batched_f64, gsmvi_softmax_laplace_step_batched_f64 (the multinomial logit)
+ *   gsmvi_softmax_hessian_batched_f64, gsmvi_softmax_laplace_step_batched_f64 (the multinomial logit),
+ *   gsmvi_glm_shared_hessian_batched_f64, gsmvi_laplace_shared_step_batched_f64 (the GLMs on one design matrix)
  *   initializers.py:5-17 the same role with a start picked by its ELBO along the L-BFGS path (Pathfinder; no reference twin) -> gsmvi_pathfinder_propose_batched_f64, gsmvi_pathfinder_select_batched_f64
  *   examples/example_gsm.py:34-35 the use of the fit: predictions and the held-out score of K fitted GLMs (no reference twin) -> gsmvi_glm_predict_batched_f64
  *   monitors.py:83-125 the role (is q_k close to its target?), per problem and comparable across problems: the Pareto-smoothed
@@ -307,9 +308,9 @@ int gsmvi_get_profile(gsmvi_ctx* ctx, float* ms, int n);
 #define GSMVI_PATH_BATCHED_BAM 0x4000u     /* k_bam_batched: the batched BaM entry points                           */
 #define GSMVI_PATH_BATCHED_KL 0x8000u      /* k_kl_batched: the batched KL monitor's entry points                  */
 #define GSMVI_PATH_BATCHED_ADVI 0x10000u   /* k_advi_batched / k_advi_cov_batched: the batched ADVI entry points   */
-#define GSMVI_PATH_BATCHED_TARGET 0x20000u /* k_logistic_batched: the batched non-Gaussian target's entry point     */
+#define GSMVI_PATH_BATCHED_TARGET 0x20000u /* k_logistic_batched: the batched non-Gaussian target's entry point; with GSMVI_PATH_BATCHED_LAPLACE in one call: k_laplace_shared_batched (all 32 bits are taken; no other call sets that pair) */
 #define GSMVI_PATH_BATCHED_LBFGS 0x40000u  /* k_lbfgs_step_batched / k_lbfgs_hess_inv_batched: the batched initialiser   */
-#define GSMVI_PATH_BATCHED_LAPLACE 0x80000u /* k_laplace_batched: the batched GLM Hessian and Newton step             */
+#define GSMVI_PATH_BATCHED_LAPLACE 0x80000u /* k_laplace_batched: the batched GLM Hessian and Newton step; with GSMVI_PATH_BATCHED_TARGET in one call: k_laplace_shared_batched, the shared-design Hessian and Newton step */
 #define GSMVI_PATH_BATCHED_PREDICT 0x100000u /* k_glm_predict_batched: the batched GLM posterior predictive; with GSMVI_PATH_BATCHED_SOFTMAX: k_softmax_predict_batched */
 #define GSMVI_PATH_BATCHED_PSIS 0x200000u /* k_psis_batched: the batched Pareto-smoothed importance diagnostic            */
 #define GSMVI_PATH_BATCHED_LOO 0x400000u /* k_psis_loo_batched: the batched PSIS leave-one-out; with GSMVI_PATH_BATCHED_SOFTMAX: k_psis_loo_softmax_batched */
@@ -796,6 +797,49 @@ int gsmvi_softmax_laplace_step_batched_f64(gsmvi_ctx* ctx, void* stream, int64_t
                                            const int* labels, const int* counts_dev, double prior_prec,
                                            const double* prior_prec_dev, int start, double* x, double* g, double* d, double* sc,
                                            int* ist, double* Xt, int* stopped_dev, int maxiter, int maxfun, double gtol);
+
+/*
+ * Shared-design Laplace initialiser: the Newton mode of K GLM posteriors over ONE design matrix and the inverse of the negative
+ * Hessian there as the covariance: the two entry points above for the model of gsmvi_glm_shared_batched_f64 (the role of
+ * gsmvi/initializers.py:5-17 for the models of examples/example_gsm.py:34-35; no reference twin).  A is (N x D), shared; y, offset
+ * (NULL = none) and weights (NULL = 1 everywhere) are (K x N); weights v_kn >= 0 are observation weights.  With eta_n = a_n . x +
+ * o_kn, the link (r, t) of gsmvi_glm_batched_f64 and the weight w = -dr / d eta of gsmvi_glm_hessian_batched_f64:
+ *   f_k(x) = -( sum_n v_kn t(eta_n, y_kn) - lam_k |x|^2 / 2 )       g_k(x) = -( sum_n v_kn r(eta_n, y_kn) a_n - lam_k x )
+ *   H_k(x) =    sum_n v_kn w(eta_n, y_kn) a_n a_n^T + lam_k I       positive semi-definite, since v >= 0.
+ * An observation whose weight is not > 0 is removed by selection, not by a product with zero: it contributes exactly nothing to f,
+ * g and H whatever y, offset and eta hold there (a NaN y, an infinite offset, an e^eta that overflows) and flags nothing.  A is
+ * never replicated: one tile of 32 rows of A is staged in LDS per workgroup and serves every problem of that workgroup (four for
+ * D <= 16, one above), and nothing of size K N D exists anywhere.  Every sum over n runs n = 0 .. N - 1 in tiles of 32, the Gram
+ * product on the fp64 MFMA, in an order fixed by (N, D) alone: a problem's bits depend on its own data only, not on K, its
+ * position or its neighbours.  The bounds of gsmvi_glm_shared_batched_f64 at nc = 1 hold (1 <= D <= 64, any N >= 1, K within the
+ * packing of gsmvi_glm_hessian_batched_f64), noise_prec is the gaussian family's alone.
+ *
+ * gsmvi_glm_shared_hessian_batched_f64: H (K x D x D, or NULL), cov (K x D x D, or NULL) and info_dev (K ints, required with cov and
+ * only with it) as gsmvi_glm_hessian_batched_f64 gives them, at the rows x_k of X (K x D): H exactly symmetric, the pivot rule
+ * 64 eps H_jj, cov_k = I where the factorisation fails.  A non-finite x_k, or (poisson) an e^eta that is not finite at an
+ * observation with v > 0, gives H_k = NaN, info[k] = 1, cov_k = I, and no other problem is touched; a non-finite entry of A
+ * reaches every problem.  At least one of H, cov is given.
+ *
+ * gsmvi_laplace_shared_step_batched_f64: one launch is one damped Newton round of phi_k = f_k for every running problem: the state
+ * (x, g, d, Xt (K x D), sc (K x 4), ist (K x 8)), the status codes 1 - 5, the Armijo test with its slack 1e-10 max(1, |f|), the
+ * halving, the 20 rejections, *stopped_dev and the meaning of start, maxiter, maxfun and gtol are those documented for
+ * gsmvi_laplace_step_batched_f64, word for word; a flagged trial point is status 4 at the start and a rejected trial later.  A
+ * problem whose status is not 0 is frozen: nothing of it is written and nothing of y, offset or weights is loaded for it; a
+ * workgroup all of whose problems are frozen leaves after reading the status words.
+ * Both: shapes, NULL arrays and overlaps (only the written arrays may not overlap anything) are checked before the context is
+ * looked at (then a NULL ctx); every failure returns GSMVI_ERR_BAD_ARG before anything is enqueued.  Inputs are only read; no
+ * context workspace is used; at most 64 KB of dynamic LDS (no kernel attribute).  Both set GSMVI_PATH_BATCHED_LAPLACE |
+ * GSMVI_PATH_BATCHED_TARGET: no other call sets that pair, so gsmvi_last_path still proves which kernel ran.
+ */
+int gsmvi_glm_shared_hessian_batched_f64(gsmvi_ctx* ctx, void* stream, int64_t K, int D, int64_t N, int family, const double* A,
+                                         const double* y, const double* offset, const double* weights, double noise_prec,
+                                         const double* noise_prec_dev, double prior_prec, const double* prior_prec_dev,
+                                         const double* X, double* H, double* cov, int* info_dev);
+int gsmvi_laplace_shared_step_batched_f64(gsmvi_ctx* ctx, void* stream, int64_t K, int D, int64_t N, int family, const double* A,
+                                          const double* y, const double* offset, const double* weights, double noise_prec,
+                                          const double* noise_prec_dev, double prior_prec, const double* prior_prec_dev, int start,
+                                          double* x, double* g, double* d, double* sc, int* ist, double* Xt, int* stopped_dev,
+                                          int maxiter, int maxfun, double gtol);
 
 /*
  * Batched GLM posterior predictive: what a fitted q_k = N(mean_k, cov_k) over the coefficients of K GLMs of one D says about M new
