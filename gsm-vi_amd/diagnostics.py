@@ -6,7 +6,8 @@ effective sample size, an estimate of the log normalising constant, and importan
 the same draws one step further for the GLM targets: the PSIS leave-one-out log predictive density of every observation
 (csrc/gsmvi_psis_loo_batched.hip; Vehtari, Gelman, Gabry 2017; Magnusson, Andersen, Jonasson, Vehtari 2019), the number by which
 fitted models are compared; ``psis_loo_softmax_batched`` is the same for ``BatchedSoftmaxTarget``
-(csrc/gsmvi_psis_loo_softmax_batched.hip)."""
+(csrc/gsmvi_psis_loo_softmax_batched.hip) and ``psis_loo_negbin_batched`` for ``BatchedNegBinomialTarget``
+(csrc/gsmvi_psis_loo_negbin_batched.hip)."""
 from dataclasses import dataclass
 
 import numpy as np
@@ -176,8 +177,8 @@ def _reusable(psis, K, D, eng, fn="psis_loo_batched"):
 
 
 def _loo_result(eng, target, psis, S, nlaunch, as_torch, elpd_i, lpd_i, khat, ess, info, loglik):
-    """The ``LOOBatchedResult`` of the pointwise outputs of a leave-one-out launch (``psis_loo_batched`` and
-    ``psis_loo_softmax_batched``): the per-problem summaries are torch reductions under the mask of the valid rows of
+    """The ``LOOBatchedResult`` of the pointwise outputs of a leave-one-out launch (``psis_loo_batched``,
+    ``psis_loo_softmax_batched`` and ``psis_loo_negbin_batched``): the per-problem summaries are torch reductions under the mask of the valid rows of
     ``target.counts`` (a stand-in engine's numpy arrays: on the host)"""
     import torch
     K, N = target.K, target.N
@@ -204,7 +205,7 @@ def _loo_result(eng, target, psis, S, nlaunch, as_torch, elpd_i, lpd_i, khat, es
 
 
 def _loo_draws(fn, target, mean, cov, keys, num_draws, call, psis, engine):
-    """The argument checks and the problem-level run shared by the two leave-one-out functions: (eng, psis, nlaunch, X, logr, lw)"""
+    """The argument checks and the problem-level run shared by the three leave-one-out functions: (eng, psis, nlaunch, X, logr, lw)"""
     K, D = target.K, target.D
     if _shape(mean) != (K, D):
         raise ValueError(f"{fn}: mean must be (K, D) = {(K, D)} of the target, got {_shape(mean)}")
@@ -279,4 +280,35 @@ def psis_loo_softmax_batched(target, mean, cov, keys, num_draws=1024, *, call=0,
     S = _shape(X)[1]
     elpd_i, lpd_i, khat, ess, info, loglik = eng.psis_loo_softmax_batched(
         X, logr, lw, target.A, target.y, target.C, counts=target.counts, pointwise_loglik=bool(pointwise_loglik))
+    return _loo_result(eng, target, psis, S, nlaunch, as_torch, elpd_i, lpd_i, khat, ess, info, loglik)
+
+
+def psis_loo_negbin_batched(target, mean, cov, keys, num_draws=1024, *, call=0, psis=None, pointwise_loglik=False, as_torch=False,
+                            engine=None):
+    """PSIS leave-one-out of K fitted negative binomial posteriors q_k = N(mean_k, cov_k) over (beta, log size): returns a
+    ``LOOBatchedResult``, the twin of ``psis_loo_batched`` for the likelihood whose draws carry a shape parameter.
+
+    ``target`` is the ``BatchedNegBinomialTarget`` the posteriors were fitted to (its A, y, offset and counts are the model;
+    anything else raises TypeError); mean (K, D), D = P + 1, cov (K, D, D) and ``keys`` are ``psis_batched``'s.  Without ``psis``
+    it first runs ``psis_batched(target.lp, mean, cov, keys, num_draws, call=call, moments=False, as_torch=True)`` (two launches
+    and one call of ``target.lp``); with ``psis``, the result of such a call, its draws, ratios and weights are reused
+    (``num_draws`` and ``call`` are then not used).  Then one launch, gsmvi_psis_loo_negbin_batched_f64: the linear predictors of
+    every draw on the fp64 MFMA, the pointwise log likelihood l_si = t(eta_si, theta_s, y_i) - lgamma(y_i + 1) through the
+    target's own link, and per observation the PSIS stage on the ratios logr_s - l_si and the two log-sum-exps (the definition is
+    in include/gsmvi_hip.h).  The term -lgamma(y + 1), which ``target.lp`` drops, is INCLUDED: l_si is the normalised log
+    probability of the count, as in ``psis_loo_batched`` of a poisson ``BatchedGLMTarget``, so ``elpd_loo`` of the two models are
+    on one scale and their difference says whether the shape parameter earns its place.  No (K, N, S) block of log likelihoods is
+    formed unless ``pointwise_loglik`` asks for it (K * N * S * 8 bytes).  The per-problem sums are those of
+    ``psis_loo_batched``.  mean and cov are only read.
+    A mean that is not (K, D) of the target, a cov that is not (K, D, D), ``num_draws`` outside 5..4096, keys of another length
+    than K, or a ``psis`` that is not a ``PSISBatchedResult`` holding device tensors of the right shapes raise ValueError before
+    any device work."""
+    from .targets import BatchedNegBinomialTarget
+    fn = "psis_loo_negbin_batched"
+    if not isinstance(target, BatchedNegBinomialTarget):
+        raise TypeError(f"{fn}: target must be a BatchedNegBinomialTarget, got {type(target).__name__}")
+    eng, psis, nlaunch, X, logr, lw = _loo_draws(fn, target, mean, cov, keys, num_draws, call, psis, engine)
+    S = _shape(X)[1]
+    elpd_i, lpd_i, khat, ess, info, loglik = eng.psis_loo_negbin_batched(
+        X, logr, lw, target.A, target.y, offset=target.offset, counts=target.counts, pointwise_loglik=bool(pointwise_loglik))
     return _loo_result(eng, target, psis, S, nlaunch, as_torch, elpd_i, lpd_i, khat, ess, info, loglik)

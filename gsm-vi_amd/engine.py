@@ -1301,6 +1301,35 @@ class HipEngine:
                    self._packed(ess, (K, N), "ess"), self._ints(info, K * N, "info"))
         return elpd, lpd, khat, ess, info, loglik
 
+    # ---- the same for K fitted negative binomial posteriors (csrc/gsmvi_psis_loo_negbin_batched.hip) ---------------------------
+    def psis_loo_negbin_tile(self, P, S):
+        """gsmvi_psis_loo_negbin_tile: the observations one workgroup of ``psis_loo_negbin_batched`` takes at (P, S); a pure
+        function, no GPU"""
+        return int(self.lib.gsmvi_psis_loo_negbin_tile(int(P), int(S)))
+
+    def psis_loo_negbin_batched(self, X, logr, lw, A, y, offset=None, counts=None, pointwise_loglik=False):
+        """PSIS leave-one-out of K fitted negative binomial posteriors from the draws X (K, S, P + 1) = (beta, theta) of q_k, theta
+        the log of the size, and the problem-level ratios ``logr`` and smoothed weights ``lw`` (K, S) of ``psis_batched`` on the
+        same draws, one launch (gsmvi_psis_loo_negbin_batched_f64; the definition is in include/gsmvi_hip.h)  [no reference twin]:
+        returns what ``psis_loo_batched`` returns, (elpd, lpd, khat, ess (K, N), info (K, N) int32, loglik (K, N, S) or None).  The
+        pointwise log likelihood includes -lgamma(y + 1), as the poisson family of ``psis_loo_batched`` does: the two elpd are on
+        one scale.  ``A`` (K, N, P), ``y`` (K, N), ``offset`` and ``counts`` are ``negbin_batched``'s."""
+        K, S, D = X.shape
+        N, P = A.shape[1], A.shape[2]
+        if D != P + 1:
+            raise ValueError(f"X: expected P + 1 = {P + 1} columns (beta, then the log size), got {D}")
+        self._any_ctx()
+        X, logr, lw = X.contiguous(), logr.contiguous(), lw.contiguous()
+        elpd, lpd, khat, ess = self.empty(K, N), self.empty(K, N), self.empty(K, N), self.empty(K, N)
+        info = self.batched_ints(K * N).view(K, N)
+        loglik = self.empty(K, N, S) if pointwise_loglik else None
+        self._call("gsmvi_psis_loo_negbin_batched_f64", K, P, N, S, self._packed(A, (K, N, P), "A"), self._packed(y, (K, N), "y"),
+                   self._dp(offset, (K, N), "offset"), self._ints(counts, K, "counts"), self._packed(X, (K, S, D), "X"),
+                   self._packed(logr, (K, S), "logr"), self._packed(lw, (K, S), "lw"), self._dp(loglik, (K, N, S), "loglik"),
+                   self._packed(elpd, (K, N), "elpd"), self._packed(lpd, (K, N), "lpd"), self._packed(khat, (K, N), "khat"),
+                   self._packed(ess, (K, N), "ess"), self._ints(info, K * N, "info"))
+        return elpd, lpd, khat, ess, info, loglik
+
     # ---- batched softmax posterior predictive: the use of K fitted multinomial logit posteriors (csrc/gsmvi_softmax_predict_batched.hip)
     def softmax_predict_lds_bytes(self, C, P):
         """gsmvi_softmax_predict_lds_bytes: the dynamic LDS in bytes of one workgroup of ``softmax_predict_batched`` at (C, P), 0

@@ -543,7 +543,9 @@ class BatchedNegBinomialTarget:
     allocation with ``out``).  ``lp(x)``: (K, rows, D) -> (K, rows) values; a device tensor or numpy.  ``lp_and_score(x)``:
     (scores, values) from one launch.  Attributes ``K, N, P, D``.  Not a ``BatchedGLMTarget``: its Hessian is not A^T W A (every
     row contributes a 2 x 2 block in (eta, theta)), so it has no ``neg_hessian``, ``predict`` or ``loo``, and
-    ``laplace_init_batched`` and ``psis_loo_batched`` refuse it (TypeError)."""
+    ``laplace_init_batched`` and ``psis_loo_batched`` refuse it (TypeError).  Its leave-one-out is the function
+    ``psis_loo_negbin_batched(target, mean, cov, keys, ...)``, which includes the -lgamma(y + 1) that ``lp`` drops and is so on one
+    scale with ``psis_loo_batched`` of a poisson ``BatchedGLMTarget``."""
 
     def __init__(self, A, y, prior_precision=1.0, counts=None, offset=None, log_size_mean=0.0, log_size_precision=1.0,
                  engine=None):

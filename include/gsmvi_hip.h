@@ -35,6 +35,7 @@
  *   examples/example_gsm.py:34-35 the comparison of fitted models: the PSIS leave-one-out density of every observation of K fitted
  *   GLMs (no reference twin)                                           ->  gsmvi_psis_loo_batched_f64, gsmvi_psis_loo_tile
  *   the same for K fitted multinomial logit regressions (no reference twin) -> gsmvi_psis_loo_softmax_batched_f64, gsmvi_psis_loo_softmax_tile
+ *   the same for K fitted negative binomial regressions (no reference twin) -> gsmvi_psis_loo_negbin_batched_f64, gsmvi_psis_loo_negbin_tile
  *   examples/example_gsm.py:34-35 the use of the fit for K fitted multinomial logit regressions: class probabilities and the held-out
  *   score from draws of q_k (no reference twin)                        ->  gsmvi_softmax_predict_batched_f64, gsmvi_softmax_predict_lds_bytes
  *   gsmvi/bam.py:72-114       bam_lowrank_update(samples,vs,mu0,S0,reg) ->  gsmvi_bam_update_f64
@@ -308,12 +309,12 @@ int gsmvi_get_profile(gsmvi_ctx* ctx, float* ms, int n);
 #define GSMVI_PATH_BATCHED_BAM 0x4000u     /* k_bam_batched: the batched BaM entry points                           */
 #define GSMVI_PATH_BATCHED_KL 0x8000u      /* k_kl_batched: the batched KL monitor's entry points                  */
 #define GSMVI_PATH_BATCHED_ADVI 0x10000u   /* k_advi_batched / k_advi_cov_batched: the batched ADVI entry points   */
-#define GSMVI_PATH_BATCHED_TARGET 0x20000u /* k_logistic_batched: the batched non-Gaussian target's entry point; with GSMVI_PATH_BATCHED_LAPLACE in one call: k_laplace_shared_batched (all 32 bits are taken; no other call sets that pair) */
+#define GSMVI_PATH_BATCHED_TARGET 0x20000u /* k_logistic_batched: the batched non-Gaussian target's entry point; with GSMVI_PATH_BATCHED_LAPLACE in one call: k_laplace_shared_batched; with GSMVI_PATH_BATCHED_LOO in one call: k_psis_loo_negbin_batched (all 32 bits are taken; no other call sets either pair) */
 #define GSMVI_PATH_BATCHED_LBFGS 0x40000u  /* k_lbfgs_step_batched / k_lbfgs_hess_inv_batched: the batched initialiser   */
 #define GSMVI_PATH_BATCHED_LAPLACE 0x80000u /* k_laplace_batched: the batched GLM Hessian and Newton step; with GSMVI_PATH_BATCHED_TARGET in one call: k_laplace_shared_batched, the shared-design Hessian and Newton step */
 #define GSMVI_PATH_BATCHED_PREDICT 0x100000u /* k_glm_predict_batched: the batched GLM posterior predictive; with GSMVI_PATH_BATCHED_SOFTMAX: k_softmax_predict_batched */
 #define GSMVI_PATH_BATCHED_PSIS 0x200000u /* k_psis_batched: the batched Pareto-smoothed importance diagnostic            */
-#define GSMVI_PATH_BATCHED_LOO 0x400000u /* k_psis_loo_batched: the batched PSIS leave-one-out; with GSMVI_PATH_BATCHED_SOFTMAX: k_psis_loo_softmax_batched */
+#define GSMVI_PATH_BATCHED_LOO 0x400000u /* k_psis_loo_batched: the batched PSIS leave-one-out; with GSMVI_PATH_BATCHED_SOFTMAX: k_psis_loo_softmax_batched; with GSMVI_PATH_BATCHED_TARGET: k_psis_loo_negbin_batched */
 #define GSMVI_PATH_GSM_TWO_LAUNCH 0x800000u /* the dense GSM update ran as two launches (no k_gsm_scalars_fast, no records)          */
 #define GSMVI_PATH_BATCHED_SOFTMAX 0x1000000u /* k_softmax_batched: the batched multinomial logit target's entry point            */
 #define GSMVI_PATH_PANEL_CHUNK512 0x2000000u /* the two-launch product ran as two slabs of one 512-row chunk each (D = 1024, no explicit "panel_kc") */
@@ -1003,6 +1004,53 @@ int gsmvi_psis_loo_softmax_batched_f64(gsmvi_ctx* ctx, void* stream, int64_t K, 
                                        const double* A, const int* labels, const int* counts_dev, const double* X,
                                        const double* logr, const double* lw, double* loglik, double* elpd, double* lpd,
                                        double* khat, double* ess, int* info);
+
+/*
+ * Batched negative binomial PSIS leave-one-out: the same for K fitted posteriors of the overdispersed count model of
+ * gsmvi_negbin_batched_f64, whose draws carry a shape parameter.  The reference has no twin.  One launch, one workgroup per
+ * (problem, tile of gsmvi_psis_loo_negbin_tile(P, S) observations).
+ * Problem k has A_k (N x P; A is K x N x P), responses y_ki >= 0 (K x N), an optional offset o_ki (K x N, or NULL), n_k =
+ * counts_dev[k] clamped to 0 .. N valid rows (N without counts_dev), and the draws x_s = (beta_s, theta_s) (s < S; X is K x S x D,
+ * D = P + 1 <= 64, theta = log r the log of the size) of q_k.  logr (K x S) and lw (K x S) are what gsmvi_psis_batched_f64 writes
+ * for the same draws.  For a valid row i < n_k:
+ *   eta_si = a_i . beta_s + o_i
+ *   l_si   = t(eta_si, theta_s, y_i) - lgamma(y_i + 1)
+ * with t the per-row density term of gsmvi_negbin_batched_f64 (lgamma(y + r) - lgamma(r) - r softplus(eta - theta) - y softplus(theta
+ * - eta), r = e^theta; the lgamma difference is formed as a difference, never from two lgamma calls, and e^eta is never formed).  The
+ * term -lgamma(y_i + 1) is INCLUDED, so l_si is the normalised log probability of the count y_i -- as the poisson family of
+ * gsmvi_psis_loo_batched_f64 includes it: the elpd of the two launches are on one scale and may be subtracted (is the shape
+ * parameter worth having over Poisson?).  No prior enters.
+ * A draw is flagged when one of its D entries, theta included, is not finite, or when e^theta is not a positive normal number
+ * (|theta| above about 708: the row flag of gsmvi_negbin_batched_f64); a flagged draw has l_si = NaN for every observation of the
+ * problem.  The flag is taken from the draw's entries, not from the product: nothing else produces a NaN.
+ * From there on the text is that of gsmvi_psis_loo_batched_f64 above, word for word:
+ *   rho_si = logr_s - l_si (one subtraction)
+ *   the PSIS stage, steps 1-8 of gsmvi_psis_weights_batched_f64 exactly (the (value, row) order of the sort and the -1 / -2
+ *   verdicts included), on rho_.i gives the normalised smoothed log weights w_si, khat[k, i], ess[k, i] and info[k, i]
+ *   elpd[k, i] = log sum_s exp(w_si + l_si)
+ *   lpd[k, i]  = log sum_s exp(lw_s + l_si)
+ * both as max + log sum exp(. - max), the maximum and the sum each a fixed tree over the S draws (a thread's entries in order, a
+ * butterfly within each wave, the waves in order; no atomics): the outputs are bit-identical from run to run.
+ * info[k, i] = -1 (a NaN or +inf among rho_.i -- a flagged draw, a NaN logr --, or every rho -inf): elpd, lpd, khat and ess of (k, i)
+ * are NaN.  info[k, i] = -2 (fewer than five tail entries): plain self-normalised weights and khat = +inf.  Rows i >= n_k are never
+ * loaded: elpd, lpd, khat and ess are NaN and info[k, i] = -3.  A verdict touches only its own (k, i).  loglik (K x N x S, or NULL)
+ * receives l_si (NaN for rows i >= n_k).  Outputs: elpd, lpd, khat, ess (K x N doubles each) and info (K x N ints), all required.
+ * gsmvi_psis_loo_negbin_tile(P, S) is a pure function (no GPU): the observations per workgroup, the largest count of at most 4
+ * whose l_si (S doubles each) fit in the workgroup's 160 KB of LDS (20480 doubles) beside max(stage, tiles) doubles, where stage =
+ * S2 + S + 508 + S2 / 2 (S2 = S rounded up to a power of two, at least 8) and tiles = 80 (4 ceil(P / 4) + 1) + 240; 0 for P or S
+ * out of bounds.
+ * P >= 1, D = P + 1 <= 64, 5 <= S <= 4096, N >= 1, K >= 1 with K ceil(N / gsmvi_psis_loo_negbin_tile(P, S)) <= 2^24 - 1, K N S
+ * doubles addressable.  Shapes, NULL arrays and overlaps (loglik, elpd, lpd, khat, ess and info are the written arrays, everything
+ * else is read) are checked before the context is looked at (then a NULL ctx); every failure returns GSMVI_ERR_BAD_ARG before
+ * anything is enqueued.  Inputs are only read; no context workspace is used; one capturable launch with no host synchronisation
+ * and no atomics.  Sets GSMVI_PATH_BATCHED_LOO | GSMVI_PATH_BATCHED_TARGET: after a reset exactly that pair identifies this launch
+ * (the GLM leave-one-out sets the first bit alone, the negative binomial score launch the second alone).
+ */
+int gsmvi_psis_loo_negbin_tile(int P, int64_t S);
+int gsmvi_psis_loo_negbin_batched_f64(gsmvi_ctx* ctx, void* stream, int64_t K, int P, int64_t N, int64_t S, const double* A,
+                                      const double* y, const double* offset, const int* counts_dev, const double* X,
+                                      const double* logr, const double* lw, double* loglik, double* elpd, double* lpd,
+                                      double* khat, double* ess, int* info);
 
 /*
  * Batched softmax posterior predictive: what the fitted q_k = N(mean_k, cov_k) of K multinomial logit regressions (the model of
