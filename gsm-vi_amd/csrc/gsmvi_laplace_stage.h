@@ -1,9 +1,9 @@
 // The tail of a batched Laplace kernel after its sweep over the data: the layout of the Newton state, the
 // in-LDS Cholesky factorisation with the relative pivot rule, the write of H, the inverse R^{-1} R^{-T}, and the accept / reject
 // decision, the stopping tests, the two triangular solves and the state update of one Newton round -- the state machine
-// documented for gsmvi_laplace_step_batched_f64 in include/gsmvi_hip.h.  Used by gsmvi_softmax_laplace_batched.hip and
-// gsmvi_laplace_shared_batched.hip.  The GLM kernel (gsmvi_laplace_batched.hip) keeps its own, older copy of the same statements
-// inline, and a change to one copy belongs in the other: built from this header it gives the same bits, registers and occupancy,
+// documented for gsmvi_laplace_step_batched_f64 in include/gsmvi_hip.h.  Used by gsmvi_softmax_laplace_batched.hip,
+// gsmvi_laplace_shared_batched.hip and gsmvi_negbin_laplace_batched.hip (which puts its last-pivot rule between lp_chol_lds and
+// lp_step_tail).  The GLM kernel (gsmvi_laplace_batched.hip) keeps its own, older copy of the same statements inline, and a change to one copy belongs in the other: built from this header it gives the same bits, registers and occupancy,
 // and misses the speed bound of the A/B against the parent's library in 11 of 18 cases, its 64-thread step launch by 1 to 3 %
 // ("One copy of each initialiser stage"; profiles/batched/initialiser_stages_ab_parent.txt, second job).
 // Every function is for the problem of one workgroup slot: l is the thread's index in the slot (NT threads), Hs the slot's D x D

@@ -1176,6 +1176,61 @@ class HipEngine:
                    self._ist(state, K), self._packed(state["Xt"], (K, D), "Xt"), self._ints(stopped, 1, "stopped"),
                    int(maxiter), int(maxfun), float(gtol))
 
+    # ---- negative binomial Laplace initialiser: the same for K count regressions with a fitted size
+    # (csrc/gsmvi_negbin_laplace_batched.hip) --------------------------------------------------------------------------------------
+    def _negbin_model_args(self, A, y, offset, counts, prior_prec, log_size_mean, log_size_prec):
+        """the model's arguments of the two negative binomial Laplace entry points, in the order of include/gsmvi_hip.h"""
+        K, N, P = A.shape
+        r, rp = self._reg_arg(prior_prec, K)
+        m, mp = self._reg_arg(log_size_mean, K)
+        s, sp = self._reg_arg(log_size_prec, K)
+        return (K, P, N, self._packed(A, (K, N, P), "A"), self._packed(y, (K, N), "y"), self._dp(offset, (K, N), "offset"),
+                self._ints(counts, K, "counts"), m, mp, s, sp, r, rp)
+
+    def negbin_hessian_batched(self, X, A, y, offset=None, counts=None, prior_prec=1.0, log_size_mean=0.0, log_size_prec=1.0,
+                               want="h", out=None, cov_out=None, info_out=None):
+        """The negative Hessian of lp_k of K negative binomial regressions at the rows of X (K, P + 1) = (beta, theta), and / or
+        its inverse, one launch (the P x P block and the border column as one Gram product on the fp64 MFMA)  [no reference twin;
+        the model of examples/example_gsm.py:34-35]: bordered, H[:P, :P] = sum_n w_ee a a^T + lam I, H[:P, P] = sum_n w_et a,
+        H[P, P] = sum_n w_tt + kap, and not positive semi-definite in general.  ``want`` = "h" -> H (K, D, D), "cov" -> (cov,
+        info), "both" -> (H, cov, info); ``info`` (K,) int32: 0, or 1 + the first failing pivot, and then cov_k = I.  The other
+        arguments are ``negbin_batched``'s."""
+        self._check_want(want, "h", "cov")
+        X = X.contiguous()
+        K, D = X.shape
+        if D != A.shape[2] + 1:
+            raise ValueError(f"X: expected P + 1 = {A.shape[2] + 1} columns (beta, then the log size), got {D}")
+        self._any_ctx()
+        H = cov = info = None
+        if want != "cov":
+            H = self.empty(K, D, D) if out is None else out
+        if want != "h":
+            cov = self.empty(K, D, D) if cov_out is None else cov_out
+            info = torch.zeros(K, dtype=torch.int32, device=self.device) if info_out is None else info_out
+        self._call("gsmvi_negbin_hessian_batched_f64",
+                   *self._negbin_model_args(A, y, offset, counts, prior_prec, log_size_mean, log_size_prec),
+                   self._packed(X, (K, D), "X"), self._dp(H, (K, D, D), "out"), self._dp(cov, (K, D, D), "cov_out"),
+                   self._ints(info, K, "info_out"))
+        return H if want == "h" else (cov, info) if want == "cov" else (H, cov, info)
+
+    def negbin_laplace_step_batched(self, state, A, y, offset=None, counts=None, prior_prec=1.0, log_size_mean=0.0,
+                                    log_size_prec=1.0, start=False, maxiter=100, maxfun=200, gtol=1e-8):
+        """One damped Newton round of every running problem of ``state`` (``laplace_state_batched``) for K negative binomial
+        regressions (csrc/gsmvi_negbin_laplace_batched.hip): f, g and H at ``state["Xt"]`` in one sweep over A, then the round of
+        ``laplace_step_batched`` with the last-pivot rule of include/gsmvi_hip.h; ``state["ist"][:, 4]`` counts the rounds with a
+        modified pivot  [the role of gsmvi/initializers.py:5-17]"""
+        K, D = state["x"].shape
+        if D != A.shape[2] + 1:
+            raise ValueError(f"state: expected P + 1 = {A.shape[2] + 1} columns (beta, then the log size), got {D}")
+        self._any_ctx()
+        stopped = state.get("stopped")
+        self._call("gsmvi_negbin_laplace_step_batched_f64",
+                   *self._negbin_model_args(A, y, offset, counts, prior_prec, log_size_mean, log_size_prec), int(bool(start)),
+                   self._packed(state["x"], (K, D), "x"), self._packed(state["g"], (K, D), "g"),
+                   self._packed(state["d"], (K, D), "d"), self._packed(state["sc"], (K, 4), "sc"),
+                   self._ist(state, K), self._packed(state["Xt"], (K, D), "Xt"), self._ints(stopped, 1, "stopped"),
+                   int(maxiter), int(maxfun), float(gtol))
+
     # ---- batched GLM posterior predictive: the use of K fitted Gaussians (csrc/gsmvi_glm_predict_batched.hip) -----------------
     @staticmethod
     def gauss_hermite(Q):

@@ -409,3 +409,49 @@ def laplace_init_shared_batched(target, x0=None, maxiter=100, maxfun=200, *, gto
         lambda x: eng.glm_shared_hessian_batched(x, target.A, target.y, target.family, want="cov", **model))
     res.status = np.where((res.status == 1) & (res.info != 0), 5, res.status)     # stationary, but H is not positive definite
     return mean, cov, res
+
+
+@dataclass
+class LaplaceNegBinBatchedResult(LaplaceBatchedResult):
+    """``LaplaceBatchedResult`` of ``laplace_init_negbin_batched`` with ``nmod`` (K,): the Newton rounds of each problem whose
+    direction came from a factorisation with a modified last pivot (0: plain Newton throughout)."""
+    nmod: np.ndarray = None
+
+
+def laplace_init_negbin_batched(target, x0=None, maxiter=100, maxfun=200, *, gtol=1e-8, check_every=4, as_torch=False, engine=None):
+    """The Laplace start of K negative binomial posteriors at once: returns ``(mean (K, D), cov (K, D, D), res)``, the Newton
+    modes of ``lp_k`` in x = (beta, theta), the inverses of the negative Hessians there (``neg_hessian_negbin_batched``) and a
+    ``LaplaceNegBinBatchedResult``.  It fills the role of ``lbfgs_init`` (gsmvi/initializers.py:5-17) for the negative binomial
+    target.
+
+    ``target``: a ``BatchedNegBinomialTarget`` (anything else: TypeError).  ``x0``, the line search, the stopping rule,
+    ``check_every``, one launch per round (csrc/gsmvi_negbin_laplace_batched.hip), the frozen problems, the failure policy (a
+    problem without success returns its last ``x`` and the identity) and the defaults are ``laplace_init_batched``'s.  Two things
+    are this function's own, because the posterior is not log-concave in theta = log r and the negative Hessian away from the
+    mode is often indefinite in that direction (at x0 = 0 for about half of well-posed problems).  First, the last-pivot rule:
+    when the factorisation of a round fails at exactly its last pivot -- theta's, given beta -- that pivot is replaced by its
+    absolute value (if it is not within 64 eps of the sizes it is the difference of); the modified matrix is positive definite,
+    the direction a descent direction, and the Armijo search does the rest.  ``res.nmod`` counts such rounds per problem.  A
+    pivot failing before the last still ends the problem with ``status`` 5.  The covariance is never modified: second, as in
+    ``laplace_init_shared_batched``, a problem that stopped by the gradient test but whose Hessian at that point is not positive
+    definite (``info`` != 0) is reported with ``status`` 5, has no ``success`` and gets the identity.  With a flat prior on theta
+    (``log_size_precision`` = 0) and data without overdispersion the mode is at theta = inf: such a problem ends with ``status``
+    2, 3 or 5 and is reported, not hidden.  Prints nothing."""
+    from .targets import BatchedNegBinomialTarget
+    if not isinstance(target, BatchedNegBinomialTarget):
+        raise TypeError(f"laplace_init_negbin_batched: target must be a BatchedNegBinomialTarget, got {type(target).__name__}")
+    model = dict(offset=target.offset, counts=target.counts, prior_prec=target.prior_precision,
+                 log_size_mean=target.log_size_mean, log_size_prec=target.log_size_precision)
+    eng = engine if engine is not None else target.engine
+    kept = {}
+
+    def step(st, **kw):
+        kept["ist"] = st["ist"]
+        eng.negbin_laplace_step_batched(st, target.A, target.y, **kw, **model)
+
+    mean, cov, res = _laplace_run(
+        "laplace_init_negbin_batched", target, x0, maxiter, maxfun, gtol, check_every, as_torch, eng, step,
+        lambda x: eng.negbin_hessian_batched(x, target.A, target.y, want="cov", **model))
+    status = np.where((res.status == 1) & (res.info != 0), 5, res.status)         # stationary, but H is not positive definite
+    fields = {f: getattr(res, f) for f in ("x", "fun", "jac", "nit", "nfev", "success", "info", "nlaunch")}
+    return mean, cov, LaplaceNegBinBatchedResult(status=status, nmod=eng.read_ints(kept["ist"])[:, 4].copy(), **fields)

@@ -543,7 +543,8 @@ class BatchedNegBinomialTarget:
     allocation with ``out``).  ``lp(x)``: (K, rows, D) -> (K, rows) values; a device tensor or numpy.  ``lp_and_score(x)``:
     (scores, values) from one launch.  Attributes ``K, N, P, D``.  Not a ``BatchedGLMTarget``: its Hessian is not A^T W A (every
     row contributes a 2 x 2 block in (eta, theta)), so it has no ``neg_hessian``, ``predict`` or ``loo``, and
-    ``laplace_init_batched`` and ``psis_loo_batched`` refuse it (TypeError).  Its leave-one-out is the function
+    ``laplace_init_batched`` and ``psis_loo_batched`` refuse it (TypeError).  Its negative Hessian is the function
+    ``neg_hessian_negbin_batched(target, x)`` and its second-order start ``laplace_init_negbin_batched``.  Its leave-one-out is the function
     ``psis_loo_negbin_batched(target, mean, cov, keys, ...)``, which includes the -lgamma(y + 1) that ``lp`` drops and is so on one
     scale with ``psis_loo_batched`` of a poisson ``BatchedGLMTarget``."""
 
@@ -593,6 +594,28 @@ class BatchedNegBinomialTarget:
     def lp_and_score(self, x):
         """(scores (K, rows, D), values (K, rows)) from one launch"""
         return self._call(self.engine.asarray(x), want="both")
+
+
+def neg_hessian_negbin_batched(target, x, *, engine=None):
+    """(K, D, D) negative Hessians of lp_k of a ``BatchedNegBinomialTarget`` at the rows of x (K, D) = (beta, theta): with d =
+    eta - theta, r = exp(theta), sigma = sigmoid(d), r_eta = y sigmoid(-d) - r sigma, dps = psi(y + r) - psi(r) and dtg =
+    psi'(y + r) - psi'(r),
+
+        w_ee = (y + r) sigma sigmoid(-d),   w_et = -sigma r_eta,   w_tt = -[r (dps - softplus(d)) + r^2 dtg + r sigma - sigma r_eta]
+        H[:P, :P] = sum_n w_ee,n a_n a_n^T + lam_k I,   H[:P, P] = sum_n w_et,n a_n,   H[P, P] = sum_n w_tt,n + kap_k
+
+    Exactly symmetric, and NOT positive semi-definite in general (w_tt has any sign: lp_k is not concave in theta).  A point
+    whose exp(theta) is not a positive normal number gives NaN.  A device tensor or numpy in; one launch
+    (gsmvi_negbin_hessian_batched_f64).  Anything that is not a ``BatchedNegBinomialTarget`` raises TypeError."""
+    if not isinstance(target, BatchedNegBinomialTarget):
+        raise TypeError(f"neg_hessian_negbin_batched: target must be a BatchedNegBinomialTarget, got {type(target).__name__}")
+    K, D = target.K, target.D
+    if _shape(x) != (K, D):
+        raise ValueError(f"neg_hessian_negbin_batched: x must be (K, D) = {(K, D)} of the target, got {_shape(x)}")
+    eng = engine if engine is not None else target.engine
+    return eng.negbin_hessian_batched(eng.asarray(x), target.A, target.y, offset=target.offset, counts=target.counts,
+                                      prior_prec=target.prior_precision, log_size_mean=target.log_size_mean,
+                                      log_size_prec=target.log_size_precision, want="h")
 
 
 def _check_labels(y, C, live):

@@ -27,7 +27,8 @@
  *   initializers.py:5-17 lbfgs_init (maximiser of lp, dense inverse-Hessian estimate), K problems -> gsmvi_lbfgs_step_batched_f64, gsmvi_lbfgs_hess_inv_batched_f64
  *   initializers.py:5-17 the same role by Newton rounds on the GLMs of examples/example_gsm.py:34-35 (no reference twin) -> gsmvi_glm_hessian_batched_f64, gsmvi_laplace_step_batched_f64,
  *   gsmvi_softmax_hessian_batched_f64, gsmvi_softmax_laplace_step_batched_f64 (the multinomial logit),
- *   gsmvi_glm_shared_hessian_batched_f64, gsmvi_laplace_shared_step_batched_f64 (the GLMs on one design matrix)
+ *   gsmvi_glm_shared_hessian_batched_f64, gsmvi_laplace_shared_step_batched_f64 (the GLMs on one design matrix),
+ *   gsmvi_negbin_hessian_batched_f64, gsmvi_negbin_laplace_step_batched_f64 (the negative binomial regressions)
  *   initializers.py:5-17 the same role with a start picked by its ELBO along the L-BFGS path (Pathfinder; no reference twin) -> gsmvi_pathfinder_propose_batched_f64, gsmvi_pathfinder_select_batched_f64
  *   examples/example_gsm.py:34-35 the use of the fit: predictions and the held-out score of K fitted GLMs (no reference twin) -> gsmvi_glm_predict_batched_f64
  *   monitors.py:83-125 the role (is q_k close to its target?), per problem and comparable across problems: the Pareto-smoothed
@@ -309,9 +310,9 @@ int gsmvi_get_profile(gsmvi_ctx* ctx, float* ms, int n);
 #define GSMVI_PATH_BATCHED_BAM 0x4000u     /* k_bam_batched: the batched BaM entry points                           */
 #define GSMVI_PATH_BATCHED_KL 0x8000u      /* k_kl_batched: the batched KL monitor's entry points                  */
 #define GSMVI_PATH_BATCHED_ADVI 0x10000u   /* k_advi_batched / k_advi_cov_batched: the batched ADVI entry points   */
-#define GSMVI_PATH_BATCHED_TARGET 0x20000u /* k_logistic_batched: the batched non-Gaussian target's entry point; with GSMVI_PATH_BATCHED_LAPLACE in one call: k_laplace_shared_batched; with GSMVI_PATH_BATCHED_LOO in one call: k_psis_loo_negbin_batched (all 32 bits are taken; no other call sets either pair) */
+#define GSMVI_PATH_BATCHED_TARGET 0x20000u /* k_logistic_batched: the batched non-Gaussian target's entry point; with GSMVI_PATH_BATCHED_LAPLACE in one call: k_laplace_shared_batched or k_negbin_laplace_batched; with GSMVI_PATH_BATCHED_LOO in one call: k_psis_loo_negbin_batched (all 32 bits are taken; no other call sets either pair) */
 #define GSMVI_PATH_BATCHED_LBFGS 0x40000u  /* k_lbfgs_step_batched / k_lbfgs_hess_inv_batched: the batched initialiser   */
-#define GSMVI_PATH_BATCHED_LAPLACE 0x80000u /* k_laplace_batched: the batched GLM Hessian and Newton step; with GSMVI_PATH_BATCHED_TARGET in one call: k_laplace_shared_batched, the shared-design Hessian and Newton step */
+#define GSMVI_PATH_BATCHED_LAPLACE 0x80000u /* k_laplace_batched: the batched GLM Hessian and Newton step; with GSMVI_PATH_BATCHED_TARGET in one call: k_laplace_shared_batched, the shared-design Hessian and Newton step, or k_negbin_laplace_batched, the negative binomial one */
 #define GSMVI_PATH_BATCHED_PREDICT 0x100000u /* k_glm_predict_batched: the batched GLM posterior predictive; with GSMVI_PATH_BATCHED_SOFTMAX: k_softmax_predict_batched */
 #define GSMVI_PATH_BATCHED_PSIS 0x200000u /* k_psis_batched: the batched Pareto-smoothed importance diagnostic            */
 #define GSMVI_PATH_BATCHED_LOO 0x400000u /* k_psis_loo_batched: the batched PSIS leave-one-out; with GSMVI_PATH_BATCHED_SOFTMAX: k_psis_loo_softmax_batched; with GSMVI_PATH_BATCHED_TARGET: k_psis_loo_negbin_batched */
@@ -830,7 +831,8 @@ int gsmvi_softmax_laplace_step_batched_f64(gsmvi_ctx* ctx, void* stream, int64_t
  * Both: shapes, NULL arrays and overlaps (only the written arrays may not overlap anything) are checked before the context is
  * looked at (then a NULL ctx); every failure returns GSMVI_ERR_BAD_ARG before anything is enqueued.  Inputs are only read; no
  * context workspace is used; at most 64 KB of dynamic LDS (no kernel attribute).  Both set GSMVI_PATH_BATCHED_LAPLACE |
- * GSMVI_PATH_BATCHED_TARGET: no other call sets that pair, so gsmvi_last_path still proves which kernel ran.
+ * GSMVI_PATH_BATCHED_TARGET: only the two negative binomial entry points below set that pair too (all 32 bits are taken), so
+ * gsmvi_last_path still proves that a batched Laplace kernel with a model of its own ran.
  */
 int gsmvi_glm_shared_hessian_batched_f64(gsmvi_ctx* ctx, void* stream, int64_t K, int D, int64_t N, int family, const double* A,
                                          const double* y, const double* offset, const double* weights, double noise_prec,
@@ -841,6 +843,52 @@ int gsmvi_laplace_shared_step_batched_f64(gsmvi_ctx* ctx, void* stream, int64_t 
                                           const double* noise_prec_dev, double prior_prec, const double* prior_prec_dev, int start,
                                           double* x, double* g, double* d, double* sc, int* ist, double* Xt, int* stopped_dev,
                                           int maxiter, int maxfun, double gtol);
+
+/*
+ * Negative binomial Laplace initialiser: the Newton mode of K negative binomial posteriors and the inverse of the negative Hessian
+ * there as the covariance: the two entry points above for the model of gsmvi_negbin_batched_f64, whose arguments (K, P, N, A, y,
+ * offset, counts_dev, theta_mean, theta_prec, prior_prec and their _dev forms) and bounds at nc = 1 they take (the role of
+ * gsmvi/initializers.py:5-17 for the model of examples/example_gsm.py:34-35; no reference twin).  x = (beta, theta), D = P + 1 <= 64,
+ * r = e^theta, d = eta - theta, sigma = sigma(d); with (t, r_eta, r_theta) of gsmvi_negbin_batched_f64, dps = psi(y + r) - psi(r)
+ * and dtg = psi'(y + r) - psi'(r), each formed as one difference and never from two calls:
+ *   w_ee = (y + r) sigma(d) sigma(-d) >= 0      w_et = -sigma r_eta      w_tt = -[ r (dps - softplus(d)) + r^2 dtg + r sigma - sigma r_eta ]
+ *   f_k(x) = -lp_k(x),   g_k(x) = -score_k(x),
+ *   H_k[:P, :P] = sum_{n < n_k} w_ee,n a_n a_n^T + lam_k I     H_k[:P, P] = sum_{n < n_k} w_et,n a_n     H_k[P, P] = sum_{n < n_k} w_tt,n + kap_k
+ * H_k is the negative Hessian of lp_k.  It is NOT positive semi-definite in general: w_tt has any sign, and lp_k is not concave
+ * in theta.  The P x P block and the border column are one Gram product on the fp64 MFMA over tiles of 32 rows; H[P, P] is summed
+ * in order by one thread.  Every sum over n runs in an order fixed by (N, P) alone: a problem's bits depend on its own data only.
+ *
+ * gsmvi_negbin_hessian_batched_f64: H (K x D x D, or NULL), cov (K x D x D, or NULL) and info_dev (K ints, required with cov and only
+ * with it) as gsmvi_glm_hessian_batched_f64 gives them, at the rows x_k of X (K x D): H exactly symmetric, the pivot rule
+ * 64 eps H_jj, cov_k = I and info[k] = 1 + the first failing pivot where H_k is not positive definite (nothing is modified here).  A
+ * non-finite x_k, or an e^theta that is not a positive normal number, gives H_k = NaN, info[k] = 1, cov_k = I, and no other problem
+ * is touched.  At least one of H, cov is given.
+ *
+ * gsmvi_negbin_laplace_step_batched_f64: one launch is one damped Newton round of phi_k = f_k for every running problem: the state
+ * (x, g, d, Xt (K x D), sc (K x 4), ist (K x 8)), the status codes 1 - 5, the Armijo test with its slack 1e-10 max(1, |f|), the
+ * halving, the 20 rejections, *stopped_dev and the meaning of start, maxiter, maxfun and gtol are those documented for
+ * gsmvi_laplace_step_batched_f64; a flagged trial point is status 4 at the start and a rejected trial later.  One rule is this entry
+ * point's own, the last-pivot rule: when the factorisation for a new direction fails at exactly the last pivot (info = D: no
+ * positive curvature in theta given beta), with R the factor, s = H[P, P] - sum_{c < P} R[c, P]^2 and m = |H[P, P]| + sum_{c < P}
+ * R[c, P]^2 (both in c order), and |s| finite and > 64 eps m, the last pivot is replaced by sqrt|s|, the round goes on as if the
+ * factorisation had succeeded (the modified matrix is positive definite, so d is a descent direction) and ist[4], zero at the
+ * start, grows by one: the rounds with a modified pivot.  A pivot that fails before the last, or an |s| below that bar, is
+ * status 5 as before.  A problem whose status is not 0 is frozen: nothing of it is written and nothing of A_k is loaded for it.
+ * Both: shapes, NULL arrays and overlaps (only the written arrays may not overlap anything) are checked before the context is
+ * looked at (then a NULL ctx); every failure returns GSMVI_ERR_BAD_ARG before anything is enqueued.  Inputs are only read; no
+ * context workspace is used; at most 64 KB of dynamic LDS (no kernel attribute).  Both set GSMVI_PATH_BATCHED_LAPLACE |
+ * GSMVI_PATH_BATCHED_TARGET, the pair of the shared-design entry points above.
+ */
+int gsmvi_negbin_hessian_batched_f64(gsmvi_ctx* ctx, void* stream, int64_t K, int P, int64_t N, const double* A, const double* y,
+                                     const double* offset, const int* counts_dev, double theta_mean, const double* theta_mean_dev,
+                                     double theta_prec, const double* theta_prec_dev, double prior_prec,
+                                     const double* prior_prec_dev, const double* X, double* H, double* cov, int* info_dev);
+int gsmvi_negbin_laplace_step_batched_f64(gsmvi_ctx* ctx, void* stream, int64_t K, int P, int64_t N, const double* A,
+                                          const double* y, const double* offset, const int* counts_dev, double theta_mean,
+                                          const double* theta_mean_dev, double theta_prec, const double* theta_prec_dev,
+                                          double prior_prec, const double* prior_prec_dev, int start, double* x, double* g,
+                                          double* d, double* sc, int* ist, double* Xt, int* stopped_dev, int maxiter, int maxfun,
+                                          double gtol);
 
 /*
  * Batched GLM posterior predictive: what a fitted q_k = N(mean_k, cov_k) over the coefficients of K GLMs of one D says about M new

@@ -58,6 +58,10 @@ int gsmvi_debug_glm_shared_batched_lds(int D, int want, int family, size_t* byte
  * most GB_LDS_MAX (76 KB: four problems of D = 16 with both outputs and an offset).  Host arithmetic only, no device needed. */
 int gsmvi_debug_negbin_batched_lds(int D, int nc, int want, int has_offset, size_t* bytes, int* problems_per_workgroup);
 
+/* The same for a gsmvi_negbin_hessian_batched_f64 or gsmvi_negbin_laplace_step_batched_f64 launch at D = P + 1 in 2 .. 64 (both
+ * request the same, with or without an offset): at most 64 KB, so no kernel attribute.  Host arithmetic only, no device needed. */
+int gsmvi_debug_negbin_laplace_lds(int D, size_t* bytes, int* problems_per_workgroup);
+
 /* The same for a gsmvi_softmax_batched_f64 launch at (C, P, nc), and the rows of X one tile holds at (C, P) (the launch holds
  * min(nc, that) rows).  Host arithmetic only, no device needed. */
 int gsmvi_debug_softmax_batched_lds(int C, int P, int nc, int want, size_t* bytes, int* problems_per_workgroup,
