@@ -57,6 +57,10 @@ Mirrors the reference's public surface for the hot path (reference file:line):
     logit posteriors on new rows, from draws of q_k,
     uniform or PSIS-weighted: class probabilities,
     labels, held-out elpd; one launch after the draws) examples/example_gsm.py:34-35, the use of the fit; no reference twin
+    predict_negbin_batched, NegBinPrediction (the same
+    for K fitted negative binomial posteriors: mean and
+    variance of the predictive count from three log
+    moments, held-out elpd on the leave-one-out's scale) examples/example_gsm.py:34-35, the use of the fit; no reference twin
     lbfgs_init_batched (the L-BFGS initialiser
     for K problems at once, D <= 64: one launch
     per function evaluation after lp_g and lp)   gsmvi/initializers.py:5-17
@@ -96,6 +100,7 @@ from .targets import BatchedSoftmaxTarget                            # noqa: F40
 from .targets import SharedDesignGLMTarget                           # noqa: F401
 from .targets import BatchedNegBinomialTarget                        # noqa: F401
 from .targets import predict_softmax_batched, SoftmaxPrediction      # noqa: F401
+from .targets import predict_negbin_batched, NegBinPrediction        # noqa: F401
 from .targets import neg_hessian_shared_batched                      # noqa: F401
 from .targets import neg_hessian_negbin_batched                      # noqa: F401
 from .batched import GSMBatch, gsm_update_batched                    # noqa: F401

@@ -1408,6 +1408,28 @@ class HipEngine:
                    self._dp(lw, (K, S), "lw"), self._packed(prob, (K, M, Cc), "prob"), self._dp(lpd, (K, M), "lpd"))
         return prob, lpd
 
+    # ---- the same use of K fitted negative binomial posteriors (csrc/gsmvi_negbin_predict_batched.hip) ---------------------------
+    def negbin_predict_batched(self, X, lw, A_new, y=None, offset=None, counts=None):
+        """The posterior predictive of K fitted negative binomial posteriors at the rows of A_new (K, M, P) from the draws X
+        (K, S, P + 1) = (beta, theta) of q_k, weighted by the normalised log weights ``lw`` (K, S) (``psis_batched``'s; None:
+        uniform), one launch (gsmvi_negbin_predict_batched_f64; the definition is in include/gsmvi_hip.h)  [no reference twin]:
+        returns (lmom (K, M, 3) = log E[mu], log E[mu^2], log E[mu^2 / r], lpd (K, M) or None without ``y``).  ``y`` (K, M),
+        ``offset`` and ``counts`` are ``negbin_batched``'s, for the new rows."""
+        K, S, D = X.shape
+        M, P = A_new.shape[1], A_new.shape[2]
+        if D != P + 1:
+            raise ValueError(f"X: expected P + 1 = {P + 1} columns (beta, then the log size), got {D}")
+        self._any_ctx()
+        X = X.contiguous()
+        lw = lw.contiguous() if lw is not None else None
+        lmom = self.empty(K, M, 3)
+        lpd = self.empty(K, M) if y is not None else None
+        self._call("gsmvi_negbin_predict_batched_f64", K, P, M, S, self._packed(A_new, (K, M, P), "A_new"),
+                   self._dp(y, (K, M), "y"), self._dp(offset, (K, M), "offset"), self._ints(counts, K, "counts"),
+                   self._packed(X, (K, S, D), "X"), self._dp(lw, (K, S), "lw"), self._packed(lmom, (K, M, 3), "lmom"),
+                   self._dp(lpd, (K, M), "lpd"))
+        return lmom, lpd
+
     def bam_update(self, X, G, mu0, S0, reg, jitter=0.0, out=None, flag=None):
         """(mu, S) of BaM [gsmvi/bam.py:72-114]; S symmetrised, jitter on the diagonal."""
         assert X.dim() == 2 and G.dim() == 2            # bam.py:47-48

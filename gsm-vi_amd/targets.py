@@ -546,7 +546,8 @@ class BatchedNegBinomialTarget:
     ``laplace_init_batched`` and ``psis_loo_batched`` refuse it (TypeError).  Its negative Hessian is the function
     ``neg_hessian_negbin_batched(target, x)`` and its second-order start ``laplace_init_negbin_batched``.  Its leave-one-out is the function
     ``psis_loo_negbin_batched(target, mean, cov, keys, ...)``, which includes the -lgamma(y + 1) that ``lp`` drops and is so on one
-    scale with ``psis_loo_batched`` of a poisson ``BatchedGLMTarget``."""
+    scale with ``psis_loo_batched`` of a poisson ``BatchedGLMTarget``.  Its posterior predictive is the function
+    ``predict_negbin_batched(target, mean, cov, A_new, keys, ...)``, a mean over draws of q_k (the class gains no method)."""
 
     def __init__(self, A, y, prior_precision=1.0, counts=None, offset=None, log_size_mean=0.0, log_size_precision=1.0,
                  engine=None):
@@ -616,6 +617,126 @@ def neg_hessian_negbin_batched(target, x, *, engine=None):
     return eng.negbin_hessian_batched(eng.asarray(x), target.A, target.y, offset=target.offset, counts=target.counts,
                                       prior_prec=target.prior_precision, log_size_mean=target.log_size_mean,
                                       log_size_prec=target.log_size_precision, want="h")
+
+
+@dataclass
+class NegBinPrediction:
+    """What ``predict_negbin_batched`` returns for M new rows of each of K negative binomial problems under the fitted q_k =
+    N(mean_k, cov_k) over (beta, theta = log r) (numpy arrays, or the engine's tensors with ``as_torch``): ``log_moments``
+    (K, M, 3) = log E[mu], log E[mu^2], log E[mu^2 / r] over the (weighted) draws, mu = exp(eta); ``mean`` (K, M) = exp(log E[mu]),
+    the predictive mean of the count; ``var`` (K, M) = E[mu + mu^2 / r] + Var[mu], its predictive variance (wider than the mean:
+    the overdispersion and the spread of the draws).  ``mean`` is +inf where log E[mu] exceeds 709.78 (and ``var`` with it):
+    ``log_moments`` stays finite there and is what to use.  With ``y``, ``lpd`` (K, M) = log E[p(y | eta, theta)] per row,
+    -lgamma(y + 1) included (the scale of ``psis_loo_negbin_batched``), and ``elpd`` (K,), its sum over the valid rows: the
+    held-out score by which fits are compared (both None without ``y``).  Rows beyond ``counts[k]`` are NaN.  ``psis`` the
+    problem-level ``PSISBatchedResult`` whose draws (and, with ``weights="psis"``, weights) were used (device tensors: hand it
+    back as ``psis=`` to reuse them), None where none was made or given; ``num_draws`` = S; ``nlaunch`` the kernel launches made.
+    A Monte-Carlo mean: no y is sampled and there are no quantiles.  [examples/example_gsm.py:34-35, the use of the fit; no
+    reference twin]"""
+    mean: Any
+    var: Any
+    log_moments: Any
+    lpd: Any
+    elpd: Any
+    psis: Any
+    num_draws: int
+    nlaunch: int
+
+
+def predict_negbin_batched(target, mean, cov, A_new, keys, offset=None, y=None, counts=None, num_draws=1024, *, call=0, psis=None,
+                           weights="uniform", as_torch=False, engine=None):
+    """The posterior predictive of K fitted negative binomial posteriors q_k = N(mean_k, cov_k) on new rows: returns a
+    ``NegBinPrediction``.
+
+    ``target`` is the ``BatchedNegBinomialTarget`` the posteriors were fitted to (its P is the model; anything else raises
+    TypeError); mean (K, D), D = P + 1, cov (K, D, D) and ``keys`` are ``psis_batched``'s; ``A_new`` (K, M, P) are the new rows,
+    ``offset`` (K, M) is added to their linear predictor, ``y`` (K, M) their counts (None: no ``lpd`` / ``elpd``), ``counts`` (K,)
+    the valid rows per problem (None: all M).  theta = log r is a coordinate of q_k, correlated with beta, so a row's density
+    depends on the pair (eta, theta) and there is no one-dimensional quadrature: the predictive is a mean over S = ``num_draws``
+    draws of q_k.
+    ``weights="uniform"``: one call of ``kl_draw_batched`` with ``psis_batched``'s seed rule (seed (keys[k] % 2**32) ^
+    0x5DEECE66D, draw number ``call``: the bits ``psis_batched`` would draw), no call of ``target.lp``, then one launch,
+    gsmvi_negbin_predict_batched_f64 (the definition is in include/gsmvi_hip.h): the linear predictors of every draw on the fp64
+    MFMA, then four log-sum-exps over the draws; no (K, S, M) block is formed.  ``weights="psis"``: first
+    ``psis_batched(target.lp, mean, cov, keys, num_draws, call=call, moments=False, as_torch=True)``, then the launch with its
+    smoothed ``log_weights``: the importance-corrected predictive; the result carries ``psis`` (khat, ``ok``), and a problem whose
+    problem-level run failed comes out NaN.  ``psis=``, the result of such a call, is reused (``num_draws`` and ``call`` are then
+    not used): its draws alone with ``"uniform"``, its weights too with ``"psis"``.  mean and cov are only read.
+    An ``A_new`` that is not (K, M, P), a mean that is not (K, D) of the target, a cov that is not (K, D, D), an ``offset`` that is
+    not (K, M) or not finite in the valid rows, a ``y`` that is not (K, M) or not finite and >= 0 in the valid rows (non-integers
+    are allowed, as in the target), bad ``counts``, keys of another length than K, ``num_draws`` outside 5..4096, an unknown
+    ``weights`` or a ``psis`` that is not a ``PSISBatchedResult`` holding device tensors of the right shapes raise ValueError
+    naming the argument before any device work."""
+    from .diagnostics import MAX_DRAWS, MIN_DRAWS, _reusable, psis_batched
+    from .monitors import _to_numpy
+    fn = "predict_negbin_batched"
+    if not isinstance(target, BatchedNegBinomialTarget):
+        raise TypeError(f"{fn}: target must be a BatchedNegBinomialTarget, got {type(target).__name__}")
+    if weights not in ("uniform", "psis"):
+        raise ValueError(f"{fn}: weights: expected 'uniform' or 'psis', got {weights!r}")
+    K, D, P = target.K, target.D, target.P
+    sa = _shape(A_new)
+    if len(sa) != 3 or min(sa) < 1 or sa[0] != K or sa[2] != P:
+        raise ValueError(f"{fn}: A_new: expected shape (K, M, P) with K = {K}, P = {P} and M >= 1, got {sa}")
+    M = sa[1]
+    if _shape(mean) != (K, D):
+        raise ValueError(f"{fn}: mean must be (K, D) = {(K, D)} of the target, got {_shape(mean)}")
+    if _shape(cov) != (K, D, D):
+        raise ValueError(f"{fn}: cov must be {(K, D, D)}, got {_shape(cov)}")
+    try:
+        cnt = _check_counts(counts, K, M, rows="M")
+        live = _live_rows(cnt, M)
+        yh = None
+        if y is not None:
+            if _shape(y) != (K, M):
+                raise ValueError(f"y: expected shape (K, M) = {(K, M)}, got {_shape(y)}")
+            yh = _check_responses(y, "poisson", live, name_family=False)      # the count range: finite and >= 0
+        oh = _check_offset(offset, K, M, live, rows="M")
+    except ValueError as e:
+        raise ValueError(f"{fn}: {e}") from None
+    keys_l = [int(k) for k in np.asarray(list(keys) if isinstance(keys, (list, tuple, range)) else _to_numpy(keys)).reshape(-1)]
+    if len(keys_l) != K:
+        raise ValueError(f"{fn}: {len(keys_l)} keys for K = {K} problems")
+    eng = engine if engine is not None else target.engine
+    if psis is None:
+        S = int(num_draws)
+        if S != num_draws or not MIN_DRAWS <= S <= MAX_DRAWS:
+            raise ValueError(f"{fn}: num_draws = {num_draws} is outside {MIN_DRAWS} <= num_draws <= {MAX_DRAWS}")
+        if weights == "psis":
+            psis = psis_batched(target.lp, mean, cov, keys_l, S, call=call, moments=False, as_torch=True, engine=eng)
+            nlaunch = psis.nlaunch + 1
+            X, _, lw = _reusable(psis, K, D, eng, fn)
+        else:
+            seeds = eng.batched_seeds(tuple((k % (2 ** 32)) ^ 0x5DEECE66D for k in keys_l))
+            X, _, _ = eng.kl_draw_batched(eng.asarray(mean), eng.asarray(cov), seeds, int(call), 0, S)
+            nlaunch, lw = 2, None
+    else:
+        X, _, lw = _reusable(psis, K, D, eng, fn)
+        S = _shape(X)[1]
+        nlaunch = 1
+        if weights == "uniform":
+            lw = None
+    lmom, lpd = eng.negbin_predict_batched(X, lw, eng.asarray(A_new.contiguous() if isinstance(A_new, torch.Tensor) else A_new),
+                                           y=eng.asarray(yh) if yh is not None else None,
+                                           offset=eng.asarray(oh) if oh is not None else None,
+                                           counts=eng.batched_counts(cnt) if cnt is not None else None)
+    ten = lambda a: a if isinstance(a, torch.Tensor) else torch.as_tensor(np.asarray(a))      # noqa: E731
+    lm = ten(lmom)
+    m1 = torch.exp(lm[..., 0])
+    # E[mu + mu^2 / r] + Var[mu]; the variance of mu as e^lmom1 (1 - e^(2 lmom0 - lmom1)): one exponential of a difference <= 0
+    # (where it rounds to no spread at all the term is 0, not inf x 0)
+    spread = -torch.expm1(2.0 * lm[..., 0] - lm[..., 1])
+    var = m1 + torch.exp(lm[..., 2]) + torch.where(spread > 0.0, torch.exp(lm[..., 1]) * spread, torch.zeros_like(spread))
+    elpd = None
+    if lpd is not None:
+        lt = ten(lpd)
+        nk = ten(cnt).to(lt.device) if cnt is not None else torch.full((K,), M, device=lt.device)
+        mask = torch.arange(M, device=lt.device)[None, :] < nk[:, None]
+        elpd = torch.where(mask, lt, torch.zeros((), dtype=lt.dtype, device=lt.device)).sum(1)
+    out = dict(mean=m1, var=var, log_moments=lmom, lpd=lpd, elpd=elpd)
+    if not as_torch:
+        out = {n: None if t is None else np.asarray(eng.to_numpy(t)) for n, t in out.items()}
+    return NegBinPrediction(psis=psis, num_draws=S, nlaunch=nlaunch, **out)
 
 
 def _check_labels(y, C, live):

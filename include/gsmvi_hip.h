@@ -39,6 +39,8 @@
  *   the same for K fitted negative binomial regressions (no reference twin) -> gsmvi_psis_loo_negbin_batched_f64, gsmvi_psis_loo_negbin_tile
  *   examples/example_gsm.py:34-35 the use of the fit for K fitted multinomial logit regressions: class probabilities and the held-out
  *   score from draws of q_k (no reference twin)                        ->  gsmvi_softmax_predict_batched_f64, gsmvi_softmax_predict_lds_bytes
+ *   the same use for K fitted negative binomial regressions: log moments of the predictive count and the held-out score from
+ *   draws of q_k (no reference twin)                                   ->  gsmvi_negbin_predict_batched_f64
  *   gsmvi/bam.py:72-114       bam_lowrank_update(samples,vs,mu0,S0,reg) ->  gsmvi_bam_update_f64
  *   gsmvi/bam.py:31-69        bam_update(samples,vs,mu0,S0,reg)         ->  gsmvi_bam_update_f64 (same result, K6)
  *
@@ -310,10 +312,10 @@ int gsmvi_get_profile(gsmvi_ctx* ctx, float* ms, int n);
 #define GSMVI_PATH_BATCHED_BAM 0x4000u     /* k_bam_batched: the batched BaM entry points                           */
 #define GSMVI_PATH_BATCHED_KL 0x8000u      /* k_kl_batched: the batched KL monitor's entry points                  */
 #define GSMVI_PATH_BATCHED_ADVI 0x10000u   /* k_advi_batched / k_advi_cov_batched: the batched ADVI entry points   */
-#define GSMVI_PATH_BATCHED_TARGET 0x20000u /* k_logistic_batched: the batched non-Gaussian target's entry point; with GSMVI_PATH_BATCHED_LAPLACE in one call: k_laplace_shared_batched or k_negbin_laplace_batched; with GSMVI_PATH_BATCHED_LOO in one call: k_psis_loo_negbin_batched (all 32 bits are taken; no other call sets either pair) */
+#define GSMVI_PATH_BATCHED_TARGET 0x20000u /* k_logistic_batched: the batched non-Gaussian target's entry point; with GSMVI_PATH_BATCHED_LAPLACE in one call: k_laplace_shared_batched or k_negbin_laplace_batched; with GSMVI_PATH_BATCHED_LOO in one call: k_psis_loo_negbin_batched; with GSMVI_PATH_BATCHED_PREDICT in one call: k_negbin_predict_batched (all 32 bits are taken; no other call sets any of these pairs) */
 #define GSMVI_PATH_BATCHED_LBFGS 0x40000u  /* k_lbfgs_step_batched / k_lbfgs_hess_inv_batched: the batched initialiser   */
 #define GSMVI_PATH_BATCHED_LAPLACE 0x80000u /* k_laplace_batched: the batched GLM Hessian and Newton step; with GSMVI_PATH_BATCHED_TARGET in one call: k_laplace_shared_batched, the shared-design Hessian and Newton step, or k_negbin_laplace_batched, the negative binomial one */
-#define GSMVI_PATH_BATCHED_PREDICT 0x100000u /* k_glm_predict_batched: the batched GLM posterior predictive; with GSMVI_PATH_BATCHED_SOFTMAX: k_softmax_predict_batched */
+#define GSMVI_PATH_BATCHED_PREDICT 0x100000u /* k_glm_predict_batched: the batched GLM posterior predictive; with GSMVI_PATH_BATCHED_SOFTMAX: k_softmax_predict_batched; with GSMVI_PATH_BATCHED_TARGET: k_negbin_predict_batched */
 #define GSMVI_PATH_BATCHED_PSIS 0x200000u /* k_psis_batched: the batched Pareto-smoothed importance diagnostic            */
 #define GSMVI_PATH_BATCHED_LOO 0x400000u /* k_psis_loo_batched: the batched PSIS leave-one-out; with GSMVI_PATH_BATCHED_SOFTMAX: k_psis_loo_softmax_batched; with GSMVI_PATH_BATCHED_TARGET: k_psis_loo_negbin_batched */
 #define GSMVI_PATH_GSM_TWO_LAUNCH 0x800000u /* the dense GSM update ran as two launches (no k_gsm_scalars_fast, no records)          */
@@ -1145,6 +1147,51 @@ int gsmvi_softmax_predict_lds_bytes(int C, int P);
 int gsmvi_softmax_predict_batched_f64(gsmvi_ctx* ctx, void* stream, int64_t K, int C, int P, int64_t M, int64_t S,
                                       const double* A, const int* labels, const int* counts_dev, const double* X,
                                       const double* lw, double* prob, double* lpd);
+
+/*
+ * Batched negative binomial posterior predictive: what the fitted q_k = N(mean_k, cov_k) of K overdispersed count regressions (the
+ * model of gsmvi_negbin_batched_f64) says about M new rows per problem, from S draws of q_k: three log moments of the predictive
+ * count and, with the rows' counts, the log predictive density of every row (the held-out score, on the scale of
+ * gsmvi_psis_loo_negbin_batched_f64).  theta = log r is a coordinate of q_k and is correlated with beta, so a row's density depends
+ * on the pair (eta, theta) and the one-dimensional quadrature of gsmvi_glm_predict_batched_f64 does not apply; the draws are those
+ * of gsmvi_kl_draw_batched_f64, optionally with the smoothed weights of gsmvi_psis_batched_f64.  The reference has no twin.  One
+ * launch, one 256-thread workgroup per (problem, tile of 16 new rows).
+ * A (K x M x P) are the new rows, y (K x M, or NULL) their counts >= 0, offset (K x M, or NULL) is added to the linear predictor,
+ * n_k = counts_dev[k] clamped to 0 .. M valid rows (M without counts_dev), X (K x S x D, D = P + 1 <= 64) the draws x_s = (beta_s,
+ * theta_s) of q_k.  lw (K x S, or NULL) are normalised log weights, e.g. the log_weights of gsmvi_psis_batched_f64 for the same
+ * draws; NULL means uniform: lw_s = -log S.  For a valid row i < n_k and draw s:
+ *   eta_si = a_i . beta_s + o_i,   theta_s = x_s[P],   r_s = e^theta_s
+ *   lmom[k, i, 0] = log sum_s exp(lw_s + eta_si)                 (log E[mu])
+ *   lmom[k, i, 1] = log sum_s exp(lw_s + 2 eta_si)               (log E[mu^2])
+ *   lmom[k, i, 2] = log sum_s exp(lw_s + 2 eta_si - theta_s)     (log E[mu^2 / r])
+ *   l_si   = t(eta_si, theta_s, y_i) - lgamma(y_i + 1)
+ *   lpd[k, i]     = log sum_s exp(lw_s + l_si)
+ * with t the per-row density term of gsmvi_negbin_batched_f64 at the same eta (the same device function, whole).  The predictive
+ * mean is e^lmom0 and the predictive variance E[mu + mu^2 / r] + Var[mu] = e^lmom0 + e^lmom2 + e^lmom1 - e^(2 lmom0); they are left
+ * to the caller because e^lmom0 overflows above 709.78 where the logs do not.  The term -lgamma(y_i + 1) is INCLUDED, as in
+ * gsmvi_psis_loo_negbin_batched_f64.  Without y the density is not evaluated.
+ * All four are log-sum-exps that cannot overflow or underflow where the truth is finite: a fixed tree of (max, scaled sum) pairs
+ * merged as (m1, s1) + (m2, s2) = (M, s1 e^(m1 - M) + s2 e^(m2 - M)), M = max(m1, m2); a pair whose maximum is -inf contributes 0;
+ * e^eta is never formed.  Every sum is a fixed tree or chain (a lane's entries in order, a fixed cross-lane order, the draw tiles
+ * in order, the waves in order; no atomics): the outputs are bit-identical from run to run.
+ * Draws s >= S of a partial tile contribute nothing (masked, not weighted).  A draw s < S is flagged when one of its D entries,
+ * theta included, is not finite, or when e^theta is not a positive normal number (|theta| above about 708: the row flag of
+ * gsmvi_negbin_batched_f64); the flag is taken from the draw's entries, not from the product, and a flagged draw makes every valid
+ * row of its problem NaN whatever its weight.  A non-finite eta_si at a draw s < S (a non-finite entry of a_i or o_i) makes the
+ * outputs of row i NaN.  A problem whose lw holds a NaN or +inf, or only -inf, has NaN in every valid row (a lone -inf is legal:
+ * weight 0).  Rows i >= n_k are never loaded and their outputs are NaN.  A verdict touches only its own (k, i) or k.  Outputs:
+ * lmom (K x M x 3, required) and lpd (K x M): required exactly when y is given, NULL otherwise.
+ * The launch asks for 8 (80 (4 ceil(P / 4) + 1) + 824) bytes of dynamic LDS, at most 48192 (P = 63).
+ * P >= 1, D = P + 1 <= 64, 1 <= S <= 4096, M >= 1, 1 <= K <= 2^24 - 1 with K ceil(M / 16) <= 2^24 - 1.  Shapes, NULL arrays, the
+ * y / lpd pairing and overlaps (lmom and lpd are the written arrays, everything else is read) are checked before the context is
+ * looked at (then a NULL ctx); every failure returns GSMVI_ERR_BAD_ARG before anything is enqueued.  Inputs are only read; no
+ * context workspace is used; one capturable launch with no host synchronisation and no atomics.  Sets GSMVI_PATH_BATCHED_PREDICT |
+ * GSMVI_PATH_BATCHED_TARGET: after a reset exactly that pair identifies this launch (the GLM predictive sets the first bit alone,
+ * the negative binomial score launch the second alone).
+ */
+int gsmvi_negbin_predict_batched_f64(gsmvi_ctx* ctx, void* stream, int64_t K, int P, int64_t M, int64_t S, const double* A,
+                                     const double* y, const double* offset, const int* counts_dev, const double* X,
+                                     const double* lw, double* lmom, double* lpd);
 
 /*
  * Upper Cholesky factor R (R^T R = S, R upper triangular, strictly-lower part zeroed) of a
