@@ -101,7 +101,7 @@ __global__ __launch_bounds__(256) void k_psis_loo_batched(pl_args a) {
     }
     __syncthreads();                          // l_si is published; the tiles are dead, the stage may take their place
 
-    ps_loo_stage(a.o, sm, ell, ni, nv, ks, kn, S, S2, M, l);     // (2)
+    ps_loo_stage(a.o, sm, ell, ni, nv, nullptr, ks, kn, S, S2, M, l);     // (2)
 }
 
 hipError_t gsmvi_psis_loo_batched_prepare() {

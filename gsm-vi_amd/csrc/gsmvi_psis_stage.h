@@ -1,8 +1,10 @@
 // The PSIS stage of the batched diagnostics: steps 1-8 of the definition in include/gsmvi_hip.h (gsmvi_psis_weights_batched_f64)
 // on the S log ratios that one 256-thread workgroup holds in LDS.  One copy, called by k_psis_batched<PS_WEIGHTS>,
 // k_psis_batched<PS_FUSED> (gsmvi_psis_batched.hip: once per problem) and, once per observation, by ps_loo_stage at the end of this
-// file: the observation stage of the two leave-one-out kernels, k_psis_loo_batched (gsmvi_psis_loo_batched.hip) and
-// k_psis_loo_softmax_batched (gsmvi_psis_loo_softmax_batched.hip), with the tile geometry the two share; DESIGN.md section 9.
+// file: the observation stage of the leave-one-out kernels, k_psis_loo_batched (gsmvi_psis_loo_batched.hip),
+// k_psis_loo_softmax_batched (gsmvi_psis_loo_softmax_batched.hip), k_psis_loo_negbin_batched (gsmvi_psis_loo_negbin_batched.hip) and,
+// with observation weights, k_psis_loo_shared_batched (gsmvi_psis_loo_shared_batched.hip), with the tile geometry they share;
+// DESIGN.md section 9.
 // In LDS: the S ratios padded with +inf to S2 = the next power of two, their S2 indices, the S normalised weights in row order,
 // the tail (at most 192 exceedances) and the 43 candidates of its fit.  Two reductions (non-finite count, maximum); a bitonic
 // network on (value, index) pairs, ascending by value then by index -- numpy's stable argsort, so ties fall the same way on
@@ -251,17 +253,20 @@ struct ps_loo_io {
     int* info;                  // (K, N) 0; -1 non-finite ratios; -2 tail too short; -3 not a valid row
 };
 
-// Stage (2), per observation i < ni of the tile (the first nv are valid rows): rho_s = logr_s - l_si into the stage's array,
-// ps_stage, then the two log-sum-exps -- the maximum by a block reduction, then the sum of exp(. - max) -- elpd from the stage's
-// weights, lpd from the problem-level weights lw.  ell: the tile's l_si in LDS (NI x S, published by a barrier before the call);
-// ks = k S, kn = k N + the tile's first observation.
-__device__ __forceinline__ void ps_loo_stage(const ps_loo_io a, const ps_lds sm, const double* ell, int ni, int nv, size_t ks,
-                                             size_t kn, int S, int S2, int M, int l) {
+// Stage (2), per observation i < ni of the tile: rho_s = logr_s - l_si into the stage's array, ps_stage, then the two
+// log-sum-exps -- the maximum by a block reduction, then the sum of exp(. - max) -- elpd from the stage's weights, lpd from the
+// problem-level weights lw.  ell: the tile's l_si in LDS (NI x S, published by a barrier before the call); ks = k S, kn = k N + the
+// tile's first observation.  w: null -- the first nv rows of the tile are the valid ones -- or the observation weights of the
+// tile's ni rows (k_psis_loo_shared_batched; nv is then not used): row i is valid iff w_i > 0 (not for 0 or NaN), and leaving it
+// out removes its whole weighted term, rho_s = logr_s - w_i l_si (w_i = 1: the product is exact, the same bits as without w).
+__device__ __forceinline__ void ps_loo_stage(const ps_loo_io a, const ps_lds sm, const double* ell, int ni, int nv, const double* w,
+                                             size_t ks, size_t kn, int S, int S2, int M, int l) {
     const double qnan = __longlong_as_double(0x7ff8000000000000LL), inf = __builtin_huge_val();
     for (int i = 0; i < ni; ++i) {
         const size_t ki = kn + i;
         double* lk = a.loglik ? a.loglik + ki * S : nullptr;
-        if (i >= nv) {                        // not a valid row (uniform in the workgroup: no barrier is skipped by a part of it)
+        const double wi = w ? w[i] : 1.0;
+        if (w ? !(wi > 0.0) : i >= nv) {      // not a valid row (uniform in the workgroup: no barrier is skipped by a part of it)
             if (lk)
                 for (int s = l; s < S; s += 256) lk[s] = qnan;
             if (l == 0) {
@@ -276,7 +281,7 @@ __device__ __forceinline__ void ps_loo_stage(const ps_loo_io a, const ps_lds sm,
         const double* el = ell + i * S;
         for (int s = l; s < S; s += 256) {
             const double e = el[s];
-            sm.val[s] = a.logr[ks + s] - e;
+            sm.val[s] = w ? a.logr[ks + s] - wi * e : a.logr[ks + s] - e;
             if (lk) lk[s] = e;
         }
         __syncthreads();

@@ -6,8 +6,9 @@ effective sample size, an estimate of the log normalising constant, and importan
 the same draws one step further for the GLM targets: the PSIS leave-one-out log predictive density of every observation
 (csrc/gsmvi_psis_loo_batched.hip; Vehtari, Gelman, Gabry 2017; Magnusson, Andersen, Jonasson, Vehtari 2019), the number by which
 fitted models are compared; ``psis_loo_softmax_batched`` is the same for ``BatchedSoftmaxTarget``
-(csrc/gsmvi_psis_loo_softmax_batched.hip) and ``psis_loo_negbin_batched`` for ``BatchedNegBinomialTarget``
-(csrc/gsmvi_psis_loo_negbin_batched.hip)."""
+(csrc/gsmvi_psis_loo_softmax_batched.hip), ``psis_loo_negbin_batched`` for ``BatchedNegBinomialTarget``
+(csrc/gsmvi_psis_loo_negbin_batched.hip) and ``psis_loo_shared_batched`` for ``SharedDesignGLMTarget``, observation weights
+honoured (csrc/gsmvi_psis_loo_shared_batched.hip)."""
 from dataclasses import dataclass
 
 import numpy as np
@@ -138,7 +139,10 @@ class LOOBatchedResult:
     sqrt(n_k var(elpd_i)) with the unbiased variance over the n_k valid rows (NaN for n_k < 2), ``n_bad`` = the valid rows with
     ``info`` != 0 or ``khat`` >= ``threshold``, ``ok`` = ``psis.ok`` & (``n_bad`` == 0).  ``loglik`` (K, N, S) the pointwise log
     likelihood of every draw, or None; ``psis`` the problem-level ``PSISBatchedResult`` (device tensors: hand it back as
-    ``psis=`` to reuse its draws); ``threshold`` = min(1 - 1 / log10(S), 0.7); ``nlaunch`` the kernel launches made."""
+    ``psis=`` to reuse its draws); ``threshold`` = min(1 - 1 / log10(S), 0.7); ``nlaunch`` the kernel launches made.
+    From ``psis_loo_shared_batched`` with observation weights v_ki the valid rows are those with v_ki > 0, ``elpd_i`` and ``lpd_i``
+    are densities of ONE unit observation (unweighted), and the sums are weighted: with c_i = v_ki ``elpd_i``, ``elpd_loo`` = sum
+    c_i, ``p_loo`` = sum v_ki (``lpd_i`` - ``elpd_i``), ``se`` = sqrt(n_k var(c_i)) over the n_k valid rows."""
     elpd_loo: object
     p_loo: object
     se: object
@@ -176,22 +180,35 @@ def _reusable(psis, K, D, eng, fn="psis_loo_batched"):
     return X, logr, lw
 
 
-def _loo_result(eng, target, psis, S, nlaunch, as_torch, elpd_i, lpd_i, khat, ess, info, loglik):
+def _loo_result(eng, target, psis, S, nlaunch, as_torch, elpd_i, lpd_i, khat, ess, info, loglik, weights=None, by_weights=False):
     """The ``LOOBatchedResult`` of the pointwise outputs of a leave-one-out launch (``psis_loo_batched``,
-    ``psis_loo_softmax_batched`` and ``psis_loo_negbin_batched``): the per-problem summaries are torch reductions under the mask of the valid rows of
-    ``target.counts`` (a stand-in engine's numpy arrays: on the host)"""
+    ``psis_loo_softmax_batched``, ``psis_loo_negbin_batched`` and ``psis_loo_shared_batched``): the per-problem summaries are torch
+    reductions under the mask of the valid rows (a stand-in engine's numpy arrays: on the host).  The valid rows are the first
+    ``target.counts[k]``, or with ``by_weights`` (the shared design, which has no counts) the rows whose weight in ``weights``
+    (K, N) is > 0, every row for None; the sums are then weighted: c_i = v_i elpd_i, p_loo = sum v_i (lpd_i - elpd_i).  Weights
+    of 0 and 1 give the unweighted sums bit for bit."""
     import torch
     K, N = target.K, target.N
     thr = khat_threshold(S)
     ten = lambda a: a if isinstance(a, torch.Tensor) else torch.as_tensor(np.asarray(a))      # noqa: E731
     e, lp_, kh, inf = ten(elpd_i), ten(lpd_i), ten(khat), ten(info)
-    nk = ten(target.counts).to(e.device).clamp(0, N) if target.counts is not None else torch.full((K,), N, device=e.device)
-    mask = torch.arange(N, device=e.device)[None, :] < nk[:, None]
+    c, d = e, lp_ - e
+    if by_weights and weights is not None:
+        v = ten(weights).to(e.device)
+        mask = v > 0.0
+        nk = mask.sum(1)
+        c, d = v * c, v * d
+    elif by_weights:
+        nk = torch.full((K,), N, device=e.device)
+        mask = torch.ones((K, N), dtype=torch.bool, device=e.device)
+    else:
+        nk = ten(target.counts).to(e.device).clamp(0, N) if target.counts is not None else torch.full((K,), N, device=e.device)
+        mask = torch.arange(N, device=e.device)[None, :] < nk[:, None]
     zero = torch.zeros((), dtype=e.dtype, device=e.device)
     nf = nk.to(e.dtype)
-    elpd_loo = torch.where(mask, e, zero).sum(1)
-    p_loo = torch.where(mask, lp_ - e, zero).sum(1)
-    dev = torch.where(mask, e - (elpd_loo / nf)[:, None], zero)
+    elpd_loo = torch.where(mask, c, zero).sum(1)
+    p_loo = torch.where(mask, d, zero).sum(1)
+    dev = torch.where(mask, c - (elpd_loo / nf)[:, None], zero)
     se = torch.sqrt(nf * ((dev * dev).sum(1) / (nf - 1.0)))
     se = torch.where(nk >= 2, se, torch.full_like(se, float("nan")))
     n_bad = (mask & ((inf != 0) | (kh >= thr))).sum(1)
@@ -205,7 +222,7 @@ def _loo_result(eng, target, psis, S, nlaunch, as_torch, elpd_i, lpd_i, khat, es
 
 
 def _loo_draws(fn, target, mean, cov, keys, num_draws, call, psis, engine):
-    """The argument checks and the problem-level run shared by the three leave-one-out functions: (eng, psis, nlaunch, X, logr, lw)"""
+    """The argument checks and the problem-level run shared by the four leave-one-out functions: (eng, psis, nlaunch, X, logr, lw)"""
     K, D = target.K, target.D
     if _shape(mean) != (K, D):
         raise ValueError(f"{fn}: mean must be (K, D) = {(K, D)} of the target, got {_shape(mean)}")
@@ -243,9 +260,11 @@ def psis_loo_batched(target, mean, cov, keys, num_draws=1024, *, call=0, psis=No
     A mean that is not (K, D) of the target, a cov that is not (K, D, D), ``num_draws`` outside 5..4096, keys of another length
     than K, or a ``psis`` that is not a ``PSISBatchedResult`` holding device tensors of the right shapes raise ValueError before
     any device work."""
-    from .targets import BatchedGLMTarget
+    from .targets import BatchedGLMTarget, SharedDesignGLMTarget
     if not isinstance(target, BatchedGLMTarget):
-        raise TypeError(f"psis_loo_batched: target must be a BatchedGLMTarget or BatchedLogisticTarget, got {type(target).__name__}")
+        hint = "; call psis_loo_shared_batched(target, ...) for it" if isinstance(target, SharedDesignGLMTarget) else ""
+        raise TypeError(f"psis_loo_batched: target must be a BatchedGLMTarget or BatchedLogisticTarget, got "
+                        f"{type(target).__name__}{hint}")
     eng, psis, nlaunch, X, logr, lw = _loo_draws("psis_loo_batched", target, mean, cov, keys, num_draws, call, psis, engine)
     S = _shape(X)[1]
     elpd_i, lpd_i, khat, ess, info, loglik = eng.psis_loo_batched(
@@ -312,3 +331,38 @@ def psis_loo_negbin_batched(target, mean, cov, keys, num_draws=1024, *, call=0, 
     elpd_i, lpd_i, khat, ess, info, loglik = eng.psis_loo_negbin_batched(
         X, logr, lw, target.A, target.y, offset=target.offset, counts=target.counts, pointwise_loglik=bool(pointwise_loglik))
     return _loo_result(eng, target, psis, S, nlaunch, as_torch, elpd_i, lpd_i, khat, ess, info, loglik)
+
+
+def psis_loo_shared_batched(target, mean, cov, keys, num_draws=1024, *, call=0, psis=None, pointwise_loglik=False, as_torch=False,
+                            engine=None):
+    """PSIS leave-one-out of K fitted GLM posteriors q_k = N(mean_k, cov_k) on ONE design matrix: returns a ``LOOBatchedResult``,
+    the twin of ``psis_loo_batched`` for ``SharedDesignGLMTarget`` -- which lambda of a sweep, which response, which bootstrap
+    replicate predicts best -- with no copy of A per problem and the observation weights honoured.
+
+    ``target`` is the ``SharedDesignGLMTarget`` the posteriors were fitted to (its A, y, offset, weights and noise precision are
+    the model; anything else raises TypeError); mean (K, D), cov (K, D, D) and ``keys`` are ``psis_batched``'s.  Without ``psis``
+    it first runs ``psis_batched(target.lp, mean, cov, keys, num_draws, call=call, moments=False, as_torch=True)`` (two launches
+    and one call of ``target.lp``, the weighted density); with ``psis``, the result of such a call, its draws, ratios and weights
+    are reused (``num_draws`` and ``call`` are then not used).  Then one launch, gsmvi_psis_loo_shared_batched_f64 (the
+    definition is in include/gsmvi_hip.h).  Row i of problem k is valid iff its weight v_ki is > 0 (no weights: every row): any
+    subset of the rows, and what y and the offset hold at the others is never looked at; those rows get ``info`` = -3 and NaN.
+    The pointwise log likelihood l_si is that of ONE unit observation at row i, normalised as ``psis_loo_batched`` does and
+    unweighted; leaving row i out removes its whole weighted term, so the PSIS stage runs on logr_s - v_ki l_si.  The sums are
+    weighted, over the n_k valid rows with c_i = v_ki elpd_i: ``elpd_loo`` = sum c_i, ``p_loo`` = sum v_ki (lpd_i - elpd_i),
+    ``se`` = sqrt(n_k var(c_i)).  With weights None, all ones, or 0 / 1 these are ``psis_loo_batched``'s numbers on the replicated
+    design, bit for bit.  A row of weight 0 is NOT scored as a held-out row: K-fold cross-validation through the weights is not
+    what this computes.  ``pointwise_loglik`` also returns the (K, N, S) block l_si.  mean and cov are only read.
+    A mean that is not (K, D) of the target, a cov that is not (K, D, D), ``num_draws`` outside 5..4096, keys of another length
+    than K, or a ``psis`` that is not a ``PSISBatchedResult`` holding device tensors of the right shapes raise ValueError before
+    any device work."""
+    from .targets import SharedDesignGLMTarget
+    fn = "psis_loo_shared_batched"
+    if not isinstance(target, SharedDesignGLMTarget):
+        raise TypeError(f"{fn}: target must be a SharedDesignGLMTarget, got {type(target).__name__}")
+    eng, psis, nlaunch, X, logr, lw = _loo_draws(fn, target, mean, cov, keys, num_draws, call, psis, engine)
+    S = _shape(X)[1]
+    elpd_i, lpd_i, khat, ess, info, loglik = eng.psis_loo_shared_batched(
+        X, logr, lw, target.A, target.y, target.family, offset=target.offset, weights=target.weights,
+        noise_prec=target.noise_precision, pointwise_loglik=bool(pointwise_loglik))
+    return _loo_result(eng, target, psis, S, nlaunch, as_torch, elpd_i, lpd_i, khat, ess, info, loglik, weights=target.weights,
+                       by_weights=True)

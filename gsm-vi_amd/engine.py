@@ -1385,6 +1385,32 @@ class HipEngine:
                    self._packed(ess, (K, N), "ess"), self._ints(info, K * N, "info"))
         return elpd, lpd, khat, ess, info, loglik
 
+    # ---- the same for K fitted GLM posteriors on ONE design matrix, weighted (csrc/gsmvi_psis_loo_shared_batched.hip) -------------
+    def psis_loo_shared_batched(self, X, logr, lw, A, y, family, offset=None, weights=None, noise_prec=1.0, pointwise_loglik=False):
+        """PSIS leave-one-out of K fitted GLM posteriors that share ONE design matrix, from the draws X (K, S, D) of q_k and the
+        problem-level ratios ``logr`` and smoothed weights ``lw`` (K, S) of ``psis_batched`` on the same draws, one launch with no
+        copy of A per problem (gsmvi_psis_loo_shared_batched_f64; the definition is in include/gsmvi_hip.h)  [no reference twin]:
+        returns what ``psis_loo_batched`` returns, (elpd, lpd, khat, ess (K, N), info (K, N) int32, loglik (K, N, S) or None).
+        ``A`` (N, D) shared, ``y`` (K, N), ``offset`` and ``weights`` None or (K, N), ``family`` and ``noise_prec`` are
+        ``glm_shared_batched``'s.  Row i of problem k is valid iff its weight is > 0 (any subset of the rows; the others get
+        info = -3 and NaN); the pointwise log likelihood is that of one unit observation, unweighted, and leaving row i out removes
+        weight x log likelihood from the ratios.  The tile of observations per workgroup is ``psis_loo_tile(D, S)``."""
+        K, S, D = X.shape
+        N = A.shape[0]
+        fam, t, tp = self._glm_family_args(family, noise_prec, K)
+        self._any_ctx()
+        X, logr, lw = X.contiguous(), logr.contiguous(), lw.contiguous()
+        elpd, lpd, khat, ess = self.empty(K, N), self.empty(K, N), self.empty(K, N), self.empty(K, N)
+        info = self.batched_ints(K * N).view(K, N)
+        loglik = self.empty(K, N, S) if pointwise_loglik else None
+        self._call("gsmvi_psis_loo_shared_batched_f64", fam, K, N, D, S, self._packed(A, (N, D), "A"),
+                   self._packed(y, (K, N), "y"), self._dp(offset, (K, N), "offset"), self._dp(weights, (K, N), "weights"), t, tp,
+                   self._packed(X, (K, S, D), "X"), self._packed(logr, (K, S), "logr"), self._packed(lw, (K, S), "lw"),
+                   self._dp(loglik, (K, N, S), "loglik"), self._packed(elpd, (K, N), "elpd"),
+                   self._packed(lpd, (K, N), "lpd"), self._packed(khat, (K, N), "khat"), self._packed(ess, (K, N), "ess"),
+                   self._ints(info, K * N, "info"))
+        return elpd, lpd, khat, ess, info, loglik
+
     # ---- batched softmax posterior predictive: the use of K fitted multinomial logit posteriors (csrc/gsmvi_softmax_predict_batched.hip)
     def softmax_predict_lds_bytes(self, C, P):
         """gsmvi_softmax_predict_lds_bytes: the dynamic LDS in bytes of one workgroup of ``softmax_predict_batched`` at (C, P), 0

@@ -435,8 +435,10 @@ class SharedDesignGLMTarget:
     ``lp_g(x, out=None)``: (K, B, D) -> (K, B, D) scores, ``device_native`` and ``graph_safe`` (one capturable launch, no
     allocation with ``out``).  ``lp(x)``: (K, rows, D) -> (K, rows) values.  ``lp_and_score(x)``: (scores, values) from one launch.
     Not a ``BatchedGLMTarget``: it has no ``neg_hessian``, ``predict`` or ``loo``, and ``laplace_init_batched``,
-    ``psis_loo_batched`` refuse it.  Its negative Hessian is ``neg_hessian_shared_batched(target, x)`` and its second-order start
-    ``laplace_init_shared_batched(target, ...)``, both on the shared design without a copy per problem."""
+    ``psis_loo_batched`` refuse it.  Its negative Hessian is ``neg_hessian_shared_batched(target, x)``, its second-order start
+    ``laplace_init_shared_batched(target, ...)`` and its PSIS leave-one-out ``psis_loo_shared_batched(target, mean, cov, keys,
+    ...)`` (weighted sums over the rows of weight > 0), all on the shared design without a copy per problem; a posterior
+    predictive stays absent."""
 
     FAMILIES = BatchedGLMTarget.FAMILIES
 

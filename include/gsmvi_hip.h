@@ -37,6 +37,7 @@
  *   GLMs (no reference twin)                                           ->  gsmvi_psis_loo_batched_f64, gsmvi_psis_loo_tile
  *   the same for K fitted multinomial logit regressions (no reference twin) -> gsmvi_psis_loo_softmax_batched_f64, gsmvi_psis_loo_softmax_tile
  *   the same for K fitted negative binomial regressions (no reference twin) -> gsmvi_psis_loo_negbin_batched_f64, gsmvi_psis_loo_negbin_tile
+ *   the same for K fitted GLMs on one design matrix, weighted (no reference twin) -> gsmvi_psis_loo_shared_batched_f64
  *   examples/example_gsm.py:34-35 the use of the fit for K fitted multinomial logit regressions: class probabilities and the held-out
  *   score from draws of q_k (no reference twin)                        ->  gsmvi_softmax_predict_batched_f64, gsmvi_softmax_predict_lds_bytes
  *   the same use for K fitted negative binomial regressions: log moments of the predictive count and the held-out score from
@@ -1101,6 +1102,48 @@ int gsmvi_psis_loo_negbin_batched_f64(gsmvi_ctx* ctx, void* stream, int64_t K, i
                                       const double* y, const double* offset, const int* counts_dev, const double* X,
                                       const double* logr, const double* lw, double* loglik, double* elpd, double* lpd,
                                       double* khat, double* ess, int* info);
+
+/*
+ * Shared-design PSIS leave-one-out: the same for K fitted posteriors of the model of gsmvi_glm_shared_batched_f64: K GLMs on ONE
+ * design matrix with observation weights.  The reference has no twin.  One launch, one workgroup per (problem, tile of
+ * gsmvi_psis_loo_tile(D, S) consecutive observations), k-major; A is never replicated.
+ * A (N x D) is the one design matrix with rows a_i.  Problem k has responses y_ki (K x N, required), an optional offset o_ki (K x N, or
+ * NULL), observation weights v_ki >= 0 (K x N, or NULL: every v = 1), the noise precision tau_k (noise_prec / noise_prec_dev: the
+ * gaussian family's alone) and no prior.  X (K x S x D) are the draws x_s of q_k; logr (K x S) and lw (K x S) are what
+ * gsmvi_psis_batched_f64 writes for the same draws, logr from the WEIGHTED density lp_k(x) = sum_i v_ki t_ki(x) - lam_k |x|^2 / 2.
+ * Row i of problem k is valid iff v_ki > 0: the selection of gsmvi_glm_shared_hessian_batched_f64.  A weight of 0 or NaN removes
+ * the row whatever y and the offset hold there (they are never fed to the link); the valid rows are an arbitrary subset, not a
+ * prefix.  For a valid row:
+ *   eta_si = a_i . x_s + o_ki
+ *   l_si   = the log density of ONE unit observation, UNWEIGHTED: l_si of gsmvi_psis_loo_batched_f64 exactly (the poisson family
+ *            subtracts lgamma(y + 1), the gaussian family adds log(tau_k / (2 pi)) / 2; a flagged draw has l_si = NaN)
+ *   rho_si = logr_s - v_ki l_si (one product, one subtraction, not fused): leaving row i out removes its whole weighted term.  With
+ *            v_ki = 1 the product is exact and rho has the bits of gsmvi_psis_loo_batched_f64
+ * From there on the text is that of gsmvi_psis_loo_batched_f64 above, word for word:
+ *   the PSIS stage, steps 1-8 of gsmvi_psis_weights_batched_f64 exactly (the (value, row) order of the sort and the -1 / -2
+ *   verdicts included), on rho_.i gives the normalised smoothed log weights w_si, khat[k, i], ess[k, i] and info[k, i]
+ *   elpd[k, i] = log sum_s exp(w_si + l_si):  the leave-one-out log predictive density of one unit observation at row i
+ *   lpd[k, i]  = log sum_s exp(lw_s + l_si)
+ * both as max + log sum exp(. - max), the maximum and the sum each a fixed tree over the S draws: the outputs are bit-identical from
+ * run to run.  info[k, i] = -1 (a NaN or +inf among rho_.i, or every rho -inf): elpd, lpd, khat and ess of (k, i) are NaN.
+ * info[k, i] = -2 (fewer than five tail entries): plain self-normalised weights and khat = +inf.  A row that is not valid has NaN in
+ * elpd, lpd, khat and ess and info[k, i] = -3; it flags nothing else.  A verdict touches only its own (k, i).  loglik (K x N x S, or
+ * NULL) receives l_si (NaN for the rows that are not valid).  Outputs: elpd, lpd, khat, ess (K x N doubles each) and info (K x N
+ * ints), all required.  The per-problem sums are the caller's: with c_i = v_ki elpd[k, i] over the n_k valid rows, elpd_loo = sum
+ * c_i, p_loo = sum v_ki (lpd - elpd), se = sqrt(n_k var(c_i)).  A row of weight 0 is NOT scored as a held-out row.
+ * With weights NULL or all 1 every output has the bits of gsmvi_psis_loo_batched_f64 on K copies of A; with 0 / 1 weights that form
+ * a prefix, those of its counts_dev.
+ * 1 <= D <= 64, 5 <= S <= 4096, N >= 1, K >= 1 with K ceil(N / gsmvi_psis_loo_tile(D, S)) <= 2^24 - 1, K N S doubles addressable.
+ * Shapes, NULL arrays and overlaps (loglik, elpd, lpd, khat, ess and info are the written arrays, everything else is read; A counts
+ * N D doubles) are checked before the context is looked at (then a NULL ctx); every failure returns GSMVI_ERR_BAD_ARG before
+ * anything is enqueued.  Inputs are only read; no context workspace is used; one capturable launch with no host synchronisation
+ * and no atomics.  Sets GSMVI_PATH_BATCHED_LOO | GSMVI_PATH_BATCHED_TARGET (no bit of its own).
+ */
+int gsmvi_psis_loo_shared_batched_f64(gsmvi_ctx* ctx, void* stream, int family, int64_t K, int64_t N, int D, int64_t S,
+                                      const double* A, const double* y, const double* offset, const double* weights,
+                                      double noise_prec, const double* noise_prec_dev, const double* X, const double* logr,
+                                      const double* lw, double* loglik, double* elpd, double* lpd, double* khat, double* ess,
+                                      int* info);
 
 /*
  * Batched softmax posterior predictive: what the fitted q_k = N(mean_k, cov_k) of K multinomial logit regressions (the model of
