@@ -64,6 +64,11 @@ Mirrors the reference's public surface for the hot path (reference file:line):
     for K fitted negative binomial posteriors: mean and
     variance of the predictive count from three log
     moments, held-out elpd on the leave-one-out's scale) examples/example_gsm.py:34-35, the use of the fit; no reference twin
+    predict_shared_batched (the GLM predictive of K
+    fitted posteriors of a SharedDesignGLMTarget on
+    ONE set of new rows with per-problem row weights:
+    the held-out score of K-fold cross-validation;
+    one launch, no copy of the rows per problem)   examples/example_gsm.py:34-35, the use of the fit; no reference twin
     lbfgs_init_batched (the L-BFGS initialiser
     for K problems at once, D <= 64: one launch
     per function evaluation after lp_g and lp)   gsmvi/initializers.py:5-17
@@ -105,6 +110,7 @@ from .targets import BatchedNegBinomialTarget                        # noqa: F40
 from .targets import predict_softmax_batched, SoftmaxPrediction      # noqa: F401
 from .targets import predict_negbin_batched, NegBinPrediction        # noqa: F401
 from .targets import neg_hessian_shared_batched                      # noqa: F401
+from .targets import predict_shared_batched                          # noqa: F401
 from .targets import neg_hessian_negbin_batched                      # noqa: F401
 from .batched import GSMBatch, gsm_update_batched                    # noqa: F401
 from .batched import BaMBatch, bam_update_batched, bam_lowrank_update_batched   # noqa: F401

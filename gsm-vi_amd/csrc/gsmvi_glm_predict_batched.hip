@@ -26,6 +26,7 @@
 //   quad  the tile's LDS is free by now and holds the node values: 8 adjacent lanes share a row (32 rows at once with 256
 //         threads, 8 rows at a time with 64), lane g takes the nodes g, g + 8, ..; the maximum is a butterfly over the 8 lanes,
 //         and one of them sums the Q values in ascending q from LDS.
+// `row` and `quad` are gp_row_stage of gsmvi_glm_predict_stage.h, the one copy shared with k_glm_shared_predict_batched.
 // Order: every sum of a row is taken in an order fixed by D and Q alone; elpd runs n = 0 .. n_k - 1 in one thread.  A slot reads
 // and writes only slice k of every array and every slot of a workgroup runs the same barriers.  Rows n >= n_k are never loaded;
 // their outputs are NaN.  A row whose m or v is not finite has NaN outputs (and makes elpd[k] NaN).  No context workspace.
@@ -35,14 +36,12 @@
 #include "gsmvi_ctx.h"
 #include "gsmvi_batched.h"
 #include "gsmvi_glm_model.h"
+#include "gsmvi_glm_predict_stage.h"      // GP_MAXQ, GP_LF, GP_QL, gp_row_stage
 #include "../../include/gsmvi_hip.h"
 #include <cmath>
 #include <cstdint>
 
 #define GP_AQ 8        // tile elements per thread: LB_TN D / NT <= 8 in both packings
-#define GP_MAXQ 64     // quadrature nodes at most
-#define GP_LF 65       // row stride of the node values in LDS
-#define GP_QL 8        // lanes per row in the quadrature
 #define GP_NROW 6      // per-row LDS arrays of a tile: y, o, m, s, lpd, bad
 
 struct gp_args {
@@ -74,7 +73,7 @@ __host__ __device__ inline int gp_lds_doubles(int D, int nt) {
 template <int NT, int FAM>
 __global__ __launch_bounds__(256) void k_glm_predict_batched(gp_args a) {
     extern __shared__ double gp_sm[];
-    constexpr int PPW = 256 / NT, NW = NT / 64, NG = NT / LB_TN, RG = NT / GP_QL, NGRP = LB_TN / RG;
+    constexpr int PPW = 256 / NT, NW = NT / 64, NG = NT / LB_TN;
     const int D = a.m.D, Q = a.Q, nb = (D + 15) >> 4, Dp = nb * 16, lda = Dp + 1, DD = D * D;
     const long long M = a.m.N;
     const int slot = threadIdx.x / NT, l = threadIdx.x % NT;
@@ -125,7 +124,6 @@ __global__ __launch_bounds__(256) void k_glm_predict_batched(gp_args a) {
     // the tile elements e = l + q NT of this thread as (row, column), stepped without a division
     const int row0 = l / D, col0 = l - row0 * D, dr = NT / D, dc = NT - dr * D;
     const int en = l / NG, eg = l % NG;       // the m pass: row en of the tile, columns eg, eg + NG, ..
-    const int rr = l / GP_QL, g = l % GP_QL;  // the quadrature: row rr of the group, nodes g, g + 8, ..
     const int pad = Dp - D;
 
     double pre[GP_AQ], ypre = 0.0, opre = 0.0;
@@ -216,86 +214,10 @@ __global__ __launch_bounds__(256) void k_glm_predict_batched(gp_args a) {
             }
         }
         __syncthreads();
-        if (l < tnv) {                        // row l: v, the NaN rule, the closed forms
-            const int n = l;
-            double v = 0.0;
-            for (int jb = 0; jb < nb; ++jb) v += Vp[jb * LB_TN + n];
-            const double m = Ms[n];
-            const bool bad = !(gb_finite(m) && gb_finite(v));
-            const double vp = v > 0.0 ? v : 0.0;
-            Hs[n] = sqrt(2.0 * vp);
-            Bd[n] = bad ? 1.0 : 0.0;
-            em[n0 + n] = bad ? qnan : m;
-            ev[n0 + n] = bad ? qnan : v;
-            if (FAM == LB_GAUSSIAN) pm[n0 + n] = bad ? qnan : m;
-            if (FAM == LB_PROBIT) pm[n0 + n] = bad ? qnan : 0.5 * erfc(-(m / sqrt(1.0 + vp)) * 0.70710678118654752440);
-            if (FAM == LB_POISSON) pm[n0 + n] = bad ? qnan : exp(m + 0.5 * vp);
-            if (FAM == LB_GAUSSIAN && hasy) {
-                const double var = vp + 1.0 / tau, d = Ys[n] - m;
-                const double t = -0.5 * log(6.28318530717958647692 * var) - (d * d) / (2.0 * var);
-                const double out = bad ? qnan : t;
-                lp[n0 + n] = out;
-                Ls[n] = out;
-            }
-        }
-        __syncthreads();                      // m, s and the flags are published; the tile is free
-        if (quad) {
-#pragma unroll 1
-            for (int grp = 0; grp < NGRP; ++grp) {
-                const int n = grp * RG + rr;
-                const bool on = n < tnv;
-                double* F = As + rr * GP_LF;
-                double m = 0.0, s = 0.0, yv = 0.0;
-                bool bad = false;
-                if (on) {
-                    m = Ms[n];
-                    s = Hs[n];
-                    bad = Bd[n] != 0.0;
-                    if (hasy) yv = Ys[n];
-                }
-                if (FAM == LB_LOGISTIC) {     // pmean: sigma(eta_q) = -r(eta_q, y = 0) of the link
-                    if (on)
-                        for (int q = g; q < Q; q += GP_QL) {
-                            double r = 0.0, t = 0.0;
-                            lb_link<FAM, true, false>(m + s * gt[q], 0.0, 1.0, r, t);
-                            F[q] = gw[q] * -r;
-                        }
-                    __syncthreads();
-                    if (on && g == 0) {
-                        double sum = 0.0;
-                        for (int q = 0; q < Q; ++q) sum += F[q];
-                        pm[n0 + n] = bad ? qnan : sum / 1.77245385090551602730;
-                    }
-                    __syncthreads();
-                }
-                if (hasy) {                   // lpd: the maximum first, then the sum in ascending q
-                    double mx = -__builtin_huge_val();
-                    if (on)
-                        for (int q = g; q < Q; q += GP_QL) {
-                            double r = 0.0, t = 0.0;
-                            lb_link<FAM, false, true>(m + s * gt[q], yv, 1.0, r, t);
-                            const double f = gl[q] + t;
-                            F[q] = f;
-                            mx = fmax(mx, f);
-                        }
-#pragma unroll
-                    for (int o = GP_QL / 2; o > 0; o >>= 1) mx = fmax(mx, __shfl_xor(mx, o));
-                    if (on)
-                        for (int q = g; q < Q; q += GP_QL) F[q] = exp(F[q] - mx);
-                    __syncthreads();
-                    if (on && g == 0) {
-                        double sum = 0.0;
-                        for (int q = 0; q < Q; ++q) sum += F[q];
-                        double t = (mx + log(sum)) - 0.57236494292470008707;
-                        if (FAM == LB_POISSON) t -= lgamma(yv + 1.0);
-                        const double out = bad ? qnan : t;
-                        lp[n0 + n] = out;
-                        Ls[n] = out;
-                    }
-                    __syncthreads();
-                }
-            }
-        }
+        // the row stage (gsmvi_glm_predict_stage.h, one copy for this kernel and k_glm_shared_predict_batched): v, the NaN rule,
+        // the closed forms, then the quadrature over the tile's LDS, where the link is called (lb_link<FAM, ..>), not restated
+        gp_row_stage<NT, FAM, false>(hasy, quad, Q, nb, l, tnv, n0, tau, gt, gl, gw, Vp, Ms, Ys, nullptr, Hs, Bd, Ls, As, em, ev, pm,
+                                     lp);
         if (hasy && l == NT - 1)
             for (int n = 0; n < tnv; ++n) eacc += Ls[n];
         __syncthreads();                      // the next tile overwrites the tile region and the per-row arrays

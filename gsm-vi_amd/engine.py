@@ -1270,6 +1270,34 @@ class HipEngine:
                    self._dp(elpd, (K,), "elpd"))
         return em, ev, pm, lpd, elpd
 
+    # ---- the same for K fitted GLMs on ONE set of new rows, weighted (csrc/gsmvi_glm_shared_predict_batched.hip) ----------------
+    def glm_shared_predict_batched(self, mean, cov, A, family, offset=None, y=None, weights=None, noise_prec=1.0, nodes=32):
+        """The posterior predictive of K fitted GLMs at the rows of ONE matrix A (M, D) under q_k = N(mean_k, cov_k), with row
+        weights, one launch and no copy of A per problem (gsmvi_glm_shared_predict_batched_f64; the definition is in
+        include/gsmvi_hip.h)  [no reference twin]: returns (eta_mean, eta_var, pmean (K, M), lpd (K, M), elpd (K,)), the last two
+        None without ``y``.  Row m of problem k is valid iff ``weights`` is None or weights[k, m] > 0; the other rows are NaN,
+        their ``y`` and ``offset`` are never read, and elpd[k] = sum over the valid rows of weights[k, m] lpd[k, m].  The other
+        arguments are ``glm_predict_batched``'s; the Gauss-Hermite table is the engine's cached one."""
+        K = mean.shape[0]
+        fam, t, tp = self._glm_family_args(family, noise_prec, K)
+        Q = int(nodes)
+        if not 1 <= Q <= 64:
+            raise ValueError(f"nodes = {nodes!r}: expected 1 .. 64")
+        M, D = A.shape
+        self._any_ctx()
+        gt, gl = self._gh_table(Q)
+        em, ev, pm = self.empty(K, M), self.empty(K, M), self.empty(K, M)
+        lpd = elpd = None
+        if y is not None:
+            lpd, elpd = self.empty(K, M), self.empty(K)
+        self._call("gsmvi_glm_shared_predict_batched_f64", K, D, M, fam, self._packed(A, (M, D), "A"),
+                   self._dp(offset, (K, M), "offset"), self._dp(y, (K, M), "y"), self._dp(weights, (K, M), "weights"), t, tp,
+                   self._packed(mean, (K, D), "mean"), self._packed(cov, (K, D, D), "cov"), Q,
+                   self._packed(gt, (Q,), "gh_t"), self._packed(gl, (Q,), "gh_logw"), self._packed(em, (K, M), "eta_mean"),
+                   self._packed(ev, (K, M), "eta_var"), self._packed(pm, (K, M), "pmean"), self._dp(lpd, (K, M), "lpd"),
+                   self._dp(elpd, (K,), "elpd"))
+        return em, ev, pm, lpd, elpd
+
     # ---- batched Pareto-smoothed importance diagnostic of K fitted Gaussians (csrc/gsmvi_psis_batched.hip) ----------------------
     def psis_weights_batched(self, logr):
         """The PSIS stage on the log ratios logr (K, S), 5 <= S <= 4096, one launch (gsmvi_psis_weights_batched_f64; the steps

@@ -397,13 +397,14 @@ class BatchedLogisticTarget(BatchedGLMTarget):
         return self.engine.logistic_batched(x, self.A, self.y, self.counts, self.prior_precision, **kw)
 
 
-def _check_weights(weights, K, N):
-    """the observation weights as a host float64 array (None stays None): shape (K, N), finite and >= 0, else ValueError"""
+def _check_weights(weights, K, N, rows="N"):
+    """the observation weights as a host float64 array (None stays None): shape (K, N), finite and >= 0, else ValueError
+    (``rows`` names the row count in the message: "N", or "M" for the new rows of a predictive)"""
     if weights is None:
         return None
     sw = _shape(weights)
     if sw != (K, N):
-        raise ValueError(f"weights: expected shape (K, N) = {(K, N)}, got {sw}")
+        raise ValueError(f"weights: expected shape (K, {rows}) = {(K, N)}, got {sw}")
     wh = np.asarray(_host_array(weights), dtype=np.float64)
     with np.errstate(invalid="ignore"):
         bad = ~(np.isfinite(wh) & (wh >= 0.0))
@@ -437,8 +438,9 @@ class SharedDesignGLMTarget:
     Not a ``BatchedGLMTarget``: it has no ``neg_hessian``, ``predict`` or ``loo``, and ``laplace_init_batched``,
     ``psis_loo_batched`` refuse it.  Its negative Hessian is ``neg_hessian_shared_batched(target, x)``, its second-order start
     ``laplace_init_shared_batched(target, ...)`` and its PSIS leave-one-out ``psis_loo_shared_batched(target, mean, cov, keys,
-    ...)`` (weighted sums over the rows of weight > 0), all on the shared design without a copy per problem; a posterior
-    predictive stays absent."""
+    ...)`` (weighted sums over the rows of weight > 0) and its posterior predictive ``predict_shared_batched(target, mean, cov,
+    A_new, ...)`` (one shared set of new rows with per-problem row weights: the held-out score of K-fold cross-validation
+    through the weights), all on the shared design without a copy per problem."""
 
     FAMILIES = BatchedGLMTarget.FAMILIES
 
@@ -507,6 +509,61 @@ def neg_hessian_shared_batched(target, x, *, engine=None):
     return eng.glm_shared_hessian_batched(eng.asarray(x), target.A, target.y, target.family, offset=target.offset,
                                           weights=target.weights, prior_prec=target.prior_precision,
                                           noise_prec=target.noise_precision, want="h")
+
+
+def predict_shared_batched(target, mean, cov, A_new, offset=None, y=None, weights=None, nodes=32, *, engine=None):
+    """The posterior predictive of the K fitted problems of a ``SharedDesignGLMTarget`` on ONE shared set of new rows:
+    ``BatchedGLMTarget.predict`` without a copy of the rows per problem, and with row weights.  ``mean`` (K, D) and ``cov``
+    (K, D, D) are the fitted Gaussians (of GSMBatch, BaMBatch, ADVIBatch or ``laplace_init_shared_batched``), ``A_new`` (M, D)
+    the new rows of every problem (``target.A`` itself is taken as it is, without a copy), ``offset`` (K, M) their offsets (None:
+    none, whether or not the target was built with one), ``y`` (K, M) their responses (None: no ``lpd`` / ``elpd``),
+    ``weights`` (K, M) the row weights v_km, finite and >= 0 (None: 1 everywhere), ``nodes`` = Q the Gauss-Hermite nodes, 1 .. 64.
+
+    Row m of problem k is valid iff v_km > 0, the rule of the target's own weights.  A valid row gets what ``predict`` gives
+    for that row (``eta_mean``, ``eta_var``, ``mean``, and with ``y`` ``lpd``, the density of one unit observation, not
+    weighted); a row of weight 0 is NaN in all four and its ``y`` and ``offset`` may hold anything, NaN included;
+    ``elpd[k]`` = sum over the valid rows of v_km lpd[k, m], 0 for a problem without a valid row.  K-fold cross-validation:
+    with the fold's mask as ``weights`` here and 1 - mask as the weights of the fit, ``elpd`` is the fold's held-out score
+    (examples/kfold_shared_batched.py).  With ``weights`` None every field has the bits of ``predict`` on K copies of ``A_new``.
+
+    Returns a ``GLMPrediction``; numpy in gives numpy out, CUDA tensors in give tensors out.  The shapes, ``nodes``,
+    ``weights``, and ``y`` and ``offset`` where the weight is > 0, are validated before any device work (ValueError naming the
+    argument and the problems).  Anything that is not a ``SharedDesignGLMTarget`` raises TypeError: a ``BatchedGLMTarget`` has
+    ``BatchedGLMTarget.predict``.  One launch (gsmvi_glm_shared_predict_batched_f64)."""
+    fn = "predict_shared_batched"
+    if not isinstance(target, SharedDesignGLMTarget):
+        raise TypeError(f"{fn}: target must be a SharedDesignGLMTarget, got {type(target).__name__}"
+                        " (a BatchedGLMTarget has BatchedGLMTarget.predict)")
+    K, D, family = target.K, target.D, target.family
+    if isinstance(nodes, bool) or not isinstance(nodes, (int, np.integer)) or not 1 <= nodes <= 64:
+        raise ValueError(f"nodes: expected an integer in 1 .. 64, got {nodes!r}")
+    sa = _shape(A_new)
+    if len(sa) != 2 or min(sa) < 1 or sa[1] != D:
+        raise ValueError(f"A_new: expected shape (M, D) with D = {D} and M >= 1 (one set of new rows for all problems), got {sa}")
+    M = sa[0]
+    if _shape(mean) != (K, D):
+        raise ValueError(f"mean: expected shape (K, D) = {(K, D)}, got {_shape(mean)}")
+    if _shape(cov) != (K, D, D):
+        raise ValueError(f"cov: expected shape (K, D, D) = {(K, D, D)}, got {_shape(cov)}")
+    wh = _check_weights(weights, K, M, rows="M")
+    live = wh > 0.0 if wh is not None else np.ones((1, M), dtype=bool)
+    yh = None
+    if y is not None:
+        if _shape(y) != (K, M):
+            raise ValueError(f"y: expected shape (K, M) = {(K, M)}, got {_shape(y)}")
+        yh = _check_responses(y, family, live)
+    oh = _check_offset(offset, K, M, live, rows="M")
+    eng = engine if engine is not None else target.engine
+    as_tensor = isinstance(mean, torch.Tensor)
+    dev = lambda x: eng.asarray(x.contiguous() if isinstance(x, torch.Tensor) else x)      # noqa: E731
+    out = eng.glm_shared_predict_batched(dev(mean), dev(cov), A_new if A_new is target.A else dev(A_new), family,
+                                         offset=eng.asarray(oh) if oh is not None else None,
+                                         y=eng.asarray(yh) if yh is not None else None,
+                                         weights=eng.asarray(wh) if wh is not None else None,
+                                         noise_prec=target.noise_precision, nodes=int(nodes))
+    if not as_tensor:
+        out = tuple(eng.to_numpy(t) if t is not None else None for t in out)
+    return GLMPrediction(*out)
 
 
 def _check_finite_per_problem(x, name, K):

@@ -42,6 +42,8 @@
  *   score from draws of q_k (no reference twin)                        ->  gsmvi_softmax_predict_batched_f64, gsmvi_softmax_predict_lds_bytes
  *   the same use for K fitted negative binomial regressions: log moments of the predictive count and the held-out score from
  *   draws of q_k (no reference twin)                                   ->  gsmvi_negbin_predict_batched_f64
+ *   the use of the fit for K fitted GLMs on one design matrix: the GLM predictive on one shared set of new rows with per-problem
+ *   row weights, the held-out score of K-fold cross-validation (no reference twin) -> gsmvi_glm_shared_predict_batched_f64
  *   gsmvi/bam.py:72-114       bam_lowrank_update(samples,vs,mu0,S0,reg) ->  gsmvi_bam_update_f64
  *   gsmvi/bam.py:31-69        bam_update(samples,vs,mu0,S0,reg)         ->  gsmvi_bam_update_f64 (same result, K6)
  *
@@ -313,10 +315,10 @@ int gsmvi_get_profile(gsmvi_ctx* ctx, float* ms, int n);
 #define GSMVI_PATH_BATCHED_BAM 0x4000u     /* k_bam_batched: the batched BaM entry points                           */
 #define GSMVI_PATH_BATCHED_KL 0x8000u      /* k_kl_batched: the batched KL monitor's entry points                  */
 #define GSMVI_PATH_BATCHED_ADVI 0x10000u   /* k_advi_batched / k_advi_cov_batched: the batched ADVI entry points   */
-#define GSMVI_PATH_BATCHED_TARGET 0x20000u /* k_logistic_batched: the batched non-Gaussian target's entry point; with GSMVI_PATH_BATCHED_LAPLACE in one call: k_laplace_shared_batched or k_negbin_laplace_batched; with GSMVI_PATH_BATCHED_LOO in one call: k_psis_loo_negbin_batched; with GSMVI_PATH_BATCHED_PREDICT in one call: k_negbin_predict_batched (all 32 bits are taken; no other call sets any of these pairs) */
+#define GSMVI_PATH_BATCHED_TARGET 0x20000u /* k_logistic_batched: the batched non-Gaussian target's entry point; with GSMVI_PATH_BATCHED_LAPLACE in one call: k_laplace_shared_batched or k_negbin_laplace_batched; with GSMVI_PATH_BATCHED_LOO in one call: k_psis_loo_negbin_batched; with GSMVI_PATH_BATCHED_PREDICT in one call: k_negbin_predict_batched or k_glm_shared_predict_batched (all 32 bits are taken; no other call sets any of these pairs) */
 #define GSMVI_PATH_BATCHED_LBFGS 0x40000u  /* k_lbfgs_step_batched / k_lbfgs_hess_inv_batched: the batched initialiser   */
 #define GSMVI_PATH_BATCHED_LAPLACE 0x80000u /* k_laplace_batched: the batched GLM Hessian and Newton step; with GSMVI_PATH_BATCHED_TARGET in one call: k_laplace_shared_batched, the shared-design Hessian and Newton step, or k_negbin_laplace_batched, the negative binomial one */
-#define GSMVI_PATH_BATCHED_PREDICT 0x100000u /* k_glm_predict_batched: the batched GLM posterior predictive; with GSMVI_PATH_BATCHED_SOFTMAX: k_softmax_predict_batched; with GSMVI_PATH_BATCHED_TARGET: k_negbin_predict_batched */
+#define GSMVI_PATH_BATCHED_PREDICT 0x100000u /* k_glm_predict_batched: the batched GLM posterior predictive; with GSMVI_PATH_BATCHED_SOFTMAX: k_softmax_predict_batched; with GSMVI_PATH_BATCHED_TARGET: k_negbin_predict_batched or k_glm_shared_predict_batched, the shared-design GLM predictive */
 #define GSMVI_PATH_BATCHED_PSIS 0x200000u /* k_psis_batched: the batched Pareto-smoothed importance diagnostic            */
 #define GSMVI_PATH_BATCHED_LOO 0x400000u /* k_psis_loo_batched: the batched PSIS leave-one-out; with GSMVI_PATH_BATCHED_SOFTMAX: k_psis_loo_softmax_batched; with GSMVI_PATH_BATCHED_TARGET: k_psis_loo_negbin_batched */
 #define GSMVI_PATH_GSM_TWO_LAUNCH 0x800000u /* the dense GSM update ran as two launches (no k_gsm_scalars_fast, no records)          */
@@ -1229,12 +1231,53 @@ int gsmvi_softmax_predict_batched_f64(gsmvi_ctx* ctx, void* stream, int64_t K, i
  * y / lpd pairing and overlaps (lmom and lpd are the written arrays, everything else is read) are checked before the context is
  * looked at (then a NULL ctx); every failure returns GSMVI_ERR_BAD_ARG before anything is enqueued.  Inputs are only read; no
  * context workspace is used; one capturable launch with no host synchronisation and no atomics.  Sets GSMVI_PATH_BATCHED_PREDICT |
- * GSMVI_PATH_BATCHED_TARGET: after a reset exactly that pair identifies this launch (the GLM predictive sets the first bit alone,
- * the negative binomial score launch the second alone).
+ * GSMVI_PATH_BATCHED_TARGET: after a reset exactly that pair identifies this launch or gsmvi_glm_shared_predict_batched_f64's
+ * (the GLM predictive sets the first bit alone, the negative binomial score launch the second alone).
  */
 int gsmvi_negbin_predict_batched_f64(gsmvi_ctx* ctx, void* stream, int64_t K, int P, int64_t M, int64_t S, const double* A,
                                      const double* y, const double* offset, const int* counts_dev, const double* X,
                                      const double* lw, double* lmom, double* lpd);
+
+/*
+ * Shared-design GLM posterior predictive: gsmvi_glm_predict_batched_f64 for K fitted posteriors q_k = N(mean_k, cov_k) on ONE
+ * shared set of new rows, with per-problem row weights: the held-out score of K-fold cross-validation on the model of
+ * gsmvi_glm_shared_batched_f64 (F folds x L settings are K = F L problems on one design).  The reference has no twin.  One launch;
+ * A is never replicated.
+ * A (M x D) is the one matrix of new rows a_m.  Problem k has mean_k (D), cov_k (D x D, read as given, both triangles), an optional
+ * offset o_km (K x M, or NULL), optional responses y_km (K x M, or NULL), optional row weights v_km (K x M, or NULL: every v = 1)
+ * and, for the gaussian family, the noise precision tau_k (noise_prec / noise_prec_dev); no prior.  gh_t and gh_logw (Q each) are
+ * the nodes and the logarithms of the weights of the Q-point Gauss-Hermite rule (weight exp(-t^2)), 1 <= Q <= 64.
+ * Row m of problem k is valid iff weights is NULL or v_km > 0: the selection of gsmvi_glm_shared_hessian_batched_f64 and
+ * gsmvi_psis_loo_shared_batched_f64.  A weight of 0 or NaN removes the row; the valid rows are an arbitrary subset, not a prefix.
+ * For a valid row, eta_mean[k, m], eta_var[k, m], pmean[k, m] and lpd[k, m] are what gsmvi_glm_predict_batched_f64 defines for row
+ * m of a problem whose design is A: m = a_m . mean_k + o_km, v = a_m^T cov_k a_m (eta_var, the raw value), v+ = max(v, 0), the four
+ * families' closed forms, the Gauss-Hermite log-sum-exp (the maximum first, then the sum of exp(. - max) in ascending q) with t and
+ * r of gsmvi_glm_batched_f64's link, and the row's NaN rule (m or v not finite: the row's outputs are NaN).
+ *   lpd[k, m]  = the log predictive density of ONE unit observation y_km, UNWEIGHTED: the convention of
+ *                gsmvi_psis_loo_shared_batched_f64
+ *   elpd[k]    = sum over the valid rows of v_km lpd[k, m] (v = 1 without weights; one product, one addition, not fused), summed
+ *                by one thread in ascending m, the rows that are not valid skipped; 0 for a problem without a valid row; NaN when a
+ *                valid row's lpd is
+ * For a row that is not valid, y[k, m] and offset[k, m] are never read (a NaN y, an infinite offset there are harmless), the row's
+ * four outputs are NaN and it adds nothing to elpd[k].  Without y, lpd and elpd are NULL; the weights still select the rows of the
+ * other three outputs.  A is shared: a non-finite entry in row m of it reaches row m of every problem, and only row m; a non-finite
+ * entry of mean_k or cov_k reaches problem k alone.
+ * With weights NULL or all exactly 1.0 every output has the bits of gsmvi_glm_predict_batched_f64 on K copies of A; with 0 / 1
+ * weights that form a prefix, those of its counts_dev.  The outputs are bit-identical from run to run and do not depend on K or on
+ * the other problems of the launch.
+ * 1 <= D <= 64, M >= 1, K >= 1 within the launch bound of gsmvi_glm_shared_hessian_batched_f64, K M D doubles addressable.  Shapes,
+ * the family and its noise precision, Q, NULL arrays, the y / lpd / elpd pairing (lpd and elpd are required with y and only with it)
+ * and overlaps (eta_mean, eta_var, pmean, lpd and elpd are the written arrays, everything else, weights included, is read; A counts
+ * M D doubles) are checked before the context is looked at (then a NULL ctx); every failure returns GSMVI_ERR_BAD_ARG with its own
+ * message before anything is enqueued.  Inputs are only read; no context workspace is used; one capturable launch with no host
+ * synchronisation and no atomics; at most 53.5 KB of dynamic LDS.  Sets GSMVI_PATH_BATCHED_PREDICT | GSMVI_PATH_BATCHED_TARGET (no
+ * bit of its own: the pair is also gsmvi_negbin_predict_batched_f64's).
+ */
+int gsmvi_glm_shared_predict_batched_f64(gsmvi_ctx* ctx, void* stream, int64_t K, int D, int64_t M, int family, const double* A,
+                                         const double* offset, const double* y, const double* weights, double noise_prec,
+                                         const double* noise_prec_dev, const double* mean, const double* cov, int Q,
+                                         const double* gh_t, const double* gh_logw, double* eta_mean, double* eta_var, double* pmean,
+                                         double* lpd, double* elpd);
 
 /*
  * Upper Cholesky factor R (R^T R = S, R upper triangular, strictly-lower part zeroed) of a
