@@ -33,6 +33,9 @@ Mirrors the reference's public surface for the hot path (reference file:line):
     BatchedNegBinomialTarget (K negative binomial
     regressions with a fitted log size, P + 1 <= 64:
     log-density and score in one launch)         examples/example_gsm.py:34-35 (log_prob, jit(grad(.)))
+    BatchedOrdinalTarget (K cumulative-logit
+    regressions of C ordered classes, P + C - 1 <= 64:
+    log-density and score in one launch)         examples/example_gsm.py:34-35 (log_prob, jit(grad(.)))
     BatchedGLMTarget.predict, GLMPrediction (the
     posterior predictive of K fitted GLMs on new
     rows: mean, variance of the linear predictor,
@@ -107,6 +110,7 @@ from .targets import BatchedGLMTarget, GLMPrediction                 # noqa: F40
 from .targets import BatchedSoftmaxTarget                            # noqa: F401
 from .targets import SharedDesignGLMTarget                           # noqa: F401
 from .targets import BatchedNegBinomialTarget                        # noqa: F401
+from .targets import BatchedOrdinalTarget                            # noqa: F401
 from .targets import predict_softmax_batched, SoftmaxPrediction      # noqa: F401
 from .targets import predict_negbin_batched, NegBinPrediction        # noqa: F401
 from .targets import neg_hessian_shared_batched                      # noqa: F401

@@ -125,6 +125,8 @@ _SIGS = {
                                             C.c_double, _c_dp, _c_dp, _c_dp, _c_dp]),
     "gsmvi_negbin_batched_f64": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int64, _c_dp, _c_dp, _c_dp, _c_dp,
                                            C.c_double, _c_dp, C.c_double, _c_dp, C.c_double, _c_dp, _c_dp, _c_dp, _c_dp]),
+    "gsmvi_ordinal_batched_f64": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int64, _c_dp, _c_dp, _c_dp,
+                                            _c_dp, C.c_double, _c_dp, C.c_double, _c_dp, _c_dp, _c_dp, _c_dp]),
     "gsmvi_lbfgs_step_batched_f64": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, _c_dp, _c_dp, C.c_double, _c_dp,
                                                _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, C.c_int, C.c_int, C.c_double,
                                                C.c_double]),
@@ -213,6 +215,8 @@ _DEBUG_SIGS = {
     "gsmvi_debug_glm_batched_lds": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t), C.POINTER(C.c_int)]),
     "gsmvi_debug_glm_shared_batched_lds": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t), C.POINTER(C.c_int)]),
     "gsmvi_debug_negbin_batched_lds": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t), C.POINTER(C.c_int)]),
+    "gsmvi_debug_ordinal_batched_lds": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t),
+                                                  C.POINTER(C.c_int)]),
     "gsmvi_debug_negbin_laplace_lds": (C.c_int, [C.c_int, C.POINTER(C.c_size_t), C.POINTER(C.c_int)]),
     "gsmvi_debug_softmax_batched_lds": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t), C.POINTER(C.c_int),
                                                   C.POINTER(C.c_int)]),

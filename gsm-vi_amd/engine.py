@@ -922,6 +922,32 @@ class HipEngine:
                    self._packed(X, (K, nc, D), "X"), self._dp(G, (K, nc, D), "out"), self._dp(lp, (K, nc), "lp_out"))
         return ret
 
+    # ---- batched ordinal target: K cumulative-logit regressions of C ordered classes (csrc/gsmvi_ordinal_batched.hip) -----------
+    def ordinal_batched(self, X, A, y, C, offset=None, counts=None, prior_prec=1.0, cut_prec=1.0, out=None, lp_out=None, want="g"):
+        """Score and / or log-density of K cumulative-logit (proportional odds) regressions at the rows of X (K, nc, P + C - 1) =
+        (beta, delta), cut_0 = delta_0 and cut_j = cut_{j-1} + exp(delta_j), one launch [examples/example_gsm.py:34-35 for this
+        model]: A (K, N, P) without an intercept column, ``y`` (K, N) device int32 labels in 0 .. C - 1, ``C`` the number of
+        classes, ``offset`` None or (K, N) added to A beta, ``counts`` None or K device int32 valid rows; ``prior_prec`` (of beta)
+        and ``cut_prec`` (of delta) each a number or a (K,) device tensor.  ``want`` = "g" -> G (K, nc, P + C - 1), "lp" -> the
+        values (K, nc), "both" -> (G, lp)."""
+        N, P, Cc = A.shape[1], A.shape[2], int(C)
+        if Cc < 2:
+            raise ValueError(f"C: expected at least 2 classes, got {Cc}")
+        if X.shape[2] != P + Cc - 1:
+            raise ValueError(f"X: expected P + C - 1 = {P + Cc - 1} columns (beta, then the C - 1 cutpoint parameters), got {X.shape[2]}")
+        G, lp, ret = self._want_g_lp(want, X, out, lp_out)
+        X = X.contiguous()
+        K, nc, D = X.shape
+        assert y.is_cuda and y.dtype == torch.int32 and y.is_contiguous() and tuple(y.shape) == (K, N), \
+            f"y: expected a contiguous int32 CUDA tensor of shape {(K, N)}"
+        self._any_ctx()
+        r, rp = self._reg_arg(prior_prec, K)
+        c, cp = self._reg_arg(cut_prec, K)
+        self._call("gsmvi_ordinal_batched_f64", K, P, Cc, nc, N, self._packed(A, (K, N, P), "A"), _ptr(y),
+                   self._dp(offset, (K, N), "offset"), self._ints(counts, K, "counts"), r, rp, c, cp,
+                   self._packed(X, (K, nc, D), "X"), self._dp(G, (K, nc, D), "out"), self._dp(lp, (K, nc), "lp_out"))
+        return ret
+
     # ---- shared-design GLM target: K problems on one design matrix (csrc/gsmvi_glm_shared_batched.hip) -----------------------
     def glm_shared_batched(self, X, A, y, family, offset=None, weights=None, prior_prec=1.0, noise_prec=1.0, out=None,
                            lp_out=None, want="g"):

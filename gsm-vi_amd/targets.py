@@ -22,6 +22,8 @@ multinomial logit regressions (C classes, C - 1 linear predictors per row), a la
                                                                                                  checks refuse it)
     BatchedNegBinomialTarget  counts y >= 0, a fitted size    gsmvi_negbin_batched_f64           no (not a BatchedGLMTarget: the Hessian
                               (x = (beta, log r))                                                has a 2 x 2 block per row)
+    BatchedOrdinalTarget      ordered labels in 0 .. C - 1,   gsmvi_ordinal_batched_f64          no (none exists yet for this family; the
+                              x = (beta, C - 1 cutpoints)                                        isinstance checks refuse it)
     BatchedSoftmaxTarget      integer labels in 0 .. C - 1    gsmvi_softmax_batched_f64          laplace_init_softmax_batched and
                                                                                                  neg_hessian; predict, loo: no (TypeError):
                                                                                                  predict_softmax_batched,
@@ -897,6 +899,92 @@ class BatchedSoftmaxTarget:
         """``psis_loo_batched(self, ...)``, which takes the GLM targets only: TypeError"""
         from .diagnostics import psis_loo_batched
         return psis_loo_batched(self, mean, cov, keys, **kw)
+
+
+class BatchedOrdinalTarget:
+    """K Bayesian cumulative-logit (proportional odds) regressions with their own data sets -- ordered categories: ratings, grades,
+    severity scores, Likert items -- for ``GSMBatch``, ``BaMBatch``, ``ADVIBatch``, ``BatchedKLMonitor``, ``lbfgs_init_batched``,
+    ``pathfinder_init_batched`` and ``psis_batched``.  Problem k has the design matrix A[k] (N, P) WITHOUT an intercept column (the
+    cutpoints are the intercepts), integer labels y[k] (N,) in 0 .. C - 1 (``num_classes`` = C >= 2), an optional ``offset[k]`` (N,)
+    added to the linear predictor and ``counts[k]`` <= N valid rows (None: all N; the rows beyond are ignored whatever they hold).
+    The parameter is x = (beta, delta) in R^D, D = P + C - 1 <= 64; the cutpoints are ordered by construction:
+
+        cut_0 = delta_0,   cut_j = cut_{j-1} + exp(delta_j)     (j = 1 .. C - 2)          (``cutpoints(x)``)
+        P(y_n = c)   = sigmoid(cut_c - eta_n) - sigmoid(cut_{c-1} - eta_n),   eta = A[k] beta + offset[k],  cut_{-1} = -inf, cut_{C-1} = inf
+        lp_k(x)      = sum_n log P(y_n) - lam_k |beta|^2 / 2 - kap_k |delta|^2 / 2
+
+    evaluated with its score by gsmvi_ordinal_batched_f64: what examples/example_gsm.py:34-35 gets from a model's log_prob and
+    jit(grad(...)).  No two probabilities are subtracted: with a = cut_{y-1} - eta, b = cut_y - eta and w = exp(delta_y) the gap of
+    an interior class, log P = -softplus(-b) - softplus(a) + log(1 - exp(-w)), and the residuals are sigmoids and 1 / expm1(w).  The
+    priors: beta ~ N(0, I / lam_k), ``prior_precision`` = lam; delta ~ N(0, I / kap_k), ``cut_precision`` = kap; each a float or K
+    values, a precision of 0 = flat.  For C = 2 the model is logistic regression on the design [A, -1].  A point at which some
+    exp(delta_j), j >= 1, is not a positive normal number (|delta_j| above 708) gets NaN outputs (the fits then revert that step);
+    delta_0 is a location and is not limited.  numpy arrays or tensors in; everything is kept on the device as float64 / int32.
+    Arguments are validated on the host before any device work (ValueError naming the argument and the problems).
+
+    ``lp_g(x, out=None)``: (K, B, D) -> (K, B, D) scores, ``device_native`` and ``graph_safe`` (one capturable launch, no
+    allocation with ``out``).  ``lp(x)``: (K, rows, D) -> (K, rows) values; a device tensor or numpy.  ``lp_and_score(x)``:
+    (scores, values) from one launch.  ``cutpoints(x)``: (..., D) -> (..., C - 1), how a fit is read.  Attributes ``K, N, P, C, D``.
+    Not a ``BatchedGLMTarget``: it has no ``neg_hessian``, ``predict`` or ``loo``, and ``laplace_init_batched``,
+    ``psis_loo_batched`` and their softmax and negative binomial namesakes refuse it (TypeError).  A Hessian and Laplace start, a
+    leave-one-out and a posterior predictive do not exist yet for this family."""
+
+    def __init__(self, A, y, num_classes, prior_precision=1.0, cut_precision=1.0, counts=None, offset=None, engine=None):
+        if isinstance(num_classes, bool) or not isinstance(num_classes, (int, np.integer)) or num_classes < 2:
+            raise ValueError(f"num_classes: expected an integer >= 2, got {num_classes!r}")
+        C = int(num_classes)
+        sa = _shape(A)
+        if len(sa) != 3 or min(sa) < 1:
+            raise ValueError(f"A: expected shape (K, N, P) with K, N, P >= 1, got {sa}")
+        K, N, P = sa
+        if P + C - 1 > 64:
+            raise ValueError(f"A: D = P + num_classes - 1 = {P + C - 1} is outside 2 <= D <= 64 (beta and the C - 1 cutpoints)")
+        if _shape(y) != (K, N):
+            raise ValueError(f"y: expected shape (K, N) = {(K, N)}, got {_shape(y)}")
+        cnt = _check_counts(counts, K, N)
+        live = _live_rows(cnt, N)
+        yh = _check_labels(y, C, live)
+        oh = _check_offset(offset, K, N, live)
+        lam = _check_per_problem(prior_precision, "prior_precision", K)
+        kap = _check_per_problem(cut_precision, "cut_precision", K)
+        self.engine = engine if engine is not None else get_engine()
+        eng = self.engine
+        self.K, self.N, self.P, self.C, self.D = K, N, P, C, P + C - 1
+        self.A = eng.asarray(A.contiguous() if isinstance(A, torch.Tensor) else A)
+        self.y = eng.batched_labels(yh)
+        self.offset = eng.asarray(oh) if oh is not None else None
+        self.counts = eng.batched_counts(cnt) if cnt is not None else None
+        self.prior_precision = float(lam) if lam.shape == () else eng.batched_regs(lam)
+        self.cut_precision = float(kap) if kap.shape == () else eng.batched_regs(kap)
+
+        def lp_g(x, out=None):
+            return self._call(x, out=out, want="g")
+        lp_g.device_native = True
+        lp_g.graph_safe = True          # one capturable kernel launch, no allocation when `out` is given, no host work
+        self.lp_g = lp_g
+
+    def _call(self, x, **kw):
+        return self.engine.ordinal_batched(x, self.A, self.y, self.C, offset=self.offset, counts=self.counts,
+                                           prior_prec=self.prior_precision, cut_prec=self.cut_precision, **kw)
+
+    def lp(self, x):
+        """(K, rows) values lp_k(x_kr) at the rows of x (K, rows, D), a device tensor or numpy; one launch"""
+        return self._call(self.engine.asarray(x), want="lp")
+
+    def lp_and_score(self, x):
+        """(scores (K, rows, D), values (K, rows)) from one launch"""
+        return self._call(self.engine.asarray(x), want="both")
+
+    def cutpoints(self, x):
+        """(..., D) parameters -> the (..., C - 1) ordered cutpoints cut_0 = delta_0, cut_j = cut_{j-1} + exp(delta_j): plain torch
+        ops on the device or host the parameters are on; numpy in gives numpy out"""
+        as_numpy = not isinstance(x, torch.Tensor)
+        t = torch.as_tensor(np.asarray(x, dtype=np.float64)) if as_numpy else x
+        if t.shape[-1] != self.D:
+            raise ValueError(f"x: expected {self.D} = P + C - 1 trailing entries, got shape {tuple(t.shape)}")
+        d = t[..., self.P:]
+        cut = torch.cumsum(torch.cat([d[..., :1], torch.exp(d[..., 1:])], dim=-1), dim=-1)
+        return cut.numpy() if as_numpy else cut
 
 
 @dataclass

@@ -24,6 +24,7 @@
  *   examples/example_gsm.py:34-35 the same for K Poisson, probit or Gaussian regressions with offsets -> gsmvi_glm_batched_f64
  *   examples/example_gsm.py:34-35 the same for K such regressions on ONE design matrix, with observation weights -> gsmvi_glm_shared_batched_f64
  *   examples/example_gsm.py:34-35 the same for K multinomial logit (softmax) regressions of C classes -> gsmvi_softmax_batched_f64
+ *   examples/example_gsm.py:34-35 the same for K cumulative-logit (ordinal) regressions of C ordered classes -> gsmvi_ordinal_batched_f64
  *   initializers.py:5-17 lbfgs_init (maximiser of lp, dense inverse-Hessian estimate), K problems -> gsmvi_lbfgs_step_batched_f64, gsmvi_lbfgs_hess_inv_batched_f64
  *   initializers.py:5-17 the same role by Newton rounds on the GLMs of examples/example_gsm.py:34-35 (no reference twin) -> gsmvi_glm_hessian_batched_f64, gsmvi_laplace_step_batched_f64,
  *   gsmvi_softmax_hessian_batched_f64, gsmvi_softmax_laplace_step_batched_f64 (the multinomial logit),
@@ -609,6 +610,43 @@ int gsmvi_negbin_batched_f64(gsmvi_ctx* ctx, void* stream, int64_t K, int P, int
                              const double* offset, const int* counts_dev, double theta_mean, const double* theta_mean_dev,
                              double theta_prec, const double* theta_prec_dev, double prior_prec, const double* prior_prec_dev,
                              const double* X, double* G, double* lp);
+
+/*
+ * Batched ordinal target: the log-density and the score of K cumulative-logit (proportional odds) regressions of one (N, P, C) at nc
+ * points each, one launch.  examples/example_gsm.py:34-35, a model's log_prob and lp_g = jit(grad(...)) of it, for an ordered
+ * response (ratings, grades, severity scores) -> gsmvi_ordinal_batched_f64.  Problem k has the design matrix A_k (N rows a_n of P
+ * columns, no intercept column), integer labels y_kn in 0 .. C - 1, an optional offset o_kn (NULL = none), n_k valid rows, and the
+ * parameter x = (beta, delta) of length D = P + C - 1.  The cutpoints are ordered by construction:
+ *   cut_0 = delta_0,   cut_j = cut_{j-1} + e^{delta_j}   (j = 1 .. C - 2)
+ * and P(y_n = c) = sigma(cut_c - eta_n) - sigma(cut_{c-1} - eta_n) with eta_n = a_n . beta + o_n, cut_{-1} = -inf, cut_{C-1} = +inf.
+ * With a = cut_{y-1} - eta (y >= 1), b = cut_y - eta (y <= C - 2) and, for an interior class 1 <= y <= C - 2, w = e^{delta_y}:
+ *   t     = -[y <= C-2] softplus(-b) - [y >= 1] softplus(a) + [interior] log(1 - e^{-w})
+ *   u_lo  = -sigma(a) - [interior] / expm1(w)     (= dt / d cut_{y-1}; y >= 1, else 0)
+ *   u_hi  = sigma(-b) + [interior] / expm1(w)     (= dt / d cut_y;     y <= C-2, else 0)
+ *   r_eta = sigma(a) - sigma(-b)                  (= dt / d eta)
+ *   lp[k, c]       = sum_{n < n_k} t_n - lam_k |beta|^2 / 2 - kap_k |delta|^2 / 2
+ *   G[k, c, :P]    = sum_{n < n_k} r_eta,n a_n - lam_k beta
+ *   gcut_j         = sum_{n < n_k} ([y_n = j + 1] u_lo,n + [y_n = j] u_hi,n)
+ *   G[k, c, P]     = sum_{j >= 0} gcut_j - kap_k delta_0
+ *   G[k, c, P + i] = e^{delta_i} sum_{j >= i} gcut_j - kap_k delta_i          (i = 1 .. C - 2)
+ * No two probabilities are subtracted: the gap w is e^{delta_y} itself and log(1 - e^{-w}) is a proper log1mexp.  For C = 2 the
+ * model is logistic regression on the design [A, -1] with the intercept's prior precision kap.  A (K x N x P) doubles, y (K x N)
+ * ints, offset (K x N), X, G (K x nc x D), lp (K x nc), packed, in device memory; C >= 2, P >= 1, D <= 64; K, nc, N, counts_dev and
+ * prior_prec / prior_prec_dev (lam, the prior N(0, I / lam_k) of beta) as in gsmvi_glm_batched_f64; cut_prec / cut_prec_dev (kap,
+ * finite and >= 0; 0 = flat) in the same scalar-or-K-values style: the prior N(0, I / kap_k) of delta.  At least one of G, lp is
+ * given.  Every output row sums over n in the order 0 .. n_k - 1 in one thread, the suffix sums over j run from C - 2 downwards, and
+ * a row depends on its problem and its own row of X only: the same bits for any K, nc and neighbours; no atomics.  Rows n >= n_k are
+ * never loaded; n_k = 0 leaves the two priors.  A label outside 0 .. C - 1 cannot be checked on this side of the ABI: the kernel
+ * clamps it, so it reads nothing out of bounds (the range is the caller's to keep).  A row of X with a non-finite entry, or in which
+ * some e^{delta_j}, j >= 1, is not a positive normal number (|delta_j| above 708), gets NaN outputs and no other row is touched;
+ * delta_0 is a location and is not limited.  Shapes, priors, NULL arrays and overlaps (G and lp are the written arrays) are checked
+ * before the context is looked at (then a NULL ctx); every failure returns GSMVI_ERR_BAD_ARG before anything is enqueued.  Inputs
+ * are only read; no context workspace; one capturable launch.  Sets GSMVI_PATH_BATCHED_TARGET.
+ */
+int gsmvi_ordinal_batched_f64(gsmvi_ctx* ctx, void* stream, int64_t K, int P, int C, int nc, int64_t N, const double* A,
+                              const int* y, const double* offset, const int* counts_dev, double prior_prec,
+                              const double* prior_prec_dev, double cut_prec, const double* cut_prec_dev, const double* X, double* G,
+                              double* lp);
 
 /*
  * Batched softmax target: the log-density and the score of K Bayesian multinomial logit regressions of one (N, C, P) at nc points

@@ -58,6 +58,11 @@ int gsmvi_debug_glm_shared_batched_lds(int D, int want, int family, size_t* byte
  * most GB_LDS_MAX (76 KB: four problems of D = 16 with both outputs and an offset).  Host arithmetic only, no device needed. */
 int gsmvi_debug_negbin_batched_lds(int D, int nc, int want, int has_offset, size_t* bytes, int* problems_per_workgroup);
 
+/* The same for a gsmvi_ordinal_batched_f64 launch at (C >= 2, P >= 1, P + C - 1 <= 64, nc), with (has_offset != 0) or without an
+ * offset: at most GB_LDS_MAX (113.1 KB: one problem of C = 64 with both outputs and an offset).  Host arithmetic only, no device
+ * needed. */
+int gsmvi_debug_ordinal_batched_lds(int C, int P, int nc, int want, int has_offset, size_t* bytes, int* problems_per_workgroup);
+
 /* The same for a gsmvi_negbin_hessian_batched_f64 or gsmvi_negbin_laplace_step_batched_f64 launch at D = P + 1 in 2 .. 64 (both
  * request the same, with or without an offset): at most 64 KB, so no kernel attribute.  Host arithmetic only, no device needed. */
 int gsmvi_debug_negbin_laplace_lds(int D, size_t* bytes, int* problems_per_workgroup);
