@@ -1,99 +1,86 @@
 // Batched PSIS leave-one-out: for K fitted Gaussians q_k over the coefficients of K GLMs of one (N, D), D <= 64, the pointwise
 // leave-one-out log predictive density of every observation from S draws of q_k, one launch ("Batched
-// PSIS-LOO"; the definition is in include/gsmvi_hip.h: Vehtari, Gelman, Gabry 2017 with the correction for draws of an
-// approximation, Magnusson, Andersen, Jonasson, Vehtari 2019).  The reference has no twin.
-//   k_psis_loo_batched<FAM>
-// Work mapping: one 256-thread workgroup per (problem k, tile of NI = gsmvi_psis_loo_tile(D, S) observations).
-//   (1) eta = X_k A_tile^T (S x NI) on the fp64 MFMA (16 x 16 x 4): the NI rows of A_k sit in LDS zero-padded to 16 rows of
-//       Dp = glm_dp(D) columns (row stride Dp + 1); X_k streams through LDS once in tiles of 64 draws, zero-padded the same
-//       way; wave w takes the 16 draws 16 w .. 16 w + 15 of the tile, the A operand x_{s, 4 j + ks}, the B operand
-//       a_{i, 4 j + ks}, Dp / 4 steps.  Each accumulator entry gets its offset, goes through lb_link (gsmvi_glm_link.h) and is
-//       normalised as the predictive's lpd is; the tile's l_si stay in LDS (NI x S doubles).
-//   (2) per observation of the tile: ps_loo_stage (gsmvi_psis_stage.h, shared with k_psis_loo_softmax_batched): rho_s = logr_s -
-//       l_si into the PSIS stage's array, ps_stage, then the two log-sum-exps -- elpd from the stage's weights, lpd from the
-//       problem-level weights lw.
-// The tiles of (1) lie over the stage's LDS (they are dead before the first stage starts).  NI is the largest count, at most
-// PL_NI_CAP, whose l_si fit beside that region in GB_LDS_MAX.  Every sum is a fixed tree and there are no atomics; every thread
-// of a workgroup runs the same barriers whatever the verdicts (the number of valid observations of a tile is uniform in it); a
-// workgroup reads only slice k of the inputs and writes only its own (k, i) entries.  Inputs are only read; no context workspace.
+// PSIS-LOO" and "Shared-design PSIS-LOO"; the definitions are in include/gsmvi_hip.h: Vehtari, Gelman, Gabry 2017 with the
+// correction for draws of an approximation, Magnusson, Andersen, Jonasson, Vehtari 2019).  The reference has no twin.
+//   k_psis_loo_batched<FAM, SHARED>   SHARED = false: a design matrix A_k and a count of valid rows per problem
+//                                     (gsmvi_psis_loo_batched_f64); true: ONE design matrix A (N, D) and observation weights
+//                                     (gsmvi_psis_loo_shared_batched_f64, recorded as k_psis_loo_shared_batched)
+// The work mapping, the LDS and stage (2) are the tile block's (gsmvi_psis_loo_tile.h), NI = gsmvi_psis_loo_tile(D, S) for both.
+//   (1) eta = X_k A_tile^T (S x NI): the A tile has Dp = glm_dp(D) columns (row stride Dp + 1), the draw tiles the same, Dp / 4
+//       steps of ps_loo_eta.  Each accumulator entry of a valid observation gets its offset, goes through lb_link
+//       (gsmvi_glm_link.h) and is normalised as the predictive's lpd is; l_si is the UNWEIGHTED log density of one unit observation.
+// The two forms differ in four places and nowhere else.  The A tile: read at row k N + i0 of A, rows past nv zero -- or at row i0
+// of the one A (no k term), rows past ni zero.  The valid rows: the first nv = min(counts_k - i0, ni) -- or those with a weight
+// v_ki > 0 (not 0, not NaN; no weights: all ni), read from global memory, the same values by every thread, so that either rule is
+// uniform in the workgroup; the weights are not staged in LDS because stage (2), which needs them again, runs after the tiles are
+// dead.  y_i, o_i and the normalising term go into LDS for the valid rows only (0 for the others: what an invalid row holds in y
+// and offset never reaches the link), and a lane whose column is not valid skips the link and stores nothing.  tau: the same
+// expression, there being no counts to read with it.  Stage (2): (nv, no weights) -- or (ni, the tile's weights): rho_s = logr_s -
+// v_ki l_si.  Operand order and K-loop are one text: with A_k = A, all rows valid and no weights the two launches give the same bits.
 #include "gsmvi_common.h"
 #include "gsmvi_ctx.h"
 #include "gsmvi_batched.h"
 #include "gsmvi_glm_model.h"
-#include "gsmvi_psis_stage.h"
+#include "gsmvi_psis_loo_tile.h"
 #include "../../include/gsmvi_hip.h"
 #include <cmath>
 #include <cstdint>
 
 struct pl_args {
-    glm_model m;                // the fitted model: A, y, offset, counts, noise precision; no prior
-    int S, S2, M;               // draws, draws padded to a power of two, the tail size before ties
-    int NI, U;                  // observations per tile; doubles of the region the stage and the MFMA tiles share
-    unsigned ntile;             // tiles per problem: ceil(N / NI)
-    const double* X;            // (K, S, D) the draws of q_k
-    ps_loo_io o;                // the ratios and weights of the problem-level run, the outputs
+    glm_model m;                // the fitted model: A ((K, N, D), or the one (N, D)), y, offset, counts, noise precision; no prior
+    const double* w;            // SHARED: (K, N) observation weights, or null: 1
+    ps_loo_args c;
 };
 
 // doubles of the kernel's own use of the shared region: the two MFMA tiles and three per-observation arrays
 static inline int pl_tiles_doubles(int D) { return (PS_LOO_TR + PS_LOO_NB) * (glm_dp(D) + 1) + 3 * PS_LOO_NB; }
 
-static int pl_tile(int D, int S) { return ps_loo_tile(pl_tiles_doubles(D), S, PL_NI_CAP); }
-
-template <int FAM>
+template <int FAM, bool SHARED>
 __global__ __launch_bounds__(256) void k_psis_loo_batched(pl_args a) {
-    extern __shared__ double pl_sm[];
-    const int l = threadIdx.x, S = a.S, S2 = a.S2, M = a.M, NI = a.NI;
+    const int l = threadIdx.x, S = a.c.S;
     const int D = a.m.D, Dp = glm_dp(D), lda = Dp + 1;
-    const long long N = a.m.N;
-    const size_t k = blockIdx.x / a.ntile;
-    const long long i0 = (long long)(blockIdx.x - (unsigned)k * a.ntile) * NI;       // the tile's first observation
-    const int ni = (int)(N - i0 < NI ? N - i0 : NI);
-    const glm_problem pk = glm_problem_of<FAM>(a.m, (long long)k, true);
-    const int nv = (int)(pk.nk - i0 < 0 ? 0 : (pk.nk - i0 < ni ? pk.nk - i0 : ni));  // its valid observations: the first nv
-    const ps_lds sm = ps_carve(pl_sm, reinterpret_cast<int*>(pl_sm + ps_lds_doubles(S, S2)), S, S2);
-    double* Xs = pl_sm;                       // 64 x lda      a tile of draws          (over the stage's arrays)
-    double* As = Xs + PS_LOO_TR * lda;        // 16 x lda      the tile's rows of A_k
+    const ps_loo_pos p = ps_loo_pos_of(a.c, a.m.N);
+    const glm_problem pk = glm_problem_of<FAM>(a.m, (long long)p.k, true);
+    const double* wk = SHARED && a.w ? a.w + p.kn : nullptr;                         // the tile's weights (ni of them)
+    const int nv = SHARED ? p.ni : ps_loo_valid(pk.nk, p);
+    const auto on = [&](int i) { return i < nv && (!wk || wk[i] > 0.0); };           // row i of the tile is a valid observation
+    bool any = SHARED ? wk == nullptr : nv > 0;                                      // a valid row in the tile
+    if (SHARED)
+        for (int i = 0; i < nv && !any; ++i) any = wk[i] > 0.0;
+    const ps_loo_lds lds = ps_loo_carve(a.c);
+    double* Xs = lds.tiles;                   // 64 x lda      a tile of draws          (over the stage's arrays)
+    double* As = Xs + PS_LOO_TR * lda;        // 16 x lda      the tile's rows of A
     double* ys = As + PS_LOO_NB * lda;        // 16 each: y_i, offset_i, the normalising term of l_si
     double* os = ys + PS_LOO_NB;
     double* cs = os + PS_LOO_NB;
-    double* ell = pl_sm + a.U;                // NI x S        l_si of the tile
-    const size_t ks = k * (size_t)S, kn = k * (size_t)N + (size_t)i0;
     const double qnan = __longlong_as_double(0x7ff8000000000000LL);
 
     // ---- (1) l_si of the tile's valid observations ------------------------------------------------------------------------
-    if (nv > 0) {                             // (uniform in the workgroup)
-        const double* Ak = a.m.A + kn * D;
-        for (int e = l; e < PS_LOO_NB * lda; e += 256) {
-            const int r = e / lda, j = e - r * lda;
-            As[e] = r < nv && j < D ? Ak[(size_t)r * D + j] : 0.0;
-        }
+    if (any) {                                // (uniform in the workgroup)
+        ps_loo_load_rows(As, lda, a.m.A + (SHARED ? (size_t)p.i0 : p.kn) * D, D, nv, D, l);
         if (l < PS_LOO_NB) {
-            const double yv = l < nv ? a.m.y[kn + l] : 0.0;
+            const bool v = on(l);
+            const double yv = v ? a.m.y[p.kn + l] : 0.0;
             ys[l] = yv;
-            os[l] = a.m.offset && l < nv ? a.m.offset[kn + l] : 0.0;
+            os[l] = a.m.offset && v ? a.m.offset[p.kn + l] : 0.0;
             cs[l] = FAM == LB_POISSON ? -lgamma(yv + 1.0) : (FAM == LB_GAUSSIAN ? 0.5 * log(pk.tau / 6.28318530717958647692) : 0.0);
         }
-        const double* Xk = a.X + ks * D;
-        const int wv = l >> 6, ln = l & 63, cc = ln & 15, kq = ln >> 4;
+        const double* Xk = a.c.X + p.ks * D;
+        const ps_loo_lane ln = ps_loo_lane_of(l);
+        const bool von = on(ln.cc);           // this lane's column is a valid observation
         for (int t0 = 0; t0 < S; t0 += PS_LOO_TR) {
             __syncthreads();                  // the previous tile's readers are done
-            for (int e = l; e < PS_LOO_TR * lda; e += 256) {
-                const int r = e / lda, j = e - r * lda;
-                Xs[e] = t0 + r < S && j < D ? Xk[(size_t)(t0 + r) * D + j] : 0.0;
-            }
+            ps_loo_load_draws(Xs, lda, Xk, D, D, t0, S, l);
             __syncthreads();
-            if (t0 + 16 * wv < S) {           // (wave-uniform)
-                const double* pa = Xs + (16 * wv + cc) * lda + kq;
-                const double* pb = As + cc * lda + kq;
-                v4d acc = v4d{0.0, 0.0, 0.0, 0.0};
-                for (int j = 0; j < Dp; j += 4) acc = GSMVI_MFMA_F64(pa[j], pb[j], acc);
+            if (t0 + 16 * ln.wv < S) {        // (wave-uniform)
+                const v4d acc = ps_loo_eta(Xs, As, lda, Dp, ln);
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
-                    const int s = t0 + 16 * wv + kq + 4 * r;    // the draw; cc is the observation
-                    if (s < S && cc < nv) {
+                    const int s = ps_loo_draw(t0, ln, r);
+                    if (s < S && von) {
                         double g = 0.0, t = 0.0;
-                        const bool ok = lb_link<FAM, false, true>(acc[r] + os[cc], ys[cc], pk.tau, g, t);
-                        ell[cc * S + s] = ok ? t + cs[cc] : qnan;
+                        const bool ok = lb_link<FAM, false, true>(acc[r] + os[ln.cc], ys[ln.cc], pk.tau, g, t);
+                        lds.ell[ln.cc * S + s] = ok ? t + cs[ln.cc] : qnan;
                     }
                 }
             }
@@ -101,19 +88,31 @@ __global__ __launch_bounds__(256) void k_psis_loo_batched(pl_args a) {
     }
     __syncthreads();                          // l_si is published; the tiles are dead, the stage may take their place
 
-    ps_loo_stage(a.o, sm, ell, ni, nv, nullptr, ks, kn, S, S2, M, l);     // (2)
+    ps_loo_stage(a.c.o, lds.sm, lds.ell, p.ni, nv, wk, p.ks, p.kn, S, a.c.S2, a.c.M, l);     // (2)
 }
 
-hipError_t gsmvi_psis_loo_batched_prepare() {
-    return gb_allow_lds(k_psis_loo_batched<LB_LOGISTIC>, k_psis_loo_batched<LB_POISSON>, k_psis_loo_batched<LB_PROBIT>,
-                        k_psis_loo_batched<LB_GAUSSIAN>);
+template <bool SHARED>
+static hipError_t pl_prepare() {
+    return gb_allow_lds(k_psis_loo_batched<LB_LOGISTIC, SHARED>, k_psis_loo_batched<LB_POISSON, SHARED>,
+                        k_psis_loo_batched<LB_PROBIT, SHARED>, k_psis_loo_batched<LB_GAUSSIAN, SHARED>);
+}
+hipError_t gsmvi_psis_loo_batched_prepare() { return pl_prepare<false>(); }
+hipError_t gsmvi_psis_loo_shared_batched_prepare() { return pl_prepare<true>(); }
+
+template <bool SHARED>
+static void pl_launch(int family, const glm_model& m, const double* w, const ps_loo_launch& p, void* stream) {
+    const pl_args a = {m, w, p.c};
+    glm_for_family(family, [&](auto fam) {
+        hipLaunchKernelGGL((k_psis_loo_batched<decltype(fam)::value, SHARED>), dim3(p.grid), dim3(256), p.lds,
+                           reinterpret_cast<hipStream_t>(stream), a);
+    });
 }
 
 extern "C" {
 
 int gsmvi_psis_loo_tile(int D, int64_t S) {
     if (D < 1 || D > GB_MAX_D || S < PS_MIN_S || S > PS_MAX_S) return 0;
-    return pl_tile(D, (int)S);
+    return ps_loo_tile(pl_tiles_doubles(D), (int)S, PL_NI_CAP);
 }
 
 int gsmvi_psis_loo_batched_f64(gsmvi_ctx* ctx, void* stream, int family, int64_t K, int64_t N, int D, int64_t S, const double* A,
@@ -122,35 +121,41 @@ int gsmvi_psis_loo_batched_f64(gsmvi_ctx* ctx, void* stream, int family, int64_t
                                double* loglik, double* elpd, double* lpd, double* khat, double* ess, int* info) {
     const glm_model m = {K, N, D, A, y, offset, counts_dev, 0.0, nullptr, noise_prec, noise_prec_dev};
     if (int st = glm_check_model(__func__, m, family, "N", false)) return st;
-    GB_BAD(S < PS_MIN_S || S > PS_MAX_S, "S must be in [5, 4096]");
-    GB_BAD(!A || !y || !X || !logr || !lw || !elpd || !lpd || !khat || !ess || !info, "NULL array");
-    GB_BAD(N > (INT64_MAX / 8 / S) / K, "K N S is too large");
-    const int NI = pl_tile(D, (int)S);
-    const int64_t ntile = (N + NI - 1) / NI;
-    GB_BAD(ntile > 16777215 / K, "K ceil(N / gsmvi_psis_loo_tile(D, S)) must be at most 2^24 - 1 (one tile per workgroup)");
-    const size_t nn = (size_t)K * N * 8, ns = (size_t)K * S * 8;
-    if (int st = gb_check_overlaps(__func__, m, {{X, ns * D, "X", GB_RD}, {logr, ns, "logr", GB_RD}, {lw, ns, "lw", GB_RD},
-                                                 {loglik, nn * S, "loglik", GB_WR}, {elpd, nn, "elpd", GB_WR}, {lpd, nn, "lpd", GB_WR},
-                                                 {khat, nn, "khat", GB_WR}, {ess, nn, "ess", GB_WR},
-                                                 {info, (size_t)K * N * 4, "info", GB_WR}}))
+    ps_loo_launch p = {};
+    if (int st = ps_loo_plan(__func__, K, N, S, 0, !A || !y, X, {logr, lw, loglik, elpd, lpd, khat, ess, info},
+                             pl_tiles_doubles(D), PL_NI_CAP, "gsmvi_psis_loo_tile(D, S)", &p))
         return st;
+    gb_arr own[PS_LOO_ROWS];
+    ps_loo_overlap_rows(own, K, N, D, p.c);
+    if (int st = gb_check_overlaps(__func__, m, own)) return st;
     GB_BAD(!ctx, "ctx is NULL");
-    pl_args a = {};
-    a.m = m;
-    a.S = (int)S;
-    ps_sizes(a.S, &a.S2, &a.M);
-    a.NI = NI;
-    a.U = ps_loo_region_doubles(pl_tiles_doubles(D), a.S, a.S2);
-    a.ntile = (unsigned)ntile;
-    a.X = X;
-    a.o = {logr, lw, loglik, elpd, lpd, khat, ess, info};
-    const size_t lds = ((size_t)a.U + (size_t)NI * a.S) * sizeof(double);      // <= GB_LDS_MAX by the choice of NI
-    const unsigned grid = (unsigned)(K * ntile);
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    glm_for_family(family, [&](auto fam) {
-        hipLaunchKernelGGL((k_psis_loo_batched<decltype(fam)::value>), dim3(grid), dim3(256), lds, st, a);
-    });
+    pl_launch<false>(family, m, nullptr, p, stream);
     return gb_launched(ctx, GSMVI_PATH_BATCHED_LOO, "k_psis_loo_batched");
+}
+
+int gsmvi_psis_loo_shared_batched_f64(gsmvi_ctx* ctx, void* stream, int family, int64_t K, int64_t N, int D, int64_t S,
+                                      const double* A, const double* y, const double* offset, const double* weights,
+                                      double noise_prec, const double* noise_prec_dev, const double* X, const double* logr,
+                                      const double* lw, double* loglik, double* elpd, double* lpd, double* khat, double* ess,
+                                      int* info) {
+    // the model's checks are the per-problem entry's (its "K N D is too large" bounds y, offset and weights, and A a fortiori)
+    const glm_model m = {K, N, D, A, y, offset, nullptr, 0.0, nullptr, noise_prec, noise_prec_dev};
+    if (int st = glm_check_model(__func__, m, family, "N", false)) return st;
+    ps_loo_launch p = {};
+    if (int st = ps_loo_plan(__func__, K, N, S, 0, !A || !y, X, {logr, lw, loglik, elpd, lpd, khat, ess, info},
+                             pl_tiles_doubles(D), PL_NI_CAP, "gsmvi_psis_loo_tile(D, S)", &p))
+        return st;
+    const size_t nn = (size_t)K * N * 8;
+    gb_arr all[5 + PS_LOO_ROWS] = {{A, (size_t)N * D * 8, "A", GB_RD},       // (one (N, D) matrix here)
+                                   {y, nn, "y", GB_RD},
+                                   {offset, nn, "offset", GB_RD},
+                                   {weights, nn, "weights", GB_RD},
+                                   {noise_prec_dev, (size_t)K * 8, "noise_prec_dev", GB_RD}};
+    ps_loo_overlap_rows(all + 5, K, N, D, p.c);
+    if (int st = gb_check_overlaps(__func__, all, all + 5 + PS_LOO_ROWS)) return st;
+    GB_BAD(!ctx, "ctx is NULL");
+    pl_launch<true>(family, m, weights, p, stream);
+    return gb_launched(ctx, GSMVI_PATH_BATCHED_LOO | GSMVI_PATH_BATCHED_TARGET, "k_psis_loo_shared_batched");
 }
 
 }  // extern "C"

@@ -1,10 +1,7 @@
 // The PSIS stage of the batched diagnostics: steps 1-8 of the definition in include/gsmvi_hip.h (gsmvi_psis_weights_batched_f64)
 // on the S log ratios that one 256-thread workgroup holds in LDS.  One copy, called by k_psis_batched<PS_WEIGHTS>,
-// k_psis_batched<PS_FUSED> (gsmvi_psis_batched.hip: once per problem) and, once per observation, by ps_loo_stage at the end of this
-// file: the observation stage of the leave-one-out kernels, k_psis_loo_batched (gsmvi_psis_loo_batched.hip),
-// k_psis_loo_softmax_batched (gsmvi_psis_loo_softmax_batched.hip), k_psis_loo_negbin_batched (gsmvi_psis_loo_negbin_batched.hip) and,
-// with observation weights, k_psis_loo_shared_batched (gsmvi_psis_loo_shared_batched.hip), with the tile geometry they share;
-// DESIGN.md section 9.
+// k_psis_batched<PS_FUSED> (gsmvi_psis_batched.hip: once per problem) and, once per observation, by ps_loo_stage of
+// gsmvi_psis_loo_tile.h, the observation stage of the leave-one-out kernels; DESIGN.md section 9.
 // In LDS: the S ratios padded with +inf to S2 = the next power of two, their S2 indices, the S normalised weights in row order,
 // the tail (at most 192 exceedances) and the 43 candidates of its fit.  Two reductions (non-finite count, maximum); a bitonic
 // network on (value, index) pairs, ascending by value then by index -- numpy's stable argsort, so ties fall the same way on
@@ -210,105 +207,4 @@ __device__ __forceinline__ ps_verdict ps_stage(const ps_lds p, int S, int S2, in
     }
     const double ess = 1.0 / ps_sum(s2, red, l);   // (its barriers also publish lwu)
     return ps_verdict{kh, ess, lse, vmax, bad, fit};
-}
-
-// ---- the leave-one-out kernels' shared part -----------------------------------------------------------------------------------
-// One 256-thread workgroup per (problem, tile of NI observations).  Stage (1), the kernel's own, leaves l_si of the tile in LDS from
-// MFMA tiles that lie over this stage's arrays; stage (2) is ps_loo_stage below.
-#define PS_LOO_TR 64    // draws per tile of X_k: one 16-row MFMA block per wave
-#define PS_LOO_NB 16    // rows of the A_k tile: the MFMA's 16 columns, NI of them in use
-// observations per workgroup at most (fewer observations, more workgroups per CU); a diagnostic build changes the cap
-// of one kernel with -DPL_NI_CAP=n (k_psis_loo_batched) or -DPLS_NI_CAP=n (k_psis_loo_softmax_batched)
-#ifndef PL_NI_CAP
-#define PL_NI_CAP 4
-#endif
-#ifndef PLS_NI_CAP
-#define PLS_NI_CAP 4
-#endif
-
-// doubles of the region the stage shares with a kernel's `tiles` doubles of MFMA tiles: the stage's arrays and its S2 indices, or
-// the tiles, whichever is larger
-__host__ __device__ inline int ps_loo_region_doubles(int tiles, int S, int S2) {
-    const int stage = ps_lds_doubles(S, S2) + S2 / 2;
-    return stage > tiles ? stage : tiles;
-}
-
-// NI: the largest count, at most `cap`, whose l_si (NI x S doubles) fit beside the region in GB_LDS_MAX (>= 2 at S = 4096)
-static inline int ps_loo_tile(int tiles, int S, int cap) {
-    int S2, M;
-    ps_sizes(S, &S2, &M);
-    const int fit = (GB_LDS_MAX / 8 - ps_loo_region_doubles(tiles, S, S2)) / S;
-    return fit < cap ? fit : cap;
-}
-
-// what stage (2) reads and writes beside the l_si: a member of both kernels' argument blocks
-struct ps_loo_io {
-    const double* logr;         // (K, S) lp - log q of the problem-level run
-    const double* lw;           // (K, S) its normalised smoothed log weights
-    double* loglik;             // (K, N, S) or null
-    double* elpd;               // (K, N) each
-    double* lpd;
-    double* khat;
-    double* ess;
-    int* info;                  // (K, N) 0; -1 non-finite ratios; -2 tail too short; -3 not a valid row
-};
-
-// Stage (2), per observation i < ni of the tile: rho_s = logr_s - l_si into the stage's array, ps_stage, then the two
-// log-sum-exps -- the maximum by a block reduction, then the sum of exp(. - max) -- elpd from the stage's weights, lpd from the
-// problem-level weights lw.  ell: the tile's l_si in LDS (NI x S, published by a barrier before the call); ks = k S, kn = k N + the
-// tile's first observation.  w: null -- the first nv rows of the tile are the valid ones -- or the observation weights of the
-// tile's ni rows (k_psis_loo_shared_batched; nv is then not used): row i is valid iff w_i > 0 (not for 0 or NaN), and leaving it
-// out removes its whole weighted term, rho_s = logr_s - w_i l_si (w_i = 1: the product is exact, the same bits as without w).
-__device__ __forceinline__ void ps_loo_stage(const ps_loo_io a, const ps_lds sm, const double* ell, int ni, int nv, const double* w,
-                                             size_t ks, size_t kn, int S, int S2, int M, int l) {
-    const double qnan = __longlong_as_double(0x7ff8000000000000LL), inf = __builtin_huge_val();
-    for (int i = 0; i < ni; ++i) {
-        const size_t ki = kn + i;
-        double* lk = a.loglik ? a.loglik + ki * S : nullptr;
-        const double wi = w ? w[i] : 1.0;
-        if (w ? !(wi > 0.0) : i >= nv) {      // not a valid row (uniform in the workgroup: no barrier is skipped by a part of it)
-            if (lk)
-                for (int s = l; s < S; s += 256) lk[s] = qnan;
-            if (l == 0) {
-                a.elpd[ki] = qnan;
-                a.lpd[ki] = qnan;
-                a.khat[ki] = qnan;
-                a.ess[ki] = qnan;
-                a.info[ki] = -3;
-            }
-            continue;
-        }
-        const double* el = ell + i * S;
-        for (int s = l; s < S; s += 256) {
-            const double e = el[s];
-            sm.val[s] = w ? a.logr[ks + s] - wi * e : a.logr[ks + s] - e;
-            if (lk) lk[s] = e;
-        }
-        __syncthreads();
-        const ps_verdict v = ps_stage(sm, S, S2, M, l, false);
-        double m1 = -inf, m2 = -inf;
-        for (int s = l; s < S; s += 256) {
-            const double e = el[s];
-            m1 = fmax(m1, sm.lwu[s] + e);
-            m2 = fmax(m2, a.lw[ks + s] + e);
-        }
-        m1 = ps_max(m1, sm.red, l);
-        m2 = ps_max(m2, sm.red, l);
-        double s1 = 0.0, s2 = 0.0;
-        for (int s = l; s < S; s += 256) {
-            const double e = el[s];
-            s1 += exp((sm.lwu[s] + e) - m1);
-            s2 += exp((a.lw[ks + s] + e) - m2);
-        }
-        s1 = ps_sum(s1, sm.red, l);
-        s2 = ps_sum(s2, sm.red, l);
-        if (l == 0) {
-            a.elpd[ki] = v.bad ? qnan : m1 + log(s1);
-            a.lpd[ki] = v.bad ? qnan : m2 + log(s2);
-            a.khat[ki] = v.bad ? qnan : v.khat;
-            a.ess[ki] = v.bad ? qnan : v.ess;
-            a.info[ki] = v.bad ? -1 : (v.fit ? 0 : -2);
-        }
-        __syncthreads();                      // the next observation overwrites the stage's arrays
-    }
 }

@@ -8,7 +8,7 @@ the same draws one step further for the GLM targets: the PSIS leave-one-out log 
 fitted models are compared; ``psis_loo_softmax_batched`` is the same for ``BatchedSoftmaxTarget``
 (csrc/gsmvi_psis_loo_softmax_batched.hip), ``psis_loo_negbin_batched`` for ``BatchedNegBinomialTarget``
 (csrc/gsmvi_psis_loo_negbin_batched.hip) and ``psis_loo_shared_batched`` for ``SharedDesignGLMTarget``, observation weights
-honoured (csrc/gsmvi_psis_loo_shared_batched.hip)."""
+honoured (the other form of the kernel in csrc/gsmvi_psis_loo_batched.hip)."""
 from dataclasses import dataclass
 
 import numpy as np

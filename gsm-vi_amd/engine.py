@@ -1358,6 +1358,19 @@ class HipEngine:
         return logr, lw, khat, ess, log_z, mean_is, cov_is, info
 
     # ---- batched PSIS leave-one-out of K fitted GLM posteriors (csrc/gsmvi_psis_loo_batched.hip) ----------------------------------
+    def _loo_call(self, name, head, K, N, S, D, X, logr, lw, pointwise_loglik):
+        """The end of the four ``psis_loo_*_batched``: the outputs, the launch of ``name`` on the entry's own leading arguments
+        ``head`` followed by the nine that every entry ends with, and what they all return"""
+        X, logr, lw = X.contiguous(), logr.contiguous(), lw.contiguous()
+        elpd, lpd, khat, ess = self.empty(K, N), self.empty(K, N), self.empty(K, N), self.empty(K, N)
+        info = self.batched_ints(K * N).view(K, N)
+        loglik = self.empty(K, N, S) if pointwise_loglik else None
+        self._call(name, *head, self._packed(X, (K, S, D), "X"), self._packed(logr, (K, S), "logr"),
+                   self._packed(lw, (K, S), "lw"), self._dp(loglik, (K, N, S), "loglik"), self._packed(elpd, (K, N), "elpd"),
+                   self._packed(lpd, (K, N), "lpd"), self._packed(khat, (K, N), "khat"), self._packed(ess, (K, N), "ess"),
+                   self._ints(info, K * N, "info"))
+        return elpd, lpd, khat, ess, info, loglik
+
     def psis_loo_tile(self, D, S):
         """gsmvi_psis_loo_tile: the observations one workgroup of ``psis_loo_batched`` takes at (D, S); a pure function, no GPU"""
         return int(self.lib.gsmvi_psis_loo_tile(int(D), int(S)))
@@ -1373,17 +1386,9 @@ class HipEngine:
         N = A.shape[1]
         fam, t, tp = self._glm_family_args(family, noise_prec, K)
         self._any_ctx()
-        X, logr, lw = X.contiguous(), logr.contiguous(), lw.contiguous()
-        elpd, lpd, khat, ess = self.empty(K, N), self.empty(K, N), self.empty(K, N), self.empty(K, N)
-        info = self.batched_ints(K * N).view(K, N)
-        loglik = self.empty(K, N, S) if pointwise_loglik else None
-        self._call("gsmvi_psis_loo_batched_f64", fam, K, N, D, S, self._packed(A, (K, N, D), "A"),
-                   self._packed(y, (K, N), "y"), self._dp(offset, (K, N), "offset"), self._ints(counts, K, "counts"), t, tp,
-                   self._packed(X, (K, S, D), "X"), self._packed(logr, (K, S), "logr"), self._packed(lw, (K, S), "lw"),
-                   self._dp(loglik, (K, N, S), "loglik"), self._packed(elpd, (K, N), "elpd"),
-                   self._packed(lpd, (K, N), "lpd"), self._packed(khat, (K, N), "khat"), self._packed(ess, (K, N), "ess"),
-                   self._ints(info, K * N, "info"))
-        return elpd, lpd, khat, ess, info, loglik
+        head = (fam, K, N, D, S, self._packed(A, (K, N, D), "A"), self._packed(y, (K, N), "y"),
+                self._dp(offset, (K, N), "offset"), self._ints(counts, K, "counts"), t, tp)
+        return self._loo_call("gsmvi_psis_loo_batched_f64", head, K, N, S, D, X, logr, lw, pointwise_loglik)
 
     # ---- the same for K fitted multinomial logit posteriors (csrc/gsmvi_psis_loo_softmax_batched.hip) --------------------------
     def psis_loo_softmax_tile(self, C, P, S):
@@ -1400,15 +1405,8 @@ class HipEngine:
         K, S, D = X.shape
         (Cc, P, N), model = self._softmax_model_args(K, D, A, labels, num_classes, counts)
         self._any_ctx()
-        X, logr, lw = X.contiguous(), logr.contiguous(), lw.contiguous()
-        elpd, lpd, khat, ess = self.empty(K, N), self.empty(K, N), self.empty(K, N), self.empty(K, N)
-        info = self.batched_ints(K * N).view(K, N)
-        loglik = self.empty(K, N, S) if pointwise_loglik else None
-        self._call("gsmvi_psis_loo_softmax_batched_f64", K, Cc, P, N, S, *model, self._packed(X, (K, S, D), "X"),
-                   self._packed(logr, (K, S), "logr"), self._packed(lw, (K, S), "lw"), self._dp(loglik, (K, N, S), "loglik"),
-                   self._packed(elpd, (K, N), "elpd"), self._packed(lpd, (K, N), "lpd"), self._packed(khat, (K, N), "khat"),
-                   self._packed(ess, (K, N), "ess"), self._ints(info, K * N, "info"))
-        return elpd, lpd, khat, ess, info, loglik
+        return self._loo_call("gsmvi_psis_loo_softmax_batched_f64", (K, Cc, P, N, S, *model), K, N, S, D, X, logr, lw,
+                              pointwise_loglik)
 
     # ---- the same for K fitted negative binomial posteriors (csrc/gsmvi_psis_loo_negbin_batched.hip) ---------------------------
     def psis_loo_negbin_tile(self, P, S):
@@ -1428,18 +1426,11 @@ class HipEngine:
         if D != P + 1:
             raise ValueError(f"X: expected P + 1 = {P + 1} columns (beta, then the log size), got {D}")
         self._any_ctx()
-        X, logr, lw = X.contiguous(), logr.contiguous(), lw.contiguous()
-        elpd, lpd, khat, ess = self.empty(K, N), self.empty(K, N), self.empty(K, N), self.empty(K, N)
-        info = self.batched_ints(K * N).view(K, N)
-        loglik = self.empty(K, N, S) if pointwise_loglik else None
-        self._call("gsmvi_psis_loo_negbin_batched_f64", K, P, N, S, self._packed(A, (K, N, P), "A"), self._packed(y, (K, N), "y"),
-                   self._dp(offset, (K, N), "offset"), self._ints(counts, K, "counts"), self._packed(X, (K, S, D), "X"),
-                   self._packed(logr, (K, S), "logr"), self._packed(lw, (K, S), "lw"), self._dp(loglik, (K, N, S), "loglik"),
-                   self._packed(elpd, (K, N), "elpd"), self._packed(lpd, (K, N), "lpd"), self._packed(khat, (K, N), "khat"),
-                   self._packed(ess, (K, N), "ess"), self._ints(info, K * N, "info"))
-        return elpd, lpd, khat, ess, info, loglik
+        head = (K, P, N, S, self._packed(A, (K, N, P), "A"), self._packed(y, (K, N), "y"), self._dp(offset, (K, N), "offset"),
+                self._ints(counts, K, "counts"))
+        return self._loo_call("gsmvi_psis_loo_negbin_batched_f64", head, K, N, S, D, X, logr, lw, pointwise_loglik)
 
-    # ---- the same for K fitted GLM posteriors on ONE design matrix, weighted (csrc/gsmvi_psis_loo_shared_batched.hip) -------------
+    # ---- the same for K fitted GLM posteriors on ONE design matrix, weighted (k_psis_loo_batched<FAM, true> of the same file) ---
     def psis_loo_shared_batched(self, X, logr, lw, A, y, family, offset=None, weights=None, noise_prec=1.0, pointwise_loglik=False):
         """PSIS leave-one-out of K fitted GLM posteriors that share ONE design matrix, from the draws X (K, S, D) of q_k and the
         problem-level ratios ``logr`` and smoothed weights ``lw`` (K, S) of ``psis_batched`` on the same draws, one launch with no
@@ -1453,17 +1444,9 @@ class HipEngine:
         N = A.shape[0]
         fam, t, tp = self._glm_family_args(family, noise_prec, K)
         self._any_ctx()
-        X, logr, lw = X.contiguous(), logr.contiguous(), lw.contiguous()
-        elpd, lpd, khat, ess = self.empty(K, N), self.empty(K, N), self.empty(K, N), self.empty(K, N)
-        info = self.batched_ints(K * N).view(K, N)
-        loglik = self.empty(K, N, S) if pointwise_loglik else None
-        self._call("gsmvi_psis_loo_shared_batched_f64", fam, K, N, D, S, self._packed(A, (N, D), "A"),
-                   self._packed(y, (K, N), "y"), self._dp(offset, (K, N), "offset"), self._dp(weights, (K, N), "weights"), t, tp,
-                   self._packed(X, (K, S, D), "X"), self._packed(logr, (K, S), "logr"), self._packed(lw, (K, S), "lw"),
-                   self._dp(loglik, (K, N, S), "loglik"), self._packed(elpd, (K, N), "elpd"),
-                   self._packed(lpd, (K, N), "lpd"), self._packed(khat, (K, N), "khat"), self._packed(ess, (K, N), "ess"),
-                   self._ints(info, K * N, "info"))
-        return elpd, lpd, khat, ess, info, loglik
+        head = (fam, K, N, D, S, self._packed(A, (N, D), "A"), self._packed(y, (K, N), "y"),
+                self._dp(offset, (K, N), "offset"), self._dp(weights, (K, N), "weights"), t, tp)
+        return self._loo_call("gsmvi_psis_loo_shared_batched_f64", head, K, N, S, D, X, logr, lw, pointwise_loglik)
 
     # ---- batched softmax posterior predictive: the use of K fitted multinomial logit posteriors (csrc/gsmvi_softmax_predict_batched.hip)
     def softmax_predict_lds_bytes(self, C, P):

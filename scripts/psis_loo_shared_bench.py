@@ -1,4 +1,4 @@
-"""Shared-design PSIS leave-one-out benchmark (gsmvi_psis_loo_shared_batched_f64, csrc/gsmvi_psis_loo_shared_batched.hip).
+"""Shared-design PSIS leave-one-out benchmark (gsmvi_psis_loo_shared_batched_f64, csrc/gsmvi_psis_loo_batched.hip, SHARED).
 
 Writes one JSON object with, at (K, N, D, S) in {(1024, 64, 10, 1024), (1024, 256, 16, 1024)}, all in one process:
   loo[]  the launch alone and ``psis_loo_shared_batched`` end to end on a SharedDesignGLMTarget (logistic, K prior precisions on

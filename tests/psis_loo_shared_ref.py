@@ -1,5 +1,5 @@
 """Numpy restatement of the shared-design PSIS leave-one-out (gsmvi_psis_loo_shared_batched_f64,
-csrc/gsmvi_psis_loo_shared_batched.hip) in np.longdouble (``dtype=np.float64`` measures the float64 noise floor of the same
+csrc/gsmvi_psis_loo_batched.hip, SHARED) in np.longdouble (``dtype=np.float64`` measures the float64 noise floor of the same
 arithmetic), the generator of its test inputs, the closed-form leave-row-out density of the weighted conjugate Gaussian model, and
 a stand-in engine for the host logic of ``psis_loo_shared_batched``.  Test-only.  Built on psis_loo_ref (the pointwise likelihood,
 the log-sum-exps), psis_batched_ref (the PSIS stage) and shared_glm_ref (the weighted density).  From the definition in

@@ -1,4 +1,4 @@
-"""The shared-design PSIS leave-one-out on the GPU (csrc/gsmvi_psis_loo_shared_batched.hip): l_si against the longdouble
+"""The shared-design PSIS leave-one-out on the GPU (csrc/gsmvi_psis_loo_batched.hip, SHARED): l_si against the longdouble
 restatement (tests/psis_loo_shared_ref.py) and every other output against the restatement fed the device's own l_si, logr and lw,
 on every case of psis_loo_ref.CASES with A = A[0] and weights from {0, 0.5, 1, 2.5}; the bits of the per-problem launch on the
 replicated design where the weights say nothing new; the weighted sum over the rows against the target's lp; the verdicts among
