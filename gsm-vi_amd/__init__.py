@@ -55,6 +55,9 @@ Mirrors the reference's public surface for the hot path (reference file:line):
     psis_loo_negbin_batched (the same for K fitted
     negative binomial posteriors, -lgamma(y + 1)
     included: on one scale with the Poisson GLM's) examples/example_gsm.py:34-35, comparing fitted models; no reference twin
+    psis_loo_ordinal_batched (the same for K fitted
+    cumulative-logit posteriors over (beta, cutpoints):
+    on one scale with the multinomial logit's)     examples/example_gsm.py:34-35, comparing fitted models; no reference twin
     psis_loo_shared_batched (the same for K fitted
     GLM posteriors on ONE design matrix, observation
     weights honoured, no copy of A per problem)    examples/example_gsm.py:34-35, comparing fitted models; no reference twin
@@ -130,6 +133,7 @@ from .diagnostics import psis_batched, psis_weights_batched, PSISBatchedResult  
 from .diagnostics import psis_loo_batched, LOOBatchedResult          # noqa: F401
 from .diagnostics import psis_loo_softmax_batched                    # noqa: F401
 from .diagnostics import psis_loo_negbin_batched                     # noqa: F401
+from .diagnostics import psis_loo_ordinal_batched                    # noqa: F401
 from .diagnostics import psis_loo_shared_batched                     # noqa: F401
 from .advi import ADVI                                               # noqa: F401
 

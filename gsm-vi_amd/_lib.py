@@ -177,6 +177,10 @@ _SIGS = {
     "gsmvi_psis_loo_negbin_tile": (C.c_int, [C.c_int, C.c_int64]),
     "gsmvi_psis_loo_negbin_batched_f64": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int64, C.c_int64, _c_dp, _c_dp,
                                                     _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp]),
+    "gsmvi_psis_loo_ordinal_tile": (C.c_int, [C.c_int, C.c_int, C.c_int64]),
+    "gsmvi_psis_loo_ordinal_batched_f64": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int64, C.c_int64, _c_dp,
+                                                     _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp,
+                                                     _c_dp]),
     "gsmvi_psis_loo_shared_batched_f64": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_int64, _c_dp,
                                                     _c_dp, _c_dp, _c_dp, C.c_double, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp,
                                                     _c_dp, _c_dp, _c_dp]),

@@ -29,6 +29,7 @@ hipError_t gsmvi_psis_batched_prepare();
 hipError_t gsmvi_psis_loo_batched_prepare();
 hipError_t gsmvi_psis_loo_softmax_batched_prepare();
 hipError_t gsmvi_psis_loo_negbin_batched_prepare();
+hipError_t gsmvi_psis_loo_ordinal_batched_prepare();
 hipError_t gsmvi_psis_loo_shared_batched_prepare();
 hipError_t gsmvi_softmax_predict_batched_prepare();
 hipError_t gsmvi_negbin_batched_prepare();
@@ -266,6 +267,7 @@ int gsmvi_create(gsmvi_ctx** out, int device, int max_D, int max_B) {
     if (e == hipSuccess) e = gsmvi_psis_loo_batched_prepare();
     if (e == hipSuccess) e = gsmvi_psis_loo_softmax_batched_prepare();
     if (e == hipSuccess) e = gsmvi_psis_loo_negbin_batched_prepare();
+    if (e == hipSuccess) e = gsmvi_psis_loo_ordinal_batched_prepare();
     if (e == hipSuccess) e = gsmvi_psis_loo_shared_batched_prepare();
     if (e == hipSuccess) e = gsmvi_softmax_predict_batched_prepare();
     if (e == hipSuccess) e = gsmvi_negbin_batched_prepare();

@@ -1,7 +1,7 @@
 // The tile block of the PSIS leave-one-out kernels ("The leave-one-out tile block"): one copy of what
-// k_psis_loo_batched<FAM, SHARED> (gsmvi_psis_loo_batched.hip), k_psis_loo_softmax_batched (gsmvi_psis_loo_softmax_batched.hip) and
-// k_psis_loo_negbin_batched (gsmvi_psis_loo_negbin_batched.hip) share around their link steps, and of what their entry points share
-// around their model checks.
+// k_psis_loo_batched<FAM, SHARED> (gsmvi_psis_loo_batched.hip), k_psis_loo_softmax_batched (gsmvi_psis_loo_softmax_batched.hip),
+// k_psis_loo_negbin_batched (gsmvi_psis_loo_negbin_batched.hip) and k_psis_loo_ordinal_batched (gsmvi_psis_loo_ordinal_batched.hip)
+// share around their link steps, and of what their entry points share around their model checks.
 // Work mapping: one 256-thread workgroup per (problem k, tile of NI consecutive observations), k-major.
 //   (1) the kernel's own: l_si of the tile (NI x S doubles) into LDS.  The NI rows of A sit in LDS zero-padded to PS_LOO_NB = 16 rows
 //       (ps_loo_load_rows); X_k streams through LDS once in tiles of PS_LOO_TR = 64 draws, zero-padded the same way
@@ -24,8 +24,8 @@
 #define PS_LOO_TR 64    // draws per tile of X_k: one 16-row MFMA block per wave
 #define PS_LOO_NB 16    // rows of the A_k tile: the MFMA's 16 columns, NI of them in use
 // observations per workgroup at most (fewer observations, more workgroups per CU); a diagnostic build changes the cap
-// of one kernel, 1 <= n <= 16, with -DPL_NI_CAP=n (k_psis_loo_batched, both forms), -DPLS_NI_CAP=n (k_psis_loo_softmax_batched) or
-// -DPLN_NI_CAP=n (k_psis_loo_negbin_batched)
+// of one kernel, 1 <= n <= 16, with -DPL_NI_CAP=n (k_psis_loo_batched, both forms), -DPLS_NI_CAP=n (k_psis_loo_softmax_batched),
+// -DPLN_NI_CAP=n (k_psis_loo_negbin_batched) or -DPLO_NI_CAP=n (k_psis_loo_ordinal_batched)
 #ifndef PL_NI_CAP
 #define PL_NI_CAP 4
 #endif
@@ -35,7 +35,11 @@
 #ifndef PLN_NI_CAP
 #define PLN_NI_CAP 4
 #endif
+#ifndef PLO_NI_CAP
+#define PLO_NI_CAP 4
+#endif
 static_assert(PLN_NI_CAP >= 1 && PLN_NI_CAP <= PS_LOO_NB, "the tile's observations are columns of one 16-column MFMA block");
+static_assert(PLO_NI_CAP >= 1 && PLO_NI_CAP <= PS_LOO_NB, "the tile's observations are columns of one 16-column MFMA block");
 
 // doubles of the region the stage shares with a kernel's `tiles` doubles of MFMA tiles: the stage's arrays and its S2 indices, or
 // the tiles, whichever is larger

@@ -7,7 +7,8 @@ the same draws one step further for the GLM targets: the PSIS leave-one-out log 
 (csrc/gsmvi_psis_loo_batched.hip; Vehtari, Gelman, Gabry 2017; Magnusson, Andersen, Jonasson, Vehtari 2019), the number by which
 fitted models are compared; ``psis_loo_softmax_batched`` is the same for ``BatchedSoftmaxTarget``
 (csrc/gsmvi_psis_loo_softmax_batched.hip), ``psis_loo_negbin_batched`` for ``BatchedNegBinomialTarget``
-(csrc/gsmvi_psis_loo_negbin_batched.hip) and ``psis_loo_shared_batched`` for ``SharedDesignGLMTarget``, observation weights
+(csrc/gsmvi_psis_loo_negbin_batched.hip), ``psis_loo_ordinal_batched`` for ``BatchedOrdinalTarget``
+(csrc/gsmvi_psis_loo_ordinal_batched.hip) and ``psis_loo_shared_batched`` for ``SharedDesignGLMTarget``, observation weights
 honoured (the other form of the kernel in csrc/gsmvi_psis_loo_batched.hip)."""
 from dataclasses import dataclass
 
@@ -182,7 +183,7 @@ def _reusable(psis, K, D, eng, fn="psis_loo_batched"):
 
 def _loo_result(eng, target, psis, S, nlaunch, as_torch, elpd_i, lpd_i, khat, ess, info, loglik, weights=None, by_weights=False):
     """The ``LOOBatchedResult`` of the pointwise outputs of a leave-one-out launch (``psis_loo_batched``,
-    ``psis_loo_softmax_batched``, ``psis_loo_negbin_batched`` and ``psis_loo_shared_batched``): the per-problem summaries are torch
+    ``psis_loo_softmax_batched``, ``psis_loo_negbin_batched``, ``psis_loo_ordinal_batched`` and ``psis_loo_shared_batched``): the per-problem summaries are torch
     reductions under the mask of the valid rows (a stand-in engine's numpy arrays: on the host).  The valid rows are the first
     ``target.counts[k]``, or with ``by_weights`` (the shared design, which has no counts) the rows whose weight in ``weights``
     (K, N) is > 0, every row for None; the sums are then weighted: c_i = v_i elpd_i, p_loo = sum v_i (lpd_i - elpd_i).  Weights
@@ -222,7 +223,7 @@ def _loo_result(eng, target, psis, S, nlaunch, as_torch, elpd_i, lpd_i, khat, es
 
 
 def _loo_draws(fn, target, mean, cov, keys, num_draws, call, psis, engine):
-    """The argument checks and the problem-level run shared by the four leave-one-out functions: (eng, psis, nlaunch, X, logr, lw)"""
+    """The argument checks and the problem-level run shared by the five leave-one-out functions: (eng, psis, nlaunch, X, logr, lw)"""
     K, D = target.K, target.D
     if _shape(mean) != (K, D):
         raise ValueError(f"{fn}: mean must be (K, D) = {(K, D)} of the target, got {_shape(mean)}")
@@ -330,6 +331,39 @@ def psis_loo_negbin_batched(target, mean, cov, keys, num_draws=1024, *, call=0, 
     S = _shape(X)[1]
     elpd_i, lpd_i, khat, ess, info, loglik = eng.psis_loo_negbin_batched(
         X, logr, lw, target.A, target.y, offset=target.offset, counts=target.counts, pointwise_loglik=bool(pointwise_loglik))
+    return _loo_result(eng, target, psis, S, nlaunch, as_torch, elpd_i, lpd_i, khat, ess, info, loglik)
+
+
+def psis_loo_ordinal_batched(target, mean, cov, keys, num_draws=1024, *, call=0, psis=None, pointwise_loglik=False, as_torch=False,
+                             engine=None):
+    """PSIS leave-one-out of K fitted cumulative-logit (proportional odds) posteriors q_k = N(mean_k, cov_k) over (beta, delta):
+    returns a ``LOOBatchedResult``, the twin of ``psis_loo_batched`` for the likelihood whose draws carry the cutpoints.
+
+    ``target`` is the ``BatchedOrdinalTarget`` the posteriors were fitted to (its A, labels, number of classes, offset and counts
+    are the model; anything else raises TypeError); mean (K, D), D = P + C - 1, cov (K, D, D) and ``keys`` are ``psis_batched``'s.
+    Without ``psis`` it first runs ``psis_batched(target.lp, mean, cov, keys, num_draws, call=call, moments=False,
+    as_torch=True)`` (two launches and one call of ``target.lp``); with ``psis``, the result of such a call, its draws, ratios
+    and weights are reused (``num_draws`` and ``call`` are then not used).  Then one launch, gsmvi_psis_loo_ordinal_batched_f64:
+    the linear predictors of every draw on the fp64 MFMA, the cutpoints of every draw, the pointwise log likelihood l_si =
+    log P(y_i | eta_si, cut_s) through the target's own link (no two probabilities are subtracted), and per observation the PSIS
+    stage on the ratios logr_s - l_si and the two log-sum-exps (the definition is in include/gsmvi_hip.h).  l_si is the log of a
+    normalised categorical probability and no constant is added, so ``elpd_loo`` is on the scale of
+    ``psis_loo_softmax_batched`` on the same labels -- does proportional odds beat a multinomial logit? -- and of another
+    ordinal fit -- does a covariate earn its place?  No (K, N, S) block of log likelihoods is formed unless
+    ``pointwise_loglik`` asks for it (K * N * S * 8 bytes).  The per-problem sums are those of ``psis_loo_batched``.  mean and
+    cov are only read.
+    A mean that is not (K, D) of the target, a cov that is not (K, D, D), ``num_draws`` outside 5..4096, keys of another length
+    than K, or a ``psis`` that is not a ``PSISBatchedResult`` holding device tensors of the right shapes raise ValueError before
+    any device work."""
+    from .targets import BatchedOrdinalTarget
+    fn = "psis_loo_ordinal_batched"
+    if not isinstance(target, BatchedOrdinalTarget):
+        raise TypeError(f"{fn}: target must be a BatchedOrdinalTarget, got {type(target).__name__}")
+    eng, psis, nlaunch, X, logr, lw = _loo_draws(fn, target, mean, cov, keys, num_draws, call, psis, engine)
+    S = _shape(X)[1]
+    elpd_i, lpd_i, khat, ess, info, loglik = eng.psis_loo_ordinal_batched(
+        X, logr, lw, target.A, target.y, target.C, offset=target.offset, counts=target.counts,
+        pointwise_loglik=bool(pointwise_loglik))
     return _loo_result(eng, target, psis, S, nlaunch, as_torch, elpd_i, lpd_i, khat, ess, info, loglik)
 
 

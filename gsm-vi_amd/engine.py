@@ -1359,7 +1359,7 @@ class HipEngine:
 
     # ---- batched PSIS leave-one-out of K fitted GLM posteriors (csrc/gsmvi_psis_loo_batched.hip) ----------------------------------
     def _loo_call(self, name, head, K, N, S, D, X, logr, lw, pointwise_loglik):
-        """The end of the four ``psis_loo_*_batched``: the outputs, the launch of ``name`` on the entry's own leading arguments
+        """The end of the five ``psis_loo_*_batched``: the outputs, the launch of ``name`` on the entry's own leading arguments
         ``head`` followed by the nine that every entry ends with, and what they all return"""
         X, logr, lw = X.contiguous(), logr.contiguous(), lw.contiguous()
         elpd, lpd, khat, ess = self.empty(K, N), self.empty(K, N), self.empty(K, N), self.empty(K, N)
@@ -1429,6 +1429,30 @@ class HipEngine:
         head = (K, P, N, S, self._packed(A, (K, N, P), "A"), self._packed(y, (K, N), "y"), self._dp(offset, (K, N), "offset"),
                 self._ints(counts, K, "counts"))
         return self._loo_call("gsmvi_psis_loo_negbin_batched_f64", head, K, N, S, D, X, logr, lw, pointwise_loglik)
+
+    # ---- the same for K fitted cumulative-logit posteriors (csrc/gsmvi_psis_loo_ordinal_batched.hip) ---------------------------
+    def psis_loo_ordinal_tile(self, P, C, S):
+        """gsmvi_psis_loo_ordinal_tile: the observations one workgroup of ``psis_loo_ordinal_batched`` takes at (P, C, S); a pure
+        function, no GPU"""
+        return int(self.lib.gsmvi_psis_loo_ordinal_tile(int(P), int(C), int(S)))
+
+    def psis_loo_ordinal_batched(self, X, logr, lw, A, y, C, offset=None, counts=None, pointwise_loglik=False):
+        """PSIS leave-one-out of K fitted cumulative-logit posteriors from the draws X (K, S, P + C - 1) = (beta, delta) of q_k,
+        delta the C - 1 cutpoint parameters, and the problem-level ratios ``logr`` and smoothed weights ``lw`` (K, S) of
+        ``psis_batched`` on the same draws, one launch (gsmvi_psis_loo_ordinal_batched_f64; the definition is in
+        include/gsmvi_hip.h)  [no reference twin]: returns what ``psis_loo_batched`` returns, (elpd, lpd, khat, ess (K, N), info
+        (K, N) int32, loglik (K, N, S) or None).  The pointwise log likelihood is the log of the label's probability, already
+        normalised: elpd is on the scale of ``psis_loo_softmax_batched``.  ``A`` (K, N, P), ``y`` (K, N) int32 labels, ``C``,
+        ``offset`` and ``counts`` are ``ordinal_batched``'s."""
+        K, S, D = X.shape
+        N, P = A.shape[1], A.shape[2]
+        Cc = int(C)
+        if D != P + Cc - 1:
+            raise ValueError(f"X: expected P + C - 1 = {P + Cc - 1} columns (beta, then the C - 1 cutpoint parameters), got {D}")
+        self._any_ctx()
+        head = (K, P, Cc, N, S, self._packed(A, (K, N, P), "A"), self._ints(y, K * N, "y"), self._dp(offset, (K, N), "offset"),
+                self._ints(counts, K, "counts"))
+        return self._loo_call("gsmvi_psis_loo_ordinal_batched_f64", head, K, N, S, D, X, logr, lw, pointwise_loglik)
 
     # ---- the same for K fitted GLM posteriors on ONE design matrix, weighted (k_psis_loo_batched<FAM, true> of the same file) ---
     def psis_loo_shared_batched(self, X, logr, lw, A, y, family, offset=None, weights=None, noise_prec=1.0, pointwise_loglik=False):

@@ -22,8 +22,9 @@ multinomial logit regressions (C classes, C - 1 linear predictors per row), a la
                                                                                                  checks refuse it)
     BatchedNegBinomialTarget  counts y >= 0, a fitted size    gsmvi_negbin_batched_f64           no (not a BatchedGLMTarget: the Hessian
                               (x = (beta, log r))                                                has a 2 x 2 block per row)
-    BatchedOrdinalTarget      ordered labels in 0 .. C - 1,   gsmvi_ordinal_batched_f64          no (none exists yet for this family; the
-                              x = (beta, C - 1 cutpoints)                                        isinstance checks refuse it)
+    BatchedOrdinalTarget      ordered labels in 0 .. C - 1,   gsmvi_ordinal_batched_f64          laplace, predict: no (none exists yet for
+                              x = (beta, C - 1 cutpoints)                                        this family); loo: no method (TypeError from
+                                                                                                 the others): psis_loo_ordinal_batched
     BatchedSoftmaxTarget      integer labels in 0 .. C - 1    gsmvi_softmax_batched_f64          laplace_init_softmax_batched and
                                                                                                  neg_hessian; predict, loo: no (TypeError):
                                                                                                  predict_softmax_batched,
@@ -926,8 +927,10 @@ class BatchedOrdinalTarget:
     allocation with ``out``).  ``lp(x)``: (K, rows, D) -> (K, rows) values; a device tensor or numpy.  ``lp_and_score(x)``:
     (scores, values) from one launch.  ``cutpoints(x)``: (..., D) -> (..., C - 1), how a fit is read.  Attributes ``K, N, P, C, D``.
     Not a ``BatchedGLMTarget``: it has no ``neg_hessian``, ``predict`` or ``loo``, and ``laplace_init_batched``,
-    ``psis_loo_batched`` and their softmax and negative binomial namesakes refuse it (TypeError).  A Hessian and Laplace start, a
-    leave-one-out and a posterior predictive do not exist yet for this family."""
+    ``psis_loo_batched`` and their softmax and negative binomial namesakes refuse it (TypeError).  The leave-one-out of this
+    family is the free function ``psis_loo_ordinal_batched(target, mean, cov, keys, ...)``: l_si = log P(y_i) is normalised, so its
+    ``elpd_loo`` is on the scale of ``psis_loo_softmax_batched`` on the same labels.  A Hessian and Laplace start and a posterior
+    predictive do not exist yet for this family."""
 
     def __init__(self, A, y, num_classes, prior_precision=1.0, cut_precision=1.0, counts=None, offset=None, engine=None):
         if isinstance(num_classes, bool) or not isinstance(num_classes, (int, np.integer)) or num_classes < 2:

@@ -38,6 +38,7 @@
  *   GLMs (no reference twin)                                           ->  gsmvi_psis_loo_batched_f64, gsmvi_psis_loo_tile
  *   the same for K fitted multinomial logit regressions (no reference twin) -> gsmvi_psis_loo_softmax_batched_f64, gsmvi_psis_loo_softmax_tile
  *   the same for K fitted negative binomial regressions (no reference twin) -> gsmvi_psis_loo_negbin_batched_f64, gsmvi_psis_loo_negbin_tile
+ *   the same for K fitted cumulative-logit regressions (no reference twin) -> gsmvi_psis_loo_ordinal_batched_f64, gsmvi_psis_loo_ordinal_tile
  *   the same for K fitted GLMs on one design matrix, weighted (no reference twin) -> gsmvi_psis_loo_shared_batched_f64
  *   examples/example_gsm.py:34-35 the use of the fit for K fitted multinomial logit regressions: class probabilities and the held-out
  *   score from draws of q_k (no reference twin)                        ->  gsmvi_softmax_predict_batched_f64, gsmvi_softmax_predict_lds_bytes
@@ -316,12 +317,12 @@ int gsmvi_get_profile(gsmvi_ctx* ctx, float* ms, int n);
 #define GSMVI_PATH_BATCHED_BAM 0x4000u     /* k_bam_batched: the batched BaM entry points                           */
 #define GSMVI_PATH_BATCHED_KL 0x8000u      /* k_kl_batched: the batched KL monitor's entry points                  */
 #define GSMVI_PATH_BATCHED_ADVI 0x10000u   /* k_advi_batched / k_advi_cov_batched: the batched ADVI entry points   */
-#define GSMVI_PATH_BATCHED_TARGET 0x20000u /* k_logistic_batched: the batched non-Gaussian target's entry point; with GSMVI_PATH_BATCHED_LAPLACE in one call: k_laplace_shared_batched or k_negbin_laplace_batched; with GSMVI_PATH_BATCHED_LOO in one call: k_psis_loo_negbin_batched; with GSMVI_PATH_BATCHED_PREDICT in one call: k_negbin_predict_batched or k_glm_shared_predict_batched (all 32 bits are taken; no other call sets any of these pairs) */
+#define GSMVI_PATH_BATCHED_TARGET 0x20000u /* k_logistic_batched: the batched non-Gaussian target's entry point; with GSMVI_PATH_BATCHED_LAPLACE in one call: k_laplace_shared_batched or k_negbin_laplace_batched; with GSMVI_PATH_BATCHED_LOO in one call: k_psis_loo_negbin_batched or k_psis_loo_ordinal_batched; with GSMVI_PATH_BATCHED_PREDICT in one call: k_negbin_predict_batched or k_glm_shared_predict_batched (all 32 bits are taken; no other call sets any of these pairs) */
 #define GSMVI_PATH_BATCHED_LBFGS 0x40000u  /* k_lbfgs_step_batched / k_lbfgs_hess_inv_batched: the batched initialiser   */
 #define GSMVI_PATH_BATCHED_LAPLACE 0x80000u /* k_laplace_batched: the batched GLM Hessian and Newton step; with GSMVI_PATH_BATCHED_TARGET in one call: k_laplace_shared_batched, the shared-design Hessian and Newton step, or k_negbin_laplace_batched, the negative binomial one */
 #define GSMVI_PATH_BATCHED_PREDICT 0x100000u /* k_glm_predict_batched: the batched GLM posterior predictive; with GSMVI_PATH_BATCHED_SOFTMAX: k_softmax_predict_batched; with GSMVI_PATH_BATCHED_TARGET: k_negbin_predict_batched or k_glm_shared_predict_batched, the shared-design GLM predictive */
 #define GSMVI_PATH_BATCHED_PSIS 0x200000u /* k_psis_batched: the batched Pareto-smoothed importance diagnostic            */
-#define GSMVI_PATH_BATCHED_LOO 0x400000u /* k_psis_loo_batched: the batched PSIS leave-one-out; with GSMVI_PATH_BATCHED_SOFTMAX: k_psis_loo_softmax_batched; with GSMVI_PATH_BATCHED_TARGET: k_psis_loo_negbin_batched */
+#define GSMVI_PATH_BATCHED_LOO 0x400000u /* k_psis_loo_batched: the batched PSIS leave-one-out; with GSMVI_PATH_BATCHED_SOFTMAX: k_psis_loo_softmax_batched; with GSMVI_PATH_BATCHED_TARGET: k_psis_loo_negbin_batched or k_psis_loo_ordinal_batched */
 #define GSMVI_PATH_GSM_TWO_LAUNCH 0x800000u /* the dense GSM update ran as two launches (no k_gsm_scalars_fast, no records)          */
 #define GSMVI_PATH_BATCHED_SOFTMAX 0x1000000u /* k_softmax_batched: the batched multinomial logit target's entry point            */
 #define GSMVI_PATH_PANEL_CHUNK512 0x2000000u /* the two-launch product ran as two slabs of one 512-row chunk each (D = 1024, no explicit "panel_kc") */
@@ -1135,13 +1136,63 @@ int gsmvi_psis_loo_softmax_batched_f64(gsmvi_ctx* ctx, void* stream, int64_t K, 
  * else is read) are checked before the context is looked at (then a NULL ctx); every failure returns GSMVI_ERR_BAD_ARG before
  * anything is enqueued.  Inputs are only read; no context workspace is used; one capturable launch with no host synchronisation
  * and no atomics.  Sets GSMVI_PATH_BATCHED_LOO | GSMVI_PATH_BATCHED_TARGET: after a reset exactly that pair identifies this launch
- * (the GLM leave-one-out sets the first bit alone, the negative binomial score launch the second alone).
+ * or its ordinal sibling below (the GLM leave-one-out sets the first bit alone, the negative binomial score launch the second alone).
  */
 int gsmvi_psis_loo_negbin_tile(int P, int64_t S);
 int gsmvi_psis_loo_negbin_batched_f64(gsmvi_ctx* ctx, void* stream, int64_t K, int P, int64_t N, int64_t S, const double* A,
                                       const double* y, const double* offset, const int* counts_dev, const double* X,
                                       const double* logr, const double* lw, double* loglik, double* elpd, double* lpd,
                                       double* khat, double* ess, int* info);
+
+/*
+ * Batched ordinal PSIS leave-one-out: the same for K fitted posteriors of the cumulative-logit (proportional odds) model of
+ * gsmvi_ordinal_batched_f64, whose draws carry the C - 1 cutpoint parameters behind the coefficients.  The reference has no twin.
+ * One launch, one workgroup per (problem, tile of gsmvi_psis_loo_ordinal_tile(P, C, S) observations).
+ * Problem k has A_k (N x P, no intercept column; A is K x N x P), labels y_ki in 0 .. C - 1 (K x N ints; a label outside the range
+ * is clamped into it), an optional offset o_ki (K x N, or NULL), n_k = counts_dev[k] clamped to 0 .. N valid rows (N without
+ * counts_dev), and the draws x_s = (beta_s, delta_s) (s < S; X is K x S x D, D = P + C - 1 <= 64) of q_k.  logr (K x S) and lw
+ * (K x S) are what gsmvi_psis_batched_f64 writes for the same draws.  For a draw s and a valid row i < n_k:
+ *   cut_s0 = delta_s0,   cut_sj = cut_s,j-1 + e^{delta_sj}  (j = 1 .. C - 2, one chain in ascending j: the score launch's bits)
+ *   eta_si = a_i . beta_s + o_i
+ *   l_si   = t(eta_si, cut_s, e^{delta_s}, y_i) = log P(y_i | eta_si, cut_s)
+ * with t the per-row density term of gsmvi_ordinal_batched_f64: with a = cut_{y-1} - eta (y >= 1), b = cut_y - eta (y <= C - 2) and
+ * w = e^{delta_y} for an interior label, t = -[y <= C - 2] softplus(-b) - [y >= 1] softplus(a) + [interior] log(1 - e^{-w}); no two
+ * probabilities are subtracted and e^{+|z|} is never formed.  The categorical probability is normalised: no constant is added, and
+ * elpd is on the scale of gsmvi_psis_loo_softmax_batched_f64 on the same labels (does proportional odds beat a multinomial
+ * logit?).  No prior enters.
+ * A draw is flagged when one of its D entries is not finite, or when some e^{delta_j}, j >= 1, is not a positive normal number
+ * (|delta_j| above about 708: the row flag of gsmvi_ordinal_batched_f64), whether or not a row is labelled j; a flagged draw has
+ * l_si = NaN for every observation of the problem.  The flag is taken from the draw's entries, not from the product: nothing else
+ * produces a NaN.
+ * From there on the text is that of gsmvi_psis_loo_batched_f64 above, word for word:
+ *   rho_si = logr_s - l_si (one subtraction)
+ *   the PSIS stage, steps 1-8 of gsmvi_psis_weights_batched_f64 exactly (the (value, row) order of the sort and the -1 / -2
+ *   verdicts included), on rho_.i gives the normalised smoothed log weights w_si, khat[k, i], ess[k, i] and info[k, i]
+ *   elpd[k, i] = log sum_s exp(w_si + l_si)
+ *   lpd[k, i]  = log sum_s exp(lw_s + l_si)
+ * both as max + log sum exp(. - max), the maximum and the sum each a fixed tree over the S draws (a thread's entries in order, a
+ * butterfly within each wave, the waves in order; no atomics): the outputs are bit-identical from run to run.
+ * info[k, i] = -1 (a NaN or +inf among rho_.i -- a flagged draw, a NaN logr --, or every rho -inf): elpd, lpd, khat and ess of (k, i)
+ * are NaN.  info[k, i] = -2 (fewer than five tail entries): plain self-normalised weights and khat = +inf.  Rows i >= n_k are never
+ * loaded: elpd, lpd, khat and ess are NaN and info[k, i] = -3.  A verdict touches only its own (k, i).  loglik (K x N x S, or NULL)
+ * receives l_si (NaN for rows i >= n_k).  Outputs: elpd, lpd, khat, ess (K x N doubles each) and info (K x N ints), all required.
+ * gsmvi_psis_loo_ordinal_tile(P, C, S) is a pure function (no GPU): the observations per workgroup, the largest count of at most 4
+ * whose l_si (S doubles each) fit in the workgroup's 160 KB of LDS (20480 doubles) beside max(stage, tiles) doubles, where stage =
+ * S2 + S + 508 + S2 / 2 (S2 = S rounded up to a power of two, at least 8) and tiles = 80 (4 ceil(P / 4) + 1) + 64 ((C - 1) | 1) +
+ * 344 (at most 5736, at (P, C) = (61, 4): 4 for every legal shape at S <= 2048, 2 at S = 4096); 0 for P, C or S out of bounds.
+ * 2 <= C <= 64, 1 <= P <= 65 - C, 5 <= S <= 4096, N >= 1, K >= 1 with K ceil(N / gsmvi_psis_loo_ordinal_tile(P, C, S)) <= 2^24 - 1,
+ * K N S doubles addressable.  Shapes, NULL arrays and overlaps (loglik, elpd, lpd, khat, ess and info are the written arrays,
+ * everything else is read) are checked before the context is looked at (then a NULL ctx); every failure returns
+ * GSMVI_ERR_BAD_ARG before anything is enqueued.  Inputs are only read; no context workspace is used; one capturable launch with
+ * no host synchronisation and no atomics.  Sets GSMVI_PATH_BATCHED_LOO | GSMVI_PATH_BATCHED_TARGET, the pair of the negative
+ * binomial leave-one-out above (all 32 bits are taken): after a reset the pair says that one of the two ran (the GLM
+ * leave-one-out sets the first bit alone, the ordinal score launch the second alone).
+ */
+int gsmvi_psis_loo_ordinal_tile(int P, int C, int64_t S);
+int gsmvi_psis_loo_ordinal_batched_f64(gsmvi_ctx* ctx, void* stream, int64_t K, int P, int C, int64_t N, int64_t S, const double* A,
+                                       const int* y, const double* offset, const int* counts_dev, const double* X,
+                                       const double* logr, const double* lw, double* loglik, double* elpd, double* lpd,
+                                       double* khat, double* ess, int* info);
 
 /*
  * Shared-design PSIS leave-one-out: the same for K fitted posteriors of the model of gsmvi_glm_shared_batched_f64: K GLMs on ONE
