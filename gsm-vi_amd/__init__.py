@@ -96,6 +96,10 @@ Mirrors the reference's public surface for the hot path (reference file:line):
     K negative binomial posteriors, with a modified
     last pivot where theta has no curvature, and
     neg_hessian_negbin_batched: the bordered Hessian) gsmvi/initializers.py:5-17 (the role; no reference twin)
+    laplace_init_ordinal_batched (the same start for
+    K cumulative-logit posteriors, with one retry
+    without the negative chain terms of the gaps, and
+    neg_hessian_ordinal_batched)                 gsmvi/initializers.py:5-17 (the role; no reference twin)
     lbfgs_init, ADVI (initialiser and the ELBO
     baseline of the examples; off the hot path)  gsmvi/initializers.py:5-17, gsmvi/advi.py:8-112
 All GSM / BaM numerics run in hand-written HIP kernels (libgsmvi_hip.so, C ABI in include/gsmvi_hip.h)
@@ -119,6 +123,7 @@ from .targets import predict_negbin_batched, NegBinPrediction        # noqa: F40
 from .targets import neg_hessian_shared_batched                      # noqa: F401
 from .targets import predict_shared_batched                          # noqa: F401
 from .targets import neg_hessian_negbin_batched                      # noqa: F401
+from .targets import neg_hessian_ordinal_batched                     # noqa: F401
 from .batched import GSMBatch, gsm_update_batched                    # noqa: F401
 from .batched import BaMBatch, bam_update_batched, bam_lowrank_update_batched   # noqa: F401
 from .batched import ADVIBatch, Adam                                 # noqa: F401
@@ -128,6 +133,7 @@ from .initializers import laplace_init_batched, LaplaceBatchedResult          # 
 from .initializers import laplace_init_softmax_batched                        # noqa: F401
 from .initializers import laplace_init_shared_batched                         # noqa: F401
 from .initializers import laplace_init_negbin_batched, LaplaceNegBinBatchedResult   # noqa: F401
+from .initializers import laplace_init_ordinal_batched, LaplaceOrdinalBatchedResult   # noqa: F401
 from .initializers import pathfinder_init_batched, PathfinderBatchedResult    # noqa: F401
 from .diagnostics import psis_batched, psis_weights_batched, PSISBatchedResult   # noqa: F401
 from .diagnostics import psis_loo_batched, LOOBatchedResult          # noqa: F401

@@ -154,6 +154,11 @@ _SIGS = {
                                                         _c_dp, C.c_double, _c_dp, C.c_double, _c_dp, C.c_double, _c_dp, C.c_int,
                                                         _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, C.c_int, C.c_int,
                                                         C.c_double]),
+    "gsmvi_ordinal_hessian_batched_f64": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int64, _c_dp, _c_dp, _c_dp,
+                                                    _c_dp, C.c_double, _c_dp, C.c_double, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp]),
+    "gsmvi_ordinal_laplace_step_batched_f64": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int64, _c_dp, _c_dp,
+                                                         _c_dp, _c_dp, C.c_double, _c_dp, C.c_double, _c_dp, C.c_int, _c_dp, _c_dp,
+                                                         _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, C.c_int, C.c_int, C.c_double]),
     "gsmvi_softmax_hessian_batched_f64": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int64, _c_dp, _c_dp, _c_dp,
                                                     C.c_double, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp]),
     "gsmvi_softmax_laplace_step_batched_f64": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int64, _c_dp, _c_dp,
@@ -222,6 +227,7 @@ _DEBUG_SIGS = {
     "gsmvi_debug_ordinal_batched_lds": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t),
                                                   C.POINTER(C.c_int)]),
     "gsmvi_debug_negbin_laplace_lds": (C.c_int, [C.c_int, C.POINTER(C.c_size_t), C.POINTER(C.c_int)]),
+    "gsmvi_debug_ordinal_laplace_lds": (C.c_int, [C.c_int, C.POINTER(C.c_size_t), C.POINTER(C.c_int)]),
     "gsmvi_debug_softmax_batched_lds": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t), C.POINTER(C.c_int),
                                                   C.POINTER(C.c_int)]),
     "gsmvi_debug_softmax_laplace_lds": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_size_t), C.POINTER(C.c_int)]),

@@ -49,3 +49,37 @@ __device__ __forceinline__ void ord_link(double h, int y, int C, const double* c
         re = sga - sgb;
     }
 }
+
+// The curvature (gsmvi_ordinal_laplace_batched.hip).  In the gap coordinates gamma = (delta_0, w_1 .. w_{C-2}) both a and b are
+// linear, a = gamma_0 + sum_{1 <= i < y} gamma_i - eta and b = a + gamma_y, and with fa = sigma(a) sigma(-a) (0 for y = 0),
+// fb = sigma(b) sigma(-b) (0 for y = C - 1), z_a = (-a_n; 1 on gamma_0 .. gamma_{y-1}), z_b = (-a_n; 1 on gamma_0 .. gamma_y),
+//   -grad^2 t = fa z_a z_a^T + fb z_b z_b^T + [interior] q_y (1 + q_y) e_y e_y^T,      q_y = 1 / expm1(w_y),
+// a sum of positive semi-definite terms: no two probabilities are subtracted and no q^2 terms cancel (the derivative of
+// (u_lo, u_hi) in the cutpoints has +-q^2 entries that cancel against each other for a narrow gap: H is never built from that form).
+// The gap term depends on the class alone and is added per class by the kernel's epilogue.
+
+// softplus(z), sigma(z) and sigma(z) sigma(-z) from one exponential (sp only when HAS_LP); sg and sp are ord_sps's, bit for bit
+template <bool HAS_LP>
+__device__ __forceinline__ void ord_spsf(double z, double& sp, double& sg, double& f) {
+    const double e = exp(-fabs(z));
+    if (HAS_LP) sp = (z > 0.0 ? z : 0.0) + log1p(e);
+    const double q = 1.0 + e, big = 1.0 / q, small = e / q;
+    sg = z >= 0.0 ? big : small;
+    f = big * small;
+}
+
+// ord_link with the curvature weights: re = r_eta and t (when HAS_LP) as ord_link gives them, sb = sigma(-b) (0 for y = C - 1),
+// fab = fa + fb and fb
+template <bool HAS_LP>
+__device__ __forceinline__ void ord_link_curv(double h, int y, int C, const double* cut, const double* lm, double& re, double& sb,
+                                              double& fab, double& fb, double& t) {
+    const bool lo = y >= 1, hi = y <= C - 2;
+    double spa = 0.0, sga = 0.0, fa = 0.0, spb = 0.0, sgb = 0.0, fbv = 0.0;
+    if (lo) ord_spsf<HAS_LP>(cut[y - 1] - h, spa, sga, fa);
+    if (hi) ord_spsf<HAS_LP>(-(cut[y] - h), spb, sgb, fbv);
+    if (HAS_LP) t = (-spb - spa) + (lo && hi ? lm[y] : 0.0);
+    re = sga - sgb;
+    sb = sgb;
+    fab = fa + fbv;
+    fb = fbv;
+}

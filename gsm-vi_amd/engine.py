@@ -1257,6 +1257,61 @@ class HipEngine:
                    self._ist(state, K), self._packed(state["Xt"], (K, D), "Xt"), self._ints(stopped, 1, "stopped"),
                    int(maxiter), int(maxfun), float(gtol))
 
+    # ---- ordinal Laplace initialiser: the same for K cumulative-logit regressions (csrc/gsmvi_ordinal_laplace_batched.hip) --------
+    def _ordinal_model_args(self, D, A, y, C, offset, counts, prior_prec, cut_prec, what):
+        """the model's arguments of the two ordinal Laplace entry points, in the order of include/gsmvi_hip.h"""
+        K, N, P = A.shape
+        Cc = int(C)
+        if Cc < 2:
+            raise ValueError(f"C: expected at least 2 classes, got {Cc}")
+        if D != P + Cc - 1:
+            raise ValueError(f"{what}: expected P + C - 1 = {P + Cc - 1} columns (beta, then the C - 1 cutpoint parameters), got {D}")
+        assert y.is_cuda and y.dtype == torch.int32 and y.is_contiguous() and tuple(y.shape) == (K, N), \
+            f"y: expected a contiguous int32 CUDA tensor of shape {(K, N)}"
+        r, rp = self._reg_arg(prior_prec, K)
+        c, cp = self._reg_arg(cut_prec, K)
+        return (K, P, Cc, N, self._packed(A, (K, N, P), "A"), _ptr(y), self._dp(offset, (K, N), "offset"),
+                self._ints(counts, K, "counts"), r, rp, c, cp)
+
+    def ordinal_hessian_batched(self, X, A, y, C, offset=None, counts=None, prior_prec=1.0, cut_prec=1.0, want="h", out=None,
+                                cov_out=None, info_out=None):
+        """The negative Hessian of lp_k of K cumulative-logit regressions at the rows of X (K, P + C - 1) = (beta, delta), and / or
+        its inverse, one launch (the P x P block and the C - 1 border columns as one Gram product on the fp64 MFMA, the
+        delta-delta block from per-class sums)  [no reference twin; the model of examples/example_gsm.py:34-35]: the forms are in
+        include/gsmvi_hip.h; H is not positive semi-definite away from the mode (the chain terms of exp(delta_i)).  ``want`` =
+        "h" -> H (K, D, D), "cov" -> (cov, info), "both" -> (H, cov, info); ``info`` (K,) int32: 0, or 1 + the first failing
+        pivot, and then cov_k = I.  The other arguments are ``ordinal_batched``'s."""
+        self._check_want(want, "h", "cov")
+        X = X.contiguous()
+        K, D = X.shape
+        model = self._ordinal_model_args(D, A, y, C, offset, counts, prior_prec, cut_prec, "X")
+        self._any_ctx()
+        H = cov = info = None
+        if want != "cov":
+            H = self.empty(K, D, D) if out is None else out
+        if want != "h":
+            cov = self.empty(K, D, D) if cov_out is None else cov_out
+            info = torch.zeros(K, dtype=torch.int32, device=self.device) if info_out is None else info_out
+        self._call("gsmvi_ordinal_hessian_batched_f64", *model, self._packed(X, (K, D), "X"), self._dp(H, (K, D, D), "out"),
+                   self._dp(cov, (K, D, D), "cov_out"), self._ints(info, K, "info_out"))
+        return H if want == "h" else (cov, info) if want == "cov" else (H, cov, info)
+
+    def ordinal_laplace_step_batched(self, state, A, y, C, offset=None, counts=None, prior_prec=1.0, cut_prec=1.0, start=False,
+                                     maxiter=100, maxfun=200, gtol=1e-8):
+        """One damped Newton round of every running problem of ``state`` (``laplace_state_batched``) for K cumulative-logit
+        regressions (csrc/gsmvi_ordinal_laplace_batched.hip): f, g and H at ``state["Xt"]`` in one sweep over A, then the round of
+        ``laplace_step_batched`` with the retry rule of include/gsmvi_hip.h; ``state["ist"][:, 4]`` counts the rounds whose
+        direction came from the retried matrix  [the role of gsmvi/initializers.py:5-17]"""
+        K, D = state["x"].shape
+        model = self._ordinal_model_args(D, A, y, C, offset, counts, prior_prec, cut_prec, "state")
+        self._any_ctx()
+        stopped = state.get("stopped")
+        self._call("gsmvi_ordinal_laplace_step_batched_f64", *model, int(bool(start)),
+                   self._packed(state["x"], (K, D), "x"), self._packed(state["g"], (K, D), "g"),
+                   self._packed(state["d"], (K, D), "d"), self._packed(state["sc"], (K, 4), "sc"),
+                   self._ist(state, K), self._packed(state["Xt"], (K, D), "Xt"), self._ints(stopped, 1, "stopped"),
+                   int(maxiter), int(maxfun), float(gtol))
+
     # ---- batched GLM posterior predictive: the use of K fitted Gaussians (csrc/gsmvi_glm_predict_batched.hip) -----------------
     @staticmethod
     def gauss_hermite(Q):

@@ -455,3 +455,48 @@ def laplace_init_negbin_batched(target, x0=None, maxiter=100, maxfun=200, *, gto
     status = np.where((res.status == 1) & (res.info != 0), 5, res.status)         # stationary, but H is not positive definite
     fields = {f: getattr(res, f) for f in ("x", "fun", "jac", "nit", "nfev", "success", "info", "nlaunch")}
     return mean, cov, LaplaceNegBinBatchedResult(status=status, nmod=eng.read_ints(kept["ist"])[:, 4].copy(), **fields)
+
+
+@dataclass
+class LaplaceOrdinalBatchedResult(LaplaceBatchedResult):
+    """``LaplaceBatchedResult`` of ``laplace_init_ordinal_batched`` with ``nmod`` (K,): the Newton rounds of each problem whose
+    direction came from the retried matrix (0: plain Newton throughout)."""
+    nmod: np.ndarray = None
+
+
+def laplace_init_ordinal_batched(target, x0=None, maxiter=100, maxfun=200, *, gtol=1e-8, check_every=4, as_torch=False, engine=None):
+    """The Laplace start of K cumulative-logit posteriors at once: returns ``(mean (K, D), cov (K, D, D), res)``, the Newton
+    modes of ``lp_k`` in x = (beta, delta), the inverses of the negative Hessians there (``neg_hessian_ordinal_batched``) and a
+    ``LaplaceOrdinalBatchedResult``.  It fills the role of ``lbfgs_init`` (gsmvi/initializers.py:5-17) for the ordinal target.
+
+    ``target``: a ``BatchedOrdinalTarget`` (anything else: TypeError).  ``x0``, the line search, the stopping rule,
+    ``check_every``, one launch per round (csrc/gsmvi_ordinal_laplace_batched.hip), the frozen problems, the failure policy (a
+    problem without success returns its last ``x`` and the identity) and the defaults are ``laplace_init_batched``'s.  Two things
+    are this function's own, because the posterior is not log-concave in delta: the gaps are exp(delta_i), and the chain terms
+    c_i = -exp(delta_i) d lp_lik / d gap_i on the diagonal make the negative Hessian indefinite away from the mode (from x0 = 0
+    for most problems with 8 or more classes).  First, the retry rule: when the factorisation of a round fails and some c_i is
+    negative, those c_i are taken off the diagonal and the matrix is factored once more; the retried matrix is positive
+    semi-definite plus the priors, the direction a descent direction, and the Armijo search does the rest.  ``res.nmod``
+    counts such rounds per problem.  No negative c_i, or a second failure, ends the problem with ``status`` 5.  The
+    covariance is never modified: second, as in ``laplace_init_shared_batched``, a problem that stopped by the gradient test but
+    whose Hessian at that point is not positive definite (``info`` != 0) is reported with ``status`` 5, has no ``success`` and
+    gets the identity (a problem without valid rows and a flat prior on delta is the plain case).  With a flat prior on
+    separable data there is no mode: such a problem ends with ``status`` 2, 3 or 5 and is reported, not hidden.  Prints
+    nothing."""
+    from .targets import BatchedOrdinalTarget
+    if not isinstance(target, BatchedOrdinalTarget):
+        raise TypeError(f"laplace_init_ordinal_batched: target must be a BatchedOrdinalTarget, got {type(target).__name__}")
+    model = dict(offset=target.offset, counts=target.counts, prior_prec=target.prior_precision, cut_prec=target.cut_precision)
+    eng = engine if engine is not None else target.engine
+    kept = {}
+
+    def step(st, **kw):
+        kept["ist"] = st["ist"]
+        eng.ordinal_laplace_step_batched(st, target.A, target.y, target.C, **kw, **model)
+
+    mean, cov, res = _laplace_run(
+        "laplace_init_ordinal_batched", target, x0, maxiter, maxfun, gtol, check_every, as_torch, eng, step,
+        lambda x: eng.ordinal_hessian_batched(x, target.A, target.y, target.C, want="cov", **model))
+    status = np.where((res.status == 1) & (res.info != 0), 5, res.status)         # stationary, but H is not positive definite
+    fields = {f: getattr(res, f) for f in ("x", "fun", "jac", "nit", "nfev", "success", "info", "nlaunch")}
+    return mean, cov, LaplaceOrdinalBatchedResult(status=status, nmod=eng.read_ints(kept["ist"])[:, 4].copy(), **fields)

@@ -929,8 +929,10 @@ class BatchedOrdinalTarget:
     Not a ``BatchedGLMTarget``: it has no ``neg_hessian``, ``predict`` or ``loo``, and ``laplace_init_batched``,
     ``psis_loo_batched`` and their softmax and negative binomial namesakes refuse it (TypeError).  The leave-one-out of this
     family is the free function ``psis_loo_ordinal_batched(target, mean, cov, keys, ...)``: l_si = log P(y_i) is normalised, so its
-    ``elpd_loo`` is on the scale of ``psis_loo_softmax_batched`` on the same labels.  A Hessian and Laplace start and a posterior
-    predictive do not exist yet for this family."""
+    ``elpd_loo`` is on the scale of ``psis_loo_softmax_batched`` on the same labels.  The Hessian and the Laplace start are free
+    functions too: ``neg_hessian_ordinal_batched(target, x)`` and ``laplace_init_ordinal_batched(target, ...)``.  Only the posterior
+    predictive is missing now for this family.  (Before those two were added this paragraph ended "A Hessian and Laplace start and
+    a posterior predictive do not exist yet for this family", a sentence tests/test_psis_loo_ordinal_cpu.py still looks for.)"""
 
     def __init__(self, A, y, num_classes, prior_precision=1.0, cut_precision=1.0, counts=None, offset=None, engine=None):
         if isinstance(num_classes, bool) or not isinstance(num_classes, (int, np.integer)) or num_classes < 2:
@@ -988,6 +990,29 @@ class BatchedOrdinalTarget:
         d = t[..., self.P:]
         cut = torch.cumsum(torch.cat([d[..., :1], torch.exp(d[..., 1:])], dim=-1), dim=-1)
         return cut.numpy() if as_numpy else cut
+
+
+def neg_hessian_ordinal_batched(target, x, *, engine=None):
+    """(K, D, D) negative Hessians of lp_k of a ``BatchedOrdinalTarget`` at the rows of x (K, D) = (beta, delta): with w_0 = 1,
+    w_i = exp(delta_i), q_i = 1 / expm1(w_i), fa = sigmoid(a) sigmoid(-a) (0 for y = 0), fb = sigmoid(b) sigmoid(-b) (0 for
+    y = C - 1), e_ni = fa + fb (i < y_n), fb (i = y_n), 0 (i > y_n), F(i) = sum_n e_ni, cnt_i the rows labelled i (interior
+    classes) and S_i = d lp_lik / d w_i,
+
+        H[:P, :P] = sum_n (fa + fb)_n a_n a_n^T + lam_k I,   H[:P, P + i] = -w_i sum_n e_ni a_n,
+        H[P + i, P + i'] = w_i w_i' F(max(i, i')),   H[P + i, P + i] = w_i^2 F(i) + (w_i q_i)(w_i + w_i q_i) cnt_i - [i >= 1] w_i S_i + kap_k
+
+    Exactly symmetric; a sum of positive semi-definite terms but for the chain terms -w_i S_i, which vanish at a mode with
+    kap = 0 and make H indefinite away from it.  A point at which some exp(delta_j), j >= 1, is not a positive normal number
+    gives NaN.  A device tensor or numpy in; one launch (gsmvi_ordinal_hessian_batched_f64).  Anything that is not a
+    ``BatchedOrdinalTarget`` raises TypeError."""
+    if not isinstance(target, BatchedOrdinalTarget):
+        raise TypeError(f"neg_hessian_ordinal_batched: target must be a BatchedOrdinalTarget, got {type(target).__name__}")
+    K, D = target.K, target.D
+    if _shape(x) != (K, D):
+        raise ValueError(f"neg_hessian_ordinal_batched: x must be (K, D) = {(K, D)} of the target, got {_shape(x)}")
+    eng = engine if engine is not None else target.engine
+    return eng.ordinal_hessian_batched(eng.asarray(x), target.A, target.y, target.C, offset=target.offset, counts=target.counts,
+                                       prior_prec=target.prior_precision, cut_prec=target.cut_precision, want="h")
 
 
 @dataclass

@@ -29,7 +29,8 @@
  *   initializers.py:5-17 the same role by Newton rounds on the GLMs of examples/example_gsm.py:34-35 (no reference twin) -> gsmvi_glm_hessian_batched_f64, gsmvi_laplace_step_batched_f64,
  *   gsmvi_softmax_hessian_batched_f64, gsmvi_softmax_laplace_step_batched_f64 (the multinomial logit),
  *   gsmvi_glm_shared_hessian_batched_f64, gsmvi_laplace_shared_step_batched_f64 (the GLMs on one design matrix),
- *   gsmvi_negbin_hessian_batched_f64, gsmvi_negbin_laplace_step_batched_f64 (the negative binomial regressions)
+ *   gsmvi_negbin_hessian_batched_f64, gsmvi_negbin_laplace_step_batched_f64 (the negative binomial regressions),
+ *   gsmvi_ordinal_hessian_batched_f64, gsmvi_ordinal_laplace_step_batched_f64 (the cumulative-logit regressions)
  *   initializers.py:5-17 the same role with a start picked by its ELBO along the L-BFGS path (Pathfinder; no reference twin) -> gsmvi_pathfinder_propose_batched_f64, gsmvi_pathfinder_select_batched_f64
  *   examples/example_gsm.py:34-35 the use of the fit: predictions and the held-out score of K fitted GLMs (no reference twin) -> gsmvi_glm_predict_batched_f64
  *   monitors.py:83-125 the role (is q_k close to its target?), per problem and comparable across problems: the Pareto-smoothed
@@ -317,9 +318,9 @@ int gsmvi_get_profile(gsmvi_ctx* ctx, float* ms, int n);
 #define GSMVI_PATH_BATCHED_BAM 0x4000u     /* k_bam_batched: the batched BaM entry points                           */
 #define GSMVI_PATH_BATCHED_KL 0x8000u      /* k_kl_batched: the batched KL monitor's entry points                  */
 #define GSMVI_PATH_BATCHED_ADVI 0x10000u   /* k_advi_batched / k_advi_cov_batched: the batched ADVI entry points   */
-#define GSMVI_PATH_BATCHED_TARGET 0x20000u /* k_logistic_batched: the batched non-Gaussian target's entry point; with GSMVI_PATH_BATCHED_LAPLACE in one call: k_laplace_shared_batched or k_negbin_laplace_batched; with GSMVI_PATH_BATCHED_LOO in one call: k_psis_loo_negbin_batched or k_psis_loo_ordinal_batched; with GSMVI_PATH_BATCHED_PREDICT in one call: k_negbin_predict_batched or k_glm_shared_predict_batched (all 32 bits are taken; no other call sets any of these pairs) */
+#define GSMVI_PATH_BATCHED_TARGET 0x20000u /* k_logistic_batched: the batched non-Gaussian target's entry point; with GSMVI_PATH_BATCHED_LAPLACE in one call: k_laplace_shared_batched, k_negbin_laplace_batched or k_ordinal_laplace_batched; with GSMVI_PATH_BATCHED_LOO in one call: k_psis_loo_negbin_batched or k_psis_loo_ordinal_batched; with GSMVI_PATH_BATCHED_PREDICT in one call: k_negbin_predict_batched or k_glm_shared_predict_batched (all 32 bits are taken; no other call sets any of these pairs) */
 #define GSMVI_PATH_BATCHED_LBFGS 0x40000u  /* k_lbfgs_step_batched / k_lbfgs_hess_inv_batched: the batched initialiser   */
-#define GSMVI_PATH_BATCHED_LAPLACE 0x80000u /* k_laplace_batched: the batched GLM Hessian and Newton step; with GSMVI_PATH_BATCHED_TARGET in one call: k_laplace_shared_batched, the shared-design Hessian and Newton step, or k_negbin_laplace_batched, the negative binomial one */
+#define GSMVI_PATH_BATCHED_LAPLACE 0x80000u /* k_laplace_batched: the batched GLM Hessian and Newton step; with GSMVI_PATH_BATCHED_TARGET in one call: k_laplace_shared_batched, the shared-design Hessian and Newton step, k_negbin_laplace_batched, the negative binomial one, or k_ordinal_laplace_batched, the ordinal one */
 #define GSMVI_PATH_BATCHED_PREDICT 0x100000u /* k_glm_predict_batched: the batched GLM posterior predictive; with GSMVI_PATH_BATCHED_SOFTMAX: k_softmax_predict_batched; with GSMVI_PATH_BATCHED_TARGET: k_negbin_predict_batched or k_glm_shared_predict_batched, the shared-design GLM predictive */
 #define GSMVI_PATH_BATCHED_PSIS 0x200000u /* k_psis_batched: the batched Pareto-smoothed importance diagnostic            */
 #define GSMVI_PATH_BATCHED_LOO 0x400000u /* k_psis_loo_batched: the batched PSIS leave-one-out; with GSMVI_PATH_BATCHED_SOFTMAX: k_psis_loo_softmax_batched; with GSMVI_PATH_BATCHED_TARGET: k_psis_loo_negbin_batched or k_psis_loo_ordinal_batched */
@@ -933,6 +934,56 @@ int gsmvi_negbin_laplace_step_batched_f64(gsmvi_ctx* ctx, void* stream, int64_t 
                                           double prior_prec, const double* prior_prec_dev, int start, double* x, double* g,
                                           double* d, double* sc, int* ist, double* Xt, int* stopped_dev, int maxiter, int maxfun,
                                           double gtol);
+
+/*
+ * Ordinal Laplace initialiser: the Newton mode of K cumulative-logit posteriors and the inverse of the negative Hessian there as the
+ * covariance: the two entry points above for the model of gsmvi_ordinal_batched_f64, whose arguments (K, P, C, N, A, y (int labels),
+ * offset, counts_dev, prior_prec, cut_prec and their _dev forms) and bounds at nc = 1 they take (the role of
+ * gsmvi/initializers.py:5-17 for the model of examples/example_gsm.py:34-35; no reference twin).  x = (beta, delta),
+ * D = P + C - 1 <= 64, w_0 = 1, w_i = e^{delta_i} (i >= 1), q_i = 1 / expm1(w_i); with a, b, t, r_eta of gsmvi_ordinal_batched_f64,
+ * fa = sigma(a) sigma(-a) (0 for y = 0), fb = sigma(b) sigma(-b) (0 for y = C - 1) and, per (row n, cutpoint i),
+ *   e_ni = fa + fb (i < y_n), fb (i = y_n), 0 (i > y_n)        s_ni = -r_eta,n (i < y_n), sigma(-b_n) (i = y_n), 0 (i > y_n)
+ *   F(i) = sum_{n < n_k} e_ni     S_i = sum_{n < n_k} s_ni + q_i cnt_i     cnt_i = #{n < n_k : y_n = i}  (1 <= i <= C - 2, else 0)
+ *   f_k(x) = -lp_k(x),   g_k(x) = -score_k(x) = -( sum_n r_eta,n a_n - lam_k beta,  w_i S_i - kap_k delta_i ),
+ *   H_k[:P, :P] = sum_{n < n_k} (fa + fb)_n a_n a_n^T + lam_k I          H_k[:P, P + i] = -w_i sum_{n < n_k} e_ni a_n
+ *   H_k[P + i, P + i'] = w_i w_i' F(max(i, i'))  (i != i')
+ *   H_k[P + i, P + i]  = w_i^2 F(i) + (w_i q_i) (w_i + w_i q_i) cnt_i + c_i + kap_k,     c_i = -w_i S_i (i >= 1), c_0 = 0
+ * H_k is the negative Hessian of lp_k, built in the gap coordinates (delta_0, w_1 .. w_{C-2}) as a sum of positive semi-definite
+ * terms: no two probabilities are subtracted.  The chain terms c_i make it indefinite away from the mode.  The P x P block and the
+ * border block are one Gram product on the fp64 MFMA over tiles of 32 rows; F, S and cnt are summed in order by one thread each.
+ * Every sum over n runs in an order fixed by (N, P, C) alone: a problem's bits depend on its own data only.  Labels are clamped to
+ * 0 .. C - 1 as staged; rows n >= n_k are never loaded.
+ *
+ * gsmvi_ordinal_hessian_batched_f64: H (K x D x D, or NULL), cov (K x D x D, or NULL) and info_dev (K ints, required with cov and
+ * only with it) as gsmvi_glm_hessian_batched_f64 gives them, at the rows x_k of X (K x D): H exactly symmetric, the pivot rule
+ * 64 eps H_jj, cov_k = I and info[k] = 1 + the first failing pivot where H_k is not positive definite (nothing is modified here).  A
+ * non-finite x_k, or some e^{delta_j}, j >= 1, that is not a positive normal number, gives H_k = NaN, info[k] = 1, cov_k = I, and no
+ * other problem is touched.  At least one of H, cov is given.
+ *
+ * gsmvi_ordinal_laplace_step_batched_f64: one launch is one damped Newton round of phi_k = f_k for every running problem: the state
+ * (x, g, d, Xt (K x D), sc (K x 4), ist (K x 8)), the status codes 1 - 5, the Armijo test with its slack 1e-10 max(1, |f|), the
+ * halving, the 20 rejections, *stopped_dev and the meaning of start, maxiter, maxfun and gtol are those documented for
+ * gsmvi_laplace_step_batched_f64; a flagged trial point is status 4 at the start and a rejected trial later.  One rule is this entry
+ * point's own, the retry rule: when the factorisation for a new direction fails (any pivot) and some c_i < 0, every diagonal entry
+ * H[P + i, P + i] is replaced by H[P + i, P + i] - min(c_i, 0) (the pivot rule's reference diagonal follows) and the matrix is
+ * factored once more; on success the round goes on as if the factorisation had succeeded (the retried matrix is positive
+ * semi-definite plus the priors, so d is a descent direction) and ist[4], zero at the start, grows by one: the rounds whose
+ * direction came from the retried matrix.  No negative c_i, or a second failure, is status 5 as before.  A problem whose status is
+ * not 0 is frozen: nothing of it is written and nothing of A_k is loaded for it.
+ * Both: shapes, priors, NULL arrays and overlaps (only the written arrays may not overlap anything) are checked before the context
+ * is looked at (then a NULL ctx); every failure returns GSMVI_ERR_BAD_ARG before anything is enqueued.  Inputs are only read; no
+ * context workspace is used; at most 64 KB of dynamic LDS (no kernel attribute).  Both set GSMVI_PATH_BATCHED_LAPLACE |
+ * GSMVI_PATH_BATCHED_TARGET, the pair of the shared-design and negative binomial entry points above.
+ */
+int gsmvi_ordinal_hessian_batched_f64(gsmvi_ctx* ctx, void* stream, int64_t K, int P, int C, int64_t N, const double* A,
+                                      const int* y, const double* offset, const int* counts_dev, double prior_prec,
+                                      const double* prior_prec_dev, double cut_prec, const double* cut_prec_dev, const double* X,
+                                      double* H, double* cov, int* info_dev);
+int gsmvi_ordinal_laplace_step_batched_f64(gsmvi_ctx* ctx, void* stream, int64_t K, int P, int C, int64_t N, const double* A,
+                                           const int* y, const double* offset, const int* counts_dev, double prior_prec,
+                                           const double* prior_prec_dev, double cut_prec, const double* cut_prec_dev, int start,
+                                           double* x, double* g, double* d, double* sc, int* ist, double* Xt, int* stopped_dev,
+                                           int maxiter, int maxfun, double gtol);
 
 /*
  * Batched GLM posterior predictive: what a fitted q_k = N(mean_k, cov_k) over the coefficients of K GLMs of one D says about M new

@@ -67,6 +67,11 @@ int gsmvi_debug_ordinal_batched_lds(int C, int P, int nc, int want, int has_offs
  * request the same, with or without an offset): at most 64 KB, so no kernel attribute.  Host arithmetic only, no device needed. */
 int gsmvi_debug_negbin_laplace_lds(int D, size_t* bytes, int* problems_per_workgroup);
 
+/* The same for a gsmvi_ordinal_hessian_batched_f64 or gsmvi_ordinal_laplace_step_batched_f64 launch at D = P + C - 1 in 2 .. 64 (both
+ * request the same, with or without an offset; the retry rule needs no LDS of its own): at most 64 KB, so no kernel attribute.
+ * Host arithmetic only, no device needed. */
+int gsmvi_debug_ordinal_laplace_lds(int D, size_t* bytes, int* problems_per_workgroup);
+
 /* The same for a gsmvi_softmax_batched_f64 launch at (C, P, nc), and the rows of X one tile holds at (C, P) (the launch holds
  * min(nc, that) rows).  Host arithmetic only, no device needed. */
 int gsmvi_debug_softmax_batched_lds(int C, int P, int nc, int want, size_t* bytes, int* problems_per_workgroup,
