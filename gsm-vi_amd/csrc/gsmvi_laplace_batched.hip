@@ -37,37 +37,17 @@
 #include "gsmvi_common.h"
 #include "gsmvi_ctx.h"
 #include "gsmvi_batched.h"
+#include "gsmvi_laplace_stage.h"
 #include "gsmvi_glm_model.h"
 #include "../../include/gsmvi_hip.h"
 #include <cmath>
 #include <cstdint>
 
-#define LP_NSC 4       // doubles per problem in sc
-#define LP_NIS 8       // ints per problem in ist
 #define LP_AQ 8        // tile elements per thread: LB_TN D / NT <= 8 in both packings
-#define LP_PIVOT_REL 1.4210854715202004e-14   // 64 eps
-enum { LP_F = 0, LP_T = 1, LP_GD = 2 };
-enum { LP_STATUS = 0, LP_NIT = 1, LP_NFEV = 2, LP_NLS = 3 };
-enum { LP_HESS = 0, LP_STEP = 1 };
 
 struct lp_args {
     glm_model m;
-    int start;
-    // LP_HESS
-    const double* X;            // (K, D)
-    double* H;                  // (K, D, D) or null
-    double* cov;                // (K, D, D) or null
-    int* info;                  // (K), with cov
-    // LP_STEP: the state
-    double* x;                  // (K, D)
-    double* g;                  // (K, D)
-    double* d;                  // (K, D)
-    double* sc;                 // (K, 4)
-    int* ist;                   // (K, 8)
-    double* Xt;                 // (K, D)
-    int* stopped;               // (1) or null
-    int maxiter, maxfun;
-    double gtol;
+    lp_io io;
 };
 
 // LDS doubles per problem: the A tile (32 x (Dp + 1)), y, offset, r, w, t of its rows (32 each), x, g, pivots, the diagonal of H
@@ -75,44 +55,6 @@ struct lp_args {
 __host__ __device__ inline int lp_lds_doubles(int D) {
     const int Dp = glm_dp(D);
     return LB_TN * (Dp + 1) + 5 * LB_TN + 5 * Dp + 4 + D * (D | 1);
-}
-
-// gb_chol_lds with the relative pivot rule (dg: the diagonal of S before the factorisation): 0, or 1 + the first pivot that is
-// not finite or not > 64 eps dg[c].  `on` is uniform in the slot; every slot runs the D barriers.
-template <int NT, int MAXE>
-__device__ __forceinline__ int lp_chol_lds(bool on, int D, int l, int ld, double* S, double* pv, const double* dg) {
-    const int DD = D * D;
-    int info = 0;
-    for (int c = 0; c < D; ++c) {
-        if (on) {
-            const double acc_ = S[c * ld + c];
-            if (info == 0 && !(acc_ > LP_PIVOT_REL * dg[c] && acc_ < __builtin_huge_val())) info = c + 1;
-            const double piv = sqrt(acc_), inv = 1.0 / piv;
-            if (l == 0) pv[c] = piv;
-#pragma unroll
-            for (int q = 0; q < MAXE; ++q) {
-                const int e = l + q * NT;
-                if (e < DD) {
-                    const int i = e / D, j = e - i * D;
-                    if (i > c && j >= i) S[i * ld + j] -= (S[c * ld + i] * inv) * (S[c * ld + j] * inv);
-                }
-            }
-        }
-        __syncthreads();
-    }
-    if (on) {
-#pragma unroll
-        for (int q = 0; q < MAXE; ++q) {
-            const int e = l + q * NT;
-            if (e < DD) {
-                const int i = e / D, j = e - i * D;
-                if (j > i) S[i * ld + j] = S[i * ld + j] / pv[i];
-                else if (j == i) S[i * ld + j] = pv[i];
-            }
-        }
-    }
-    __syncthreads();
-    return info;
 }
 
 template <int NT, int FAM, int MODE>
@@ -143,13 +85,13 @@ __global__ __launch_bounds__(256) void k_laplace_batched(lp_args a) {
     double* Hs = cell + 4;                    // D x ldh
     const double qnan = __longlong_as_double(0x7ff8000000000000LL);
 
-    int* is = STEP ? a.ist + kk * LP_NIS : nullptr;
-    double* sc = STEP ? a.sc + kk * LP_NSC : nullptr;
+    int* is = STEP ? a.io.ist + kk * LP_NIS : nullptr;
+    double* sc = STEP ? a.io.sc + kk * LP_NSC : nullptr;
     int status = 0, nit = 0, nfev = 0, nls = 0;
     double f = 0.0, t = 0.0, gd = 0.0;
     bool live = valid;
     if (STEP) {
-        if (valid && !a.start) {
+        if (valid && !a.io.start) {
             status = is[LP_STATUS]; nit = is[LP_NIT]; nfev = is[LP_NFEV]; nls = is[LP_NLS];
             f = sc[LP_F]; t = sc[LP_T]; gd = sc[LP_GD];
         }
@@ -165,7 +107,7 @@ __global__ __launch_bounds__(256) void k_laplace_batched(lp_args a) {
     const double lam = pk.lam, tau = pk.tau;
     for (int e = l; e < LB_TN * lda; e += NT) As[e] = 0.0;          // the padding columns stay zero
     if (l < Dp) {
-        const double* xsrc = STEP ? a.Xt : a.X;
+        const double* xsrc = STEP ? a.io.Xt : a.io.X;
         xs[l] = live && l < D ? xsrc[kd + l] : 0.0;
     }
     if (l == 0) cell[0] = 0.0;
@@ -329,22 +271,22 @@ __global__ __launch_bounds__(256) void k_laplace_batched(lp_args a) {
         fin = !bad && gb_finite(ft) && __all(gb_finite(gtl));
         gmax = gb_wave_max(fabs(gtl));
         if (live) {
-            if (a.start)
-                need = fin && !(gmax <= a.gtol);
+            if (a.io.start)
+                need = fin && !(gmax <= a.io.gtol);
             else {
                 ok = fin && ft <= (f + (1e-4 * t) * gd) + 1e-10 * fmax(1.0, fabs(f));
-                need = ok && !(gmax <= a.gtol) && !(nit + 1 >= a.maxiter || nfev + 1 >= a.maxfun);
+                need = ok && !(gmax <= a.io.gtol) && !(nit + 1 >= a.io.maxiter || nfev + 1 >= a.io.maxfun);
             }
         }
     } else {
-        need = live && !bad && a.cov != nullptr;
-        if (live && a.H) {
+        need = live && !bad && a.io.cov != nullptr;
+        if (live && a.io.H) {
 #pragma unroll
             for (int q = 0; q < MAXE; ++q) {
                 const int e = l + q * NT;
                 if (e < DD) {
                     const int i = e / D, j = e - i * D;
-                    a.H[kk * DD + e] = bad ? qnan : (i <= j ? Hs[i * ldh + j] : Hs[j * ldh + i]);
+                    a.io.H[kk * DD + e] = bad ? qnan : (i <= j ? Hs[i * ldh + j] : Hs[j * ldh + i]);
                 }
             }
         }
@@ -356,7 +298,7 @@ __global__ __launch_bounds__(256) void k_laplace_batched(lp_args a) {
     int info = lp_chol_lds<NT, MAXE>(need, D, l, ldh, Hs, pv, dg);     // (its last barrier publishes R and the pivots)
 
     if (!STEP) {
-        if (!a.cov) return;                   // (uniform)
+        if (!a.io.cov) return;                   // (uniform)
         if (live && bad) info = 1;
         const bool inv = need && info == 0;
         if (inv && l < D) {                   // column l of R^{-1} into row l of the lower triangle, its diagonal into rd
@@ -384,12 +326,12 @@ __global__ __launch_bounds__(256) void k_laplace_batched(lp_args a) {
                             for (int c = j + 1; c < D; ++c) s += Hs[c * ldh + i] * Hs[c * ldh + j];
                         } else
                             s = i == j ? 1.0 : 0.0;                     // nothing is known: the identity
-                        a.cov[kk * DD + e] = s;
-                        a.cov[kk * DD + (size_t)j * D + i] = s;
+                        a.io.cov[kk * DD + e] = s;
+                        a.io.cov[kk * DD + (size_t)j * D + i] = s;
                     }
                 }
             }
-            if (l == 0) a.info[k] = info;
+            if (l == 0) a.io.info[k] = info;
         }
         return;
     }
@@ -398,7 +340,7 @@ __global__ __launch_bounds__(256) void k_laplace_batched(lp_args a) {
     const bool act = l < D;
     double xl = act ? xs[l] : 0.0, gl = gtl, dl = 0.0;
     bool newdir = false;
-    if (a.start) {
+    if (a.io.start) {
         nfev = 1;
         nit = 0;
         nls = 0;
@@ -406,7 +348,7 @@ __global__ __launch_bounds__(256) void k_laplace_batched(lp_args a) {
         t = 0.0;
         gd = 0.0;
         if (!fin) status = 4;
-        else if (gmax <= a.gtol) status = 1;
+        else if (gmax <= a.io.gtol) status = 1;
         else if (info != 0) status = 5;
         else newdir = true;
     } else {
@@ -415,19 +357,19 @@ __global__ __launch_bounds__(256) void k_laplace_batched(lp_args a) {
             t = 0.5 * t;
             nls += 1;
             if (nls > 20) status = 3;
-            else if (nfev >= a.maxfun) status = 2;
-            else if (act) a.Xt[kd + l] = a.x[kd + l] + t * a.d[kd + l];
+            else if (nfev >= a.io.maxfun) status = 2;
+            else if (act) a.io.Xt[kd + l] = a.io.x[kd + l] + t * a.io.d[kd + l];
             if (l == 0) {
                 sc[LP_T] = t;
                 is[LP_NLS] = nls; is[LP_NFEV] = nfev; is[LP_STATUS] = status;
-                if (status != 0 && a.stopped) atomicAdd(a.stopped, 1);
+                if (status != 0 && a.io.stopped) atomicAdd(a.io.stopped, 1);
             }
             return;
         }
         f = ft;
         nit += 1;
-        if (gmax <= a.gtol) status = 1;
-        else if (nit >= a.maxiter || nfev >= a.maxfun) status = 2;
+        if (gmax <= a.io.gtol) status = 1;
+        else if (nit >= a.io.maxiter || nfev >= a.io.maxfun) status = 2;
         else if (info != 0) status = 5;
         else newdir = true;
     }
@@ -449,35 +391,29 @@ __global__ __launch_bounds__(256) void k_laplace_batched(lp_args a) {
         nls = 0;
     }
     if (act) {
-        a.x[kd + l] = xl;
-        a.g[kd + l] = gl;
-        if (newdir || a.start) a.d[kd + l] = dl;
-        if (newdir) a.Xt[kd + l] = xl + dl;
+        a.io.x[kd + l] = xl;
+        a.io.g[kd + l] = gl;
+        if (newdir || a.io.start) a.io.d[kd + l] = dl;
+        if (newdir) a.io.Xt[kd + l] = xl + dl;
     }
     if (l == 0) {
         sc[LP_F] = f;
-        if (newdir || a.start) {
+        if (newdir || a.io.start) {
             sc[LP_T] = t;
             sc[LP_GD] = gd;
         }
-        if (a.start) sc[3] = 0.0;
+        if (a.io.start) sc[3] = 0.0;
         is[LP_STATUS] = status; is[LP_NIT] = nit; is[LP_NFEV] = nfev; is[LP_NLS] = nls;
-        if (a.start) { is[4] = 0; is[5] = 0; is[6] = 0; is[7] = 0; }
-        if (status != 0 && a.stopped) atomicAdd(a.stopped, 1);
+        if (a.io.start) { is[4] = 0; is[5] = 0; is[6] = 0; is[7] = 0; }
+        if (status != 0 && a.io.stopped) atomicAdd(a.io.stopped, 1);
     }
-}
-
-// dynamic LDS bytes of a launch at D: at most 52.5 KB, below the default limit of 64 KB, so no kernel attribute is needed
-static size_t lp_launch_lds(int D, int* ppw) {
-    *ppw = 256 / gb_nt(D);
-    return (size_t)*ppw * lp_lds_doubles(D) * sizeof(double);
 }
 
 template <int MODE>
 static int lp_go(gsmvi_ctx* ctx, void* stream, int family, const lp_args& a) {
     int ppw;
-    const size_t lds = lp_launch_lds(a.m.D, &ppw);
-    const unsigned grid = (unsigned)((a.m.K + ppw - 1) / ppw);
+    unsigned grid;
+    const size_t lds = lp_slot_launch(a.m.K, a.m.D, lp_lds_doubles(a.m.D), 0, &ppw, &grid);
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     glm_for_family(family, [&](auto fam) {
         if (ppw == 4)
@@ -494,18 +430,15 @@ int gsmvi_glm_hessian_batched_f64(gsmvi_ctx* ctx, void* stream, int64_t K, int D
                                   const double* y, const double* offset, const int* counts_dev, double noise_prec,
                                   const double* noise_prec_dev, double prior_prec, const double* prior_prec_dev, const double* X,
                                   double* H, double* cov, int* info_dev) {
-    const glm_model m = {K, N, D, A, y, offset, counts_dev, prior_prec, prior_prec_dev, noise_prec, noise_prec_dev};
-    if (int st = glm_check_model(__func__, m, family, "N", true)) return st;
-    GB_BAD(!A || !y || !X, "NULL array");
-    GB_BAD(!H && !cov, "give H or cov (or both)");
-    GB_BAD((cov != nullptr) != (info_dev != nullptr), "info_dev is required with cov and only with it");
-    const size_t nx = (size_t)K * D * 8, nh = nx * D;
-    if (int st = gb_check_overlaps(__func__, m, {{X, nx, "X", GB_RD}, {H, nh, "H", GB_WR}, {cov, nh, "cov", GB_WR},
-                                                 {info_dev, (size_t)K * 4, "info_dev", GB_WR}}))
-        return st;
+    const lp_args a = {{K, N, D, A, y, offset, counts_dev, prior_prec, prior_prec_dev, noise_prec, noise_prec_dev},
+                       lp_hess_io(X, H, cov, info_dev)};
+    if (int st = glm_check_model(__func__, a.m, family, "N", true)) return st;
+    GB_BAD(!A || !y, "NULL array");
+    if (int st = lp_check_hess(__func__, a.io)) return st;
+    gb_arr own[LP_HESS_ROWS];
+    lp_hess_rows(own, K, D, a.io);
+    if (int st = gb_check_overlaps(__func__, a.m, own)) return st;
     GB_BAD(!ctx, "ctx is NULL");
-    lp_args a = {};
-    a.m = m; a.X = X; a.H = H; a.cov = cov; a.info = info_dev;
     return lp_go<LP_HESS>(ctx, stream, family, a);
 }
 
@@ -514,21 +447,15 @@ int gsmvi_laplace_step_batched_f64(gsmvi_ctx* ctx, void* stream, int64_t K, int 
                                    const double* noise_prec_dev, double prior_prec, const double* prior_prec_dev, int start,
                                    double* x, double* g, double* d, double* sc, int* ist, double* Xt, int* stopped_dev, int maxiter,
                                    int maxfun, double gtol) {
-    const glm_model m = {K, N, D, A, y, offset, counts_dev, prior_prec, prior_prec_dev, noise_prec, noise_prec_dev};
-    if (int st = glm_check_model(__func__, m, family, "N", true)) return st;
-    GB_BAD(!A || !y || !x || !g || !d || !sc || !ist || !Xt, "NULL array");
-    GB_BAD(maxiter < 1 || maxfun < 2, "maxiter must be at least 1 and maxfun at least 2");
-    GB_BAD(!(gtol >= 0.0), "gtol must be >= 0");
-    const size_t nv = (size_t)K * D * 8;
-    if (int st = gb_check_overlaps(__func__, m, {{x, nv, "x", GB_WR}, {g, nv, "g", GB_WR}, {d, nv, "d", GB_WR},
-                                                 {sc, (size_t)K * LP_NSC * 8, "sc", GB_WR},
-                                                 {ist, (size_t)K * LP_NIS * 4, "ist", GB_WR}, {Xt, nv, "Xt", GB_WR},
-                                                 {stopped_dev, 4, "stopped_dev", GB_WR}}))
-        return st;
+    const lp_args a = {{K, N, D, A, y, offset, counts_dev, prior_prec, prior_prec_dev, noise_prec, noise_prec_dev},
+                       lp_step_io(start, x, g, d, sc, ist, Xt, stopped_dev, maxiter, maxfun, gtol)};
+    if (int st = glm_check_model(__func__, a.m, family, "N", true)) return st;
+    GB_BAD(!A || !y, "NULL array");
+    if (int st = lp_check_step(__func__, a.io)) return st;
+    gb_arr own[LP_STEP_ROWS];
+    lp_step_rows(own, K, D, a.io);
+    if (int st = gb_check_overlaps(__func__, a.m, own)) return st;
     GB_BAD(!ctx, "ctx is NULL");
-    lp_args a = {};
-    a.m = m; a.start = start != 0; a.x = x; a.g = g; a.d = d; a.sc = sc; a.ist = ist; a.Xt = Xt; a.stopped = stopped_dev;
-    a.maxiter = maxiter; a.maxfun = maxfun; a.gtol = gtol;
     return lp_go<LP_STEP>(ctx, stream, family, a);
 }
 

@@ -57,22 +57,7 @@ struct ls_args {
     const double* lam_dev;      // ... or (K) per-problem values on the device (null: `lam`)
     double tau;                 // gaussian family: the noise precision of every problem ...
     const double* tau_dev;      // ... or (K) per-problem values on the device (null: `tau`)
-    int start;
-    // LP_HESS
-    const double* X;            // (K, D)
-    double* H;                  // (K, D, D) or null
-    double* cov;                // (K, D, D) or null
-    int* info;                  // (K), with cov
-    // LP_STEP: the state
-    double* x;                  // (K, D)
-    double* g;                  // (K, D)
-    double* d;                  // (K, D)
-    double* sc;                 // (K, 4)
-    int* ist;                   // (K, 8)
-    double* Xt;                 // (K, D)
-    int* stopped;               // (1) or null
-    int maxiter, maxfun;
-    double gtol;
+    lp_io io;
 };
 
 // LDS doubles of the workgroup's one tile of A (32 x (Dp + 1)) and of one problem: y, o, v, v r, v w, v t of its rows (32 each), x,
@@ -110,12 +95,12 @@ __global__ __launch_bounds__(256) void k_laplace_shared_batched(ls_args a) {
     double* Hs = cell + 4;                    // D x ldh
     const double qnan = __longlong_as_double(0x7ff8000000000000LL);
 
-    int* is = STEP ? a.ist + kk * LP_NIS : nullptr;
-    double* sc = STEP ? a.sc + kk * LP_NSC : nullptr;
+    int* is = STEP ? a.io.ist + kk * LP_NIS : nullptr;
+    double* sc = STEP ? a.io.sc + kk * LP_NSC : nullptr;
     lp_run s;
     bool live = valid;
     if (STEP) {
-        lp_load_state(a, valid, is, sc, s);
+        lp_load_state(a.io, valid, is, sc, s);
         live = valid && s.status == 0;
         if (!__syncthreads_or(live)) return;  // every problem of the workgroup is frozen (uniform)
     }
@@ -130,7 +115,7 @@ __global__ __launch_bounds__(256) void k_laplace_shared_batched(ls_args a) {
     }
     for (int e = t; e < LS_TN * lda; e += 256) As[e] = 0.0;         // the padding columns stay zero
     if (l < Dp) {
-        const double* xsrc = STEP ? a.Xt : a.X;
+        const double* xsrc = STEP ? a.io.Xt : a.io.X;
         xs[l] = live && l < D ? xsrc[kd + l] : 0.0;
     }
     if (l == 0) cell[0] = 0.0;
@@ -293,35 +278,29 @@ __global__ __launch_bounds__(256) void k_laplace_shared_batched(ls_args a) {
     lp_verdict v;
     bool need;
     if (STEP) {
-        lp_step_test(a, live, bad, D, ln, gs, cell, s, v);
+        lp_step_test(a.io, live, bad, D, ln, gs, cell, s, v);
         need = v.need;
     } else {
-        need = live && !bad && a.cov != nullptr;
-        lp_write_h<NT, MAXE>(a, live, bad, kk, D, l, ldh, Hs);
+        need = live && !bad && a.io.cov != nullptr;
+        lp_write_h<NT, MAXE>(a.io, live, bad, kk, D, l, ldh, Hs);
     }
 
     const int info = lp_chol_lds<NT, MAXE>(need, D, l, ldh, Hs, pv, dg);     // (its last barrier publishes R and the pivots)
 
     if (!STEP) {
-        if (!a.cov) return;                   // (uniform)
-        lp_inverse_tail<NT, MAXE>(a, live, bad, need, info, k, kk, D, l, ldh, Hs, pv, rd);
+        if (!a.io.cov) return;                   // (uniform)
+        lp_inverse_tail<NT, MAXE>(a.io, live, bad, need, info, k, kk, D, l, ldh, Hs, pv, rd);
         return;
     }
     if (!live || l >= 64) return;             // the rest is the first wave's: component l of every vector in lane l
-    lp_step_tail(a, s, v, info, kd, D, l, ldh, Hs, pv, xs, sc, is);
-}
-
-// dynamic LDS bytes of a launch at D: at most 52.8 KB, below the default limit of 64 KB, so no kernel attribute is needed
-static size_t ls_launch_lds(int D, int* ppw) {
-    *ppw = 256 / gb_nt(D);
-    return ((size_t)ls_tile_doubles(D) + (size_t)*ppw * ls_slot_doubles(D)) * sizeof(double);
+    lp_step_tail(a.io, s, v, info, kd, D, l, ldh, Hs, pv, xs, sc, is);
 }
 
 template <int MODE>
 static int ls_go(gsmvi_ctx* ctx, void* stream, int family, const ls_args& a) {
     int ppw;
-    const size_t lds = ls_launch_lds(a.D, &ppw);
-    const unsigned grid = (unsigned)((a.K + ppw - 1) / ppw);
+    unsigned grid;
+    const size_t lds = lp_slot_launch(a.K, a.D, ls_slot_doubles(a.D), ls_tile_doubles(a.D), &ppw, &grid);
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     glm_for_family(family, [&](auto fam) {
         if (ppw == 4)
@@ -347,11 +326,8 @@ static int ls_check_overlaps(const char* fn, const glm_model& m, const double* w
     return gb_check_overlaps(fn, all, all + 6 + NOWN);
 }
 
-static ls_args ls_model_args(const glm_model& m, const double* weights) {
-    ls_args a = {};
-    a.K = m.K; a.N = m.N; a.D = m.D; a.A = m.A; a.y = m.y; a.offset = m.offset; a.w = weights; a.lam = m.lam; a.lam_dev = m.lam_dev;
-    a.tau = m.tau; a.tau_dev = m.tau_dev;
-    return a;
+static ls_args ls_args_of(const glm_model& m, const double* weights, const lp_io& io) {
+    return {m.K, m.N, m.D, m.A, m.y, m.offset, weights, m.lam, m.lam_dev, m.tau, m.tau_dev, io};
 }
 
 extern "C" {
@@ -364,16 +340,13 @@ int gsmvi_glm_shared_hessian_batched_f64(gsmvi_ctx* ctx, void* stream, int64_t K
                                          const double* X, double* H, double* cov, int* info_dev) {
     const glm_model m = {K, N, D, A, y, offset, nullptr, prior_prec, prior_prec_dev, noise_prec, noise_prec_dev};
     if (int st = glm_check_model(__func__, m, family, "N", true)) return st;
-    GB_BAD(!A || !y || !X, "NULL array");
-    GB_BAD(!H && !cov, "give H or cov (or both)");
-    GB_BAD((cov != nullptr) != (info_dev != nullptr), "info_dev is required with cov and only with it");
-    const size_t nx = (size_t)K * D * 8, nh = nx * D;
-    const gb_arr own[] = {{X, nx, "X", GB_RD}, {H, nh, "H", GB_WR}, {cov, nh, "cov", GB_WR},
-                          {info_dev, (size_t)K * 4, "info_dev", GB_WR}};
+    const ls_args a = ls_args_of(m, weights, lp_hess_io(X, H, cov, info_dev));
+    GB_BAD(!A || !y, "NULL array");
+    if (int st = lp_check_hess(__func__, a.io)) return st;
+    gb_arr own[LP_HESS_ROWS];
+    lp_hess_rows(own, K, D, a.io);
     if (int st = ls_check_overlaps(__func__, m, weights, own)) return st;
     GB_BAD(!ctx, "ctx is NULL");
-    ls_args a = ls_model_args(m, weights);
-    a.X = X; a.H = H; a.cov = cov; a.info = info_dev;
     return ls_go<LP_HESS>(ctx, stream, family, a);
 }
 
@@ -384,18 +357,13 @@ int gsmvi_laplace_shared_step_batched_f64(gsmvi_ctx* ctx, void* stream, int64_t 
                                           int maxiter, int maxfun, double gtol) {
     const glm_model m = {K, N, D, A, y, offset, nullptr, prior_prec, prior_prec_dev, noise_prec, noise_prec_dev};
     if (int st = glm_check_model(__func__, m, family, "N", true)) return st;
-    GB_BAD(!A || !y || !x || !g || !d || !sc || !ist || !Xt, "NULL array");
-    GB_BAD(maxiter < 1 || maxfun < 2, "maxiter must be at least 1 and maxfun at least 2");
-    GB_BAD(!(gtol >= 0.0), "gtol must be >= 0");
-    const size_t nv = (size_t)K * D * 8;
-    const gb_arr own[] = {{x, nv, "x", GB_WR}, {g, nv, "g", GB_WR}, {d, nv, "d", GB_WR},
-                          {sc, (size_t)K * LP_NSC * 8, "sc", GB_WR}, {ist, (size_t)K * LP_NIS * 4, "ist", GB_WR},
-                          {Xt, nv, "Xt", GB_WR}, {stopped_dev, 4, "stopped_dev", GB_WR}};
+    const ls_args a = ls_args_of(m, weights, lp_step_io(start, x, g, d, sc, ist, Xt, stopped_dev, maxiter, maxfun, gtol));
+    GB_BAD(!A || !y, "NULL array");
+    if (int st = lp_check_step(__func__, a.io)) return st;
+    gb_arr own[LP_STEP_ROWS];
+    lp_step_rows(own, K, D, a.io);
     if (int st = ls_check_overlaps(__func__, m, weights, own)) return st;
     GB_BAD(!ctx, "ctx is NULL");
-    ls_args a = ls_model_args(m, weights);
-    a.start = start != 0; a.x = x; a.g = g; a.d = d; a.sc = sc; a.ist = ist; a.Xt = Xt; a.stopped = stopped_dev;
-    a.maxiter = maxiter; a.maxfun = maxfun; a.gtol = gtol;
     return ls_go<LP_STEP>(ctx, stream, family, a);
 }
 

@@ -1,14 +1,20 @@
-// The tail of a batched Laplace kernel after its sweep over the data: the layout of the Newton state, the
-// in-LDS Cholesky factorisation with the relative pivot rule, the write of H, the inverse R^{-1} R^{-T}, and the accept / reject
-// decision, the stopping tests, the two triangular solves and the state update of one Newton round -- the state machine
-// documented for gsmvi_laplace_step_batched_f64 in include/gsmvi_hip.h.  Used by gsmvi_softmax_laplace_batched.hip,
-// gsmvi_laplace_shared_batched.hip and gsmvi_negbin_laplace_batched.hip (which puts its last-pivot rule between lp_chol_lds and
-// lp_step_tail).  The GLM kernel (gsmvi_laplace_batched.hip) keeps its own, older copy of the same statements inline, and a change to one copy belongs in the other: built from this header it gives the same bits, registers and occupancy,
-// and misses the speed bound of the A/B against the parent's library in 11 of 18 cases, its 64-thread step launch by 1 to 3 %
-// ("One copy of each initialiser stage"; profiles/batched/initialiser_stages_ab_parent.txt, second job).
+// What the five batched Laplace kernels share around their sweep over the data ("The Laplace stage block"):
+// lp_io, the state and output fields that end every kernel's argument block; the tail after the sweep -- the layout of the Newton
+// state, the in-LDS Cholesky factorisation with the relative pivot rule, the write of H, the inverse R^{-1} R^{-T}, and the accept /
+// reject decision, the stopping tests, the two triangular solves and the state update of one Newton round, the state machine
+// documented for gsmvi_laplace_step_batched_f64 in include/gsmvi_hip.h; and on the host what the ten entry points check and set
+// after their model's checks.  The tail serves gsmvi_softmax_laplace_batched.hip, gsmvi_laplace_shared_batched.hip,
+// gsmvi_negbin_laplace_batched.hip (its last-pivot rule stands between lp_chol_lds and lp_step_tail) and
+// gsmvi_ordinal_laplace_batched.hip (its retry rule, likewise).  The GLM kernel (gsmvi_laplace_batched.hip) takes lp_chol_lds from
+// here and keeps the statements of the rest of the tail inline, and a change to one copy belongs in the other: with its tail from
+// this header its listing is not the parent's, and in the A/B against the parent's library with the parent's own copy as the
+// noise base it passes 17 of 18 cases and misses one (Hessian at K = 8192, N = 1024, D = 64: +0.45 % against a margin of 0.37 %;
+// profiles/batched/laplace_glm_tail_ab_parent.txt), so by the rule of that pass the copy stays.
+// The sweep itself (block map, prefetched tile walk, row counts) stays inline in each kernel: as functions those pieces reach the
+// tile loop already unrolled, the compiler then lifts the put's eight LDS addresses out of the loop, and 14 of 90 cases of that A/B
+// missed and four instantiations took 2 to 6 more VGPRs (profiles/batched/laplace_sweep_ab_parent.txt).
 // Every function is for the problem of one workgroup slot: l is the thread's index in the slot (NT threads), Hs the slot's D x D
-// matrix in LDS with row stride ldh, and every slot of a workgroup calls the functions that hold a barrier.  `Args` is the
-// kernel's argument block with the fields start, H, cov, info, x, g, d, Xt, stopped, maxiter, maxfun, gtol.
+// matrix in LDS with row stride ldh, and every slot of a workgroup calls the functions that hold a barrier.
 #pragma once
 #include "gsmvi_batched.h"
 
@@ -18,6 +24,26 @@
 enum { LP_F = 0, LP_T = 1, LP_GD = 2 };
 enum { LP_STATUS = 0, LP_NIT = 1, LP_NFEV = 2, LP_NLS = 3 };
 enum { LP_HESS = 0, LP_STEP = 1 };
+
+// the state and the outputs of a launch: the last member of every kernel's argument block, after its model's fields
+struct lp_io {
+    int start;
+    // LP_HESS
+    const double* X;            // (K, D)
+    double* H;                  // (K, D, D) or null
+    double* cov;                // (K, D, D) or null
+    int* info;                  // (K), with cov
+    // LP_STEP: the state
+    double* x;                  // (K, D)
+    double* g;                  // (K, D)
+    double* d;                  // (K, D)
+    double* sc;                 // (K, 4)
+    int* ist;                   // (K, 8)
+    double* Xt;                 // (K, D)
+    int* stopped;               // (1) or null
+    int maxiter, maxfun;
+    double gtol;
+};
 
 // the running state of one problem (ist, sc of include/gsmvi_hip.h) in registers
 struct lp_run {
@@ -71,8 +97,7 @@ __device__ __forceinline__ int lp_chol_lds(bool on, int D, int l, int ld, double
 }
 
 // the state of problem kk at the start of a round (zeros at the first one)
-template <class Args>
-__device__ __forceinline__ void lp_load_state(const Args& a, bool valid, const int* is, const double* sc, lp_run& s) {
+__device__ __forceinline__ void lp_load_state(const lp_io& a, bool valid, const int* is, const double* sc, lp_run& s) {
     s.status = 0; s.nit = 0; s.nfev = 0; s.nls = 0;
     s.f = 0.0; s.t = 0.0; s.gd = 0.0;
     if (valid && !a.start) {
@@ -83,8 +108,7 @@ __device__ __forceinline__ void lp_load_state(const Args& a, bool valid, const i
 
 // LP_STEP: f = cell[1] and g = gs at the trial point (NaN when `bad`), the Armijo test against the state, and whether a new
 // direction will be needed
-template <class Args>
-__device__ __forceinline__ void lp_step_test(const Args& a, bool live, bool bad, int D, int ln, const double* gs, const double* cell,
+__device__ __forceinline__ void lp_step_test(const lp_io& a, bool live, bool bad, int D, int ln, const double* gs, const double* cell,
                                              const lp_run& s, lp_verdict& v) {
     const double qnan = __longlong_as_double(0x7ff8000000000000LL);
     v.ok = false;
@@ -105,8 +129,8 @@ __device__ __forceinline__ void lp_step_test(const Args& a, bool live, bool bad,
 
 // LP_HESS: H of a live problem from LDS (the upper triangle holds it; NaN when `bad`), then the barrier after which the
 // factorisation may overwrite it: entry (i, j), i > j, is read from another thread's cell (j, i)
-template <int NT, int MAXE, class Args>
-__device__ __forceinline__ void lp_write_h(const Args& a, bool live, bool bad, size_t kk, int D, int l, int ldh, const double* Hs) {
+template <int NT, int MAXE>
+__device__ __forceinline__ void lp_write_h(const lp_io& a, bool live, bool bad, size_t kk, int D, int l, int ldh, const double* Hs) {
     const double qnan = __longlong_as_double(0x7ff8000000000000LL);
     const int DD = D * D;
     if (live && a.H) {
@@ -124,8 +148,8 @@ __device__ __forceinline__ void lp_write_h(const Args& a, bool live, bool bad, s
 
 // LP_HESS after the factorisation: cov = R^{-1} R^{-T} (thread j back-substitutes column j of R^{-1} into row j of the free lower
 // triangle, then entry (i, j), i <= j, is one dot product, written to (i, j) and (j, i)), or the identity, and info
-template <int NT, int MAXE, class Args>
-__device__ __forceinline__ void lp_inverse_tail(const Args& a, bool live, bool bad, bool need, int info, long long k, size_t kk, int D,
+template <int NT, int MAXE>
+__device__ __forceinline__ void lp_inverse_tail(const lp_io& a, bool live, bool bad, bool need, int info, long long k, size_t kk, int D,
                                                 int l, int ldh, double* Hs, const double* pv, double* rd) {
     const int DD = D * D;
     if (live && bad) info = 1;
@@ -166,8 +190,7 @@ __device__ __forceinline__ void lp_inverse_tail(const Args& a, bool live, bool b
 
 // LP_STEP after the factorisation, for the first wave of a live slot (component l of every vector in lane l < 64): the state
 // machine of gsmvi_laplace_step_batched_f64 (include/gsmvi_hip.h), the Newton direction by two triangular solves, the writes
-template <class Args>
-__device__ __forceinline__ void lp_step_tail(const Args& a, lp_run s, const lp_verdict& v, int info, size_t kd, int D, int l, int ldh,
+__device__ __forceinline__ void lp_step_tail(const lp_io& a, lp_run s, const lp_verdict& v, int info, size_t kd, int D, int l, int ldh,
                                              const double* Hs, const double* pv, const double* xs, double* sc, int* is) {
     const bool act = l < D;
     double xl = act ? xs[l] : 0.0, gl = v.gtl, dl = 0.0;
@@ -239,4 +262,61 @@ __device__ __forceinline__ void lp_step_tail(const Args& a, lp_run s, const lp_v
         if (a.start) { is[4] = 0; is[5] = 0; is[6] = 0; is[7] = 0; }
         if (s.status != 0 && a.stopped) atomicAdd(a.stopped, 1);
     }
+}
+
+// ---- host side: what every entry point checks and sets after its model's checks ---------------------------------------------------
+// the Hessian entries' own conditions, in their order (the model's "NULL array" comes before, the overlap table and the context after)
+static inline int lp_check_hess(const char* fn, const lp_io& o) {
+    if (!o.X) return gb_bad(fn, "NULL array");
+    if (!o.H && !o.cov) return gb_bad(fn, "give H or cov (or both)");
+    if ((o.cov != nullptr) != (o.info != nullptr)) return gb_bad(fn, "info_dev is required with cov and only with it");
+    return GSMVI_OK;
+}
+
+// the step entries' own conditions
+static inline int lp_check_step(const char* fn, const lp_io& o) {
+    if (!o.x || !o.g || !o.d || !o.sc || !o.ist || !o.Xt) return gb_bad(fn, "NULL array");
+    if (o.maxiter < 1 || o.maxfun < 2) return gb_bad(fn, "maxiter must be at least 1 and maxfun at least 2");
+    if (!(o.gtol >= 0.0)) return gb_bad(fn, "gtol must be >= 0");
+    return GSMVI_OK;
+}
+
+static inline lp_io lp_hess_io(const double* X, double* H, double* cov, int* info_dev) {
+    lp_io o = {};
+    o.X = X; o.H = H; o.cov = cov; o.info = info_dev;
+    return o;
+}
+
+static inline lp_io lp_step_io(int start, double* x, double* g, double* d, double* sc, int* ist, double* Xt, int* stopped_dev,
+                               int maxiter, int maxfun, double gtol) {
+    lp_io o = {};
+    o.start = start != 0; o.x = x; o.g = g; o.d = d; o.sc = sc; o.ist = ist; o.Xt = Xt; o.stopped = stopped_dev;
+    o.maxiter = maxiter; o.maxfun = maxfun; o.gtol = gtol;
+    return o;
+}
+
+// the rows every entry's overlap table ends with, after its model's
+#define LP_HESS_ROWS 4
+#define LP_STEP_ROWS 7
+static inline void lp_hess_rows(gb_arr* rows, int64_t K, int D, const lp_io& o) {
+    const size_t nx = (size_t)K * D * 8, nh = nx * D;
+    const gb_arr own[LP_HESS_ROWS] = {{o.X, nx, "X", GB_RD}, {o.H, nh, "H", GB_WR}, {o.cov, nh, "cov", GB_WR},
+                                      {o.info, (size_t)K * 4, "info_dev", GB_WR}};
+    for (int i = 0; i < LP_HESS_ROWS; ++i) rows[i] = own[i];
+}
+
+static inline void lp_step_rows(gb_arr* rows, int64_t K, int D, const lp_io& o) {
+    const size_t nv = (size_t)K * D * 8;
+    const gb_arr own[LP_STEP_ROWS] = {{o.x, nv, "x", GB_WR}, {o.g, nv, "g", GB_WR}, {o.d, nv, "d", GB_WR},
+                                      {o.sc, (size_t)K * LP_NSC * 8, "sc", GB_WR}, {o.ist, (size_t)K * LP_NIS * 4, "ist", GB_WR},
+                                      {o.Xt, nv, "Xt", GB_WR}, {o.stopped, 4, "stopped_dev", GB_WR}};
+    for (int i = 0; i < LP_STEP_ROWS; ++i) rows[i] = own[i];
+}
+
+// a launch at D: the problems per workgroup, the grid, and the dynamic LDS in bytes of `slot` doubles per problem and `shared`
+// doubles per workgroup: at most 56.0 KB in every kernel, below the default limit of 64 KB, so no kernel attribute is needed
+static inline size_t lp_slot_launch(long long K, int D, int slot, int shared, int* ppw, unsigned* grid) {
+    *ppw = 256 / gb_nt(D);
+    *grid = (unsigned)((K + *ppw - 1) / *ppw);
+    return ((size_t)shared + (size_t)*ppw * slot) * sizeof(double);
 }

@@ -67,22 +67,7 @@ struct nl_args {
     const double* tm_dev;       // ... or (K)
     double tk;                  // the prior precision of theta ...
     const double* tk_dev;       // ... or (K)
-    int start;
-    // LP_HESS
-    const double* X;            // (K, D)
-    double* H;                  // (K, D, D) or null
-    double* cov;                // (K, D, D) or null
-    int* info;                  // (K), with cov
-    // LP_STEP: the state
-    double* x;                  // (K, D)
-    double* g;                  // (K, D)
-    double* d;                  // (K, D)
-    double* sc;                 // (K, 4)
-    int* ist;                   // (K, 8)
-    double* Xt;                 // (K, D)
-    int* stopped;               // (1) or null
-    int maxiter, maxfun;
-    double gtol;
+    lp_io io;
 };
 
 // LDS doubles per problem: the A tile (32 x (Dp + 1)), eight per-row arrays (32 each), x, g, pivots, the diagonal of H and of
@@ -122,12 +107,12 @@ __global__ __launch_bounds__(256) void k_negbin_laplace_batched(nl_args a) {
     double* cell = rd + Dp;                   // [1] f
     double* Hs = cell + 4;                    // D x ldh
 
-    int* is = STEP ? a.ist + kk * LP_NIS : nullptr;
-    double* sc = STEP ? a.sc + kk * LP_NSC : nullptr;
+    int* is = STEP ? a.io.ist + kk * LP_NIS : nullptr;
+    double* sc = STEP ? a.io.sc + kk * LP_NSC : nullptr;
     lp_run s;
     bool live = valid;
     if (STEP) {
-        lp_load_state(a, valid, is, sc, s);
+        lp_load_state(a.io, valid, is, sc, s);
         live = valid && s.status == 0;
         if (!__syncthreads_or(live)) return;  // every problem of the workgroup is frozen (uniform)
     }
@@ -152,7 +137,7 @@ __global__ __launch_bounds__(256) void k_negbin_laplace_batched(nl_args a) {
         As[e] = e - r * lda == P ? 1.0 : 0.0;
     }
     if (l < Dp) {
-        const double* xsrc = STEP ? a.Xt : a.X;
+        const double* xsrc = STEP ? a.io.Xt : a.io.X;
         xs[l] = live && l < D ? xsrc[kd + l] : 0.0;
     }
     __syncthreads();                          // the zeros are in place before any thread writes the first tile
@@ -317,18 +302,18 @@ __global__ __launch_bounds__(256) void k_negbin_laplace_batched(nl_args a) {
     lp_verdict v;
     bool need;
     if (STEP) {
-        lp_step_test(a, live, bad, D, ln, gs, cell, s, v);
+        lp_step_test(a.io, live, bad, D, ln, gs, cell, s, v);
         need = v.need;
     } else {
-        need = live && !bad && a.cov != nullptr;
-        lp_write_h<NT, MAXE>(a, live, bad, kk, D, l, ldh, Hs);
+        need = live && !bad && a.io.cov != nullptr;
+        lp_write_h<NT, MAXE>(a.io, live, bad, kk, D, l, ldh, Hs);
     }
 
     int info = lp_chol_lds<NT, MAXE>(need, D, l, ldh, Hs, pv, dg);     // (its last barrier publishes R and the pivots)
 
     if (!STEP) {
-        if (!a.cov) return;                   // (uniform)
-        lp_inverse_tail<NT, MAXE>(a, live, bad, need, info, k, kk, D, l, ldh, Hs, pv, rd);
+        if (!a.io.cov) return;                   // (uniform)
+        lp_inverse_tail<NT, MAXE>(a.io, live, bad, need, info, k, kk, D, l, ldh, Hs, pv, rd);
         return;
     }
     // the last-pivot rule (every thread of the slot forms s and m from the same cells of LDS, which nothing writes here)
@@ -356,21 +341,15 @@ __global__ __launch_bounds__(256) void k_negbin_laplace_batched(nl_args a) {
     __syncthreads();                          // (uniform: every slot of the workgroup is here)
     if (mod) info = 0;
     if (!live || l >= 64) return;             // the rest is the first wave's: component l of every vector in lane l
-    lp_step_tail(a, s, v, info, kd, D, l, ldh, Hs, pv, xs, sc, is);
-    if (mod && l == 0) is[NL_MOD] = (a.start ? 0 : is[NL_MOD]) + 1;    // (after the tail's own writes of the state words)
-}
-
-// dynamic LDS bytes of a launch at D: at most 53.3 KB, below the default limit of 64 KB, so no kernel attribute is needed
-static size_t nl_launch_lds(int D, int* ppw) {
-    *ppw = 256 / gb_nt(D);
-    return (size_t)*ppw * nl_lds_doubles(D) * sizeof(double);
+    lp_step_tail(a.io, s, v, info, kd, D, l, ldh, Hs, pv, xs, sc, is);
+    if (mod && l == 0) is[NL_MOD] = (a.io.start ? 0 : is[NL_MOD]) + 1;    // (after the tail's own writes of the state words)
 }
 
 template <int MODE>
 static int nl_go(gsmvi_ctx* ctx, void* stream, const nl_args& a) {
     int ppw;
-    const size_t lds = nl_launch_lds(a.P + 1, &ppw);
-    const unsigned grid = (unsigned)((a.K + ppw - 1) / ppw);
+    unsigned grid;
+    const size_t lds = lp_slot_launch(a.K, a.P + 1, nl_lds_doubles(a.P + 1), 0, &ppw, &grid);
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     if (ppw == 4) {
         if (a.offset) hipLaunchKernelGGL((k_negbin_laplace_batched<64, true, MODE>), dim3(grid), dim3(256), lds, st, a);
@@ -385,22 +364,35 @@ static int nl_go(gsmvi_ctx* ctx, void* stream, const nl_args& a) {
 
 static bool nl_fin(double v) { return v > -__builtin_huge_val() && v < __builtin_huge_val(); }
 
-// the model's checks of both entry points, those of gsmvi_negbin_batched_f64 at nc = 1, and its argument block
-static int nl_check_model(const char* fn, int64_t K, int P, int64_t N, const double* A, const double* y, double theta_mean,
-                          const double* theta_mean_dev, double theta_prec, const double* theta_prec_dev, double prior_prec,
-                          const double* prior_prec_dev) {
+static nl_args nl_args_of(int64_t K, int P, int64_t N, const double* A, const double* y, const double* offset, const int* counts_dev,
+                          double theta_mean, const double* theta_mean_dev, double theta_prec, const double* theta_prec_dev,
+                          double prior_prec, const double* prior_prec_dev, const lp_io& io) {
+    return {K, N, P, A, y, offset, counts_dev, prior_prec, prior_prec_dev, theta_mean, theta_mean_dev, theta_prec, theta_prec_dev, io};
+}
+
+// the model's checks of both entry points, those of gsmvi_negbin_batched_f64 at nc = 1
+static int nl_check_model(const char* fn, const nl_args& a) {
 #define NL_BAD(cond, msg) \
     if (cond) return gb_bad(fn, msg)
-    NL_BAD(P < 1 || P > GB_MAX_D - 1, "P must be in [1, 63] (D = P + 1 <= 64)");
-    if (int st = gb_check_shape(fn, K, P + 1, gb_ppw)) return st;
-    NL_BAD(N < 1, "N must be at least 1");
-    NL_BAD(N > (INT64_MAX / 8 / P) / K, "K N P is too large");
-    NL_BAD(!prior_prec_dev && !(prior_prec >= 0.0 && prior_prec < __builtin_huge_val()), "prior_prec must be finite and >= 0");
-    NL_BAD(!theta_mean_dev && !nl_fin(theta_mean), "theta_mean must be finite");
-    NL_BAD(!theta_prec_dev && !(theta_prec >= 0.0 && theta_prec < __builtin_huge_val()), "theta_prec must be finite and >= 0");
-    NL_BAD(!A || !y, "NULL array");
+    NL_BAD(a.P < 1 || a.P > GB_MAX_D - 1, "P must be in [1, 63] (D = P + 1 <= 64)");
+    if (int st = gb_check_shape(fn, a.K, a.P + 1, gb_ppw)) return st;
+    NL_BAD(a.N < 1, "N must be at least 1");
+    NL_BAD(a.N > (INT64_MAX / 8 / a.P) / a.K, "K N P is too large");
+    NL_BAD(!a.lam_dev && !(a.lam >= 0.0 && a.lam < __builtin_huge_val()), "prior_prec must be finite and >= 0");
+    NL_BAD(!a.tm_dev && !nl_fin(a.tm), "theta_mean must be finite");
+    NL_BAD(!a.tk_dev && !(a.tk >= 0.0 && a.tk < __builtin_huge_val()), "theta_prec must be finite and >= 0");
+    NL_BAD(!a.A || !a.y, "NULL array");
 #undef NL_BAD
     return GSMVI_OK;
+}
+
+// gb_check_overlaps over the model's eight read-only arrays followed by the entry point's own, which stand at own + 2
+template <size_t NOWN>
+static int nl_check_overlaps(const char* fn, const nl_args& a, gb_arr (&own)[NOWN]) {
+    const glm_model m = {a.K, a.N, a.P, a.A, a.y, a.offset, a.counts, a.lam, a.lam_dev, 1.0, nullptr};
+    own[0] = {a.tm_dev, (size_t)a.K * 8, "theta_mean_dev", GB_RD};
+    own[1] = {a.tk_dev, (size_t)a.K * 8, "theta_prec_dev", GB_RD};
+    return gb_check_overlaps(fn, m, own);
 }
 
 extern "C" {
@@ -409,27 +401,14 @@ int gsmvi_negbin_hessian_batched_f64(gsmvi_ctx* ctx, void* stream, int64_t K, in
                                      const double* offset, const int* counts_dev, double theta_mean, const double* theta_mean_dev,
                                      double theta_prec, const double* theta_prec_dev, double prior_prec,
                                      const double* prior_prec_dev, const double* X, double* H, double* cov, int* info_dev) {
-    if (int st = nl_check_model(__func__, K, P, N, A, y, theta_mean, theta_mean_dev, theta_prec, theta_prec_dev, prior_prec,
-                                prior_prec_dev))
-        return st;
-    GB_BAD(!X, "NULL array");
-    GB_BAD(!H && !cov, "give H or cov (or both)");
-    GB_BAD((cov != nullptr) != (info_dev != nullptr), "info_dev is required with cov and only with it");
-    const int D = P + 1;
-    const glm_model m = {K, N, P, A, y, offset, counts_dev, prior_prec, prior_prec_dev, 1.0, nullptr};
-    const size_t nx = (size_t)K * D * 8, nh = nx * D, nkb = (size_t)K * 8;
-    if (int st = gb_check_overlaps(__func__, m, {{theta_mean_dev, nkb, "theta_mean_dev", GB_RD},
-                                                 {theta_prec_dev, nkb, "theta_prec_dev", GB_RD},
-                                                 {X, nx, "X", GB_RD},
-                                                 {H, nh, "H", GB_WR},
-                                                 {cov, nh, "cov", GB_WR},
-                                                 {info_dev, (size_t)K * 4, "info_dev", GB_WR}}))
-        return st;
+    const nl_args a = nl_args_of(K, P, N, A, y, offset, counts_dev, theta_mean, theta_mean_dev, theta_prec, theta_prec_dev, prior_prec,
+                                 prior_prec_dev, lp_hess_io(X, H, cov, info_dev));
+    if (int st = nl_check_model(__func__, a)) return st;
+    if (int st = lp_check_hess(__func__, a.io)) return st;
+    gb_arr own[2 + LP_HESS_ROWS];
+    lp_hess_rows(own + 2, K, P + 1, a.io);
+    if (int st = nl_check_overlaps(__func__, a, own)) return st;
     GB_BAD(!ctx, "ctx is NULL");
-    nl_args a = {};
-    a.K = K; a.N = N; a.P = P; a.A = A; a.y = y; a.offset = offset; a.counts = counts_dev; a.lam = prior_prec;
-    a.lam_dev = prior_prec_dev; a.tm = theta_mean; a.tm_dev = theta_mean_dev; a.tk = theta_prec; a.tk_dev = theta_prec_dev;
-    a.X = X; a.H = H; a.cov = cov; a.info = info_dev;
     return nl_go<LP_HESS>(ctx, stream, a);
 }
 
@@ -439,38 +418,22 @@ int gsmvi_negbin_laplace_step_batched_f64(gsmvi_ctx* ctx, void* stream, int64_t 
                                           double prior_prec, const double* prior_prec_dev, int start, double* x, double* g,
                                           double* d, double* sc, int* ist, double* Xt, int* stopped_dev, int maxiter, int maxfun,
                                           double gtol) {
-    if (int st = nl_check_model(__func__, K, P, N, A, y, theta_mean, theta_mean_dev, theta_prec, theta_prec_dev, prior_prec,
-                                prior_prec_dev))
-        return st;
-    GB_BAD(!x || !g || !d || !sc || !ist || !Xt, "NULL array");
-    GB_BAD(maxiter < 1 || maxfun < 2, "maxiter must be at least 1 and maxfun at least 2");
-    GB_BAD(!(gtol >= 0.0), "gtol must be >= 0");
-    const int D = P + 1;
-    const glm_model m = {K, N, P, A, y, offset, counts_dev, prior_prec, prior_prec_dev, 1.0, nullptr};
-    const size_t nv = (size_t)K * D * 8, nkb = (size_t)K * 8;
-    if (int st = gb_check_overlaps(__func__, m, {{theta_mean_dev, nkb, "theta_mean_dev", GB_RD},
-                                                 {theta_prec_dev, nkb, "theta_prec_dev", GB_RD},
-                                                 {x, nv, "x", GB_WR},
-                                                 {g, nv, "g", GB_WR},
-                                                 {d, nv, "d", GB_WR},
-                                                 {sc, (size_t)K * LP_NSC * 8, "sc", GB_WR},
-                                                 {ist, (size_t)K * LP_NIS * 4, "ist", GB_WR},
-                                                 {Xt, nv, "Xt", GB_WR},
-                                                 {stopped_dev, 4, "stopped_dev", GB_WR}}))
-        return st;
+    const nl_args a = nl_args_of(K, P, N, A, y, offset, counts_dev, theta_mean, theta_mean_dev, theta_prec, theta_prec_dev, prior_prec,
+                                 prior_prec_dev, lp_step_io(start, x, g, d, sc, ist, Xt, stopped_dev, maxiter, maxfun, gtol));
+    if (int st = nl_check_model(__func__, a)) return st;
+    if (int st = lp_check_step(__func__, a.io)) return st;
+    gb_arr own[2 + LP_STEP_ROWS];
+    lp_step_rows(own + 2, K, P + 1, a.io);
+    if (int st = nl_check_overlaps(__func__, a, own)) return st;
     GB_BAD(!ctx, "ctx is NULL");
-    nl_args a = {};
-    a.K = K; a.N = N; a.P = P; a.A = A; a.y = y; a.offset = offset; a.counts = counts_dev; a.lam = prior_prec;
-    a.lam_dev = prior_prec_dev; a.tm = theta_mean; a.tm_dev = theta_mean_dev; a.tk = theta_prec; a.tk_dev = theta_prec_dev;
-    a.start = start != 0; a.x = x; a.g = g; a.d = d; a.sc = sc; a.ist = ist; a.Xt = Xt; a.stopped = stopped_dev;
-    a.maxiter = maxiter; a.maxfun = maxfun; a.gtol = gtol;
     return nl_go<LP_STEP>(ctx, stream, a);
 }
 
 // include/gsmvi_hip_debug.h: what a launch of either entry point at D = P + 1 requests (exported by the debug library only)
 int gsmvi_debug_negbin_laplace_lds(int D, size_t* bytes, int* problems_per_workgroup) {
     GB_BAD(D < 2 || D > GB_MAX_D || !bytes || !problems_per_workgroup, "bad shape or NULL output");
-    *bytes = nl_launch_lds(D, problems_per_workgroup);
+    unsigned grid;
+    *bytes = lp_slot_launch(1, D, nl_lds_doubles(D), 0, problems_per_workgroup, &grid);
     return GSMVI_OK;
 }
 

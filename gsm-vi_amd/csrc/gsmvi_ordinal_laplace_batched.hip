@@ -71,22 +71,7 @@ struct ol_args {
     const double* lam_dev;      // ... or (K) per-problem values on the device (null: `lam`)
     double kap;                 // the prior precision of delta ...
     const double* kap_dev;      // ... or (K)
-    int start;
-    // LP_HESS
-    const double* X;            // (K, D)
-    double* H;                  // (K, D, D) or null
-    double* cov;                // (K, D, D) or null
-    int* info;                  // (K), with cov
-    // LP_STEP: the state
-    double* x;                  // (K, D)
-    double* g;                  // (K, D)
-    double* d;                  // (K, D)
-    double* sc;                 // (K, 4)
-    int* ist;                   // (K, 8)
-    double* Xt;                 // (K, D)
-    int* stopped;               // (1) or null
-    int maxiter, maxfun;
-    double gtol;
+    lp_io io;
 };
 
 // LDS doubles per problem: the A tile (32 x (Dp + 1)), seven per-row arrays (32 each), eleven vectors (Dp each: x, g, pivots, the
@@ -132,12 +117,12 @@ __global__ __launch_bounds__(256) void k_ordinal_laplace_batched(ol_args a) {
     double* cell = cv + Dp;                   // [1] f
     double* Hs = cell + 4;                    // D x ldh
 
-    int* is = STEP ? a.ist + kk * LP_NIS : nullptr;
-    double* sc = STEP ? a.sc + kk * LP_NSC : nullptr;
+    int* is = STEP ? a.io.ist + kk * LP_NIS : nullptr;
+    double* sc = STEP ? a.io.sc + kk * LP_NSC : nullptr;
     lp_run s;
     bool live = valid;
     if (STEP) {
-        lp_load_state(a, valid, is, sc, s);
+        lp_load_state(a.io, valid, is, sc, s);
         live = valid && s.status == 0;
         if (!__syncthreads_or(live)) return;  // every problem of the workgroup is frozen (uniform)
     }
@@ -158,7 +143,7 @@ __global__ __launch_bounds__(256) void k_ordinal_laplace_batched(ol_args a) {
     }
     for (int e = l; e < LB_TN * lda; e += NT) As[e] = 0.0;          // the padding columns (from P on) stay zero
     if (l < Dp) {
-        const double* xsrc = STEP ? a.Xt : a.X;
+        const double* xsrc = STEP ? a.io.Xt : a.io.X;
         const double xv = live && l < D ? xsrc[kd + l] : 0.0;
         xs[l] = xv;
         // the gap terms of cutpoint parameter i = l - P (a NaN delta gives a NaN w: flagged below)
@@ -383,7 +368,7 @@ __global__ __launch_bounds__(256) void k_ordinal_laplace_batched(ol_args a) {
     lp_verdict v;
     bool need;
     if (STEP) {
-        lp_step_test(a, live, bad, D, ln, gs, cell, s, v);
+        lp_step_test(a.io, live, bad, D, ln, gs, cell, s, v);
         need = v.need;
         if (need) {                           // the strict upper triangle into the free lower one: what a retry restores
 #pragma unroll
@@ -396,15 +381,15 @@ __global__ __launch_bounds__(256) void k_ordinal_laplace_batched(ol_args a) {
             }
         }
     } else {
-        need = live && !bad && a.cov != nullptr;
-        lp_write_h<NT, MAXE>(a, live, bad, kk, D, l, ldh, Hs);
+        need = live && !bad && a.io.cov != nullptr;
+        lp_write_h<NT, MAXE>(a.io, live, bad, kk, D, l, ldh, Hs);
     }
 
     int info = lp_chol_lds<NT, MAXE>(need, D, l, ldh, Hs, pv, dg);     // (its last barrier publishes R and the pivots)
 
     if (!STEP) {
-        if (!a.cov) return;                   // (uniform)
-        lp_inverse_tail<NT, MAXE>(a, live, bad, need, info, k, kk, D, l, ldh, Hs, pv, rd);
+        if (!a.io.cov) return;                   // (uniform)
+        lp_inverse_tail<NT, MAXE>(a.io, live, bad, need, info, k, kk, D, l, ldh, Hs, pv, rd);
         return;
     }
     // the retry rule (every thread of the slot reads the same cells of LDS, so `retry` is uniform in it)
@@ -435,21 +420,16 @@ __global__ __launch_bounds__(256) void k_ordinal_laplace_batched(ol_args a) {
         }
     }
     if (!live || l >= 64) return;             // the rest is the first wave's: component l of every vector in lane l
-    lp_step_tail(a, s, v, info, kd, D, l, ldh, Hs, pv, xs, sc, is);
-    if (retry && l == 0) is[OL_MOD] = (a.start ? 0 : is[OL_MOD]) + 1;  // (after the tail's own writes of the state words)
-}
-
-// dynamic LDS bytes of a launch at D: at most 56.0 KB, below the default limit of 64 KB, so no kernel attribute is needed
-static size_t ol_launch_lds(int D, int* ppw) {
-    *ppw = 256 / gb_nt(D);
-    return (size_t)*ppw * ol_lds_doubles(D) * sizeof(double);
+    lp_step_tail(a.io, s, v, info, kd, D, l, ldh, Hs, pv, xs, sc, is);
+    if (retry && l == 0) is[OL_MOD] = (a.io.start ? 0 : is[OL_MOD]) + 1;  // (after the tail's own writes of the state words)
 }
 
 template <int MODE>
 static int ol_go(gsmvi_ctx* ctx, void* stream, const ol_args& a) {
     int ppw;
-    const size_t lds = ol_launch_lds(a.P + a.C - 1, &ppw);
-    const unsigned grid = (unsigned)((a.K + ppw - 1) / ppw);
+    unsigned grid;
+    const int D = a.P + a.C - 1;
+    const size_t lds = lp_slot_launch(a.K, D, ol_lds_doubles(D), 0, &ppw, &grid);
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     if (ppw == 4) {
         if (a.offset) hipLaunchKernelGGL((k_ordinal_laplace_batched<64, true, MODE>), dim3(grid), dim3(256), lds, st, a);
@@ -463,30 +443,37 @@ static int ol_go(gsmvi_ctx* ctx, void* stream, const ol_args& a) {
     return gb_launched(ctx, GSMVI_PATH_BATCHED_LAPLACE | GSMVI_PATH_BATCHED_TARGET, "k_ordinal_laplace_batched");
 }
 
+static ol_args ol_args_of(int64_t K, int P, int C, int64_t N, const double* A, const int* y, const double* offset,
+                          const int* counts_dev, double prior_prec, const double* prior_prec_dev, double cut_prec,
+                          const double* cut_prec_dev, const lp_io& io) {
+    return {K, N, P, C, A, y, offset, counts_dev, prior_prec, prior_prec_dev, cut_prec, cut_prec_dev, io};
+}
+
 // the model's checks of both entry points, those of gsmvi_ordinal_batched_f64 at nc = 1
-static int ol_check_model(const char* fn, int64_t K, int P, int C, int64_t N, const double* A, const int* y, double prior_prec,
-                          const double* prior_prec_dev, double cut_prec, const double* cut_prec_dev) {
+static int ol_check_model(const char* fn, const ol_args& a) {
 #define OL_BAD(cond, msg) \
     if (cond) return gb_bad(fn, msg)
-    OL_BAD(C < 2 || C > GB_MAX_D, "C must be in [2, 64]");
-    OL_BAD(P < 1 || P > GB_MAX_D - (C - 1), "P must be in [1, 65 - C] (D = P + C - 1 <= 64)");
-    if (int st = gb_check_shape(fn, K, P + C - 1, gb_ppw)) return st;
-    OL_BAD(N < 1, "N must be at least 1");
-    OL_BAD(N > (INT64_MAX / 8 / P) / K, "K N P is too large");
-    OL_BAD(!prior_prec_dev && !(prior_prec >= 0.0 && prior_prec < __builtin_huge_val()), "prior_prec must be finite and >= 0");
-    OL_BAD(!cut_prec_dev && !(cut_prec >= 0.0 && cut_prec < __builtin_huge_val()), "cut_prec must be finite and >= 0");
-    OL_BAD(!A || !y, "NULL array");
+    OL_BAD(a.C < 2 || a.C > GB_MAX_D, "C must be in [2, 64]");
+    OL_BAD(a.P < 1 || a.P > GB_MAX_D - (a.C - 1), "P must be in [1, 65 - C] (D = P + C - 1 <= 64)");
+    if (int st = gb_check_shape(fn, a.K, a.P + a.C - 1, gb_ppw)) return st;
+    OL_BAD(a.N < 1, "N must be at least 1");
+    OL_BAD(a.N > (INT64_MAX / 8 / a.P) / a.K, "K N P is too large");
+    OL_BAD(!a.lam_dev && !(a.lam >= 0.0 && a.lam < __builtin_huge_val()), "prior_prec must be finite and >= 0");
+    OL_BAD(!a.kap_dev && !(a.kap >= 0.0 && a.kap < __builtin_huge_val()), "cut_prec must be finite and >= 0");
+    OL_BAD(!a.A || !a.y, "NULL array");
 #undef OL_BAD
     return GSMVI_OK;
 }
 
-static ol_args ol_model_args(int64_t K, int P, int C, int64_t N, const double* A, const int* y, const double* offset,
-                             const int* counts_dev, double prior_prec, const double* prior_prec_dev, double cut_prec,
-                             const double* cut_prec_dev) {
-    ol_args a = {};
-    a.K = K; a.N = N; a.P = P; a.C = C; a.A = A; a.y = y; a.offset = offset; a.counts = counts_dev; a.lam = prior_prec;
-    a.lam_dev = prior_prec_dev; a.kap = cut_prec; a.kap_dev = cut_prec_dev;
-    return a;
+// gb_check_overlaps over the model's six read-only arrays followed by the entry point's own, which stand at own + 6
+template <size_t NOWN>
+static int ol_check_overlaps(const char* fn, const ol_args& a, gb_arr (&own)[NOWN]) {
+    const size_t nn = (size_t)a.K * a.N, nkb = (size_t)a.K * 8;
+    const gb_arr model[6] = {{a.A, nn * a.P * 8, "A", GB_RD},          {a.y, nn * 4, "y", GB_RD},
+                             {a.offset, nn * 8, "offset", GB_RD},      {a.counts, (size_t)a.K * 4, "counts_dev", GB_RD},
+                             {a.lam_dev, nkb, "prior_prec_dev", GB_RD}, {a.kap_dev, nkb, "cut_prec_dev", GB_RD}};
+    for (int i = 0; i < 6; ++i) own[i] = model[i];
+    return gb_check_overlaps(fn, own, own + NOWN);
 }
 
 extern "C" {
@@ -495,26 +482,14 @@ int gsmvi_ordinal_hessian_batched_f64(gsmvi_ctx* ctx, void* stream, int64_t K, i
                                       const int* y, const double* offset, const int* counts_dev, double prior_prec,
                                       const double* prior_prec_dev, double cut_prec, const double* cut_prec_dev, const double* X,
                                       double* H, double* cov, int* info_dev) {
-    if (int st = ol_check_model(__func__, K, P, C, N, A, y, prior_prec, prior_prec_dev, cut_prec, cut_prec_dev)) return st;
-    GB_BAD(!X, "NULL array");
-    GB_BAD(!H && !cov, "give H or cov (or both)");
-    GB_BAD((cov != nullptr) != (info_dev != nullptr), "info_dev is required with cov and only with it");
-    const int D = P + C - 1;
-    const size_t nx = (size_t)K * D * 8, nh = nx * D, nn = (size_t)K * N, nkb = (size_t)K * 8;
-    if (int st = gb_check_overlaps(__func__, {{A, nn * P * 8, "A", GB_RD},
-                                              {y, nn * 4, "y", GB_RD},
-                                              {offset, nn * 8, "offset", GB_RD},
-                                              {counts_dev, (size_t)K * 4, "counts_dev", GB_RD},
-                                              {prior_prec_dev, nkb, "prior_prec_dev", GB_RD},
-                                              {cut_prec_dev, nkb, "cut_prec_dev", GB_RD},
-                                              {X, nx, "X", GB_RD},
-                                              {H, nh, "H", GB_WR},
-                                              {cov, nh, "cov", GB_WR},
-                                              {info_dev, (size_t)K * 4, "info_dev", GB_WR}}))
-        return st;
+    const ol_args a = ol_args_of(K, P, C, N, A, y, offset, counts_dev, prior_prec, prior_prec_dev, cut_prec, cut_prec_dev,
+                                 lp_hess_io(X, H, cov, info_dev));
+    if (int st = ol_check_model(__func__, a)) return st;
+    if (int st = lp_check_hess(__func__, a.io)) return st;
+    gb_arr own[6 + LP_HESS_ROWS];
+    lp_hess_rows(own + 6, K, P + C - 1, a.io);
+    if (int st = ol_check_overlaps(__func__, a, own)) return st;
     GB_BAD(!ctx, "ctx is NULL");
-    ol_args a = ol_model_args(K, P, C, N, A, y, offset, counts_dev, prior_prec, prior_prec_dev, cut_prec, cut_prec_dev);
-    a.X = X; a.H = H; a.cov = cov; a.info = info_dev;
     return ol_go<LP_HESS>(ctx, stream, a);
 }
 
@@ -523,37 +498,22 @@ int gsmvi_ordinal_laplace_step_batched_f64(gsmvi_ctx* ctx, void* stream, int64_t
                                            const double* prior_prec_dev, double cut_prec, const double* cut_prec_dev, int start,
                                            double* x, double* g, double* d, double* sc, int* ist, double* Xt, int* stopped_dev,
                                            int maxiter, int maxfun, double gtol) {
-    if (int st = ol_check_model(__func__, K, P, C, N, A, y, prior_prec, prior_prec_dev, cut_prec, cut_prec_dev)) return st;
-    GB_BAD(!x || !g || !d || !sc || !ist || !Xt, "NULL array");
-    GB_BAD(maxiter < 1 || maxfun < 2, "maxiter must be at least 1 and maxfun at least 2");
-    GB_BAD(!(gtol >= 0.0), "gtol must be >= 0");
-    const int D = P + C - 1;
-    const size_t nv = (size_t)K * D * 8, nn = (size_t)K * N, nkb = (size_t)K * 8;
-    if (int st = gb_check_overlaps(__func__, {{A, nn * P * 8, "A", GB_RD},
-                                              {y, nn * 4, "y", GB_RD},
-                                              {offset, nn * 8, "offset", GB_RD},
-                                              {counts_dev, (size_t)K * 4, "counts_dev", GB_RD},
-                                              {prior_prec_dev, nkb, "prior_prec_dev", GB_RD},
-                                              {cut_prec_dev, nkb, "cut_prec_dev", GB_RD},
-                                              {x, nv, "x", GB_WR},
-                                              {g, nv, "g", GB_WR},
-                                              {d, nv, "d", GB_WR},
-                                              {sc, (size_t)K * LP_NSC * 8, "sc", GB_WR},
-                                              {ist, (size_t)K * LP_NIS * 4, "ist", GB_WR},
-                                              {Xt, nv, "Xt", GB_WR},
-                                              {stopped_dev, 4, "stopped_dev", GB_WR}}))
-        return st;
+    const ol_args a = ol_args_of(K, P, C, N, A, y, offset, counts_dev, prior_prec, prior_prec_dev, cut_prec, cut_prec_dev,
+                                 lp_step_io(start, x, g, d, sc, ist, Xt, stopped_dev, maxiter, maxfun, gtol));
+    if (int st = ol_check_model(__func__, a)) return st;
+    if (int st = lp_check_step(__func__, a.io)) return st;
+    gb_arr own[6 + LP_STEP_ROWS];
+    lp_step_rows(own + 6, K, P + C - 1, a.io);
+    if (int st = ol_check_overlaps(__func__, a, own)) return st;
     GB_BAD(!ctx, "ctx is NULL");
-    ol_args a = ol_model_args(K, P, C, N, A, y, offset, counts_dev, prior_prec, prior_prec_dev, cut_prec, cut_prec_dev);
-    a.start = start != 0; a.x = x; a.g = g; a.d = d; a.sc = sc; a.ist = ist; a.Xt = Xt; a.stopped = stopped_dev;
-    a.maxiter = maxiter; a.maxfun = maxfun; a.gtol = gtol;
     return ol_go<LP_STEP>(ctx, stream, a);
 }
 
 // include/gsmvi_hip_debug.h: what a launch of either entry point at D = P + C - 1 requests (exported by the debug library only)
 int gsmvi_debug_ordinal_laplace_lds(int D, size_t* bytes, int* problems_per_workgroup) {
     GB_BAD(D < 2 || D > GB_MAX_D || !bytes || !problems_per_workgroup, "bad shape or NULL output");
-    *bytes = ol_launch_lds(D, problems_per_workgroup);
+    unsigned grid;
+    *bytes = lp_slot_launch(1, D, ol_lds_doubles(D), 0, problems_per_workgroup, &grid);
     return GSMVI_OK;
 }
 

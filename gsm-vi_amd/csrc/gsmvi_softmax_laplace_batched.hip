@@ -60,22 +60,7 @@ struct sl_args {
     const int* counts;          // (K) valid rows, clamped to 0 .. N (null: N)
     double lam;                 // the prior precision of every problem ...
     const double* lam_dev;      // ... or (K) per-problem values on the device (null: `lam`)
-    int start;
-    // LP_HESS
-    const double* X;            // (K, D)
-    double* H;                  // (K, D, D) or null
-    double* cov;                // (K, D, D) or null
-    int* info;                  // (K), with cov
-    // LP_STEP: the state
-    double* x;                  // (K, D)
-    double* g;                  // (K, D)
-    double* d;                  // (K, D)
-    double* sc;                 // (K, 4)
-    int* ist;                   // (K, 8)
-    double* Xt;                 // (K, D)
-    int* stopped;               // (1) or null
-    int maxiter, maxfun;
-    double gtol;
+    lp_io io;
 };
 
 __host__ __device__ inline int sl_dp(int D) { return ((D + 15) >> 4) << 4; }
@@ -116,12 +101,12 @@ __global__ __launch_bounds__(256) void k_softmax_laplace_batched(sl_args a) {
     double* Hs = As;                          // D x ldh           ... and H after it
     const double qnan = __longlong_as_double(0x7ff8000000000000LL);
 
-    int* is = STEP ? a.ist + kk * LP_NIS : nullptr;
-    double* sc = STEP ? a.sc + kk * LP_NSC : nullptr;
+    int* is = STEP ? a.io.ist + kk * LP_NIS : nullptr;
+    double* sc = STEP ? a.io.sc + kk * LP_NSC : nullptr;
     lp_run s;
     bool live = valid;
     if (STEP) {
-        lp_load_state(a, valid, is, sc, s);
+        lp_load_state(a.io, valid, is, sc, s);
         live = valid && s.status == 0;
         if (!__syncthreads_or(live)) return;  // every problem of the workgroup is frozen (uniform)
     }
@@ -132,7 +117,7 @@ __global__ __launch_bounds__(256) void k_softmax_laplace_batched(sl_args a) {
     const long long nk = pk.nk;               // the rows that count (a frozen slot: none, so nothing of A_k is loaded)
     const double lam = pk.lam;
     if (l < Dp) {
-        const double* xsrc = STEP ? a.Xt : a.X;
+        const double* xsrc = STEP ? a.io.Xt : a.io.X;
         xs[l] = live && l < D ? xsrc[kd + l] : 0.0;
     }
     if (l == 0) cell[0] = 0.0;
@@ -341,35 +326,29 @@ __global__ __launch_bounds__(256) void k_softmax_laplace_batched(sl_args a) {
     lp_verdict v;
     bool need;
     if (STEP) {
-        lp_step_test(a, live, bad, D, ln, gs, cell, s, v);
+        lp_step_test(a.io, live, bad, D, ln, gs, cell, s, v);
         need = v.need;
     } else {
-        need = live && !bad && a.cov != nullptr;
-        lp_write_h<NT, MAXE>(a, live, bad, kk, D, l, ldh, Hs);
+        need = live && !bad && a.io.cov != nullptr;
+        lp_write_h<NT, MAXE>(a.io, live, bad, kk, D, l, ldh, Hs);
     }
 
     const int info = lp_chol_lds<NT, MAXE>(need, D, l, ldh, Hs, pv, dg);     // (its last barrier publishes R and the pivots)
 
     if (!STEP) {
-        if (!a.cov) return;                   // (uniform)
-        lp_inverse_tail<NT, MAXE>(a, live, bad, need, info, k, kk, D, l, ldh, Hs, pv, rd);
+        if (!a.io.cov) return;                   // (uniform)
+        lp_inverse_tail<NT, MAXE>(a.io, live, bad, need, info, k, kk, D, l, ldh, Hs, pv, rd);
         return;
     }
     if (!live || l >= 64) return;             // the rest is the first wave's: component l of every vector in lane l
-    lp_step_tail(a, s, v, info, kd, D, l, ldh, Hs, pv, xs, sc, is);
-}
-
-// dynamic LDS bytes of a launch at (C, P): at most 38.6 KB, below the default limit of 64 KB, so no kernel attribute is needed
-static size_t sl_launch_lds(int C, int P, int* ppw) {
-    *ppw = 256 / gb_nt((C - 1) * P);
-    return (size_t)*ppw * sl_lds_doubles(C, P) * sizeof(double);
+    lp_step_tail(a.io, s, v, info, kd, D, l, ldh, Hs, pv, xs, sc, is);
 }
 
 template <int MODE>
 static int sl_go(gsmvi_ctx* ctx, void* stream, const sl_args& a) {
     int ppw;
-    const size_t lds = sl_launch_lds(a.C, a.P, &ppw);
-    const unsigned grid = (unsigned)((a.K + ppw - 1) / ppw);
+    unsigned grid;
+    const size_t lds = lp_slot_launch(a.K, a.D, sl_lds_doubles(a.C, a.P), 0, &ppw, &grid);
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     if (ppw == 4)
         hipLaunchKernelGGL((k_softmax_laplace_batched<64, MODE>), dim3(grid), dim3(256), lds, st, a);
@@ -385,18 +364,13 @@ int gsmvi_softmax_hessian_batched_f64(gsmvi_ctx* ctx, void* stream, int64_t K, i
                                       const double* X, double* H, double* cov, int* info_dev) {
     const sm_model m = sm_model_of(K, N, C, P, A, labels, counts_dev, prior_prec, prior_prec_dev);
     if (int st = sm_check_model(__func__, m, true, "N")) return st;
-    const int D = m.D;
-    GB_BAD(!A || !labels || !X, "NULL array");
-    GB_BAD(!H && !cov, "give H or cov (or both)");
-    GB_BAD((cov != nullptr) != (info_dev != nullptr), "info_dev is required with cov and only with it");
-    const size_t nx = (size_t)K * D * 8, nh = nx * D;
-    if (int st = gb_check_overlaps(__func__, m, {{X, nx, "X", GB_RD}, {H, nh, "H", GB_WR}, {cov, nh, "cov", GB_WR},
-                                                 {info_dev, (size_t)K * 4, "info_dev", GB_WR}}))
-        return st;
+    const sl_args a = {K, N, C, P, m.D, A, labels, counts_dev, prior_prec, prior_prec_dev, lp_hess_io(X, H, cov, info_dev)};
+    GB_BAD(!A || !labels, "NULL array");
+    if (int st = lp_check_hess(__func__, a.io)) return st;
+    gb_arr own[LP_HESS_ROWS];
+    lp_hess_rows(own, K, m.D, a.io);
+    if (int st = gb_check_overlaps(__func__, m, own)) return st;
     GB_BAD(!ctx, "ctx is NULL");
-    sl_args a = {};
-    a.K = K; a.N = N; a.C = C; a.P = P; a.D = D; a.A = A; a.labels = labels; a.counts = counts_dev; a.lam = prior_prec;
-    a.lam_dev = prior_prec_dev; a.X = X; a.H = H; a.cov = cov; a.info = info_dev;
     return sl_go<LP_HESS>(ctx, stream, a);
 }
 
@@ -406,28 +380,22 @@ int gsmvi_softmax_laplace_step_batched_f64(gsmvi_ctx* ctx, void* stream, int64_t
                                            int* ist, double* Xt, int* stopped_dev, int maxiter, int maxfun, double gtol) {
     const sm_model m = sm_model_of(K, N, C, P, A, labels, counts_dev, prior_prec, prior_prec_dev);
     if (int st = sm_check_model(__func__, m, true, "N")) return st;
-    const int D = m.D;
-    GB_BAD(!A || !labels || !x || !g || !d || !sc || !ist || !Xt, "NULL array");
-    GB_BAD(maxiter < 1 || maxfun < 2, "maxiter must be at least 1 and maxfun at least 2");
-    GB_BAD(!(gtol >= 0.0), "gtol must be >= 0");
-    const size_t nv = (size_t)K * D * 8;
-    if (int st = gb_check_overlaps(__func__, m, {{x, nv, "x", GB_WR}, {g, nv, "g", GB_WR}, {d, nv, "d", GB_WR},
-                                                 {sc, (size_t)K * LP_NSC * 8, "sc", GB_WR},
-                                                 {ist, (size_t)K * LP_NIS * 4, "ist", GB_WR}, {Xt, nv, "Xt", GB_WR},
-                                                 {stopped_dev, 4, "stopped_dev", GB_WR}}))
-        return st;
+    const sl_args a = {K, N, C, P, m.D, A, labels, counts_dev, prior_prec, prior_prec_dev,
+                       lp_step_io(start, x, g, d, sc, ist, Xt, stopped_dev, maxiter, maxfun, gtol)};
+    GB_BAD(!A || !labels, "NULL array");
+    if (int st = lp_check_step(__func__, a.io)) return st;
+    gb_arr own[LP_STEP_ROWS];
+    lp_step_rows(own, K, m.D, a.io);
+    if (int st = gb_check_overlaps(__func__, m, own)) return st;
     GB_BAD(!ctx, "ctx is NULL");
-    sl_args a = {};
-    a.K = K; a.N = N; a.C = C; a.P = P; a.D = D; a.A = A; a.labels = labels; a.counts = counts_dev; a.lam = prior_prec;
-    a.lam_dev = prior_prec_dev; a.start = start != 0; a.x = x; a.g = g; a.d = d; a.sc = sc; a.ist = ist; a.Xt = Xt;
-    a.stopped = stopped_dev; a.maxiter = maxiter; a.maxfun = maxfun; a.gtol = gtol;
     return sl_go<LP_STEP>(ctx, stream, a);
 }
 
 // include/gsmvi_hip_debug.h: what a launch at (C, P) requests (exported by the debug library only)
 int gsmvi_debug_softmax_laplace_lds(int C, int P, size_t* bytes, int* problems_per_workgroup) {
     GB_BAD(!sm_shape_ok(C, P) || !bytes || !problems_per_workgroup, "bad shape or NULL output");
-    *bytes = sl_launch_lds(C, P, problems_per_workgroup);
+    unsigned grid;
+    *bytes = lp_slot_launch(1, (C - 1) * P, sl_lds_doubles(C, P), 0, problems_per_workgroup, &grid);
     return GSMVI_OK;
 }
 

@@ -1065,6 +1065,28 @@ class HipEngine:
                    self._packed(pf["best_cov"], (K, D, D), "best_cov"), self._ints(pf["best_it"], K, "best_it"))
 
     # ---- batched Laplace initialiser: Hessian, inverse and Newton rounds of the GLM targets (csrc/gsmvi_laplace_batched.hip) ----
+    def _hess_call(self, name, model_args, X, want, out, cov_out, info_out):
+        """The Hessian entry ``name`` of a Laplace family at the rows of X (K, D) after its model's arguments, for a caller that
+        has made its context (``_any_ctx``) where it always did among its own checks: allocates what
+        ``want`` asks for and ``out`` / ``cov_out`` / ``info_out`` do not give, and returns H, (cov, info) or (H, cov, info)"""
+        K, D = X.shape
+        H = cov = info = None
+        if want != "cov":
+            H = self.empty(K, D, D) if out is None else out
+        if want != "h":
+            cov = self.empty(K, D, D) if cov_out is None else cov_out
+            info = torch.zeros(K, dtype=torch.int32, device=self.device) if info_out is None else info_out
+        self._call(name, *model_args, self._packed(X, (K, D), "X"), self._dp(H, (K, D, D), "out"),
+                   self._dp(cov, (K, D, D), "cov_out"), self._ints(info, K, "info_out"))
+        return H if want == "h" else (cov, info) if want == "cov" else (H, cov, info)
+
+    def _laplace_step_args(self, state, K, D, start, maxiter, maxfun, gtol):
+        """the eleven arguments every Laplace step entry ends with, after its model's: start, the state, the limits"""
+        return (int(bool(start)), self._packed(state["x"], (K, D), "x"), self._packed(state["g"], (K, D), "g"),
+                self._packed(state["d"], (K, D), "d"), self._packed(state["sc"], (K, 4), "sc"), self._ist(state, K),
+                self._packed(state["Xt"], (K, D), "Xt"), self._ints(state.get("stopped"), 1, "stopped"), int(maxiter),
+                int(maxfun), float(gtol))
+
     def _glm_model_args(self, A, y, family, offset, counts, prior_prec, noise_prec):
         """the model's arguments of the two Laplace entry points, in the order of include/gsmvi_hip.h"""
         K, N, D = A.shape
@@ -1080,19 +1102,10 @@ class HipEngine:
         H (K, D, D), "cov" -> (cov, info), "both" -> (H, cov, info); ``info`` (K,) int32: 0, or 1 + the first failing pivot, and
         then cov_k = I.  The other arguments are ``glm_batched``'s."""
         self._check_want(want, "h", "cov")
-        X = X.contiguous()
-        K, D = X.shape
         self._any_ctx()
-        H = cov = info = None
-        if want != "cov":
-            H = self.empty(K, D, D) if out is None else out
-        if want != "h":
-            cov = self.empty(K, D, D) if cov_out is None else cov_out
-            info = torch.zeros(K, dtype=torch.int32, device=self.device) if info_out is None else info_out
-        self._call("gsmvi_glm_hessian_batched_f64",
-                   *self._glm_model_args(A, y, family, offset, counts, prior_prec, noise_prec), self._packed(X, (K, D), "X"),
-                   self._dp(H, (K, D, D), "out"), self._dp(cov, (K, D, D), "cov_out"), self._ints(info, K, "info_out"))
-        return H if want == "h" else (cov, info) if want == "cov" else (H, cov, info)
+        return self._hess_call("gsmvi_glm_hessian_batched_f64",
+                               self._glm_model_args(A, y, family, offset, counts, prior_prec, noise_prec), X.contiguous(), want,
+                               out, cov_out, info_out)
 
     def laplace_state_batched(self, x0):
         """The state of K Newton runs started at the rows of x0 (K, D), as include/gsmvi_hip.h lays it out: a dict of device
@@ -1109,13 +1122,8 @@ class HipEngine:
         ``state["stopped"]`` (optional) grows by the problems that stopped  [the role of gsmvi/initializers.py:5-17]"""
         K, D = state["x"].shape
         self._any_ctx()
-        stopped = state.get("stopped")
-        self._call("gsmvi_laplace_step_batched_f64",
-                   *self._glm_model_args(A, y, family, offset, counts, prior_prec, noise_prec), int(bool(start)),
-                   self._packed(state["x"], (K, D), "x"), self._packed(state["g"], (K, D), "g"),
-                   self._packed(state["d"], (K, D), "d"), self._packed(state["sc"], (K, 4), "sc"),
-                   self._ist(state, K), self._packed(state["Xt"], (K, D), "Xt"), self._ints(stopped, 1, "stopped"),
-                   int(maxiter), int(maxfun), float(gtol))
+        self._call("gsmvi_laplace_step_batched_f64", *self._glm_model_args(A, y, family, offset, counts, prior_prec, noise_prec),
+                   *self._laplace_step_args(state, K, D, start, maxiter, maxfun, gtol))
 
     # ---- batched softmax Laplace initialiser: the same for the multinomial logit (csrc/gsmvi_softmax_laplace_batched.hip) -------
     def softmax_hessian_batched(self, X, A, labels, num_classes, counts=None, prior_prec=1.0, want="h", out=None, cov_out=None,
@@ -1129,16 +1137,8 @@ class HipEngine:
         X = X.contiguous()
         K, D = X.shape
         self._any_ctx()
-        H = cov = info = None
-        if want != "cov":
-            H = self.empty(K, D, D) if out is None else out
-        if want != "h":
-            cov = self.empty(K, D, D) if cov_out is None else cov_out
-            info = torch.zeros(K, dtype=torch.int32, device=self.device) if info_out is None else info_out
         (Cc, P, N), model = self._softmax_model_args(K, D, A, labels, num_classes, counts, prior_prec)
-        self._call("gsmvi_softmax_hessian_batched_f64", K, Cc, P, N, *model, self._packed(X, (K, D), "X"),
-                   self._dp(H, (K, D, D), "out"), self._dp(cov, (K, D, D), "cov_out"), self._ints(info, K, "info_out"))
-        return H if want == "h" else (cov, info) if want == "cov" else (H, cov, info)
+        return self._hess_call("gsmvi_softmax_hessian_batched_f64", (K, Cc, P, N, *model), X, want, out, cov_out, info_out)
 
     def softmax_laplace_step_batched(self, state, A, labels, num_classes, counts=None, prior_prec=1.0, start=False, maxiter=100,
                                      maxfun=200, gtol=1e-8):
@@ -1147,13 +1147,9 @@ class HipEngine:
         ``laplace_step_batched``, the same state machine  [the role of gsmvi/initializers.py:5-17]"""
         K, D = state["x"].shape
         self._any_ctx()
-        stopped = state.get("stopped")
         (Cc, P, N), model = self._softmax_model_args(K, D, A, labels, num_classes, counts, prior_prec)
-        self._call("gsmvi_softmax_laplace_step_batched_f64", K, Cc, P, N, *model, int(bool(start)),
-                   self._packed(state["x"], (K, D), "x"), self._packed(state["g"], (K, D), "g"),
-                   self._packed(state["d"], (K, D), "d"), self._packed(state["sc"], (K, 4), "sc"),
-                   self._ist(state, K), self._packed(state["Xt"], (K, D), "Xt"), self._ints(stopped, 1, "stopped"),
-                   int(maxiter), int(maxfun), float(gtol))
+        self._call("gsmvi_softmax_laplace_step_batched_f64", K, Cc, P, N, *model,
+                   *self._laplace_step_args(state, K, D, start, maxiter, maxfun, gtol))
 
     # ---- shared-design Laplace initialiser: the same for K GLMs on one design matrix (csrc/gsmvi_laplace_shared_batched.hip) -----
     def _glm_shared_model_args(self, K, A, y, family, offset, weights, prior_prec, noise_prec):
@@ -1175,17 +1171,9 @@ class HipEngine:
         X = X.contiguous()
         K, D = X.shape
         self._any_ctx()
-        H = cov = info = None
-        if want != "cov":
-            H = self.empty(K, D, D) if out is None else out
-        if want != "h":
-            cov = self.empty(K, D, D) if cov_out is None else cov_out
-            info = torch.zeros(K, dtype=torch.int32, device=self.device) if info_out is None else info_out
-        self._call("gsmvi_glm_shared_hessian_batched_f64",
-                   *self._glm_shared_model_args(K, A, y, family, offset, weights, prior_prec, noise_prec),
-                   self._packed(X, (K, D), "X"), self._dp(H, (K, D, D), "out"), self._dp(cov, (K, D, D), "cov_out"),
-                   self._ints(info, K, "info_out"))
-        return H if want == "h" else (cov, info) if want == "cov" else (H, cov, info)
+        return self._hess_call("gsmvi_glm_shared_hessian_batched_f64",
+                               self._glm_shared_model_args(K, A, y, family, offset, weights, prior_prec, noise_prec), X, want, out,
+                               cov_out, info_out)
 
     def laplace_shared_step_batched(self, state, A, y, family, offset=None, weights=None, prior_prec=1.0, noise_prec=1.0,
                                     start=False, maxiter=100, maxfun=200, gtol=1e-8):
@@ -1194,13 +1182,9 @@ class HipEngine:
         of ``laplace_step_batched``, the same state machine  [the role of gsmvi/initializers.py:5-17]"""
         K, D = state["x"].shape
         self._any_ctx()
-        stopped = state.get("stopped")
         self._call("gsmvi_laplace_shared_step_batched_f64",
-                   *self._glm_shared_model_args(K, A, y, family, offset, weights, prior_prec, noise_prec), int(bool(start)),
-                   self._packed(state["x"], (K, D), "x"), self._packed(state["g"], (K, D), "g"),
-                   self._packed(state["d"], (K, D), "d"), self._packed(state["sc"], (K, 4), "sc"),
-                   self._ist(state, K), self._packed(state["Xt"], (K, D), "Xt"), self._ints(stopped, 1, "stopped"),
-                   int(maxiter), int(maxfun), float(gtol))
+                   *self._glm_shared_model_args(K, A, y, family, offset, weights, prior_prec, noise_prec),
+                   *self._laplace_step_args(state, K, D, start, maxiter, maxfun, gtol))
 
     # ---- negative binomial Laplace initialiser: the same for K count regressions with a fitted size
     # (csrc/gsmvi_negbin_laplace_batched.hip) --------------------------------------------------------------------------------------
@@ -1227,17 +1211,9 @@ class HipEngine:
         if D != A.shape[2] + 1:
             raise ValueError(f"X: expected P + 1 = {A.shape[2] + 1} columns (beta, then the log size), got {D}")
         self._any_ctx()
-        H = cov = info = None
-        if want != "cov":
-            H = self.empty(K, D, D) if out is None else out
-        if want != "h":
-            cov = self.empty(K, D, D) if cov_out is None else cov_out
-            info = torch.zeros(K, dtype=torch.int32, device=self.device) if info_out is None else info_out
-        self._call("gsmvi_negbin_hessian_batched_f64",
-                   *self._negbin_model_args(A, y, offset, counts, prior_prec, log_size_mean, log_size_prec),
-                   self._packed(X, (K, D), "X"), self._dp(H, (K, D, D), "out"), self._dp(cov, (K, D, D), "cov_out"),
-                   self._ints(info, K, "info_out"))
-        return H if want == "h" else (cov, info) if want == "cov" else (H, cov, info)
+        return self._hess_call("gsmvi_negbin_hessian_batched_f64",
+                               self._negbin_model_args(A, y, offset, counts, prior_prec, log_size_mean, log_size_prec), X, want, out,
+                               cov_out, info_out)
 
     def negbin_laplace_step_batched(self, state, A, y, offset=None, counts=None, prior_prec=1.0, log_size_mean=0.0,
                                     log_size_prec=1.0, start=False, maxiter=100, maxfun=200, gtol=1e-8):
@@ -1249,13 +1225,9 @@ class HipEngine:
         if D != A.shape[2] + 1:
             raise ValueError(f"state: expected P + 1 = {A.shape[2] + 1} columns (beta, then the log size), got {D}")
         self._any_ctx()
-        stopped = state.get("stopped")
         self._call("gsmvi_negbin_laplace_step_batched_f64",
-                   *self._negbin_model_args(A, y, offset, counts, prior_prec, log_size_mean, log_size_prec), int(bool(start)),
-                   self._packed(state["x"], (K, D), "x"), self._packed(state["g"], (K, D), "g"),
-                   self._packed(state["d"], (K, D), "d"), self._packed(state["sc"], (K, 4), "sc"),
-                   self._ist(state, K), self._packed(state["Xt"], (K, D), "Xt"), self._ints(stopped, 1, "stopped"),
-                   int(maxiter), int(maxfun), float(gtol))
+                   *self._negbin_model_args(A, y, offset, counts, prior_prec, log_size_mean, log_size_prec),
+                   *self._laplace_step_args(state, K, D, start, maxiter, maxfun, gtol))
 
     # ---- ordinal Laplace initialiser: the same for K cumulative-logit regressions (csrc/gsmvi_ordinal_laplace_batched.hip) --------
     def _ordinal_model_args(self, D, A, y, C, offset, counts, prior_prec, cut_prec, what):
@@ -1286,15 +1258,7 @@ class HipEngine:
         K, D = X.shape
         model = self._ordinal_model_args(D, A, y, C, offset, counts, prior_prec, cut_prec, "X")
         self._any_ctx()
-        H = cov = info = None
-        if want != "cov":
-            H = self.empty(K, D, D) if out is None else out
-        if want != "h":
-            cov = self.empty(K, D, D) if cov_out is None else cov_out
-            info = torch.zeros(K, dtype=torch.int32, device=self.device) if info_out is None else info_out
-        self._call("gsmvi_ordinal_hessian_batched_f64", *model, self._packed(X, (K, D), "X"), self._dp(H, (K, D, D), "out"),
-                   self._dp(cov, (K, D, D), "cov_out"), self._ints(info, K, "info_out"))
-        return H if want == "h" else (cov, info) if want == "cov" else (H, cov, info)
+        return self._hess_call("gsmvi_ordinal_hessian_batched_f64", model, X, want, out, cov_out, info_out)
 
     def ordinal_laplace_step_batched(self, state, A, y, C, offset=None, counts=None, prior_prec=1.0, cut_prec=1.0, start=False,
                                      maxiter=100, maxfun=200, gtol=1e-8):
@@ -1305,12 +1269,8 @@ class HipEngine:
         K, D = state["x"].shape
         model = self._ordinal_model_args(D, A, y, C, offset, counts, prior_prec, cut_prec, "state")
         self._any_ctx()
-        stopped = state.get("stopped")
-        self._call("gsmvi_ordinal_laplace_step_batched_f64", *model, int(bool(start)),
-                   self._packed(state["x"], (K, D), "x"), self._packed(state["g"], (K, D), "g"),
-                   self._packed(state["d"], (K, D), "d"), self._packed(state["sc"], (K, 4), "sc"),
-                   self._ist(state, K), self._packed(state["Xt"], (K, D), "Xt"), self._ints(stopped, 1, "stopped"),
-                   int(maxiter), int(maxfun), float(gtol))
+        self._call("gsmvi_ordinal_laplace_step_batched_f64", *model,
+                   *self._laplace_step_args(state, K, D, start, maxiter, maxfun, gtol))
 
     # ---- batched GLM posterior predictive: the use of K fitted Gaussians (csrc/gsmvi_glm_predict_batched.hip) -----------------
     @staticmethod

@@ -6,7 +6,9 @@ four families with and without an offset, at (D, N, rows of X) shapes on both si
 softmax entry points (score and density in the three ``want``s, Hessian and inverse, six Newton rounds, the leave-one-out, the
 predictive) at K = 13, at (C, P, N, rows of X, S) shapes on both sides of theirs; and the KL monitor's draw (one call and two
 chunks) and log-density, Pathfinder's propose and select over five L-BFGS rounds, and one ADVI start and step, at K = 13 and
-six D, with the fewest rows and one more than a tile.
+six D, with the fewest rows and one more than a tile; and the Hessian with its inverse and six Newton rounds from x0 = 0 of the
+shared-design, negative binomial and ordinal Laplace entries at K = 13, at the smallest sizes where their mapping changes, with the
+count of problems whose last-pivot or retry rule fired (``ist[:, 4] > 0``) printed per kernel.
 
   python scripts/batched_dump.py OUT.npz                 dump with the library the package loads
   GSMVI_HIP_LIB_VARIANT=old python scripts/batched_dump.py OUT.npz   ... with gsm-vi_amd/libgsmvi_hip_old.so
@@ -34,6 +36,122 @@ SOFTMAX_SHAPES = ((2, 1, 1, 1, 5), (2, 64, 33, 17, 65), (65, 1, 32, 33, 5), (17,
 # D of the KL, Pathfinder and ADVI entries: one lane, an odd D, the four-problem packing's last, the first of one problem per
 # workgroup, an odd D above it, the largest; rows: the fewest, and one more than a tile of the draw stage
 INIT_DIMS = (1, 5, 16, 17, 33, 64)
+
+
+# the three later Laplace families.  N: one row, a full tile of 32, one row more, three tiles.  Shared design: D on both sides of
+# the four-problem packing, one lane and the largest.  Negative binomial: D = P + 1 the same.  Ordinal (P, C): D = 16 and 17, P on a
+# block boundary (a block of rows that is all cutpoints), and both ways to D = 64
+LAPLACE_N = (1, 32, 33, 70)
+SHARED_LAPLACE_D = (1, 16, 17, 64)
+NEGBIN_LAPLACE_P = (1, 15, 16, 63)
+ORDINAL_LAPLACE_PC = ((1, 2), (13, 4), (13, 5), (16, 2), (16, 5), (1, 64), (40, 25))
+
+
+def laplace_edges(rs, K, N):
+    """what the K = 13 inputs of the three dumps below share: counts 0 for problem 1 and N for problem 2, lam = 0 for problem 0"""
+    cnt = np.array([max(1, N - k) for k in range(K)])
+    cnt[1], cnt[2] = 0, N
+    lam = 0.1 + rs.random_sample(K)
+    lam[0] = 0.0
+    return cnt, lam
+
+
+def negbin_laplace_inputs(P, N, K=13):
+    """A, y, offset, counts, lam, theta mean and precision (K,) of the negative binomial dump: the recipe of the step tests
+    (A = N(0, 1) / sqrt(P), beta* ~ 0.7 N(0, 1), offsets 1 + 0.3 N(0, 1), size 3), so that H at x0 = 0 is indefinite in theta for
+    a large share of the problems and the last-pivot rule fires in the first rounds"""
+    rs = np.random.RandomState(1000 * N + 10 * P + 3)
+    A = rs.standard_normal((K, N, P)) / np.sqrt(P)
+    o = 1.0 + 0.3 * rs.standard_normal((K, N))
+    mu = np.exp(np.einsum("knp,kp->kn", A, 0.7 * rs.standard_normal((K, P))) + o)
+    y = rs.poisson(rs.gamma(3.0, mu / 3.0)).astype(np.float64)
+    cnt, lam = laplace_edges(rs, K, N)
+    return A, y, o, cnt, lam, 0.2 * rs.standard_normal(K), 0.5 + rs.random_sample(K)
+
+
+def ordinal_laplace_inputs(P, C, N, K=13):
+    """A, labels, offset, counts, lam, kap (K,) of the ordinal dump: labels from a latent logistic variable cut at C - 1 sorted
+    points, so every class occurs at the larger N; from x0 = 0 the chain terms make H indefinite where classes are many and
+    the retry rule fires"""
+    rs = np.random.RandomState(100000 * C + 1000 * P + 10 * N + 7)
+    A = rs.standard_normal((K, N, P)) / np.sqrt(P)
+    o = 0.3 * rs.standard_normal((K, N))
+    z = np.einsum("knp,kp->kn", A, rs.standard_normal((K, P))) + o + rs.logistic(size=(K, N))
+    cuts = np.sort(2.5 * rs.standard_normal((K, C - 1)), 1)
+    y = (z[:, :, None] > cuts[:, None, :]).sum(2)
+    cnt, lam = laplace_edges(rs, K, N)
+    return A, y, o, cnt, lam, 0.5 + rs.random_sample(K)
+
+
+def dump_laplace_families(out, K=13):
+    """Hessian + inverse + info at random rows of X, then six Newton rounds from x0 = 0 with every state array after every round,
+    for the shared-design, negative binomial and ordinal entries; problem 4 has a NaN in X and in x0"""
+    from gsmvi_amd.engine import get_engine
+    eng = get_engine()
+    host = lambda *ts: np.concatenate([eng.to_numpy(t).astype(np.float64).reshape(K, -1) for t in ts], 1)     # noqa: E731
+    state = ("x", "g", "d", "Xt", "sc", "ist")
+    fired = {"negbin": 0, "ordinal": 0}
+
+    def points(rs, D):
+        X, x0 = rs.standard_normal((K, D)), np.zeros((K, D))
+        X[4, D - 1] = x0[4, 0] = np.nan
+        return eng.asarray(X), eng.asarray(x0)
+
+    def rounds(tag, step, x0):
+        st = eng.laplace_state_batched(x0)
+        for r in range(6):
+            step(st, r == 0)
+            out[tag.replace("_", f"_laplace{r}_", 1)] = host(*(st[n] for n in state))
+        return int((eng.to_numpy(st["ist"])[:, 4] > 0).sum())
+
+    for N in LAPLACE_N:
+        for D in SHARED_LAPLACE_D:
+            for fi, family in enumerate(GLM_FAMILIES):
+                rs = np.random.RandomState(20000 * D + 100 * N + fi)
+                Ah = rs.standard_normal((N, D)) / np.sqrt(D)
+                oh = 0.3 * rs.standard_normal((K, N))
+                eta = Ah @ rs.standard_normal((D, K))
+                eta = eta.T + oh
+                tau_h = 0.5 + rs.random_sample(K)
+                if family == "poisson":
+                    yh = rs.poisson(np.exp(np.minimum(eta, 3.0))).astype(np.float64)
+                elif family == "gaussian":
+                    yh = eta + rs.standard_normal((K, N)) / np.sqrt(tau_h)[:, None]
+                else:
+                    yh = (rs.random_sample((K, N)) < 1.0 / (1.0 + np.exp(-eta))).astype(np.float64)
+                _, lam_h = laplace_edges(rs, K, N)
+                wh = rs.random_sample((K, N)) * (rs.random_sample((K, N)) < 0.7)       # some zero; problem 1: all zero
+                wh[1] = 0.0
+                A, y, off = eng.asarray(Ah), eng.asarray(yh), eng.asarray(oh)
+                X, x0 = points(rs, D)
+                for w in (None, eng.asarray(wh)):
+                    model = dict(offset=off, weights=w, prior_prec=eng.batched_regs(lam_h),
+                                 noise_prec=eng.batched_regs(tau_h) if family == "gaussian" else 1.0)
+                    tag = f"shared_{family}_{'w' if w is not None else 'now'}_D{D}_N{N}"
+                    out[tag.replace("_", "_hessian_", 1)] = host(*eng.glm_shared_hessian_batched(X, A, y, family, want="both", **model))
+                    rounds(tag, lambda st, start: eng.laplace_shared_step_batched(st, A, y, family, start=start, **model), x0)
+        for P in NEGBIN_LAPLACE_P:
+            Ah, yh, oh, cnt, lam_h, tm_h, tk_h = negbin_laplace_inputs(P, N, K)
+            A, y = eng.asarray(Ah), eng.asarray(yh)
+            X, x0 = points(np.random.RandomState(31 * P + N), P + 1)
+            for off in (None, eng.asarray(oh)):
+                model = dict(offset=off, counts=eng.batched_counts(cnt), prior_prec=eng.batched_regs(lam_h),
+                             log_size_mean=eng.batched_regs(tm_h), log_size_prec=eng.batched_regs(tk_h))
+                tag = f"negbin_{'off' if off is not None else 'nooff'}_P{P}_N{N}"
+                out[tag.replace("_", "_hessian_", 1)] = host(*eng.negbin_hessian_batched(X, A, y, want="both", **model))
+                fired["negbin"] += rounds(tag, lambda st, start: eng.negbin_laplace_step_batched(st, A, y, start=start, **model), x0)
+        for P, C in ORDINAL_LAPLACE_PC:
+            Ah, yh, oh, cnt, lam_h, kap_h = ordinal_laplace_inputs(P, C, N, K)
+            A, y = eng.asarray(Ah), eng.batched_labels(yh)
+            X, x0 = points(np.random.RandomState(977 * P + 31 * C + N), P + C - 1)
+            for off in (None, eng.asarray(oh)):
+                model = dict(offset=off, counts=eng.batched_counts(cnt), prior_prec=eng.batched_regs(lam_h),
+                             cut_prec=eng.batched_regs(kap_h))
+                tag = f"ordinal_{'off' if off is not None else 'nooff'}_P{P}_C{C}_N{N}"
+                out[tag.replace("_", "_hessian_", 1)] = host(*eng.ordinal_hessian_batched(X, A, y, C, want="both", **model))
+                fired["ordinal"] += rounds(tag, lambda st, start: eng.ordinal_laplace_step_batched(st, A, y, C, start=start, **model), x0)
+    print(f"problems that end their six rounds with ist[:, 4] > 0: negbin (last-pivot rule) {fired['negbin']}, "
+          f"ordinal (retry rule) {fired['ordinal']}")
 
 
 def dump_glm(out, K=13):
@@ -195,6 +313,7 @@ def dump(path):
     dump_glm(out, K)
     dump_softmax(out, K)
     dump_initialisers(out, K)
+    dump_laplace_families(out, K)
     for D, B in SHAPES:
         rs = np.random.RandomState(100 * D + B)
         A = rs.standard_normal((K, D, D))
