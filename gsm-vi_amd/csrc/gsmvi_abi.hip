@@ -52,13 +52,14 @@ bool gsmvi_launch_gsm_scalars_fast(hipStream_t st, hipEvent_t* ev, int D, int B,
 bool gsmvi_launch_gsm_cov_sym(hipStream_t st, hipEvent_t* ev, int D, int B, const double* rec, int ldrec,
                               const double* mu0, const double* S0, int lds0, double* S, int lds, double* mu_out,
                               int dbg, unsigned long long* stamps, int num_cu);
-void gsmvi_launch_panel_fast_part(hipStream_t st, hipEvent_t* ev, dim3 grid, int D, int B, const double* G, int ldg,
+bool gsmvi_launch_panel_fast_part(hipStream_t st, hipEvent_t* ev, dim3 grid, int D, int B, const double* G, int ldg,
                                   const double* S0, int lds0, double* Pp, int chunks_per_wg, const double* X, int ldx,
                                   const double* mu0, double* Qg, double* Qm, int chw, bool qm_whole, int stream,
-                                  unsigned long long* stamps);
-void gsmvi_launch_gsm_cov_sym_slabs(hipStream_t st, hipEvent_t* ev, int D, int B, const struct gsm_slab_src& fs, const double* mu0,
+                                  unsigned long long* stamps, bool preload);
+bool gsmvi_launch_gsm_cov_sym_slabs(hipStream_t st, hipEvent_t* ev, int D, int B, const struct gsm_slab_src& fs, const double* mu0,
                                     const double* S0, int lds0, double* S, int lds, double* mu_out, int kct, bool fold,
-                                    bool s0_last, bool store_wt, bool qm_whole, bool quad, bool wave_store, unsigned long long* stamps);
+                                    bool s0_last, bool store_wt, bool qm_whole, bool quad, bool wave_store, unsigned long long* stamps,
+                                    bool preload);
 int gsmvi_cov_sym_pairs(int nt);
 int gsmvi_panel_fast_chunk(int MT);
 int gsmvi_potrf_impl(struct gsmvi_ctx* ctx, hipStream_t st, int D, const double* S, int lds, double* R, int ldr,
@@ -344,6 +345,7 @@ int gsmvi_set_tuning(gsmvi_ctx* ctx, const char* name, int value) {
     else if (!strcmp(name, "cov_store_wt")) ctx->tune_cov_store_wt = value;
     else if (!strcmp(name, "panel_qm_whole")) ctx->tune_panel_qm_whole = value;
     else if (!strcmp(name, "panel_stream")) ctx->tune_panel_stream = value;
+    else if (!strcmp(name, "kernarg_preload")) ctx->tune_kernarg_preload = value;
     else if (!strcmp(name, "cov_dbg")) ctx->tune_cov_dbg = value;   // ablation bits, timing experiments only
     else if (!strcmp(name, "timeline")) {                           // whole-update timeline stamps (diagnostic)
         if (value && !ctx->stamps) {
@@ -702,7 +704,7 @@ static int gsm_two_launch(gsmvi_ctx* ctx, hipStream_t hs, int D, int B, int cpw,
     // Qm only; the same bytes either way, so no path bit -- the timeline's stamp words 4 - 7 tell the instances apart)
     const int stream = (chw == 512 && D == 1024 && cpw == 1 && !qm_whole && ctx->tune_panel_stream != 0) ? (ctx->tune_panel_stream == 4 ? 4 : 2) : 0;
     gsmvi_launch_panel_fast_part(hs, ev0, dim3(strips, kc, chw == 512 ? B / 16 : 1), D, B, G, ldg, S0, lds0, ctx->pp, cpw, X, ldx, mu0, Qg, Qm, chw,
-                                 qm_whole, stream, ctx->timeline_stamps(0));
+                                 qm_whole, stream, ctx->timeline_stamps(0), ctx->tune_kernarg_preload != 0);
     ctx->path |= GSMVI_PATH_PANEL_FAST | (chw == 512 ? GSMVI_PATH_PANEL_CHUNK512 : 0u) | (qm_whole ? GSMVI_PATH_PANEL_QM_WHOLE : 0u);
     int st = check_launch("k_panel_fast(partials)");
     if (st != GSMVI_OK) return st;
@@ -733,7 +735,8 @@ static int gsm_two_launch(gsmvi_ctx* ctx, hipStream_t hs, int D, int B, int cpw,
     const bool quad = quad_form && ((ctx->tune_cov_diag_quad >= 2 && ctx->tune_cov_fold_diag != 0) ||
                                     (ctx->tune_cov_diag_quad == 1 && chw == 512 && ctx->tune_cov_fold_diag == 1 && fold));
     gsmvi_launch_gsm_cov_sym_slabs(hs, ctx->stage_events(2), D, B, fs, mu0, S0, lds0, S, lds, mu, chw == 512 ? 2 : 4, fold,
-                                   s0_last, store_wt, qm_whole, quad, quad && ctx->tune_cov_wave_store != 0, ctx->timeline_stamps(2));
+                                   s0_last, store_wt, qm_whole, quad, quad && ctx->tune_cov_wave_store != 0, ctx->timeline_stamps(2),
+                                   ctx->tune_kernarg_preload != 0);   // round 15: the same bytes either way, and no path bit (all 32 are taken)
     ctx->path |= GSMVI_PATH_COV_SYM | GSMVI_PATH_GSM_TWO_LAUNCH | ((fold || quad) ? GSMVI_PATH_COV_FOLD_DIAG : 0u) |
                  (s0_last ? GSMVI_PATH_COV_S0_LAST : 0u) | (store_wt ? GSMVI_PATH_COV_STORE_WT : 0u);
     return check_launch("k_gsm_cov_sym(slabs)");

@@ -128,6 +128,8 @@ struct gsmvi_ctx {
     int tune_panel_qm_whole = 0;   // the same route: ONE Qm value per sample from the product's idle slab-1 workgroups (results move at rounding level)
     int tune_panel_stream = 1;     // the same route without whole-sample Qm: a wave of the product loads the part of G it multiplies, in stages along K, and starts each
                                    // stage's MFMAs behind that stage alone (1 or 2: two stages, what ships; 4: four; 0: one batch behind a workgroup barrier; bit-identical results)
+    int tune_kernarg_preload = 1;  // the same route: both launches through the entry points of gsmvi_fast_hot.hip, whose first load batch takes its arguments from
+                                   // preloaded SGPRs (0: the entry points of gsmvi_fast.hip; A/B runs); the same body, bit-identical results
     int tune_gsm_two_launch = 1;   // dense GSM update at B in {16, 32}, D % 256 == 0, D <= 1024 without the per-sample launch (0: three launches; A/B runs)
     int* bam_hint_host = nullptr;       // pinned word: k* of the last device BaM chain (step-count hint, never synchronised on)
     int tune_bam_kenq = 0;     // > 0: enqueue exactly this many multi-workgroup steps (tests of the tail kernel)

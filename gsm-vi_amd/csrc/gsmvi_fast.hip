@@ -75,8 +75,8 @@
 template <int NS>
 __device__ __forceinline__ void panel_stream_chunk(double* As, int D, int nrows, const double* __restrict__ A, int lda, double alpha,
                                                    const double* __restrict__ M, int ldm, const gsmvi_panel_extras& px,
-                                                   unsigned long long* __restrict__ stamps, v4d& acc, double& pq_g, double& pq_x,
-                                                   double& pq_m) {
+                                                   unsigned long long* __restrict__ stamps, const unsigned long long t0, v4d& acc,
+                                                   double& pq_g, double& pq_x, double& pq_m) {
     static_assert(NS == 2 || NS == 4, "stages of the streamed left operand");
     constexpr int LDG = 514;                       // as k_panel_fast<.., 512, ..>
     constexpr int UPR = 32 / NS;                   // 16-B units per row and stage
@@ -140,6 +140,7 @@ __device__ __forceinline__ void panel_stream_chunk(double* As, int D, int nrows,
         const unsigned long long t7 = __builtin_amdgcn_s_memrealtime();
         const unsigned wg = (blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
         if (tid == 0 && wg < GSMVI_STAMP_WG) {
+            stamps[(size_t)wg * 8] = t0;           // the kernel's first instruction (round 15)
             stamps[(size_t)wg * 8 + 1] = t6;       // "left operand staged", as without STREAM: wave 0's last stage
             stamps[(size_t)wg * 8 + 4] = t4;
             stamps[(size_t)wg * 8 + 5] = t5;
@@ -151,20 +152,27 @@ __device__ __forceinline__ void panel_stream_chunk(double* As, int D, int nrows,
 
 template <int MT, bool HAS_SHIFT, int CHW, bool EXTRA, bool RIDER = false, bool RAG = false, bool PART = false, bool QMW = false,
           int STREAM = 0>
-__global__ __launch_bounds__(512) void k_panel_fast(int D, int nrows, const double* __restrict__ A, int lda,
-                                                    const double* __restrict__ shift, double alpha,
-                                                    const double* __restrict__ M, int ldm,
-                                                    double* Pp, int chunks_per_wg, int ncols,
-                                                    unsigned long long* __restrict__ stamps, double* __restrict__ Out,
-                                                    int ldo, const double* __restrict__ addvec, gsmvi_panel_extras px) {
+__device__ __forceinline__ void panel_fast_body(const unsigned long long t0, int D, int nrows, const double* __restrict__ A, int lda,
+                                                const double* __restrict__ shift, double alpha,
+                                                const double* __restrict__ M, int ldm,
+                                                double* Pp, int chunks_per_wg, int ncols,
+                                                unsigned long long* __restrict__ stamps, double* __restrict__ Out,
+                                                int ldo, const double* __restrict__ addvec, const gsmvi_panel_extras& px) {
+    // The body of k_panel_fast and of the preloaded entry points of gsmvi_fast_hot.hip (round 15).  t0 = the clock at the kernel's
+    // first instruction: stamp word 0, written with the first later stamp -- no test of `stamps` stands in front of the loads.
     // timeline diagnostic: a kernel's slot holds GSMVI_STAMP_WG workgroups x 8 words; workgroups beyond it write nothing
+    // (the empty asm keeps the test of `stamps` at the stamp: hoisted out of the chunk loop it stood, with a wait for the argument,
+    // in front of the loads)
 #define PSTAMP(k)                                                                                              \
     do {                                                                                                       \
         const unsigned wg_ = (blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;                   \
-        if (stamps && threadIdx.x == 0 && wg_ < GSMVI_STAMP_WG)                                                \
-            stamps[(size_t)wg_ * 8 + (k)] = __builtin_amdgcn_s_memrealtime();                                  \
+        unsigned long long* sp_ = stamps;                                                                      \
+        asm volatile("" : "+s"(sp_));                                                                          \
+        if (sp_ && threadIdx.x == 0 && wg_ < GSMVI_STAMP_WG) {                                                 \
+            if ((k) == 1) sp_[(size_t)wg_ * 8] = t0;                                                           \
+            sp_[(size_t)wg_ * 8 + (k)] = __builtin_amdgcn_s_memrealtime();                                     \
+        }                                                                                                      \
     } while (0)
-    PSTAMP(0);
     constexpr int LDG = CHW + 2;                   // LDS row stride of the staged A chunk (doubles)
     constexpr int NR = 16 * MT;
     constexpr int RW = CHW / 8;                    // rows of the chunk per wave (8 waves)
@@ -203,7 +211,7 @@ __global__ __launch_bounds__(512) void k_panel_fast(int D, int nrows, const doub
 
     for (int ch = 0; ch < chunks_per_wg; ++ch) {
         if constexpr (STREAM > 0) {        // one chunk per workgroup (the launcher checks it)
-            panel_stream_chunk<STREAM>(As, D, nrows, A, lda, alpha, M, ldm, px, stamps, acc[0], pq_g, pq_x, pq_m);
+            panel_stream_chunk<STREAM>(As, D, nrows, A, lda, alpha, M, ldm, px, stamps, t0, acc[0], pq_g, pq_x, pq_m);
             break;
         }
         const int cbase = (blockIdx.y * chunks_per_wg + ch) * CHW;          // block-uniform
@@ -414,6 +422,19 @@ __global__ __launch_bounds__(512) void k_panel_fast(int D, int nrows, const doub
 #undef PSTAMP
 }
 
+template <int MT, bool HAS_SHIFT, int CHW, bool EXTRA, bool RIDER = false, bool RAG = false, bool PART = false, bool QMW = false,
+          int STREAM = 0>
+__global__ __launch_bounds__(512) void k_panel_fast(int D, int nrows, const double* __restrict__ A, int lda,
+                                                    const double* __restrict__ shift, double alpha,
+                                                    const double* __restrict__ M, int ldm,
+                                                    double* Pp, int chunks_per_wg, int ncols,
+                                                    unsigned long long* __restrict__ stamps, double* __restrict__ Out,
+                                                    int ldo, const double* __restrict__ addvec, gsmvi_panel_extras px) {
+    const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
+    panel_fast_body<MT, HAS_SHIFT, CHW, EXTRA, RIDER, RAG, PART, QMW, STREAM>(t0, D, nrows, A, lda, shift, alpha, M, ldm, Pp, chunks_per_wg,
+                                                                              ncols, stamps, Out, ldo, addvec, px);
+}
+
 // =====================================================================================
 // k_panel_fast with the NEXT chunk's loads in flight (round 6; D >= 2048, rows <= 32, on the grid, plain products).
 // At D = 4096 a workgroup of k_panel_fast walks eight 256-row chunks, and each chunk is a serial chain: issue the loads (64 KB of
@@ -534,8 +555,8 @@ __global__ __launch_bounds__(NT) void k_gsm_scalars_fast(int D, int B, int KC, c
                                                          const double* __restrict__ Pp,
                                                          double* __restrict__ rec, int ldrec,
                                                          unsigned long long* __restrict__ stamps) {
+    const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();   // stamp word 0, written with word 1 (round 15)
     if (blockIdx.x >= GSMVI_STAMP_WG) stamps = nullptr;          // timeline diagnostic: slot capacity
-    if (stamps && threadIdx.x == 0) stamps[(size_t)blockIdx.x * 8] = __builtin_amdgcn_s_memrealtime();
     constexpr int NW = NT / 64;
     __shared__ double lds[2 * NW];
     const int b = blockIdx.x, tid = threadIdx.x;
@@ -565,7 +586,10 @@ __global__ __launch_bounds__(NT) void k_gsm_scalars_fast(int D, int B, int KC, c
             p1 += dd[e] * gv[e];
         }
     }
-    if (stamps && threadIdx.x == 0) stamps[(size_t)blockIdx.x * 8 + 1] = __builtin_amdgcn_s_memrealtime();
+    if (stamps && threadIdx.x == 0) {
+        stamps[(size_t)blockIdx.x * 8] = t0;
+        stamps[(size_t)blockIdx.x * 8 + 1] = __builtin_amdgcn_s_memrealtime();
+    }
     p0 = wave_sum(p0);
     p1 = wave_sum(p1);
     const int w = tid >> 6;
@@ -773,17 +797,22 @@ __device__ __forceinline__ void gsm_cov_wave_mirror(const double* PB, [[maybe_un
     } while (0)
 
 template <int SB, int KCT, bool S0L, bool WT, bool WST = false>
-__device__ __forceinline__ void gsm_cov_quad(double* __restrict__ smem, int p, int D, int B, double invB, const double* __restrict__ mu0,
-                                             const double* __restrict__ S0, int lds0, double* __restrict__ S, int lds,
-                                             double* __restrict__ mu_out, unsigned long long* __restrict__ stamps, const gsm_slab_src& fs) {
-#define QBARRIER()                                                                        \
+__device__ __forceinline__ void gsm_cov_quad(double* __restrict__ smem, int p, int D, int B, const double& invB, const double* __restrict__ mu0,
+                                             const double* __restrict__ S0, int lds0, double* __restrict__ const& S, const int& lds,
+                                             double* __restrict__ const& mu_out, unsigned long long* __restrict__ const& stamps,
+                                             const unsigned long long t0, const gsm_slab_src& fs) {
+    // (invB, S, lds, mu_out, stamps by reference: as gsm_cov_sym_body takes them)
+#define QBARRIER()                                                                       \
     do {                                                                                  \
         if constexpr (S0L) asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); \
         else __syncthreads();                                                             \
     } while (0)
 #define QSTAMP(k)                                                                         \
     do {                                                                                  \
-        if (stamps && threadIdx.x == 0) stamps[(size_t)blockIdx.x * 8 + (k)] = __builtin_amdgcn_s_memrealtime(); \
+        if (stamps && threadIdx.x == 0) {                                                 \
+            if ((k) == 1) stamps[(size_t)blockIdx.x * 8] = t0;                            \
+            stamps[(size_t)blockIdx.x * 8 + (k)] = __builtin_amdgcn_s_memrealtime();      \
+        }                                                                                 \
     } while (0)
     constexpr int RS = 48, TILE = SB * RS, NU = SB * 16, NS = SB / 4, NQG = 2 * KCT;
     constexpr int LWS = 32 * 33, MUO = 3 * LWS, PAO = MUO + 2 * SB * 32, SCO = COV_QUAD_SCR<SB>;
@@ -1137,12 +1166,16 @@ __device__ __forceinline__ void gsm_cov_quad(double* __restrict__ smem, int p, i
 
 template <int SB, bool RAG, bool FROM_SLABS = false, int KCT = 4, bool FOLD = false, bool S0L = false, bool WT = false, bool QMW = false, bool QUAD = false,
           bool WST = false>
-__global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(FROM_SLABS && !(WST && SB == 32) ? 4 : 2))) void k_gsm_cov_sym(int D, int B, double invB, const double* __restrict__ rec, int ldrec,
-                                                     const double* __restrict__ mu0,
-                                                     const double* __restrict__ S0, int lds0,
-                                                     double* __restrict__ S, int lds,
-                                                     double* __restrict__ mu_out, int dbg,
-                                                     unsigned long long* __restrict__ stamps, gsm_slab_src fs) {
+__device__ __forceinline__ void gsm_cov_sym_body(const unsigned long long t0, int D, int B, const double& invB, const double* __restrict__ rec, int ldrec,
+                                                 const double* __restrict__ mu0,
+                                                 const double* __restrict__ S0, int lds0,
+                                                 double* __restrict__ const& S, const int& lds,
+                                                 double* __restrict__ const& mu_out, int dbg,
+                                                 unsigned long long* __restrict__ const& stamps_arg, const gsm_slab_src& fs) {
+    // The body of k_gsm_cov_sym and of the preloaded entry points of gsmvi_fast_hot.hip (round 15).  t0 = the clock at the kernel's
+    // first instruction: stamp word 0, written with stamp 1.  What no load of the first batch needs -- 1 / B, the outputs, the stamps --
+    // comes by reference: k_gsm_cov_sym passes its own parameters (values, as before), a preloaded entry point members of a by-value
+    // struct behind its hot block, which are then fetched where they are first used and not in front of the loads.
     static_assert(!FOLD || FROM_SLABS, "folded diagonal tiles: the two-launch form only");
     static_assert(!(S0L || WT || QMW) || (FROM_SLABS && KCT == 2 && !RAG), "S0 last / write-through stores / whole-sample Qm: the two-slab two-launch form only, on the grid");
     static_assert(!QUAD || (FROM_SLABS && !FOLD && !QMW && !RAG && (SB == 16 || SB == 32)), "quads: the two-launch form, in place of the fold");
@@ -1155,14 +1188,19 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(FROM_SLABS 
     } while (0)
 #define STAMP(k)                                                                          \
     do {                                                                                  \
-        if (stamps && threadIdx.x == 0) stamps[(size_t)blockIdx.x * 8 + (k)] = __builtin_amdgcn_s_memrealtime(); \
+        if (stamps && threadIdx.x == 0) {                                                 \
+            if ((k) == 1) stamps[(size_t)blockIdx.x * 8] = t0;                            \
+            stamps[(size_t)blockIdx.x * 8 + (k)] = __builtin_amdgcn_s_memrealtime();      \
+        }                                                                                 \
     } while (0)
     // (Round 4 tried LDS-only barriers here -- s_waitcnt lgkmcnt(0); s_barrier instead of __syncthreads(), whose workgroup fence
     // also drains the vector-memory counter: 6.45 against 6.38 us at D = 1024, B = 32, no effect; they matter in the persistent
     // form below, where loads of the next item are in flight across the barriers.)
-    if (blockIdx.x >= GSMVI_STAMP_WG) stamps = nullptr;          // timeline diagnostic: slot capacity (D >= 2048 has more workgroups)
-    STAMP(0);
-    constexpr int RS = 48;                       // LDS row stride (doubles): 32 columns + 16 pad
+    // timeline diagnostic: slot capacity (D >= 2048 has more workgroups; the two-launch form has D <= 1024, at most 272 workgroups,
+    // and no use of `stamps` in front of its loads)
+    unsigned long long* const stamps_slot = (!FROM_SLABS && blockIdx.x < GSMVI_STAMP_WG) ? stamps_arg : nullptr;
+    unsigned long long* __restrict__ const& stamps = FROM_SLABS ? stamps_arg : stamps_slot;
+    constexpr int RS = 48;                      // LDS row stride (doubles): 32 columns + 16 pad
     constexpr int NPASS = (SB > 32) ? SB / 32 : 1;   // samples are staged 32 at a time: <= 74 KB of LDS, so
     constexpr int SBP = SB / NPASS;              //   two workgroups fit per CU also at B = 64
     constexpr int TILE = SBP * RS;               // one staged tile (per pass)
@@ -1187,7 +1225,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(FROM_SLABS 
     int fold = 0;                                                // FOLD: 1 = hosts the diagonal tile of its own row, 2 = that of the last row
     if constexpr (QUAD) {                                        // quads first (gsm_cov_quad above), then the pairs right of them
         if ((int)blockIdx.x < (nt >> 1)) {
-            gsm_cov_quad<SB, KCT, S0L, WT, WST>(smem, blockIdx.x, D, B, invB, mu0, S0, lds0, S, lds, mu_out, stamps, fs);
+            gsm_cov_quad<SB, KCT, S0L, WT, WST>(smem, blockIdx.x, D, B, invB, mu0, S0, lds0, S, lds, mu_out, stamps, t0, fs);
             return;
         }
         int rem = blockIdx.x - (nt >> 1);
@@ -1617,6 +1655,18 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(FROM_SLABS 
 #undef PRE_W_BARRIER
 }
 
+template <int SB, bool RAG, bool FROM_SLABS = false, int KCT = 4, bool FOLD = false, bool S0L = false, bool WT = false, bool QMW = false, bool QUAD = false,
+          bool WST = false>
+__global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(FROM_SLABS && !(WST && SB == 32) ? 4 : 2))) void k_gsm_cov_sym(int D, int B, double invB, const double* __restrict__ rec, int ldrec,
+                                                     const double* __restrict__ mu0,
+                                                     const double* __restrict__ S0, int lds0,
+                                                     double* __restrict__ S, int lds,
+                                                     double* __restrict__ mu_out, int dbg,
+                                                     unsigned long long* __restrict__ stamps, gsm_slab_src fs) {
+    const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
+    gsm_cov_sym_body<SB, RAG, FROM_SLABS, KCT, FOLD, S0L, WT, QMW, QUAD, WST>(t0, D, B, invB, rec, ldrec, mu0, S0, lds0, S, lds, mu_out, dbg, stamps, fs);
+}
+
 // =====================================================================================
 // PERSISTENT form of k_gsm_cov_sym for large D (round 4).  Same tiles, same arithmetic, same results bit for bit: a work ITEM
 // is what one workgroup of k_gsm_cov_sym does (row block I of 32 rows x two adjacent column tiles, or a lone diagonal tile).
@@ -1822,6 +1872,9 @@ __global__ __launch_bounds__(512) void k_gsm_cov_sym_p(int D, int B, double invB
     }
 }
 
+// gsmvi_fast_hot.hip includes this file for the templates above (the shared bodies) and stops here: the kernel and the launch
+// helpers below belong to this translation unit alone.
+#ifndef GSMVI_FAST_BODIES_ONLY
 // =====================================================================================
 // k_gsm_cov_sym for ANY batch size (round 6; until then B <= 128 only and B = 130 fell to the guarded kernel of
 // gsmvi_kernels.hip).  Same items, same tile layout, same store path as k_gsm_cov_sym; the samples come in a RUN-TIME loop of
@@ -2040,10 +2093,25 @@ void gsmvi_launch_panel_fast(hipStream_t st, hipEvent_t* ev, int MT, dim3 grid, 
 // 2 D / 16 Qg partials per sample, and B = 32 still fills 256 workgroups.  The two sample halves of a (strip, slab) read the
 // same S0 rows; their linear ids differ by 128, the same XCD, and the second read is served from its L2 (DESIGN 8.1, round 8:
 // the MT = 2 form on 128 workgroups staged 128 KB per workgroup and was 2 us slower per launch).
-void gsmvi_launch_panel_fast_part(hipStream_t st, hipEvent_t* ev, dim3 grid, int D, int B, const double* G, int ldg,
+// preload (round 15, knob "kernarg_preload"): the entry points of gsmvi_fast_hot.hip, whose first load batch takes its arguments from
+// preloaded SGPRs, where they cover the form; returns whether they ran.  The same body, the same bytes.
+bool gsmvi_launch_panel_part_hot(hipStream_t st, hipEvent_t* ev, dim3 grid, int D, int B, const double* G, int ldg, const double* S0,
+                                 int lds0, double* Pp, int chunks_per_wg, const double* X, int ldx, const double* mu0, double* Qg,
+                                 double* Qm, int chw, int stream, unsigned long long* stamps);
+bool gsmvi_launch_gsm_cov_slabs_hot(hipStream_t st, hipEvent_t* ev, dim3 grid, int D, int B, const gsm_slab_src& fs, const double* mu0,
+                                    const double* S0, int lds0, double* S, int lds, double* mu_out, int kct, bool fold, bool quad,
+                                    bool wave_store, unsigned long long* stamps);
+
+bool gsmvi_launch_panel_fast_part(hipStream_t st, hipEvent_t* ev, dim3 grid, int D, int B, const double* G, int ldg,
                                   const double* S0, int lds0, double* Pp, int chunks_per_wg, const double* X, int ldx,
                                   const double* mu0, double* Qg, double* Qm, int chw, bool qm_whole, int stream,
-                                  unsigned long long* stamps) {
+                                  unsigned long long* stamps, bool preload) {
+    if (preload && !(chw == 512 && qm_whole)) {    // the instance the chain below would pick, behind the preloaded entry point
+        const bool streamed = chw == 512 && stream != 0 && chunks_per_wg == 1 && D == 512 * (int)grid.y && B % 16 == 0;
+        const int inst = streamed ? (stream == 4 ? 4 : 2) : ((chw == 512 && stamps != nullptr && chunks_per_wg == 1) ? -1 : 0);
+        if (gsmvi_launch_panel_part_hot(st, ev, grid, D, B, G, ldg, S0, lds0, Pp, chunks_per_wg, X, ldx, mu0, Qg, Qm, chw, inst, stamps))
+            return true;
+    }
     gsmvi_panel_extras px;                     // (PART's arguments ride in free members: gsmvi_ctx.h)
     px.sj_src = X;
     px.sj_len = ldx;
@@ -2066,6 +2134,7 @@ void gsmvi_launch_panel_fast_part(hipStream_t st, hipEvent_t* ev, dim3 grid, int
     } else if (chw == 512) PFQ(1, 512);
     else { if (B == 16) PFQ(1, 256); else PFQ(2, 256); }
 #undef PFQ
+    return false;
 }
 
 // column width of one staged chunk for a given MT (the ABI's chunk arithmetic must agree)
@@ -2160,10 +2229,16 @@ bool gsmvi_launch_gsm_cov_sym(hipStream_t st, hipEvent_t* ev, int D, int B, cons
 // KC <= 4, even leading dimensions, 16-byte aligned bases).  Same grid as above.  kct = 2: the instance compiled for exactly two
 // slabs (the caller's product ran the 512-row split: fs.KC == 2, D == 1024); kct = 4: any KC <= 4.
 // fold (round 9): the grid is the two-tile workgroups alone, the diagonal leftovers are third tiles of their hosts (FOLD above).
-void gsmvi_launch_gsm_cov_sym_slabs(hipStream_t st, hipEvent_t* ev, int D, int B, const gsm_slab_src& fs, const double* mu0,
+// preload: as gsmvi_launch_panel_fast_part (the quad map only); returns whether the preloaded entry point ran.
+bool gsmvi_launch_gsm_cov_sym_slabs(hipStream_t st, hipEvent_t* ev, int D, int B, const gsm_slab_src& fs, const double* mu0,
                                     const double* S0, int lds0, double* S, int lds, double* mu_out, int kct, bool fold,
-                                    bool s0_last, bool store_wt, bool qm_whole, bool quad, bool wave_store, unsigned long long* stamps) {
+                                    bool s0_last, bool store_wt, bool qm_whole, bool quad, bool wave_store, unsigned long long* stamps,
+                                    bool preload) {
     const double invB = 1.0 / (double)B;
+    if (preload && !qm_whole &&
+        gsmvi_launch_gsm_cov_slabs_hot(st, ev, dim3(quad ? cov_sym_quad_grid(D / 32) : (fold ? gsmvi_cov_sym_pairs(D / 32) : cov_sym_grid(D / 32))),
+                                       D, B, fs, mu0, S0, lds0, S, lds, mu_out, kct, fold, quad, wave_store, stamps))
+        return true;
     // quad (round 13; the caller passes it for the shipped two-slab form -- S0 last, write-through stores, per-strip Qm -- and for
     // the plain kct = 4 form only): the quad / pair map, (nt / 2)^2 workgroups
     if (quad) {
@@ -2177,7 +2252,7 @@ void gsmvi_launch_gsm_cov_sym_slabs(hipStream_t st, hipEvent_t* ev, int D, int B
         else { if (B == 16) CSD(16, 4, false, false); else CSD(32, 4, false, false); }
 #undef CSD
 #undef CSE
-        return;
+        return false;
     }
     const dim3 grid(fold ? gsmvi_cov_sym_pairs(D / 32) : cov_sym_grid(D / 32));
 #define CSQ(SBV, KV, FV, LV, WV, QV)                                                                                      \
@@ -2200,4 +2275,6 @@ void gsmvi_launch_gsm_cov_sym_slabs(hipStream_t st, hipEvent_t* ev, int D, int B
 #undef CSF
 #undef CSS
 #undef CSQ
+    return false;
 }
+#endif   // GSMVI_FAST_BODIES_ONLY

@@ -135,6 +135,10 @@ int gsmvi_destroy(gsmvi_ctx* ctx);
  * Sigma0 + U for the 16 x 16 block it computed, stores it and mirrors it through a wave-private LDS buffer, with no workgroup
  * barrier behind the MFMAs, default; 0 = the store path through shared LDS buffers and three barriers; bit-identical results,
  * no path bit);
+ * round 15: "kernarg_preload" (both launches of the two-launch form: 1 = entry points whose argument block begins with the 14
+ * dwords that the first load batch takes, delivered in SGPRs with the wave (gfx950 kernel-argument preload; firmware without it
+ * runs an equivalent prologue), the remaining arguments fetched behind the first vector loads, default; 0 = the entry points with
+ * the ordinary argument block; the same kernel bodies, bit-identical results, no path bit: all 32 are taken);
  * diagnostics "timeline", "cov_dbg"
  * (see gsmvi_hip_debug.h). */
 int gsmvi_set_tuning(gsmvi_ctx* ctx, const char* name, int value);
