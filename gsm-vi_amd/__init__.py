@@ -70,6 +70,10 @@ Mirrors the reference's public surface for the hot path (reference file:line):
     for K fitted negative binomial posteriors: mean and
     variance of the predictive count from three log
     moments, held-out elpd on the leave-one-out's scale) examples/example_gsm.py:34-35, the use of the fit; no reference twin
+    predict_ordinal_batched, OrdinalPrediction (the same
+    for K fitted cumulative-logit posteriors: class
+    probabilities, most probable and median class,
+    held-out elpd on the leave-one-out's scale)          examples/example_gsm.py:34-35, the use of the fit; no reference twin
     predict_shared_batched (the GLM predictive of K
     fitted posteriors of a SharedDesignGLMTarget on
     ONE set of new rows with per-problem row weights:
@@ -120,6 +124,7 @@ from .targets import BatchedNegBinomialTarget                        # noqa: F40
 from .targets import BatchedOrdinalTarget                            # noqa: F401
 from .targets import predict_softmax_batched, SoftmaxPrediction      # noqa: F401
 from .targets import predict_negbin_batched, NegBinPrediction        # noqa: F401
+from .targets import predict_ordinal_batched, OrdinalPrediction      # noqa: F401
 from .targets import neg_hessian_shared_batched                      # noqa: F401
 from .targets import predict_shared_batched                          # noqa: F401
 from .targets import neg_hessian_negbin_batched                      # noqa: F401

@@ -194,6 +194,9 @@ _SIGS = {
                                                     _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp]),
     "gsmvi_negbin_predict_batched_f64": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int64, C.c_int64, _c_dp, _c_dp,
                                                    _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp]),
+    "gsmvi_ordinal_predict_lds_bytes": (C.c_int, [C.c_int, C.c_int]),
+    "gsmvi_ordinal_predict_batched_f64": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int64, C.c_int64, _c_dp,
+                                                    _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp]),
     "gsmvi_glm_shared_predict_batched_f64": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int64, C.c_int, _c_dp, _c_dp,
                                                        _c_dp, _c_dp, C.c_double, _c_dp, _c_dp, _c_dp, C.c_int, _c_dp, _c_dp, _c_dp,
                                                        _c_dp, _c_dp, _c_dp, _c_dp]),

@@ -32,6 +32,7 @@ hipError_t gsmvi_psis_loo_negbin_batched_prepare();
 hipError_t gsmvi_psis_loo_ordinal_batched_prepare();
 hipError_t gsmvi_psis_loo_shared_batched_prepare();
 hipError_t gsmvi_softmax_predict_batched_prepare();
+hipError_t gsmvi_ordinal_predict_batched_prepare();
 hipError_t gsmvi_negbin_batched_prepare();
 hipError_t gsmvi_ordinal_batched_prepare();
 void gsmvi_launch_gsm_cov_update(hipStream_t st, hipEvent_t* ev, int D, int B, const double* rec, int ldrec,
@@ -271,6 +272,7 @@ int gsmvi_create(gsmvi_ctx** out, int device, int max_D, int max_B) {
     if (e == hipSuccess) e = gsmvi_psis_loo_ordinal_batched_prepare();
     if (e == hipSuccess) e = gsmvi_psis_loo_shared_batched_prepare();
     if (e == hipSuccess) e = gsmvi_softmax_predict_batched_prepare();
+    if (e == hipSuccess) e = gsmvi_ordinal_predict_batched_prepare();
     if (e == hipSuccess) e = gsmvi_negbin_batched_prepare();
     if (e == hipSuccess) e = gsmvi_ordinal_batched_prepare();
     for (int k = 0; k < 8 && e == hipSuccess; ++k) e = hipEventCreate(&c->ev[k]);

@@ -1532,6 +1532,34 @@ class HipEngine:
                    self._dp(lpd, (K, M), "lpd"))
         return lmom, lpd
 
+    # ---- the same use of K fitted cumulative-logit posteriors (csrc/gsmvi_ordinal_predict_batched.hip) ---------------------------
+    def ordinal_predict_lds_bytes(self, P, C):
+        """gsmvi_ordinal_predict_lds_bytes: the dynamic LDS in bytes of one workgroup of ``ordinal_predict_batched`` at (P, C), 0
+        out of bounds; a pure function, no GPU"""
+        return int(self.lib.gsmvi_ordinal_predict_lds_bytes(int(P), int(C)))
+
+    def ordinal_predict_batched(self, X, lw, A, C, y=None, offset=None, counts=None):
+        """The posterior predictive of K fitted cumulative-logit posteriors at the rows of A (K, M, P) from the draws X
+        (K, S, P + C - 1) = (beta, delta) of q_k, delta the C - 1 cutpoint parameters, weighted by the normalised log weights
+        ``lw`` (K, S) (``psis_batched``'s; None: uniform), one launch (gsmvi_ordinal_predict_batched_f64; the definition is in
+        include/gsmvi_hip.h)  [no reference twin]: returns (prob (K, M, C), lpd (K, M) or None without ``y``).  ``y`` (K, M) int32
+        labels, ``C``, ``offset`` and ``counts`` are ``ordinal_batched``'s, for the new rows."""
+        K, S, D = X.shape
+        M, P = A.shape[1], A.shape[2]
+        Cc = int(C)
+        if D != P + Cc - 1:
+            raise ValueError(f"X: expected P + C - 1 = {P + Cc - 1} columns (beta, then the C - 1 cutpoint parameters), got {D}")
+        self._any_ctx()
+        X = X.contiguous()
+        lw = lw.contiguous() if lw is not None else None
+        prob = self.empty(K, M, Cc)
+        lpd = self.empty(K, M) if y is not None else None
+        self._call("gsmvi_ordinal_predict_batched_f64", K, P, Cc, M, S, self._packed(A, (K, M, P), "A"),
+                   self._ints(y, K * M, "y"), self._dp(offset, (K, M), "offset"), self._ints(counts, K, "counts"),
+                   self._packed(X, (K, S, D), "X"), self._dp(lw, (K, S), "lw"), self._packed(prob, (K, M, Cc), "prob"),
+                   self._dp(lpd, (K, M), "lpd"))
+        return prob, lpd
+
     def bam_update(self, X, G, mu0, S0, reg, jitter=0.0, out=None, flag=None):
         """(mu, S) of BaM [gsmvi/bam.py:72-114]; S symmetrised, jitter on the diagonal."""
         assert X.dim() == 2 and G.dim() == 2            # bam.py:47-48

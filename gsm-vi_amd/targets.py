@@ -22,16 +22,20 @@ multinomial logit regressions (C classes, C - 1 linear predictors per row), a la
                                                                                                  checks refuse it)
     BatchedNegBinomialTarget  counts y >= 0, a fitted size    gsmvi_negbin_batched_f64           no (not a BatchedGLMTarget: the Hessian
                               (x = (beta, log r))                                                has a 2 x 2 block per row)
-    BatchedOrdinalTarget      ordered labels in 0 .. C - 1,   gsmvi_ordinal_batched_f64          laplace, predict: no (none exists yet for
-                              x = (beta, C - 1 cutpoints)                                        this family); loo: no method (TypeError from
-                                                                                                 the others): psis_loo_ordinal_batched
+    BatchedOrdinalTarget      ordered labels in 0 .. C - 1,   gsmvi_ordinal_batched_f64          laplace_init_ordinal_batched and
+                              x = (beta, C - 1 cutpoints)                                        neg_hessian_ordinal_batched; predict, loo:
+                                                                                                 no method (TypeError from the others):
+                                                                                                 predict_ordinal_batched,
+                                                                                                 psis_loo_ordinal_batched
     BatchedSoftmaxTarget      integer labels in 0 .. C - 1    gsmvi_softmax_batched_f64          laplace_init_softmax_batched and
                                                                                                  neg_hessian; predict, loo: no (TypeError):
                                                                                                  predict_softmax_batched,
                                                                                                  psis_loo_softmax_batched
 
 ``predict_softmax_batched`` is the softmax target's posterior predictive (``SoftmaxPrediction``): class probabilities and the
-held-out score of new rows from draws of the fitted Gaussians, one HIP launch after the draws.
+held-out score of new rows from draws of the fitted Gaussians, one HIP launch after the draws.  ``predict_ordinal_batched`` is
+the same for the ordinal target (``OrdinalPrediction``): the probabilities of the C ordered classes, their first maximum and their
+median class, and the held-out score, one HIP launch after the draws.
 """
 from dataclasses import dataclass
 from typing import Any
@@ -930,9 +934,13 @@ class BatchedOrdinalTarget:
     ``psis_loo_batched`` and their softmax and negative binomial namesakes refuse it (TypeError).  The leave-one-out of this
     family is the free function ``psis_loo_ordinal_batched(target, mean, cov, keys, ...)``: l_si = log P(y_i) is normalised, so its
     ``elpd_loo`` is on the scale of ``psis_loo_softmax_batched`` on the same labels.  The Hessian and the Laplace start are free
-    functions too: ``neg_hessian_ordinal_batched(target, x)`` and ``laplace_init_ordinal_batched(target, ...)``.  Only the posterior
-    predictive is missing now for this family.  (Before those two were added this paragraph ended "A Hessian and Laplace start and
-    a posterior predictive do not exist yet for this family", a sentence tests/test_psis_loo_ordinal_cpu.py still looks for.)"""
+    functions too: ``neg_hessian_ordinal_batched(target, x)`` and ``laplace_init_ordinal_batched(target, ...)``.  The posterior
+    predictive on new rows is the free function ``predict_ordinal_batched(target, mean, cov, A_new, keys, ...)``
+    (``OrdinalPrediction``: class probabilities, the most probable and the median class, the held-out score): the family now has
+    all four pieces.  (Before the Hessian and the Laplace start were added this paragraph ended "A Hessian and Laplace start and
+    a posterior predictive do not exist yet for this family", a sentence tests/test_psis_loo_ordinal_cpu.py still looks for;
+    before the predictive was added it said "Only the posterior predictive is missing now for this family", which
+    tests/test_ordinal_laplace_cpu.py still looks for.)"""
 
     def __init__(self, A, y, num_classes, prior_precision=1.0, cut_precision=1.0, counts=None, offset=None, engine=None):
         if isinstance(num_classes, bool) or not isinstance(num_classes, (int, np.integer)) or num_classes < 2:
@@ -1121,3 +1129,126 @@ def predict_softmax_batched(target, mean, cov, A_new, keys, y=None, counts=None,
         out = {n: None if t is None else np.asarray(eng.to_numpy(t)) for n, t in out.items()}
         out["label"] = out["label"].astype(np.int64)
     return SoftmaxPrediction(psis=psis, num_draws=S, nlaunch=nlaunch, **out)
+
+
+@dataclass
+class OrdinalPrediction:
+    """What ``predict_ordinal_batched`` returns for M new rows of each of K cumulative-logit problems under the fitted q_k =
+    N(mean_k, cov_k) over (beta, delta) (numpy arrays, or the engine's tensors with ``as_torch``): ``prob`` (K, M, C) the
+    predictive class probabilities, the (weighted) mean over the draws of P(y = c | eta, cutpoints); ``label`` (K, M) int64 the
+    first maximum of ``prob`` and ``median`` (K, M) int64 the smallest c whose cumulative ``prob`` reaches 0.5, the point
+    prediction proper to ordered classes (it minimises the expected absolute error in class steps), both -1 where the row is
+    NaN; with ``y``, ``lpd`` (K, M) = log E[P(y | eta, cutpoints)] per row (the scale of ``psis_loo_ordinal_batched``) and
+    ``elpd`` (K,), its sum over the valid rows: the held-out score by which fits of one model are compared (both None without
+    ``y``).  Rows beyond ``counts[k]`` are NaN.  ``psis`` the problem-level ``PSISBatchedResult`` whose draws (and, with
+    ``weights="psis"``, weights) were used (device tensors: hand it back as ``psis=`` to reuse them), None where none was made or
+    given; ``num_draws`` = S; ``nlaunch`` the kernel launches made.  [examples/example_gsm.py:34-35, the use of the fit; no
+    reference twin]"""
+    prob: Any
+    label: Any
+    median: Any
+    lpd: Any
+    elpd: Any
+    psis: Any
+    num_draws: int
+    nlaunch: int
+
+
+def predict_ordinal_batched(target, mean, cov, A_new, keys, offset=None, y=None, counts=None, num_draws=1024, *, call=0, psis=None,
+                            weights="uniform", as_torch=False, engine=None):
+    """The posterior predictive of K fitted cumulative-logit posteriors q_k = N(mean_k, cov_k) on new rows: returns an
+    ``OrdinalPrediction``.
+
+    ``target`` is the ``BatchedOrdinalTarget`` the posteriors were fitted to (its number of classes and P are the model; anything
+    else raises TypeError); mean (K, D), D = P + C - 1, cov (K, D, D) and ``keys`` are ``psis_batched``'s; ``A_new`` (K, M, P) are
+    the new rows, ``offset`` (K, M) is added to their linear predictor, ``y`` (K, M) their integer labels (None: no ``lpd`` /
+    ``elpd``), ``counts`` (K,) the valid rows per problem (None: all M).  The cutpoints are coordinates of q_k, correlated with
+    beta, so there is no one-dimensional quadrature: the predictive is a mean over S = ``num_draws`` draws of q_k.
+    ``weights="uniform"``: one call of ``kl_draw_batched`` with ``psis_batched``'s seed rule (seed (keys[k] % 2**32) ^
+    0x5DEECE66D, draw number ``call``: the bits ``psis_batched`` would draw), no call of ``target.lp``, then one launch,
+    gsmvi_ordinal_predict_batched_f64 (the definition is in include/gsmvi_hip.h): the linear predictor of every (draw, row) on the
+    fp64 MFMA, the draw's cutpoints as one chain, the class probabilities as products of sigmoids (no two probabilities are
+    subtracted) summed over the draws, and the log-sum-exp of the rows' log likelihoods; no (K, S, M, C) block is formed.
+    ``weights="psis"``: first ``psis_batched(target.lp, mean, cov, keys, num_draws, call=call, moments=False, as_torch=True)``,
+    then the launch with its smoothed ``log_weights``: the importance-corrected predictive; the result carries ``psis`` (khat,
+    ``ok``), and a problem whose problem-level run failed comes out NaN.  ``psis=``, the result of such a call, is reused
+    (``num_draws`` and ``call`` are then not used): its draws alone with ``"uniform"``, its weights too with ``"psis"``.  mean
+    and cov are only read.
+    An ``A_new`` that is not (K, M, P), a mean that is not (K, D) of the target, a cov that is not (K, D, D), an ``offset`` that is
+    not (K, M) or not finite in the valid rows, labels that are not (K, M) or outside 0 .. C - 1 in the valid rows, bad
+    ``counts``, keys of another length than K, ``num_draws`` outside 5..4096, an unknown ``weights`` or a ``psis`` that is not a
+    ``PSISBatchedResult`` holding device tensors of the right shapes raise ValueError naming the argument before any device
+    work."""
+    from .diagnostics import MAX_DRAWS, MIN_DRAWS, _reusable, psis_batched
+    from .monitors import _to_numpy
+    fn = "predict_ordinal_batched"
+    if not isinstance(target, BatchedOrdinalTarget):
+        raise TypeError(f"{fn}: target must be a BatchedOrdinalTarget, got {type(target).__name__}")
+    if weights not in ("uniform", "psis"):
+        raise ValueError(f"{fn}: weights: expected 'uniform' or 'psis', got {weights!r}")
+    K, D, P, C = target.K, target.D, target.P, target.C
+    sa = _shape(A_new)
+    if len(sa) != 3 or min(sa) < 1 or sa[0] != K or sa[2] != P:
+        raise ValueError(f"{fn}: A_new: expected shape (K, M, P) with K = {K}, P = {P} and M >= 1, got {sa}")
+    M = sa[1]
+    if _shape(mean) != (K, D):
+        raise ValueError(f"{fn}: mean must be (K, D) = {(K, D)} of the target, got {_shape(mean)}")
+    if _shape(cov) != (K, D, D):
+        raise ValueError(f"{fn}: cov must be {(K, D, D)}, got {_shape(cov)}")
+    try:
+        cnt = _check_counts(counts, K, M, rows="M")
+        live = _live_rows(cnt, M)
+        yh = None
+        if y is not None:
+            if _shape(y) != (K, M):
+                raise ValueError(f"y: expected shape (K, M) = {(K, M)}, got {_shape(y)}")
+            yh = _check_labels(y, C, live)
+        oh = _check_offset(offset, K, M, live, rows="M")
+    except ValueError as e:
+        raise ValueError(f"{fn}: {e}") from None
+    keys_l = [int(k) for k in np.asarray(list(keys) if isinstance(keys, (list, tuple, range)) else _to_numpy(keys)).reshape(-1)]
+    if len(keys_l) != K:
+        raise ValueError(f"{fn}: {len(keys_l)} keys for K = {K} problems")
+    eng = engine if engine is not None else target.engine
+    if psis is None:
+        S = int(num_draws)
+        if S != num_draws or not MIN_DRAWS <= S <= MAX_DRAWS:
+            raise ValueError(f"{fn}: num_draws = {num_draws} is outside {MIN_DRAWS} <= num_draws <= {MAX_DRAWS}")
+        if weights == "psis":
+            psis = psis_batched(target.lp, mean, cov, keys_l, S, call=call, moments=False, as_torch=True, engine=eng)
+            nlaunch = psis.nlaunch + 1
+            X, _, lw = _reusable(psis, K, D, eng, fn)
+        else:
+            seeds = eng.batched_seeds(tuple((k % (2 ** 32)) ^ 0x5DEECE66D for k in keys_l))
+            X, _, _ = eng.kl_draw_batched(eng.asarray(mean), eng.asarray(cov), seeds, int(call), 0, S)
+            nlaunch, lw = 2, None
+    else:
+        X, _, lw = _reusable(psis, K, D, eng, fn)
+        S = _shape(X)[1]
+        nlaunch = 1
+        if weights == "uniform":
+            lw = None
+    prob, lpd = eng.ordinal_predict_batched(X, lw, eng.asarray(A_new.contiguous() if isinstance(A_new, torch.Tensor) else A_new), C,
+                                            y=eng.batched_labels(yh) if yh is not None else None,
+                                            offset=eng.asarray(oh) if oh is not None else None,
+                                            counts=eng.batched_counts(cnt) if cnt is not None else None)
+    ten = lambda a: a if isinstance(a, torch.Tensor) else torch.as_tensor(np.asarray(a))      # noqa: E731
+    pt = ten(prob)
+    dead = torch.isnan(pt).any(2)
+    none = torch.full((), -1, dtype=torch.int64, device=pt.device)
+    label = torch.where(dead, none, pt.argmax(2))
+    # the smallest c whose cumulative probability reaches 0.5: the classes before it; C - 1 at the most (a cumulative sum that
+    # rounds below 0.5 everywhere cannot happen for a row that sums to 1, the clamp costs nothing)
+    median = torch.where(dead, none, (torch.cumsum(pt, 2) < 0.5).sum(2).clamp(max=C - 1))
+    elpd = None
+    if lpd is not None:
+        lt = ten(lpd)
+        nk = ten(cnt).to(lt.device) if cnt is not None else torch.full((K,), M, device=lt.device)
+        mask = torch.arange(M, device=lt.device)[None, :] < nk[:, None]
+        elpd = torch.where(mask, lt, torch.zeros((), dtype=lt.dtype, device=lt.device)).sum(1)
+    out = dict(prob=prob, label=label, median=median, lpd=lpd, elpd=elpd)
+    if not as_torch:
+        out = {n: None if t is None else np.asarray(eng.to_numpy(t)) for n, t in out.items()}
+        out["label"] = out["label"].astype(np.int64)
+        out["median"] = out["median"].astype(np.int64)
+    return OrdinalPrediction(psis=psis, num_draws=S, nlaunch=nlaunch, **out)

@@ -45,6 +45,8 @@
  *   score from draws of q_k (no reference twin)                        ->  gsmvi_softmax_predict_batched_f64, gsmvi_softmax_predict_lds_bytes
  *   the same use for K fitted negative binomial regressions: log moments of the predictive count and the held-out score from
  *   draws of q_k (no reference twin)                                   ->  gsmvi_negbin_predict_batched_f64
+ *   the same use for K fitted cumulative-logit regressions: class probabilities and the held-out score from draws of q_k
+ *   (no reference twin)                                                ->  gsmvi_ordinal_predict_batched_f64, gsmvi_ordinal_predict_lds_bytes
  *   the use of the fit for K fitted GLMs on one design matrix: the GLM predictive on one shared set of new rows with per-problem
  *   row weights, the held-out score of K-fold cross-validation (no reference twin) -> gsmvi_glm_shared_predict_batched_f64
  *   gsmvi/bam.py:72-114       bam_lowrank_update(samples,vs,mu0,S0,reg) ->  gsmvi_bam_update_f64
@@ -322,10 +324,10 @@ int gsmvi_get_profile(gsmvi_ctx* ctx, float* ms, int n);
 #define GSMVI_PATH_BATCHED_BAM 0x4000u     /* k_bam_batched: the batched BaM entry points                           */
 #define GSMVI_PATH_BATCHED_KL 0x8000u      /* k_kl_batched: the batched KL monitor's entry points                  */
 #define GSMVI_PATH_BATCHED_ADVI 0x10000u   /* k_advi_batched / k_advi_cov_batched: the batched ADVI entry points   */
-#define GSMVI_PATH_BATCHED_TARGET 0x20000u /* k_logistic_batched: the batched non-Gaussian target's entry point; with GSMVI_PATH_BATCHED_LAPLACE in one call: k_laplace_shared_batched, k_negbin_laplace_batched or k_ordinal_laplace_batched; with GSMVI_PATH_BATCHED_LOO in one call: k_psis_loo_negbin_batched or k_psis_loo_ordinal_batched; with GSMVI_PATH_BATCHED_PREDICT in one call: k_negbin_predict_batched or k_glm_shared_predict_batched (all 32 bits are taken; no other call sets any of these pairs) */
+#define GSMVI_PATH_BATCHED_TARGET 0x20000u /* k_logistic_batched: the batched non-Gaussian target's entry point; with GSMVI_PATH_BATCHED_LAPLACE in one call: k_laplace_shared_batched, k_negbin_laplace_batched or k_ordinal_laplace_batched; with GSMVI_PATH_BATCHED_LOO in one call: k_psis_loo_negbin_batched or k_psis_loo_ordinal_batched; with GSMVI_PATH_BATCHED_PREDICT in one call: k_negbin_predict_batched, k_ordinal_predict_batched or k_glm_shared_predict_batched (all 32 bits are taken; no other call sets any of these pairs) */
 #define GSMVI_PATH_BATCHED_LBFGS 0x40000u  /* k_lbfgs_step_batched / k_lbfgs_hess_inv_batched: the batched initialiser   */
 #define GSMVI_PATH_BATCHED_LAPLACE 0x80000u /* k_laplace_batched: the batched GLM Hessian and Newton step; with GSMVI_PATH_BATCHED_TARGET in one call: k_laplace_shared_batched, the shared-design Hessian and Newton step, k_negbin_laplace_batched, the negative binomial one, or k_ordinal_laplace_batched, the ordinal one */
-#define GSMVI_PATH_BATCHED_PREDICT 0x100000u /* k_glm_predict_batched: the batched GLM posterior predictive; with GSMVI_PATH_BATCHED_SOFTMAX: k_softmax_predict_batched; with GSMVI_PATH_BATCHED_TARGET: k_negbin_predict_batched or k_glm_shared_predict_batched, the shared-design GLM predictive */
+#define GSMVI_PATH_BATCHED_PREDICT 0x100000u /* k_glm_predict_batched: the batched GLM posterior predictive; with GSMVI_PATH_BATCHED_SOFTMAX: k_softmax_predict_batched; with GSMVI_PATH_BATCHED_TARGET: k_negbin_predict_batched, k_ordinal_predict_batched, the ordinal predictive, or k_glm_shared_predict_batched, the shared-design GLM predictive */
 #define GSMVI_PATH_BATCHED_PSIS 0x200000u /* k_psis_batched: the batched Pareto-smoothed importance diagnostic            */
 #define GSMVI_PATH_BATCHED_LOO 0x400000u /* k_psis_loo_batched: the batched PSIS leave-one-out; with GSMVI_PATH_BATCHED_SOFTMAX: k_psis_loo_softmax_batched; with GSMVI_PATH_BATCHED_TARGET: k_psis_loo_negbin_batched or k_psis_loo_ordinal_batched */
 #define GSMVI_PATH_GSM_TWO_LAUNCH 0x800000u /* the dense GSM update ran as two launches (no k_gsm_scalars_fast, no records)          */
@@ -1381,6 +1383,59 @@ int gsmvi_softmax_predict_batched_f64(gsmvi_ctx* ctx, void* stream, int64_t K, i
 int gsmvi_negbin_predict_batched_f64(gsmvi_ctx* ctx, void* stream, int64_t K, int P, int64_t M, int64_t S, const double* A,
                                      const double* y, const double* offset, const int* counts_dev, const double* X,
                                      const double* lw, double* lmom, double* lpd);
+
+/*
+ * Batched ordinal posterior predictive: what the fitted q_k = N(mean_k, cov_k) of K cumulative-logit (proportional odds) regressions
+ * (the model of gsmvi_ordinal_batched_f64) says about M new rows per problem, from S draws of q_k: the class probabilities and, with
+ * the rows' labels, the log predictive density of every row (the held-out score, on the scale of the lpd of
+ * gsmvi_psis_loo_ordinal_batched_f64).  The cutpoints are coordinates of q_k and are correlated with beta, so a row's probabilities
+ * depend on the whole draw and the one-dimensional quadrature of gsmvi_glm_predict_batched_f64 does not apply; the draws are those
+ * of gsmvi_kl_draw_batched_f64, optionally with the smoothed weights of gsmvi_psis_batched_f64.  The reference has no twin.  One
+ * launch, one 256-thread workgroup per (problem, tile of 16 new rows); no (K, S, M, C) block is formed.
+ * A (K x M x P) are the new rows, y (K x M ints, or NULL) their labels in 0 .. C - 1, offset (K x M, or NULL) is added to the linear
+ * predictor, n_k = counts_dev[k] clamped to 0 .. M valid rows (M without counts_dev), C classes with D = P + C - 1 <= 64, X
+ * (K x S x D) the draws x_s = (beta_s, delta_s) of q_k, beta first.  lw (K x S, or NULL) are normalised log weights, e.g. the
+ * log_weights of gsmvi_psis_batched_f64 for the same draws; NULL means uniform: lw_s = -log S and w_s = 1.0 / S.  For a valid row
+ * i < n_k and draw s:
+ *   cut_s0 = delta_s0,  cut_sj = cut_s,j-1 + w_sj,  w_sj = exp(delta_sj)   (j = 1 .. C - 2: one chain in ascending j, the bits of
+ *                                                                          gsmvi_ordinal_batched_f64's prologue)
+ *   eta_si = a_i . beta_s + o_i
+ *   z_sij  = cut_sj - eta_si
+ *   p_si0  = sigma(z_si0),   p_si,C-1 = sigma(-z_si,C-2),   p_sic = sigma(z_sic) sigma(-z_si,c-1) (-expm1(-w_sc))   (0 < c < C - 1)
+ *   prob[k, i, c] = sum_s w_s p_sic,   w_s = exp(lw_s)
+ *   l_si   = t of the link of gsmvi_ordinal_batched_f64 at the label y_i (the l_si of gsmvi_psis_loo_ordinal_batched_f64: the same
+ *            device function, the same bits at the same eta and cutpoints)
+ *   lpd[k, i]     = log sum_s exp(lw_s + l_si)
+ * No two probabilities are subtracted: sigma(cut_c - eta) - sigma(cut_{c-1} - eta) = sigma(z_c) sigma(-z_{c-1}) (1 - e^{-w_c}), with
+ * sigma(z) and sigma(-z) from one exp(-|z|) and one -expm1(-w) per (draw, interior class); at |eta| around 1000 the probabilities
+ * stay finite, with exact 0 and 1 entries.  lpd is a log-sum-exp that cannot underflow: a fixed tree of (max, scaled sum) pairs
+ * merged as (m1, s1) + (m2, s2) = (M, s1 e^(m1 - M) + s2 e^(m2 - M)), M = max(m1, m2); a pair whose maximum is -inf contributes 0;
+ * it is never the log of a linear-space sum.  prob is summed in linear space.  Every sum is a fixed tree or chain (a lane's entries
+ * in order, a fixed cross-lane order, the draw tiles in order, the waves in order; no atomics): the outputs are bit-identical from
+ * run to run and a problem's bits do not depend on K or on its neighbours.
+ * Draws s >= S of a partial tile contribute nothing (masked, not weighted).  A draw s < S is flagged by the rule of
+ * gsmvi_psis_loo_ordinal_batched_f64: a non-finite entry of x_s, or some w_sj, j >= 1, that is not a positive normal number; the
+ * flag is taken from the draw's entries, not from the product, and a flagged draw makes every valid row of its problem NaN whatever
+ * its weight.  A non-finite eta_si at a draw s < S (a non-finite entry of a_i or o_i) makes the outputs of row i NaN.  A problem
+ * whose lw holds a NaN or +inf, or only -inf, has NaN in every valid row (a lone -inf is legal: weight 0).  A label outside
+ * 0 .. C - 1 gives a NaN lpd for its row only (a label is compared or clamped, never used as an unchecked index).  Rows i >= n_k
+ * are never loaded and their outputs are NaN.  A verdict touches only its own (k, i) or k.  Outputs: prob (K x M x C, required) and
+ * lpd (K x M): required exactly when y is given, NULL otherwise.
+ * gsmvi_ordinal_predict_lds_bytes(P, C) is a pure function (no GPU): the dynamic LDS of the launch in bytes, 8 (80 (4 ceil(P / 4) +
+ * 1) + 128 ((C - 1) | 1) + 64 C + 616) -- the tile of 64 draws' beta and the 16 rows, the tables of the cutpoints and of the gap
+ * factors, the accumulators of (wave, class, row), the weights and gap cells of the tile and the waves' partial results --,
+ * at most 105408 (P = 1, C = 64), inside the workgroup's 160 KB; 0 for (P, C) out of bounds.
+ * 2 <= C <= 64, 1 <= P <= 65 - C, 1 <= S <= 4096, M >= 1, 1 <= K <= 2^24 - 1 with K ceil(M / 16) <= 2^24 - 1.  Shapes, NULL arrays,
+ * the y / lpd pairing and overlaps (prob and lpd are the written arrays, everything else is read) are checked before the context is
+ * looked at (then a NULL ctx); every failure returns GSMVI_ERR_BAD_ARG before anything is enqueued.  Inputs are only read; no
+ * context workspace is used; one capturable launch with no host synchronisation and no atomics.  Sets GSMVI_PATH_BATCHED_PREDICT |
+ * GSMVI_PATH_BATCHED_TARGET (no bit of its own: the pair is also gsmvi_negbin_predict_batched_f64's and
+ * gsmvi_glm_shared_predict_batched_f64's).
+ */
+int gsmvi_ordinal_predict_lds_bytes(int P, int C);
+int gsmvi_ordinal_predict_batched_f64(gsmvi_ctx* ctx, void* stream, int64_t K, int P, int C, int64_t M, int64_t S, const double* A,
+                                      const int* y, const double* offset, const int* counts_dev, const double* X,
+                                      const double* lw, double* prob, double* lpd);
 
 /*
  * Shared-design GLM posterior predictive: gsmvi_glm_predict_batched_f64 for K fitted posteriors q_k = N(mean_k, cov_k) on ONE
