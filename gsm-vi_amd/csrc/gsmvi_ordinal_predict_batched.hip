@@ -3,9 +3,10 @@
 // predictive density of every row, from S (optionally weighted) draws of q_k, one launch ("Batched ordinal
 // predictive"; the definition is in include/gsmvi_hip.h, above gsmvi_ordinal_predict_batched_f64).  The reference has no twin.
 //   k_ordinal_predict_batched       (not a template over C: the class walk is rolled)
-// Work mapping (k_softmax_predict_batched's): one 256-thread workgroup per (problem k, tile of OP_NB = 16 new rows): all 16 columns
-// of the fp64 MFMA (16 x 16 x 4) carry a row.  X_k streams through LDS once in tiles of 64 draws, in three steps between barriers
-// (steps (1)(a)-(b) of k_psis_loo_ordinal_batched, with its loaders, lane map and MFMA chain: gsmvi_psis_loo_tile.h):
+// Work mapping (the draw-predictive block's, gsmvi_predict_draws.h): one 256-thread workgroup per (problem k, tile of OP_NB = 16
+// new rows): all 16 columns of the fp64 MFMA (16 x 16 x 4) carry a row.  X_k streams through LDS once in tiles of 64 draws, in three
+// steps between barriers (steps (1)(a)-(b) of k_psis_loo_ordinal_batched, with its loaders, lane map and MFMA chain:
+// gsmvi_psis_loo_tile.h):
 //   (a) the beta columns j < P of the tile's draws into the operand tile, 64 rows of Pp = 4 ceil(P / 4) columns (row stride Pp + 1);
 //       every padded position (j >= P, rows past S) holds 0.0 and loads nothing, and the C - 1 delta columns never enter the
 //       operand (at C = 2 delta_0 sits right behind beta in memory: it is not read through the operand).  The 16 rows of A_k sit
@@ -25,25 +26,24 @@
 //       formed as in the leave-one-out kernel (ord_gap of e^{delta_y} read from X_k again: the same bits), and lw_s + l_si goes
 //       into the row's log-sum-exp pair.
 // The slots (4 x C x 16 doubles) are the per-class accumulators: each is updated by one thread alone, tile after tile.  lpd is a
-// log-sum-exp kept as (maximum, scaled sum) pairs, merged with op_merge (sp_merge of gsmvi_softmax_predict_batched.hip: a pair
-// whose maximum is -inf contributes 0).  At the end the four waves' slots and pairs are added in wave order.  Every sum is a fixed
-// tree and there are no atomics.  The verdicts are flags, not arithmetic: a row with a non-finite eta at a draw s < S; a problem
-// with a flagged draw s < S, whatever its weight; a problem whose lw holds a NaN or +inf or only -inf (ps_sum and ps_max of
-// gsmvi_psis_stage.h).  Every thread of a workgroup runs the same barriers whatever the verdicts; a workgroup reads only slice k of
-// the inputs and writes only its own (k, i) entries.  A label is compared and clamped, never used as an unchecked index.  Inputs
-// are only read; no context workspace.
+// log-sum-exp kept as (maximum, scaled sum) pairs (pd_fold and pd_merge of gsmvi_predict_draws.h: a pair whose maximum is -inf
+// contributes 0).  At the end the four waves' slots and pairs are added in wave order.  Every sum is a fixed tree and there are no
+// atomics.  The verdicts are flags, not arithmetic: a row with a non-finite eta at a draw s < S; a problem with a flagged draw s <
+// S, whatever its weight; a problem whose lw holds a NaN or +inf or only -inf.  Everything around steps (a)-(c) is the block's (the
+// tile position, the weight verdict and tile, the slots, the fold, the flags, the outputs).  Every thread of a workgroup runs the
+// same barriers whatever the verdicts; a workgroup reads only slice k of the inputs and writes only its own (k, i) entries.  A label
+// is compared and clamped, never used as an unchecked index.  Inputs are only read; no context workspace.
 #include "gsmvi_common.h"
 #include "gsmvi_ctx.h"
 #include "gsmvi_batched.h"
 #include "gsmvi_ordinal_link.h"
-#include "gsmvi_psis_loo_tile.h"
+#include "gsmvi_predict_draws.h"
 #include "../../include/gsmvi_hip.h"
 #include <cmath>
 #include <cstdint>
 
-#define OP_TR PS_LOO_TR     // draws per tile of X_k: one 16-row MFMA block per wave
-#define OP_NB PS_LOO_NB     // new rows per workgroup: the MFMA's 16 columns
-#define OP_MAX_S 4096
+#define OP_TR PD_TR     // draws per tile of X_k: one 16-row MFMA block per wave
+#define OP_NB PD_NB     // new rows per workgroup: the MFMA's 16 columns
 
 struct op_args {
     long long M;
@@ -60,25 +60,16 @@ struct op_args {
     double* lpd;                // (K, M) or null
 };
 
-__host__ __device__ inline int op_pp(int P) { return (P + 3) & ~3; }
 __host__ __device__ inline int op_ldc(int C) { return (C - 1) | 1; }
 
 // doubles of the launch's LDS: the X tile and the A tile (80 rows of Pp + 1), the tables T and G (64 rows of (C - 1) | 1 each), the
 // 16 offsets, the 16 labels, lw_s and w_s of the tile, one cell per thread for the gap term, the accumulator slots, the four
 // waves' lpd pairs and row flags, the 8 words of the block reductions
 __host__ __device__ inline int op_lds_doubles(int P, int C) {
-    return (OP_TR + OP_NB) * (op_pp(P) + 1) + 2 * OP_TR * op_ldc(C) + 2 * OP_NB + 2 * OP_TR + 256 + 4 * OP_NB * C + 3 * 4 * OP_NB + 8;
+    return (OP_TR + OP_NB) * (pd_pp(P) + 1) + 2 * OP_TR * op_ldc(C) + 2 * OP_NB + 2 * OP_TR + 256 + pd_tail_doubles(C, 1);
 }
 
 __host__ __device__ inline bool op_shape_ok(int P, int C) { return C >= 2 && C <= GB_MAX_D && P >= 1 && P <= GB_MAX_D - (C - 1); }
-
-// (m1, s1) + (m2, s2) of two log-sum-exp pairs, into the first (sp_merge of gsmvi_softmax_predict_batched.hip)
-__device__ __forceinline__ void op_merge(double& m1, double& s1, double m2, double s2) {
-    const double mm = fmax(m1, m2);
-    const double e = mm == -__builtin_huge_val() ? 0.0 : exp(fmin(m1, m2) - mm);
-    s1 = m1 >= m2 ? s1 + s2 * e : s1 * e + s2;
-    m1 = mm;
-}
 
 // sigma(z) and sigma(-z) from one exponential (the two branches of ord_sps's sg): e^{+|z|} is never formed
 __device__ __forceinline__ void op_sig2(double z, double& sp, double& sn) {
@@ -90,18 +81,10 @@ __device__ __forceinline__ void op_sig2(double z, double& sp, double& sn) {
 
 __global__ __launch_bounds__(256) void k_ordinal_predict_batched(op_args a) {
     extern __shared__ double op_sm[];
-    const int l = threadIdx.x, S = a.S, C = a.C, P = a.P, lc = C - 1, D = P + lc, Pp = op_pp(P), lda = Pp + 1, ldc = op_ldc(C);
-    const long long M = a.M;
-    const size_t k = blockIdx.x / a.ntile;
-    const long long i0 = (long long)(blockIdx.x - (unsigned)k * a.ntile) * OP_NB;    // the tile's first row
-    const int ni = (int)(M - i0 < OP_NB ? M - i0 : OP_NB);
-    long long nk = M;                         // the rows that count
-    if (a.counts) {
-        const long long c = a.counts[k];
-        nk = c < 0 ? 0 : (c > M ? M : c);
-    }
-    const int nv = (int)(nk - i0 < 0 ? 0 : (nk - i0 < ni ? nk - i0 : ni));           // the tile's valid rows: the first nv
-    double* Xs = op_sm;                       // OP_TR x lda   the beta part of a tile of draws
+    const int l = threadIdx.x, S = a.S, C = a.C, P = a.P, lc = C - 1, D = P + lc, Pp = pd_pp(P), lda = Pp + 1, ldc = op_ldc(C);
+    const ps_loo_pos pos = pd_pos_of(a.ntile, a.M, S);
+    const int nv = pd_valid(a.counts, a.M, pos);               // the tile's valid rows: the first nv
+    double* Xs = op_sm;                      // OP_TR x lda   the beta part of a tile of draws
     double* As = Xs + OP_TR * lda;            // OP_NB x lda   the tile's rows of A_k, zero-padded
     double* Ct = As + OP_NB * lda;            // OP_TR x ldc   delta_0 and w_j of the tile's draws, then their cutpoints
     double* Gt = Ct + OP_TR * ldc;            // OP_TR x ldc   g_j = -expm1(-w_j), j >= 1
@@ -110,47 +93,28 @@ __global__ __launch_bounds__(256) void k_ordinal_predict_batched(op_args a) {
     double* lws = os + 2 * OP_NB;             // OP_TR         lw_s of the tile
     double* wts = lws + OP_TR;                // OP_TR         w_s = exp(lw_s)
     double* gs = wts + OP_TR;                 // 256           the gap term of the thread's pair
-    double* pac = gs + 256;                   // 4 x C x OP_NB the accumulator slots: (wave, class, row)
-    double* pm = pac + 4 * OP_NB * C;         // 4 x OP_NB     the waves' lpd pairs: maxima
-    double* psum = pm + 4 * OP_NB;            // 4 x OP_NB                           scaled sums
-    int* pbad = reinterpret_cast<int*>(psum + 4 * OP_NB);   // 4 x OP_NB row flags (in 4 x OP_NB doubles)
-    double* red = psum + 2 * 4 * OP_NB;       // 8             the block reductions
-    const size_t ks = k * (size_t)S, km = k * (size_t)M + (size_t)i0;
-    const double qnan = __longlong_as_double(0x7ff8000000000000LL), inf = __builtin_huge_val();
+    const pd_tail tl = pd_carve_tail(gs + 256, C, 1);
+    const double inf = __builtin_huge_val();
     const ps_loo_lane ln = ps_loo_lane_of(l);
     const int wv = ln.wv, cc = ln.cc, kq = ln.kq;
 
-    if (nv == 0) {                            // no valid row (uniform in the workgroup): nothing is loaded
-        for (int e = l; e < ni * C; e += 256) a.prob[km * C + e] = qnan;
-        if (a.lpd && l < ni) a.lpd[km + l] = qnan;
+    if (nv == 0) {                            // no valid row (uniform in the workgroup)
+        pd_no_rows(a.prob, C, a.lpd, pos, l);
         return;
     }
-
-    // ---- the problem's weights: a NaN or +inf, or nothing but -inf, refuses every row --------------------------------------
-    bool wbad = false;
     const double lwu = -log((double)S), wu = 1.0 / (double)S;      // the uniform weights of lw = null
-    if (a.lw) {
-        double nb = 0.0, vmax = -inf;
-        for (int s = l; s < S; s += 256) {
-            const double v = a.lw[ks + s];
-            if (!(v < inf)) nb += 1.0;        // NaN or +inf
-            vmax = fmax(vmax, v);
-        }
-        nb = ps_sum(nb, red, l);
-        vmax = ps_max(vmax, red, l);
-        wbad = nb > 0.0 || vmax == -inf;
-    }
+    const bool wbad = pd_weights_bad(a.lw, pos.ks, S, tl.red, l);
 
-    ps_loo_load_rows(As, lda, a.A + km * P, P, nv, P, l);
+    ps_loo_load_rows(As, lda, a.A + pos.kn * P, P, nv, P, l);
     if (l < OP_NB) {
-        ys[l] = a.y && l < nv ? a.y[km + l] : 0;
-        os[l] = a.offset && l < nv ? a.offset[km + l] : 0.0;
+        ys[l] = a.y && l < nv ? a.y[pos.kn + l] : 0;
+        os[l] = a.offset && l < nv ? a.offset[pos.kn + l] : 0.0;
     }
-    for (int e = l; e < 4 * OP_NB * C; e += 256) pac[e] = 0.0;
+    pd_zero_slots(tl.pac, C, l);
 
-    const double* Xk = a.X + ks * D;
+    const double* Xk = a.X + pos.ks * D;
     const bool live = cc < nv;                // the lane's column is a valid row
-    double lm = -inf, ls = 0.0;               // lane kq = 0: the row's lpd pair over the wave's draws so far
+    double lm[1] = {-inf}, ls[1] = {0.0};     // lane kq = 0: the row's lpd pair over the wave's draws so far
     bool rbad = false;                        // a non-finite eta of the lane's row at one of its draws
     double dbad = 0.0;                        // thread s < 64: the flagged draws among s, s + 64, ...
     for (int t0 = 0; t0 < S; t0 += OP_TR) {
@@ -167,23 +131,17 @@ __global__ __launch_bounds__(256) void k_ordinal_predict_batched(op_args a) {
                 Gt[r * ldc + j] = -expm1(-w);                                      // (entry 0 of G is neither written nor read)
             }
         }
-        if (l < OP_TR) {
-            const double v = t0 + l < S ? (a.lw ? a.lw[ks + t0 + l] : lwu) : -inf;
-            lws[l] = v;
-            wts[l] = t0 + l < S ? (a.lw ? exp(v) : wu) : 0.0;
-        }
+        pd_load_weights(lws, wts, a.lw, pos.ks, t0, S, lwu, wu, l);
         __syncthreads();
         if (l < OP_TR) {                                                           // (b) the per-draw values ...
-            const double* xr = Xs + l * lda;
             double* cr = Ct + l * ldc;
-            double z = 0.0;
-            for (int j = 0; j < P; ++j) z += xr[j] * 0.0;                          // (NaN for a non-finite beta_sj)
+            double z = pd_beta_flag(Xs + l * lda, P);
             double cut = cr[0];
             z += cut * 0.0;
             bool okw = true;
             for (int j = 1; j < lc; ++j) {
                 const double w = cr[j];
-                okw = okw && w >= 2.2250738585072014e-308 && w < inf;
+                okw = okw && pd_pos_normal(w);
                 cut += w;
                 cr[j] = cut;                                                       // (over the w_j just read)
             }
@@ -225,17 +183,13 @@ __global__ __launch_bounds__(256) void k_ordinal_predict_batched(op_args a) {
                         v += in[r] ? w[r] * p : 0.0;
                     }
                 }
-                v += __shfl_xor(v, 16);
-                v += __shfl_xor(v, 32);
-                if (live && kq == 0) pac[(wv * C + c) * OP_NB + cc] += v;
+                pd_add_slot(tl.pac, C, c, v, live, ln);
             }
             if (a.lpd) {                                    // (uniform in the grid)
-                double tm = -inf, ts = 0.0;                 // the lane's four entries: their maximum, then the sum in order
+                double t[4] = {-inf, -inf, -inf, -inf};
                 if (live) {
-                    double t[4];
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
-                        t[r] = -inf;
                         if (in[r]) {
                             const int q = 16 * wv + kq + 4 * r;
                             double glm = 0.0, qe = 0.0;
@@ -245,47 +199,15 @@ __global__ __launch_bounds__(256) void k_ordinal_predict_batched(op_args a) {
                             ord_link<false, true>(eta[r], yv, C, cr[r], gs + l - yv, nullptr, re, ulo, uhi, tt);
                             t[r] = lws[q] + tt;
                         }
-                        tm = fmax(tm, t[r]);
                     }
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) ts += tm == -inf ? 0.0 : exp(t[r] - tm);
                 }
-#pragma unroll
-                for (int o2 = 16; o2 <= 32; o2 <<= 1) {
-                    const double om = __shfl_xor(tm, o2), osm = __shfl_xor(ts, o2);
-                    op_merge(tm, ts, om, osm);
-                }
-                op_merge(lm, ls, tm, ts);                   // (used from lane kq = 0 alone)
+                pd_fold(lm[0], ls[0], t, live);
             }
         }
     }
-    // a row's flag: its four lanes, then its four waves
-    int fl = rbad ? 1 : 0;
-    fl |= __shfl_xor(fl, 16);
-    fl |= __shfl_xor(fl, 32);
-    if (kq == 0) {
-        pm[wv * OP_NB + cc] = lm;
-        psum[wv * OP_NB + cc] = ls;
-        pbad[wv * OP_NB + cc] = fl;
-    }
-    const double nflag = ps_sum(dbad, red, l);                // (its barriers publish the slots, the pairs and the flags)
-    const bool pbadk = wbad || nflag > 0.0;
-
-    // ---- the tile's outputs: the waves in order ------------------------------------------------------------------------------
-    for (int e = l; e < ni * C; e += 256) {
-        const int r = e / C, c = e - r * C;
-        const bool bad = r >= nv || pbadk || (pbad[r] | pbad[OP_NB + r] | pbad[2 * OP_NB + r] | pbad[3 * OP_NB + r]) != 0;
-        const double* q = pac + c * OP_NB + r;
-        a.prob[km * C + e] = bad ? qnan : ((q[0] + q[C * OP_NB]) + q[2 * C * OP_NB]) + q[3 * C * OP_NB];
-    }
-    if (a.lpd && l < ni) {
-        const int yv = ys[l];
-        const bool bad = l >= nv || pbadk || yv < 0 || yv > lc ||
-                         (pbad[l] | pbad[OP_NB + l] | pbad[2 * OP_NB + l] | pbad[3 * OP_NB + l]) != 0;
-        double mm = pm[l], ss = psum[l];
-        for (int w = 1; w < 4; ++w) op_merge(mm, ss, pm[w * OP_NB + l], psum[w * OP_NB + l]);
-        a.lpd[km + l] = bad ? qnan : mm + log(ss);
-    }
+    pd_publish(tl, lm, ls, rbad, ln);
+    const bool kbad = pd_draws_bad(dbad, tl.red, l) || wbad;               // (its barriers publish the slots, the pairs and the flags)
+    pd_write_classes(a.prob, a.lpd, tl, ys, C, nv, kbad, pos, l);
 }
 
 hipError_t gsmvi_ordinal_predict_batched_prepare() { return gb_allow_lds(k_ordinal_predict_batched); }
@@ -304,12 +226,9 @@ int gsmvi_ordinal_predict_batched_f64(gsmvi_ctx* ctx, void* stream, int64_t K, i
     GB_BAD(P < 1 || P > GB_MAX_D - (C - 1), "P must be in [1, 65 - C] (D = P + C - 1 <= 64)");
     GB_BAD(K < 1 || K > 16777215, "K must be in [1, 2^24 - 1]");
     GB_BAD(M < 1, "M must be at least 1");
-    GB_BAD(S < 1 || S > OP_MAX_S, "S must be in [1, 4096]");
-    GB_BAD(M > (INT64_MAX / 8 / 64) / K, "K M is too large");                 // K M P and K M C doubles addressable (P, C <= 64)
-    const int64_t ntile = (M + OP_NB - 1) / OP_NB;
-    GB_BAD(ntile > 16777215 / K, "K ceil(M / 16) must be at most 2^24 - 1 (one tile of 16 rows per workgroup)");
-    GB_BAD(!A || !X || !prob, "NULL array");
-    GB_BAD((y != nullptr) != (lpd != nullptr), "labels and lpd are given together or not at all");
+    pd_launch pl;                                                             // K M P and K M C doubles addressable (P, C <= 64)
+    if (int st = pd_plan(__func__, K, M, S, 64, !A || !X || !prob, y, lpd, "labels and lpd are given together or not at all", &pl))
+        return st;
     const int D = P + C - 1;
     const size_t nm = (size_t)K * M, ns = (size_t)K * S * 8;
     if (int st = gb_check_overlaps(__func__, {{A, nm * P * 8, "A", GB_RD},
@@ -325,11 +244,11 @@ int gsmvi_ordinal_predict_batched_f64(gsmvi_ctx* ctx, void* stream, int64_t K, i
     op_args a = {};
     a.M = M; a.P = P; a.C = C;
     a.S = (int)S;
-    a.ntile = (unsigned)ntile;
+    a.ntile = pl.ntile;
     a.A = A; a.y = y; a.offset = offset; a.counts = counts_dev; a.X = X; a.lw = lw; a.prob = prob; a.lpd = lpd;
-    const size_t lds = (size_t)gsmvi_ordinal_predict_lds_bytes(P, C);          // <= 105408 bytes, reached at (1, 64): the kernel
-    const unsigned grid = (unsigned)(K * ntile);                              // attribute of ..._prepare() allows it
-    hipLaunchKernelGGL(k_ordinal_predict_batched, dim3(grid), dim3(256), lds, reinterpret_cast<hipStream_t>(stream), a);
+    // <= 105408 bytes, reached at (1, 64): the kernel attribute of ..._prepare() allows it
+    const size_t lds = (size_t)gsmvi_ordinal_predict_lds_bytes(P, C);
+    hipLaunchKernelGGL(k_ordinal_predict_batched, dim3(pl.grid), dim3(256), lds, reinterpret_cast<hipStream_t>(stream), a);
     return gb_launched(ctx, GSMVI_PATH_BATCHED_PREDICT | GSMVI_PATH_BATCHED_TARGET, "k_ordinal_predict_batched");
 }
 

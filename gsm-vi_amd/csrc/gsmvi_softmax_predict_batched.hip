@@ -14,14 +14,11 @@
 //   sweep 2  z = sum_c exp(eta_c - m) in class order, the reference class's exp(-m) last, as 1 + rest (sm_add_term of
 //            gsmvi_softmax_model.h); the lpd's log z is log1p(rest) (sm_log_s: log(z) is 0 where rest < eps / 2)
 //   sweep 3  per class (the reference class last) the lane's four exp(eta_c - m) (w_s / z) in order, draws s >= S left out, then
-//            the four lanes of the row by a butterfly (xor 16, xor 32); lane kq = 0 adds the sum to the LDS slot of (wave, class, row)
-// The slots (4 x C x 16 doubles) are the per-class accumulators: each is updated by one thread alone, tile after tile.  lpd is a
-// log-sum-exp of lw_s + l_si kept as a (maximum, scaled sum) pair: the lane's four entries (their maximum, then the sum in
-// order), the butterfly, then lane kq = 0 merges the tile's pair into the pair it carries from tile to tile; a pair whose
-// maximum is -inf contributes 0, so no inf - inf is formed.  At the end the four waves' slots and pairs are added in wave order.
-// Every sum is a fixed tree and there are no atomics.  The verdicts are flags, not arithmetic: a row with a non-finite eta at a
-// draw s < S, and a problem whose lw holds a NaN or +inf or only -inf (two block reductions over lw_k before the first tile:
-// ps_sum and ps_max of gsmvi_psis_stage.h, the only use of that header here), write NaN.
+//            the slot of (wave, class, row) takes their sum (pd_add_slot)
+// Everything around the sweeps is the draw-predictive block's (gsmvi_predict_draws.h: the tile position, the weight verdict and
+// tile, the class slots, the log-sum-exp pair of lw_s + l_si and its fold, the row flags, the outputs; its comment gives the sum
+// orders and the barrier rule).  The verdicts are flags, not arithmetic: a row with a non-finite eta at a draw s < S, and a problem
+// whose lw holds a NaN or +inf or only -inf, write NaN.  Only the draw tile is this kernel's own.
 // The padding rule is k_psis_loo_softmax_batched's: a k position 4 j + kq >= P feeds 0.0 from the X side and loads nothing, so a
 // padded position is 0 x 0 and no LDS word outside the row's D entries is read (sm_eta of gsmvi_softmax_model.h, shared with it).
 // Every thread of a workgroup runs the same barriers whatever the verdicts; a workgroup reads only slice k of the inputs and
@@ -29,15 +26,14 @@
 #include "gsmvi_common.h"
 #include "gsmvi_ctx.h"
 #include "gsmvi_batched.h"
-#include "gsmvi_psis_stage.h"
+#include "gsmvi_predict_draws.h"
 #include "gsmvi_softmax_model.h"
 #include "../../include/gsmvi_hip.h"
 #include <cmath>
 #include <cstdint>
 
-#define SP_TR 64        // draws per tile of X_k: one 16-row MFMA block per wave
-#define SP_NB 16        // new rows per workgroup: the MFMA's 16 columns
-#define SP_MAX_S 4096
+#define SP_TR PD_TR     // draws per tile of X_k: one 16-row MFMA block per wave
+#define SP_NB PD_NB     // new rows per workgroup: the MFMA's 16 columns
 
 struct sp_args {
     long long K, M;
@@ -54,75 +50,40 @@ struct sp_args {
 };
 
 // doubles of the launch's LDS: the X tile, the A tile, the 16 labels, lw_s and w_s of the tile, the accumulator slots, the four
-// waves' lpd pairs and row flags, the 8 words of the block reductions
+// waves' lpd pairs and row flags, the 8 words of the block reductions (pd_tail_doubles)
 __host__ __device__ inline int sp_lds_doubles(int C, int P) {
-    return SP_TR * (((C - 1) * P) | 1) + SP_NB * (sm_pp(P) + 1) + SP_NB + 2 * SP_TR + 4 * SP_NB * C + 3 * 4 * SP_NB + 8;
-}
-
-// (m1, s1) + (m2, s2) of two log-sum-exp pairs, into the first: (M, s1 e^(m1 - M) + s2 e^(m2 - M)) with M the larger maximum, whose
-// own factor e^0 is exactly 1 and is not computed; a pair whose maximum is -inf contributes 0 (two of them: no inf - inf is formed)
-__device__ __forceinline__ void sp_merge(double& m1, double& s1, double m2, double s2) {
-    const double mm = fmax(m1, m2);
-    const double e = mm == -__builtin_huge_val() ? 0.0 : exp(fmin(m1, m2) - mm);
-    s1 = m1 >= m2 ? s1 + s2 * e : s1 * e + s2;
-    m1 = mm;
+    return SP_TR * (((C - 1) * P) | 1) + SP_NB * (sm_pp(P) + 1) + SP_NB + 2 * SP_TR + pd_tail_doubles(C, 1);
 }
 
 __global__ __launch_bounds__(256) void k_softmax_predict_batched(sp_args a) {
     extern __shared__ double sp_sm[];
     const int l = threadIdx.x, S = a.S, C = a.C, P = a.P, Cm = C - 1, D = a.D, Pp = sm_pp(P), lda = Pp + 1, ldx = D | 1;
-    const long long M = a.M;
-    const size_t k = blockIdx.x / a.ntile;
-    const long long i0 = (long long)(blockIdx.x - (unsigned)k * a.ntile) * SP_NB;    // the tile's first row
-    const int ni = (int)(M - i0 < SP_NB ? M - i0 : SP_NB);
-    const long long nk = sm_rows_of(a.counts, (long long)k, M);
-    const int nv = (int)(nk - i0 < 0 ? 0 : (nk - i0 < ni ? nk - i0 : ni));           // its valid rows: the first nv
+    const ps_loo_pos pos = pd_pos_of(a.ntile, a.M, S);
+    const int nv = pd_valid(a.counts, a.M, pos);               // the tile's valid rows: the first nv
     double* Xs = sp_sm;                       // SP_TR x ldx   a tile of draws
     double* As = Xs + SP_TR * ldx;            // SP_NB x lda   the tile's rows of A_k, zero-padded
     int* ys = reinterpret_cast<int*>(As + SP_NB * lda);     // SP_NB labels (in SP_NB doubles)
     double* lws = As + SP_NB * lda + SP_NB;   // SP_TR         lw_s of the tile
     double* wts = lws + SP_TR;                // SP_TR         w_s = exp(lw_s)
-    double* pac = wts + SP_TR;                // 4 x C x SP_NB the accumulator slots: (wave, class, row)
-    double* pm = pac + 4 * SP_NB * C;         // 4 x SP_NB     the waves' lpd pairs: maxima
-    double* psum = pm + 4 * SP_NB;            // 4 x SP_NB                           scaled sums
-    int* pbad = reinterpret_cast<int*>(psum + 4 * SP_NB);   // 4 x SP_NB row flags (in 4 x SP_NB doubles)
-    double* red = psum + 2 * 4 * SP_NB;       // 8             the block reductions
-    const size_t ks = k * (size_t)S, km = k * (size_t)M + (size_t)i0;
-    const double qnan = __longlong_as_double(0x7ff8000000000000LL), inf = __builtin_huge_val();
-    const int wv = l >> 6, ln = l & 63, cc = ln & 15, kq = ln >> 4;
+    const pd_tail tl = pd_carve_tail(wts + SP_TR, C, 1);
+    const double inf = __builtin_huge_val();
+    const ps_loo_lane ln = ps_loo_lane_of(l);
+    const int wv = ln.wv, cc = ln.cc, kq = ln.kq;
 
-    if (nv == 0) {                            // no valid row (uniform in the workgroup): nothing is loaded
-        for (int e = l; e < ni * C; e += 256) a.prob[km * C + e] = qnan;
-        if (a.lpd && l < ni) a.lpd[km + l] = qnan;
+    if (nv == 0) {                            // no valid row (uniform in the workgroup)
+        pd_no_rows(a.prob, C, a.lpd, pos, l);
         return;
     }
-
-    // ---- the problem's weights: a NaN or +inf, or nothing but -inf, refuses every row --------------------------------------
-    bool wbad = false;
+    const bool wbad = pd_weights_bad(a.lw, pos.ks, S, tl.red, l);
     const double lwu = -log((double)S), wu = 1.0 / (double)S;      // the uniform weights of lw = null
-    if (a.lw) {
-        double nb = 0.0, vmax = -inf;
-        for (int s = l; s < S; s += 256) {
-            const double v = a.lw[ks + s];
-            if (!(v < inf)) nb += 1.0;        // NaN or +inf
-            vmax = fmax(vmax, v);
-        }
-        nb = ps_sum(nb, red, l);
-        vmax = ps_max(vmax, red, l);
-        wbad = nb > 0.0 || vmax == -inf;
-    }
 
-    const double* Ak = a.A + km * P;
-    for (int e = l; e < SP_NB * lda; e += 256) {
-        const int r = e / lda, j = e - r * lda;
-        As[e] = r < nv && j < P ? Ak[(size_t)r * P + j] : 0.0;
-    }
-    if (l < SP_NB) ys[l] = a.labels && l < nv ? a.labels[km + l] : 0;
-    for (int e = l; e < 4 * SP_NB * C; e += 256) pac[e] = 0.0;
+    ps_loo_load_rows(As, lda, a.A + pos.kn * P, P, nv, P, l);
+    if (l < SP_NB) ys[l] = a.labels && l < nv ? a.labels[pos.kn + l] : 0;
+    pd_zero_slots(tl.pac, C, l);
 
-    const double* Xk = a.X + ks * D;
+    const double* Xk = a.X + pos.ks * D;
     const bool live = cc < nv;                // the lane's column is a valid row
-    double lm = -inf, ls = 0.0;               // lane kq = 0: the row's lpd pair over the wave's draws so far
+    double lm[1] = {-inf}, ls[1] = {0.0};     // lane kq = 0: the row's lpd pair over the wave's draws so far
     bool rbad = false;                        // a non-finite eta of the lane's row at one of its draws
     for (int t0 = 0; t0 < S; t0 += SP_TR) {
         __syncthreads();                      // the previous tile's readers are done (first pass: As, ys, pac are published below)
@@ -130,11 +91,7 @@ __global__ __launch_bounds__(256) void k_softmax_predict_batched(sp_args a) {
             const int r = e / ldx, j = e - r * ldx;
             Xs[e] = t0 + r < S && j < D ? Xk[(size_t)(t0 + r) * D + j] : 0.0;
         }
-        if (l < SP_TR) {
-            const double v = t0 + l < S ? (a.lw ? a.lw[ks + t0 + l] : lwu) : -inf;
-            lws[l] = v;
-            wts[l] = t0 + l < S ? (a.lw ? exp(v) : wu) : 0.0;
-        }
+        pd_load_weights(lws, wts, a.lw, pos.ks, t0, S, lwu, wu, l);
         __syncthreads();
         if (t0 + 16 * wv < S) {               // (wave-uniform)
             const double* px = Xs + (16 * wv + cc) * ldx + kq;
@@ -187,57 +144,20 @@ __global__ __launch_bounds__(256) void k_softmax_predict_batched(sp_args a) {
 #pragma unroll
                     for (int r = 0; r < 4; ++r) v += g[r] * (c < Cm ? exp(acc[r] - m[r]) : e0[r]);
                 }
-                v += __shfl_xor(v, 16);
-                v += __shfl_xor(v, 32);
-                if (live && kq == 0) pac[(wv * C + c) * SP_NB + cc] += v;
+                pd_add_slot(tl.pac, C, c, v, live, ln);
             }
             if (a.lpd) {                                    // (uniform in the grid)
-                double tm = -inf, ts = 0.0;                 // the lane's four entries: their maximum, then the sum in order
-                if (live) {
-                    double t[4];
+                double t[4];
 #pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        t[r] = in[r] ? lws[16 * wv + kq + 4 * r] + (ey[r] - m[r] - sm_log_s(rest[r], z[r])) : -inf;
-                        tm = fmax(tm, t[r]);
-                    }
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) ts += tm == -inf ? 0.0 : exp(t[r] - tm);
-                }
-#pragma unroll
-                for (int o = 16; o <= 32; o <<= 1) {
-                    const double om = __shfl_xor(tm, o), os = __shfl_xor(ts, o);
-                    sp_merge(tm, ts, om, os);
-                }
-                sp_merge(lm, ls, tm, ts);                   // (used from lane kq = 0 alone)
+                for (int r = 0; r < 4; ++r)
+                    t[r] = live && in[r] ? lws[16 * wv + kq + 4 * r] + (ey[r] - m[r] - sm_log_s(rest[r], z[r])) : -inf;
+                pd_fold(lm[0], ls[0], t, live);
             }
         }
     }
-    // a row's flag: its four lanes, then its four waves
-    int fl = rbad ? 1 : 0;
-    fl |= __shfl_xor(fl, 16);
-    fl |= __shfl_xor(fl, 32);
-    if (kq == 0) {
-        pm[wv * SP_NB + cc] = lm;
-        psum[wv * SP_NB + cc] = ls;
-        pbad[wv * SP_NB + cc] = fl;
-    }
+    pd_publish(tl, lm, ls, rbad, ln);
     __syncthreads();
-
-    // ---- the tile's outputs: the waves in order ------------------------------------------------------------------------------
-    for (int e = l; e < ni * C; e += 256) {
-        const int r = e / C, c = e - r * C;
-        const bool bad = r >= nv || wbad || (pbad[r] | pbad[SP_NB + r] | pbad[2 * SP_NB + r] | pbad[3 * SP_NB + r]) != 0;
-        const double* q = pac + c * SP_NB + r;
-        a.prob[km * C + e] = bad ? qnan : ((q[0] + q[C * SP_NB]) + q[2 * C * SP_NB]) + q[3 * C * SP_NB];
-    }
-    if (a.lpd && l < ni) {
-        const int yv = ys[l];
-        const bool bad = l >= nv || wbad || yv < 0 || yv > Cm ||
-                         (pbad[l] | pbad[SP_NB + l] | pbad[2 * SP_NB + l] | pbad[3 * SP_NB + l]) != 0;
-        double mm = pm[l], ss = psum[l];
-        for (int w = 1; w < 4; ++w) sp_merge(mm, ss, pm[w * SP_NB + l], psum[w * SP_NB + l]);
-        a.lpd[km + l] = bad ? qnan : mm + log(ss);
-    }
+    pd_write_classes(a.prob, a.lpd, tl, ys, C, nv, wbad, pos, l);
 }
 
 hipError_t gsmvi_softmax_predict_batched_prepare() { return gb_allow_lds(k_softmax_predict_batched); }
@@ -255,12 +175,9 @@ int gsmvi_softmax_predict_batched_f64(gsmvi_ctx* ctx, void* stream, int64_t K, i
     const sm_model m = sm_model_of(K, M, C, P, A, labels, counts_dev);
     if (int st = sm_check_model(__func__, m, false, "M")) return st;
     const int D = m.D;
-    GB_BAD(S < 1 || S > SP_MAX_S, "S must be in [1, 4096]");
-    GB_BAD(!A || !X || !prob, "NULL array");
-    GB_BAD((labels != nullptr) != (lpd != nullptr), "labels and lpd are given together or not at all");
-    GB_BAD(M > (INT64_MAX / 8 / 128) / K, "K M is too large");               // K M P and K M C doubles addressable (C <= 65)
-    const int64_t ntile = (M + SP_NB - 1) / SP_NB;
-    GB_BAD(ntile > 16777215 / K, "K ceil(M / 16) must be at most 2^24 - 1 (one tile of 16 rows per workgroup)");
+    pd_launch pl;                                                            // K M P and K M C doubles addressable (C <= 65)
+    if (int st = pd_plan(__func__, K, M, S, 128, !A || !X || !prob, labels, lpd, "labels and lpd are given together or not at all", &pl))
+        return st;
     const size_t nm = (size_t)K * M * 8, ns = (size_t)K * S * 8;
     if (int st = gb_check_overlaps(__func__, m, {{X, ns * D, "X", GB_RD}, {lw, ns, "lw", GB_RD}, {prob, nm * C, "prob", GB_WR},
                                                  {lpd, nm, "lpd", GB_WR}}))
@@ -269,11 +186,10 @@ int gsmvi_softmax_predict_batched_f64(gsmvi_ctx* ctx, void* stream, int64_t K, i
     sp_args a = {};
     a.K = K; a.M = M; a.C = C; a.P = P; a.D = D;
     a.S = (int)S;
-    a.ntile = (unsigned)ntile;
+    a.ntile = pl.ntile;
     a.A = A; a.labels = labels; a.counts = counts_dev; a.X = X; a.lw = lw; a.prob = prob; a.lpd = lpd;
     const size_t lds = (size_t)gsmvi_softmax_predict_lds_bytes(C, P);                  // <= 69 KB, reached at (65, 1)
-    const unsigned grid = (unsigned)(K * ntile);
-    hipLaunchKernelGGL(k_softmax_predict_batched, dim3(grid), dim3(256), lds, reinterpret_cast<hipStream_t>(stream), a);
+    hipLaunchKernelGGL(k_softmax_predict_batched, dim3(pl.grid), dim3(256), lds, reinterpret_cast<hipStream_t>(stream), a);
     return gb_launched(ctx, GSMVI_PATH_BATCHED_PREDICT | GSMVI_PATH_BATCHED_SOFTMAX, "k_softmax_predict_batched");
 }
 

@@ -685,6 +685,95 @@ def neg_hessian_negbin_batched(target, x, *, engine=None):
                                       log_size_prec=target.log_size_precision, want="h")
 
 
+def _as_tensor(a):
+    return a if isinstance(a, torch.Tensor) else torch.as_tensor(np.asarray(a))
+
+
+def _predict_draws_args(fn, target, mean, cov, A_new, keys, offset, y, check_y, counts, num_draws, call, psis, weights, engine):
+    """What ``predict_softmax_batched``, ``predict_negbin_batched`` and ``predict_ordinal_batched`` share before their launch,
+    after their own check of the target's type: the argument checks in the order of their docstrings (``check_y(y, live)`` is the
+    family's response check; every message carries ``fn``), then the draws and weights: a ``psis`` that is given is reused, else
+    ``psis_batched`` (``weights="psis"``) or one ``kl_draw_batched`` with its seed rule.  Returns a namespace: ``eng``; ``X``,
+    ``lw`` (None: uniform), ``A_new``, ``offset`` and ``counts_dev`` for the launch; ``y`` the checked responses on the host;
+    ``counts`` on the host; ``K``, ``M``, ``S``, ``nlaunch`` (this launch included) and ``psis``."""
+    from types import SimpleNamespace
+    from .diagnostics import MAX_DRAWS, MIN_DRAWS, _reusable, psis_batched
+    from .monitors import _to_numpy
+    if weights not in ("uniform", "psis"):
+        raise ValueError(f"{fn}: weights: expected 'uniform' or 'psis', got {weights!r}")
+    K, D, P = target.K, target.D, target.P
+    sa = _shape(A_new)
+    if len(sa) != 3 or min(sa) < 1 or sa[0] != K or sa[2] != P:
+        raise ValueError(f"{fn}: A_new: expected shape (K, M, P) with K = {K}, P = {P} and M >= 1, got {sa}")
+    M = sa[1]
+    if _shape(mean) != (K, D):
+        raise ValueError(f"{fn}: mean must be (K, D) = {(K, D)} of the target, got {_shape(mean)}")
+    if _shape(cov) != (K, D, D):
+        raise ValueError(f"{fn}: cov must be {(K, D, D)}, got {_shape(cov)}")
+    try:
+        cnt = _check_counts(counts, K, M, rows="M")
+        live = _live_rows(cnt, M)
+        yh = None
+        if y is not None:
+            if _shape(y) != (K, M):
+                raise ValueError(f"y: expected shape (K, M) = {(K, M)}, got {_shape(y)}")
+            yh = check_y(y, live)
+        oh = _check_offset(offset, K, M, live, rows="M")
+    except ValueError as e:
+        raise ValueError(f"{fn}: {e}") from None
+    keys_l = [int(k) for k in np.asarray(list(keys) if isinstance(keys, (list, tuple, range)) else _to_numpy(keys)).reshape(-1)]
+    if len(keys_l) != K:
+        raise ValueError(f"{fn}: {len(keys_l)} keys for K = {K} problems")
+    eng = engine if engine is not None else target.engine
+    if psis is None:
+        S = int(num_draws)
+        if S != num_draws or not MIN_DRAWS <= S <= MAX_DRAWS:
+            raise ValueError(f"{fn}: num_draws = {num_draws} is outside {MIN_DRAWS} <= num_draws <= {MAX_DRAWS}")
+        if weights == "psis":
+            psis = psis_batched(target.lp, mean, cov, keys_l, S, call=call, moments=False, as_torch=True, engine=eng)
+            nlaunch = psis.nlaunch + 1
+            X, _, lw = _reusable(psis, K, D, eng, fn)
+        else:
+            seeds = eng.batched_seeds(tuple((k % (2 ** 32)) ^ 0x5DEECE66D for k in keys_l))
+            X, _, _ = eng.kl_draw_batched(eng.asarray(mean), eng.asarray(cov), seeds, int(call), 0, S)
+            nlaunch, lw = 2, None
+    else:
+        X, _, lw = _reusable(psis, K, D, eng, fn)
+        S = _shape(X)[1]
+        nlaunch = 1
+        if weights == "uniform":
+            lw = None
+    return SimpleNamespace(eng=eng, X=X, lw=lw, A_new=eng.asarray(A_new.contiguous() if isinstance(A_new, torch.Tensor) else A_new),
+                           y=yh, offset=eng.asarray(oh) if oh is not None else None, counts=cnt,
+                           counts_dev=eng.batched_counts(cnt) if cnt is not None else None, K=K, M=M, S=S, nlaunch=nlaunch,
+                           psis=psis)
+
+
+def _predict_draws_result(result, a, out, lpd, as_torch, ints=()):
+    """The ``result`` dataclass of a draw-based predictive from the namespace ``a`` of ``_predict_draws_args``, the family's
+    outputs ``out`` and ``lpd``: ``elpd`` is the sum of ``lpd`` over the valid rows (None without ``lpd``); without ``as_torch``
+    everything goes to numpy, the fields named in ``ints`` as int64"""
+    elpd = None
+    if lpd is not None:
+        lt = _as_tensor(lpd)
+        nk = _as_tensor(a.counts).to(lt.device) if a.counts is not None else torch.full((a.K,), a.M, device=lt.device)
+        mask = torch.arange(a.M, device=lt.device)[None, :] < nk[:, None]
+        elpd = torch.where(mask, lt, torch.zeros((), dtype=lt.dtype, device=lt.device)).sum(1)
+    out = dict(out, lpd=lpd, elpd=elpd)
+    if not as_torch:
+        out = {n: None if t is None else np.asarray(a.eng.to_numpy(t)) for n, t in out.items()}
+        for n in ints:
+            out[n] = out[n].astype(np.int64)
+    return result(psis=a.psis, num_draws=a.S, nlaunch=a.nlaunch, **out)
+
+
+def _first_maximum(prob):
+    """``prob`` (K, M, C) as a tensor, the mask of its NaN rows, and ``label``: the first maximum of a row, -1 where it is NaN"""
+    pt = _as_tensor(prob)
+    dead = torch.isnan(pt).any(2)
+    return pt, dead, torch.where(dead, torch.full((), -1, dtype=torch.int64, device=pt.device), pt.argmax(2))
+
+
 @dataclass
 class NegBinPrediction:
     """What ``predict_negbin_batched`` returns for M new rows of each of K negative binomial problems under the fitted q_k =
@@ -733,76 +822,21 @@ def predict_negbin_batched(target, mean, cov, A_new, keys, offset=None, y=None, 
     are allowed, as in the target), bad ``counts``, keys of another length than K, ``num_draws`` outside 5..4096, an unknown
     ``weights`` or a ``psis`` that is not a ``PSISBatchedResult`` holding device tensors of the right shapes raise ValueError
     naming the argument before any device work."""
-    from .diagnostics import MAX_DRAWS, MIN_DRAWS, _reusable, psis_batched
-    from .monitors import _to_numpy
     fn = "predict_negbin_batched"
     if not isinstance(target, BatchedNegBinomialTarget):
         raise TypeError(f"{fn}: target must be a BatchedNegBinomialTarget, got {type(target).__name__}")
-    if weights not in ("uniform", "psis"):
-        raise ValueError(f"{fn}: weights: expected 'uniform' or 'psis', got {weights!r}")
-    K, D, P = target.K, target.D, target.P
-    sa = _shape(A_new)
-    if len(sa) != 3 or min(sa) < 1 or sa[0] != K or sa[2] != P:
-        raise ValueError(f"{fn}: A_new: expected shape (K, M, P) with K = {K}, P = {P} and M >= 1, got {sa}")
-    M = sa[1]
-    if _shape(mean) != (K, D):
-        raise ValueError(f"{fn}: mean must be (K, D) = {(K, D)} of the target, got {_shape(mean)}")
-    if _shape(cov) != (K, D, D):
-        raise ValueError(f"{fn}: cov must be {(K, D, D)}, got {_shape(cov)}")
-    try:
-        cnt = _check_counts(counts, K, M, rows="M")
-        live = _live_rows(cnt, M)
-        yh = None
-        if y is not None:
-            if _shape(y) != (K, M):
-                raise ValueError(f"y: expected shape (K, M) = {(K, M)}, got {_shape(y)}")
-            yh = _check_responses(y, "poisson", live, name_family=False)      # the count range: finite and >= 0
-        oh = _check_offset(offset, K, M, live, rows="M")
-    except ValueError as e:
-        raise ValueError(f"{fn}: {e}") from None
-    keys_l = [int(k) for k in np.asarray(list(keys) if isinstance(keys, (list, tuple, range)) else _to_numpy(keys)).reshape(-1)]
-    if len(keys_l) != K:
-        raise ValueError(f"{fn}: {len(keys_l)} keys for K = {K} problems")
-    eng = engine if engine is not None else target.engine
-    if psis is None:
-        S = int(num_draws)
-        if S != num_draws or not MIN_DRAWS <= S <= MAX_DRAWS:
-            raise ValueError(f"{fn}: num_draws = {num_draws} is outside {MIN_DRAWS} <= num_draws <= {MAX_DRAWS}")
-        if weights == "psis":
-            psis = psis_batched(target.lp, mean, cov, keys_l, S, call=call, moments=False, as_torch=True, engine=eng)
-            nlaunch = psis.nlaunch + 1
-            X, _, lw = _reusable(psis, K, D, eng, fn)
-        else:
-            seeds = eng.batched_seeds(tuple((k % (2 ** 32)) ^ 0x5DEECE66D for k in keys_l))
-            X, _, _ = eng.kl_draw_batched(eng.asarray(mean), eng.asarray(cov), seeds, int(call), 0, S)
-            nlaunch, lw = 2, None
-    else:
-        X, _, lw = _reusable(psis, K, D, eng, fn)
-        S = _shape(X)[1]
-        nlaunch = 1
-        if weights == "uniform":
-            lw = None
-    lmom, lpd = eng.negbin_predict_batched(X, lw, eng.asarray(A_new.contiguous() if isinstance(A_new, torch.Tensor) else A_new),
-                                           y=eng.asarray(yh) if yh is not None else None,
-                                           offset=eng.asarray(oh) if oh is not None else None,
-                                           counts=eng.batched_counts(cnt) if cnt is not None else None)
-    ten = lambda a: a if isinstance(a, torch.Tensor) else torch.as_tensor(np.asarray(a))      # noqa: E731
-    lm = ten(lmom)
+    count_range = lambda y, live: _check_responses(y, "poisson", live, name_family=False)      # noqa: E731  (finite and >= 0)
+    a = _predict_draws_args(fn, target, mean, cov, A_new, keys, offset, y, count_range, counts, num_draws, call, psis, weights, engine)
+    eng = a.eng
+    lmom, lpd = eng.negbin_predict_batched(a.X, a.lw, a.A_new, y=eng.asarray(a.y) if a.y is not None else None, offset=a.offset,
+                                           counts=a.counts_dev)
+    lm = _as_tensor(lmom)
     m1 = torch.exp(lm[..., 0])
     # E[mu + mu^2 / r] + Var[mu]; the variance of mu as e^lmom1 (1 - e^(2 lmom0 - lmom1)): one exponential of a difference <= 0
     # (where it rounds to no spread at all the term is 0, not inf x 0)
     spread = -torch.expm1(2.0 * lm[..., 0] - lm[..., 1])
     var = m1 + torch.exp(lm[..., 2]) + torch.where(spread > 0.0, torch.exp(lm[..., 1]) * spread, torch.zeros_like(spread))
-    elpd = None
-    if lpd is not None:
-        lt = ten(lpd)
-        nk = ten(cnt).to(lt.device) if cnt is not None else torch.full((K,), M, device=lt.device)
-        mask = torch.arange(M, device=lt.device)[None, :] < nk[:, None]
-        elpd = torch.where(mask, lt, torch.zeros((), dtype=lt.dtype, device=lt.device)).sum(1)
-    out = dict(mean=m1, var=var, log_moments=lmom, lpd=lpd, elpd=elpd)
-    if not as_torch:
-        out = {n: None if t is None else np.asarray(eng.to_numpy(t)) for n, t in out.items()}
-    return NegBinPrediction(psis=psis, num_draws=S, nlaunch=nlaunch, **out)
+    return _predict_draws_result(NegBinPrediction, a, dict(mean=m1, var=var, log_moments=lmom), lpd, as_torch)
 
 
 def _check_labels(y, C, live):
@@ -1065,70 +1099,17 @@ def predict_softmax_batched(target, mean, cov, A_new, keys, y=None, counts=None,
     0 .. C - 1 in the valid rows, bad ``counts``, keys of another length than K, ``num_draws`` outside 5..4096, an unknown
     ``weights`` or a ``psis`` that is not a ``PSISBatchedResult`` holding device tensors of the right shapes raise ValueError
     naming the argument before any device work."""
-    from .diagnostics import MAX_DRAWS, MIN_DRAWS, _reusable, psis_batched
-    from .monitors import _to_numpy
     fn = "predict_softmax_batched"
     if not isinstance(target, BatchedSoftmaxTarget):
         raise TypeError(f"{fn}: target must be a BatchedSoftmaxTarget, got {type(target).__name__}")
-    if weights not in ("uniform", "psis"):
-        raise ValueError(f"{fn}: weights: expected 'uniform' or 'psis', got {weights!r}")
-    K, D, P, C = target.K, target.D, target.P, target.C
-    sa = _shape(A_new)
-    if len(sa) != 3 or min(sa) < 1 or sa[0] != K or sa[2] != P:
-        raise ValueError(f"{fn}: A_new: expected shape (K, M, P) with K = {K}, P = {P} and M >= 1, got {sa}")
-    M = sa[1]
-    if _shape(mean) != (K, D):
-        raise ValueError(f"{fn}: mean must be (K, D) = {(K, D)} of the target, got {_shape(mean)}")
-    if _shape(cov) != (K, D, D):
-        raise ValueError(f"{fn}: cov must be {(K, D, D)}, got {_shape(cov)}")
-    try:
-        cnt = _check_counts(counts, K, M, rows="M")
-        yh = None
-        if y is not None:
-            if _shape(y) != (K, M):
-                raise ValueError(f"y: expected shape (K, M) = {(K, M)}, got {_shape(y)}")
-            yh = _check_labels(y, C, _live_rows(cnt, M))
-    except ValueError as e:
-        raise ValueError(f"{fn}: {e}") from None
-    keys_l = [int(k) for k in np.asarray(list(keys) if isinstance(keys, (list, tuple, range)) else _to_numpy(keys)).reshape(-1)]
-    if len(keys_l) != K:
-        raise ValueError(f"{fn}: {len(keys_l)} keys for K = {K} problems")
-    eng = engine if engine is not None else target.engine
-    if psis is None:
-        S = int(num_draws)
-        if S != num_draws or not MIN_DRAWS <= S <= MAX_DRAWS:
-            raise ValueError(f"{fn}: num_draws = {num_draws} is outside {MIN_DRAWS} <= num_draws <= {MAX_DRAWS}")
-        if weights == "psis":
-            psis = psis_batched(target.lp, mean, cov, keys_l, S, call=call, moments=False, as_torch=True, engine=eng)
-            nlaunch = psis.nlaunch + 1
-            X, _, lw = _reusable(psis, K, D, eng, fn)
-        else:
-            seeds = eng.batched_seeds(tuple((k % (2 ** 32)) ^ 0x5DEECE66D for k in keys_l))
-            X, _, _ = eng.kl_draw_batched(eng.asarray(mean), eng.asarray(cov), seeds, int(call), 0, S)
-            nlaunch, lw = 2, None
-    else:
-        X, _, lw = _reusable(psis, K, D, eng, fn)
-        S = _shape(X)[1]
-        nlaunch = 1
-        if weights == "uniform":
-            lw = None
-    prob, lpd = eng.softmax_predict_batched(X, lw, eng.asarray(A_new.contiguous() if isinstance(A_new, torch.Tensor) else A_new), C,
-                                            labels=eng.batched_labels(yh) if yh is not None else None,
-                                            counts=eng.batched_counts(cnt) if cnt is not None else None)
-    ten = lambda a: a if isinstance(a, torch.Tensor) else torch.as_tensor(np.asarray(a))      # noqa: E731
-    pt = ten(prob)
-    label = torch.where(torch.isnan(pt).any(2), torch.full((), -1, dtype=torch.int64, device=pt.device), pt.argmax(2))
-    elpd = None
-    if lpd is not None:
-        lt = ten(lpd)
-        nk = ten(cnt).to(lt.device) if cnt is not None else torch.full((K,), M, device=lt.device)
-        mask = torch.arange(M, device=lt.device)[None, :] < nk[:, None]
-        elpd = torch.where(mask, lt, torch.zeros((), dtype=lt.dtype, device=lt.device)).sum(1)
-    out = dict(prob=prob, label=label, lpd=lpd, elpd=elpd)
-    if not as_torch:
-        out = {n: None if t is None else np.asarray(eng.to_numpy(t)) for n, t in out.items()}
-        out["label"] = out["label"].astype(np.int64)
-    return SoftmaxPrediction(psis=psis, num_draws=S, nlaunch=nlaunch, **out)
+    C = target.C
+    a = _predict_draws_args(fn, target, mean, cov, A_new, keys, None, y, lambda y, live: _check_labels(y, C, live), counts, num_draws,
+                            call, psis, weights, engine)
+    eng = a.eng
+    prob, lpd = eng.softmax_predict_batched(a.X, a.lw, a.A_new, C, labels=eng.batched_labels(a.y) if a.y is not None else None,
+                                            counts=a.counts_dev)
+    _, _, label = _first_maximum(prob)
+    return _predict_draws_result(SoftmaxPrediction, a, dict(prob=prob, label=label), lpd, as_torch, ints=("label",))
 
 
 @dataclass
@@ -1179,76 +1160,18 @@ def predict_ordinal_batched(target, mean, cov, A_new, keys, offset=None, y=None,
     ``counts``, keys of another length than K, ``num_draws`` outside 5..4096, an unknown ``weights`` or a ``psis`` that is not a
     ``PSISBatchedResult`` holding device tensors of the right shapes raise ValueError naming the argument before any device
     work."""
-    from .diagnostics import MAX_DRAWS, MIN_DRAWS, _reusable, psis_batched
-    from .monitors import _to_numpy
     fn = "predict_ordinal_batched"
     if not isinstance(target, BatchedOrdinalTarget):
         raise TypeError(f"{fn}: target must be a BatchedOrdinalTarget, got {type(target).__name__}")
-    if weights not in ("uniform", "psis"):
-        raise ValueError(f"{fn}: weights: expected 'uniform' or 'psis', got {weights!r}")
-    K, D, P, C = target.K, target.D, target.P, target.C
-    sa = _shape(A_new)
-    if len(sa) != 3 or min(sa) < 1 or sa[0] != K or sa[2] != P:
-        raise ValueError(f"{fn}: A_new: expected shape (K, M, P) with K = {K}, P = {P} and M >= 1, got {sa}")
-    M = sa[1]
-    if _shape(mean) != (K, D):
-        raise ValueError(f"{fn}: mean must be (K, D) = {(K, D)} of the target, got {_shape(mean)}")
-    if _shape(cov) != (K, D, D):
-        raise ValueError(f"{fn}: cov must be {(K, D, D)}, got {_shape(cov)}")
-    try:
-        cnt = _check_counts(counts, K, M, rows="M")
-        live = _live_rows(cnt, M)
-        yh = None
-        if y is not None:
-            if _shape(y) != (K, M):
-                raise ValueError(f"y: expected shape (K, M) = {(K, M)}, got {_shape(y)}")
-            yh = _check_labels(y, C, live)
-        oh = _check_offset(offset, K, M, live, rows="M")
-    except ValueError as e:
-        raise ValueError(f"{fn}: {e}") from None
-    keys_l = [int(k) for k in np.asarray(list(keys) if isinstance(keys, (list, tuple, range)) else _to_numpy(keys)).reshape(-1)]
-    if len(keys_l) != K:
-        raise ValueError(f"{fn}: {len(keys_l)} keys for K = {K} problems")
-    eng = engine if engine is not None else target.engine
-    if psis is None:
-        S = int(num_draws)
-        if S != num_draws or not MIN_DRAWS <= S <= MAX_DRAWS:
-            raise ValueError(f"{fn}: num_draws = {num_draws} is outside {MIN_DRAWS} <= num_draws <= {MAX_DRAWS}")
-        if weights == "psis":
-            psis = psis_batched(target.lp, mean, cov, keys_l, S, call=call, moments=False, as_torch=True, engine=eng)
-            nlaunch = psis.nlaunch + 1
-            X, _, lw = _reusable(psis, K, D, eng, fn)
-        else:
-            seeds = eng.batched_seeds(tuple((k % (2 ** 32)) ^ 0x5DEECE66D for k in keys_l))
-            X, _, _ = eng.kl_draw_batched(eng.asarray(mean), eng.asarray(cov), seeds, int(call), 0, S)
-            nlaunch, lw = 2, None
-    else:
-        X, _, lw = _reusable(psis, K, D, eng, fn)
-        S = _shape(X)[1]
-        nlaunch = 1
-        if weights == "uniform":
-            lw = None
-    prob, lpd = eng.ordinal_predict_batched(X, lw, eng.asarray(A_new.contiguous() if isinstance(A_new, torch.Tensor) else A_new), C,
-                                            y=eng.batched_labels(yh) if yh is not None else None,
-                                            offset=eng.asarray(oh) if oh is not None else None,
-                                            counts=eng.batched_counts(cnt) if cnt is not None else None)
-    ten = lambda a: a if isinstance(a, torch.Tensor) else torch.as_tensor(np.asarray(a))      # noqa: E731
-    pt = ten(prob)
-    dead = torch.isnan(pt).any(2)
-    none = torch.full((), -1, dtype=torch.int64, device=pt.device)
-    label = torch.where(dead, none, pt.argmax(2))
+    C = target.C
+    a = _predict_draws_args(fn, target, mean, cov, A_new, keys, offset, y, lambda y, live: _check_labels(y, C, live), counts,
+                            num_draws, call, psis, weights, engine)
+    eng = a.eng
+    prob, lpd = eng.ordinal_predict_batched(a.X, a.lw, a.A_new, C, y=eng.batched_labels(a.y) if a.y is not None else None,
+                                            offset=a.offset, counts=a.counts_dev)
+    pt, dead, label = _first_maximum(prob)
     # the smallest c whose cumulative probability reaches 0.5: the classes before it; C - 1 at the most (a cumulative sum that
     # rounds below 0.5 everywhere cannot happen for a row that sums to 1, the clamp costs nothing)
-    median = torch.where(dead, none, (torch.cumsum(pt, 2) < 0.5).sum(2).clamp(max=C - 1))
-    elpd = None
-    if lpd is not None:
-        lt = ten(lpd)
-        nk = ten(cnt).to(lt.device) if cnt is not None else torch.full((K,), M, device=lt.device)
-        mask = torch.arange(M, device=lt.device)[None, :] < nk[:, None]
-        elpd = torch.where(mask, lt, torch.zeros((), dtype=lt.dtype, device=lt.device)).sum(1)
-    out = dict(prob=prob, label=label, median=median, lpd=lpd, elpd=elpd)
-    if not as_torch:
-        out = {n: None if t is None else np.asarray(eng.to_numpy(t)) for n, t in out.items()}
-        out["label"] = out["label"].astype(np.int64)
-        out["median"] = out["median"].astype(np.int64)
-    return OrdinalPrediction(psis=psis, num_draws=S, nlaunch=nlaunch, **out)
+    median = torch.where(dead, label.new_full((), -1), (torch.cumsum(pt, 2) < 0.5).sum(2).clamp(max=C - 1))
+    return _predict_draws_result(OrdinalPrediction, a, dict(prob=prob, label=label, median=median), lpd, as_torch,
+                                 ints=("label", "median"))

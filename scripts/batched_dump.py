@@ -4,7 +4,10 @@ fit and a fit with one NaN target, for both methods -- 48 arrays of results; and
 logistic entry, Hessian and inverse, six Newton rounds, the predictive, three L-BFGS rounds, the leave-one-out) at K = 13 for the
 four families with and without an offset, at (D, N, rows of X) shapes on both sides of every packing and tile boundary; and the
 softmax entry points (score and density in the three ``want``s, Hessian and inverse, six Newton rounds, the leave-one-out, the
-predictive) at K = 13, at (C, P, N, rows of X, S) shapes on both sides of theirs; and the KL monitor's draw (one call and two
+predictive, also with a NaN and with nothing but -inf among one problem's weights and a NaN in one draw) at K = 13, at
+(C, P, N, rows of X, S) shapes on both sides of theirs; and the negative binomial and ordinal draw-based predictives at K = 4, at
+(P, S, M) and (P, C, S, M) shapes on both sides of every tile boundary, with uniform and given weights, with and without y and
+an offset, counts of 0, inside a tile and M, and the same verdict inputs; and the KL monitor's draw (one call and two
 chunks) and log-density, Pathfinder's propose and select over five L-BFGS rounds, and one ADVI start and step, at K = 13 and
 six D, with the fewest rows and one more than a tile; and the Hessian with its inverse and six Newton rounds from x0 = 0 of the
 shared-design, negative binomial and ordinal Laplace entries at K = 13, at the smallest sizes where their mapping changes, with the
@@ -244,6 +247,62 @@ def dump_softmax(out, K=13):
             out[f"softmax_predict_{wname}_{tag}"] = host(prob)
             out[f"softmax_predict_{wname}_labels_{tag}"] = host(*eng.softmax_predict_batched(Xd, w, A, C, labels=y,
                                                                                              counts=model["counts"]))
+        # the verdict paths: a NaN among problem 3's weights, nothing but -inf for problem 4 (softmax has no draw flag: the NaN
+        # in one draw of problem 5 refuses the rows it reaches)
+        Xv, lwv = eng.to_numpy(Xd).copy(), eng.to_numpy(lw).copy()
+        Xv[5, S // 2, D - 1] = lwv[3, S - 1] = np.nan
+        lwv[4] = -np.inf
+        out[f"softmax_predict_verdict_{tag}"] = host(*eng.softmax_predict_batched(eng.asarray(Xv), eng.asarray(lwv), A, C, labels=y,
+                                                                                  counts=model["counts"]))
+
+
+# the draw-based predictives of the negative binomial and ordinal families, K = 4.  S: the fewest draws, one below, one above and
+# exactly a tile of 64, four tiles and one draw; M: one row, one below, one above and exactly a tile of 16 rows, two tiles and one
+# row; P: one column, P % 4 != 0, a multiple of 4, the largest; C: the fewest classes (no interior class), one and two interior
+# classes, the most classes
+NEGBIN_PREDICT_SHAPES = ((1, 5, 1), (3, 63, 15), (5, 257, 33), (4, 64, 16), (63, 65, 17))                         # (P, S, M)
+ORDINAL_PREDICT_SHAPES = ((1, 2, 5, 1), (3, 3, 63, 15), (5, 4, 257, 33), (3, 2, 65, 17), (1, 64, 63, 17), (63, 2, 65, 33))  # (P, C, S, M)
+
+
+def dump_draw_predict(out, K=4):
+    """the negative binomial and ordinal predictives at every shape above: uniform and given lw, with and without y, with and
+    without an offset; counts 0 for problem 0, a value that ends inside a tile for problem 1, M for problems 2 and 3.  Then, with
+    everything given, the verdict inputs: a NaN in one draw of problem 2 and nothing but -inf among the weights of problem 3"""
+    from gsmvi_amd.engine import get_engine
+    eng = get_engine()
+    host = lambda *ts: np.concatenate([eng.to_numpy(t).astype(np.float64).reshape(K, -1) for t in ts if t is not None], 1)     # noqa: E731
+
+    def runs(tag, launch, rs, S, M, D, Xh, yd, od):
+        cnt = eng.batched_counts(np.array([0, max(1, M - 5), M, M]))
+        logr = eng.asarray(rs.standard_normal((K, S)))
+        lw = eng.psis_weights_batched(logr)[0]
+        X = eng.asarray(Xh)
+        for wname, w in (("uniform", None), ("weighted", lw)):
+            for yname, yv in (("noy", None), ("y", yd)):
+                for oname, ov in (("nooff", None), ("off", od)):
+                    out[f"{tag}_{wname}_{yname}_{oname}"] = host(*launch(X, w, yv, ov, cnt))
+        Xv, lwv = Xh.copy(), eng.to_numpy(lw).copy()
+        Xv[2, S // 2, D - 1] = np.nan
+        lwv[3] = -np.inf
+        out[f"{tag}_verdict"] = host(*launch(eng.asarray(Xv), eng.asarray(lwv), yd, od, cnt))
+        Xv[2, S // 2, D - 1], Xv[2, S - 1, 0] = Xh[2, S // 2, D - 1], np.inf              # a beta column instead
+        out[f"{tag}_verdict_beta"] = host(*launch(eng.asarray(Xv), eng.asarray(lwv), yd, od, cnt))
+
+    for P, S, M in NEGBIN_PREDICT_SHAPES:
+        rs = np.random.RandomState(100000 * P + 100 * S + M)
+        A = eng.asarray(rs.standard_normal((K, M, P)) / np.sqrt(P))
+        Xh = np.concatenate([0.5 * rs.standard_normal((K, S, P)), 1.0 + 0.3 * rs.standard_normal((K, S, 1))], 2)
+        y, o = eng.asarray(rs.poisson(3.0, (K, M)).astype(np.float64)), eng.asarray(0.3 * rs.standard_normal((K, M)))
+        runs(f"negbin_predict_P{P}_S{S}_M{M}", lambda X, w, yv, ov, cnt: eng.negbin_predict_batched(X, w, A, y=yv, offset=ov, counts=cnt),
+             rs, S, M, P + 1, Xh, y, o)
+    for P, C, S, M in ORDINAL_PREDICT_SHAPES:
+        rs = np.random.RandomState(1000000 * P + 10000 * C + 100 * S + M)
+        A = eng.asarray(rs.standard_normal((K, M, P)) / np.sqrt(P))
+        Xh = np.concatenate([0.5 * rs.standard_normal((K, S, P)), -1.0 + 0.3 * rs.standard_normal((K, S, 1)),
+                             -0.5 + 0.3 * rs.standard_normal((K, S, C - 2))], 2)
+        y, o = eng.batched_labels(rs.randint(0, C, (K, M))), eng.asarray(0.3 * rs.standard_normal((K, M)))
+        runs(f"ordinal_predict_P{P}_C{C}_S{S}_M{M}",
+             lambda X, w, yv, ov, cnt: eng.ordinal_predict_batched(X, w, A, C, y=yv, offset=ov, counts=cnt), rs, S, M, P + C - 1, Xh, y, o)
 
 
 def dump_initialisers(out, K=13):
@@ -310,10 +369,9 @@ def dump(path):
     import gsmvi_amd
     K = 13
     out = {}
-    dump_glm(out, K)
-    dump_softmax(out, K)
-    dump_initialisers(out, K)
-    dump_laplace_families(out, K)
+    for part, k in ((dump_glm, K), (dump_softmax, K), (dump_draw_predict, 4), (dump_initialisers, K), (dump_laplace_families, K)):
+        part(out, k)
+        print(f"{part.__name__}: {len(out)} arrays so far", flush=True)
     for D, B in SHAPES:
         rs = np.random.RandomState(100 * D + B)
         A = rs.standard_normal((K, D, D))
